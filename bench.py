@@ -11,7 +11,12 @@ i.e. a batch of 64 x 1024 transitions per GPU, so that even `--steps 20` times a
 `value` = whole-job env-steps/s; learner updates/s is reported next to it.  All inputs (frame ring,
 sum-tree, networks) are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = one timed step).  `--full` adds everything else the benchmark
+measures: per-kernel probes inside the timed loop and the roofline, subfigures and role timings, the PER micro-benchmark, the CPU baseline and, at N > 1,
+the single-GPU strong-scaling reference.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (same arguments, same inputs).
+
     python bench.py --gpus 1 --steps 20 --warmup 2
+    python bench.py --gpus 1 --steps 20 --warmup 2 --full --dump-outputs out/
     python bench.py --gpus 8                       # no launcher: spawns the 8 ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -71,7 +76,19 @@ def parse_args():
                     help="replay (N >= 3): the reference's enable_mp_memory topology on the device path -- rank 0 learner, rank 1 replay GPU, ranks 2.. actors "
                          "(device/replay_role.py; srl/base/run/play_mp_memory.py:595-621)")
     ap.add_argument("--no-strong-ref", action="store_true", help="N>1: skip the single-GPU engine at the job's total environment count that rank 0 times after the distributed region")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel probes in the timed loop and the roofline, actor-only / learner-only "
+                         "subfigures and role timings, the PER micro-benchmark, the CPU baseline and (N>1) the single-GPU strong-scaling reference; "
+                         "the --no-* switches above then turn single pieces off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed seeded sample of "
+                         "arrays above 2^20 elements); Rainbow line only")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.algo != "rainbow" or args.topology != "default" or args.roles_only):
+        ap.error("--dump-outputs covers the Rainbow line (--algo rainbow, --topology default)")
+    return args
 
 
 def self_launch(args):
@@ -230,12 +247,13 @@ def main():
 
     # HIP events around the actors' network pass (the dominant kernel group) and, inside it, around the two launches of the
     # dominant single kernel (conv2 + conv3), all on the stream they are launched on; every 4th lock-step is probed
+    # (--full only: a plain run times the lock-steps and nothing else)
     n_lock = args.steps * inner
     probe_every = 4
     n_probe = (n_lock + probe_every - 1) // probe_every
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)] if args.full else []
     local = getattr(eng, "local", eng)
-    probing = bool(local.mfma) and getattr(eng, "acts", True)
+    probing = args.full and bool(local.mfma) and getattr(eng, "acts", True)
     pr = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)] if probing else []
     pf = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_probe)] if probing else []
     for a_, b_ in pr + pf:  # torch creates the underlying hipEvent_t at the first record
@@ -252,7 +270,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(n_lock):
-        if k % probe_every == 0:
+        if ev and k % probe_every == 0:
             if probing:
                 local.inf_actor.set_probe(*pr[k // probe_every])
                 local.inf_actor.set_probe_fc1(*pf[k // probe_every])
@@ -275,16 +293,16 @@ def main():
         v = sorted(a_.elapsed_time(b_) for a_, b_ in events)
         return {"min_ms": v[0], "median_ms": v[len(v) // 2], "mean_ms": sum(v) / len(v), "max_ms": v[-1], "probes": len(v)}
 
-    ev_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / len(ev)
+    ev_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / len(ev) if ev else 0.0
     conv_ms = sum(a_.elapsed_time(b_) for a_, b_ in pr) / len(pr) if probing else 0.0
     fc1_ms = sum(a_.elapsed_time(b_) for a_, b_ in pf) / len(pf) if probing else 0.0
-    probe_stats = {"pass": stats(ev), "conv": stats(pr) if probing else None, "fc1": stats(pf) if probing else None}
+    probe_stats = {"pass": stats(ev), "conv": stats(pr) if probing else None, "fc1": stats(pf) if probing else None} if ev else None
     if spans is not None:
         sp = spans.cpu()
         v = sorted(float(b_ - a_) * 1e-5 for a_, b_ in sp.tolist() if a_ != -1 and b_ > a_)  # 100 MHz ticks -> ms
         if v:
             probe_stats["fc1_kernel_span"] = {"min_ms": v[0], "median_ms": v[len(v) // 2], "mean_ms": sum(v) / len(v), "max_ms": v[-1], "probes": len(v)}
-    if dist is not None:  # a learner-only rank 0 runs no actor pass: report the slowest actor rank's
+    if dist is not None and args.full:  # a learner-only rank 0 runs no actor pass: report the slowest actor rank's
         t = torch.tensor([ev_ms, conv_ms, fc1_ms], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ev_ms, conv_ms, fc1_ms = float(t[0].item()), float(t[1].item()), float(t[2].item())
@@ -293,7 +311,7 @@ def main():
     # N > 1: the SAME number of environments on ONE GPU (rank 0, after the distributed region), so that the line carries its own strong-scaling ratio:
     # value / strong_ref.value = what spreading E_total environments over the actor GPUs bought (north_star: >= 6x at 8 GPUs)
     strong_ref = None
-    if dist is not None and world > 1 and not args.no_strong_ref:
+    if dist is not None and world > 1 and args.full and not args.no_strong_ref:
         if rank == 0:
             try:
                 # in a process of its own (one process per GPU is how the N = 1 line is measured too; and what a process's earlier streams do to a later
@@ -330,6 +348,8 @@ def main():
     env_steps = n_lock * envs_per_gpu * actor_ranks
     updates = n_lock * args.updates
     info = eng.info()
+    if args.dump_outputs is not None:  # before anything below steps the engine again
+        dump_outputs(args.dump_outputs, rainbow_outputs(eng))
     out = {
         "metric": "env-steps/sec + learner updates/sec, Rainbow 84x84x4",
         "value": env_steps / elapsed,
@@ -372,21 +392,21 @@ def main():
                          else f"{world} GPUs: rank0 learner + replay, {world - 1} actor ranks (BASELINE.json configs[3] topology), grouped send/recv push + flat broadcast"),
             "actor_gpus": actor_ranks,
         },
-        "roofline": roofline(eng, ev_ms, conv_ms, fc1_ms, probe_stats),
+        "roofline": roofline(eng, ev_ms, conv_ms, fc1_ms, probe_stats) if args.full else None,
         "final": {"loss": info["loss"], "train_count": info["train_count"], "memory": info["memory"]},
     }
     if strong_ref is not None:
         out["strong_ref"] = strong_ref
         if "value" in strong_ref:
             out["strong_ratio"] = out["value"] / strong_ref["value"]
-    if dist is None and not args.no_subfigures:
+    if dist is None and args.full and not args.no_subfigures:
         out["subfigures"] = subfigures(eng, args, inner)
         eng.close()  # (the engine took the thread to its actors' low-priority stream: hand it back before other engines are built and timed)
         if args.algo == "rainbow" and not args.noisy and args.envs >= 512 and args.envs % 128 == 0 and os.environ.get("SRLX_NO_ROLES", "0") != "1":
             out["subfigures"]["roles"] = roles_in_own_process(args, dev_index)
-    if not args.no_per_micro:
+    if args.full and not args.no_per_micro:
         out["per_micro"] = per_micro(eng)
-    if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other runs would only repeat it
+    if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other runs would only repeat it
         out["cpu_baseline"] = cpu_baseline(args, cfg)
     if dist is not None:
         dist.destroy_process_group()
@@ -502,7 +522,7 @@ def bench_agent57_light(args, dev_index, rank, world, dist=None, envs_per_gpu=No
     _loc = eng.local if dist is not None else eng
     multi = bool(getattr(_loc, "multi_trunk", False) and _loc.sets and _loc.intrinsic)  # the five image blocks as ONE launch (the probe brackets the first handle's)
     probe_handle = _loc.nets["emb" if multi else "q_ext"].actor  # (None on a rank that only learns)
-    if probe_handle is not None:
+    if probe_handle is not None and args.full:
         pr = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range((n_lock + probe_every - 1) // probe_every)]
         for a_, b_ in pr:
             a_.record()
@@ -551,7 +571,7 @@ def bench_agent57_light(args, dev_index, rank, world, dist=None, envs_per_gpu=No
                         "Rainbow policy pass (profiles/r6_pmc_traffic.json: the kernel and its launch geometry are identical)"}
     info = eng.info()
     cpu = None
-    if dist is None and rank == 0 and not args.no_cpu_baseline:
+    if dist is None and rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_agent57(args, rl, E)
     out = {
         "metric": "env-steps/sec + learner updates/sec, Agent57_light 84x84x4", "value": n_lock * E * actor_ranks / elapsed, "unit": "env-steps/s", "n_gpus": world,
@@ -635,7 +655,8 @@ def bench_ppo(args, dev_index, rank, world, dist):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     updates = args.steps * cfg.epochs * cfg.minibatches
     info = eng.info()
-    if eng.fused:
+    roofline = None  # (--full only: the dominant kernel timed in launches of its own)
+    if args.full and eng.fused:
         # the dominant kernel: one minibatch's forward + loss + backward (k_ppo_minibatch, + the 6 us gradient reduction the same C call launches), timed live on
         # the engine's own buffers with HIP events on the launch stream
         n, mb = T * E, T * E // cfg.minibatches
@@ -667,7 +688,7 @@ def bench_ppo(args, dev_index, rank, world, dist):
                             "per 64-sample tile the kernel measures ~3.2 k clocks per 32-MFMA product against the pipe's 2.0 k, plus ~20 k clocks of vector phases "
                             "(first layer, heads, loss, head gradients) and barriers per 30 k of MFMA; rocprofv3 cross-check: profiles/r6_ppo_kernel_stats.csv; HBM "
                             "traffic is the gathered samples (~50 B each) and the 13 MB of per-workgroup partial gradients: far from the bound"}
-    else:
+    elif args.full:
         # the GAE scan in isolation: 16 B read + 8 B written per (environment, step)
         r, v, d, lv, adv = (torch.rand(T, E, device=dev), torch.rand(T, E, device=dev), (torch.rand(T, E, device=dev) < 0.01).to(torch.uint8), torch.rand(E, device=dev),
                             torch.zeros(T, E, device=dev))
@@ -701,9 +722,50 @@ def bench_ppo(args, dev_index, rank, world, dist):
         "roofline": roofline,
         "final": {k: info.get(k) for k in ("policy_loss", "value_loss", "entropy_loss")},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_ppo(args, cfg)
     _emit(out)
+
+
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: a larger array is written as this many elements at fixed, seeded positions
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def rainbow_outputs(eng):
+    """What the last timed lock-step computed, as a caller of the engine receives it: the actors' actions and the environments' step (rewards, episode ends,
+    next frames), the learner's last update (loss, TD targets, new priorities) and the online network's parameters after it."""
+    import torch
+
+    local = getattr(eng, "local", eng)
+    out = {}
+    if getattr(eng, "acts", True) and local.role != "learner":
+        out["actions"] = local.actions
+        for name in ("rewards", "terminated", "done", "next_obs"):
+            if hasattr(local.env, name):
+                out[name] = getattr(local.env, name)
+    if local.role != "actor":
+        out.update(loss=local.loss, td_target=local.target, priorities=local.priorities)
+        out.update({"q_online." + k: v for k, v in local.q_online.state_dict().items()})
+    torch.cuda.synchronize()
+    return {k: (v.detach().float() if v.dtype in (torch.float16, torch.bfloat16) else v.detach()).cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array as path/<name>.npy -- floating point as float32 / float64, integers and flags as float64 (exact) -- and arrays above
+    DUMP_SAMPLE elements as the same DUMP_SAMPLE flat positions in every run (a generator seeded with 0), so that two builds compare output for output."""
+    import numpy as np
+
+    ready = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        ready[name] = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+    total = sum(a.nbytes for a in ready.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in ready.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def subfigures(eng, args, inner):

@@ -153,7 +153,7 @@ def test_bench_multi_rank_rehearsal(n, actor_gpus, launcher):
 
     steps, warmup, inner = 3, 1, 4
     bench = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--backend", "gloo", "--steps", str(steps), "--warmup", str(warmup), "--inner", str(inner),
-             "--envs", "128", "--capacity", "100000", "--batch-size", "16", "--no-per-micro"]
+             "--envs", "128", "--capacity", "100000", "--batch-size", "16", "--full", "--no-per-micro"]
     if launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port",
                str(_free_port())] + bench

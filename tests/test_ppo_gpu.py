@@ -227,7 +227,7 @@ def test_bench_ppo_line():
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     for extra, n in ((["--gpus", "1"], 1), (["--gpus", "2", "--backend", "gloo"], 2)):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--algo", "ppo", "--envs", "256", "--steps", "3", "--warmup", "2"] + extra, cwd=root,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--algo", "ppo", "--envs", "256", "--steps", "3", "--warmup", "2", "--full"] + extra, cwd=root,
                            capture_output=True, text=True, timeout=900, env=env)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
