@@ -543,9 +543,16 @@ int srlx_store_gather_obs(srlx_store_t *h, int64_t batch, int k_begin, int k_cou
  * dense layer (three of the four products, the cross terms in a 2^11-scaled accumulator; the dropped one is below 2^-24 |a b|).  BACKWARD GEMMs: three bf16
  * parts per operand on v_mfma_f32_32x32x16_bf16, six of the nine products (gradients live below float16's normal range).  Q-values agree with the
  * all-float32 pipe to float32 round-off (3e-7 of max |Q| against float64 for either; the tolerance promised against the reference is 1e-5).  The float16
- * split holds activations up to 65 504: srlx_qnet_range_flags reports a pass that met a larger one.  Environment switches (read once per process):
- * SRLX_CONV_BF16X3=1 (convolutions on three bf16 parts, float32's range), SRLX_CONV1_F32=1 (all convolutions) / SRLX_CONV23_F32=1 / SRLX_FC1_F32=1
- * keep them on the float32 pipe.
+ * split holds activations up to 65 504: srlx_qnet_range_flags reports a pass that met a larger one.
+ *
+ * Environment switches: A/B arms of the numeric paths, each on when its variable starts with '1'.  Read once per process, when a Q-network first needs one.
+ *   SRLX_CONV_BF16X3    the fused convolution kernel's products on three bf16 parts (six of the nine products; rounds 3-5), whose range is
+ *                       float32's, instead of two float16 parts
+ *   SRLX_CONV1_F32      every convolution on the float32 matrix pipe
+ *   SRLX_CONV23_F32     conv2 / conv3 on the float32 matrix pipe; conv1 then runs on three bf16 parts (implies SRLX_CONV_BF16X3)
+ *   SRLX_FC1_F32        the first dense layer on the float32 matrix pipe
+ *   SRLX_NO_FUSED_CONV  the three-launch convolution path instead of the fused kernel (the Python engines read it too: they must agree)
+ *   SRLX_NO_CONV_PLANES the fused kernel writes float32 activations, and a split pass makes the first dense layer's operand planes
  *
  * Replaces the no-grad forwards of the reference's torch modules -- DQNImageBlock
  * (srl/rl/torch_/blocks/dqn_image_block.py:10-67) + DuelingNetworkBlock
@@ -669,16 +676,13 @@ int srlx_qnet_set_fc1_span(srlx_qnet_t *h, uint64_t *d_span);
 int srlx_qnet_enable_fc1_planes(srlx_qnet_t *h);
 int srlx_qnet_refresh_fc1_planes(srlx_qnet_t *h, const float *d_src_wf, float *d_copy_dst, void *stream);
 int srlx_qnet_invalidate_fc1_planes(srlx_qnet_t *h);
-/* the weight-gradient branch of srlx_qnet_backward_u8 runs on a stream of the handle's own; a caller that confines the learner to a set
- * of CUs (hipExtStreamCreateWithCUMask) hands in a stream carrying that mask instead (caller-owned, must outlive the handle's use) */
-int srlx_qnet_set_side_stream(srlx_qnet_t *h, void *stream);
 /* measurement aid: d_phase_stamps = device uint64 [8 waves][8] (or NULL to switch off): the fused convolution kernel's workgroup 0
  * records its shader clock at the phase boundaries (start, frames issued, staged, conv1 done, barrier, conv2 done, barrier, end) */
 int srlx_qnet_set_debug(srlx_qnet_t *h, void *d_phase_stamps);
 /* Round 6: the fused convolution kernel evaluates its float32 products as three exact products of two float16 parts per operand (x = hi + lo / 2048).  An
  * activation above 65 504 does not fit; the kernel then sets bit (layer - 1) of a device word of the handle instead of failing silently.  *out_bits = that word
- * (blocking device-to-host copy: call where the host has synchronised; the host side raises, device/qnet.py:check_ranges).  SRLX_CONV_BF16X3=1 selects the
- * three-part bf16 split of rounds 3-5, whose range is float32's. */
+ * (blocking device-to-host copy: call where the host has synchronised; the host side raises, device/qnet.py:check_ranges).  SRLX_CONV_BF16X3=1 (the
+ * environment switches above) avoids the limit. */
 int srlx_qnet_range_flags(srlx_qnet_t *h, int *out_bits);
 /* Training on the vectorised path (replaces `loss.backward()` + the framework forward it needs,
  * srl/algorithms/rainbow/model_torch.py:103-109):

@@ -15,6 +15,18 @@ namespace srlx {
 
 void set_error(const char *fmt, ...);
 
+// The library's numeric-path switches (include/srlx.h, "Environment switches"): read from the environment once per process, on the first call of
+// switches() (srlx_core.hip), which is the only place libsrlx reads the environment.
+struct Switches {
+    bool conv1_f32;       // SRLX_CONV1_F32=1: every convolution on the float32 matrix pipe
+    bool conv23_f32;      // SRLX_CONV23_F32=1: conv2 / conv3 on the float32 matrix pipe (conv1 keeps the 16-bit pipe, on three bf16 parts)
+    bool conv_h16;        // the convolutions' 16-bit products on two float16 parts (default); off with SRLX_CONV_BF16X3=1 or SRLX_CONV23_F32=1: three bf16 parts
+    bool fc1_f32;         // SRLX_FC1_F32=1: the first dense layer on the float32 matrix pipe
+    bool no_fused_conv;   // SRLX_NO_FUSED_CONV=1: the three-launch convolution path instead of the fused kernel
+    bool no_conv_planes;  // SRLX_NO_CONV_PLANES=1: the fused kernel writes float32 act3 and a split pass makes the first dense layer's operand planes
+};
+const Switches &switches();
+
 #define SRLX_HIP(expr)                                                                         \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \

@@ -1,4 +1,4 @@
-// srlx_core.hip -- error reporting and device queries of libsrlx.so
+// srlx_core.hip -- error reporting, the environment switches and device queries of libsrlx.so
 #include "srlx_common.h"
 
 namespace srlx {
@@ -8,6 +8,24 @@ void set_error(const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+const Switches &switches() {
+    static const Switches sw = [] {
+        auto on = [](const char *name) {
+            const char *v = getenv(name);
+            return v && v[0] == '1';
+        };
+        Switches s;
+        s.conv1_f32 = on("SRLX_CONV1_F32");
+        s.conv23_f32 = on("SRLX_CONV23_F32");
+        s.conv_h16 = !(on("SRLX_CONV_BF16X3") || s.conv23_f32);
+        s.fc1_f32 = on("SRLX_FC1_F32");
+        s.no_fused_conv = on("SRLX_NO_FUSED_CONV");
+        s.no_conv_planes = on("SRLX_NO_CONV_PLANES");
+        return s;
+    }();
+    return sw;
 }
 }  // namespace srlx
 

@@ -862,10 +862,9 @@ int srlx_qnet_dense_rows(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hi
     if (splits < 1) splits = 1;
     const int kps = ((ksteps + splits - 1) / splits);
     const int used = (ksteps + kps - 1) / kps;  // splits that actually own a K range
-    static const bool fc1_f32 = getenv("SRLX_FC1_F32") && getenv("SRLX_FC1_F32")[0] == '1';  // A/B switch: FC1 on the float32 matrix pipe
+    const bool fc1_f32 = srlx::switches().fc1_f32;
     // chip-filling launches of a handle with valid weight planes (the actors' pass): conversion-free GEMM on pre-split operands, bit-identical to k_gemm_s16
-    static const bool no_planes_gemm = getenv("SRLX_NO_PLANES_GEMM") && getenv("SRLX_NO_PLANES_GEMM")[0] == '1';  // measurement only (a selected set's pass then reads the BOUND float32 weight)
-    const bool planes = !fc1_f32 && !no_planes_gemm && stride == 1 && h->planes_valid && !h->eff[0] && srlx_fc1_planes_applicable(h, B);
+    const bool planes = !fc1_f32 && stride == 1 && h->planes_valid && !h->eff[0] && srlx_fc1_planes_applicable(h, B);
     if (planes && !h->a3_planes_fresh) SRLX_TRY(srlx_fc1_planes_split_act(h, B, st));  // (a convolution path that wrote float32 act3 only)
     h->a3_planes_fresh = false;
     if (h->probe_fc0) SRLX_HIP(hipEventRecord(h->probe_fc0, st));
@@ -918,23 +917,17 @@ int srlx_qnet_dgrad_gemm(const float *dY, int B, int QH, int QW, int OH, int OW,
     a.fill_taps(K, KW / S);
     const i64 M = (i64)B * QH * QW;
     const unsigned Z = (unsigned)(S * S);
-    static const bool dgrad_f32 = getenv("SRLX_DGRAD_F32") && getenv("SRLX_DGRAD_F32")[0] == '1';  // A/B switch: the data-gradient GEMMs on the float32 matrix pipe
+    // six exact bf16 partial products, operands split while staging (k_gemm_s16)
     if (CI == 64 && ksplits > 1) {  // stride 1 only (blockIdx.z is the K split here, the parity class otherwise): ksplits partial slabs of M x CI floats
-        SRLX_REQUIRE(S == 1 && (K / BK) % ksplits == 0 && !dgrad_f32, "dgrad_gemm: K splits need stride 1 and a K that divides");
+        SRLX_REQUIRE(S == 1 && (K / BK) % ksplits == 0, "dgrad_gemm: K splits need stride 1 and a K that divides");
         dim3 grid((unsigned)((M + 63) / 64), 1, (unsigned)ksplits);
         hipLaunchKernelGGL((k_gemm_s16<ADgrad, 64, true, 64>), grid, dim3(256), 0, st, a, wT, dXq, M, CI, K, K / ksplits);
     } else if (CI == 64) {
         dim3 grid((unsigned)((M + 63) / 64), 1, Z);
-        if (dgrad_f32)
-            hipLaunchKernelGGL((k_gemm<ADgrad, 64, false, false, 64>), grid, dim3(256), 0, st, a, wT, nullptr, dXq, M, CI, K, K, (i64)CI * K, M * CI);
-        else  // six exact bf16 partial products, operands split while staging (k_gemm_s16)
-            hipLaunchKernelGGL((k_gemm_s16<ADgrad, 64, false, 64>), grid, dim3(256), 0, st, a, wT, dXq, M, CI, K, K, (i64)CI * K, M * CI);
+        hipLaunchKernelGGL((k_gemm_s16<ADgrad, 64, false, 64>), grid, dim3(256), 0, st, a, wT, dXq, M, CI, K, K, (i64)CI * K, M * CI);
     } else {
         dim3 grid((unsigned)((M + BM - 1) / BM), 1, Z);
-        if (dgrad_f32)
-            hipLaunchKernelGGL((k_gemm<ADgrad, 32, false, false>), grid, dim3(256), 0, st, a, wT, nullptr, dXq, M, CI, K, K, (i64)CI * K, M * CI);
-        else
-            hipLaunchKernelGGL((k_gemm_s16<ADgrad, 32, false>), grid, dim3(256), 0, st, a, wT, dXq, M, CI, K, K, (i64)CI * K, M * CI);
+        hipLaunchKernelGGL((k_gemm_s16<ADgrad, 32, false>), grid, dim3(256), 0, st, a, wT, dXq, M, CI, K, K, (i64)CI * K, M * CI);
     }
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
@@ -1025,7 +1018,7 @@ int srlx_qnet_destroy(srlx_qnet_t *h) {
     if (h->wpack) (void)hipFree(h->wpack);
     if (h->wf_planes) (void)hipFree(h->wf_planes);
     if (h->a3_planes) (void)hipFree(h->a3_planes);
-    if (h->side && !h->side_external) (void)hipStreamDestroy(h->side);
+    if (h->side) (void)hipStreamDestroy(h->side);
     if (h->side2) (void)hipStreamDestroy(h->side2);
     for (hipEvent_t e : {h->ev_fork, h->ev_d3, h->ev_d2, h->ev_d1, h->ev_join, h->ev_wt, h->ev_join2})
         if (e) (void)hipEventDestroy(e);
@@ -1071,15 +1064,6 @@ int srlx_qnet_refresh_fc1_planes(srlx_qnet_t *h, const float *d_src_wf, float *d
 int srlx_qnet_invalidate_fc1_planes(srlx_qnet_t *h) {
     SRLX_REQUIRE(h, "qnet_invalidate_fc1_planes: NULL handle");
     h->planes_valid = false;
-    return SRLX_OK;
-}
-
-int srlx_qnet_set_side_stream(srlx_qnet_t *h, void *stream) {
-    SRLX_REQUIRE(h && stream, "qnet_set_side_stream: NULL argument");
-    SRLX_REQUIRE(h->max_train > 0, "qnet_set_side_stream: call srlx_qnet_enable_training first");
-    if (h->side && !h->side_external) (void)hipStreamDestroy(h->side);
-    h->side = (hipStream_t)stream;
-    h->side_external = true;
     return SRLX_OK;
 }
 
@@ -1336,8 +1320,7 @@ int srlx_qnet_set_head_mode(srlx_qnet_t *h, int mode, int out_cols, const float 
 
 // conv1 -> conv2 -> conv3 from the uint8 ring into h->act3, then (d_q != NULL) the dense layers
 static int forward_u8_impl(srlx_qnet_t *h, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, float *d_q, hipStream_t st) {
-    static const bool no_fused = getenv("SRLX_NO_FUSED_CONV") && getenv("SRLX_NO_FUSED_CONV")[0] == '1';  // A/B switch for measurements
-    if (!no_fused && h->H == 84 && h->W == 84 && h->Wn == 4 && h->F1 == 32) {
+    if (!srlx::switches().no_fused_conv && h->H == 84 && h->W == 84 && h->Wn == 4 && h->F1 == 32) {
         // conv1 -> conv2 -> conv3 in one kernel, one workgroup per sample, activations in LDS (srlx_qnet_fused.hip)
         // (the probe events are recorded inside, right around k_convnet_fused: the filter-packing launch before it is not part of the timed kernel)
         h->want_planes_out = d_q != nullptr;

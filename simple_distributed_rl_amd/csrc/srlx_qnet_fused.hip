@@ -897,14 +897,6 @@ __global__ void __launch_bounds__(64 * kWaves) k_convnet_fused_multi(const u8 *_
 
 }  // namespace
 
-// SRLX_CONV_BF16X3=1: the convolutions' matrix-pipe products as six of the nine products of three bf16 parts (rounds 3-5) instead of three products of two float16
-// parts (A/B switch, and the path for networks whose activations leave float16's range); read once per process
-bool srlx_conv_h16() {
-    static const bool bf16x3 = (getenv("SRLX_CONV_BF16X3") && getenv("SRLX_CONV_BF16X3")[0] == '1') ||
-                               (getenv("SRLX_CONV23_F32") && getenv("SRLX_CONV23_F32")[0] == '1');  // (that A/B variant's conv1 reads the bf16 fragments)
-    return !bf16x3;
-}
-
 size_t srlx_qnet_pack_bytes() { return (size_t)kPackFloats * sizeof(float); }
 
 // k_pack_filters over `src`'s bound filters into its own packed buffer (+ the transposed filters of a training handle) and, with `dst_set`, a second copy
@@ -917,7 +909,7 @@ int srlx_qnet_pack_publish(srlx_qnet *src, srlx_qnet::ActorSet *dst_set, const s
     const float *w1 = b ? b[0] : src->w1, *w2 = b ? b[2] : src->w2, *w3 = b ? b[4] : src->w3;
     int pack_threads = (kW1 + kW2 + kW3) / 4 + 16 * 64 + (32 + 36) * 2 * 64 + (keep ? kW3 + kW2 : 0);
     SmallCopy sm{};
-    sm.h16 = srlx_conv_h16() ? 1 : 0;
+    sm.h16 = srlx::switches().conv_h16 ? 1 : 0;
     sm.bump = (long long *)bump;
     const bool adam = adam_small && src->rest_on && src->rest_armed;
     srlx_small_layout own_layout;
@@ -952,8 +944,8 @@ int srlx_qnet_pack_publish(srlx_qnet *src, srlx_qnet::ActorSet *dst_set, const s
 // Launcher: true when the fused kernel covers this handle's geometry (then act3 -- and act1 / act2 when training is enabled -- are valid).
 bool srlx_qnet_fused_convs(srlx_qnet *h, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, hipStream_t st) {
     if (!(h->H == 84 && h->W == 84 && h->Wn == 4 && h->F1 == 32)) return false;
-    static bool attr_set = false;
-    if (!attr_set) {
+    // the LDS limit of every instantiation below, set once per process (thread-safe initialisation of a function-local static)
+    static const bool attr_ok = [] {
         const void *kerns[] = {(const void *)k_convnet_fused<true, true, true, 1>, (const void *)k_convnet_fused<false, true, true, 2>,
                                (const void *)k_convnet_fused<true, true, true>,  (const void *)k_convnet_fused<false, true, true>,
                                (const void *)k_convnet_fused<true, true, true, 1, true>, (const void *)k_convnet_fused<false, true, true, 2, true>,
@@ -962,49 +954,49 @@ bool srlx_qnet_fused_convs(srlx_qnet *h, int64_t batch, const uint8_t *d_frame_b
                                (const void *)k_convnet_fused<true, false, false>, (const void *)k_convnet_fused<false, false, false>};
         for (const void *kp : kerns)
             if (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes) != hipSuccess) return false;
-        attr_set = true;
-    }
+        return true;
+    }();
+    if (!attr_ok) return false;
     const bool keep = h->max_train > 0;  // a training handle: the backward pass reads act1 / act2 and the transposed filters
     if (!h->pack_valid) {  // (valid: packed right after the last optimiser step by srlx_qnet_publish, a selected actor set, or a sticky pack of unchanged weights)
         if (srlx_qnet_pack_publish(h, nullptr, nullptr, st) != SRLX_OK) return false;
         h->pack_valid = h->pack_sticky;
     }
     h->wt_from_forward = keep;
-    static const bool c1_f32 = getenv("SRLX_CONV1_F32") && getenv("SRLX_CONV1_F32")[0] == '1';  // A/B switch: conv1 on the float32 matrix pipe
-    float *out3 = h->act3;
-    const bool h16 = srlx_conv_h16();
-    const size_t lds = h16 && !c1_f32 ? kLdsH16 : kLdsBytes;
+    const srlx::Switches &sw = srlx::switches();
+    const bool h16 = sw.conv_h16 && !sw.conv1_f32;  // the kernel runs the two-part float16 split (and needs less LDS)
+    const bool big = batch >= 512;
+    // the dense layers will run on operand planes (srlx_qnet_dense_rows's own condition): conv3 writes them itself
+    const bool planes = h->want_planes_out && !sw.no_conv_planes && !sw.conv1_f32 && !sw.conv23_f32 && h->planes_valid && !h->eff[0] &&
+                        srlx_fc1_planes_applicable(h, batch);
     // one workgroup per sample.  (Measured and dropped in round 4: fewer, sample-walking workgroups -- the loop form cost 20 % in code generation -- and the launch
     // cut into chunks of consecutive samples so that the update's kernels get compute units earlier: -1.1 % / +0.4 % per lock-step on two boxes; profiles/NOTES.md.)
-    auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(64 * kWaves), lds, st, d_frame_base, d_frame_off, h->wpack, h->b1, h->b2, h->b3, out3,
-                           keep ? h->act1 : nullptr, keep ? h->act2 : nullptr, (unsigned long long *)h->fused_dbg, (unsigned char *)nullptr, 0ll, (long long)batch, 0ll, h->range_flag);
-    };
-    static const bool c23_f32 = getenv("SRLX_CONV23_F32") && getenv("SRLX_CONV23_F32")[0] == '1';  // A/B switch: conv2 / conv3 on the float32 matrix pipe
-    if (h->probe0 && hipEventRecord(h->probe0, st) != hipSuccess) return false;  // measurement hook: exactly this kernel, on its launch stream
-    // the dense layers will run on operand planes (srlx_qnet_dense_rows's own condition): conv3 writes them itself, float32 act3 is not produced
-    static const bool no_planes_out = (getenv("SRLX_NO_CONV_PLANES") && getenv("SRLX_NO_CONV_PLANES")[0] == '1') ||  // A/B switch: float32 act3 + a split pass
-                                      (getenv("SRLX_NO_PLANES_GEMM") && getenv("SRLX_NO_PLANES_GEMM")[0] == '1');
-    h->a3_planes_fresh = false;
-    if (h->want_planes_out && !no_planes_out && !c1_f32 && !c23_f32 && !keep && h->planes_valid && !h->eff[0] && srlx_fc1_planes_applicable(h, batch) && batch >= 512) {
+    using Kern = decltype(&k_convnet_fused<true, true, true>);
+    Kern kern;
+    float *out3 = h->act3;
+    unsigned char *planes_out = nullptr;
+    long long prow = 0;  // rows of planes_out
+    if (planes && !keep && big) {  // an inference pass: the planes instead of float32 act3
+        kern = h16 ? k_convnet_fused<true, true, true, 1, true> : k_convnet_fused<true, true, true, 1>;
         out3 = reinterpret_cast<float *>(h->a3_planes);
-        h16 ? launch(k_convnet_fused<true, true, true, 1, true>) : launch(k_convnet_fused<true, true, true, 1>);
-        h->a3_planes_fresh = true;
-    } else if (h->want_planes_out && !no_planes_out && !c1_f32 && !c23_f32 && h->planes_valid && !h->eff[0] && srlx_fc1_planes_applicable(h, batch)) {
+    } else if (planes) {
         // a learner's pass (96 / 128 rows; `planes_small`): float32 act3 for its backward pass AND the planes for the first dense layer, rows padded to the GEMM's tile
-        const long long prow = (batch + 127) / 128 * 128;
-        auto launch2 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(64 * kWaves), lds, st, d_frame_base, d_frame_off, h->wpack, h->b1, h->b2, h->b3, out3,
-                               keep ? h->act1 : nullptr, keep ? h->act2 : nullptr, (unsigned long long *)h->fused_dbg, (unsigned char *)h->a3_planes, prow, (long long)batch, 0ll, h->range_flag);
-        };
-        h16 ? launch2(k_convnet_fused<false, true, true, 2, true>) : launch2(k_convnet_fused<false, true, true, 2>);
-        h->a3_planes_fresh = true;
-    } else if (batch >= 512)
-        c1_f32 ? launch(k_convnet_fused<true, false, false>) : c23_f32 ? launch(k_convnet_fused<true, true, false>)
-               : h16 ? launch(k_convnet_fused<true, true, true, 0, true>) : launch(k_convnet_fused<true, true, true>);
-    else
-        c1_f32 ? launch(k_convnet_fused<false, false, false>) : c23_f32 ? launch(k_convnet_fused<false, true, false>)
-               : h16 ? launch(k_convnet_fused<false, true, true, 0, true>) : launch(k_convnet_fused<false, true, true>);
+        kern = h16 ? k_convnet_fused<false, true, true, 2, true> : k_convnet_fused<false, true, true, 2>;
+        planes_out = (unsigned char *)h->a3_planes;
+        prow = (batch + 127) / 128 * 128;
+    } else if (sw.conv1_f32) {
+        kern = big ? k_convnet_fused<true, false, false> : k_convnet_fused<false, false, false>;
+    } else if (sw.conv23_f32) {
+        kern = big ? k_convnet_fused<true, true, false> : k_convnet_fused<false, true, false>;
+    } else if (h16) {
+        kern = big ? k_convnet_fused<true, true, true, 0, true> : k_convnet_fused<false, true, true, 0, true>;
+    } else {
+        kern = big ? k_convnet_fused<true, true, true> : k_convnet_fused<false, true, true>;
+    }
+    if (h->probe0 && hipEventRecord(h->probe0, st) != hipSuccess) return false;  // measurement hook: exactly this kernel, on its launch stream
+    hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(64 * kWaves), h16 ? kLdsH16 : kLdsBytes, st, d_frame_base, d_frame_off, h->wpack, h->b1, h->b2, h->b3, out3,
+                       keep ? h->act1 : nullptr, keep ? h->act2 : nullptr, (unsigned long long *)h->fused_dbg, planes_out, prow, (long long)batch, 0ll, h->range_flag);
+    h->a3_planes_fresh = planes;
     if (h->probe1 && hipEventRecord(h->probe1, st) != hipSuccess) return false;
     if (h->stamp_buf && srlx_debug_stamp(h->stamp_buf, 10, st) != SRLX_OK) return false;  // (measurement aid: the convolution launch of a forward pass is done)
     return hipGetLastError() == hipSuccess;
@@ -1014,12 +1006,11 @@ bool srlx_qnet_fused_convs(srlx_qnet *h, int64_t batch, const uint8_t *d_frame_b
 // kernel (operand planes fresh): srlx_qnet_forward_dense_planes continues each.
 int srlx_qnet_fused_convs_multi(srlx_qnet *const *hs, int n, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, hipStream_t st) {
     SRLX_REQUIRE(n >= 1 && n <= kMultiMax && batch >= 512, "qnet_forward_convs_multi: 1..%d handles, chip-filling batches", kMultiMax);
-    static bool attr_set = false;
-    if (!attr_set) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_convnet_fused_multi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_convnet_fused_multi<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        attr_set = true;
-    }
+    static const hipError_t attr = [] {  // once per process, like srlx_qnet_fused_convs's
+        const hipError_t e = hipFuncSetAttribute((const void *)k_convnet_fused_multi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+        return e != hipSuccess ? e : hipFuncSetAttribute((const void *)k_convnet_fused_multi<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    }();
+    SRLX_HIP(attr);
     MultiNets nets{};
     for (int k = 0; k < n; k++) {
         srlx_qnet *h = hs[k];
@@ -1034,7 +1025,7 @@ int srlx_qnet_fused_convs_multi(srlx_qnet *const *hs, int n, int64_t batch, cons
         nets.wpk[k] = h->wpack, nets.b1[k] = h->b1, nets.b2[k] = h->b2, nets.b3[k] = h->b3, nets.act3[k] = reinterpret_cast<float *>(h->a3_planes), nets.flag[k] = h->range_flag;
     }
     if (hs[0]->probe0) SRLX_HIP(hipEventRecord(hs[0]->probe0, st));
-    if (srlx_conv_h16())
+    if (srlx::switches().conv_h16)
         hipLaunchKernelGGL(k_convnet_fused_multi<true>, dim3((unsigned)(n * batch)), dim3(64 * kWaves), kLdsH16, st, d_frame_base, d_frame_off, nets, (long long)batch);
     else
         hipLaunchKernelGGL(k_convnet_fused_multi<false>, dim3((unsigned)(n * batch)), dim3(64 * kWaves), kLdsBytes, st, d_frame_base, d_frame_off, nets, (long long)batch);

@@ -47,7 +47,6 @@ struct srlx_qnet {
     float *g_sig[6];                      // BORROWED gradient tensors of the sigmas (srlx_qnet_bind_noisy_grads)
     int *range_flag;                      // device word: bit l set when an activation of layer l + 1 left float16's range in the two-part split (srlx_qnet_range_flags)
     void *fused_dbg;                      // optional device buffer [8 waves][8] of phase timestamps (srlx_qnet_set_debug; NULL in production)
-    bool side_external;                   // h->side was handed in (srlx_qnet_set_side_stream): not ours to destroy
     bool wt_from_forward;                 // the last forward already built w_t / w_t2 (fused path of a training handle)
     float *wpack;                         // conv filters in MFMA-fragment order (srlx_qnet_fused.hip), rebuilt per forward
     // pre-split bf16 operand planes of the first dense layer (srlx_fc1_planes.hip; srlx_qnet_enable_fc1_planes): [row][K/8][3 parts][8 bf16]
@@ -168,7 +167,6 @@ int srlx_qnet_noisy_sigma_grads(srlx_qnet *h, float *const *g, hipStream_t st);
 int srlx_qnet_dense_rows(srlx_qnet *h, int64_t rows, int64_t stride, float *d_q, hipStream_t st);
 
 // srlx_qnet_fused.hip: conv1 -> conv2 -> conv3 in one kernel (activations in LDS); false when the geometry is not the Atari one
-bool srlx_conv_h16();  // the convolutions' split: two float16 parts (default) or three bf16 parts (SRLX_CONV_BF16X3=1)
 bool srlx_qnet_fused_convs(srlx_qnet *h, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, hipStream_t st);
 
 int srlx_qnet_fused_convs_multi(srlx_qnet *const *hs, int n, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, hipStream_t st);

@@ -21,13 +21,12 @@ module trees (algorithms/agent57_light.py: the reference's, so parameters stay i
 IMAGE BLOCKS never run through torch: actors and learner evaluate them with libsrlx's fused convolution kernel straight from
 the uint8 ring (device/qnet.py:ImageTrunk / TrainableImageTrunk, weights bound by address) and the learner differentiates
 them with the hand-written backward (srlx_qnet_backward_convs_u8); only the dense tails and Adam are torch (hipBLASLt).
-SRLX_A57_TORCH_LEARNER=1 puts the learner back on torch's convolutions (a test yardstick).  `Agent57LightLearner` is shared
+Agent57LightEngine(torch_learner=True) puts the learner back on torch's convolutions (a test yardstick).  `Agent57LightLearner` is shared
 with the single-environment plugin trainer.  With overlap=True the update runs on its own stream beside the next lock-step's
 actors, which act on copies of the networks they need (refreshed after the join), like the Rainbow engine.
 """
 import ctypes
 import functools
-import os
 from typing import Optional
 
 import numpy as np
@@ -277,11 +276,12 @@ class Agent57LightEngine:
     `parameter`: its Parameter (the five networks), created here when not given."""
 
     def __init__(self, rl_config, n_envs: int, device: int = 0, episode_len: int = 200, seed: int = 0, env=None, parameter=None, ring_len: Optional[int] = None,
-                 overlap: bool = False):
+                 overlap: bool = False, torch_trunks: bool = False, torch_learner: bool = False):
         """overlap=True (round 4): the update runs on its own stream BESIDE the actors' lock-step, forked before the policy pass and joined before the ring commit,
         exactly like RainbowEngine's overlap: the actors act on private copies of the two Q-networks (refreshed after every join; the reference's distributed actors
         poll the trainer's parameter board on a timer, play_mp.py:151-165).  The update's HIP graph is launched by a helper thread: hipGraphLaunch keeps its caller
-        busy for the whole ~2.4 ms of that graph (tools/_r4_a57.sh), during which the main thread issues the actors' launches."""
+        busy for the whole ~2.4 ms of that graph (tools/_r4_a57.sh), during which the main thread issues the actors' launches.
+        torch_trunks=True: the actors' image blocks through torch; torch_learner=True: the learner's (A/B yardsticks of the tests)."""
         from simple_distributed_rl_amd.device.rainbow import SyntheticAtariVecEnv
 
         c = self.cfg = rl_config
@@ -323,7 +323,7 @@ class Agent57LightEngine:
         self.ucb = UcbBank(E, Na, c.ucb_window_size, c.ucb_epsilon, c.ucb_beta, d, self.seed)
         # The actors' five image blocks (two UVFA Q-networks, embedding, RND target / predictor) straight from the uint8 ring through libsrlx's
         # convolution kernels (device/qnet.py:ImageTrunk) -- MIOpen's fp32 convolutions + replication-pad + layout transposes were 60 % of a
-        # lock-step; the dense parts and the whole learner stay torch.  SRLX_A57_TORCH_TRUNKS=1: the all-torch pass (A/B, tests).
+        # lock-step; the dense parts and the whole learner stay torch.  torch_trunks=True: the all-torch pass (A/B, tests).
         from simple_distributed_rl_amd.device.qnet import ImageTrunk
 
         self.overlap = bool(overlap)
@@ -346,7 +346,7 @@ class Agent57LightEngine:
         nets = {"q_ext": self._act_q["q_ext"], "q_int": self._act_q["q_int"]}
         if c.enable_intrinsic_reward:
             nets.update(emb=self._act_q["emb"], rnd_target=p.lifelong_target, rnd_train=self._act_q["rnd_train"])
-        if os.environ.get("SRLX_A57_TORCH_TRUNKS", "0") != "1":
+        if not torch_trunks:
             for name, net in nets.items():
                 blk = getattr(getattr(net, "in_block", None), "image_block", None)
                 if blk is not None and getattr(net.in_block, "out_flatten", False) and ImageTrunk.supported(blk):
@@ -360,9 +360,9 @@ class Agent57LightEngine:
         # The LEARNER's image blocks, forward and backward, hand-written too (device/qnet.py:TrainableImageTrunk): one handle per network that trains
         # (its forward keeps the activations, its backward writes the six convolution gradients) and one per network that is only evaluated (targets).
         # No MIOpen on the update path: its convolutions were 3.3 ms of the update and chose their solvers per engine instance by timing, so that one
-        # instance in four learned on a different trajectory.  SRLX_A57_TORCH_LEARNER=1: the torch image blocks (A/B, tests).
+        # instance in four learned on a different trajectory.  torch_learner=True: the torch image blocks (A/B, tests).
         self._ltrunks = None
-        if self._all_fused and os.environ.get("SRLX_A57_TORCH_LEARNER", "0") != "1" and 2 * B <= 64 and nets["q_ext"].in_block.image_block.image_layers[0].out_channels == 32:
+        if self._all_fused and not torch_learner and 2 * B <= 64 and nets["q_ext"].in_block.image_block.image_layers[0].out_channels == 32:
             from simple_distributed_rl_amd.device.qnet import TrainableImageTrunk
 
             blk = lambda net: net.in_block.image_block  # noqa: E731

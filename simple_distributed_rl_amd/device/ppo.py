@@ -25,7 +25,6 @@ it sits INSIDE the captured update graph, between the gradient reduction and the
 """
 import ctypes
 import math
-import os
 from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
 
@@ -170,15 +169,14 @@ class PPOEngine:
         self.episode_return = torch.zeros(E, **f32)
         self.finished_returns = torch.zeros(2, **f32)  # sum, count of finished episodes since the last read
         # One minibatch permutation per epoch from libsrlx's keyed permutation kernel (srlx_rng_permutation: device state only), INSIDE the captured
-        # update.  What round 2 hid behind a hipStreamSynchronize per iteration (tools/ppo_replay_bisect.py, ROCm 7.2 / torch 2.10, E = 4096): with NO
+        # update.  What round 2 hid behind a hipStreamSynchronize per iteration (a bisect on ROCm 7.2 / torch 2.10, E = 4096; tools/README.md): with NO
         # eager launch between replays of the two large graphs (~700 / ~1000 nodes) -- fixed permutations, or this kernel -- 40 unsynchronised iterations
         # equal the synchronised run to 1e-7; with torch.randperm as a graph node (torch refreshes the generator's offset tensors with eager launches before
         # every replay) they turn non-finite, and with torch.randperm drawn eagerly between the replays they stay finite but train differently: eager
         # kernels enqueued behind a large graph launch do not reliably wait for the graph's tail (an event recorded there does not either:
-        # event.synchronize() per iteration does not help, hipStreamSynchronize does).  A graph whose only node is randperm replays fine
-        # (tools/randperm_graph_repro.py).  SRLX_PPO_PERM = in_graph (torch.randperm as a node) / eager / fixed: the bisect's other arms.
-        self._perm_mode = os.environ.get("SRLX_PPO_PERM", "srlx")
-        self._perms = torch.stack([torch.randperm(T * E, device=d) for _ in range(cfg.epochs)])  # ("fixed": these stay)
+        # event.synchronize() per iteration does not help, hipStreamSynchronize does).  A graph whose only node is randperm replays fine.
+        # (The initial values below are overwritten before their first use; the draws keep torch's CUDA generator where every later draw expects it.)
+        self._perms = torch.stack([torch.randperm(T * E, device=d) for _ in range(cfg.epochs)])
         self.perm_counter = torch.zeros(1, dtype=torch.int64, device=d)
 
     # --- rollout ---------------------------------------------------------------------------------------------------
@@ -256,9 +254,8 @@ class PPOEngine:
         if self.fused:
             return self._update_fused(n, mb, obs, act, logp, adv, val, v_target)
         for ep in range(cfg.epochs):
-            if self._perm_mode == "srlx":
-                N.check(self.lib.srlx_rng_permutation(cfg.seed ^ 0x7065726D, N.tptr(self.perm_counter), n, N.tptr(self._perms[ep]), N.torch_stream_ptr()))
-            perm = self._perms[ep] if self._perm_mode != "in_graph" else torch.randperm(n, device=self.dev)
+            N.check(self.lib.srlx_rng_permutation(cfg.seed ^ 0x7065726D, N.tptr(self.perm_counter), n, N.tptr(self._perms[ep]), N.torch_stream_ptr()))
+            perm = self._perms[ep]
             for k in range(cfg.minibatches):
                 idx = perm[k * mb : (k + 1) * mb]
                 outs, seeds = self.loss_and_seeds(obs[idx], act[idx].contiguous(), logp[idx].contiguous(), adv[idx].contiguous(), v_target[idx].contiguous(),
@@ -276,8 +273,8 @@ class PPOEngine:
         permutation's rows."""
         cfg = self.cfg
         st = N.torch_stream_ptr()
-        if self._perm_mode == "srlx":  # the epochs' shuffles in one launch (the values `epochs` successive srlx_rng_permutation calls would write)
-            N.check(self.lib.srlx_rng_permutations(cfg.seed ^ 0x7065726D, N.tptr(self.perm_counter), n, cfg.epochs, N.tptr(self._perms), st))
+        # the epochs' shuffles in one launch (the values `epochs` successive srlx_rng_permutation calls would write)
+        N.check(self.lib.srlx_rng_permutations(cfg.seed ^ 0x7065726D, N.tptr(self.perm_counter), n, cfg.epochs, N.tptr(self._perms), st))
         for ep in range(cfg.epochs):
             for k in range(cfg.minibatches):
                 rows = self._perms[ep][k * mb : (k + 1) * mb]
@@ -312,28 +309,12 @@ class PPOEngine:
         self._rollout_graph, self._update_graph = g1, g2
         torch.cuda.synchronize(self.dev)
 
-    def _draw_permutations(self):
-        if self._perm_mode == "eager":
-            for ep in range(self.cfg.epochs):
-                torch.randperm(self._perms.shape[1], device=self.dev, out=self._perms[ep])
-
     def step(self):
         """one PPO iteration: T x E environment steps + epochs x minibatches updates"""
-        self._draw_permutations()
         if self._rollout_graph is not None:
             # two graph launches per iteration, nothing waits on the host and nothing is launched eagerly between them (see __init__)
             self._rollout_graph.replay()
             self._update_graph.replay()
-            mode = os.environ.get("SRLX_PPO_SYNC", "none")  # tools/ppo_replay_bisect.py: host-side waits as an experiment
-            if mode == "stream":
-                torch.cuda.current_stream(self.dev).synchronize()
-            elif mode == "event":
-                ev = torch.cuda.Event()
-                ev.record()
-                ev.synchronize()
-            elif mode.startswith("every"):
-                if (self.iterations + 1) % int(mode[5:]) == 0:
-                    torch.cuda.current_stream(self.dev).synchronize()
         else:
             self.rollout()
             self.update()

@@ -195,7 +195,7 @@ class RainbowEngine:
             raise ValueError("RainbowEngine: schedule.fast=True where the fast lock-step does not apply")
         self.fast = can_fast and (bool(fast) if fast is not None else True)
         # the single-GPU round-5 lock-step (actors + learner here, the learner's replay = this ring): the tree add of a lock-step runs one lock-step behind its ring
-        # commit, on a side branch of the next update -- the ring gets one spare slot (DeviceReplay(lagged_add=True)).  SRLX_LAGGED_ADD=0: the add behind the join.
+        # commit, on a side branch of the next update -- the ring gets one spare slot (DeviceReplay(lagged_add=True)).  EngineSchedule(lagged_add=False): the add behind the join.
         lag = self.fast and role == "both" and learner_replay is None and sch.lagged_add
         self.replay = DeviceReplay(
             E, ring_len + (1 if lag else 0), H * W_, cfg.window_length, n, A, B, True, cfg.enable_reward_clip,
@@ -272,14 +272,14 @@ class RainbowEngine:
             self.inf_actor.enable_actor_sets()
             # the passes run BESIDE the update: half-CU workgroups in a steady stream instead of one CU-filling workgroup per CU for the whole launch
             # (same-box A/B of the lock-step, tools/_r4_probe3.sh: 0.508 ms with 4 K splits -- 256 workgroups that leave half of every CU to the update --, 0.515
-            # with 8, 0.528 with 16, 0.545 with the CU-filling kernel; SRLX_FC1_NEIGHBOUR=0 selects that one, = k the K splits)
+            # with 8, 0.528 with 16, 0.545 with the CU-filling kernel; EngineSchedule(fc1_neighbour=0) selects that one, = k the K splits)
             self.inf_actor.set_fc1_neighbour(int(sch.fc1_neighbour))
         elif not self.noisy and E >= 512 and E % 128 == 0 and (2 * cfg.hidden_units) % 128 == 0 and (planes == "1" or (planes == "auto" and not overlap)):
             # Chip-filling policy passes with the first dense layer on pre-split bf16 operand planes (srlx_fc1_planes.hip): the GEMM itself is 1.6x faster
             # (85 against 137 us at 1024 rows), but beside a learner it LOSES: same-box A/B (tools/_ab_lockstep.sh) 0.565 against 0.511 ms per lock-step --
             # the refresh of the actors' copy also has to split the 32 MB weight (22 us on the serial tail every lock-step) and the planes kernel's 144 KB /
             # 512-thread workgroups keep the learner's dependent kernels waiting for compute units like the convolution kernel does.  So: on for an engine
-            # that only acts (no update shares the GPU: the actor ranks of device/dist.py), off when actors and learner overlap on one GPU.  SRLX_FC1_PLANES=1 / 0
+            # that only acts (no update shares the GPU: the actor ranks of device/dist.py), off when actors and learner overlap on one GPU.  EngineSchedule(fc1_planes="1" / "0")
             # forces it.
             self.inf_actor.enable_fc1_planes(private_weights=self.q_actor is not self.q_online)
         self.inf_online = QNetInference(self.q_online, max(B * (n + 1), 64), device, noise_seed=cfg.seed * 3 + 0x0B0E)
@@ -350,7 +350,7 @@ class RainbowEngine:
         # pre-draw: the NEXT update's batch is drawn right behind this update's write-back, into the replay's other buffer set, instead of at the head of the next
         # update's chain.  On for a learner rank's replay, where the update's own chain is the period (0.338 -> 0.323 ms per period alone on a GPU, same box); beside
         # this GPU's own actors the period is contention-bound and the move changed nothing (0.457 against 0.454 ms, same box; 0.441 against 0.434 for the 2-GPU
-        # topology's acting learner rank): on for learner-ONLY ranks unless SRLX_PREDRAW says otherwise.
+        # topology's acting learner rank): on for learner-ONLY ranks unless EngineSchedule.predraw says otherwise.
         self._predraw = bool(self.fast and self._update_side and self.s_ingest is not None and getattr(self.lreplay, "two_sets", False)
                              and (sch.predraw if sch.predraw is not None else (learner_replay is not None and role == "learner")))
         self._bset, self._drawn, self._drawn_at = 0, None, 0
@@ -702,7 +702,7 @@ class RainbowEngine:
                 mark(6)
                 if self._update_side:
                     return
-        else:  # SRLX_TORCH_BACKWARD=1: the test yardstick -- matrix-core evaluation of s_1..s_n, autograd for the gradient step
+        else:  # EngineSchedule(autograd_yardstick=True): the test yardstick -- matrix-core evaluation of s_1..s_n, autograd for the gradient step
             b = r.sample_items(self.train_count_dev)
             cur = torch.cuda.current_stream(self.dev)
             fork_ingest(cur)

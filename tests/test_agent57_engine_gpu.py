@@ -202,7 +202,7 @@ def test_image_trunks_equal_the_torch_image_blocks(hw):
     assert eng.train_count > 5
 
 
-def _engine84(batch=16, E=16, seed=3):
+def _engine84(batch=16, E=16, seed=3, torch_learner=False):
     from simple_distributed_rl_amd.device.agent57_light import Agent57LightEngine
 
     cfg = agent57_light.Config(batch_size=batch, actor_num=4, target_model_update_interval=5, episodic_memory_capacity=64, ucb_window_size=6)
@@ -213,7 +213,7 @@ def _engine84(batch=16, E=16, seed=3):
     cfg.hidden_block.set_dueling_network((64,))
     env = srl.make_env(srl.EnvConfig("SyntheticAtari-v0", kwargs=dict(hw=(84, 84), n_actions=4, episode_len=11)))
     cfg.setup(env)
-    return Agent57LightEngine(cfg, E, 0, episode_len=11, seed=seed), cfg
+    return Agent57LightEngine(cfg, E, 0, episode_len=11, seed=seed, torch_learner=torch_learner), cfg
 
 
 def test_trainable_trunk_gradients_equal_autograd():
@@ -270,9 +270,9 @@ def test_trainable_trunk_gradients_equal_autograd():
             torch.testing.assert_close(p.grad.double().cpu(), w, rtol=1e-5, atol=1e-5 * float(w.abs().max()))
 
 
-def test_hand_written_learner_equals_the_torch_learner_and_is_reproducible():
+def test_hand_written_learner_matches_the_torch_learner_argument_and_is_reproducible():
     """The update with the image blocks of all five networks in libsrlx (forward + backward; no MIOpen on the update path) against the same update through
-    torch's convolutions (SRLX_A57_TORCH_LEARNER=1) from the same seed.  Two statements, two tolerances:
+    torch's convolutions (torch_learner=True) from the same seed.  Two statements, two tolerances:
     * the FIRST update's four losses -- same weights, same batch, only the forward arithmetic differs (split-bf16 products on the matrix pipe against
       MIOpen's fp32 convolutions) -- agree to north_star's 1e-5;
     * after 12 updates the losses agree to 5e-3 (1e-3 held for the three-part bf16 split of rounds 3-5; round 6's two-part float16 split -- the same 2.9e-7 forward
@@ -285,15 +285,10 @@ def test_hand_written_learner_equals_the_torch_learner_and_is_reproducible():
       train_step_agent57_light.npz).
     Two hand-written instances give the SAME losses bit for bit."""
     def run(torch_learner):
-        if torch_learner:
-            os.environ["SRLX_A57_TORCH_LEARNER"] = "1"
         torch.manual_seed(11)  # the five networks are initialised from torch's global generator
         random.seed(11)
         np.random.seed(11)
-        try:
-            eng, _ = _engine84()
-        finally:
-            os.environ.pop("SRLX_A57_TORCH_LEARNER", None)
+        eng, _ = _engine84(torch_learner=torch_learner)
         assert (eng._ltrunks is None) == torch_learner
         first = None
         for _ in range(20):

@@ -241,7 +241,7 @@ def test_bench_ppo_line():
 def test_graph_replays_do_not_depend_on_host_synchronisation():
     """PPOEngine.step() with captured graphs, iterations queued back to back (nothing waits on the host) vs one host synchronisation per iteration: the
     same training, finite at E = 4096.  The engine draws its minibatch permutations eagerly, outside the captured update: torch.randperm as a graph
-    node was what made unsynchronised replays diverge (tools/ppo_replay_bisect.py, tools/randperm_graph_repro.py; device/ppo.py:__init__)."""
+    node was what made unsynchronised replays diverge (tools/README.md, finding 37; device/ppo.py:__init__)."""
     import torch
 
     from simple_distributed_rl_amd.device.ppo import PPODeviceConfig, PPOEngine

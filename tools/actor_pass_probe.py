@@ -1,6 +1,7 @@
 """The actors' policy pass exactly as the round-4 engine launches it beside a learner (E rows: fused convolution kernel reading a PUBLISHED parameter set, first
 dense layer on operand planes with half-CU workgroups, head kernel with the epsilon-greedy selection in its epilogue) in a loop -- the target of the rocprofv3
-kernel-trace / PMC passes of tools/r4_measure.sh.  SRLX_FC1_NEIGHBOUR=0: the CU-filling first-dense-layer kernel; SRLX_PROBE_S16=1: the staging-split GEMM."""
+kernel-trace / PMC passes of tools/r4_measure.sh.  Arguments: E, repetitions, K splits of the half-CU first-dense-layer kernel (default 4; 0: the CU-filling
+kernel).  SRLX_PROBE_S16=1: the staging-split GEMM."""
 import os
 import sys
 
@@ -12,6 +13,7 @@ from simple_distributed_rl_amd.device.qnet import EngineQNet, QNetInference
 
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+splits = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 torch.manual_seed(0)
 online = EngineQNet(6).cuda()
 src = QNetInference(online, 128)
@@ -19,7 +21,7 @@ qn = QNetInference(online, E)
 if os.environ.get("SRLX_PROBE_S16", "0") != "1":
     qn.enable_fc1_planes(private_weights=True)
     qn.enable_actor_sets()
-    qn.set_fc1_neighbour(int(os.environ.get("SRLX_FC1_NEIGHBOUR", "4")))
+    qn.set_fc1_neighbour(splits)
     src.publish_to(qn, 0, with_fc1=True)
     qn.select_set(0)
 F = 84 * 84
