@@ -116,14 +116,19 @@ int srlx_per_sample(srlx_per_t *h, int64_t batch_size, int64_t step, const int64
                     int64_t n_uniforms, int64_t *out_idx, double *out_w, float *out_w32, int64_t *out_used,
                     int on_device, void *stream);
 /* The host loop of the reference's memory -- add one item, sample, update (srl/rl/memories/priority_replay_buffer.py:205-258; tests/quick/rl/memories/speedtest.py:15-58)
- * -- as ONE launch per sample: `n_add` <= 16 adds queued since the tree was last observed (host values: final leaf priorities with SRLX_PRIO_RAW, or add_values = NULL
- * with SRLX_PRIO_NONE) are applied inside the sampling launch, in order, exactly like srlx_per_add would; uniforms in and results out travel through a device-visible
- * pinned slot and the host spins on a completion flag the kernel stores last (no stream synchronisation).  Host pointers; results as srlx_per_sample(on_device = 0). */
+ * -- as ONE launch per sample: `n_add` <= min(16, capacity) adds queued since the tree was last observed (host values: final leaf priorities with SRLX_PRIO_RAW, or
+ * add_values = NULL with SRLX_PRIO_NONE) are applied inside the sampling launch, in order, exactly like srlx_per_add would; uniforms in and results out travel through a
+ * device-visible pinned slot and the host spins on a completion flag the kernel stores last (no stream synchronisation).  batch_size <= n_uniforms <= 8192; a draw
+ * whose uniforms and results do not fit one 16 KB slot (pad(8 n_uniforms) + 2 pad(8 batch_size) + pad(4 batch_size) + 512 bytes, pad rounding up to 256: up
+ * to batch_size = 544 when n_uniforms = batch_size) takes srlx_per_add + srlx_per_sample(on_device = 0) instead, with the same results.  More adds than
+ * min(16, capacity) is SRLX_ERR_INVALID, before anything runs.  Host pointers; results as srlx_per_sample(on_device = 0); SRLX_OK and
+ * SRLX_ERR_UNIFORMS_EXHAUSTED both mean the adds were applied. */
 int srlx_per_sample_after_adds(srlx_per_t *h, int64_t n_add, const double *add_values, int add_kind, int64_t batch_size, int64_t step, const double *uniforms,
                                int64_t n_uniforms, int64_t *out_idx, double *out_w, float *out_w32, int64_t *out_used, void *stream);
 /* The same with the uniforms given as consecutive MT19937 outputs, two 32-bit words per uniform -- what `random.getrandbits(64 * n).to_bytes(8 * n, "little")` yields
  * and `random.random()` would have consumed (CPython: (a >> 5) * 2^26 + (b >> 6)) / 2^53 of consecutive outputs a, b): the host shim hands the generator's raw
- * words over instead of building n Python floats.  out_slots (or NULL): the data slot of every index (tree index - (capacity - 1)). */
+ * words over instead of building n Python floats.  Any batch_size <= n_uniforms <= 8192, inside a slot or not; same limits on the adds.  out_slots (or NULL): the
+ * data slot of every index (tree index - (capacity - 1)). */
 int srlx_per_sample_after_adds_mt(srlx_per_t *h, int64_t n_add, const double *add_values, int add_kind, int64_t batch_size, int64_t step,
                                   const uint32_t *mt_words, int64_t n_uniforms, int64_t *out_idx, double *out_w, float *out_w32,
                                   int64_t *out_used, int64_t *out_slots, void *stream);

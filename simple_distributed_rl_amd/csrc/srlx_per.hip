@@ -27,8 +27,10 @@
 //   per_sample : (depth+1)*8 B tree reads + 8 B uniform + 16 B out per draw  -> HBM/L2 bound
 //   per_update : 16 B leaf R/W + depth*16 B ancestor RMW per index           -> latency bound at B=32
 //   per_add    : same as update + 8 B priority                               -> root chain (n fp64 adds)
+#include <atomic>
 #include <new>
 #include <type_traits>
+#include <vector>
 
 #include "srlx_common.h"
 #include "srlx_store_dev.h"
@@ -1732,6 +1734,8 @@ static int sample_after_adds_impl(srlx_per_t *h, int64_t n_add, const double *ad
     SRLX_REQUIRE(h, "per_sample_after_adds: NULL handle");
     SRLX_REQUIRE(n_add >= 0 && n_add <= kTinyAddMax && (n_add == 0 || add_kind == SRLX_PRIO_NONE || (add_kind == SRLX_PRIO_RAW && add_values)),
                  "per_sample_after_adds: at most %d adds, SRLX_PRIO_RAW values or SRLX_PRIO_NONE", kTinyAddMax);
+    // (srlx_per_add's rule: the one-wave add writes each leaf once, and its write position wraps once)
+    SRLX_REQUIRE(n_add <= h->capacity, "per_sample_after_adds: n_add=%lld must not exceed capacity=%lld", (long long)n_add, (long long)h->capacity);
     SRLX_REQUIRE(batch_size > 0 && (uniforms || mt_words) && n_uniforms >= batch_size && n_uniforms <= kSmallSampleMax && out_idx && out_used,
                  "per_sample_after_adds: batch_size <= n_uniforms <= %lld", (long long)kSmallSampleMax);
     srlx::DeviceGuard guard(h->device);
@@ -1742,9 +1746,17 @@ static int sample_after_adds_impl(srlx_per_t *h, int64_t n_add, const double *ad
     int slot = 0;
     SRLX_TRY(ring_acquire(h, need, &slot_ptr, &slot));
     if (!slot_ptr) {  // does not fit a slot: the plain calls
-        SRLX_REQUIRE(uniforms && !out_slots, "per_sample_after_adds_mt: the draw does not fit a pinned slot");
+        std::vector<double> u_mt;
+        if (!uniforms) {  // the words as doubles, with the slot path's formula below
+            u_mt.resize((size_t)n_uniforms);
+            for (i64 j = 0; j < n_uniforms; j++) u_mt[j] = ((double)(mt_words[2 * j] >> 5) * 67108864.0 + (double)(mt_words[2 * j + 1] >> 6)) * (1.0 / 9007199254740992.0);
+            uniforms = u_mt.data();
+        }
         if (n_add > 0) SRLX_TRY(srlx_per_add(h, n_add, add_values, add_kind, 0, stream));
-        return srlx_per_sample(h, batch_size, step, nullptr, uniforms, n_uniforms, out_idx, out_w, out_w32, out_used, 0, stream);
+        const int st_sample = srlx_per_sample(h, batch_size, step, nullptr, uniforms, n_uniforms, out_idx, out_w, out_w32, out_used, 0, stream);
+        if (st_sample == SRLX_OK && out_slots)
+            for (i64 j = 0; j < batch_size; j++) out_slots[j] = out_idx[j] - (h->capacity - 1);
+        return st_sample;
     }
     C sp(slot_ptr);
     double *m_u = sp.take<double>(n_uniforms);
@@ -1757,8 +1769,8 @@ static int sample_after_adds_impl(srlx_per_t *h, int64_t n_add, const double *ad
         memcpy(m_u, uniforms, (size_t)n_uniforms * 8);
     else  // CPython's random.random() (Modules/_randommodule.c: random_random) on consecutive MT19937 outputs
         for (i64 j = 0; j < n_uniforms; j++) m_u[j] = ((double)(mt_words[2 * j] >> 5) * 67108864.0 + (double)(mt_words[2 * j + 1] >> 6)) * (1.0 / 9007199254740992.0);
-    static unsigned long long ticket = 0;
-    const unsigned long long want = ++ticket;
+    static std::atomic<unsigned long long> ticket{0};  // (separate handles may sample from separate threads)
+    const unsigned long long want = ticket.fetch_add(1, std::memory_order_relaxed) + 1;
     *m_flag = 0;
     const i64 M = n_uniforms, B = batch_size;
     SRLX_TRY(h->scratch.reserve(SampleScratch::bytes(M, B, false)));

@@ -78,6 +78,7 @@ class ProportionalMemory(IPriorityMemory):
         self._write = 0
         self._queue: List[float] = []  # values of queued adds (one priority kind per run)
         self._queue_kind = None
+        self._queue_in_launch = min(16, self.capacity)  # queued adds one sampling launch applies (srlx_per_sample_after_adds: n_add <= min(16, capacity))
         self._max_host = 1.0  # mirror of max_priority (exact while host_transform: every value that can raise it passes through `update` here)
 
     def __del__(self):
@@ -149,11 +150,13 @@ class ProportionalMemory(IPriorityMemory):
         batch_size = int(batch_size)
         idx, w, slots, used, p_idx, p_w, p_slots, p_used = self._buffers(batch_size)
         with self._lock:
-            # up to 16 queued adds of one kind ride INSIDE the sampling launch (srlx_per_sample_after_adds); a longer queue is flushed by a launch of its own first
+            # up to min(16, capacity) queued adds of one kind ride INSIDE the sampling launch (srlx_per_sample_after_adds); a longer queue is flushed by a launch of
+            # its own first, and so is any queue when the batch is larger than that launch draws
             q_kind = self._queue_kind
-            if len(self._queue) > 16 or (self._queue and q_kind not in (N.PRIO_RAW, N.PRIO_NONE)):
+            if len(self._queue) > self._queue_in_launch or (self._queue and q_kind not in (N.PRIO_RAW, N.PRIO_NONE)) or batch_size > 8192:
                 self._flush()
-            adds, self._queue, self._queue_kind = self._queue, [], None
+                q_kind = None
+            adds = self._queue
             add_arr = array("d", adds) if (adds and q_kind == N.PRIO_RAW) else None
             add_ptr = add_arr.buffer_info()[0] if add_arr is not None else None
             # Uniforms: the reference calls random.random() once per descent attempt (:147).  Without rejected draws a batch consumes exactly `batch_size` of them: the
@@ -167,17 +170,19 @@ class ProportionalMemory(IPriorityMemory):
                 raw = random.getrandbits(64 * batch_size).to_bytes(8 * batch_size, "little")
                 st = self._lib.srlx_per_sample_after_adds_mt(self._h, len(adds), add_ptr, q_kind if adds else N.PRIO_NONE, batch_size, int(step), raw, batch_size, p_idx, p_w,
                                                              None, p_used, p_slots, None)
-                adds = []  # (applied by the first attempt, whatever the draw's outcome)
+                if st != N.OK and st != N.ERR_UNIFORMS_EXHAUSTED:
+                    N.check(st)  # the call did not run: the queue stays as it is
+                self._queue, self._queue_kind = [], None  # (applied by the first attempt, whatever the draw's outcome)
             if st != N.OK:
-                self._sample_slow(batch_size, step, raw, adds, add_arr, q_kind, idx, w, used)
+                self._sample_slow(batch_size, step, raw, idx, w, used)
                 np.subtract(idx, self.capacity - 1, out=slots)
             data = self.data
             indices = idx.tolist()
             batches = [data[i] for i in slots.tolist()]
         return batches, w.copy(), indices
 
-    def _sample_slow(self, batch_size, step, raw, adds, add_arr, q_kind, idx, w, used):
-        """Rejected draws ate the first attempt's uniforms (or the batch is larger than one sampling launch takes): the list-based loop (lock held)."""
+    def _sample_slow(self, batch_size, step, raw, idx, w, used):
+        """Rejected draws ate the first attempt's uniforms (or the batch is larger than one sampling launch takes): the list-based loop (lock held, queue empty)."""
         cap = 8192 if not self.has_duplicate else 9999 * batch_size  # without duplicates one call walks at most 8192 uniforms
         if raw is not None:  # the uniforms the first attempt consumed: random.random() of consecutive generator outputs (a >> 5, b >> 6)
             wd = np.frombuffer(raw, dtype="<u4")
@@ -188,18 +193,13 @@ class ProportionalMemory(IPriorityMemory):
             drawn = [random.random() for _ in range(batch_size)]
             state, base = None, 0  # state: the generator AFTER `base` of the drawn uniforms
         forced = False
-        add_np = np.asarray(add_arr, np.float64) if add_arr is not None else None
         while True:
             m = len(drawn)
             u = np.asarray(drawn, np.float64)
             if m <= 8192:
-                st = self._lib.srlx_per_sample_after_adds(self._h, len(adds), N.np_ptr(add_np) if (adds and add_np is not None) else None, q_kind if adds else N.PRIO_NONE,
-                                                          batch_size, int(step), N.np_ptr(u), m, N.np_ptr(idx), N.np_ptr(w), None, ctypes.byref(used), None)
-                adds = []
+                st = self._lib.srlx_per_sample_after_adds(self._h, 0, None, N.PRIO_NONE, batch_size, int(step), N.np_ptr(u), m, N.np_ptr(idx), N.np_ptr(w), None,
+                                                          ctypes.byref(used), None)
             else:
-                if adds:
-                    N.check(self._lib.srlx_per_add(self._h, len(adds), N.np_ptr(add_np) if add_np is not None else None, q_kind, 2, None))
-                    adds = []
                 st = self._lib.srlx_per_sample(self._h, batch_size, int(step), None, N.np_ptr(u), m, N.np_ptr(idx), N.np_ptr(w), None, ctypes.byref(used), 2, None)
             if st == N.ERR_UNIFORMS_EXHAUSTED and m < cap:  # rejected draws ate the uniforms: again with more (the same prefix: the same walk up to there)
                 state, base = random.getstate(), m
