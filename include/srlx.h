@@ -564,7 +564,12 @@ int srlx_store_gather_obs(srlx_store_t *h, int64_t batch, int k_begin, int k_cou
  * (srl/rl/torch_/blocks/dueling_network.py:8-59) behind pred_q / pred_target_q
  * (srl/algorithms/rainbow/model_torch.py:55-67) -- for the actor's policy step and the
  * learner's online/target evaluation of s_1..s_n.
- *   dueling_type: 0 "average", 1 "max", 2 "" (naive)
+ *   dueling_type: 0 "average", 1 "max", 2 "" (naive), 3 no dueling -- DQN's plain head q = W2 relu(h) + b2
+ *   (srl/algorithms/dqn/model_torch.py:17-29) over ALL 2*hidden units of the first dense layer (a DQN layer of width W is
+ *   a handle with hidden = W / 2).  With 3 the a2 entries of srlx_qnet_bind carry W2 [A][2*hidden] and b2 [A], and the
+ *   v2 entries are not read (bind any valid pointer; their gradient buffers are not written, their packed ranges are empty).
+ *   The published sets, the fused policy, srlx_qnet_backward_u8 / _td_u8 and the fused Adam serve it; srlx_qnet_bind_uvfa,
+ *   srlx_qnet_bind_noisy and srlx_qnet_set_head_mode(h, 1, ...) refuse it.
  *   srlx_qnet_bind: 12 device pointers to float32 parameters that the kernels read IN PLACE (no copy;
  *   they must stay valid and may be updated between calls):
  *     conv1.weight [F][window][8][8]      conv1.bias

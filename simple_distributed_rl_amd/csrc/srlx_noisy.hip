@@ -110,6 +110,7 @@ extern "C" {
 int srlx_qnet_bind_noisy(srlx_qnet_t *h, const float *const *d_sigma, uint64_t seed) {
     SRLX_REQUIRE(h && d_sigma, "qnet_bind_noisy: NULL argument");
     SRLX_REQUIRE(h->w1, "qnet_bind_noisy: bind the parameters first (srlx_qnet_bind: the dense-layer entries are the mu tensors)");
+    SRLX_REQUIRE(h->dueling != kHeadPlain, "qnet_bind_noisy: the plain Q head (dueling_type 3) has no NoisyLinear form");
     for (int t = 0; t < 6; t++) SRLX_REQUIRE(d_sigma[t], "qnet_bind_noisy: sigma %d is NULL", t);
     srlx::DeviceGuard guard(h->device);
     const int N1 = 2 * h->hidden;

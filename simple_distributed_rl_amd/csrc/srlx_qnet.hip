@@ -510,6 +510,42 @@ __global__ void __launch_bounds__(256) k_gemm_s16(AL al, const float *__restrict
         }
 }
 
+// ---- the batched Worker.policy step's selection (rainbow.py:301-329), fused into a head kernel: epsilon-greedy on the Q row thread 0 of row m's workgroup
+//      has just finished (out[0..A)), with the two uniforms srlx_rng_uniform(seed, counter, 2 E) would have written for the row (u[2 m], u[2 m + 1]);
+//      arithmetic = k_eps_greedy (srlx_rollout.hip).  The counter is only READ here (one workgroup per row): the caller advances it once per pass, in a later launch.
+template <int AMAX>
+__device__ __forceinline__ void fused_policy(const srlx_qnet::Policy &pol, i64 m, int A, const float (&out)[AMAX]) {
+    if (pol.actions) {
+        const unsigned long long c = (unsigned long long)pol.counter[0];
+        const unsigned char *inv = pol.invalid ? pol.invalid + m * A : nullptr;
+        int act = 0;
+        if (srlx::u53(srlx::rng_u64(pol.seed, c, (unsigned long long)(2 * m))) < (double)pol.eps[m]) {  // random.random() < epsilon (:317)
+            int nv = 0;
+            for (int a = 0; a < A; a++) nv += !(inv && inv[a]);
+            int pick = (int)(srlx::u53(srlx::rng_u64(pol.seed, c, (unsigned long long)(2 * m + 1))) * (double)nv);
+            if (pick >= nv) pick = nv - 1;
+            for (int a = 0; a < A; a++) {
+                if (inv && inv[a]) continue;
+                if (pick == 0) {
+                    act = a;
+                    break;
+                }
+                pick--;
+            }
+        } else {  // q[invalid] = -inf; first maximum, like np.argmax (:321-325)
+            float bv = -INFINITY;
+            bool have = false;
+#pragma unroll
+            for (int a = 0; a < AMAX; a++)
+                if (a < A) {
+                    const float x = (inv && inv[a]) ? -INFINITY : out[a];
+                    if (!have || x > bv) act = a, bv = x, have = true;
+                }
+        }
+        pol.actions[m] = act;
+    }
+}
+
 // ---- head: reduce FC1 splits (+bias, ReLU), second layers, dueling combine; one workgroup per sample ----
 constexpr int kMaxActions = 32;
 // AMAX = 8 / 16 / 32 >= A (round 5: with the loops over kMaxActions = 32 and a run-time A, every one of the accumulate / shuffle / store loops carried 32 uniform
@@ -642,38 +678,71 @@ __global__ void __launch_bounds__(512) k_head(const float *__restrict__ partial,
                 q[mo * A + j] = out[j];
                 if (pol.q_copy) pol.q_copy[mo * A + j] = out[j];
             }
-        // ---- the batched Worker.policy step's selection (rainbow.py:301-329), fused: epsilon-greedy on the Q row this thread has just finished, with the two
-        //      uniforms srlx_rng_uniform(seed, counter, 2 E) would have written for the row (u[2 e], u[2 e + 1]); arithmetic = k_eps_greedy (srlx_rollout.hip).
-        //      The counter is only READ here (one workgroup per row): the caller advances it once per pass, in a later launch.
-        if (pol.actions) {
-            const unsigned long long c = (unsigned long long)pol.counter[0];
-            const unsigned char *inv = pol.invalid ? pol.invalid + m * A : nullptr;
-            int act = 0;
-            if (srlx::u53(srlx::rng_u64(pol.seed, c, (unsigned long long)(2 * m))) < (double)pol.eps[m]) {  // random.random() < epsilon (:317)
-                int nv = 0;
-                for (int a = 0; a < A; a++) nv += !(inv && inv[a]);
-                int pick = (int)(srlx::u53(srlx::rng_u64(pol.seed, c, (unsigned long long)(2 * m + 1))) * (double)nv);
-                if (pick >= nv) pick = nv - 1;
-                for (int a = 0; a < A; a++) {
-                    if (inv && inv[a]) continue;
-                    if (pick == 0) {
-                        act = a;
-                        break;
-                    }
-                    pick--;
-                }
-            } else {  // q[invalid] = -inf; first maximum, like np.argmax (:321-325)
-                float bv = -INFINITY;
-                bool have = false;
+        fused_policy<AMAX>(pol, m, A, out);
+    }
+}
+
+// ---- the plain head (dueling_type kHeadPlain): DQN's out_layer over all N1 = 2 hidden units (srl/algorithms/dqn/model_torch.py:17-29) ----
+// One workgroup per row, like k_head: the split sums of every unit in a fixed order (chain c takes splits c, c + 8, c + 16, ... -- what k_head's chains take),
+// + bias, ReLU -> h1 (training), then q[j] = b2[j] + sum_u W2[j][u] h[u] in a fixed order (per thread over its units, lanes by xor-shuffle, waves in wave order),
+// and the same fused epsilon-greedy selection.  W2 = the binding's a2w entry [A][N1], b2 = a2b [A].
+template <int AMAX>
+__global__ void __launch_bounds__(512) k_head_plain(const float *__restrict__ partial, int splits, i64 M, int N1, const float *__restrict__ b1,
+                                                    const float *__restrict__ w2, const float *__restrict__ b2, int A, float *__restrict__ q,
+                                                    float *__restrict__ h1, i64 ostride, srlx_qnet::Policy pol) {
+    __shared__ float red[8][kMaxActions];  // one row per wave (256 or 512 threads)
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const i64 m = blockIdx.x, mo = m * ostride;
+    float acc[AMAX];
 #pragma unroll
-                for (int a = 0; a < AMAX; a++)
-                    if (a < A) {
-                        const float x = (inv && inv[a]) ? -INFINITY : out[a];
-                        if (!have || x > bv) act = a, bv = x, have = true;
-                    }
+    for (int j = 0; j < AMAX; j++) acc[j] = 0.f;
+    const i64 ss = M * N1;
+    for (int u = t; u < N1; u += blockDim.x) {
+        const float *p = partial + m * N1 + u;
+        float c8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int s = 0;
+        for (; s + 8 <= splits; s += 8)
+#pragma unroll
+            for (int c = 0; c < 8; c++) c8[c] += p[(s + c) * ss];
+#pragma unroll
+        for (int c = 0; c < 8; c++)  // the remainder (chain c takes split s + c; constant indices keep c8 in registers)
+            if (s + c < splits) c8[c] += p[(s + c) * ss];
+        float hv = b1[u] + (((c8[0] + c8[1]) + (c8[2] + c8[3])) + ((c8[4] + c8[5]) + (c8[6] + c8[7])));
+        hv = hv > 0.f ? hv : 0.f;
+        if (h1) h1[mo * N1 + u] = hv;  // training: the backward pass needs the hidden layer
+        int wi = u;  // W2[j][u], walked down the column (a per-lane index: no uniform row offset per action held in scalar registers)
+#pragma unroll
+        for (int j = 0; j < AMAX; j++)
+            if (j < A) acc[j] += hv * w2[wi], wi += N1;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int j = 0; j < AMAX; j++)
+            if (j < A) acc[j] += __shfl_xor(acc[j], off);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < AMAX; j++)
+            if (j < A) red[wave][j] = acc[j];
+    __syncthreads();
+    if (wave != 0) return;
+    // lane j < A sums column j over the waves in wave order; thread 0 collects the row through the wave's registers
+    const int nwaves = blockDim.x >> 6;
+    float colsum = 0.f;
+    if (lane < A)
+        for (int w = 0; w < nwaves; w++) colsum += red[w][lane];
+    float out[AMAX];
+#pragma unroll
+    for (int j = 0; j < AMAX; j++) out[j] = j < A ? __shfl(colsum, j) : 0.f;
+    if (t == 0) {
+#pragma unroll
+        for (int j = 0; j < AMAX; j++)
+            if (j < A) {
+                out[j] = out[j] + b2[j];
+                q[mo * A + j] = out[j];
+                if (pol.q_copy) pol.q_copy[mo * A + j] = out[j];
             }
-            pol.actions[m] = act;
-        }
+        fused_policy<AMAX>(pol, m, A, out);
     }
 }
 
@@ -895,7 +964,15 @@ int srlx_qnet_dense_rows(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hi
                  "qnet_forward: a UVFA network needs its per-row inputs (srlx_qnet_set_uvfa_inputs)");
     if (h->head_mode == 1)  // the handle ends behind the first dense layer: d_q is the hidden layer's first out_cols units (+ LayerNorm)
         hipLaunchKernelGGL(k_hidden_out, hgrid, dim3(256), 0, st, h->partial, used, Mp, N1, h->bf, d_q, h->out_cols, h->h1, (i64)stride, h->ln_w, h->ln_b, h->ln_eps);
-    else if (h->A <= 8)
+    else if (h->dueling == kHeadPlain) {  // DQN's plain head over all N1 units (no NoisyLinear, no UVFA columns: refused where they are bound)
+        const dim3 pblock(B <= 256 && N1 > 256 ? 512 : 256);
+        if (h->A <= 8)
+            hipLaunchKernelGGL(k_head_plain<8>, hgrid, pblock, 0, st, h->partial, used, Mp, N1, h->bf, h->a2w, h->a2b, h->A, d_q, h->h1, (i64)stride, h->pol);
+        else if (h->A <= 16)
+            hipLaunchKernelGGL(k_head_plain<16>, hgrid, pblock, 0, st, h->partial, used, Mp, N1, h->bf, h->a2w, h->a2b, h->A, d_q, h->h1, (i64)stride, h->pol);
+        else
+            hipLaunchKernelGGL(k_head_plain<32>, hgrid, pblock, 0, st, h->partial, used, Mp, N1, h->bf, h->a2w, h->a2b, h->A, d_q, h->h1, (i64)stride, h->pol);
+    } else if (h->A <= 8)
         hipLaunchKernelGGL(k_head<8>, hgrid, hblock, 0, st, h->partial, used, Mp, h->hidden, h->bf, h->v2w, h->v2b, h->a2w, h->a2b, h->A, h->dueling, d_q, h->h1, (i64)stride, hdraw, h->pol, uv);
     else if (h->A <= 16)
         hipLaunchKernelGGL(k_head<16>, hgrid, hblock, 0, st, h->partial, used, Mp, h->hidden, h->bf, h->v2w, h->v2b, h->a2w, h->a2b, h->A, h->dueling, d_q, h->h1, (i64)stride, hdraw, h->pol, uv);
@@ -942,6 +1019,7 @@ int srlx_qnet_create(srlx_qnet_t **out, int in_h, int in_w, int window, int filt
                  "qnet_create: unsupported shape (filters and hidden must be multiples of 32, n_actions <= %d)", kMaxActions);
     SRLX_REQUIRE((window * 64) % BK == 0, "qnet_create: window*64 must be a multiple of %d", BK);
     SRLX_REQUIRE(filters == 32 || filters == 64 || filters == 128, "qnet_create: filters must be 32, 64 or 128 (channel counts are powers of two, <= 80 K-slabs)");
+    SRLX_REQUIRE(dueling_type >= 0 && dueling_type <= kHeadPlain, "qnet_create: dueling_type 0 (average), 1 (max), 2 (naive) or 3 (plain Q head, no dueling)");
     int ndev = 0;
     SRLX_HIP(hipGetDeviceCount(&ndev));
     SRLX_REQUIRE(device >= 0 && device < ndev, "qnet_create: device %d not present", device);
@@ -1281,6 +1359,7 @@ int srlx_qnet_bind_uvfa(srlx_qnet_t *h, const float *d_wx, int n_cols, int col_e
     SRLX_REQUIRE(h->uvfa.X == 0 || h->uvfa.X == n_cols, "qnet_bind_uvfa: the column count of a handle is fixed by its first binding");
     SRLX_REQUIRE(h->uvfa.X == n_cols || !h->aset[0].small, "qnet_bind_uvfa: bind before srlx_qnet_actor_sets_enable (the sets hold a copy of the columns)");
     SRLX_REQUIRE(!h->eff[0] && h->head_mode == 0, "qnet_bind_uvfa: plain dueling handles only");
+    SRLX_REQUIRE(h->dueling != kHeadPlain, "qnet_bind_uvfa: the plain Q head (dueling_type 3) takes no UVFA columns");
     auto ok = [&](int c, int n) { return c < 0 || (n > 0 && c + n <= n_cols); };
     SRLX_REQUIRE(ok(col_ext, 1) && ok(col_int, 1) && ok(col_action, n_action_in) && ok(col_actor, n_actor), "qnet_bind_uvfa: a column range leaves the matrix");
     srlx_qnet::Uvfa &u = h->uvfa;
@@ -1313,6 +1392,7 @@ int srlx_qnet_set_head_mode(srlx_qnet_t *h, int mode, int out_cols, const float 
     SRLX_REQUIRE(h && (mode == 0 || mode == 1), "qnet_set_head_mode: mode 0 (dueling head) or 1 (hidden layer out)");
     SRLX_REQUIRE(mode == 0 || (out_cols > 0 && out_cols <= 2 * h->hidden && 2 * h->hidden <= 1024 && !h->eff[0] && h->uvfa.X == 0),
                  "qnet_set_head_mode: 1 <= out_cols <= 2 * hidden <= 1024, plain layers");
+    SRLX_REQUIRE(mode == 0 || h->dueling != kHeadPlain, "qnet_set_head_mode: a plain-Q-head handle (dueling_type 3) has no hidden-layer mode");
     SRLX_REQUIRE(!d_ln_w == !d_ln_b, "qnet_set_head_mode: LayerNorm needs weight and bias");
     h->head_mode = mode, h->out_cols = out_cols, h->ln_w = d_ln_w, h->ln_b = d_ln_b, h->ln_eps = (float)ln_eps;
     return SRLX_OK;

@@ -159,6 +159,83 @@ __global__ void __launch_bounds__(256) k_uvfa_wgrad(int B, i64 sstride, int N1, 
 }
 
 // ---- head_mode 1: the gradient arrives at the post-ReLU hidden layer's first out_cols units, g [B][out_cols] (the other units of a padded layer get none):
+// ---- the plain head (dueling_type kHeadPlain: DQN's out_layer, srl/algorithms/dqn/model_torch.py:17-29) ------------------------------------
+// q = W2 relu(h) + b2 over all N1 units.  Same decomposition as k_head_bwd -- 64 units per workgroup x 4 sample slices, slice sums combined in slice order --:
+// g_W2[j][u] = sum_b dq[b][j] h[b][u], g_b2[j] = sum_b dq[b][j] (workgroup 0, batch order), dh1 = (dq W2) * 1[h > 0] into the buffers the first dense layer's
+// weight / data gradients read, and the bias gradient of that layer.  with_td: d loss / d Q from the TD prologue k_head_bwd runs (srlx::td_rows).
+template <int AMAX>
+__global__ void __launch_bounds__(256) k_head_plain_bwd(int B, i64 sstride, int N1, int A, const float *__restrict__ dq, const float *__restrict__ h1,
+                                                         const float *__restrict__ w2, float *__restrict__ dh1, float *__restrict__ dh1t /*[N1][32] or NULL*/,
+                                                         float *__restrict__ g_bf, float *__restrict__ g_w2, float *__restrict__ g_b2, srlx::TdArgs td, int with_td) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];  // part[1 + AMAX][256], dq[B][A] (+ with_td: 256 doubles)
+    float *part = sm, *sdq = sm + (1 + AMAX) * 256;
+    const int t = threadIdx.x;
+    if (with_td) {
+        int off = (1 + AMAX) * 256 + B * A;
+        off += off & 1;
+        double *red = reinterpret_cast<double *>(sm + off);
+        const double la = srlx::td_rows(td, t, 256, sdq, blockIdx.x == 0);
+        if (blockIdx.x == 0) {
+            red[t] = la;
+            __syncthreads();
+            for (int s = 128; s > 0; s >>= 1) {
+                if (t < s) red[t] += red[t + s];
+                __syncthreads();
+            }
+            if (t == 0) td.loss[0] = (float)(red[0] / (double)td.B);
+        }
+    } else {
+        for (int i = t; i < B * A; i += 256) sdq[i] = dq[i];
+    }
+    __syncthreads();
+    const int ul = t & 63, slice = t >> 6;
+    const int u = blockIdx.x * 64 + ul;
+    float gb = 0.f, ga[AMAX];
+#pragma unroll
+    for (int j = 0; j < AMAX; j++) ga[j] = 0.f;
+    if (u < N1) {
+        float wa[AMAX];
+#pragma unroll
+        for (int j = 0; j < AMAX; j++) wa[j] = j < A ? w2[(i64)j * N1 + u] : 0.f;
+#pragma unroll 4
+        for (int b = slice; b < B; b += 4) {
+            const float hv = h1[(i64)b * sstride * N1 + u];
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < AMAX; j++)
+                if (j < A) {
+                    const float d = sdq[b * A + j];
+                    ga[j] += d * hv;
+                    s += d * wa[j];
+                }
+            const float dh = hv > 0.f ? s : 0.f;  // ReLU of the first dense layer
+            dh1[(i64)b * N1 + u] = dh;
+            if (dh1t) dh1t[u * 32 + b] = dh;
+            gb += dh;
+        }
+        if (dh1t)  // the matrix-core data gradient multiplies whole 32-sample tiles: absent samples contribute zeros
+            for (int b = slice; b < 32; b += 4)
+                if (b >= B) dh1t[u * 32 + b] = 0.f;
+    }
+    part[t] = gb;
+#pragma unroll
+    for (int j = 0; j < AMAX; j++)
+        if (j < A) part[(1 + j) * 256 + t] = ga[j];
+    __syncthreads();
+    if (slice == 0 && u < N1) {
+        auto sum4 = [&](int row) { return ((part[row * 256 + ul] + part[row * 256 + 64 + ul]) + part[row * 256 + 128 + ul]) + part[row * 256 + 192 + ul]; };
+        g_bf[u] = sum4(0);
+#pragma unroll
+        for (int j = 0; j < AMAX; j++)
+            if (j < A) g_w2[(i64)j * N1 + u] = sum4(1 + j);
+    }
+    if (blockIdx.x == 0 && t < A) {
+        float s = 0.f;
+        for (int b = 0; b < B; b++) s += sdq[b * A + t];
+        g_b2[t] = s;
+    }
+}
+
 // dh1 = g masked by the ReLU, its transpose for the matrix-core data gradient, and the bias gradient (batch in slice order, as k_head_bwd) -------------------
 __global__ void __launch_bounds__(256) k_hidden_bwd(int B, i64 sstride, int N1, int out_cols, const float *__restrict__ g, const float *__restrict__ h1,
                                                     float *__restrict__ dh1, float *__restrict__ dh1t, float *__restrict__ g_bf) {
@@ -678,7 +755,7 @@ int srlx_qnet_enable_training(srlx_qnet_t *h, int64_t max_train_batch) {
     SRLX_REQUIRE(max_train_batch > 0 && max_train_batch <= 64 && max_train_batch <= h->max_batch, "qnet_enable_training: 1 <= max_train_batch <= 64");
     SRLX_REQUIRE(h->F1 == 32 && h->dueling != 1 && h->H == h->W && h->W % 4 == 0 && (2 * h->hidden) % kFcSplits == 0 &&
                      2 * h->hidden / kFcSplits <= 64 && 4 * (h->OH1 - 1) + 8 <= kC1Pad,
-                 "qnet_enable_training: the backward kernels cover the DQN image block with 32 filters, square frames, hidden <= 512, dueling average / none");
+                 "qnet_enable_training: the backward kernels cover the DQN image block with 32 filters, square frames, hidden <= 512, dueling average / none or the plain head");
     if (h->max_train >= max_train_batch) return SRLX_OK;
     SRLX_REQUIRE(h->max_train == 0, "qnet_enable_training: already enabled with a smaller batch");
     srlx::DeviceGuard guard(h->device);
@@ -929,6 +1006,19 @@ static int backward_impl(srlx_qnet_t *h, int64_t batch, int64_t sample_stride, c
     if (h->head_mode == 1) {  // the handle ends behind the first dense layer: d_grad_q is the gradient at its first out_cols post-ReLU units
         SRLX_REQUIRE(!td && !h->ln_w, "qnet_backward_u8: a hidden-layer handle takes the gradient of its output (no TD prologue, no LayerNorm inside)");
         hipLaunchKernelGGL(k_hidden_bwd, dim3((unsigned)((N1 + 63) / 64)), dim3(256), 0, st, B, ss, N1, h->out_cols, d_grad_q, h->h1, h->dh1, mfma_dgrad ? h->dh1t : nullptr, g_bf);
+    } else if (h->dueling == kHeadPlain) {  // DQN's plain head: W2 / b2 are the a2w / a2b entries, v2w / v2b's gradients are not written
+        const int amax = A <= 8 ? 8 : (A <= 16 ? 16 : 32);
+        const size_t hl = (size_t)((1 + amax) * 256 + B * A + 2 + (td ? 512 : 0)) * sizeof(float);
+        float *dh1t = mfma_dgrad ? h->dh1t : nullptr;
+        const srlx::TdArgs tda = td ? *td : srlx::TdArgs{};
+        const int with_td = td ? 1 : 0;
+        const dim3 hg((unsigned)((N1 + 63) / 64));
+        if (A <= 8)
+            hipLaunchKernelGGL(k_head_plain_bwd<8>, hg, dim3(256), hl, st, B, ss, N1, A, d_grad_q, h->h1, h->a2w, h->dh1, dh1t, g_bf, g_a2w, g_a2b, tda, with_td);
+        else if (A <= 16)
+            hipLaunchKernelGGL(k_head_plain_bwd<16>, hg, dim3(256), hl, st, B, ss, N1, A, d_grad_q, h->h1, h->a2w, h->dh1, dh1t, g_bf, g_a2w, g_a2b, tda, with_td);
+        else
+            hipLaunchKernelGGL(k_head_plain_bwd<32>, hg, dim3(256), hl, st, B, ss, N1, A, d_grad_q, h->h1, h->a2w, h->dh1, dh1t, g_bf, g_a2w, g_a2b, tda, with_td);
     } else {
         const dim3 hg((unsigned)((h->hidden + 63) / 64));
         const size_t hl = (size_t)(B + B * A + (3 + (A <= 8 ? 8 : (A <= 16 ? 16 : 32))) * 256 + (td ? B * A + 2 + 512 : 0)) * sizeof(float);

@@ -921,7 +921,9 @@ int srlx_qnet_pack_publish(srlx_qnet *src, srlx_qnet::ActorSet *dst_set, const s
         const float *v[kSmallVecs] = {b ? b[1] : src->b1, b ? b[3] : src->b2, b ? b[5] : src->b3, b ? b[7] : src->bf, b ? b[8] : src->v2w, b ? b[9] : src->v2b,
                                       b ? b[10] : src->a2w, b ? b[11] : src->a2b, src->uvfa.wx_bound};
         const int off[kSmallVecs + 1] = {L->b1, L->b2, L->b3, L->bf, L->v2w, L->v2b, L->a2w, L->a2b, L->wx, L->total};
-        const int len[kSmallVecs] = {src->F1, 2 * src->F1, 2 * src->F1, 2 * src->hidden, src->hidden, 1, src->A * src->hidden, src->A, src->uvfa.X * 2 * src->hidden};
+        const bool plain = src->dueling == kHeadPlain;  // (v2w / v2b absent: zero-length ranges)
+        const int len[kSmallVecs] = {src->F1, 2 * src->F1, 2 * src->F1, 2 * src->hidden, plain ? 0 : src->hidden, plain ? 0 : 1,
+                                     src->A * (plain ? 2 : 1) * src->hidden, src->A, src->uvfa.X * 2 * src->hidden};
         for (int k = 0; k < kSmallVecs; k++) sm.src[k] = v[k], sm.len[k] = len[k];
         for (int k = 0; k <= kSmallVecs; k++) sm.off[k] = off[k];
         sm.dst = dst_set ? dst_set->small : nullptr;

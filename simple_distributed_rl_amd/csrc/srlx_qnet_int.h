@@ -2,6 +2,10 @@
 #pragma once
 #include "srlx_common.h"
 
+// dueling_type kHeadPlain (srlx_qnet_create): no dueling split -- DQN's plain head q = W2 relu(h) + b2 (srl/algorithms/dqn/model_torch.py:17-29) over all
+// N1 = 2 hidden units of the first dense layer; the a2w / a2b entries of the binding carry W2 [A][N1] and b2 [A], v2w / v2b are not read
+constexpr int kHeadPlain = 3;
+
 struct srlx_qnet {
     int device;
     int H, W, Wn, F1, hidden, A, dueling;
@@ -151,9 +155,10 @@ inline srlx_small_layout srlx_small_offsets(const srlx_qnet *h) {
     L.b3 = L.b2 + pad(2 * h->F1);
     L.bf = L.b3 + pad(2 * h->F1);
     L.v2w = L.bf + pad(2 * h->hidden);
-    L.v2b = L.v2w + pad(h->hidden);
-    L.a2w = L.v2b + 4;
-    L.a2b = L.a2w + pad(h->A * h->hidden);
+    const bool plain = h->dueling == kHeadPlain;  // (no value stream; the head's weight spans all 2 hidden units)
+    L.v2b = L.v2w + (plain ? 0 : pad(h->hidden));
+    L.a2w = L.v2b + (plain ? 0 : 4);
+    L.a2b = L.a2w + pad(h->A * (plain ? 2 : 1) * h->hidden);
     L.wx = L.a2b + pad(h->A);
     L.total = L.wx + pad(h->uvfa.X * 2 * h->hidden);
     return L;

@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from simple_distributed_rl_amd import _native as N
 
-_DUELING = {"average": 0, "max": 1, "": 2}
+_DUELING = {"average": 0, "max": 1, "": 2, "plain": 3}  # "plain": no dueling split -- DQN's out_layer over every unit (srlx.h: dueling_type 3)
 
 
 class EngineQNet(nn.Module):
@@ -34,12 +34,16 @@ class EngineQNet(nn.Module):
         tensors, `fc1_sigma_w` ... `a2_sigma_b` the sigmas, in the same (fused, NHWC-column) layouts.
         uvfa_cols = X > 0 (round 6): Agent57(_light)'s Q-network (agent57_light/model_torch.py:18-64) -- X further input columns behind the image features (previous
         rewards, one-hot previous action, one-hot actor).  They are kept apart as `fcx` [X][2*hidden] (column-major: what srlx_qnet_bind_uvfa reads); such a
-        network is initialised by `load_reference_state_dict` (the reference's He-normal scale depends on the fan-in of the 7744 + X wide layer)."""
+        network is initialised by `load_reference_state_dict` (the reference's He-normal scale depends on the fan-in of the 7744 + X wide layer).
+        dueling_type="plain": DQN's network (dqn/model_torch.py:17-29, algorithms/dqn.py:build_qnetwork) -- one dense layer of W = 2*hidden units (`fc1`, NHWC columns)
+        and a plain `out_layer` Linear(W, A) over all of them; `unused_w` / `unused_b` fill the kernels' v2 entries (zero, never read, never updated)."""
         super().__init__()
         self.hw, self.window, self.hidden, self.filters, self.n_actions, self.dueling_type = tuple(hw), window, hidden, filters, n_actions, dueling_type
         self.noisy = bool(noisy)
         self.uvfa_cols = int(uvfa_cols)
         assert not (self.noisy and self.uvfa_cols)
+        self.plain = dueling_type == "plain"
+        assert not (self.plain and (self.noisy or self.uvfa_cols)), "the plain Q head has no NoisyLinear or UVFA form"
         Fi = filters
         self.conv1 = nn.Conv2d(window, Fi, 8, 4, padding=3, padding_mode="replicate")
         self.conv2 = nn.Conv2d(Fi, 2 * Fi, 4, 2, padding=2, padding_mode="replicate")
@@ -49,8 +53,13 @@ class EngineQNet(nn.Module):
         self.out_c, self.out_p = y.shape[1], y.shape[2] * y.shape[3]
         self.flat = self.out_c * self.out_p
         self.fc1 = nn.Linear(self.flat, 2 * hidden)
-        self.v2 = nn.Linear(hidden, 1)
-        self.a2 = nn.Linear(hidden, n_actions)
+        if self.plain:
+            self.out_layer = nn.Linear(2 * hidden, n_actions)
+            self.unused_w = nn.Parameter(torch.zeros(4))
+            self.unused_b = nn.Parameter(torch.zeros(4))
+        else:
+            self.v2 = nn.Linear(hidden, 1)
+            self.a2 = nn.Linear(hidden, n_actions)
         if self.uvfa_cols:
             self.fcx = nn.Parameter(torch.zeros(self.uvfa_cols, 2 * hidden))
         if self.noisy:
@@ -63,8 +72,19 @@ class EngineQNet(nn.Module):
         self.weights_version = 0  # bumped by every state-dict load: caches derived from the weights (QNetInference's operand planes) compare it
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._bump_version())
         self.fix_formats()
-        if not self.uvfa_cols:
+        if self.plain:
+            self.load_reference_state_dict(self.reference_module().state_dict())
+        elif not self.uvfa_cols:
             self.load_reference_state_dict(atari_qnetwork(n_actions, hw, window, hidden, self.noisy, filters, dueling_type).state_dict())
+
+    def reference_module(self):
+        """(plain head) The module tree algorithms/dqn.py:build_qnetwork builds for this shape -- in_block -> hidden_block (MLP, one ReLU layer of 2*hidden) ->
+        out_layer -- with the reference's initialisation; its state_dict is what `load_reference_state_dict` / `reference_state_dict` speak."""
+        from simple_distributed_rl_amd.rl.torch_.networks import InputImageBlock, MLPBlock, QNetwork
+
+        assert self.plain
+        in_block = InputImageBlock((self.hw[0], self.hw[1], self.window), filters=self.filters)
+        return QNetwork(in_block, MLPBlock(in_block.out_size, (2 * self.hidden,)), nn.Linear(2 * self.hidden, self.n_actions))
 
     def fix_formats(self):
         """conv2/conv3 weights in channels_last memory = [Cout][ky][kx][Cin], the K order of an NHWC implicit GEMM."""
@@ -95,6 +115,8 @@ class EngineQNet(nn.Module):
             h = F.relu(lin("fc1", x))
             v = lin("v2", h[:, : self.hidden])
             adv = lin("a2", h[:, self.hidden :])
+        elif self.plain:
+            return self.out_layer(F.relu(self.fc1(x)))
         else:
             pre = self.fc1(x)
             if self.uvfa_cols:
@@ -111,6 +133,7 @@ class EngineQNet(nn.Module):
     # ---- reference <-> engine layouts -----------------------------------------------------------
     _CONV_KEYS = {"conv1": "in_block.image_block.image_layers.0", "conv2": "in_block.image_block.image_layers.2", "conv3": "in_block.image_block.image_layers.4"}
     _HEAD = "hidden_block.hidden_layers.0"
+    _PLAIN_KEYS = ("hidden_block.hidden_layers.0", "out_layer")  # DQN: the MLP's dense layer, the head (dqn/model_torch.py:17-29)
 
     def _fuse_fc1(self, v1, a1):
         """[H, C*P (+ X)] x 2 (columns c*P+p, then the UVFA columns) -> [2H, P*C] (NHWC columns); the UVFA columns go to `fcx` (transposed)"""
@@ -142,6 +165,14 @@ class EngineQNet(nn.Module):
             for mine, ref in self._CONV_KEYS.items():
                 getattr(self, mine).weight.copy_(sd[ref + ".weight"])
                 getattr(self, mine).bias.copy_(sd[ref + ".bias"])
+            if self.plain:  # channel-major columns -> NHWC
+                hk, ok = self._PLAIN_KEYS
+                C, P, W = self.out_c, self.out_p, 2 * H
+                self.fc1.weight.copy_(sd[hk + ".weight"].to(dev).reshape(W, C, P).permute(0, 2, 1).reshape(W, P * C))
+                self.fc1.bias.copy_(sd[hk + ".bias"])
+                self.out_layer.weight.copy_(sd[ok + ".weight"])
+                self.out_layer.bias.copy_(sd[ok + ".bias"])
+                return self
             hd = self._HEAD
             self.fc1.weight.copy_(self._fuse_fc1(sd[f"{hd}.v_layers.0.{wk}"].to(dev), sd[f"{hd}.adv_layers.0.{wk}"].to(dev)))
             self.fc1.bias.copy_(torch.cat([sd[f"{hd}.v_layers.0.{bk}"], sd[f"{hd}.adv_layers.0.{bk}"]]))
@@ -165,6 +196,14 @@ class EngineQNet(nn.Module):
         for mine, ref in self._CONV_KEYS.items():
             sd[ref + ".weight"] = getattr(self, mine).weight.detach().contiguous().clone()
             sd[ref + ".bias"] = getattr(self, mine).bias.detach().clone()
+        if self.plain:
+            hk, ok = self._PLAIN_KEYS
+            C, P, W = self.out_c, self.out_p, 2 * H
+            sd[hk + ".weight"] = self.fc1.weight.detach().reshape(W, P, C).permute(0, 2, 1).reshape(W, C * P).clone()
+            sd[hk + ".bias"] = self.fc1.bias.detach().clone()
+            sd[ok + ".weight"] = self.out_layer.weight.detach().clone()
+            sd[ok + ".bias"] = self.out_layer.bias.detach().clone()
+            return sd
         hd = self._HEAD
 
         def put(layer, sub, w, b, sw=None, sb=None):
@@ -191,6 +230,9 @@ class EngineQNet(nn.Module):
     def kernel_parameters(self):
         """The tensors libsrlx binds, in its order: 12 (conv1..a2, weight then bias; mu for noisy layers) + the 6 sigmas of a noisy net."""
         n = self
+        if self.plain:  # the head in the a2 entries, the unused v2 entries zero (srlx.h: dueling_type 3)
+            return [n.conv1.weight, n.conv1.bias, n.conv2.weight, n.conv2.bias, n.conv3.weight, n.conv3.bias, n.fc1.weight, n.fc1.bias,
+                    n.unused_w, n.unused_b, n.out_layer.weight, n.out_layer.bias]
         ps = [n.conv1.weight, n.conv1.bias, n.conv2.weight, n.conv2.bias, n.conv3.weight, n.conv3.bias, n.fc1.weight, n.fc1.bias,
               n.v2.weight, n.v2.bias, n.a2.weight, n.a2.bias]
         if self.noisy:

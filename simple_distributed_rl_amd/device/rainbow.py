@@ -76,6 +76,8 @@ class RainbowDeviceConfig:
     hidden_units: int = 512
     filters: int = 32
     dueling_type: str = "average"  # DuelingNetworkConfig: "average" | "max" | ""
+    plain_head: bool = False  # DQN (dqn/model_torch.py:17-29): no dueling block -- one dense layer of `hidden_units` units (a multiple of 64, <= 1024) and a plain
+    # Linear(hidden_units, A) head over all of them (libsrlx dueling_type 3); `dueling_type` is then not read
     # --- engine
     obs_hw: tuple = (84, 84)
     n_actions: int = 6
@@ -173,14 +175,19 @@ class RainbowEngine:
         self.mfma = True  # (kept for callers that used to branch on it: there is no other network path)
         sch = self.schedule = cfg.schedule
         self.autograd_yardstick = bool(sch.autograd_yardstick)
-        covered = cfg.filters == 32 and cfg.hidden_units <= 512 and cfg.hidden_units % 32 == 0 and B <= 64 and H == W_ and W_ % 4 == 0 and cfg.dueling_type != "max"
+        # the kernels' `hidden` (their first dense layer has 2 * hidden units): a plain head's layer of W units is a handle with hidden = W / 2
+        self.plain = bool(cfg.plain_head)
+        hid = cfg.hidden_units // 2 if self.plain else cfg.hidden_units
+        head_ok = (cfg.hidden_units % 64 == 0 and not self.noisy) if self.plain else cfg.dueling_type != "max"
+        covered = cfg.filters == 32 and hid <= 512 and hid % 32 == 0 and B <= 64 and H == W_ and W_ % 4 == 0 and head_ok
         if not covered and not self.autograd_yardstick:
             raise ValueError("RainbowEngine: the hand-written gradient step covers the DQN image block with 32 filters on square frames (side % 4 == 0), one dueling "
-                             f"layer of <= 512 units (average / none) and batches <= 64; got filters={cfg.filters}, hidden={cfg.hidden_units}, batch={B}, "
-                             f"frames={cfg.obs_hw}, dueling='{cfg.dueling_type}'.  There is no fallback network path.")
+                             "layer of <= 512 units (average / none) or one plain layer of <= 1024 units in multiples of 64 (plain_head, no NoisyLinear) and batches "
+                             f"<= 64; got filters={cfg.filters}, hidden={cfg.hidden_units}, batch={B}, frames={cfg.obs_hw}, dueling='{cfg.dueling_type}', "
+                             f"plain_head={self.plain}.  There is no fallback network path.")
         self.mfma_train = covered and not self.autograd_yardstick
         fused_adam = self.mfma_train and not self.noisy and sch.fused_adam and role != "actor"
-        fast_actor = self.fused_convs and not self.noisy and E >= 512 and E % 128 == 0 and (2 * cfg.hidden_units) % 128 == 0
+        fast_actor = self.fused_convs and not self.noisy and E >= 512 and E % 128 == 0 and (2 * hid) % 128 == 0
         fast_learner = fused_adam and self.fused_convs and sch.fused_td
         # (actor-side initial priorities on one GPU keep the fifteen-launch lock-step: their tree add runs one lock-step behind the ring commit, which the
         #  deferred-advance commit does not model; a distributed learner -- learner_replay -- commits ring and tree together, two slabs behind: device/dist.py)
@@ -221,7 +228,7 @@ class RainbowEngine:
             torch.cuda.set_stream(self.actor_stream)
 
         def make_net():
-            return EngineQNet(A, cfg.obs_hw, cfg.window_length, cfg.hidden_units, cfg.filters, cfg.dueling_type, noisy=self.noisy).to(self.dev)
+            return EngineQNet(A, cfg.obs_hw, cfg.window_length, hid, cfg.filters, "plain" if self.plain else cfg.dueling_type, noisy=self.noisy).to(self.dev)
 
         self.q_online = make_net()
         if role == "actor":  # an actor rank: the online network is the broadcast's landing place, nothing trains here
@@ -235,7 +242,7 @@ class RainbowEngine:
                 self.inf_actor.set_fc1_neighbour(0)  # nobody shares the GPU: CU-filling workgroups (83 against 97-130 us at 1024 rows)
                 self._planes_ptr = [self.inf_actor.set_planes_ptr(0), self.inf_actor.set_planes_ptr(1)]
                 self._set, self._published, self._seen_versions, self._fresh_set, self._learner_planes = 0, None, None, None, False
-            elif not self.noisy and E >= 512 and E % 128 == 0 and (2 * cfg.hidden_units) % 128 == 0:
+            elif not self.noisy and E >= 512 and E % 128 == 0 and (2 * hid) % 128 == 0:
                 self.inf_actor.enable_fc1_planes(private_weights=True)  # (re-split by `on_weights_broadcast`)
             self.mfma_train = False
             self.optimizer = None
@@ -274,7 +281,7 @@ class RainbowEngine:
             # (same-box A/B of the lock-step, tools/_r4_probe3.sh: 0.508 ms with 4 K splits -- 256 workgroups that leave half of every CU to the update --, 0.515
             # with 8, 0.528 with 16, 0.545 with the CU-filling kernel; EngineSchedule(fc1_neighbour=0) selects that one, = k the K splits)
             self.inf_actor.set_fc1_neighbour(int(sch.fc1_neighbour))
-        elif not self.noisy and E >= 512 and E % 128 == 0 and (2 * cfg.hidden_units) % 128 == 0 and (planes == "1" or (planes == "auto" and not overlap)):
+        elif not self.noisy and E >= 512 and E % 128 == 0 and (2 * hid) % 128 == 0 and (planes == "1" or (planes == "auto" and not overlap)):
             # Chip-filling policy passes with the first dense layer on pre-split bf16 operand planes (srlx_fc1_planes.hip): the GEMM itself is 1.6x faster
             # (85 against 137 us at 1024 rows), but beside a learner it LOSES: same-box A/B (tools/_ab_lockstep.sh) 0.565 against 0.511 ms per lock-step --
             # the refresh of the actors' copy also has to split the 32 MB weight (22 us on the serial tail every lock-step) and the planes kernel's 144 KB /
@@ -573,7 +580,10 @@ class RainbowEngine:
         w1 = (c.obs_hw[1] + 6 - 8) // 4 + 1
         h2, w2 = (h1 + 4 - 4) // 2 + 1, (w1 + 4 - 4) // 2 + 1
         mac = h1 * w1 * F1 * c.window_length * 64 + h2 * w2 * 2 * F1 * F1 * 16 + h2 * w2 * 2 * F1 * 2 * F1 * 9
-        mac += h2 * w2 * 2 * F1 * 2 * c.hidden_units + c.hidden_units * (1 + c.n_actions)
+        if c.plain_head:  # one layer of hidden_units units, then Linear(hidden_units, A)
+            mac += h2 * w2 * 2 * F1 * c.hidden_units + c.hidden_units * c.n_actions
+        else:
+            mac += h2 * w2 * 2 * F1 * 2 * c.hidden_units + c.hidden_units * (1 + c.n_actions)
         return 2.0 * mac * c.n_envs
 
     def conv_gemm_flops(self, with_conv1: bool = False) -> float:

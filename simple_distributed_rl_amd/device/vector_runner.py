@@ -252,6 +252,16 @@ def why_not_vector(context, env, rl_config) -> str:
         return "input block is not the DQN image block (32 filters, ReLU)"
     hb = rl_config.hidden_block
     sizes = tuple(hb.kwargs.get("layer_sizes", ()))
+    if kind == "dqn":  # dqn/model_torch.py:17-29: MLP hidden block + out_layer -- the plain Q head (srlx.h: dueling_type 3)
+        if hb.name != "MLP" or len(sizes) != 1:
+            return "hidden block is not one MLP layer (the plain Q head covers in_block -> one dense layer -> out_layer)"
+        if str(hb.kwargs.get("activation", "relu")).lower() != "relu":
+            return "the plain Q head's dense layer is ReLU"
+        if sizes[0] % 64 != 0 or sizes[0] > 1024:
+            return "the plain Q head covers a dense layer of a multiple of 64 (<= 1024) units"
+        if rl_config.batch_size > 64:
+            return "the hand-written gradient step covers batches of at most 64"
+        return ""
     if hb.name != "DuelingNetwork" or len(sizes) != 1 or sizes[0] % 32 != 0 or sizes[0] > 512:
         return "hidden block is not one dueling layer of a multiple of 32 (<= 512) units"
     if hb.kwargs.get("dueling_kwargs", {}).get("dueling_type", "average") not in ("average", ""):
@@ -263,7 +273,7 @@ def why_not_vector(context, env, rl_config) -> str:
 
 def engine_kind(rl_config) -> Optional[str]:
     """Which device engine serves this algorithm config (None = the plugin classes only)."""
-    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light"}.get(rl_config.get_name())
+    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light", "DQN": "dqn"}.get(rl_config.get_name())
 
 
 def frame_space(env, rl_config):
@@ -283,7 +293,8 @@ def frame_processor(rl_config):
 
 
 def device_config_from(rl_config, env, n_envs: int, seed: int):
-    """rainbow.Config (srl/algorithms/rainbow/rainbow.py:57-114) -> the engine's configuration."""
+    """rainbow.Config (srl/algorithms/rainbow/rainbow.py:57-114) -> the engine's configuration; dqn.Config (srl/algorithms/dqn/dqn.py:50-101) -> the same engine
+    with the plain Q head and 1-step targets (dqn.py:144-176 is rainbow_nomultisteps.py:10-43's formula: multisteps=1, retrace_h unused)."""
     from simple_distributed_rl_amd.device.rainbow import RainbowDeviceConfig
 
     mem = rl_config.memory
@@ -291,11 +302,15 @@ def device_config_from(rl_config, env, n_envs: int, seed: int):
     kw = mem.kwargs if prop else {}
     hw = _image_hw(frame_space(env, rl_config))
     hb = rl_config.hidden_block
+    if engine_kind(rl_config) == "dqn":
+        head = dict(enable_noisy_dense=False, multisteps=1, retrace_h=1.0, hidden_units=int(hb.kwargs["layer_sizes"][0]), plain_head=True)
+    else:
+        head = dict(enable_noisy_dense=rl_config.enable_noisy_dense, multisteps=rl_config.multisteps, retrace_h=rl_config.retrace_h,
+                    hidden_units=int(hb.kwargs["layer_sizes"][0]), dueling_type=hb.kwargs.get("dueling_kwargs", {}).get("dueling_type", "average"))
     return RainbowDeviceConfig(
         batch_size=rl_config.batch_size, epsilon=rl_config.epsilon, test_epsilon=rl_config.test_epsilon, lr=rl_config.lr, discount=rl_config.discount,
         target_model_update_interval=rl_config.target_model_update_interval, enable_reward_clip=rl_config.enable_reward_clip,
-        enable_double_dqn=rl_config.enable_double_dqn, enable_noisy_dense=rl_config.enable_noisy_dense, enable_rescale=rl_config.enable_rescale,
-        multisteps=rl_config.multisteps, retrace_h=rl_config.retrace_h, window_length=rl_config.window_length,
+        enable_double_dqn=rl_config.enable_double_dqn, enable_rescale=rl_config.enable_rescale, window_length=rl_config.window_length,
         memory_capacity=mem.capacity, memory_warmup_size=mem.warmup_size,
         # the uniform ReplayBuffer (priority_memories/replay_buffer.py:10-55) is the alpha = 0 corner of the sum-tree: every leaf
         # weighs 1, so every importance weight is 1 whatever beta is; like random.sample its draws are WITHOUT replacement (a second hit
@@ -303,8 +318,7 @@ def device_config_from(rl_config, env, n_envs: int, seed: int):
         memory_has_duplicate=bool(kw.get("has_duplicate", True)) if prop else False,
         memory_alpha=float(kw.get("alpha", 0.0)), memory_beta_initial=float(kw.get("beta_initial", 0.4)),
         memory_beta_steps=int(kw.get("beta_steps", 1_000_000)), memory_epsilon=float(kw.get("epsilon", 1e-4)),
-        hidden_units=int(hb.kwargs["layer_sizes"][0]), dueling_type=hb.kwargs.get("dueling_kwargs", {}).get("dueling_type", "average"),
-        filters=32, obs_hw=tuple(hw), n_actions=env.action_space.n, n_envs=n_envs, seed=seed,
+        filters=32, obs_hw=tuple(hw), n_actions=env.action_space.n, n_envs=n_envs, seed=seed, **head,
     )
 
 
@@ -360,7 +374,7 @@ class VectorActor(ActorDriver):
         if eng.ledger is None:
             eng.ledger = EpisodeLedger(self.lanes, dev)  # same tensors for the engine's lifetime: the captured commit graph points at them
         eng.ledger.clear()
-        self._eps_sched = None if self.rl_config.enable_noisy_dense else self.rl_config.epsilon_scheduler.create(self.rl_config.epsilon)
+        self._eps_sched = None if getattr(self.rl_config, "enable_noisy_dense", False) else self.rl_config.epsilon_scheduler.create(self.rl_config.epsilon)
         self._eps_now = None
         self._iteration = 0  # every lane is a worker whose step_in_training restarts with the run (worker_run.py setup)
         self._training = bool(context.training)

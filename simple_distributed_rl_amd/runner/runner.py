@@ -218,6 +218,8 @@ class Runner:
                 from simple_distributed_rl_amd.device import vector_runner as vr
 
                 self.vector_reason = vr.why_not_vector(c, self.make_env(), self.rl_config)
+                if not self.vector_reason and vr.engine_kind(self.rl_config) == "dqn":  # (device/mp_runner.py serves the Rainbow family)
+                    self.vector_reason = "DQN runs on the device engine in train(); train_mp() keeps it on the plugin path"
                 if not self.vector_reason:  # one process per GPU over RCCL (device/mp_runner.py); this process is the learner rank
                     from simple_distributed_rl_amd.device.mp_runner import train_mp_on_engine
 
