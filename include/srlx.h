@@ -226,7 +226,8 @@ int srlx_store_commit_step(srlx_store_t *h, const int32_t *d_actions, const floa
                            const uint8_t *d_done, const void *d_next_obs, uint8_t *d_item_mask, void *stream);
 /* The same commit as ONE launch with two options (the round-4 lock-step):
  *   d_next_frame_table  int64 [E][window] or NULL: the frame-offset table of the NEXT policy pass (what srlx_store_frame_table_current would write after
- *                       the position has advanced), so the next pass needs no launch of its own for it (uint8 stores)
+ *                       the position has advanced), so the next pass needs no launch of its own for it (uint8 stores; window-1 float32 stores too -- every
+ *                       frame-offset table and gather of this header counts elements, so a float32 ring's offsets index float32 observations)
  *   advance             1: p advances inside the launch (srlx_store_commit_step = this with NULL, 1); 0: p stays and the caller advances it later --
  *                       srlx_store_advance, or srlx_per_set_add_counters on the position view (srlx_store_views).  Ring slot p + 1 and the scalars of p are
  *                       referenced by no stored item, so with advance = 0 the commit may run while a learner still reads the ring; p itself feeds the
@@ -833,6 +834,43 @@ int srlx_qnet_bind_noisy(srlx_qnet_t *h, const float *const *d_sigma, uint64_t s
 int srlx_qnet_bind_noisy_grads(srlx_qnet_t *h, float *const *d_grad_sigma);
 int srlx_qnet_redraw_rows(srlx_qnet_t *h, int64_t rows, int64_t row_stride, float *d_q, void *stream);
 int srlx_qnet_noisy_effective(srlx_qnet_t *h, int which, float *d_out, int64_t *n_elems, int64_t *draw_id, void *stream);
+
+/* DQN's Q-network for flat observations (srl/algorithms/dqn/model_torch.py:17-29: in_block -> hidden_block (MLP) -> out_layer), srlx_mlpq.hip.
+ * obs_dim D = 1..256 float32 elements, n_layers = 1..3 Linear + ReLU layers (the input value block's layers, then the hidden block's) of widths[l] = 32..512 units
+ * (multiples of 32), out_layer Linear to n_actions = 2..32.  Plain float32 arithmetic.
+ *   srlx_mlpq_create       : max_rows = most rows of one srlx_mlpq_forward; max_batch = most items of one srlx_mlpq_train_step (<= 256; 0: the handle never trains)
+ *   srlx_mlpq_bind         : d_params[2 * (n_layers + 1)] = weight [out][in], bias [out] of every layer in the reference's key order (in_block, hidden_block, out_layer)
+ *   srlx_mlpq_bind_grads   : gradient tensors of the same shapes (NULL table: none); srlx_mlpq_train_step writes them
+ *   srlx_mlpq_bind_adam    : exp_avg / exp_avg_sq of every parameter: srlx_mlpq_train_step then takes torch's Adam step (srlx_adam_math.h) in the launch that
+ *                            finishes each gradient
+ *   srlx_mlpq_forward      : Q of `rows` observations, row r at d_obs + d_row_offsets[r] (NULL: + r * D); d_q [rows][A] may be NULL.  d_actions != NULL: the
+ *                            epsilon-greedy action of every row in the same launch, k_head's rule (srlx_policy_epsilon_greedy on the uniforms
+ *                            srlx_rng_uniform(seed, counter, 2 * rows) would write); the counter is read, not advanced
+ *   srlx_mlpq_train_step   : one DQN update (dqn.py:144-176, model_torch.py:89-131) in two launches: online forward over s_0 / s_1, target forward over s_1, the
+ *                            1-step (double) target, IS-weighted Huber loss, d loss / d q, priorities |target - q|, backward through every layer, Adam.
+ *                            d_offsets int64 [B][2] = element offsets of s_0, s_1 from d_obs_base (the store's frame_off_all at window 1, n_step 1); actions /
+ *                            rewards / terminated / weights as srlx_per_sample_gather_train writes them; d_steps_taken = Adam steps already taken (device
+ *                            scalar, not advanced here).  Outputs: d_q0 [B][A] (online Q of s_0 before the step), d_target, d_priorities [B], d_loss [1].
+ *                            Gradient sums run in item order: two runs on the same inputs are bit-identical.
+ *   srlx_mlpq_publish      : every parameter of `src` into `dst` (online -> target, online -> an actor copy), one launch
+ * Batch CartPole (envs/cartpole.py:step; srlx_mlpq.hip): float64 state [E][4], steps / episodes int32 [E].  A lane whose d_needs_reset entry is set (the store's
+ * needs_reset view, srlx_store_views) starts its next episode instead of stepping: state uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane), its
+ * first observation in d_obs, reward / terminated / done 0.  d_needs_reset NULL: every lane starts an episode (actions and scalar outputs may be NULL).
+ * Otherwise one Euler step: reward 1, terminated outside +-12 degrees / +-2.4, done = terminated or step count >= max_steps; d_obs [E][4] float32. */
+typedef struct srlx_mlpq srlx_mlpq_t;
+int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int64_t max_rows, int64_t max_batch, int device);
+int srlx_mlpq_destroy(srlx_mlpq_t *h);
+int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params);
+int srlx_mlpq_bind_grads(srlx_mlpq_t *h, float *const *d_grads);
+int srlx_mlpq_bind_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, double lr, double beta1, double beta2, double eps);
+int srlx_mlpq_forward(srlx_mlpq_t *h, int64_t rows, const float *d_obs, const int64_t *d_row_offsets, float *d_q, const float *d_eps, uint64_t seed,
+                      const int64_t *d_counter, int32_t *d_actions, void *stream);
+int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batch, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions,
+                         const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
+                         const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream);
+int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream);
+int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
+                       int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 
 #ifdef __cplusplus
 }

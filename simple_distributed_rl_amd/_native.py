@@ -197,6 +197,15 @@ SIGNATURES = {
     "srlx_agent57_emb_tail": (c_int, [c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p]),
     "srlx_agent57_rnd_tail": (c_int, [c_i64, c_int, c_i64] + [c_p] * 12 + [c_f64] * 5 + [c_p, c_p, c_p, c_p]),
     "srlx_agent57_priority": (c_int, [c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_mlpq_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_p, c_int, c_i64, c_i64, c_int]),
+    "srlx_mlpq_destroy": (c_int, [c_p]),
+    "srlx_mlpq_bind": (c_int, [c_p, c_p]),
+    "srlx_mlpq_bind_grads": (c_int, [c_p, c_p]),
+    "srlx_mlpq_bind_adam": (c_int, [c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64]),
+    "srlx_mlpq_forward": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_u64, c_p, c_p, c_p]),
+    "srlx_mlpq_train_step": (c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_mlpq_publish": (c_int, [c_p, c_p, c_p]),
+    "srlx_cartpole_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

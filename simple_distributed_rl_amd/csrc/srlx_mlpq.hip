@@ -1,0 +1,577 @@
+// srlx_mlpq.hip -- DQN's Q-network for flat observations (srl/algorithms/dqn/model_torch.py:17-29: in_block -> hidden_block (MLP) -> out_layer), its
+// acting pass with the fused epsilon-greedy selection, the whole learner step in two launches, the online -> target / actor copy, and a batch CartPole.
+//
+// Every dense layer is Linear (+ ReLU except out_layer), weights in torch's [out][in] layout, plain float32 on the VALU: at D <= 256 inputs, <= 3 layers of
+// <= 512 units and <= 32 actions a pass is a few thousand dependent multiply-adds per row, so launch count and the layer chain bound it, not throughput.
+//   k_mlpq_actor      16 rows per workgroup: rows -> LDS, layer by layer through two LDS buffers (each layer's weight staged in LDS by coalesced loads, in
+//                     tiles of whole rows), Q rows out, epsilon-greedy on each row (= k_head's rule).
+//   k_mlpq_learn_rows 8 sampled items per workgroup: online pass over s_0 and s_1, target pass over s_1, the 1-step (double) DQN target / Huber / priority of
+//                     srlx_td_math.h:td_rows, then the backward chain d loss / d h_l of every layer for these rows (the chain is row-local).  Writes the
+//                     s_0 activations and the d h_l rows.
+//   k_mlpq_grad_adam  one thread per parameter: the gradient as a sum over the batch in item order (no atomics: bit-reproducible), then torch's Adam
+//                     (srlx_adam_math.h) in the same thread; block 0 reduces the loss.
+#include "srlx_adam_math.h"
+#include "srlx_common.h"
+#include "srlx_td_math.h"
+
+struct srlx_mlpq {
+    int D, L, A, device;
+    int W[3];
+    int64_t max_rows, max_batch;
+    float *p[8];  // layer 0 weight, bias, ..., out_layer weight, bias
+    bool bound;
+    float *grads[8];
+    float *m[8], *v[8];
+    double lr, beta1, beta2, eps;
+    bool adam;
+    // learner scratch (max_batch > 0)
+    float *x0, *h, *dh, *q_on_next, *q_tg_next, *grad_q;
+    double *loss_rows;
+    int wmax;
+    void *d_net;  // the descriptor of the bound parameters in device memory (the learner step's launch reads it)
+};
+
+namespace {
+
+using i64 = int64_t;
+using u64 = unsigned long long;
+using u8 = unsigned char;
+
+constexpr int kThreads = 256;
+constexpr int kRows = 16;      // rows of one acting workgroup, and of the learner's online pass (s_0 and s_1 of kItems items)
+constexpr int kItems = kRows / 2;
+constexpr int kMaxParams = 8;
+
+struct Net {  // (scalar fields and selects, no arrays: a kernel-argument array indexed by a run-time layer number is copied to scratch memory)
+    int D, L, A;
+    int W0, W1, W2;
+    const float *w0, *w1, *w2, *w3, *b0, *b1, *b2, *b3;
+    const float *wout;  // out_layer's weight (= the weight of layer L)
+    __device__ int width(int l) const { return l == 0 ? W0 : (l == 1 ? W1 : W2); }
+    __device__ int in_of(int l) const { return l == 0 ? D : width(l - 1); }
+    __device__ int out_of(int l) const { return l < L ? width(l) : A; }
+    __device__ const float *weight(int l) const { return l == 0 ? w0 : (l == 1 ? w1 : (l == 2 ? w2 : w3)); }
+    __device__ const float *bias(int l) const { return l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3)); }
+};
+
+Net net_of(const srlx_mlpq *h) {
+    Net n;
+    n.D = h->D, n.L = h->L, n.A = h->A;
+    n.W0 = h->W[0], n.W1 = h->L > 1 ? h->W[1] : 0, n.W2 = h->L > 2 ? h->W[2] : 0;
+    const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l <= h->L; l++) w[l] = h->p[2 * l], b[l] = h->p[2 * l + 1];
+    n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
+    n.wout = w[h->L];
+    return n;
+}
+
+int lds_stride(const srlx_mlpq *h) { return h->wmax + 1; }  // (odd: rows of different row groups fall on different banks)
+
+// y[r][u] = act(sum_k W[u][k] x[r][k] + b[u]) for rows r < rows (<= kRows), both in LDS with row strides sx / sy.  The weight goes through LDS: a tile of whole
+// [out][in] rows (as many units as kWTile floats hold, row stride In + 1) is loaded by the whole workgroup with coalesced reads, then thread -> (unit, row group):
+// a tile narrower than the workgroup runs kThreads / units row groups side by side; each thread keeps its rows' sums in registers.  Every thread of the
+// workgroup must call this (it holds barriers).
+constexpr int kWTile = 8192;  // floats of the weight tile in LDS (32 KB)
+__device__ __forceinline__ void dense(const float *__restrict__ Wt, const float *__restrict__ bias, int In, int Out, int rows, const float *x, int sx, float *y, int sy,
+                                      bool relu, float *wl) {
+    const int t = threadIdx.x;
+    const int ws = In + 1;
+    const int tu_max = kWTile / ws < Out ? kWTile / ws : Out;
+    for (int u0 = 0; u0 < Out; u0 += tu_max) {
+        const int tu = Out - u0 < tu_max ? Out - u0 : tu_max;
+        __syncthreads();  // (the previous tile's readers are done)
+        const float *src = Wt + (i64)u0 * In;
+        for (int i = t; i < tu * In; i += kThreads) wl[(i / In) * ws + i % In] = src[i];
+        __syncthreads();
+        const int uc = tu < kThreads ? tu : kThreads;
+        const int G = kThreads / uc;
+        const int g = t / uc, ul = t % uc;
+        if (g >= G) continue;
+        const int nr = g < rows ? (rows - g + G - 1) / G : 0;
+        for (int u = ul; u < tu; u += uc) {
+            float acc[kRows];
+#pragma unroll
+            for (int j = 0; j < kRows; j++) acc[j] = 0.f;
+            const float *wr = wl + u * ws;
+            for (int k = 0; k < In; k++) {
+                const float w = wr[k];
+#pragma unroll
+                for (int j = 0; j < kRows; j++)
+                    if (j < nr) acc[j] = __builtin_fmaf(w, x[(g + j * G) * sx + k], acc[j]);
+            }
+            const float bu = bias[u0 + u];
+#pragma unroll
+            for (int j = 0; j < kRows; j++)
+                if (j < nr) {
+                    const float z = acc[j] + bu;
+                    y[(g + j * G) * sy + u0 + u] = relu ? (z > 0.f ? z : 0.f) : z;
+                }
+        }
+    }
+}
+
+// the whole network over the rows in buf[0] (inputs, D columns); returns the buffer that holds the Q rows.  `keep` (global, per layer l < L: [rows_kept][W_l],
+// NULL: not kept) receives rows 0..kept-1 of every hidden layer's output.
+__device__ __forceinline__ float *forward_rows(const Net &n, int rows, float *buf0, float *buf1, int S, float *wl, float *keep, i64 keep_plane, i64 keep_row0,
+                                               int kept) {
+    float *cur = buf0, *nxt = buf1;
+    for (int l = 0; l <= n.L; l++) {
+        const int In = n.in_of(l), Out = n.out_of(l);
+        dense(n.weight(l), n.bias(l), In, Out, rows, cur, S, nxt, S, l < n.L, wl);
+        __syncthreads();
+        if (keep && l < n.L)
+            for (int p = threadIdx.x; p < kept * Out; p += kThreads) keep[l * keep_plane + (keep_row0 + p / Out) * Out + p % Out] = nxt[(p / Out) * S + p % Out];
+        float *tmp = cur;
+        cur = nxt, nxt = tmp;
+    }
+    return cur;
+}
+
+struct Policy {
+    u64 seed;
+    const i64 *counter;
+    const float *eps;
+    int32_t *actions;
+};
+
+// k_head's selection (srlx_qnet.hip: fused_policy; rainbow.py:301-329): u53(rng_u64(seed, counter, 2 m)) < eps[m] -> the uniform draw
+// u53(rng_u64(seed, counter, 2 m + 1)) picks one of the A actions, else the first maximum of the row (np.argmax).  The counter is only read here.
+__device__ __forceinline__ int select_action(const Policy &pol, i64 m, int A, const float *q) {
+    const u64 c = (u64)pol.counter[0];
+    int act = 0;
+    if (srlx::u53(srlx::rng_u64(pol.seed, c, (u64)(2 * m))) < (double)pol.eps[m]) {
+        int pick = (int)(srlx::u53(srlx::rng_u64(pol.seed, c, (u64)(2 * m + 1))) * (double)A);
+        if (pick >= A) pick = A - 1;
+        act = pick;
+    } else {
+        float bv = -INFINITY;
+        bool have = false;
+        for (int a = 0; a < A; a++)
+            if (!have || q[a] > bv) act = a, bv = q[a], have = true;
+    }
+    return act;
+}
+
+__device__ __forceinline__ const float *row_ptr(const float *base, const i64 *off, i64 row, int D) { return off ? base + off[row] : base + row * D; }
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S, float *__restrict__ q,
+                                                         Policy pol) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
+    const int t = threadIdx.x;
+    const i64 r0 = (i64)blockIdx.x * kRows;
+    const int rows = (int)(rows_total - r0 < kRows ? rows_total - r0 : kRows);
+    for (int p = t; p < rows * n.D; p += kThreads) {
+        const int r = p / n.D, k = p % n.D;
+        b0[r * S + k] = row_ptr(obs, off, r0 + r, n.D)[k];
+    }
+    __syncthreads();
+    const float *qs = forward_rows(n, rows, b0, b1, S, wl, nullptr, 0, 0, 0);
+    if (q)
+        for (int p = t; p < rows * n.A; p += kThreads) q[(r0 + p / n.A) * n.A + p % n.A] = qs[(p / n.A) * S + p % n.A];
+    if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.A, qs + t * S);
+}
+
+// srlx_td_math.h:td_rows at n = 1, written out (its per-step arrays, indexed by the run-time n, would live in scratch memory): dqn.py:144-176 -- the retrace sum
+// is the single term float32(gain * float32(discount ** 0)) * 1.0 = gain -- and model_torch.py:89-131.  Returns the item's Huber term (float64).
+__device__ __forceinline__ double td_one(const srlx::TdArgs &a, i64 b) {
+    const int A = a.A;
+    const float *qon = a.q_on_next + b * A, *qtg = a.q_tg_next + b * A;
+    const int nact = srlx::argmax_masked(a.double_dqn ? qon : qtg, nullptr, A);
+    float maxq = qtg[nact];
+    if (a.rescale) maxq = srlx::inverse_rescaling(maxq);
+    float gain = a.rewards[b] + ((1.0f - a.terminated[b]) * (float)a.discount) * maxq;
+    if (a.rescale) gain = srlx::rescaling(gain);
+    const float target = gain;
+    a.target[b] = target;
+    const int a0 = a.actions[b];
+    const float q0 = a.q_on_0[b * A + a0];
+    const float w = a.weights[b];
+    const float tw = target * w, qw = q0 * w;
+    const float diff = tw - qw;
+    const float z = fabsf(diff);
+    const double huber = (z < 1.0f) ? 0.5 * (double)z * (double)z : (double)z - 0.5;
+    const float dclamp = diff > 1.0f ? 1.0f : (diff < -1.0f ? -1.0f : diff);
+    const float gsel = -(w * dclamp) / (float)a.B;
+    for (int k = 0; k < A; k++) a.grad_q0[b * A + k] = k == a0 ? gsel : 0.f;
+    a.priorities[b] = fabsf(target - q0);
+    return huber;
+}
+
+struct Learn {
+    i64 B;
+    const float *obs;
+    const i64 *off;  // [B][2]: element offsets of s_0 and s_1 (srlx_per_sample_gather_train's frame_off_all with window 1, n_step 1)
+    float *x0, *h, *dh, *q0, *grad_q;
+    double *loss_rows;
+    int hstride;  // floats between the per-layer planes of h / dh (max_batch * wmax)
+    srlx::TdArgs td;
+};
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restrict__ onp, const Net *__restrict__ tgp, Learn a, int S) {
+    // (the two networks' descriptors are read from memory: as kernel arguments, held in scalar registers through both passes, they spilled to scratch)
+    const Net &on = *onp, &tg = *tgp;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *d0 = sm + 2 * kRows * S, *d1 = d0 + kItems * S, *wl = d1 + kItems * S;
+    __shared__ float gsel[kItems];
+    __shared__ int act0[kItems];
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * kItems;
+    const int nb = (int)(a.B - i0 < kItems ? a.B - i0 : kItems);
+    const int D = on.D, A = on.A, L = on.L;
+    // rows 0..kItems-1: s_0 of the items, kItems..: s_1 (missing items: zero rows, never stored)
+    for (int p = t; p < kRows * D; p += kThreads) {
+        const int r = p / D, k = p % D, it = r % kItems, which = r / kItems;
+        const float x = it < nb ? a.obs[a.off[(i0 + it) * 2 + which] + k] : 0.f;
+        b0[r * S + k] = x;
+        if (which == 0 && it < nb) a.x0[(i0 + it) * D + k] = x;
+    }
+    __syncthreads();
+    const float *qs = forward_rows(on, kRows, b0, b1, S, wl, a.h, a.hstride, i0, nb);  // (the kept planes are [B][W_l] dense)
+    for (int p = t; p < nb * A; p += kThreads) {
+        const int r = p / A, c = p % A;
+        a.q0[(i0 + r) * A + c] = qs[r * S + c];
+        const_cast<float *>(a.td.q_on_next)[(i0 + r) * A + c] = qs[(kItems + r) * S + c];
+    }
+    __syncthreads();
+    // target pass over s_1
+    for (int p = t; p < kItems * D; p += kThreads) {
+        const int r = p / D, k = p % D;
+        b0[r * S + k] = r < nb ? a.obs[a.off[(i0 + r) * 2 + 1] + k] : 0.f;
+    }
+    __syncthreads();
+    const float *qt = forward_rows(tg, kItems, b0, b1, S, wl, nullptr, 0, 0, 0);
+    for (int p = t; p < nb * A; p += kThreads) const_cast<float *>(a.td.q_tg_next)[(i0 + p / A) * A + p % A] = qt[(p / A) * S + p % A];
+    __threadfence_block();
+    __syncthreads();
+    // dqn.py:144-176 + model_torch.py:89-131 for these items (td_rows with n = 1: target, Huber term, d loss / d q, priority)
+    if (t < nb) {
+        const i64 b = i0 + t;
+        a.loss_rows[b] = td_one(a.td, b);
+        act0[t] = a.td.actions[b];
+        gsel[t] = a.td.grad_q0[b * A + act0[t]];
+    }
+    __syncthreads();
+    // backward chain, row by row: d h_{L-1} from the Q seed (one non-zero column per row), then through every hidden layer's weight; ReLU masks from the kept outputs
+    float *dcur = d0, *dnext = d1;
+    for (int l = L - 1; l >= 0; l--) {
+        const int Wl = on.width(l);
+        const float *hl = a.h + (i64)l * a.hstride;
+        float *dhl = a.dh + (i64)l * a.hstride;
+        for (int p = t; p < nb * Wl; p += kThreads) {
+            const int r = p / Wl, k = p % Wl;
+            float g;
+            if (l == L - 1) {
+                g = gsel[r] * on.wout[act0[r] * Wl + k];
+            } else {
+                const int Wn = on.width(l + 1);
+                const float *wn = on.weight(l + 1);
+                g = 0.f;
+#pragma unroll 8
+                for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
+            }
+            g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
+            dcur[r * S + k] = g;
+            dhl[(i0 + r) * Wl + k] = g;
+        }
+        __syncthreads();
+        float *tmp = dcur;
+        dcur = dnext, dnext = tmp;
+    }
+}
+
+struct GradAdam {
+    i64 B;
+    int nseg;
+    i64 seg_end[kMaxParams];  // running element counts of the parameter tensors
+    int seg_out[kMaxParams], seg_in[kMaxParams];  // in = 0: a bias
+    const float *dout[kMaxParams];  // [B][out]: d loss / d (layer output) rows
+    const float *xin[kMaxParams];   // [B][in]: the layer's input rows
+    float *p[kMaxParams], *g[kMaxParams], *m[kMaxParams], *v[kMaxParams];
+    int adam;
+    double lr, beta1, beta2, eps;
+    const i64 *steps_taken;
+    const double *loss_rows;
+    float *loss;
+};
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_grad_adam(GradAdam a) {
+    const i64 i = (i64)blockIdx.x * kThreads + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.loss) {
+        double s = 0.0;
+        for (i64 b = 0; b < a.B; b++) s += a.loss_rows[b];
+        a.loss[0] = (float)(s / (double)a.B);
+    }
+    if (i >= a.seg_end[a.nseg - 1]) return;
+    int s = 0;
+    while (i >= a.seg_end[s]) s++;
+    const i64 e = i - (s ? a.seg_end[s - 1] : 0);
+    const int Out = a.seg_out[s], In = a.seg_in[s];
+    float g = 0.f;
+    if (In) {
+        const int u = (int)(e / In), k = (int)(e % In);
+        const float *dout = a.dout[s] + u, *xin = a.xin[s] + k;
+#pragma unroll 8
+        for (int b = 0; b < (int)a.B; b++) g = __builtin_fmaf(dout[(i64)b * Out], xin[(i64)b * In], g);
+    } else {
+        const float *dout = a.dout[s] + e;
+#pragma unroll 8
+        for (int b = 0; b < (int)a.B; b++) g += dout[(i64)b * Out];
+    }
+    if (a.g[s]) a.g[s][e] = g;
+    if (a.adam) {
+        const srlx::AdamCoef c = srlx::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.steps_taken[0]);
+        float p = a.p[s][e], m = a.m[s][e], v = a.v[s][e];
+        srlx::adam_one(p, g, m, v, c);
+        a.p[s][e] = p, a.m[s][e] = m, a.v[s][e] = v;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_copy(int nseg, GradAdam segs /* p = src, g = dst */) {
+    const i64 i = (i64)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= segs.seg_end[nseg - 1]) return;
+    int s = 0;
+    while (i >= segs.seg_end[s]) s++;
+    const i64 e = i - (s ? segs.seg_end[s - 1] : 0);
+    segs.g[s][e] = segs.p[s][e];
+}
+
+// ---- CartPole (envs/cartpole.py:step) for E lanes, float64 state -------------------------------------------------------------------------------------------
+constexpr double kGravity = 9.8, kMassCart = 1.0, kMassPole = 0.1, kHalfLength = 0.5, kForce = 10.0, kTau = 0.02;
+constexpr double kPi = 3.141592653589793;
+
+__global__ void __launch_bounds__(256) k_cartpole(i64 E, double *__restrict__ state, int32_t *__restrict__ steps, int32_t *__restrict__ episodes,
+                                                  const u8 *__restrict__ needs_reset, const int32_t *__restrict__ actions, i64 max_steps, u64 seed,
+                                                  float *__restrict__ obs, float *__restrict__ reward, u8 *__restrict__ terminated, u8 *__restrict__ done) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double *s = state + 4 * e;
+    if (!needs_reset || needs_reset[e]) {  // the lane's next episode: uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane)
+        const u64 key = (u64)e * 0x100000000ull + (u64)(uint32_t)episodes[e];
+        for (int k = 0; k < 4; k++) s[k] = -0.05 + 0.1 * srlx::u53(srlx::rng_u64(seed ^ 0xCA27901Eull, key, (u64)k));
+        episodes[e] += 1;
+        steps[e] = 0;
+        for (int k = 0; k < 4; k++) obs[4 * e + k] = (float)s[k];
+        if (reward) reward[e] = 0.f, terminated[e] = 0, done[e] = 0;
+        return;
+    }
+    double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+    const double force = actions[e] == 1 ? kForce : -kForce;
+    const double cos_t = cos(theta), sin_t = sin(theta);
+    const double total_mass = kMassCart + kMassPole, pole_ml = kMassPole * kHalfLength;
+    const double temp = (force + pole_ml * theta_dot * theta_dot * sin_t) / total_mass;
+    const double theta_acc = (kGravity * sin_t - cos_t * temp) / (kHalfLength * (4.0 / 3.0 - kMassPole * cos_t * cos_t / total_mass));
+    const double x_acc = temp - pole_ml * theta_acc * cos_t / total_mass;
+    const double nx = x + kTau * x_dot, nx_dot = x_dot + kTau * x_acc;
+    const double nth = theta + kTau * theta_dot, nth_dot = theta_dot + kTau * theta_acc;
+    s[0] = nx, s[1] = nx_dot, s[2] = nth, s[3] = nth_dot;
+    const int st = steps[e] + 1;
+    steps[e] = st;
+    const double theta_limit = 12 * 2 * kPi / 360, x_limit = 2.4;
+    const bool term = nx < -x_limit || nx > x_limit || nth < -theta_limit || nth > theta_limit;
+    const bool trunc = !term && st >= max_steps;
+    for (int k = 0; k < 4; k++) obs[4 * e + k] = (float)s[k];
+    reward[e] = 1.f;
+    terminated[e] = term ? 1 : 0;
+    done[e] = (term || trunc) ? 1 : 0;
+}
+
+int set_lds(const void *fn, size_t bytes) {
+    if (bytes > 65536) SRLX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SRLX_OK;
+}
+
+GradAdam segments(const srlx_mlpq *h) {
+    GradAdam a{};
+    a.nseg = 2 * (h->L + 1);
+    i64 run = 0;
+    for (int l = 0; l <= h->L; l++) {
+        const int In = l == 0 ? h->D : h->W[l - 1], Out = l < h->L ? h->W[l] : h->A;
+        run += (i64)Out * In;
+        a.seg_end[2 * l] = run, a.seg_out[2 * l] = Out, a.seg_in[2 * l] = In;
+        run += Out;
+        a.seg_end[2 * l + 1] = run, a.seg_out[2 * l + 1] = Out, a.seg_in[2 * l + 1] = 0;
+    }
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int64_t max_rows, int64_t max_batch, int device) {
+    SRLX_REQUIRE(out && widths, "mlpq_create: NULL argument");
+    *out = nullptr;
+    SRLX_REQUIRE(obs_dim >= 1 && obs_dim <= 256, "mlpq_create: %d observation elements (covered: 1..256)", obs_dim);
+    SRLX_REQUIRE(n_layers >= 1 && n_layers <= 3, "mlpq_create: %d dense layers (covered: 1..3)", n_layers);
+    for (int l = 0; l < n_layers; l++)
+        SRLX_REQUIRE(widths[l] >= 32 && widths[l] <= 512 && widths[l] % 32 == 0, "mlpq_create: layer width %d (covered: 32..512, multiples of 32)", widths[l]);
+    SRLX_REQUIRE(n_actions >= 2 && n_actions <= 32, "mlpq_create: %d actions (covered: 2..32)", n_actions);
+    SRLX_REQUIRE(max_rows >= 1 && max_batch >= 0 && max_batch <= 256, "mlpq_create: max_rows %lld, max_batch %lld (learner batches <= 256)", (long long)max_rows,
+                 (long long)max_batch);
+    srlx::DeviceGuard g(device);
+    SRLX_REQUIRE(g.ok, "mlpq_create: device %d unavailable", device);
+    srlx_mlpq *h = new srlx_mlpq();
+    h->D = obs_dim, h->L = n_layers, h->A = n_actions, h->device = device;
+    h->max_rows = max_rows, h->max_batch = max_batch;
+    h->wmax = obs_dim > n_actions ? obs_dim : n_actions;
+    for (int l = 0; l < n_layers; l++) {
+        h->W[l] = widths[l];
+        if (widths[l] > h->wmax) h->wmax = widths[l];
+    }
+    if (max_batch > 0) {
+        const size_t plane = (size_t)max_batch * h->wmax;
+        hipError_t e = hipMalloc((void **)&h->x0, sizeof(float) * max_batch * obs_dim);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->h, sizeof(float) * 3 * plane);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->dh, sizeof(float) * 3 * plane);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->q_on_next, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->q_tg_next, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->grad_q, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->loss_rows, sizeof(double) * max_batch);
+        if (e != hipSuccess) {
+            srlx_mlpq_destroy(h);
+            srlx::set_error("mlpq_create: hipMalloc failed: %s", hipGetErrorString(e));
+            return SRLX_ERR_NOMEM;
+        }
+    }
+    const int S = lds_stride(h);
+    int st = set_lds((const void *)k_mlpq_actor, sizeof(float) * (2 * kRows * S + kWTile));
+    if (st == SRLX_OK) st = set_lds((const void *)k_mlpq_learn_rows, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
+    if (st != SRLX_OK) {
+        srlx_mlpq_destroy(h);
+        return st;
+    }
+    *out = h;
+    return SRLX_OK;
+}
+
+int srlx_mlpq_destroy(srlx_mlpq_t *h) {
+    if (!h) return SRLX_OK;
+    srlx::DeviceGuard g(h->device);
+    for (void *p : {h->d_net, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->q_on_next, (void *)h->q_tg_next, (void *)h->grad_q, (void *)h->loss_rows})
+        if (p) (void)hipFree(p);
+    delete h;
+    return SRLX_OK;
+}
+
+int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params) {
+    SRLX_REQUIRE(h && d_params, "mlpq_bind: NULL argument");
+    for (int i = 0; i < 2 * (h->L + 1); i++) {
+        SRLX_REQUIRE(d_params[i], "mlpq_bind: parameter %d is NULL", i);
+        h->p[i] = d_params[i];
+    }
+    h->bound = true;
+    srlx::DeviceGuard g(h->device);
+    if (!h->d_net) SRLX_HIP(hipMalloc(&h->d_net, sizeof(Net)));
+    const Net n = net_of(h);
+    SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(Net), hipMemcpyHostToDevice));
+    return SRLX_OK;
+}
+
+int srlx_mlpq_bind_grads(srlx_mlpq_t *h, float *const *d_grads) {
+    SRLX_REQUIRE(h, "mlpq_bind_grads: NULL handle");
+    for (int i = 0; i < 2 * (h->L + 1); i++) h->grads[i] = d_grads ? d_grads[i] : nullptr;
+    return SRLX_OK;
+}
+
+int srlx_mlpq_bind_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, double lr, double beta1, double beta2, double eps) {
+    SRLX_REQUIRE(h && d_exp_avg && d_exp_avg_sq, "mlpq_bind_adam: NULL argument");
+    for (int i = 0; i < 2 * (h->L + 1); i++) {
+        SRLX_REQUIRE(d_exp_avg[i] && d_exp_avg_sq[i], "mlpq_bind_adam: state %d is NULL", i);
+        h->m[i] = d_exp_avg[i], h->v[i] = d_exp_avg_sq[i];
+    }
+    h->lr = lr, h->beta1 = beta1, h->beta2 = beta2, h->eps = eps;
+    h->adam = true;
+    return SRLX_OK;
+}
+
+int srlx_mlpq_forward(srlx_mlpq_t *h, int64_t rows, const float *d_obs, const int64_t *d_row_offsets, float *d_q, const float *d_eps, uint64_t seed,
+                      const int64_t *d_counter, int32_t *d_actions, void *stream) {
+    SRLX_REQUIRE(h && h->bound && d_obs, "mlpq_forward: unbound handle or NULL observations");
+    SRLX_REQUIRE(rows >= 1 && rows <= h->max_rows, "mlpq_forward: %lld rows (handle sized for %lld)", (long long)rows, (long long)h->max_rows);
+    SRLX_REQUIRE(!d_actions || (d_eps && d_counter), "mlpq_forward: the policy needs eps and the counter");
+    SRLX_REQUIRE(d_q || d_actions, "mlpq_forward: nothing to write");
+    srlx::DeviceGuard g(h->device);
+    const int S = lds_stride(h);
+    Policy pol{(u64)seed, (const i64 *)d_counter, d_eps, d_actions};
+    hipLaunchKernelGGL(k_mlpq_actor, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(kThreads), sizeof(float) * (2 * kRows * S + kWTile), (hipStream_t)stream, net_of(h),
+                       (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batch, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions,
+                         const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
+                         const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
+    SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_step: unbound handle");
+    SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A, "mlpq_train_step: online and target shapes differ");
+    for (int l = 0; l < h->L; l++) SRLX_REQUIRE(h->W[l] == target->W[l], "mlpq_train_step: online and target layer widths differ");
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "mlpq_train_step: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_obs_base && d_offsets && d_actions && d_rewards && d_terminated && d_weights && d_q0 && d_target && d_loss && d_priorities,
+                 "mlpq_train_step: NULL argument");
+    SRLX_REQUIRE(!h->adam || d_steps_taken, "mlpq_train_step: Adam needs the step count");
+    bool any_grad = false;
+    for (int i = 0; i < 2 * (h->L + 1); i++) any_grad |= h->grads[i] != nullptr;
+    SRLX_REQUIRE(h->adam || any_grad, "mlpq_train_step: neither gradients nor Adam bound");
+    srlx::DeviceGuard g(h->device);
+    const int S = lds_stride(h);
+    Learn a{};
+    a.B = batch, a.obs = d_obs_base, a.off = (const i64 *)d_offsets;
+    a.x0 = h->x0, a.h = h->h, a.dh = h->dh, a.q0 = d_q0, a.grad_q = h->grad_q, a.loss_rows = h->loss_rows;
+    a.hstride = (int)(h->max_batch * h->wmax);
+    srlx::TdArgs &td = a.td;
+    td.B = batch, td.n = 1, td.A = h->A;
+    td.q_on_next = h->q_on_next, td.q_tg_next = h->q_tg_next, td.q_on_0 = d_q0;
+    td.actions = d_actions, td.rewards = d_rewards, td.terminated = d_terminated, td.invalid_next = nullptr, td.weights = d_weights;
+    td.discount = discount, td.retrace_h = 1.0, td.double_dqn = double_dqn, td.rescale = rescale;
+    td.target = d_target, td.loss = d_loss, td.grad_q0 = h->grad_q, td.priorities = d_priorities;
+    td.on_next_stride = h->A, td.on_0_stride = h->A;
+    td.disc_ps = nullptr, td.td_signed = nullptr;
+    hipLaunchKernelGGL(k_mlpq_learn_rows, dim3((unsigned)((batch + kItems - 1) / kItems)), dim3(kThreads), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile),
+                       (hipStream_t)stream, (const Net *)h->d_net, (const Net *)target->d_net, a, S);
+    GradAdam ga = segments(h);
+    ga.B = batch;
+    for (int l = 0; l <= h->L; l++) {
+        const i64 plane = h->max_batch * h->wmax;
+        const float *dout = l < h->L ? h->dh + l * plane : h->grad_q;
+        const float *xin = l == 0 ? h->x0 : h->h + (l - 1) * plane;
+        for (int k = 0; k < 2; k++) {
+            const int s = 2 * l + k;
+            ga.dout[s] = dout, ga.xin[s] = xin;
+            ga.p[s] = h->p[s], ga.g[s] = h->grads[s], ga.m[s] = h->m[s], ga.v[s] = h->v[s];
+        }
+    }
+    ga.adam = h->adam ? 1 : 0;
+    ga.lr = h->lr, ga.beta1 = h->beta1, ga.beta2 = h->beta2, ga.eps = h->eps;
+    ga.steps_taken = (const i64 *)d_steps_taken;
+    ga.loss_rows = h->loss_rows, ga.loss = d_loss;
+    const i64 total = ga.seg_end[ga.nseg - 1];
+    hipLaunchKernelGGL(k_mlpq_grad_adam, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream) {
+    SRLX_REQUIRE(src && dst && src->bound && dst->bound, "mlpq_publish: unbound handle");
+    SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A, "mlpq_publish: shapes differ");
+    for (int l = 0; l < src->L; l++) SRLX_REQUIRE(src->W[l] == dst->W[l], "mlpq_publish: shapes differ");
+    srlx::DeviceGuard g(src->device);
+    GradAdam c = segments(src);
+    for (int s = 0; s < c.nseg; s++) c.p[s] = src->p[s], c.g[s] = dst->p[s];
+    const i64 total = c.seg_end[c.nseg - 1];
+    hipLaunchKernelGGL(k_mlpq_copy, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, c.nseg, c);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
+                       int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream) {
+    SRLX_REQUIRE(n_envs > 0 && d_state && d_steps && d_episodes && d_obs && max_steps > 0, "cartpole_step: bad argument");
+    SRLX_REQUIRE(!d_needs_reset || (d_actions && d_reward && d_terminated && d_done), "cartpole_step: a step needs actions and the scalar outputs");
+    hipLaunchKernelGGL(k_cartpole, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (i64)n_envs, d_state, d_steps, d_episodes,
+                       d_needs_reset, d_actions, (i64)max_steps, (u64)seed, d_obs, d_reward, d_terminated, d_done);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+}  // extern "C"

@@ -580,7 +580,7 @@ int srlx_store_stack_current(srlx_store_t *h, float *d_out, void *stream) {
 int srlx_store_commit_step_ex(srlx_store_t *h, const int32_t *d_actions, const float *d_rewards, const uint8_t *d_terminated, const uint8_t *d_done,
                               const void *d_next_obs, uint8_t *d_item_mask, int64_t *d_next_frame_table, int advance, int64_t *d_bump, void *stream) {
     SRLX_REQUIRE(h && d_actions && d_rewards && d_terminated && d_done && d_next_obs, "store_commit_step: NULL argument");
-    SRLX_REQUIRE(!d_next_frame_table || h->d.obs_dtype == SRLX_OBS_U8, "store_commit_step: frame tables exist for uint8 stores only");
+    SRLX_REQUIRE(!d_next_frame_table || h->d.obs_dtype == SRLX_OBS_U8 || h->d.W == 1, "store_commit_step: frame tables exist for uint8 stores and window-1 float32 stores");
     srlx::DeviceGuard guard(h->device);
     hipStream_t st = pick(h, stream);
     const StoreDev &d = h->d;
@@ -597,7 +597,7 @@ int srlx_store_commit_step_ex(srlx_store_t *h, const int32_t *d_actions, const f
 int srlx_store_commit_step_at(srlx_store_t *h, int64_t position, const int32_t *d_actions, const float *d_rewards, const uint8_t *d_terminated, const uint8_t *d_done,
                               const void *d_next_obs, uint8_t *d_item_mask, int64_t *d_next_frame_table, int64_t *d_bump, void *stream) {
     SRLX_REQUIRE(h && d_actions && d_rewards && d_terminated && d_done && d_next_obs && position >= 0, "store_commit_step_at: bad argument");
-    SRLX_REQUIRE(!d_next_frame_table || h->d.obs_dtype == SRLX_OBS_U8, "store_commit_step_at: frame tables exist for uint8 stores only");
+    SRLX_REQUIRE(!d_next_frame_table || h->d.obs_dtype == SRLX_OBS_U8 || h->d.W == 1, "store_commit_step_at: frame tables exist for uint8 stores and window-1 float32 stores");
     srlx::DeviceGuard guard(h->device);
     hipStream_t st = pick(h, stream);
     const StoreDev &d = h->d;
@@ -872,7 +872,7 @@ int srlx_store_obs_base(srlx_store_t *h, void **d_base, int64_t *frame_bytes) {
 
 int srlx_store_frame_table_current(srlx_store_t *h, int64_t *d_out, void *stream) {
     SRLX_REQUIRE(h && d_out, "store_frame_table_current: NULL argument");
-    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8, "store_frame_table_current: uint8 stores only");
+    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8 || h->d.W == 1, "store_frame_table_current: uint8 stores and window-1 float32 stores only");
     srlx::DeviceGuard guard(h->device);
     const i64 n = h->d.E * h->d.W;
     hipLaunchKernelGGL(k_frame_table_current, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pick(h, stream), h->d, (i64 *)d_out);
@@ -884,7 +884,7 @@ int srlx_store_gather_items(srlx_store_t *h, int64_t batch, const int64_t *d_tre
                             int32_t *d_actions, float *d_rewards, float *d_terminated, void *stream) {
     SRLX_REQUIRE(h && d_tree_idx && d_frame_off && d_actions && d_rewards && d_terminated, "store_gather_items: NULL argument");
     SRLX_REQUIRE(batch > 0 && k_begin >= 0 && k_count > 0 && k_begin + k_count <= h->d.n + 1, "store_gather_items: bad range");
-    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8, "store_gather_items: uint8 stores only");
+    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8 || h->d.W == 1, "store_gather_items: uint8 stores and window-1 float32 stores only");
     srlx::DeviceGuard guard(h->device);
     hipStream_t st = pick(h, stream);
     SRLX_TRY(h->scratch.reserve((size_t)batch * sizeof(ItemMeta)));
@@ -902,7 +902,7 @@ int srlx_store_gather_train(srlx_store_t *h, int64_t batch, const int64_t *d_tre
                             int32_t *d_actions, float *d_rewards, float *d_terminated, void *stream) {
     SRLX_REQUIRE(h && d_tree_idx && d_frame_off_all && d_actions && d_rewards && d_terminated, "store_gather_train: NULL argument");
     SRLX_REQUIRE(batch > 0, "store_gather_train: empty batch");
-    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8, "store_gather_train: uint8 stores only");
+    SRLX_REQUIRE(h->d.obs_dtype == SRLX_OBS_U8 || h->d.W == 1, "store_gather_train: uint8 stores and window-1 float32 stores only");
     srlx::DeviceGuard guard(h->device);
     hipStream_t st = pick(h, stream);
     SRLX_TRY(h->scratch.reserve((size_t)batch * sizeof(ItemMeta)));

@@ -1,0 +1,321 @@
+"""DQN on flat observations on the device engine: the MLP Q-network of libsrlx (`srlx_mlpq_*`, srlx_mlpq.hip), a device-resident batch CartPole, and
+`VectorQEngine`, which speaks the driver surface `VectorActor` / `VectorLearner` call on `RainbowEngine` (device/vector_runner.py).
+
+Reference semantics kept (file:line under the reference root):
+  srl/algorithms/dqn/model_torch.py:17-29   in_block -> hidden_block (MLP) -> out_layer             -> EngineMLPQNet
+  srl/algorithms/dqn/dqn.py:144-176         the 1-step (double) DQN target                           -> srlx_mlpq_train_step
+  srl/algorithms/dqn/model_torch.py:89-131  IS-weighted Huber loss, Adam, priorities, target sync   -> srlx_mlpq_train_step, srlx_mlpq_publish
+The replay is the engine's `DeviceReplay` with float32 observations, window 1 and 1-step items.
+"""
+import ctypes
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from simple_distributed_rl_amd import _native as N
+from simple_distributed_rl_amd.device.replay import DeviceReplay
+
+
+class EngineMLPQNet(nn.Module):
+    """DQN's module tree for a flat input (algorithms/dqn.py:build_qnetwork): `in_sizes` = the input value block's layers, `hidden_sizes` = the MLP hidden
+    block's, every one Linear + ReLU, then `out_layer`.  Parameters stay in torch's Linear layout, which is the one libsrlx reads."""
+
+    def __init__(self, obs_dim: int, in_sizes: Sequence[int], hidden_sizes: Sequence[int], n_actions: int):
+        super().__init__()
+        self.obs_dim, self.n_actions = int(obs_dim), int(n_actions)
+        self.in_sizes, self.hidden_sizes = tuple(int(x) for x in in_sizes), tuple(int(x) for x in hidden_sizes)
+        sizes = self.in_sizes + self.hidden_sizes
+        self.layers = nn.ModuleList()
+        prev = self.obs_dim
+        for s in sizes:
+            self.layers.append(nn.Linear(prev, s))
+            prev = s
+        self.out_layer = nn.Linear(prev, self.n_actions)
+        # the reference's keys: in_block.hidden_layers = [Flatten, Linear, ReLU, ...], hidden_block.hidden_layers = [Linear, ReLU, ...]
+        self._keys = [f"in_block.hidden_layers.{1 + 2 * k}" for k in range(len(self.in_sizes))]
+        self._keys += [f"hidden_block.hidden_layers.{2 * k}" for k in range(len(self.hidden_sizes))]
+        self._keys.append("out_layer")
+        self.weights_version = 0
+
+    @property
+    def widths(self):
+        return self.in_sizes + self.hidden_sizes
+
+    def forward(self, x):
+        x = x.reshape(x.shape[0], -1)
+        for layer in self.layers:
+            x = F.relu(layer(x))
+        return self.out_layer(x)
+
+    def _linears(self):
+        return list(self.layers) + [self.out_layer]
+
+    def kernel_parameters(self):
+        """The tensors libsrlx binds, in the reference's key order: weight then bias of every layer, out_layer last."""
+        ps = []
+        for lin in self._linears():
+            ps += [lin.weight, lin.bias]
+        return ps
+
+    def load_reference_state_dict(self, sd):
+        self.weights_version += 1
+        with torch.no_grad():
+            for key, lin in zip(self._keys, self._linears()):
+                lin.weight.copy_(sd[key + ".weight"])
+                lin.bias.copy_(sd[key + ".bias"])
+        return self
+
+    def reference_state_dict(self):
+        sd = {}
+        for key, lin in zip(self._keys, self._linears()):
+            sd[key + ".weight"] = lin.weight.detach().clone()
+            sd[key + ".bias"] = lin.bias.detach().clone()
+        return sd
+
+
+class MLPQHandle:
+    """One libsrlx handle over an EngineMLPQNet's parameters (zero copy).  `max_batch` > 0: the handle trains -- gradient tensors (`p.grad`) and, with `lr`,
+    torch's Adam state are bound, and `train_step` runs the whole update in two launches."""
+
+    def __init__(self, net: EngineMLPQNet, max_rows: int, device: int = 0, max_batch: int = 0, lr: Optional[float] = None, betas=(0.9, 0.999),
+                 eps: float = 1e-8, write_grads: bool = True):
+        self.lib = N.lib()
+        self.net = net
+        widths = (ctypes.c_int * 3)(*(list(net.widths) + [0, 0, 0])[:3])
+        h = N.c_p()
+        N.check(self.lib.srlx_mlpq_create(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.n_actions, int(max_rows), int(max_batch),
+                                          int(device)))
+        self.h = h
+        self.params = net.kernel_parameters()
+        assert all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params)
+        self._ptab = (N.c_p * len(self.params))(*[p.data_ptr() for p in self.params])
+        N.check(self.lib.srlx_mlpq_bind(h, ctypes.cast(self._ptab, N.c_p)))
+        self.exp_avg = self.exp_avg_sq = None
+        if max_batch > 0:
+            for p in self.params:
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+            if write_grads:
+                self._gtab = (N.c_p * len(self.params))(*[p.grad.data_ptr() for p in self.params])
+                N.check(self.lib.srlx_mlpq_bind_grads(h, ctypes.cast(self._gtab, N.c_p)))
+            if lr is not None:
+                self.exp_avg = [torch.zeros_like(p) for p in self.params]
+                self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+                self._mtab = (N.c_p * len(self.params))(*[t.data_ptr() for t in self.exp_avg])
+                self._vtab = (N.c_p * len(self.params))(*[t.data_ptr() for t in self.exp_avg_sq])
+                N.check(self.lib.srlx_mlpq_bind_adam(h, ctypes.cast(self._mtab, N.c_p), ctypes.cast(self._vtab, N.c_p), float(lr), float(betas[0]), float(betas[1]),
+                                                     float(eps)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                torch.cuda.synchronize()
+                self.lib.srlx_mlpq_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def forward(self, rows: int, obs, offsets=None, q=None, eps=None, seed: int = 0, counter=None, actions=None):
+        """Q of `rows` observations (obs: a float32 tensor, or a device address with `offsets` int64 [rows] element offsets) and, with `actions`, the
+        epsilon-greedy action of every row in the same launch."""
+        base = obs if isinstance(obs, int) else obs.data_ptr()
+        N.check(self.lib.srlx_mlpq_forward(self.h, int(rows), N.c_p(base), N.tptr(offsets), N.tptr(q), N.tptr(eps), ctypes.c_uint64(seed & (2**64 - 1)),
+                                           N.tptr(counter), N.tptr(actions), N.torch_stream_ptr()))
+        return q
+
+    def train_step(self, target: "MLPQHandle", batch: int, obs_base: int, offsets, actions, rewards, terminated, weights, discount: float, double_dqn: bool,
+                   rescale: bool, steps_taken, q0, target_out, loss, priorities):
+        N.check(self.lib.srlx_mlpq_train_step(self.h, target.h, int(batch), N.c_p(obs_base), N.tptr(offsets), N.tptr(actions), N.tptr(rewards), N.tptr(terminated),
+                                              N.tptr(weights), float(discount), int(bool(double_dqn)), int(bool(rescale)), N.tptr(steps_taken), N.tptr(q0),
+                                              N.tptr(target_out), N.tptr(loss), N.tptr(priorities), N.torch_stream_ptr()))
+
+    def publish_to(self, dst: "MLPQHandle"):
+        """Every parameter of this handle's network into `dst`'s (one launch, on the current stream)."""
+        N.check(self.lib.srlx_mlpq_publish(self.h, dst.h, N.torch_stream_ptr()))
+
+
+class CartPoleVecEnv:
+    """E device-resident CartPole-v1 environments (envs/cartpole.py, libsrlx srlx_cartpole_step): float64 state, float32 observations.  A lane that ended gets
+    its next episode on the NEXT lock-step, which only delivers that episode's first observation (the store's needs_reset protocol)."""
+
+    capturable = True
+
+    def __init__(self, replay: DeviceReplay, max_steps: int = 500, seed: Optional[int] = None):
+        assert not replay.obs_uint8 and replay.F == 4
+        self.replay, self.E, self.max_steps = replay, replay.E, int(max_steps)
+        self.seed = replay.seed if seed is None else int(seed)
+        d = replay.dev
+        self.lib = N.lib()
+        self.state = torch.zeros((self.E, 4), dtype=torch.float64, device=d)
+        self.steps = torch.zeros(self.E, dtype=torch.int32, device=d)
+        self.episodes = torch.zeros(self.E, dtype=torch.int32, device=d)
+        self.next_obs = torch.zeros((self.E, 4), dtype=torch.float32, device=d)
+        self.rewards = torch.zeros(self.E, dtype=torch.float32, device=d)
+        self.terminated = torch.zeros(self.E, dtype=torch.uint8, device=d)
+        self.done = torch.zeros(self.E, dtype=torch.uint8, device=d)
+
+    def reset(self) -> torch.Tensor:
+        N.check(self.lib.srlx_cartpole_step(self.E, N.tptr(self.state), N.tptr(self.steps), N.tptr(self.episodes), None, None, self.max_steps, ctypes.c_uint64(self.seed),
+                                            N.tptr(self.next_obs), None, None, None, N.torch_stream_ptr()))
+        return self.next_obs.clone()
+
+    def step(self, actions: torch.Tensor):
+        N.check(self.lib.srlx_cartpole_step(self.E, N.tptr(self.state), N.tptr(self.steps), N.tptr(self.episodes), self.replay.needs_reset_ptr, N.tptr(actions),
+                                            self.max_steps, ctypes.c_uint64(self.seed), N.tptr(self.next_obs), N.tptr(self.rewards), N.tptr(self.terminated),
+                                            N.tptr(self.done), N.torch_stream_ptr()))
+        return self.next_obs, self.rewards, self.terminated, self.done
+
+
+@dataclass
+class VectorQConfig:
+    # --- dqn.Config fields (srl/algorithms/dqn/dqn.py:50-101)
+    batch_size: int = 32
+    epsilon: float = 0.1
+    test_epsilon: float = 0.0
+    lr: float = 0.001
+    discount: float = 0.99
+    target_model_update_interval: int = 1000
+    enable_reward_clip: bool = False
+    enable_double_dqn: bool = True
+    enable_rescale: bool = False
+    # --- memory
+    memory_capacity: int = 100_000
+    memory_warmup_size: int = 1000
+    memory_alpha: float = 0.0
+    memory_beta_initial: float = 0.4
+    memory_beta_steps: int = 1_000_000
+    memory_epsilon: float = 0.0001
+    memory_has_duplicate: bool = False
+    # --- model: input value block layers, then the hidden block's
+    obs_dim: int = 4
+    in_sizes: tuple = ()
+    hidden_sizes: tuple = (512,)
+    n_actions: int = 2
+    # --- engine
+    n_envs: int = 1024
+    seed: int = 0
+
+
+class VectorQEngine:
+    """E lock-stepped environments and DQN updates on one GPU for flat observations, every network pass in libsrlx:
+      actor_front   1 launch (Q rows + epsilon-greedy from the store's float ring) + the environments' step
+      actor_commit  ring commit (also writes the next pass's row table and advances the policy counter) + the replay's add
+      learner_step  the replay's draw + gather, srlx_mlpq_train_step (2 launches), the priority write-back (train_count += 1 on the device)
+    Actors and learner share one stream and one parameter set (no copy to refresh)."""
+
+    overlap = False
+
+    def __init__(self, cfg: VectorQConfig, device: int = 0, env=None):
+        self.cfg = cfg
+        self.dev = torch.device(f"cuda:{device}")
+        self.lib = N.lib()
+        torch.manual_seed(cfg.seed)
+        E, B, A, D = cfg.n_envs, cfg.batch_size, cfg.n_actions, cfg.obs_dim
+        ring_len = -(-cfg.memory_capacity // E) + 2  # item_len * E >= capacity (n_step 1 + window 1)
+        self.replay = DeviceReplay(E, ring_len, D, 1, 1, A, B, False, cfg.enable_reward_clip, cfg.memory_alpha, cfg.memory_beta_initial, cfg.memory_beta_steps,
+                                   cfg.memory_epsilon, cfg.memory_warmup_size, cfg.seed, device, has_duplicate=cfg.memory_has_duplicate,
+                                   # (a draw without replacement rejects repeats: 8 spare uniforms serve B <= 64 as in RainbowEngine; B = 128 from 512 items needs ~16)
+                                   sample_slack=8 if B <= 64 else 4 * B)
+        if env is None:
+            self.env = CartPoleVecEnv(self.replay)
+        else:
+            self.env = env(self.replay) if callable(env) else env
+        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A).to(self.dev)
+        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A).to(self.dev)
+        self.q_target.load_state_dict(self.q_online.state_dict())
+        self.q_actor = self.q_online
+        self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr)
+        self.inf_target = MLPQHandle(self.q_target, max(E, B), device)
+        d = self.dev
+        self.eps = torch.full((E,), float(cfg.epsilon), dtype=torch.float32, device=d)
+        self.actions = torch.zeros(E, dtype=torch.int32, device=d)
+        self.policy_counter = torch.zeros(1, dtype=torch.int64, device=d)
+        self.train_count_dev = torch.zeros(1, dtype=torch.int64, device=d)
+        self.replay.count_updates_in(self.train_count_dev)  # train_count += 1 rides on the priority write-back (= the Adam steps taken)
+        self.q0 = torch.zeros((B, A), dtype=torch.float32, device=d)
+        self.target = torch.zeros(B, dtype=torch.float32, device=d)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=d)
+        self.priorities = torch.zeros(B, dtype=torch.float32, device=d)
+        self.train_count = self.sync_count = self.total_env_steps = 0
+        self.ledger = None
+        self._learner_graph = None
+        self.first_obs = self.env.reset()
+        self.replay.reset_all(self.first_obs)
+
+    # ---- actors -----------------------------------------------------------------------------------
+    def actor_front(self, events=None):
+        r = self.replay
+        off = r.frame_table_current()  # (no launch: the last commit wrote it)
+        self.inf_online.forward(self.cfg.n_envs, r.obs_base, off.view(-1), eps=self.eps, seed=self.cfg.seed ^ 0xAC7, counter=self.policy_counter, actions=self.actions)
+        self.env.step(self.actions)
+
+    def actor_commit(self):
+        e = self.env
+        if self.ledger is not None:  # before the commit: the store's needs_reset view still marks the lanes that only received a first observation
+            self.ledger.account(e.rewards, e.done, self.replay.needs_reset_ptr)
+        self.replay.commit(self.actions, e.rewards, e.terminated, e.done, e.next_obs, next_table=True, bump=self.policy_counter)
+        self.total_env_steps += self.cfg.n_envs
+
+    def actor_step(self):
+        self.actor_front()
+        self.actor_commit()
+
+    def join_learner(self):
+        """(actors and learner share one stream)"""
+
+    def refresh_actor_copy(self):
+        """(the actors read the online parameters themselves)"""
+
+    # ---- learner ----------------------------------------------------------------------------------
+    def _learner_body(self):
+        cfg, r = self.cfg, self.replay
+        b = r.sample_items(self.train_count_dev, all_states=True)
+        self.inf_online.train_step(self.inf_target, cfg.batch_size, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, b.weights, cfg.discount,
+                                   cfg.enable_double_dqn, cfg.enable_rescale, self.train_count_dev, self.q0, self.target, self.loss, self.priorities)
+        r.update(b.indices, self.priorities)  # model_torch.py:121-122; train_count_dev += 1 in the same launch
+
+    def learner_step(self) -> bool:
+        if self.replay.is_warmup_needed():
+            return False
+        if self._learner_graph is not None:
+            self._learner_graph.replay()
+        else:
+            self._learner_body()
+        if self.train_count % self.cfg.target_model_update_interval == 0:  # model_torch.py:125-127 (fires at 0 too)
+            self.sync_target()
+        self.train_count += 1
+        return True
+
+    def sync_target(self):
+        self.inf_online.publish_to(self.inf_target)
+        self.sync_count += 1
+
+    def capture_graphs(self, actor: bool = True, learner: bool = True, warm_actor: bool = True, warm_learner: bool = True):
+        """The update (draw + gather, the two network launches, the write-back) as one HIP graph once the replay is warm; the actors stay eager."""
+        torch.cuda.synchronize(self.dev)
+        if actor and warm_actor:
+            self.actor_step()
+        if learner and warm_learner:
+            self.learner_step()  # a real update, eager
+        if learner and not self.replay.is_warmup_needed():
+            side = torch.cuda.Stream(device=self.dev)
+            side.wait_stream(torch.cuda.current_stream(self.dev))
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                    self._learner_body()
+            torch.cuda.current_stream(self.dev).wait_stream(side)
+            self._learner_graph = g
+        torch.cuda.synchronize(self.dev)
+
+    def step(self, learner_updates: int = 1):
+        self.actor_step()
+        for _ in range(learner_updates):
+            self.learner_step()
+
+    def info(self):
+        self.replay.check_draws()
+        return dict(loss=float(self.loss.item()), train_count=self.train_count, sync=self.sync_count, memory=self.replay.length())

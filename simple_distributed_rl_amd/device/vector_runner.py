@@ -113,16 +113,19 @@ class HostVecEnv:
 
     capturable = False  # step() synchronises with the host
 
-    def __init__(self, env_config, n_envs: int, device: torch.device, seed: Optional[int] = None, processor=None):
+    def __init__(self, env_config, n_envs: int, device: torch.device, seed: Optional[int] = None, processor=None, float_obs: bool = False):
         """processor: an ImageProcessor whose space has been remapped from this environment's (raw uint8 frames, e.g. ALE's 210 x 160 x 3):
         the raw frames are uploaded as they are and ONE srlx_image_preprocess launch per lock-step turns them into the ring's gray frames
-        -- the reference runs OpenCV per frame on the host and hands the network float32 (image_processor.py:104-151)."""
+        -- the reference runs OpenCV per frame on the host and hands the network float32 (image_processor.py:104-151).
+        float_obs: the observations go to a float32 ring as they are (a flat BoxSpace((D,)) environment: no /255 scaling, no processor)."""
         from simple_distributed_rl_amd.base.env.registration import make as make_env_run
 
         self.envs = [make_env_run(env_config) for _ in range(n_envs)]
         self.E, self.dev = n_envs, device
         self.seed = seed
         self.processor = processor
+        self.float_obs = bool(float_obs)
+        assert not (self.float_obs and processor is not None)
         sp = self.envs[0].observation_space
         if processor is not None:
             self._raw_shape = tuple(sp.shape)
@@ -131,9 +134,10 @@ class HostVecEnv:
         else:
             self.F = int(np.prod(sp.shape))
         self._scale = 255.0 if float(np.max(sp.high)) <= 1.0 else 1.0  # "0to1" frames (image_processor.py:140-142) back to bytes
-        self._host_obs = torch.zeros((n_envs, self.F), dtype=torch.uint8).pin_memory()
+        obs_dtype = torch.float32 if self.float_obs else torch.uint8
+        self._host_obs = torch.zeros((n_envs, self.F), dtype=obs_dtype).pin_memory()
         self._host_scal = torch.zeros((n_envs, 3), dtype=torch.float32).pin_memory()
-        self.next_obs = torch.zeros((n_envs, self.F), dtype=torch.uint8, device=device)
+        self.next_obs = torch.zeros((n_envs, self.F), dtype=obs_dtype, device=device)
         self.rewards = torch.zeros(n_envs, dtype=torch.float32, device=device)
         self.terminated = torch.zeros(n_envs, dtype=torch.uint8, device=device)
         self.done = torch.zeros(n_envs, dtype=torch.uint8, device=device)
@@ -141,6 +145,8 @@ class HostVecEnv:
         self._episodes = 0
 
     def _bytes(self, frame) -> np.ndarray:
+        if self.float_obs:
+            return np.asarray(frame, np.float32).reshape(-1)
         return np.rint(np.asarray(frame, np.float32).reshape(-1) * self._scale).astype(np.uint8)
 
     def _take(self, i: int):
@@ -176,7 +182,7 @@ class HostVecEnv:
     def reset(self) -> torch.Tensor:
         for i in range(self.E):
             self._reset_lane(i)
-        first = self._upload(torch.zeros((self.E, self.F), dtype=torch.uint8, device=self.dev))
+        first = self._upload(torch.zeros((self.E, self.F), dtype=self.next_obs.dtype, device=self.dev))
         torch.cuda.current_stream(self.dev).synchronize()
         return first
 
@@ -234,13 +240,13 @@ def why_not_vector(context, env, rl_config) -> str:
     if getattr(rl_config, "_obs_processors", None) and frame_processor(rl_config) is None:
         return "observation processors other than one ImageProcessor over uint8 frames are served by the plugin path"
     hw = _image_hw(frame_space(env, rl_config))
+    if kind == "dqn" and hw is None:  # flat observations: the MLP Q-network (device/mlpq.py, srlx_mlpq.hip)
+        return _why_not_flat_dqn(env, rl_config)
     if hw is None or hw[0] < 8 or hw[1] < 8:
         return "observations are not single-channel image frames (after the config's ImageProcessor, if any)"
-    mem = rl_config.memory
-    if mem.name not in ("Proportional", "Proportional_cpp", "ReplayBuffer"):
-        return f"no device replay for memory '{mem.name}'"
-    if mem.enable_demo_memory:
-        return "demo memory is served by the plugin memory"
+    why = _why_not_memory(rl_config)
+    if why:
+        return why
     if kind == "agent57_light":  # torch networks: any DQN-image / dueling shape the plugin builds
         if getattr(rl_config.input_block, "image", None) is None or rl_config.input_block.image.name != "DQN":
             return "input block is not the DQN image block"
@@ -269,6 +275,111 @@ def why_not_vector(context, env, rl_config) -> str:
     if rl_config.batch_size > 64:
         return "the hand-written gradient step covers batches of at most 64"
     return ""
+
+
+def _why_not_memory(rl_config) -> str:
+    mem = rl_config.memory
+    if mem.name not in ("Proportional", "Proportional_cpp", "ReplayBuffer"):
+        return f"no device replay for memory '{mem.name}'"
+    if mem.enable_demo_memory:
+        return "demo memory is served by the plugin memory"
+    return ""
+
+
+def flat_dim(space) -> Optional[int]:
+    """D for a flat BoxSpace((D,)) observation, None otherwise."""
+    from simple_distributed_rl_amd.base.spaces.box import BoxSpace
+
+    if type(space) is not BoxSpace or len(tuple(space.shape)) != 1 or _image_hw(space) is not None:
+        return None
+    return int(space.shape[0])
+
+
+def mlp_layer_sizes(rl_config):
+    """(input value block layers, hidden block layers) of a DQN config, or None when either block is not an MLP of ReLU layers."""
+    iv, hb = rl_config.input_block.value, rl_config.hidden_block
+    if iv.name != "MLP" or hb.name != "MLP":
+        return None
+    if any(str(b.kwargs.get("activation", "relu")).lower() != "relu" for b in (iv, hb)):
+        return None
+    return tuple(int(x) for x in iv.kwargs.get("layer_sizes", ())), tuple(int(x) for x in hb.kwargs.get("layer_sizes", ()))
+
+
+# the block kwargs the MLP Q-network's module tree does not depend on (rl/torch_/networks.py: InputValueBlock, MLPBlock); use_bias / input_flatten only at
+# their defaults -- without biases, or without the Flatten module, the reference's keys differ from EngineMLPQNet's
+_MLP_FREE_KWARGS = ("layer_sizes", "activation", "kernel_initializer", "bias_initializer")
+_MLP_DEFAULT_KWARGS = dict(use_bias=True, input_flatten=True)
+
+
+def _mlp_kwargs_reason(rl_config) -> str:
+    for b in (rl_config.input_block.value, rl_config.hidden_block):
+        for k, v in b.kwargs.items():
+            if k in _MLP_FREE_KWARGS or (k in _MLP_DEFAULT_KWARGS and v == _MLP_DEFAULT_KWARGS[k]):
+                continue
+            return f"the MLP Q-network covers Linear layers with biases after a Flatten; block option {k}={v!r} stays on the plugin path"
+    return ""
+
+
+def is_flat_dqn(env, rl_config) -> bool:
+    """Does this (environment, config) pair belong to the MLP Q-network engine (VectorQEngine) rather than the image engine?"""
+    return engine_kind(rl_config) == "dqn" and _image_hw(frame_space(env, rl_config)) is None
+
+
+def _why_not_flat_dqn(env, rl_config) -> str:
+    """dqn.Config on flat observations: the shapes srlx_mlpq covers (srlx.h)."""
+    space = frame_space(env, rl_config)
+    D = flat_dim(space)
+    if D is None:  # (neither image frames nor a flat vector: the reason every engine gave before flat observations were served)
+        return "observations are not single-channel image frames (after the config's ImageProcessor, if any)"
+    if getattr(rl_config, "_obs_processors", None):
+        return "observation processors on flat observations are served by the plugin path"
+    if D > 256:
+        return "the MLP Q-network reads at most 256 observation elements"
+    if rl_config.window_length != 1:
+        return "the MLP Q-network reads one observation (window_length 1)"
+    if env.action_space.n < 2:
+        return "the MLP Q-network serves at least 2 actions"
+    sizes = mlp_layer_sizes(rl_config)
+    if sizes is None:
+        return "the MLP Q-network's input value block and hidden block are MLPs of ReLU layers"
+    why = _mlp_kwargs_reason(rl_config)
+    if why:
+        return why
+    layers = sizes[0] + sizes[1]
+    if not 1 <= len(layers) <= 3:
+        return "the MLP Q-network covers 1 to 3 dense layers (input value block plus hidden block)"
+    if any(w % 32 != 0 or not 32 <= w <= 512 for w in layers):
+        return "the MLP Q-network covers dense layers of 32..512 units in multiples of 32"
+    if rl_config.batch_size > 256:
+        return "the MLP Q-network's gradient step covers batches of at most 256"
+    return _why_not_memory(rl_config)
+
+
+def auto_lanes_reason(env, rl_config, n_envs) -> str:
+    """Flat-observation DQN engages the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
+    if is_flat_dqn(env, rl_config) and isinstance(n_envs, str):
+        return "flat-observation DQN stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
+    return ""
+
+
+def mlp_config_from(rl_config, env, n_envs: int, seed: int):
+    """dqn.Config (srl/algorithms/dqn/dqn.py:50-101) on a flat observation -> VectorQConfig (device/mlpq.py)."""
+    from simple_distributed_rl_amd.device.mlpq import VectorQConfig
+
+    mem = rl_config.memory
+    prop = mem.name != "ReplayBuffer"
+    kw = mem.kwargs if prop else {}
+    ins, hid = mlp_layer_sizes(rl_config)
+    return VectorQConfig(
+        batch_size=rl_config.batch_size, epsilon=rl_config.epsilon, test_epsilon=rl_config.test_epsilon, lr=rl_config.lr, discount=rl_config.discount,
+        target_model_update_interval=rl_config.target_model_update_interval, enable_reward_clip=rl_config.enable_reward_clip,
+        enable_double_dqn=rl_config.enable_double_dqn, enable_rescale=rl_config.enable_rescale,
+        memory_capacity=mem.capacity, memory_warmup_size=mem.warmup_size,
+        memory_has_duplicate=bool(kw.get("has_duplicate", True)) if prop else False,
+        memory_alpha=float(kw.get("alpha", 0.0)), memory_beta_initial=float(kw.get("beta_initial", 0.4)),
+        memory_beta_steps=int(kw.get("beta_steps", 1_000_000)), memory_epsilon=float(kw.get("epsilon", 1e-4)),
+        obs_dim=flat_dim(frame_space(env, rl_config)), in_sizes=ins, hidden_sizes=hid, n_actions=env.action_space.n, n_envs=n_envs, seed=seed,
+    )
 
 
 def engine_kind(rl_config) -> Optional[str]:
@@ -354,7 +465,10 @@ class VectorActor(ActorDriver):
         maker = getattr(type(base), "device_vector", None)
         if maker is not None:
             return maker(replay, **self.env_run.config.kwargs)
-        env = HostVecEnv(self.env_run.config, self.lanes, replay.dev, context.seed, processor=frame_processor(self.rl_config))
+        if not replay.obs_uint8:  # flat observations (VectorQEngine)
+            env = HostVecEnv(self.env_run.config, self.lanes, replay.dev, context.seed, float_obs=True)
+        else:
+            env = HostVecEnv(self.env_run.config, self.lanes, replay.dev, context.seed, processor=frame_processor(self.rl_config))
         env.setup(context)
         return env
 
@@ -367,8 +481,14 @@ class VectorActor(ActorDriver):
         dev = torch.device(context.used_device_torch)
         if self.engine is None:  # the engine (replay included) lives as long as the Runner: a second train() continues on the same memory
             seed = 0 if context.seed is None else int(context.seed)
-            self.cfg = device_config_from(self.rl_config, self.env_run, self.lanes, seed)
-            self.engine = RainbowEngine(self.cfg, dev.index or 0, env=lambda replay: self._make_batch_env(replay, context), overlap=self.overlap)
+            if is_flat_dqn(self.env_run, self.rl_config):  # flat observations: the MLP Q-network engine
+                from simple_distributed_rl_amd.device.mlpq import VectorQEngine
+
+                self.cfg = mlp_config_from(self.rl_config, self.env_run, self.lanes, seed)
+                self.engine = VectorQEngine(self.cfg, dev.index or 0, env=lambda replay: self._make_batch_env(replay, context))
+            else:
+                self.cfg = device_config_from(self.rl_config, self.env_run, self.lanes, seed)
+                self.engine = RainbowEngine(self.cfg, dev.index or 0, env=lambda replay: self._make_batch_env(replay, context), overlap=self.overlap)
         eng = self.engine
         self._load_weights()
         if eng.ledger is None:

@@ -80,6 +80,13 @@ class CartPole(EnvBase):
         truncated = (not terminated) and self.steps >= self.max_steps
         return self.state.astype(np.float32), 1.0, terminated, truncated
 
+    @staticmethod
+    def device_vector(replay, max_steps: int = 500, **kwargs):
+        """E copies of this environment stepped on the GPU (libsrlx srlx_cartpole_step) for the device engine (device/vector_runner.py)."""
+        from simple_distributed_rl_amd.device.mlpq import CartPoleVecEnv
+
+        return CartPoleVecEnv(replay, max_steps=max_steps)
+
     def backup(self, **kwargs) -> Any:
         return (self.state.copy(), self.steps)
 

@@ -119,7 +119,7 @@ class Runner:
             return None
         from simple_distributed_rl_amd.device import vector_runner as vr
 
-        self.vector_reason = vr.why_not_vector(c, env, self.rl_config)
+        self.vector_reason = vr.why_not_vector(c, env, self.rl_config) or vr.auto_lanes_reason(env, self.rl_config, self._vector_envs)
         if self.vector_reason:
             return None
         lanes = self._vector_envs

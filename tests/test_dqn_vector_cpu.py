@@ -1,0 +1,125 @@
+"""DQN on flat observations, the parts that need no GPU: which shapes the MLP Q-network engine accepts (and the reason for each one it leaves to the plugin
+path), the mapping of dqn.Config onto VectorQConfig, EngineMLPQNet against the module tree algorithms/dqn.py:build_qnetwork builds, and the "AUTO" /
+explicit-count routing decision."""
+import types
+
+import pytest
+import torch
+
+import simple_distributed_rl_amd as srl
+from simple_distributed_rl_amd.algorithms import dqn, rainbow
+from simple_distributed_rl_amd.device import vector_runner as vr
+
+
+def _ctx():
+    return types.SimpleNamespace(used_device_torch="cuda:0")
+
+
+def _cartpole_cfg():
+    rl = dqn.Config(batch_size=32, lr=0.001, target_model_update_interval=200, discount=0.99)
+    rl.memory.set_replay_buffer()
+    rl.memory.capacity, rl.memory.warmup_size = 100_000, 500
+    rl.hidden_block.set((64, 64))
+    return rl
+
+
+def _reason(env_id, cfg):
+    r = srl.Runner(env_id, cfg)
+    r.setup_rl_config()
+    return vr.why_not_vector(_ctx(), r.env, r.rl_config)
+
+
+def test_cartpole_dqn_is_accepted():
+    assert _reason("CartPole-v1", _cartpole_cfg()) == ""
+    assert _reason("CartPole-v1", dqn.Config()) == ""  # DQN's default hidden block (512,)
+    c = dqn.Config()
+    c.input_block.value.set((32,))
+    c.hidden_block.set((64, 96), use_bias=True, kernel_initializer="he_normal")
+    assert _reason("CartPole-v1", c) == ""
+
+
+@pytest.mark.parametrize("change, env_id, reason", [
+    (lambda c: c.hidden_block.set((64, 64, 64, 64)), "CartPole-v1", "1 to 3 dense layers"),
+    (lambda c: c.hidden_block.set((48,)), "CartPole-v1", "32..512 units in multiples of 32"),
+    (lambda c: c.hidden_block.set((1024,)), "CartPole-v1", "32..512 units in multiples of 32"),
+    (lambda c: c.hidden_block.set((64,), activation="tanh"), "CartPole-v1", "MLPs of ReLU layers"),
+    (lambda c: setattr(c, "window_length", 2), "CartPole-v1", "window_length 1"),
+    (lambda c: setattr(c, "batch_size", 512), "CartPole-v1", "batches of at most 256"),
+    (lambda c: c.hidden_block.set((64,), use_bias=False), "CartPole-v1", "use_bias=False"),
+    (lambda c: c.input_block.value.set((32,), input_flatten=False), "CartPole-v1", "input_flatten=False"),
+    (lambda c: None, "Grid", "observations are not single-channel image frames (after the config's ImageProcessor, if any)"),  # the reason it had before
+])
+def test_uncovered_shapes_keep_the_plugin_path(change, env_id, reason):
+    c = _cartpole_cfg()
+    change(c)
+    assert reason in _reason(env_id, c)
+
+
+def test_more_than_32_actions_keep_the_existing_reason():
+    from simple_distributed_rl_amd.base.env import registration
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+    from simple_distributed_rl_amd.envs.cartpole import CartPole
+
+    class WideCartPole(CartPole):
+        @property
+        def action_space(self):
+            return DiscreteSpace(40)
+
+    registration.register("WideCartPole-test", __name__ + ":WideCartPole", {}, check_duplicate=False)
+    globals()["WideCartPole"] = WideCartPole
+    assert "at most 32 actions" in _reason("WideCartPole-test", _cartpole_cfg())
+
+
+def test_rainbow_on_flat_observations_keeps_its_reason():
+    assert "image" in _reason("CartPole-v1", rainbow.Config())
+    assert vr.engine_kind(dqn.Config()) == "dqn"
+
+
+def test_device_config_mapping():
+    r = srl.Runner("CartPole-v1", _cartpole_cfg())
+    r.setup_rl_config()
+    d = vr.mlp_config_from(r.rl_config, r.env, 256, 7)
+    assert (d.obs_dim, d.in_sizes, d.hidden_sizes, d.n_actions, d.n_envs, d.seed) == (4, (), (64, 64), 2, 256, 7)
+    assert (d.batch_size, d.lr, d.discount, d.target_model_update_interval, d.enable_double_dqn) == (32, 0.001, 0.99, 200, True)
+    assert (d.memory_capacity, d.memory_warmup_size, d.memory_alpha, d.memory_has_duplicate) == (100_000, 500, 0.0, False)  # the uniform ReplayBuffer
+    c = _cartpole_cfg()
+    c.memory.set_proportional(alpha=0.6, beta_initial=0.5)
+    c.input_block.value.set((32,))
+    r = srl.Runner("CartPole-v1", c)
+    r.setup_rl_config()
+    d = vr.mlp_config_from(r.rl_config, r.env, 16, 0)
+    assert (d.in_sizes, d.hidden_sizes, d.memory_alpha, d.memory_beta_initial) == ((32,), (64, 64), 0.6, 0.5)
+
+
+@pytest.mark.parametrize("in_sizes, hidden", [((), (64, 64)), ((), (512,)), ((32,), (96,))])
+def test_engine_mlp_qnet_speaks_the_dqn_module_tree(in_sizes, hidden):
+    from simple_distributed_rl_amd.algorithms.dqn import build_qnetwork
+    from simple_distributed_rl_amd.device.mlpq import EngineMLPQNet
+
+    c = dqn.Config()
+    c.input_block.value.set(in_sizes)
+    c.hidden_block.set(hidden)
+    r = srl.Runner("CartPole-v1", c)
+    r.setup_rl_config()
+    torch.manual_seed(4)
+    ref = build_qnetwork(r.rl_config)
+    net = EngineMLPQNet(4, in_sizes, hidden, 2).load_reference_state_dict(ref.state_dict())
+    sd = net.reference_state_dict()
+    assert list(sd) == list(ref.state_dict())
+    assert all(torch.equal(sd[k], v) for k, v in ref.state_dict().items())
+    x = torch.randn(33, 4, dtype=torch.float64)
+    with torch.no_grad():
+        want = ref.double()(x)
+        got = net.double()(x)
+    assert float((got - want).abs().max()) <= 1e-12 * float(want.abs().max())
+    assert len(net.kernel_parameters()) == 2 * (len(in_sizes) + len(hidden) + 1)
+
+
+def test_auto_keeps_flat_dqn_on_the_plugin_path():
+    r = srl.Runner("CartPole-v1", _cartpole_cfg())
+    r.setup_rl_config()
+    assert "set_vector_envs(n)" in vr.auto_lanes_reason(r.env, r.rl_config, "AUTO")
+    assert vr.auto_lanes_reason(r.env, r.rl_config, 256) == ""
+    img = srl.Runner("SyntheticAtari-v0", rainbow.Config())
+    img.setup_rl_config()
+    assert vr.auto_lanes_reason(img.env, img.rl_config, "AUTO") == ""  # image configs keep "AUTO" as it is
