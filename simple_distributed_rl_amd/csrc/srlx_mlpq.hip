@@ -172,16 +172,33 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, 
     if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.A, qs + t * S);
 }
 
+// srl/rl/functions.py:10-17 in float64 (one evaluation per item)
+__device__ __forceinline__ double rescaling64(double x) {
+    const double s = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0);
+    return s * (sqrt(fabs(x) + 1.0) - 1.0) + 0.001 * x;
+}
+__device__ __forceinline__ double inverse_rescaling64(double x) {
+    const double s = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0);
+    const double n = (sqrt(1.0 + 4.0 * 0.001 * (fabs(x) + 1.0 + 0.001)) - 1.0) / (2.0 * 0.001);
+    return s * (n * n - 1.0);
+}
+
 // srlx_td_math.h:td_rows at n = 1, written out (its per-step arrays, indexed by the run-time n, would live in scratch memory): dqn.py:144-176 -- the retrace sum
-// is the single term float32(gain * float32(discount ** 0)) * 1.0 = gain -- and model_torch.py:89-131.  Returns the item's Huber term (float64).
+// is the single term float32(gain * float32(discount ** 0)) * 1.0 = gain -- and model_torch.py:89-131.  With `rescale` the two value transforms run in float64.
+// Returns the item's Huber term (float64).
 __device__ __forceinline__ double td_one(const srlx::TdArgs &a, i64 b) {
     const int A = a.A;
     const float *qon = a.q_on_next + b * A, *qtg = a.q_tg_next + b * A;
     const int nact = srlx::argmax_masked(a.double_dqn ? qon : qtg, nullptr, A);
-    float maxq = qtg[nact];
-    if (a.rescale) maxq = srlx::inverse_rescaling(maxq);
-    float gain = a.rewards[b] + ((1.0f - a.terminated[b]) * (float)a.discount) * maxq;
-    if (a.rescale) gain = srlx::rescaling(gain);
+    const float maxq = qtg[nact];
+    float gain;
+    if (a.rescale) {
+        // (float64: in float32, sqrt(1 + 0.004 (|x| + 1.001)) - 1 of the inverse cancels to ~3e-5 relative, 5e-5 absolute on the target at |Q| ~ 1)
+        const double inv = inverse_rescaling64((double)maxq);
+        gain = (float)rescaling64((double)a.rewards[b] + ((1.0 - (double)a.terminated[b]) * a.discount) * inv);
+    } else {
+        gain = a.rewards[b] + ((1.0f - a.terminated[b]) * (float)a.discount) * maxq;
+    }
     const float target = gain;
     a.target[b] = target;
     const int a0 = a.actions[b];

@@ -81,3 +81,23 @@ def test_hardware_queue_default_is_set_before_the_runtime_starts():
     code = "import os; os.environ['GPU_MAX_HW_QUEUES'] = '4'; import simple_distributed_rl_amd._native as n; print(os.environ['GPU_MAX_HW_QUEUES'])"
     out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
     assert out.stdout.strip().splitlines()[-1] == "4"
+
+
+def test_mlpq_create_rejects_arguments_outside_its_envelope():
+    """srlx_mlpq_create validates before it touches a device: observation length 1..256, 1..3 layers of 32..512 units in multiples of 32, 2..32 actions,
+    learner batches <= 256, max_rows >= 1.  Each violation returns a status, sets srlx_last_error() and leaves the handle NULL."""
+    import ctypes
+
+    from simple_distributed_rl_amd import _native as N
+
+    lib = N.lib()
+    ok = dict(D=4, widths=(64,), A=2, max_rows=16, max_batch=32)
+    bad = [dict(D=0), dict(D=257), dict(widths=()), dict(widths=(64, 64, 64, 64)), dict(widths=(0,)), dict(widths=(31,)), dict(widths=(48,)), dict(widths=(544,)),
+           dict(widths=(64, 64, 48)), dict(A=1), dict(A=33), dict(max_batch=257), dict(max_rows=0)]
+    for change in bad:
+        c = dict(ok, **change)
+        widths = (ctypes.c_int * 4)(*(list(c["widths"]) + [0, 0, 0, 0])[:4])
+        h = N.c_p()
+        st = lib.srlx_mlpq_create(ctypes.byref(h), c["D"], len(c["widths"]), ctypes.cast(widths, N.c_p), c["A"], c["max_rows"], c["max_batch"], 0)
+        assert st != 0 and not h, change
+        assert b"mlpq_create" in lib.srlx_last_error(), change

@@ -123,3 +123,44 @@ def test_auto_keeps_flat_dqn_on_the_plugin_path():
     img = srl.Runner("SyntheticAtari-v0", rainbow.Config())
     img.setup_rl_config()
     assert vr.auto_lanes_reason(img.env, img.rl_config, "AUTO") == ""  # image configs keep "AUTO" as it is
+
+
+@pytest.mark.parametrize("shape_key", ["h64x64", "h512"])
+@pytest.mark.parametrize("double_dqn", [True, False])
+def test_float64_reference_matches_the_reference_trainer(shape_key, double_dqn):
+    """tests/mlpq_reference.py (the float64 yardstick of the GPU tests) against ONE recorded Trainer.train() of the reference's DQN
+    (tests/golden/train_step_dqn_vec.npz, inputs from tests/dqn_vec_recipe.py), at the bars of the GPU golden test: target, online Q of s_0, loss and priorities
+    within rel 1e-5; every p.grad within rel 1e-5 with an absolute slack of 1e-5 * max |g|; every parameter after Adam within rel 1e-5 (+ 1e-7), except entries
+    whose reference gradient is below 1e-4 * max |g| (the first Adam step is about lr * g / |g|: only the bound 2 lr holds there)."""
+    import os
+    import sys
+
+    import numpy as np
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, here)
+    import dqn_vec_recipe as R
+    import mlpq_reference as M
+
+    z = np.load(os.path.join(here, "golden", "train_step_dqn_vec.npz"))
+    hidden, name = R.SHAPES[shape_key], R.case_name(shape_key, double_dqn)
+    g = lambda k: z[f"{name}.{k}"]  # noqa: E731
+    keys = [k for k, _ in R.keys_shapes(hidden)]
+    on = [torch.tensor(R.recipe_state_dict(hidden, R.SEED_ONLINE)[k]).double() for k in keys]
+    tg = [torch.tensor(R.recipe_state_dict(hidden, R.SEED_TARGET)[k]).double() for k in keys]
+    s0, s1, actions, reward, undone, weights = (torch.tensor(a) for a in R.make_items())
+    lr = float(g("lr"))
+    out = M.learner_step(on, tg, s0.double(), s1.double(), actions.long(), reward.double(), 1.0 - undone.double(), weights.double(), float(g("discount")),
+                         double_dqn, False)
+    np.testing.assert_allclose(out.q0.numpy(), g("q0"), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(out.target.numpy(), g("target_q"), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(out.loss, float(g("loss")), rtol=1e-5)
+    np.testing.assert_allclose(out.priorities.numpy(), g("priorities"), rtol=1e-5, atol=1e-5 * float(np.abs(g("target_q")).max()))
+    after = M.adam_steps(on, [out.grads], lr)[0][0]
+    for k, grad, aft in zip(keys, out.grads, after):
+        gr, gmax = g("grad." + k), float(np.abs(g("grad." + k)).max())
+        np.testing.assert_allclose(grad.numpy(), gr, rtol=1e-5, atol=1e-5 * gmax, err_msg=k)
+        want = g("after." + k)
+        firm = np.abs(gr) >= 1e-4 * gmax
+        np.testing.assert_allclose(aft.numpy()[firm], want[firm], rtol=1e-5, atol=1e-7, err_msg=k)
+        assert np.abs(aft.numpy()[~firm] - want[~firm]).max(initial=0.0) <= 2 * lr * (1 + 1e-3), k

@@ -95,20 +95,14 @@ def test_fused_policy_selection():
     assert torch.equal(acts, first)
 
 
-def _huber_grad_ref(net64, tgt64, s0, s1, act, rew, term, w, discount, double_dqn):
-    """dqn.py:144-176 + model_torch.py:89-131 in float64 autograd: target, loss, priorities and every parameter's gradient."""
-    with torch.no_grad():
-        qt = tgt64(s1)
-        sel = net64(s1) if double_dqn else qt
-        maxq = qt.gather(1, sel.argmax(1, keepdim=True)).squeeze(1)
-        target = rew + (1 - term) * discount * maxq
-    for p in net64.parameters():
-        p.grad = None
-    q = net64(s0)
-    qa = q.gather(1, act.view(-1, 1)).squeeze(1)
-    loss = torch.nn.functional.huber_loss(target * w, qa * w, delta=1.0)
-    loss.backward()
-    return target, float(loss.detach()), (target - qa).abs().detach(), q.detach(), [p.grad.clone() for p in net64.kernel_parameters()]
+def _reference():
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mlpq_reference
+
+    return mlpq_reference
 
 
 @pytest.mark.parametrize("widths", [(64, 64), (512,)])
@@ -136,15 +130,10 @@ def test_learner_step_matches_float64_autograd_and_torch_adam(widths, double_dqn
     q0, target, loss, pri = torch.zeros(B, A, device="cuda"), torch.zeros(B, device="cuda"), torch.zeros(1, device="cuda"), torch.zeros(B, device="cuda")
     h.train_step(ht, B, obs.data_ptr(), off, act, rew, term, w, 0.99, double_dqn, False, steps, q0, target, loss, pri)
     torch.cuda.synchronize()
-    net64, tgt64 = _net(D, widths, A).double(), _net(D, widths, A).double()
-    with torch.no_grad():
-        for p, b in zip(net64.kernel_parameters(), before):
-            p.copy_(b.double())
-        for p, b in zip(tgt64.kernel_parameters(), tgt.kernel_parameters()):
-            p.copy_(b.double())
-    o = obs.double().view(B, 2, D)
-    t_ref, l_ref, p_ref, q_ref, g_ref = _huber_grad_ref(net64, tgt64, o[:, 0], o[:, 1], act.long().view(-1), rew.double().view(-1), term.double().view(-1),
-                                                        w.double(), 0.99, double_dqn)
+    o = obs.double().cpu().view(B, 2, D)
+    ref = _reference().learner_step([b.double().cpu() for b in before], [p.detach().double().cpu() for p in tgt.kernel_parameters()], o[:, 0], o[:, 1],
+                                    act.long().cpu().view(-1), rew.double().cpu().view(-1), term.double().cpu().view(-1), w.double().cpu(), 0.99, double_dqn)
+    t_ref, l_ref, p_ref, q_ref, g_ref = ref.target, ref.loss, ref.priorities, ref.q0, ref.grads
     np.testing.assert_allclose(q0.double().cpu(), q_ref.cpu(), rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(target.double().cpu(), t_ref.cpu(), rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(pri.double().cpu(), p_ref.cpu(), rtol=1e-5, atol=1e-6)
