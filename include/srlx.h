@@ -449,6 +449,55 @@ int srlx_ppo_net_adam(int obs_dim, int action_dim, float *d_params, float *d_gra
                       void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Discrete-action PPO on the vectorised path: a categorical policy head and a self-resetting CartPole (BASELINE config 1's
+ * environment).  Parity UNPINNED like the whole PPO row (the reference's PPO needs TensorFlow); restated from the cited lines
+ * and checked against tests/ppo_cat_reference.py + torch autograd.  The exact arithmetic: csrc/srlx_ppo_math.h.
+ *   srlx_ppo_categorical_act     : ppo.py:316-324 + srl/rl/tf/distributions/categorical_dist_block.py (CategoricalDist.sample /
+ *       mode / log_prob): logits f32 [rows][n_actions] -> action i32 [rows] by inverse CDF over the float32 softmax with ONE keyed
+ *       uniform per row (seed, *d_counter, row), *d_counter += 1; logprob f32 [rows] of the taken action floored at log(1e-6)
+ *       (ppo.py:324).  deterministic != 0: the first maximum (:318-319), no draw, d_counter may be NULL.
+ *   srlx_cartpole_autoreset_step : envs/cartpole.py:step (the reference reaches CartPole-v1 through srl/base/env/gym_user_wrapper.py)
+ *       for E lanes, float64 state [E][4], steps / episodes i32 [E] as srlx_cartpole_step keeps them; a lane whose step ends its
+ *       episode (termination, or steps >= max_steps) returns reward 1, done 1 and starts its next episode in the same call: d_obs
+ *       f32 [E][4] is then that episode's first observation (reset key: (seed ^ 0xCA27901E, lane << 32 | episode, k), as
+ *       srlx_cartpole_step).  A finished episode is never bootstrapped, truncation included (ppo.py:396-397).
+ * The fused network with this head (srlx_ppo_net.hip): the trunk of srlx_ppo_net_*, in -> 64 -> 64 -> {64 -> V, 64 -> n logits}
+ * (ppo.py:55-99 with a CategoricalDistBlock); parameters in `ActorCritic.parameters()` order: w1, b1, w2, b2, wv, bv, wvo, bvo, wp, bp,
+ * wlogit [n][64], blogit [n]; obs_dim 1..8, n_actions 2..8 (the heads table's eight policy slots per row).
+ *   srlx_ppo_cat_param_count / _partials_floats / _rollout_max_horizon : as their srlx_ppo_net_ counterparts (-1: not covered).
+ *   srlx_ppo_cat_forward   : v f32 [n], logits f32 [n][n_actions] of obs f32 [n][obs_dim].
+ *   srlx_ppo_cat_rollout   : ppo.py:316-324 (policy) + CartPole + :389-404 (GAE) for `horizon` steps of `n_envs` (a multiple of 16)
+ *       environments in ONE launch: the arithmetic of srlx_ppo_categorical_act (key: act_seed, *d_act_counter + t, env),
+ *       srlx_cartpole_autoreset_step and srlx_gae_scan run step by step; *d_act_counter += horizon.  env_obs f32 [E][4]; b_obs f32
+ *       [T+1][E][4], b_act i32 [T][E], b_logp / b_val / b_rew / b_adv f32 [T][E], b_done u8 [T][E], last_v, episode_return, finished as
+ *       srlx_ppo_net_rollout.
+ *   srlx_ppo_cat_minibatch : compute_train_loss (:102-169) with new_logpi = log_softmax(logits)[action] + backward, as
+ *       srlx_ppo_net_minibatch (entropy term of the taken action only, :166; d loss / d logit_k = g_lp ((k == a) - p_k)).
+ *   srlx_ppo_cat_adam      : srlx_ppo_net_adam over this head's parameter vector (the same reduction and clip + Adam kernels).
+ * ------------------------------------------------------------------------------------------------ */
+int srlx_ppo_categorical_act(int64_t rows, int n_actions, const float *d_logits, uint64_t seed, int64_t *d_counter, int deterministic,
+                             int32_t *d_action, float *d_logprob, void *stream);
+int srlx_cartpole_autoreset_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const int32_t *d_actions,
+                                 int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_done, void *stream);
+int srlx_ppo_cat_param_count(int obs_dim, int n_actions);
+int srlx_ppo_cat_partials_floats(int obs_dim, int n_actions);
+int srlx_ppo_cat_rollout_max_horizon(int n_actions);
+int srlx_ppo_cat_forward(int64_t n, int obs_dim, int n_actions, const float *d_params, const float *d_obs, float *d_v, float *d_logits,
+                         void *stream);
+int srlx_ppo_cat_rollout(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps,
+                         int32_t *d_episodes, float *d_env_obs, int64_t max_steps, uint64_t env_seed, uint64_t act_seed,
+                         int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act, float *d_b_logp,
+                         float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return,
+                         float *d_finished, void *stream);
+int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params,
+                           const float *d_b_obs, const int32_t *d_b_act, const float *d_b_logp, const float *d_b_adv,
+                           const float *d_b_v_target, const float *d_b_val, int baseline_advantage, int surrogate_clip,
+                           double policy_clip_range, int enable_value_clip, double value_clip_range, double value_loss_weight,
+                           double entropy_weight, float *d_partials, float *d_grad, float *d_losses, void *stream);
+int srlx_ppo_cat_adam(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step,
+                      double lr, double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Never-Give-Up intrinsic reward + Agent57_light priorities
  *
  * srlx_ngu_t: one bounded episodic memory per environment, [E][emb_dim][capacity] float32 in HBM

@@ -176,6 +176,16 @@ SIGNATURES = {
     "srlx_ppo_net_minibatch": (c_int, [c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_f64, c_int, c_f64, c_f64, c_f64, c_p, c_p, c_p,
                                        c_p]),
     "srlx_ppo_net_adam": (c_int, [c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_p]),
+    "srlx_ppo_categorical_act": (c_int, [c_i64, c_int, c_p, c_u64, c_p, c_int, c_p, c_p, c_p]),
+    "srlx_cartpole_autoreset_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_cat_param_count": (c_int, [c_int, c_int]),
+    "srlx_ppo_cat_partials_floats": (c_int, [c_int, c_int]),
+    "srlx_ppo_cat_rollout_max_horizon": (c_int, [c_int]),
+    "srlx_ppo_cat_forward": (c_int, [c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_cat_rollout": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_u64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                     c_p]),
+    "srlx_ppo_cat_minibatch": (c_int, [c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f64, c_int, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_cat_adam": (c_int, [c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_p]),
     "srlx_ngu_create": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_int, c_f64, c_f64, c_f64, c_int]),
     "srlx_ngu_destroy": (c_int, [c_p]),
     "srlx_ngu_reset": (c_int, [c_p, c_p]),

@@ -12,6 +12,7 @@
 //                     (srlx_adam_math.h) in the same thread; block 0 reduces the loss.
 #include "srlx_adam_math.h"
 #include "srlx_common.h"
+#include "srlx_ppo_math.h"
 #include "srlx_td_math.h"
 
 struct srlx_mlpq {
@@ -354,40 +355,27 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_copy(int nseg, GradAdam segs 
 }
 
 // ---- CartPole (envs/cartpole.py:step) for E lanes, float64 state -------------------------------------------------------------------------------------------
-constexpr double kGravity = 9.8, kMassCart = 1.0, kMassPole = 0.1, kHalfLength = 0.5, kForce = 10.0, kTau = 0.02;
-constexpr double kPi = 3.141592653589793;
-
+// (the step and the reset are srlx_ppo_math.h's: one definition with the self-resetting step of the PPO path)
 __global__ void __launch_bounds__(256) k_cartpole(i64 E, double *__restrict__ state, int32_t *__restrict__ steps, int32_t *__restrict__ episodes,
                                                   const u8 *__restrict__ needs_reset, const int32_t *__restrict__ actions, i64 max_steps, u64 seed,
                                                   float *__restrict__ obs, float *__restrict__ reward, u8 *__restrict__ terminated, u8 *__restrict__ done) {
     const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    double *s = state + 4 * e;
+    double s[4] = {state[4 * e], state[4 * e + 1], state[4 * e + 2], state[4 * e + 3]};
+    int st = steps[e];
     if (!needs_reset || needs_reset[e]) {  // the lane's next episode: uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane)
-        const u64 key = (u64)e * 0x100000000ull + (u64)(uint32_t)episodes[e];
-        for (int k = 0; k < 4; k++) s[k] = -0.05 + 0.1 * srlx::u53(srlx::rng_u64(seed ^ 0xCA27901Eull, key, (u64)k));
-        episodes[e] += 1;
-        steps[e] = 0;
-        for (int k = 0; k < 4; k++) obs[4 * e + k] = (float)s[k];
+        int ep = episodes[e];
+        srlxp::cartpole_reset(s, st, ep, seed, e);
+        episodes[e] = ep;
+        steps[e] = st;
+        for (int k = 0; k < 4; k++) state[4 * e + k] = s[k], obs[4 * e + k] = (float)s[k];
         if (reward) reward[e] = 0.f, terminated[e] = 0, done[e] = 0;
         return;
     }
-    double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
-    const double force = actions[e] == 1 ? kForce : -kForce;
-    const double cos_t = cos(theta), sin_t = sin(theta);
-    const double total_mass = kMassCart + kMassPole, pole_ml = kMassPole * kHalfLength;
-    const double temp = (force + pole_ml * theta_dot * theta_dot * sin_t) / total_mass;
-    const double theta_acc = (kGravity * sin_t - cos_t * temp) / (kHalfLength * (4.0 / 3.0 - kMassPole * cos_t * cos_t / total_mass));
-    const double x_acc = temp - pole_ml * theta_acc * cos_t / total_mass;
-    const double nx = x + kTau * x_dot, nx_dot = x_dot + kTau * x_acc;
-    const double nth = theta + kTau * theta_dot, nth_dot = theta_dot + kTau * theta_acc;
-    s[0] = nx, s[1] = nx_dot, s[2] = nth, s[3] = nth_dot;
-    const int st = steps[e] + 1;
+    bool term, trunc;
+    srlxp::cartpole_dynamics(s, st, actions[e], max_steps, term, trunc);
     steps[e] = st;
-    const double theta_limit = 12 * 2 * kPi / 360, x_limit = 2.4;
-    const bool term = nx < -x_limit || nx > x_limit || nth < -theta_limit || nth > theta_limit;
-    const bool trunc = !term && st >= max_steps;
-    for (int k = 0; k < 4; k++) obs[4 * e + k] = (float)s[k];
+    for (int k = 0; k < 4; k++) state[4 * e + k] = s[k], obs[4 * e + k] = (float)s[k];
     reward[e] = 1.f;
     terminated[e] = term ? 1 : 0;
     done[e] = (term || trunc) ? 1 : 0;

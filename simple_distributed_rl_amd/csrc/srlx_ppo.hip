@@ -8,6 +8,10 @@
 //                           seeds d loss / d (new_logpi, v)
 //   srlx_pendulum_step    : the Pendulum-shaped synthetic workload of BASELINE config 5 (obs (cos, sin, thdot),
 //                           one torque) for E lock-stepped environments
+//   srlx_ppo_categorical_act     : Categorical policy head -> action sample + its log-probability, one keyed uniform per row
+//                                  (ppo.py:316-324, CategoricalDist.sample / mode)
+//   srlx_cartpole_autoreset_step : CartPole (envs/cartpole.py:step) that starts its next episode in the call that ends one, like
+//                                  srlx_pendulum_step -- the discrete-action workload of the PPO engine
 // The reference module imports TensorFlow and cannot be imported in the build container: these follow the source
 // lines only (parity UNPINNED, like srlx_gae_scan); tests check them against oracle/hot_path_oracle.py and
 // against torch autograd of the same formula.
@@ -104,6 +108,28 @@ __global__ void __launch_bounds__(256) k_pendulum(i64 E, float *state /*[E][2] t
 
 __global__ void k_advance1(i64 *c) { c[0] += 1; }
 
+__global__ void __launch_bounds__(256) k_categorical_act(i64 rows, int n, const float *__restrict__ logits, unsigned long long seed, const i64 *counter, int deterministic,
+                                                         int32_t *__restrict__ action, float *__restrict__ logprob) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int a;
+    srlxp::cat_act_one(logits + r * n, n, seed, deterministic ? 0ull : (unsigned long long)counter[0], r, deterministic, a, logprob[r]);
+    action[r] = a;
+}
+
+__global__ void __launch_bounds__(256) k_cartpole_auto(i64 E, double *__restrict__ state, int32_t *__restrict__ steps, int32_t *__restrict__ episodes,
+                                                       const int32_t *__restrict__ actions, i64 max_steps, unsigned long long seed, float *__restrict__ obs,
+                                                       float *__restrict__ reward, u8 *__restrict__ done) {
+    const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double s[4] = {state[4 * e], state[4 * e + 1], state[4 * e + 2], state[4 * e + 3]};
+    int st = steps[e], ep = episodes[e];
+    float o[4];
+    srlxp::cartpole_one(s, st, ep, actions[e], max_steps, seed, e, o, reward[e], done[e]);
+    for (int k = 0; k < 4; k++) state[4 * e + k] = s[k], obs[4 * e + k] = o[k];
+    steps[e] = st, episodes[e] = ep;
+}
+
 }  // namespace
 
 extern "C" {
@@ -190,6 +216,25 @@ int srlx_ppo_loss_logpi(int64_t batch, int n_logpi, const float *d_new_logpi, co
     a.d_logpi = d_grad_logpi;
     a.d_v = d_grad_v;
     return ppo_loss_common(a, false, stream);
+}
+
+int srlx_ppo_categorical_act(int64_t rows, int n_actions, const float *d_logits, uint64_t seed, int64_t *d_counter, int deterministic, int32_t *d_action,
+                             float *d_logprob, void *stream) {
+    SRLX_REQUIRE(rows > 0 && n_actions >= 1 && d_logits && d_action && d_logprob && (deterministic || d_counter), "ppo_categorical_act: bad argument");
+    hipLaunchKernelGGL(k_categorical_act, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (i64)rows, n_actions, d_logits, (unsigned long long)seed,
+                       (const i64 *)d_counter, deterministic, d_action, d_logprob);
+    if (!deterministic) hipLaunchKernelGGL(k_advance1, dim3(1), dim3(1), 0, (hipStream_t)stream, d_counter);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_cartpole_autoreset_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const int32_t *d_actions, int64_t max_steps, uint64_t seed,
+                                 float *d_obs, float *d_reward, uint8_t *d_done, void *stream) {
+    SRLX_REQUIRE(n_envs > 0 && d_state && d_steps && d_episodes && d_actions && d_obs && d_reward && d_done && max_steps > 0, "cartpole_autoreset_step: bad argument");
+    hipLaunchKernelGGL(k_cartpole_auto, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (i64)n_envs, d_state, d_steps, d_episodes, d_actions,
+                       (i64)max_steps, (unsigned long long)seed, d_obs, d_reward, d_done);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
 }
 
 int srlx_pendulum_step(int64_t n_envs, float *d_state, int32_t *d_step_in_episode, const float *d_action, int64_t episode_len, uint64_t seed,

@@ -1,6 +1,17 @@
 // srlx_ppo_math.h -- the per-sample arithmetic of the PPO path, shared by the one-purpose kernels of srlx_ppo.hip (policy sampling, loss + gradient seeds,
-// the Pendulum-shaped environment) and the fused network kernels of srlx_ppo_net.hip (whole rollout / whole minibatch in one launch): one definition, same bits.
-// Reference lines: srl/algorithms/ppo/ppo.py:102-169 (compute_train_loss), :316-339 (policy), srl/rl/tf/distributions/normal_dist_block.py:13-20,64-74,144-149.
+// the Pendulum-shaped environment, the self-resetting CartPole) and the fused network kernels of srlx_ppo_net.hip (whole rollout / whole minibatch in one launch):
+// one definition, same bits.  The CartPole step is srlx_mlpq.hip's k_cartpole as well.
+// Reference lines: srl/algorithms/ppo/ppo.py:102-169 (compute_train_loss), :316-339 (policy), srl/rl/tf/distributions/normal_dist_block.py:13-20,64-74,144-149,
+// srl/rl/tf/distributions/categorical_dist_block.py (CategoricalDist: log_softmax of the logits, sample, mode = argmax).
+//
+// The categorical head, exactly (tests/ppo_cat_reference.py restates it):
+//   log-softmax, float32: m = max_k logit_k; s = sum_k expf(logit_k - m), k ascending from 0.f; lse = logf(s); logp_k = (logit_k - m) - lse.
+//   sample: ONE keyed uniform per row, u = u53(rng_u64(seed, counter, row)) (a double in [0, 1)); p_k = expf(logp_k) in float32; cum = 0.f; cum += p_k for k
+//           ascending; the action is the first k with (double)cum > u, and n_actions - 1 when no k qualifies (cum may end a few ulp short of 1).
+//   deterministic: the first k whose logit equals the maximum (CategoricalDist.mode; torch.argmax).
+//   the taken action's log-probability is floored at kLogFloor (ppo.py:324).
+//   loss seeds: lp = logp_a (not floored: the graph's log_softmax, ppo.py:117-119), g_lp = policy_lp_terms at K = 1 (entropy term -exp(lp) lp of the taken action
+//           only, :166), d loss / d logit_k = g_lp * ((k == a) - p_k).  Unimix and the "kl" surrogate are not offered.
 #pragma once
 #include "srlx_common.h"
 
@@ -117,6 +128,95 @@ __device__ __forceinline__ void pendulum_one(float &th, float &thd, int &t, floa
     o0 = cosf(th);
     o1 = sinf(th);
     o2 = thd;
+}
+
+// ---- categorical head ---------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kCatMax = 8;  // n_actions the fused network covers (its heads table has 8 policy slots per row)
+
+__device__ __forceinline__ void cat_lse(const float *__restrict__ logits, int n, float &m, float &lse) {
+    m = logits[0];
+    for (int k = 1; k < n; k++) m = fmaxf(m, logits[k]);
+    float s = 0.f;
+    for (int k = 0; k < n; k++) s += expf(logits[k] - m);
+    lse = logf(s);
+}
+__device__ __forceinline__ float cat_logp(float logit, float m, float lse) { return (logit - m) - lse; }
+
+// logits [n] (memory: global or LDS) -> action + its log-probability; row = the index the uniform is keyed with
+__device__ __forceinline__ void cat_act_one(const float *__restrict__ logits, int n, u64 seed, u64 c, i64 row, int deterministic, int &action, float &logprob) {
+    float m, lse;
+    cat_lse(logits, n, m, lse);
+    int a;
+    if (deterministic) {
+        a = 0;
+        for (int k = n - 1; k >= 0; k--)
+            if (logits[k] == m) a = k;  // the first maximum
+    } else {
+        const double u = srlx::u53(srlx::rng_u64(seed, c, (u64)row));
+        a = n - 1;
+        float cum = 0.f;
+        bool found = false;
+        for (int k = 0; k < n; k++) {
+            cum += expf(cat_logp(logits[k], m, lse));
+            if (!found && (double)cum > u) a = k, found = true;
+        }
+    }
+    action = a;
+    logprob = fmaxf(cat_logp(logits[a], m, lse), kLogFloor);
+}
+
+// Categorical head: log-probability of `action` and the seeds d loss / d logit_k (fixed extent kCatMax, zero beyond n: no run-time register index)
+__device__ __forceinline__ void policy_categorical(const LossCfg &a, const float *__restrict__ logits, int n, int action, float old_lp, float adv, float &term, float &ent,
+                                                   float (&d_logit)[kCatMax]) {
+    float m, lse;
+    cat_lse(logits, n, m, lse);
+    const float lp = cat_logp(logits[action], m, lse);
+    const float g_lp = policy_lp_terms(a, lp, old_lp, adv, term, ent);
+#pragma unroll
+    for (int k = 0; k < kCatMax; k++) d_logit[k] = k < n ? g_lp * ((k == action ? 1.0f : 0.0f) - expf(cat_logp(logits[k], m, lse))) : 0.f;
+}
+
+// ---- CartPole (envs/cartpole.py), float64 state x, x_dot, theta, theta_dot ------------------------------------------------------------------------------------
+constexpr double kCpGravity = 9.8, kCpMassCart = 1.0, kCpMassPole = 0.1, kCpHalfLength = 0.5, kCpForce = 10.0, kCpTau = 0.02;
+constexpr double kCpPi = 3.141592653589793;
+
+// the lane's next episode: uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane); the episode count advances, the step count restarts
+__device__ __forceinline__ void cartpole_reset(double (&s)[4], int &steps, int &episode, u64 seed, i64 lane) {
+    const u64 key = (u64)lane * 0x100000000ull + (u64)(uint32_t)episode;
+#pragma unroll
+    for (int k = 0; k < 4; k++) s[k] = -0.05 + 0.1 * srlx::u53(srlx::rng_u64(seed ^ 0xCA27901Eull, key, (u64)k));
+    episode += 1;
+    steps = 0;
+}
+
+// one explicit-Euler step (envs/cartpole.py:step): action 1 pushes right, anything else left
+__device__ __forceinline__ void cartpole_dynamics(double (&s)[4], int &steps, int action, i64 max_steps, bool &terminated, bool &truncated) {
+    const double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+    const double force = action == 1 ? kCpForce : -kCpForce;
+    const double cos_t = cos(theta), sin_t = sin(theta);
+    const double total_mass = kCpMassCart + kCpMassPole, pole_ml = kCpMassPole * kCpHalfLength;
+    const double temp = (force + pole_ml * theta_dot * theta_dot * sin_t) / total_mass;
+    const double theta_acc = (kCpGravity * sin_t - cos_t * temp) / (kCpHalfLength * (4.0 / 3.0 - kCpMassPole * cos_t * cos_t / total_mass));
+    const double x_acc = temp - pole_ml * theta_acc * cos_t / total_mass;
+    const double nx = x + kCpTau * x_dot, nx_dot = x_dot + kCpTau * x_acc;
+    const double nth = theta + kCpTau * theta_dot, nth_dot = theta_dot + kCpTau * theta_acc;
+    s[0] = nx, s[1] = nx_dot, s[2] = nth, s[3] = nth_dot;
+    steps += 1;
+    const double theta_limit = 12 * 2 * kCpPi / 360, x_limit = 2.4;
+    terminated = nx < -x_limit || nx > x_limit || nth < -theta_limit || nth > theta_limit;
+    truncated = !terminated && steps >= max_steps;
+}
+
+// step + auto-reset, as pendulum_one: the call that ends an episode (termination or the step limit) returns that step's reward and done = 1, and the NEXT
+// episode's first observation
+__device__ __forceinline__ void cartpole_one(double (&s)[4], int &steps, int &episode, int action, i64 max_steps, u64 seed, i64 lane, float (&obs)[4], float &reward, u8 &done) {
+    bool term, trunc;
+    cartpole_dynamics(s, steps, action, max_steps, term, trunc);
+    reward = 1.f;
+    done = (term || trunc) ? 1 : 0;
+    if (done) cartpole_reset(s, steps, episode, seed, lane);
+#pragma unroll
+    for (int k = 0; k < 4; k++) obs[k] = (float)s[k];
 }
 
 }  // namespace srlxp

@@ -9,6 +9,10 @@
 //   k_ppo_reduce    : partial gradients -> the flat gradient (fixed order: deterministic) + the three reported losses.
 //   k_ppo_adam      : global-norm clip (:240-241, torch.nn.utils.clip_grad_norm_) + Adam (torch.optim.Adam) over the flat parameter vector, one workgroup; between
 //                     k_ppo_reduce and k_ppo_adam sits the data-parallel job's ONE all-reduce of the flat gradient (device/ppo.py).
+// The same four kernels serve a CATEGORICAL head (template parameter CAT; discrete actions, ppo.py:316-324): in -> 64 -> 64 -> {64 -> V, 64 -> n logits}, parameters
+// ... wp, bp, wlogit [n][64], blogit [n].  The n <= 8 logit rows take the 2 * A_MAX = 8 policy-head slots the Normal head's loc / log_scale rows take (slot k: k < 4
+// in wloc's place, else in wls's), so the LDS image, the heads / seeds tables and the whole backward pass are shared; what differs is the parameter layout, the
+// loss seeds and the rollout's policy + environment: k_ppo_cat_rollout steps CartPole (float64 state, srlx_ppo_math.h: cartpole_one) under a categorical sample.
 // float32 throughout, fmaf accumulation in ascending input order; the per-sample policy / loss / environment arithmetic is srlx_ppo_math.h, shared with the
 // one-purpose kernels of srlx_ppo.hip.  Parameters are ONE flat float32 vector in torch's `ActorCritic.parameters()` order (weights [out][in]).
 // Bounds: VALU (f32 FMA) -- about 76 kFLOP per sample and update (forward + backward), 25 kFLOP per environment step; HBM traffic is the buffers only.
@@ -53,11 +57,27 @@ __host__ __device__ inline NetOff net_off(int obs, int A) {
     return o;
 }
 
+// categorical head: wlogit / blogit stand where wloc / bloc do; there is no second head tensor
+__host__ __device__ inline NetOff net_off_cat(int obs, int n) {
+    NetOff o = net_off(obs, 0);
+    int p = o.wloc;
+    o.wloc = p, p += n * H;
+    o.bloc = p, p += n;
+    o.wls = o.bls = o.total = p;
+    return o;
+}
+template <bool CAT>
+__host__ __device__ inline NetOff net_off_of(int obs, int A) {
+    return CAT ? net_off_cat(obs, A) : net_off(obs, A);
+}
+static_assert(srlxp::kCatMax == 2 * A_MAX, "the logit rows take the loc + log_scale slots");
+
 // LDS image of the small tensors (everything but the three 64 x 64 matrices)
 struct Small {
     float w1[H * OBS_MAX], b1[H], b2[H], bv[H], bp[H], wvo[H], wloc[A_MAX * H], wls[A_MAX * H], bvo[4], bloc[A_MAX], bls[A_MAX];  // (a multiple of 16 bytes)
 };
 
+template <bool CAT = false>
 __device__ __forceinline__ void load_small(Small &sm, const float *__restrict__ p, const NetOff &o, int obs, int A) {
     const int t = threadIdx.x, n = blockDim.x;
     for (int i = t; i < H * obs; i += n) sm.w1[i] = p[o.w1 + i];
@@ -68,13 +88,28 @@ __device__ __forceinline__ void load_small(Small &sm, const float *__restrict__ 
         sm.bp[i] = p[o.bp + i];
         sm.wvo[i] = p[o.wvo + i];
     }
-    for (int i = t; i < A * H; i += n) {
-        sm.wloc[i] = p[o.wloc + i];
-        sm.wls[i] = p[o.wls + i];
-    }
-    if (t < A) {
-        sm.bloc[t] = p[o.bloc + t];
-        sm.bls[t] = p[o.bls + t];
+    if constexpr (CAT) {  // logit row k: slot k of the eight policy-head rows
+        for (int i = t; i < A * H; i += n) {
+            if (i < A_MAX * H)
+                sm.wloc[i] = p[o.wloc + i];
+            else
+                sm.wls[i - A_MAX * H] = p[o.wloc + i];
+        }
+        if (t < A) {
+            if (t < A_MAX)
+                sm.bloc[t] = p[o.bloc + t];
+            else
+                sm.bls[t - A_MAX] = p[o.bloc + t];
+        }
+    } else {
+        for (int i = t; i < A * H; i += n) {
+            sm.wloc[i] = p[o.wloc + i];
+            sm.wls[i] = p[o.wls + i];
+        }
+        if (t < A) {
+            sm.bloc[t] = p[o.bloc + t];
+            sm.bls[t] = p[o.bls + t];
+        }
     }
     if (t == 0) sm.bvo[0] = p[o.bvo];
 }
@@ -115,7 +150,7 @@ __device__ __forceinline__ float dot64(const float *__restrict__ a, const float 
 // v_mfma_f32_16x16x4_f32 tiles: wave w owns units 16 w .. 16 w + 15 of all 16 rows, 16 chained MFMAs per layer (lane l supplies in[row l & 15][k] and
 // Wt[k][unit l & 15] for k = (l >> 4) + 4 q; D[4 (l >> 4) + i][l & 15] = acc[i]) -- a layer is 0.5 k clocks of matrix pipe instead of ~3 k clocks of LDS-latency-
 // bound FMAs (one workgroup per CU, one wave per SIMD).  Activation rows are 65 floats long ("lane i reads row i" without bank conflicts).
-// heads [RE][1 + 2 A]: v, loc, log_scale.  value_only: the policy branch is skipped (V(s_T)).  Ends behind a barrier.
+// heads [RE][1 + 2 A]: v, loc, log_scale (CAT: [RE][1 + n]: v, logits).  value_only: the policy branch is skipped (V(s_T)).  Ends behind a barrier.
 constexpr int LDF = 65;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct FwdLds {
@@ -137,6 +172,7 @@ __device__ __forceinline__ void mfma16_dense(const float *__restrict__ in, const
     for (int i = 0; i < 4; i++) out[(4 * g + i) * LDF + n0 + c] = fmaxf(acc[i], 0.f);
 }
 
+template <bool CAT = false>
 __device__ __forceinline__ void forward_rows(FwdLds &L, int obs, int A, bool value_only) {
     const int tid = threadIdx.x, e = tid >> 4, j0 = (tid & 15) * 4;
     {
@@ -150,7 +186,7 @@ __device__ __forceinline__ void forward_rows(FwdLds &L, int obs, int A, bool val
     mfma16_dense(L.h2, L.wtv, L.sm.bv, L.hv);
     if (!value_only) mfma16_dense(L.h2, L.wtp, L.sm.bp, L.hp);
     __syncthreads();
-    const int n_out = 1 + 2 * A;
+    const int n_out = CAT ? 1 + A : 1 + 2 * A;
     if (tid < RE * n_out) {
         const int r = tid % RE, o = tid / RE;  // (consecutive lanes: consecutive rows)
         float v;
@@ -158,6 +194,8 @@ __device__ __forceinline__ void forward_rows(FwdLds &L, int obs, int A, bool val
             v = dot64(L.hv + r * LDF, L.sm.wvo, L.sm.bvo[0]);
         else if (value_only)
             v = 0.f;
+        else if (CAT)
+            v = o <= A_MAX ? dot64(L.hp + r * LDF, L.sm.wloc + (o - 1) * H, L.sm.bloc[o - 1]) : dot64(L.hp + r * LDF, L.sm.wls + (o - 1 - A_MAX) * H, L.sm.bls[o - 1 - A_MAX]);
         else if (o <= A)
             v = dot64(L.hp + r * LDF, L.sm.wloc + (o - 1) * H, L.sm.bloc[o - 1]);
         else
@@ -167,20 +205,23 @@ __device__ __forceinline__ void forward_rows(FwdLds &L, int obs, int A, bool val
     __syncthreads();
 }
 
+template <bool CAT = false>
 __device__ __forceinline__ void load_forward_weights(FwdLds &L, const float *__restrict__ params, const NetOff &o, int obs, int A) {
     load_transposed(L.wt2, params + o.w2);
     load_transposed(L.wtv, params + o.wv);
     load_transposed(L.wtp, params + o.wp);
-    load_small(L.sm, params, o, obs, A);
+    load_small<CAT>(L.sm, params, o, obs, A);
 }
 
 // ---- plain forward (evaluation, tests, rollouts of environments other than the built-in one) -----------------------------------------------------------------------
+// (CAT: loc [n][A] receives the logits, ls is not written)
+template <bool CAT>
 __global__ void __launch_bounds__(256) k_ppo_forward(i64 n, int obs, int A, const float *__restrict__ params, const float *__restrict__ x, float *__restrict__ v, float *__restrict__ loc,
                                                      float *__restrict__ ls) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     FwdLds &L = *reinterpret_cast<FwdLds *>(lds_raw);
-    const NetOff o = net_off(obs, A);
-    load_forward_weights(L, params, o, obs, A);
+    const NetOff o = net_off_of<CAT>(obs, A);
+    load_forward_weights<CAT>(L, params, o, obs, A);
     const int tid = threadIdx.x;
     for (i64 r0 = (i64)blockIdx.x * RE; r0 < n; r0 += (i64)gridDim.x * RE) {
         __syncthreads();
@@ -189,13 +230,13 @@ __global__ void __launch_bounds__(256) k_ppo_forward(i64 n, int obs, int A, cons
             L.x[r * OBS_MAX + c] = r0 + r < n ? x[(r0 + r) * obs + c] : 0.f;
         }
         __syncthreads();
-        forward_rows(L, obs, A, false);
+        forward_rows<CAT>(L, obs, A, false);
         if (tid < RE && r0 + tid < n) {
             const float *hd = L.heads + tid * (1 + 2 * A_MAX);
             v[r0 + tid] = hd[0];
             for (int a = 0; a < A; a++) {
                 loc[(r0 + tid) * A + a] = hd[1 + a];
-                ls[(r0 + tid) * A + a] = hd[1 + A + a];
+                if (!CAT) ls[(r0 + tid) * A + a] = hd[1 + A + a];
             }
         }
     }
@@ -218,6 +259,27 @@ struct RolloutArgs {
     u8 *b_done;
     float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
 };
+
+// The GAE scan of one environment (thread tid < RE) over the rollout's LDS records (the arithmetic of k_gae_scan, srlx_train.hip)
+__device__ __forceinline__ void gae_rows(const float *t_rew, const float *t_val, const float *t_done, i64 T, i64 E, i64 eg, int tid, float lv, double discount, double lam,
+                                         float *__restrict__ b_adv) {
+    const float g = (float)discount, gl = (float)(discount * lam);
+    float gae = 0.f;
+    for (i64 i = T - 1; i >= 0; i--) {
+        const float r = t_rew[i * RE + tid], v = t_val[i * RE + tid];
+        float delta;
+        if (t_done[i * RE + tid] != 0.f) {
+            delta = r - v;
+            gae = 0.f;
+        } else if (i == T - 1) {
+            delta = (r + g * lv) - v;
+        } else {
+            delta = (r + g * t_val[(i + 1) * RE + tid]) - v;
+        }
+        gae = delta + gl * gae;
+        b_adv[i * E + eg] = gae;
+    }
+}
 
 __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -279,22 +341,7 @@ __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs a) {
     if (tid < RE) {
         const float lv = L.heads[tid * (1 + 2 * A_MAX)];
         a.last_v[eg] = lv;
-        const float g = (float)a.discount, gl = (float)(a.discount * a.lam);
-        float gae = 0.f;
-        for (i64 i = a.T - 1; i >= 0; i--) {  // (the arithmetic of k_gae_scan, srlx_train.hip)
-            const float r = t_rew[i * RE + tid], v = t_val[i * RE + tid];
-            float delta;
-            if (t_done[i * RE + tid] != 0.f) {
-                delta = r - v;
-                gae = 0.f;
-            } else if (i == a.T - 1) {
-                delta = (r + g * lv) - v;
-            } else {
-                delta = (r + g * t_val[(i + 1) * RE + tid]) - v;
-            }
-            gae = delta + gl * gae;
-            a.b_adv[i * a.E + eg] = gae;
-        }
+        gae_rows(t_rew, t_val, t_done, a.T, a.E, eg, tid, lv, a.discount, a.lam, a.b_adv);
         a.env_state[2 * eg] = th, a.env_state[2 * eg + 1] = thd, a.t_in_ep[eg] = tstep, a.episode_return[eg] = er;
         for (int c = 0; c < 3; c++) a.env_obs[3 * eg + c] = L.x[tid * OBS_MAX + c];
         if (fin_cnt > 0.f) {
@@ -309,13 +356,101 @@ __global__ void k_advance2(i64 *c0, i64 *c1, i64 n) {
     c1[0] += n;
 }
 
+// ---- the rollout of the categorical head on CartPole -----------------------------------------------------------------------------------------------------------------
+// As k_ppo_rollout: one workgroup owns 16 environments for all T steps.  The environment is float64 (cartpole_one: about 40 f64 operations, one sin and one cos per
+// step on 16 of the workgroup's 256 lanes) and keeps no counter: a reset is keyed with (lane, episode of the lane).
+struct CatRolloutArgs {
+    i64 E, T;
+    int n;  // actions
+    const float *params;
+    double *env_state;           // [E][4]
+    int32_t *steps, *episodes;   // [E]
+    float *env_obs;              // [E][4]: the observation the rollout starts from / ends at
+    i64 max_steps;
+    u64 env_seed, act_seed;
+    const i64 *act_counter;  // advances by T per rollout (k_advance, behind this kernel)
+    double discount, lam;
+    float *b_obs /*[T+1][E][4]*/;
+    int32_t *b_act /*[T][E]*/;
+    float *b_logp, *b_val /*[T][E]*/, *b_rew;
+    u8 *b_done;
+    float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
+};
+
+__global__ void __launch_bounds__(256) k_ppo_cat_rollout(CatRolloutArgs a) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    FwdLds &L = *reinterpret_cast<FwdLds *>(lds_raw);
+    float *t_rew = reinterpret_cast<float *>(lds_raw + sizeof(FwdLds));  // [T][RE]
+    float *t_val = t_rew + a.T * RE;
+    float *t_done = t_val + a.T * RE;
+    const int obs = 4, A = a.n, tid = threadIdx.x;
+    const NetOff o = net_off_cat(obs, A);
+    load_forward_weights<true>(L, a.params, o, obs, A);
+    const i64 e0 = (i64)blockIdx.x * RE, eg = e0 + tid;  // (tid < RE: this thread's environment)
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    int steps = 0, episode = 0;
+    float er = 0.f, fin_sum = 0.f, fin_cnt = 0.f;
+    if (tid < RE) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) s[c] = a.env_state[4 * eg + c];
+        steps = a.steps[eg], episode = a.episodes[eg], er = a.episode_return[eg];
+        for (int c = 0; c < 4; c++) {
+            const float v = a.env_obs[4 * eg + c];
+            L.x[tid * OBS_MAX + c] = v;
+            a.b_obs[4 * eg + c] = v;
+        }
+    }
+    const u64 c_act = (u64)a.act_counter[0];
+    __syncthreads();
+    for (i64 t = 0; t < a.T; t++) {
+        forward_rows<true>(L, obs, A, false);
+        if (tid < RE) {
+            const float *hd = L.heads + tid * (1 + 2 * A_MAX);
+            int ac;
+            float lp, ob[4], rw;
+            u8 dn;
+            srlxp::cat_act_one(hd + 1, A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp);
+            srlxp::cartpole_one(s, steps, episode, ac, a.max_steps, a.env_seed, eg, ob, rw, dn);
+            const i64 k = t * a.E + eg;
+            a.b_act[k] = ac;
+            a.b_logp[k] = lp;
+            a.b_val[k] = hd[0];
+            a.b_rew[k] = rw;
+            a.b_done[k] = dn;
+            float *bo = a.b_obs + ((t + 1) * a.E + eg) * 4;
+#pragma unroll
+            for (int c = 0; c < 4; c++) bo[c] = ob[c], L.x[tid * OBS_MAX + c] = ob[c];
+            t_rew[t * RE + tid] = rw, t_val[t * RE + tid] = hd[0], t_done[t * RE + tid] = dn ? 1.f : 0.f;
+            er += rw;
+            if (dn) fin_sum += er, fin_cnt += 1.f, er = 0.f;
+        }
+        __syncthreads();
+    }
+    forward_rows<true>(L, obs, A, true);  // V(s_T)
+    if (tid < RE) {
+        const float lv = L.heads[tid * (1 + 2 * A_MAX)];
+        a.last_v[eg] = lv;
+        gae_rows(t_rew, t_val, t_done, a.T, a.E, eg, tid, lv, a.discount, a.lam, a.b_adv);
+#pragma unroll
+        for (int c = 0; c < 4; c++) a.env_state[4 * eg + c] = s[c];
+        a.steps[eg] = steps, a.episodes[eg] = episode, a.episode_return[eg] = er;
+        for (int c = 0; c < 4; c++) a.env_obs[4 * eg + c] = L.x[tid * OBS_MAX + c];
+        if (fin_cnt > 0.f) {
+            atomicAdd(&a.finished[0], fin_sum);
+            atomicAdd(&a.finished[1], fin_cnt);
+        }
+    }
+}
+
+__global__ void k_advance(i64 *c, i64 n) { c[0] += n; }
+
 // ---- one minibatch: forward + loss + backward ----------------------------------------------------------------------------------------------------------------------
 struct MbArgs {
     i64 mb;           // samples in this minibatch
     const i64 *perm;  // [mb] rows of the [T * E] buffers
     int obs, A;
     const float *params;
-    const float *b_obs, *b_act, *b_logp, *b_adv, *b_vt, *b_val;
+    const float *b_obs, *b_act /*CAT: int32 [n]*/, *b_logp, *b_adv, *b_vt, *b_val;
     LossCfg cfg;
     float *partials;  // [gridDim.x][stride]: per-workgroup gradient sums (parameter order) + 3 loss sums
     int stride;
@@ -373,11 +508,13 @@ __device__ __forceinline__ f32x16 mfma_wgrad(f32x16 acc, const float *__restrict
     return mfma_block(acc, [&](int row, int s) { return dz[s * LD + m0 + row]; }, [&](int s, int col) { return h[s * LD + n0 + col]; });
 }
 
+// CAT: A = the number of actions; logit k lives in policy-head slot k (seeds column 1 + k; weights wloc[k] for k < 4, wls[k - 4] beyond)
+template <bool CAT>
 __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     MbLds &L = *reinterpret_cast<MbLds *>(lds_raw);
-    const int obs = a.obs, A = a.A, tid = threadIdx.x, n_out = 1 + 2 * A;
-    const NetOff o = net_off(obs, A);
+    const int obs = a.obs, A = a.A, tid = threadIdx.x, n_out = CAT ? 1 + A : 1 + 2 * A;
+    const NetOff o = net_off_of<CAT>(obs, A);
 #pragma unroll 4
     for (int i = tid; i < H * H; i += 256) {
         const int j = i >> 6, k = i & 63;
@@ -385,7 +522,7 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
         L.wv[j * LD + k] = a.params[o.wv + i];
         L.wp[j * LD + k] = a.params[o.wp + i];
     }
-    load_small(L.sm, a.params, o, obs, A);
+    load_small<CAT>(L.sm, a.params, o, obs, A);
     const int wave = tid >> 6, m0 = (wave >> 1) * 32, n0 = (wave & 1) * 32, li = tid & 31;
     // the matrices: this wave's block of W [m0 + acc_row(r)][n0 + li], summed over the workgroup's tiles
     f32x16 g_w2, g_wv, g_wp;
@@ -402,7 +539,7 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
 #pragma unroll
     for (int c = 0; c < OBS_MAX; c++) w1u[c] = c < obs ? L.sm.w1[u * obs + c] : 0.f;
 #pragma unroll
-    for (int d = 0; d < A_MAX; d++) wloc_u[d] = d < A ? L.sm.wloc[d * H + u] : 0.f, wls_u[d] = d < A ? L.sm.wls[d * H + u] : 0.f;
+    for (int d = 0; d < A_MAX; d++) wloc_u[d] = d < A ? L.sm.wloc[d * H + u] : 0.f, wls_u[d] = (CAT ? A_MAX + d : d) < A ? L.sm.wls[d * H + u] : 0.f;
     const float b1u = L.sm.b1[u], wvo_u = L.sm.wvo[u];
     const i64 tiles = (a.mb + S - 1) / S;
     for (i64 tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -410,12 +547,18 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
         const i64 row = tile * S + tid;  // (tid < S)
         i64 idx = -1;
         float in_vt = 0.f, in_adv = 0.f, in_val = 0.f, in_act[A_MAX], in_logp[A_MAX];  // this sample's loss inputs: gathered now, used behind the forward
+        int in_a = 0;                                                                    // (CAT: the action, and in_logp[0])
         if (tid < S) {
             idx = row < a.mb ? a.perm[row] : -1;
             for (int c = 0; c < OBS_MAX; c++) L.x[tid * OBS_MAX + c] = (idx >= 0 && c < obs) ? a.b_obs[idx * obs + c] : 0.f;
             if (idx >= 0) {
                 in_vt = a.b_vt[idx], in_adv = a.b_adv[idx], in_val = a.b_val[idx];
-                for (int d = 0; d < A; d++) in_act[d] = a.b_act[idx * A + d], in_logp[d] = a.b_logp[idx * A + d];
+                if constexpr (CAT) {
+                    in_a = min(max(reinterpret_cast<const int32_t *>(a.b_act)[idx], 0), A - 1);
+                    in_logp[0] = a.b_logp[idx];
+                } else {
+                    for (int d = 0; d < A; d++) in_act[d] = a.b_act[idx * A + d], in_logp[d] = a.b_logp[idx * A + d];
+                }
             }
         }
         __syncthreads();
@@ -437,8 +580,9 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
         for (int w = tid; w < S * n_out; w += 256) {
             const int r = w % S, oo = w / S;  // (consecutive lanes: consecutive rows of an LD = 65 matrix: conflict-free)
             const float *hrow = (oo == 0 ? L.hv : L.hp) + r * LD;
-            const float *wrow = oo == 0 ? L.sm.wvo : (oo <= A ? L.sm.wloc + (oo - 1) * H : L.sm.wls + (oo - 1 - A) * H);
-            L.heads[r * HS + oo] = dot64(hrow, wrow, oo == 0 ? L.sm.bvo[0] : (oo <= A ? L.sm.bloc[oo - 1] : L.sm.bls[oo - 1 - A]));
+            const int split = CAT ? A_MAX : A;  // heads 1 .. split from wloc / bloc, the rest from wls / bls
+            const float *wrow = oo == 0 ? L.sm.wvo : (oo <= split ? L.sm.wloc + (oo - 1) * H : L.sm.wls + (oo - 1 - split) * H);
+            L.heads[r * HS + oo] = dot64(hrow, wrow, oo == 0 ? L.sm.bvo[0] : (oo <= split ? L.sm.bloc[oo - 1] : L.sm.bls[oo - 1 - split]));
         }
         __syncthreads();
         // ---- loss + gradient seeds (compute_train_loss, ppo.py:102-169): one thread per sample; seeds row: [0] d/dv, [1 + d] d/dloc, [5 + d] d/dlog_scale ----
@@ -449,11 +593,19 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
                 const float v = hd[0];
                 const float adv = a.cfg.baseline_advantage ? in_adv - v : in_adv;
                 float ent = 0.f;
-                for (int d = 0; d < A; d++) {
-                    float term, e1;
-                    srlxp::policy_normal(a.cfg, hd[1 + d], hd[1 + A + d], in_act[d], in_logp[d], adv, term, e1, sd[1 + d], sd[5 + d]);
+                if constexpr (CAT) {
+                    float term, dl[srlxp::kCatMax];
+                    srlxp::policy_categorical(a.cfg, hd + 1, A, in_a, in_logp[0], adv, term, ent, dl);
                     s_pol += term;
-                    ent += e1;
+#pragma unroll
+                    for (int k = 0; k < srlxp::kCatMax; k++) sd[1 + k] = dl[k];
+                } else {
+                    for (int d = 0; d < A; d++) {
+                        float term, e1;
+                        srlxp::policy_normal(a.cfg, hd[1 + d], hd[1 + A + d], in_act[d], in_logp[d], adv, term, e1, sd[1 + d], sd[5 + d]);
+                        s_pol += term;
+                        ent += e1;
+                    }
                 }
                 s_ent += ent;
                 s_val += srlxp::value_term(a.cfg, v, in_vt, a.cfg.value_clip ? in_val : 0.f, sd[0]);
@@ -553,10 +705,19 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
     if (tid < H) {
         for (int c = 0; c < obs; c++) out[o.w1 + tid * obs + c] = g_w1[c];
         out[o.b1 + tid] = g_b1, out[o.b2 + tid] = g_b2, out[o.bv + tid] = g_bv, out[o.bp + tid] = g_bp, out[o.wvo + tid] = g_wvo;
-        for (int d = 0; d < A; d++) out[o.wloc + d * H + tid] = g_wloc[d], out[o.wls + d * H + tid] = g_wls[d];
         if (tid == 0) out[o.bvo] = g_head_b;
-        if (tid >= 1 && tid <= A) out[o.bloc + tid - 1] = g_head_b;
-        if (tid >= 5 && tid < 5 + A) out[o.bls + tid - 5] = g_head_b;
+        if constexpr (CAT) {
+#pragma unroll
+            for (int d = 0; d < A_MAX; d++) {
+                if (d < A) out[o.wloc + d * H + tid] = g_wloc[d];
+                if (A_MAX + d < A) out[o.wloc + (A_MAX + d) * H + tid] = g_wls[d];
+            }
+            if (tid >= 1 && tid <= A) out[o.bloc + tid - 1] = g_head_b;
+        } else {
+            for (int d = 0; d < A; d++) out[o.wloc + d * H + tid] = g_wloc[d], out[o.wls + d * H + tid] = g_wls[d];
+            if (tid >= 1 && tid <= A) out[o.bloc + tid - 1] = g_head_b;
+            if (tid >= 5 && tid < 5 + A) out[o.bls + tid - 5] = g_head_b;
+        }
     }
     __syncthreads();
     if (tid < S) L.red[tid] = s_pol, L.red[S + tid] = s_val, L.red[2 * S + tid] = s_ent;
@@ -638,6 +799,48 @@ __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ pa
 
 static_assert(H * OBS_MAX + 3 * H * H + 2 * A_MAX * H + 5 * H + 1 + 2 * A_MAX <= 16 * 1024, "k_ppo_adam: sixteen elements per thread");
 bool geometry_ok(int obs, int A) { return obs >= 1 && obs <= OBS_MAX && A >= 1 && A <= A_MAX; }
+// categorical: 2 .. 8 actions -- the heads table's eight policy slots per row; more would widen the tables and the backward's fixed extents
+bool cat_geometry_ok(int obs, int n) { return obs >= 1 && obs <= OBS_MAX && n >= 2 && n <= srlxp::kCatMax; }
+constexpr size_t kLdsMax = 160 * 1024;
+
+template <bool CAT>
+int launch_forward(i64 n, int obs, int A, const float *params, const float *x, float *v, float *h0, float *h1, void *stream) {
+    static bool attr = false;
+    if (!attr) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_forward<CAT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FwdLds)));
+        attr = true;
+    }
+    i64 wgs = (n + RE - 1) / RE;
+    if (wgs > 1024) wgs = 1024;
+    hipLaunchKernelGGL(k_ppo_forward<CAT>, dim3((unsigned)wgs), dim3(256), sizeof(FwdLds), (hipStream_t)stream, (i64)n, obs, A, params, x, v, h0, h1);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+template <bool CAT>
+int launch_minibatch(MbArgs &a, float *d_grad, float *d_losses, void *stream) {
+    static bool attr = false;
+    if (!attr) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_minibatch<CAT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MbLds)));
+        attr = true;
+    }
+    const NetOff o = net_off_of<CAT>(a.obs, a.A);
+    a.stride = (o.total + 3 + 3) & ~3;
+    const i64 tiles = (a.mb + S - 1) / S;
+    const int wgs = (int)(tiles < 256 ? tiles : 256);
+    hipLaunchKernelGGL(k_ppo_minibatch<CAT>, dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((4 * (o.total + 3) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wgs, o.total, a.stride, a.partials, d_grad, d_losses, a.cfg);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int launch_adam(int P, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2, double eps,
+                double max_grad_norm, double grad_scale, void *stream) {
+    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((P + 1023) / 1024)), dim3(1024), 0, (hipStream_t)stream, P, d_params, d_grad, d_exp_avg, d_exp_avg_sq, (i64 *)d_step, lr, beta1, beta2, eps,
+                       (float)max_grad_norm, (float)grad_scale);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
 
 }  // namespace
 
@@ -647,16 +850,7 @@ int srlx_ppo_net_param_count(int obs_dim, int action_dim) { return geometry_ok(o
 
 int srlx_ppo_net_forward(int64_t n, int obs_dim, int action_dim, const float *d_params, const float *d_obs, float *d_v, float *d_loc, float *d_log_scale, void *stream) {
     SRLX_REQUIRE(n > 0 && geometry_ok(obs_dim, action_dim) && d_params && d_obs && d_v && d_loc && d_log_scale, "ppo_net_forward: bad argument");
-    static bool attr = false;
-    if (!attr) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FwdLds)));
-        attr = true;
-    }
-    i64 wgs = (n + RE - 1) / RE;
-    if (wgs > 1024) wgs = 1024;
-    hipLaunchKernelGGL(k_ppo_forward, dim3((unsigned)wgs), dim3(256), sizeof(FwdLds), (hipStream_t)stream, (i64)n, obs_dim, action_dim, d_params, d_obs, d_v, d_loc, d_log_scale);
-    SRLX_HIP(hipGetLastError());
-    return SRLX_OK;
+    return launch_forward<false>(n, obs_dim, action_dim, d_params, d_obs, d_v, d_loc, d_log_scale, stream);
 }
 
 int srlx_ppo_net_rollout_max_horizon(int action_dim) {  // what fits the workgroup's LDS beside weights and activations
@@ -697,15 +891,6 @@ int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
                            double entropy_weight, float *d_partials, float *d_grad, float *d_losses, void *stream) {
     SRLX_REQUIRE(minibatch > 0 && geometry_ok(obs_dim, action_dim), "ppo_net_minibatch: bad geometry");
     SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_net_minibatch: NULL argument");
-    static bool attr = false;
-    if (!attr) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_minibatch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MbLds)));
-        attr = true;
-    }
-    const NetOff o = net_off(obs_dim, action_dim);
-    const int stride = (o.total + 3 + 3) & ~3;
-    i64 tiles = (minibatch + S - 1) / S;
-    const int wgs = (int)(tiles < 256 ? tiles : 256);
     MbArgs a{};
     a.mb = minibatch;
     a.perm = d_rows;
@@ -715,11 +900,7 @@ int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
     a.cfg = LossCfg{(float)log_scale_min, (float)log_scale_max, baseline_advantage, surrogate_clip, enable_value_clip, (float)policy_clip_range, (float)value_clip_range,
                     (float)value_loss_weight, (float)entropy_weight, 1.0f / (float)minibatch, 1.0f / (float)(minibatch * action_dim)};
     a.partials = d_partials;
-    a.stride = stride;
-    hipLaunchKernelGGL(k_ppo_minibatch, dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((4 * (o.total + 3) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wgs, o.total, stride, d_partials, d_grad, d_losses, a.cfg);
-    SRLX_HIP(hipGetLastError());
-    return SRLX_OK;
+    return launch_minibatch<false>(a, d_grad, d_losses, stream);
 }
 
 int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) {
@@ -730,10 +911,75 @@ int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) {
 int srlx_ppo_net_adam(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
     SRLX_REQUIRE(geometry_ok(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam: bad argument");
-    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((net_off(obs_dim, action_dim).total + 1023) / 1024)), dim3(1024), 0, (hipStream_t)stream, net_off(obs_dim, action_dim).total, d_params, d_grad, d_exp_avg, d_exp_avg_sq, (i64 *)d_step, lr, beta1,
-                       beta2, eps, (float)max_grad_norm, (float)grad_scale);
+    return launch_adam(net_off(obs_dim, action_dim).total, d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
+}
+
+// ---- the categorical head ---------------------------------------------------------------------------------------------------------------------------------------------
+int srlx_ppo_cat_param_count(int obs_dim, int n_actions) { return cat_geometry_ok(obs_dim, n_actions) ? net_off_cat(obs_dim, n_actions).total : -1; }
+
+int srlx_ppo_cat_partials_floats(int obs_dim, int n_actions) {
+    if (!cat_geometry_ok(obs_dim, n_actions)) return -1;
+    return 256 * ((net_off_cat(obs_dim, n_actions).total + 3 + 3) & ~3);
+}
+
+int srlx_ppo_cat_rollout_max_horizon(int n_actions) {  // what fits the workgroup's LDS beside weights and activations: three records per step and environment
+    if (!cat_geometry_ok(4, n_actions)) return -1;
+    const long long t = ((long long)kLdsMax - (long long)sizeof(FwdLds)) / ((long long)RE * 3 * (long long)sizeof(float));
+    return (int)(t < 1024 ? t : 1024);
+}
+
+int srlx_ppo_cat_forward(int64_t n, int obs_dim, int n_actions, const float *d_params, const float *d_obs, float *d_v, float *d_logits, void *stream) {
+    SRLX_REQUIRE(n > 0 && cat_geometry_ok(obs_dim, n_actions) && d_params && d_obs && d_v && d_logits, "ppo_cat_forward: bad argument");
+    return launch_forward<true>(n, obs_dim, n_actions, d_params, d_obs, d_v, d_logits, nullptr, stream);
+}
+
+int srlx_ppo_cat_rollout(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps, int32_t *d_episodes, float *d_env_obs,
+                         int64_t max_steps, uint64_t env_seed, uint64_t act_seed, int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act,
+                         float *d_b_logp, float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
+                         void *stream) {
+    SRLX_REQUIRE(n_envs > 0 && n_envs % RE == 0, "ppo_cat_rollout: the environment count must be a multiple of 16");
+    SRLX_REQUIRE(horizon > 0 && cat_geometry_ok(4, n_actions) && horizon <= srlx_ppo_cat_rollout_max_horizon(n_actions) && max_steps > 0,
+                 "ppo_cat_rollout: bad geometry (horizon <= srlx_ppo_cat_rollout_max_horizon)");
+    SRLX_REQUIRE(d_params && d_env_state && d_steps && d_episodes && d_env_obs && d_act_counter && d_b_obs && d_b_act && d_b_logp && d_b_val && d_b_rew && d_b_done && d_b_adv &&
+                     d_last_v && d_episode_return && d_finished,
+                 "ppo_cat_rollout: NULL argument");
+    const size_t lds = sizeof(FwdLds) + (size_t)horizon * RE * 3 * sizeof(float);
+    SRLX_REQUIRE(lds <= kLdsMax, "ppo_cat_rollout: horizon too long for the workgroup's LDS");
+    static size_t lds_set = 0;
+    if (lds > lds_set) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_cat_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set = lds;
+    }
+    CatRolloutArgs a{n_envs, horizon, n_actions, d_params, d_env_state, d_steps, d_episodes, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter, discount, gae_lambda,
+                     d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished};
+    hipLaunchKernelGGL(k_ppo_cat_rollout, dim3((unsigned)(n_envs / RE)), dim3(256), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, d_act_counter, (i64)horizon);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
+}
+
+int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params, const float *d_b_obs, const int32_t *d_b_act,
+                           const float *d_b_logp, const float *d_b_adv, const float *d_b_v_target, const float *d_b_val, int baseline_advantage, int surrogate_clip,
+                           double policy_clip_range, int enable_value_clip, double value_clip_range, double value_loss_weight, double entropy_weight, float *d_partials,
+                           float *d_grad, float *d_losses, void *stream) {
+    SRLX_REQUIRE(minibatch > 0 && cat_geometry_ok(obs_dim, n_actions), "ppo_cat_minibatch: bad geometry");
+    SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_cat_minibatch: NULL argument");
+    MbArgs a{};
+    a.mb = minibatch;
+    a.perm = d_rows;
+    a.obs = obs_dim, a.A = n_actions;
+    a.params = d_params;
+    a.b_obs = d_b_obs, a.b_act = reinterpret_cast<const float *>(d_b_act), a.b_logp = d_b_logp, a.b_adv = d_b_adv, a.b_vt = d_b_v_target, a.b_val = d_b_val;
+    a.cfg = LossCfg{0.f, 0.f, baseline_advantage, surrogate_clip, enable_value_clip, (float)policy_clip_range, (float)value_clip_range, (float)value_loss_weight,
+                    (float)entropy_weight, 1.0f / (float)minibatch, 1.0f / (float)minibatch};
+    a.partials = d_partials;
+    return launch_minibatch<true>(a, d_grad, d_losses, stream);
+}
+
+int srlx_ppo_cat_adam(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
+                      double eps, double max_grad_norm, double grad_scale, void *stream) {
+    SRLX_REQUIRE(cat_geometry_ok(obs_dim, n_actions) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_cat_adam: bad argument");
+    return launch_adam(net_off_cat(obs_dim, n_actions).total, d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
 }
 
 }  // extern "C"

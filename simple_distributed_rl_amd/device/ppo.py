@@ -19,6 +19,11 @@ launch, a minibatch update is three (forward + loss + backward; gradient reducti
 kernels.  The parameters are one flat float32 vector; the `ActorCritic` module's tensors are views of it.  `fused=False` keeps the torch-autograd path as the
 yardstick the fused one is tested against.
 
+Discrete actions (`PPODeviceConfig.n_actions > 0`): a categorical head (ppo.py:316-324, CategoricalDist) on E self-resetting CartPole environments (envs/cartpole.py
+on the device, float64 state; `episode_len` is its step limit).  The same three-launch update and one-launch rollout with the head swapped (`srlx_ppo_cat_*`); the
+torch-autograd yardstick is log_softmax -> `srlx_ppo_categorical_act` / `srlx_ppo_loss_logpi`.  `export_to` / `load_from` exchange the weights with the PPO plugin's
+`Parameter` (algorithms/ppo.py), so a policy trained here is evaluated through `Runner.evaluate()`.
+
 Data parallel (config 5): `DistributedPPO` gives every rank its own E environments and averages the gradients of
 every minibatch with one all-reduce of the flat ~52 KB gradient vector (latency-bound; RCCL over xGMI) -- the only exchange; with the fused network and RCCL
 it sits INSIDE the captured update graph, between the gradient reduction and the clip + Adam launch.
@@ -60,10 +65,13 @@ class PPODeviceConfig:
     global_gradient_clip_norm: float = 0.5
     stable_gradients_scale_range: Tuple[float, float] = (1e-10, 10)
     seed: int = 0
+    n_actions: int = 0                         # 0: the Normal head on Pendulum; > 0: a categorical head on CartPole (obs_dim 4; action_dim unused; episode_len = max_steps).
+    #                                            CartPole has two moves: action 1 pushes right, every other action pushes left -- n_actions 3..8 is accepted, but adds duplicates of "left"
 
 
 class ActorCritic(nn.Module):
-    """in -> hidden_block -> {value_block -> V, policy_block -> (loc, log_scale)} (ppo.py:55-99)."""
+    """in -> hidden_block -> {value_block -> V, policy_block -> (loc, log_scale)} (ppo.py:55-99); with `n_actions` the policy head is `logits_layer` and forward
+    returns (v, logits)."""
 
     def __init__(self, cfg: PPODeviceConfig):
         super().__init__()
@@ -79,18 +87,34 @@ class ActorCritic(nn.Module):
         self.value_block, nv = mlp(n, cfg.value_sizes)
         self.value_out_layer = nn.Linear(nv, 1)
         self.policy_block, n_pol = mlp(n, cfg.policy_sizes)
-        self.loc_layer = nn.Linear(n_pol, cfg.action_dim)
-        self.log_scale_layer = nn.Linear(n_pol, cfg.action_dim)
+        self.categorical = cfg.n_actions > 0
+        if self.categorical:
+            self.logits_layer = nn.Linear(n_pol, cfg.n_actions)  # categorical_dist_block.py:134-153
+        else:
+            self.loc_layer = nn.Linear(n_pol, cfg.action_dim)
+            self.log_scale_layer = nn.Linear(n_pol, cfg.action_dim)
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.orthogonal_(m.weight)  # ppo.py:60-61
                 nn.init.zeros_(m.bias)
-        nn.init.trunc_normal_(self.loc_layer.bias, std=0.05)  # normal_dist_block.py:101-106
+        if self.categorical:
+            nn.init.zeros_(self.logits_layer.weight)  # categorical_dist_block.py:147: the policy starts uniform
+        else:
+            nn.init.trunc_normal_(self.loc_layer.bias, std=0.05)  # normal_dist_block.py:101-106
 
     def forward(self, x):
         h = self.hidden_block(x)
         p = self.policy_block(h)
-        return self.value_out_layer(self.value_block(h)).squeeze(-1), self.loc_layer(p), self.log_scale_layer(p)
+        v = self.value_out_layer(self.value_block(h)).squeeze(-1)
+        if self.categorical:
+            return v, self.logits_layer(p)
+        return v, self.loc_layer(p), self.log_scale_layer(p)
+
+    def linears(self):
+        """The Linear layers in the plugin network's order (algorithms/ppo.py:ActorCriticNetwork): hidden, value, value_out, policy, policy_out [, log_scale_out]."""
+        lin = lambda seq: [m for m in seq if isinstance(m, nn.Linear)]  # noqa: E731
+        heads = [self.logits_layer] if self.categorical else [self.loc_layer, self.log_scale_layer]
+        return lin(self.hidden_block) + lin(self.value_block) + [self.value_out_layer] + lin(self.policy_block) + heads
 
 
 class PendulumVecEnv:
@@ -111,6 +135,46 @@ class PendulumVecEnv:
                                             N.tptr(obs_out), N.tptr(reward_out), N.tptr(done_out), N.torch_stream_ptr()))
 
 
+class CartPoleAutoVecEnv:
+    """E CartPole environments (envs/cartpole.py) stepped by `srlx_cartpole_autoreset_step`: float64 state on the device, a lane starts its next episode in the step
+    that ends one.  `episode_len` is the step limit (max_steps)."""
+
+    def __init__(self, n_envs: int, episode_len: int, seed: int, device: torch.device):
+        self.E, self.episode_len, self.seed, self.dev, self.lib = n_envs, episode_len, seed, device, N.lib()
+        self.state = torch.zeros((n_envs, 4), dtype=torch.float64, device=device)
+        self.t = torch.zeros(n_envs, dtype=torch.int32, device=device)
+        self.episodes = torch.zeros(n_envs, dtype=torch.int32, device=device)
+        self.obs = torch.zeros((n_envs, 4), dtype=torch.float32, device=device)
+        # every lane's first episode: the reset of srlx_cartpole_step (the same key the self-resetting step uses)
+        N.check(self.lib.srlx_cartpole_step(n_envs, N.tptr(self.state), N.tptr(self.t), N.tptr(self.episodes), None, None, episode_len, seed, N.tptr(self.obs), None, None, None,
+                                            N.torch_stream_ptr()))
+
+    def step(self, action: torch.Tensor, obs_out: torch.Tensor, reward_out: torch.Tensor, done_out: torch.Tensor):
+        N.check(self.lib.srlx_cartpole_autoreset_step(self.E, N.tptr(self.state), N.tptr(self.t), N.tptr(self.episodes), N.tptr(action), self.episode_len, self.seed,
+                                                      N.tptr(obs_out), N.tptr(reward_out), N.tptr(done_out), N.torch_stream_ptr()))
+
+
+def make_env(cfg: PPODeviceConfig, seed: int, device: torch.device):
+    """The built-in environment of a configuration: CartPole under a categorical head, the Pendulum-shaped one otherwise."""
+    cls = CartPoleAutoVecEnv if cfg.n_actions > 0 else PendulumVecEnv
+    return cls(cfg.n_envs, cfg.episode_len, seed, device)
+
+
+def _plugin_linears(model):
+    lin = lambda block: [m for m in block.modules() if isinstance(m, nn.Linear)]  # noqa: E731
+    if any(True for _ in model.in_block.parameters()):
+        raise ValueError("the plugin network has a trainable input block: the engine's network has none")
+    heads = [model.policy_out] + ([model.log_scale_out] if model.continuous else [])
+    return lin(model.hidden_block) + lin(model.value_block) + [model.value_out] + lin(model.policy_block) + heads
+
+
+def _paired_linears(net: ActorCritic, parameter):
+    mine, theirs = net.linears(), _plugin_linears(parameter.model)
+    if len(mine) != len(theirs) or any(a.weight.shape != b.weight.shape for a, b in zip(mine, theirs)):
+        raise ValueError("the plugin's network and the engine's differ in shape: %s vs %s" % ([tuple(m.weight.shape) for m in theirs], [tuple(m.weight.shape) for m in mine]))
+    return list(zip(mine, theirs))
+
+
 class PPOEngine:
     def __init__(self, cfg: PPODeviceConfig, device: int = 0, grad_sync: Optional[Callable[[nn.Module], None]] = None, fused: Optional[bool] = None,
                  flat_grad_sync: Optional[Callable[[torch.Tensor], float]] = None):
@@ -124,16 +188,25 @@ class PPOEngine:
         self.cfg, self.lib = cfg, N.lib()
         self.dev = torch.device(f"cuda:{device}")
         torch.manual_seed(cfg.seed)
+        self.cat = cfg.n_actions > 0
+        if self.cat and cfg.obs_dim != 4:
+            raise ValueError("PPODeviceConfig(n_actions > 0) runs CartPole: obs_dim must be 4")
+        if self.cat and cfg.n_actions < 2:
+            raise ValueError("a categorical policy needs at least 2 actions")
         self.net = ActorCritic(cfg).to(self.dev)
+        # the libsrlx network's entry points for this head (same trunk, same update kernels), and its head size
+        self._head = cfg.n_actions if self.cat else cfg.action_dim
+        self._net_fn = lambda name: getattr(self.lib, ("srlx_ppo_cat_" if self.cat else "srlx_ppo_net_") + name)  # noqa: E731
         can_fuse = (tuple(cfg.hidden_sizes) == (64, 64) and tuple(cfg.value_sizes) == (64,) and tuple(cfg.policy_sizes) == (64,) and 1 <= cfg.obs_dim <= 8
-                    and 1 <= cfg.action_dim <= 4)
+                    and (2 <= cfg.n_actions <= 8 if self.cat else 1 <= cfg.action_dim <= 4))
         if fused and not can_fuse:
-            raise ValueError("PPOEngine(fused=True): the libsrlx network covers hidden (64, 64), value (64,), policy (64,), obs_dim <= 8, action_dim <= 4")
+            raise ValueError("PPOEngine(fused=True): the libsrlx network covers hidden (64, 64), value (64,), policy (64,), obs_dim <= 8, action_dim <= 4 "
+                             "(categorical: 2 <= n_actions <= 8)")
         self.fused = can_fuse if fused is None else bool(fused)
         self.grad_sync, self.flat_grad_sync = grad_sync, flat_grad_sync
         if self.fused:
             # one flat parameter vector in `parameters()` order; the module's tensors become views of it (state_dict / export keep working, always current)
-            P = self.lib.srlx_ppo_net_param_count(cfg.obs_dim, cfg.action_dim)
+            P = self._net_fn("param_count")(cfg.obs_dim, self._head)
             ps = list(self.net.parameters())
             assert sum(p.numel() for p in ps) == P
             self.flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
@@ -144,17 +217,21 @@ class PPOEngine:
             self.flat_grad = torch.zeros(P, dtype=torch.float32, device=self.dev)
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
             self.opt_step = torch.zeros(2, dtype=torch.int64, device=self.dev)  # [steps taken, the optimiser launch's arrival counter]
-            self.partials = torch.zeros(self.lib.srlx_ppo_net_partials_floats(cfg.obs_dim, cfg.action_dim), dtype=torch.float32, device=self.dev)
+            self.partials = torch.zeros(self._net_fn("partials_floats")(cfg.obs_dim, self._head), dtype=torch.float32, device=self.dev)
             self.opt = None
         else:
             self.opt = torch.optim.Adam(self.net.parameters(), lr=cfg.lr, capturable=True)
-        self.env = PendulumVecEnv(cfg.n_envs, cfg.episode_len, cfg.seed, self.dev)
+        self.env = make_env(cfg, cfg.seed, self.dev)
         self.ls_range = (math.log(cfg.stable_gradients_scale_range[0]), math.log(cfg.stable_gradients_scale_range[1]))
         E, T, A, d = cfg.n_envs, cfg.horizon, cfg.action_dim, self.dev
         f32 = dict(dtype=torch.float32, device=d)
         self.b_obs = torch.zeros((T + 1, E, cfg.obs_dim), **f32)
-        self.b_act = torch.zeros((T, E, A), **f32)
-        self.b_logp = torch.zeros((T, E, A), **f32)
+        if self.cat:  # one action index and one log-probability per step
+            self.b_act = torch.zeros((T, E), dtype=torch.int32, device=d)
+            self.b_logp = torch.zeros((T, E), **f32)
+        else:
+            self.b_act = torch.zeros((T, E, A), **f32)
+            self.b_logp = torch.zeros((T, E, A), **f32)
         self.b_val = torch.zeros((T, E), **f32)
         self.b_rew = torch.zeros((T, E), **f32)
         self.b_done = torch.zeros((T, E), dtype=torch.uint8, device=d)
@@ -181,6 +258,12 @@ class PPOEngine:
 
     # --- rollout ---------------------------------------------------------------------------------------------------
     def act(self, obs: torch.Tensor, action_out: torch.Tensor, logp_out: torch.Tensor, deterministic: bool = False):
+        if self.cat:
+            v, logits = self.forward(obs)
+            self._keep = (logits,)
+            N.check(self.lib.srlx_ppo_categorical_act(logits.shape[0], self.cfg.n_actions, N.tptr(logits), self.cfg.seed ^ 0x61637400, N.tptr(self.act_counter),
+                                                      int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
+            return v
         v, loc, ls = self.forward(obs)
         self._keep = (loc, ls)
         N.check(self.lib.srlx_ppo_normal_act(loc.numel(), N.tptr(loc), N.tptr(ls), self.ls_range[0], self.ls_range[1], self.cfg.seed ^ 0x61637400,
@@ -188,10 +271,17 @@ class PPOEngine:
         return v
 
     def forward(self, obs: torch.Tensor):
-        """(v [n], loc [n][A], log_scale [n][A]) of obs [n][obs_dim]: the libsrlx network when fused, the torch modules otherwise."""
+        """(v [n], loc [n][A], log_scale [n][A]) of obs [n][obs_dim] -- categorical: (v [n], logits [n][n_actions]): the libsrlx network when fused, the torch modules
+        otherwise."""
         if not self.fused:
             with torch.no_grad():
                 return self.net(obs)
+        if self.cat:
+            n = obs.shape[0]
+            v, logits = torch.empty(n, dtype=torch.float32, device=self.dev), torch.empty((n, self.cfg.n_actions), dtype=torch.float32, device=self.dev)
+            N.check(self.lib.srlx_ppo_cat_forward(n, self.cfg.obs_dim, self.cfg.n_actions, N.tptr(self.flat), N.tptr(obs.contiguous()), N.tptr(v), N.tptr(logits),
+                                                  N.torch_stream_ptr()))
+            return v, logits
         n, A = obs.shape[0], self.cfg.action_dim
         v, loc, ls = (torch.empty(n, dtype=torch.float32, device=self.dev), torch.empty((n, A), dtype=torch.float32, device=self.dev),
                       torch.empty((n, A), dtype=torch.float32, device=self.dev))
@@ -199,11 +289,22 @@ class PPOEngine:
         return v, loc, ls
 
     def _fused_rollout_ok(self) -> bool:
+        if self.cat:
+            return (self.fused and isinstance(self.env, CartPoleAutoVecEnv) and self.cfg.n_envs % 16 == 0
+                    and self.cfg.horizon <= self.lib.srlx_ppo_cat_rollout_max_horizon(self.cfg.n_actions))
         return (self.fused and isinstance(self.env, PendulumVecEnv) and self.cfg.obs_dim == 3 and self.cfg.n_envs % 16 == 0
                 and self.cfg.horizon <= self.lib.srlx_ppo_net_rollout_max_horizon(self.cfg.action_dim))  # (longer horizons: the step-wise kernels)
 
     def rollout(self):
         cfg = self.cfg
+        if self.cat and self._fused_rollout_ok():  # (csrc/srlx_ppo_net.hip: k_ppo_cat_rollout)
+            env = self.env
+            N.check(self.lib.srlx_ppo_cat_rollout(cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(self.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes),
+                                                  N.tptr(env.obs), env.episode_len, env.seed, cfg.seed ^ 0x61637400, N.tptr(self.act_counter), cfg.discount, cfg.gae_discount,
+                                                  N.tptr(self.b_obs), N.tptr(self.b_act), N.tptr(self.b_logp), N.tptr(self.b_val), N.tptr(self.b_rew), N.tptr(self.b_done),
+                                                  N.tptr(self.b_adv), N.tptr(self._last_v), N.tptr(self.episode_return), N.tptr(self.finished_returns),
+                                                  N.torch_stream_ptr()))
+            return
         if self._fused_rollout_ok():  # T steps of everything in ONE launch (csrc/srlx_ppo_net.hip: k_ppo_rollout)
             env = self.env
             N.check(self.lib.srlx_ppo_net_rollout(cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(self.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len,
@@ -214,13 +315,16 @@ class PPOEngine:
             return
         for t in range(cfg.horizon):
             self.b_val[t].copy_(self.act(self.b_obs[t], self.b_act[t], self.b_logp[t]))
-            self.env.step(self.b_act[t, :, 0].contiguous() if cfg.action_dim > 1 else self.b_act[t].view(-1), self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
+            if self.cat:
+                self.env.step(self.b_act[t], self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
+            else:
+                self.env.step(self.b_act[t, :, 0].contiguous() if cfg.action_dim > 1 else self.b_act[t].view(-1), self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
             self.episode_return += self.b_rew[t]
             d = self.b_done[t].bool()
             self.finished_returns[0] += (self.episode_return * d).sum()
             self.finished_returns[1] += d.sum()
             self.episode_return.masked_fill_(d, 0.0)
-        last_v, _, _ = self.forward(self.b_obs[cfg.horizon])
+        last_v = self.forward(self.b_obs[cfg.horizon])[0]
         # episode ends are never bootstrapped (ppo.py:396-397); a horizon cut inside an episode bootstraps from V(s_T)
         N.check(self.lib.srlx_gae_scan(cfg.n_envs, cfg.horizon, N.tptr(self.b_rew), N.tptr(self.b_val), N.tptr(self.b_done), N.tptr(last_v.contiguous()),
                                        cfg.discount, cfg.gae_discount, N.tptr(self.b_adv), N.torch_stream_ptr()))
@@ -228,8 +332,18 @@ class PPOEngine:
 
     # --- update ----------------------------------------------------------------------------------------------------
     def loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v):
-        """forward + the fused loss kernel; returns (v, loc, log_scale) with their gradient seeds."""
+        """forward + the fused loss kernel; returns (v, loc, log_scale) with their gradient seeds -- categorical: (v, log-probability of the taken action)."""
         cfg = self.cfg
+        if self.cat:
+            v, logits = self.net(obs)
+            lp = torch.log_softmax(logits, dim=-1).gather(1, action.long().view(-1, 1))  # CategoricalDist.log_prob of the taken action, [B][1]
+            g_lp, g_v = torch.empty_like(lp), torch.empty_like(v)
+            self._keep_loss = (lp.detach().contiguous(), v.detach().contiguous())
+            N.check(self.lib.srlx_ppo_loss_logpi(
+                lp.shape[0], 1, N.tptr(self._keep_loss[0]), N.tptr(old_logp), N.tptr(adv), N.tptr(self._keep_loss[1]), N.tptr(v_target), N.tptr(old_v),
+                int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
+                cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.losses), N.tptr(g_lp), N.tptr(g_v), N.torch_stream_ptr()))
+            return (v, lp), (g_v, g_lp)
         v, loc, ls = self.net(obs)
         B, A = loc.shape
         g_loc, g_ls, g_v = torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(v)
@@ -245,8 +359,8 @@ class PPOEngine:
         T, E = cfg.horizon, cfg.n_envs
         n = T * E
         obs = self.b_obs[:T].reshape(n, cfg.obs_dim)
-        act = self.b_act.reshape(n, cfg.action_dim)
-        logp = self.b_logp.reshape(n, cfg.action_dim)
+        act = self.b_act.reshape(n, -1)  # [n][action_dim]; categorical: [n][1]
+        logp = self.b_logp.reshape(n, -1)
         adv = self.b_adv.reshape(n)
         val = self.b_val.reshape(n)
         v_target = adv if cfg.v_target == "gae" else adv + val
@@ -278,13 +392,16 @@ class PPOEngine:
         for ep in range(cfg.epochs):
             for k in range(cfg.minibatches):
                 rows = self._perms[ep][k * mb : (k + 1) * mb]
-                N.check(self.lib.srlx_ppo_net_minibatch(mb, N.tptr(rows), cfg.obs_dim, cfg.action_dim, N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(adv),
-                                                        N.tptr(v_target), N.tptr(val), self.ls_range[0], self.ls_range[1], int(cfg.baseline_type == "advantage"),
-                                                        int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
-                                                        cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st))
+                loss_cfg = (int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
+                            cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st)
+                buffers = (N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(adv), N.tptr(v_target), N.tptr(val))
+                if self.cat:
+                    N.check(self.lib.srlx_ppo_cat_minibatch(mb, N.tptr(rows), cfg.obs_dim, cfg.n_actions, *buffers, *loss_cfg))
+                else:
+                    N.check(self.lib.srlx_ppo_net_minibatch(mb, N.tptr(rows), cfg.obs_dim, cfg.action_dim, *buffers, self.ls_range[0], self.ls_range[1], *loss_cfg))
                 scale = self.flat_grad_sync(self.flat_grad) if self.flat_grad_sync is not None else 1.0
-                N.check(self.lib.srlx_ppo_net_adam(cfg.obs_dim, cfg.action_dim, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq),
-                                                   N.tptr(self.opt_step), cfg.lr, 0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st))
+                N.check(self._net_fn("adam")(cfg.obs_dim, self._head, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq),
+                                             N.tptr(self.opt_step), cfg.lr, 0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st))
 
     def capture_graphs(self):
         """Captures the T-step rollout (+ GAE) and the whole update phase into two HIP graphs: an iteration becomes two
@@ -330,6 +447,21 @@ class PPOEngine:
         pl, vl, el = self.losses.tolist()
         return dict(policy_loss=pl, value_loss=vl, entropy_loss=el)
 
+    # --- weight exchange with the PPO plugin (algorithms/ppo.py:Parameter; its network's keys: hidden_block, value_block, value_out, policy_block, policy_out) ---
+    def export_to(self, parameter) -> None:
+        """Copies this engine's network into a plugin `ppo.Parameter` (same blocks, same head), e.g. to evaluate it with `Runner.evaluate()`."""
+        with torch.no_grad():
+            for a, b in _paired_linears(self.net, parameter):
+                b.weight.copy_(a.weight)
+                b.bias.copy_(a.bias)
+
+    def load_from(self, parameter) -> None:
+        """Copies a plugin `ppo.Parameter`'s network into this engine (the fused path's flat vector included: the module's tensors are views of it)."""
+        with torch.no_grad():
+            for a, b in _paired_linears(self.net, parameter):
+                a.weight.copy_(b.weight)
+                a.bias.copy_(b.bias)
+
 
 def flat_grad_all_reduce(net: nn.Module, group=None):
     """Average the gradients of every rank: ONE all-reduce of a flat buffer (about 40 KB for the config-5 network)."""
@@ -373,7 +505,7 @@ class DistributedPPO:
         local = dataclasses.replace(cfg, seed=cfg.seed)  # same seed -> same initial network on every rank
         self.engine = PPOEngine(local, device, grad_sync=flat_grad_all_reduce, flat_grad_sync=flat_vector_all_reduce, fused=fused)
         # decorrelate environments and sampling noise across ranks
-        self.engine.env = PendulumVecEnv(cfg.n_envs, cfg.episode_len, cfg.seed + 7919 * (self.rank + 1), self.engine.dev)
+        self.engine.env = make_env(cfg, cfg.seed + 7919 * (self.rank + 1), self.engine.dev)
         self.engine.b_obs[0].copy_(self.engine.env.obs)
         self.engine.act_counter.fill_(self.rank << 40)
         tensors = [self.engine.flat] if self.engine.fused else [p.data for p in self.engine.net.parameters()]
