@@ -1,6 +1,7 @@
 // srlx_ppo_net.hip -- PPO's actor-critic (srl/algorithms/ppo/ppo.py:55-99 with the default blocks: in -> 64 -> 64 -> {64 -> V, 64 -> (loc, log_scale)}) as four kernels:
-//   k_ppo_rollout   : the WHOLE rollout of an iteration in one launch -- T steps of E Pendulum-shaped environments: network forward, Normal policy sample +
-//                     log-probability (ppo.py:316-339), environment step with auto-reset, the [T][E] buffers, episode returns, V(s_T) and the GAE scan (:389-404).
+//   k_ppo_rollout   : the WHOLE rollout of an iteration in one launch -- T steps of E environments: network forward, policy sample + log-probability
+//                     (ppo.py:316-339), environment step with auto-reset, the [T][E] buffers, episode returns, V(s_T) and the GAE scan (:389-404).  A template over
+//                     its Task -- a policy head on its built-in environment: PendulumNormal, CartPoleCategorical -- which holds all that differs between them.
 //                     One workgroup owns 16 environments for all T steps (an environment's steps depend on each other, the environments do not): weights and
 //                     activations live in LDS (the 64 x 64 layers as v_mfma_f32_16x16x4_f32 tiles), nothing but the buffers goes to HBM.
 //   k_ppo_minibatch : one minibatch of the update in one launch -- gather of the permuted samples, forward, compute_train_loss + gradient seeds (:102-169), the whole
@@ -12,7 +13,7 @@
 // The same four kernels serve a CATEGORICAL head (template parameter CAT; discrete actions, ppo.py:316-324): in -> 64 -> 64 -> {64 -> V, 64 -> n logits}, parameters
 // ... wp, bp, wlogit [n][64], blogit [n].  The n <= 8 logit rows take the 2 * A_MAX = 8 policy-head slots the Normal head's loc / log_scale rows take (slot k: k < 4
 // in wloc's place, else in wls's), so the LDS image, the heads / seeds tables and the whole backward pass are shared; what differs is the parameter layout, the
-// loss seeds and the rollout's policy + environment: k_ppo_cat_rollout steps CartPole (float64 state, srlx_ppo_math.h: cartpole_one) under a categorical sample.
+// loss seeds and the rollout's Task: CartPoleCategorical steps CartPole (float64 state, srlx_ppo_math.h: cartpole_one) under a categorical sample.
 // float32 throughout, fmaf accumulation in ascending input order; the per-sample policy / loss / environment arithmetic is srlx_ppo_math.h, shared with the
 // one-purpose kernels of srlx_ppo.hip.  Parameters are ONE flat float32 vector in torch's `ActorCritic.parameters()` order (weights [out][in]).
 // Bounds: VALU (f32 FMA) -- about 76 kFLOP per sample and update (forward + backward), 25 kFLOP per environment step; HBM traffic is the buffers only.
@@ -243,21 +244,117 @@ __global__ void __launch_bounds__(256) k_ppo_forward(i64 n, int obs, int A, cons
 }
 
 // ---- the rollout -------------------------------------------------------------------------------------------------------------------------------------------------------
+// k_ppo_rollout<Task> is the scaffold -- LDS, weights, the T-step loop, the record tables, episode returns, V(s_T), GAE; a Task (below) is a policy head on its
+// built-in environment: everything the scaffold does not know.
+template <class Task>
 struct RolloutArgs {
     i64 E, T;
-    int A;
+    int A;  // action dimensions (CAT: actions)
     const float *params;
-    float *env_state;  // [E][2] th, thdot
-    int32_t *t_in_ep;  // [E]
-    float *env_obs;    // [E][3]: the observation the rollout starts from / ends at
-    i64 episode_len;
+    float *env_obs;   // [E][OBS]: the observation the rollout starts from / ends at
+    i64 episode_len;  // (CartPole: max_steps)
     u64 env_seed, act_seed;
-    const i64 *env_counter, *act_counter;  // both advance by T per rollout (k_advance2, behind this kernel)
-    float ls_lo, ls_hi;
+    i64 *act_counter;  // advances by T per rollout (Task::advance, behind this kernel)
+    typename Task::Env env;
     double discount, lam;
-    float *b_obs /*[T+1][E][3]*/, *b_act /*[T][E][A]*/, *b_logp, *b_val /*[T][E]*/, *b_rew;
+    float *b_obs /*[T+1][E][OBS]*/;
+    typename Task::Act *b_act /*[T][E][A]; CAT: [T][E]*/;
+    float *b_logp, *b_val /*[T][E]*/, *b_rew;
     u8 *b_done;
     float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
+};
+
+__global__ void k_advance2(i64 *c0, i64 *c1, i64 n) {
+    c0[0] += n;
+    c1[0] += n;
+}
+__global__ void k_advance(i64 *c, i64 n) { c[0] += n; }
+
+// The Normal head on the Pendulum-shaped environment (float32 state; a reset is keyed with the environment counter)
+struct PendulumNormal {
+    static constexpr bool CAT = false;
+    static constexpr int OBS = 3;
+    using Act = float;
+    struct Env {
+        float *state;      // [E][2] th, thdot
+        int32_t *t_in_ep;  // [E]
+        i64 *counter;      // advances by T per rollout, like the action counter
+        float ls_lo, ls_hi;
+    };
+    static bool env_ok(const Env &v) { return v.state && v.t_in_ep && v.counter; }
+    static constexpr int records(int A) { return 3 + A; }  // LDS floats per step and environment: reward, value, done + the A draws of zbuf
+    static void advance(const Env &v, i64 *act_counter, i64 n, hipStream_t s) { hipLaunchKernelGGL(k_advance2, dim3(1), dim3(1), 0, s, v.counter, act_counter, n); }
+    struct Lane {
+        float th = 0.f, thd = 0.f;
+        int tstep = 0;
+        const u64 c_env;  // (uniform)
+        __device__ explicit Lane(const Env &v) : c_env((u64)v.counter[0]) {}
+        __device__ void load(const Env &v, i64 eg) { th = v.state[2 * eg], thd = v.state[2 * eg + 1], tstep = v.t_in_ep[eg]; }
+        __device__ void store(const Env &v, i64 eg) const { v.state[2 * eg] = th, v.state[2 * eg + 1] = thd, v.t_in_ep[eg] = tstep; }
+    };
+    // zbuf [T][RE][A]: the policy's standard-normal draws of the whole rollout, made up front by all threads (double-precision log / cos off the step loop)
+    static __device__ __forceinline__ void draw(const RolloutArgs<PendulumNormal> &a, float *zbuf, u64 c_act, i64 e0) {
+        const int A = a.A;
+        for (i64 w = threadIdx.x; w < a.T * RE * A; w += 256) {
+            const i64 t = w / (RE * A);
+            const int rem = (int)(w % (RE * A)), e = rem / A, d = rem % A;
+            zbuf[w] = srlxp::normal_z(a.act_seed, c_act + (u64)t, (e0 + e) * A + d);
+        }
+    }
+    // policy sample + log-probability (ppo.py:316-339) -> b_act / b_logp [t][eg]; then the environment's step
+    static __device__ __forceinline__ void step(const RolloutArgs<PendulumNormal> &a, Lane &s, const float *hd, const float *zbuf, i64 t, u64, i64 eg, float (&ob)[OBS], float &rw, u8 &dn) {
+        const int A = a.A, tid = threadIdx.x;
+        float act0 = 0.f;
+        for (int d = 0; d < A; d++) {
+            float ac, lp;
+            srlxp::normal_act_from_z(hd[1 + d], hd[1 + A + d], a.env.ls_lo, a.env.ls_hi, zbuf[(t * RE + tid) * A + d], 0, ac, lp);
+            a.b_act[(t * a.E + eg) * A + d] = ac;
+            a.b_logp[(t * a.E + eg) * A + d] = lp;
+            if (d == 0) act0 = ac;
+        }
+        srlxp::pendulum_one(s.th, s.thd, s.tstep, act0, a.episode_len, a.env_seed, s.c_env + (u64)t, eg, ob[0], ob[1], ob[2], rw, dn);
+    }
+};
+
+// The categorical head on CartPole: the environment is float64 (cartpole_one: about 40 f64 operations, one sin and one cos per step on 16 of the workgroup's 256
+// lanes) and keeps no counter: a reset is keyed with (lane, episode of the lane).
+struct CartPoleCategorical {
+    static constexpr bool CAT = true;
+    static constexpr int OBS = 4;
+    using Act = int32_t;
+    struct Env {
+        double *state;              // [E][4]
+        int32_t *steps, *episodes;  // [E]
+    };
+    static bool env_ok(const Env &v) { return v.state && v.steps && v.episodes; }
+    static constexpr int records(int) { return 3; }  // reward, value, done
+    static void advance(const Env &, i64 *act_counter, i64 n, hipStream_t s) { hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, s, act_counter, n); }
+    struct Lane {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        int steps = 0, episode = 0;
+        __device__ explicit Lane(const Env &) {}
+        __device__ void load(const Env &v, i64 eg) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) s[c] = v.state[4 * eg + c];
+            steps = v.steps[eg], episode = v.episodes[eg];
+        }
+        __device__ void store(const Env &v, i64 eg) const {
+#pragma unroll
+            for (int c = 0; c < 4; c++) v.state[4 * eg + c] = s[c];
+            v.steps[eg] = steps, v.episodes[eg] = episode;
+        }
+    };
+    static __device__ __forceinline__ void draw(const RolloutArgs<CartPoleCategorical> &, float *, u64, i64) {}  // (one uniform per step, drawn in it)
+    // categorical sample + log-probability (ppo.py:316-324), the environment's step; then b_act / b_logp [t][eg]
+    static __device__ __forceinline__ void step(const RolloutArgs<CartPoleCategorical> &a, Lane &s, const float *hd, const float *, i64 t, u64 c_act, i64 eg, float (&ob)[OBS], float &rw,
+                                                u8 &dn) {
+        int ac;
+        float lp;
+        srlxp::cat_act_one(hd + 1, a.A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp);
+        srlxp::cartpole_one(s.s, s.steps, s.episode, ac, a.episode_len, a.env_seed, eg, ob, rw, dn);
+        a.b_act[t * a.E + eg] = ac;
+        a.b_logp[t * a.E + eg] = lp;
+    }
 };
 
 // The GAE scan of one environment (thread tid < RE) over the rollout's LDS records (the arithmetic of k_gae_scan, srlx_train.hip)
@@ -281,168 +378,67 @@ __device__ __forceinline__ void gae_rows(const float *t_rew, const float *t_val,
     }
 }
 
-__global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs a) {
+template <class Task>
+__global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
+    constexpr int OBS = Task::OBS;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     FwdLds &L = *reinterpret_cast<FwdLds *>(lds_raw);
     float *t_rew = reinterpret_cast<float *>(lds_raw + sizeof(FwdLds));  // [T][RE]
     float *t_val = t_rew + a.T * RE;
     float *t_done = t_val + a.T * RE;
-    float *zbuf = t_done + a.T * RE;  // [T][RE][A]: the policy's standard-normal draws of the whole rollout, made up front by all threads (double-precision log / cos off the step loop)
-    const int obs = 3, A = a.A, tid = threadIdx.x;
-    const NetOff o = net_off(obs, A);
-    load_forward_weights(L, a.params, o, obs, A);
+    float *zbuf = t_done + a.T * RE;  // (the records a Task asks for beyond these three)
+    const int A = a.A, tid = threadIdx.x;
+    const NetOff o = net_off_of<Task::CAT>(OBS, A);
+    load_forward_weights<Task::CAT>(L, a.params, o, OBS, A);
     const i64 e0 = (i64)blockIdx.x * RE, eg = e0 + tid;  // (tid < RE: this thread's environment)
-    float th = 0.f, thd = 0.f, er = 0.f, fin_sum = 0.f, fin_cnt = 0.f;
-    int tstep = 0;
-    if (tid < RE) {
-        th = a.env_state[2 * eg], thd = a.env_state[2 * eg + 1], tstep = a.t_in_ep[eg], er = a.episode_return[eg];
-        for (int c = 0; c < 3; c++) {
-            const float v = a.env_obs[3 * eg + c];
-            L.x[tid * OBS_MAX + c] = v;
-            a.b_obs[3 * eg + c] = v;
-        }
-    }
-    const u64 c_act = (u64)a.act_counter[0], c_env = (u64)a.env_counter[0];
-    for (i64 w = tid; w < a.T * RE * A; w += 256) {
-        const i64 t = w / (RE * A);
-        const int rem = (int)(w % (RE * A)), e = rem / A, d = rem % A;
-        zbuf[w] = srlxp::normal_z(a.act_seed, c_act + (u64)t, (e0 + e) * A + d);
-    }
-    __syncthreads();
-    for (i64 t = 0; t < a.T; t++) {
-        forward_rows(L, obs, A, false);
-        if (tid < RE) {
-            const float *hd = L.heads + tid * (1 + 2 * A_MAX);
-            float act0 = 0.f;
-            for (int d = 0; d < A; d++) {
-                float ac, lp;
-                srlxp::normal_act_from_z(hd[1 + d], hd[1 + A + d], a.ls_lo, a.ls_hi, zbuf[(t * RE + tid) * A + d], 0, ac, lp);
-                a.b_act[(t * a.E + eg) * A + d] = ac;
-                a.b_logp[(t * a.E + eg) * A + d] = lp;
-                if (d == 0) act0 = ac;
-            }
-            float o0, o1, o2, rw;
-            u8 dn;
-            srlxp::pendulum_one(th, thd, tstep, act0, a.episode_len, a.env_seed, c_env + (u64)t, eg, o0, o1, o2, rw, dn);
-            const i64 k = t * a.E + eg;
-            a.b_val[k] = hd[0];
-            a.b_rew[k] = rw;
-            a.b_done[k] = dn;
-            float *ob = a.b_obs + ((t + 1) * a.E + eg) * 3;
-            ob[0] = o0, ob[1] = o1, ob[2] = o2;
-            L.x[tid * OBS_MAX + 0] = o0, L.x[tid * OBS_MAX + 1] = o1, L.x[tid * OBS_MAX + 2] = o2;
-            t_rew[t * RE + tid] = rw, t_val[t * RE + tid] = hd[0], t_done[t * RE + tid] = dn ? 1.f : 0.f;
-            er += rw;
-            if (dn) fin_sum += er, fin_cnt += 1.f, er = 0.f;
-        }
-        __syncthreads();
-    }
-    forward_rows(L, obs, A, true);  // V(s_T): a horizon cut inside an episode bootstraps from it, an episode end never does (ppo.py:396-397)
-    if (tid < RE) {
-        const float lv = L.heads[tid * (1 + 2 * A_MAX)];
-        a.last_v[eg] = lv;
-        gae_rows(t_rew, t_val, t_done, a.T, a.E, eg, tid, lv, a.discount, a.lam, a.b_adv);
-        a.env_state[2 * eg] = th, a.env_state[2 * eg + 1] = thd, a.t_in_ep[eg] = tstep, a.episode_return[eg] = er;
-        for (int c = 0; c < 3; c++) a.env_obs[3 * eg + c] = L.x[tid * OBS_MAX + c];
-        if (fin_cnt > 0.f) {
-            atomicAdd(&a.finished[0], fin_sum);
-            atomicAdd(&a.finished[1], fin_cnt);
-        }
-    }
-}
-
-__global__ void k_advance2(i64 *c0, i64 *c1, i64 n) {
-    c0[0] += n;
-    c1[0] += n;
-}
-
-// ---- the rollout of the categorical head on CartPole -----------------------------------------------------------------------------------------------------------------
-// As k_ppo_rollout: one workgroup owns 16 environments for all T steps.  The environment is float64 (cartpole_one: about 40 f64 operations, one sin and one cos per
-// step on 16 of the workgroup's 256 lanes) and keeps no counter: a reset is keyed with (lane, episode of the lane).
-struct CatRolloutArgs {
-    i64 E, T;
-    int n;  // actions
-    const float *params;
-    double *env_state;           // [E][4]
-    int32_t *steps, *episodes;   // [E]
-    float *env_obs;              // [E][4]: the observation the rollout starts from / ends at
-    i64 max_steps;
-    u64 env_seed, act_seed;
-    const i64 *act_counter;  // advances by T per rollout (k_advance, behind this kernel)
-    double discount, lam;
-    float *b_obs /*[T+1][E][4]*/;
-    int32_t *b_act /*[T][E]*/;
-    float *b_logp, *b_val /*[T][E]*/, *b_rew;
-    u8 *b_done;
-    float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
-};
-
-__global__ void __launch_bounds__(256) k_ppo_cat_rollout(CatRolloutArgs a) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    FwdLds &L = *reinterpret_cast<FwdLds *>(lds_raw);
-    float *t_rew = reinterpret_cast<float *>(lds_raw + sizeof(FwdLds));  // [T][RE]
-    float *t_val = t_rew + a.T * RE;
-    float *t_done = t_val + a.T * RE;
-    const int obs = 4, A = a.n, tid = threadIdx.x;
-    const NetOff o = net_off_cat(obs, A);
-    load_forward_weights<true>(L, a.params, o, obs, A);
-    const i64 e0 = (i64)blockIdx.x * RE, eg = e0 + tid;  // (tid < RE: this thread's environment)
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    int steps = 0, episode = 0;
+    typename Task::Lane lane(a.env);
     float er = 0.f, fin_sum = 0.f, fin_cnt = 0.f;
     if (tid < RE) {
-#pragma unroll
-        for (int c = 0; c < 4; c++) s[c] = a.env_state[4 * eg + c];
-        steps = a.steps[eg], episode = a.episodes[eg], er = a.episode_return[eg];
-        for (int c = 0; c < 4; c++) {
-            const float v = a.env_obs[4 * eg + c];
+        lane.load(a.env, eg);
+        er = a.episode_return[eg];
+        for (int c = 0; c < OBS; c++) {
+            const float v = a.env_obs[OBS * eg + c];
             L.x[tid * OBS_MAX + c] = v;
-            a.b_obs[4 * eg + c] = v;
+            a.b_obs[OBS * eg + c] = v;
         }
     }
     const u64 c_act = (u64)a.act_counter[0];
+    Task::draw(a, zbuf, c_act, e0);
     __syncthreads();
     for (i64 t = 0; t < a.T; t++) {
-        forward_rows<true>(L, obs, A, false);
+        forward_rows<Task::CAT>(L, OBS, A, false);
         if (tid < RE) {
             const float *hd = L.heads + tid * (1 + 2 * A_MAX);
-            int ac;
-            float lp, ob[4], rw;
+            float ob[OBS], rw;
             u8 dn;
-            srlxp::cat_act_one(hd + 1, A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp);
-            srlxp::cartpole_one(s, steps, episode, ac, a.max_steps, a.env_seed, eg, ob, rw, dn);
+            Task::step(a, lane, hd, zbuf, t, c_act, eg, ob, rw, dn);
             const i64 k = t * a.E + eg;
-            a.b_act[k] = ac;
-            a.b_logp[k] = lp;
             a.b_val[k] = hd[0];
             a.b_rew[k] = rw;
             a.b_done[k] = dn;
-            float *bo = a.b_obs + ((t + 1) * a.E + eg) * 4;
+            float *bo = a.b_obs + ((t + 1) * a.E + eg) * OBS;
 #pragma unroll
-            for (int c = 0; c < 4; c++) bo[c] = ob[c], L.x[tid * OBS_MAX + c] = ob[c];
+            for (int c = 0; c < OBS; c++) bo[c] = ob[c], L.x[tid * OBS_MAX + c] = ob[c];
             t_rew[t * RE + tid] = rw, t_val[t * RE + tid] = hd[0], t_done[t * RE + tid] = dn ? 1.f : 0.f;
             er += rw;
             if (dn) fin_sum += er, fin_cnt += 1.f, er = 0.f;
         }
         __syncthreads();
     }
-    forward_rows<true>(L, obs, A, true);  // V(s_T)
+    forward_rows<Task::CAT>(L, OBS, A, true);  // V(s_T): a horizon cut inside an episode bootstraps from it, an episode end never does (ppo.py:396-397)
     if (tid < RE) {
         const float lv = L.heads[tid * (1 + 2 * A_MAX)];
         a.last_v[eg] = lv;
         gae_rows(t_rew, t_val, t_done, a.T, a.E, eg, tid, lv, a.discount, a.lam, a.b_adv);
-#pragma unroll
-        for (int c = 0; c < 4; c++) a.env_state[4 * eg + c] = s[c];
-        a.steps[eg] = steps, a.episodes[eg] = episode, a.episode_return[eg] = er;
-        for (int c = 0; c < 4; c++) a.env_obs[4 * eg + c] = L.x[tid * OBS_MAX + c];
+        lane.store(a.env, eg);
+        a.episode_return[eg] = er;
+        for (int c = 0; c < OBS; c++) a.env_obs[OBS * eg + c] = L.x[tid * OBS_MAX + c];
         if (fin_cnt > 0.f) {
             atomicAdd(&a.finished[0], fin_sum);
             atomicAdd(&a.finished[1], fin_cnt);
         }
     }
 }
-
-__global__ void k_advance(i64 *c, i64 n) { c[0] += n; }
 
 // ---- one minibatch: forward + loss + backward ----------------------------------------------------------------------------------------------------------------------
 struct MbArgs {
@@ -798,10 +794,50 @@ __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ pa
 }
 
 static_assert(H * OBS_MAX + 3 * H * H + 2 * A_MAX * H + 5 * H + 1 + 2 * A_MAX <= 16 * 1024, "k_ppo_adam: sixteen elements per thread");
-bool geometry_ok(int obs, int A) { return obs >= 1 && obs <= OBS_MAX && A >= 1 && A <= A_MAX; }
 // categorical: 2 .. 8 actions -- the heads table's eight policy slots per row; more would widen the tables and the backward's fixed extents
-bool cat_geometry_ok(int obs, int n) { return obs >= 1 && obs <= OBS_MAX && n >= 2 && n <= srlxp::kCatMax; }
-constexpr size_t kLdsMax = 160 * 1024;
+template <bool CAT>
+bool geometry_ok(int obs, int A) {
+    return obs >= 1 && obs <= OBS_MAX && (CAT ? A >= 2 && A <= srlxp::kCatMax : A >= 1 && A <= A_MAX);
+}
+template <bool CAT>
+int param_count(int obs, int A) {
+    return geometry_ok<CAT>(obs, A) ? net_off_of<CAT>(obs, A).total : -1;
+}
+constexpr int partials_stride(int params) { return (params + 3 + 3) & ~3; }  // per-workgroup gradient sums + 3 loss sums, 16-byte rows
+template <bool CAT>
+int partials_floats(int obs, int A) {
+    return geometry_ok<CAT>(obs, A) ? 256 * partials_stride(net_off_of<CAT>(obs, A).total) : -1;
+}
+constexpr size_t kLdsMax = 160 * 1024;  // a workgroup's LDS (gfx950)
+
+template <class Task>
+int rollout_max_horizon(int A) {  // what fits the workgroup's LDS beside weights and activations
+    if (!geometry_ok<Task::CAT>(Task::OBS, A)) return -1;
+    const long long t = ((long long)kLdsMax - (long long)sizeof(FwdLds)) / ((long long)RE * Task::records(A) * (long long)sizeof(float));
+    return (int)(t < 1024 ? t : 1024);
+}
+
+// name: the entry point's, for its error texts
+template <class Task>
+int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream) {
+    SRLX_REQUIRE(a.E > 0 && a.E % RE == 0, "%s: the environment count must be a multiple of 16", name);
+    SRLX_REQUIRE(a.T > 0 && geometry_ok<Task::CAT>(Task::OBS, a.A) && a.T <= rollout_max_horizon<Task>(a.A) && a.episode_len > 0,
+                 "%s: bad geometry (horizon <= srlx_%s_max_horizon)", name, name);
+    SRLX_REQUIRE(a.params && Task::env_ok(a.env) && a.env_obs && a.act_counter && a.b_obs && a.b_act && a.b_logp && a.b_val && a.b_rew && a.b_done && a.b_adv && a.last_v &&
+                     a.episode_return && a.finished,
+                 "%s: NULL argument", name);
+    const size_t lds = sizeof(FwdLds) + (size_t)a.T * RE * Task::records(a.A) * sizeof(float);
+    SRLX_REQUIRE(lds <= kLdsMax, "%s: horizon too long for the workgroup's LDS", name);
+    static size_t lds_set = 0;
+    if (lds > lds_set) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout<Task>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL(k_ppo_rollout<Task>, dim3((unsigned)(a.E / RE)), dim3(256), lds, (hipStream_t)stream, a);
+    Task::advance(a.env, a.act_counter, a.T, (hipStream_t)stream);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
 
 template <bool CAT>
 int launch_forward(i64 n, int obs, int A, const float *params, const float *x, float *v, float *h0, float *h1, void *stream) {
@@ -825,7 +861,7 @@ int launch_minibatch(MbArgs &a, float *d_grad, float *d_losses, void *stream) {
         attr = true;
     }
     const NetOff o = net_off_of<CAT>(a.obs, a.A);
-    a.stride = (o.total + 3 + 3) & ~3;
+    a.stride = partials_stride(o.total);
     const i64 tiles = (a.mb + S - 1) / S;
     const int wgs = (int)(tiles < 256 ? tiles : 256);
     hipLaunchKernelGGL(k_ppo_minibatch<CAT>, dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, a);
@@ -846,50 +882,30 @@ int launch_adam(int P, float *d_params, float *d_grad, float *d_exp_avg, float *
 
 extern "C" {
 
-int srlx_ppo_net_param_count(int obs_dim, int action_dim) { return geometry_ok(obs_dim, action_dim) ? net_off(obs_dim, action_dim).total : -1; }
+int srlx_ppo_net_param_count(int obs_dim, int action_dim) { return param_count<false>(obs_dim, action_dim); }
 
 int srlx_ppo_net_forward(int64_t n, int obs_dim, int action_dim, const float *d_params, const float *d_obs, float *d_v, float *d_loc, float *d_log_scale, void *stream) {
-    SRLX_REQUIRE(n > 0 && geometry_ok(obs_dim, action_dim) && d_params && d_obs && d_v && d_loc && d_log_scale, "ppo_net_forward: bad argument");
+    SRLX_REQUIRE(n > 0 && geometry_ok<false>(obs_dim, action_dim) && d_params && d_obs && d_v && d_loc && d_log_scale, "ppo_net_forward: bad argument");
     return launch_forward<false>(n, obs_dim, action_dim, d_params, d_obs, d_v, d_loc, d_log_scale, stream);
 }
 
-int srlx_ppo_net_rollout_max_horizon(int action_dim) {  // what fits the workgroup's LDS beside weights and activations
-    if (!geometry_ok(3, action_dim)) return -1;
-    const long long t = ((long long)160 * 1024 - (long long)sizeof(FwdLds)) / ((long long)RE * (3 + action_dim) * (long long)sizeof(float));
-    return (int)(t < 1024 ? t : 1024);
-}
+int srlx_ppo_net_rollout_max_horizon(int action_dim) { return rollout_max_horizon<PendulumNormal>(action_dim); }
 
 int srlx_ppo_net_rollout(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state, int32_t *d_step_in_episode, float *d_env_obs,
                          int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter, uint64_t act_seed, int64_t *d_act_counter, double log_scale_min,
                          double log_scale_max, double discount, double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
                          uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished, void *stream) {
-    SRLX_REQUIRE(n_envs > 0 && n_envs % RE == 0, "ppo_net_rollout: the environment count must be a multiple of 16");
-    SRLX_REQUIRE(horizon > 0 && geometry_ok(3, action_dim) && horizon <= srlx_ppo_net_rollout_max_horizon(action_dim) && episode_len > 0,
-                 "ppo_net_rollout: bad geometry (horizon <= srlx_ppo_net_rollout_max_horizon)");
-    SRLX_REQUIRE(d_params && d_env_state && d_step_in_episode && d_env_obs && d_env_counter && d_act_counter && d_b_obs && d_b_act && d_b_logp && d_b_val && d_b_rew && d_b_done &&
-                     d_b_adv && d_last_v && d_episode_return && d_finished,
-                 "ppo_net_rollout: NULL argument");
-    const size_t lds = sizeof(FwdLds) + (size_t)horizon * RE * (3 + action_dim) * sizeof(float);
-    SRLX_REQUIRE(lds <= 160 * 1024, "ppo_net_rollout: horizon too long for the workgroup's LDS");
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
-    RolloutArgs a{n_envs, horizon, action_dim, d_params, d_env_state, d_step_in_episode, d_env_obs, episode_len, (u64)env_seed, (u64)act_seed, d_env_counter, d_act_counter,
-                  (float)log_scale_min, (float)log_scale_max, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return,
-                  d_finished};
-    hipLaunchKernelGGL(k_ppo_rollout, dim3((unsigned)(n_envs / RE)), dim3(256), lds, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_advance2, dim3(1), dim3(1), 0, (hipStream_t)stream, d_env_counter, d_act_counter, (i64)horizon);
-    SRLX_HIP(hipGetLastError());
-    return SRLX_OK;
+    const RolloutArgs<PendulumNormal> a{n_envs, horizon, action_dim, d_params, d_env_obs, episode_len, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                        {d_env_state, d_step_in_episode, d_env_counter, (float)log_scale_min, (float)log_scale_max}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv,
+                                        d_last_v, d_episode_return, d_finished};
+    return launch_rollout("ppo_net_rollout", a, stream);
 }
 
 int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int action_dim, const float *d_params, const float *d_b_obs, const float *d_b_act,
                            const float *d_b_logp, const float *d_b_adv, const float *d_b_v_target, const float *d_b_val, double log_scale_min, double log_scale_max,
                            int baseline_advantage, int surrogate_clip, double policy_clip_range, int enable_value_clip, double value_clip_range, double value_loss_weight,
                            double entropy_weight, float *d_partials, float *d_grad, float *d_losses, void *stream) {
-    SRLX_REQUIRE(minibatch > 0 && geometry_ok(obs_dim, action_dim), "ppo_net_minibatch: bad geometry");
+    SRLX_REQUIRE(minibatch > 0 && geometry_ok<false>(obs_dim, action_dim), "ppo_net_minibatch: bad geometry");
     SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_net_minibatch: NULL argument");
     MbArgs a{};
     a.mb = minibatch;
@@ -903,33 +919,23 @@ int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
     return launch_minibatch<false>(a, d_grad, d_losses, stream);
 }
 
-int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) {
-    if (!geometry_ok(obs_dim, action_dim)) return -1;
-    return 256 * ((net_off(obs_dim, action_dim).total + 3 + 3) & ~3);
-}
+int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) { return partials_floats<false>(obs_dim, action_dim); }
 
 int srlx_ppo_net_adam(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
-    SRLX_REQUIRE(geometry_ok(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam: bad argument");
-    return launch_adam(net_off(obs_dim, action_dim).total, d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
+    SRLX_REQUIRE(geometry_ok<false>(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam: bad argument");
+    return launch_adam(param_count<false>(obs_dim, action_dim), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
 }
 
 // ---- the categorical head ---------------------------------------------------------------------------------------------------------------------------------------------
-int srlx_ppo_cat_param_count(int obs_dim, int n_actions) { return cat_geometry_ok(obs_dim, n_actions) ? net_off_cat(obs_dim, n_actions).total : -1; }
+int srlx_ppo_cat_param_count(int obs_dim, int n_actions) { return param_count<true>(obs_dim, n_actions); }
 
-int srlx_ppo_cat_partials_floats(int obs_dim, int n_actions) {
-    if (!cat_geometry_ok(obs_dim, n_actions)) return -1;
-    return 256 * ((net_off_cat(obs_dim, n_actions).total + 3 + 3) & ~3);
-}
+int srlx_ppo_cat_partials_floats(int obs_dim, int n_actions) { return partials_floats<true>(obs_dim, n_actions); }
 
-int srlx_ppo_cat_rollout_max_horizon(int n_actions) {  // what fits the workgroup's LDS beside weights and activations: three records per step and environment
-    if (!cat_geometry_ok(4, n_actions)) return -1;
-    const long long t = ((long long)kLdsMax - (long long)sizeof(FwdLds)) / ((long long)RE * 3 * (long long)sizeof(float));
-    return (int)(t < 1024 ? t : 1024);
-}
+int srlx_ppo_cat_rollout_max_horizon(int n_actions) { return rollout_max_horizon<CartPoleCategorical>(n_actions); }
 
 int srlx_ppo_cat_forward(int64_t n, int obs_dim, int n_actions, const float *d_params, const float *d_obs, float *d_v, float *d_logits, void *stream) {
-    SRLX_REQUIRE(n > 0 && cat_geometry_ok(obs_dim, n_actions) && d_params && d_obs && d_v && d_logits, "ppo_cat_forward: bad argument");
+    SRLX_REQUIRE(n > 0 && geometry_ok<true>(obs_dim, n_actions) && d_params && d_obs && d_v && d_logits, "ppo_cat_forward: bad argument");
     return launch_forward<true>(n, obs_dim, n_actions, d_params, d_obs, d_v, d_logits, nullptr, stream);
 }
 
@@ -937,32 +943,16 @@ int srlx_ppo_cat_rollout(int64_t n_envs, int64_t horizon, int n_actions, const f
                          int64_t max_steps, uint64_t env_seed, uint64_t act_seed, int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act,
                          float *d_b_logp, float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
                          void *stream) {
-    SRLX_REQUIRE(n_envs > 0 && n_envs % RE == 0, "ppo_cat_rollout: the environment count must be a multiple of 16");
-    SRLX_REQUIRE(horizon > 0 && cat_geometry_ok(4, n_actions) && horizon <= srlx_ppo_cat_rollout_max_horizon(n_actions) && max_steps > 0,
-                 "ppo_cat_rollout: bad geometry (horizon <= srlx_ppo_cat_rollout_max_horizon)");
-    SRLX_REQUIRE(d_params && d_env_state && d_steps && d_episodes && d_env_obs && d_act_counter && d_b_obs && d_b_act && d_b_logp && d_b_val && d_b_rew && d_b_done && d_b_adv &&
-                     d_last_v && d_episode_return && d_finished,
-                 "ppo_cat_rollout: NULL argument");
-    const size_t lds = sizeof(FwdLds) + (size_t)horizon * RE * 3 * sizeof(float);
-    SRLX_REQUIRE(lds <= kLdsMax, "ppo_cat_rollout: horizon too long for the workgroup's LDS");
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_cat_rollout, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
-    CatRolloutArgs a{n_envs, horizon, n_actions, d_params, d_env_state, d_steps, d_episodes, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter, discount, gae_lambda,
-                     d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished};
-    hipLaunchKernelGGL(k_ppo_cat_rollout, dim3((unsigned)(n_envs / RE)), dim3(256), lds, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, d_act_counter, (i64)horizon);
-    SRLX_HIP(hipGetLastError());
-    return SRLX_OK;
+    const RolloutArgs<CartPoleCategorical> a{n_envs, horizon, n_actions, d_params, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                             {d_env_state, d_steps, d_episodes}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished};
+    return launch_rollout("ppo_cat_rollout", a, stream);
 }
 
 int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params, const float *d_b_obs, const int32_t *d_b_act,
                            const float *d_b_logp, const float *d_b_adv, const float *d_b_v_target, const float *d_b_val, int baseline_advantage, int surrogate_clip,
                            double policy_clip_range, int enable_value_clip, double value_clip_range, double value_loss_weight, double entropy_weight, float *d_partials,
                            float *d_grad, float *d_losses, void *stream) {
-    SRLX_REQUIRE(minibatch > 0 && cat_geometry_ok(obs_dim, n_actions), "ppo_cat_minibatch: bad geometry");
+    SRLX_REQUIRE(minibatch > 0 && geometry_ok<true>(obs_dim, n_actions), "ppo_cat_minibatch: bad geometry");
     SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_cat_minibatch: NULL argument");
     MbArgs a{};
     a.mb = minibatch;
@@ -978,8 +968,8 @@ int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
 
 int srlx_ppo_cat_adam(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
-    SRLX_REQUIRE(cat_geometry_ok(obs_dim, n_actions) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_cat_adam: bad argument");
-    return launch_adam(net_off_cat(obs_dim, n_actions).total, d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
+    SRLX_REQUIRE(geometry_ok<true>(obs_dim, n_actions) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_cat_adam: bad argument");
+    return launch_adam(param_count<true>(obs_dim, n_actions), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
 }
 
 }  // extern "C"

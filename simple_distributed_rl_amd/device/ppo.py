@@ -87,7 +87,7 @@ class ActorCritic(nn.Module):
         self.value_block, nv = mlp(n, cfg.value_sizes)
         self.value_out_layer = nn.Linear(nv, 1)
         self.policy_block, n_pol = mlp(n, cfg.policy_sizes)
-        self.categorical = cfg.n_actions > 0
+        self.categorical = head_of(cfg).cat
         if self.categorical:
             self.logits_layer = nn.Linear(n_pol, cfg.n_actions)  # categorical_dist_block.py:134-153
         else:
@@ -156,8 +156,100 @@ class CartPoleAutoVecEnv:
 
 def make_env(cfg: PPODeviceConfig, seed: int, device: torch.device):
     """The built-in environment of a configuration: CartPole under a categorical head, the Pendulum-shaped one otherwise."""
-    cls = CartPoleAutoVecEnv if cfg.n_actions > 0 else PendulumVecEnv
-    return cls(cfg.n_envs, cfg.episode_len, seed, device)
+    return head_of(cfg).env_cls(cfg.n_envs, cfg.episode_len, seed, device)
+
+
+def _loss_args(cfg):
+    return (int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
+            cfg.value_loss_weight, cfg.entropy_weight)
+
+
+class NormalPendulumHead:
+    """The Normal head (loc, log_scale per action dimension; ppo.py:316-339) on the Pendulum-shaped environment: `srlx_ppo_net_*`.  Every method takes the engine `e`
+    and reads its environment, buffers and counters at call time (`e.env` may be swapped after construction)."""
+    cat, env_cls, env_obs_dim, act_dtype, fused_sizes, envelope = False, PendulumVecEnv, 3, torch.float32, range(1, 5), "action_dim <= 4"
+
+    def __init__(self, cfg, lib):
+        self.size, self.act_shape = cfg.action_dim, (cfg.action_dim,)  # the head's size for libsrlx; b_act / b_logp are [T][E] + act_shape
+        self.param_count, self.partials_floats = lib.srlx_ppo_net_param_count, lib.srlx_ppo_net_partials_floats
+        self.adam, self.rollout_max_horizon = lib.srlx_ppo_net_adam, lib.srlx_ppo_net_rollout_max_horizon
+
+    def sample(self, e, loc, ls, action_out, logp_out, deterministic):  # the step-wise path's policy sample + log-probability
+        N.check(e.lib.srlx_ppo_normal_act(loc.numel(), N.tptr(loc), N.tptr(ls), e.ls_range[0], e.ls_range[1], e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter),
+                                          int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
+
+    def forward(self, e, obs):  # the libsrlx network: (v [n], loc [n][A], log_scale [n][A])
+        n, A = obs.shape[0], self.size
+        v, loc, ls = (torch.empty(shape, dtype=torch.float32, device=e.dev) for shape in (n, (n, A), (n, A)))
+        N.check(e.lib.srlx_ppo_net_forward(n, e.cfg.obs_dim, A, N.tptr(e.flat), N.tptr(obs.contiguous()), N.tptr(v), N.tptr(loc), N.tptr(ls), N.torch_stream_ptr()))
+        return v, loc, ls
+
+    def rollout(self, e):  # T steps of everything in ONE launch (csrc/srlx_ppo_net.hip: k_ppo_rollout<PendulumNormal>)
+        cfg, env = e.cfg, e.env
+        N.check(e.lib.srlx_ppo_net_rollout(cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len,
+                                           env.seed, N.tptr(env.counter), cfg.seed ^ 0x61637400, N.tptr(e.act_counter), e.ls_range[0], e.ls_range[1], cfg.discount,
+                                           cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done),
+                                           N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns), N.torch_stream_ptr()))
+
+    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
+        v, loc, ls = e.net(obs)
+        B, A = loc.shape
+        g_loc, g_ls, g_v = torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(v)
+        N.check(e.lib.srlx_ppo_loss_normal(
+            B, A, N.tptr(loc.detach()), N.tptr(ls.detach()), e.ls_range[0], e.ls_range[1], N.tptr(action), N.tptr(old_logp), N.tptr(adv), N.tptr(v.detach()),
+            N.tptr(v_target), N.tptr(old_v), *_loss_args(e.cfg), N.tptr(e.losses), N.tptr(g_loc), N.tptr(g_ls), N.tptr(g_v), N.torch_stream_ptr()))
+        return (v, loc, ls), (g_v, g_loc, g_ls)
+
+    def minibatch(self, e, mb, rows, buffers, outputs):
+        N.check(e.lib.srlx_ppo_net_minibatch(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, e.ls_range[0], e.ls_range[1], *_loss_args(e.cfg), *outputs))
+
+
+class CategoricalCartPoleHead:
+    """The categorical head (n_actions logits; ppo.py:316-324, CategoricalDist) on self-resetting CartPole: `srlx_ppo_cat_*`; one action index and one
+    log-probability per step.  Same methods as the Normal head."""
+    cat, env_cls, env_obs_dim, act_dtype, fused_sizes, envelope = True, CartPoleAutoVecEnv, 4, torch.int32, range(2, 9), "2 <= n_actions <= 8"
+
+    def __init__(self, cfg, lib):
+        if cfg.obs_dim != 4:
+            raise ValueError("PPODeviceConfig(n_actions > 0) runs CartPole: obs_dim must be 4")
+        if cfg.n_actions < 2:
+            raise ValueError("a categorical policy needs at least 2 actions")
+        self.size, self.act_shape = cfg.n_actions, ()
+        self.param_count, self.partials_floats = lib.srlx_ppo_cat_param_count, lib.srlx_ppo_cat_partials_floats
+        self.adam, self.rollout_max_horizon = lib.srlx_ppo_cat_adam, lib.srlx_ppo_cat_rollout_max_horizon
+
+    def sample(self, e, logits, action_out, logp_out, deterministic):
+        N.check(e.lib.srlx_ppo_categorical_act(logits.shape[0], self.size, N.tptr(logits), e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter), int(deterministic),
+                                               N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
+
+    def forward(self, e, obs):  # the libsrlx network: (v [n], logits [n][n_actions])
+        n = obs.shape[0]
+        v, logits = torch.empty(n, dtype=torch.float32, device=e.dev), torch.empty((n, self.size), dtype=torch.float32, device=e.dev)
+        N.check(e.lib.srlx_ppo_cat_forward(n, e.cfg.obs_dim, self.size, N.tptr(e.flat), N.tptr(obs.contiguous()), N.tptr(v), N.tptr(logits), N.torch_stream_ptr()))
+        return v, logits
+
+    def rollout(self, e):  # (csrc/srlx_ppo_net.hip: k_ppo_rollout<CartPoleCategorical>)
+        cfg, env = e.cfg, e.env
+        N.check(e.lib.srlx_ppo_cat_rollout(cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes), N.tptr(env.obs),
+                                           env.episode_len, env.seed, cfg.seed ^ 0x61637400, N.tptr(e.act_counter), cfg.discount, cfg.gae_discount, N.tptr(e.b_obs),
+                                           N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v),
+                                           N.tptr(e.episode_return), N.tptr(e.finished_returns), N.torch_stream_ptr()))
+
+    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
+        v, logits = e.net(obs)
+        lp = torch.log_softmax(logits, dim=-1).gather(1, action.long().view(-1, 1))  # CategoricalDist.log_prob of the taken action, [B][1]
+        g_lp, g_v = torch.empty_like(lp), torch.empty_like(v)
+        e._keep_loss = (lp.detach().contiguous(), v.detach().contiguous())
+        N.check(e.lib.srlx_ppo_loss_logpi(lp.shape[0], 1, N.tptr(e._keep_loss[0]), N.tptr(old_logp), N.tptr(adv), N.tptr(e._keep_loss[1]), N.tptr(v_target), N.tptr(old_v),
+                                          *_loss_args(e.cfg), N.tptr(e.losses), N.tptr(g_lp), N.tptr(g_v), N.torch_stream_ptr()))
+        return (v, lp), (g_v, g_lp)
+
+    def minibatch(self, e, mb, rows, buffers, outputs):
+        N.check(e.lib.srlx_ppo_cat_minibatch(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, *_loss_args(e.cfg), *outputs))
+
+
+def head_of(cfg: PPODeviceConfig):  # the head (and with it the built-in environment) a configuration selects
+    return CategoricalCartPoleHead if cfg.n_actions > 0 else NormalPendulumHead
 
 
 def _plugin_linears(model):
@@ -188,25 +280,17 @@ class PPOEngine:
         self.cfg, self.lib = cfg, N.lib()
         self.dev = torch.device(f"cuda:{device}")
         torch.manual_seed(cfg.seed)
-        self.cat = cfg.n_actions > 0
-        if self.cat and cfg.obs_dim != 4:
-            raise ValueError("PPODeviceConfig(n_actions > 0) runs CartPole: obs_dim must be 4")
-        if self.cat and cfg.n_actions < 2:
-            raise ValueError("a categorical policy needs at least 2 actions")
+        self.head = head = head_of(cfg)(cfg, self.lib)  # everything below that depends on the policy head goes through it
+        self.cat = head.cat
         self.net = ActorCritic(cfg).to(self.dev)
-        # the libsrlx network's entry points for this head (same trunk, same update kernels), and its head size
-        self._head = cfg.n_actions if self.cat else cfg.action_dim
-        self._net_fn = lambda name: getattr(self.lib, ("srlx_ppo_cat_" if self.cat else "srlx_ppo_net_") + name)  # noqa: E731
-        can_fuse = (tuple(cfg.hidden_sizes) == (64, 64) and tuple(cfg.value_sizes) == (64,) and tuple(cfg.policy_sizes) == (64,) and 1 <= cfg.obs_dim <= 8
-                    and (2 <= cfg.n_actions <= 8 if self.cat else 1 <= cfg.action_dim <= 4))
+        can_fuse = tuple(cfg.hidden_sizes) == (64, 64) and tuple(cfg.value_sizes) == (64,) and tuple(cfg.policy_sizes) == (64,) and 1 <= cfg.obs_dim <= 8 and head.size in head.fused_sizes
         if fused and not can_fuse:
-            raise ValueError("PPOEngine(fused=True): the libsrlx network covers hidden (64, 64), value (64,), policy (64,), obs_dim <= 8, action_dim <= 4 "
-                             "(categorical: 2 <= n_actions <= 8)")
+            raise ValueError("PPOEngine(fused=True): the libsrlx network covers hidden (64, 64), value (64,), policy (64,), obs_dim <= 8, " + head.envelope)
         self.fused = can_fuse if fused is None else bool(fused)
         self.grad_sync, self.flat_grad_sync = grad_sync, flat_grad_sync
         if self.fused:
             # one flat parameter vector in `parameters()` order; the module's tensors become views of it (state_dict / export keep working, always current)
-            P = self._net_fn("param_count")(cfg.obs_dim, self._head)
+            P = head.param_count(cfg.obs_dim, head.size)
             ps = list(self.net.parameters())
             assert sum(p.numel() for p in ps) == P
             self.flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
@@ -217,21 +301,17 @@ class PPOEngine:
             self.flat_grad = torch.zeros(P, dtype=torch.float32, device=self.dev)
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
             self.opt_step = torch.zeros(2, dtype=torch.int64, device=self.dev)  # [steps taken, the optimiser launch's arrival counter]
-            self.partials = torch.zeros(self._net_fn("partials_floats")(cfg.obs_dim, self._head), dtype=torch.float32, device=self.dev)
+            self.partials = torch.zeros(head.partials_floats(cfg.obs_dim, head.size), dtype=torch.float32, device=self.dev)
             self.opt = None
         else:
             self.opt = torch.optim.Adam(self.net.parameters(), lr=cfg.lr, capturable=True)
         self.env = make_env(cfg, cfg.seed, self.dev)
         self.ls_range = (math.log(cfg.stable_gradients_scale_range[0]), math.log(cfg.stable_gradients_scale_range[1]))
-        E, T, A, d = cfg.n_envs, cfg.horizon, cfg.action_dim, self.dev
+        E, T, d = cfg.n_envs, cfg.horizon, self.dev
         f32 = dict(dtype=torch.float32, device=d)
         self.b_obs = torch.zeros((T + 1, E, cfg.obs_dim), **f32)
-        if self.cat:  # one action index and one log-probability per step
-            self.b_act = torch.zeros((T, E), dtype=torch.int32, device=d)
-            self.b_logp = torch.zeros((T, E), **f32)
-        else:
-            self.b_act = torch.zeros((T, E, A), **f32)
-            self.b_logp = torch.zeros((T, E, A), **f32)
+        self.b_act = torch.zeros((T, E) + head.act_shape, dtype=head.act_dtype, device=d)
+        self.b_logp = torch.zeros((T, E) + head.act_shape, **f32)
         self.b_val = torch.zeros((T, E), **f32)
         self.b_rew = torch.zeros((T, E), **f32)
         self.b_done = torch.zeros((T, E), dtype=torch.uint8, device=d)
@@ -258,16 +338,8 @@ class PPOEngine:
 
     # --- rollout ---------------------------------------------------------------------------------------------------
     def act(self, obs: torch.Tensor, action_out: torch.Tensor, logp_out: torch.Tensor, deterministic: bool = False):
-        if self.cat:
-            v, logits = self.forward(obs)
-            self._keep = (logits,)
-            N.check(self.lib.srlx_ppo_categorical_act(logits.shape[0], self.cfg.n_actions, N.tptr(logits), self.cfg.seed ^ 0x61637400, N.tptr(self.act_counter),
-                                                      int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
-            return v
-        v, loc, ls = self.forward(obs)
-        self._keep = (loc, ls)
-        N.check(self.lib.srlx_ppo_normal_act(loc.numel(), N.tptr(loc), N.tptr(ls), self.ls_range[0], self.ls_range[1], self.cfg.seed ^ 0x61637400,
-                                             N.tptr(self.act_counter), int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
+        v, *self._keep = self.forward(obs)  # (the head's outputs stay alive behind the launch)
+        self.head.sample(self, *self._keep, action_out, logp_out, deterministic)
         return v
 
     def forward(self, obs: torch.Tensor):
@@ -276,49 +348,21 @@ class PPOEngine:
         if not self.fused:
             with torch.no_grad():
                 return self.net(obs)
-        if self.cat:
-            n = obs.shape[0]
-            v, logits = torch.empty(n, dtype=torch.float32, device=self.dev), torch.empty((n, self.cfg.n_actions), dtype=torch.float32, device=self.dev)
-            N.check(self.lib.srlx_ppo_cat_forward(n, self.cfg.obs_dim, self.cfg.n_actions, N.tptr(self.flat), N.tptr(obs.contiguous()), N.tptr(v), N.tptr(logits),
-                                                  N.torch_stream_ptr()))
-            return v, logits
-        n, A = obs.shape[0], self.cfg.action_dim
-        v, loc, ls = (torch.empty(n, dtype=torch.float32, device=self.dev), torch.empty((n, A), dtype=torch.float32, device=self.dev),
-                      torch.empty((n, A), dtype=torch.float32, device=self.dev))
-        N.check(self.lib.srlx_ppo_net_forward(n, self.cfg.obs_dim, A, N.tptr(self.flat), N.tptr(obs.contiguous()), N.tptr(v), N.tptr(loc), N.tptr(ls), N.torch_stream_ptr()))
-        return v, loc, ls
+        return self.head.forward(self, obs)
 
     def _fused_rollout_ok(self) -> bool:
-        if self.cat:
-            return (self.fused and isinstance(self.env, CartPoleAutoVecEnv) and self.cfg.n_envs % 16 == 0
-                    and self.cfg.horizon <= self.lib.srlx_ppo_cat_rollout_max_horizon(self.cfg.n_actions))
-        return (self.fused and isinstance(self.env, PendulumVecEnv) and self.cfg.obs_dim == 3 and self.cfg.n_envs % 16 == 0
-                and self.cfg.horizon <= self.lib.srlx_ppo_net_rollout_max_horizon(self.cfg.action_dim))  # (longer horizons: the step-wise kernels)
+        cfg, head = self.cfg, self.head  # the head's built-in environment, 16 environments per workgroup, a horizon that fits its LDS (longer: the step-wise kernels)
+        return (self.fused and isinstance(self.env, head.env_cls) and cfg.obs_dim == head.env_obs_dim and cfg.n_envs % 16 == 0
+                and cfg.horizon <= head.rollout_max_horizon(head.size))
 
     def rollout(self):
         cfg = self.cfg
-        if self.cat and self._fused_rollout_ok():  # (csrc/srlx_ppo_net.hip: k_ppo_cat_rollout)
-            env = self.env
-            N.check(self.lib.srlx_ppo_cat_rollout(cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(self.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes),
-                                                  N.tptr(env.obs), env.episode_len, env.seed, cfg.seed ^ 0x61637400, N.tptr(self.act_counter), cfg.discount, cfg.gae_discount,
-                                                  N.tptr(self.b_obs), N.tptr(self.b_act), N.tptr(self.b_logp), N.tptr(self.b_val), N.tptr(self.b_rew), N.tptr(self.b_done),
-                                                  N.tptr(self.b_adv), N.tptr(self._last_v), N.tptr(self.episode_return), N.tptr(self.finished_returns),
-                                                  N.torch_stream_ptr()))
-            return
-        if self._fused_rollout_ok():  # T steps of everything in ONE launch (csrc/srlx_ppo_net.hip: k_ppo_rollout)
-            env = self.env
-            N.check(self.lib.srlx_ppo_net_rollout(cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(self.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len,
-                                                  env.seed, N.tptr(env.counter), cfg.seed ^ 0x61637400, N.tptr(self.act_counter), self.ls_range[0], self.ls_range[1],
-                                                  cfg.discount, cfg.gae_discount, N.tptr(self.b_obs), N.tptr(self.b_act), N.tptr(self.b_logp), N.tptr(self.b_val),
-                                                  N.tptr(self.b_rew), N.tptr(self.b_done), N.tptr(self.b_adv), N.tptr(self._last_v), N.tptr(self.episode_return),
-                                                  N.tptr(self.finished_returns), N.torch_stream_ptr()))
-            return
+        if self._fused_rollout_ok():
+            return self.head.rollout(self)
         for t in range(cfg.horizon):
             self.b_val[t].copy_(self.act(self.b_obs[t], self.b_act[t], self.b_logp[t]))
-            if self.cat:
-                self.env.step(self.b_act[t], self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
-            else:
-                self.env.step(self.b_act[t, :, 0].contiguous() if cfg.action_dim > 1 else self.b_act[t].view(-1), self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
+            # the environment takes the first action dimension (a categorical head's only one; a copy only where action_dim > 1)
+            self.env.step(self.b_act[t].reshape(cfg.n_envs, -1)[:, 0].contiguous(), self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
             self.episode_return += self.b_rew[t]
             d = self.b_done[t].bool()
             self.finished_returns[0] += (self.episode_return * d).sum()
@@ -333,26 +377,7 @@ class PPOEngine:
     # --- update ----------------------------------------------------------------------------------------------------
     def loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v):
         """forward + the fused loss kernel; returns (v, loc, log_scale) with their gradient seeds -- categorical: (v, log-probability of the taken action)."""
-        cfg = self.cfg
-        if self.cat:
-            v, logits = self.net(obs)
-            lp = torch.log_softmax(logits, dim=-1).gather(1, action.long().view(-1, 1))  # CategoricalDist.log_prob of the taken action, [B][1]
-            g_lp, g_v = torch.empty_like(lp), torch.empty_like(v)
-            self._keep_loss = (lp.detach().contiguous(), v.detach().contiguous())
-            N.check(self.lib.srlx_ppo_loss_logpi(
-                lp.shape[0], 1, N.tptr(self._keep_loss[0]), N.tptr(old_logp), N.tptr(adv), N.tptr(self._keep_loss[1]), N.tptr(v_target), N.tptr(old_v),
-                int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
-                cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.losses), N.tptr(g_lp), N.tptr(g_v), N.torch_stream_ptr()))
-            return (v, lp), (g_v, g_lp)
-        v, loc, ls = self.net(obs)
-        B, A = loc.shape
-        g_loc, g_ls, g_v = torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(v)
-        N.check(self.lib.srlx_ppo_loss_normal(
-            B, A, N.tptr(loc.detach()), N.tptr(ls.detach()), self.ls_range[0], self.ls_range[1], N.tptr(action), N.tptr(old_logp), N.tptr(adv), N.tptr(v.detach()),
-            N.tptr(v_target), N.tptr(old_v), int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range,
-            int(cfg.enable_value_clip), cfg.value_clip_range, cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.losses), N.tptr(g_loc), N.tptr(g_ls),
-            N.tptr(g_v), N.torch_stream_ptr()))
-        return (v, loc, ls), (g_v, g_loc, g_ls)
+        return self.head.loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v)
 
     def update(self):
         cfg = self.cfg
@@ -392,16 +417,11 @@ class PPOEngine:
         for ep in range(cfg.epochs):
             for k in range(cfg.minibatches):
                 rows = self._perms[ep][k * mb : (k + 1) * mb]
-                loss_cfg = (int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
-                            cfg.value_loss_weight, cfg.entropy_weight, N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st)
-                buffers = (N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(adv), N.tptr(v_target), N.tptr(val))
-                if self.cat:
-                    N.check(self.lib.srlx_ppo_cat_minibatch(mb, N.tptr(rows), cfg.obs_dim, cfg.n_actions, *buffers, *loss_cfg))
-                else:
-                    N.check(self.lib.srlx_ppo_net_minibatch(mb, N.tptr(rows), cfg.obs_dim, cfg.action_dim, *buffers, self.ls_range[0], self.ls_range[1], *loss_cfg))
+                self.head.minibatch(self, mb, rows, (N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(adv), N.tptr(v_target), N.tptr(val)),
+                                    (N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st))
                 scale = self.flat_grad_sync(self.flat_grad) if self.flat_grad_sync is not None else 1.0
-                N.check(self._net_fn("adam")(cfg.obs_dim, self._head, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq),
-                                             N.tptr(self.opt_step), cfg.lr, 0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st))
+                N.check(self.head.adam(cfg.obs_dim, self.head.size, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq),
+                                       N.tptr(self.opt_step), cfg.lr, 0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st))
 
     def capture_graphs(self):
         """Captures the T-step rollout (+ GAE) and the whole update phase into two HIP graphs: an iteration becomes two

@@ -271,7 +271,7 @@ def _give_the_logits_content(torch, *engines):
 
 
 def test_one_launch_rollout_equals_the_stepwise_kernels():
-    """k_ppo_cat_rollout against the launches it fuses (network forward -> srlx_ppo_categorical_act -> srlx_cartpole_autoreset_step per step, then srlx_gae_scan),
+    """k_ppo_rollout<CartPoleCategorical> against the launches it fuses (network forward -> srlx_ppo_categorical_act -> srlx_cartpole_autoreset_step per step, then srlx_gae_scan),
     same seeds: every buffer, both counters (the action stream's, the lanes' episode counts), the environments' state and the episode bookkeeping -- bit for bit;
     every lane ends an episode inside the rollout (episode_len 11 < T).  The policy is not uniform (the logits layer is given content), and the third rollout
     runs on parameters that two updates have moved."""

@@ -129,7 +129,7 @@ def _engines(torch, E, T, seed, **kw):
 
 
 def test_one_launch_rollout_equals_the_stepwise_kernels():
-    """k_ppo_rollout against the launches it fuses (network forward -> srlx_ppo_normal_act -> srlx_pendulum_step per step, then srlx_gae_scan), same seeds: every
+    """k_ppo_rollout<PendulumNormal> against the launches it fuses (network forward -> srlx_ppo_normal_act -> srlx_pendulum_step per step, then srlx_gae_scan), same seeds: every
     buffer, the environments' state and the episode bookkeeping -- bit for bit (one definition of the arithmetic, srlx_ppo_math.h); episodes end inside the
     rollout (episode_len 11 < T)."""
     N, lib, torch, dev = _env()

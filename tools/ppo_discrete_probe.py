@@ -5,6 +5,7 @@ of the torch-autograd path (`fused=False`), of the continuous Pendulum engine ne
     python tools/ppo_discrete_probe.py --out profiles/ppo_discrete_probe.json
     rocprofv3 --kernel-trace --stats -d DIR -o p --output-format csv -- python tools/ppo_discrete_probe.py --kernels-only    # a run of its own: the tracer slows the loop
     python tools/ppo_discrete_probe.py --merge-kernel-stats DIR --out profiles/ppo_discrete_probe.json                       # kernel times into the same file
+    python tools/ppo_discrete_probe.py --graphs-only [--tree TREE]     # the CartPole engine, fused with graphs, alone: one JSON line (ppo_discrete_check.py bench-ab)
 """
 import argparse
 import csv
@@ -14,9 +15,14 @@ import os
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
-KERNELS = ("k_ppo_cat_rollout", "k_ppo_rollout", "k_ppo_minibatch", "k_ppo_reduce", "k_ppo_adam", "k_categorical_act", "k_cartpole_auto", "k_ppo_forward")
+KERNELS = ("k_ppo_rollout", "k_ppo_minibatch", "k_ppo_reduce", "k_ppo_adam", "k_categorical_act", "k_cartpole_auto", "k_ppo_forward")
+# a kernel's head, from its template argument: the rollout's task (k_ppo_rollout<PendulumNormal> / <CartPoleCategorical>), CAT of the others
+HEADS = (("<categorical>", ("<true>", "CartPoleCategorical")), ("<normal>", ("<false>", "PendulumNormal")))
+# (builds before the rollout became one template had two kernels)
+OLD_NAMES = (("k_ppo_cat_rollout(", "k_ppo_rollout<CartPoleCategorical>("), ("k_ppo_rollout(", "k_ppo_rollout<PendulumNormal>("))
 
 
 def _engine(discrete, fused, E, T=32):
@@ -84,14 +90,23 @@ def _plugin(seconds):
                      "parent commit's")
 
 
-def _merge(directory, out):
+def kernel_stats(directory):
+    """{kernel<head>: calls, average / min / max us} of the PPO kernels in a rocprofv3 --stats output directory (or one *kernel_stats.csv)"""
     rows = {}
-    for f in glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
+    for f in [directory] if os.path.isfile(directory) else glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
+            name = r["Name"]
+            for old, new in OLD_NAMES:
+                name = name.replace(old, new)
             for k in KERNELS:
-                if k + "(" in r["Name"] or k + "<" in r["Name"]:
-                    key = k + ("<categorical>" if "<true>" in r["Name"] else "<normal>" if "<false>" in r["Name"] else "")
+                if k + "(" in name or k + "<" in name:
+                    key = k + next((head for head, marks in HEADS if any(m in name for m in marks)), "")
                     rows[key] = dict(calls=int(r["Calls"]), average_us=float(r["AverageNs"]) / 1e3, min_us=float(r["MinNs"]) / 1e3, max_us=float(r["MaxNs"]) / 1e3)
+    return rows
+
+
+def _merge(directory, out):
+    rows = kernel_stats(directory)
     d = json.load(open(out)) if os.path.exists(out) else {}
     d["kernels_rocprofv3"] = dict(sorted(rows.items()), note="E = 4096, T = 32, rocprofv3 --kernel-trace --stats in a run of its own (eager launches)")
     json.dump(d, open(out, "w"), indent=1)
@@ -106,7 +121,10 @@ def main():
     ap.add_argument("--plugin-seconds", type=float, default=20.0)
     ap.add_argument("--kernels-only", action="store_true", help="a few eager iterations of both heads and of the step-wise kernels, for a profiler")
     ap.add_argument("--merge-kernel-stats", default=None)
+    ap.add_argument("--graphs-only", action="store_true", help="the CartPole engine, fused with graphs: one JSON line, no record")
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose package runs (default: this one)")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.tree))
     if a.merge_kernel_stats:
         return _merge(a.merge_kernel_stats, a.out)
     import torch
@@ -122,6 +140,9 @@ def main():
             eng.step()
         torch.cuda.synchronize()
         return
+    if a.graphs_only:
+        print(json.dumps(_throughput(_engine(True, True, a.envs), True, a.iters)))
+        return
     from simple_distributed_rl_amd import _native as N
 
     res = dict(device=str(N.device_info(0)), envs=a.envs, horizon=32, epochs=4, minibatches=4)
@@ -130,7 +151,7 @@ def main():
     res["cartpole_unfused_eager"] = _throughput(_engine(True, False, a.envs), False, max(4, a.iters // 6))
     res["pendulum_fused_graphs"] = _throughput(_engine(False, True, a.envs), True, a.iters)
     res["rollout_launch_us"] = dict(cartpole=_rollout_us(_engine(True, True, a.envs)), pendulum=_rollout_us(_engine(False, True, a.envs)),
-                                    note="k_ppo_cat_rollout / k_ppo_rollout + the counter kernel behind it, back to back, event-timed")
+                                    note="k_ppo_rollout<CartPoleCategorical> / <PendulumNormal> + the counter kernel behind it, back to back, event-timed")
     if a.plugin_seconds > 0:
         res["plugin_cartpole"] = _plugin(a.plugin_seconds)
     old = json.load(open(a.out)) if os.path.exists(a.out) else {}
