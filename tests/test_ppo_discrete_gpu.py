@@ -4,7 +4,6 @@ autograd in float64, the one-launch rollout against the step-wise kernels (bit-e
 graphs, two data-parallel ranks, the hand-over to the PPO plugin, learning.
 float32 work: tolerance 1e-5 relative (to a tensor's largest entry where sums cancel), the bars of tests/test_ppo_net_gpu.py; the reference's PPO needs
 TensorFlow -- parity UNPINNED, as for the whole PPO row."""
-import copy
 import os
 import subprocess
 import sys
@@ -15,6 +14,7 @@ import pytest
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ppo_cat_reference as R  # noqa: E402
+from ppo_net_reference import rows_off_the_kinks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -203,14 +203,7 @@ def test_minibatch_gradients_against_autograd_in_float64(base, clip, vclip, obs,
     b_logp = (torch.log_softmax(lg0, dim=-1).gather(1, b_act.long().view(-1, 1)).squeeze(1) + 0.3 * r(total)).contiguous()
     b_val = (v0 + 0.3 * r(total)).contiguous()
     # rows away from the ReLU kinks (the existing test's filter: a pre-activation within float32 rounding of zero takes the other branch in float64)
-    with torch.no_grad():
-        n64 = copy.deepcopy(net).double()
-        x64 = b_obs.double()
-        z1 = n64.hidden_block[0](x64)
-        z2 = n64.hidden_block[2](torch.relu(z1))
-        h64 = torch.relu(z2)
-        zmin = torch.stack([z.abs().min(dim=1).values for z in (z1, z2, n64.value_block[0](h64), n64.policy_block[0](h64))]).min(dim=0).values
-    cand = torch.nonzero(zmin > 1e-5).reshape(-1)
+    cand = rows_off_the_kinks(torch, net, b_obs)
     assert cand.numel() > 2 * mb
     rows = cand[torch.randperm(cand.numel(), device=dev, generator=g)[:mb]].contiguous()
     pc, vc, vw, ew = 0.2, 0.2, 0.7, 0.01

@@ -11,6 +11,7 @@ import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ppo_net_reference import rows_off_the_kinks  # noqa: E402
 from test_ppo_gpu import LS_RANGE, _torch_loss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -70,18 +71,9 @@ def test_minibatch_gradients_against_autograd_in_float64(base, clip, vclip, obs,
     ls_c = torch.clamp(ls0, LS_RANGE[0], LS_RANGE[1])
     b_logp = (-0.5 * math.log(2 * math.pi) - ls_c - 0.5 * ((b_act - loc0) / torch.exp(ls_c)) ** 2 + 0.3 * r(n, A)).contiguous()
     b_val = (v0 + 0.3 * r(n)).contiguous()
-    # rows away from the ReLU kinks: a pre-activation within float32 rounding of zero takes the other branch in float64 (measured: 1e-8 among 8192 x 256
-    # pre-activations, which moved the value block's gradient by 5e-4 of its largest entry) -- a property of the yardstick's precision, not of the kernel
-    import copy
-
-    with torch.no_grad():
-        n64 = copy.deepcopy(net).double()
-        x64 = b_obs.double()
-        z1 = n64.hidden_block[0](x64)
-        z2 = n64.hidden_block[2](torch.relu(z1))
-        h64 = torch.relu(z2)
-        zmin = torch.stack([z.abs().min(dim=1).values for z in (z1, z2, n64.value_block[0](h64), n64.policy_block[0](h64))]).min(dim=0).values
-    cand = torch.nonzero(zmin > 1e-5).reshape(-1)
+    # rows away from the ReLU kinks: a pre-activation within float32 rounding of zero takes the other branch in float64 -- a property of the yardstick's
+    # precision, not of the kernel (tests/ppo_net_reference.py)
+    cand = rows_off_the_kinks(torch, net, b_obs)
     assert cand.numel() > 2 * mb
     rows = cand[torch.randperm(cand.numel(), device=dev, generator=g)[:mb]].contiguous()
     pc, vc, vw, ew = 0.2, 0.2, 0.7, 0.01
