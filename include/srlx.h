@@ -902,6 +902,22 @@ int srlx_qnet_noisy_effective(srlx_qnet_t *h, int which, float *d_out, int64_t *
  *                            scalar, not advanced here).  Outputs: d_q0 [B][A] (online Q of s_0 before the step), d_target, d_priorities [B], d_loss [1].
  *                            Gradient sums run in item order: two runs on the same inputs are bit-identical.
  *   srlx_mlpq_publish      : every parameter of `src` into `dst` (online -> target, online -> an actor copy), one launch
+ * Rainbow's network on the same kernels (srl/algorithms/rainbow/model_torch.py:15-29: in_block -> MLP over layer_sizes[:-1] -> DuelingNetworkBlock):
+ *   srlx_mlpq_create_dueling : n_trunk = 0..2 Linear + ReLU layers of trunk_widths[l] = 32..512 units (multiples of 32; the input value block's layers, then the
+ *                            hidden block's layer_sizes[:-1]; 0: the head reads the observation row), then the dueling head (srl/rl/torch_/blocks/
+ *                            dueling_network.py:8-59) with dueling_units H = 32..512 (multiples of 32) in each branch, dueling_type 0 "average" / 1 "",
+ *                            n_actions 2..32, max_batch <= 256, max_nstep = 1..7 (the longest item of srlx_mlpq_train_nstep).  Anything else: an error before
+ *                            any device call.  srlx_mlpq_bind / _bind_grads / _bind_adam take 2 * n_trunk + 8 tensors on such a handle, in the reference's
+ *                            state_dict order: the trunk layers (weight, bias), v_layers.0 ([H][in], [H]), v_layers.2 ([1][H], [1]), adv_layers.0,
+ *                            adv_layers.2 ([A][H], [A]).  srlx_mlpq_forward and srlx_mlpq_publish serve both kinds of handle.  In LDS the two branches' hidden
+ *                            rows share one buffer (the value row is reduced to its scalar first): the row stride stays max width + 1.
+ *   srlx_mlpq_train_nstep  : one Rainbow update (rainbow.py:185-287, model_torch.py:85-122) in two launches, on a dueling or a plain handle: 16 / (n + 1) items
+ *                            per workgroup, online forward over s_0..s_n, target forward over s_1..s_n, the n-step retrace target of srlx_td_math.h:td_rows
+ *                            (numpy's float32 order, float32(discount ** m) from the host; with `rescale` both value transforms in float64), IS-weighted
+ *                            Huber loss, priorities, backward through the head (d adv_k = g ((k == a_0) - 1/A), "": g (k == a_0); d v = g) and the trunk, Adam.
+ *                            d_offsets int64 [B][n + 1] (the store's frame_off_all at window 1), actions / rewards / terminated [B][n].  No invalid-action
+ *                            mask.  Outputs as srlx_mlpq_train_step; bit-reproducible.  On a plain handle at n = 1, retrace_h = 1 every output, gradient and
+ *                            post-Adam parameter is bit-equal to srlx_mlpq_train_step's.
  * Batch CartPole (envs/cartpole.py:step; srlx_mlpq.hip): float64 state [E][4], steps / episodes int32 [E].  A lane whose d_needs_reset entry is set (the store's
  * needs_reset view, srlx_store_views) starts its next episode instead of stepping: state uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane), its
  * first observation in d_obs, reward / terminated / done 0.  d_needs_reset NULL: every lane starts an episode (actions and scalar outputs may be NULL).
@@ -918,6 +934,11 @@ int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batc
                          const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
                          const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream);
 int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream);
+int srlx_mlpq_create_dueling(srlx_mlpq_t **out, int obs_dim, int n_trunk, const int *trunk_widths, int dueling_units, int dueling_type, int n_actions,
+                             int64_t max_rows, int64_t max_batch, int max_nstep, int device);
+int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batch, int n, const float *d_obs_base, const int64_t *d_offsets,
+                          const int32_t *d_actions, const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, double retrace_h,
+                          int double_dqn, int rescale, const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream);
 int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
                        int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 

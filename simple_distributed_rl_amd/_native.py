@@ -215,6 +215,8 @@ SIGNATURES = {
     "srlx_mlpq_forward": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_u64, c_p, c_p, c_p]),
     "srlx_mlpq_train_step": (c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_mlpq_publish": (c_int, [c_p, c_p, c_p]),
+    "srlx_mlpq_create_dueling": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_p, c_int, c_int, c_int, c_i64, c_i64, c_int, c_int]),
+    "srlx_mlpq_train_nstep": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_cartpole_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1

@@ -8,6 +8,9 @@
 //   k_mlpq_learn_rows 8 sampled items per workgroup: online pass over s_0 and s_1, target pass over s_1, the 1-step (double) DQN target / Huber / priority of
 //                     srlx_td_math.h:td_rows, then the backward chain d loss / d h_l of every layer for these rows (the chain is row-local).  Writes the
 //                     s_0 activations and the d h_l rows.
+//   k_mlpq_learn_nstep<n>  Rainbow's update (rainbow/model_torch.py:15-29, rainbow.py:185-287) on the same layers: 16 / (n + 1) items per workgroup, online pass
+//                     over s_0..s_n, target pass over s_1..s_n, the n-step retrace target, then the backward chain -- through out_layer, or through the
+//                     dueling head (forward_rows: MLP trunk of 0..2 layers, then v_layers / adv_layers; srl/rl/torch_/blocks/dueling_network.py:8-59).
 //   k_mlpq_grad_adam  one thread per parameter: the gradient as a sum over the batch in item order (no atomics: bit-reproducible), then torch's Adam
 //                     (srlx_adam_math.h) in the same thread; block 0 reduces the loss.
 #include "srlx_adam_math.h"
@@ -16,17 +19,19 @@
 #include "srlx_td_math.h"
 
 struct srlx_mlpq {
-    int D, L, A, device;
+    int D, L, A, device;  // L: the Linear + ReLU layers in front of the head (plain: 1..3, then out_layer; dueling: the trunk, 0..2)
     int W[3];
+    int H, head;  // dueling: units of each branch; head 0 = out_layer, 1 = dueling "average", 2 = dueling ""
+    int max_nstep;
     int64_t max_rows, max_batch;
-    float *p[8];  // layer 0 weight, bias, ..., out_layer weight, bias
+    float *p[12];  // layer 0 weight, bias, ..., then out_layer weight, bias -- or v_layers.0, v_layers.2, adv_layers.0, adv_layers.2 (weight, bias each)
     bool bound;
-    float *grads[8];
-    float *m[8], *v[8];
+    float *grads[12];
+    float *m[12], *v[12];
     double lr, beta1, beta2, eps;
     bool adam;
     // learner scratch (max_batch > 0)
-    float *x0, *h, *dh, *q_on_next, *q_tg_next, *grad_q;
+    float *x0, *h, *dh, *q_on_next, *q_tg_next, *grad_q, *grad_v;
     double *loss_rows;
     int wmax;
     void *d_net;  // the descriptor of the bound parameters in device memory (the learner step's launch reads it)
@@ -41,13 +46,18 @@ using u8 = unsigned char;
 constexpr int kThreads = 256;
 constexpr int kRows = 16;      // rows of one acting workgroup, and of the learner's online pass (s_0 and s_1 of kItems items)
 constexpr int kItems = kRows / 2;
-constexpr int kMaxParams = 8;
+constexpr int kMaxParams = 12;  // two trunk layers and the dueling head's four
+constexpr int kMaxNstep = 7;    // kRows / (n + 1) >= 2 items per workgroup
 
 struct Net {  // (scalar fields and selects, no arrays: a kernel-argument array indexed by a run-time layer number is copied to scratch memory)
     int D, L, A;
     int W0, W1, W2;
     const float *w0, *w1, *w2, *w3, *b0, *b1, *b2, *b3;
     const float *wout;  // out_layer's weight (= the weight of layer L)
+    // the dueling head (head != 0; srl/rl/torch_/blocks/dueling_network.py:8-59) behind the L trunk layers: v_layers.0 [H][in], v_layers.2 [1][H],
+    // adv_layers.0 [H][in], adv_layers.2 [A][H]; head 1 = "average", 2 = ""
+    int H, head;
+    const float *vw0, *vb0, *vw1, *vb1, *aw0, *ab0, *aw1, *ab1;
     __device__ int width(int l) const { return l == 0 ? W0 : (l == 1 ? W1 : W2); }
     __device__ int in_of(int l) const { return l == 0 ? D : width(l - 1); }
     __device__ int out_of(int l) const { return l < L ? width(l) : A; }
@@ -60,11 +70,18 @@ Net net_of(const srlx_mlpq *h) {
     n.D = h->D, n.L = h->L, n.A = h->A;
     n.W0 = h->W[0], n.W1 = h->L > 1 ? h->W[1] : 0, n.W2 = h->L > 2 ? h->W[2] : 0;
     const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int l = 0; l <= h->L; l++) w[l] = h->p[2 * l], b[l] = h->p[2 * l + 1];
+    const int plain_layers = h->head ? h->L : h->L + 1;
+    for (int l = 0; l < plain_layers; l++) w[l] = h->p[2 * l], b[l] = h->p[2 * l + 1];
     n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
-    n.wout = w[h->L];
+    n.wout = h->head ? nullptr : w[h->L];
+    n.H = h->H, n.head = h->head;
+    float *const *q = h->p + 2 * h->L;
+    n.vw0 = n.vb0 = n.vw1 = n.vb1 = n.aw0 = n.ab0 = n.aw1 = n.ab1 = nullptr;
+    if (h->head) n.vw0 = q[0], n.vb0 = q[1], n.vw1 = q[2], n.vb1 = q[3], n.aw0 = q[4], n.ab0 = q[5], n.aw1 = q[6], n.ab1 = q[7];
     return n;
 }
+
+int n_params(const srlx_mlpq *h) { return h->head ? 2 * h->L + 8 : 2 * (h->L + 1); }
 
 int lds_stride(const srlx_mlpq *h) { return h->wmax + 1; }  // (odd: rows of different row groups fall on different banks)
 
@@ -111,12 +128,28 @@ __device__ __forceinline__ void dense(const float *__restrict__ Wt, const float 
     }
 }
 
+// The head's second layers (v_layers.2: 1 output, adv_layers.2: A <= 32 outputs, H inputs each): y[r][u] = sum_k W[u][k] x[r][k] + b[u] with 16 lanes per
+// row (kThreads = 16 * kRows) -- every lane a strided partial sum, then a butterfly over the 16.  dense() would leave all but `rows` threads idle on a chain
+// of H dependent multiply-adds per output.  The weight is read from memory as it is ([out][in] rows, 16 consecutive floats per row group).  No barrier inside.
+__device__ __forceinline__ void narrow_rows(const float *__restrict__ Wt, const float *__restrict__ bias, int In, int Out, int rows, const float *x, int sx, float *y,
+                                            int sy) {
+    const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
+    for (int u = 0; u < Out; u++) {
+        float acc = 0.f;
+        if (r < rows)
+            for (int k = j; k < In; k += 16) acc = __builtin_fmaf(Wt[u * In + k], x[r * sx + k], acc);
+        for (int d = 8; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 16);
+        if (j == 0 && r < rows) y[r * sy + u] = acc + bias[u];
+    }
+}
+
 // the whole network over the rows in buf[0] (inputs, D columns); returns the buffer that holds the Q rows.  `keep` (global, per layer l < L: [rows_kept][W_l],
 // NULL: not kept) receives rows 0..kept-1 of every hidden layer's output.
 __device__ __forceinline__ float *forward_rows(const Net &n, int rows, float *buf0, float *buf1, int S, float *wl, float *keep, i64 keep_plane, i64 keep_row0,
                                                int kept) {
     float *cur = buf0, *nxt = buf1;
-    for (int l = 0; l <= n.L; l++) {
+    const int plain_layers = n.head ? n.L : n.L + 1;
+    for (int l = 0; l < plain_layers; l++) {
         const int In = n.in_of(l), Out = n.out_of(l);
         dense(n.weight(l), n.bias(l), In, Out, rows, cur, S, nxt, S, l < n.L, wl);
         __syncthreads();
@@ -125,6 +158,35 @@ __device__ __forceinline__ float *forward_rows(const Net &n, int rows, float *bu
         float *tmp = cur;
         cur = nxt, nxt = tmp;
     }
+    if (!n.head) return cur;
+    // the dueling head on the trunk's output rows in `cur` (the observation rows when there is no trunk).  Both branches' hidden rows go through `nxt`, one after
+    // the other: the value branch's row is reduced to its scalar before the advantage branch overwrites it, so the row stride stays max width + 1.  Kept planes:
+    // L = the value branch's hidden rows, L + 1 = the advantage branch's.
+    __shared__ float vrow[kRows], mrow[kRows];
+    const int t = threadIdx.x, In = n.in_of(n.L), H = n.H, A = n.A;
+    dense(n.vw0, n.vb0, In, H, rows, cur, S, nxt, S, true, wl);
+    __syncthreads();
+    if (keep)
+        for (int p = t; p < kept * H; p += kThreads) keep[n.L * keep_plane + (keep_row0 + p / H) * H + p % H] = nxt[(p / H) * S + p % H];
+    narrow_rows(n.vw1, n.vb1, H, 1, rows, nxt, S, vrow, 1);
+    dense(n.aw0, n.ab0, In, H, rows, cur, S, nxt, S, true, wl);  // (its first barrier is behind every read of the value rows above)
+    __syncthreads();
+    if (keep)
+        for (int p = t; p < kept * H; p += kThreads) keep[(n.L + 1) * keep_plane + (keep_row0 + p / H) * H + p % H] = nxt[(p / H) * S + p % H];
+    narrow_rows(n.aw1, n.ab1, H, A, rows, nxt, S, cur, S);  // (the barrier above is behind every read of the trunk rows in `cur`)
+    __syncthreads();
+    if (t < rows) {  // torch.mean(adv, dim=-1)
+        float s = 0.f;
+        for (int a = 0; a < A; a++) s += cur[t * S + a];
+        mrow[t] = n.head == 1 ? s / (float)A : 0.f;
+    }
+    __syncthreads();
+    for (int p = t; p < rows * A; p += kThreads) {  // v + adv - mean (dueling_network.py:51); "": v + adv
+        const int r = p / A, a = p % A;
+        const float q = vrow[r] + cur[r * S + a];
+        cur[r * S + a] = n.head == 1 ? q - mrow[r] : q;
+    }
+    __syncthreads();
     return cur;
 }
 
@@ -298,6 +360,205 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restr
     }
 }
 
+
+// ---- the n-step learner step (Rainbow on flat observations) -------------------------------------------------------------------------------------------------
+struct LearnN {
+    i64 B;
+    const float *obs;
+    const i64 *off;  // [B][n + 1]: element offsets of s_0..s_n (the store's frame_off_all at window 1)
+    const int32_t *actions;              // [B][n]
+    const float *rewards, *terminated;   // [B][n]
+    const float *weights;                // [B]
+    float *x0, *h, *dh, *q0, *grad_q, *grad_v;
+    double *loss_rows;
+    int hstride;
+    float *target, *priorities;
+    double discount, retrace_h;
+    int double_dqn, rescale;
+    float dm[kMaxNstep];  // float32(discount ** m), filled on the host (srlx_td_math.h: multi_discounts)
+};
+
+// srlx_td_math.h:td_rows for one item with the step count a compile-time bound (its per-step values stay in registers): rainbow.py:226-287 and
+// model_torch.py:103-113 in numpy's float32 order.  qon: the online Q rows of s_1.. (step stride qstep floats), qtg: the target's.  With `rescale` the two value
+// transforms run in float64, like td_one.  Returns the Huber term; gsel = d loss / d q[a_0].
+template <int NS>
+__device__ __forceinline__ double td_item(const LearnN &a, i64 b, int A, const float *qon, const float *qtg, int qstep, const float *q0row, float &gsel, int &a0_out) {
+    double c = 1.0;
+    float target = 0.f;
+#pragma unroll
+    for (int m = 0; m < NS; m++) {
+        const float *qo = qon + m * qstep, *qt = qtg + m * qstep;
+        const int na = srlx::argmax_masked(a.double_dqn ? qo : qt, nullptr, A);  // :245-253
+        const float maxq = qt[na];
+        const float r = a.rewards[b * NS + m], term = a.terminated[b * NS + m];
+        float gain;
+        if (a.rescale)
+            gain = (float)rescaling64((double)r + ((1.0 - (double)term) * a.discount) * inverse_rescaling64((double)maxq));
+        else
+            gain = r + ((1.0f - term) * (float)a.discount) * maxq;  // :258
+        const int am = a.actions[b * NS + m];
+        const float qsel = m == 0 ? 0.f : (qon + (m - 1) * qstep)[am];  // :231-233
+        const float td = gain - qsel;
+        if (m > 0) c *= a.retrace_h * (am == na ? 1.0 : 0.0);  // :267-280
+        target = target + (float)((double)(td * a.dm[m]) * c);  // :285
+    }
+    a.target[b] = target;
+    const int a0 = a.actions[b * NS];
+    const float q0 = q0row[a0];
+    const float w = a.weights[b];
+    const float tw = target * w, qw = q0 * w;
+    const float diff = tw - qw;
+    const float z = fabsf(diff);
+    const double huber = (z < 1.0f) ? 0.5 * (double)z * (double)z : (double)z - 0.5;
+    const float dclamp = diff > 1.0f ? 1.0f : (diff < -1.0f ? -1.0f : diff);
+    gsel = -(w * dclamp) / (float)a.B;
+    a0_out = a0;
+    a.priorities[b] = fabsf(target - q0);
+    return huber;
+}
+
+// kRows / (NS + 1) items per workgroup, rows step-major (row s * P + item): the online pass over s_0..s_n, the target pass over s_1..s_n, td_item, then the
+// row-local backward chain -- through out_layer as in k_mlpq_learn_rows, or through the dueling head's two branches into the trunk.  At NS = 1 on a plain net the
+// row layout, every sum and every store are k_mlpq_learn_rows's.
+template <int NS>
+__global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep(const Net *__restrict__ onp, const Net *__restrict__ tgp, LearnN a, int S) {
+    constexpr int P = kRows / (NS + 1), R = P * (NS + 1);
+    const Net &on = *onp, &tg = *tgp;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *d0 = sm + 2 * kRows * S, *d1 = d0 + kItems * S, *wl = d1 + kItems * S;
+    __shared__ float qon_s[kRows * 32], qtg_s[kRows * 32];  // Q rows of s_1..s_n: row (s - 1) * P + item, A floats each
+    __shared__ float gsel[kItems];
+    __shared__ int act0[kItems];
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * P;
+    const int nb = (int)(a.B - i0 < P ? a.B - i0 : P);
+    const int D = on.D, A = on.A, L = on.L;
+    for (int p = t; p < R * D; p += kThreads) {  // (missing items: zero rows, never stored)
+        const int r = p / D, k = p % D, it = r % P, st = r / P;
+        const float x = it < nb ? a.obs[a.off[(i0 + it) * (NS + 1) + st] + k] : 0.f;
+        b0[r * S + k] = x;
+        if (st == 0 && it < nb) a.x0[(i0 + it) * D + k] = x;
+    }
+    __syncthreads();
+    const float *qs = forward_rows(on, R, b0, b1, S, wl, a.h, a.hstride, i0, nb);
+    for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
+    for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qs[(P + p / A) * S + p % A];
+    __syncthreads();
+    for (int p = t; p < NS * P * D; p += kThreads) {
+        const int r = p / D, k = p % D, it = r % P, st = r / P + 1;
+        b0[r * S + k] = it < nb ? a.obs[a.off[(i0 + it) * (NS + 1) + st] + k] : 0.f;
+    }
+    __syncthreads();
+    const float *qt = forward_rows(tg, NS * P, b0, b1, S, wl, nullptr, 0, 0, 0);
+    for (int p = t; p < NS * P * A; p += kThreads) qtg_s[p] = qt[(p / A) * S + p % A];
+    __threadfence_block();  // (q0 rows are read back from memory below)
+    __syncthreads();
+    if (t < nb) {
+        const i64 b = i0 + t;
+        float g;
+        int a0;
+        a.loss_rows[b] = td_item<NS>(a, b, A, qon_s + t * A, qtg_s + t * A, P * A, a.q0 + b * A, g, a0);
+        gsel[t] = g, act0[t] = a0;
+        if (!on.head)
+            for (int k = 0; k < A; k++) a.grad_q[b * A + k] = k == a0 ? g : 0.f;
+    }
+    __syncthreads();
+    if (!on.head) {
+        // backward chain, row by row: d h_{L-1} from the Q seed (one non-zero column per row), then through every hidden layer's weight (k_mlpq_learn_rows)
+        float *dcur = d0, *dnext = d1;
+        for (int l = L - 1; l >= 0; l--) {
+            const int Wl = on.width(l);
+            const float *hl = a.h + (i64)l * a.hstride;
+            float *dhl = a.dh + (i64)l * a.hstride;
+            for (int p = t; p < nb * Wl; p += kThreads) {
+                const int r = p / Wl, k = p % Wl;
+                float g;
+                if (l == L - 1) {
+                    g = gsel[r] * on.wout[act0[r] * Wl + k];
+                } else {
+                    const int Wn = on.width(l + 1);
+                    const float *wn = on.weight(l + 1);
+                    g = 0.f;
+#pragma unroll 8
+                    for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
+                }
+                g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
+                dcur[r * S + k] = g;
+                dhl[(i0 + r) * Wl + k] = g;
+            }
+            __syncthreads();
+            float *tmp = dcur;
+            dcur = dnext, dnext = tmp;
+        }
+        return;
+    }
+    // the dueling head: d adv_k = g ((k == a_0) - 1/A) ("": g (k == a_0)), d v = g; through adv_layers.2 / v_layers.2 into the two hidden rows (d0: value branch,
+    // d1: advantage branch), then through both first layers into the trunk's last output, and down the trunk
+    const int H = on.H;
+    const float sub = on.head == 1 ? 1.0f / (float)A : 0.f;
+    for (int p = t; p < nb * A; p += kThreads) {
+        const int r = p / A, k = p % A;
+        a.grad_q[(i0 + r) * A + k] = gsel[r] * ((k == act0[r] ? 1.0f : 0.f) - sub);
+    }
+    if (t < nb) a.grad_v[i0 + t] = gsel[t];
+    {
+        const float *hv = a.h + (i64)L * a.hstride, *ha = a.h + (i64)(L + 1) * a.hstride;
+        float *dhv = a.dh + (i64)L * a.hstride, *dha = a.dh + (i64)(L + 1) * a.hstride;
+        for (int p = t; p < nb * H; p += kThreads) {
+            const int r = p / H, k = p % H;
+            const float g = gsel[r];
+            const int a0 = act0[r];
+            float gv = g * on.vw1[k];
+            gv = hv[(i0 + r) * H + k] > 0.f ? gv : 0.f;
+            float ga = 0.f;
+            for (int c = 0; c < A; c++) ga = __builtin_fmaf(g * ((c == a0 ? 1.0f : 0.f) - sub), on.aw1[c * H + k], ga);
+            ga = ha[(i0 + r) * H + k] > 0.f ? ga : 0.f;
+            d0[r * S + k] = gv, dhv[(i0 + r) * H + k] = gv;
+            d1[r * S + k] = ga, dha[(i0 + r) * H + k] = ga;
+        }
+    }
+    __syncthreads();
+    if (L > 0) {
+        const int Wl = on.width(L - 1);
+        const float *hl = a.h + (i64)(L - 1) * a.hstride;
+        float *dhl = a.dh + (i64)(L - 1) * a.hstride;
+        for (int p = t; p < nb * Wl; p += kThreads) {
+            const int r = p / Wl, k = p % Wl;
+            float g = 0.f;
+#pragma unroll 8
+            for (int u = 0; u < H; u++) g = __builtin_fmaf(d0[r * S + u], on.vw0[(i64)u * Wl + k], g);
+#pragma unroll 8
+            for (int u = 0; u < H; u++) g = __builtin_fmaf(d1[r * S + u], on.aw0[(i64)u * Wl + k], g);
+            g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
+            b0[r * S + k] = g;
+            dhl[(i0 + r) * Wl + k] = g;
+        }
+        __syncthreads();
+    }
+    if (L > 1) {
+        const int W0 = on.W0, W1 = on.W1;
+        for (int p = t; p < nb * W0; p += kThreads) {
+            const int r = p / W0, k = p % W0;
+            float g = 0.f;
+#pragma unroll 8
+            for (int u = 0; u < W1; u++) g = __builtin_fmaf(b0[r * S + u], on.w1[(i64)u * W0 + k], g);
+            a.dh[(i0 + r) * W0 + k] = a.h[(i0 + r) * W0 + k] > 0.f ? g : 0.f;
+        }
+    }
+}
+
+const void *learn_nstep_fn(int n) {
+    switch (n) {
+    case 1: return (const void *)k_mlpq_learn_nstep<1>;
+    case 2: return (const void *)k_mlpq_learn_nstep<2>;
+    case 3: return (const void *)k_mlpq_learn_nstep<3>;
+    case 4: return (const void *)k_mlpq_learn_nstep<4>;
+    case 5: return (const void *)k_mlpq_learn_nstep<5>;
+    case 6: return (const void *)k_mlpq_learn_nstep<6>;
+    default: return (const void *)k_mlpq_learn_nstep<7>;
+    }
+}
+
 struct GradAdam {
     i64 B;
     int nseg;
@@ -386,12 +647,30 @@ int set_lds(const void *fn, size_t bytes) {
     return SRLX_OK;
 }
 
+// (Out, In) of the handle's n_params / 2 Linear layers in binding order
+int layer_shapes(const srlx_mlpq *h, int *outs, int *ins) {
+    const int last = h->L == 0 ? h->D : h->W[h->L - 1];
+    int n = 0;
+    for (int l = 0; l < h->L; l++) outs[n] = h->W[l], ins[n] = l == 0 ? h->D : h->W[l - 1], n++;
+    if (h->head) {
+        outs[n] = h->H, ins[n] = last, n++;
+        outs[n] = 1, ins[n] = h->H, n++;
+        outs[n] = h->H, ins[n] = last, n++;
+        outs[n] = h->A, ins[n] = h->H, n++;
+    } else {
+        outs[n] = h->A, ins[n] = last, n++;
+    }
+    return n;
+}
+
 GradAdam segments(const srlx_mlpq *h) {
     GradAdam a{};
-    a.nseg = 2 * (h->L + 1);
+    int outs[kMaxParams / 2], ins[kMaxParams / 2];
+    const int layers = layer_shapes(h, outs, ins);
+    a.nseg = 2 * layers;
     i64 run = 0;
-    for (int l = 0; l <= h->L; l++) {
-        const int In = l == 0 ? h->D : h->W[l - 1], Out = l < h->L ? h->W[l] : h->A;
+    for (int l = 0; l < layers; l++) {
+        const int In = ins[l], Out = outs[l];
         run += (i64)Out * In;
         a.seg_end[2 * l] = run, a.seg_out[2 * l] = Out, a.seg_in[2 * l] = In;
         run += Out;
@@ -404,6 +683,9 @@ GradAdam segments(const srlx_mlpq *h) {
 
 extern "C" {
 
+static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int dueling_units, int head, int n_actions, int64_t max_rows,
+                          int64_t max_batch, int max_nstep, int device);
+
 int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int64_t max_rows, int64_t max_batch, int device) {
     SRLX_REQUIRE(out && widths, "mlpq_create: NULL argument");
     *out = nullptr;
@@ -414,21 +696,50 @@ int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *wi
     SRLX_REQUIRE(n_actions >= 2 && n_actions <= 32, "mlpq_create: %d actions (covered: 2..32)", n_actions);
     SRLX_REQUIRE(max_rows >= 1 && max_batch >= 0 && max_batch <= 256, "mlpq_create: max_rows %lld, max_batch %lld (learner batches <= 256)", (long long)max_rows,
                  (long long)max_batch);
+    return create_checked(out, obs_dim, n_layers, widths, 0, 0, n_actions, max_rows, max_batch, kMaxNstep, device);
+}
+
+int srlx_mlpq_create_dueling(srlx_mlpq_t **out, int obs_dim, int n_trunk, const int *trunk_widths, int dueling_units, int dueling_type, int n_actions,
+                             int64_t max_rows, int64_t max_batch, int max_nstep, int device) {
+    SRLX_REQUIRE(out && (trunk_widths || n_trunk == 0), "mlpq_create_dueling: NULL argument");
+    *out = nullptr;
+    SRLX_REQUIRE(obs_dim >= 1 && obs_dim <= 256, "mlpq_create_dueling: %d observation elements (covered: 1..256)", obs_dim);
+    SRLX_REQUIRE(n_trunk >= 0 && n_trunk <= 2, "mlpq_create_dueling: %d trunk layers (covered: 0..2)", n_trunk);
+    for (int l = 0; l < n_trunk; l++)
+        SRLX_REQUIRE(trunk_widths[l] >= 32 && trunk_widths[l] <= 512 && trunk_widths[l] % 32 == 0,
+                     "mlpq_create_dueling: trunk layer width %d (covered: 32..512, multiples of 32)", trunk_widths[l]);
+    SRLX_REQUIRE(dueling_units >= 32 && dueling_units <= 512 && dueling_units % 32 == 0, "mlpq_create_dueling: %d dueling units (covered: 32..512, multiples of 32)",
+                 dueling_units);
+    SRLX_REQUIRE(dueling_type == 0 || dueling_type == 1, "mlpq_create_dueling: dueling type %d (covered: 0 \"average\", 1 \"\")", dueling_type);
+    SRLX_REQUIRE(n_actions >= 2 && n_actions <= 32, "mlpq_create_dueling: %d actions (covered: 2..32)", n_actions);
+    SRLX_REQUIRE(max_rows >= 1 && max_batch >= 0 && max_batch <= 256, "mlpq_create_dueling: max_rows %lld, max_batch %lld (learner batches <= 256)",
+                 (long long)max_rows, (long long)max_batch);
+    SRLX_REQUIRE(max_nstep >= 1 && max_nstep <= kMaxNstep, "mlpq_create_dueling: max_nstep %d (covered: 1..%d)", max_nstep, kMaxNstep);
+    return create_checked(out, obs_dim, n_trunk, trunk_widths, dueling_units, dueling_type + 1, n_actions, max_rows, max_batch, max_nstep, device);
+}
+
+// (the arguments are inside the envelope; no device call has been made yet)
+static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int dueling_units, int head, int n_actions, int64_t max_rows,
+                          int64_t max_batch, int max_nstep, int device) {
     srlx::DeviceGuard g(device);
     SRLX_REQUIRE(g.ok, "mlpq_create: device %d unavailable", device);
     srlx_mlpq *h = new srlx_mlpq();
     h->D = obs_dim, h->L = n_layers, h->A = n_actions, h->device = device;
+    h->H = dueling_units, h->head = head, h->max_nstep = max_nstep;
     h->max_rows = max_rows, h->max_batch = max_batch;
     h->wmax = obs_dim > n_actions ? obs_dim : n_actions;
+    if (dueling_units > h->wmax) h->wmax = dueling_units;
     for (int l = 0; l < n_layers; l++) {
         h->W[l] = widths[l];
         if (widths[l] > h->wmax) h->wmax = widths[l];
     }
     if (max_batch > 0) {
         const size_t plane = (size_t)max_batch * h->wmax;
+        const size_t planes = head ? n_layers + 2 : 3;  // (dueling: the trunk's, then the value and the advantage branch's hidden rows)
         hipError_t e = hipMalloc((void **)&h->x0, sizeof(float) * max_batch * obs_dim);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->h, sizeof(float) * 3 * plane);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->dh, sizeof(float) * 3 * plane);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->h, sizeof(float) * planes * plane);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->dh, sizeof(float) * planes * plane);
+        if (e == hipSuccess && head) e = hipMalloc((void **)&h->grad_v, sizeof(float) * max_batch);
         if (e == hipSuccess) e = hipMalloc((void **)&h->q_on_next, sizeof(float) * max_batch * n_actions);
         if (e == hipSuccess) e = hipMalloc((void **)&h->q_tg_next, sizeof(float) * max_batch * n_actions);
         if (e == hipSuccess) e = hipMalloc((void **)&h->grad_q, sizeof(float) * max_batch * n_actions);
@@ -442,6 +753,7 @@ int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *wi
     const int S = lds_stride(h);
     int st = set_lds((const void *)k_mlpq_actor, sizeof(float) * (2 * kRows * S + kWTile));
     if (st == SRLX_OK) st = set_lds((const void *)k_mlpq_learn_rows, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
+    for (int n = 1; n <= kMaxNstep && st == SRLX_OK; n++) st = set_lds(learn_nstep_fn(n), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     if (st != SRLX_OK) {
         srlx_mlpq_destroy(h);
         return st;
@@ -453,7 +765,8 @@ int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *wi
 int srlx_mlpq_destroy(srlx_mlpq_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
-    for (void *p : {h->d_net, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->q_on_next, (void *)h->q_tg_next, (void *)h->grad_q, (void *)h->loss_rows})
+    for (void *p : {h->d_net, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->q_on_next, (void *)h->q_tg_next, (void *)h->grad_q, (void *)h->grad_v,
+                    (void *)h->loss_rows})
         if (p) (void)hipFree(p);
     delete h;
     return SRLX_OK;
@@ -461,7 +774,7 @@ int srlx_mlpq_destroy(srlx_mlpq_t *h) {
 
 int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params) {
     SRLX_REQUIRE(h && d_params, "mlpq_bind: NULL argument");
-    for (int i = 0; i < 2 * (h->L + 1); i++) {
+    for (int i = 0; i < n_params(h); i++) {
         SRLX_REQUIRE(d_params[i], "mlpq_bind: parameter %d is NULL", i);
         h->p[i] = d_params[i];
     }
@@ -475,13 +788,13 @@ int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params) {
 
 int srlx_mlpq_bind_grads(srlx_mlpq_t *h, float *const *d_grads) {
     SRLX_REQUIRE(h, "mlpq_bind_grads: NULL handle");
-    for (int i = 0; i < 2 * (h->L + 1); i++) h->grads[i] = d_grads ? d_grads[i] : nullptr;
+    for (int i = 0; i < n_params(h); i++) h->grads[i] = d_grads ? d_grads[i] : nullptr;
     return SRLX_OK;
 }
 
 int srlx_mlpq_bind_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, double lr, double beta1, double beta2, double eps) {
     SRLX_REQUIRE(h && d_exp_avg && d_exp_avg_sq, "mlpq_bind_adam: NULL argument");
-    for (int i = 0; i < 2 * (h->L + 1); i++) {
+    for (int i = 0; i < n_params(h); i++) {
         SRLX_REQUIRE(d_exp_avg[i] && d_exp_avg_sq[i], "mlpq_bind_adam: state %d is NULL", i);
         h->m[i] = d_exp_avg[i], h->v[i] = d_exp_avg_sq[i];
     }
@@ -509,6 +822,7 @@ int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batc
                          const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
                          const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
     SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_step: unbound handle");
+    SRLX_REQUIRE(!h->head && !target->head, "mlpq_train_step: a dueling handle trains through srlx_mlpq_train_nstep");
     SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A, "mlpq_train_step: online and target shapes differ");
     for (int l = 0; l < h->L; l++) SRLX_REQUIRE(h->W[l] == target->W[l], "mlpq_train_step: online and target layer widths differ");
     SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "mlpq_train_step: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
@@ -556,9 +870,70 @@ int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batc
     return SRLX_OK;
 }
 
+int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batch, int n, const float *d_obs_base, const int64_t *d_offsets,
+                          const int32_t *d_actions, const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, double retrace_h,
+                          int double_dqn, int rescale, const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
+    SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_nstep: unbound handle");
+    SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A && h->head == target->head && h->H == target->H,
+                 "mlpq_train_nstep: online and target shapes differ");
+    for (int l = 0; l < h->L; l++) SRLX_REQUIRE(h->W[l] == target->W[l], "mlpq_train_nstep: online and target layer widths differ");
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "mlpq_train_nstep: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(n >= 1 && n <= h->max_nstep, "mlpq_train_nstep: %d steps (handle sized for %d)", n, h->max_nstep);
+    SRLX_REQUIRE(d_obs_base && d_offsets && d_actions && d_rewards && d_terminated && d_weights && d_q0 && d_target && d_loss && d_priorities,
+                 "mlpq_train_nstep: NULL argument");
+    SRLX_REQUIRE(!h->adam || d_steps_taken, "mlpq_train_nstep: Adam needs the step count");
+    bool any_grad = false;
+    for (int i = 0; i < n_params(h); i++) any_grad |= h->grads[i] != nullptr;
+    SRLX_REQUIRE(h->adam || any_grad, "mlpq_train_nstep: neither gradients nor Adam bound");
+    srlx::DeviceGuard g(h->device);
+    const int S = lds_stride(h);
+    LearnN a{};
+    a.B = batch, a.obs = d_obs_base, a.off = (const i64 *)d_offsets;
+    a.actions = d_actions, a.rewards = d_rewards, a.terminated = d_terminated, a.weights = d_weights;
+    a.x0 = h->x0, a.h = h->h, a.dh = h->dh, a.q0 = d_q0, a.grad_q = h->grad_q, a.grad_v = h->grad_v, a.loss_rows = h->loss_rows;
+    a.hstride = (int)(h->max_batch * h->wmax);
+    a.target = d_target, a.priorities = d_priorities;
+    a.discount = discount, a.retrace_h = retrace_h, a.double_dqn = double_dqn, a.rescale = rescale;
+    for (int m = 0; m < kMaxNstep; m++) a.dm[m] = m < n ? (float)pow(discount, (double)m) : 0.f;  // (srlx_td_math.h:td_fill_discounts)
+    const int P = kRows / (n + 1);
+    const Net *onp = (const Net *)h->d_net, *tgp = (const Net *)target->d_net;
+    void *args[] = {(void *)&onp, (void *)&tgp, (void *)&a, (void *)&S};
+    SRLX_HIP(hipLaunchKernel(learn_nstep_fn(n), dim3((unsigned)((batch + P - 1) / P)), dim3(kThreads), args, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile),
+                             (hipStream_t)stream));
+    GradAdam ga = segments(h);
+    ga.B = batch;
+    const i64 plane = h->max_batch * h->wmax;
+    const float *trunk_out = h->L == 0 ? h->x0 : h->h + (h->L - 1) * plane;
+    for (int l = 0; l < ga.nseg / 2; l++) {
+        const float *dout, *xin;
+        if (l < h->L) {
+            dout = h->dh + l * plane, xin = l == 0 ? h->x0 : h->h + (l - 1) * plane;
+        } else if (!h->head) {
+            dout = h->grad_q, xin = trunk_out;
+        } else {
+            const int k = l - h->L;  // v_layers.0, v_layers.2, adv_layers.0, adv_layers.2
+            dout = k == 0 ? h->dh + h->L * plane : (k == 1 ? h->grad_v : (k == 2 ? h->dh + (h->L + 1) * plane : h->grad_q));
+            xin = k == 0 || k == 2 ? trunk_out : (k == 1 ? h->h + h->L * plane : h->h + (h->L + 1) * plane);
+        }
+        for (int k = 0; k < 2; k++) {
+            const int s = 2 * l + k;
+            ga.dout[s] = dout, ga.xin[s] = xin;
+            ga.p[s] = h->p[s], ga.g[s] = h->grads[s], ga.m[s] = h->m[s], ga.v[s] = h->v[s];
+        }
+    }
+    ga.adam = h->adam ? 1 : 0;
+    ga.lr = h->lr, ga.beta1 = h->beta1, ga.beta2 = h->beta2, ga.eps = h->eps;
+    ga.steps_taken = (const i64 *)d_steps_taken;
+    ga.loss_rows = h->loss_rows, ga.loss = d_loss;
+    const i64 total = ga.seg_end[ga.nseg - 1];
+    hipLaunchKernelGGL(k_mlpq_grad_adam, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
 int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream) {
     SRLX_REQUIRE(src && dst && src->bound && dst->bound, "mlpq_publish: unbound handle");
-    SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A, "mlpq_publish: shapes differ");
+    SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A && src->head == dst->head && src->H == dst->H, "mlpq_publish: shapes differ");
     for (int l = 0; l < src->L; l++) SRLX_REQUIRE(src->W[l] == dst->W[l], "mlpq_publish: shapes differ");
     srlx::DeviceGuard g(src->device);
     GradAdam c = segments(src);

@@ -5,7 +5,9 @@ Reference semantics kept (file:line under the reference root):
   srl/algorithms/dqn/model_torch.py:17-29   in_block -> hidden_block (MLP) -> out_layer             -> EngineMLPQNet
   srl/algorithms/dqn/dqn.py:144-176         the 1-step (double) DQN target                           -> srlx_mlpq_train_step
   srl/algorithms/dqn/model_torch.py:89-131  IS-weighted Huber loss, Adam, priorities, target sync   -> srlx_mlpq_train_step, srlx_mlpq_publish
-The replay is the engine's `DeviceReplay` with float32 observations, window 1 and 1-step items.
+  srl/algorithms/rainbow/model_torch.py:15-29  in_block -> hidden_block (MLP over layer_sizes[:-1] + DuelingNetworkBlock) -> EngineMLPQNet(dueling_units=H)
+  srl/algorithms/rainbow/rainbow.py:185-287    the n-step retrace target                              -> srlx_mlpq_train_nstep
+The replay is the engine's `DeviceReplay` with float32 observations, window 1 and `multisteps`-step items.
 """
 import ctypes
 from dataclasses import dataclass
@@ -19,25 +21,41 @@ from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.device.replay import DeviceReplay
 
 
+DUELING_TYPES = {"average": 0, "": 1}  # srlx_mlpq_create_dueling's dueling_type
+
+
 class EngineMLPQNet(nn.Module):
     """DQN's module tree for a flat input (algorithms/dqn.py:build_qnetwork): `in_sizes` = the input value block's layers, `hidden_sizes` = the MLP hidden
-    block's, every one Linear + ReLU, then `out_layer`.  Parameters stay in torch's Linear layout, which is the one libsrlx reads."""
+    block's, every one Linear + ReLU, then `out_layer`.  Parameters stay in torch's Linear layout, which is the one libsrlx reads.
 
-    def __init__(self, obs_dim: int, in_sizes: Sequence[int], hidden_sizes: Sequence[int], n_actions: int):
+    `dueling_units` = H > 0 is Rainbow's tree instead (rl/torch_/networks.py:create_dueling_hidden_block): `hidden_sizes` = the hidden block's layer_sizes[:-1],
+    then a DuelingNetworkBlock with H = layer_sizes[-1] units in its value and advantage branches (`dueling_type` "average" or "") in place of `out_layer`."""
+
+    def __init__(self, obs_dim: int, in_sizes: Sequence[int], hidden_sizes: Sequence[int], n_actions: int, dueling_units: int = 0,
+                 dueling_type: str = "average"):
         super().__init__()
         self.obs_dim, self.n_actions = int(obs_dim), int(n_actions)
         self.in_sizes, self.hidden_sizes = tuple(int(x) for x in in_sizes), tuple(int(x) for x in hidden_sizes)
+        self.dueling_units, self.dueling_type = int(dueling_units), str(dueling_type)
         sizes = self.in_sizes + self.hidden_sizes
         self.layers = nn.ModuleList()
         prev = self.obs_dim
         for s in sizes:
             self.layers.append(nn.Linear(prev, s))
             prev = s
-        self.out_layer = nn.Linear(prev, self.n_actions)
         # the reference's keys: in_block.hidden_layers = [Flatten, Linear, ReLU, ...], hidden_block.hidden_layers = [Linear, ReLU, ...]
         self._keys = [f"in_block.hidden_layers.{1 + 2 * k}" for k in range(len(self.in_sizes))]
         self._keys += [f"hidden_block.hidden_layers.{2 * k}" for k in range(len(self.hidden_sizes))]
-        self._keys.append("out_layer")
+        if self.dueling_units:
+            assert self.dueling_type in DUELING_TYPES, self.dueling_type
+            H = self.dueling_units
+            self.v_hidden, self.v_out = nn.Linear(prev, H), nn.Linear(H, 1)
+            self.adv_hidden, self.adv_out = nn.Linear(prev, H), nn.Linear(H, self.n_actions)
+            head = f"hidden_block.hidden_layers.{2 * len(self.hidden_sizes)}"  # the DuelingNetworkBlock: v_layers / adv_layers = [Linear, ReLU, Linear]
+            self._keys += [head + ".v_layers.0", head + ".v_layers.2", head + ".adv_layers.0", head + ".adv_layers.2"]
+        else:
+            self.out_layer = nn.Linear(prev, self.n_actions)
+            self._keys.append("out_layer")
         self.weights_version = 0
 
     @property
@@ -48,13 +66,21 @@ class EngineMLPQNet(nn.Module):
         x = x.reshape(x.shape[0], -1)
         for layer in self.layers:
             x = F.relu(layer(x))
-        return self.out_layer(x)
+        if not self.dueling_units:
+            return self.out_layer(x)
+        v, adv = self.v_out(F.relu(self.v_hidden(x))), self.adv_out(F.relu(self.adv_hidden(x)))
+        if self.dueling_type == "average":
+            return v + adv - torch.mean(adv, dim=-1, keepdim=True)
+        return v + adv
 
     def _linears(self):
+        if self.dueling_units:
+            return list(self.layers) + [self.v_hidden, self.v_out, self.adv_hidden, self.adv_out]
         return list(self.layers) + [self.out_layer]
 
     def kernel_parameters(self):
-        """The tensors libsrlx binds, in the reference's key order: weight then bias of every layer, out_layer last."""
+        """The tensors libsrlx binds, in the reference's key order: weight then bias of every layer, out_layer (or the head's v_layers.0, v_layers.2,
+        adv_layers.0, adv_layers.2) last."""
         ps = []
         for lin in self._linears():
             ps += [lin.weight, lin.bias]
@@ -78,16 +104,21 @@ class EngineMLPQNet(nn.Module):
 
 class MLPQHandle:
     """One libsrlx handle over an EngineMLPQNet's parameters (zero copy).  `max_batch` > 0: the handle trains -- gradient tensors (`p.grad`) and, with `lr`,
-    torch's Adam state are bound, and `train_step` runs the whole update in two launches."""
+    torch's Adam state are bound, and `train_step` / `train_nstep` run the whole update in two launches.  A dueling net gets a srlx_mlpq_create_dueling handle
+    (`max_nstep`: the longest item its `train_nstep` takes)."""
 
     def __init__(self, net: EngineMLPQNet, max_rows: int, device: int = 0, max_batch: int = 0, lr: Optional[float] = None, betas=(0.9, 0.999),
-                 eps: float = 1e-8, write_grads: bool = True):
+                 eps: float = 1e-8, write_grads: bool = True, max_nstep: int = 7):
         self.lib = N.lib()
         self.net = net
         widths = (ctypes.c_int * 3)(*(list(net.widths) + [0, 0, 0])[:3])
         h = N.c_p()
-        N.check(self.lib.srlx_mlpq_create(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.n_actions, int(max_rows), int(max_batch),
-                                          int(device)))
+        if net.dueling_units:
+            N.check(self.lib.srlx_mlpq_create_dueling(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.dueling_units,
+                                                      DUELING_TYPES[net.dueling_type], net.n_actions, int(max_rows), int(max_batch), int(max_nstep), int(device)))
+        else:
+            N.check(self.lib.srlx_mlpq_create(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.n_actions, int(max_rows),
+                                              int(max_batch), int(device)))
         self.h = h
         self.params = net.kernel_parameters()
         assert all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in self.params)
@@ -131,6 +162,13 @@ class MLPQHandle:
         N.check(self.lib.srlx_mlpq_train_step(self.h, target.h, int(batch), N.c_p(obs_base), N.tptr(offsets), N.tptr(actions), N.tptr(rewards), N.tptr(terminated),
                                               N.tptr(weights), float(discount), int(bool(double_dqn)), int(bool(rescale)), N.tptr(steps_taken), N.tptr(q0),
                                               N.tptr(target_out), N.tptr(loss), N.tptr(priorities), N.torch_stream_ptr()))
+
+    def train_nstep(self, target: "MLPQHandle", batch: int, n: int, obs_base: int, offsets, actions, rewards, terminated, weights, discount: float,
+                    retrace_h: float, double_dqn: bool, rescale: bool, steps_taken, q0, target_out, loss, priorities):
+        """One n-step retrace update (rainbow.py:185-287, model_torch.py:85-122): offsets int64 [B][n + 1], actions / rewards / terminated [B][n]."""
+        N.check(self.lib.srlx_mlpq_train_nstep(self.h, target.h, int(batch), int(n), N.c_p(obs_base), N.tptr(offsets), N.tptr(actions), N.tptr(rewards),
+                                               N.tptr(terminated), N.tptr(weights), float(discount), float(retrace_h), int(bool(double_dqn)), int(bool(rescale)),
+                                               N.tptr(steps_taken), N.tptr(q0), N.tptr(target_out), N.tptr(loss), N.tptr(priorities), N.torch_stream_ptr()))
 
     def publish_to(self, dst: "MLPQHandle"):
         """Every parameter of this handle's network into `dst`'s (one launch, on the current stream)."""
@@ -194,16 +232,23 @@ class VectorQConfig:
     in_sizes: tuple = ()
     hidden_sizes: tuple = (512,)
     n_actions: int = 2
+    # --- rainbow.Config (srl/algorithms/rainbow/rainbow.py:57-107): dueling_units = the hidden block's layer_sizes[-1] (0: the plain out_layer; `hidden_sizes`
+    # is then layer_sizes[:-1]), its dueling_type ("average" or ""), multisteps, retrace_h
+    dueling_units: int = 0
+    dueling_type: str = "average"
+    multisteps: int = 1
+    retrace_h: float = 1.0
     # --- engine
     n_envs: int = 1024
     seed: int = 0
 
 
 class VectorQEngine:
-    """E lock-stepped environments and DQN updates on one GPU for flat observations, every network pass in libsrlx:
+    """E lock-stepped environments and DQN (or, with `dueling_units` / `multisteps`, Rainbow) updates on one GPU for flat observations, every network pass in
+    libsrlx:
       actor_front   1 launch (Q rows + epsilon-greedy from the store's float ring) + the environments' step
       actor_commit  ring commit (also writes the next pass's row table and advances the policy counter) + the replay's add
-      learner_step  the replay's draw + gather, srlx_mlpq_train_step (2 launches), the priority write-back (train_count += 1 on the device)
+      learner_step  the replay's draw + gather, srlx_mlpq_train_step (or srlx_mlpq_train_nstep; 2 launches), the priority write-back (train_count += 1 on the device)
     Actors and learner share one stream and one parameter set (no copy to refresh)."""
 
     overlap = False
@@ -214,8 +259,10 @@ class VectorQEngine:
         self.lib = N.lib()
         torch.manual_seed(cfg.seed)
         E, B, A, D = cfg.n_envs, cfg.batch_size, cfg.n_actions, cfg.obs_dim
-        ring_len = -(-cfg.memory_capacity // E) + 2  # item_len * E >= capacity (n_step 1 + window 1)
-        self.replay = DeviceReplay(E, ring_len, D, 1, 1, A, B, False, cfg.enable_reward_clip, cfg.memory_alpha, cfg.memory_beta_initial, cfg.memory_beta_steps,
+        n = int(cfg.multisteps)
+        self.nstep = n > 1 or cfg.dueling_units > 0  # srlx_mlpq_train_nstep; the defaults keep srlx_mlpq_train_step
+        ring_len = -(-cfg.memory_capacity // E) + n + 1  # item_len * E >= capacity (n_step n + window 1)
+        self.replay = DeviceReplay(E, ring_len, D, 1, n, A, B, False, cfg.enable_reward_clip, cfg.memory_alpha, cfg.memory_beta_initial, cfg.memory_beta_steps,
                                    cfg.memory_epsilon, cfg.memory_warmup_size, cfg.seed, device, has_duplicate=cfg.memory_has_duplicate,
                                    # (a draw without replacement rejects repeats: 8 spare uniforms serve B <= 64 as in RainbowEngine; B = 128 from 512 items needs ~16)
                                    sample_slack=8 if B <= 64 else 4 * B)
@@ -223,12 +270,12 @@ class VectorQEngine:
             self.env = CartPoleVecEnv(self.replay)
         else:
             self.env = env(self.replay) if callable(env) else env
-        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A).to(self.dev)
-        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A).to(self.dev)
+        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type).to(self.dev)
+        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type).to(self.dev)
         self.q_target.load_state_dict(self.q_online.state_dict())
         self.q_actor = self.q_online
-        self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr)
-        self.inf_target = MLPQHandle(self.q_target, max(E, B), device)
+        self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr, max_nstep=n)
+        self.inf_target = MLPQHandle(self.q_target, max(E, B), device, max_nstep=n)
         d = self.dev
         self.eps = torch.full((E,), float(cfg.epsilon), dtype=torch.float32, device=d)
         self.actions = torch.zeros(E, dtype=torch.int32, device=d)
@@ -273,8 +320,13 @@ class VectorQEngine:
     def _learner_body(self):
         cfg, r = self.cfg, self.replay
         b = r.sample_items(self.train_count_dev, all_states=True)
-        self.inf_online.train_step(self.inf_target, cfg.batch_size, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, b.weights, cfg.discount,
-                                   cfg.enable_double_dqn, cfg.enable_rescale, self.train_count_dev, self.q0, self.target, self.loss, self.priorities)
+        if self.nstep:
+            self.inf_online.train_nstep(self.inf_target, cfg.batch_size, cfg.multisteps, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, b.weights,
+                                        cfg.discount, cfg.retrace_h, cfg.enable_double_dqn, cfg.enable_rescale, self.train_count_dev, self.q0, self.target,
+                                        self.loss, self.priorities)
+        else:
+            self.inf_online.train_step(self.inf_target, cfg.batch_size, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, b.weights, cfg.discount,
+                                       cfg.enable_double_dqn, cfg.enable_rescale, self.train_count_dev, self.q0, self.target, self.loss, self.priorities)
         r.update(b.indices, self.priorities)  # model_torch.py:121-122; train_count_dev += 1 in the same launch
 
     def learner_step(self) -> bool:

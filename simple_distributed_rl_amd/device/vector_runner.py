@@ -355,6 +355,62 @@ def _why_not_flat_dqn(env, rl_config) -> str:
     return _why_not_memory(rl_config)
 
 
+def dueling_layer_sizes(rl_config):
+    """(input value block layers, the hidden block's layer_sizes[:-1], dueling units, dueling_type) of a rainbow.Config whose hidden block is a DuelingNetwork
+    of ReLU layers behind an MLP input value block, or None."""
+    iv, hb = rl_config.input_block.value, rl_config.hidden_block
+    if iv.name != "MLP" or hb.name != "DuelingNetwork":
+        return None
+    acts = [iv.kwargs.get("activation", "relu"), hb.kwargs.get("mlp_kwargs", {}).get("activation", "relu"),
+            hb.kwargs.get("dueling_kwargs", {}).get("activation", "relu")]
+    sizes = tuple(int(x) for x in hb.kwargs.get("layer_sizes", ()))
+    if any(str(a).lower() != "relu" for a in acts) or not sizes:
+        return None
+    return (tuple(int(x) for x in iv.kwargs.get("layer_sizes", ())), sizes[:-1], sizes[-1],
+            str(hb.kwargs.get("dueling_kwargs", {}).get("dueling_type", "average")))
+
+
+def why_not_flat_rainbow(env, rl_config) -> str:
+    """rainbow.Config on flat observations: the shapes srlx_mlpq_create_dueling / srlx_mlpq_train_nstep cover (srlx.h).  Empty string: VectorQEngine can run it
+    (`mlp_config_from`).  `Runner.train()` does not ask yet: `why_not_vector` keeps Rainbow on flat observations on the plugin path."""
+    space = frame_space(env, rl_config)
+    D = flat_dim(space)
+    if D is None:
+        return "observations are not single-channel image frames (after the config's ImageProcessor, if any)"
+    if getattr(rl_config, "_obs_processors", None):
+        return "observation processors on flat observations are served by the plugin path"
+    if D > 256:
+        return "the MLP Q-network reads at most 256 observation elements"
+    if rl_config.window_length != 1:
+        return "the MLP Q-network reads one observation (window_length 1)"
+    if not 2 <= env.action_space.n <= 32:
+        return "the MLP Q-network serves 2 to 32 actions"
+    if rl_config.enable_noisy_dense:
+        return "the MLP Q-network has no noisy dense layers"
+    if rl_config.hidden_block.name == "MLP":
+        return "the MLP Q-network's Rainbow form ends in a dueling head; an MLP hidden block stays on the plugin path"
+    sizes = dueling_layer_sizes(rl_config)
+    if sizes is None:
+        return "the MLP Q-network's input value block is an MLP and its hidden block a DuelingNetwork, all of ReLU layers"
+    ins, hid, units, dtype = sizes
+    if dtype not in ("average", ""):
+        return "the dueling head covers the dueling types 'average' and ''"
+    hb = rl_config.hidden_block
+    for k, v in list(rl_config.input_block.value.kwargs.items()) + list(hb.kwargs.get("mlp_kwargs", {}).items()):
+        if k in _MLP_FREE_KWARGS or (k in _MLP_DEFAULT_KWARGS and v == _MLP_DEFAULT_KWARGS[k]):
+            continue
+        return f"the MLP Q-network covers Linear layers with biases after a Flatten; block option {k}={v!r} stays on the plugin path"
+    if len(ins + hid) > 2:
+        return "the dueling MLP Q-network covers at most 2 dense layers in front of the head (input value block plus the hidden block's layer_sizes[:-1])"
+    if any(w % 32 != 0 or not 32 <= w <= 512 for w in ins + hid + (units,)):
+        return "the MLP Q-network covers dense layers of 32..512 units in multiples of 32"
+    if rl_config.multisteps > 7:
+        return "the MLP Q-network's gradient step covers multisteps of at most 7"
+    if rl_config.batch_size > 256:
+        return "the MLP Q-network's gradient step covers batches of at most 256"
+    return _why_not_memory(rl_config)
+
+
 def auto_lanes_reason(env, rl_config, n_envs) -> str:
     """Flat-observation DQN engages the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
     if is_flat_dqn(env, rl_config) and isinstance(n_envs, str):
@@ -363,13 +419,19 @@ def auto_lanes_reason(env, rl_config, n_envs) -> str:
 
 
 def mlp_config_from(rl_config, env, n_envs: int, seed: int):
-    """dqn.Config (srl/algorithms/dqn/dqn.py:50-101) on a flat observation -> VectorQConfig (device/mlpq.py)."""
+    """dqn.Config (srl/algorithms/dqn/dqn.py:50-101) or rainbow.Config (srl/algorithms/rainbow/rainbow.py:57-107) on a flat observation -> VectorQConfig
+    (device/mlpq.py)."""
     from simple_distributed_rl_amd.device.mlpq import VectorQConfig
 
     mem = rl_config.memory
     prop = mem.name != "ReplayBuffer"
     kw = mem.kwargs if prop else {}
-    ins, hid = mlp_layer_sizes(rl_config)
+    head = {}
+    if engine_kind(rl_config) == "rainbow":
+        ins, hid, units, dtype = dueling_layer_sizes(rl_config)
+        head = dict(dueling_units=units, dueling_type=dtype, multisteps=int(rl_config.multisteps), retrace_h=float(rl_config.retrace_h))
+    else:
+        ins, hid = mlp_layer_sizes(rl_config)
     return VectorQConfig(
         batch_size=rl_config.batch_size, epsilon=rl_config.epsilon, test_epsilon=rl_config.test_epsilon, lr=rl_config.lr, discount=rl_config.discount,
         target_model_update_interval=rl_config.target_model_update_interval, enable_reward_clip=rl_config.enable_reward_clip,
@@ -378,7 +440,7 @@ def mlp_config_from(rl_config, env, n_envs: int, seed: int):
         memory_has_duplicate=bool(kw.get("has_duplicate", True)) if prop else False,
         memory_alpha=float(kw.get("alpha", 0.0)), memory_beta_initial=float(kw.get("beta_initial", 0.4)),
         memory_beta_steps=int(kw.get("beta_steps", 1_000_000)), memory_epsilon=float(kw.get("epsilon", 1e-4)),
-        obs_dim=flat_dim(frame_space(env, rl_config)), in_sizes=ins, hidden_sizes=hid, n_actions=env.action_space.n, n_envs=n_envs, seed=seed,
+        obs_dim=flat_dim(frame_space(env, rl_config)), in_sizes=ins, hidden_sizes=hid, n_actions=env.action_space.n, n_envs=n_envs, seed=seed, **head,
     )
 
 
