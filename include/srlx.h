@@ -918,6 +918,35 @@ int srlx_qnet_noisy_effective(srlx_qnet_t *h, int which, float *d_out, int64_t *
  *                            d_offsets int64 [B][n + 1] (the store's frame_off_all at window 1), actions / rewards / terminated [B][n].  No invalid-action
  *                            mask.  Outputs as srlx_mlpq_train_step; bit-reproducible.  On a plain handle at n = 1, retrace_h = 1 every output, gradient and
  *                            post-Adam parameter is bit-equal to srlx_mlpq_train_step's.
+ * NoisyLinear layers on a dueling handle (srl/rl/torch_/modules/noisy_linear.py:8-52: W = w_mu + w_sigma * eps, b = b_mu + b_sigma * eps, eps iid N(0, 1), drawn
+ * anew on every forward call and shared by all rows of the call; rainbow.Config(enable_noisy_dense=True)):
+ *   srlx_mlpq_bind_noisy   : d_sigma[2 * n_trunk + 8] in srlx_mlpq_bind's order; a layer is noisy iff both of its entries (weight sigma, bias sigma) are non-NULL.
+ *                            The four head layers must be noisy; trunk layers may be plain, but only as a prefix (the input value block).  The tensors given to
+ *                            srlx_mlpq_bind are then the mu tensors.  The handle allocates its effective tensors (two sets when it trains) and a device-resident
+ *                            draw counter starting at 0.  A plain (srlx_mlpq_create) handle refuses: DQN has no noisy form.
+ *   srlx_mlpq_bind_noisy_grads / _adam : the sigmas' gradient tensors (NULL table: none) and exp_avg / exp_avg_sq, tables in the same order (entries of plain
+ *                            tensors are ignored); Adam's hyper-parameters are srlx_mlpq_bind_adam's, which comes first.
+ *   The generator: eps(seed, draw, tensor index, element) = srlx_noise_math.h:noisy_eps_pair, a pure function (Box-Muller on srlx::rng_u64; elements 2 j and
+ *                            2 j + 1 share one evaluation).  One launch (k_mlpq_noisy_eff) writes mu + sigma * eps of every noisy tensor; every other kernel
+ *                            reads the effective tensors like plain weights.
+ *   The draw-id contract: a handle's passes consume consecutive ids from its counter.  srlx_mlpq_forward on a noisy handle consumes 1.
+ *                            srlx_mlpq_train_nstep consumes 2 on the online handle (id: the pass over s_1..s_n, id + 1: the pass over s_0, whose gradient is
+ *                            taken) and 1 on the target handle, whatever double_dqn is.  The ids are read from device memory, so a captured update replays with
+ *                            fresh noise.  A counter is advanced by the launch BEHIND the one that reads it (the acting kernel, the learner kernel), never by
+ *                            a launch whose other workgroups still read it.  The sigma gradients d loss / d sigma = d loss / d W * eps regenerate eps from the
+ *                            id the s_0 pass used, which the materialising launch recorded.
+ *   srlx_mlpq_forward      : effective tensors of a fresh draw (one added launch), otherwise unchanged; a noisy net acts greedily (rainbow.py:305-309): the caller
+ *                            passes eps = 0 rows.
+ *   srlx_mlpq_train_nstep  : three launches on noisy handles: the three draws, the learner kernel (the online pass split: rows of s_0 under draw id + 1 with
+ *                            their kept planes, rows of s_1..s_n under draw id; the target pass under the target's draw and its own sigmas; the backward chain
+ *                            through the s_0 effective weights), and the gradient / Adam launch, where the thread that sums d loss / d W of an element also
+ *                            writes g_mu = g, g_sigma = g * eps and takes both Adam steps.  With every sigma 0 the outputs, mu gradients and post-Adam mu are the
+ *                            plain dueling handle's bits.  Refused: a noisy online handle with a plain target or the reverse, neither sigma gradients nor sigma
+ *                            Adam state bound.  srlx_mlpq_train_step refuses noisy handles.
+ *   srlx_mlpq_publish      : copies the sigmas too (a second launch); refuses a noisy source with a plain destination and the reverse
+ *   srlx_mlpq_noisy_draw   : synchronises the device; *set_next (may be NULL) becomes the id the next pass uses; *next_out (may be NULL) receives that id
+ *   srlx_mlpq_noisy_eps    : writes eps(seed of the handle, draw, param_index, .) of one noisy tensor into d_out (its shape): the noise of a step, known before
+ *                            the step runs
  * Batch CartPole (envs/cartpole.py:step; srlx_mlpq.hip): float64 state [E][4], steps / episodes int32 [E].  A lane whose d_needs_reset entry is set (the store's
  * needs_reset view, srlx_store_views) starts its next episode instead of stepping: state uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane), its
  * first observation in d_obs, reward / terminated / done 0.  d_needs_reset NULL: every lane starts an episode (actions and scalar outputs may be NULL).
@@ -939,6 +968,11 @@ int srlx_mlpq_create_dueling(srlx_mlpq_t **out, int obs_dim, int n_trunk, const 
 int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batch, int n, const float *d_obs_base, const int64_t *d_offsets,
                           const int32_t *d_actions, const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, double retrace_h,
                           int double_dqn, int rescale, const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream);
+int srlx_mlpq_bind_noisy(srlx_mlpq_t *h, float *const *d_sigma, uint64_t seed);
+int srlx_mlpq_bind_noisy_grads(srlx_mlpq_t *h, float *const *d_grad_sigma);
+int srlx_mlpq_bind_noisy_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq);
+int srlx_mlpq_noisy_draw(srlx_mlpq_t *h, const int64_t *set_next, int64_t *next_out);
+int srlx_mlpq_noisy_eps(srlx_mlpq_t *h, int64_t draw, int param_index, float *d_out, void *stream);
 int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
                        int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 

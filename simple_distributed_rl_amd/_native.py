@@ -216,6 +216,11 @@ SIGNATURES = {
     "srlx_mlpq_train_step": (c_int, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_mlpq_publish": (c_int, [c_p, c_p, c_p]),
     "srlx_mlpq_create_dueling": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_p, c_int, c_int, c_int, c_i64, c_i64, c_int, c_int]),
+    "srlx_mlpq_bind_noisy": (c_int, [c_p, c_p, c_u64]),
+    "srlx_mlpq_bind_noisy_grads": (c_int, [c_p, c_p]),
+    "srlx_mlpq_bind_noisy_adam": (c_int, [c_p, c_p, c_p]),
+    "srlx_mlpq_noisy_draw": (c_int, [c_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "srlx_mlpq_noisy_eps": (c_int, [c_p, c_i64, c_int, c_p, c_p]),
     "srlx_mlpq_train_nstep": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_cartpole_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
 }

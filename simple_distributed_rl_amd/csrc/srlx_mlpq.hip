@@ -13,8 +13,18 @@
 //                     dueling head (forward_rows: MLP trunk of 0..2 layers, then v_layers / adv_layers; srl/rl/torch_/blocks/dueling_network.py:8-59).
 //   k_mlpq_grad_adam  one thread per parameter: the gradient as a sum over the batch in item order (no atomics: bit-reproducible), then torch's Adam
 //                     (srlx_adam_math.h) in the same thread; block 0 reduces the loss.
+//
+// NoisyLinear layers (srl/rl/torch_/modules/noisy_linear.py:8-52; rainbow.Config(enable_noisy_dense=True)) on a dueling handle, srlx_mlpq_bind_noisy: the
+// bound tensors are the mu tensors, and ONE launch per call (k_mlpq_noisy_eff) writes mu + sigma * eps of every noisy tensor into the handle's effective
+// tensors, which dense / narrow_rows / the backward chain read like plain weights -- srlx_noisy.hip:1-16's argument: inside dense() every workgroup would
+// regenerate every normal of the layer, on the VALU that the multiply-adds need.  eps(seed, draw, tensor, element) is a pure function (srlx_noise_math.h), the
+// draw ids come from a device-resident counter (srlx.h: the draw-id contract), and k_mlpq_grad_adam_noisy regenerates the s_0 pass's eps for d loss / d sigma.
+//   k_mlpq_noisy_eff        up to three draws in one launch (the learner: the online handle's s_1..s_n and s_0 draws and the target's)
+//   k_mlpq_learn_nstep_noisy<n>  k_mlpq_learn_nstep<n> with the online pass split: rows of s_0 under one draw, rows of s_1..s_n under the other
+//   k_mlpq_grad_adam_noisy  k_mlpq_grad_adam; for a noisy tensor the thread also writes g_sigma = g * eps and takes sigma's Adam step
 #include "srlx_adam_math.h"
 #include "srlx_common.h"
+#include "srlx_noise_math.h"
 #include "srlx_ppo_math.h"
 #include "srlx_td_math.h"
 
@@ -35,6 +45,14 @@ struct srlx_mlpq {
     double *loss_rows;
     int wmax;
     void *d_net;  // the descriptor of the bound parameters in device memory (the learner step's launch reads it)
+    // NoisyLinear (srlx_mlpq_bind_noisy): p[] are the mu tensors; sig[i] != NULL marks a noisy tensor.  eff[0]: the effective tensors of srlx_mlpq_forward, of
+    // the learner's s_1..s_n pass and of a target handle's pass; eff[1] (training handles): those of the learner's s_0 pass.  d_net describes set 0, d_net0 set 1.
+    bool noisy, noisy_adam;
+    float *sig[12], *gsig[12], *msig[12], *vsig[12];
+    float *eff[2][12];
+    unsigned long long noisy_seed;
+    int64_t *d_draw;  // [0] the id the next pass will use, [1] the id set 0 holds, [2] the id set 1 holds
+    void *d_net0;
 };
 
 namespace {
@@ -65,19 +83,23 @@ struct Net {  // (scalar fields and selects, no arrays: a kernel-argument array 
     __device__ const float *bias(int l) const { return l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3)); }
 };
 
-Net net_of(const srlx_mlpq *h) {
+// the tensors a pass reads: the bound ones, or for a noisy tensor the effective one of `set`
+const float *read_ptr(const srlx_mlpq *h, int i, int set) { return h->sig[i] ? h->eff[set][i] : h->p[i]; }
+
+Net net_of(const srlx_mlpq *h, int set = 0) {
     Net n;
     n.D = h->D, n.L = h->L, n.A = h->A;
     n.W0 = h->W[0], n.W1 = h->L > 1 ? h->W[1] : 0, n.W2 = h->L > 2 ? h->W[2] : 0;
     const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
     const int plain_layers = h->head ? h->L : h->L + 1;
-    for (int l = 0; l < plain_layers; l++) w[l] = h->p[2 * l], b[l] = h->p[2 * l + 1];
+    for (int l = 0; l < plain_layers; l++) w[l] = read_ptr(h, 2 * l, set), b[l] = read_ptr(h, 2 * l + 1, set);
     n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
     n.wout = h->head ? nullptr : w[h->L];
     n.H = h->H, n.head = h->head;
-    float *const *q = h->p + 2 * h->L;
-    n.vw0 = n.vb0 = n.vw1 = n.vb1 = n.aw0 = n.ab0 = n.aw1 = n.ab1 = nullptr;
-    if (h->head) n.vw0 = q[0], n.vb0 = q[1], n.vw1 = q[2], n.vb1 = q[3], n.aw0 = q[4], n.ab0 = q[5], n.aw1 = q[6], n.ab1 = q[7];
+    const float *q[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (h->head)
+        for (int k = 0; k < 8; k++) q[k] = read_ptr(h, 2 * h->L + k, set);
+    n.vw0 = q[0], n.vb0 = q[1], n.vw1 = q[2], n.vb1 = q[3], n.aw0 = q[4], n.ab0 = q[5], n.aw1 = q[6], n.ab1 = q[7];
     return n;
 }
 
@@ -218,12 +240,13 @@ __device__ __forceinline__ int select_action(const Policy &pol, i64 m, int A, co
 __device__ __forceinline__ const float *row_ptr(const float *base, const i64 *off, i64 row, int D) { return off ? base + off[row] : base + row * D; }
 
 __global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S, float *__restrict__ q,
-                                                         Policy pol) {
+                                                         Policy pol, i64 *draw) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
     const int t = threadIdx.x;
     const i64 r0 = (i64)blockIdx.x * kRows;
     const int rows = (int)(rows_total - r0 < kRows ? rows_total - r0 : kRows);
+    if (draw && blockIdx.x == 0 && t == 0) draw[0] += 1;  // NoisyLinear: this pass's draw is spent (every reader of draw[0] ran in the launch before)
     for (int p = t; p < rows * n.D; p += kThreads) {
         const int r = p / n.D, k = p % n.D;
         b0[r * S + k] = row_ptr(obs, off, r0 + r, n.D)[k];
@@ -420,10 +443,13 @@ __device__ __forceinline__ double td_item(const LearnN &a, i64 b, int A, const f
 // kRows / (NS + 1) items per workgroup, rows step-major (row s * P + item): the online pass over s_0..s_n, the target pass over s_1..s_n, td_item, then the
 // row-local backward chain -- through out_layer as in k_mlpq_learn_rows, or through the dueling head's two branches into the trunk.  At NS = 1 on a plain net the
 // row layout, every sum and every store are k_mlpq_learn_rows's.
-template <int NS>
-__global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep(const Net *__restrict__ onp, const Net *__restrict__ tgp, LearnN a, int S) {
+//
+// NZ (NoisyLinear handles): `on` describes the effective tensors of the s_0 draw, `on_next` those of the s_1..s_n draw, and the online pass runs as two calls
+// of forward_rows -- rows 0..P-1 under `on` with their kept planes, rows P.. under `on_next`.  dense() and narrow_rows() give a row the same sums whichever
+// rows share the call, so with every sigma 0 the results are the plain kernel's bits.  The backward chain reads `on`.
+template <int NS, bool NZ>
+__device__ __forceinline__ void learn_nstep_body(const Net &on, const Net &on_next, const Net &tg, const LearnN &a, int S) {
     constexpr int P = kRows / (NS + 1), R = P * (NS + 1);
-    const Net &on = *onp, &tg = *tgp;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *b0 = sm, *b1 = sm + kRows * S, *d0 = sm + 2 * kRows * S, *d1 = d0 + kItems * S, *wl = d1 + kItems * S;
     __shared__ float qon_s[kRows * 32], qtg_s[kRows * 32];  // Q rows of s_1..s_n: row (s - 1) * P + item, A floats each
@@ -440,9 +466,18 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep(const Net *__rest
         if (st == 0 && it < nb) a.x0[(i0 + it) * D + k] = x;
     }
     __syncthreads();
-    const float *qs = forward_rows(on, R, b0, b1, S, wl, a.h, a.hstride, i0, nb);
-    for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
-    for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qs[(P + p / A) * S + p % A];
+    if constexpr (NZ) {
+        // (forward_rows writes rows < `rows` of either buffer only: the s_1..s_n inputs in rows P.. of b0 outlive the s_0 pass)
+        const float *qs = forward_rows(on, P, b0, b1, S, wl, a.h, a.hstride, i0, nb);
+        for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
+        __syncthreads();
+        const float *qn = forward_rows(on_next, NS * P, b0 + P * S, b1 + P * S, S, wl, nullptr, 0, 0, 0);
+        for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qn[(p / A) * S + p % A];
+    } else {
+        const float *qs = forward_rows(on, R, b0, b1, S, wl, a.h, a.hstride, i0, nb);
+        for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
+        for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qs[(P + p / A) * S + p % A];
+    }
     __syncthreads();
     for (int p = t; p < NS * P * D; p += kThreads) {
         const int r = p / D, k = p % D, it = r % P, st = r / P + 1;
@@ -547,6 +582,31 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep(const Net *__rest
     }
 }
 
+template <int NS>
+__global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep(const Net *__restrict__ onp, const Net *__restrict__ tgp, LearnN a, int S) {
+    learn_nstep_body<NS, false>(*onp, *onp, *tgp, a, S);
+}
+
+// draw_on / draw_tg: the two handles' draw counters.  k_mlpq_noisy_eff, the launch before this one, was their last reader: the three ids are spent here.
+template <int NS>
+__global__ void __launch_bounds__(kThreads) k_mlpq_learn_nstep_noisy(const Net *__restrict__ on0p, const Net *__restrict__ onp, const Net *__restrict__ tgp, LearnN a,
+                                                                     int S, i64 *draw_on, i64 *draw_tg) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) draw_on[0] += 2, draw_tg[0] += 1;
+    learn_nstep_body<NS, true>(*on0p, *onp, *tgp, a, S);
+}
+
+const void *learn_nstep_noisy_fn(int n) {
+    switch (n) {
+    case 1: return (const void *)k_mlpq_learn_nstep_noisy<1>;
+    case 2: return (const void *)k_mlpq_learn_nstep_noisy<2>;
+    case 3: return (const void *)k_mlpq_learn_nstep_noisy<3>;
+    case 4: return (const void *)k_mlpq_learn_nstep_noisy<4>;
+    case 5: return (const void *)k_mlpq_learn_nstep_noisy<5>;
+    case 6: return (const void *)k_mlpq_learn_nstep_noisy<6>;
+    default: return (const void *)k_mlpq_learn_nstep_noisy<7>;
+    }
+}
+
 const void *learn_nstep_fn(int n) {
     switch (n) {
     case 1: return (const void *)k_mlpq_learn_nstep<1>;
@@ -574,7 +634,15 @@ struct GradAdam {
     float *loss;
 };
 
-__global__ void __launch_bounds__(kThreads) k_mlpq_grad_adam(GradAdam a) {
+// the sigma side of a noisy handle's update (NULL sig[s]: a plain tensor)
+struct NoisyGrad {
+    float *sig[kMaxParams], *g[kMaxParams], *m[kMaxParams], *v[kMaxParams];
+    u64 seed;
+    const i64 *draw;  // draw[2]: the id of the s_0 pass whose gradient this is
+};
+
+template <bool NZ>
+__device__ __forceinline__ void grad_adam_body(const GradAdam &a, const NoisyGrad *z) {
     const i64 i = (i64)blockIdx.x * kThreads + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.loss) {
         double s = 0.0;
@@ -603,6 +671,70 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_grad_adam(GradAdam a) {
         float p = a.p[s][e], m = a.m[s][e], v = a.v[s][e];
         srlx::adam_one(p, g, m, v, c);
         a.p[s][e] = p, a.m[s][e] = m, a.v[s][e] = v;
+    }
+    if constexpr (NZ) {
+        // noisy_linear.py:50-52: W = w_mu + w_sigma * eps, so d loss / d w_sigma = d loss / d W * eps of the pass the gradient belongs to
+        if (!z->sig[s]) return;
+        const float2 n2 = srlx::noisy_eps_pair(z->seed, (u64)z->draw[2], s, (u64)(e >> 1));
+        const float gs = g * ((e & 1) ? n2.y : n2.x);
+        if (z->g[s]) z->g[s][e] = gs;
+        if (a.adam) {
+            const srlx::AdamCoef c = srlx::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.steps_taken[0]);
+            float p = z->sig[s][e], m = z->m[s][e], v = z->v[s][e];
+            srlx::adam_one(p, gs, m, v, c);
+            z->sig[s][e] = p, z->m[s][e] = m, z->v[s][e] = v;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_grad_adam(GradAdam a) { grad_adam_body<false>(a, nullptr); }
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_grad_adam_noisy(GradAdam a, NoisyGrad z) { grad_adam_body<true>(a, &z); }
+
+// ---- NoisyLinear: the effective tensors of a draw -------------------------------------------------------------------------------------------------------------
+struct EffJob {  // one draw of one handle
+    const float *mu[kMaxParams], *sig[kMaxParams];  // sig NULL: a plain tensor (no elements in `begin`)
+    float *out[kMaxParams];
+    i64 *draw;  // the handle's counter block: the id is draw[0] + add, recorded in draw[rec]
+    int add, rec;
+    u64 seed;
+};
+struct EffArgs {
+    EffJob job[3];  // blockIdx.y
+    i64 begin[kMaxParams + 1];  // prefix sums of the noisy tensors' element PAIR counts (one Box-Muller evaluation yields elements 2 j, 2 j + 1)
+    i64 n[kMaxParams];
+};
+
+__device__ __forceinline__ int find_segment(const i64 *begin, i64 j) {
+    int t = 0;
+#pragma unroll
+    for (int k = 1; k < kMaxParams; k++) t += j >= begin[k] ? 1 : 0;
+    return t;
+}
+
+// out = mu + sigma * eps(seed, id, tensor, element) for every noisy tensor of up to three draws.  The counters are only read here (the call's next launch
+// advances them); block (0, y) records the id its job used.
+__global__ void __launch_bounds__(kThreads) k_mlpq_noisy_eff(EffArgs s) {
+    const EffJob &jb = s.job[blockIdx.y];
+    const i64 id = jb.draw[0] + jb.add;
+    if (blockIdx.x == 0 && threadIdx.x == 0) jb.draw[jb.rec] = id;
+    const i64 total = s.begin[kMaxParams];
+    for (i64 j = (i64)blockIdx.x * kThreads + threadIdx.x; j < total; j += (i64)gridDim.x * kThreads) {
+        const int t = find_segment(s.begin, j);
+        const i64 p = j - s.begin[t], e = 2 * p;
+        const float2 z = srlx::noisy_eps_pair(jb.seed, (u64)id, t, (u64)p);
+        jb.out[t][e] = jb.mu[t][e] + jb.sig[t][e] * z.x;
+        if (e + 1 < s.n[t]) jb.out[t][e + 1] = jb.mu[t][e + 1] + jb.sig[t][e + 1] * z.y;
+    }
+}
+
+// eps of one tensor under a given draw (tests: the noise of a step, known before it runs)
+__global__ void __launch_bounds__(kThreads) k_mlpq_noisy_eps(u64 seed, i64 id, int t, i64 n, float *__restrict__ out) {
+    const i64 pairs = (n + 1) / 2;
+    for (i64 p = (i64)blockIdx.x * kThreads + threadIdx.x; p < pairs; p += (i64)gridDim.x * kThreads) {
+        const float2 z = srlx::noisy_eps_pair(seed, (u64)id, t, (u64)p);
+        out[2 * p] = z.x;
+        if (2 * p + 1 < n) out[2 * p + 1] = z.y;
     }
 }
 
@@ -677,6 +809,50 @@ GradAdam segments(const srlx_mlpq *h) {
         a.seg_end[2 * l + 1] = run, a.seg_out[2 * l + 1] = Out, a.seg_in[2 * l + 1] = 0;
     }
     return a;
+}
+
+// the descriptors the learner's launch reads from memory: set 0, and on a noisy training handle set 1 (the s_0 pass)
+int upload_nets(srlx_mlpq *h) {
+    if (!h->d_net) SRLX_HIP(hipMalloc(&h->d_net, sizeof(Net)));
+    const Net n = net_of(h, 0);
+    SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(Net), hipMemcpyHostToDevice));
+    if (h->noisy && h->eff[1][n_params(h) - 1]) {
+        if (!h->d_net0) SRLX_HIP(hipMalloc(&h->d_net0, sizeof(Net)));
+        const Net n0 = net_of(h, 1);
+        SRLX_HIP(hipMemcpy(h->d_net0, &n0, sizeof(Net), hipMemcpyHostToDevice));
+    }
+    return SRLX_OK;
+}
+
+// begin / n of EffArgs for this handle's shapes; returns the pair count of one draw
+i64 eff_shapes(const srlx_mlpq *h, EffArgs &a) {
+    const GradAdam seg = segments(h);
+    a.begin[0] = 0;
+    for (int t = 0; t < kMaxParams; t++) {
+        const i64 n = t < seg.nseg ? seg.seg_end[t] - (t ? seg.seg_end[t - 1] : 0) : 0;
+        a.n[t] = n;
+        a.begin[t + 1] = a.begin[t] + (t < seg.nseg && h->sig[t] ? (n + 1) / 2 : 0);
+    }
+    return a.begin[kMaxParams];
+}
+
+EffJob eff_job(const srlx_mlpq *h, int set, int add) {
+    EffJob j{};
+    for (int t = 0; t < n_params(h); t++) j.mu[t] = h->p[t], j.sig[t] = h->sig[t], j.out[t] = h->eff[set][t];
+    j.draw = h->d_draw, j.add = add, j.rec = 1 + set, j.seed = h->noisy_seed;
+    return j;
+}
+
+void launch_eff(const EffArgs &a, int jobs, hipStream_t st) {
+    const i64 total = a.begin[kMaxParams];
+    const i64 blocks = (total + 4 * kThreads - 1) / (4 * kThreads);  // (about four pairs per thread)
+    hipLaunchKernelGGL(k_mlpq_noisy_eff, dim3((unsigned)(blocks < 1 ? 1 : blocks), (unsigned)jobs), dim3(kThreads), 0, st, a);
+}
+
+bool same_noisy_layers(const srlx_mlpq *a, const srlx_mlpq *b) {
+    for (int t = 0; t < n_params(a); t++)
+        if ((a->sig[t] != nullptr) != (b->sig[t] != nullptr)) return false;
+    return true;
 }
 
 }  // namespace
@@ -754,6 +930,8 @@ static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const in
     int st = set_lds((const void *)k_mlpq_actor, sizeof(float) * (2 * kRows * S + kWTile));
     if (st == SRLX_OK) st = set_lds((const void *)k_mlpq_learn_rows, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     for (int n = 1; n <= kMaxNstep && st == SRLX_OK; n++) st = set_lds(learn_nstep_fn(n), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
+    for (int n = 1; n <= kMaxNstep && st == SRLX_OK && head; n++)
+        st = set_lds(learn_nstep_noisy_fn(n), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     if (st != SRLX_OK) {
         srlx_mlpq_destroy(h);
         return st;
@@ -765,7 +943,10 @@ static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const in
 int srlx_mlpq_destroy(srlx_mlpq_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
-    for (void *p : {h->d_net, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->q_on_next, (void *)h->q_tg_next, (void *)h->grad_q, (void *)h->grad_v,
+    for (int set = 0; set < 2; set++)
+        for (int t = 0; t < kMaxParams; t++)
+            if (h->eff[set][t]) (void)hipFree(h->eff[set][t]);
+    for (void *p : {h->d_net0, (void *)h->d_draw, h->d_net, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->q_on_next, (void *)h->q_tg_next, (void *)h->grad_q, (void *)h->grad_v,
                     (void *)h->loss_rows})
         if (p) (void)hipFree(p);
     delete h;
@@ -780,9 +961,85 @@ int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params) {
     }
     h->bound = true;
     srlx::DeviceGuard g(h->device);
-    if (!h->d_net) SRLX_HIP(hipMalloc(&h->d_net, sizeof(Net)));
-    const Net n = net_of(h);
-    SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(Net), hipMemcpyHostToDevice));
+    return upload_nets(h);
+}
+
+int srlx_mlpq_bind_noisy(srlx_mlpq_t *h, float *const *d_sigma, uint64_t seed) {
+    SRLX_REQUIRE(h && d_sigma, "mlpq_bind_noisy: NULL argument");
+    SRLX_REQUIRE(h->head, "mlpq_bind_noisy: a plain (out_layer) handle has no NoisyLinear form; noisy layers belong to srlx_mlpq_create_dueling handles");
+    SRLX_REQUIRE(h->bound, "mlpq_bind_noisy: bind the parameters first (srlx_mlpq_bind: a noisy layer's entries are its mu tensors)");
+    const int np = n_params(h);
+    bool seen = false;
+    for (int l = 0; l < np / 2; l++) {
+        const bool w = d_sigma[2 * l] != nullptr, b = d_sigma[2 * l + 1] != nullptr;
+        SRLX_REQUIRE(w == b, "mlpq_bind_noisy: layer %d has one of its two sigma tensors (weight and bias sigma come together)", l);
+        SRLX_REQUIRE(w || l < h->L, "mlpq_bind_noisy: head layer %d has no sigma tensors (the four head layers are noisy)", l - h->L);
+        SRLX_REQUIRE(w || !seen, "mlpq_bind_noisy: plain trunk layer %d behind a noisy one (plain layers form a prefix: the input value block)", l);
+        seen |= w;
+    }
+    srlx::DeviceGuard g(h->device);
+    SRLX_REQUIRE(g.ok, "mlpq_bind_noisy: device %d unavailable", h->device);
+    const GradAdam seg = segments(h);
+    for (int t = 0; t < np; t++) {
+        const size_t n = (size_t)(seg.seg_end[t] - (t ? seg.seg_end[t - 1] : 0));
+        for (int set = 0; set < (h->max_batch > 0 ? 2 : 1); set++) {
+            if (d_sigma[t] && !h->eff[set][t]) SRLX_HIP(hipMalloc((void **)&h->eff[set][t], n * sizeof(float)));
+            if (!d_sigma[t] && h->eff[set][t]) {
+                SRLX_HIP(hipFree(h->eff[set][t]));
+                h->eff[set][t] = nullptr;
+            }
+        }
+        h->sig[t] = d_sigma[t];
+    }
+    if (!h->d_draw) {
+        SRLX_HIP(hipMalloc((void **)&h->d_draw, 4 * sizeof(int64_t)));
+        const int64_t init[4] = {0, -1, -1, 0};
+        SRLX_HIP(hipMemcpy(h->d_draw, init, sizeof(init), hipMemcpyHostToDevice));
+    }
+    h->noisy = true, h->noisy_seed = seed;
+    return upload_nets(h);  // from now on every pass reads the effective tensors of the noisy layers
+}
+
+int srlx_mlpq_bind_noisy_grads(srlx_mlpq_t *h, float *const *d_grad_sigma) {
+    SRLX_REQUIRE(h && h->noisy, "mlpq_bind_noisy_grads: not a noisy handle (srlx_mlpq_bind_noisy)");
+    for (int t = 0; t < n_params(h); t++) {
+        SRLX_REQUIRE(!d_grad_sigma || !h->sig[t] || d_grad_sigma[t], "mlpq_bind_noisy_grads: gradient tensor %d is NULL", t);
+        h->gsig[t] = d_grad_sigma && h->sig[t] ? d_grad_sigma[t] : nullptr;
+    }
+    return SRLX_OK;
+}
+
+int srlx_mlpq_bind_noisy_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq) {
+    SRLX_REQUIRE(h && h->noisy && d_exp_avg && d_exp_avg_sq, "mlpq_bind_noisy_adam: not a noisy handle (srlx_mlpq_bind_noisy), or a NULL argument");
+    SRLX_REQUIRE(h->adam, "mlpq_bind_noisy_adam: bind the mu tensors' Adam state first (srlx_mlpq_bind_adam: its hyper-parameters serve mu and sigma alike)");
+    for (int t = 0; t < n_params(h); t++) {
+        SRLX_REQUIRE(!h->sig[t] || (d_exp_avg[t] && d_exp_avg_sq[t]), "mlpq_bind_noisy_adam: state %d is NULL", t);
+        h->msig[t] = h->sig[t] ? d_exp_avg[t] : nullptr, h->vsig[t] = h->sig[t] ? d_exp_avg_sq[t] : nullptr;
+    }
+    h->noisy_adam = true;
+    return SRLX_OK;
+}
+
+int srlx_mlpq_noisy_draw(srlx_mlpq_t *h, const int64_t *set_next, int64_t *next_out) {
+    SRLX_REQUIRE(h && h->noisy, "mlpq_noisy_draw: not a noisy handle (srlx_mlpq_bind_noisy)");
+    SRLX_REQUIRE(!set_next || *set_next >= 0, "mlpq_noisy_draw: draw ids are non-negative");
+    srlx::DeviceGuard g(h->device);
+    SRLX_HIP(hipDeviceSynchronize());
+    if (set_next) SRLX_HIP(hipMemcpy(h->d_draw, set_next, sizeof(int64_t), hipMemcpyHostToDevice));
+    if (next_out) SRLX_HIP(hipMemcpy(next_out, h->d_draw, sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SRLX_OK;
+}
+
+int srlx_mlpq_noisy_eps(srlx_mlpq_t *h, int64_t draw, int param_index, float *d_out, void *stream) {
+    SRLX_REQUIRE(h && h->noisy && d_out, "mlpq_noisy_eps: not a noisy handle (srlx_mlpq_bind_noisy), or NULL output");
+    SRLX_REQUIRE(param_index >= 0 && param_index < n_params(h) && h->sig[param_index], "mlpq_noisy_eps: tensor %d is not a noisy tensor of this handle", param_index);
+    SRLX_REQUIRE(draw >= 0, "mlpq_noisy_eps: draw ids are non-negative");
+    srlx::DeviceGuard g(h->device);
+    const GradAdam seg = segments(h);
+    const i64 n = seg.seg_end[param_index] - (param_index ? seg.seg_end[param_index - 1] : 0);
+    const i64 blocks = ((n + 1) / 2 + 4 * kThreads - 1) / (4 * kThreads);
+    hipLaunchKernelGGL(k_mlpq_noisy_eps, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, (u64)h->noisy_seed, (i64)draw, param_index, n, d_out);
+    SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
 
@@ -812,8 +1069,14 @@ int srlx_mlpq_forward(srlx_mlpq_t *h, int64_t rows, const float *d_obs, const in
     srlx::DeviceGuard g(h->device);
     const int S = lds_stride(h);
     Policy pol{(u64)seed, (const i64 *)d_counter, d_eps, d_actions};
+    if (h->noisy) {  // a fresh draw for this call's rows (noisy_linear.py:44-52), then the pass spends it
+        EffArgs ea{};
+        eff_shapes(h, ea);
+        ea.job[0] = eff_job(h, 0, 0);
+        launch_eff(ea, 1, (hipStream_t)stream);
+    }
     hipLaunchKernelGGL(k_mlpq_actor, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(kThreads), sizeof(float) * (2 * kRows * S + kWTile), (hipStream_t)stream, net_of(h),
-                       (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol);
+                       (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol, h->noisy ? (i64 *)h->d_draw : (i64 *)nullptr);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
@@ -822,6 +1085,7 @@ int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batc
                          const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
                          const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
     SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_step: unbound handle");
+    SRLX_REQUIRE(!h->noisy && !target->noisy, "mlpq_train_step: a noisy handle trains through srlx_mlpq_train_nstep");
     SRLX_REQUIRE(!h->head && !target->head, "mlpq_train_step: a dueling handle trains through srlx_mlpq_train_nstep");
     SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A, "mlpq_train_step: online and target shapes differ");
     for (int l = 0; l < h->L; l++) SRLX_REQUIRE(h->W[l] == target->W[l], "mlpq_train_step: online and target layer widths differ");
@@ -885,6 +1149,15 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
     bool any_grad = false;
     for (int i = 0; i < n_params(h); i++) any_grad |= h->grads[i] != nullptr;
     SRLX_REQUIRE(h->adam || any_grad, "mlpq_train_nstep: neither gradients nor Adam bound");
+    SRLX_REQUIRE(h->noisy == target->noisy && (!h->noisy || same_noisy_layers(h, target)),
+                 "mlpq_train_nstep: a noisy online handle needs a noisy target with the same noisy layers, a plain one a plain target");
+    if (h->noisy) {
+        bool any_sigma_grad = false;
+        for (int i = 0; i < n_params(h); i++) any_sigma_grad |= h->gsig[i] != nullptr;
+        SRLX_REQUIRE(h->noisy_adam || any_sigma_grad, "mlpq_train_nstep: neither sigma gradients nor sigma Adam state bound (srlx_mlpq_bind_noisy_grads / _adam)");
+        SRLX_REQUIRE(h->adam == h->noisy_adam, "mlpq_train_nstep: Adam steps mu and sigma alike: bind the state of both (srlx_mlpq_bind_adam, srlx_mlpq_bind_noisy_adam)");
+        SRLX_REQUIRE(h != target && h->d_net0, "mlpq_train_nstep: the online handle was not created for training");
+    }
     srlx::DeviceGuard g(h->device);
     const int S = lds_stride(h);
     LearnN a{};
@@ -897,9 +1170,22 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
     for (int m = 0; m < kMaxNstep; m++) a.dm[m] = m < n ? (float)pow(discount, (double)m) : 0.f;  // (srlx_td_math.h:td_fill_discounts)
     const int P = kRows / (n + 1);
     const Net *onp = (const Net *)h->d_net, *tgp = (const Net *)target->d_net;
-    void *args[] = {(void *)&onp, (void *)&tgp, (void *)&a, (void *)&S};
-    SRLX_HIP(hipLaunchKernel(learn_nstep_fn(n), dim3((unsigned)((batch + P - 1) / P)), dim3(kThreads), args, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile),
-                             (hipStream_t)stream));
+    if (h->noisy) {
+        // three draws in one launch: the online handle's id (s_1..s_n pass, set 0) and id + 1 (s_0 pass, set 1), the target handle's id (set 0)
+        EffArgs ea{};
+        eff_shapes(h, ea);
+        ea.job[0] = eff_job(h, 0, 0), ea.job[1] = eff_job(h, 1, 1), ea.job[2] = eff_job(target, 0, 0);
+        launch_eff(ea, 3, (hipStream_t)stream);
+        const Net *on0p = (const Net *)h->d_net0;
+        i64 *draw_on = (i64 *)h->d_draw, *draw_tg = (i64 *)target->d_draw;
+        void *args[] = {(void *)&on0p, (void *)&onp, (void *)&tgp, (void *)&a, (void *)&S, (void *)&draw_on, (void *)&draw_tg};
+        SRLX_HIP(hipLaunchKernel(learn_nstep_noisy_fn(n), dim3((unsigned)((batch + P - 1) / P)), dim3(kThreads), args,
+                                 sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile), (hipStream_t)stream));
+    } else {
+        void *args[] = {(void *)&onp, (void *)&tgp, (void *)&a, (void *)&S};
+        SRLX_HIP(hipLaunchKernel(learn_nstep_fn(n), dim3((unsigned)((batch + P - 1) / P)), dim3(kThreads), args,
+                                 sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile), (hipStream_t)stream));
+    }
     GradAdam ga = segments(h);
     ga.B = batch;
     const i64 plane = h->max_batch * h->wmax;
@@ -926,7 +1212,14 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
     ga.steps_taken = (const i64 *)d_steps_taken;
     ga.loss_rows = h->loss_rows, ga.loss = d_loss;
     const i64 total = ga.seg_end[ga.nseg - 1];
-    hipLaunchKernelGGL(k_mlpq_grad_adam, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga);
+    if (h->noisy) {
+        NoisyGrad z{};
+        for (int s = 0; s < ga.nseg; s++) z.sig[s] = h->sig[s], z.g[s] = h->gsig[s], z.m[s] = h->msig[s], z.v[s] = h->vsig[s];
+        z.seed = h->noisy_seed, z.draw = (const i64 *)h->d_draw;
+        hipLaunchKernelGGL(k_mlpq_grad_adam_noisy, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga, z);
+    } else {
+        hipLaunchKernelGGL(k_mlpq_grad_adam, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga);
+    }
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
@@ -935,11 +1228,23 @@ int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream) {
     SRLX_REQUIRE(src && dst && src->bound && dst->bound, "mlpq_publish: unbound handle");
     SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A && src->head == dst->head && src->H == dst->H, "mlpq_publish: shapes differ");
     for (int l = 0; l < src->L; l++) SRLX_REQUIRE(src->W[l] == dst->W[l], "mlpq_publish: shapes differ");
+    SRLX_REQUIRE(src->noisy == dst->noisy && (!src->noisy || same_noisy_layers(src, dst)),
+                 "mlpq_publish: a noisy source needs a noisy destination with the same noisy layers, a plain one a plain destination");
     srlx::DeviceGuard g(src->device);
     GradAdam c = segments(src);
     for (int s = 0; s < c.nseg; s++) c.p[s] = src->p[s], c.g[s] = dst->p[s];
     const i64 total = c.seg_end[c.nseg - 1];
     hipLaunchKernelGGL(k_mlpq_copy, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, c.nseg, c);
+    if (src->noisy) {  // the sigmas (model_torch.py:125-127 copies the whole state_dict): the noisy tensors' segments, compacted
+        GradAdam z{};
+        i64 run = 0;
+        for (int s = 0; s < c.nseg; s++) {
+            if (!src->sig[s]) continue;
+            run += c.seg_end[s] - (s ? c.seg_end[s - 1] : 0);
+            z.seg_end[z.nseg] = run, z.p[z.nseg] = src->sig[s], z.g[z.nseg] = dst->sig[s], z.nseg++;
+        }
+        hipLaunchKernelGGL(k_mlpq_copy, dim3((unsigned)((run + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, z.nseg, z);
+    }
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

@@ -14,11 +14,13 @@
 // Parity with the reference is statistical (its noise comes from torch's Philox stream): tests/test_noisy_gpu.py checks
 // mean / variance of the effective weights and of Q over many draws against torch's NoisyLinear, exact equality at sigma = 0,
 // and the gradients against torch autograd of the same effective weights.
+#include "srlx_noise_math.h"
 #include "srlx_qnet_int.h"
 
 namespace {
 using i64 = int64_t;
 using u64 = unsigned long long;
+using srlx::normal_pair;  // (srlx_noise_math.h: shared with the MLP Q-network)
 using srlx::rng_u64;
 
 struct NoisySet {
@@ -26,16 +28,6 @@ struct NoisySet {
     float *out[6];
     i64 begin[7];  // prefix sums of the element PAIR counts (one Box-Muller evaluation yields the normals of elements 2j, 2j+1)
 };
-
-// two independent standard normals from one 64-bit draw (Box-Muller on two 24-bit uniforms; u1 in (0, 1])
-__device__ __forceinline__ float2 normal_pair(u64 x) {
-    const float u1 = (float)((unsigned)(x >> 40) + 1u) * (1.0f / 16777216.0f);
-    const float u2 = (float)((unsigned)(x >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincosf(6.283185307179586f * u2, &s, &c);
-    return make_float2(r * c, r * s);
-}
 
 __device__ __forceinline__ int find_tensor(const i64 *begin, i64 j) {
     int t = 0;

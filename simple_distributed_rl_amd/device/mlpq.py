@@ -7,6 +7,8 @@ Reference semantics kept (file:line under the reference root):
   srl/algorithms/dqn/model_torch.py:89-131  IS-weighted Huber loss, Adam, priorities, target sync   -> srlx_mlpq_train_step, srlx_mlpq_publish
   srl/algorithms/rainbow/model_torch.py:15-29  in_block -> hidden_block (MLP over layer_sizes[:-1] + DuelingNetworkBlock) -> EngineMLPQNet(dueling_units=H)
   srl/algorithms/rainbow/rainbow.py:185-287    the n-step retrace target                              -> srlx_mlpq_train_nstep
+  srl/rl/torch_/modules/noisy_linear.py:8-52   NoisyLinear (enable_noisy_dense: the hidden block's MLP layers and the head) -> EngineMLPQNet(noisy=True),
+                                               srlx_mlpq_bind_noisy; rainbow.py:305-309: a noisy net acts greedily          -> VectorQEngine.eps = 0
 The replay is the engine's `DeviceReplay` with float32 observations, window 1 and `multisteps`-step items.
 """
 import ctypes
@@ -19,6 +21,7 @@ import torch.nn.functional as F
 
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.device.replay import DeviceReplay
+from simple_distributed_rl_amd.rl.torch_.networks import NoisyLinear
 
 
 DUELING_TYPES = {"average": 0, "": 1}  # srlx_mlpq_create_dueling's dueling_type
@@ -29,19 +32,26 @@ class EngineMLPQNet(nn.Module):
     block's, every one Linear + ReLU, then `out_layer`.  Parameters stay in torch's Linear layout, which is the one libsrlx reads.
 
     `dueling_units` = H > 0 is Rainbow's tree instead (rl/torch_/networks.py:create_dueling_hidden_block): `hidden_sizes` = the hidden block's layer_sizes[:-1],
-    then a DuelingNetworkBlock with H = layer_sizes[-1] units in its value and advantage branches (`dueling_type` "average" or "") in place of `out_layer`."""
+    then a DuelingNetworkBlock with H = layer_sizes[-1] units in its value and advantage branches (`dueling_type` "average" or "") in place of `out_layer`.
+
+    `noisy` (Rainbow's enable_noisy_dense; dueling nets only): the `hidden_sizes` layers and the four head layers are NoisyLinear (`w_mu / w_sigma / b_mu /
+    b_sigma`, the reference's initialisation and keys, fresh torch.randn noise on every forward); the `in_sizes` layers stay nn.Linear
+    (rainbow/model_torch.py:19-24: the input value block takes no noisy flag)."""
 
     def __init__(self, obs_dim: int, in_sizes: Sequence[int], hidden_sizes: Sequence[int], n_actions: int, dueling_units: int = 0,
-                 dueling_type: str = "average"):
+                 dueling_type: str = "average", noisy: bool = False):
         super().__init__()
+        self.noisy = bool(noisy)
+        assert not self.noisy or dueling_units, "noisy layers belong to the dueling (Rainbow) network"
+        lin = NoisyLinear if self.noisy else nn.Linear
         self.obs_dim, self.n_actions = int(obs_dim), int(n_actions)
         self.in_sizes, self.hidden_sizes = tuple(int(x) for x in in_sizes), tuple(int(x) for x in hidden_sizes)
         self.dueling_units, self.dueling_type = int(dueling_units), str(dueling_type)
         sizes = self.in_sizes + self.hidden_sizes
         self.layers = nn.ModuleList()
         prev = self.obs_dim
-        for s in sizes:
-            self.layers.append(nn.Linear(prev, s))
+        for k, s in enumerate(sizes):
+            self.layers.append((nn.Linear if k < len(self.in_sizes) else lin)(prev, s))
             prev = s
         # the reference's keys: in_block.hidden_layers = [Flatten, Linear, ReLU, ...], hidden_block.hidden_layers = [Linear, ReLU, ...]
         self._keys = [f"in_block.hidden_layers.{1 + 2 * k}" for k in range(len(self.in_sizes))]
@@ -49,8 +59,8 @@ class EngineMLPQNet(nn.Module):
         if self.dueling_units:
             assert self.dueling_type in DUELING_TYPES, self.dueling_type
             H = self.dueling_units
-            self.v_hidden, self.v_out = nn.Linear(prev, H), nn.Linear(H, 1)
-            self.adv_hidden, self.adv_out = nn.Linear(prev, H), nn.Linear(H, self.n_actions)
+            self.v_hidden, self.v_out = lin(prev, H), lin(H, 1)
+            self.adv_hidden, self.adv_out = lin(prev, H), lin(H, self.n_actions)
             head = f"hidden_block.hidden_layers.{2 * len(self.hidden_sizes)}"  # the DuelingNetworkBlock: v_layers / adv_layers = [Linear, ReLU, Linear]
             self._keys += [head + ".v_layers.0", head + ".v_layers.2", head + ".adv_layers.0", head + ".adv_layers.2"]
         else:
@@ -83,32 +93,47 @@ class EngineMLPQNet(nn.Module):
         adv_layers.0, adv_layers.2) last."""
         ps = []
         for lin in self._linears():
-            ps += [lin.weight, lin.bias]
+            ps += [lin.w_mu, lin.b_mu] if isinstance(lin, NoisyLinear) else [lin.weight, lin.bias]
         return ps
+
+    def kernel_sigmas(self):
+        """One entry per `kernel_parameters()` tensor: the sigma tensor of a noisy layer's weight / bias, None for a plain layer's."""
+        ss = []
+        for lin in self._linears():
+            ss += [lin.w_sigma, lin.b_sigma] if isinstance(lin, NoisyLinear) else [None, None]
+        return ss
+
+    @staticmethod
+    def _named(key, lin):
+        """(reference key, tensor) pairs of one layer in the reference's parameter order."""
+        if isinstance(lin, NoisyLinear):
+            return [(key + ".w_mu", lin.w_mu), (key + ".w_sigma", lin.w_sigma), (key + ".b_mu", lin.b_mu), (key + ".b_sigma", lin.b_sigma)]
+        return [(key + ".weight", lin.weight), (key + ".bias", lin.bias)]
 
     def load_reference_state_dict(self, sd):
         self.weights_version += 1
         with torch.no_grad():
             for key, lin in zip(self._keys, self._linears()):
-                lin.weight.copy_(sd[key + ".weight"])
-                lin.bias.copy_(sd[key + ".bias"])
+                for k, t in self._named(key, lin):
+                    t.copy_(sd[k])
         return self
 
     def reference_state_dict(self):
         sd = {}
         for key, lin in zip(self._keys, self._linears()):
-            sd[key + ".weight"] = lin.weight.detach().clone()
-            sd[key + ".bias"] = lin.bias.detach().clone()
+            for k, t in self._named(key, lin):
+                sd[k] = t.detach().clone()
         return sd
 
 
 class MLPQHandle:
     """One libsrlx handle over an EngineMLPQNet's parameters (zero copy).  `max_batch` > 0: the handle trains -- gradient tensors (`p.grad`) and, with `lr`,
     torch's Adam state are bound, and `train_step` / `train_nstep` run the whole update in two launches.  A dueling net gets a srlx_mlpq_create_dueling handle
-    (`max_nstep`: the longest item its `train_nstep` takes)."""
+    (`max_nstep`: the longest item its `train_nstep` takes).  A noisy net's sigma tensors, their gradients and Adam state are bound beside the mu tensors'
+    (srlx_mlpq_bind_noisy, `noise_seed`: the key of the handle's noise stream; srlx.h: the draw-id contract)."""
 
     def __init__(self, net: EngineMLPQNet, max_rows: int, device: int = 0, max_batch: int = 0, lr: Optional[float] = None, betas=(0.9, 0.999),
-                 eps: float = 1e-8, write_grads: bool = True, max_nstep: int = 7):
+                 eps: float = 1e-8, write_grads: bool = True, max_nstep: int = 7, noise_seed: int = 0):
         self.lib = N.lib()
         self.net = net
         widths = (ctypes.c_int * 3)(*(list(net.widths) + [0, 0, 0])[:3])
@@ -125,6 +150,14 @@ class MLPQHandle:
         self._ptab = (N.c_p * len(self.params))(*[p.data_ptr() for p in self.params])
         N.check(self.lib.srlx_mlpq_bind(h, ctypes.cast(self._ptab, N.c_p)))
         self.exp_avg = self.exp_avg_sq = None
+        self.noise_seed = int(noise_seed) & (2**64 - 1)
+        self.sigmas = net.kernel_sigmas() if getattr(net, "noisy", False) else []
+        self.exp_avg_sigma = self.exp_avg_sq_sigma = None
+        table = lambda ts: (N.c_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
+        if self.sigmas:
+            assert all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in self.sigmas)
+            self._stab = table(self.sigmas)
+            N.check(self.lib.srlx_mlpq_bind_noisy(h, ctypes.cast(self._stab, N.c_p), ctypes.c_uint64(self.noise_seed)))
         if max_batch > 0:
             for p in self.params:
                 if p.grad is None:
@@ -139,6 +172,18 @@ class MLPQHandle:
                 self._vtab = (N.c_p * len(self.params))(*[t.data_ptr() for t in self.exp_avg_sq])
                 N.check(self.lib.srlx_mlpq_bind_adam(h, ctypes.cast(self._mtab, N.c_p), ctypes.cast(self._vtab, N.c_p), float(lr), float(betas[0]), float(betas[1]),
                                                      float(eps)))
+            if self.sigmas:
+                for t in self.sigmas:
+                    if t is not None and t.grad is None:
+                        t.grad = torch.zeros_like(t)
+                if write_grads:
+                    self._sgtab = table([None if t is None else t.grad for t in self.sigmas])
+                    N.check(self.lib.srlx_mlpq_bind_noisy_grads(h, ctypes.cast(self._sgtab, N.c_p)))
+                if lr is not None:
+                    self.exp_avg_sigma = [None if t is None else torch.zeros_like(t) for t in self.sigmas]
+                    self.exp_avg_sq_sigma = [None if t is None else torch.zeros_like(t) for t in self.sigmas]
+                    self._smtab, self._svtab = table(self.exp_avg_sigma), table(self.exp_avg_sq_sigma)
+                    N.check(self.lib.srlx_mlpq_bind_noisy_adam(h, ctypes.cast(self._smtab, N.c_p), ctypes.cast(self._svtab, N.c_p)))
 
     def __del__(self):
         try:
@@ -148,6 +193,22 @@ class MLPQHandle:
                 self.h = None
         except Exception:
             pass
+
+    # ---- NoisyLinear: the handle's draw counter and its noise (srlx.h: the draw-id contract) ----
+    def next_draw(self) -> int:
+        """The id the handle's next pass will use (synchronises the device)."""
+        out = N.c_i64(0)
+        N.check(self.lib.srlx_mlpq_noisy_draw(self.h, None, ctypes.byref(out)))
+        return int(out.value)
+
+    def set_next_draw(self, draw: int):
+        N.check(self.lib.srlx_mlpq_noisy_draw(self.h, ctypes.byref(N.c_i64(int(draw))), None))
+
+    def eps(self, draw: int, k: int) -> torch.Tensor:
+        """The noise of tensor `k` (kernel_parameters() index) under draw id `draw`, in the tensor's shape."""
+        out = torch.empty_like(self.params[k])
+        N.check(self.lib.srlx_mlpq_noisy_eps(self.h, int(draw), int(k), N.tptr(out), N.torch_stream_ptr()))
+        return out
 
     def forward(self, rows: int, obs, offsets=None, q=None, eps=None, seed: int = 0, counter=None, actions=None):
         """Q of `rows` observations (obs: a float32 tensor, or a device address with `offsets` int64 [rows] element offsets) and, with `actions`, the
@@ -238,6 +299,8 @@ class VectorQConfig:
     dueling_type: str = "average"
     multisteps: int = 1
     retrace_h: float = 1.0
+    # rainbow.Config.enable_noisy_dense (rainbow.py:46): NoisyLinear in the hidden block's MLP layers and the dueling head, greedy acting (needs dueling_units)
+    enable_noisy_dense: bool = False
     # --- engine
     n_envs: int = 1024
     seed: int = 0
@@ -249,7 +312,9 @@ class VectorQEngine:
       actor_front   1 launch (Q rows + epsilon-greedy from the store's float ring) + the environments' step
       actor_commit  ring commit (also writes the next pass's row table and advances the policy counter) + the replay's add
       learner_step  the replay's draw + gather, srlx_mlpq_train_step (or srlx_mlpq_train_nstep; 2 launches), the priority write-back (train_count += 1 on the device)
-    Actors and learner share one stream and one parameter set (no copy to refresh)."""
+    Actors and learner share one stream and one parameter set (no copy to refresh).  With `enable_noisy_dense` both networks hold NoisyLinear layers: every pass
+    costs one more launch (the draw's effective tensors; the learner's three draws share one), the draw ids live on the device, so the captured update replays
+    with fresh noise, and every lane acts greedily on its noisy Q row (`eps` = 0)."""
 
     overlap = False
 
@@ -270,14 +335,17 @@ class VectorQEngine:
             self.env = CartPoleVecEnv(self.replay)
         else:
             self.env = env(self.replay) if callable(env) else env
-        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type).to(self.dev)
-        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type).to(self.dev)
+        noisy = bool(cfg.enable_noisy_dense)
+        assert not noisy or cfg.dueling_units > 0, "enable_noisy_dense needs the dueling head (dueling_units > 0)"
+        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy).to(self.dev)
+        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy).to(self.dev)
         self.q_target.load_state_dict(self.q_online.state_dict())
         self.q_actor = self.q_online
-        self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr, max_nstep=n)
-        self.inf_target = MLPQHandle(self.q_target, max(E, B), device, max_nstep=n)
+        # (the two networks' noise streams are independent: the target pass has its own layers, model_torch.py:103)
+        self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr, max_nstep=n, noise_seed=cfg.seed ^ 0x6E6F6973)
+        self.inf_target = MLPQHandle(self.q_target, max(E, B), device, max_nstep=n, noise_seed=cfg.seed ^ 0x74677473)
         d = self.dev
-        self.eps = torch.full((E,), float(cfg.epsilon), dtype=torch.float32, device=d)
+        self.eps = torch.full((E,), 0.0 if noisy else float(cfg.epsilon), dtype=torch.float32, device=d)  # rainbow.py:305-309: no epsilon for a noisy net
         self.actions = torch.zeros(E, dtype=torch.int32, device=d)
         self.policy_counter = torch.zeros(1, dtype=torch.int64, device=d)
         self.train_count_dev = torch.zeros(1, dtype=torch.int64, device=d)

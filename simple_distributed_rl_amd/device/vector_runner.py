@@ -370,9 +370,12 @@ def dueling_layer_sizes(rl_config):
             str(hb.kwargs.get("dueling_kwargs", {}).get("dueling_type", "average")))
 
 
-def why_not_flat_rainbow(env, rl_config) -> str:
+def why_not_flat_rainbow(env, rl_config, admit_noisy: bool = False) -> str:
     """rainbow.Config on flat observations: the shapes srlx_mlpq_create_dueling / srlx_mlpq_train_nstep cover (srlx.h).  Empty string: VectorQEngine can run it
-    (`mlp_config_from`).  `Runner.train()` does not ask yet: `why_not_vector` keeps Rainbow on flat observations on the plugin path."""
+    (`mlp_config_from`).  `Runner.train()` does not ask yet: `why_not_vector` keeps Rainbow on flat observations on the plugin path.
+
+    `admit_noisy=True` puts `enable_noisy_dense` inside the envelope (srlx_mlpq_bind_noisy serves it); the default keeps the answer callers have had so far.
+    The change that routes `Runner.train()` here drops the keyword and admits noisy configs always."""
     space = frame_space(env, rl_config)
     D = flat_dim(space)
     if D is None:
@@ -385,7 +388,7 @@ def why_not_flat_rainbow(env, rl_config) -> str:
         return "the MLP Q-network reads one observation (window_length 1)"
     if not 2 <= env.action_space.n <= 32:
         return "the MLP Q-network serves 2 to 32 actions"
-    if rl_config.enable_noisy_dense:
+    if rl_config.enable_noisy_dense and not admit_noisy:
         return "the MLP Q-network has no noisy dense layers"
     if rl_config.hidden_block.name == "MLP":
         return "the MLP Q-network's Rainbow form ends in a dueling head; an MLP hidden block stays on the plugin path"
@@ -429,7 +432,8 @@ def mlp_config_from(rl_config, env, n_envs: int, seed: int):
     head = {}
     if engine_kind(rl_config) == "rainbow":
         ins, hid, units, dtype = dueling_layer_sizes(rl_config)
-        head = dict(dueling_units=units, dueling_type=dtype, multisteps=int(rl_config.multisteps), retrace_h=float(rl_config.retrace_h))
+        head = dict(dueling_units=units, dueling_type=dtype, multisteps=int(rl_config.multisteps), retrace_h=float(rl_config.retrace_h),
+                    enable_noisy_dense=bool(rl_config.enable_noisy_dense))
     else:
         ins, hid = mlp_layer_sizes(rl_config)
     return VectorQConfig(

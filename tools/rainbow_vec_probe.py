@@ -1,7 +1,8 @@
 """Rainbow on CartPole-v1 on the MLP Q-network engine (device/mlpq.py:VectorQEngine with a dueling head and n-step items), next to the plugin path's Rainbow and
 to the DQN engine at the same lane count.  `Runner.train()` does not route Rainbow on flat observations to the engine yet, so the engine runs are driven here:
 E = 1024 lanes of the device CartPole, 32 updates per lock-step (one per 32 env steps, tools/dqn_vec_probe.py's ratio), the update replayed from its captured
-graph.  Configs: rainbow.Config() (dueling (512,), n = 3, proportional replay) and the same with the dueling block (64, 64); DQN with the hidden block (64, 64).
+graph.  Configs: rainbow.Config() (dueling (512,), n = 3, proportional replay), the same with the dueling block (64, 64), the same with `enable_noisy_dense`
+(`rainbow_noisy`: NoisyLinear head, greedy acting; next to it the same config on the plugin path); DQN with the hidden block (64, 64).
 Prints one JSON line and writes it to profiles/rainbow_vec_probe.json: env-steps/s and updates/s of each run, measured over a timed stretch after an untimed warm
 one.  The plugin path runs one environment with one update per step: updates/s is the like-for-like figure.
 
@@ -24,8 +25,8 @@ from simple_distributed_rl_amd.device import vector_runner as vr  # noqa: E402
 LANES, UPDATES_PER_LOCKSTEP = 1024, 32
 
 
-def rainbow_config(layer_sizes=(512,)):
-    rl = rainbow.Config()
+def rainbow_config(layer_sizes=(512,), noisy=False):
+    rl = rainbow.Config(enable_noisy_dense=noisy)
     rl.hidden_block.set_dueling_network(layer_sizes)
     rl.memory.capacity, rl.memory.warmup_size = 100_000, 2048
     return rl
@@ -46,7 +47,7 @@ def run_engine(rl_config, seconds: float):
     runner.set_device("cuda:0")
     runner.setup_rl_config()
     if vr.engine_kind(runner.rl_config) == "rainbow":
-        why = vr.why_not_flat_rainbow(runner.env, runner.rl_config)
+        why = vr.why_not_flat_rainbow(runner.env, runner.rl_config, admit_noisy=True)
         assert why == "", why
     eng = VectorQEngine(vr.mlp_config_from(runner.rl_config, runner.env, LANES, 0), 0)
     while eng.replay.is_warmup_needed():
@@ -63,6 +64,7 @@ def run_engine(rl_config, seconds: float):
     dt = time.perf_counter() - t0
     info = eng.info()
     return {"path": "device", "lanes": LANES, "updates_per_lockstep": UPDATES_PER_LOCKSTEP, "multisteps": eng.cfg.multisteps, "dueling_units": eng.cfg.dueling_units,
+            "noisy": bool(eng.cfg.enable_noisy_dense),
             "trunk": list(eng.cfg.in_sizes + eng.cfg.hidden_sizes), "seconds": round(dt, 3), "env_steps_per_s": round((eng.total_env_steps - s0) / dt),
             "updates_per_s": round((eng.train_count - u0) / dt, 1), "loss": info["loss"]}
 
@@ -80,8 +82,8 @@ def run_plugin(rl_config, seconds: float):
             "updates_per_s": round(st.train_count / dt, 1)}
 
 
-def plugin_config():
-    rl = rainbow.Config()
+def plugin_config(noisy=False):
+    rl = rainbow.Config(enable_noisy_dense=noisy)
     rl.memory.warmup_size = 500
     return rl
 
@@ -91,6 +93,8 @@ RUNS = {
     "rainbow_64x64": lambda s: run_engine(rainbow_config((64, 64)), s),
     "dqn_64x64": lambda s: run_engine(dqn_config(), s),
     "rainbow_plugin": lambda s: run_plugin(plugin_config(), s),
+    "rainbow_noisy": lambda s: run_engine(rainbow_config((512,), noisy=True), s),
+    "rainbow_noisy_plugin": lambda s: run_plugin(plugin_config(noisy=True), s),
 }
 
 
