@@ -498,6 +498,83 @@ int srlx_ppo_cat_adam(int obs_dim, int n_actions, float *d_params, float *d_grad
                       double lr, double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * What a ppo.Config asks of the engine beyond the network (srl/algorithms/ppo/config.py:43-110): a learning-rate schedule, the
+ * batch baselines of the advantage, reward / state clips and the action rescale.  All of it stays on the device: the update's
+ * HIP graph is captured once and follows the schedule by itself.
+ *   srlx_lr_schedule_t     : LRSchedulerConfig (srl/rl/schedulers/lr_scheduler.py:5-140) as plain data: kind, decay_steps,
+ *       decay_rate, min_lr, up to SRLX_LR_MAX_BOUNDARIES piecewise boundaries with one more value than boundaries.
+ *   srlx_lr_factor         : HOST arithmetic (no device needed): *out = the multiplier of `lr` at optimiser step `step` (0-based),
+ *       LRSchedulerConfig.factor restated -- step: rate ** (step // decay_steps); exp: rate ** (step / decay_steps); cosine:
+ *       (1 - a) / 2 (1 + cos(pi min(step, decay_steps) / decay_steps)) + a, a = min_lr / lr; piecewise: values[#{b: step > b}] / lr;
+ *       warmup_steps is not part of `factor`.  float64.  SRLX_ERR_INVALID: unknown kind, decay_steps <= 0, too many boundaries, lr <= 0.
+ *   srlx_ppo_net_adam_sched / srlx_ppo_cat_adam_sched : srlx_ppo_*_adam with the rate lr * factor(schedule, d_step[0], lr), evaluated
+ *       inside the launch from the step count it reads from device memory (the kernel's integer power for "step" is within a few ulp
+ *       of pow()): optimiser step k (0-based) runs at factor(k), as `optimizer.step(); lr_scheduler.step()` under a LambdaLR does.
+ *       srlx_ppo_*_adam is the constant schedule of the same kernel (its instantiation without the schedule's code and arguments; a constant
+ *       srlx_lr_schedule_t launches that one too): bit for bit.
+ *   srlx_ppo_adv_baseline  : baseline_type "ave" / "std" / "normal" (ppo.py:222-233) over ONE minibatch: mean and POPULATION standard
+ *       deviation of b_adv[rows[0 .. minibatch)] (two passes, float64 sums in a fixed order: deterministic), then d_out[rows[i]] =
+ *       adv - mean (SRLX_PPO_BASELINE_AVE), adv / (std + 1e-8) (_STD), (adv - mean) / (std + 1e-8) (_NORMAL) as float32; d_out is a second
+ *       [T x E] buffer, entries outside `rows` are not touched.  Up to 16 workgroups that each compute the whole statistics (no grid-wide exchange) and
+ *       transform their own slice.  The minibatch launch then
+ *       takes d_out as its d_b_adv, while d_b_v_target keeps reading the untouched advantages.
+ *   srlx_ppo_env_opts_t    : the rollout's options; NULL = all off.  reward clip: the clipped reward goes to b_rew and the GAE
+ *       records, episode_return / finished keep the raw reward (ppo.py:374-379 clips what the trainer sees); state clip: every
+ *       observation row the network reads and every row of b_obs, the first included (env_obs is written back clipped: the clip is
+ *       idempotent), never the environment's state; action rescale (Normal head only): the environment's step receives
+ *       action * action_scale + action_offset (a multiply, then an add), b_act / b_logp keep the policy's action (ppo.py:336).
+ *   srlx_ppo_net_rollout_ex / srlx_ppo_cat_rollout_ex : srlx_ppo_*_rollout with these options; the plain entry points are the
+ *       all-off case of the same kernel (instantiated without the options' code, which an all-off struct launches too): bit for bit.
+ * ------------------------------------------------------------------------------------------------ */
+#define SRLX_LR_CONSTANT 0
+#define SRLX_LR_STEP 1
+#define SRLX_LR_EXP 2
+#define SRLX_LR_COSINE 3
+#define SRLX_LR_PIECEWISE 4
+#define SRLX_LR_MAX_BOUNDARIES 8
+typedef struct {
+    int32_t kind;         /* SRLX_LR_* */
+    int32_t n_boundaries; /* piecewise: 0 .. SRLX_LR_MAX_BOUNDARIES */
+    int64_t decay_steps;
+    double decay_rate;
+    double min_lr;
+    int64_t boundaries[SRLX_LR_MAX_BOUNDARIES];
+    double values[SRLX_LR_MAX_BOUNDARIES + 1]; /* learning rates (not factors), n_boundaries + 1 of them */
+} srlx_lr_schedule_t;
+
+#define SRLX_PPO_BASELINE_AVE 1
+#define SRLX_PPO_BASELINE_STD 2
+#define SRLX_PPO_BASELINE_NORMAL 3
+
+typedef struct {
+    int32_t reward_clip; /* != 0: on */
+    float reward_lo, reward_hi;
+    int32_t state_clip;
+    float state_lo, state_hi;
+    float action_scale, action_offset; /* (1, 0): off */
+} srlx_ppo_env_opts_t;
+
+int srlx_lr_factor(const srlx_lr_schedule_t *schedule, int64_t step, double lr, double *out);
+int srlx_ppo_net_adam_sched(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq,
+                            int64_t *d_step, double lr, const srlx_lr_schedule_t *schedule, double beta1, double beta2, double eps,
+                            double max_grad_norm, double grad_scale, void *stream);
+int srlx_ppo_cat_adam_sched(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq,
+                            int64_t *d_step, double lr, const srlx_lr_schedule_t *schedule, double beta1, double beta2, double eps,
+                            double max_grad_norm, double grad_scale, void *stream);
+int srlx_ppo_adv_baseline(int64_t minibatch, const int64_t *d_rows, const float *d_b_adv, int mode, float *d_out, void *stream);
+int srlx_ppo_net_rollout_ex(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state,
+                            int32_t *d_step_in_episode, float *d_env_obs, int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter,
+                            uint64_t act_seed, int64_t *d_act_counter, double log_scale_min, double log_scale_max, double discount,
+                            double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
+                            uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
+                            const srlx_ppo_env_opts_t *opts, void *stream);
+int srlx_ppo_cat_rollout_ex(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps,
+                            int32_t *d_episodes, float *d_env_obs, int64_t max_steps, uint64_t env_seed, uint64_t act_seed,
+                            int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act, float *d_b_logp,
+                            float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return,
+                            float *d_finished, const srlx_ppo_env_opts_t *opts, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Never-Give-Up intrinsic reward + Agent57_light priorities
  *
  * srlx_ngu_t: one bounded episodic memory per environment, [E][emb_dim][capacity] float32 in HBM

@@ -186,6 +186,14 @@ SIGNATURES = {
                                      c_p]),
     "srlx_ppo_cat_minibatch": (c_int, [c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f64, c_int, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p]),
     "srlx_ppo_cat_adam": (c_int, [c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_p]),
+    "srlx_lr_factor": (c_int, [c_p, c_i64, c_f64, ctypes.POINTER(c_f64)]),
+    "srlx_ppo_net_adam_sched": (c_int, [c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f64, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_p]),
+    "srlx_ppo_cat_adam_sched": (c_int, [c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f64, c_p, c_f64, c_f64, c_f64, c_f64, c_f64, c_p]),
+    "srlx_ppo_adv_baseline": (c_int, [c_i64, c_p, c_p, c_int, c_p, c_p]),
+    "srlx_ppo_net_rollout_ex": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_u64, c_p, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p, c_p]),
+    "srlx_ppo_cat_rollout_ex": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_u64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p]),
     "srlx_ngu_create": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_int, c_f64, c_f64, c_f64, c_int]),
     "srlx_ngu_destroy": (c_int, [c_p]),
     "srlx_ngu_reset": (c_int, [c_p, c_p]),
@@ -227,6 +235,56 @@ SIGNATURES = {
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4
 PRIO_EST_F32 = 5
+
+
+# ---- PPO: plain-data arguments of srlx.h -----------------------------------------------------------------------------
+LR_CONSTANT, LR_STEP, LR_EXP, LR_COSINE, LR_PIECEWISE = range(5)
+LR_MAX_BOUNDARIES = 8
+LR_KINDS = {"": LR_CONSTANT, "step": LR_STEP, "exp": LR_EXP, "cosine": LR_COSINE, "piecewise": LR_PIECEWISE}
+PPO_BASELINE_MODES = {"ave": 1, "std": 2, "normal": 3}
+
+
+class LRSchedule(ctypes.Structure):
+    """srlx_lr_schedule_t"""
+    _fields_ = [("kind", ctypes.c_int32), ("n_boundaries", ctypes.c_int32), ("decay_steps", c_i64), ("decay_rate", c_f64), ("min_lr", c_f64),
+                ("boundaries", c_i64 * LR_MAX_BOUNDARIES), ("values", c_f64 * (LR_MAX_BOUNDARIES + 1))]
+
+
+class PPOEnvOpts(ctypes.Structure):
+    """srlx_ppo_env_opts_t"""
+    _fields_ = [("reward_clip", ctypes.c_int32), ("reward_lo", ctypes.c_float), ("reward_hi", ctypes.c_float), ("state_clip", ctypes.c_int32),
+                ("state_lo", ctypes.c_float), ("state_hi", ctypes.c_float), ("action_scale", ctypes.c_float), ("action_offset", ctypes.c_float)]
+
+
+def lr_schedule(cfg) -> LRSchedule:
+    """LRSchedulerConfig (rl/schedulers/lr_scheduler.py) -> srlx_lr_schedule_t.  Raises for what `factor` would not run either: an unknown type, a piecewise
+    schedule with more than 8 boundaries or without one more value than boundaries."""
+    kind = LR_KINDS.get(cfg.schedule_type)
+    if kind is None:
+        raise ValueError(f"LRSchedulerConfig.schedule_type {cfg.schedule_type!r}: libsrlx knows {sorted(LR_KINDS)}")
+    s = LRSchedule(kind=kind, n_boundaries=0, decay_steps=int(cfg.decay_steps), decay_rate=float(cfg.decay_rate), min_lr=float(cfg.min_lr))
+    if kind == LR_PIECEWISE:
+        b, v = list(cfg.piecewise_boundaries), list(cfg.piecewise_values)
+        if len(b) > LR_MAX_BOUNDARIES:
+            raise ValueError(f"a piecewise schedule of {len(b)} boundaries: libsrlx takes at most {LR_MAX_BOUNDARIES}")
+        if len(v) != len(b) + 1:
+            raise ValueError("a piecewise schedule has one more value than boundaries")
+        s.n_boundaries = len(b)
+        for i, x in enumerate(b):
+            s.boundaries[i] = int(x)
+        for i, x in enumerate(v):
+            s.values[i] = float(x)
+    elif kind != LR_CONSTANT and s.decay_steps <= 0:
+        raise ValueError("LRSchedulerConfig.decay_steps must be positive")
+    return s
+
+
+def lr_factor(schedule: LRSchedule, step: int, lr: float) -> float:
+    """srlx_lr_factor: host arithmetic, no device needed."""
+    out = c_f64(0.0)
+    check(lib().srlx_lr_factor(ctypes.byref(schedule), step, lr, ctypes.byref(out)))
+    return out.value
+
 
 _lib = None
 _lock = threading.Lock()

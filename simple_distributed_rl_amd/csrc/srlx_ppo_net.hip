@@ -10,6 +10,10 @@
 //   k_ppo_reduce    : partial gradients -> the flat gradient (fixed order: deterministic) + the three reported losses.
 //   k_ppo_adam      : global-norm clip (:240-241, torch.nn.utils.clip_grad_norm_) + Adam (torch.optim.Adam) over the flat parameter vector, one workgroup; between
 //                     k_ppo_reduce and k_ppo_adam sits the data-parallel job's ONE all-reduce of the flat gradient (device/ppo.py).
+//   k_ppo_adv_baseline : baseline_type "ave" / "std" / "normal" (:222-233) over one minibatch's advantages, in front of k_ppo_minibatch: one workgroup, two float64 passes.
+// What a ppo.Config asks beyond the network is compiled in on demand: k_ppo_adam<SCHED> evaluates a learning-rate schedule (srlx_lr_math.h) from the step count it reads
+// from device memory, k_ppo_rollout<Task, EX> clips rewards / observations and rescales the action (srlx_ppo_env_opts_t); the <false> instantiations are the kernels
+// as they were, and what a constant schedule / an all-off options struct launches.
 // The same four kernels serve a CATEGORICAL head (template parameter CAT; discrete actions, ppo.py:316-324): in -> 64 -> 64 -> {64 -> V, 64 -> n logits}, parameters
 // ... wp, bp, wlogit [n][64], blogit [n].  The n <= 8 logit rows take the 2 * A_MAX = 8 policy-head slots the Normal head's loc / log_scale rows take (slot k: k < 4
 // in wloc's place, else in wls's), so the LDS image, the heads / seeds tables and the whole backward pass are shared; what differs is the parameter layout, the
@@ -17,8 +21,11 @@
 // float32 throughout, fmaf accumulation in ascending input order; the per-sample policy / loss / environment arithmetic is srlx_ppo_math.h, shared with the
 // one-purpose kernels of srlx_ppo.hip.  Parameters are ONE flat float32 vector in torch's `ActorCritic.parameters()` order (weights [out][in]).
 // Bounds: VALU (f32 FMA) -- about 76 kFLOP per sample and update (forward + backward), 25 kFLOP per environment step; HBM traffic is the buffers only.
+#include <type_traits>
+
 #include "srlx_adam_math.h"
 #include "srlx_common.h"
+#include "srlx_lr_math.h"
 #include "srlx_ppo_math.h"
 
 namespace {
@@ -262,7 +269,10 @@ struct RolloutArgs {
     float *b_logp, *b_val /*[T][E]*/, *b_rew;
     u8 *b_done;
     float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
+    srlx_ppo_env_opts_t opts;  // reward / state clips, action rescale (srlx.h); all off: the arithmetic of the plain entry points
 };
+constexpr srlx_ppo_env_opts_t kEnvOptsOff = {0, 0.f, 0.f, 0, 0.f, 0.f, 1.f, 0.f};
+__host__ __device__ inline bool rescales(const srlx_ppo_env_opts_t &o) { return o.action_scale != 1.f || o.action_offset != 0.f; }
 
 __global__ void k_advance2(i64 *c0, i64 *c1, i64 n) {
     c0[0] += n;
@@ -302,6 +312,7 @@ struct PendulumNormal {
         }
     }
     // policy sample + log-probability (ppo.py:316-339) -> b_act / b_logp [t][eg]; then the environment's step
+    template <bool EX>
     static __device__ __forceinline__ void step(const RolloutArgs<PendulumNormal> &a, Lane &s, const float *hd, const float *zbuf, i64 t, u64, i64 eg, float (&ob)[OBS], float &rw, u8 &dn) {
         const int A = a.A, tid = threadIdx.x;
         float act0 = 0.f;
@@ -312,6 +323,7 @@ struct PendulumNormal {
             a.b_logp[(t * a.E + eg) * A + d] = lp;
             if (d == 0) act0 = ac;
         }
+        if (EX && rescales(a.opts)) act0 = act0 * a.opts.action_scale + a.opts.action_offset;  // ppo.py:336: [-1, 1] onto the environment's bounds (no contraction: two roundings)
         srlxp::pendulum_one(s.th, s.thd, s.tstep, act0, a.episode_len, a.env_seed, s.c_env + (u64)t, eg, ob[0], ob[1], ob[2], rw, dn);
     }
 };
@@ -346,6 +358,7 @@ struct CartPoleCategorical {
     };
     static __device__ __forceinline__ void draw(const RolloutArgs<CartPoleCategorical> &, float *, u64, i64) {}  // (one uniform per step, drawn in it)
     // categorical sample + log-probability (ppo.py:316-324), the environment's step; then b_act / b_logp [t][eg]
+    template <bool EX>
     static __device__ __forceinline__ void step(const RolloutArgs<CartPoleCategorical> &a, Lane &s, const float *hd, const float *, i64 t, u64 c_act, i64 eg, float (&ob)[OBS], float &rw,
                                                 u8 &dn) {
         int ac;
@@ -378,7 +391,8 @@ __device__ __forceinline__ void gae_rows(const float *t_rew, const float *t_val,
     }
 }
 
-template <class Task>
+// EX: with the options of a.opts (reward / state clips, action rescale); false: no trace of them in the code -- the rollout as it was before they existed
+template <class Task, bool EX>
 __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
     constexpr int OBS = Task::OBS;
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -397,7 +411,8 @@ __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
         lane.load(a.env, eg);
         er = a.episode_return[eg];
         for (int c = 0; c < OBS; c++) {
-            const float v = a.env_obs[OBS * eg + c];
+            float v = a.env_obs[OBS * eg + c];
+            if (EX && a.opts.state_clip) v = srlxp::clampf(v, a.opts.state_lo, a.opts.state_hi);
             L.x[tid * OBS_MAX + c] = v;
             a.b_obs[OBS * eg + c] = v;
         }
@@ -411,7 +426,15 @@ __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
             const float *hd = L.heads + tid * (1 + 2 * A_MAX);
             float ob[OBS], rw;
             u8 dn;
-            Task::step(a, lane, hd, zbuf, t, c_act, eg, ob, rw, dn);
+            Task::template step<EX>(a, lane, hd, zbuf, t, c_act, eg, ob, rw, dn);
+            const float raw = rw;  // (the episode's return counts the raw reward)
+            if constexpr (EX) {
+                if (a.opts.reward_clip) rw = srlxp::clampf(rw, a.opts.reward_lo, a.opts.reward_hi);
+                if (a.opts.state_clip) {
+#pragma unroll
+                    for (int c = 0; c < OBS; c++) ob[c] = srlxp::clampf(ob[c], a.opts.state_lo, a.opts.state_hi);
+                }
+            }
             const i64 k = t * a.E + eg;
             a.b_val[k] = hd[0];
             a.b_rew[k] = rw;
@@ -420,7 +443,7 @@ __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
 #pragma unroll
             for (int c = 0; c < OBS; c++) bo[c] = ob[c], L.x[tid * OBS_MAX + c] = ob[c];
             t_rew[t * RE + tid] = rw, t_val[t * RE + tid] = hd[0], t_done[t * RE + tid] = dn ? 1.f : 0.f;
-            er += rw;
+            er += raw;
             if (dn) fin_sum += er, fin_cnt += 1.f, er = 0.f;
         }
         __syncthreads();
@@ -746,8 +769,11 @@ __global__ void __launch_bounds__(256) k_ppo_reduce(int n_wg, int P, int stride,
 }
 
 // The gradient scaled by grad_scale (1 / world size behind the data-parallel all-reduce); global-norm clip; Adam.
+// SCHED: the rate is lr * factor(schedule, steps taken) (srlx_lr_math.h); false: lr as it is, and no trace of the schedule in the code or the arguments.
+struct NoSchedule {};
+template <bool SCHED>
 __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ params, const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v, i64 *__restrict__ step,
-                                                    double lr, double b1, double b2, double eps, float max_norm, float grad_scale) {
+                                                    double lr, std::conditional_t<SCHED, srlx_lr_schedule_t, NoSchedule> sched, double b1, double b2, double eps, float max_norm, float grad_scale) {
     // ceil(P / 1024) workgroups: every one computes the WHOLE vector's norm (52 KB out of L2, the same sums in the same order everywhere), then steps its own 1 024
     // parameters -- no grid-wide exchange for the clip factor; the last workgroup out (step[1]: an arrival counter) advances the step count.
     __shared__ float red[1024];
@@ -757,6 +783,12 @@ __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ pa
     const bool in_mine = mine < P;
     float pp = 0.f, mm = 0.f, vv = 0.f;
     if (in_mine) pp = params[mine], mm = m[mine], vv = v[mine];
+    // The rate of THIS step, evaluated by one lane beside the norm pass and handed over through LDS behind the reduction's barriers -- a captured graph follows the
+    // schedule from the step count alone.
+    __shared__ double lr_shared;  // (SCHED only)
+    if constexpr (SCHED) {
+        if (tid == 1023) lr_shared = lr * srlx::lr_factor(sched, steps_taken, lr);
+    }
     float g[kPer];
     float ss = 0.f;
 #pragma unroll
@@ -774,7 +806,9 @@ __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ pa
     }
     const float clip = max_norm > 0.f ? fminf(max_norm / (sqrtf(red[0]) + 1e-6f), 1.0f) : 1.0f;  // torch.nn.utils.clip_grad_norm_
     if (in_mine) {
-        const srlx::AdamCoef c = srlx::adam_coef(lr, b1, b2, eps, steps_taken);
+        double lr_now = lr;
+        if constexpr (SCHED) lr_now = lr_shared;
+        const srlx::AdamCoef c = srlx::adam_coef(lr_now, b1, b2, eps, steps_taken);
         float gc = 0.f;
 #pragma unroll
         for (int k = 0; k < kPer; k++)
@@ -790,6 +824,62 @@ __global__ void __launch_bounds__(1024) k_ppo_adam(int P, float *__restrict__ pa
             step[1] = 0;
             step[0] = steps_taken + 1;
         }
+    }
+}
+
+// baseline_type "ave" / "std" / "normal" (ppo.py:222-233) over one minibatch of at most E T / minibatches elements.  Up to 16 workgroups, and EVERY one computes the
+// whole minibatch's statistics (the same sums in the same order everywhere: no grid-wide exchange, as k_ppo_adam does for the norm), then transforms its own
+// slice -- measured at 32 768 elements: one workgroup making every pass from HBM 90.5 us, with the gather staged in LDS 63.6 us, and what is left is one CU's
+// address pipe working through 32 768 scattered reads and 32 768 scattered writes plus the float64 divisions; the slices divide the writes and the divisions.
+// The gather adv[rows[i]] is made ONCE per workgroup, 16 elements per lane in flight at a time, into LDS (the
+// first kBaseStage = 32 768 elements: 128 KiB; what a larger minibatch has beyond them is read again from HBM in every pass), and the three passes -- the sum, the sum
+// of squared deviations from the mean (no cancellation at mean >> spread), the transform -- read it there.  Each lane adds its elements i = tid, tid + 1024, ... in
+// ascending order into a float64, the 1 024 lane sums meet in a fixed tree: deterministic.  The population deviation, and 1e-8 beside it, as numpy's in the
+// reference.  The quotient is formed in float64 and rounded to float32 once.
+constexpr i64 kBaseStage = 32 * 1024;
+__device__ __forceinline__ double block_sum_1024(double x, double *red) {
+    const int tid = threadIdx.x;
+    __syncthreads();  // (the previous use of `red` is over; the staged values are written)
+    red[tid] = x;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ void __launch_bounds__(1024) k_ppo_adv_baseline(i64 mb, const i64 *__restrict__ rows, const float *__restrict__ adv, int mode, float *__restrict__ out) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    float *xs = reinterpret_cast<float *>(lds_raw);  // [min(mb, kBaseStage)]
+    __shared__ double red[1024];
+    const int tid = threadIdx.x;
+    const i64 staged = mb < kBaseStage ? mb : kBaseStage;
+    for (i64 base = 0; base < staged; base += 16 * 1024) {
+        i64 r[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const i64 i = base + tid + 1024 * k;
+            r[k] = i < staged ? rows[i] : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (r[k] >= 0) xs[base + tid + 1024 * k] = adv[r[k]];
+    }
+    __syncthreads();  // (the last pass reads what other lanes staged)
+    auto at = [&](i64 i) { return i < staged ? xs[i] : adv[rows[i]]; };
+    double s = 0.0;
+    for (i64 i = tid; i < mb; i += 1024) s += (double)at(i);
+    const double mean = block_sum_1024(s, red) / (double)mb;
+    double q = 0.0;
+    for (i64 i = tid; i < mb; i += 1024) {
+        const double d = (double)at(i) - mean;
+        q += d * d;
+    }
+    const double sd = sqrt(block_sum_1024(q, red) / (double)mb) + 1e-8;
+    for (i64 i = (i64)blockIdx.x * 1024 + tid; i < mb; i += (i64)gridDim.x * 1024) {  // this workgroup's slice
+        const double a = (double)at(i);
+        out[rows[i]] = (float)(mode == SRLX_PPO_BASELINE_AVE ? a - mean : (mode == SRLX_PPO_BASELINE_STD ? a / sd : (a - mean) / sd));
     }
 }
 
@@ -817,6 +907,17 @@ int rollout_max_horizon(int A) {  // what fits the workgroup's LDS beside weight
     return (int)(t < 1024 ? t : 1024);
 }
 
+template <class Task, bool EX>
+int launch_rollout_kernel(const RolloutArgs<Task> &a, size_t lds, void *stream) {
+    static size_t lds_set = 0;
+    if (lds > lds_set) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout<Task, EX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set = lds;
+    }
+    hipLaunchKernelGGL((k_ppo_rollout<Task, EX>), dim3((unsigned)(a.E / RE)), dim3(256), lds, (hipStream_t)stream, a);
+    return SRLX_OK;
+}
+
 // name: the entry point's, for its error texts
 template <class Task>
 int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream) {
@@ -826,14 +927,14 @@ int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream) {
     SRLX_REQUIRE(a.params && Task::env_ok(a.env) && a.env_obs && a.act_counter && a.b_obs && a.b_act && a.b_logp && a.b_val && a.b_rew && a.b_done && a.b_adv && a.last_v &&
                      a.episode_return && a.finished,
                  "%s: NULL argument", name);
+    SRLX_REQUIRE((!a.opts.reward_clip || a.opts.reward_lo <= a.opts.reward_hi) && (!a.opts.state_clip || a.opts.state_lo <= a.opts.state_hi), "%s: a clip's lower bound exceeds its upper bound",
+                 name);
+    SRLX_REQUIRE(!Task::CAT || !rescales(a.opts), "%s: the action rescale belongs to the Normal head", name);
     const size_t lds = sizeof(FwdLds) + (size_t)a.T * RE * Task::records(a.A) * sizeof(float);
     SRLX_REQUIRE(lds <= kLdsMax, "%s: horizon too long for the workgroup's LDS", name);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout<Task>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL(k_ppo_rollout<Task>, dim3((unsigned)(a.E / RE)), dim3(256), lds, (hipStream_t)stream, a);
+    const bool ex = a.opts.reward_clip || a.opts.state_clip || rescales(a.opts);  // all off: the kernel without the options' code
+    const int st = ex ? launch_rollout_kernel<Task, true>(a, lds, stream) : launch_rollout_kernel<Task, false>(a, lds, stream);
+    if (st != SRLX_OK) return st;
     Task::advance(a.env, a.act_counter, a.T, (hipStream_t)stream);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
@@ -870,10 +971,18 @@ int launch_minibatch(MbArgs &a, float *d_grad, float *d_losses, void *stream) {
     return SRLX_OK;
 }
 
-int launch_adam(int P, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2, double eps,
-                double max_grad_norm, double grad_scale, void *stream) {
-    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((P + 1023) / 1024)), dim3(1024), 0, (hipStream_t)stream, P, d_params, d_grad, d_exp_avg, d_exp_avg_sq, (i64 *)d_step, lr, beta1, beta2, eps,
-                       (float)max_grad_norm, (float)grad_scale);
+constexpr srlx_lr_schedule_t kLrConstant = {SRLX_LR_CONSTANT, 0, 0, 0.0, 0.0, {}, {}};
+
+int launch_adam(const char *name, int P, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, const srlx_lr_schedule_t *sched, double beta1,
+                double beta2, double eps, double max_grad_norm, double grad_scale, void *stream) {
+    SRLX_REQUIRE(sched && srlx::lr_schedule_ok(*sched) && (sched->kind == SRLX_LR_CONSTANT || lr > 0), "%s: bad learning-rate schedule", name);
+    const dim3 grid((unsigned)((P + 1023) / 1024)), block(1024);
+    if (sched->kind == SRLX_LR_CONSTANT)  // the kernel without the schedule's code and arguments
+        hipLaunchKernelGGL(k_ppo_adam<false>, grid, block, 0, (hipStream_t)stream, P, d_params, d_grad, d_exp_avg, d_exp_avg_sq, (i64 *)d_step, lr, NoSchedule{}, beta1, beta2, eps,
+                           (float)max_grad_norm, (float)grad_scale);
+    else
+        hipLaunchKernelGGL(k_ppo_adam<true>, grid, block, 0, (hipStream_t)stream, P, d_params, d_grad, d_exp_avg, d_exp_avg_sq, (i64 *)d_step, lr, *sched, beta1, beta2, eps,
+                           (float)max_grad_norm, (float)grad_scale);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
@@ -891,14 +1000,23 @@ int srlx_ppo_net_forward(int64_t n, int obs_dim, int action_dim, const float *d_
 
 int srlx_ppo_net_rollout_max_horizon(int action_dim) { return rollout_max_horizon<PendulumNormal>(action_dim); }
 
+int srlx_ppo_net_rollout_ex(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state, int32_t *d_step_in_episode, float *d_env_obs,
+                            int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter, uint64_t act_seed, int64_t *d_act_counter, double log_scale_min,
+                            double log_scale_max, double discount, double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
+                            uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished, const srlx_ppo_env_opts_t *opts, void *stream) {
+    const RolloutArgs<PendulumNormal> a{n_envs, horizon, action_dim, d_params, d_env_obs, episode_len, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                        {d_env_state, d_step_in_episode, d_env_counter, (float)log_scale_min, (float)log_scale_max}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv,
+                                        d_last_v, d_episode_return, d_finished, opts ? *opts : kEnvOptsOff};
+    return launch_rollout("ppo_net_rollout", a, stream);
+}
+
 int srlx_ppo_net_rollout(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state, int32_t *d_step_in_episode, float *d_env_obs,
                          int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter, uint64_t act_seed, int64_t *d_act_counter, double log_scale_min,
                          double log_scale_max, double discount, double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
                          uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished, void *stream) {
-    const RolloutArgs<PendulumNormal> a{n_envs, horizon, action_dim, d_params, d_env_obs, episode_len, (u64)env_seed, (u64)act_seed, d_act_counter,
-                                        {d_env_state, d_step_in_episode, d_env_counter, (float)log_scale_min, (float)log_scale_max}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv,
-                                        d_last_v, d_episode_return, d_finished};
-    return launch_rollout("ppo_net_rollout", a, stream);
+    return srlx_ppo_net_rollout_ex(n_envs, horizon, action_dim, d_params, d_env_state, d_step_in_episode, d_env_obs, episode_len, env_seed, d_env_counter, act_seed, d_act_counter,
+                                   log_scale_min, log_scale_max, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return,
+                                   d_finished, nullptr, stream);
 }
 
 int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int action_dim, const float *d_params, const float *d_b_obs, const float *d_b_act,
@@ -924,7 +1042,36 @@ int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) { return partials_
 int srlx_ppo_net_adam(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
     SRLX_REQUIRE(geometry_ok<false>(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam: bad argument");
-    return launch_adam(param_count<false>(obs_dim, action_dim), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
+    return launch_adam("ppo_net_adam", param_count<false>(obs_dim, action_dim), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, &kLrConstant, beta1, beta2, eps, max_grad_norm,
+                       grad_scale, stream);
+}
+
+int srlx_ppo_net_adam_sched(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr,
+                            const srlx_lr_schedule_t *schedule, double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, void *stream) {
+    SRLX_REQUIRE(geometry_ok<false>(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam_sched: bad argument");
+    return launch_adam("ppo_net_adam_sched", param_count<false>(obs_dim, action_dim), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, schedule, beta1, beta2, eps, max_grad_norm,
+                       grad_scale, stream);
+}
+
+int srlx_lr_factor(const srlx_lr_schedule_t *schedule, int64_t step, double lr, double *out) {
+    SRLX_REQUIRE(schedule && out && srlx::lr_schedule_ok(*schedule) && step >= 0 && lr > 0, "lr_factor: bad argument (kind, decay_steps > 0, at most 8 boundaries, step >= 0, lr > 0)");
+    *out = srlx::lr_factor(*schedule, step, lr);
+    return SRLX_OK;
+}
+
+int srlx_ppo_adv_baseline(int64_t minibatch, const int64_t *d_rows, const float *d_b_adv, int mode, float *d_out, void *stream) {
+    SRLX_REQUIRE(minibatch > 0 && d_rows && d_b_adv && d_out && d_out != d_b_adv, "ppo_adv_baseline: bad argument (the output is a second buffer)");
+    SRLX_REQUIRE(mode >= SRLX_PPO_BASELINE_AVE && mode <= SRLX_PPO_BASELINE_NORMAL, "ppo_adv_baseline: mode is SRLX_PPO_BASELINE_AVE / _STD / _NORMAL");
+    const size_t lds = (size_t)(minibatch < kBaseStage ? minibatch : kBaseStage) * sizeof(float);
+    static size_t lds_set = 0;
+    if (lds > lds_set) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_adv_baseline, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set = lds;
+    }
+    const int64_t wgs = (minibatch + 1023) / 1024;
+    hipLaunchKernelGGL(k_ppo_adv_baseline, dim3((unsigned)(wgs < 16 ? wgs : 16)), dim3(1024), lds, (hipStream_t)stream, (i64)minibatch, d_rows, d_b_adv, mode, d_out);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
 }
 
 // ---- the categorical head ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -939,13 +1086,22 @@ int srlx_ppo_cat_forward(int64_t n, int obs_dim, int n_actions, const float *d_p
     return launch_forward<true>(n, obs_dim, n_actions, d_params, d_obs, d_v, d_logits, nullptr, stream);
 }
 
+int srlx_ppo_cat_rollout_ex(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps, int32_t *d_episodes, float *d_env_obs,
+                            int64_t max_steps, uint64_t env_seed, uint64_t act_seed, int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act,
+                            float *d_b_logp, float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
+                            const srlx_ppo_env_opts_t *opts, void *stream) {
+    const RolloutArgs<CartPoleCategorical> a{n_envs, horizon, n_actions, d_params, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                             {d_env_state, d_steps, d_episodes}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished,
+                                             opts ? *opts : kEnvOptsOff};
+    return launch_rollout("ppo_cat_rollout", a, stream);
+}
+
 int srlx_ppo_cat_rollout(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps, int32_t *d_episodes, float *d_env_obs,
                          int64_t max_steps, uint64_t env_seed, uint64_t act_seed, int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act,
                          float *d_b_logp, float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
                          void *stream) {
-    const RolloutArgs<CartPoleCategorical> a{n_envs, horizon, n_actions, d_params, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter,
-                                             {d_env_state, d_steps, d_episodes}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished};
-    return launch_rollout("ppo_cat_rollout", a, stream);
+    return srlx_ppo_cat_rollout_ex(n_envs, horizon, n_actions, d_params, d_env_state, d_steps, d_episodes, d_env_obs, max_steps, env_seed, act_seed, d_act_counter, discount, gae_lambda,
+                                   d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished, nullptr, stream);
 }
 
 int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params, const float *d_b_obs, const int32_t *d_b_act,
@@ -969,7 +1125,15 @@ int srlx_ppo_cat_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
 int srlx_ppo_cat_adam(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
     SRLX_REQUIRE(geometry_ok<true>(obs_dim, n_actions) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_cat_adam: bad argument");
-    return launch_adam(param_count<true>(obs_dim, n_actions), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, beta1, beta2, eps, max_grad_norm, grad_scale, stream);
+    return launch_adam("ppo_cat_adam", param_count<true>(obs_dim, n_actions), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, &kLrConstant, beta1, beta2, eps, max_grad_norm,
+                       grad_scale, stream);
+}
+
+int srlx_ppo_cat_adam_sched(int obs_dim, int n_actions, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr,
+                            const srlx_lr_schedule_t *schedule, double beta1, double beta2, double eps, double max_grad_norm, double grad_scale, void *stream) {
+    SRLX_REQUIRE(geometry_ok<true>(obs_dim, n_actions) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_cat_adam_sched: bad argument");
+    return launch_adam("ppo_cat_adam_sched", param_count<true>(obs_dim, n_actions), d_params, d_grad, d_exp_avg, d_exp_avg_sq, d_step, lr, schedule, beta1, beta2, eps, max_grad_norm,
+                       grad_scale, stream);
 }
 
 }  // extern "C"

@@ -24,19 +24,27 @@ on the device, float64 state; `episode_len` is its step limit).  The same three-
 torch-autograd yardstick is log_softmax -> `srlx_ppo_categorical_act` / `srlx_ppo_loss_logpi`.  `export_to` / `load_from` exchange the weights with the PPO plugin's
 `Parameter` (algorithms/ppo.py), so a policy trained here is evaluated through `Runner.evaluate()`.
 
+What a `ppo.Config` asks beyond the network (`vector_runner.ppo_config_from` maps one): `lr_scheduler` -- evaluated INSIDE the clip + Adam launch from the step count in
+device memory (`srlx_ppo_*_adam_sched`), so the captured update graph follows it; `baseline_type` "ave" / "std" / "normal" -- one `srlx_ppo_adv_baseline` launch per
+minibatch in front of the minibatch launch (mean / population deviation of THAT minibatch, as the plugin's trainer normalises the batch it drew); `reward_clip`,
+`state_clip`, `action_scale` / `action_offset` -- inside the one-launch rollout (`srlx_ppo_*_rollout_ex`), with torch ops around the step-wise kernels.  With none of
+them set the engine launches exactly what it launched before they existed.
+
 Data parallel (config 5): `DistributedPPO` gives every rank its own E environments and averages the gradients of
 every minibatch with one all-reduce of the flat ~52 KB gradient vector (latency-bound; RCCL over xGMI) -- the only exchange; with the fused network and RCCL
 it sits INSIDE the captured update graph, between the gradient reduction and the clip + Adam launch.
 """
 import ctypes
 import math
-from dataclasses import dataclass
+import struct
+from dataclasses import dataclass, field
 from typing import Callable, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from simple_distributed_rl_amd import _native as N
+from simple_distributed_rl_amd.rl.schedulers.lr_scheduler import LRSchedulerConfig
 
 
 @dataclass
@@ -67,6 +75,11 @@ class PPODeviceConfig:
     seed: int = 0
     n_actions: int = 0                         # 0: the Normal head on Pendulum; > 0: a categorical head on CartPole (obs_dim 4; action_dim unused; episode_len = max_steps).
     #                                            CartPole has two moves: action 1 pushes right, every other action pushes left -- n_actions 3..8 is accepted, but adds duplicates of "left"
+    lr_scheduler: LRSchedulerConfig = field(default_factory=LRSchedulerConfig)  # constant by default; optimiser step k (0-based) runs at lr * factor(k) (ppo.Config: set_step(2000, 0.01))
+    reward_clip: Optional[Tuple[float, float]] = None  # (lo, hi): what the buffers and GAE see; episode returns keep the raw reward (ppo.py:374-379)
+    state_clip: Optional[Tuple[float, float]] = None   # (lo, hi): every observation the network reads or the buffers keep; never the environment's state
+    action_scale: float = 1.0                  # the Normal head's action reaches the environment as action * action_scale + action_offset (ppo.py:336: [-1, 1] onto
+    action_offset: float = 0.0                 # the action space's bounds; Pendulum: 2 and 0); b_act / b_logp keep the policy's own action
 
 
 class ActorCritic(nn.Module):
@@ -159,8 +172,16 @@ def make_env(cfg: PPODeviceConfig, seed: int, device: torch.device):
     return head_of(cfg).env_cls(cfg.n_envs, cfg.episode_len, seed, device)
 
 
+BASELINES = {"advantage": "advantage", "v": "advantage", "": "none", "none": "none", "ave": "ave", "std": "std", "normal": "normal"}  # ppo.py:222-233 (+ the aliases)
+
+
+def _f32(x: float) -> float:
+    """x rounded to float32 (what a float field of a libsrlx struct holds): the torch ops of the step-wise path clip at the same bounds as the kernels."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
 def _loss_args(cfg):
-    return (int(cfg.baseline_type == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
+    return (int(BASELINES.get(cfg.baseline_type) == "advantage"), int(cfg.surrogate_type == "clip"), cfg.policy_clip_range, int(cfg.enable_value_clip), cfg.value_clip_range,
             cfg.value_loss_weight, cfg.entropy_weight)
 
 
@@ -172,7 +193,7 @@ class NormalPendulumHead:
     def __init__(self, cfg, lib):
         self.size, self.act_shape = cfg.action_dim, (cfg.action_dim,)  # the head's size for libsrlx; b_act / b_logp are [T][E] + act_shape
         self.param_count, self.partials_floats = lib.srlx_ppo_net_param_count, lib.srlx_ppo_net_partials_floats
-        self.adam, self.rollout_max_horizon = lib.srlx_ppo_net_adam, lib.srlx_ppo_net_rollout_max_horizon
+        self.adam, self.adam_sched, self.rollout_max_horizon = lib.srlx_ppo_net_adam, lib.srlx_ppo_net_adam_sched, lib.srlx_ppo_net_rollout_max_horizon
 
     def sample(self, e, loc, ls, action_out, logp_out, deterministic):  # the step-wise path's policy sample + log-probability
         N.check(e.lib.srlx_ppo_normal_act(loc.numel(), N.tptr(loc), N.tptr(ls), e.ls_range[0], e.ls_range[1], e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter),
@@ -186,10 +207,13 @@ class NormalPendulumHead:
 
     def rollout(self, e):  # T steps of everything in ONE launch (csrc/srlx_ppo_net.hip: k_ppo_rollout<PendulumNormal>)
         cfg, env = e.cfg, e.env
-        N.check(e.lib.srlx_ppo_net_rollout(cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len,
-                                           env.seed, N.tptr(env.counter), cfg.seed ^ 0x61637400, N.tptr(e.act_counter), e.ls_range[0], e.ls_range[1], cfg.discount,
-                                           cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done),
-                                           N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns), N.torch_stream_ptr()))
+        args = (cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len, env.seed, N.tptr(env.counter),
+                cfg.seed ^ 0x61637400, N.tptr(e.act_counter), e.ls_range[0], e.ls_range[1], cfg.discount, cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp),
+                N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns))
+        if e.env_opts is None:
+            N.check(e.lib.srlx_ppo_net_rollout(*args, N.torch_stream_ptr()))
+        else:
+            N.check(e.lib.srlx_ppo_net_rollout_ex(*args, ctypes.byref(e.env_opts), N.torch_stream_ptr()))
 
     def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
         v, loc, ls = e.net(obs)
@@ -216,7 +240,7 @@ class CategoricalCartPoleHead:
             raise ValueError("a categorical policy needs at least 2 actions")
         self.size, self.act_shape = cfg.n_actions, ()
         self.param_count, self.partials_floats = lib.srlx_ppo_cat_param_count, lib.srlx_ppo_cat_partials_floats
-        self.adam, self.rollout_max_horizon = lib.srlx_ppo_cat_adam, lib.srlx_ppo_cat_rollout_max_horizon
+        self.adam, self.adam_sched, self.rollout_max_horizon = lib.srlx_ppo_cat_adam, lib.srlx_ppo_cat_adam_sched, lib.srlx_ppo_cat_rollout_max_horizon
 
     def sample(self, e, logits, action_out, logp_out, deterministic):
         N.check(e.lib.srlx_ppo_categorical_act(logits.shape[0], self.size, N.tptr(logits), e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter), int(deterministic),
@@ -230,10 +254,13 @@ class CategoricalCartPoleHead:
 
     def rollout(self, e):  # (csrc/srlx_ppo_net.hip: k_ppo_rollout<CartPoleCategorical>)
         cfg, env = e.cfg, e.env
-        N.check(e.lib.srlx_ppo_cat_rollout(cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes), N.tptr(env.obs),
-                                           env.episode_len, env.seed, cfg.seed ^ 0x61637400, N.tptr(e.act_counter), cfg.discount, cfg.gae_discount, N.tptr(e.b_obs),
-                                           N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v),
-                                           N.tptr(e.episode_return), N.tptr(e.finished_returns), N.torch_stream_ptr()))
+        args = (cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes), N.tptr(env.obs), env.episode_len, env.seed,
+                cfg.seed ^ 0x61637400, N.tptr(e.act_counter), cfg.discount, cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew),
+                N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns))
+        if e.env_opts is None:
+            N.check(e.lib.srlx_ppo_cat_rollout(*args, N.torch_stream_ptr()))
+        else:
+            N.check(e.lib.srlx_ppo_cat_rollout_ex(*args, ctypes.byref(e.env_opts), N.torch_stream_ptr()))
 
     def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
         v, logits = e.net(obs)
@@ -277,6 +304,28 @@ class PPOEngine:
             raise RuntimeError("simple_distributed_rl_amd.device.ppo needs an MI355X: its rollout / GAE / loss arithmetic is libsrlx HIP code (no CPU fallback)")
         if cfg.surrogate_type not in ("clip", ""):
             raise ValueError('surrogate_type must be "clip" or "" (the reference\'s "kl" needs tensorflow_probability, functions.py:95-103)')
+        if cfg.baseline_type not in BASELINES:
+            raise ValueError(f"baseline_type {cfg.baseline_type!r}: the engine serves {sorted(BASELINES)}")
+        self.baseline = BASELINES[cfg.baseline_type]  # "advantage" (inside the loss), "none", or a batch statistic: "ave" / "std" / "normal"
+        for name in ("reward_clip", "state_clip"):
+            c = getattr(cfg, name)
+            if c is not None and not (len(c) == 2 and float(c[0]) <= float(c[1])):
+                raise ValueError(f"{name} is None or (lo, hi) with lo <= hi")
+        self.rescale = (float(cfg.action_scale), float(cfg.action_offset)) != (1.0, 0.0)
+        if self.rescale and head_of(cfg).cat:
+            raise ValueError("action_scale / action_offset belong to the Normal head: a categorical action is an index")
+        self.lr_sched = N.lr_schedule(cfg.lr_scheduler)  # (raises for an unknown type or a piecewise schedule beyond 8 boundaries)
+        self.scheduled = self.lr_sched.kind != N.LR_CONSTANT
+        if self.scheduled and not cfg.lr > 0:
+            raise ValueError("a learning-rate schedule needs lr > 0")
+        # srlx_ppo_env_opts_t for the one-launch rollout (None: the plain entry point); the step-wise path clips at the same float32 bounds
+        self.reward_clip = None if cfg.reward_clip is None else (_f32(cfg.reward_clip[0]), _f32(cfg.reward_clip[1]))
+        self.state_clip = None if cfg.state_clip is None else (_f32(cfg.state_clip[0]), _f32(cfg.state_clip[1]))
+        self.action_map = (_f32(cfg.action_scale), _f32(cfg.action_offset))
+        self.env_opts = None
+        if self.reward_clip or self.state_clip or self.rescale:
+            rc, sc = self.reward_clip or (0.0, 0.0), self.state_clip or (0.0, 0.0)
+            self.env_opts = N.PPOEnvOpts(int(self.reward_clip is not None), rc[0], rc[1], int(self.state_clip is not None), sc[0], sc[1], *self.action_map)
         self.cfg, self.lib = cfg, N.lib()
         self.dev = torch.device(f"cuda:{device}")
         torch.manual_seed(cfg.seed)
@@ -305,6 +354,7 @@ class PPOEngine:
             self.opt = None
         else:
             self.opt = torch.optim.Adam(self.net.parameters(), lr=cfg.lr, capturable=True)
+            self.lr_sch = cfg.lr_scheduler.apply_torch_scheduler(self.opt)  # a LambdaLR over `factor`, as the plugin's trainer (None: constant)
         self.env = make_env(cfg, cfg.seed, self.dev)
         self.ls_range = (math.log(cfg.stable_gradients_scale_range[0]), math.log(cfg.stable_gradients_scale_range[1]))
         E, T, d = cfg.n_envs, cfg.horizon, self.dev
@@ -316,6 +366,7 @@ class PPOEngine:
         self.b_rew = torch.zeros((T, E), **f32)
         self.b_done = torch.zeros((T, E), dtype=torch.uint8, device=d)
         self.b_adv = torch.zeros((T, E), **f32)
+        self.b_adv_base = torch.zeros((T, E), **f32) if self.baseline in N.PPO_BASELINE_MODES else None  # what srlx_ppo_adv_baseline writes, minibatch by minibatch
         self.act_counter = torch.zeros(1, dtype=torch.int64, device=d)
         self.losses = torch.zeros(3, **f32)
         self.b_obs[0].copy_(self.env.obs)
@@ -359,15 +410,26 @@ class PPOEngine:
         cfg = self.cfg
         if self._fused_rollout_ok():
             return self.head.rollout(self)
+        # reward_clip / state_clip / the action rescale with torch ops around the step-wise kernels: the arithmetic of k_ppo_rollout's options (clamp = min(max(x, lo), hi)
+        # in float32; the rescale a multiply, then an add)
+        if self.state_clip:
+            self.b_obs[0].clamp_(*self.state_clip)
         for t in range(cfg.horizon):
             self.b_val[t].copy_(self.act(self.b_obs[t], self.b_act[t], self.b_logp[t]))
             # the environment takes the first action dimension (a categorical head's only one; a copy only where action_dim > 1)
-            self.env.step(self.b_act[t].reshape(cfg.n_envs, -1)[:, 0].contiguous(), self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
-            self.episode_return += self.b_rew[t]
+            env_action = self.b_act[t].reshape(cfg.n_envs, -1)[:, 0].contiguous()
+            if self.rescale:
+                env_action = (env_action * self.action_map[0] + self.action_map[1]).contiguous()
+            self.env.step(env_action, self.b_obs[t + 1], self.b_rew[t], self.b_done[t])
+            self.episode_return += self.b_rew[t]  # (the raw reward)
             d = self.b_done[t].bool()
             self.finished_returns[0] += (self.episode_return * d).sum()
             self.finished_returns[1] += d.sum()
             self.episode_return.masked_fill_(d, 0.0)
+            if self.reward_clip:
+                self.b_rew[t].clamp_(*self.reward_clip)
+            if self.state_clip:
+                self.b_obs[t + 1].clamp_(*self.state_clip)
         last_v = self.forward(self.b_obs[cfg.horizon])[0]
         # episode ends are never bootstrapped (ppo.py:396-397); a horizon cut inside an episode bootstraps from V(s_T)
         N.check(self.lib.srlx_gae_scan(cfg.n_envs, cfg.horizon, N.tptr(self.b_rew), N.tptr(self.b_val), N.tptr(self.b_done), N.tptr(last_v.contiguous()),
@@ -397,8 +459,8 @@ class PPOEngine:
             perm = self._perms[ep]
             for k in range(cfg.minibatches):
                 idx = perm[k * mb : (k + 1) * mb]
-                outs, seeds = self.loss_and_seeds(obs[idx], act[idx].contiguous(), logp[idx].contiguous(), adv[idx].contiguous(), v_target[idx].contiguous(),
-                                                  val[idx].contiguous())
+                outs, seeds = self.loss_and_seeds(obs[idx], act[idx].contiguous(), logp[idx].contiguous(), self._batch_baseline(adv[idx]).contiguous(),
+                                                  v_target[idx].contiguous(), val[idx].contiguous())
                 self.opt.zero_grad(set_to_none=False)
                 torch.autograd.backward(outs, seeds)
                 if self.grad_sync is not None:
@@ -406,27 +468,48 @@ class PPOEngine:
                 if cfg.global_gradient_clip_norm != 0:
                     torch.nn.utils.clip_grad_norm_(self.net.parameters(), cfg.global_gradient_clip_norm)
                 self.opt.step()
+                if self.lr_sch is not None:
+                    self.lr_sch.step()
+
+    def _batch_baseline(self, a: torch.Tensor) -> torch.Tensor:
+        """baseline_type "ave" / "std" / "normal" over one minibatch's advantages with torch ops (ppo.py:222-233: population deviation, + 1e-8) -- the yardstick of
+        `srlx_ppo_adv_baseline`: float64 statistics, one rounding to float32.  Under `DistributedPPO` the statistics are per rank, over the LOCAL minibatch (only
+        gradients are exchanged), on this path and on the fused one."""
+        if self.baseline not in N.PPO_BASELINE_MODES:
+            return a
+        x = a.double()
+        mean, sd = x.mean(), x.std(unbiased=False) + 1e-8
+        return {"ave": x - mean, "std": x / sd, "normal": (x - mean) / sd}[self.baseline].float()
 
     def _update_fused(self, n, mb, obs, act, logp, adv, val, v_target):
-        """epochs x minibatches of (k_ppo_minibatch + k_ppo_reduce) -> [all-reduce of the flat gradient] -> k_ppo_adam; the buffers are read in place through the
-        permutation's rows."""
+        """epochs x minibatches of [k_ppo_adv_baseline ->] (k_ppo_minibatch + k_ppo_reduce) -> [all-reduce of the flat gradient] -> k_ppo_adam; the buffers are read in
+        place through the permutation's rows.  baseline_type "ave" / "std" / "normal": one more launch per minibatch writes that minibatch's transformed advantages
+        into `b_adv_base` at the same rows, and the minibatch launch reads them there (`v_target` keeps the untouched ones).  Under `DistributedPPO` the mean and
+        deviation are per rank, over the local minibatch.  A schedule goes to the launch as data: it is evaluated there, from `opt_step[0]`."""
         cfg = self.cfg
         st = N.torch_stream_ptr()
+        mode = N.PPO_BASELINE_MODES.get(self.baseline, 0)
         # the epochs' shuffles in one launch (the values `epochs` successive srlx_rng_permutation calls would write)
         N.check(self.lib.srlx_rng_permutations(cfg.seed ^ 0x7065726D, N.tptr(self.perm_counter), n, cfg.epochs, N.tptr(self._perms), st))
         for ep in range(cfg.epochs):
             for k in range(cfg.minibatches):
                 rows = self._perms[ep][k * mb : (k + 1) * mb]
-                self.head.minibatch(self, mb, rows, (N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(adv), N.tptr(v_target), N.tptr(val)),
-                                    (N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st))
+                if mode:
+                    N.check(self.lib.srlx_ppo_adv_baseline(mb, N.tptr(rows), N.tptr(adv), mode, N.tptr(self.b_adv_base), st))
+                self.head.minibatch(self, mb, rows, (N.tptr(self.flat), N.tptr(obs), N.tptr(act), N.tptr(logp), N.tptr(self.b_adv_base if mode else adv), N.tptr(v_target),
+                                                     N.tptr(val)), (N.tptr(self.partials), N.tptr(self.flat_grad), N.tptr(self.losses), st))
                 scale = self.flat_grad_sync(self.flat_grad) if self.flat_grad_sync is not None else 1.0
-                N.check(self.head.adam(cfg.obs_dim, self.head.size, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq),
-                                       N.tptr(self.opt_step), cfg.lr, 0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st))
+                state = (cfg.obs_dim, self.head.size, N.tptr(self.flat), N.tptr(self.flat_grad), N.tptr(self.exp_avg), N.tptr(self.exp_avg_sq), N.tptr(self.opt_step), cfg.lr)
+                rest = (0.9, 0.999, 1e-8, cfg.global_gradient_clip_norm, scale, st)
+                N.check(self.head.adam_sched(*state, ctypes.byref(self.lr_sched), *rest) if self.scheduled else self.head.adam(*state, *rest))
 
     def capture_graphs(self):
         """Captures the T-step rollout (+ GAE) and the whole update phase into two HIP graphs: an iteration becomes two
         graph launches instead of ~T*20 + epochs*minibatches*60 eager ones.  Call after a few eager iterations (Adam
-        state and every scratch buffer must exist)."""
+        state and every scratch buffer must exist).  The fused update's graph follows `lr_scheduler` (the rate is computed in the launch); the torch path's Adam
+        takes its rate from the host, so a schedule there cannot be captured."""
+        if not self.fused and self.scheduled:
+            raise ValueError("capture_graphs(): the torch path's learning-rate schedule is stepped on the host; the fused engine's is evaluated on the device")
         torch.cuda.synchronize(self.dev)
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
@@ -514,7 +597,9 @@ def flat_vector_all_reduce(flat: torch.Tensor, group=None) -> float:
 
 
 class DistributedPPO:
-    """Data-parallel PPO (BASELINE config 5): identical networks, disjoint environments, averaged gradients."""
+    """Data-parallel PPO (BASELINE config 5): identical networks, disjoint environments, averaged gradients.  Only gradients are exchanged: the batch baselines
+    ("ave" / "std" / "normal") take their mean and deviation per rank, over the local minibatch; the learning-rate schedule follows each rank's own step count,
+    which is the same on every rank."""
 
     def __init__(self, cfg: PPODeviceConfig, device: int, fused: Optional[bool] = None):
         import dataclasses

@@ -6,6 +6,10 @@ of the torch-autograd path (`fused=False`), of the continuous Pendulum engine ne
     rocprofv3 --kernel-trace --stats -d DIR -o p --output-format csv -- python tools/ppo_discrete_probe.py --kernels-only    # a run of its own: the tracer slows the loop
     python tools/ppo_discrete_probe.py --merge-kernel-stats DIR --out profiles/ppo_discrete_probe.json                       # kernel times into the same file
     python tools/ppo_discrete_probe.py --graphs-only [--tree TREE]     # the CartPole engine, fused with graphs, alone: one JSON line (ppo_discrete_check.py bench-ab)
+    rocprofv3 ... -- python tools/ppo_discrete_probe.py --kernels-only --arm config     # the CartPole engine of a mapped ppo.Config (a staircase schedule that steps
+                                                                                         # inside the run, baseline_type "normal"); --arm default: the engine as it was
+The `cartpole_plugin_config_graphs` arm runs `vector_runner.ppo_config_from(ppo.Config(), CartPole-v1, E, seed)` as it is: the default staircase schedule
+set_step(2000, 0.01) evaluated inside k_ppo_adam, the environment's 500-step limit.
 """
 import argparse
 import csv
@@ -18,7 +22,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNELS = ("k_ppo_rollout", "k_ppo_minibatch", "k_ppo_reduce", "k_ppo_adam", "k_categorical_act", "k_cartpole_auto", "k_ppo_forward")
+KERNELS = ("k_ppo_rollout", "k_ppo_minibatch", "k_ppo_reduce", "k_ppo_adam", "k_ppo_adv_baseline", "k_categorical_act", "k_cartpole_auto", "k_ppo_forward")
 # a kernel's head, from its template argument: the rollout's task (k_ppo_rollout<PendulumNormal> / <CartPoleCategorical>), CAT of the others
 HEADS = (("<categorical>", ("<true>", "CartPoleCategorical")), ("<normal>", ("<false>", "PendulumNormal")))
 # (builds before the rollout became one template had two kernels)
@@ -30,6 +34,25 @@ def _engine(discrete, fused, E, T=32):
 
     kw = dict(obs_dim=4, n_actions=2, episode_len=500) if discrete else {}
     return PPOEngine(PPODeviceConfig(n_envs=E, horizon=T, seed=1, **kw), 0, fused=fused)
+
+
+def _config_engine(E, T=32, **config_kw):
+    """PPOEngine of a ppo.Config on CartPole-v1, mapped by vector_runner.ppo_config_from (config_kw: ppo.Config fields; `schedule`: (decay_steps, decay_rate) of a
+    staircase in place of the default one)."""
+    import simple_distributed_rl_amd as srl
+    from simple_distributed_rl_amd.algorithms import ppo
+    from simple_distributed_rl_amd.device import vector_runner as vr
+    from simple_distributed_rl_amd.device.ppo import PPOEngine
+
+    schedule = config_kw.pop("schedule", None)
+    rl = ppo.Config(**config_kw)
+    if schedule:
+        rl.lr_scheduler.set_step(*schedule)
+    runner = srl.Runner("CartPole-v1", rl)
+    runner.setup_rl_config()
+    why = vr.why_not_ppo_engine(runner.env, runner.rl_config)
+    assert why == "", why
+    return PPOEngine(vr.ppo_config_from(runner.rl_config, runner.env, E, 1, horizon=T), 0, fused=True)
 
 
 def _throughput(eng, graphs, iters):
@@ -100,7 +123,11 @@ def kernel_stats(directory):
                 name = name.replace(old, new)
             for k in KERNELS:
                 if k + "(" in name or k + "<" in name:
-                    key = k + next((head for head, marks in HEADS if any(m in name for m in marks)), "")
+                    if k == "k_ppo_adam":  # its template argument is the schedule, not the head: k_ppo_adam<true> evaluates one, k_ppo_adam<false> is the constant rate
+                        key = k + ("<scheduled>" if "k_ppo_adam<true>" in name else "")
+                    else:
+                        key = k + next((head for head, marks in HEADS if any(m in name for m in marks)), "")
+                        key += "+options" if k == "k_ppo_rollout" and ", true>" in name else ""  # (reward / state clips, action rescale compiled in)
                     rows[key] = dict(calls=int(r["Calls"]), average_us=float(r["AverageNs"]) / 1e3, min_us=float(r["MinNs"]) / 1e3, max_us=float(r["MaxNs"]) / 1e3)
     return rows
 
@@ -120,6 +147,7 @@ def main():
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--plugin-seconds", type=float, default=20.0)
     ap.add_argument("--kernels-only", action="store_true", help="a few eager iterations of both heads and of the step-wise kernels, for a profiler")
+    ap.add_argument("--arm", choices=("default", "config"), default="default", help="--kernels-only: the engines as they were, or the CartPole engine of a mapped ppo.Config")
     ap.add_argument("--merge-kernel-stats", default=None)
     ap.add_argument("--graphs-only", action="store_true", help="the CartPole engine, fused with graphs: one JSON line, no record")
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package runs (default: this one)")
@@ -129,6 +157,12 @@ def main():
         return _merge(a.merge_kernel_stats, a.out)
     import torch
 
+    if a.kernels_only and a.arm == "config":
+        eng = _config_engine(a.envs, baseline_type="normal", schedule=(50, 0.5))  # 160 optimiser steps: the staircase steps three times
+        for _ in range(10):
+            eng.step()
+        torch.cuda.synchronize()
+        return
     if a.kernels_only:
         for discrete in (True, False):
             eng = _engine(discrete, None, a.envs)
@@ -147,6 +181,8 @@ def main():
 
     res = dict(device=str(N.device_info(0)), envs=a.envs, horizon=32, epochs=4, minibatches=4)
     res["cartpole_fused_graphs"] = _throughput(_engine(True, True, a.envs), True, a.iters)
+    res["cartpole_plugin_config_graphs"] = dict(_throughput(_config_engine(a.envs), True, a.iters),
+                                                note="vector_runner.ppo_config_from(ppo.Config(), CartPole-v1, E, 1): lr_scheduler set_step(2000, 0.01) inside k_ppo_adam")
     res["cartpole_fused_eager"] = _throughput(_engine(True, True, a.envs), False, a.iters)
     res["cartpole_unfused_eager"] = _throughput(_engine(True, False, a.envs), False, max(4, a.iters // 6))
     res["pendulum_fused_graphs"] = _throughput(_engine(False, True, a.envs), True, a.iters)
