@@ -381,7 +381,7 @@ int srlx_rank_priorities(srlx_rank_t *h, float **d_prio);
  *   srlx_ppo_loss_normal : compute_train_loss (ppo.py:102-169) for a Normal policy, forward + gradient seeds.
  *       loc/log_scale/action/old_logpi f32 [B][action_dim]; advantage/v/v_target/old_v f32 [B];
  *       baseline_advantage: advantage -= stop_gradient(v) (:121-122); surrogate_clip 1 = "clip" (:127-137),
- *       0 = "" (:148-149) ("kl" needs tensorflow_probability in the reference and is not offered);
+ *       0 = "" (:148-149) ("kl": srlx_ppo_loss_normal_kl / srlx_ppo_loss_categorical_kl below);
  *       losses f32 [3] = policy, value, entropy as the reference reports them;
  *       grad_loc/grad_log_scale f32 [B][action_dim], grad_v f32 [B] = d(policy+value+entropy)/d(.)
  *   srlx_ppo_loss_logpi  : the same given the policy head's log-probabilities f32 [B][n_logpi]
@@ -573,6 +573,74 @@ int srlx_ppo_cat_rollout_ex(int64_t n_envs, int64_t horizon, int n_actions, cons
                             int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act, float *d_b_logp,
                             float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return,
                             float *d_finished, const srlx_ppo_env_opts_t *opts, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * PPO's adaptive-KL surrogate (surrogate_type "kl": srl/algorithms/ppo/ppo.py:138-146, :279-287; srl/rl/tf/functions.py:86-103).
+ * Per element the policy term is ratio * adv - beta * kl with no ratio clip; kl is KL(old || new) against the distribution the
+ * policy acted with.  Categorical: sum_k q_k log(q_k / p_k) with both sides clipped to [1e-10, 1] (the clip passes the gradient
+ * inside its bounds, bounds included); Normal, per dimension: (ls2 - ls1) + (exp(2 ls1) + (m1 - m2)^2) / 2 exp(-2 ls2) - 1/2 with
+ * ls2 the new log-scale clamped to [log_scale_min, log_scale_max] (the gradient reaches the raw log-scale inside that range only)
+ * and ls1 the old one as clamped at acting time.  The exact float32 arithmetic: csrc/srlx_ppo_math.h; tests/ppo_kl_reference.py.
+ * beta is ONE float32 in device memory (d_kl_beta; the reference starts it at 0.5).  The launch that forms a minibatch's losses
+ * adapts it: kl_mean = mean of kl over all elements; kl_mean < target / 1.5: beta /= 2; else kl_mean > target * 1.5 and beta < 10:
+ * beta *= 2 (compared in double against thresholds formed on the host in double; halving and doubling are exact: the halving stops
+ * at the smallest normal float32, 1.18e-38, where a float32 would start to lose bits and then reach 0 for good).  No host read, no
+ * added launch: the next minibatch reads the adapted value through stream order, and a captured graph follows it.
+ * losses f32 [5] = policy, value, entropy (as the other entry points report them), kl_mean, beta as adapted.
+ *   srlx_ppo_normal_act_dist / srlx_ppo_categorical_act_dist : srlx_ppo_normal_act / srlx_ppo_categorical_act (same draws, same bits)
+ *       which also write the acting distribution: old_loc / old_log_scale f32 [n] (the log-scale clamped), probs f32 [rows][n_actions]
+ *       (expf of the float32 log-softmax: the values the sampler sums).
+ *   srlx_ppo_loss_normal_kl      : srlx_ppo_loss_normal under "kl": old_loc / old_log_scale f32 [B][action_dim] beside old_logpi.
+ *   srlx_ppo_loss_categorical_kl : logits f32 [B][n_actions] (2 <= n_actions <= 8), action i32 [B], old_logpi f32 [B], old_probs f32
+ *       [B][n_actions]; returns d loss / d logits f32 [B][n_actions] and d loss / d v.  Both loss kernels run as one workgroup that
+ *       sums in a fixed order: deterministic.
+ *   srlx_ppo_net_rollout_kl / srlx_ppo_cat_rollout_kl : srlx_ppo_*_rollout_ex (opts may be NULL) which also record the acting
+ *       distribution of every step: b_loc / b_log_scale f32 [T][E][A], b_probs f32 [T][E][n_actions]; every other output bit for bit.
+ *   srlx_ppo_net_minibatch_kl / srlx_ppo_cat_minibatch_kl : srlx_ppo_*_minibatch under "kl": the old distribution is gathered through
+ *       `rows` like b_logp; partials f32 [srlx_ppo_*_kl_partials_floats] (a fourth loss sum per workgroup); the gradient reduction
+ *       launch adapts *d_kl_beta and writes losses [5] (NULL: beta is adapted all the same).
+ * ------------------------------------------------------------------------------------------------ */
+int srlx_ppo_normal_act_dist(int64_t n, const float *d_loc, const float *d_log_scale, double log_scale_min, double log_scale_max,
+                             uint64_t seed, int64_t *d_counter, int deterministic, float *d_action, float *d_logprob, float *d_old_loc,
+                             float *d_old_log_scale, void *stream);
+int srlx_ppo_categorical_act_dist(int64_t rows, int n_actions, const float *d_logits, uint64_t seed, int64_t *d_counter,
+                                  int deterministic, int32_t *d_action, float *d_logprob, float *d_probs, void *stream);
+int srlx_ppo_loss_normal_kl(int64_t batch, int action_dim, const float *d_loc, const float *d_log_scale, double log_scale_min,
+                            double log_scale_max, const float *d_action, const float *d_old_logpi, const float *d_old_loc,
+                            const float *d_old_log_scale, const float *d_advantage, const float *d_v, const float *d_v_target,
+                            const float *d_old_v, int baseline_advantage, int enable_value_clip, double value_clip_range,
+                            double value_loss_weight, double entropy_weight, double adaptive_kl_target, float *d_kl_beta,
+                            float *d_losses, float *d_grad_loc, float *d_grad_log_scale, float *d_grad_v, void *stream);
+int srlx_ppo_loss_categorical_kl(int64_t batch, int n_actions, const float *d_logits, const int32_t *d_action, const float *d_old_logpi,
+                                 const float *d_old_probs, const float *d_advantage, const float *d_v, const float *d_v_target,
+                                 const float *d_old_v, int baseline_advantage, int enable_value_clip, double value_clip_range,
+                                 double value_loss_weight, double entropy_weight, double adaptive_kl_target, float *d_kl_beta,
+                                 float *d_losses, float *d_grad_logits, float *d_grad_v, void *stream);
+int srlx_ppo_net_kl_partials_floats(int obs_dim, int action_dim);
+int srlx_ppo_cat_kl_partials_floats(int obs_dim, int n_actions);
+int srlx_ppo_net_rollout_kl(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state,
+                            int32_t *d_step_in_episode, float *d_env_obs, int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter,
+                            uint64_t act_seed, int64_t *d_act_counter, double log_scale_min, double log_scale_max, double discount,
+                            double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
+                            uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
+                            float *d_b_loc, float *d_b_log_scale, const srlx_ppo_env_opts_t *opts, void *stream);
+int srlx_ppo_cat_rollout_kl(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps,
+                            int32_t *d_episodes, float *d_env_obs, int64_t max_steps, uint64_t env_seed, uint64_t act_seed,
+                            int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act, float *d_b_logp,
+                            float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return,
+                            float *d_finished, float *d_b_probs, const srlx_ppo_env_opts_t *opts, void *stream);
+int srlx_ppo_net_minibatch_kl(int64_t minibatch, const int64_t *d_rows, int obs_dim, int action_dim, const float *d_params,
+                              const float *d_b_obs, const float *d_b_act, const float *d_b_logp, const float *d_b_adv,
+                              const float *d_b_v_target, const float *d_b_val, const float *d_b_loc, const float *d_b_log_scale,
+                              double log_scale_min, double log_scale_max, int baseline_advantage, int enable_value_clip,
+                              double value_clip_range, double value_loss_weight, double entropy_weight, double adaptive_kl_target,
+                              float *d_kl_beta, float *d_partials, float *d_grad, float *d_losses, void *stream);
+int srlx_ppo_cat_minibatch_kl(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params,
+                              const float *d_b_obs, const int32_t *d_b_act, const float *d_b_logp, const float *d_b_adv,
+                              const float *d_b_v_target, const float *d_b_val, const float *d_b_probs, int baseline_advantage,
+                              int enable_value_clip, double value_clip_range, double value_loss_weight, double entropy_weight,
+                              double adaptive_kl_target, float *d_kl_beta, float *d_partials, float *d_grad, float *d_losses,
+                              void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Never-Give-Up intrinsic reward + Agent57_light priorities

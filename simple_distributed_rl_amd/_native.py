@@ -194,6 +194,20 @@ SIGNATURES = {
                                         c_p, c_p, c_p, c_p]),
     "srlx_ppo_cat_rollout_ex": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_u64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                         c_p, c_p]),
+    "srlx_ppo_normal_act_dist": (c_int, [c_i64, c_p, c_p, c_f64, c_f64, c_u64, c_p, c_int, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_categorical_act_dist": (c_int, [c_i64, c_int, c_p, c_u64, c_p, c_int, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_loss_normal_kl": (c_int, [c_i64, c_int, c_p, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p,
+                                        c_p, c_p]),
+    "srlx_ppo_loss_categorical_kl": (c_int, [c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_net_kl_partials_floats": (c_int, [c_int, c_int]),
+    "srlx_ppo_cat_kl_partials_floats": (c_int, [c_int, c_int]),
+    "srlx_ppo_net_rollout_kl": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_u64, c_p, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_ppo_cat_rollout_kl": (c_int, [c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_u64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p]),
+    "srlx_ppo_net_minibatch_kl": (c_int, [c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_p, c_p,
+                                          c_p, c_p, c_p]),
+    "srlx_ppo_cat_minibatch_kl": (c_int, [c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
     "srlx_ngu_create": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_int, c_f64, c_f64, c_f64, c_int]),
     "srlx_ngu_destroy": (c_int, [c_p]),
     "srlx_ngu_reset": (c_int, [c_p, c_p]),

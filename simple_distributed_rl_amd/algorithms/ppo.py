@@ -14,7 +14,11 @@ bonus with their gradient seeds come from one `srlx_ppo_loss_logpi` launch, torc
 through the small actor-critic MLP; global-norm clipping and Adam with the staircase schedule as configured.
 Continuous (NpArraySpace) actions: a Normal policy head (loc, log-scale clipped to the stable-gradient range,
 srl/rl/tf/distributions/normal_dist_block.py:76-155), the worker samples loc + scale * N(0,1), rescales [-1, 1] onto the
-environment's bounds and sanitises (:332-339), the trainer's losses and seeds come from `srlx_ppo_loss_normal`.  The
+environment's bounds and sanitises (:332-339), the trainer's losses and seeds come from `srlx_ppo_loss_normal`.
+`surrogate_type="kl"` (:138-146, :279-287): the worker also records the acting distribution (`probs`, or `mean` and `stddev`,
+:326-327, :341-343), the trainer's launch is `srlx_ppo_loss_categorical_kl` / `srlx_ppo_loss_normal_kl` -- the KL term, its
+seeds and the adaptation of beta in one kernel, beta living in device memory and mirrored in `parameter.adaptive_kl_beta`
+after every update (discrete action spaces of 2..8 actions).  The
 vectorised engine for the same policy (E environments on the device) is device/ppo.py."""
 import math
 from dataclasses import dataclass, field
@@ -60,7 +64,7 @@ class Config(RLConfig):
     discount: float = 0.9
     gae_discount: float = 0.9
     baseline_type: str = "advantage"  # "" "none" | "ave" | "std" | "normal" | "advantage" "v"
-    surrogate_type: str = "clip"  # "" | "clip"  ("kl" is not offered: see module docstring of device/ppo.py)
+    surrogate_type: str = "clip"  # "" | "clip" | "kl" (the adaptive KL penalty: beta starts at 0.5 and follows adaptive_kl_target)
     policy_clip_range: float = 0.2
     adaptive_kl_target: float = 0.01
     enable_value_clip: float = True
@@ -164,7 +168,7 @@ class Parameter(RLParameter):
         self.np_dtype = self.config.get_dtype("np")
         self.device = torch.device(self.config.used_device_torch)
         self.model = ActorCriticNetwork(self.config).to(self.device)
-        self.adaptive_kl_beta = 0.5  # ppo.py:176 (kept in the backup layout; the "kl" surrogate is not offered)
+        self.adaptive_kl_beta = 0.5  # ppo.py:176: the "kl" surrogate's penalty coefficient (the trainer mirrors its device value here)
 
     def call_restore(self, data: Any, **kwargs) -> None:
         self.model.load_state_dict(data[0])
@@ -193,8 +197,16 @@ class Trainer(RLTrainer):
         self.np_dtype = self.config.get_dtype("np")
         self.optimizer = torch.optim.Adam(self.parameter.model.parameters(), lr=self.config.lr)
         self.lr_sch = self.config.lr_scheduler.apply_torch_scheduler(self.optimizer)
-        if self.config.surrogate_type not in ("clip", ""):
+        if self.config.surrogate_type not in ("clip", "", "kl"):
             raise UndefinedError(self.config.surrogate_type)
+        self.kl = self.config.surrogate_type == "kl"
+        if self.kl:
+            n = getattr(self.config.action_space, "n", None)
+            if isinstance(self.config.action_space, DiscreteSpace) and not 2 <= n <= 8:
+                raise ValueError(f'surrogate_type "kl": srlx_ppo_loss_categorical_kl covers 2..8 actions, this action space has {n}')
+            if not self.config.adaptive_kl_target > 0:
+                raise ValueError("adaptive_kl_target must be positive")
+            self.kl_beta = torch.zeros(1, dtype=torch.float32, device=self.device)  # set from parameter.adaptive_kl_beta in front of every update
         self.parameter.model.train()
 
     def train(self) -> None:  # ppo.py:191-201
@@ -242,6 +254,31 @@ class Trainer(RLTrainer):
         self._keep = keep
         return losses, g_loc, g_ls, g_v
 
+    def losses_and_seeds_kl(self, heads, action, old_logpi, old_dist, advantage, v, v_target, old_v):
+        """compute_train_loss under "kl" in one launch, beta adapted in it: (losses[5], seeds of `heads`, d loss / d v).  heads = (logits,) with action i32 [B] and
+        old_dist = (probs,), or (loc, log_scale) with action [B][D] and old_dist = (mean, log of stddev)."""
+        cfg, d = self.config, self.device
+        B = heads[0].shape[0]
+        losses = torch.empty(5, dtype=torch.float32, device=d)
+        g_v = torch.empty(B, dtype=torch.float32, device=d)
+        hk = [t.detach().contiguous().float() for t in heads]
+        g_heads = [torch.empty_like(t) for t in hk]
+        keep = [t.detach().contiguous().float() for t in (old_logpi, advantage, v, v_target, old_v) + tuple(old_dist)]
+        rest = (int(cfg.baseline_type in ("advantage", "v")), int(bool(cfg.enable_value_clip)), float(cfg.value_clip_range), float(cfg.value_loss_weight), float(cfg.entropy_weight),
+                float(cfg.adaptive_kl_target), N.tptr(self.kl_beta), N.tptr(losses))
+        if self.parameter.model.continuous:
+            lo, hi = self.parameter.model.log_scale_range
+            act = action.detach().contiguous().float()
+            N.check(self.lib.srlx_ppo_loss_normal_kl(B, hk[0].shape[1], N.tptr(hk[0]), N.tptr(hk[1]), float(lo), float(hi), N.tptr(act), N.tptr(keep[0]), N.tptr(keep[5]), N.tptr(keep[6]),
+                                                     N.tptr(keep[1]), N.tptr(keep[2]), N.tptr(keep[3]), N.tptr(keep[4]), *rest, N.tptr(g_heads[0]), N.tptr(g_heads[1]), N.tptr(g_v),
+                                                     N.torch_stream_ptr()))
+        else:
+            act = action.detach().contiguous().to(torch.int32)
+            N.check(self.lib.srlx_ppo_loss_categorical_kl(B, hk[0].shape[1], N.tptr(hk[0]), N.tptr(act), N.tptr(keep[0]), N.tptr(keep[5]), N.tptr(keep[1]), N.tptr(keep[2]), N.tptr(keep[3]),
+                                                          N.tptr(keep[4]), *rest, N.tptr(g_heads[0]), N.tptr(g_v), N.torch_stream_ptr()))
+        self._keep = hk + keep + [act]
+        return losses, g_heads, g_v
+
     def _train(self) -> bool:
         batches = self.memory.sample()
         if batches is None:
@@ -267,7 +304,21 @@ class Trainer(RLTrainer):
         adv_t, vt_t = torch.as_tensor(adv, device=d), torch.as_tensor(v_target, device=d)
         out = self.parameter.model(torch.as_tensor(states.astype(self.np_dtype), device=d))
         v1 = out[0].view(-1)
-        if self.parameter.model.continuous:
+        if self.kl:
+            self.kl_beta.fill_(float(self.parameter.adaptive_kl_beta))  # (a restore may have changed it)
+            if self.parameter.model.continuous:
+                pol = [out[1], out[2]]
+                act = actions.view(out[1].shape)
+                sd = np.asarray([e["stddev"] for e in batches], dtype=np.float64).reshape(out[1].shape)
+                old = (torch.as_tensor(np.asarray([e["mean"] for e in batches], dtype=np.float32).reshape(out[1].shape), device=d),
+                       torch.as_tensor(np.log(sd).astype(np.float32), device=d))  # the log-scale the worker clamped and exponentiated
+            else:
+                pol = [out[1]]
+                act = actions.argmax(-1)
+                old = (torch.as_tensor(np.asarray([e["probs"] for e in batches], dtype=np.float32), device=d),)
+            losses, g_pol, g_v = self.losses_and_seeds_kl(pol, act, old_logpi, old, adv_t, v1, vt_t, old_v)
+            heads, seeds = pol + [v1], g_pol + [g_v]
+        elif self.parameter.model.continuous:
             loc, log_scale = out[1], out[2]
             losses, g_loc, g_ls, g_v = self.losses_and_seeds_normal(loc, log_scale, actions.view(loc.shape), old_logpi, adv_t, v1, vt_t, old_v)
             heads, seeds = [loc, log_scale, v1], [g_loc, g_ls, g_v]
@@ -282,8 +333,11 @@ class Trainer(RLTrainer):
         self.optimizer.step()
         if self.lr_sch is not None:
             self.lr_sch.step()
-        pl, vl, el = losses.tolist()
+        pl, vl, el, *kl = losses.tolist()
         self.info["policy_loss"], self.info["value_loss"], self.info["entropy_loss"] = pl, vl, el
+        if self.kl:  # :279-287: adapted on the device, in the loss launch; mirrored here
+            self.info["kl_mean"], self.info["kl_beta"] = kl
+            self.parameter.adaptive_kl_beta = kl[1]
         self.train_count += 1
         return True
 
@@ -323,6 +377,9 @@ class Worker(RLWorker):
                 "v": float(v.item()),
                 "log_prob": np.maximum(logp.cpu().numpy().astype(np.float32), math.log(1e-6)),  # :322
             })
+            if self.config.surrogate_type == "kl":  # :341-343
+                self.recent_batch[-1]["mean"] = loc.cpu().numpy().astype(np.float32)
+                self.recent_batch[-1]["stddev"] = scale.cpu().numpy().astype(np.float32)
             if np.isnan(a_np).any():  # :333-335
                 return self.config.action_space.sample()
             env_action = self.config.action_space.rescale_from(a_np)  # the policy's [-1, 1] onto the environment's bounds (:336)
@@ -340,6 +397,8 @@ class Worker(RLWorker):
             "v": float(v.item()),
             "log_prob": max(float(logp[a].item()), math.log(1e-6)),  # :307
         })
+        if self.config.surrogate_type == "kl":  # :326-327
+            self.recent_batch[-1]["probs"] = torch.exp(logp).cpu().numpy().astype(np.float32)
         return a
 
     def on_step(self, worker):

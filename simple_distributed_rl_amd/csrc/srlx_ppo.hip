@@ -12,6 +12,9 @@
 //                                  (ppo.py:316-324, CategoricalDist.sample / mode)
 //   srlx_cartpole_autoreset_step : CartPole (envs/cartpole.py:step) that starts its next episode in the call that ends one, like
 //                                  srlx_pendulum_step -- the discrete-action workload of the PPO engine
+//   srlx_ppo_loss_categorical_kl / srlx_ppo_loss_normal_kl : compute_train_loss under surrogate_type "kl" (ppo.py:138-146): the KL term against the recorded old
+//                                  distribution, its gradient in the seeds, and the adaptation of beta (:279-287) in device memory, one launch
+//   srlx_ppo_categorical_act_dist / srlx_ppo_normal_act_dist : the two samplers, which also write the acting distribution the "kl" surrogate compares with
 // The reference module imports TensorFlow and cannot be imported in the build container: these follow the source
 // lines only (parity UNPINNED, like srlx_gae_scan); tests check them against oracle/hot_path_oracle.py and
 // against torch autograd of the same formula.
@@ -92,6 +95,89 @@ __global__ void __launch_bounds__(256) k_ppo_loss(PpoArgs a) {
         atomicAdd(&a.losses[1], a.value_w * c.inv_b * vl);
         atomicAdd(&a.losses[2], a.entropy_w * -c.inv_b * en);
     }
+}
+
+// The "kl" surrogate.  ONE workgroup of 1024 threads walks the batch: the sums meet in a fixed tree (deterministic, no atomics), and the thread that forms kl_mean
+// adapts beta behind every other thread's read of it -- no second launch, no counter.  losses [5]: policy, value, entropy, kl_mean, beta as adapted.
+struct KlLossArgs {
+    i64 B;
+    int K;                                           // NORMAL: action dimensions; else the number of actions (<= kCatMax)
+    const float *loc, *log_scale, *action;           // NORMAL: loc = [B][K]; else loc = the logits [B][K]
+    const int32_t *action_index;                     // categorical: [B]
+    const float *old_logpi, *old0, *old1;            // NORMAL: old loc, old clamped log_scale [B][K]; else old0 = old probs [B][K]
+    const float *advantage, *v, *v_target, *old_v;
+    LossCfg cfg;
+    double kl_lo, kl_hi;  // target / 1.5, target * 1.5
+    float *beta, *losses, *d_loc, *d_log_scale, *d_v;
+};
+
+__device__ __forceinline__ float block_sum_kl(float v, float *red) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+template <bool NORMAL>
+__global__ void __launch_bounds__(1024) k_ppo_loss_kl(KlLossArgs a) {
+    __shared__ float red[1024];
+    const LossCfg &c = a.cfg;
+    const float beta = a.beta[0];
+    float s_pol = 0.f, s_val = 0.f, s_ent = 0.f, s_kl = 0.f;
+    for (i64 b = threadIdx.x; b < a.B; b += 1024) {
+        const float v = a.v[b], vt = a.v_target[b];
+        const float adv = c.baseline_advantage ? a.advantage[b] - v : a.advantage[b];
+        float ent = 0.f;
+        if constexpr (NORMAL) {
+            for (int k = 0; k < a.K; k++) {
+                const i64 i = b * a.K + k;
+                float term, e1, kl;
+                srlxp::policy_normal_kl(c, beta, a.loc[i], a.log_scale[i], a.action[i], a.old_logpi[i], a.old0[i], a.old1[i], adv, term, e1, kl, a.d_loc[i], a.d_log_scale[i]);
+                s_pol += term, ent += e1, s_kl += kl;
+            }
+        } else {
+            float term, kl, dl[srlxp::kCatMax];
+            const int act = min(max(a.action_index[b], 0), a.K - 1);
+            srlxp::policy_categorical_kl(c, beta, a.loc + b * a.K, a.K, act, a.old_logpi[b], a.old0 + b * a.K, adv, term, ent, kl, dl);
+            s_pol += term, s_kl += kl;
+#pragma unroll
+            for (int k = 0; k < srlxp::kCatMax; k++)
+                if (k < a.K) a.d_loc[b * a.K + k] = dl[k];
+        }
+        s_ent += ent;
+        float g_v;
+        s_val += srlxp::value_term(c, v, vt, c.value_clip ? a.old_v[b] : 0.f, g_v);
+        a.d_v[b] = g_v;
+    }
+    const float p = block_sum_kl(s_pol, red), vl = block_sum_kl(s_val, red), en = block_sum_kl(s_ent, red), kl = block_sum_kl(s_kl, red);  // (every thread has read beta by now)
+    if (threadIdx.x == 0) {
+        const float kl_mean = c.inv_bk * kl, nb = srlxp::kl_adapt_beta(beta, kl_mean, a.kl_lo, a.kl_hi);
+        a.losses[0] = -c.inv_bk * p, a.losses[1] = c.value_w * c.inv_b * vl, a.losses[2] = c.entropy_w * -c.inv_b * en, a.losses[3] = kl_mean, a.losses[4] = nb;
+        a.beta[0] = nb;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_normal_act_dist(i64 n, const float *loc, const float *log_scale, float ls_lo, float ls_hi, unsigned long long seed, const i64 *counter,
+                                                         int deterministic, float *action, float *logprob, float *old_loc, float *old_ls) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    srlxp::normal_act_one(loc[i], log_scale[i], ls_lo, ls_hi, seed, deterministic ? 0ull : (unsigned long long)counter[0], i, deterministic, action[i], logprob[i]);
+    old_loc[i] = loc[i];
+    old_ls[i] = srlxp::clampf(log_scale[i], ls_lo, ls_hi);
+}
+
+__global__ void __launch_bounds__(256) k_categorical_act_dist(i64 rows, int n, const float *__restrict__ logits, unsigned long long seed, const i64 *counter, int deterministic,
+                                                              int32_t *__restrict__ action, float *__restrict__ logprob, float *__restrict__ probs) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int a;
+    srlxp::cat_act_one<true>(logits + r * n, n, seed, deterministic ? 0ull : (unsigned long long)counter[0], r, deterministic, a, logprob[r], probs + r * n);
+    action[r] = a;
 }
 
 __global__ void __launch_bounds__(256) k_pendulum(i64 E, float *state /*[E][2] th, thdot*/, int32_t *t_in_ep, const float *action, i64 episode_len,
@@ -226,6 +312,72 @@ int srlx_ppo_categorical_act(int64_t rows, int n_actions, const float *d_logits,
     if (!deterministic) hipLaunchKernelGGL(k_advance1, dim3(1), dim3(1), 0, (hipStream_t)stream, d_counter);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
+}
+
+int srlx_ppo_normal_act_dist(int64_t n, const float *d_loc, const float *d_log_scale, double log_scale_min, double log_scale_max, uint64_t seed, int64_t *d_counter,
+                             int deterministic, float *d_action, float *d_logprob, float *d_old_loc, float *d_old_log_scale, void *stream) {
+    SRLX_REQUIRE(n > 0 && d_loc && d_log_scale && d_action && d_logprob && d_old_loc && d_old_log_scale && (deterministic || d_counter), "ppo_normal_act_dist: bad argument");
+    hipLaunchKernelGGL(k_normal_act_dist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (i64)n, d_loc, d_log_scale, (float)log_scale_min, (float)log_scale_max,
+                       (unsigned long long)seed, (const i64 *)d_counter, deterministic, d_action, d_logprob, d_old_loc, d_old_log_scale);
+    if (!deterministic) hipLaunchKernelGGL(k_advance1, dim3(1), dim3(1), 0, (hipStream_t)stream, d_counter);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_ppo_categorical_act_dist(int64_t rows, int n_actions, const float *d_logits, uint64_t seed, int64_t *d_counter, int deterministic, int32_t *d_action, float *d_logprob,
+                                  float *d_probs, void *stream) {
+    SRLX_REQUIRE(rows > 0 && n_actions >= 1 && d_logits && d_action && d_logprob && d_probs && (deterministic || d_counter), "ppo_categorical_act_dist: bad argument");
+    hipLaunchKernelGGL(k_categorical_act_dist, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (i64)rows, n_actions, d_logits, (unsigned long long)seed,
+                       (const i64 *)d_counter, deterministic, d_action, d_logprob, d_probs);
+    if (!deterministic) hipLaunchKernelGGL(k_advance1, dim3(1), dim3(1), 0, (hipStream_t)stream, d_counter);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+static int ppo_loss_kl_common(const char *name, KlLossArgs &a, bool normal, int baseline_advantage, int enable_value_clip, double value_clip_range, double value_loss_weight,
+                              double entropy_weight, double ls_lo, double ls_hi, double kl_target, void *stream) {
+    SRLX_REQUIRE(a.B > 0 && a.K > 0 && a.loc && a.old_logpi && a.old0 && a.advantage && a.v && a.v_target && a.beta && a.losses && a.d_loc && a.d_v, "%s: bad argument", name);
+    SRLX_REQUIRE(!enable_value_clip || a.old_v, "%s: enable_value_clip needs old_v", name);
+    SRLX_REQUIRE(kl_target > 0, "%s: adaptive_kl_target must be positive", name);
+    a.cfg = LossCfg{(float)ls_lo, (float)ls_hi, baseline_advantage, 0, enable_value_clip, 0.f, (float)value_clip_range, (float)value_loss_weight, (float)entropy_weight,
+                    1.0f / (float)a.B, 1.0f / (float)(normal ? a.B * a.K : a.B)};
+    a.kl_lo = kl_target / 1.5, a.kl_hi = kl_target * 1.5;
+    if (normal)
+        hipLaunchKernelGGL(k_ppo_loss_kl<true>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(k_ppo_loss_kl<false>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_ppo_loss_normal_kl(int64_t batch, int action_dim, const float *d_loc, const float *d_log_scale, double log_scale_min, double log_scale_max, const float *d_action,
+                            const float *d_old_logpi, const float *d_old_loc, const float *d_old_log_scale, const float *d_advantage, const float *d_v, const float *d_v_target,
+                            const float *d_old_v, int baseline_advantage, int enable_value_clip, double value_clip_range, double value_loss_weight, double entropy_weight,
+                            double adaptive_kl_target, float *d_kl_beta, float *d_losses, float *d_grad_loc, float *d_grad_log_scale, float *d_grad_v, void *stream) {
+    SRLX_REQUIRE(d_log_scale && d_action && d_old_log_scale && d_grad_log_scale, "ppo_loss_normal_kl: NULL argument");
+    KlLossArgs a{};
+    a.B = batch, a.K = action_dim;
+    a.loc = d_loc, a.log_scale = d_log_scale, a.action = d_action;
+    a.old_logpi = d_old_logpi, a.old0 = d_old_loc, a.old1 = d_old_log_scale;
+    a.advantage = d_advantage, a.v = d_v, a.v_target = d_v_target, a.old_v = d_old_v;
+    a.beta = d_kl_beta, a.losses = d_losses, a.d_loc = d_grad_loc, a.d_log_scale = d_grad_log_scale, a.d_v = d_grad_v;
+    return ppo_loss_kl_common("ppo_loss_normal_kl", a, true, baseline_advantage, enable_value_clip, value_clip_range, value_loss_weight, entropy_weight, log_scale_min, log_scale_max,
+                              adaptive_kl_target, stream);
+}
+
+int srlx_ppo_loss_categorical_kl(int64_t batch, int n_actions, const float *d_logits, const int32_t *d_action, const float *d_old_logpi, const float *d_old_probs,
+                                 const float *d_advantage, const float *d_v, const float *d_v_target, const float *d_old_v, int baseline_advantage, int enable_value_clip,
+                                 double value_clip_range, double value_loss_weight, double entropy_weight, double adaptive_kl_target, float *d_kl_beta, float *d_losses,
+                                 float *d_grad_logits, float *d_grad_v, void *stream) {
+    SRLX_REQUIRE(d_action && n_actions >= 2 && n_actions <= srlxp::kCatMax, "ppo_loss_categorical_kl: 2 <= n_actions <= 8, an action index per row");
+    KlLossArgs a{};
+    a.B = batch, a.K = n_actions;
+    a.loc = d_logits, a.action_index = d_action;
+    a.old_logpi = d_old_logpi, a.old0 = d_old_probs;
+    a.advantage = d_advantage, a.v = d_v, a.v_target = d_v_target, a.old_v = d_old_v;
+    a.beta = d_kl_beta, a.losses = d_losses, a.d_loc = d_grad_logits, a.d_v = d_grad_v;
+    return ppo_loss_kl_common("ppo_loss_categorical_kl", a, false, baseline_advantage, enable_value_clip, value_clip_range, value_loss_weight, entropy_weight, 0.0, 0.0,
+                              adaptive_kl_target, stream);
 }
 
 int srlx_cartpole_autoreset_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const int32_t *d_actions, int64_t max_steps, uint64_t seed,

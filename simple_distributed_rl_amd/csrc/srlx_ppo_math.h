@@ -11,7 +11,17 @@
 //   deterministic: the first k whose logit equals the maximum (CategoricalDist.mode; torch.argmax).
 //   the taken action's log-probability is floored at kLogFloor (ppo.py:324).
 //   loss seeds: lp = logp_a (not floored: the graph's log_softmax, ppo.py:117-119), g_lp = policy_lp_terms at K = 1 (entropy term -exp(lp) lp of the taken action
-//           only, :166), d loss / d logit_k = g_lp * ((k == a) - p_k).  Unimix and the "kl" surrogate are not offered.
+//           only, :166), d loss / d logit_k = g_lp * ((k == a) - p_k).  Unimix is not offered.
+//
+// The adaptive-KL surrogate (surrogate_type "kl": ppo.py:138-146, :279-287; tests/ppo_kl_reference.py restates it in float64):
+//   policy term of an element = ratio * adv - beta * kl, no ratio clip; beta is a float32 in device memory that the update adapts after every minibatch
+//           (kl_adapt_beta: kl_mean < target / 1.5 halves it, kl_mean > target * 1.5 doubles it while it is below 10; the comparison in double).
+//   categorical (srl/rl/tf/functions.py:86-92): q = clip(old_probs, 1e-10, 1), p = clip(new_probs, 1e-10, 1), kl = sum_k q_k logf(q_k / p_k), k ascending from 0.f;
+//           new_probs_k = expf(logp_k) (cat_act_one<true> records the same values as the NEXT update's old_probs).  tf.clip_by_value passes the gradient where
+//           1e-10 <= p_k <= 1, bounds included: g_k = -q_k / p_k there and 0 elsewhere, d kl / d logit_j = g_j P_j - P_j sum_k g_k P_k with P the unclipped softmax.
+//   Normal (functions.py:95-103: tfp's Normal.kl_divergence, closed form per dimension): kl = (ls2 - ls1) + (exp(2 ls1) + (m1 - m2)^2) * 0.5 * exp(-2 ls2) - 0.5,
+//           old mean m1 and old log-scale ls1 as clamped at acting time, new mean m2, ls2 = the new log-scale clamped to the stable-gradient range;
+//           d kl / d m2 = (m2 - m1) exp(-2 ls2); d kl / d ls2 = 1 - (exp(2 ls1) + (m1 - m2)^2) exp(-2 ls2), passed to the raw log-scale inside the clamp range only.
 #pragma once
 #include "srlx_common.h"
 
@@ -86,6 +96,41 @@ __device__ __forceinline__ void policy_normal(const LossCfg &a, float loc, float
     d_ls = pass ? g_lp * (q * q - 1.0f) : 0.f;
 }
 
+// ---- the adaptive-KL surrogate (the head comment has the formulas) ------------------------------------------------------------------------------------------
+constexpr float kKlProbFloor = 1e-10f;  // functions.py:88-89
+
+// beta after one minibatch whose mean KL is kl_mean; lo = target / 1.5, hi = target * 1.5 (formed on the host, in double).  Halving and doubling are exact in float32
+// as long as beta stays a normal number, so the halving stops at the smallest one (1.18e-38: 125 consecutive halvings from 0.5): below it the reference's Python
+// float goes on halving (with no effect on a float32 loss: beta * kl is gone long before), but a float32 would lose bits and then reach 0, from which no doubling
+// returns -- measured: 16 updates per iteration on a KL far below the target put it there within ten iterations.
+constexpr float kKlBetaMin = 1.17549435e-38f;  // FLT_MIN
+__device__ __forceinline__ float kl_adapt_beta(float beta, float kl_mean, double lo, double hi) {
+    if ((double)kl_mean < lo) return beta * 0.5f >= kKlBetaMin ? beta * 0.5f : beta;
+    if ((double)kl_mean > hi && beta < 10.0f) return beta * 2.0f;
+    return beta;
+}
+
+// Normal head, one (sample, dimension): KL(old || new) and its derivatives at the new mean and the new CLAMPED log-scale
+__device__ __forceinline__ float kl_normal(float m1, float ls1, float m2, float ls2, float &d_m2, float &d_ls2) {
+    const float e = expf(-2.0f * ls2), dm = m1 - m2;
+    const float s = expf(2.0f * ls1) + dm * dm;
+    d_m2 = (m2 - m1) * e;
+    d_ls2 = 1.0f - s * e;
+    return (ls2 - ls1) + s * 0.5f * e - 0.5f;
+}
+
+// policy_normal under the "kl" surrogate (a.surrogate_clip == 0): term = ratio * adv - beta * kl, the seeds gain beta * inv_bk * d kl
+__device__ __forceinline__ void policy_normal_kl(const LossCfg &a, float beta, float loc, float ls_raw, float action, float old_lp, float old_loc, float old_ls, float adv, float &term,
+                                                 float &ent, float &kl, float &d_loc, float &d_ls) {
+    policy_normal(a, loc, ls_raw, action, old_lp, adv, term, ent, d_loc, d_ls);
+    float k_m, k_ls;
+    kl = kl_normal(old_loc, old_ls, loc, clampf(ls_raw, a.ls_lo, a.ls_hi), k_m, k_ls);
+    const bool pass = ls_raw >= a.ls_lo && ls_raw <= a.ls_hi;
+    term -= beta * kl;
+    d_loc += beta * a.inv_bk * k_m;
+    d_ls += pass ? beta * a.inv_bk * k_ls : 0.f;
+}
+
 // value loss :152-158: returns the summand, g_v = d loss / d v
 __device__ __forceinline__ float value_term(const LossCfg &a, float v, float vt, float ov, float &g_v) {
     const float e1 = v - vt;
@@ -142,8 +187,11 @@ __device__ __forceinline__ void cat_lse(const float *__restrict__ logits, int n,
 }
 __device__ __forceinline__ float cat_logp(float logit, float m, float lse) { return (logit - m) - lse; }
 
-// logits [n] (memory: global or LDS) -> action + its log-probability; row = the index the uniform is keyed with
-__device__ __forceinline__ void cat_act_one(const float *__restrict__ logits, int n, u64 seed, u64 c, i64 row, int deterministic, int &action, float &logprob) {
+// logits [n] (memory: global or LDS) -> action + its log-probability; row = the index the uniform is keyed with.
+// PROBS: probs [n] also receives the probabilities the sampler sums (what the "kl" surrogate records as old_probs); false: the function as it was
+template <bool PROBS = false>
+__device__ __forceinline__ void cat_act_one(const float *__restrict__ logits, int n, u64 seed, u64 c, i64 row, int deterministic, int &action, float &logprob,
+                                            float *__restrict__ probs = nullptr) {
     float m, lse;
     cat_lse(logits, n, m, lse);
     int a;
@@ -151,13 +199,18 @@ __device__ __forceinline__ void cat_act_one(const float *__restrict__ logits, in
         a = 0;
         for (int k = n - 1; k >= 0; k--)
             if (logits[k] == m) a = k;  // the first maximum
+        if constexpr (PROBS) {
+            for (int k = 0; k < n; k++) probs[k] = expf(cat_logp(logits[k], m, lse));
+        }
     } else {
         const double u = srlx::u53(srlx::rng_u64(seed, c, (u64)row));
         a = n - 1;
         float cum = 0.f;
         bool found = false;
         for (int k = 0; k < n; k++) {
-            cum += expf(cat_logp(logits[k], m, lse));
+            const float p = expf(cat_logp(logits[k], m, lse));
+            if constexpr (PROBS) probs[k] = p;
+            cum += p;
             if (!found && (double)cum > u) a = k, found = true;
         }
     }
@@ -174,6 +227,32 @@ __device__ __forceinline__ void policy_categorical(const LossCfg &a, const float
     const float g_lp = policy_lp_terms(a, lp, old_lp, adv, term, ent);
 #pragma unroll
     for (int k = 0; k < kCatMax; k++) d_logit[k] = k < n ? g_lp * ((k == action ? 1.0f : 0.0f) - expf(cat_logp(logits[k], m, lse))) : 0.f;
+}
+
+// policy_categorical under the "kl" surrogate (a.surrogate_clip == 0): term = ratio * adv - beta * kl, the seeds gain beta * inv_b * d kl / d logit
+__device__ __forceinline__ void policy_categorical_kl(const LossCfg &a, float beta, const float *__restrict__ logits, int n, int action, float old_lp, const float *__restrict__ old_probs,
+                                                      float adv, float &term, float &ent, float &kl, float (&d_logit)[kCatMax]) {
+    float m, lse;
+    cat_lse(logits, n, m, lse);
+    const float lp = cat_logp(logits[action], m, lse);
+    const float g_lp = policy_lp_terms(a, lp, old_lp, adv, term, ent);
+    float P[kCatMax], g[kCatMax], s_kl = 0.f, s_gp = 0.f;
+#pragma unroll
+    for (int k = 0; k < kCatMax; k++) {
+        P[k] = 0.f, g[k] = 0.f;
+        if (k < n) {
+            P[k] = expf(cat_logp(logits[k], m, lse));
+            const float q = clampf(old_probs[k], kKlProbFloor, 1.0f), p = clampf(P[k], kKlProbFloor, 1.0f);
+            s_kl += q * logf(q / p);
+            g[k] = (P[k] >= kKlProbFloor && P[k] <= 1.0f) ? -q / p : 0.f;
+            s_gp = fmaf(g[k], P[k], s_gp);
+        }
+    }
+    kl = s_kl;
+    term -= beta * kl;
+    const float w = beta * a.inv_b;
+#pragma unroll
+    for (int k = 0; k < kCatMax; k++) d_logit[k] = k < n ? g_lp * ((k == action ? 1.0f : 0.0f) - P[k]) + w * (g[k] * P[k] - P[k] * s_gp) : 0.f;
 }
 
 // ---- CartPole (envs/cartpole.py), float64 state x, x_dot, theta, theta_dot ------------------------------------------------------------------------------------

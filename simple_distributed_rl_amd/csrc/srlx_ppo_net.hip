@@ -13,7 +13,9 @@
 //   k_ppo_adv_baseline : baseline_type "ave" / "std" / "normal" (:222-233) over one minibatch's advantages, in front of k_ppo_minibatch: one workgroup, two float64 passes.
 // What a ppo.Config asks beyond the network is compiled in on demand: k_ppo_adam<SCHED> evaluates a learning-rate schedule (srlx_lr_math.h) from the step count it reads
 // from device memory, k_ppo_rollout<Task, EX> clips rewards / observations and rescales the action (srlx_ppo_env_opts_t); the <false> instantiations are the kernels
-// as they were, and what a constant schedule / an all-off options struct launches.
+// as they were, and what a constant schedule / an all-off options struct launches.  surrogate_type "kl" is a third such switch (KL): k_ppo_rollout<Task, EX, true> also
+// records the acting distribution, k_ppo_minibatch<CAT, true> gathers it, adds the KL seeds and a fourth loss sum, and k_ppo_reduce_kl forms kl_mean and adapts beta in
+// device memory (srlx_ppo_math.h: kl_adapt_beta) -- the captured update graph follows beta as it follows the schedule.
 // The same four kernels serve a CATEGORICAL head (template parameter CAT; discrete actions, ppo.py:316-324): in -> 64 -> 64 -> {64 -> V, 64 -> n logits}, parameters
 // ... wp, bp, wlogit [n][64], blogit [n].  The n <= 8 logit rows take the 2 * A_MAX = 8 policy-head slots the Normal head's loc / log_scale rows take (slot k: k < 4
 // in wloc's place, else in wls's), so the LDS image, the heads / seeds tables and the whole backward pass are shared; what differs is the parameter layout, the
@@ -271,6 +273,18 @@ struct RolloutArgs {
     float *b_adv, *last_v /*[E]*/, *episode_return /*[E]*/, *finished /*[2] sum, count*/;
     srlx_ppo_env_opts_t opts;  // reward / state clips, action rescale (srlx.h); all off: the arithmetic of the plain entry points
 };
+// surrogate_type "kl": where the rollout records the acting distribution -- CAT: d0 = b_probs [T][E][n]; Normal: d0 = b_loc, d1 = b_ls (clamped) [T][E][A]
+struct RolloutKl {
+    float *d0, *d1;
+};
+template <class Task, bool KL>
+struct RolloutArgsOf;
+template <class Task>
+struct RolloutArgsOf<Task, false> : RolloutArgs<Task> {};  // (an empty base: the arguments as they were)
+template <class Task>
+struct RolloutArgsOf<Task, true> : RolloutArgs<Task> {
+    RolloutKl kl;
+};
 constexpr srlx_ppo_env_opts_t kEnvOptsOff = {0, 0.f, 0.f, 0, 0.f, 0.f, 1.f, 0.f};
 __host__ __device__ inline bool rescales(const srlx_ppo_env_opts_t &o) { return o.action_scale != 1.f || o.action_offset != 0.f; }
 
@@ -312,8 +326,10 @@ struct PendulumNormal {
         }
     }
     // policy sample + log-probability (ppo.py:316-339) -> b_act / b_logp [t][eg]; then the environment's step
-    template <bool EX>
-    static __device__ __forceinline__ void step(const RolloutArgs<PendulumNormal> &a, Lane &s, const float *hd, const float *zbuf, i64 t, u64, i64 eg, float (&ob)[OBS], float &rw, u8 &dn) {
+    // KL: kl-> also receives the acting distribution of this step: the mean, and the log-scale as normal_act_from_z clamps it
+    template <bool EX, bool KL>
+    static __device__ __forceinline__ void step(const RolloutArgs<PendulumNormal> &a, const RolloutKl *kl, Lane &s, const float *hd, const float *zbuf, i64 t, u64, i64 eg, float (&ob)[OBS],
+                                                float &rw, u8 &dn) {
         const int A = a.A, tid = threadIdx.x;
         float act0 = 0.f;
         for (int d = 0; d < A; d++) {
@@ -321,6 +337,10 @@ struct PendulumNormal {
             srlxp::normal_act_from_z(hd[1 + d], hd[1 + A + d], a.env.ls_lo, a.env.ls_hi, zbuf[(t * RE + tid) * A + d], 0, ac, lp);
             a.b_act[(t * a.E + eg) * A + d] = ac;
             a.b_logp[(t * a.E + eg) * A + d] = lp;
+            if constexpr (KL) {
+                kl->d0[(t * a.E + eg) * A + d] = hd[1 + d];
+                kl->d1[(t * a.E + eg) * A + d] = srlxp::clampf(hd[1 + A + d], a.env.ls_lo, a.env.ls_hi);
+            }
             if (d == 0) act0 = ac;
         }
         if (EX && rescales(a.opts)) act0 = act0 * a.opts.action_scale + a.opts.action_offset;  // ppo.py:336: [-1, 1] onto the environment's bounds (no contraction: two roundings)
@@ -358,12 +378,16 @@ struct CartPoleCategorical {
     };
     static __device__ __forceinline__ void draw(const RolloutArgs<CartPoleCategorical> &, float *, u64, i64) {}  // (one uniform per step, drawn in it)
     // categorical sample + log-probability (ppo.py:316-324), the environment's step; then b_act / b_logp [t][eg]
-    template <bool EX>
-    static __device__ __forceinline__ void step(const RolloutArgs<CartPoleCategorical> &a, Lane &s, const float *hd, const float *, i64 t, u64 c_act, i64 eg, float (&ob)[OBS], float &rw,
-                                                u8 &dn) {
+    // KL: kl->d0 also receives the acting distribution of this step: the probabilities the sampler sums (cat_act_one<true>)
+    template <bool EX, bool KL>
+    static __device__ __forceinline__ void step(const RolloutArgs<CartPoleCategorical> &a, const RolloutKl *kl, Lane &s, const float *hd, const float *, i64 t, u64 c_act, i64 eg,
+                                                float (&ob)[OBS], float &rw, u8 &dn) {
         int ac;
         float lp;
-        srlxp::cat_act_one(hd + 1, a.A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp);
+        if constexpr (KL)
+            srlxp::cat_act_one<true>(hd + 1, a.A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp, kl->d0 + (t * a.E + eg) * a.A);
+        else
+            srlxp::cat_act_one(hd + 1, a.A, a.act_seed, c_act + (u64)t, eg, 0, ac, lp);
         srlxp::cartpole_one(s.s, s.steps, s.episode, ac, a.episode_len, a.env_seed, eg, ob, rw, dn);
         a.b_act[t * a.E + eg] = ac;
         a.b_logp[t * a.E + eg] = lp;
@@ -392,8 +416,9 @@ __device__ __forceinline__ void gae_rows(const float *t_rew, const float *t_val,
 }
 
 // EX: with the options of a.opts (reward / state clips, action rescale); false: no trace of them in the code -- the rollout as it was before they existed
-template <class Task, bool EX>
-__global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
+// KL: the step also writes the acting distribution, from the heads row it samples from; false: no trace of it in the code or the arguments
+template <class Task, bool EX, bool KL = false>
+__global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgsOf<Task, KL> a) {
     constexpr int OBS = Task::OBS;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     FwdLds &L = *reinterpret_cast<FwdLds *>(lds_raw);
@@ -426,7 +451,9 @@ __global__ void __launch_bounds__(256) k_ppo_rollout(RolloutArgs<Task> a) {
             const float *hd = L.heads + tid * (1 + 2 * A_MAX);
             float ob[OBS], rw;
             u8 dn;
-            Task::template step<EX>(a, lane, hd, zbuf, t, c_act, eg, ob, rw, dn);
+            const RolloutKl *kl = nullptr;
+            if constexpr (KL) kl = &a.kl;
+            Task::template step<EX, KL>(a, kl, lane, hd, zbuf, t, c_act, eg, ob, rw, dn);
             const float raw = rw;  // (the episode's return counts the raw reward)
             if constexpr (EX) {
                 if (a.opts.reward_clip) rw = srlxp::clampf(rw, a.opts.reward_lo, a.opts.reward_hi);
@@ -471,8 +498,20 @@ struct MbArgs {
     const float *params;
     const float *b_obs, *b_act /*CAT: int32 [n]*/, *b_logp, *b_adv, *b_vt, *b_val;
     LossCfg cfg;
-    float *partials;  // [gridDim.x][stride]: per-workgroup gradient sums (parameter order) + 3 loss sums
+    float *partials;  // [gridDim.x][stride]: per-workgroup gradient sums (parameter order) + 3 loss sums (KL: 4)
     int stride;
+};
+// surrogate_type "kl": the old distribution's buffers, rows as b_logp's (CAT: b_old0 = b_probs [n]; Normal: b_old0 = b_loc, b_old1 = b_ls [A]) and the beta state
+struct MbKl {
+    const float *b_old0, *b_old1, *beta;
+};
+template <bool KL>
+struct MbArgsOf;
+template <>
+struct MbArgsOf<false> : MbArgs {};
+template <>
+struct MbArgsOf<true> : MbArgs {
+    MbKl kl;
 };
 
 // The three 64 x 64 layers run on the matrix cores: v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: an fmaf chain per output, the f32 MFMA peak equals the vector
@@ -528,8 +567,10 @@ __device__ __forceinline__ f32x16 mfma_wgrad(f32x16 acc, const float *__restrict
 }
 
 // CAT: A = the number of actions; logit k lives in policy-head slot k (seeds column 1 + k; weights wloc[k] for k < 4, wls[k - 4] beyond)
-template <bool CAT>
-__global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
+// KL: the "kl" surrogate (a.cfg.surrogate_clip == 0): a sample's old distribution is gathered with its other loss inputs and waits in the sample's row of the seeds
+// table (free until the loss writes it: no register is held across the forward), the seeds gain beta * d kl, and a fourth loss sum (kl) joins the three.
+template <bool CAT, bool KL = false>
+__global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgsOf<KL> a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     MbLds &L = *reinterpret_cast<MbLds *>(lds_raw);
     const int obs = a.obs, A = a.A, tid = threadIdx.x, n_out = CAT ? 1 + A : 1 + 2 * A;
@@ -553,6 +594,7 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
     float g_w1[OBS_MAX] = {}, g_b1 = 0.f, g_b2 = 0.f, g_bv = 0.f, g_bp = 0.f, g_wvo = 0.f, g_wloc[A_MAX] = {}, g_wls[A_MAX] = {};
     float g_head_b = 0.f;                         // u < 12: the seeds' column u (0: bvo, 1 + d: bloc[d], 5 + d: bls[d])
     float s_pol = 0.f, s_val = 0.f, s_ent = 0.f;  // tid < S: loss sums
+    [[maybe_unused]] float s_kl = 0.f;            // (KL)
     __syncthreads();
     float w1u[OBS_MAX], wloc_u[A_MAX], wls_u[A_MAX];
 #pragma unroll
@@ -577,6 +619,14 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
                     in_logp[0] = a.b_logp[idx];
                 } else {
                     for (int d = 0; d < A; d++) in_act[d] = a.b_act[idx * A + d], in_logp[d] = a.b_logp[idx * A + d];
+                }
+                if constexpr (KL) {  // columns 1 .. 8 of this sample's seeds row, where its seeds will go
+                    float *od = L.seeds + tid * HS;
+                    if constexpr (CAT) {
+                        for (int k = 0; k < A; k++) od[1 + k] = a.kl.b_old0[idx * A + k];
+                    } else {
+                        for (int d = 0; d < A; d++) od[1 + d] = a.kl.b_old0[idx * A + d], od[5 + d] = a.kl.b_old1[idx * A + d];
+                    }
                 }
             }
         }
@@ -614,14 +664,27 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
                 float ent = 0.f;
                 if constexpr (CAT) {
                     float term, dl[srlxp::kCatMax];
-                    srlxp::policy_categorical(a.cfg, hd + 1, A, in_a, in_logp[0], adv, term, ent, dl);
+                    if constexpr (KL) {
+                        float kl;
+                        srlxp::policy_categorical_kl(a.cfg, a.kl.beta[0], hd + 1, A, in_a, in_logp[0], L.seeds + tid * HS + 1, adv, term, ent, kl, dl);
+                        s_kl += kl;
+                    } else {
+                        srlxp::policy_categorical(a.cfg, hd + 1, A, in_a, in_logp[0], adv, term, ent, dl);
+                    }
                     s_pol += term;
 #pragma unroll
                     for (int k = 0; k < srlxp::kCatMax; k++) sd[1 + k] = dl[k];
                 } else {
                     for (int d = 0; d < A; d++) {
                         float term, e1;
-                        srlxp::policy_normal(a.cfg, hd[1 + d], hd[1 + A + d], in_act[d], in_logp[d], adv, term, e1, sd[1 + d], sd[5 + d]);
+                        if constexpr (KL) {
+                            const float *od = L.seeds + tid * HS;
+                            float kl;
+                            srlxp::policy_normal_kl(a.cfg, a.kl.beta[0], hd[1 + d], hd[1 + A + d], in_act[d], in_logp[d], od[1 + d], od[5 + d], adv, term, e1, kl, sd[1 + d], sd[5 + d]);
+                            s_kl += kl;
+                        } else {
+                            srlxp::policy_normal(a.cfg, hd[1 + d], hd[1 + A + d], in_act[d], in_logp[d], adv, term, e1, sd[1 + d], sd[5 + d]);
+                        }
                         s_pol += term;
                         ent += e1;
                     }
@@ -740,20 +803,40 @@ __global__ void __launch_bounds__(256) k_ppo_minibatch(MbArgs a) {
     }
     __syncthreads();
     if (tid < S) L.red[tid] = s_pol, L.red[S + tid] = s_val, L.red[2 * S + tid] = s_ent;
+    if constexpr (KL) {
+        if (tid < S) L.seeds[tid] = s_kl;  // (the seeds table is dead by now)
+    }
     __syncthreads();
     if (tid < 3) {
         float acc = 0.f;
         for (int s = 0; s < S; s++) acc += L.red[tid * S + s];
         out[o.total + tid] = acc;
     }
+    if constexpr (KL) {
+        if (tid == 3) {
+            float acc = 0.f;
+            for (int s = 0; s < S; s++) acc += L.seeds[s];
+            out[o.total + 3] = acc;
+        }
+    }
 }
 
 // partial[w][p] -> grad[p]: four lanes per parameter, each sums every fourth partial in ascending order, then (s0 + s1) + (s2 + s3) -- a fixed order: deterministic.
 // The three loss sums -> the values the reference reports (weighted means).
-__global__ void __launch_bounds__(256) k_ppo_reduce(int n_wg, int P, int stride, const float *__restrict__ partials, float *__restrict__ grad, float *__restrict__ losses, LossCfg cfg) {
+// KL (k_ppo_reduce_kl): a fourth loss sum, kl; the lane that forms kl_mean adapts beta (ppo.py:279-287) -- the minibatch launch in front of this one has read beta, the
+// next one reads what this lane writes: stream order.  losses [5]: policy, value, entropy, kl_mean, beta as adapted.
+struct ReduceKl {
+    float *beta;
+    double lo, hi;  // target / 1.5, target * 1.5
+};
+struct NoKl {};
+template <bool KL>
+__device__ __forceinline__ void reduce_partials(int n_wg, int P, int stride, const float *__restrict__ partials, float *__restrict__ grad, float *__restrict__ losses, const LossCfg &cfg,
+                                                const std::conditional_t<KL, ReduceKl, NoKl> &kl) {
+    constexpr int NL = KL ? 4 : 3;
     const int t = blockIdx.x * 256 + threadIdx.x, p = t >> 2, q = t & 3;
     float acc = 0.f;
-    if (p < P + 3) {
+    if (p < P + NL) {
 #pragma unroll 8
         for (int w = q; w < n_wg; w += 4) acc += partials[(i64)w * stride + p];
     }
@@ -761,11 +844,26 @@ __global__ void __launch_bounds__(256) k_ppo_reduce(int n_wg, int P, int stride,
     acc = (q & 1) ? a1 + acc : acc + a1;  // (both lanes of a pair hold s_even + s_odd, added in that order)
     const float a2 = __shfl_xor(acc, 2);
     acc = (q & 2) ? a2 + acc : acc + a2;
-    if (q != 0 || p >= P + 3) return;
+    if (q != 0 || p >= P + NL) return;
+    if constexpr (KL) {
+        if (p == P + 3) {
+            const float kl_mean = cfg.inv_bk * acc, nb = srlxp::kl_adapt_beta(kl.beta[0], kl_mean, kl.lo, kl.hi);
+            kl.beta[0] = nb;
+            if (losses) losses[3] = kl_mean, losses[4] = nb;
+            return;
+        }
+    }
     if (p < P)
         grad[p] = acc;
     else if (losses)
         losses[p - P] = p - P == 0 ? -cfg.inv_bk * acc : (p - P == 1 ? cfg.value_w * cfg.inv_b * acc : cfg.entropy_w * -cfg.inv_b * acc);
+}
+__global__ void __launch_bounds__(256) k_ppo_reduce(int n_wg, int P, int stride, const float *__restrict__ partials, float *__restrict__ grad, float *__restrict__ losses, LossCfg cfg) {
+    reduce_partials<false>(n_wg, P, stride, partials, grad, losses, cfg, NoKl{});
+}
+__global__ void __launch_bounds__(256) k_ppo_reduce_kl(int n_wg, int P, int stride, const float *__restrict__ partials, float *__restrict__ grad, float *__restrict__ losses, LossCfg cfg,
+                                                       ReduceKl kl) {
+    reduce_partials<true>(n_wg, P, stride, partials, grad, losses, cfg, kl);
 }
 
 // The gradient scaled by grad_scale (1 / world size behind the data-parallel all-reduce); global-norm clip; Adam.
@@ -898,6 +996,11 @@ template <bool CAT>
 int partials_floats(int obs, int A) {
     return geometry_ok<CAT>(obs, A) ? 256 * partials_stride(net_off_of<CAT>(obs, A).total) : -1;
 }
+constexpr int partials_stride_kl(int params) { return (params + 4 + 3) & ~3; }  // ... + 4 loss sums
+template <bool CAT>
+int partials_floats_kl(int obs, int A) {
+    return geometry_ok<CAT>(obs, A) ? 256 * partials_stride_kl(net_off_of<CAT>(obs, A).total) : -1;
+}
 constexpr size_t kLdsMax = 160 * 1024;  // a workgroup's LDS (gfx950)
 
 template <class Task>
@@ -907,20 +1010,21 @@ int rollout_max_horizon(int A) {  // what fits the workgroup's LDS beside weight
     return (int)(t < 1024 ? t : 1024);
 }
 
-template <class Task, bool EX>
-int launch_rollout_kernel(const RolloutArgs<Task> &a, size_t lds, void *stream) {
+template <class Task, bool EX, bool KL>
+int launch_rollout_kernel(const RolloutArgsOf<Task, KL> &a, size_t lds, void *stream) {
     static size_t lds_set = 0;
     if (lds > lds_set) {
-        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout<Task, EX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_rollout<Task, EX, KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set = lds;
     }
-    hipLaunchKernelGGL((k_ppo_rollout<Task, EX>), dim3((unsigned)(a.E / RE)), dim3(256), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_ppo_rollout<Task, EX, KL>), dim3((unsigned)(a.E / RE)), dim3(256), lds, (hipStream_t)stream, a);
     return SRLX_OK;
 }
 
 // name: the entry point's, for its error texts
+// kl: NULL = the rollout as it is; else the "kl" surrogate's record of the acting distribution
 template <class Task>
-int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream) {
+int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream, const RolloutKl *kl = nullptr) {
     SRLX_REQUIRE(a.E > 0 && a.E % RE == 0, "%s: the environment count must be a multiple of 16", name);
     SRLX_REQUIRE(a.T > 0 && geometry_ok<Task::CAT>(Task::OBS, a.A) && a.T <= rollout_max_horizon<Task>(a.A) && a.episode_len > 0,
                  "%s: bad geometry (horizon <= srlx_%s_max_horizon)", name, name);
@@ -933,7 +1037,18 @@ int launch_rollout(const char *name, const RolloutArgs<Task> &a, void *stream) {
     const size_t lds = sizeof(FwdLds) + (size_t)a.T * RE * Task::records(a.A) * sizeof(float);
     SRLX_REQUIRE(lds <= kLdsMax, "%s: horizon too long for the workgroup's LDS", name);
     const bool ex = a.opts.reward_clip || a.opts.state_clip || rescales(a.opts);  // all off: the kernel without the options' code
-    const int st = ex ? launch_rollout_kernel<Task, true>(a, lds, stream) : launch_rollout_kernel<Task, false>(a, lds, stream);
+    int st;
+    if (kl) {
+        SRLX_REQUIRE(kl->d0 && (Task::CAT || kl->d1), "%s: NULL buffer for the acting distribution", name);
+        RolloutArgsOf<Task, true> k;
+        static_cast<RolloutArgs<Task> &>(k) = a;
+        k.kl = *kl;
+        st = ex ? launch_rollout_kernel<Task, true, true>(k, lds, stream) : launch_rollout_kernel<Task, false, true>(k, lds, stream);
+    } else {
+        RolloutArgsOf<Task, false> k;
+        static_cast<RolloutArgs<Task> &>(k) = a;
+        st = ex ? launch_rollout_kernel<Task, true, false>(k, lds, stream) : launch_rollout_kernel<Task, false, false>(k, lds, stream);
+    }
     if (st != SRLX_OK) return st;
     Task::advance(a.env, a.act_counter, a.T, (hipStream_t)stream);
     SRLX_HIP(hipGetLastError());
@@ -965,8 +1080,33 @@ int launch_minibatch(MbArgs &a, float *d_grad, float *d_losses, void *stream) {
     a.stride = partials_stride(o.total);
     const i64 tiles = (a.mb + S - 1) / S;
     const int wgs = (int)(tiles < 256 ? tiles : 256);
-    hipLaunchKernelGGL(k_ppo_minibatch<CAT>, dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, a);
+    MbArgsOf<false> k;
+    static_cast<MbArgs &>(k) = a;
+    hipLaunchKernelGGL(k_ppo_minibatch<CAT>, dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, k);
     hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((4 * (o.total + 3) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wgs, o.total, a.stride, a.partials, d_grad, d_losses, a.cfg);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+// the "kl" surrogate's two launches: the same shape, the KL instantiations; partials [srlx_ppo_*_kl_partials_floats]
+template <bool CAT>
+int launch_minibatch_kl(const char *name, MbArgs &a, const float *b_old0, const float *b_old1, double kl_target, float *d_kl_beta, float *d_grad, float *d_losses, void *stream) {
+    SRLX_REQUIRE(b_old0 && (CAT || b_old1) && d_kl_beta && kl_target > 0, "%s: the old distribution's buffers, the beta state and a positive adaptive_kl_target", name);
+    static bool attr = false;
+    if (!attr) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_ppo_minibatch<CAT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MbLds)));
+        attr = true;
+    }
+    const NetOff o = net_off_of<CAT>(a.obs, a.A);
+    a.stride = partials_stride_kl(o.total);
+    const i64 tiles = (a.mb + S - 1) / S;
+    const int wgs = (int)(tiles < 256 ? tiles : 256);
+    MbArgsOf<true> k;
+    static_cast<MbArgs &>(k) = a;
+    k.kl = MbKl{b_old0, b_old1, d_kl_beta};
+    hipLaunchKernelGGL((k_ppo_minibatch<CAT, true>), dim3((unsigned)wgs), dim3(256), sizeof(MbLds), (hipStream_t)stream, k);
+    hipLaunchKernelGGL(k_ppo_reduce_kl, dim3((unsigned)((4 * (o.total + 4) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wgs, o.total, a.stride, a.partials, d_grad, d_losses, a.cfg,
+                       ReduceKl{d_kl_beta, kl_target / 1.5, kl_target * 1.5});
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
@@ -1039,6 +1179,38 @@ int srlx_ppo_net_minibatch(int64_t minibatch, const int64_t *d_rows, int obs_dim
 
 int srlx_ppo_net_partials_floats(int obs_dim, int action_dim) { return partials_floats<false>(obs_dim, action_dim); }
 
+int srlx_ppo_net_kl_partials_floats(int obs_dim, int action_dim) { return partials_floats_kl<false>(obs_dim, action_dim); }
+
+int srlx_ppo_net_rollout_kl(int64_t n_envs, int64_t horizon, int action_dim, const float *d_params, float *d_env_state, int32_t *d_step_in_episode, float *d_env_obs,
+                            int64_t episode_len, uint64_t env_seed, int64_t *d_env_counter, uint64_t act_seed, int64_t *d_act_counter, double log_scale_min,
+                            double log_scale_max, double discount, double gae_lambda, float *d_b_obs, float *d_b_act, float *d_b_logp, float *d_b_val, float *d_b_rew,
+                            uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished, float *d_b_loc, float *d_b_log_scale,
+                            const srlx_ppo_env_opts_t *opts, void *stream) {
+    const RolloutArgs<PendulumNormal> a{n_envs, horizon, action_dim, d_params, d_env_obs, episode_len, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                        {d_env_state, d_step_in_episode, d_env_counter, (float)log_scale_min, (float)log_scale_max}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv,
+                                        d_last_v, d_episode_return, d_finished, opts ? *opts : kEnvOptsOff};
+    const RolloutKl kl{d_b_loc, d_b_log_scale};
+    return launch_rollout("ppo_net_rollout_kl", a, stream, &kl);
+}
+
+int srlx_ppo_net_minibatch_kl(int64_t minibatch, const int64_t *d_rows, int obs_dim, int action_dim, const float *d_params, const float *d_b_obs, const float *d_b_act,
+                              const float *d_b_logp, const float *d_b_adv, const float *d_b_v_target, const float *d_b_val, const float *d_b_loc, const float *d_b_log_scale,
+                              double log_scale_min, double log_scale_max, int baseline_advantage, int enable_value_clip, double value_clip_range, double value_loss_weight,
+                              double entropy_weight, double adaptive_kl_target, float *d_kl_beta, float *d_partials, float *d_grad, float *d_losses, void *stream) {
+    SRLX_REQUIRE(minibatch > 0 && geometry_ok<false>(obs_dim, action_dim), "ppo_net_minibatch_kl: bad geometry");
+    SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_net_minibatch_kl: NULL argument");
+    MbArgs a{};
+    a.mb = minibatch;
+    a.perm = d_rows;
+    a.obs = obs_dim, a.A = action_dim;
+    a.params = d_params;
+    a.b_obs = d_b_obs, a.b_act = d_b_act, a.b_logp = d_b_logp, a.b_adv = d_b_adv, a.b_vt = d_b_v_target, a.b_val = d_b_val;
+    a.cfg = LossCfg{(float)log_scale_min, (float)log_scale_max, baseline_advantage, 0, enable_value_clip, 0.f, (float)value_clip_range, (float)value_loss_weight, (float)entropy_weight,
+                    1.0f / (float)minibatch, 1.0f / (float)(minibatch * action_dim)};
+    a.partials = d_partials;
+    return launch_minibatch_kl<false>("ppo_net_minibatch_kl", a, d_b_loc, d_b_log_scale, adaptive_kl_target, d_kl_beta, d_grad, d_losses, stream);
+}
+
 int srlx_ppo_net_adam(int obs_dim, int action_dim, float *d_params, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t *d_step, double lr, double beta1, double beta2,
                       double eps, double max_grad_norm, double grad_scale, void *stream) {
     SRLX_REQUIRE(geometry_ok<false>(obs_dim, action_dim) && d_params && d_grad && d_exp_avg && d_exp_avg_sq && d_step, "ppo_net_adam: bad argument");
@@ -1080,6 +1252,37 @@ int srlx_ppo_cat_param_count(int obs_dim, int n_actions) { return param_count<tr
 int srlx_ppo_cat_partials_floats(int obs_dim, int n_actions) { return partials_floats<true>(obs_dim, n_actions); }
 
 int srlx_ppo_cat_rollout_max_horizon(int n_actions) { return rollout_max_horizon<CartPoleCategorical>(n_actions); }
+
+int srlx_ppo_cat_kl_partials_floats(int obs_dim, int n_actions) { return partials_floats_kl<true>(obs_dim, n_actions); }
+
+int srlx_ppo_cat_rollout_kl(int64_t n_envs, int64_t horizon, int n_actions, const float *d_params, double *d_env_state, int32_t *d_steps, int32_t *d_episodes, float *d_env_obs,
+                            int64_t max_steps, uint64_t env_seed, uint64_t act_seed, int64_t *d_act_counter, double discount, double gae_lambda, float *d_b_obs, int32_t *d_b_act,
+                            float *d_b_logp, float *d_b_val, float *d_b_rew, uint8_t *d_b_done, float *d_b_adv, float *d_last_v, float *d_episode_return, float *d_finished,
+                            float *d_b_probs, const srlx_ppo_env_opts_t *opts, void *stream) {
+    const RolloutArgs<CartPoleCategorical> a{n_envs, horizon, n_actions, d_params, d_env_obs, max_steps, (u64)env_seed, (u64)act_seed, d_act_counter,
+                                             {d_env_state, d_steps, d_episodes}, discount, gae_lambda, d_b_obs, d_b_act, d_b_logp, d_b_val, d_b_rew, d_b_done, d_b_adv, d_last_v, d_episode_return, d_finished,
+                                             opts ? *opts : kEnvOptsOff};
+    const RolloutKl kl{d_b_probs, nullptr};
+    return launch_rollout("ppo_cat_rollout_kl", a, stream, &kl);
+}
+
+int srlx_ppo_cat_minibatch_kl(int64_t minibatch, const int64_t *d_rows, int obs_dim, int n_actions, const float *d_params, const float *d_b_obs, const int32_t *d_b_act,
+                              const float *d_b_logp, const float *d_b_adv, const float *d_b_v_target, const float *d_b_val, const float *d_b_probs, int baseline_advantage,
+                              int enable_value_clip, double value_clip_range, double value_loss_weight, double entropy_weight, double adaptive_kl_target, float *d_kl_beta,
+                              float *d_partials, float *d_grad, float *d_losses, void *stream) {
+    SRLX_REQUIRE(minibatch > 0 && geometry_ok<true>(obs_dim, n_actions), "ppo_cat_minibatch_kl: bad geometry");
+    SRLX_REQUIRE(d_rows && d_params && d_b_obs && d_b_act && d_b_logp && d_b_adv && d_b_v_target && d_b_val && d_partials && d_grad, "ppo_cat_minibatch_kl: NULL argument");
+    MbArgs a{};
+    a.mb = minibatch;
+    a.perm = d_rows;
+    a.obs = obs_dim, a.A = n_actions;
+    a.params = d_params;
+    a.b_obs = d_b_obs, a.b_act = reinterpret_cast<const float *>(d_b_act), a.b_logp = d_b_logp, a.b_adv = d_b_adv, a.b_vt = d_b_v_target, a.b_val = d_b_val;
+    a.cfg = LossCfg{0.f, 0.f, baseline_advantage, 0, enable_value_clip, 0.f, (float)value_clip_range, (float)value_loss_weight, (float)entropy_weight, 1.0f / (float)minibatch,
+                    1.0f / (float)minibatch};
+    a.partials = d_partials;
+    return launch_minibatch_kl<true>("ppo_cat_minibatch_kl", a, d_b_probs, nullptr, adaptive_kl_target, d_kl_beta, d_grad, d_losses, stream);
+}
 
 int srlx_ppo_cat_forward(int64_t n, int obs_dim, int n_actions, const float *d_params, const float *d_obs, float *d_v, float *d_logits, void *stream) {
     SRLX_REQUIRE(n > 0 && geometry_ok<true>(obs_dim, n_actions) && d_params && d_obs && d_v && d_logits, "ppo_cat_forward: bad argument");

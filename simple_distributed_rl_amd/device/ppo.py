@@ -30,6 +30,12 @@ minibatch in front of the minibatch launch (mean / population deviation of THAT 
 `state_clip`, `action_scale` / `action_offset` -- inside the one-launch rollout (`srlx_ppo_*_rollout_ex`), with torch ops around the step-wise kernels.  With none of
 them set the engine launches exactly what it launched before they existed.
 
+`surrogate_type="kl"` (ppo.py:138-146, :279-287): the policy term is ratio * adv - beta * KL(old || new), no ratio clip.  The rollout records the acting distribution
+(`old_dist`: probs [T][E][n], or loc and clamped log-scale [T][E][A]; `srlx_ppo_*_rollout_kl`, the step-wise samplers `srlx_ppo_*_act_dist`), the minibatch launch
+gathers it and adds the KL seeds (`srlx_ppo_*_minibatch_kl`; torch path: `srlx_ppo_loss_*_kl`), and beta is ONE float32 in device memory (`kl_beta`) which the launch
+that forms the losses adapts after every minibatch -- so `capture_graphs()` works on both paths, and `export_to` / `load_from` carry beta in
+`parameter.adaptive_kl_beta`.  Not data-parallel: each rank would adapt its own beta from its local kl_mean.
+
 Data parallel (config 5): `DistributedPPO` gives every rank its own E environments and averages the gradients of
 every minibatch with one all-reduce of the flat ~52 KB gradient vector (latency-bound; RCCL over xGMI) -- the only exchange; with the fused network and RCCL
 it sits INSIDE the captured update graph, between the gradient reduction and the clip + Adam launch.
@@ -80,6 +86,8 @@ class PPODeviceConfig:
     state_clip: Optional[Tuple[float, float]] = None   # (lo, hi): every observation the network reads or the buffers keep; never the environment's state
     action_scale: float = 1.0                  # the Normal head's action reaches the environment as action * action_scale + action_offset (ppo.py:336: [-1, 1] onto
     action_offset: float = 0.0                 # the action space's bounds; Pendulum: 2 and 0); b_act / b_logp keep the policy's own action
+    adaptive_kl_target: float = 0.01           # surrogate_type "kl": beta halves below target / 1.5 and doubles above target * 1.5 while beta < 10 (ppo.py:279-287)
+    adaptive_kl_beta: float = 0.5              # ... and starts here (ppo.py:177)
 
 
 class ActorCritic(nn.Module):
@@ -185,6 +193,11 @@ def _loss_args(cfg):
             cfg.value_loss_weight, cfg.entropy_weight)
 
 
+def _kl_loss_args(cfg):  # the "kl" entry points: no surrogate switch, no clip range; the target in their place
+    return (int(BASELINES.get(cfg.baseline_type) == "advantage"), int(cfg.enable_value_clip), cfg.value_clip_range, cfg.value_loss_weight, cfg.entropy_weight,
+            cfg.adaptive_kl_target)
+
+
 class NormalPendulumHead:
     """The Normal head (loc, log_scale per action dimension; ppo.py:316-339) on the Pendulum-shaped environment: `srlx_ppo_net_*`.  Every method takes the engine `e`
     and reads its environment, buffers and counters at call time (`e.env` may be swapped after construction)."""
@@ -194,8 +207,14 @@ class NormalPendulumHead:
         self.size, self.act_shape = cfg.action_dim, (cfg.action_dim,)  # the head's size for libsrlx; b_act / b_logp are [T][E] + act_shape
         self.param_count, self.partials_floats = lib.srlx_ppo_net_param_count, lib.srlx_ppo_net_partials_floats
         self.adam, self.adam_sched, self.rollout_max_horizon = lib.srlx_ppo_net_adam, lib.srlx_ppo_net_adam_sched, lib.srlx_ppo_net_rollout_max_horizon
+        self.kl_partials_floats = lib.srlx_ppo_net_kl_partials_floats
+        self.dist_shapes = ((cfg.action_dim,), (cfg.action_dim,))  # "kl": the old distribution's buffers are [T][E] + these: loc, clamped log_scale
 
-    def sample(self, e, loc, ls, action_out, logp_out, deterministic):  # the step-wise path's policy sample + log-probability
+    def sample(self, e, loc, ls, action_out, logp_out, deterministic, dist_out=None):  # the step-wise path's policy sample + log-probability [+ the acting distribution]
+        if dist_out is not None:
+            N.check(e.lib.srlx_ppo_normal_act_dist(loc.numel(), N.tptr(loc), N.tptr(ls), e.ls_range[0], e.ls_range[1], e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter),
+                                                   int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.tptr(dist_out[0]), N.tptr(dist_out[1]), N.torch_stream_ptr()))
+            return
         N.check(e.lib.srlx_ppo_normal_act(loc.numel(), N.tptr(loc), N.tptr(ls), e.ls_range[0], e.ls_range[1], e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter),
                                           int(deterministic), N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
 
@@ -210,21 +229,36 @@ class NormalPendulumHead:
         args = (cfg.n_envs, cfg.horizon, cfg.action_dim, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.obs), env.episode_len, env.seed, N.tptr(env.counter),
                 cfg.seed ^ 0x61637400, N.tptr(e.act_counter), e.ls_range[0], e.ls_range[1], cfg.discount, cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp),
                 N.tptr(e.b_val), N.tptr(e.b_rew), N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns))
-        if e.env_opts is None:
+        if e.kl:
+            N.check(e.lib.srlx_ppo_net_rollout_kl(*args, N.tptr(e.old_dist[0]), N.tptr(e.old_dist[1]), None if e.env_opts is None else ctypes.byref(e.env_opts),
+                                                  N.torch_stream_ptr()))
+        elif e.env_opts is None:
             N.check(e.lib.srlx_ppo_net_rollout(*args, N.torch_stream_ptr()))
         else:
             N.check(e.lib.srlx_ppo_net_rollout_ex(*args, ctypes.byref(e.env_opts), N.torch_stream_ptr()))
 
-    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
+    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v, old_dist=None):
         v, loc, ls = e.net(obs)
         B, A = loc.shape
         g_loc, g_ls, g_v = torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(v)
+        if e.kl:
+            e._keep_loss = (loc.detach().contiguous(), ls.detach().contiguous(), v.detach().contiguous()) + tuple(old_dist)
+            N.check(e.lib.srlx_ppo_loss_normal_kl(
+                B, A, N.tptr(e._keep_loss[0]), N.tptr(e._keep_loss[1]), e.ls_range[0], e.ls_range[1], N.tptr(action), N.tptr(old_logp), N.tptr(old_dist[0]), N.tptr(old_dist[1]),
+                N.tptr(adv), N.tptr(e._keep_loss[2]), N.tptr(v_target), N.tptr(old_v), *_kl_loss_args(e.cfg), N.tptr(e.kl_beta), N.tptr(e.losses), N.tptr(g_loc), N.tptr(g_ls),
+                N.tptr(g_v), N.torch_stream_ptr()))
+            return (v, loc, ls), (g_v, g_loc, g_ls)
         N.check(e.lib.srlx_ppo_loss_normal(
             B, A, N.tptr(loc.detach()), N.tptr(ls.detach()), e.ls_range[0], e.ls_range[1], N.tptr(action), N.tptr(old_logp), N.tptr(adv), N.tptr(v.detach()),
             N.tptr(v_target), N.tptr(old_v), *_loss_args(e.cfg), N.tptr(e.losses), N.tptr(g_loc), N.tptr(g_ls), N.tptr(g_v), N.torch_stream_ptr()))
         return (v, loc, ls), (g_v, g_loc, g_ls)
 
     def minibatch(self, e, mb, rows, buffers, outputs):
+        if e.kl:
+            partials, grad, losses, st = outputs
+            N.check(e.lib.srlx_ppo_net_minibatch_kl(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, N.tptr(e.old_dist[0]), N.tptr(e.old_dist[1]), e.ls_range[0], e.ls_range[1],
+                                                    *_kl_loss_args(e.cfg), N.tptr(e.kl_beta), partials, grad, losses, st))
+            return
         N.check(e.lib.srlx_ppo_net_minibatch(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, e.ls_range[0], e.ls_range[1], *_loss_args(e.cfg), *outputs))
 
 
@@ -241,8 +275,14 @@ class CategoricalCartPoleHead:
         self.size, self.act_shape = cfg.n_actions, ()
         self.param_count, self.partials_floats = lib.srlx_ppo_cat_param_count, lib.srlx_ppo_cat_partials_floats
         self.adam, self.adam_sched, self.rollout_max_horizon = lib.srlx_ppo_cat_adam, lib.srlx_ppo_cat_adam_sched, lib.srlx_ppo_cat_rollout_max_horizon
+        self.kl_partials_floats = lib.srlx_ppo_cat_kl_partials_floats
+        self.dist_shapes = ((cfg.n_actions,),)  # "kl": probs [T][E][n]
 
-    def sample(self, e, logits, action_out, logp_out, deterministic):
+    def sample(self, e, logits, action_out, logp_out, deterministic, dist_out=None):
+        if dist_out is not None:
+            N.check(e.lib.srlx_ppo_categorical_act_dist(logits.shape[0], self.size, N.tptr(logits), e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter), int(deterministic),
+                                                        N.tptr(action_out), N.tptr(logp_out), N.tptr(dist_out[0]), N.torch_stream_ptr()))
+            return
         N.check(e.lib.srlx_ppo_categorical_act(logits.shape[0], self.size, N.tptr(logits), e.cfg.seed ^ 0x61637400, N.tptr(e.act_counter), int(deterministic),
                                                N.tptr(action_out), N.tptr(logp_out), N.torch_stream_ptr()))
 
@@ -257,13 +297,24 @@ class CategoricalCartPoleHead:
         args = (cfg.n_envs, cfg.horizon, cfg.n_actions, N.tptr(e.flat), N.tptr(env.state), N.tptr(env.t), N.tptr(env.episodes), N.tptr(env.obs), env.episode_len, env.seed,
                 cfg.seed ^ 0x61637400, N.tptr(e.act_counter), cfg.discount, cfg.gae_discount, N.tptr(e.b_obs), N.tptr(e.b_act), N.tptr(e.b_logp), N.tptr(e.b_val), N.tptr(e.b_rew),
                 N.tptr(e.b_done), N.tptr(e.b_adv), N.tptr(e._last_v), N.tptr(e.episode_return), N.tptr(e.finished_returns))
-        if e.env_opts is None:
+        if e.kl:
+            N.check(e.lib.srlx_ppo_cat_rollout_kl(*args, N.tptr(e.old_dist[0]), None if e.env_opts is None else ctypes.byref(e.env_opts), N.torch_stream_ptr()))
+        elif e.env_opts is None:
             N.check(e.lib.srlx_ppo_cat_rollout(*args, N.torch_stream_ptr()))
         else:
             N.check(e.lib.srlx_ppo_cat_rollout_ex(*args, ctypes.byref(e.env_opts), N.torch_stream_ptr()))
 
-    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v):
+    def loss_and_seeds(self, e, obs, action, old_logp, adv, v_target, old_v, old_dist=None):
         v, logits = e.net(obs)
+        if e.kl:  # the KL term needs every logit: the kernel takes the logits and returns their seeds
+            if self.size not in self.fused_sizes:
+                raise ValueError('surrogate_type "kl": srlx_ppo_loss_categorical_kl covers ' + self.envelope)
+            g_logits, g_v = torch.empty_like(logits), torch.empty_like(v)
+            e._keep_loss = (logits.detach().contiguous(), v.detach().contiguous(), action.reshape(-1).contiguous(), old_dist[0])
+            N.check(e.lib.srlx_ppo_loss_categorical_kl(logits.shape[0], self.size, N.tptr(e._keep_loss[0]), N.tptr(e._keep_loss[2]), N.tptr(old_logp), N.tptr(old_dist[0]), N.tptr(adv),
+                                                       N.tptr(e._keep_loss[1]), N.tptr(v_target), N.tptr(old_v), *_kl_loss_args(e.cfg), N.tptr(e.kl_beta), N.tptr(e.losses),
+                                                       N.tptr(g_logits), N.tptr(g_v), N.torch_stream_ptr()))
+            return (v, logits), (g_v, g_logits)
         lp = torch.log_softmax(logits, dim=-1).gather(1, action.long().view(-1, 1))  # CategoricalDist.log_prob of the taken action, [B][1]
         g_lp, g_v = torch.empty_like(lp), torch.empty_like(v)
         e._keep_loss = (lp.detach().contiguous(), v.detach().contiguous())
@@ -272,6 +323,11 @@ class CategoricalCartPoleHead:
         return (v, lp), (g_v, g_lp)
 
     def minibatch(self, e, mb, rows, buffers, outputs):
+        if e.kl:
+            partials, grad, losses, st = outputs
+            N.check(e.lib.srlx_ppo_cat_minibatch_kl(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, N.tptr(e.old_dist[0]), *_kl_loss_args(e.cfg), N.tptr(e.kl_beta), partials, grad,
+                                                    losses, st))
+            return
         N.check(e.lib.srlx_ppo_cat_minibatch(mb, N.tptr(rows), e.cfg.obs_dim, self.size, *buffers, *_loss_args(e.cfg), *outputs))
 
 
@@ -302,8 +358,13 @@ class PPOEngine:
         place, returns the factor the optimiser launch applies: 1 / world size)."""
         if not torch.cuda.is_available():
             raise RuntimeError("simple_distributed_rl_amd.device.ppo needs an MI355X: its rollout / GAE / loss arithmetic is libsrlx HIP code (no CPU fallback)")
-        if cfg.surrogate_type not in ("clip", ""):
-            raise ValueError('surrogate_type must be "clip" or "" (the reference\'s "kl" needs tensorflow_probability, functions.py:95-103)')
+        if cfg.surrogate_type not in ("clip", "", "kl"):
+            raise ValueError('surrogate_type must be "clip", "" or "kl"')
+        self.kl = cfg.surrogate_type == "kl"
+        if self.kl and not cfg.adaptive_kl_target > 0:
+            raise ValueError("adaptive_kl_target must be positive")
+        if self.kl and (grad_sync is not None or flat_grad_sync is not None):
+            raise ValueError('surrogate_type "kl" is not data-parallel: each rank would adapt its own beta from its local kl_mean (exchanging kl_mean is not built)')
         if cfg.baseline_type not in BASELINES:
             raise ValueError(f"baseline_type {cfg.baseline_type!r}: the engine serves {sorted(BASELINES)}")
         self.baseline = BASELINES[cfg.baseline_type]  # "advantage" (inside the loss), "none", or a batch statistic: "ave" / "std" / "normal"
@@ -350,7 +411,7 @@ class PPOEngine:
             self.flat_grad = torch.zeros(P, dtype=torch.float32, device=self.dev)
             self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
             self.opt_step = torch.zeros(2, dtype=torch.int64, device=self.dev)  # [steps taken, the optimiser launch's arrival counter]
-            self.partials = torch.zeros(head.partials_floats(cfg.obs_dim, head.size), dtype=torch.float32, device=self.dev)
+            self.partials = torch.zeros((head.kl_partials_floats if self.kl else head.partials_floats)(cfg.obs_dim, head.size), dtype=torch.float32, device=self.dev)
             self.opt = None
         else:
             self.opt = torch.optim.Adam(self.net.parameters(), lr=cfg.lr, capturable=True)
@@ -368,7 +429,10 @@ class PPOEngine:
         self.b_adv = torch.zeros((T, E), **f32)
         self.b_adv_base = torch.zeros((T, E), **f32) if self.baseline in N.PPO_BASELINE_MODES else None  # what srlx_ppo_adv_baseline writes, minibatch by minibatch
         self.act_counter = torch.zeros(1, dtype=torch.int64, device=d)
-        self.losses = torch.zeros(3, **f32)
+        self.losses = torch.zeros(5 if self.kl else 3, **f32)  # policy, value, entropy [, kl_mean, beta as adapted]
+        # "kl": the acting distribution of every step, and beta -- device state, adapted by the launch that forms the losses
+        self.old_dist = tuple(torch.zeros((T, E) + shape, **f32) for shape in head.dist_shapes) if self.kl else None
+        self.kl_beta = torch.full((1,), float(cfg.adaptive_kl_beta), **f32) if self.kl else None
         self.b_obs[0].copy_(self.env.obs)
         self.iterations = 0
         self._rollout_graph = None
@@ -388,9 +452,13 @@ class PPOEngine:
         self.perm_counter = torch.zeros(1, dtype=torch.int64, device=d)
 
     # --- rollout ---------------------------------------------------------------------------------------------------
-    def act(self, obs: torch.Tensor, action_out: torch.Tensor, logp_out: torch.Tensor, deterministic: bool = False):
+    def act(self, obs: torch.Tensor, action_out: torch.Tensor, logp_out: torch.Tensor, deterministic: bool = False, dist_out=None):
+        """dist_out ("kl"): tensors that receive the acting distribution -- (probs [n][n_actions],), or (loc, clamped log_scale) [n][A]"""
         v, *self._keep = self.forward(obs)  # (the head's outputs stay alive behind the launch)
-        self.head.sample(self, *self._keep, action_out, logp_out, deterministic)
+        if dist_out is None:
+            self.head.sample(self, *self._keep, action_out, logp_out, deterministic)
+        else:
+            self.head.sample(self, *self._keep, action_out, logp_out, deterministic, dist_out)
         return v
 
     def forward(self, obs: torch.Tensor):
@@ -415,7 +483,7 @@ class PPOEngine:
         if self.state_clip:
             self.b_obs[0].clamp_(*self.state_clip)
         for t in range(cfg.horizon):
-            self.b_val[t].copy_(self.act(self.b_obs[t], self.b_act[t], self.b_logp[t]))
+            self.b_val[t].copy_(self.act(self.b_obs[t], self.b_act[t], self.b_logp[t], dist_out=tuple(b[t] for b in self.old_dist) if self.kl else None))
             # the environment takes the first action dimension (a categorical head's only one; a copy only where action_dim > 1)
             env_action = self.b_act[t].reshape(cfg.n_envs, -1)[:, 0].contiguous()
             if self.rescale:
@@ -437,8 +505,11 @@ class PPOEngine:
         self._last_v = last_v
 
     # --- update ----------------------------------------------------------------------------------------------------
-    def loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v):
-        """forward + the fused loss kernel; returns (v, loc, log_scale) with their gradient seeds -- categorical: (v, log-probability of the taken action)."""
+    def loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v, old_dist=None):
+        """forward + the fused loss kernel; returns (v, loc, log_scale) with their gradient seeds -- categorical: (v, log-probability of the taken action); under "kl"
+        (old_dist: the sampled rows of the acting distribution) the categorical pair is (v, logits), and the launch adapts `kl_beta`."""
+        if self.kl:
+            return self.head.loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v, old_dist)
         return self.head.loss_and_seeds(self, obs, action, old_logp, adv, v_target, old_v)
 
     def update(self):
@@ -459,8 +530,9 @@ class PPOEngine:
             perm = self._perms[ep]
             for k in range(cfg.minibatches):
                 idx = perm[k * mb : (k + 1) * mb]
+                old = tuple(b.reshape(n, -1)[idx].contiguous() for b in self.old_dist) if self.kl else None
                 outs, seeds = self.loss_and_seeds(obs[idx], act[idx].contiguous(), logp[idx].contiguous(), self._batch_baseline(adv[idx]).contiguous(),
-                                                  v_target[idx].contiguous(), val[idx].contiguous())
+                                                  v_target[idx].contiguous(), val[idx].contiguous(), old)
                 self.opt.zero_grad(set_to_none=False)
                 torch.autograd.backward(outs, seeds)
                 if self.grad_sync is not None:
@@ -547,8 +619,11 @@ class PPOEngine:
         return s / c if c else float("nan")
 
     def info(self) -> dict:
-        pl, vl, el = self.losses.tolist()
-        return dict(policy_loss=pl, value_loss=vl, entropy_loss=el)
+        pl, vl, el, *kl = self.losses.tolist()
+        out = dict(policy_loss=pl, value_loss=vl, entropy_loss=el)
+        if self.kl:
+            out["kl_mean"], out["kl_beta"] = kl[0], float(self.kl_beta.item())  # (the last minibatch's mean KL; beta as it stands)
+        return out
 
     # --- weight exchange with the PPO plugin (algorithms/ppo.py:Parameter; its network's keys: hidden_block, value_block, value_out, policy_block, policy_out) ---
     def export_to(self, parameter) -> None:
@@ -557,6 +632,8 @@ class PPOEngine:
             for a, b in _paired_linears(self.net, parameter):
                 b.weight.copy_(a.weight)
                 b.bias.copy_(a.bias)
+        if getattr(self, "kl", False):
+            parameter.adaptive_kl_beta = float(self.kl_beta.item())
 
     def load_from(self, parameter) -> None:
         """Copies a plugin `ppo.Parameter`'s network into this engine (the fused path's flat vector included: the module's tensors are views of it)."""
@@ -564,6 +641,8 @@ class PPOEngine:
             for a, b in _paired_linears(self.net, parameter):
                 a.weight.copy_(b.weight)
                 a.bias.copy_(b.bias)
+        if getattr(self, "kl", False):
+            self.kl_beta.fill_(float(parameter.adaptive_kl_beta))
 
 
 def flat_grad_all_reduce(net: nn.Module, group=None):
@@ -606,6 +685,8 @@ class DistributedPPO:
 
         import torch.distributed as dist
 
+        if cfg.surrogate_type == "kl":
+            raise ValueError('DistributedPPO: surrogate_type "kl" is not data-parallel -- each rank would adapt its own beta from its local kl_mean (exchanging kl_mean is not built)')
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         local = dataclasses.replace(cfg, seed=cfg.seed)  # same seed -> same initial network on every rank
         self.engine = PPOEngine(local, device, grad_sync=flat_grad_all_reduce, flat_grad_sync=flat_vector_all_reduce, fused=fused)

@@ -484,9 +484,11 @@ def _ppo_action_map(env) -> Optional[Tuple[float, float]]:
     return float((hi[0] - lo[0]) / 2.0), float((hi[0] + lo[0]) / 2.0)
 
 
-def why_not_ppo_engine(env, rl_config) -> str:
+def why_not_ppo_engine(env, rl_config, admit_kl: bool = False) -> str:
     """Empty string when `PPOEngine` (device/ppo.py) can run this ppo.Config on this environment as it is configured -- `ppo_config_from` maps it; otherwise EVERY
-    reason it cannot, joined with "; ".  `Runner.train()` does not ask: PPO stays on the plugin path (`engine_kind`, `why_not_vector` are as they were)."""
+    reason it cannot, joined with "; ".  `Runner.train()` does not ask: PPO stays on the plugin path (`engine_kind`, `why_not_vector` are as they were).
+    `admit_kl=True` puts `surrogate_type="kl"` (with `adaptive_kl_target`) inside the envelope -- the engine serves it (srlx_ppo_*_minibatch_kl); the default keeps the
+    answer, and the three field tuples the reading, callers have had so far.  The keyword disappears when the route flips."""
     from simple_distributed_rl_amd.device.ppo import BASELINES
     from simple_distributed_rl_amd.envs.cartpole import CartPole
     from simple_distributed_rl_amd.envs.pendulum import Pendulum
@@ -524,7 +526,10 @@ def why_not_ppo_engine(env, rl_config) -> str:
         why.append("enable_stable_gradients=False: the Normal head's log-scale clip is part of the kernels")
     if c.baseline_type not in BASELINES:
         why.append(f"unknown baseline_type {c.baseline_type!r}")
-    if c.surrogate_type not in ("clip", ""):
+    if admit_kl and c.surrogate_type == "kl":
+        if not c.adaptive_kl_target > 0:
+            why.append("adaptive_kl_target must be positive")
+    elif c.surrogate_type not in ("clip", ""):
         why.append(f'unknown surrogate_type {c.surrogate_type!r} (the engine serves "clip" and "", and "kl", with adaptive_kl_target, is not offered)')
     try:
         N.lr_schedule(c.lr_scheduler)
@@ -533,21 +538,23 @@ def why_not_ppo_engine(env, rl_config) -> str:
     return "; ".join(why)
 
 
-def ppo_config_from(rl_config, env, n_envs: int, seed: int, horizon: int = 32, epochs: int = 4, minibatches: int = 4):
+def ppo_config_from(rl_config, env, n_envs: int, seed: int, horizon: int = 32, epochs: int = 4, minibatches: int = 4, admit_kl: bool = False):
     """ppo.Config (srl/algorithms/ppo/config.py:31-128) -> PPODeviceConfig, for a pair `why_not_ppo_engine` admits.  Carried over: the three blocks, both discounts,
     every loss field, lr and its schedule, the gradient clip norm, the log-scale range, reward_clip / state_clip, episode_len = the environment's step limit, the head
     (n_actions of a discrete action space; action_dim, and action_scale / action_offset from the bounds, of a continuous one -- Pendulum: 2 and 0).
     `batch_size`, `memory.*`, `train_num` and `train_every_epoch` describe the plugin's collect-then-train schedule and have no counterpart: the engine's schedule is
-    `horizon` x `n_envs` steps per iteration, then `epochs` x `minibatches` updates -- its operating point, chosen here by the caller (PPO_OPERATING_POINT_FIELDS)."""
+    `horizon` x `n_envs` steps per iteration, then `epochs` x `minibatches` updates -- its operating point, chosen here by the caller (PPO_OPERATING_POINT_FIELDS).
+    `admit_kl=True` (as `why_not_ppo_engine`'s) also maps `surrogate_type="kl"` and carries `adaptive_kl_target`; beta starts at the reference's 0.5."""
     import copy
 
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
     from simple_distributed_rl_amd.device.ppo import PPODeviceConfig
 
-    why = why_not_ppo_engine(env, rl_config)
+    why = why_not_ppo_engine(env, rl_config, admit_kl=admit_kl)
     if why:
         raise ValueError("PPOEngine cannot run this configuration: " + why)
     c = rl_config
+    kl = dict(adaptive_kl_target=float(c.adaptive_kl_target)) if c.surrogate_type == "kl" else {}
     if isinstance(env.action_space, DiscreteSpace):
         head = dict(n_actions=int(env.action_space.n))
     else:
@@ -562,7 +569,7 @@ def ppo_config_from(rl_config, env, n_envs: int, seed: int, horizon: int = 32, e
         entropy_weight=float(c.entropy_weight), global_gradient_clip_norm=float(c.global_gradient_clip_norm),
         stable_gradients_scale_range=tuple(float(x) for x in c.stable_gradients_scale_range),
         reward_clip=None if c.reward_clip is None else tuple(float(x) for x in c.reward_clip),
-        state_clip=None if c.state_clip is None else tuple(float(x) for x in c.state_clip), **head,
+        state_clip=None if c.state_clip is None else tuple(float(x) for x in c.state_clip), **head, **kl,
     )
 
 
