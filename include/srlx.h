@@ -1121,6 +1121,34 @@ int srlx_mlpq_noisy_eps(srlx_mlpq_t *h, int64_t draw, int param_index, float *d_
 int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
                        int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 
+/* ---- Agent57's recurrent layer (srlx_lstm.hip) ----------------------------------------------------------------------------------------------------------
+ * One-layer, unidirectional, batch_first LSTM in float32 with torch.nn.LSTM's parameter layout (srl/algorithms/agent57/model_torch.py:39-46,74-75):
+ *   w_ih [4 H][I], w_hh [4 H][H], b_ih [4 H], b_hh [4 H]; gate rows in the order i, f, g, o (rows g H .. g H + H - 1 belong to gate g).
+ *   x [B][T][I], y [B][T][H] (row b T + t), h0 / c0 / h_n / c_n [B][H] (torch's (1, B, H) without the leading 1).  All tensors dense.
+ *   i, f, o = 1 / (1 + expf(-pre)), g = tanhf(pre), c_t = f c_{t-1} + i g, h_t = o tanhf(c_t); pre = x_t W_ih^T + b_ih + b_hh + h_{t-1} W_hh^T.
+ * Envelope (validated before any device call; a violation returns SRLX_ERR_INVALID and srlx_last_error() names lstm): B 1..256, T 1..256, I 1..16384,
+ * H a multiple of 16 in 16..512.  h0, w_hh, y and scratch must be 16-byte aligned.
+ *   srlx_lstm_workspace_floats : floats of the training workspace (gate activations [B T][4 H], then cell states [B T][H]: 5 B T H) when `training`, 0
+ *                                otherwise (a pass without gradient keeps nothing); -1 outside the envelope.  Host arithmetic.
+ *   srlx_lstm_scratch_floats   : floats of the scratch buffer of either call (the input projection or dG [B T][4 H], then the dc carry [B][H]); -1 outside
+ *                                the envelope.  Host arithmetic.  A forward and the backward that belongs to it may share one scratch buffer.
+ *   srlx_lstm_forward          : 1 + T launches.  One dense GEMM projects every time step's input, then one launch per step adds h_{t-1} W_hh^T, runs the
+ *                                cell in its epilogue and writes h_t into y[b][t], where step t + 1 reads it.  With `workspace` it also stores the gate
+ *                                activations and c_t for srlx_lstm_backward; with NULL (burn-in, target pass, acting) it stores neither and c_n carries the
+ *                                running cell state.  y, h_n and c_n are the same bits either way.  h0 / c0 must not alias h_n / c_n.
+ *   srlx_lstm_backward         : T launches (t = T-1 .. 0: dh_t = dy[:, t] + dG_{t+1} W_hh, the pointwise backward into the pre-activation gate gradients
+ *                                dG_t and the dc carry), one more for dh0 when asked, then dx = dG W_ih (when asked), dw_ih = dG^T x, dw_hh = dG^T h_prev
+ *                                and db_ih = db_hh = column sums of dG.  dh_n / dc_n (gradients of the final state) may be NULL (zero); dx, dh0, dc0 may be
+ *                                NULL (not wanted).  Outputs are overwritten, not accumulated.  Every sum over B T runs in a fixed order without atomics: two
+ *                                calls on the same inputs give the same bits. */
+int64_t srlx_lstm_workspace_floats(int64_t B, int64_t T, int64_t I, int64_t H, int training);
+int64_t srlx_lstm_scratch_floats(int64_t B, int64_t T, int64_t I, int64_t H, int training);
+int srlx_lstm_forward(int64_t B, int64_t T, int64_t I, int64_t H, const float *x, const float *h0, const float *c0, const float *w_ih, const float *w_hh,
+                      const float *b_ih, const float *b_hh, float *y, float *h_n, float *c_n, float *workspace, float *scratch, void *stream);
+int srlx_lstm_backward(int64_t B, int64_t T, int64_t I, int64_t H, const float *x, const float *h0, const float *c0, const float *w_ih, const float *w_hh,
+                       const float *y, const float *workspace, const float *dy, const float *dh_n, const float *dc_n, float *dx, float *dw_ih, float *dw_hh,
+                       float *db_ih, float *db_hh, float *dh0, float *dc0, float *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,10 @@ SIGNATURES = {
     "srlx_mlpq_noisy_eps": (c_int, [c_p, c_i64, c_int, c_p, c_p]),
     "srlx_mlpq_train_nstep": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_cartpole_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_lstm_workspace_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_int]),
+    "srlx_lstm_scratch_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_int]),
+    "srlx_lstm_forward": (c_int, [c_i64] * 4 + [c_p] * 13),
+    "srlx_lstm_backward": (c_int, [c_i64] * 4 + [c_p] * 19),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

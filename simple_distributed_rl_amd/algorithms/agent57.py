@@ -102,8 +102,64 @@ class Memory(RLPriorityReplayBuffer):
     pass
 
 
+class _LstmFunction(torch.autograd.Function):
+    """y, h_n, c_n = LSTM(x, (h0, c0)) with the forward AND the backward through time in libsrlx (srlx_lstm_forward / srlx_lstm_backward: float32 matrix-core
+    kernels with fixed summation orders, so an update is reproducible run to run).  The four LSTM parameters are inputs only so that autograd routes their
+    gradients through `backward`; the kernels read them by address.  `bufs` is the module's cached workspace / scratch pair of this (B, T)."""
+
+    @staticmethod
+    def forward(ctx, bufs, training, x, h0, c0, w_ih, w_hh, b_ih, b_hh):
+        B, T, I = x.shape
+        H = w_hh.shape[1]
+        x, h0, c0 = _dense16(x), _dense16(h0), _dense16(c0)
+        y = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
+        h_n, c_n = torch.empty_like(h0), torch.empty_like(c0)
+        ws = bufs["workspace"] if training else None
+        N.check(N.lib().srlx_lstm_forward(B, T, I, H, N.tptr(x), N.tptr(h0), N.tptr(c0), N.tptr(w_ih), N.tptr(w_hh), N.tptr(b_ih), N.tptr(b_hh), N.tptr(y),
+                                          N.tptr(h_n), N.tptr(c_n), N.tptr(ws), N.tptr(bufs["scratch"]), N.torch_stream_ptr()))
+        if training:
+            bufs["serial"] += 1
+            ctx.bufs, ctx.serial, ctx.keep = bufs, bufs["serial"], (x, h0, c0, w_ih, w_hh, y)
+            ctx.set_materialize_grads(False)
+        return y, h_n, c_n
+
+    @staticmethod
+    def backward(ctx, dy, dh_n, dc_n):
+        bufs = ctx.bufs
+        if bufs["serial"] != ctx.serial:
+            raise RuntimeError("Agent57 LSTM: another pass with gradient of the same (batch, steps) ran on this module before this one's backward; its workspace is gone")
+        x, h0, c0, w_ih, w_hh, y = ctx.keep
+        B, T, I = x.shape
+        H = w_hh.shape[1]
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dh_n, dc_n = (None if g is None else g.contiguous() for g in (dh_n, dc_n))
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[2] else None
+        dh0 = torch.empty_like(h0) if need[3] else None
+        dc0 = torch.empty_like(c0) if need[4] else None
+        dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+        db_ih, db_hh = (torch.empty(4 * H, dtype=torch.float32, device=x.device) for _ in range(2))
+        N.check(N.lib().srlx_lstm_backward(B, T, I, H, N.tptr(x), N.tptr(h0), N.tptr(c0), N.tptr(w_ih), N.tptr(w_hh), N.tptr(y), N.tptr(bufs["workspace"]), N.tptr(dy),
+                                           N.tptr(dh_n), N.tptr(dc_n), N.tptr(dx), N.tptr(dw_ih), N.tptr(dw_hh), N.tptr(db_ih), N.tptr(db_hh), N.tptr(dh0),
+                                           N.tptr(dc0), N.tptr(bufs["scratch"]), N.torch_stream_ptr()))
+        ctx._keep_grads = (dy, dh_n, dc_n)  # alive until the stream has run the launches
+        return None, None, dx, dh0, dc0, dw_ih, dw_hh, db_ih, db_hh
+
+
+def _dense16(t):
+    """float32, dense and 16-byte aligned (the kernels' vector loads): a view at an odd storage offset is copied."""
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class QNetwork(nn.Module):
-    """in_block per step -> UVFA concat -> LSTM -> dueling head per step (model_torch.py:18-87)."""
+    """in_block per step -> UVFA concat -> LSTM -> dueling head per step (model_torch.py:18-87).
+
+    `lstm_layer` holds the recurrent layer's parameters under torch's keys.  With `lstm_backend == "srlx"`, tensors on a GPU and a shape inside libsrlx's
+    envelope (srlx.h: B, T <= 256, I <= 16384, H a multiple of 16 up to 512) the layer runs on libsrlx's kernels; otherwise (CPU parameters,
+    `lstm_backend = "torch"`, other shapes) it is `nn.LSTM` itself.  `lstm_path` names the path of the last call."""
+
+    lstm_backend = "srlx"  # "srlx" | "torch": an attribute of the network (of the class: the default), not of the process environment
 
     def __init__(self, config: Config):
         super().__init__()
@@ -117,6 +173,33 @@ class QNetwork(nn.Module):
         self.hidden_size = config.lstm_units
         self.lstm_layer = nn.LSTM(in_size, config.lstm_units, batch_first=True)
         self.hidden_block = config.hidden_block.create_torch_block(config.lstm_units, config.action_space.n)
+        self.lstm_path = None
+        self._lstm_bufs = {}  # (device, B, T) -> workspace / scratch of that shape, allocated once
+
+    def _lstm(self, x, hidden_states):
+        m = self.lstm_layer
+        if self.lstm_backend not in ("srlx", "torch"):
+            raise ValueError(f"lstm_backend {self.lstm_backend!r}: 'srlx' or 'torch'")
+        B, T, I = x.shape
+        H = self.hidden_size
+        on_gpu = x.is_cuda and m.weight_ih_l0.is_cuda and x.dtype == torch.float32 and m.weight_ih_l0.dtype == torch.float32
+        if self.lstm_backend != "srlx" or not on_gpu or N.lib().srlx_lstm_scratch_floats(B, T, I, H, 1) < 0:
+            self.lstm_path = "torch"
+            return m(x, hidden_states)
+        self.lstm_path = "srlx"
+        key = (x.device, B, T)
+        bufs = self._lstm_bufs.get(key)
+        if bufs is None:
+            lib = N.lib()
+            bufs = self._lstm_bufs[key] = dict(workspace=None, serial=0,
+                                               scratch=torch.empty(lib.srlx_lstm_scratch_floats(B, T, I, H, 1), dtype=torch.float32, device=x.device))
+        h0, c0 = hidden_states[0][0], hidden_states[1][0]
+        params = (m.weight_ih_l0, m.weight_hh_l0, m.bias_ih_l0, m.bias_hh_l0)
+        training = torch.is_grad_enabled() and any(t.requires_grad for t in (x, h0, c0) + params)
+        if training and bufs["workspace"] is None:
+            bufs["workspace"] = torch.empty(N.lib().srlx_lstm_workspace_floats(B, T, I, H, 1), dtype=torch.float32, device=x.device)
+        y, h_n, c_n = _LstmFunction.apply(bufs, training, x, h0, c0, *params)
+        return y, (h_n.unsqueeze(0), c_n.unsqueeze(0))
 
     def forward(self, inputs, hidden_states):
         state, reward_ext, reward_int, onehot_action, onehot_actor = inputs
@@ -129,7 +212,7 @@ class QNetwork(nn.Module):
         if self.input_action:
             parts.append(onehot_action)
         parts.append(onehot_actor)
-        x, hidden_states = self.lstm_layer(torch.cat(parts, dim=2), hidden_states)
+        x, hidden_states = self._lstm(torch.cat(parts, dim=2), hidden_states)
         return self.hidden_block(x.reshape(B * S, -1)).view(B, S, -1), hidden_states
 
     def get_initial_state(self, batch_size, device):
