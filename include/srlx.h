@@ -1149,6 +1149,40 @@ int srlx_lstm_backward(int64_t B, int64_t T, int64_t I, int64_t H, const float *
                        const float *y, const float *workspace, const float *dy, const float *dh_n, const float *dc_n, float *dx, float *dw_ih, float *dw_hh,
                        float *db_ih, float *db_hh, float *dh0, float *dc0, float *scratch, void *stream);
 
+/* ---- Agent57 sequence store (srlx_seqstore.hip) ---------------------------------------------------------------------------------------------------------
+ * Batch assembly of Agent57's sequence replay (srl/algorithms/agent57/agent57.py:652-663 stores the window; model_torch.py's `train` rebuilds the batch on the
+ * host) from device-resident arrays the CALLER owns (device/sequence_store.py keeps them as torch tensors); the entry point is stateless.
+ *   ring    f32 [frame_capacity][frame_stride]: every distinct observation once; frame_stride >= frame_elems, padded by the caller to a multiple of 4 floats
+ *           so that rows start on 16 bytes.  Row offsets are 64-bit (100 000 frames of 84 x 84 floats are 2.8 GB).
+ *   records i32 [seq_capacity][record_stride]: one packed record per stored sequence, in dwords (L = burnin + sequence_length + 1, S = sequence_length):
+ *             [0, L)            frame table i32: the ring row of every step's observation; -1 = an all-zero frame (episode padding)
+ *             [L, 2L)           action indices i32
+ *             [2L, 3L), [3L,4L) r_ext, r_int f32
+ *             [4L, 4L+S)        undone f32 (0 after a terminal step)
+ *             4L+S              actor index i32
+ *             then 4 H          h_ext, c_ext, h_int, c_int f32 [H] each: both networks' recurrent state at the window head
+ *             then S A bytes    next-step invalid-action mask u8 [S][A]
+ *           srlx_seq_record_dwords(L, S, A, H) is that length rounded up to a multiple of 4 (host arithmetic; -1 outside the envelope).
+ *   slots   i64 [B]: the records to gather (repeats allowed).  A slot outside [0, seq_capacity), or a table entry outside [-1, frame_capacity), reads nothing and
+ *           yields zeros: the kernel never dereferences an index it was not given room for.
+ * Outputs, dense, in the layouts the trainer feeds its networks: states f32 [B][L][frame_elems], actions i64 [B][L], r_ext / r_int f32 [B][L], dones f32 [B][S],
+ * invalid u8 [B][S][A], actor i64 [B], h_ext / c_ext / h_int / c_int f32 [B][H].
+ * One launch, no atomics, no scratch.  Rows move as 16-byte accesses when frame_elems and frame_stride are multiples of 4 and ring and states are 16-byte aligned,
+ * as dwords otherwise (chosen per launch).  Envelope, validated before any device call (a violation returns SRLX_ERR_INVALID and srlx_last_error() names
+ * srlx_seq_gather): B 1..1024, L 2..513, 1 <= S < L, A 1..64, H 1..1024, frame_elems 1..2^20, frame_stride >= frame_elems, frame_capacity 1..2^31-1,
+ * seq_capacity >= 1, record_stride >= srlx_seq_record_dwords, no NULL pointer. */
+#define SRLX_SEQ_MAX_B 1024
+#define SRLX_SEQ_MAX_L 513
+#define SRLX_SEQ_MAX_A 64
+#define SRLX_SEQ_MAX_H 1024
+#define SRLX_SEQ_MAX_FRAME_ELEMS 1048576
+#define SRLX_SEQ_MAX_FRAME_CAPACITY 2147483647
+int64_t srlx_seq_record_dwords(int64_t L, int64_t S, int64_t A, int64_t H);
+int srlx_seq_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H, int64_t frame_elems, int64_t frame_stride, int64_t frame_capacity, int64_t seq_capacity,
+                    int64_t record_stride, const int64_t *d_slots, const float *d_ring, const int32_t *d_records, float *d_states, int64_t *d_actions,
+                    float *d_r_ext, float *d_r_int, float *d_dones, uint8_t *d_invalid, int64_t *d_actor, float *d_h_ext, float *d_c_ext, float *d_h_int,
+                    float *d_c_int, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,8 @@ SIGNATURES = {
     "srlx_lstm_scratch_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_int]),
     "srlx_lstm_forward": (c_int, [c_i64] * 4 + [c_p] * 13),
     "srlx_lstm_backward": (c_int, [c_i64] * 4 + [c_p] * 19),
+    "srlx_seq_record_dwords": (c_i64, [c_i64] * 4),
+    "srlx_seq_gather": (c_int, [c_i64] * 10 + [c_p] * 15),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

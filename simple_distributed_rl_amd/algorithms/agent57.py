@@ -20,6 +20,7 @@ from simple_distributed_rl_amd.base.rl.algorithms.base_dqn import RLConfig, RLWo
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
 from simple_distributed_rl_amd.base.rl.registration import register
 from simple_distributed_rl_amd.base.rl.trainer import RLTrainer
+from simple_distributed_rl_amd.device.sequence_store import SequenceBatch
 from simple_distributed_rl_amd.rl import functions as funcs
 from simple_distributed_rl_amd.rl.memories.priority_replay_buffer import PriorityReplayBufferConfig, RLPriorityReplayBuffer
 from simple_distributed_rl_amd.rl.models.config import DuelingNetworkConfig, HiddenBlockConfig, InputBlockConfig, RLConfigComponentFramework
@@ -99,7 +100,79 @@ register(Config(), __name__ + ":Memory", __name__ + ":Parameter", __name__ + ":T
 
 
 class Memory(RLPriorityReplayBuffer):
-    pass
+    """The reference's priority replay of whole windows, or, with `sequence_store = "device"`, the same priority memory over sequences kept in HBM
+    (device/sequence_store.py): `add` uploads what is new of the window and hands the inner `IPriorityMemory` the sequence's serial number as
+    its opaque item, so the tree, its random stream and its eviction order are what they are on the host path; `sample` returns a `SequenceBatch` of device
+    tensors assembled by one launch.  `memory.compress` has no meaning for the device store and is ignored there.
+
+    "device" needs first-in-first-out eviction (a sequence slot is serial % capacity), plain adds in the worker's order and a GPU; it refuses the rank-based
+    memories, the demo memory, serialized adds (`train_mp`) and a run without a GPU, each with its reason."""
+
+    sequence_store = "host"  # "host" | "device": an attribute of the memory (of the class: the default), like QNetwork.lstm_backend
+
+    def __init__(self, *args):
+        self._sequence_store = self.sequence_store
+        self._store = None
+        if self._sequence_store not in ("host", "device"):
+            raise ValueError(f"sequence_store {self._sequence_store!r}: 'host' or 'device'")
+        if self._sequence_store == "device":
+            self._refuse(args[0].memory)  # before the inner memory is built
+        super().__init__(*args)
+
+    @staticmethod
+    def _refuse(cfg: PriorityReplayBufferConfig) -> None:
+        if cfg.name not in ("Proportional", "Proportional_cpp", "ReplayBuffer"):
+            why = {"RankBasedLinear": "evicts its lowest priority, not its oldest item",
+                   "RankBased": "is not one of the memories the store is tested against (the reference leaves its eviction order to the implementation)"}
+            raise ValueError(f"sequence_store 'device': the {cfg.name} memory {why.get(cfg.name, 'is not known to evict first-in-first-out')}; a sequence's slot "
+                             "must follow its serial number: use Proportional, Proportional_cpp or ReplayBuffer")
+        if cfg.enable_demo_memory:
+            raise ValueError("sequence_store 'device': enable_demo_memory keeps demonstration items in a host ring of its own; use sequence_store 'host'")
+
+    def _device_store(self, item=None):
+        if self._store is None:
+            from simple_distributed_rl_amd.device.sequence_store import DeviceSequenceStore
+
+            c = self.config
+            device = require_gpu(c.used_device_torch)
+            shape = np.asarray(item[0][0]).shape if item is not None else tuple(c.observation_space.shape)
+            self._store = DeviceSequenceStore(device, self.cfg.capacity, c.burnin + c.sequence_length + 1, c.sequence_length, c.action_space.n, c.lstm_units, shape)
+        return self._store
+
+    def add(self, batch: Any, priority=None, serialized: bool = False) -> None:
+        if self._sequence_store != "device":
+            return super().add(batch, priority, serialized)
+        if serialized:
+            raise RuntimeError("sequence_store 'device': a serialized add (train_mp) arrives pickled, its frames shared with no other item; use sequence_store 'host'")
+        self.memory.add(self._device_store(batch).add(batch), priority)
+
+    def sample(self, step: int = -1, batch_size: int = -1):
+        if self._sequence_store != "device":
+            return super().sample(step, batch_size)
+        if self.memory.length() < self.cfg.warmup_size:
+            return None
+        serials, weights, update_args = self.memory.sample(batch_size if batch_size > -1 else self.batch_size, step if step > -1 else self.step)
+        return self._device_store().gather_serials(serials), np.asarray(weights, dtype=self.dtype), update_args
+
+    def call_backup(self, **kwargs):
+        data = super().call_backup(**kwargs)
+        if self._sequence_store == "device":
+            data = data + [self._store.backup() if self._store is not None else None]  # the store's own format, next to the inner memory's
+        return data
+
+    def call_restore(self, data: Any, **kwargs) -> None:
+        super().call_restore(data, **kwargs)
+        if self._sequence_store == "device":
+            if len(data) < 3:
+                raise ValueError("sequence_store 'device': this backup was taken from a 'host' memory and holds no sequence store")
+            if data[2] is not None:
+                if self._store is None:
+                    from simple_distributed_rl_amd.device.sequence_store import DeviceSequenceStore
+
+                    c, lay = self.config, data[2]["layout"]
+                    self._store = DeviceSequenceStore(require_gpu(c.used_device_torch), self.cfg.capacity, lay[0], lay[1], lay[2], lay[3], data[2]["frame_shape"],
+                                                      data[2]["ledger"]["frame_capacity"])
+                self._store.restore(data[2])
 
 
 class _LstmFunction(torch.autograd.Function):
@@ -332,31 +405,39 @@ class Trainer(RLTrainer):
             return
         batches, weights, update_args = sampled
         c, d, p = self.config, self.device, self.parameter
-        states, onehot_actions, rewards_ext, rewards_int, dones, actors, invalid_lists, hidden_ext, hidden_int = zip(*batches)
         B, A, bi, S = len(batches), c.action_space.n, c.burnin, c.sequence_length
         f32 = lambda x: torch.as_tensor(np.asarray(x, dtype=np.float32), device=d)  # noqa: E731
-        states = f32(states)  # (B, burnin + S + 1, ...)
-        r_ext, r_int = f32(rewards_ext).unsqueeze(-1), f32(rewards_int).unsqueeze(-1)
-        act_idx = torch.as_tensor(np.argmax(np.asarray(onehot_actions), axis=2).astype(np.int64), device=d)  # (B, burnin + S + 1)
+        if isinstance(batches, SequenceBatch):  # Memory.sequence_store == "device": srlx_seq_gather has assembled the batch in HBM
+            sb = batches
+            states, act_idx, actor, step_dones = sb.states, sb.act_idx, sb.actor, sb.dones
+            r_ext, r_int = sb.r_ext.unsqueeze(-1), sb.r_int.unsqueeze(-1)
+            invalid = sb.invalid if sb.any_invalid else None
+            hidden_ext, hidden_int = (sb.h_ext.unsqueeze(0), sb.c_ext.unsqueeze(0)), (sb.h_int.unsqueeze(0), sb.c_int.unsqueeze(0))
+            hid = lambda hs: hs  # noqa: E731
+        else:
+            states, onehot_actions, rewards_ext, rewards_int, dones, actors, invalid_lists, hidden_ext, hidden_int = zip(*batches)
+            states = f32(states)  # (B, burnin + S + 1, ...)
+            r_ext, r_int = f32(rewards_ext).unsqueeze(-1), f32(rewards_int).unsqueeze(-1)
+            act_idx = torch.as_tensor(np.argmax(np.asarray(onehot_actions), axis=2).astype(np.int64), device=d)  # (B, burnin + S + 1)
+            actor = torch.as_tensor(np.asarray(actors, dtype=np.int64), device=d)
+            step_dones = f32(dones)
+            inv = np.zeros((B, S, A), np.uint8)
+            any_inv = False
+            for b, per_step in enumerate(invalid_lists):
+                for t, lst in enumerate(per_step):
+                    for a in lst:
+                        inv[b, t, a] = 1
+                        any_inv = True
+            invalid = torch.from_numpy(inv).to(d) if any_inv else None
+            hid = lambda hs: (f32([h[0] for h in hs]).permute(1, 0, 2).contiguous(), f32([h[1] for h in hs]).permute(1, 0, 2).contiguous())  # noqa: E731
         onehot = self.action_eye[act_idx]
-        actor = torch.as_tensor(np.asarray(actors, dtype=np.int64), device=d)
         actor_onehot = self.actor_eye[actor].unsqueeze(1).expand(B, bi + S + 1, c.actor_num)
         in_burnin = [states[:, :bi], r_ext[:, :bi], r_int[:, :bi], onehot[:, :bi], actor_onehot[:, :bi]]
         in_steps = [states[:, bi:], r_ext[:, bi:], r_int[:, bi:], onehot[:, bi:], actor_onehot[:, bi:]]
         step_actions = act_idx[:, bi + 1 :].to(torch.int32).contiguous()  # agent57.py:237: instep actions shifted by one
         step_r_ext, step_r_int = r_ext[:, bi + 1 :, 0].contiguous(), r_int[:, bi + 1 :, 0].contiguous()
-        step_dones = f32(dones)
-        inv = np.zeros((B, S, A), np.uint8)
-        any_inv = False
-        for b, per_step in enumerate(invalid_lists):
-            for t, lst in enumerate(per_step):
-                for a in lst:
-                    inv[b, t, a] = 1
-                    any_inv = True
-        invalid = torch.from_numpy(inv).to(d) if any_inv else None
         discounts = self.discount_list[actor]
         w = f32(weights)
-        hid = lambda hs: (f32([h[0] for h in hs]).permute(1, 0, 2).contiguous(), f32([h[1] for h in hs]).permute(1, 0, 2).contiguous())  # noqa: E731
 
         self.td_ext, ext_loss = self._train_q(p.q_ext_online, p.q_ext_target, self.q_ext_optimizer, step_r_ext, hid(hidden_ext), in_burnin, in_steps, step_actions,
                                               step_dones, invalid, discounts, w)
