@@ -930,6 +930,27 @@ int srlx_qnet_backward_td_u8(srlx_qnet_t *h, int64_t batch, int n_step, const ui
                              const uint8_t *d_invalid_next, const float *d_weights, double discount, double retrace_h, int enable_double_dqn,
                              int enable_rescale, float *d_target, float *d_loss, float *d_grad_q0, float *d_priorities, float *const *d_grads, void *stream);
 int srlx_qnet_forward_f32(srlx_qnet_t *h, int64_t batch, const float *d_obs_nchw, float *d_q, void *stream);
+/* The image block over float32 frame SEQUENCES of thousands of rows (Agent57's in-block: srl/rl/torch_/blocks/dqn_image_block.py:29-54 as
+ * srl/algorithms/agent57/model_torch.py:39-87 calls it on [B * S] states), on a handle used the way srlx_qnet_forward_convs_u8's callers use it (entries 0..5 of
+ * srlx_qnet_bind are read).  Every row count takes the same launches, float32 MFMA with fixed summation orders: results are bit-identical run to run.
+ *   srlx_qnet_forward_convs_f32    : d_frames f32 [rows][H][W][C] (channels LAST, C = the handle's `window`, 1..4; C = 1 is the bytes of a channels-first stack);
+ *       row r of the features at d_features + r * ld_features: 2 F * OH3 * OW3 floats in torch's flatten order (channel-major); ld_features >= that, columns behind
+ *       the features are not touched (the rows may be the first columns of wider rows, an LSTM's input).  rows <= max_batch, <= 65536.  The post-ReLU activations
+ *       of the LAST forward stay in the handle (NHWC) for the backward pass.
+ *   srlx_qnet_seq_training_bytes   : host arithmetic, no device: the bytes srlx_qnet_enable_seq_training(h, max_rows) allocates on a handle of this geometry,
+ *       or -1 outside the envelope: filters = 32, square frames, H a multiple of 4 in 8..84, 1..4 channels, 1 <= max_rows <= 65536.
+ *   srlx_qnet_enable_seq_training  : gradient scratch for up to max_rows (<= max_batch) gradient rows; *bytes_allocated (may be NULL) = what was allocated.  Not
+ *       combined with srlx_qnet_enable_training on one handle.
+ *   srlx_qnet_backward_convs_f32   : d loss / d features of ALL `rows` rows of the LAST srlx_qnet_forward_convs_f32 on this handle (same d_frames; rows in the
+ *       same channel-major order, row stride ld_grad >= the feature count); applies the ReLU mask of the kept activations and writes d_grads[0..5] = conv1 w, b,
+ *       conv2 w, b, conv3 w, b in each parameter's own memory layout (conv2 / conv3 channels_last, as srlx_qnet_bind reads them).  Weight gradients: the rows are cut
+ *       into ceil(rows / ceil(rows / 256)) parts of consecutive rows, a part adds its rows in row order, the parts are added in part order -- one summation order per
+ *       element, no atomics: two calls on the same data give bit-equal gradients.  One stream, one launch per stage. */
+int srlx_qnet_forward_convs_f32(srlx_qnet_t *h, int64_t rows, const float *d_frames, float *d_features, int64_t ld_features, void *stream);
+int64_t srlx_qnet_seq_training_bytes(int in_h, int in_w, int channels, int filters, int64_t max_rows);
+int srlx_qnet_enable_seq_training(srlx_qnet_t *h, int64_t max_rows, int64_t *bytes_allocated);
+int srlx_qnet_backward_convs_f32(srlx_qnet_t *h, int64_t rows, const float *d_frames, const float *d_grad_features, int64_t ld_grad, float *const *d_grads,
+                                 void *stream);
 /* Several networks over the SAME frames (round 6; Agent57_light evaluates five networks on the state a lock-step has just produced: the two UVFA Q-networks of the next
  * Worker.policy, agent57_light.py:355-363, and the embedding / RND networks of the intrinsic reward, :383-391):
  *   srlx_qnet_forward_convs_multi_u8 : the image blocks of `n` <= 8 inference handles (84 x 84 x 4, operand planes valid, batch >= 512 in multiples of 128) as ONE

@@ -135,6 +135,10 @@ SIGNATURES = {
     "srlx_qnet_fuse_adam_rest": (c_int, [c_p, c_p, c_p, c_p]),
     "srlx_qnet_backward_u8": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "srlx_qnet_backward_convs_u8": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_qnet_forward_convs_f32": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p]),
+    "srlx_qnet_seq_training_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_i64]),
+    "srlx_qnet_enable_seq_training": (c_int, [c_p, c_i64, c_p]),
+    "srlx_qnet_backward_convs_f32": (c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_p]),
     "srlx_qnet_backward_td_u8": (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_qnet_forward_f32": (c_int, [c_p, c_i64, c_p, c_p, c_p]),
     "srlx_qnet_bind_noisy": (c_int, [c_p, c_p, c_u64]),

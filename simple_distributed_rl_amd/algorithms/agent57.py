@@ -230,9 +230,15 @@ class QNetwork(nn.Module):
 
     `lstm_layer` holds the recurrent layer's parameters under torch's keys.  With `lstm_backend == "srlx"`, tensors on a GPU and a shape inside libsrlx's
     envelope (srlx.h: B, T <= 256, I <= 16384, H a multiple of 16 up to 512) the layer runs on libsrlx's kernels; otherwise (CPU parameters,
-    `lstm_backend = "torch"`, other shapes) it is `nn.LSTM` itself.  `lstm_path` names the path of the last call."""
+    `lstm_backend = "torch"`, other shapes) it is `nn.LSTM` itself.  `lstm_path` names the path of the last call.
+
+    `in_block_backend` chooses the image block's path the same way: with "srlx", float32 GPU tensors and a DQN block inside libsrlx's envelope (ReLU, 32
+    filters, square frames with H a multiple of 4 in 8..84, 1..4 channels) the block runs on `device/qnet.py:SeqImageTrunk` and writes its
+    features straight into the LSTM's input rows; otherwise, and with the default "torch", it is the torch module itself.  `in_block_path` names the path of
+    the last call and `why_not_srlx_in_block` why a request for "srlx" was not served (None when it was, or was not made)."""
 
     lstm_backend = "srlx"  # "srlx" | "torch": an attribute of the network (of the class: the default), not of the process environment
+    in_block_backend = "torch"  # "torch" | "srlx"
 
     def __init__(self, config: Config):
         super().__init__()
@@ -248,6 +254,47 @@ class QNetwork(nn.Module):
         self.hidden_block = config.hidden_block.create_torch_block(config.lstm_units, config.action_space.n)
         self.lstm_path = None
         self._lstm_bufs = {}  # (device, B, T) -> workspace / scratch of that shape, allocated once
+        self.in_block_path = None
+        self.why_not_srlx_in_block = None
+        self._in_block_rows = config.batch_size * max(config.sequence_length + 1, config.burnin)  # the trainer's largest pass (the worker's acting pass is one row)
+        self._trunk = None  # created on the first call that is served by libsrlx
+
+    def _in_block_trunk(self, state):
+        """The SeqImageTrunk that serves this call, or None with `why_not_srlx_in_block` set."""
+        from simple_distributed_rl_amd.device.qnet import ImageTrunk, SeqImageTrunk
+
+        def no(why):
+            self.why_not_srlx_in_block = why
+            return None
+
+        block = getattr(self.in_block, "image_block", None)
+        if block is None or not getattr(self.in_block, "out_flatten", False):
+            return no("the input block is not a flattened image block")
+        if not ImageTrunk.supported(block):
+            return no("the image block is not the DQN block with ReLU activations")
+        convs = list(block.image_layers)[0::2]
+        w = convs[0].weight
+        if not (state.is_cuda and w.is_cuda and state.dtype == torch.float32 and w.dtype == torch.float32):
+            return no("the parameters or the states are not float32 tensors on a GPU")
+        if convs[0].out_channels != 32:
+            return no(f"{convs[0].out_channels} filters: the backward kernels cover the 32 / 64 / 64-filter block")
+        hw, C = tuple(self.in_block.in_shape[:2]), int(self.in_block.in_shape[2])
+        rows = state.shape[0] * state.shape[1]
+        if tuple(state.shape[2:]) not in ((hw[0], hw[1], C),) + (((hw[0], hw[1]),) if C == 1 else ()):
+            return no(f"states of shape {tuple(state.shape[2:])} are not the block's {hw[0]} x {hw[1]} x {C} frames")
+        if self._trunk is not None and self._trunk.dev != w.device:
+            self._trunk = None  # the network moved to another device
+        if self._trunk is None:
+            max_rows = self._in_block_rows
+            if SeqImageTrunk.seq_training_bytes(hw, C, 32, max_rows) < 0:
+                return no(f"{hw[0]} x {hw[1]} x {C} frames or {max_rows} rows are outside the kernels' envelope")
+            if rows > max_rows:
+                return no(f"{rows} rows: the handle is built for {max_rows}")
+            self._trunk = SeqImageTrunk(block, hw, max_rows, device=w.device.index or 0)
+        if rows > self._trunk.max_rows:
+            return no(f"{rows} rows: the handle was built for {self._trunk.max_rows}")
+        self.why_not_srlx_in_block = None
+        return self._trunk
 
     def _lstm(self, x, hidden_states):
         m = self.lstm_layer
@@ -277,15 +324,31 @@ class QNetwork(nn.Module):
     def forward(self, inputs, hidden_states):
         state, reward_ext, reward_int, onehot_action, onehot_actor = inputs
         B, S = state.shape[:2]
-        parts = [self.in_block(state.reshape((B * S,) + tuple(state.shape[2:]))).view(B, S, -1)]
-        if self.input_ext_reward:
-            parts.append(reward_ext)
-        if self.input_int_reward:
-            parts.append(reward_int)
-        if self.input_action:
-            parts.append(onehot_action)
-        parts.append(onehot_actor)
-        x, hidden_states = self._lstm(torch.cat(parts, dim=2), hidden_states)
+        if self.in_block_backend not in ("srlx", "torch"):
+            raise ValueError(f"in_block_backend {self.in_block_backend!r}: 'srlx' or 'torch'")
+        self.why_not_srlx_in_block = None
+        trunk = self._in_block_trunk(state) if self.in_block_backend == "srlx" else None
+        extras = ([reward_ext] if self.input_ext_reward else []) + ([reward_int] if self.input_int_reward else []) + \
+                 ([onehot_action] if self.input_action else []) + [onehot_actor]
+        if trunk is not None:
+            # the LSTM's input rows [B S][I]: the small UVFA columns first (plain copies, no gradient flows into them), then the features into the first
+            # columns by the trunk, in place -- no torch.cat copy of the wide rows
+            self.in_block_path = "srlx"
+            F_, I = trunk.n_features, self.lstm_layer.input_size
+            x = torch.empty((B * S, I), dtype=torch.float32, device=state.device)
+            col = F_
+            with torch.no_grad():
+                for e in extras:
+                    n = e.shape[2]
+                    x[:, col : col + n] = e.reshape(B * S, n)
+                    col += n
+            assert col == I
+            frames = state.reshape((B * S,) + tuple(state.shape[2:])).contiguous()
+            x = trunk.features(frames if frames.data_ptr() % 16 == 0 else frames.clone(), out=x).view(B, S, I)
+        else:
+            self.in_block_path = "torch"
+            x = torch.cat([self.in_block(state.reshape((B * S,) + tuple(state.shape[2:]))).view(B, S, -1)] + extras, dim=2)
+        x, hidden_states = self._lstm(x, hidden_states)
         return self.hidden_block(x.reshape(B * S, -1)).view(B, S, -1), hidden_states
 
     def get_initial_state(self, batch_size, device):

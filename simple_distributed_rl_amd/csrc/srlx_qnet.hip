@@ -830,6 +830,44 @@ struct ANchw {
     }
 };
 
+// float32 frames in channels-LAST memory [rows][H][W][C] (Agent57's states as the replay holds them); k = c * 64 + ky * 8 + kx, conv1's torch weight
+// order like ANchw / AU8 (a 32-wide slab never straddles a channel); replicate padding.  C = 1 addresses the same bytes ANchw does.
+struct ANhwc {
+    const float *in;
+    int C, H, W, S, P, OH, OW;
+    struct Row {
+        const float *img;
+        int iy0, ix0;
+    };
+    __device__ __forceinline__ Row row(i64 m, i64 M) const {
+        if (m >= M) return Row{nullptr, 0, 0};
+        const int per = OH * OW;
+        const i64 b = m / per;
+        const int pix = (int)(m % per);
+        return Row{in + b * (i64)H * W * C, (pix / OW) * S - P, (pix % OW) * S - P};
+    }
+    __device__ __forceinline__ float4 load4(const Row &r, int k0, int c4) const {
+        if (!r.img) return make_float4(0.f, 0.f, 0.f, 0.f);
+        const int c = k0 >> 6, ky = ((k0 & 63) + c4) >> 3, kx = c4 & 7;  // 8x8 kernel
+        const float *row = r.img + (i64)clampi(r.iy0 + ky, 0, H - 1) * W * C + c;
+        const int x = r.ix0 + kx;
+        return make_float4(row[clampi(x, 0, W - 1) * C], row[clampi(x + 1, 0, W - 1) * C], row[clampi(x + 2, 0, W - 1) * C], row[clampi(x + 3, 0, W - 1) * C]);
+    }
+};
+
+// act3 rows [P pixels][CH channels] (NHWC) -> feature rows in torch's flatten order [CH][P] at out + r * ld, through LDS (rows of CH + 1 floats: the
+// transposed reads of a wave fall into different banks).  One workgroup per row; columns >= CH * P of an output row are not touched.
+__global__ void __launch_bounds__(256) k_features_out(const float *__restrict__ act3, int P, int CH, float *__restrict__ out, i64 ld) {
+    extern __shared__ float tr[];
+    const i64 r = blockIdx.x;
+    const int flat = P * CH;
+    const float *src = act3 + r * flat;
+    for (int idx = threadIdx.x; idx < flat; idx += 256) tr[(idx / CH) * (CH + 1) + idx % CH] = src[idx];
+    __syncthreads();
+    float *dst = out + r * ld;
+    for (int idx = threadIdx.x; idx < flat; idx += 256) dst[idx] = tr[(idx % P) * (CH + 1) + idx / P];
+}
+
 
 // data gradient of a convolution as implicit GEMMs over the PADDED input grid (replicate padding = an explicit pad
 // followed by a plain convolution, so its gradient is the plain transposed convolution on the padded grid; the caller
@@ -1475,6 +1513,28 @@ int srlx_qnet_forward_f32(srlx_qnet_t *h, int64_t batch, const float *d_obs_nchw
     ANchw c1{d_obs_nchw, h->Wn, h->H, h->W, 4, 3, h->OH1, h->OW1};
     launch_gemm<ANchw, 32, true, false>(c1, h->w1, h->b1, h->act1, batch * h->OH1 * h->OW1, h->F1, h->Wn * 64, 1, st);
     return run_tail(h, batch, d_q, st);
+}
+
+// The image block over float32 frame sequences: conv1 by the general implicit GEMM with the channels-last loader, conv2 / conv3 by run_tail's two
+// launches (every row count takes the same kernels: float32 MFMA, fixed k order), then ONE transposing launch from the kept NHWC act3 to the caller's feature rows.
+int srlx_qnet_forward_convs_f32(srlx_qnet_t *h, int64_t rows, const float *d_frames, float *d_features, int64_t ld_features, void *stream) {
+    SRLX_REQUIRE(h && d_frames && d_features, "qnet_forward_convs_f32: NULL argument");
+    SRLX_REQUIRE(h->w1, "qnet_forward_convs_f32: no parameters bound (srlx_qnet_bind)");
+    SRLX_REQUIRE(rows > 0 && rows <= h->max_batch && rows <= kSeqMaxRows, "qnet_forward_convs_f32: %lld rows exceed max_batch %lld", (long long)rows, (long long)h->max_batch);
+    SRLX_REQUIRE(ld_features >= h->flat, "qnet_forward_convs_f32: ld_features %lld is below the %d features of a row", (long long)ld_features, h->flat);
+    SRLX_REQUIRE(h->Wn <= 4 && (size_t)h->OH3 * h->OW3 * (2 * h->F1 + 1) * sizeof(float) <= 64 * 1024, "qnet_forward_convs_f32: 1..4 channels, a feature row within 64 KB of LDS");
+    srlx::DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    h->wt_from_forward = false;
+    h->seq_fwd_rows = 0;
+    ANhwc c1{d_frames, h->Wn, h->H, h->W, 4, 3, h->OH1, h->OW1};
+    launch_gemm<ANhwc, 32, true, false>(c1, h->w1, h->b1, h->act1, rows * h->OH1 * h->OW1, h->F1, h->Wn * 64, 1, st);
+    SRLX_TRY(run_tail(h, rows, nullptr, st));
+    const int P = h->OH3 * h->OW3, CH = 2 * h->F1;
+    hipLaunchKernelGGL(k_features_out, dim3((unsigned)rows), dim3(256), (size_t)P * (CH + 1) * sizeof(float), st, h->act3, P, CH, d_features, (i64)ld_features);
+    SRLX_HIP(hipGetLastError());
+    h->seq_fwd_rows = rows;
+    return SRLX_OK;
 }
 
 }  // extern "C"

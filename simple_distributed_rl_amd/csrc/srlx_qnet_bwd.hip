@@ -1103,3 +1103,209 @@ int srlx_qnet_backward_td_u8(srlx_qnet_t *h, int64_t batch, int n_step, const ui
 }
 
 }  // extern "C"
+
+// ---- float32 frame sequences of thousands of rows (Agent57's in-block) --------------------------------------------------------------------------
+namespace {
+
+// Weight gradient of one convolution over MANY rows, on the matrix cores.  The rows are cut into parts of `rpp` consecutive rows (srlx_qnet_int.h: rpp =
+// ceil(rows / kSeqParts)); blockIdx.y is the part.  One wave per (part, 32 x 32 tile of the weight): it walks ITS rows in row order and, inside a row, the output
+// pixels in order, two per v_mfma_f32_32x32x2_f32, into ONE accumulator -- an element's partial sum has one order; the parts are then added in part order by
+// k_reduce_parts<false>.  No atomics, no LDS, no barriers; operands come straight from global memory eight steps ahead of their MFMAs (k_conv_wgrad_mfma's pipeline,
+// restarted per row).
+//   NCI = 1 / 2 (conv2 / conv3): X is an NHWC activation with 32 NCI channels, dY has 64 channels; tile = (tap, half of the output channels, 32 input channels);
+//       part[p][co][tap][ci] (channels_last, the parameter's own layout).
+//   NCI = 0 (conv1): X is the float32 frames [H][W][C], dY has 32 channels; tile = 32 consecutive k = c * 64 + ky * 8 + kx (lane i owns ITS tap: half a channel's
+//       kernel rows); part[p][co][k] (torch's contiguous conv weight).
+struct SeqGeo {
+    int H, W, CI, OH, OW, KH, KW, S, P;  // input grid (conv1: the frame, CI = C), output grid, kernel, stride, padding
+};
+template <int NCI>
+__global__ void __launch_bounds__(256) k_wgrad_seq(SeqGeo g, const float *__restrict__ X, const float *__restrict__ dY, float *__restrict__ part,
+                                                   float *__restrict__ bias_part /*[part][CO]*/, i64 rows, int rpp) {
+    constexpr bool kFrames = NCI == 0;
+    constexpr int CO = kFrames ? 32 : 64;
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int combo = blockIdx.x * 4 + (threadIdx.x >> 6), taps = g.KH * g.KW;
+    const int ncombo = kFrames ? 2 * g.CI : taps * 2 * NCI;
+    if (combo >= ncombo) return;  // (wave-uniform)
+    int ky, kx, cot = 0, xoff, tap = 0, cit = 0;
+    if (kFrames) {
+        const int k = combo * 32 + i;
+        xoff = k >> 6, ky = (k & 63) >> 3, kx = k & 7;
+    } else {
+        cit = combo % (NCI ? NCI : 1), cot = (combo / (NCI ? NCI : 1)) & 1, tap = combo / (2 * (NCI ? NCI : 1));
+        ky = tap / g.KW, kx = tap % g.KW, xoff = cit * 32 + i;
+    }
+    const i64 p = blockIdx.y, b_lo = p * rpp, b_hi = b_lo + rpp < rows ? b_lo + rpp : rows;
+    const int per_img = g.OH * g.OW, steps = (per_img + 1) / 2;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+    float bsum = 0.f;
+    for (i64 b = b_lo; b < b_hi; b++) {
+        const float *pa = dY + b * per_img * CO + cot * 32 + i;
+        const float *px = X + b * (i64)g.H * g.W * g.CI + xoff;
+        int m = h, oy = 0, ox = h;  // this lane's pixel of the next step to fetch (OW >= 2)
+        float a0[8], x0[8], a1[8], x1[8];
+        auto fetch = [&](float *a, float *x) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const bool live = m < per_img;
+                const int iy = clampi(oy * g.S + ky - g.P, 0, g.H - 1), ix = clampi(ox * g.S + kx - g.P, 0, g.W - 1);
+                a[q] = live ? pa[(i64)m * CO] : 0.f;
+                x[q] = live ? px[((i64)iy * g.W + ix) * g.CI] : 0.f;
+                m += 2, ox += 2;
+                if (ox >= g.OW) ox -= g.OW, oy++;
+            }
+        };
+        auto mfma8 = [&](const float *a, const float *x) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                bsum += a[q];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], x[q], acc, 0, 0, 0);
+            }
+        };
+        fetch(a0, x0);
+        for (int s0 = 0; s0 < steps; s0 += 16) {
+            if (s0 + 8 < steps) fetch(a1, x1);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma8(a0, x0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (s0 + 8 >= steps) break;
+            if (s0 + 16 < steps) fetch(a0, x0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma8(a1, x1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int co = cot * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;  // C/D layout: row = output channel, column = input channel / tap
+        if (kFrames)
+            part[(p * CO + co) * ((i64)g.CI * 64) + combo * 32 + i] = acc[r];
+        else
+            part[((p * CO + co) * taps + tap) * g.CI + cit * 32 + i] = acc[r];
+    }
+    if (kFrames ? combo == 0 : (tap == 0 && cit == 0)) {  // bias gradient of this part: the dY column sums the A operand already walked (even pixels + odd pixels)
+        const float tot = bsum + __shfl_xor(bsum, 32);
+        if (h == 0) bias_part[p * CO + cot * 32 + i] = tot;
+    }
+}
+
+// d loss / d features, rows in torch's flatten order [CH][P] at g + r * ld  ->  dact3 rows [P][CH] (NHWC) under the ReLU mask of the kept act3; through LDS
+// like k_features_out (srlx_qnet.hip), one workgroup per row
+__global__ void __launch_bounds__(256) k_seq_grad_in(const float *__restrict__ gy, i64 ld, const float *__restrict__ act3, int P, int CH, float *__restrict__ dact3) {
+    extern __shared__ float tr[];
+    const i64 r = blockIdx.x;
+    const int flat = P * CH;
+    const float *src = gy + r * ld;
+    for (int idx = threadIdx.x; idx < flat; idx += 256) tr[(idx % P) * (CH + 1) + idx / P] = src[idx];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < flat; idx += 256) dact3[r * flat + idx] = act3[r * flat + idx] > 0.f ? tr[(idx / CH) * (CH + 1) + idx % CH] : 0.f;
+}
+
+struct SeqSizes {
+    size_t dact3, dact2, dact1, dxpad, w_t, w_t2, w_part, part_stride;  // floats
+    size_t bytes() const { return (dact3 + dact2 + dact1 + dxpad + w_t + w_t2 + w_part) * sizeof(float); }
+};
+// false outside the envelope: the DQN block with 32 filters on square frames, H a multiple of 4 in 8..84, 1..4 channels, 1..kSeqMaxRows rows
+bool seq_sizes(int H, int W, int C, int F1, i64 rows, SeqSizes *z) {
+    if (F1 != 32 || H != W || H % 4 != 0 || H < 8 || H > 84 || C < 1 || C > 4 || rows < 1 || rows > kSeqMaxRows) return false;
+    const size_t OH1 = (size_t)(H + 6 - 8) / 4 + 1, OH2 = (OH1 + 4 - 4) / 2 + 1, OH3 = OH2, R = (size_t)rows;
+    z->dact3 = R * OH3 * OH3 * 64, z->dact2 = R * OH2 * OH2 * 64, z->dact1 = R * OH1 * OH1 * 32;
+    const size_t q = (OH1 + 5) / 2, pad2 = 4 * q * q * 32, pad3 = (OH2 + 2) * (OH2 + 2) * 64;  // conv2: four parity classes of the padded grid; conv3: the padded grid
+    z->dxpad = R * (pad2 > pad3 ? pad2 : pad3) + 128 * 64;
+    z->w_t = (size_t)64 * 9 * 64, z->w_t2 = (size_t)64 * 16 * 32;
+    const size_t c1 = (size_t)32 * C * 64;
+    z->part_stride = z->w_t > c1 ? z->w_t : c1;  // (conv3's is the largest of the three at every C <= 4; kept general)
+    z->w_part = (size_t)kSeqParts * (z->part_stride + 64);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t srlx_qnet_seq_training_bytes(int in_h, int in_w, int channels, int filters, int64_t max_rows) {
+    SeqSizes z;
+    return seq_sizes(in_h, in_w, channels, filters, max_rows, &z) ? (int64_t)z.bytes() : -1;
+}
+
+int srlx_qnet_enable_seq_training(srlx_qnet_t *h, int64_t max_rows, int64_t *bytes_allocated) {
+    SRLX_REQUIRE(h, "qnet_enable_seq_training: NULL handle");
+    SeqSizes z;
+    SRLX_REQUIRE(seq_sizes(h->H, h->W, h->Wn, h->F1, max_rows, &z),
+                 "qnet_enable_seq_training: outside the envelope (32 filters, square frames, H a multiple of 4 in 8..84, 1..4 channels, 1..%lld rows)", (long long)kSeqMaxRows);
+    SRLX_REQUIRE(max_rows <= h->max_batch, "qnet_enable_seq_training: max_rows %lld exceeds max_batch %lld", (long long)max_rows, (long long)h->max_batch);
+    SRLX_REQUIRE(h->max_train == 0 && h->seq_rows == 0, "qnet_enable_seq_training: the handle already has gradient scratch");
+    srlx::DeviceGuard guard(h->device);
+    struct {
+        float **p;
+        size_t n;
+    } bufs[] = {{&h->dact3, z.dact3}, {&h->dact2, z.dact2}, {&h->dact1, z.dact1}, {&h->dxpad, z.dxpad}, {&h->w_t, z.w_t}, {&h->w_t2, z.w_t2}, {&h->w_part, z.w_part}};
+    size_t total = 0;
+    for (auto &b : bufs) {
+        hipError_t e = hipMalloc((void **)b.p, b.n * sizeof(float));
+        if (e != hipSuccess) {
+            srlx::set_error("qnet_enable_seq_training: %s", hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? SRLX_ERR_NOMEM : SRLX_ERR_HIP;
+        }
+        total += b.n * sizeof(float);
+    }
+    h->w_part_floats = z.w_part;
+    h->seq_rows = max_rows;
+    if (bytes_allocated) *bytes_allocated = (int64_t)total;
+    return SRLX_OK;
+}
+
+// One stream, one launch per stage: gradient in -> [conv3: weight gradient, parts reduced; data gradient GEMM + pad fold] -> [conv2: the same] -> conv1's weight
+// gradient from the frames.  The weight-gradient scratch is shared by the three layers (stream order).
+int srlx_qnet_backward_convs_f32(srlx_qnet_t *h, int64_t rows, const float *d_frames, const float *d_grad_features, int64_t ld_grad, float *const *g, void *stream) {
+    SRLX_REQUIRE(h && d_frames && d_grad_features && g, "qnet_backward_convs_f32: NULL argument");
+    SRLX_REQUIRE(h->seq_rows > 0, "qnet_backward_convs_f32: call srlx_qnet_enable_seq_training first");
+    SRLX_REQUIRE(rows > 0 && rows <= h->seq_rows, "qnet_backward_convs_f32: %lld rows exceed the %lld the scratch was sized for", (long long)rows, (long long)h->seq_rows);
+    SRLX_REQUIRE(rows == h->seq_fwd_rows, "qnet_backward_convs_f32: the last srlx_qnet_forward_convs_f32 on this handle had %lld rows, not %lld", (long long)h->seq_fwd_rows,
+                 (long long)rows);
+    SRLX_REQUIRE(ld_grad >= h->flat, "qnet_backward_convs_f32: ld_grad %lld is below the %d features of a row", (long long)ld_grad, h->flat);
+    for (int i = 0; i < 6; i++) SRLX_REQUIRE(g[i], "qnet_backward_convs_f32: gradient buffer %d is NULL", i);
+    srlx::DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = (int)rows, C2 = 2 * h->F1, P3 = h->OH3 * h->OW3;
+    SeqSizes z;
+    SRLX_REQUIRE(seq_sizes(h->H, h->W, h->Wn, h->F1, h->seq_rows, &z), "qnet_backward_convs_f32: handle outside the envelope");
+    const int rpp = (int)((rows + kSeqParts - 1) / kSeqParts), parts = (int)((rows + rpp - 1) / rpp);
+    float *bias_part = h->w_part + (size_t)kSeqParts * z.part_stride;
+    auto reduce = [&](i64 n_, float *gw_, int nb_, float *gb_) {
+        hipLaunchKernelGGL(k_reduce_parts<false>, dim3((unsigned)((n_ + nb_ + 255) / 256)), dim3(256), 0, st, h->w_part, parts, n_, gw_, bias_part, nb_, gb_);
+    };
+    hipLaunchKernelGGL(k_seq_grad_in, dim3((unsigned)B), dim3(256), (size_t)P3 * (C2 + 1) * sizeof(float), st, d_grad_features, (i64)ld_grad, h->act3, P3, C2, h->dact3);
+    hipLaunchKernelGGL(k_transpose_filter, dim3((unsigned)((C2 * 9 * C2 + 255) / 256)), dim3(256), 0, st, h->w3, C2, 3, 3, 1, C2, h->w_t);
+    hipLaunchKernelGGL(k_transpose_filter, dim3((unsigned)((C2 * 16 * h->F1 + 255) / 256)), dim3(256), 0, st, h->w2, C2, 4, 4, 2, h->F1, h->w_t2);
+    {   // conv3 (3x3 stride 1 pad 1, act2 -> act3)
+        SeqGeo g3{h->OH2, h->OW2, C2, h->OH3, h->OW3, 3, 3, 1, 1};
+        hipLaunchKernelGGL(k_wgrad_seq<2>, dim3((9 * 2 * 2 + 3) / 4, (unsigned)parts), dim3(256), 0, st, g3, h->act2, h->dact3, h->w_part, bias_part, (i64)rows, rpp);
+        reduce((i64)C2 * 9 * C2, g[4], C2, g[5]);
+        const int HP = h->OH2 + 2, WP = h->OW2 + 2;
+        SRLX_TRY(srlx_qnet_dgrad_gemm(h->dact3, B, HP, WP, h->OH3, h->OW3, C2, 3, 3, 1, h->w_t, C2, h->dxpad, st, 1));
+        const i64 tot = (i64)B * h->OH2 * h->OW2 * C2;
+        hipLaunchKernelGGL(k_fold_pad, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, st, B, (i64)1, h->OH2, h->OW2, C2, 1, HP, WP, 1, HP, WP, h->dxpad, h->act2, h->dact2, 1, (i64)0);
+    }
+    {   // conv2 (4x4 stride 2 pad 2, act1 -> act2)
+        SeqGeo g2{h->OH1, h->OW1, h->F1, h->OH2, h->OW2, 4, 4, 2, 2};
+        hipLaunchKernelGGL(k_wgrad_seq<1>, dim3((16 * 2 * 1 + 3) / 4, (unsigned)parts), dim3(256), 0, st, g2, h->act1, h->dact2, h->w_part, bias_part, (i64)rows, rpp);
+        reduce((i64)C2 * 16 * h->F1, g[2], C2, g[3]);
+        const int HP = h->OH1 + 4, WP = h->OW1 + 4, QH = (HP + 1) / 2, QW = (WP + 1) / 2;
+        SRLX_TRY(srlx_qnet_dgrad_gemm(h->dact2, B, QH, QW, h->OH2, h->OW2, C2, 4, 4, 2, h->w_t2, h->F1, h->dxpad, st));
+        const i64 tot = (i64)B * h->OH1 * h->OW1 * h->F1;
+        hipLaunchKernelGGL(k_fold_pad, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, st, B, (i64)1, h->OH1, h->OW1, h->F1, 2, HP, WP, 2, QH, QW, h->dxpad, h->act1, h->dact1, 1, (i64)0);
+    }
+    {   // conv1 (8x8 stride 4 pad 3, frames -> act1)
+        SeqGeo g1{h->H, h->W, h->Wn, h->OH1, h->OW1, 8, 8, 4, 3};
+        hipLaunchKernelGGL(k_wgrad_seq<0>, dim3((unsigned)((2 * h->Wn + 3) / 4), (unsigned)parts), dim3(256), 0, st, g1, d_frames, h->dact1, h->w_part, bias_part, (i64)rows, rpp);
+        reduce((i64)32 * h->Wn * 64, g[0], 32, g[1]);
+    }
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+}  // extern "C"

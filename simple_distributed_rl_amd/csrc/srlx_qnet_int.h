@@ -130,6 +130,9 @@ struct srlx_qnet {
     int head_mode, out_cols;
     const float *ln_w, *ln_b;
     float ln_eps;
+    // float32 frame sequences of thousands of rows (srlx_qnet_enable_seq_training): gradient scratch for seq_rows rows in dact3 / dact2 / dact1 /
+    // dxpad / w_t / w_t2 / w_part above; seq_fwd_rows = rows of the last srlx_qnet_forward_convs_f32 (what the next backward pass must be handed)
+    int64_t seq_rows, seq_fwd_rows;
 };
 
 // what the head kernels need of srlx_qnet::Uvfa, by value
@@ -191,3 +194,8 @@ int srlx_fc1_planes_gemm(srlx_qnet *h, int64_t rows, int splits, int kps, hipStr
 // implicit-GEMM data gradient on the matrix cores (defined next to k_gemm in srlx_qnet.hip)
 int srlx_qnet_dgrad_gemm(const float *dY, int B, int QH, int QW, int OH, int OW, int CO, int KH, int KW, int S, const float *wT, int CI, float *dXq,
                          hipStream_t st, int ksplits = 1);
+
+// float32 frame sequences: the partition of `rows` gradient rows into parts of consecutive rows for the weight-gradient kernels (srlx_qnet_bwd.hip).
+// The rule: rows_per_part = ceil(rows / kSeqParts), parts = ceil(rows / rows_per_part) <= kSeqParts -- a function of `rows` alone.
+constexpr int kSeqParts = 256;
+constexpr int64_t kSeqMaxRows = 65536;

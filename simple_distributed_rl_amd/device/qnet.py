@@ -735,6 +735,121 @@ class TrainableImageTrunk(ImageTrunk):
         return _TrunkFunction.apply(self, frame_base_ptr, frame_off, grad_stride, *ps)
 
 
+class _SeqTrunkFunction(torch.autograd.Function):
+    """out[:, :features] = image_block(frames).flatten(1) with the forward AND the backward in libsrlx (srlx_qnet_forward_convs_f32 / srlx_qnet_backward_convs_f32).
+    `out` [rows][ld] is written in place (columns behind the features keep what they hold) and returned; the six convolution parameters are inputs only so
+    that autograd routes their gradients through `backward`; the kernels read them by address."""
+
+    @staticmethod
+    def forward(ctx, trunk, frames, out, w1, b1, w2, b2, w3, b3):
+        rows = frames.shape[0]
+        N.check(trunk.lib.srlx_qnet_forward_convs_f32(trunk.h, rows, N.tptr(frames), N.tptr(out), out.stride(0), N.torch_stream_ptr()))
+        trunk.serial += 1  # the handle's kept activations are now this pass's
+        ctx.trunk, ctx.frames, ctx.serial = trunk, frames, trunk.serial
+        ctx.mark_dirty(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        t = ctx.trunk
+        if t.serial != ctx.serial:
+            raise RuntimeError("SeqImageTrunk: another forward ran on this handle before this pass's backward; the activations it kept are gone")
+        g = g.contiguous()
+        assert g.dtype == torch.float32 and g.stride(1) == 1
+        grads = [torch.empty_like(p) for p in t.params()]  # each in its parameter's own memory format (channels_last conv2 / conv3)
+        arr = (N.c_p * 6)(*[b.data_ptr() for b in grads])
+        N.check(t.lib.srlx_qnet_backward_convs_f32(t.h, g.shape[0], N.tptr(ctx.frames), N.tptr(g), g.stride(0), ctypes.cast(arr, N.c_p), N.torch_stream_ptr()))
+        ctx._keep = g  # alive until the stream has run the launches
+        return (None, None, None) + tuple(grads)
+
+
+class SeqImageTrunk:
+    """The image block of a torch network (DQNImageBlock) over float32 frame SEQUENCES [rows][H][W][C] of thousands of rows, forward and backward in libsrlx
+     -- Agent57's in-block without MIOpen.  A sibling of `TrainableImageTrunk`: the same handle and binding (parameters by address, re-bound
+    when re-homed; conv2 / conv3 weights switched to channels_last memory once, here), other entry points: float32 frames instead of the uint8 ring, every
+    row carries gradient, and the features land in torch's flatten order inside rows of the caller's choice (`out`, e.g. the first columns of an LSTM's input).
+
+    The handle is forward-only until the first `features` call with gradient enabled, which allocates the gradient scratch (`seq_training_bytes`): a target
+    network, only ever called under no_grad, never pays for it."""
+
+    @staticmethod
+    def seq_training_bytes(hw, channels: int, filters: int, max_rows: int) -> int:
+        """Host arithmetic: bytes of gradient scratch for max_rows rows, or -1 outside the kernels' envelope."""
+        return int(N.lib().srlx_qnet_seq_training_bytes(int(hw[0]), int(hw[1]), int(channels), int(filters), int(max_rows)))
+
+    def __init__(self, image_block, hw, max_rows: int, device: int = 0):
+        assert ImageTrunk.supported(image_block)
+        self.lib = N.lib()
+        self.convs = list(image_block.image_layers)[0::2]
+        c1 = self.convs[0]
+        self.hw, self.in_channels, self.max_rows = (int(hw[0]), int(hw[1])), c1.in_channels, int(max_rows)
+        if self.seq_training_bytes(self.hw, c1.in_channels, c1.out_channels, self.max_rows) < 0:
+            raise ValueError(f"SeqImageTrunk: {self.hw} x {c1.in_channels} frames, {c1.out_channels} filters, {max_rows} rows are outside the kernels' envelope")
+        self.dev = torch.device(f"cuda:{device}")
+        for conv in self.convs[1:]:
+            conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
+        hh = N.c_p()
+        N.check(self.lib.srlx_qnet_create(ctypes.byref(hh), self.hw[0], self.hw[1], c1.in_channels, c1.out_channels, 32, 1, 0, self.max_rows, int(device)))
+        self.h = hh
+        self._owner_thread = threading.get_ident()
+        _LIVE_HANDLES.add(self)
+        self._unused = torch.zeros(64, dtype=torch.float32, device=self.dev)  # the dense-layer entries of srlx_qnet_bind (never read)
+        oh = [self.hw[0]]
+        for k, s_, p_ in ((8, 4, 3), (4, 2, 2), (3, 1, 1)):
+            oh.append((oh[-1] + 2 * p_ - k) // s_ + 1)
+        self.channels, self.pixels = 2 * c1.out_channels, oh[-1] * oh[-1]
+        self.n_features = self.channels * self.pixels
+        self.serial = 0  # forwards run on the handle (each replaces the kept activations)
+        self.training_bytes = 0  # > 0 once the gradient scratch exists
+        self.bind()
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                torch.cuda.synchronize(self.dev)
+            except Exception:
+                pass
+            self.lib.srlx_qnet_destroy(self.h)
+            self.h = None
+
+    def params(self):
+        return [t for c in self.convs for t in (c.weight, c.bias)]
+
+    def bind(self):
+        ps = self.params()
+        assert all(p.is_cuda and p.dtype == torch.float32 for p in ps)
+        arr = (N.c_p * 12)(*([p.data_ptr() for p in ps] + [self._unused.data_ptr()] * 6))
+        N.check(self.lib.srlx_qnet_bind(self.h, ctypes.cast(arr, N.c_p)))
+        self._bound = [p.data_ptr() for p in ps]
+
+    def enable_training(self):
+        if not self.training_bytes:
+            n = N.c_i64(0)
+            N.check(self.lib.srlx_qnet_enable_seq_training(self.h, self.max_rows, ctypes.byref(n)))
+            self.training_bytes = int(n.value)
+        return self
+
+    def features(self, frames: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """frames float32 [rows][H][W][C] (or [rows][H][W] for C = 1), dense; out None or float32 [rows][ld >= n_features] with unit column stride, without
+        gradient history.  Returns `out` (a new [rows][n_features] tensor when None) with the features in its first columns, differentiable with respect to
+        the six convolution parameters when gradient is enabled."""
+        rows = frames.shape[0]
+        assert frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.data_ptr() % 16 == 0
+        assert 0 < rows <= self.max_rows and frames.numel() == rows * self.hw[0] * self.hw[1] * self.in_channels
+        if out is None:
+            out = torch.empty((rows, self.n_features), dtype=torch.float32, device=frames.device)
+        assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == rows and out.shape[1] >= self.n_features and out.stride(1) == 1
+        assert not out.requires_grad and (rows == 1 or out.stride(0) >= out.shape[1])
+        ps = self.params()
+        if [p.data_ptr() for p in ps] != self._bound:  # the parameters were re-homed (load_state_dict keeps them, .to() / flattening does not)
+            self.bind()
+        for conv in self.convs[1:]:
+            assert conv.weight.is_contiguous(memory_format=torch.channels_last), "SeqImageTrunk: a convolution weight left channels_last memory"
+        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
+            self.enable_training()
+        return _SeqTrunkFunction.apply(self, frames, out, *ps)
+
+
 class DeviceAdam:
     """torch.optim.Adam(params, lr) for a fixed list of float32 device tensors as ONE libsrlx launch
     (`srlx_adam_step`; reference: `optim.Adam(self.q_online.parameters(), lr=...)`, model_torch.py:71, and
