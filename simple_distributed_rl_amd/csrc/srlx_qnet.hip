@@ -1054,7 +1054,8 @@ int srlx_qnet_create(srlx_qnet_t **out, int in_h, int in_w, int window, int filt
                      int device) {
     SRLX_REQUIRE(out, "qnet_create: out is NULL");
     SRLX_REQUIRE(in_h >= 8 && in_w >= 8 && window >= 1 && filters % 32 == 0 && hidden % 32 == 0 && n_actions >= 1 && n_actions <= kMaxActions && max_batch > 0,
-                 "qnet_create: unsupported shape (filters and hidden must be multiples of 32, n_actions <= %d)", kMaxActions);
+                 "qnet_create: unsupported shape (frames of at least 8 x 8, window >= 1, filters and hidden multiples of 32, 1 <= n_actions <= %d, max_batch > 0)",
+                 kMaxActions);
     SRLX_REQUIRE((window * 64) % BK == 0, "qnet_create: window*64 must be a multiple of %d", BK);
     SRLX_REQUIRE(filters == 32 || filters == 64 || filters == 128, "qnet_create: filters must be 32, 64 or 128 (channel counts are powers of two, <= 80 K-slabs)");
     SRLX_REQUIRE(dueling_type >= 0 && dueling_type <= kHeadPlain, "qnet_create: dueling_type 0 (average), 1 (max), 2 (naive) or 3 (plain Q head, no dueling)");

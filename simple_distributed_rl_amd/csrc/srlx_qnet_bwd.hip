@@ -755,7 +755,8 @@ int srlx_qnet_enable_training(srlx_qnet_t *h, int64_t max_train_batch) {
     SRLX_REQUIRE(max_train_batch > 0 && max_train_batch <= 64 && max_train_batch <= h->max_batch, "qnet_enable_training: 1 <= max_train_batch <= 64");
     SRLX_REQUIRE(h->F1 == 32 && h->dueling != 1 && h->H == h->W && h->W % 4 == 0 && (2 * h->hidden) % kFcSplits == 0 &&
                      2 * h->hidden / kFcSplits <= 64 && 4 * (h->OH1 - 1) + 8 <= kC1Pad,
-                 "qnet_enable_training: the backward kernels cover the DQN image block with 32 filters, square frames, hidden <= 512, dueling average / none or the plain head");
+                 "qnet_enable_training: the backward kernels cover the DQN image block with 32 filters, square frames whose side is a multiple of 4 and at most 84, "
+                 "hidden <= 512, dueling average / none or the plain head");
     if (h->max_train >= max_train_batch) return SRLX_OK;
     SRLX_REQUIRE(h->max_train == 0, "qnet_enable_training: already enabled with a smaller batch");
     srlx::DeviceGuard guard(h->device);
