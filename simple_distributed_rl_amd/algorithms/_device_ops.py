@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from simple_distributed_rl_amd import _native as N
+from simple_distributed_rl_amd.device.sequence_store import fill_invalid_mask
 
 
 def require_gpu(device_str: str) -> torch.device:
@@ -18,14 +19,8 @@ def require_gpu(device_str: str) -> torch.device:
 
 def invalid_mask(invalid_lists, shape, device) -> torch.Tensor:
     """nested lists of invalid action ids -> uint8 mask of `shape` (..., A), or None when all empty."""
-    m = np.zeros(shape, np.uint8)
-    any_ = False
-    flat = m.reshape(-1, shape[-1])
-    for i, inv in enumerate(invalid_lists):
-        for a in inv:
-            flat[i, a] = 1
-            any_ = True
-    return torch.from_numpy(m).to(device) if any_ else None
+    m = np.empty(shape, np.uint8)
+    return torch.from_numpy(m).to(device) if fill_invalid_mask(m.reshape(-1, shape[-1]), invalid_lists) else None
 
 
 class TdOps:
@@ -86,6 +81,22 @@ class TdOps:
         )
         self._keep3 = keep
         return td_e, td_i, pri
+
+    def agent57_seq_td(self, q, q_target, actions, rewards, dones, invalid, discounts, weights, retrace_h, double_dqn, rescale):
+        """srlx_agent57_seq_td (agent57.py:301-379 + model_torch.py:469-492) over q [B][S + 1][A]: returns (target [S][B], loss [1], grad_q, td_mean [B])."""
+        d = self.dev
+        B, S1, A = q.shape
+        S = S1 - 1
+        target = torch.empty((S, B), dtype=torch.float32, device=d)
+        loss = torch.empty(1, dtype=torch.float32, device=d)
+        grad = torch.empty((B, S1, A), dtype=torch.float32, device=d)
+        td = torch.empty(B, dtype=torch.float32, device=d)
+        scratch = torch.empty(2 * B * S, dtype=torch.float32, device=d)
+        keep = [t.detach().contiguous() if t is not None else None for t in (q, q_target, actions, rewards, dones, invalid, discounts, weights)]
+        N.check(self.lib.srlx_agent57_seq_td(B, S, A, *[N.tptr(t) for t in keep], float(retrace_h), int(double_dqn), int(rescale), N.tptr(target), N.tptr(loss),
+                                             N.tptr(grad), N.tptr(td), N.tptr(scratch), N.torch_stream_ptr()))
+        self._keep4 = keep + [scratch]
+        return target, loss, grad, td
 
 
 class NguOps:

@@ -15,12 +15,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.base.rl.algorithms.base_dqn import RLConfig, RLWorker
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
 from simple_distributed_rl_amd.base.rl.registration import register
 from simple_distributed_rl_amd.base.rl.trainer import RLTrainer
-from simple_distributed_rl_amd.device.sequence_store import SequenceBatch
+from simple_distributed_rl_amd.device.lstm import SrlxLstm
+from simple_distributed_rl_amd.device.qnet import SeqImageTrunk
+from simple_distributed_rl_amd.device.sequence_store import DeviceSequenceStore, SequenceBatch
 from simple_distributed_rl_amd.rl import functions as funcs
 from simple_distributed_rl_amd.rl.memories.priority_replay_buffer import PriorityReplayBufferConfig, RLPriorityReplayBuffer
 from simple_distributed_rl_amd.rl.models.config import DuelingNetworkConfig, HiddenBlockConfig, InputBlockConfig, RLConfigComponentFramework
@@ -129,14 +130,15 @@ class Memory(RLPriorityReplayBuffer):
         if cfg.enable_demo_memory:
             raise ValueError("sequence_store 'device': enable_demo_memory keeps demonstration items in a host ring of its own; use sequence_store 'host'")
 
+    def _build_store(self, frame_shape, layout=None, frame_capacity=None):
+        """The one construction of the store: for the configuration's window, or, for a restore, for the backup's `layout` (L, S, A, H) and frame ring."""
+        c = self.config
+        L, S, A, H = layout if layout is not None else (c.burnin + c.sequence_length + 1, c.sequence_length, c.action_space.n, c.lstm_units)
+        self._store = DeviceSequenceStore(require_gpu(c.used_device_torch), self.cfg.capacity, L, S, A, H, frame_shape, frame_capacity)
+
     def _device_store(self, item=None):
         if self._store is None:
-            from simple_distributed_rl_amd.device.sequence_store import DeviceSequenceStore
-
-            c = self.config
-            device = require_gpu(c.used_device_torch)
-            shape = np.asarray(item[0][0]).shape if item is not None else tuple(c.observation_space.shape)
-            self._store = DeviceSequenceStore(device, self.cfg.capacity, c.burnin + c.sequence_length + 1, c.sequence_length, c.action_space.n, c.lstm_units, shape)
+            self._build_store(np.asarray(item[0][0]).shape if item is not None else tuple(self.config.observation_space.shape))
         return self._store
 
     def add(self, batch: Any, priority=None, serialized: bool = False) -> None:
@@ -167,62 +169,8 @@ class Memory(RLPriorityReplayBuffer):
                 raise ValueError("sequence_store 'device': this backup was taken from a 'host' memory and holds no sequence store")
             if data[2] is not None:
                 if self._store is None:
-                    from simple_distributed_rl_amd.device.sequence_store import DeviceSequenceStore
-
-                    c, lay = self.config, data[2]["layout"]
-                    self._store = DeviceSequenceStore(require_gpu(c.used_device_torch), self.cfg.capacity, lay[0], lay[1], lay[2], lay[3], data[2]["frame_shape"],
-                                                      data[2]["ledger"]["frame_capacity"])
+                    self._build_store(data[2]["frame_shape"], data[2]["layout"], data[2]["ledger"]["frame_capacity"])
                 self._store.restore(data[2])
-
-
-class _LstmFunction(torch.autograd.Function):
-    """y, h_n, c_n = LSTM(x, (h0, c0)) with the forward AND the backward through time in libsrlx (srlx_lstm_forward / srlx_lstm_backward: float32 matrix-core
-    kernels with fixed summation orders, so an update is reproducible run to run).  The four LSTM parameters are inputs only so that autograd routes their
-    gradients through `backward`; the kernels read them by address.  `bufs` is the module's cached workspace / scratch pair of this (B, T)."""
-
-    @staticmethod
-    def forward(ctx, bufs, training, x, h0, c0, w_ih, w_hh, b_ih, b_hh):
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        x, h0, c0 = _dense16(x), _dense16(h0), _dense16(c0)
-        y = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
-        h_n, c_n = torch.empty_like(h0), torch.empty_like(c0)
-        ws = bufs["workspace"] if training else None
-        N.check(N.lib().srlx_lstm_forward(B, T, I, H, N.tptr(x), N.tptr(h0), N.tptr(c0), N.tptr(w_ih), N.tptr(w_hh), N.tptr(b_ih), N.tptr(b_hh), N.tptr(y),
-                                          N.tptr(h_n), N.tptr(c_n), N.tptr(ws), N.tptr(bufs["scratch"]), N.torch_stream_ptr()))
-        if training:
-            bufs["serial"] += 1
-            ctx.bufs, ctx.serial, ctx.keep = bufs, bufs["serial"], (x, h0, c0, w_ih, w_hh, y)
-            ctx.set_materialize_grads(False)
-        return y, h_n, c_n
-
-    @staticmethod
-    def backward(ctx, dy, dh_n, dc_n):
-        bufs = ctx.bufs
-        if bufs["serial"] != ctx.serial:
-            raise RuntimeError("Agent57 LSTM: another pass with gradient of the same (batch, steps) ran on this module before this one's backward; its workspace is gone")
-        x, h0, c0, w_ih, w_hh, y = ctx.keep
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
-        dh_n, dc_n = (None if g is None else g.contiguous() for g in (dh_n, dc_n))
-        need = ctx.needs_input_grad
-        dx = torch.empty_like(x) if need[2] else None
-        dh0 = torch.empty_like(h0) if need[3] else None
-        dc0 = torch.empty_like(c0) if need[4] else None
-        dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-        db_ih, db_hh = (torch.empty(4 * H, dtype=torch.float32, device=x.device) for _ in range(2))
-        N.check(N.lib().srlx_lstm_backward(B, T, I, H, N.tptr(x), N.tptr(h0), N.tptr(c0), N.tptr(w_ih), N.tptr(w_hh), N.tptr(y), N.tptr(bufs["workspace"]), N.tptr(dy),
-                                           N.tptr(dh_n), N.tptr(dc_n), N.tptr(dx), N.tptr(dw_ih), N.tptr(dw_hh), N.tptr(db_ih), N.tptr(db_hh), N.tptr(dh0),
-                                           N.tptr(dc0), N.tptr(bufs["scratch"]), N.torch_stream_ptr()))
-        ctx._keep_grads = (dy, dh_n, dc_n)  # alive until the stream has run the launches
-        return None, None, dx, dh0, dc0, dw_ih, dw_hh, db_ih, db_hh
-
-
-def _dense16(t):
-    """float32, dense and 16-byte aligned (the kernels' vector loads): a view at an odd storage offset is copied."""
-    t = t.detach().contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 class QNetwork(nn.Module):
@@ -253,7 +201,7 @@ class QNetwork(nn.Module):
         self.lstm_layer = nn.LSTM(in_size, config.lstm_units, batch_first=True)
         self.hidden_block = config.hidden_block.create_torch_block(config.lstm_units, config.action_space.n)
         self.lstm_path = None
-        self._lstm_bufs = {}  # (device, B, T) -> workspace / scratch of that shape, allocated once
+        self._srlx_lstm = SrlxLstm()  # the libsrlx path of `lstm_layer` (device/lstm.py): owns its cached buffers, no parameters
         self.in_block_path = None
         self.why_not_srlx_in_block = None
         self._in_block_rows = config.batch_size * max(config.sequence_length + 1, config.burnin)  # the trainer's largest pass (the worker's acting pass is one row)
@@ -261,65 +209,26 @@ class QNetwork(nn.Module):
 
     def _in_block_trunk(self, state):
         """The SeqImageTrunk that serves this call, or None with `why_not_srlx_in_block` set."""
-        from simple_distributed_rl_amd.device.qnet import ImageTrunk, SeqImageTrunk
-
-        def no(why):
-            self.why_not_srlx_in_block = why
+        self.why_not_srlx_in_block = SeqImageTrunk.why_not(self.in_block, state, self._in_block_rows)
+        if self.why_not_srlx_in_block is not None:
             return None
-
-        block = getattr(self.in_block, "image_block", None)
-        if block is None or not getattr(self.in_block, "out_flatten", False):
-            return no("the input block is not a flattened image block")
-        if not ImageTrunk.supported(block):
-            return no("the image block is not the DQN block with ReLU activations")
-        convs = list(block.image_layers)[0::2]
-        w = convs[0].weight
-        if not (state.is_cuda and w.is_cuda and state.dtype == torch.float32 and w.dtype == torch.float32):
-            return no("the parameters or the states are not float32 tensors on a GPU")
-        if convs[0].out_channels != 32:
-            return no(f"{convs[0].out_channels} filters: the backward kernels cover the 32 / 64 / 64-filter block")
-        hw, C = tuple(self.in_block.in_shape[:2]), int(self.in_block.in_shape[2])
-        rows = state.shape[0] * state.shape[1]
-        if tuple(state.shape[2:]) not in ((hw[0], hw[1], C),) + (((hw[0], hw[1]),) if C == 1 else ()):
-            return no(f"states of shape {tuple(state.shape[2:])} are not the block's {hw[0]} x {hw[1]} x {C} frames")
-        if self._trunk is not None and self._trunk.dev != w.device:
+        dev = self.in_block.image_block.image_layers[0].weight.device
+        if self._trunk is not None and self._trunk.dev != dev:
             self._trunk = None  # the network moved to another device
         if self._trunk is None:
-            max_rows = self._in_block_rows
-            if SeqImageTrunk.seq_training_bytes(hw, C, 32, max_rows) < 0:
-                return no(f"{hw[0]} x {hw[1]} x {C} frames or {max_rows} rows are outside the kernels' envelope")
-            if rows > max_rows:
-                return no(f"{rows} rows: the handle is built for {max_rows}")
-            self._trunk = SeqImageTrunk(block, hw, max_rows, device=w.device.index or 0)
+            self._trunk = SeqImageTrunk(self.in_block.image_block, self.in_block.in_shape[:2], self._in_block_rows, device=dev.index or 0)
+        rows = state.shape[0] * state.shape[1]
         if rows > self._trunk.max_rows:
-            return no(f"{rows} rows: the handle was built for {self._trunk.max_rows}")
-        self.why_not_srlx_in_block = None
+            self.why_not_srlx_in_block = f"{rows} rows: the handle was built for {self._trunk.max_rows}"
+            return None
         return self._trunk
 
     def _lstm(self, x, hidden_states):
-        m = self.lstm_layer
         if self.lstm_backend not in ("srlx", "torch"):
             raise ValueError(f"lstm_backend {self.lstm_backend!r}: 'srlx' or 'torch'")
-        B, T, I = x.shape
-        H = self.hidden_size
-        on_gpu = x.is_cuda and m.weight_ih_l0.is_cuda and x.dtype == torch.float32 and m.weight_ih_l0.dtype == torch.float32
-        if self.lstm_backend != "srlx" or not on_gpu or N.lib().srlx_lstm_scratch_floats(B, T, I, H, 1) < 0:
-            self.lstm_path = "torch"
-            return m(x, hidden_states)
-        self.lstm_path = "srlx"
-        key = (x.device, B, T)
-        bufs = self._lstm_bufs.get(key)
-        if bufs is None:
-            lib = N.lib()
-            bufs = self._lstm_bufs[key] = dict(workspace=None, serial=0,
-                                               scratch=torch.empty(lib.srlx_lstm_scratch_floats(B, T, I, H, 1), dtype=torch.float32, device=x.device))
-        h0, c0 = hidden_states[0][0], hidden_states[1][0]
-        params = (m.weight_ih_l0, m.weight_hh_l0, m.bias_ih_l0, m.bias_hh_l0)
-        training = torch.is_grad_enabled() and any(t.requires_grad for t in (x, h0, c0) + params)
-        if training and bufs["workspace"] is None:
-            bufs["workspace"] = torch.empty(N.lib().srlx_lstm_workspace_floats(B, T, I, H, 1), dtype=torch.float32, device=x.device)
-        y, h_n, c_n = _LstmFunction.apply(bufs, training, x, h0, c0, *params)
-        return y, (h_n.unsqueeze(0), c_n.unsqueeze(0))
+        srlx = self.lstm_backend == "srlx" and self._srlx_lstm.serves(self.lstm_layer, x)
+        self.lstm_path = "srlx" if srlx else "torch"
+        return self._srlx_lstm(self.lstm_layer, x, hidden_states) if srlx else self.lstm_layer(x, hidden_states)
 
     def forward(self, inputs, hidden_states):
         state, reward_ext, reward_int, onehot_action, onehot_actor = inputs
@@ -330,24 +239,13 @@ class QNetwork(nn.Module):
         trunk = self._in_block_trunk(state) if self.in_block_backend == "srlx" else None
         extras = ([reward_ext] if self.input_ext_reward else []) + ([reward_int] if self.input_int_reward else []) + \
                  ([onehot_action] if self.input_action else []) + [onehot_actor]
-        if trunk is not None:
-            # the LSTM's input rows [B S][I]: the small UVFA columns first (plain copies, no gradient flows into them), then the features into the first
-            # columns by the trunk, in place -- no torch.cat copy of the wide rows
+        frames = state.reshape((B * S,) + tuple(state.shape[2:]))
+        if trunk is not None:  # the features land in the LSTM's input rows in place, the UVFA columns behind them (SeqImageTrunk.input_rows)
             self.in_block_path = "srlx"
-            F_, I = trunk.n_features, self.lstm_layer.input_size
-            x = torch.empty((B * S, I), dtype=torch.float32, device=state.device)
-            col = F_
-            with torch.no_grad():
-                for e in extras:
-                    n = e.shape[2]
-                    x[:, col : col + n] = e.reshape(B * S, n)
-                    col += n
-            assert col == I
-            frames = state.reshape((B * S,) + tuple(state.shape[2:])).contiguous()
-            x = trunk.features(frames if frames.data_ptr() % 16 == 0 else frames.clone(), out=x).view(B, S, I)
+            x = trunk.input_rows(frames, extras).view(B, S, self.lstm_layer.input_size)
         else:
             self.in_block_path = "torch"
-            x = torch.cat([self.in_block(state.reshape((B * S,) + tuple(state.shape[2:]))).view(B, S, -1)] + extras, dim=2)
+            x = torch.cat([self.in_block(frames).view(B, S, -1)] + extras, dim=2)
         x, hidden_states = self._lstm(x, hidden_states)
         return self.hidden_block(x.reshape(B * S, -1)).view(B, S, -1), hidden_states
 
@@ -418,7 +316,6 @@ class Trainer(RLTrainer):
         self.device = require_gpu(self.config.used_device_torch)
         self.parameter.to_device(self.device)
         self.ops = TdOps(self.device)
-        self.lib = N.lib()
         c, p = self.config, self.parameter
         self.q_ext_optimizer = torch.optim.Adam(p.q_ext_online.parameters(), lr=c.lr_ext)
         self.q_int_optimizer = torch.optim.Adam(p.q_int_online.parameters(), lr=c.lr_int)
@@ -430,22 +327,6 @@ class Trainer(RLTrainer):
         self.action_eye = torch.eye(c.action_space.n, dtype=torch.float32, device=self.device)
         self.sync_count = 0
 
-    def seq_td(self, q, q_target, actions, rewards, dones, invalid, discounts, weights):
-        """srlx_agent57_seq_td: returns (target [S][B], loss [1], grad_q, td_mean [B])."""
-        c, d = self.config, self.device
-        B, S1, A = q.shape
-        S = S1 - 1
-        target = torch.empty((S, B), dtype=torch.float32, device=d)
-        loss = torch.empty(1, dtype=torch.float32, device=d)
-        grad = torch.empty((B, S1, A), dtype=torch.float32, device=d)
-        td = torch.empty(B, dtype=torch.float32, device=d)
-        scratch = torch.empty(2 * B * S, dtype=torch.float32, device=d)
-        keep = [t.detach().contiguous() if t is not None else None for t in (q, q_target, actions, rewards, dones, invalid, discounts, weights)]
-        N.check(self.lib.srlx_agent57_seq_td(B, S, A, *[N.tptr(t) for t in keep], float(c.retrace_h), int(c.enable_double_dqn), int(c.enable_rescale), N.tptr(target),
-                                             N.tptr(loss), N.tptr(grad), N.tptr(td), N.tptr(scratch), N.torch_stream_ptr()))
-        self._keep = keep + [scratch]
-        return target, loss, grad, td
-
     def _train_q(self, online, target_net, optimizer, step_rewards, hidden, in_burnin, in_steps, actions, dones, invalid, discounts, weights):
         c = self.config
         hidden_t = hidden
@@ -456,7 +337,8 @@ class Trainer(RLTrainer):
             q_target, _ = target_net(in_steps, hidden_t)
         online.train()
         q, _ = online(in_steps, hidden)
-        _, loss, grad, td = self.seq_td(q, q_target, actions, step_rewards, dones, invalid, discounts, weights)
+        _, loss, grad, td = self.ops.agent57_seq_td(q, q_target, actions, step_rewards, dones, invalid, discounts, weights, c.retrace_h, c.enable_double_dqn,
+                                                    c.enable_rescale)
         optimizer.zero_grad()
         q.backward(grad)
         optimizer.step()
@@ -469,30 +351,12 @@ class Trainer(RLTrainer):
         batches, weights, update_args = sampled
         c, d, p = self.config, self.device, self.parameter
         B, A, bi, S = len(batches), c.action_space.n, c.burnin, c.sequence_length
-        f32 = lambda x: torch.as_tensor(np.asarray(x, dtype=np.float32), device=d)  # noqa: E731
-        if isinstance(batches, SequenceBatch):  # Memory.sequence_store == "device": srlx_seq_gather has assembled the batch in HBM
-            sb = batches
-            states, act_idx, actor, step_dones = sb.states, sb.act_idx, sb.actor, sb.dones
-            r_ext, r_int = sb.r_ext.unsqueeze(-1), sb.r_int.unsqueeze(-1)
-            invalid = sb.invalid if sb.any_invalid else None
-            hidden_ext, hidden_int = (sb.h_ext.unsqueeze(0), sb.c_ext.unsqueeze(0)), (sb.h_int.unsqueeze(0), sb.c_int.unsqueeze(0))
-            hid = lambda hs: hs  # noqa: E731
-        else:
-            states, onehot_actions, rewards_ext, rewards_int, dones, actors, invalid_lists, hidden_ext, hidden_int = zip(*batches)
-            states = f32(states)  # (B, burnin + S + 1, ...)
-            r_ext, r_int = f32(rewards_ext).unsqueeze(-1), f32(rewards_int).unsqueeze(-1)
-            act_idx = torch.as_tensor(np.argmax(np.asarray(onehot_actions), axis=2).astype(np.int64), device=d)  # (B, burnin + S + 1)
-            actor = torch.as_tensor(np.asarray(actors, dtype=np.int64), device=d)
-            step_dones = f32(dones)
-            inv = np.zeros((B, S, A), np.uint8)
-            any_inv = False
-            for b, per_step in enumerate(invalid_lists):
-                for t, lst in enumerate(per_step):
-                    for a in lst:
-                        inv[b, t, a] = 1
-                        any_inv = True
-            invalid = torch.from_numpy(inv).to(d) if any_inv else None
-            hid = lambda hs: (f32([h[0] for h in hs]).permute(1, 0, 2).contiguous(), f32([h[1] for h in hs]).permute(1, 0, 2).contiguous())  # noqa: E731
+        # Memory.sequence_store == "device": srlx_seq_gather has assembled the batch in HBM; "host": the same tensors from the sampled items
+        sb = batches if isinstance(batches, SequenceBatch) else SequenceBatch.from_items(batches, S, A, d)
+        states, act_idx, actor, step_dones = sb.states, sb.act_idx, sb.actor, sb.dones  # states (B, burnin + S + 1, ...)
+        r_ext, r_int = sb.r_ext.unsqueeze(-1), sb.r_int.unsqueeze(-1)
+        invalid = sb.invalid if sb.any_invalid else None
+        hidden_ext, hidden_int = (sb.h_ext.unsqueeze(0), sb.c_ext.unsqueeze(0)), (sb.h_int.unsqueeze(0), sb.c_int.unsqueeze(0))
         onehot = self.action_eye[act_idx]
         actor_onehot = self.actor_eye[actor].unsqueeze(1).expand(B, bi + S + 1, c.actor_num)
         in_burnin = [states[:, :bi], r_ext[:, :bi], r_int[:, :bi], onehot[:, :bi], actor_onehot[:, :bi]]
@@ -500,14 +364,14 @@ class Trainer(RLTrainer):
         step_actions = act_idx[:, bi + 1 :].to(torch.int32).contiguous()  # agent57.py:237: instep actions shifted by one
         step_r_ext, step_r_int = r_ext[:, bi + 1 :, 0].contiguous(), r_int[:, bi + 1 :, 0].contiguous()
         discounts = self.discount_list[actor]
-        w = f32(weights)
+        w = torch.as_tensor(np.asarray(weights, dtype=np.float32), device=d)
 
-        self.td_ext, ext_loss = self._train_q(p.q_ext_online, p.q_ext_target, self.q_ext_optimizer, step_r_ext, hid(hidden_ext), in_burnin, in_steps, step_actions,
+        self.td_ext, ext_loss = self._train_q(p.q_ext_online, p.q_ext_target, self.q_ext_optimizer, step_r_ext, hidden_ext, in_burnin, in_steps, step_actions,
                                               step_dones, invalid, discounts, w)
         self.info["ext_loss"] = float(ext_loss.item())
         self.td_int = None
         if c.enable_intrinsic_reward:
-            self.td_int, int_loss = self._train_q(p.q_int_online, p.q_int_target, self.q_int_optimizer, step_r_int, hid(hidden_int), in_burnin, in_steps,
+            self.td_int, int_loss = self._train_q(p.q_int_online, p.q_int_target, self.q_int_optimizer, step_r_int, hidden_int, in_burnin, in_steps,
                                                   step_actions, step_dones, invalid, discounts, w)
             self.info["int_loss"] = float(int_loss.item())
             one_states, one_n_states, one_actions = states[:, bi], states[:, bi + 1], onehot[:, bi]  # model_torch.py:348-351

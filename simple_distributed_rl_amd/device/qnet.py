@@ -777,6 +777,30 @@ class SeqImageTrunk:
         """Host arithmetic: bytes of gradient scratch for max_rows rows, or -1 outside the kernels' envelope."""
         return int(N.lib().srlx_qnet_seq_training_bytes(int(hw[0]), int(hw[1]), int(channels), int(filters), int(max_rows)))
 
+    @staticmethod
+    def why_not(in_block, state, max_rows: int) -> Optional[str]:
+        """Host only, no handle: why a SeqImageTrunk of `max_rows` rows over `in_block` (an InputImageBlock) cannot serve `state` [B][S][frame], or None."""
+        block = getattr(in_block, "image_block", None)
+        if block is None or not getattr(in_block, "out_flatten", False):
+            return "the input block is not a flattened image block"
+        if not ImageTrunk.supported(block):
+            return "the image block is not the DQN block with ReLU activations"
+        c1 = list(block.image_layers)[0]
+        w = c1.weight
+        if not (state.is_cuda and w.is_cuda and state.dtype == torch.float32 and w.dtype == torch.float32):
+            return "the parameters or the states are not float32 tensors on a GPU"
+        if c1.out_channels != 32:
+            return f"{c1.out_channels} filters: the backward kernels cover the 32 / 64 / 64-filter block"
+        hw, C = tuple(in_block.in_shape[:2]), int(in_block.in_shape[2])
+        rows = state.shape[0] * state.shape[1]
+        if tuple(state.shape[2:]) not in ((hw[0], hw[1], C),) + (((hw[0], hw[1]),) if C == 1 else ()):
+            return f"states of shape {tuple(state.shape[2:])} are not the block's {hw[0]} x {hw[1]} x {C} frames"
+        if SeqImageTrunk.seq_training_bytes(hw, C, 32, max_rows) < 0:
+            return f"{hw[0]} x {hw[1]} x {C} frames or {max_rows} rows are outside the kernels' envelope"
+        if rows > max_rows:
+            return f"{rows} rows: the handle is built for {max_rows}"
+        return None
+
     def __init__(self, image_block, hw, max_rows: int, device: int = 0):
         assert ImageTrunk.supported(image_block)
         self.lib = N.lib()
@@ -848,6 +872,21 @@ class SeqImageTrunk:
         if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
             self.enable_training()
         return _SeqTrunkFunction.apply(self, frames, out, *ps)
+
+    def input_rows(self, frames: torch.Tensor, extras) -> torch.Tensor:
+        """The rows a recurrent layer reads, [rows][n_features + extra columns]: frames float32 [rows][H][W][C] (any strides), extras a list of float32
+        tensors of `rows` rows in all (e.g. [B][S][n]).  The small extra columns first (plain copies, no gradient flows into them), then the features into
+        the first columns by `features`, in place -- no torch.cat copy of the wide rows."""
+        rows = frames.shape[0]
+        cols = [e.reshape(rows, -1) for e in extras]
+        x = torch.empty((rows, self.n_features + sum(c.shape[1] for c in cols)), dtype=torch.float32, device=frames.device)
+        col = self.n_features
+        with torch.no_grad():
+            for c in cols:
+                x[:, col : col + c.shape[1]] = c
+                col += c.shape[1]
+        frames = frames.contiguous()
+        return self.features(frames if frames.data_ptr() % 16 == 0 else frames.clone(), out=x)
 
 
 class DeviceAdam:

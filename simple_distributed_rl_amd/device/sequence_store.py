@@ -19,6 +19,18 @@ def _round4(n: int) -> int:
     return (int(n) + 3) // 4 * 4
 
 
+def fill_invalid_mask(mask: np.ndarray, invalid_lists) -> bool:
+    """mask uint8 [n][A] := 0, then mask[i, a] = 1 for every action id a in invalid_lists[i]; returns whether any bit was set.  numpy only: the one loop behind
+    every invalid-action mask the plugins and the sequence store hand to libsrlx."""
+    mask[...] = 0
+    any_invalid = False
+    for i, lst in enumerate(invalid_lists):
+        for a in lst:
+            mask[i, a] = 1
+            any_invalid = True
+    return any_invalid
+
+
 class RecordLayout:
     """Dword offsets of one packed sequence record (include/srlx.h, "Agent57 sequence store")."""
 
@@ -33,7 +45,7 @@ class RecordLayout:
 
     def pack(self, row: np.ndarray, table: np.ndarray, item) -> bool:
         """Writes `item` (the list `agent57.Worker._add_memory` builds) with its frame table into `row` (int32 [dwords]); returns whether any step has an
-        invalid action.  Values are converted exactly as `Trainer.train` converts them on the host path (float32 casts, argmax of the one-hot actions)."""
+        invalid action.  Values are converted exactly as `SequenceBatch.from_items` converts them on the host path (float32 casts, argmax of the one-hot actions)."""
         L, S, A, H = self.L, self.S, self.A, self.H
         f32, u8 = row.view(np.float32), row.view(np.uint8)
         row[:L] = table
@@ -44,14 +56,7 @@ class RecordLayout:
         row[self.actor] = item[5]
         for k, part in enumerate((item[7][0], item[7][1], item[8][0], item[8][1])):
             f32[self.hidden + k * H : self.hidden + (k + 1) * H] = np.asarray(part, dtype=np.float32).reshape(-1)
-        mask = u8[4 * self.invalid : 4 * self.invalid + S * A].reshape(S, A)
-        mask[:] = 0
-        any_invalid = False
-        for t, lst in enumerate(item[6]):
-            for a in lst:
-                mask[t, a] = 1
-                any_invalid = True
-        return any_invalid
+        return fill_invalid_mask(u8[4 * self.invalid : 4 * self.invalid + S * A].reshape(S, A), item[6])
 
 
 class LedgerError(RuntimeError):
@@ -179,6 +184,21 @@ class SequenceBatch:
 
     def tensors(self) -> dict:
         return {k: getattr(self, k) for k in self.__slots__ if k != "any_invalid"}
+
+    @classmethod
+    def from_items(cls, items, S: int, A: int, device) -> "SequenceBatch":
+        """The same batch from a list of items (the lists `agent57.Worker._add_memory` builds, as the host memory samples them), with the reference's
+        conversions (model_torch.py:300-346): float32 casts, argmax of the one-hot actions.  Every tensor goes to `device` ("cpu" works) in one copy."""
+        import torch
+
+        states, onehot_actions, r_ext, r_int, dones, actors, invalid_lists, hidden_ext, hidden_int = zip(*items)
+        f32 = lambda x: torch.as_tensor(np.asarray(x, dtype=np.float32), device=device)  # noqa: E731
+        hid = lambda hs, k: f32([h[k] for h in hs]).flatten(1)  # noqa: E731  ([B][1][H], as the worker keeps them, -> [B][H])
+        inv = np.empty((len(items), S, A), np.uint8)
+        any_invalid = fill_invalid_mask(inv.reshape(-1, A), [lst for per_step in invalid_lists for lst in per_step])
+        return cls(states=f32(states), act_idx=torch.as_tensor(np.argmax(np.asarray(onehot_actions), axis=2).astype(np.int64), device=device), r_ext=f32(r_ext),
+                   r_int=f32(r_int), dones=f32(dones), invalid=torch.from_numpy(inv).to(device), actor=torch.as_tensor(np.asarray(actors, dtype=np.int64), device=device),
+                   h_ext=hid(hidden_ext, 0), c_ext=hid(hidden_ext, 1), h_int=hid(hidden_int, 0), c_int=hid(hidden_int, 1), any_invalid=any_invalid)
 
 
 class DeviceSequenceStore:

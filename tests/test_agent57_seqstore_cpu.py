@@ -187,6 +187,55 @@ def test_seq_gather_validates_its_arguments_before_it_touches_a_device():
         assert b"srlx_seq_gather" in lib.srlx_last_error(), change
 
 
+@pytest.mark.parametrize("shape,L,S,A,H", [((3,), 2, 1, 2, 16), ((7, 9, 1), 6, 3, 5, 48)], ids=["3-2-1-2-16", "7x9x1-6-3-5-48"])
+def test_from_items_equals_the_restated_host_assembly(shape, L, S, A, H):
+    """SequenceBatch.from_items on the CPU against `_host_assemble` (test_agent57_seqstore_gpu.py's restatement of the trainer's list branch): a single item
+    without invalid actions, repeated items, 64 items; every tensor equal in dtype, shape and bits, and `any_invalid`."""
+    import torch
+
+    from simple_distributed_rl_amd.device.sequence_store import SequenceBatch
+    from test_agent57_seqstore_gpu import _host_assemble, _items
+
+    items = list(_items(L, S, A, H, shape, [2, L + 3, 1, 5] * 4 + [1], tail=2))
+    quiet = [i for i, it in enumerate(items) if not any(lst for lst in it[6])]
+    assert quiet and len(quiet) < len(items)
+    rng = np.random.default_rng(5)
+    any_seen = set()
+    for picks in ([quiet[0]], [6, 0, 0, 2, 5], rng.integers(0, len(items), 64).tolist()):
+        batch = [items[i] for i in picks]
+        want, want_any = _host_assemble(batch, S, A, "cpu")
+        got = SequenceBatch.from_items(batch, S, A, "cpu")
+        assert len(got) == len(picks) and got.any_invalid is want_any
+        any_seen.add(want_any)
+        assert set(got.tensors()) == set(want)
+        for k, v in got.tensors().items():
+            assert v.dtype == want[k].dtype and v.shape == want[k].shape and v.device.type == "cpu", k
+            assert torch.equal(v, want[k]), k
+    assert any_seen == {False, True}
+
+
+def test_invalid_mask_helper_agrees_with_the_loop_it_replaces():
+    from simple_distributed_rl_amd.device.sequence_store import fill_invalid_mask
+
+    def loop(n, A, lists):
+        m, any_ = np.zeros((n, A), np.uint8), False
+        for i, lst in enumerate(lists):
+            for a in lst:
+                m[i, a] = 1
+                any_ = True
+        return m, any_
+
+    A = 5
+    for lists in ([[], [4, 0], [2], []], [[3, 3, 3]], [[A - 1]], [[], [0, 1, 2, 3, 4], [], [4, 4, 0]], [np.array([1, 4]), ()]):
+        want, want_any = loop(len(lists), A, lists)
+        got = np.full((len(lists), A), 0xA5, np.uint8)  # (the helper clears what the mask held)
+        assert fill_invalid_mask(got, lists) is True and want_any
+        np.testing.assert_array_equal(got, want)
+    for lists in ([[]], [[], [], []], []):
+        got = np.full((3, A), 0xA5, np.uint8)
+        assert fill_invalid_mask(got, lists) is False and not got.any()
+
+
 @pytest.fixture
 def sequence_store_switch():
     from simple_distributed_rl_amd.algorithms import agent57

@@ -43,7 +43,9 @@ def test_lstm_forward_refuses_shapes_outside_the_envelope_before_any_device_call
         assert st != 0 and b"lstm" in lib.srlx_last_error(), change
 
 
-def test_agent57_qnetwork_on_cpu_is_nn_lstm():
+def test_agent57_qnetwork_on_cpu_is_nn_lstm(monkeypatch):
+    from simple_distributed_rl_amd import _native as N
+    from simple_distributed_rl_amd.device.lstm import SrlxLstm
     from test_agent57_cpu import _agent57_runner
 
     runner, rl = _agent57_runner(None, intrinsic=True)
@@ -57,6 +59,14 @@ def test_agent57_qnetwork_on_cpu_is_nn_lstm():
     inputs = [torch.rand((B, S) + obs, generator=g), torch.randn(B, S, 1, generator=g), torch.randn(B, S, 1, generator=g),
               torch.eye(rl.action_space.n)[torch.randint(0, rl.action_space.n, (B, S), generator=g)], torch.eye(rl.actor_num)[torch.zeros(B, S, dtype=torch.long)]]
     hid = (torch.randn(1, B, net.hidden_size, generator=g), torch.randn(1, B, net.hidden_size, generator=g))
+    def no_lib():
+        raise AssertionError("a CPU call reached libsrlx")
+
+    x_cpu = torch.randn(B, S, net.lstm_layer.input_size, generator=g)
+    with monkeypatch.context() as mp:  # SrlxLstm answers for CPU tensors before any call into libsrlx, let alone a device call
+        mp.setattr(N, "lib", no_lib)
+        assert SrlxLstm().serves(net.lstm_layer, x_cpu) is False
+        assert SrlxLstm.serves(net.lstm_layer, x_cpu.double()) is False
     for backend in ("srlx", "torch"):
         net.lstm_backend = backend
         with torch.no_grad():

@@ -14,9 +14,7 @@ The default rule (README): "srlx" iff atari.srlx_ms_mean <= 1.10 * atari.torch_m
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -101,29 +99,9 @@ def main():
         res = _step_block_alone() if a.child == "block_alone" else _step_trainer(a.child)
         print("PROBE-JSON " + json.dumps(res))
         return
-    res = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}  # steps measured by an earlier call stay
-    for step in a.steps.split(","):
-        t0 = time.time()
-        print("step %s (limit %d s)" % (step, LIMITS[step]), flush=True)
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", step], capture_output=True, text=True, timeout=LIMITS[step], cwd=ROOT)
-        except subprocess.TimeoutExpired:
-            res[step] = dict(error="no result within %d s" % LIMITS[step])
-            break
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("PROBE-JSON ")]
-        if p.returncode != 0 or not line:
-            res[step] = dict(error="exit status %d" % p.returncode, stderr=p.stderr[-2000:])
-            break
-        res[step] = dict(json.loads(line[-1][len("PROBE-JSON "):]), wall_s=time.time() - t0)
-    if "atari" in res and "srlx_over_torch" in res["atari"]:
-        res["default_rule"] = dict(rule="in_block_backend may default to 'srlx' iff the Atari-shape trainer step with it is at most 1.10 x the torch arm's in this run",
-                                   srlx_over_torch=res["atari"]["srlx_over_torch"], default="srlx" if res["atari"]["srlx_over_torch"] <= 1.10 else "torch")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(res, open(a.out, "w"), indent=1)
-    print(json.dumps(res, indent=1))
-    if any("error" in v for v in res.values() if isinstance(v, dict)):
-        sys.exit(1)
+    from agent57_lstm_probe import run_steps
+
+    run_steps(__file__, LIMITS, a.steps, a.out, "in_block_backend may default to 'srlx' iff the Atari-shape trainer step with it is at most 1.10 x the torch arm's in this run")
 
 
 if __name__ == "__main__":

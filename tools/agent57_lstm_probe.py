@@ -113,31 +113,23 @@ def _step_trainer(kind):
 def _step_lstm_alone():
     import torch
 
-    from simple_distributed_rl_amd.algorithms import agent57
+    from simple_distributed_rl_amd.device.lstm import SrlxLstm
 
     B, T, I, H = 64, 121, 7744 + 1 + 32, 512
     dev = torch.device("cuda:0")
-
-    class Shell(agent57.QNetwork):  # the layer and its dispatch without the image block and the head
-        def __init__(self):
-            torch.nn.Module.__init__(self)
-            self.hidden_size = H
-            self.lstm_layer = torch.nn.LSTM(I, H, batch_first=True)
-            self.lstm_path, self._lstm_bufs = None, {}
-
     torch.manual_seed(0)
-    net = Shell().to(dev)
+    layer = torch.nn.LSTM(I, H, batch_first=True).to(dev)  # the layer alone, without the image block and the head
     x = torch.randn(B, T, I, device=dev).requires_grad_(True)
     hid = (torch.randn(1, B, H, device=dev) * 0.1, torch.randn(1, B, H, device=dev) * 0.1)
     dy = torch.randn(B, T, H, device=dev)
+    srlx = SrlxLstm()
+    assert srlx.serves(layer, x)
     arms = {}
     for backend in ARMS:
         def run(backend=backend):
-            net.lstm_backend = backend
-            net.zero_grad()
+            layer.zero_grad()
             x.grad = None
-            y, _ = net._lstm(x, hid)
-            assert net.lstm_path == backend
+            y, _ = srlx(layer, x, hid) if backend == "srlx" else layer(x, hid)
             y.backward(dy)
         arms[backend] = run
     return dict(what="LSTM forward + backward alone (dx and the four parameter gradients), ms", shape=dict(batch=B, steps=T, lstm_inputs=I, lstm_units=H), **_interleaved(arms))
@@ -150,6 +142,33 @@ def _trace_loop(steps):
     for _ in range(steps):
         trainer.train()
     torch.cuda.synchronize()
+
+
+def run_steps(script, limits, names, out, rule):
+    """The parent's part of a probe (this one and tools/agent57_inblock_probe.py): every step of `names` as a child of `script` under its limit, results merged
+    into the JSON file `out`, the default `rule` applied to the atari step; exits with status 1 when a step failed (nothing more was started on the GPU)."""
+    res = json.load(open(out)) if out and os.path.exists(out) else {}  # steps measured by an earlier call stay
+    for step in names.split(","):
+        t0 = time.time()
+        print("step %s (limit %d s)" % (step, limits[step]), flush=True)
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(script), "--child", step], capture_output=True, text=True, timeout=limits[step], cwd=ROOT)
+        except subprocess.TimeoutExpired:
+            res[step] = dict(error="no result within %d s" % limits[step])
+            break
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("PROBE-JSON ")]
+        if p.returncode != 0 or not line:
+            res[step] = dict(error="exit status %d" % p.returncode, stderr=p.stderr[-2000:])
+            break
+        res[step] = dict(json.loads(line[-1][len("PROBE-JSON "):]), wall_s=time.time() - t0)
+    if "atari" in res and "srlx_over_torch" in res["atari"]:
+        res["default_rule"] = dict(rule=rule, srlx_over_torch=res["atari"]["srlx_over_torch"], default="srlx" if res["atari"]["srlx_over_torch"] <= 1.10 else "torch")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+    print(json.dumps(res, indent=1))
+    if any("error" in v for v in res.values() if isinstance(v, dict)):
+        sys.exit(1)
 
 
 def main():
@@ -165,29 +184,7 @@ def main():
         res = _step_lstm_alone() if a.child == "lstm_alone" else _step_trainer(a.child)
         print("PROBE-JSON " + json.dumps(res))
         return
-    res = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}  # steps measured by an earlier call stay
-    for step in a.steps.split(","):
-        t0 = time.time()
-        print("step %s (limit %d s)" % (step, LIMITS[step]), flush=True)
-        try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", step], capture_output=True, text=True, timeout=LIMITS[step], cwd=ROOT)
-        except subprocess.TimeoutExpired:
-            res[step] = dict(error="no result within %d s" % LIMITS[step])
-            break
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("PROBE-JSON ")]
-        if p.returncode != 0 or not line:
-            res[step] = dict(error="exit status %d" % p.returncode, stderr=p.stderr[-2000:])
-            break
-        res[step] = dict(json.loads(line[-1][len("PROBE-JSON "):]), wall_s=time.time() - t0)
-    if "atari" in res and "srlx_over_torch" in res["atari"]:
-        res["default_rule"] = dict(rule="lstm_backend defaults to 'srlx' iff the Atari-shape trainer step with it is at most 1.10 x the nn.LSTM arm's in this run",
-                                   srlx_over_torch=res["atari"]["srlx_over_torch"], default="srlx" if res["atari"]["srlx_over_torch"] <= 1.10 else "torch")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(res, open(a.out, "w"), indent=1)
-    print(json.dumps(res, indent=1))
-    if any("error" in v for v in res.values() if isinstance(v, dict)):
-        sys.exit(1)
+    run_steps(__file__, LIMITS, a.steps, a.out, "lstm_backend defaults to 'srlx' iff the Atari-shape trainer step with it is at most 1.10 x the nn.LSTM arm's in this run")
 
 
 if __name__ == "__main__":
