@@ -28,6 +28,7 @@ namespace {
 using i64 = int64_t;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
 
@@ -36,7 +37,7 @@ constexpr int kTM = 128, kTN = 128;         // output tile
 // float32 [rows][K] -> planes [K/32][rows][8 chunks][8 f16] (+ an optional float32 copy: the actors' private weight and its planes in one pass);
 // one thread per 8 consecutive k of a row.  hi = f16(x), lo = f16((x - hi) * 2048)
 template <bool WEIGHT>  // WEIGHT: the weight's chunk order [part][k-group], else the activations' [k-group][part]
-__global__ void __launch_bounds__(256) k_split_planes(const float *__restrict__ src, i64 rows, int K8, f16x8 *__restrict__ planes, float *__restrict__ copy) {
+__global__ void __launch_bounds__(256) k_split_planes(const float *__restrict__ src, i64 rows, i64 prows, int K8, f16x8 *__restrict__ planes, float *__restrict__ copy) {
     const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= rows * K8) return;
     const i64 row = q / K8;
@@ -53,7 +54,7 @@ __global__ void __launch_bounds__(256) k_split_planes(const float *__restrict__ 
         const _Float16 hi = (_Float16)r[j];
         hp[j] = hi, lp[j] = (_Float16)((r[j] - (float)hi) * 2048.0f);
     }
-    f16x8 *dst = planes + ((i64)(k8 >> 2) * rows + row) * 8;
+    f16x8 *dst = planes + ((i64)(k8 >> 2) * prows + row) * 8;  // prows: rows of a K-slab in the planes (a small launch's are padded to the GEMM's tile)
     dst[WEIGHT ? (k8 & 3) : (k8 & 3) * 2] = hp;
     dst[WEIGHT ? 4 + (k8 & 3) : (k8 & 3) * 2 + 1] = lp;
 }
@@ -213,6 +214,168 @@ __global__ void __launch_bounds__(256) k_fc1_planes_h(const uint4 *__restrict__ 
     if (span && threadIdx.x == 0) atomicMax(&span[1], (unsigned long long)wall_clock64());
 }
 
+// ---- one row tile: a learner's pass (<= 128 rows) --------------------------------------------------------------------------------------------------------------------
+// k_fc1_planes_h is shaped for 1024 rows; a learner's workgroup owns ~8 K-slabs of ONE row tile, so that kernel's prologue and epilogue are most of its life.  Here a
+// workgroup of 4 waves owns (128 columns, one K split) and each wave a 32-column strip over ALL RT row tiles of 32 (3 for 96 rows, 4 for 128: a dead tile is not
+// computed).  A weight fragment is then read by exactly one wave, and the 16-byte plane chunk IS the MFMA fragment: the weight goes global -> registers, eight K-slabs
+// (the workload's whole split: 8 x 128 rows x 128 B = 128 KB per workgroup) requested by the first instructions and reloaded slab by slab where a split is longer.
+// Only the activation slabs, shared by the four waves, go through LDS: a four-slot ring of RT x 4 KB slabs in the LDS image of k_fc1_planes_h (same rotation, so the
+// same conflict-free fragment reads), filled through registers -- slabs 0-3 by the prologue, slabs 4 and 5 requested by the prologue too and parked in registers
+// until their slot is free (two parked slabs: 128 rows already take 256 VGPRs + 128 accumulator registers with them).  (Not LDS-DMA here: beside ordinary loads the compiler answers a pending
+// global_load_lds with s_waitcnt vmcnt(0) at the first use of ANY loaded register, which turns the kernel into load-everything-then-compute; with plain loads it
+// counts every wait itself and the kernel holds no hand-counted vmcnt at all.)
+// Slab st: [k-step 0: MFMAs | reads the fragments of k-step 1]  barrier  [slab st + 2: registers -> its slot (left by slab st - 2, two barriers ago); request slab
+// st + 4 into those registers]  [k-step 1: MFMAs | reads slab st + 1's first fragments (written before this barrier)]  [request the weight of slab st + 8].
+// The barrier is "s_waitcnt lgkmcnt(0); s_barrier": a wave's LDS writes and fragment reads are complete when it arrives; no vmcnt drain, the loads keep travelling.
+// Same K split, k order and partial-product order as k_gemm_s16<.., H16> and k_fc1_planes_h: bit-identical.  No cross-workgroup communication.
+constexpr int kRSlots = 4;   // LDS ring of activation slabs
+constexpr int kRPark = 2;    // activation slabs parked in registers on their way to the ring
+constexpr int kRWSlabs = 8;  // K-slabs of weight fragments held in registers
+
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <int RT>
+__global__ void __launch_bounds__(256) k_fc1_planes_rows(const uint4 *__restrict__ A, const uint4 *__restrict__ W, float *__restrict__ C, int N, int K8, int slabs_per_split) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int kSlot = RT * 32 * kHRow;  // bytes of one activation slab
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
+    unsigned by = blockIdx.y, bz = blockIdx.z;
+    {   // XCD-aware tile order: an XCD's contiguous eighth of the (split, N tile) space shares its splits' activation slabs in that XCD's L2
+        const unsigned gy = gridDim.y, total = gy * gridDim.z;
+        if (total % 8 == 0) {
+            const unsigned lin = by + gy * bz, tile = (lin % 8) * (total / 8) + lin / 8;
+            by = tile % gy, bz = tile / gy;
+        }
+    }
+    const int n0 = by * kTN;
+    const int nsl_total = K8 / 4;
+    const int s_beg = bz * slabs_per_split;
+    const int s_end = s_beg + slabs_per_split < nsl_total ? s_beg + slabs_per_split : nsl_total;
+    const int nst = s_end - s_beg;
+    if (nst <= 0) return;  // (the launch has one z per split that owns a K range)
+    f32x16 acc[RT], lo[RT];
+#pragma unroll
+    for (int a = 0; a < RT; a++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[a][r] = 0.f, lo[a][r] = 0.f;
+    // an activation slab = RT * 256 chunk slots, RT per thread: slot sl = row r = sl / 8, position q = sl % 8 holds chunk c = (q - rot(r)) mod 8 (k_fc1_planes_h)
+    struct AS {
+        u32x4 x[RT];
+    };
+    const u32x4 *ga[RT];
+#pragma unroll
+    for (int u = 0; u < RT; u++) {
+        const int sl = u * 256 + t, r = sl >> 3, q = sl & 7;
+        const int c = (q - ((r >> 1) & 7)) & 7;
+        ga[u] = reinterpret_cast<const u32x4 *>(A) + (((i64)s_beg * kTM + r) * 8 + c);  // activations [slab][128 rows][k-group 4][part 2]
+    }
+    auto load_a = [&](AS &a, int st) __attribute__((always_inline)) {  // (st past the split's end: its last slab again -- the prologue's requests are unconditional)
+        st = st < nst ? st : nst - 1;
+#pragma unroll
+        for (int u = 0; u < RT; u++) a.x[u] = ga[u][(i64)st * kTM * 8];
+    };
+    auto store_a = [&](const AS &a, int slot) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < RT; u++) *reinterpret_cast<u32x4 *>(smem + slot * kSlot + (u * 256 + t) * 16) = a.x[u];
+    };
+    // this lane's weight fragments of a slab: row n0 + 32 wave + i, chunk [part p][k-group 2 ks + h]
+    const f16x8 *gw = reinterpret_cast<const f16x8 *>(W) + (((i64)s_beg * N + n0 + wave * 32 + i) * 8 + h);
+    struct WF {
+        f16x8 b[2][2];  // [k-step][part]
+    };
+    auto load_w = [&](WF &w, int st) __attribute__((always_inline)) {
+        st = st < nst ? st : nst - 1;
+        const f16x8 *g = gw + (i64)st * N * 8;
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) w.b[ks][p] = g[p * 4 + 2 * ks];
+    };
+    // fragment of row 32 rt + i, chunk c = (2 ks + h) * 2 + p: position (c + rot) mod 8 of the row, rot = (i >> 1) & 7
+    const int rot = (i >> 1) & 7;
+    int fo[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+        for (int p = 0; p < 2; p++) fo[ks][p] = i * kHRow + ((((2 * ks + h) * 2 + p) + rot) & 7) * 16;
+    struct AF {
+        f16x8 a[RT][2];  // [row tile][part]
+    };
+    auto read_a = [&](int slot, int ks, AF &f) __attribute__((always_inline)) {
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) f.a[rt][p] = *reinterpret_cast<const f16x8 *>(smem + slot * kSlot + rt * 32 * kHRow + fo[ks][p]);
+    };
+    auto mfmas = [&](const AF &f, const WF &w, int ks) __attribute__((always_inline)) {  // lo += a_lo b_hi; lo += a_hi b_lo; acc += a_hi b_hi
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) lo[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[rt][1], w.b[ks][0], lo[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) lo[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[rt][0], w.b[ks][1], lo[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[rt][0], w.b[ks][0], acc[rt], 0, 0, 0);
+    };
+    WF wr[kRWSlabs];
+    AS ra[kRPark];  // slabs st + 2, st + 3 on their way to the ring
+    AF f0, f1;
+    {   // requests in the order of need: A 0-3, W 0-3, A 4-5, W 4-7
+        AS first[kRSlots];
+#pragma unroll
+        for (int s = 0; s < kRSlots; s++) load_a(first[s], s);
+#pragma unroll
+        for (int s = 0; s < 4; s++) load_w(wr[s], s);
+#pragma unroll
+        for (int s = 0; s < kRPark; s++) load_a(ra[s], kRSlots + s);
+#pragma unroll
+        for (int s = 4; s < kRWSlabs; s++) load_w(wr[s], s);
+#pragma unroll
+        for (int s = 0; s < kRSlots; s++) store_a(first[s], s);
+    }
+    lds_barrier();
+    read_a(0, 0, f0);
+    for (int base = 0; base < nst; base += kRWSlabs) {
+#pragma unroll
+        for (int j = 0; j < kRWSlabs; j++) {
+            const int st = base + j;
+            if (st >= nst) break;
+            read_a(j % kRSlots, 1, f1);
+            mfmas(f0, wr[j], 0);
+            lds_barrier();  // everybody has read slab st; slab st + 1 (written before the previous barrier or by the prologue) is whole
+            if (st >= 2 && st + 2 < nst) {
+                store_a(ra[j % kRPark], (j + 2) % kRSlots);
+                if (st + 4 < nst) load_a(ra[j % kRPark], st + 4);
+            }
+            if (st + 1 < nst) read_a((j + 1) % kRSlots, 0, f0);
+            mfmas(f1, wr[j], 1);
+            if (st + kRWSlabs < nst) load_w(wr[j], st + kRWSlabs);
+        }
+    }
+    float *Cz = C + (i64)bz * kTM * N;
+    const int n = n0 + wave * 32 + i;
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int m = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            Cz[(i64)m * N + n] = __builtin_fmaf(lo[rt][r], 1.0f / 2048.0f, acc[rt][r]);
+        }
+}
+
+template <int RT>
+int launch_rows(srlx_qnet *h, int used, int kps, hipStream_t st) {
+    static bool attr = false;
+    constexpr int lds = kRSlots * RT * 32 * kHRow;
+    if (!attr) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_fc1_planes_rows<RT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        attr = true;
+    }
+    const int N1 = 2 * h->hidden;
+    hipLaunchKernelGGL(k_fc1_planes_rows<RT>, dim3(1, (unsigned)(N1 / kTN), (unsigned)used), dim3(256), lds, st, (const uint4 *)h->a3_planes, (const uint4 *)h->wf_planes,
+                       h->partial, N1, h->flat / 8, kps);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
 }  // namespace
 
 // operand planes of this handle: allocated by srlx_qnet_enable_fc1_planes
@@ -230,7 +393,7 @@ size_t srlx_fc1_planes_weight_bytes(const srlx_qnet *h) { return 2 * (size_t)h->
 
 int srlx_fc1_planes_split_weight(srlx_qnet *h, const float *src, float *copy_dst, hipStream_t st, void *planes_dst) {
     const i64 rows = 2 * (i64)h->hidden, n8 = rows * h->flat / 8;
-    hipLaunchKernelGGL(k_split_planes<true>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, src, rows, h->flat / 8,
+    hipLaunchKernelGGL(k_split_planes<true>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, src, rows, rows, h->flat / 8,
                        (f16x8 *)(planes_dst ? planes_dst : h->wf_planes), copy_dst);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
@@ -239,22 +402,32 @@ int srlx_fc1_planes_split_weight(srlx_qnet *h, const float *src, float *copy_dst
 // float32 activations act3 [rows][flat] -> a3_planes (the path for geometries whose convolution kernel does not write planes itself)
 int srlx_fc1_planes_split_act(srlx_qnet *h, int64_t rows, hipStream_t st) {
     const i64 n8 = rows * h->flat / 8;
-    hipLaunchKernelGGL(k_split_planes<false>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float *)h->act3, (i64)rows, h->flat / 8, (f16x8 *)h->a3_planes,
-                       (float *)nullptr);
+    hipLaunchKernelGGL(k_split_planes<false>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float *)h->act3, (i64)rows,
+                       (i64)((rows + kTM - 1) / kTM * kTM), h->flat / 8, (f16x8 *)h->a3_planes, (float *)nullptr);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
 
-// chip-filling launches (>= 512 rows in multiples of the tile); with `planes_small` (srlx_qnet_set_planes_small: a learner's handle, half-CU kernel) any launch, rows
-// padded to the tile
+// chip-filling launches (>= 512 rows in multiples of the tile: k_fc1_planes_h); with `planes_small` (srlx_qnet_set_planes_small: a learner's handle) also launches of
+// one row tile (<= 128 rows, padded to it: k_fc1_planes_rows).  Everything between stays on the staging-split GEMM.
 bool srlx_fc1_planes_applicable(const srlx_qnet *h, int64_t rows) {
     if (!h->wf_planes) return false;
-    if (h->planes_small && h->fc1_neighbour > 0) return true;
+    if (h->planes_small && rows >= 1 && rows <= kTM) return true;
     return rows % kTM == 0 && rows >= 512;
 }
 
 // partial[split][rows][2 hidden] = a3_planes x wf_planes^T over the split's K range; `splits` / `kps` (32-deep K-slabs per split) as k_gemm_s16's launch
 int srlx_fc1_planes_gemm(srlx_qnet *h, int64_t rows, int splits, int kps, hipStream_t st) {
+    if (rows <= kTM && !h->planes_small_h) {  // a learner's pass: one row tile, one z per split that owns a K range
+        const int nsl = h->flat / 32, used = (nsl + kps - 1) / kps;
+        h->fc1_span = nullptr;
+        switch ((int)((rows + 31) / 32)) {
+            case 1: return launch_rows<1>(h, used, kps, st);
+            case 2: return launch_rows<2>(h, used, kps, st);
+            case 3: return launch_rows<3>(h, used, kps, st);
+            default: return launch_rows<4>(h, used, kps, st);
+        }
+    }
     static bool attr_h = false;
     if (!attr_h) {
         SRLX_HIP(hipFuncSetAttribute((const void *)k_fc1_planes_h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHLds));

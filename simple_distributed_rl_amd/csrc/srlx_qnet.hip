@@ -1317,13 +1317,15 @@ int srlx_qnet_set_fc1_neighbour(srlx_qnet_t *h, int splits) {
     return SRLX_OK;
 }
 
-// A learner's handle on operand planes: `on` -- planes also for launches below 512 rows (its convolution kernel then writes float32 act3 AND planes, the first
-// dense layer runs on the half-CU planes kernel with the split-K shape of the staging-split GEMM: bit-identical); d_weight_planes -- BORROWED planes of the bound
+// A learner's handle on operand planes: `on` -- planes also for launches of one row tile (<= 128 rows: its convolution kernel then writes float32 act3 AND planes, the
+// first dense layer runs on k_fc1_planes_rows with the split-K shape of the staging-split GEMM: bit-identical; on = 2: on the half-CU kernel k_fc1_planes_h padded to
+// its tile instead, the yardstick k_fc1_planes_rows was measured against); d_weight_planes -- BORROWED planes of the bound
 // weight for the next forwards (NULL: the handle's own, srlx_qnet_refresh_fc1_planes).  The caller vouches that the planes hold the bound weight.
 int srlx_qnet_set_planes_small(srlx_qnet_t *h, int on, const void *d_weight_planes) {
     SRLX_REQUIRE(h, "qnet_set_planes_small: NULL handle");
     SRLX_REQUIRE(!on || h->a3_planes, "qnet_set_planes_small: srlx_qnet_enable_fc1_planes first");
     h->planes_small = on != 0;
+    h->planes_small_h = on == 2;  // (measurement yardstick: tools/learner_fc1_planes_time.py)
     h->wf_planes_ext = d_weight_planes;
     if (on && h->fc1_neighbour <= 0) h->fc1_neighbour = 4;
     if (d_weight_planes) h->planes_valid = true;

@@ -45,6 +45,9 @@ class EngineSchedule:
     fused_td: bool = True  # TD target / Huber / priorities in the backward pass's head kernel (False: a launch of their own)
     autograd_yardstick: bool = False  # the gradient step through torch autograd on float32 pixels: a TEST yardstick, never a fallback
     fused_draw: bool = True  # PER draw + item gather as one launch
+    learner_planes: Optional[bool] = None  # single-GPU fast lock-step: the update's two forward passes run their first dense layer on float16 operand planes that exist
+    # anyway (srlx_fc1_planes.hip: k_fc1_planes_rows) -- the online pass on the published set that holds the current weight, the target pass on planes split at every
+    # target sync.  Bit-identical to the staging-split GEMM.  None: on where it applies; True: raise where it does not; False: off (the A/B switch, the tests' yardstick)
 
 
 @dataclass
@@ -307,8 +310,18 @@ class RainbowEngine:
             self._set, self._published = 0, None
             self._seen_versions = None
             self.inf_target.set_pack_sticky(True)  # the target network's packed filters change at a sync only
-            self._learner_planes = False
             self._fresh_set = None  # the set whose planes equal the online network's current weight (None: some update did not publish)
+            # the update's forward passes on operand planes (EngineSchedule.learner_planes): one row tile per pass, plain layers, the planes the fused Adam publishes
+            can_planes = (role == "both" and self.mfma_train and fused_adam and not self.noisy and B * (n + 1) <= 128 and (2 * hid) % 128 == 0
+                          and os.environ.get("SRLX_FC1_F32", "0") != "1")
+            if sch.learner_planes and not can_planes:
+                raise ValueError("EngineSchedule(learner_planes=True): needs the single-GPU fast lock-step (role 'both'), the fused first-dense-layer Adam, plain dense "
+                                 "layers, at most 128 rows per pass and a first dense layer of a multiple of 128 units")
+            self._learner_planes = bool(can_planes and sch.learner_planes is not False)
+            if self._learner_planes:
+                self.inf_online.enable_fc1_planes(private_weights=False)  # (activation planes; the weight planes it reads are a published set's)
+                self.inf_target.enable_fc1_planes(private_weights=True)  # its own weight planes: split at every sync, like its packed filters
+                self.inf_target.set_planes_small(True, None)
             # the priority write-back leaves the update's critical path: it needs the head kernel's priorities only, so it is the FIRST launch of the backward pass's
             # weight-gradient branch (srlx_qnet_set_priority_sink; no new branch in the graph -- as a branch of its own it put the update on the actors' hardware queue:
             # tools/README.md findings 3, 5); the step count it used to advance moves to the update's LAST launch (the packing / publishing one).
@@ -334,7 +347,7 @@ class RainbowEngine:
         self.loss = torch.zeros(1, dtype=torch.float32, device=d)
         self.grad_q0 = torch.zeros((B, A), dtype=torch.float32, device=d)
         self.priorities = torch.zeros(B, dtype=torch.float32, device=d)
-        self._learner_graphs = lockstep.UpdateGraphs(self.dev)  # by variant: (published set, ingest key, batch set, batch already drawn)
+        self._learner_graphs = lockstep.UpdateGraphs(self.dev)  # by variant: (published set, ingest key, batch set, batch already drawn, set whose planes the online pass reads)
         # a learner rank's ingest (device/dist.py): the commit of transitions that arrived from other ranks runs on a side stream between the update's draw and
         # its priority write-back -- `ingest` = (key, callable issuing the launches) for the NEXT update only
         self.ingest = None
@@ -439,6 +452,8 @@ class RainbowEngine:
         if self.inf_target is not None:
             self.inf_target.weights_changed()
             self.inf_target.publish_to(None)
+            if self._learner_planes:
+                self.inf_target.refresh_own_planes()
         self._fresh_set = self._set
         self._published = None
         self._seen_versions = (self.q_online.weights_version, self.q_target.weights_version)
@@ -596,14 +611,17 @@ class RainbowEngine:
         return tuple(c.obs_hw) == (84, 84) and c.window_length == 4 and c.filters == 32 and os.environ.get("SRLX_NO_FUSED_CONV", "0") != "1"
 
     # ---- learner (model_torch.py:85-122) -----------------------------------------------------
-    def _learner_body(self, publish: Optional[int] = None, ingest=None, bset: Optional[int] = None, have_batch: bool = False, predraw: bool = False):
+    def _learner_body(self, publish: Optional[int] = None, ingest=None, bset: Optional[int] = None, have_batch: bool = False, predraw: bool = False,
+                      fresh: Optional[int] = None):
         """One Rainbow update.  fast engines: `publish` = the actor set (0 / 1) this update also writes -- the first dense layer as operand planes from the fused
         Adam's epilogue, packed filters and small vectors with the packing launch that follows the optimiser step (None: that launch only packs for this handle's
         own next forward).  `ingest`: a callable issuing the launches that add committed transitions to the tree (a learner rank's arrived slab, device/dist.py; the
         single-GPU engine's previous lock-step); they run on a side stream and the priority write-back waits for them.
         Pre-draw (round 5): `bset` = the replay's buffer set this update trains on, `have_batch` = the PREVIOUS update drew it already (no draw at the head of this
         update's chain), `predraw` = this update draws the next one's batch into the other set right behind its priority write-back, beside the rest of its backward
-        pass.  The tree sees the same sequence of operations either way: ... add, write-back(u), draw(u + 1), add, write-back(u + 1), draw(u + 2) ..."""
+        pass.  The tree sees the same sequence of operations either way: ... add, write-back(u), draw(u + 1), add, write-back(u + 1), draw(u + 2) ...
+        `fresh` (EngineSchedule.learner_planes): the published set whose planes hold the online network's current first-dense-layer weight -- the online pass multiplies
+        them; None: no set does (the previous update did not publish), the pass splits the float32 weight while staging."""
         cfg, r = self.cfg, self.lreplay
         B, n, A = cfg.batch_size, cfg.multisteps, cfg.n_actions
         pe = getattr(self, "_phase_mark", None)  # tools/lockstep_phases.py: timing events recorded inside the (captured) update; None in production
@@ -627,6 +645,8 @@ class RainbowEngine:
         step_dev = r.rng_counter if self._predraw else self.train_count_dev  # (pre-draw: the draw's own number is the update's number; srlx_per.hip:sample_wg_body)
         if self.fast:
             self.inf_online.fuse_adam_planes(self._planes_ptr[publish] if publish is not None else None)
+            if self._learner_planes:
+                self.inf_online.set_planes_small(fresh is not None, self._planes_ptr[fresh] if fresh is not None else None)
         if self.mfma_train:
             b = r.batch if have_batch else r.sample_items(step_dev, all_states=True)
             mark(1)
@@ -743,7 +763,8 @@ class RainbowEngine:
             if self._drawn is not None and not have:
                 r.rng_counter.sub_(1)  # the stale draw is dropped: this update draws under the same number (the draw's number is the update's number)
         # (a combination first seen after `capture_graphs` is captured now and replayed from then on)
-        self._learner_graphs.run((publish, ing_key, bset, have), lambda: self._learner_body(publish, ing_fn, bset, have, pre))
+        fresh = self._fresh_set if self.fast and self._learner_planes else None  # (which planes the online pass reads is part of the captured variant)
+        self._learner_graphs.run((publish, ing_key, bset, have, fresh), lambda: self._learner_body(publish, ing_fn, bset, have, pre, fresh))
         if ing is not None:
             self._note_issued_commit()
         if self._predraw:
@@ -774,6 +795,8 @@ class RainbowEngine:
         if self.fast:  # the target handle keeps its packed filters between syncs: re-pack them now (current stream: the learner's)
             self.inf_target.weights_changed()
             self.inf_target.publish_to(None)
+            if self._learner_planes:  # ... and its first dense layer's operand planes (one splitting pass; no float copy)
+                self.inf_target.refresh_own_planes()
         self.sync_count += 1
 
     # ---- the pieces of a step (the Runner's vectorised loop drives them one by one: device/vector_runner.py) --------
@@ -926,7 +949,9 @@ class RainbowEngine:
         if self.fast:  # the actors' launches stay eager; the update is captured per variant: publishing into set 0 / set 1 / not at all
             if learner and self.role != "actor" and not self.lreplay.is_warmup_needed() and self.learner_replay is None and not self.replay.lagged:
                 for pub in ((None, 0, 1) if self.role == "both" else (None,)):
-                    self._learner_graphs.capture((pub, None, None, False), lambda: self._learner_body(pub))
+                    # (learner_planes: the online pass reads the planes of the OTHER set -- the one the actors read --, or none behind an update that did not publish)
+                    for fresh in ((None, 1 - pub) if self._learner_planes and pub is not None else (None, 0, 1) if self._learner_planes else (None,)):
+                        self._learner_graphs.capture((pub, None, None, False, fresh), lambda: self._learner_body(pub, fresh=fresh))
             torch.cuda.synchronize(self.dev)
             return
         if actor and self.role != "learner" and not self._own_ring_only:
@@ -941,7 +966,7 @@ class RainbowEngine:
             self.replay._steps_committed -= 1  # capture does not execute
             self._commit_graph = g
         if learner and self.role != "actor" and not self.lreplay.is_warmup_needed() and self.learner_replay is None:
-            self._learner_graphs.capture((None, None, None, False), self._learner_body)
+            self._learner_graphs.capture((None, None, None, False, None), self._learner_body)
         torch.cuda.synchronize(self.dev)
 
     def refresh_host_mirrors(self):
