@@ -1,5 +1,5 @@
-"""oracle/_golden_env.py -- TEST INFRASTRUCTURE ONLY.  A tiny image environment registered with the
-imported reference from OUTSIDE its tree (srl/base/env/registration.py:116-136) to record golden vectors."""
+"""oracle/_golden_env.py -- TEST INFRASTRUCTURE ONLY.  A tiny image environment and a flat one, registered with the
+imported reference from OUTSIDE its tree (_golden_record.register_envs) to record golden vectors."""
 import numpy as np
 from srl.base.define import SpaceTypes
 from srl.base.env.base import EnvBase
@@ -63,3 +63,19 @@ class TinyImageEnv(EnvBase):
 
     def restore(self, data, **kwargs):
         pass
+
+
+class FlatGoldenEnv(EnvBase):
+    """Box(4) float32 observations, 2 actions (D and A of tests/dqn_vec_recipe.py and rainbow_vec_recipe.py): only its spaces matter, the batch is handed to
+    the trainer directly."""
+
+    action_space = property(lambda self: DiscreteSpace(2))
+    observation_space = property(lambda self: BoxSpace((4,), -10.0, 10.0, np.float32))
+    max_episode_steps = property(lambda self: 100)
+    player_num = property(lambda self: 1)
+
+    def reset(self, **kwargs):
+        return np.zeros(4, np.float32)
+
+    def step(self, action):
+        return np.zeros(4, np.float32), 1.0, False, False

@@ -2,12 +2,12 @@
 """oracle/gen_golden.py -- TEST INFRASTRUCTURE ONLY.
 
 Generates the committed golden vectors under tests/golden/ by IMPORTING THE
-REFERENCE (pocokhc/simple_distributed_rl, mounted read-only at /root/reference)
-in this container and recording its inputs/outputs on seeded synthetic data.
-The reference itself never travels to the GPU box: only the .npz files do.
+REFERENCE (pocokhc/simple_distributed_rl, at $SRL_REFERENCE) and recording its
+inputs/outputs on seeded synthetic data.  The reference itself never travels to
+the GPU box: only the .npz files do.
 
-Run (CPU only, ~1 min):
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [--only per,td,...]
+Run (CPU only):
+    python oracle/gen_golden.py [OUT] [--only per,td,...]
 
 Fixtures written (each is data only: inputs + the reference's outputs):
     per_trace_<name>.npz   scripted add/sample/update traces of
@@ -18,19 +18,12 @@ Fixtures written (each is data only: inputs + the reference's outputs):
     train_step_<name>.npz  one full Trainer.train() (loss, q, priorities, new weights)
     stack_trace.npz        WorkerRun frame stacking sequence
 """
-import argparse
 import os
 import random
-import sys
 
 import numpy as np
 
-REF = os.environ.get("SRL_REFERENCE", "/root/reference")
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-
-sys.dont_write_bytecode = True
-if REF not in sys.path:
-    sys.path.insert(0, REF)
+import _golden_record as G
 
 
 # ----------------------------------------------------------------------------------------
@@ -54,7 +47,7 @@ class _Recorder:
         return getattr(random, name)
 
 
-def _record_per_trace(name, capacity, alpha, beta_initial, beta_steps, has_duplicate, epsilon, script, seed):
+def _record_per_trace(dest, name, capacity, alpha, beta_initial, beta_steps, has_duplicate, epsilon, script, seed):
     """script: generator function(mem_api) that yields ops; we run them on the reference and log."""
     import srl.rl.memories.priority_memories.proportional_memory as pm
 
@@ -127,7 +120,7 @@ def _record_per_trace(name, capacity, alpha, beta_initial, beta_steps, has_dupli
 
         assert len(n_used) == len(op_code)
         np.savez_compressed(
-            os.path.join(OUT, f"per_trace_{name}.npz"),
+            os.path.join(dest, f"per_trace_{name}.npz"),
             capacity=np.int64(capacity),
             alpha=np.float64(alpha),
             beta_initial=np.float64(beta_initial),
@@ -160,7 +153,7 @@ def _record_per_trace(name, capacity, alpha, beta_initial, beta_steps, has_dupli
         pm.random = random
 
 
-def gen_per():
+def gen_per(dest):
     # --- (1) the reference's own statistical test scenario, shortened
     #     (tests/quick/rl/memories/test_priority_memories.py:29-91): capacity 10,
     #     alpha .8, beta_initial 1, no duplicates -> exercises the duplicate retry loop
@@ -173,7 +166,7 @@ def gen_per():
             _, _, idx = api.sample(5, 1)
             api.update(idx, np.array([rng.integers(1, 11) for _ in idx]))  # int64 -> float64 path
 
-    _record_per_trace("small_nodup", 10, 0.8, 1.0, 10, False, 1e-4, script_small, seed=1)
+    _record_per_trace(dest, "small_nodup", 10, 0.8, 1.0, 10, False, 1e-4, script_small, seed=1)
 
     def script_small_dup(api, rng):
         for _ in range(100):
@@ -184,7 +177,7 @@ def gen_per():
             _, _, idx = api.sample(5, it)
             api.update(idx, np.array([float(rng.random()) * 3 for _ in idx]))
 
-    _record_per_trace("small_dup", 10, 0.8, 0.4, 1000, True, 1e-4, script_small_dup, seed=2)
+    _record_per_trace(dest, "small_dup", 10, 0.8, 0.4, 1000, True, 1e-4, script_small_dup, seed=2)
 
     # --- (2) Rainbow/atari parameters (rainbow.py:139-143): alpha .5, beta0 .4, beta_steps 1e6, eps 1e-4;
     #     float32 priorities from the trainer (model_torch.py:113), priority=None adds from the worker.
@@ -201,7 +194,7 @@ def gen_per():
             api.update(idx, pri)
             step += 1
 
-    _record_per_trace("rainbow_cap3000", 3000, 0.5, 0.4, 1_000_000, True, 1e-4, script_rainbow, seed=3)
+    _record_per_trace(dest, "rainbow_cap3000", 3000, 0.5, 0.4, 1_000_000, True, 1e-4, script_rainbow, seed=3)
 
     # --- (3) speedtest.py-shaped loop (tests/quick/rl/memories/speedtest.py:28-58), scaled down:
     #     add with a python-float priority, sample 64, update with a python list (float64 path)
@@ -216,7 +209,7 @@ def gen_per():
             _, _, idx = api.sample(64, step)
             api.update(idx, [random.random() for _ in range(64)])
 
-    _record_per_trace("speedtest_cap4096", 4096, 0.8, 0.4, 1000, True, 1e-4, script_speed, seed=4)
+    _record_per_trace(dest, "speedtest_cap4096", 4096, 0.8, 0.4, 1000, True, 1e-4, script_speed, seed=4)
 
     # --- (4) distributed-actor style adds (priority computed on the actor, rainbow.py:389-398),
     #     NOTE: the reference hands a numpy float32 *scalar* to add() there; under NEP-50 numpy (>=2.0)
@@ -237,7 +230,7 @@ def gen_per():
             api.update(i2, np.abs(rng.standard_normal(16)).astype(np.float32))
             api.update(i3, np.abs(rng.standard_normal(16)).astype(np.float32))
 
-    _record_per_trace("mp_cap1024", 1024, 0.5, 0.4, 200_000, True, 1e-4, script_mp, seed=5)
+    _record_per_trace(dest, "mp_cap1024", 1024, 0.5, 0.4, 200_000, True, 1e-4, script_mp, seed=5)
 
     # --- (5) duplicates inside one update batch + no-duplicate sampling on a larger tree
     def script_dups(api, rng):
@@ -248,10 +241,10 @@ def gen_per():
             idx = list(idx) + list(idx[:8])  # repeated tree indices in one update (:173-175)
             api.update(idx, np.abs(rng.standard_normal(len(idx))).astype(np.float32))
 
-    _record_per_trace("dupupdate_cap257", 257, 0.5, 0.4, 100, False, 1e-4, script_dups, seed=6)
+    _record_per_trace(dest, "dupupdate_cap257", 257, 0.5, 0.4, 100, False, 1e-4, script_dups, seed=6)
 
 
-def gen_per_is_kat():
+def gen_per_is_kat(dest):
     """IS-weight known-answer vectors (test_priority_memories.py:97-117,150-176)."""
     from srl.rl.memories.priority_memories.proportional_memory import ProportionalMemory
 
@@ -270,7 +263,7 @@ def gen_per_is_kat():
         tw /= tw.max()
         rows.append((alpha, [b[0] for b in batches], list(weights), list(idx), list(tw)))
     np.savez_compressed(
-        os.path.join(OUT, "per_is_kat.npz"),
+        os.path.join(dest, "per_is_kat.npz"),
         alpha=np.array([r[0] for r in rows]),
         item=np.array([r[1] for r in rows], np.int64),
         weights=np.array([r[2] for r in rows]),
@@ -281,34 +274,17 @@ def gen_per_is_kat():
 
 
 # ----------------------------------------------------------------------------------------
-GENERATORS = {}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="")
-    args = ap.parse_args()
-    os.makedirs(OUT, exist_ok=True)
-    GENERATORS.update(
-        per=gen_per,
-        per_is=gen_per_is_kat,
-    )
-    try:
-        from gen_golden_algo import ALGO_GENERATORS  # noqa: E402  (same directory)
+    from gen_golden_agent57 import AGENT57_GENERATORS
+    from gen_golden_algo import ALGO_GENERATORS
 
-        GENERATORS.update(ALGO_GENERATORS)
-    except ImportError:
-        pass
-    from gen_golden_agent57 import AGENT57_GENERATORS  # noqa: E402
-
-    GENERATORS.update(AGENT57_GENERATORS)
+    args = G.start(__doc__, lambda ap: ap.add_argument("--only", default="", help="comma-separated generator names"))
+    generators = dict(per=gen_per, per_is=gen_per_is_kat, **ALGO_GENERATORS, **AGENT57_GENERATORS)
     only = [s for s in args.only.split(",") if s]
-    for name, fn in GENERATORS.items():
-        if only and name not in only:
-            continue
-        fn()
+    for name, fn in generators.items():
+        if not only or name in only:
+            fn(args.out)
 
 
 if __name__ == "__main__":
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     main()

@@ -6,31 +6,22 @@ q[action])`, because the learner's max_priority is not visible to an actor proce
 Drives the reference's worker by hand with `context.distributed = True` on the tiny image environment, with `memory.add` wrapped to
 record (item, priority); stores the network weights, the environment log and the priorities.  Data only.
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_actor_priority.py   ->  tests/golden/actor_priority_{n3,n1}.npz
+    python oracle/gen_golden_actor_priority.py [OUT]   ->  tests/golden/actor_priority_{n3,n1}.npz
 """
 import os
-import random
-import sys
 
 import numpy as np
 
-REF = os.environ.get("SRL_REFERENCE", "/root/reference")
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.dont_write_bytecode = True
-sys.path.insert(0, REF)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
 
 
-def record(name, multisteps):
-    import torch
-
+def record(out, name, multisteps):
     import srl
     from srl.base.context import RunContext
     from srl.utils import common
 
-    from gen_golden_algo import _make_rainbow, _register_env
+    from gen_golden_algo import _make_rainbow
 
-    _register_env()
     env_config, rl_config = _make_rainbow(multisteps=multisteps, double_dqn=True, rescale=False)
     env_config.kwargs = dict(hw=8, actions=4, ep_len=6, truncate=False, seed=9)
     rl_config.enable_reward_clip = True
@@ -67,13 +58,23 @@ def record(name, multisteps):
     sd = {k: v.detach().numpy() for k, v in parameter.q_online.state_dict().items()}
     log = env.unwrapped.log
     np.savez_compressed(
-        os.path.join(OUT, f"actor_priority_{name}.npz"),
+        os.path.join(out, f"actor_priority_{name}.npz"),
         priorities=np.array(got, np.float64), multisteps=np.int64(multisteps), seed=np.int64(6), epsilon=np.float64(rl_config.epsilon), steps=np.int64(steps),
         actions=np.array([l[1] for l in log], np.int32), **{"w:" + k: v for k, v in sd.items()},
     )
     print(name, "ok:", steps, "steps,", len(got), "items, priorities", np.round(got[:5], 5))
 
 
+def main(out=G.GOLDEN):
+    import torch  # noqa: F401  (before the seeding: common.set_seed seeds torch only where it is imported already, srl/utils/common.py:34)
+    from srl.utils import common
+
+    # record() seeds AFTER the runner has made its parameter, so the first network of the process would be initialised from unseeded generators.  Seeded here,
+    # once: the second record's network comes from the generators as the first one leaves them (seeded with 6, torch's untouched).
+    common.set_seed(6)
+    record(out, "n3", 3)
+    record(out, "n1", 1)
+
+
 if __name__ == "__main__":
-    record("n3", 3)
-    record("n1", 1)
+    G.run(main, __doc__)

@@ -1,5 +1,5 @@
 """oracle/gen_golden_agent57.py -- TEST INFRASTRUCTURE ONLY.  Golden vectors for the NGU / Agent57_light rows
- recorded from the imported reference (run through oracle/gen_golden.py --only agent57).
+ recorded from the imported reference (run through oracle/gen_golden.py, which hands every gen_* the output directory).
 Everything saved is data: inputs and the reference's outputs."""
 import collections
 import os
@@ -8,7 +8,7 @@ import types
 
 import numpy as np
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+import _golden_record as G
 
 
 def _cfg(**kw):
@@ -23,7 +23,7 @@ def _cfg(**kw):
 # ----------------------------------------------------------------------------------------
 # episodic novelty (agent57_light.py:473-513): scripted embedding sequences -> rewards
 # ----------------------------------------------------------------------------------------
-def gen_episodic():
+def gen_episodic(dest):
     from srl.algorithms.agent57_light.agent57_light import Worker
 
     rng = np.random.default_rng(31)
@@ -59,13 +59,13 @@ def gen_episodic():
     for name, (emb, out, cap, k) in cases.items():
         save[name + ".emb"], save[name + ".reward"] = emb, out
         save[name + ".capacity"], save[name + ".k"] = np.int64(cap), np.int64(k)
-    np.savez_compressed(os.path.join(OUT, "ngu_episodic.npz"), **save)
+    np.savez_compressed(os.path.join(dest, "ngu_episodic.npz"), **save)
 
 
 # ----------------------------------------------------------------------------------------
 # lifelong novelty (agent57_light.py:515-529)
 # ----------------------------------------------------------------------------------------
-def gen_lifelong():
+def gen_lifelong(dest):
     from srl.algorithms.agent57_light.agent57_light import Worker
 
     rng = np.random.default_rng(32)
@@ -81,14 +81,14 @@ def gen_lifelong():
             parameter=types.SimpleNamespace(predict_lifelong_target=lambda s, i=i: tgt[i : i + 1], predict_lifelong_train=lambda s, i=i: trn[i : i + 1]),
         )
         out[i] = float(Worker._calc_lifelong_reward(fake, None))
-    np.savez_compressed(os.path.join(OUT, "ngu_lifelong.npz"), target=tgt, train=trn, reward=out, lifelong_max=np.float64(cfg.lifelong_max))
+    np.savez_compressed(os.path.join(dest, "ngu_lifelong.npz"), target=tgt, train=trn, reward=out, lifelong_max=np.float64(cfg.lifelong_max))
     print(f"ngu_lifelong: range [{out.min():.4f}, {out.max():.4f}], clipped {int((out == cfg.lifelong_max).sum())}")
 
 
 # ----------------------------------------------------------------------------------------
 # sliding-window UCB meta-controller (agent57_light.py:317-353)
 # ----------------------------------------------------------------------------------------
-def gen_ucb():
+def gen_ucb(dest):
     from srl.algorithms.agent57_light.agent57_light import Worker
 
     cfg = _cfg(actor_num=8, ucb_window_size=20, ucb_epsilon=0.2, ucb_beta=1.0)
@@ -104,7 +104,7 @@ def gen_ucb():
         fake.actor_index = Worker._calc_actor_index(fake)
         idx[e] = fake.actor_index
         fake.episode_reward = float(ep_rewards[e])
-    np.savez_compressed(os.path.join(OUT, "agent57_ucb.npz"), actor_num=np.int64(8), window=np.int64(20), ucb_epsilon=np.float64(0.2), ucb_beta=np.float64(1.0),
+    np.savez_compressed(os.path.join(dest, "agent57_ucb.npz"), actor_num=np.int64(8), window=np.int64(20), ucb_epsilon=np.float64(0.2), ucb_beta=np.float64(1.0),
                         seed=np.int64(77), episode_rewards=ep_rewards, actor_index=idx)
     print(f"agent57_ucb: {episodes} episodes, histogram {np.bincount(idx, minlength=8).tolist()}")
 
@@ -112,7 +112,7 @@ def gen_ucb():
 # ----------------------------------------------------------------------------------------
 # calc_target_q (agent57_light.py:218-268) with scripted Q tables
 # ----------------------------------------------------------------------------------------
-def gen_target():
+def gen_target(dest):
     from srl.algorithms.agent57_light.agent57_light import CommonInterfaceParameter
     from srl.rl import functions as F
 
@@ -138,7 +138,7 @@ def gen_target():
         fake = types.SimpleNamespace(config=cfg, predict_q_ext_target=lambda x: q_tg.copy(), predict_q_ext_online=lambda x: q_on.copy(),
                                      predict_q_int_target=lambda x: q_tg.copy(), predict_q_int_online=lambda x: q_on.copy())
         tgt = CommonInterfaceParameter.calc_target_q(fake, True, rewards, None, None, None, None, None, inv_idx, inv_act, dones, disc)
-        np.savez_compressed(os.path.join(OUT, f"agent57_light_target_{name}.npz"), double_dqn=np.int64(double_dqn), rescale=np.int64(rescale), q_online=q_on,
+        np.savez_compressed(os.path.join(dest, f"agent57_light_target_{name}.npz"), double_dqn=np.int64(double_dqn), rescale=np.int64(rescale), q_online=q_on,
                             q_target=q_tg, rewards=rewards, dones=dones, discount=disc, invalid=invalid, target=np.asarray(tgt))
         print(f"agent57_light_target_{name}: dtype {np.asarray(tgt).dtype}, range [{tgt.min():.4f}, {tgt.max():.4f}]")
 
@@ -146,16 +146,14 @@ def gen_target():
 # ----------------------------------------------------------------------------------------
 # one full Trainer.train() (agent57_light/model_torch.py:263-443)
 # ----------------------------------------------------------------------------------------
-def gen_train_step():
+def gen_train_step(dest):
     import torch
 
     import srl
     from srl.algorithms import agent57_light
     from srl.base.context import RunContext
 
-    from gen_golden_algo import _register_env
-
-    _register_env()
+    G.register_envs()
     env_config = srl.EnvConfig("TinyImageEnvGolden", kwargs=dict(hw=8, actions=4))
     cfg = agent57_light.Config(batch_size=16, actor_num=8, target_model_update_interval=5, lr_ext=0.001, lr_int=0.002)
     cfg.window_length = 4
@@ -238,7 +236,7 @@ def gen_train_step():
         if not n.endswith("_target") or n == "lifelong_target":
             for k, v in after[n].items():
                 save[f"after.{n}.{k}"] = v
-    np.savez_compressed(os.path.join(OUT, "train_step_agent57_light.npz"), **save)
+    np.savez_compressed(os.path.join(dest, "train_step_agent57_light.npz"), **save)
     print("train_step_agent57_light:", {k: round(float(v), 6) for k, v in trainer.info.items() if "loss" in k})
 
 
@@ -248,7 +246,7 @@ AGENT57_GENERATORS = dict(ngu_episodic=gen_episodic, ngu_lifelong=gen_lifelong, 
 # ----------------------------------------------------------------------------------------
 # Agent57 (LSTM): calc_target_q (agent57.py:301-379) with scripted Q tensors
 # ----------------------------------------------------------------------------------------
-def gen_a57_target():
+def gen_a57_target(dest):
     from srl.algorithms.agent57 import agent57 as a57
     from srl.rl import functions as F
 
@@ -277,7 +275,7 @@ def gen_a57_target():
         cfg = a57.Config(enable_double_dqn=double_dqn, enable_rescale=rescale, retrace_h=h, sequence_length=S, batch_size=B)
         fake = types.SimpleNamespace(config=cfg)
         tgt = a57.CommonInterfaceParameter.calc_target_q(fake, q.copy(), qt.copy(), action_q.copy(), rewards, onehot, dones, i1, i2, i3, disc)
-        np.savez_compressed(os.path.join(OUT, f"agent57_target_{name}.npz"), double_dqn=np.int64(double_dqn), rescale=np.int64(rescale), retrace_h=np.float64(h), q=q,
+        np.savez_compressed(os.path.join(dest, f"agent57_target_{name}.npz"), double_dqn=np.int64(double_dqn), rescale=np.int64(rescale), retrace_h=np.float64(h), q=q,
                             q_target=qt, actions=actions, rewards=rewards, dones=dones, discounts=disc, invalid=invalid, target=np.asarray(tgt))
         print(f"agent57_target_{name}: {np.asarray(tgt).dtype} {np.asarray(tgt).shape} range [{np.min(tgt):.3f}, {np.max(tgt):.3f}]")
 
@@ -286,9 +284,7 @@ def _a57_config(**kw):
     import srl
     from srl.algorithms import agent57
 
-    from gen_golden_algo import _register_env
-
-    _register_env()
+    G.register_envs()
     cfg = agent57.Config(batch_size=8, actor_num=4, target_model_update_interval=5, lr_ext=0.001, lr_int=0.002, lstm_units=16, burnin=2, sequence_length=3, **kw)
     cfg.window_length = 1
     cfg.memory.warmup_size = 8
@@ -304,7 +300,7 @@ def _a57_config(**kw):
 # the sequence items the reference Agent57 worker emits (window shifting, dummy-state padding at episode end,
 # stored LSTM states, UCB actor choice) for a recorded trajectory
 # ----------------------------------------------------------------------------------------
-def gen_a57_rollout():
+def gen_a57_rollout(dest):
     import srl
     import torch
 
@@ -334,14 +330,14 @@ def gen_a57_rollout():
         save["q_ext." + k] = v
     for k, v in sdi.items():
         save["q_int." + k] = v
-    np.savez_compressed(os.path.join(OUT, "rollout_items_agent57.npz"), **save)
+    np.savez_compressed(os.path.join(dest, "rollout_items_agent57.npz"), **save)
     print(f"rollout_items_agent57: {len(log)} env records, {len(items)} items, actors {sorted(set(save['item_actor'].tolist()))}")
 
 
 # ----------------------------------------------------------------------------------------
 # one full Trainer.train() of Agent57 (agent57/model_torch.py:273-493)
 # ----------------------------------------------------------------------------------------
-def gen_a57_train_step():
+def gen_a57_train_step(dest):
     import torch
 
     import srl
@@ -419,7 +415,7 @@ def gen_a57_train_step():
         if not n.endswith("_target") or n == "lifelong_target":
             for k, v in after[n].items():
                 save[f"after.{n}.{k}"] = v
-    np.savez_compressed(os.path.join(OUT, "train_step_agent57.npz"), **save)
+    np.savez_compressed(os.path.join(dest, "train_step_agent57.npz"), **save)
     print("train_step_agent57:", {k: round(float(v), 6) for k, v in trainer.info.items() if "loss" in k})
 
 
@@ -429,7 +425,7 @@ AGENT57_GENERATORS.update(agent57_seq_target=gen_a57_target, agent57_rollout=gen
 # ----------------------------------------------------------------------------------------
 # rank-based memory (srl/rl/memories/priority_memories/rankbased_memory.py) scripted trace
 # ----------------------------------------------------------------------------------------
-def gen_rankbased():
+def gen_rankbased(dest):
     from srl.rl.memories.priority_memories.rankbased_memory import RankBasedMemory
 
     rng = np.random.default_rng(51)
@@ -449,7 +445,7 @@ def gen_rankbased():
         new_p = (rng.permutation(5000)[:B].astype(np.float32) + 2000) / 3  # distinct from everything stored
         mem.update(idx, new_p)
         ops.append((n_add, np.asarray(batches), np.asarray(weights), np.asarray(idx), new_p))
-    np.savez_compressed(os.path.join(OUT, "rankbased_trace.npz"), capacity=np.int64(cap), alpha=np.float64(alpha), beta_initial=np.float64(0.4), beta_steps=np.int64(1000),
+    np.savez_compressed(os.path.join(dest, "rankbased_trace.npz"), capacity=np.int64(cap), alpha=np.float64(alpha), beta_initial=np.float64(0.4), beta_steps=np.int64(1000),
                         seed=np.int64(123), add_priorities=adds[:k], n_add=np.array([o[0] for o in ops]), batches=np.array([o[1] for o in ops]),
                         weights=np.array([o[2] for o in ops]), indices=np.array([o[3] for o in ops]), new_priorities=np.array([o[4] for o in ops]),
                         final_priorities=mem.priorities.copy())
@@ -462,7 +458,7 @@ AGENT57_GENERATORS.update(rankbased=gen_rankbased)
 # ----------------------------------------------------------------------------------------
 # rank-based linear memory (srl/rl/memories/priority_memories/rankbased_memory_linear.py) scripted trace
 # ----------------------------------------------------------------------------------------
-def gen_rankbased_linear():
+def gen_rankbased_linear(dest):
     import random
 
     from srl.rl.memories.priority_memories.rankbased_memory_linear import RankBasedMemoryLinear
@@ -483,7 +479,7 @@ def gen_rankbased_linear():
         new_p = (rng.permutation(9000)[:B].astype(np.float64) + 5000) / 11  # distinct from everything stored
         mem.update(upd, new_p)
         ops.append((n_add, np.asarray(batches), np.asarray(weights), new_p, mem.length()))
-    np.savez_compressed(os.path.join(OUT, "rankbased_linear_trace.npz"), capacity=np.int64(cap), alpha=np.float64(alpha), beta_initial=np.float64(0.4),
+    np.savez_compressed(os.path.join(dest, "rankbased_linear_trace.npz"), capacity=np.int64(cap), alpha=np.float64(alpha), beta_initial=np.float64(0.4),
                         beta_steps=np.int64(1000), seed=np.int64(321), add_priorities=adds[:k], n_add=np.array([o[0] for o in ops]),
                         batches=np.array([o[1] for o in ops]), weights=np.array([o[2] for o in ops]), new_priorities=np.array([o[3] for o in ops]),
                         lengths=np.array([o[4] for o in ops]), final_keys=np.array([m[0] for m in mem.memory]), final_items=np.array([m[1] for m in mem.memory]),
@@ -497,7 +493,7 @@ AGENT57_GENERATORS.update(rankbased_linear=gen_rankbased_linear)
 # ----------------------------------------------------------------------------------------
 # episode replay buffer (srl/rl/memories/episode_replay_buffer.py) scripted trace
 # ----------------------------------------------------------------------------------------
-def gen_episode_buffer():
+def gen_episode_buffer(dest):
     import random
 
     from srl.rl.memories.episode_replay_buffer import EpisodeReplayBuffer
@@ -523,7 +519,7 @@ def gen_episode_buffer():
             s = mem.sample_sequential(dummy_step=[-1, -1])
             out_seq.append(np.asarray(s)[..., 0])
             out_steps.append(np.asarray(mem.sample_steps())[:, 0][:5])
-    np.savez_compressed(os.path.join(OUT, "episode_buffer_trace.npz"), seed=np.int64(99), lengths=lengths, total=np.array(out_len), sample=np.array(out_sample),
+    np.savez_compressed(os.path.join(dest, "episode_buffer_trace.npz"), seed=np.int64(99), lengths=lengths, total=np.array(out_len), sample=np.array(out_sample),
                         sequential=np.array(out_seq), steps_head=np.array(out_steps), **{k: np.int64(v) for k, v in kw.items()})
     print(f"episode_buffer_trace: {len(lengths)} episodes")
 

@@ -4,7 +4,7 @@ dueling 512, embedding 32 -> 128, RND 128, UVFA inputs = previous extrinsic rewa
 torch, so that the all-libsrlx update of device/agent57_fast.py (round 6) is pinned on the reference directly: losses, signed TD errors, priorities, and for every
 parameter tensor of the four trained networks 2048 sampled entries of ITS GRADIENT (`p.grad` at `optimizer.step()`) and of its Adam step.
 
-Run here, where /root/reference is importable:  PYTHONPATH=/root/reference python oracle/gen_golden_agent57_84.py
+Run where the reference is ($SRL_REFERENCE):  python oracle/gen_golden_agent57_84.py [OUT]
 Only data travels (tests/golden/train_step_agent57_light84.npz):
   frames uint8 [B][5][84][84]   the window + 1 consecutive frames of every item (s_0 = frames[b, 0:4], s_1 = frames[b, 1:5], oldest first)
   actions, rewards_ext, rewards_int, dones, prev_actions, prev_rewards_ext, prev_rewards_int, actor_idx, weights   [B]
@@ -14,12 +14,11 @@ The 33 M weights of the seven networks are NOT stored: `recipe_networks` below r
 LayerNorm weights get + 1).
 """
 import os
-import sys
 
 import numpy as np
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
+
 B, A, NA = 8, 6, 8
 SEEDS = dict(q_ext=20261001, q_int=20261002, q_ext_target=20261003, q_int_target=20261004, emb=20261005, lifelong_target=20261006, lifelong_train=20261007)
 NETS = ("q_ext", "q_int", "q_ext_target", "q_int_target", "emb", "lifelong_target", "lifelong_train")
@@ -51,18 +50,14 @@ def make_items(seed=23):
     return d
 
 
-def main():
+def main(out=G.GOLDEN):
     import torch
 
     import srl
     from srl.algorithms import agent57_light
     from srl.base.context import RunContext
-    from srl.base.env import registration
 
-    import _golden_env  # noqa: F401
-
-    torch.set_num_threads(8)
-    registration.register("TinyImageEnvGolden", entry_point="_golden_env:TinyImageEnv", check_duplicate=False)
+    G.register_envs()
     env = srl.EnvConfig("TinyImageEnvGolden", kwargs=dict(hw=84, actions=A)).make()
     cfg = agent57_light.Config(batch_size=B, actor_num=NA, target_model_update_interval=5)
     cfg.window_length = 4
@@ -86,34 +81,9 @@ def main():
     st = lambda b, k: np.stack([f[b, k + c] for c in range(4)], axis=-1).astype(np.float32) / 255  # noqa: E731
     batches = [[st(b, 0), st(b, 1), eye[it["actions"][b]], [], float(it["rewards_ext"][b]), np.float32(it["rewards_int"][b]), int(it["dones"][b]), eye[it["prev_actions"][b]],
                 float(it["prev_rewards_ext"][b]), np.float32(it["prev_rewards_int"][b]), int(it["actor_idx"][b])] for b in range(B)]
-    rec = {}
-    memory.sample = lambda *a, **k: (batches, it["weights"].copy(), list(range(B)))
-    memory.update = lambda update_args, priorities, step: rec.__setitem__("priorities", np.asarray(priorities).copy())
-    _uq = trainer._update_q
-    tds = []
-
-    def uq(*a, **k):
-        td, loss = _uq(*a, **k)
-        tds.append(np.asarray(td).copy())
-        return td, loss
-
-    trainer._update_q = uq
-    # p.grad at optimizer.step(): what loss.backward() left (model_torch.py:437-439, 345-347, 359-361)
-    owner = {id(p): (n, k) for n, m in nets.items() for k, p in m.named_parameters()}
-    grads = {}
-    _step = torch.optim.Adam.step
-
-    def step(self, *a, **k):
-        for g in self.param_groups:
-            for p in g["params"]:
-                if p.grad is not None:
-                    grads[owner[id(p)]] = p.grad.detach().clone().numpy()
-        return _step(self, *a, **k)
-
-    torch.optim.Adam.step = step
-    trainer.train_count = 1  # not a target-sync step
-    trainer.train()
-    torch.optim.Adam.step = _step
+    # p.grad at optimizer.step(): what loss.backward() left (model_torch.py:437-439, 345-347, 359-361); _update_q runs for the extrinsic, then the intrinsic network
+    rec = G.record_train_step(trainer, memory, batches, it["weights"], nets, hook=(trainer, "_update_q", lambda out: out[0]))
+    tds = rec["hooked"]
     save = dict(it)
     save.update(td_ext=tds[0].astype(np.float32), td_int=tds[1].astype(np.float32), priorities=rec["priorities"].astype(np.float32),
                 ext_loss=np.float32(trainer.info["ext_loss"]), int_loss=np.float32(trainer.info["int_loss"]), emb_loss=np.float32(trainer.info["emb_loss"]),
@@ -124,20 +94,11 @@ def main():
         save["shapes." + n] = np.array([str(tuple(s)) for _, s in ks[n]])
     prng = np.random.default_rng(101)
     for n in ("q_ext", "q_int", "emb", "lifelong_train"):
-        after = {k: v.detach().numpy() for k, v in nets[n].state_dict().items()}
-        for k, _ in ks[n]:
-            g = grads[(n, k)].astype(np.float64).reshape(-1)
-            d = (after[k].astype(np.float64) - before[n][k].astype(np.float64)).reshape(-1)
-            pos = np.sort(prng.choice(d.size, size=min(2048, d.size), replace=False))
-            save[f"pos.{n}.{k}"] = pos.astype(np.int64)
-            save[f"grad.{n}.{k}"] = g[pos].astype(np.float32)
-            save[f"upd.{n}.{k}"] = d[pos].astype(np.float32)
-            save[f"gsum.{n}.{k}"] = np.float64(g.sum())
-            save[f"gabs.{n}.{k}"] = np.float64(np.abs(g).sum())
-            save[f"gmax.{n}.{k}"] = np.float64(np.abs(g).max())
-    np.savez_compressed(os.path.join(OUT, "train_step_agent57_light84.npz"), **save)
+        for k, v in nets[n].state_dict().items():
+            G.sampled_entries(save, prng, f"{n}.{k}", before[n][k], v.detach().numpy(), rec["grads"][n, k], step_sums=False)
+    np.savez_compressed(os.path.join(out, "train_step_agent57_light84.npz"), **save)
     print("train_step_agent57_light84:", {k: round(float(v), 6) for k, v in trainer.info.items() if "loss" in k}, "priorities", rec["priorities"][:4])
 
 
 if __name__ == "__main__":
-    main()
+    G.run(main, __doc__)

@@ -1,39 +1,25 @@
 """oracle/gen_golden_algo.py -- TEST INFRASTRUCTURE ONLY.  Algorithm-level golden vectors recorded from the
-imported reference (run through oracle/gen_golden.py).  Everything saved is data: inputs and the
-reference's outputs."""
+imported reference (run through oracle/gen_golden.py, which hands every gen_* the output directory).  Everything
+saved is data: inputs and the reference's outputs."""
 import os
 import random
-import sys
 
 import numpy as np
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-
-
-# ----------------------------------------------------------------------------------------
-# a tiny image environment registered with the reference from OUTSIDE its tree
-# (srl/base/env/registration.py:116-136)
-# ----------------------------------------------------------------------------------------
-def _register_env():
-    from srl.base.env import registration
-
-    import _golden_env
-
-    registration.register("TinyImageEnvGolden", entry_point="_golden_env:TinyImageEnv", check_duplicate=False)
-    return _golden_env.TinyImageEnv
+import _golden_record as G
 
 
 # ----------------------------------------------------------------------------------------
 # srl.rl.functions
 # ----------------------------------------------------------------------------------------
-def gen_functions():
+def gen_functions(dest):
     from srl.rl import functions as F
 
     rng = np.random.default_rng(0)
     x32 = (rng.standard_normal(257) * 5).astype(np.float32)
     x64 = rng.standard_normal(257) * 5
     np.savez_compressed(
-        os.path.join(OUT, "functions.npz"),
+        os.path.join(dest, "functions.npz"),
         x32=x32,
         x64=x64,
         rescaling32=F.rescaling(x32),
@@ -55,7 +41,7 @@ def _make_rainbow(multisteps, double_dqn, rescale, hw=8, na=4, invalid=False, re
     import srl
     from srl.algorithms import rainbow
 
-    _register_env()
+    G.register_envs()
     env_config = srl.EnvConfig("TinyImageEnvGolden", kwargs=dict(hw=hw, actions=na, invalid=invalid))
     rl_config = rainbow.Config(
         multisteps=multisteps,
@@ -103,7 +89,7 @@ def _random_batches(rng, B, n, obs_shape, A, with_invalid, end_prob=0.25):
     return batches
 
 
-def gen_target_q():
+def gen_target_q(dest):
     import torch
 
     for name, kw in [
@@ -157,7 +143,7 @@ def gen_target_q():
         q_online = rec.get("q_online")
         q_online = q_online.reshape(B, n_on, A) if q_online is not None else np.zeros((B, 0, A), np.float32)
         np.savez_compressed(
-            os.path.join(OUT, f"target_q_{name}.npz"),
+            os.path.join(dest, f"target_q_{name}.npz"),
             multisteps=np.int64(n),
             double_dqn=np.int64(rl_config.enable_double_dqn),
             rescale=np.int64(rl_config.enable_rescale),
@@ -176,7 +162,7 @@ def gen_target_q():
         print(f"target_q_{name}: target range [{float(np.min(target_q)):.4f}, {float(np.max(target_q)):.4f}]")
 
 
-def gen_train_step():
+def gen_train_step(dest):
     """One Trainer.train() of the reference (rainbow/model_torch.py:85-122) with the host arithmetic
     around the network recorded: q rows, one-hot, IS weights, target -> loss, d loss/d q, priorities;
     plus the network itself (state_dict before/after, inputs) for the Q-network + Adam parity test."""
@@ -275,11 +261,11 @@ def gen_train_step():
         save["target." + k] = v
     for k, v in sd_after.items():
         save["after." + k] = v
-    np.savez_compressed(os.path.join(OUT, "train_step_rainbow.npz"), **save)
+    np.savez_compressed(os.path.join(dest, "train_step_rainbow.npz"), **save)
     print(f"train_step_rainbow: loss={float(trainer.info['loss']):.6f}")
 
 
-def gen_dqn_target():
+def gen_dqn_target(dest):
     """dqn.py:144-176 (int `undone` -> float64 expression) and rainbow_nomultisteps.py:10-43 (float32)."""
     import torch
 
@@ -287,7 +273,7 @@ def gen_dqn_target():
     from srl.algorithms import dqn, rainbow
     from srl.algorithms.rainbow import rainbow_nomultisteps
 
-    _register_env()
+    G.register_envs()
     for name, double_dqn, rescale in [("double", True, False), ("single_rescale", False, True), ("double_rescale", True, True)]:
         env_config = srl.EnvConfig("TinyImageEnvGolden", kwargs=dict(hw=8, actions=4))
         env = env_config.make()
@@ -333,7 +319,7 @@ def gen_dqn_target():
         ]
         rtarget, _, _ = rainbow_nomultisteps.calc_target_q(rparam, rbatches, np_dtype=np.float32)
         np.savez_compressed(
-            os.path.join(OUT, f"dqn_target_{name}.npz"),
+            os.path.join(dest, f"dqn_target_{name}.npz"),
             double_dqn=np.int64(double_dqn),
             rescale=np.int64(rescale),
             discount=np.float64(0.99),
@@ -350,13 +336,13 @@ def gen_dqn_target():
         print(f"dqn_target_{name}: ok")
 
 
-def gen_rollout_items():
+def gen_rollout_items(dest):
     """The items the reference's Rainbow worker really emits (stacking, n-step assembly, terminal
     padding, reward clip) for a recorded single-env trajectory: srl.Runner.rollout on TinyImageEnv,
     items read back from the (uncompressed) memory in insertion order."""
     import srl
 
-    TinyImageEnv = _register_env()
+    G.register_envs()
     for name, truncate in [("terminated", False), ("truncated", True)]:
         env_config, rl_config = _make_rainbow(multisteps=3, double_dqn=True, rescale=False)
         env_config.kwargs = dict(hw=8, actions=4, ep_len=6, truncate=truncate, seed=9)
@@ -379,7 +365,7 @@ def gen_rollout_items():
         it_rew = np.array([[r[2] for r in it[1:]] for it in items], np.float32)
         it_term = np.array([[r[3] for r in it[1:]] for it in items], np.float32)
         np.savez_compressed(
-            os.path.join(OUT, f"rollout_items_{name}.npz"),
+            os.path.join(dest, f"rollout_items_{name}.npz"),
             frames=frames,
             actions=actions,
             rewards=rewards,

@@ -13,20 +13,15 @@
 
 Only data is stored: file bytes the reference wrote and arrays it returned.
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_f1.py
+    python oracle/gen_golden_f1.py [OUT]
 """
 import os
 import random
-import sys
 import tempfile
 
 import numpy as np
 
-REF = os.environ.get("SRL_REFERENCE", "/root/reference")
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.dont_write_bytecode = True
-sys.path.insert(0, REF)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
 
 
 def _rainbow_memory(compress, capacity=300, warmup=16, batch=8):
@@ -48,7 +43,7 @@ class _Cfg:
         return np.float32
 
 
-def gen_memory(name, compress):
+def gen_memory(out, name, compress):
     from srl.rl.memories.priority_replay_buffer import RLPriorityReplayBuffer
 
     base = _rainbow_memory(compress)
@@ -72,7 +67,7 @@ def gen_memory(name, compress):
     random.seed(77)
     batches, w, args = other.sample(step=123)
     np.savez_compressed(
-        os.path.join(OUT, f"f1_memory_{name}.npz"),
+        os.path.join(out, f"f1_memory_{name}.npz"),
         backup_file=np.frombuffer(blob, np.uint8), backup_plain=np.frombuffer(plain, np.uint8), compress=np.bool_(compress),
         capacity=np.int64(300), warmup=np.int64(16), batch=np.int64(8), alpha=0.6, beta_initial=0.4, beta_steps=1000.0,
         final_tree=tree, final_size=np.int64(mem.memory.size), final_write=np.int64(mem.memory.tree.write), final_max_priority=np.float64(mem.memory.max_priority),
@@ -82,11 +77,12 @@ def gen_memory(name, compress):
     print(name, "ok:", len(blob), "bytes,", "size", mem.memory.size)
 
 
-def gen_parameter():
+def gen_parameter(out):
     import torch
 
     import srl
     from srl.algorithms import dqn
+    from srl.utils import common
 
     cfg = dqn.Config()
     cfg.hidden_block.set((16, 8))
@@ -94,6 +90,7 @@ def gen_parameter():
     runner = srl.Runner("Grid", cfg)
     runner.set_device("CPU")
     runner.set_seed(2)
+    common.set_seed(2)  # the runner's seed is applied when a run starts, which never happens here: seed the generators the network is initialised from
     param = runner.make_parameter()
     probe = np.arange(2 * 2, dtype=np.float32).reshape(2, 2) / 4
     with torch.no_grad():
@@ -102,12 +99,16 @@ def gen_parameter():
         p = os.path.join(d, "p.dat")
         param.save(p)
         blob = open(p, "rb").read()
-    np.savez_compressed(os.path.join(OUT, "f1_parameter_dqn.npz"), parameter_file=np.frombuffer(blob, np.uint8), probe=probe, q=q,
+    np.savez_compressed(os.path.join(out, "f1_parameter_dqn.npz"), parameter_file=np.frombuffer(blob, np.uint8), probe=probe, q=q,
                         keys=np.array(list(param.q_online.state_dict().keys())))
     print("parameter ok:", len(blob), "bytes")
 
 
+def main(out=G.GOLDEN):
+    gen_memory(out, "plain_items", False)
+    gen_memory(out, "compressed_items", True)
+    gen_parameter(out)
+
+
 if __name__ == "__main__":
-    gen_memory("plain_items", False)
-    gen_memory("compressed_items", True)
-    gen_parameter()
+    G.run(main, __doc__)

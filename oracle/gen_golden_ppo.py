@@ -13,7 +13,7 @@ continuous run on a small environment registered from outside its tree) and reco
 step saw (v, n_v, new log-probabilities, distribution parameters), the batch, and the losses the reference reported
 (`info["loss_policy"]`, `info["loss_e"]`).  Only data is written.
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_ppo.py      ->  tests/golden/ppo_v_step_{discrete,continuous}.npz
+    python oracle/gen_golden_ppo.py [OUT]      ->  tests/golden/ppo_v_step_{discrete,continuous}.npz
 
 What is NOT covered by reference outputs (no importable reference code runs it) and is pinned by known-answer tests
 written out in tests/test_ppo_pinned.py instead: the GAE recursion of ppo.py:389-404 and the value-clip branch of
@@ -25,11 +25,7 @@ import sys
 
 import numpy as np
 
-REF = os.environ.get("SRL_REFERENCE", "/root/reference")
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.dont_write_bytecode = True
-sys.path.insert(0, REF)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
 
 
 def _continuous_env():
@@ -85,7 +81,7 @@ def _continuous_env():
     return "ToyContinuousGolden"
 
 
-def record(name, env_name, continuous, entropy_weight, clip_range, sgp):
+def record(out, name, env_name, continuous, entropy_weight, clip_range, sgp):
     import torch
 
     import srl
@@ -130,21 +126,27 @@ def record(name, env_name, continuous, entropy_weight, clip_range, sgp):
                           reward=trainer.reward_np.copy(), not_terminated=trainer.not_terminated_np.copy(), loss_policy=np.float64(info["loss_policy"]),
                           loss_e=np.float64(info.get("loss_e", np.nan)), **extra))
         del rng_state
-    out = {}
+    save = {}
     for k, s in enumerate(steps):
         for key, val in s.items():
-            out[f"s{k}_{key}"] = np.asarray(val)
-    out.update(n_steps=np.int64(len(steps)), discount=np.float64(cfg.discount), clip_range=np.float64(clip_range), entropy_weight=np.float64(entropy_weight),
+            save[f"s{k}_{key}"] = np.asarray(val)
+    save.update(n_steps=np.int64(len(steps)), discount=np.float64(cfg.discount), clip_range=np.float64(clip_range), entropy_weight=np.float64(entropy_weight),
                continuous=np.bool_(continuous), squashed=np.bool_(sgp))
-    np.savez_compressed(os.path.join(OUT, f"ppo_v_step_{name}.npz"), **out)
+    np.savez_compressed(os.path.join(out, f"ppo_v_step_{name}.npz"), **save)
     print(name, "ok:", [float(s["loss_policy"]) for s in steps])
 
 
-def main():
-    record("discrete", "Grid", continuous=False, entropy_weight=0.1, clip_range=0.2, sgp=False)
+def main(out=G.GOLDEN):
+    import torch  # noqa: F401  (before the seeding: common.set_seed seeds torch only where it is imported already, srl/utils/common.py:34)
+    from srl.utils import common
+
+    # `runner.set_seed(11)` takes effect when the rollout starts (core_play.py:77), AFTER the runner has made its parameter: the first network of the process
+    # would be initialised from unseeded generators.  Seeded here, once: the second record starts from the generators as the first one leaves them.
+    common.set_seed(11)
+    record(out, "discrete", "Grid", continuous=False, entropy_weight=0.1, clip_range=0.2, sgp=False)
     env = _continuous_env()
-    record("continuous", env, continuous=True, entropy_weight=0.05, clip_range=0.1, sgp=False)
+    record(out, "continuous", env, continuous=True, entropy_weight=0.05, clip_range=0.1, sgp=False)
 
 
 if __name__ == "__main__":
-    main()
+    G.run(main, __doc__)

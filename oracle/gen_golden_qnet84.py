@@ -2,7 +2,7 @@
 benchmark geometry (84 x 84 x 4 frames, 6 actions, dueling 512: srl/algorithms/rainbow/model_torch.py:15-29 built by
 `rl_config.make_parameter()`), evaluated by the reference on CPU torch.
 
-Run here, where /root/reference is importable:  PYTHONPATH=/root/reference python oracle/gen_golden_qnet84.py
+Run where the reference is ($SRL_REFERENCE):  python oracle/gen_golden_qnet84.py [OUT]
 Only data travels (tests/golden/qnet84_*.npz): uint8 inputs and the reference's Q-values.  The 8.0 M weights are NOT stored:
 `recipe_state_dict` below regenerates them bit for bit from a numpy PCG64 stream (key order = the reference's state_dict order,
 which the fixture records), the test rebuilds them with the same function and loads them into the device network.
@@ -14,12 +14,10 @@ Two weight sets:
 allowed to be" -- the reference's own float32 result sits at |q_ref_f32 - q_ref_f64|.
 """
 import os
-import sys
 
 import numpy as np
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
 
 
 def recipe_state_dict(keys_shapes, kind: str, seed: int = 20260929):
@@ -44,11 +42,8 @@ def recipe_state_dict(keys_shapes, kind: str, seed: int = 20260929):
 def _build_reference_net():
     import srl
     from srl.algorithms import rainbow
-    from srl.base.env import registration
 
-    import _golden_env  # noqa: F401
-
-    registration.register("TinyImageEnvGolden", entry_point="_golden_env:TinyImageEnv", check_duplicate=False)
+    G.register_envs()
     env_config = srl.EnvConfig("TinyImageEnvGolden", kwargs=dict(hw=84, actions=6))
     rl_config = rainbow.Config(multisteps=3, batch_size=8, lr=0.00025)
     rl_config.window_length = 4
@@ -62,10 +57,9 @@ def _build_reference_net():
     return env, rl_config
 
 
-def main():
+def main(out=G.GOLDEN):
     import torch
 
-    torch.set_num_threads(8)
     env, rl_config = _build_reference_net()
     torch.manual_seed(0)
     parameter = rl_config.make_parameter()
@@ -84,11 +78,11 @@ def main():
             net64 = net.double()
             q64 = net64(x.double()).numpy()
             net.float()
-        np.savez_compressed(os.path.join(OUT, f"qnet84_{kind}.npz"), frames=frames, q_ref_f32=q32, q_ref_f64=q64,
+        np.savez_compressed(os.path.join(out, f"qnet84_{kind}.npz"), frames=frames, q_ref_f32=q32, q_ref_f64=q64,
                             keys=np.array([k for k, _ in keys_shapes]), shapes=np.array([str(s) for _, s in keys_shapes]),
                             kind=np.array(kind), seed=np.array(20260929))
         print(kind, "max|q|", np.abs(q32).max(), "f32 vs f64 max rel", np.abs(q32 - q64).max() / np.abs(q64).max())
 
 
 if __name__ == "__main__":
-    main()
+    G.run(main, __doc__)

@@ -4,7 +4,7 @@ run by the imported reference on CPU torch, so that the SHIPPED learner path of 
 forward, fused TD / Huber / priority head, hand-written backward, Adam fused into the first dense layer's weight gradient) is pinned on the reference directly and
 not only through the 8 x 8 toy of train_step_rainbow.npz.
 
-Run here, where /root/reference is importable:  PYTHONPATH=/root/reference python oracle/gen_golden_train84.py
+Run where the reference is ($SRL_REFERENCE):  python oracle/gen_golden_train84.py [OUT]
 Only data travels (tests/golden/train_step_rainbow84.npz):
   frames uint8 [B][7][84][84]  the n + window = 7 consecutive frames of every item (state k of item b = frames[b, k : k + 4], oldest first)
   actions / reward / done [B][3], weights [B] (importance weights handed to the trainer)
@@ -14,12 +14,11 @@ Only data travels (tests/golden/train_step_rainbow84.npz):
 The 8.0 M weights of the online and the target network are NOT stored: gen_golden_qnet84.recipe_state_dict regenerates them (kind "init", seeds 20260929 / 20260930).
 """
 import os
-import sys
 
 import numpy as np
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _golden_record as G
+
 SEED_ONLINE, SEED_TARGET = 20260929, 20260930
 B, N, A = 16, 3, 6
 
@@ -59,12 +58,12 @@ def batches_from(frames, actions, reward, done):
     return out
 
 
-def main():
+def main(out=G.GOLDEN):
     import torch
+    from srl.base.context import RunContext
 
     from gen_golden_qnet84 import _build_reference_net, recipe_state_dict
 
-    torch.set_num_threads(8)
     env, rl_config = _build_reference_net()
     rl_config.batch_size = B
     rl_config.memory.warmup_size = B
@@ -73,8 +72,6 @@ def main():
     parameter = rl_config.make_parameter()
     memory = rl_config.make_memory()
     trainer = rl_config.make_trainer(parameter, memory)
-    from srl.base.context import RunContext
-
     trainer.setup(RunContext())
     keys_shapes = [(k, tuple(v.shape)) for k, v in parameter.q_online.state_dict().items()]
     sd_on = recipe_state_dict(keys_shapes, "init", SEED_ONLINE)
@@ -82,67 +79,21 @@ def main():
     parameter.q_online.load_state_dict({k: torch.tensor(v) for k, v in sd_on.items()})
     parameter.q_target.load_state_dict({k: torch.tensor(v) for k, v in sd_tg.items()})
     frames, actions, reward, done, weights = make_items()
-    batches = batches_from(frames, actions, reward, done)
-    rec = {}
-    memory.sample = lambda *a, **k: (batches, weights.copy(), list(range(B)))
-    memory.update = lambda update_args, priorities, step: rec.__setitem__("priorities", np.asarray(priorities).copy())
-    memory.is_warmup_needed = lambda: False
-    _calc = parameter.calc_target_q
-
-    def calc(bs):
-        out = _calc(bs)
-        rec["target_q"] = np.asarray(out[0]).copy()
-        return out
-
-    parameter.calc_target_q = calc
-    orig_forward = parameter.q_online.forward
-    holder = {}
-
-    def fwd(x):
-        y = orig_forward(x)
-        if y.requires_grad:
-            holder["q"] = y.detach().clone()
-        return y
-
-    parameter.q_online.forward = fwd
     # p.grad as `loss.backward()` left it (model_torch.py:107-108), caught at `optimizer.step()` (:109): Adam's FIRST step is lr * g / (|g| + eps) ~ lr * sign(g),
     # so the step alone pins signs -- the gradient entries themselves pin the hand-written backward's magnitudes on the reference
-    names = {id(p): k for k, p in parameter.q_online.named_parameters()}
-    grads = {}
-    _step = torch.optim.Adam.step
-
-    def step(self, *a, **k):
-        for g in self.param_groups:
-            for p in g["params"]:
-                if p.grad is not None and id(p) in names:
-                    grads[names[id(p)]] = p.grad.detach().clone().numpy()
-        return _step(self, *a, **k)
-
-    torch.optim.Adam.step = step
-    trainer.train_count = 1  # not a sync step
-    trainer.train()
-    torch.optim.Adam.step = _step
-    parameter.q_online.forward = orig_forward
-    after = {k: v.detach().numpy() for k, v in parameter.q_online.state_dict().items()}
-    save = dict(frames=frames, actions=actions, reward=reward, done=done, weights=weights, target_q=rec["target_q"].astype(np.float32), q0=holder["q"].numpy(),
+    rec = G.record_train_step(trainer, memory, batches_from(frames, actions, reward, done), weights, dict(q=parameter.q_online),
+                              hook=(parameter, "calc_target_q", lambda out: out[0]), q_net=parameter.q_online)
+    target_q = rec["hooked"][0]
+    save = dict(frames=frames, actions=actions, reward=reward, done=done, weights=weights, target_q=target_q.astype(np.float32), q0=rec["q"],
                 loss=np.float32(trainer.info["loss"]), priorities=rec["priorities"].astype(np.float32), lr=np.float64(rl_config.lr), discount=np.float64(rl_config.discount),
                 seed_online=np.int64(SEED_ONLINE), seed_target=np.int64(SEED_TARGET), keys=np.array([k for k, _ in keys_shapes]),
                 shapes=np.array([str(tuple(s)) for _, s in keys_shapes]))
     prng = np.random.default_rng(99)
-    for k, _ in keys_shapes:
-        d = (after[k].astype(np.float64) - sd_on[k].astype(np.float64)).reshape(-1)
-        pos = np.sort(prng.choice(d.size, size=min(2048, d.size), replace=False))
-        save["pos." + k] = pos.astype(np.int64)
-        save["upd." + k] = d[pos].astype(np.float32)
-        save["sum." + k] = np.float64(d.sum())
-        save["abs." + k] = np.float64(np.abs(d).sum())
-        g = grads[k].astype(np.float64).reshape(-1)
-        save["grad." + k] = g[pos].astype(np.float32)
-        save["gmax." + k] = np.float64(np.abs(g).max())
-        save["gsum." + k] = np.float64(g.sum())
-    np.savez_compressed(os.path.join(OUT, "train_step_rainbow84.npz"), **save)
-    print(f"train_step_rainbow84: loss={float(trainer.info['loss']):.6f} target range [{rec['target_q'].min():.4f}, {rec['target_q'].max():.4f}]")
+    for k, v in parameter.q_online.state_dict().items():
+        G.sampled_entries(save, prng, k, sd_on[k], v.detach().numpy(), rec["grads"]["q", k], step_sums=True)
+    np.savez_compressed(os.path.join(out, "train_step_rainbow84.npz"), **save)
+    print(f"train_step_rainbow84: loss={float(trainer.info['loss']):.6f} target range [{target_q.min():.4f}, {target_q.max():.4f}]")
 
 
 if __name__ == "__main__":
-    main()
+    G.run(main, __doc__)

@@ -1,4 +1,4 @@
-"""The inputs of tests/golden/train_step_dqn84.npz (tools/gen_golden_dqn84.py): DQN's network at the Atari shape (dqn/model_torch.py:17-29 --
+"""The inputs of tests/golden/train_step_dqn84.npz (oracle/gen_golden_dqn84.py): DQN's network at the Atari shape (dqn/model_torch.py:17-29 --
 DQN image block, one dense layer of 512, out_layer over 6 actions), its weights regenerated from seeds instead of stored, and the sampled batch.
 Imported by the generator and by tests/test_dqn_engine_gpu.py; pure numpy, identical on every platform."""
 import numpy as np

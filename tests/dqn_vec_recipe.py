@@ -1,4 +1,4 @@
-"""The inputs of tests/golden/train_step_dqn_vec.npz (tools/gen_golden_dqn_vec.py): DQN's network on a flat Box(4) observation with 2 actions
+"""The inputs of tests/golden/train_step_dqn_vec.npz (oracle/gen_golden_dqn_vec.py): DQN's network on a flat Box(4) observation with 2 actions
 (dqn/model_torch.py:17-29 -- in_block (flatten) -> hidden_block (MLP) -> out_layer), its weights regenerated from seeds instead of stored, and the sampled
 batch.  Imported by the generator and by tests/test_dqn_vector_gpu.py; pure numpy, identical on every platform."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The inputs of tests/golden/train_step_rainbow_noisy_vec.npz (tools/gen_golden_rainbow_noisy_vec.py): Rainbow's network with `enable_noisy_dense` on a flat
+"""The inputs of tests/golden/train_step_rainbow_noisy_vec.npz (oracle/gen_golden_rainbow_noisy_vec.py): Rainbow's network with `enable_noisy_dense` on a flat
 Box(4) observation with 2 actions (rainbow/model_torch.py:15-29 -- the input value block's layers stay Linear; the hidden block's MLP layers and the four
 layers of the dueling head are NoisyLinear, srl/rl/torch_/modules/noisy_linear.py:8-52), its mu and sigma tensors regenerated from seeds instead of stored, and
 the sampled n-step items.  Imported by the generator and by the noisy Rainbow-on-flat-observations tests; pure numpy, identical on every platform."""

@@ -1,4 +1,4 @@
-"""The inputs of tests/golden/train_step_rainbow_vec.npz (tools/gen_golden_rainbow_vec.py): Rainbow's network on a flat Box(4) observation with 2 actions
+"""The inputs of tests/golden/train_step_rainbow_vec.npz (oracle/gen_golden_rainbow_vec.py): Rainbow's network on a flat Box(4) observation with 2 actions
 (rainbow/model_torch.py:15-29 -- in_block (flatten + the input value block's layers) -> hidden_block (MLP over layer_sizes[:-1], then a DuelingNetworkBlock
 of layer_sizes[-1] units)), its weights regenerated from seeds instead of stored, and the sampled n-step items.  Imported by the generator and by the
 Rainbow-on-flat-observations tests; pure numpy, identical on every platform."""

@@ -1,6 +1,6 @@
 """GPU tests: DQN on the device engine -- the plain Q head of libsrlx (dueling_type 3: q = W2 relu(h) + b2 over all units of the first dense layer,
 srl/algorithms/dqn/model_torch.py:17-29) through every layer: forward on both first-dense-layer paths, the fused policy, one learner step against the reference's
-Trainer.train() (tests/golden/train_step_dqn84.npz, tools/gen_golden_dqn84.py), the fused TD / Adam paths, srl.Runner(...).train() and reproducibility."""
+Trainer.train() (tests/golden/train_step_dqn84.npz, oracle/gen_golden_dqn84.py), the fused TD / Adam paths, srl.Runner(...).train() and reproducibility."""
 import copy
 import os
 import sys

@@ -352,7 +352,7 @@ def _golden():
 @pytest.mark.parametrize("shape_key", ["h64x64", "h512"])
 @pytest.mark.parametrize("double_dqn", [True, False])
 def test_learner_step_against_the_reference_trainer(shape_key, double_dqn):
-    """One srlx_mlpq_train_step against ONE Trainer.train() of the reference's DQN (tools/gen_golden_dqn_vec.py; weights and batch from tests/dqn_vec_recipe.py):
+    """One srlx_mlpq_train_step against ONE Trainer.train() of the reference's DQN (oracle/gen_golden_dqn_vec.py; weights and batch from tests/dqn_vec_recipe.py):
     target, online Q of s_0, loss and priorities within rel 1e-5; every p.grad within rel 1e-5 with an absolute slack of 1e-5 * max |g| of the tensor (entries that
     are sums of cancelling per-item terms); every parameter after Adam within rel 1e-5 (+ 1e-7), except entries whose reference gradient is below 1e-4 * max |g|:
     there the first Adam step (about lr * g / |g|) turns on the sign and size of a cancelling sum, and only the bound 2 lr holds."""
