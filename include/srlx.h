@@ -1205,6 +1205,39 @@ int srlx_seq_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H, int64
                     float *d_r_ext, float *d_r_int, float *d_dones, uint8_t *d_invalid, int64_t *d_actor, float *d_h_ext, float *d_c_ext, float *d_h_int,
                     float *d_c_int, void *stream);
 
+/* ---- Agent57 lane sequence ring (srlx_seqstore.hip) ---------------------------------------------------------------------------------------------------------
+ * The sequence replay of E lock-stepped lanes (device/sequence_store.py: LaneSequenceStore; device/agent57.py).  Every per-step field is stored ONCE, time-major,
+ * in rings the CALLER owns, position t of all lanes in row t % T; both entry points are stateless.
+ *   ring_frames  f32 [T][E][frame_stride]: the observation of (position, lane); frame_stride >= frame_elems, a multiple of 4 floats for 16-byte rows
+ *   ring_scalars i32 [T][E][8]: action i32, r_ext f32, r_int f32, undone f32, actor index i32, age i32, two zero dwords.  age = steps since the lane's episode
+ *                began, 0 on the episode's first observation
+ *   ring_invalid u8  [T][E][A]: next-step invalid-action mask
+ *   ring_hidden  f32 [T][E][4][H]: h_ext, c_ext, h_int, c_int as they were BEFORE the networks consumed that position's observation
+ * srlx_seq_lane_push writes position t of all E lanes in one launch: frames f32 [E][frame_elems], action / actor i32 [E], r_ext / r_int / undone f32 [E], invalid u8
+ * [E][A] (NULL: none), the four recurrent vectors f32 [E][H] each, first u8 [E].  A lane with first[e] != 0 (and every lane at t = 0) only delivers a new
+ * episode's first frame: its entry keeps the frame and the actor index and otherwise reads like the padding before an episode -- rewards 0, undone 1, a keyed pad
+ * action, zero recurrent state, no invalid action, age 0.  Every other lane gets age = age[t - 1] + 1, read from the ring.
+ * srlx_seq_lane_gather turns B descriptors (i64 [B][3]: lane e, absolute position t of the window's last real entry, flush offset k in 0..L-1) into the outputs of
+ * srlx_seq_gather, in one launch.  Entry l of window (e, t, k) is lane position p = t - (L - 1) + l + k:
+ *   p > t               (after the end)            zero frame, rewards 0, undone 0, no invalid action, pad action
+ *   t - p > age[t][e]   (before the episode start) zero frame, rewards 0, undone 1, no invalid action, pad action; at l = 0 zero recurrent state
+ *   otherwise           the ring's entry of position p
+ * with pad action = rng_u64(seed, e, p) % A (srlx_common.h; the same seed in both calls), so a pad keeps its value in every window that contains it.  dones and
+ * invalid are the last S entries, actor is actor[t][e], the recurrent state is entry 0's.  A descriptor outside e in [0, E), t >= 0, 0 <= k < L reads nothing and
+ * yields zeros.  That position p is still in the ring (t - p < T pushes ago) is the caller's ledger's business; a stale one reads other data, never other memory.
+ * No atomics, no LDS, plain vector stores; rows move as 16-byte accesses when frame_elems and frame_stride are multiples of 4 and both frame pointers are 16-byte
+ * aligned, as dwords otherwise (per launch).  Envelope, validated before any device call (SRLX_ERR_INVALID, srlx_last_error() names the entry point): B, L, S, A, H,
+ * frame_elems, frame_stride as srlx_seq_gather; E 1..65536; T >= L (push: >= 2) with T * E <= 2^31-1; t >= 0; no NULL pointer but push's invalid. */
+#define SRLX_SEQ_MAX_LANES 65536
+int srlx_seq_lane_push(int64_t E, int64_t A, int64_t H, int64_t frame_elems, int64_t frame_stride, int64_t T, int64_t t, uint64_t seed, const float *d_frames,
+                       const int32_t *d_action, const float *d_r_ext, const float *d_r_int, const float *d_undone, const int32_t *d_actor, const uint8_t *d_invalid,
+                       const float *d_h_ext, const float *d_c_ext, const float *d_h_int, const float *d_c_int, const uint8_t *d_first, float *d_ring_frames,
+                       int32_t *d_ring_scalars, uint8_t *d_ring_invalid, float *d_ring_hidden, void *stream);
+int srlx_seq_lane_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H, int64_t E, int64_t T, int64_t frame_elems, int64_t frame_stride, uint64_t seed,
+                         const int64_t *d_desc, const float *d_ring_frames, const int32_t *d_ring_scalars, const uint8_t *d_ring_invalid, const float *d_ring_hidden,
+                         float *d_states, int64_t *d_actions, float *d_r_ext, float *d_r_int, float *d_dones, uint8_t *d_invalid, int64_t *d_actor, float *d_h_ext,
+                         float *d_c_ext, float *d_h_int, float *d_c_int, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

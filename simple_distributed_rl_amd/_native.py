@@ -255,6 +255,8 @@ SIGNATURES = {
     "srlx_lstm_backward": (c_int, [c_i64] * 4 + [c_p] * 19),
     "srlx_seq_record_dwords": (c_i64, [c_i64] * 4),
     "srlx_seq_gather": (c_int, [c_i64] * 10 + [c_p] * 15),
+    "srlx_seq_lane_push": (c_int, [c_i64] * 7 + [c_u64] + [c_p] * 17),
+    "srlx_seq_lane_gather": (c_int, [c_i64] * 9 + [c_u64] + [c_p] * 17),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

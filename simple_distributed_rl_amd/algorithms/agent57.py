@@ -107,13 +107,17 @@ class Memory(RLPriorityReplayBuffer):
     tensors assembled by one launch.  `memory.compress` has no meaning for the device store and is ignored there.
 
     "device" needs first-in-first-out eviction (a sequence slot is serial % capacity), plain adds in the worker's order and a GPU; it refuses the rank-based
-    memories, the demo memory, serialized adds (`train_mp`) and a run without a GPU, each with its reason."""
+    memories, the demo memory, serialized adds (`train_mp`) and a run without a GPU, each with its reason.
+
+    The E-lane engine (device/agent57.py) hands a "device" memory its lane ring with `attach_lane_store` before anything is added; the memory then takes serials
+    through `add_serial` and gathers its batches from the ring."""
 
     sequence_store = "host"  # "host" | "device": an attribute of the memory (of the class: the default), like QNetwork.lstm_backend
 
-    def __init__(self, *args):
-        self._sequence_store = self.sequence_store
+    def __init__(self, *args, sequence_store=None):
+        self._sequence_store = self.sequence_store if sequence_store is None else sequence_store  # (the keyword: this memory only, whatever the class says)
         self._store = None
+        self._lane_store = False  # whether `_store` is an engine's lane ring (attach_lane_store)
         if self._sequence_store not in ("host", "device"):
             raise ValueError(f"sequence_store {self._sequence_store!r}: 'host' or 'device'")
         if self._sequence_store == "device":
@@ -136,6 +140,24 @@ class Memory(RLPriorityReplayBuffer):
         L, S, A, H = layout if layout is not None else (c.burnin + c.sequence_length + 1, c.sequence_length, c.action_space.n, c.lstm_units)
         self._store = DeviceSequenceStore(require_gpu(c.used_device_torch), self.cfg.capacity, L, S, A, H, frame_shape, frame_capacity)
 
+    def attach_lane_store(self, store) -> None:
+        """Hands this memory the lane ring of an E-lane engine (device/sequence_store.py: LaneSequenceStore) in place of the store it would build
+        itself: the engine pushes lock-steps into the ring and adds each emitted window's serial with `add_serial`; `sample` gathers from the ring.  Only a
+        "device" memory that holds nothing yet can take one."""
+        if self._sequence_store != "device":
+            raise ValueError("attach_lane_store: the memory's sequence_store is 'host'; the lane ring serves sequence_store 'device'")
+        if self._store is not None or self.memory.length() > 0:
+            raise RuntimeError("attach_lane_store: the memory already holds sequences (or a store); hand it the lane ring before anything is added")
+        if store.ledger.seq_capacity != self.cfg.capacity:
+            raise ValueError(f"attach_lane_store: the lane ring keeps {store.ledger.seq_capacity} live windows, the memory's capacity is {self.cfg.capacity}")
+        self._store, self._lane_store = store, True
+
+    def add_serial(self, serial: int, priority=None) -> None:
+        """A window the attached lane ring emitted: its serial is the inner priority memory's item."""
+        if not self._lane_store:
+            raise RuntimeError("add_serial: no lane ring is attached (attach_lane_store)")
+        self.memory.add(int(serial), priority)
+
     def _device_store(self, item=None):
         if self._store is None:
             self._build_store(np.asarray(item[0][0]).shape if item is not None else tuple(self.config.observation_space.shape))
@@ -144,6 +166,8 @@ class Memory(RLPriorityReplayBuffer):
     def add(self, batch: Any, priority=None, serialized: bool = False) -> None:
         if self._sequence_store != "device":
             return super().add(batch, priority, serialized)
+        if self._lane_store:
+            raise RuntimeError("sequence_store 'device': this memory reads an engine's lane ring; items are pushed there, not added here")
         if serialized:
             raise RuntimeError("sequence_store 'device': a serialized add (train_mp) arrives pickled, its frames shared with no other item; use sequence_store 'host'")
         self.memory.add(self._device_store(batch).add(batch), priority)
@@ -163,6 +187,9 @@ class Memory(RLPriorityReplayBuffer):
         return data
 
     def call_restore(self, data: Any, **kwargs) -> None:
+        if self._lane_store:  # (before anything is changed; `call_backup` refuses through the ring's `backup`)
+            raise RuntimeError("sequence_store 'device': this memory reads an engine's lane ring, which has no restore yet (its windows are views of rings the "
+                               "running lanes still write); restore into a 'host' memory or the plugin's device store instead")
         super().call_restore(data, **kwargs)
         if self._sequence_store == "device":
             if len(data) < 3:

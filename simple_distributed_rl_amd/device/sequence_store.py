@@ -7,7 +7,10 @@ against the frames of the previous add, so every distinct observation is uploade
 
 Contract on mutation: a frame is snapshotted when its object is first seen.  An observation array that is mutated in place after it was handed to `add` is
 outside the contract (the later windows that share the object keep the snapshot).  The reference's own `compress=False` memory keeps references to the same
-objects and has the same exposure, in the other direction (there every stored window would change)."""
+objects and has the same exposure, in the other direction (there every stored window would change).
+
+The E-lane engine (device/agent57.py) has a store of its own below: `LaneLedger` / `LaneSequenceStore` keep every per-step field once in time-major
+rings `[T][E]`, and a window is a view of them (`srlx_seq_lane_push`, `srlx_seq_lane_gather`)."""
 from typing import Any, List, Optional
 
 import numpy as np
@@ -335,3 +338,227 @@ class DeviceSequenceStore:
         self.records.copy_(torch.from_numpy(np.ascontiguousarray(data["records"], dtype=np.int32)))
         self.any_invalid = np.array(data["any_invalid"], bool)
         torch.cuda.synchronize(self.device)
+
+
+# ---- E lock-stepped lanes: a window is a view of time-major rings ---------------------------------------------------------------------------------
+def pad_action(seed: int, lane, position, n_actions: int):
+    """The keyed pad action of lane position `position` (srlx.h, "Agent57 lane sequence ring"): rng_u64(seed, lane, position) % A, numpy, any shapes."""
+    m64 = lambda z: _mix64(z)  # noqa: E731
+    with np.errstate(over="ignore"):
+        s = np.uint64(seed) + np.asarray(lane).astype(np.uint64) * np.uint64(0xD1342543DE82EF95)
+        x = m64(m64(s) + np.asarray(position).astype(np.int64).astype(np.uint64) * np.uint64(0xAEF17502108EF2D9))
+    return (x % np.uint64(n_actions)).astype(np.int64)
+
+
+def _mix64(z):
+    z = np.asarray(z, np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+class LaneLedger:
+    """Host bookkeeping of the lane ring (numpy only): which ring position a lock-step takes, the serial of every emitted window and serial -> (lane e, absolute
+    position t of the window's last real entry, flush offset k).
+
+    Order: serials follow the lock-steps, lane-major within a lock-step; within a lane the step's window (k = 0) comes first, then, when the step ended the
+    episode, its L - 1 flush windows (k = 1..L-1) -- the order `agent57.Worker.on_step` adds them in.  A lane that is `first` in a lock-step (it only delivers
+    a new episode's first frame) emits nothing.
+
+    Invariant: no live window (one of the last `seq_capacity` serials) references a ring position that has been overwritten.  Window (e, t, k) references the
+    positions max(t - (L - 1) + k, t - age[t][e]) .. t; position t sits in row t % T and is overwritten by push t + T.  `push` refuses (LedgerError, before
+    anything is changed) a lock-step that would overwrite a position one of the live windows references.
+
+    Ring length: a lane emits at least W - 1 windows in any W consecutive lock-steps (an episode of n steps takes n + 1 lock-steps and emits n + L - 1 >= n + 1
+    windows; only a trailing unfinished episode of j lock-steps emits j - 1), so E lanes emit at least E (W - 1).  If the oldest live window was emitted at
+    lock-step t0 and the ring is now at lock-step t, the windows of lock-steps t0 + 1 .. t are all live and fewer than seq_capacity: E (t - t0 - 1) <
+    seq_capacity, so t - t0 <= ceil(seq_capacity / E).  That window references positions >= t0 - (L - 1), and push t + 1 overwrites position t + 1 - T:
+    T >= ceil(seq_capacity / E) + L + 1 is enough, and the default ceil(seq_capacity / E) + 2 L leaves L - 1 rows of slack."""
+
+    def __init__(self, n_lanes: int, seq_capacity: int, window: int, ring_len: Optional[int] = None):
+        self.E, self.seq_capacity, self.L = int(n_lanes), int(seq_capacity), int(window)
+        if self.E < 1 or self.L < 2 or self.seq_capacity < self.E * self.L:
+            raise ValueError(f"LaneLedger: lanes {n_lanes} >= 1, window {window} >= 2 and seq_capacity {seq_capacity} >= lanes * window (one lock-step's windows) required")
+        self.ring_len = self.default_ring_len(self.E, self.seq_capacity, self.L) if ring_len is None else int(ring_len)
+        if self.ring_len < self.L:
+            raise ValueError(f"LaneLedger: ring_len {self.ring_len} below the window {self.L}")
+        self.t = 0  # lock-steps pushed so far = the next position
+        self.serial = 0  # windows emitted so far
+        self.age = np.zeros(self.E, np.int64)  # of the last pushed position
+        self._owes_first = np.zeros(self.E, bool)  # lanes whose last step ended their episode
+        self._emitted = True  # (every push is followed by one emit)
+        C = self.seq_capacity
+        self._e, self._t, self._k, self._lo = (np.zeros(C, np.int64) for _ in range(4))  # per serial % seq_capacity; _lo: the oldest position the window references
+
+    @staticmethod
+    def default_ring_len(n_lanes: int, seq_capacity: int, window: int) -> int:
+        return -(-int(seq_capacity) // int(n_lanes)) + 2 * int(window)
+
+    def is_live(self, serial: int) -> bool:
+        return self.serial - self.seq_capacity <= serial < self.serial
+
+    def window_counts(self, first, done) -> np.ndarray:
+        """Windows each lane emits in a lock-step: 1 per stepping lane, + L - 1 when its step ended the episode, 0 for `first` lanes."""
+        first, done = np.asarray(first, bool), np.asarray(done, bool)
+        return np.where(first, 0, 1 + done * (self.L - 1)).astype(np.int64)
+
+    def push(self, first) -> int:
+        """Claims the next ring position for a lock-step whose `first` lanes (bool [E]) only deliver a new episode's first frame; returns the position."""
+        first = np.asarray(first, bool).reshape(-1)
+        if first.shape[0] != self.E:
+            raise ValueError(f"LaneLedger: a first mask of {first.shape[0]} lanes, the ring has {self.E}")
+        if not self._emitted:
+            raise RuntimeError("LaneLedger: push without the emit of the previous lock-step")
+        if self.t == 0 and not first.all():
+            raise ValueError("LaneLedger: every lane begins an episode at position 0")
+        if (self._owes_first & ~first).any():
+            raise ValueError(f"LaneLedger: lanes {np.nonzero(self._owes_first & ~first)[0].tolist()} ended their episode and must be first in this lock-step")
+        t, C = self.t, self.seq_capacity
+        gone = t - self.ring_len  # the position this push overwrites
+        oldest = max(0, self.serial - C)
+        if gone >= 0 and oldest < self.serial and gone >= self._t[oldest % C] - (self.L - 1):  # (serials are ordered by t: the cheap bound first)
+            lo = self._lo[np.arange(oldest, self.serial) % C]
+            if int(lo.min()) <= gone:
+                s = oldest + int(np.argmax(lo <= gone))
+                raise LedgerError(f"LaneLedger: lock-step {t} would overwrite position {gone}, which live window {s} (lane {self._e[s % C]}, position "
+                                  f"{self._t[s % C]}, flush {self._k[s % C]}) still references (ring of {self.ring_len} rows, {C} live windows of {self.L} entries, "
+                                  f"{self.E} lanes; {self.default_ring_len(self.E, C, self.L)} rows never refuse)")
+        self.age = np.where(first, 0, self.age + 1)
+        self._first = first
+        self.t = t + 1
+        self._emitted = False
+        return t
+
+    def emit(self, done) -> np.ndarray:
+        """Registers the windows of the lock-step just pushed, given which lanes' steps ended their episode (bool [E]); returns their serials, in order."""
+        if self._emitted:
+            raise RuntimeError("LaneLedger: emit without a push")
+        done = np.asarray(done, bool).reshape(-1) & ~self._first
+        counts = self.window_counts(self._first, done)
+        n, t, C, L = int(counts.sum()), self.t - 1, self.seq_capacity, self.L
+        lanes = np.repeat(np.arange(self.E), counts)
+        k = np.arange(n) - np.repeat(np.cumsum(counts) - counts, counts)
+        slots = (self.serial + np.arange(n)) % C
+        self._e[slots], self._t[slots], self._k[slots] = lanes, t, k
+        self._lo[slots] = t - np.minimum(L - 1 - k, self.age[lanes])
+        serials = self.serial + np.arange(n)
+        self.serial += n
+        self._owes_first = done
+        self._emitted = True
+        return serials
+
+    def descriptors(self, serials) -> np.ndarray:
+        """int64 [B][3]: (lane, position, flush offset) of live serials."""
+        s = np.asarray(serials, np.int64).reshape(-1)
+        if s.size and (s.min() < self.serial - self.seq_capacity or s.max() >= self.serial):
+            bad = int(s[(s < self.serial - self.seq_capacity) | (s >= self.serial)][0])
+            raise LedgerError(f"lane store: window {bad} is not among the last {self.seq_capacity} emitted ({self.serial} so far)")
+        i = s % self.seq_capacity
+        return np.stack([self._e[i], self._t[i], self._k[i]], axis=1)
+
+
+class LaneSequenceStore:
+    """The HBM side of the lane ring: frames [T][E][stride] float32 (stride = frame_elems rounded up to 4 floats), scalars [T][E][8] int32, invalid masks
+    [T][E][A] uint8, recurrent vectors [T][E][4][H] float32, and a `LaneLedger`.  `push` is one `srlx_seq_lane_push` launch and `gather` one
+    `srlx_seq_lane_gather` launch on torch's current stream, so pushes and gathers issued on one stream are ordered; neither synchronises."""
+
+    def __init__(self, device, n_lanes: int, seq_capacity: int, window: int, sequence_length: int, n_actions: int, units: int, frame_shape, seed: int = 0,
+                 ring_len: Optional[int] = None):
+        import torch
+
+        from simple_distributed_rl_amd import _native as N
+        from simple_distributed_rl_amd.algorithms._device_ops import require_gpu
+
+        self.device = require_gpu(str(device))
+        self._N, self._lib = N, N.lib()
+        self.frame_shape = tuple(int(d) for d in frame_shape)
+        self.frame_elems = int(np.prod(self.frame_shape, dtype=np.int64))
+        self.stride = _round4(self.frame_elems)
+        self.layout = RecordLayout(window, sequence_length, n_actions, units)  # (L, S, A, H and the envelope check; the lane ring keeps no records)
+        lay = self.layout
+        if self._lib.srlx_seq_record_dwords(lay.L, lay.S, lay.A, lay.H) != lay.dwords:
+            raise ValueError(f"lane store: window {lay.L}, sequence {lay.S}, actions {lay.A}, units {lay.H} are outside srlx_seq_lane_gather's envelope (srlx.h)")
+        if not 1 <= self.frame_elems <= 1 << 20:
+            raise ValueError(f"lane store: a frame of {self.frame_elems} elements is outside srlx_seq_lane_gather's envelope (1..2^20)")
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.ledger = LaneLedger(n_lanes, seq_capacity, window, ring_len)
+        T, E, d = self.ledger.ring_len, self.ledger.E, self.device
+        if T * E > 2**31 - 1:
+            raise ValueError(f"lane store: {T} rows of {E} lanes are outside srlx_seq_lane_gather's envelope (T * E <= 2^31-1)")
+        self.frames = torch.empty((T, E, self.stride), dtype=torch.float32, device=d)
+        self.scalars = torch.zeros((T, E, 8), dtype=torch.int32, device=d)
+        self.invalid = torch.zeros((T, E, lay.A), dtype=torch.uint8, device=d)
+        self.hidden = torch.zeros((T, E, 4, lay.H), dtype=torch.float32, device=d)
+        self.any_invalid = False  # whether any push has carried an invalid-action mask
+
+    @staticmethod
+    def ring_bytes(n_lanes: int, seq_capacity: int, window: int, n_actions: int, units: int, frame_elems: int, ring_len: Optional[int] = None) -> int:
+        """HBM bytes of the four rings (host arithmetic)."""
+        T = LaneLedger.default_ring_len(n_lanes, seq_capacity, window) if ring_len is None else int(ring_len)
+        return T * int(n_lanes) * (4 * _round4(frame_elems) + 32 + int(n_actions) + 16 * int(units))
+
+    def push(self, frames, action, r_ext, r_int, undone, actor, h_ext, c_ext, h_int, c_int, first, first_dev=None, invalid=None) -> int:
+        """One lock-step of all lanes: device tensors frames float32 [E, ...], action / actor int32 [E], r_ext / r_int / undone float32 [E], the four recurrent
+        vectors float32 [E][H] as they were before the networks consumed `frames`, `first` a host bool [E] (`first_dev`: the same mask as device uint8, uploaded
+        here when not given), `invalid` uint8 [E][A] or None.  Returns the position; `emit(done)` then names the windows."""
+        import torch
+
+        N, lay, led = self._N, self.layout, self.ledger
+        E = led.E
+        first = np.asarray(first, bool).reshape(-1)
+        want = {"frames": (torch.float32, E * self.frame_elems), "action": (torch.int32, E), "r_ext": (torch.float32, E), "r_int": (torch.float32, E),
+                "undone": (torch.float32, E), "actor": (torch.int32, E), "h_ext": (torch.float32, E * lay.H), "c_ext": (torch.float32, E * lay.H),
+                "h_int": (torch.float32, E * lay.H), "c_int": (torch.float32, E * lay.H)}
+        got = dict(frames=frames, action=action, r_ext=r_ext, r_int=r_int, undone=undone, actor=actor, h_ext=h_ext, c_ext=c_ext, h_int=h_int, c_int=c_int)
+        for k, (dt, n) in want.items():
+            v = got[k]
+            if v.dtype != dt or v.numel() != n or not v.is_contiguous() or v.device != self.device:
+                raise ValueError(f"lane store: push argument {k} must be a contiguous {dt} tensor of {n} elements on {self.device}")
+        if invalid is not None and (invalid.dtype != torch.uint8 or invalid.numel() != E * lay.A or not invalid.is_contiguous() or invalid.device != self.device):
+            raise ValueError(f"lane store: push argument invalid must be a contiguous uint8 tensor of {E * lay.A} elements on {self.device}")
+        t = led.push(first)  # (refuses before anything is written)
+        if first_dev is None:
+            first_dev = torch.from_numpy(first.astype(np.uint8)).to(self.device)
+        self._keep_push = (got, first_dev, invalid)  # alive until the stream has run the launch
+        self.any_invalid = self.any_invalid or invalid is not None
+        N.check(self._lib.srlx_seq_lane_push(E, lay.A, lay.H, self.frame_elems, self.stride, led.ring_len, t, self.seed, N.tptr(frames), N.tptr(action), N.tptr(r_ext),
+                                             N.tptr(r_int), N.tptr(undone), N.tptr(actor), N.tptr(invalid), N.tptr(h_ext), N.tptr(c_ext), N.tptr(h_int), N.tptr(c_int),
+                                             N.tptr(first_dev), N.tptr(self.frames), N.tptr(self.scalars), N.tptr(self.invalid), N.tptr(self.hidden),
+                                             N.torch_stream_ptr()))
+        return t
+
+    def emit(self, done) -> np.ndarray:
+        return self.ledger.emit(done)
+
+    def gather_serials(self, serials) -> SequenceBatch:
+        return self.gather(self.ledger.descriptors(serials))
+
+    def gather(self, descriptors) -> SequenceBatch:
+        """descriptors: int64 [B][3] (lane, position, flush offset), host or device."""
+        import torch
+
+        lay, d = self.layout, self.device
+        desc = torch.as_tensor(np.ascontiguousarray(descriptors, dtype=np.int64) if not torch.is_tensor(descriptors) else descriptors).to(d).contiguous()
+        if desc.dim() != 2 or desc.shape[1] != 3 or desc.shape[0] < 1 or desc.dtype != torch.int64:
+            raise ValueError("lane store: descriptors are int64 [B][3] with B >= 1")
+        B, L, S, A, H = int(desc.shape[0]), lay.L, lay.S, lay.A, lay.H
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=d)  # noqa: E731
+        out = dict(states=f32(B, L, *self.frame_shape), act_idx=torch.empty((B, L), dtype=torch.int64, device=d), r_ext=f32(B, L), r_int=f32(B, L), dones=f32(B, S),
+                   invalid=torch.empty((B, S, A), dtype=torch.uint8, device=d), actor=torch.empty(B, dtype=torch.int64, device=d), h_ext=f32(B, H), c_ext=f32(B, H),
+                   h_int=f32(B, H), c_int=f32(B, H))
+        self.gather_into(desc, out)
+        self._keep = desc  # alive until the stream has run the launch
+        return SequenceBatch(any_invalid=self.any_invalid, **out)
+
+    def gather_into(self, desc, out: dict) -> None:
+        """The launch alone: `desc` int64 [B][3] on the device, `out` the eleven output tensors by SequenceBatch's names."""
+        N, lay, led = self._N, self.layout, self.ledger
+        N.check(self._lib.srlx_seq_lane_gather(int(desc.shape[0]), lay.L, lay.S, lay.A, lay.H, led.E, led.ring_len, self.frame_elems, self.stride, self.seed,
+                                               N.tptr(desc), N.tptr(self.frames), N.tptr(self.scalars), N.tptr(self.invalid), N.tptr(self.hidden),
+                                               *[N.tptr(out[k]) for k in SequenceBatch.__slots__[:-1]], N.torch_stream_ptr()))
+
+    def backup(self) -> dict:
+        raise RuntimeError("lane store: the lane ring has no backup format yet (its windows are views of rings the running lanes still write); back up a "
+                           "'host' memory or the plugin's device store instead")

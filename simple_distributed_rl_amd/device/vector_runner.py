@@ -231,6 +231,8 @@ def why_not_vector(context, env, rl_config) -> str:
     kind = engine_kind(rl_config)
     if kind is None:
         return f"no device engine for algorithm '{rl_config.get_name()}'"
+    if kind == "agent57":  # the LSTM engine has its own envelope (device/agent57.py)
+        return why_not_agent57_engine(env, rl_config)
     if env.player_num != 1:
         return "multi-player environment"
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
@@ -415,7 +417,9 @@ def why_not_flat_rainbow(env, rl_config, admit_noisy: bool = False) -> str:
 
 
 def auto_lanes_reason(env, rl_config, n_envs) -> str:
-    """Flat-observation DQN engages the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
+    """Flat-observation DQN and Agent57 engage the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
+    if engine_kind(rl_config) == "agent57" and isinstance(n_envs, str):
+        return "Agent57 stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
     if is_flat_dqn(env, rl_config) and isinstance(n_envs, str):
         return "flat-observation DQN stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
     return ""
@@ -575,7 +579,50 @@ def ppo_config_from(rl_config, env, n_envs: int, seed: int, horizon: int = 32, e
 
 def engine_kind(rl_config) -> Optional[str]:
     """Which device engine serves this algorithm config (None = the plugin classes only)."""
-    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light", "DQN": "dqn"}.get(rl_config.get_name())
+    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light", "DQN": "dqn", "Agent57": "agent57"}.get(rl_config.get_name())
+
+
+AGENT57_MP_REASON = "Agent57 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
+
+
+def why_not_agent57_engine(env, rl_config, n_envs=None) -> str:
+    """Empty string when `Agent57Engine` (device/agent57.py) can run this agent57.Config on this environment; otherwise EVERY reason it cannot, joined with "; "
+    (as `why_not_ppo_engine`).  The envelope figures are srlx_seq_lane_gather's (srlx.h: SRLX_SEQ_MAX_*) and SrlxLstm's.  `n_envs`: the lane count of
+    set_vector_envs(n), when the caller has one: the reasons that depend on it are then part of the answer."""
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+
+    c, why = rl_config, []
+    if c.get_name() != "Agent57":
+        return f"'{c.get_name()}' is not an agent57.Config"
+    if not str(c.used_device_torch).startswith("cuda"):
+        why.append("the run is not on a GPU device")
+    if not isinstance(env.action_space, DiscreteSpace):
+        why.append("the engine serves discrete action spaces")
+    if env.player_num != 1:
+        why.append("multi-player environment")
+    mem = _why_not_memory(c)
+    if mem:
+        why.append(mem)
+    if c.window_length != 1:
+        why.append("the engine's networks read one observation per step (window_length 1)")
+    if getattr(c, "_obs_processors", None):
+        why.append("observation processors are served by the plugin path: the lanes hand the networks the environment's float32 observation")
+    L = c.burnin + c.sequence_length + 1
+    if not 2 <= L <= 513:
+        why.append(f"the window burnin + sequence_length + 1 = {L} is outside the lane gather's 2..513")
+    n = getattr(env.action_space, "n", 0)
+    if isinstance(env.action_space, DiscreteSpace) and not 1 <= n <= 64:
+        why.append(f"{n} actions are outside the lane gather's 1..64")
+    if not 1 <= c.lstm_units <= 1024:
+        why.append(f"{c.lstm_units} recurrent units are outside the lane gather's 1..1024")
+    if c.batch_size > 1024:
+        why.append(f"a batch of {c.batch_size} is outside the lane gather's 1..1024")
+    if isinstance(n_envs, int) and n_envs > 0:
+        if n_envs > 256:
+            why.append(f"{n_envs} lanes: the acting pass's LSTM kernels serve at most 256 rows (srlx.h), and the engine does not fall back to nn.LSTM")
+        if n_envs * L > c.memory.capacity:
+            why.append(f"{n_envs} lanes of window {L} emit up to {n_envs * L} windows in one lock-step, more than memory.capacity {c.memory.capacity} keeps")
+    return "; ".join(why)
 
 
 def frame_space(env, rl_config):
@@ -903,3 +950,32 @@ class VectorAgent57Actor(VectorActor):
         eng.capture_graphs()
         self._graphs_ready = True
         return eng.train_count - before
+
+
+class VectorAgent57LstmActor(VectorAgent57Actor):
+    """`Runner.train()` with Agent57 (the LSTM one) on a GPU under set_vector_envs(n): n lanes of `Agent57Engine` (device/agent57.py), which steps host
+    environments with float32 observations and trains the Runner's Parameter in place with the plugin's own trainer."""
+
+    def _make_batch_env(self, ring, context):
+        env = HostVecEnv(self.env_run.config, self.lanes, ring.dev, context.seed, float_obs=True)
+        env.setup(context)
+        return env
+
+    def _make_engine(self, context, device: int, seed: int):
+        from simple_distributed_rl_amd.device.agent57 import Agent57Engine
+
+        return Agent57Engine(self.rl_config, self.lanes, device, seed=seed, env=lambda ring: self._make_batch_env(ring, context), parameter=self.parameter,
+                             context=context)
+
+    def attach(self, context, state):
+        fresh = self.engine is None
+        super().attach(context, state)
+        if not fresh:  # a further train() on the same engine: the trainer is set up with this run's context, as the plugin learner's is when a run opens
+            self.engine.setup_trainer(context)
+
+    def _set_mode(self, context):
+        assert context.training, "Agent57Engine only trains: evaluate / rollout stay on the plugin path"
+
+    def ensure_graphs(self):
+        """(the lock-step reads `done` back and the trainer is torch's eager autograd: nothing is captured)"""
+        return 0

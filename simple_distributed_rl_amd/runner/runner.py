@@ -14,6 +14,7 @@ algorithm, device) triple is served by the hand-written engine -- the Rainbow fa
 If so the same loop (`base/run/sequence.py`) is driven by the device drivers with `vector_envs` environments per
 iteration (`set_vector_envs`; "AUTO" = 1024 device-resident lanes, 64 for host-stepped environments) and the trained
 weights are written back into `runner.parameter` at the end, so `evaluate()` / `save_parameter()` see them.
+Agent57 (the LSTM one) has an engine of its own (`device/agent57.py`), taken by `train()` only under `set_vector_envs(n)` with n > 0.
 Everything else runs the registered plugin classes on one host environment, as the reference does;
 `runner.vector_reason` says why."""
 from typing import List, Optional, Union
@@ -120,6 +121,8 @@ class Runner:
         from simple_distributed_rl_amd.device import vector_runner as vr
 
         self.vector_reason = vr.why_not_vector(c, env, self.rl_config) or vr.auto_lanes_reason(env, self.rl_config, self._vector_envs)
+        if not self.vector_reason and vr.engine_kind(self.rl_config) == "agent57":  # the reasons that depend on the lane count
+            self.vector_reason = vr.why_not_agent57_engine(env, self.rl_config, n_envs=int(self._vector_envs))
         if self.vector_reason:
             return None
         lanes = self._vector_envs
@@ -127,7 +130,7 @@ class Runner:
             lanes = 1024 if hasattr(type(env.unwrapped), "device_vector") else 64
         actor = self._vector_actor
         if actor is None or actor.lanes != int(lanes):
-            cls = vr.VectorAgent57Actor if vr.engine_kind(self.rl_config) == "agent57_light" else vr.VectorActor
+            cls = {"agent57_light": vr.VectorAgent57Actor, "agent57": vr.VectorAgent57LstmActor}.get(vr.engine_kind(self.rl_config), vr.VectorActor)
             actor = self._vector_actor = cls(env, self.rl_config, self.make_parameter(), int(lanes))
         return actor, (vr.VectorLearner(actor) if with_learner else None)
 
@@ -218,8 +221,11 @@ class Runner:
                 from simple_distributed_rl_amd.device import vector_runner as vr
 
                 self.vector_reason = vr.why_not_vector(c, self.make_env(), self.rl_config)
-                if not self.vector_reason and vr.engine_kind(self.rl_config) == "dqn":  # (device/mp_runner.py serves the Rainbow family)
+                kind = vr.engine_kind(self.rl_config)
+                if not self.vector_reason and kind == "dqn":  # (device/mp_runner.py serves the Rainbow family)
                     self.vector_reason = "DQN runs on the device engine in train(); train_mp() keeps it on the plugin path"
+                if kind == "agent57":  # its engine is one process on one GPU
+                    self.vector_reason = vr.AGENT57_MP_REASON
                 if not self.vector_reason:  # one process per GPU over RCCL (device/mp_runner.py); this process is the learner rank
                     from simple_distributed_rl_amd.device.mp_runner import train_mp_on_engine
 
