@@ -1114,6 +1114,24 @@ int srlx_qnet_noisy_effective(srlx_qnet_t *h, int which, float *d_out, int64_t *
  *   srlx_mlpq_noisy_draw   : synchronises the device; *set_next (may be NULL) becomes the id the next pass uses; *next_out (may be NULL) receives that id
  *   srlx_mlpq_noisy_eps    : writes eps(seed of the handle, draw, param_index, .) of one noisy tensor into d_out (its shape): the noise of a step, known before
  *                            the step runs
+ *
+ * Categorical DQN (C51; srl/algorithms/c51/c51.py:23-142: in_block -> hidden_block (MLP) -> Dense(A * N) reshaped to [A][N], a softmax over the N atoms of the
+ * support linspace(v_min, v_max, N), Q = the expectation; srlx_c51_math.h holds the arithmetic once and states its precision):
+ *   srlx_mlpq_create_categorical : a plain handle whose out_layer has n_actions * n_atoms rows (row a * n_atoms + j: atom j of action a).  obs_dim 1..256,
+ *                            n_layers 1..3 of 32..512 units in multiples of 32, n_actions 2..32, n_atoms 2..256, n_actions * n_atoms <= 512, v_min < v_max both
+ *                            finite, max_batch <= 256; anything else is an error before any device call.  srlx_mlpq_bind / _bind_grads / _bind_adam /
+ *                            _publish take the 2 * (n_layers + 1) tensors of a plain handle.  srlx_mlpq_forward writes the EXPECTATIONS where Q rows go
+ *                            (d_q [rows][n_actions]) and selects actions on them by the same keyed rule.  srlx_mlpq_train_step, srlx_mlpq_train_nstep and
+ *                            srlx_mlpq_bind_noisy refuse such a handle.
+ *   srlx_mlpq_train_categorical : one C51 update (c51.py:70-142) in two launches: 8 items per workgroup, ONE online pass over s_0 and s_1 (there is no target
+ *                            network, :91), the greedy next action by expectation, the projected target distribution, the clipped cross-entropy and its seeds,
+ *                            the backward chain; then srlx_mlpq_train_step's gradient / Adam launch.  d_offsets int64 [B][2], actions i32 [B], rewards /
+ *                            terminated f32 [B].  Outputs: d_q0 [B][n_actions] expectations of s_0, d_p0 [B][n_atoms] the softmax of a_0's logits, d_m
+ *                            [B][n_atoms] the projected target, d_loss [1] the batch mean, d_item_loss [B] the items' cross-entropies (they stand where the
+ *                            priorities stand: a uniform memory ignores the values and counts the update).  Bit-reproducible.  Refuses any other handle.
+ *   srlx_c51_loss          : the same item arithmetic in one launch on logits f32 [B][n_actions * n_atoms] of s' and s that the caller computed (the plugin
+ *                            trainer's torch forward): d_m / d_p0 [B][n_atoms], d_grad_logits [B][n_actions * n_atoms] = d mean-loss / d logits of s (zero outside
+ *                            a_0's atoms), d_loss [1].  On the same logits every output is srlx_mlpq_train_categorical's bits.
  * Batch CartPole (envs/cartpole.py:step; srlx_mlpq.hip): float64 state [E][4], steps / episodes int32 [E].  A lane whose d_needs_reset entry is set (the store's
  * needs_reset view, srlx_store_views) starts its next episode instead of stepping: state uniform in [-0.05, 0.05]^4 from (seed, lane, episode of the lane), its
  * first observation in d_obs, reward / terminated / done 0.  d_needs_reset NULL: every lane starts an episode (actions and scalar outputs may be NULL).
@@ -1140,6 +1158,14 @@ int srlx_mlpq_bind_noisy_grads(srlx_mlpq_t *h, float *const *d_grad_sigma);
 int srlx_mlpq_bind_noisy_adam(srlx_mlpq_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq);
 int srlx_mlpq_noisy_draw(srlx_mlpq_t *h, const int64_t *set_next, int64_t *next_out);
 int srlx_mlpq_noisy_eps(srlx_mlpq_t *h, int64_t draw, int param_index, float *d_out, void *stream);
+int srlx_mlpq_create_categorical(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int n_atoms, double v_min, double v_max,
+                                 int64_t max_rows, int64_t max_batch, int device);
+int srlx_mlpq_train_categorical(srlx_mlpq_t *h, int64_t batch, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions, const float *d_rewards,
+                                const float *d_terminated, double discount, const int64_t *d_steps_taken, float *d_q0, float *d_p0, float *d_m, float *d_loss,
+                                float *d_item_loss, void *stream);
+int srlx_c51_loss(int64_t batch, int n_actions, int n_atoms, double v_min, double v_max, double discount, const float *d_logits_next, const float *d_logits_0,
+                  const int32_t *d_actions, const float *d_rewards, const float *d_terminated, float *d_m, float *d_p0, float *d_grad_logits, float *d_loss,
+                  void *stream);
 int srlx_cartpole_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const int32_t *d_actions,
                        int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 

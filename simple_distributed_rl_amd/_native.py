@@ -247,6 +247,9 @@ SIGNATURES = {
     "srlx_mlpq_bind_noisy_adam": (c_int, [c_p, c_p, c_p]),
     "srlx_mlpq_noisy_draw": (c_int, [c_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "srlx_mlpq_noisy_eps": (c_int, [c_p, c_i64, c_int, c_p, c_p]),
+    "srlx_mlpq_create_categorical": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_p, c_int, c_int, c_f64, c_f64, c_i64, c_i64, c_int]),
+    "srlx_mlpq_train_categorical": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_c51_loss": (c_int, [c_i64, c_int, c_int, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_mlpq_train_nstep": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "srlx_cartpole_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
     "srlx_lstm_workspace_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_int]),

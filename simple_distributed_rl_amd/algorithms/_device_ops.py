@@ -1,4 +1,4 @@
-"""Device-side arithmetic shared by the DQN / Rainbow plugin trainers: thin wrappers that hand torch
+"""Device-side arithmetic shared by the DQN / Rainbow / C51 plugin trainers: thin wrappers that hand torch
 tensors to libsrlx.  A trainer on a non-GPU device fails loudly -- there is no CPU fallback."""
 import numpy as np
 import torch
@@ -97,6 +97,30 @@ class TdOps:
                                              N.tptr(grad), N.tptr(td), N.tptr(scratch), N.torch_stream_ptr()))
         self._keep4 = keep + [scratch]
         return target, loss, grad, td
+
+
+class C51Ops:
+    """C51's update arithmetic on logits torch produced (csrc/srlx_c51_math.h through srlx_c51_loss), as `TdOps.huber` serves DQN's."""
+
+    def __init__(self, device: torch.device):
+        self.dev = device
+        self.lib = N.lib()
+
+    def loss(self, logits_next, logits, actions, rewards, terminated, n_actions, n_atoms, v_min, v_max, discount):
+        """logits_next / logits: f32 [B][A * N] (or [B][A][N]) of s' and s.  Returns (m [B][N], p0 [B][N], grad of the mean loss w.r.t. `logits` in its
+        shape, loss [1])."""
+        B, d = logits.shape[0], self.dev
+        m = torch.empty((B, n_atoms), dtype=torch.float32, device=d)
+        p0 = torch.empty((B, n_atoms), dtype=torch.float32, device=d)
+        grad = torch.empty(tuple(logits.shape), dtype=torch.float32, device=d)
+        loss = torch.empty(1, dtype=torch.float32, device=d)
+        keep = [t.detach().contiguous() for t in (logits_next, logits, actions, rewards, terminated)]
+        assert keep[0].numel() == keep[1].numel() == B * n_actions * n_atoms and keep[2].dtype == torch.int32
+        N.check(self.lib.srlx_c51_loss(B, int(n_actions), int(n_atoms), float(v_min), float(v_max), float(discount), N.tptr(keep[0]), N.tptr(keep[1]),
+                                       N.tptr(keep[2]), N.tptr(keep[3]), N.tptr(keep[4]), N.tptr(m), N.tptr(p0), N.tptr(grad), N.tptr(loss),
+                                       N.torch_stream_ptr()))
+        self._keep = keep
+        return m, p0, grad, loss
 
 
 class NguOps:

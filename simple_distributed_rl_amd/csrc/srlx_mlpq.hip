@@ -22,16 +22,27 @@
 //   k_mlpq_noisy_eff        up to three draws in one launch (the learner: the online handle's s_1..s_n and s_0 draws and the target's)
 //   k_mlpq_learn_nstep_noisy<n>  k_mlpq_learn_nstep<n> with the online pass split: rows of s_0 under one draw, rows of s_1..s_n under the other
 //   k_mlpq_grad_adam_noisy  k_mlpq_grad_adam; for a noisy tensor the thread also writes g_sigma = g * eps and takes sigma's Adam step
+//
+// The categorical head (C51; srl/algorithms/c51/c51.py:23-42, :70-142) on a srlx_mlpq_create_categorical handle: a plain network whose out_layer has A * N rows,
+// row a * N + j = atom j of action a on the support linspace(v_min, v_max, N); the arithmetic is srlx_c51_math.h's, shared with the plugin trainer's kernel.
+//   k_mlpq_actor_c51  k_mlpq_actor with one thread per (row, action) turning the logit rows into expectations before the same selection
+//   k_mlpq_learn_c51  8 items per workgroup: ONE online pass over s_0 and s_1 (no target network), the item arithmetic on the logit rows in LDS, then
+//                     k_mlpq_learn_rows's backward chain seeded through the N out_layer rows of a_0; k_mlpq_grad_adam follows unchanged
+//   k_c51_loss        the same item arithmetic on logits torch produced (srlx_c51_loss), one workgroup walking the batch
 #include "srlx_adam_math.h"
+#include "srlx_c51_math.h"
 #include "srlx_common.h"
 #include "srlx_noise_math.h"
 #include "srlx_ppo_math.h"
 #include "srlx_td_math.h"
+#include <cmath>
 
 struct srlx_mlpq {
     int D, L, A, device;  // L: the Linear + ReLU layers in front of the head (plain: 1..3, then out_layer; dueling: the trunk, 0..2)
     int W[3];
-    int H, head;  // dueling: units of each branch; head 0 = out_layer, 1 = dueling "average", 2 = dueling ""
+    int H, head;  // dueling: units of each branch; head 0 = out_layer, 1 = dueling "average", 2 = dueling "", 3 = categorical (out_layer with A * atoms rows)
+    int atoms;    // categorical: atoms per action, on the support v_min..v_max
+    double v_min, v_max;
     int max_nstep;
     int64_t max_rows, max_batch;
     float *p[12];  // layer 0 weight, bias, ..., then out_layer weight, bias -- or v_layers.0, v_layers.2, adv_layers.0, adv_layers.2 (weight, bias each)
@@ -83,27 +94,31 @@ struct Net {  // (scalar fields and selects, no arrays: a kernel-argument array 
     __device__ const float *bias(int l) const { return l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3)); }
 };
 
+bool dueling(const srlx_mlpq *h) { return h->head == 1 || h->head == 2; }
+bool categorical(const srlx_mlpq *h) { return h->head == 3; }
+int out_cols(const srlx_mlpq *h) { return categorical(h) ? h->A * h->atoms : h->A; }  // rows of out_layer / of adv_layers.2
+
 // the tensors a pass reads: the bound ones, or for a noisy tensor the effective one of `set`
 const float *read_ptr(const srlx_mlpq *h, int i, int set) { return h->sig[i] ? h->eff[set][i] : h->p[i]; }
 
 Net net_of(const srlx_mlpq *h, int set = 0) {
     Net n;
-    n.D = h->D, n.L = h->L, n.A = h->A;
+    n.D = h->D, n.L = h->L, n.A = out_cols(h);  // (a categorical handle's network is a plain one whose out_layer has A * atoms rows)
     n.W0 = h->W[0], n.W1 = h->L > 1 ? h->W[1] : 0, n.W2 = h->L > 2 ? h->W[2] : 0;
     const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    const int plain_layers = h->head ? h->L : h->L + 1;
+    const int plain_layers = dueling(h) ? h->L : h->L + 1;
     for (int l = 0; l < plain_layers; l++) w[l] = read_ptr(h, 2 * l, set), b[l] = read_ptr(h, 2 * l + 1, set);
     n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
-    n.wout = h->head ? nullptr : w[h->L];
-    n.H = h->H, n.head = h->head;
+    n.wout = dueling(h) ? nullptr : w[h->L];
+    n.H = h->H, n.head = dueling(h) ? h->head : 0;
     const float *q[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (h->head)
+    if (dueling(h))
         for (int k = 0; k < 8; k++) q[k] = read_ptr(h, 2 * h->L + k, set);
     n.vw0 = q[0], n.vb0 = q[1], n.vw1 = q[2], n.vb1 = q[3], n.aw0 = q[4], n.ab0 = q[5], n.aw1 = q[6], n.ab1 = q[7];
     return n;
 }
 
-int n_params(const srlx_mlpq *h) { return h->head ? 2 * h->L + 8 : 2 * (h->L + 1); }
+int n_params(const srlx_mlpq *h) { return dueling(h) ? 2 * h->L + 8 : 2 * (h->L + 1); }
 
 int lds_stride(const srlx_mlpq *h) { return h->wmax + 1; }  // (odd: rows of different row groups fall on different banks)
 
@@ -239,8 +254,17 @@ __device__ __forceinline__ int select_action(const Policy &pol, i64 m, int A, co
 
 __device__ __forceinline__ const float *row_ptr(const float *base, const i64 *off, i64 row, int D) { return off ? base + off[row] : base + row * D; }
 
-__global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S, float *__restrict__ q,
-                                                         Policy pol, i64 *draw) {
+// the categorical head's shape behind a Net whose out_layer has A * N rows
+struct Cat {
+    int A, N;
+    double v_min, v_max;
+};
+
+// CAT: the rows forward_rows returns are logits [A][N]; one thread per (row, action) turns them into the expectations E[Z] (srlx_c51_math.h; c51.py:165-168),
+// which go where the Q rows go and into select_action unchanged.
+template <bool CAT>
+__device__ __forceinline__ void actor_body(const Net &n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S, float *__restrict__ q,
+                                           const Policy &pol, i64 *draw, const Cat &cat) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
     const int t = threadIdx.x;
@@ -253,9 +277,32 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, 
     }
     __syncthreads();
     const float *qs = forward_rows(n, rows, b0, b1, S, wl, nullptr, 0, 0, 0);
-    if (q)
-        for (int p = t; p < rows * n.A; p += kThreads) q[(r0 + p / n.A) * n.A + p % n.A] = qs[(p / n.A) * S + p % n.A];
-    if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.A, qs + t * S);
+    if constexpr (CAT) {
+        __shared__ float qe[kRows * srlxc::kMaxActions];
+        const int A = cat.A;
+        for (int p = t; p < rows * A; p += kThreads) {
+            const int r = p / A, c = p % A;
+            const float e = srlxc::expectation(qs + r * S + c * cat.N, cat.N, cat.v_min, cat.v_max);
+            qe[r * srlxc::kMaxActions + c] = e;
+            if (q) q[(r0 + r) * A + c] = e;
+        }
+        __syncthreads();
+        if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, A, qe + t * srlxc::kMaxActions);
+    } else {
+        if (q)
+            for (int p = t; p < rows * n.A; p += kThreads) q[(r0 + p / n.A) * n.A + p % n.A] = qs[(p / n.A) * S + p % n.A];
+        if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.A, qs + t * S);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_actor(Net n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S, float *__restrict__ q,
+                                                         Policy pol, i64 *draw) {
+    actor_body<false>(n, rows_total, obs, off, S, q, pol, draw, Cat{});
+}
+
+__global__ void __launch_bounds__(kThreads) k_mlpq_actor_c51(Net n, i64 rows_total, const float *__restrict__ obs, const i64 *__restrict__ off, int S,
+                                                             float *__restrict__ q, Policy pol, Cat cat) {
+    actor_body<true>(n, rows_total, obs, off, S, q, pol, nullptr, cat);
 }
 
 // srl/rl/functions.py:10-17 in float64 (one evaluation per item)
@@ -619,6 +666,86 @@ const void *learn_nstep_fn(int n) {
     }
 }
 
+// ---- the categorical learner step (C51 on flat observations) ------------------------------------------------------------------------------------------------
+struct LearnC {
+    const float *obs;
+    const i64 *off;  // [B][2]: element offsets of s_0 and s_1
+    float *x0, *h, *dh;
+    double *loss_rows;
+    int hstride;
+    srlxc::Items it;
+};
+
+// c51.py:70-142 for kItems sampled items per workgroup: ONE online pass over s_0 (rows 0..kItems-1, kept planes) and s_1 (rows kItems..) -- there is no target
+// network (:91) -- then srlx_c51_math.h:items_step on the logit rows where they lie in LDS, then k_mlpq_learn_rows's row-local backward chain, seeded through
+// the N rows of out_layer that belong to a_0.  The item arrays (next distribution, p_0 / seeds, m) take the weight tile's place: after the pass it is free.
+__global__ void __launch_bounds__(kThreads) k_mlpq_learn_c51(const Net *__restrict__ onp, LearnC a, int S) {
+    const Net &on = *onp;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *d0 = sm + 2 * kRows * S, *d1 = d0 + kItems * S, *wl = d1 + kItems * S;
+    static_assert(3 * kItems * srlxc::kMaxAtoms <= kWTile, "the item arrays live in the weight tile");
+    float *pn = wl, *seed = wl + kItems * srlxc::kMaxAtoms, *ms = wl + 2 * kItems * srlxc::kMaxAtoms;
+    __shared__ int act0[kItems];
+    __shared__ double row_loss[kItems];
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * kItems;
+    const int nb = (int)(a.it.B - i0 < kItems ? a.it.B - i0 : kItems);
+    const int D = on.D, L = on.L, N = a.it.N;
+    for (int p = t; p < kRows * D; p += kThreads) {  // (missing items: zero rows, never stored)
+        const int r = p / D, k = p % D, it = r % kItems, which = r / kItems;
+        const float x = it < nb ? a.obs[a.off[(i0 + it) * 2 + which] + k] : 0.f;
+        b0[r * S + k] = x;
+        if (which == 0 && it < nb) a.x0[(i0 + it) * D + k] = x;
+    }
+    __syncthreads();
+    const float *lg = forward_rows(on, kRows, b0, b1, S, wl, a.h, a.hstride, i0, nb);  // (returns behind a barrier: every read of the weight tile is done)
+    srlxc::items_step<kItems>(a.it, i0, nb, lg, lg + kItems * S, S, pn, seed, ms, act0, row_loss);
+    if (t < nb) a.loss_rows[i0 + t] = row_loss[t];
+    float *dcur = d0, *dnext = d1;
+    for (int l = L - 1; l >= 0; l--) {
+        const int Wl = on.width(l);
+        const float *hl = a.h + (i64)l * a.hstride;
+        float *dhl = a.dh + (i64)l * a.hstride;
+        for (int p = t; p < nb * Wl; p += kThreads) {
+            const int r = p / Wl, k = p % Wl;
+            float g = 0.f;
+            if (l == L - 1) {
+                const float *wa = on.wout + (i64)act0[r] * N * Wl + k, *sr = seed + r * srlxc::kMaxAtoms;
+#pragma unroll 8
+                for (int j = 0; j < N; j++) g = __builtin_fmaf(sr[j], wa[(i64)j * Wl], g);
+            } else {
+                const int Wn = on.width(l + 1);
+                const float *wn = on.weight(l + 1);
+#pragma unroll 8
+                for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
+            }
+            g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
+            dcur[r * S + k] = g;
+            dhl[(i0 + r) * Wl + k] = g;
+        }
+        __syncthreads();
+        float *tmp = dcur;
+        dcur = dnext, dnext = tmp;
+    }
+}
+
+// srlx_c51_loss: the same item arithmetic on logits torch produced, one workgroup walking the batch kItems items at a time; thread 0 reduces the row terms in
+// item order as k_mlpq_grad_adam does.
+__global__ void __launch_bounds__(kThreads) k_c51_loss(srlxc::Items a, const float *__restrict__ lg_next, const float *__restrict__ lg_0, float *__restrict__ loss) {
+    __shared__ float pn[kItems * srlxc::kMaxAtoms], seed[kItems * srlxc::kMaxAtoms], ms[kItems * srlxc::kMaxAtoms];
+    __shared__ int act0[kItems];
+    __shared__ double row_loss[kItems];
+    const i64 cols = (i64)a.A * a.N;
+    double s = 0.0;
+    for (i64 i0 = 0; i0 < a.B; i0 += kItems) {
+        const int nb = (int)(a.B - i0 < kItems ? a.B - i0 : kItems);
+        srlxc::items_step<kItems>(a, i0, nb, lg_0 + i0 * cols, lg_next + i0 * cols, cols, pn, seed, ms, act0, row_loss);
+        if (threadIdx.x == 0)
+            for (int r = 0; r < nb; r++) s += row_loss[r];
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)a.B);
+}
+
 struct GradAdam {
     i64 B;
     int nseg;
@@ -784,13 +911,13 @@ int layer_shapes(const srlx_mlpq *h, int *outs, int *ins) {
     const int last = h->L == 0 ? h->D : h->W[h->L - 1];
     int n = 0;
     for (int l = 0; l < h->L; l++) outs[n] = h->W[l], ins[n] = l == 0 ? h->D : h->W[l - 1], n++;
-    if (h->head) {
+    if (dueling(h)) {
         outs[n] = h->H, ins[n] = last, n++;
         outs[n] = 1, ins[n] = h->H, n++;
         outs[n] = h->H, ins[n] = last, n++;
         outs[n] = h->A, ins[n] = h->H, n++;
     } else {
-        outs[n] = h->A, ins[n] = last, n++;
+        outs[n] = out_cols(h), ins[n] = last, n++;
     }
     return n;
 }
@@ -860,7 +987,7 @@ bool same_noisy_layers(const srlx_mlpq *a, const srlx_mlpq *b) {
 extern "C" {
 
 static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int dueling_units, int head, int n_actions, int64_t max_rows,
-                          int64_t max_batch, int max_nstep, int device);
+                          int64_t max_batch, int max_nstep, int device, int n_atoms = 0, double v_min = 0.0, double v_max = 0.0);
 
 int srlx_mlpq_create(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int64_t max_rows, int64_t max_batch, int device) {
     SRLX_REQUIRE(out && widths, "mlpq_create: NULL argument");
@@ -894,16 +1021,37 @@ int srlx_mlpq_create_dueling(srlx_mlpq_t **out, int obs_dim, int n_trunk, const 
     return create_checked(out, obs_dim, n_trunk, trunk_widths, dueling_units, dueling_type + 1, n_actions, max_rows, max_batch, max_nstep, device);
 }
 
+int srlx_mlpq_create_categorical(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int n_actions, int n_atoms, double v_min, double v_max,
+                                 int64_t max_rows, int64_t max_batch, int device) {
+    SRLX_REQUIRE(out && widths, "mlpq_create_categorical: NULL argument");
+    *out = nullptr;
+    SRLX_REQUIRE(obs_dim >= 1 && obs_dim <= 256, "mlpq_create_categorical: %d observation elements (covered: 1..256)", obs_dim);
+    SRLX_REQUIRE(n_layers >= 1 && n_layers <= 3, "mlpq_create_categorical: %d dense layers (covered: 1..3)", n_layers);
+    for (int l = 0; l < n_layers; l++)
+        SRLX_REQUIRE(widths[l] >= 32 && widths[l] <= 512 && widths[l] % 32 == 0, "mlpq_create_categorical: layer width %d (covered: 32..512, multiples of 32)",
+                     widths[l]);
+    SRLX_REQUIRE(n_actions >= 2 && n_actions <= srlxc::kMaxActions, "mlpq_create_categorical: %d actions (covered: 2..32)", n_actions);
+    SRLX_REQUIRE(n_atoms >= 2 && n_atoms <= srlxc::kMaxAtoms, "mlpq_create_categorical: %d atoms (covered: 2..256)", n_atoms);
+    SRLX_REQUIRE(n_actions * n_atoms <= 512, "mlpq_create_categorical: %d actions x %d atoms = %d out_layer rows (covered: <= 512)", n_actions, n_atoms,
+                 n_actions * n_atoms);
+    SRLX_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max, "mlpq_create_categorical: support %g..%g (v_min < v_max, both finite)", v_min, v_max);
+    SRLX_REQUIRE(max_rows >= 1 && max_batch >= 0 && max_batch <= 256, "mlpq_create_categorical: max_rows %lld, max_batch %lld (learner batches <= 256)",
+                 (long long)max_rows, (long long)max_batch);
+    return create_checked(out, obs_dim, n_layers, widths, 0, 3, n_actions, max_rows, max_batch, 1, device, n_atoms, v_min, v_max);
+}
+
 // (the arguments are inside the envelope; no device call has been made yet)
 static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const int *widths, int dueling_units, int head, int n_actions, int64_t max_rows,
-                          int64_t max_batch, int max_nstep, int device) {
+                          int64_t max_batch, int max_nstep, int device, int n_atoms, double v_min, double v_max) {
     srlx::DeviceGuard g(device);
     SRLX_REQUIRE(g.ok, "mlpq_create: device %d unavailable", device);
     srlx_mlpq *h = new srlx_mlpq();
     h->D = obs_dim, h->L = n_layers, h->A = n_actions, h->device = device;
     h->H = dueling_units, h->head = head, h->max_nstep = max_nstep;
     h->max_rows = max_rows, h->max_batch = max_batch;
-    h->wmax = obs_dim > n_actions ? obs_dim : n_actions;
+    h->atoms = n_atoms, h->v_min = v_min, h->v_max = v_max;
+    const int cols = out_cols(h);  // (categorical: the logit rows are A * atoms wide, in LDS and in the out_layer's gradient seeds)
+    h->wmax = obs_dim > cols ? obs_dim : cols;
     if (dueling_units > h->wmax) h->wmax = dueling_units;
     for (int l = 0; l < n_layers; l++) {
         h->W[l] = widths[l];
@@ -911,14 +1059,14 @@ static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const in
     }
     if (max_batch > 0) {
         const size_t plane = (size_t)max_batch * h->wmax;
-        const size_t planes = head ? n_layers + 2 : 3;  // (dueling: the trunk's, then the value and the advantage branch's hidden rows)
+        const size_t planes = dueling(h) ? n_layers + 2 : 3;  // (dueling: the trunk's, then the value and the advantage branch's hidden rows)
         hipError_t e = hipMalloc((void **)&h->x0, sizeof(float) * max_batch * obs_dim);
         if (e == hipSuccess) e = hipMalloc((void **)&h->h, sizeof(float) * planes * plane);
         if (e == hipSuccess) e = hipMalloc((void **)&h->dh, sizeof(float) * planes * plane);
-        if (e == hipSuccess && head) e = hipMalloc((void **)&h->grad_v, sizeof(float) * max_batch);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->q_on_next, sizeof(float) * max_batch * n_actions);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->q_tg_next, sizeof(float) * max_batch * n_actions);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->grad_q, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess && dueling(h)) e = hipMalloc((void **)&h->grad_v, sizeof(float) * max_batch);
+        if (e == hipSuccess && !categorical(h)) e = hipMalloc((void **)&h->q_on_next, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess && !categorical(h)) e = hipMalloc((void **)&h->q_tg_next, sizeof(float) * max_batch * n_actions);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->grad_q, sizeof(float) * max_batch * cols);
         if (e == hipSuccess) e = hipMalloc((void **)&h->loss_rows, sizeof(double) * max_batch);
         if (e != hipSuccess) {
             srlx_mlpq_destroy(h);
@@ -928,9 +1076,11 @@ static int create_checked(srlx_mlpq_t **out, int obs_dim, int n_layers, const in
     }
     const int S = lds_stride(h);
     int st = set_lds((const void *)k_mlpq_actor, sizeof(float) * (2 * kRows * S + kWTile));
+    if (st == SRLX_OK && categorical(h)) st = set_lds((const void *)k_mlpq_actor_c51, sizeof(float) * (2 * kRows * S + kWTile));
+    if (st == SRLX_OK && categorical(h)) st = set_lds((const void *)k_mlpq_learn_c51, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     if (st == SRLX_OK) st = set_lds((const void *)k_mlpq_learn_rows, sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     for (int n = 1; n <= kMaxNstep && st == SRLX_OK; n++) st = set_lds(learn_nstep_fn(n), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
-    for (int n = 1; n <= kMaxNstep && st == SRLX_OK && head; n++)
+    for (int n = 1; n <= kMaxNstep && st == SRLX_OK && dueling(h); n++)
         st = set_lds(learn_nstep_noisy_fn(n), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile));
     if (st != SRLX_OK) {
         srlx_mlpq_destroy(h);
@@ -966,6 +1116,7 @@ int srlx_mlpq_bind(srlx_mlpq_t *h, float *const *d_params) {
 
 int srlx_mlpq_bind_noisy(srlx_mlpq_t *h, float *const *d_sigma, uint64_t seed) {
     SRLX_REQUIRE(h && d_sigma, "mlpq_bind_noisy: NULL argument");
+    SRLX_REQUIRE(!categorical(h), "mlpq_bind_noisy: a categorical handle has no NoisyLinear form (c51.py builds plain Dense layers)");
     SRLX_REQUIRE(h->head, "mlpq_bind_noisy: a plain (out_layer) handle has no NoisyLinear form; noisy layers belong to srlx_mlpq_create_dueling handles");
     SRLX_REQUIRE(h->bound, "mlpq_bind_noisy: bind the parameters first (srlx_mlpq_bind: a noisy layer's entries are its mu tensors)");
     const int np = n_params(h);
@@ -1075,8 +1226,12 @@ int srlx_mlpq_forward(srlx_mlpq_t *h, int64_t rows, const float *d_obs, const in
         ea.job[0] = eff_job(h, 0, 0);
         launch_eff(ea, 1, (hipStream_t)stream);
     }
-    hipLaunchKernelGGL(k_mlpq_actor, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(kThreads), sizeof(float) * (2 * kRows * S + kWTile), (hipStream_t)stream, net_of(h),
-                       (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol, h->noisy ? (i64 *)h->d_draw : (i64 *)nullptr);
+    if (categorical(h))
+        hipLaunchKernelGGL(k_mlpq_actor_c51, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(kThreads), sizeof(float) * (2 * kRows * S + kWTile), (hipStream_t)stream,
+                           net_of(h), (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol, Cat{h->A, h->atoms, h->v_min, h->v_max});
+    else
+        hipLaunchKernelGGL(k_mlpq_actor, dim3((unsigned)((rows + kRows - 1) / kRows)), dim3(kThreads), sizeof(float) * (2 * kRows * S + kWTile), (hipStream_t)stream,
+                           net_of(h), (i64)rows, d_obs, (const i64 *)d_row_offsets, S, d_q, pol, h->noisy ? (i64 *)h->d_draw : (i64 *)nullptr);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
@@ -1085,6 +1240,7 @@ int srlx_mlpq_train_step(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t batc
                          const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, int double_dqn, int rescale,
                          const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
     SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_step: unbound handle");
+    SRLX_REQUIRE(!categorical(h) && !categorical(target), "mlpq_train_step: a categorical handle trains through srlx_mlpq_train_categorical");
     SRLX_REQUIRE(!h->noisy && !target->noisy, "mlpq_train_step: a noisy handle trains through srlx_mlpq_train_nstep");
     SRLX_REQUIRE(!h->head && !target->head, "mlpq_train_step: a dueling handle trains through srlx_mlpq_train_nstep");
     SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A, "mlpq_train_step: online and target shapes differ");
@@ -1138,6 +1294,7 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
                           const int32_t *d_actions, const float *d_rewards, const float *d_terminated, const float *d_weights, double discount, double retrace_h,
                           int double_dqn, int rescale, const int64_t *d_steps_taken, float *d_q0, float *d_target, float *d_loss, float *d_priorities, void *stream) {
     SRLX_REQUIRE(h && target && h->bound && target->bound, "mlpq_train_nstep: unbound handle");
+    SRLX_REQUIRE(!categorical(h) && !categorical(target), "mlpq_train_nstep: a categorical handle trains through srlx_mlpq_train_categorical");
     SRLX_REQUIRE(h->D == target->D && h->L == target->L && h->A == target->A && h->head == target->head && h->H == target->H,
                  "mlpq_train_nstep: online and target shapes differ");
     for (int l = 0; l < h->L; l++) SRLX_REQUIRE(h->W[l] == target->W[l], "mlpq_train_nstep: online and target layer widths differ");
@@ -1194,7 +1351,7 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
         const float *dout, *xin;
         if (l < h->L) {
             dout = h->dh + l * plane, xin = l == 0 ? h->x0 : h->h + (l - 1) * plane;
-        } else if (!h->head) {
+        } else if (!dueling(h)) {
             dout = h->grad_q, xin = trunk_out;
         } else {
             const int k = l - h->L;  // v_layers.0, v_layers.2, adv_layers.0, adv_layers.2
@@ -1224,9 +1381,75 @@ int srlx_mlpq_train_nstep(srlx_mlpq_t *h, const srlx_mlpq_t *target, int64_t bat
     return SRLX_OK;
 }
 
+int srlx_mlpq_train_categorical(srlx_mlpq_t *h, int64_t batch, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions, const float *d_rewards,
+                                const float *d_terminated, double discount, const int64_t *d_steps_taken, float *d_q0, float *d_p0, float *d_m, float *d_loss,
+                                float *d_item_loss, void *stream) {
+    SRLX_REQUIRE(h && h->bound, "mlpq_train_categorical: unbound handle");
+    SRLX_REQUIRE(categorical(h), "mlpq_train_categorical: not a categorical handle (srlx_mlpq_create_categorical); a %s handle trains through %s",
+                 dueling(h) ? "dueling" : "plain", dueling(h) ? "srlx_mlpq_train_nstep" : "srlx_mlpq_train_step");
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "mlpq_train_categorical: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_obs_base && d_offsets && d_actions && d_rewards && d_terminated && d_q0 && d_p0 && d_m && d_loss && d_item_loss,
+                 "mlpq_train_categorical: NULL argument");
+    SRLX_REQUIRE(std::isfinite(discount), "mlpq_train_categorical: discount %g", discount);
+    SRLX_REQUIRE(!h->adam || d_steps_taken, "mlpq_train_categorical: Adam needs the step count");
+    bool any_grad = false;
+    for (int i = 0; i < n_params(h); i++) any_grad |= h->grads[i] != nullptr;
+    SRLX_REQUIRE(h->adam || any_grad, "mlpq_train_categorical: neither gradients nor Adam bound");
+    srlx::DeviceGuard g(h->device);
+    const int S = lds_stride(h);
+    LearnC a{};
+    a.obs = d_obs_base, a.off = (const i64 *)d_offsets;
+    a.x0 = h->x0, a.h = h->h, a.dh = h->dh, a.loss_rows = h->loss_rows;
+    a.hstride = (int)(h->max_batch * h->wmax);
+    srlxc::Items &it = a.it;
+    it.B = batch, it.A = h->A, it.N = h->atoms, it.v_min = h->v_min, it.v_max = h->v_max, it.discount = discount;
+    it.actions = d_actions, it.rewards = d_rewards, it.terminated = d_terminated;
+    it.q0 = d_q0, it.p0 = d_p0, it.m = d_m, it.grad = h->grad_q, it.item_loss = d_item_loss;
+    hipLaunchKernelGGL(k_mlpq_learn_c51, dim3((unsigned)((batch + kItems - 1) / kItems)), dim3(kThreads), sizeof(float) * ((2 * kRows + 2 * kItems) * S + kWTile),
+                       (hipStream_t)stream, (const Net *)h->d_net, a, S);
+    GradAdam ga = segments(h);  // (the out_layer segment has seg_out = A * atoms)
+    ga.B = batch;
+    const i64 plane = h->max_batch * h->wmax;
+    for (int l = 0; l <= h->L; l++) {
+        const float *dout = l < h->L ? h->dh + l * plane : h->grad_q;
+        const float *xin = l == 0 ? h->x0 : h->h + (l - 1) * plane;
+        for (int k = 0; k < 2; k++) {
+            const int s = 2 * l + k;
+            ga.dout[s] = dout, ga.xin[s] = xin;
+            ga.p[s] = h->p[s], ga.g[s] = h->grads[s], ga.m[s] = h->m[s], ga.v[s] = h->v[s];
+        }
+    }
+    ga.adam = h->adam ? 1 : 0;
+    ga.lr = h->lr, ga.beta1 = h->beta1, ga.beta2 = h->beta2, ga.eps = h->eps;
+    ga.steps_taken = (const i64 *)d_steps_taken;
+    ga.loss_rows = h->loss_rows, ga.loss = d_loss;
+    const i64 total = ga.seg_end[ga.nseg - 1];
+    hipLaunchKernelGGL(k_mlpq_grad_adam, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, ga);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_c51_loss(int64_t batch, int n_actions, int n_atoms, double v_min, double v_max, double discount, const float *d_logits_next, const float *d_logits_0,
+                  const int32_t *d_actions, const float *d_rewards, const float *d_terminated, float *d_m, float *d_p0, float *d_grad_logits, float *d_loss,
+                  void *stream) {
+    SRLX_REQUIRE(batch >= 1, "c51_loss: batch %lld", (long long)batch);
+    SRLX_REQUIRE(n_actions >= 1 && n_actions <= srlxc::kMaxActions, "c51_loss: %d actions (covered: 1..32)", n_actions);
+    SRLX_REQUIRE(n_atoms >= 2 && n_atoms <= srlxc::kMaxAtoms, "c51_loss: %d atoms (covered: 2..256)", n_atoms);
+    SRLX_REQUIRE(std::isfinite(v_min) && std::isfinite(v_max) && v_min < v_max && std::isfinite(discount), "c51_loss: support %g..%g, discount %g", v_min, v_max, discount);
+    SRLX_REQUIRE(d_logits_next && d_logits_0 && d_actions && d_rewards && d_terminated && d_m && d_p0 && d_grad_logits && d_loss, "c51_loss: NULL argument");
+    srlxc::Items it{};
+    it.B = batch, it.A = n_actions, it.N = n_atoms, it.v_min = v_min, it.v_max = v_max, it.discount = discount;
+    it.actions = d_actions, it.rewards = d_rewards, it.terminated = d_terminated;
+    it.q0 = nullptr, it.p0 = d_p0, it.m = d_m, it.grad = d_grad_logits, it.item_loss = nullptr;
+    hipLaunchKernelGGL(k_c51_loss, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, it, d_logits_next, d_logits_0, d_loss);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
 int srlx_mlpq_publish(const srlx_mlpq_t *src, srlx_mlpq_t *dst, void *stream) {
     SRLX_REQUIRE(src && dst && src->bound && dst->bound, "mlpq_publish: unbound handle");
-    SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A && src->head == dst->head && src->H == dst->H, "mlpq_publish: shapes differ");
+    SRLX_REQUIRE(src->D == dst->D && src->L == dst->L && src->A == dst->A && src->head == dst->head && src->H == dst->H && src->atoms == dst->atoms,
+                 "mlpq_publish: shapes differ");
     for (int l = 0; l < src->L; l++) SRLX_REQUIRE(src->W[l] == dst->W[l], "mlpq_publish: shapes differ");
     SRLX_REQUIRE(src->noisy == dst->noisy && (!src->noisy || same_noisy_layers(src, dst)),
                  "mlpq_publish: a noisy source needs a noisy destination with the same noisy layers, a plain one a plain destination");

@@ -9,6 +9,8 @@ Reference semantics kept (file:line under the reference root):
   srl/algorithms/rainbow/rainbow.py:185-287    the n-step retrace target                              -> srlx_mlpq_train_nstep
   srl/rl/torch_/modules/noisy_linear.py:8-52   NoisyLinear (enable_noisy_dense: the hidden block's MLP layers and the head) -> EngineMLPQNet(noisy=True),
                                                srlx_mlpq_bind_noisy; rainbow.py:305-309: a noisy net acts greedily          -> VectorQEngine.eps = 0
+  srl/algorithms/c51/c51.py:23-42              in_block -> hidden_block (MLP) -> Dense(A * N) reshaped to [A][N]           -> EngineMLPQNet(n_atoms=N)
+  srl/algorithms/c51/c51.py:70-142             the categorical update on the online network alone (no target network)      -> srlx_mlpq_train_categorical
 The replay is the engine's `DeviceReplay` with float32 observations, window 1 and `multisteps`-step items.
 """
 import ctypes
@@ -36,11 +38,16 @@ class EngineMLPQNet(nn.Module):
 
     `noisy` (Rainbow's enable_noisy_dense; dueling nets only): the `hidden_sizes` layers and the four head layers are NoisyLinear (`w_mu / w_sigma / b_mu /
     b_sigma`, the reference's initialisation and keys, fresh torch.randn noise on every forward); the `in_sizes` layers stay nn.Linear
-    (rainbow/model_torch.py:19-24: the input value block takes no noisy flag)."""
+    (rainbow/model_torch.py:19-24: the input value block takes no noisy flag).
+
+    `n_atoms` = N > 0 is C51's tree (algorithms/c51.py:build_network): `out_layer` is Linear(., A * N), row a * N + j = atom j of action a on the support
+    linspace(v_min, v_max, N).  `forward` returns the expectations [rows][A], `dist` the probabilities [rows][A][N]."""
 
     def __init__(self, obs_dim: int, in_sizes: Sequence[int], hidden_sizes: Sequence[int], n_actions: int, dueling_units: int = 0,
-                 dueling_type: str = "average", noisy: bool = False):
+                 dueling_type: str = "average", noisy: bool = False, n_atoms: int = 0, v_min: float = -10.0, v_max: float = 10.0):
         super().__init__()
+        self.n_atoms, self.v_min, self.v_max = int(n_atoms), float(v_min), float(v_max)
+        assert not self.n_atoms or not (dueling_units or noisy), "the categorical head is a plain out_layer (c51.py:29-32)"
         self.noisy = bool(noisy)
         assert not self.noisy or dueling_units, "noisy layers belong to the dueling (Rainbow) network"
         lin = NoisyLinear if self.noisy else nn.Linear
@@ -64,7 +71,9 @@ class EngineMLPQNet(nn.Module):
             head = f"hidden_block.hidden_layers.{2 * len(self.hidden_sizes)}"  # the DuelingNetworkBlock: v_layers / adv_layers = [Linear, ReLU, Linear]
             self._keys += [head + ".v_layers.0", head + ".v_layers.2", head + ".adv_layers.0", head + ".adv_layers.2"]
         else:
-            self.out_layer = nn.Linear(prev, self.n_actions)
+            self.out_layer = nn.Linear(prev, self.n_actions * max(self.n_atoms, 1))
+            if self.n_atoms:  # (float32(linspace in float64): what the expectation multiplies by, c51.py:93)
+                self.register_buffer("support", torch.linspace(self.v_min, self.v_max, self.n_atoms, dtype=torch.float64).to(torch.float32), persistent=False)
             self._keys.append("out_layer")
         self.weights_version = 0
 
@@ -73,6 +82,8 @@ class EngineMLPQNet(nn.Module):
         return self.in_sizes + self.hidden_sizes
 
     def forward(self, x):
+        if self.n_atoms:  # the expectations over the support (c51.py:93)
+            return (self.dist(x) * self.support).sum(-1)
         x = x.reshape(x.shape[0], -1)
         for layer in self.layers:
             x = F.relu(layer(x))
@@ -82,6 +93,17 @@ class EngineMLPQNet(nn.Module):
         if self.dueling_type == "average":
             return v + adv - torch.mean(adv, dim=-1, keepdim=True)
         return v + adv
+
+    def logits(self, x):
+        """[rows][A][N] logits of the categorical head."""
+        x = x.reshape(x.shape[0], -1)
+        for layer in self.layers:
+            x = F.relu(layer(x))
+        return self.out_layer(x).view(-1, self.n_actions, self.n_atoms)
+
+    def dist(self, x):
+        """[rows][A][N] probabilities over the atoms (c51.py:92)."""
+        return torch.softmax(self.logits(x), dim=2)
 
     def _linears(self):
         if self.dueling_units:
@@ -130,7 +152,8 @@ class MLPQHandle:
     """One libsrlx handle over an EngineMLPQNet's parameters (zero copy).  `max_batch` > 0: the handle trains -- gradient tensors (`p.grad`) and, with `lr`,
     torch's Adam state are bound, and `train_step` / `train_nstep` run the whole update in two launches.  A dueling net gets a srlx_mlpq_create_dueling handle
     (`max_nstep`: the longest item its `train_nstep` takes).  A noisy net's sigma tensors, their gradients and Adam state are bound beside the mu tensors'
-    (srlx_mlpq_bind_noisy, `noise_seed`: the key of the handle's noise stream; srlx.h: the draw-id contract)."""
+    (srlx_mlpq_bind_noisy, `noise_seed`: the key of the handle's noise stream; srlx.h: the draw-id contract).  A net with `n_atoms` gets a
+    srlx_mlpq_create_categorical handle: `forward` writes expectations and `train_categorical` is its update."""
 
     def __init__(self, net: EngineMLPQNet, max_rows: int, device: int = 0, max_batch: int = 0, lr: Optional[float] = None, betas=(0.9, 0.999),
                  eps: float = 1e-8, write_grads: bool = True, max_nstep: int = 7, noise_seed: int = 0):
@@ -138,7 +161,10 @@ class MLPQHandle:
         self.net = net
         widths = (ctypes.c_int * 3)(*(list(net.widths) + [0, 0, 0])[:3])
         h = N.c_p()
-        if net.dueling_units:
+        if getattr(net, "n_atoms", 0):
+            N.check(self.lib.srlx_mlpq_create_categorical(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.n_actions, net.n_atoms,
+                                                          float(net.v_min), float(net.v_max), int(max_rows), int(max_batch), int(device)))
+        elif net.dueling_units:
             N.check(self.lib.srlx_mlpq_create_dueling(ctypes.byref(h), net.obs_dim, len(net.widths), ctypes.cast(widths, N.c_p), net.dueling_units,
                                                       DUELING_TYPES[net.dueling_type], net.n_actions, int(max_rows), int(max_batch), int(max_nstep), int(device)))
         else:
@@ -231,6 +257,12 @@ class MLPQHandle:
                                                N.tptr(terminated), N.tptr(weights), float(discount), float(retrace_h), int(bool(double_dqn)), int(bool(rescale)),
                                                N.tptr(steps_taken), N.tptr(q0), N.tptr(target_out), N.tptr(loss), N.tptr(priorities), N.torch_stream_ptr()))
 
+    def train_categorical(self, batch: int, obs_base: int, offsets, actions, rewards, terminated, discount: float, steps_taken, q0, p0, m, loss, item_loss):
+        """One C51 update (c51.py:70-142): offsets int64 [B][2], actions / rewards / terminated [B]; q0 [B][A] expectations, p0 / m [B][N], item_loss [B]."""
+        N.check(self.lib.srlx_mlpq_train_categorical(self.h, int(batch), N.c_p(obs_base), N.tptr(offsets), N.tptr(actions), N.tptr(rewards), N.tptr(terminated),
+                                                     float(discount), N.tptr(steps_taken), N.tptr(q0), N.tptr(p0), N.tptr(m), N.tptr(loss), N.tptr(item_loss),
+                                                     N.torch_stream_ptr()))
+
     def publish_to(self, dst: "MLPQHandle"):
         """Every parameter of this handle's network into `dst`'s (one launch, on the current stream)."""
         N.check(self.lib.srlx_mlpq_publish(self.h, dst.h, N.torch_stream_ptr()))
@@ -301,6 +333,11 @@ class VectorQConfig:
     retrace_h: float = 1.0
     # rainbow.Config.enable_noisy_dense (rainbow.py:46): NoisyLinear in the hidden block's MLP layers and the dueling head, greedy acting (needs dueling_units)
     enable_noisy_dense: bool = False
+    # --- c51.Config (srl/algorithms/c51/config.py:50-52): categorical_atoms = N > 0 turns out_layer into the [A][N] categorical head on the support
+    # linspace(v_min, v_max, N); the update is c51.py:70-142 on the online network alone (no target network, no dueling head, 1-step items, plain layers)
+    categorical_atoms: int = 0
+    categorical_v_min: float = -10.0
+    categorical_v_max: float = 10.0
     # --- engine
     n_envs: int = 1024
     seed: int = 0
@@ -314,7 +351,9 @@ class VectorQEngine:
       learner_step  the replay's draw + gather, srlx_mlpq_train_step (or srlx_mlpq_train_nstep; 2 launches), the priority write-back (train_count += 1 on the device)
     Actors and learner share one stream and one parameter set (no copy to refresh).  With `enable_noisy_dense` both networks hold NoisyLinear layers: every pass
     costs one more launch (the draw's effective tensors; the learner's three draws share one), the draw ids live on the device, so the captured update replays
-    with fresh noise, and every lane acts greedily on its noisy Q row (`eps` = 0)."""
+    with fresh noise, and every lane acts greedily on its noisy Q row (`eps` = 0).  With `categorical_atoms` the engine is C51's: the actors' launch turns
+    the logit rows into expectations before the same selection, the update is srlx_mlpq_train_categorical (2 launches), and there is no target network --
+    `q_target` / `inf_target` are None and `sync` stays 0."""
 
     overlap = False
 
@@ -325,6 +364,10 @@ class VectorQEngine:
         torch.manual_seed(cfg.seed)
         E, B, A, D = cfg.n_envs, cfg.batch_size, cfg.n_actions, cfg.obs_dim
         n = int(cfg.multisteps)
+        self.categorical = int(cfg.categorical_atoms) > 0
+        assert not self.categorical or not cfg.dueling_units, "categorical_atoms: C51's head is a plain out_layer (c51.py:29-32); dueling_units must be 0"
+        assert not self.categorical or n == 1, "categorical_atoms: C51's target is the 1-step distributional Bellman update (c51.py:102-121); multisteps must be 1"
+        assert not self.categorical or not cfg.enable_noisy_dense, "categorical_atoms: C51 builds plain Dense layers; enable_noisy_dense must be False"
         self.nstep = n > 1 or cfg.dueling_units > 0  # srlx_mlpq_train_nstep; the defaults keep srlx_mlpq_train_step
         ring_len = -(-cfg.memory_capacity // E) + n + 1  # item_len * E >= capacity (n_step n + window 1)
         self.replay = DeviceReplay(E, ring_len, D, 1, n, A, B, False, cfg.enable_reward_clip, cfg.memory_alpha, cfg.memory_beta_initial, cfg.memory_beta_steps,
@@ -337,13 +380,17 @@ class VectorQEngine:
             self.env = env(self.replay) if callable(env) else env
         noisy = bool(cfg.enable_noisy_dense)
         assert not noisy or cfg.dueling_units > 0, "enable_noisy_dense needs the dueling head (dueling_units > 0)"
-        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy).to(self.dev)
-        self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy).to(self.dev)
-        self.q_target.load_state_dict(self.q_online.state_dict())
+        cat = dict(n_atoms=int(cfg.categorical_atoms), v_min=cfg.categorical_v_min, v_max=cfg.categorical_v_max) if self.categorical else {}
+        self.q_online = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy, **cat).to(self.dev)
         self.q_actor = self.q_online
         # (the two networks' noise streams are independent: the target pass has its own layers, model_torch.py:103)
         self.inf_online = MLPQHandle(self.q_online, max(E, B), device, max_batch=B, lr=cfg.lr, max_nstep=n, noise_seed=cfg.seed ^ 0x6E6F6973)
-        self.inf_target = MLPQHandle(self.q_target, max(E, B), device, max_nstep=n, noise_seed=cfg.seed ^ 0x74677473)
+        if self.categorical:  # c51.py:91 evaluates s' with the online network: there is no target network to keep or to sync
+            self.q_target = self.inf_target = None
+        else:
+            self.q_target = EngineMLPQNet(D, cfg.in_sizes, cfg.hidden_sizes, A, cfg.dueling_units, cfg.dueling_type, noisy).to(self.dev)
+            self.q_target.load_state_dict(self.q_online.state_dict())
+            self.inf_target = MLPQHandle(self.q_target, max(E, B), device, max_nstep=n, noise_seed=cfg.seed ^ 0x74677473)
         d = self.dev
         self.eps = torch.full((E,), 0.0 if noisy else float(cfg.epsilon), dtype=torch.float32, device=d)  # rainbow.py:305-309: no epsilon for a noisy net
         self.actions = torch.zeros(E, dtype=torch.int32, device=d)
@@ -353,7 +400,10 @@ class VectorQEngine:
         self.q0 = torch.zeros((B, A), dtype=torch.float32, device=d)
         self.target = torch.zeros(B, dtype=torch.float32, device=d)
         self.loss = torch.zeros(1, dtype=torch.float32, device=d)
-        self.priorities = torch.zeros(B, dtype=torch.float32, device=d)
+        self.priorities = torch.zeros(B, dtype=torch.float32, device=d)  # (categorical: the items' cross-entropies stand here; alpha = 0 ignores the values)
+        if self.categorical:
+            self.p0 = torch.zeros((B, cat["n_atoms"]), dtype=torch.float32, device=d)
+            self.m = torch.zeros((B, cat["n_atoms"]), dtype=torch.float32, device=d)
         self.train_count = self.sync_count = self.total_env_steps = 0
         self.ledger = None
         self._learner_graph = None
@@ -388,7 +438,10 @@ class VectorQEngine:
     def _learner_body(self):
         cfg, r = self.cfg, self.replay
         b = r.sample_items(self.train_count_dev, all_states=True)
-        if self.nstep:
+        if self.categorical:
+            self.inf_online.train_categorical(cfg.batch_size, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, cfg.discount, self.train_count_dev,
+                                              self.q0, self.p0, self.m, self.loss, self.priorities)
+        elif self.nstep:
             self.inf_online.train_nstep(self.inf_target, cfg.batch_size, cfg.multisteps, r.obs_base, r.frame_off_all, b.actions, b.rewards, b.terminated, b.weights,
                                         cfg.discount, cfg.retrace_h, cfg.enable_double_dqn, cfg.enable_rescale, self.train_count_dev, self.q0, self.target,
                                         self.loss, self.priorities)
@@ -404,7 +457,7 @@ class VectorQEngine:
             self._learner_graph.replay()
         else:
             self._learner_body()
-        if self.train_count % self.cfg.target_model_update_interval == 0:  # model_torch.py:125-127 (fires at 0 too)
+        if not self.categorical and self.train_count % self.cfg.target_model_update_interval == 0:  # model_torch.py:125-127 (fires at 0 too)
             self.sync_target()
         self.train_count += 1
         return True

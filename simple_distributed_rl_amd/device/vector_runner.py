@@ -233,6 +233,8 @@ def why_not_vector(context, env, rl_config) -> str:
         return f"no device engine for algorithm '{rl_config.get_name()}'"
     if kind == "agent57":  # the LSTM engine has its own envelope (device/agent57.py)
         return why_not_agent57_engine(env, rl_config)
+    if kind == "c51":  # the categorical head of the MLP Q-network (device/mlpq.py)
+        return why_not_c51_engine(env, rl_config)
     if env.player_num != 1:
         return "multi-player environment"
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
@@ -417,9 +419,11 @@ def why_not_flat_rainbow(env, rl_config, admit_noisy: bool = False) -> str:
 
 
 def auto_lanes_reason(env, rl_config, n_envs) -> str:
-    """Flat-observation DQN and Agent57 engage the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
+    """Flat-observation DQN, C51 and Agent57 engage the device engine only for an explicit set_vector_envs(n): "AUTO" keeps today's plugin path."""
     if engine_kind(rl_config) == "agent57" and isinstance(n_envs, str):
         return "Agent57 stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
+    if engine_kind(rl_config) == "c51" and isinstance(n_envs, str):
+        return "C51 stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
     if is_flat_dqn(env, rl_config) and isinstance(n_envs, str):
         return "flat-observation DQN stays on the plugin path under set_vector_envs(\"AUTO\"); set_vector_envs(n) with n > 0 engages the device engine"
     return ""
@@ -579,7 +583,85 @@ def ppo_config_from(rl_config, env, n_envs: int, seed: int, horizon: int = 32, e
 
 def engine_kind(rl_config) -> Optional[str]:
     """Which device engine serves this algorithm config (None = the plugin classes only)."""
-    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light", "DQN": "dqn", "Agent57": "agent57"}.get(rl_config.get_name())
+    return {"Rainbow": "rainbow", "Rainbow_no_multisteps": "rainbow", "Agent57_light": "agent57_light", "DQN": "dqn", "Agent57": "agent57",
+            "C51": "c51"}.get(rl_config.get_name())
+
+
+C51_MP_REASON = "C51 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
+
+
+def why_not_c51_engine(env, rl_config) -> str:
+    """Empty string when `VectorQEngine` (device/mlpq.py) can run this c51.Config on this environment -- `c51_config_from` maps it; otherwise EVERY reason it
+    cannot, joined with "; " (as `why_not_ppo_engine`).  The envelope figures are srlx_mlpq_create_categorical's (srlx.h)."""
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+
+    c, why = rl_config, []
+    if c.get_name() != "C51":
+        return f"'{c.get_name()}' is not a c51.Config"
+    if env.player_num != 1:
+        why.append("multi-player environment")
+    discrete = isinstance(env.action_space, DiscreteSpace)
+    A = int(env.action_space.n) if discrete else 0
+    if not discrete or not 2 <= A <= 32:
+        why.append("the categorical MLP Q-network serves discrete action spaces of 2 to 32 actions")
+    N_ = int(c.categorical_num_atoms)
+    if not 2 <= N_ <= 256:
+        why.append(f"{N_} atoms are outside the categorical head's 2..256")
+    elif discrete and A * N_ > 512:
+        why.append(f"{A} actions x {N_} atoms = {A * N_} out_layer rows; the categorical head covers at most 512")
+    v_min, v_max = float(c.categorical_v_min), float(c.categorical_v_max)
+    if not (np.isfinite(v_min) and np.isfinite(v_max) and v_min < v_max):
+        why.append(f"the support needs finite categorical_v_min < categorical_v_max (got {v_min}..{v_max})")
+    D = flat_dim(frame_space(env, c))
+    if D is None:
+        why.append("the categorical MLP Q-network reads flat BoxSpace((D,)) observations; image observations stay on the plugin path")
+    elif D > 256:
+        why.append("the MLP Q-network reads at most 256 observation elements")
+    if getattr(c, "_obs_processors", None):
+        why.append("observation processors are served by the plugin path")
+    if c.window_length != 1:
+        why.append("the MLP Q-network reads one observation (window_length 1)")
+    sizes = mlp_layer_sizes(c)
+    if sizes is None:
+        why.append("the MLP Q-network's input value block and hidden block are MLPs of ReLU layers")
+    else:
+        kw = _mlp_kwargs_reason(c)
+        if kw:
+            why.append(kw)
+        layers = sizes[0] + sizes[1]
+        if not 1 <= len(layers) <= 3:
+            why.append("the MLP Q-network covers 1 to 3 dense layers (input value block plus hidden block)")
+        if any(w % 32 != 0 or not 32 <= w <= 512 for w in layers):
+            why.append("the MLP Q-network covers dense layers of 32..512 units in multiples of 32")
+    if c.batch_size > 256:
+        why.append("the MLP Q-network's gradient step covers batches of at most 256")
+    from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig
+
+    if not isinstance(c.memory, ReplayBufferConfig):
+        name = getattr(c.memory, "name", type(c.memory).__name__)
+        why.append(f"C51 draws uniformly from the ReplayBuffer memory (c51.py:19-20); memory '{name}' stays on the plugin path")
+    if c.lr_scheduler.schedule_type != "":
+        why.append(f"the MLP Q-network's Adam step takes a constant learning rate; lr_scheduler '{c.lr_scheduler.schedule_type}' stays on the plugin path")
+    return "; ".join(why)
+
+
+def c51_config_from(rl_config, env, n_envs: int, seed: int):
+    """c51.Config (srl/algorithms/c51/config.py:23-58) on a flat observation -> VectorQConfig (device/mlpq.py), for a pair `why_not_c51_engine` admits: the
+    categorical head's three fields, the uniform memory (alpha = 0, draws without replacement), no target network (target_model_update_interval is unused)."""
+    from simple_distributed_rl_amd.device.mlpq import VectorQConfig
+
+    why = why_not_c51_engine(env, rl_config)
+    if why:
+        raise ValueError("VectorQEngine cannot run this C51 configuration: " + why)
+    c, mem = rl_config, rl_config.memory
+    ins, hid = mlp_layer_sizes(c)
+    return VectorQConfig(
+        batch_size=c.batch_size, epsilon=c.epsilon, test_epsilon=c.test_epsilon, lr=c.lr, discount=c.discount, enable_reward_clip=False, enable_double_dqn=False,
+        enable_rescale=False, memory_capacity=mem.capacity, memory_warmup_size=mem.warmup_size, memory_has_duplicate=False, memory_alpha=0.0,
+        obs_dim=flat_dim(frame_space(env, c)), in_sizes=ins, hidden_sizes=hid, n_actions=int(env.action_space.n),
+        categorical_atoms=int(c.categorical_num_atoms), categorical_v_min=float(c.categorical_v_min), categorical_v_max=float(c.categorical_v_max),
+        n_envs=n_envs, seed=seed,
+    )
 
 
 AGENT57_MP_REASON = "Agent57 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
@@ -685,9 +767,12 @@ class _ReplayFacade:
 
 
 def load_q_weights(eng, parameter):
-    """The Runner's Parameter (reference layout) -> a Q-network engine's online and target networks, and its actors' private copy where it keeps one."""
-    online, target = parameter.q_online.state_dict(), parameter.q_target.state_dict()
-    nets = [(eng.q_online, online), (eng.q_target, target)]
+    """The Runner's Parameter (reference layout) -> a Q-network engine's online and target networks, and its actors' private copy where it keeps one.  A
+    Parameter without `q_target` (C51: c51.py:45-47 holds one network) exchanges the online network alone."""
+    online = parameter.q_online.state_dict()
+    nets = [(eng.q_online, online)]
+    if getattr(parameter, "q_target", None) is not None:
+        nets.append((eng.q_target, parameter.q_target.state_dict()))
     if eng.q_actor is not eng.q_online:
         nets.append((eng.q_actor, online))
     for net, sd in nets:
@@ -697,7 +782,10 @@ def load_q_weights(eng, parameter):
 def store_q_weights(eng, parameter):
     """The engine's trained online and target networks -> the Runner's Parameter."""
     torch.cuda.synchronize(eng.dev)
-    for mine, theirs in ((eng.q_online, parameter.q_online), (eng.q_target, parameter.q_target)):
+    pairs = [(eng.q_online, parameter.q_online)]
+    if getattr(parameter, "q_target", None) is not None:
+        pairs.append((eng.q_target, parameter.q_target))
+    for mine, theirs in pairs:
         sd = mine.reference_state_dict() if hasattr(mine, "reference_state_dict") else mine.state_dict()
         theirs.load_state_dict({k: v.to(next(theirs.parameters()).device) for k, v in sd.items()})
 
@@ -752,6 +840,11 @@ class VectorActor(ActorDriver):
         def env(replay):
             return self._make_batch_env(replay, context)
 
+        if engine_kind(self.rl_config) == "c51":  # the MLP Q-network engine with the categorical head
+            from simple_distributed_rl_amd.device.mlpq import VectorQEngine
+
+            self.cfg = c51_config_from(self.rl_config, self.env_run, self.lanes, seed)
+            return VectorQEngine(self.cfg, device, env=env)
         if is_flat_dqn(self.env_run, self.rl_config):  # flat observations: the MLP Q-network engine
             from simple_distributed_rl_amd.device.mlpq import VectorQEngine
 

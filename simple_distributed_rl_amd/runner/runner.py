@@ -226,6 +226,8 @@ class Runner:
                     self.vector_reason = "DQN runs on the device engine in train(); train_mp() keeps it on the plugin path"
                 if kind == "agent57":  # its engine is one process on one GPU
                     self.vector_reason = vr.AGENT57_MP_REASON
+                if kind == "c51":  # (device/mp_runner.py serves the Rainbow family)
+                    self.vector_reason = vr.C51_MP_REASON
                 if not self.vector_reason:  # one process per GPU over RCCL (device/mp_runner.py); this process is the learner rank
                     from simple_distributed_rl_amd.device.mp_runner import train_mp_on_engine
 
