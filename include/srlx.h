@@ -783,6 +783,14 @@ int srlx_qnet_create(srlx_qnet_t **out, int in_h, int in_w, int window, int filt
 int srlx_qnet_destroy(srlx_qnet_t *h);
 int srlx_qnet_bind(srlx_qnet_t *h, const float *const *d_params);
 int srlx_qnet_forward_u8(srlx_qnet_t *h, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, float *d_q, void *stream);
+/* Two handles' srlx_qnet_forward_u8 as THREE launches (the learner update's online pass over s_0..s_n and its target pass over s_1..s_n, which share nothing but the
+ * ring): both convolution passes in one launch, both first dense layers in one, both heads in one -- each workgroup runs the code of its own pass, so both handles
+ * are left exactly as their own srlx_qnet_forward_u8 leaves them (Q-values bit for bit, kept activations of a training handle, operand planes, partial sums, range
+ * flag, packing state).  The envelope: both handles 84 x 84 x 4 with 32 filters on the float16-split convolution kernel, valid operand planes with
+ * srlx_qnet_set_planes_small and 1..128 rows each, plain (not NoisyLinear) dueling heads of the same width with at most 8 actions, no UVFA columns, no fused policy,
+ * no probe armed.  *applied = 1: done; *applied = 0: outside the envelope -- nothing was launched and no handle was touched, the caller runs the two passes itself. */
+int srlx_qnet_forward_pair_u8(srlx_qnet_t *h_a, int64_t rows_a, const int64_t *d_frame_off_a, float *d_q_a, srlx_qnet_t *h_b, int64_t rows_b,
+                              const int64_t *d_frame_off_b, float *d_q_b, const uint8_t *d_frame_base, int *applied, void *stream);
 /* The batched Worker.policy step as one call (srl/algorithms/rainbow/rainbow.py:301-329 behind srl/base/rl/worker_run.py:316-322): srlx_qnet_forward_u8 whose head
  * kernel also selects the actions -- epsilon-greedy exactly as srlx_policy_epsilon_greedy would on the Q rows with the uniforms srlx_rng_uniform(seed, d_counter,
  * 2 * batch, u) would write (row e uses u[2 e], u[2 e + 1]).  *d_counter is READ only: advance it once per pass yourself (srlx_store_commit_step_ex's d_bump does).
@@ -890,6 +898,11 @@ int srlx_qnet_set_debug(srlx_qnet_t *h, void *d_phase_stamps);
  * (blocking device-to-host copy: call where the host has synchronised; the host side raises, device/qnet.py:check_ranges).  SRLX_CONV_BF16X3=1 (the
  * environment switches above) avoids the limit. */
 int srlx_qnet_range_flags(srlx_qnet_t *h, int *out_bits);
+/* For tests that compare two ways of running a forward pass: what the pass left in the handle.  what 0..8: the device buffer act1, act2, act3, h1 (post-ReLU hidden
+ * layer of a training handle), activation planes, split-K partial sums, packed filters, transposed filters of conv3 / conv2 -> *d_ptr (BORROWED; NULL where the
+ * handle owns none) and its size *n in float32 elements (the planes: float16 elements).  what 100: host-side state as bits of *n: 1 the last forward built the
+ * transposed filters, 2 packed filters valid, 4 activation planes fresh, 8 weight planes valid, 16 the pass continued into the dense layers, 32 partial sums used. */
+int srlx_qnet_inspect(srlx_qnet_t *h, int what, void **d_ptr, int64_t *n);
 /* Training on the vectorised path (replaces `loss.backward()` + the framework forward it needs,
  * srl/algorithms/rainbow/model_torch.py:103-109):
  *   srlx_qnet_enable_training : from now on every forward keeps its post-ReLU hidden layer, and gradient scratch for up

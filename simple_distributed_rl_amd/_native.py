@@ -97,6 +97,7 @@ SIGNATURES = {
     "srlx_qnet_destroy": (c_int, [c_p]),
     "srlx_qnet_bind": (c_int, [c_p, c_p]),
     "srlx_qnet_forward_u8": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "srlx_qnet_forward_pair_u8": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, ctypes.POINTER(c_int), c_p]),
     "srlx_qnet_forward_convs_multi_u8": (c_int, [c_p, c_int, c_i64, c_p, c_p, c_p]),
     "srlx_qnet_forward_dense_planes": (c_int, [c_p, c_i64, c_p, c_p]),
     "srlx_qnet_forward_convs_u8": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p]),
@@ -131,6 +132,7 @@ SIGNATURES = {
     "srlx_qnet_invalidate_fc1_planes": (c_int, [c_p]),
     "srlx_qnet_set_debug": (c_int, [c_p, c_p]),
     "srlx_qnet_range_flags": (c_int, [c_p, c_p]),
+    "srlx_qnet_inspect": (c_int, [c_p, c_int, ctypes.POINTER(c_p), ctypes.POINTER(c_i64)]),
     "srlx_qnet_fuse_adam_fc1": (c_int, [c_p, c_p, c_p, c_f64, c_f64, c_f64, c_f64, c_p]),
     "srlx_qnet_fuse_adam_rest": (c_int, [c_p, c_p, c_p, c_p]),
     "srlx_qnet_backward_u8": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),

@@ -234,14 +234,14 @@ constexpr int kRWSlabs = 8;  // K-slabs of weight fragments held in registers
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// (the body takes its block coordinates and grid as arguments: k_fc1_planes_rows runs it on its own grid, k_fc1_planes_rows_pair on a z range of a merged launch)
 template <int RT>
-__global__ void __launch_bounds__(256) k_fc1_planes_rows(const uint4 *__restrict__ A, const uint4 *__restrict__ W, float *__restrict__ C, int N, int K8, int slabs_per_split) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+__device__ __forceinline__ void fc1_planes_rows_body(const uint4 *__restrict__ A, const uint4 *__restrict__ W, float *__restrict__ C, int N, int K8, int slabs_per_split,
+                                                     unsigned char *smem, unsigned by, unsigned bz, unsigned gy, unsigned gz) {
     constexpr int kSlot = RT * 32 * kHRow;  // bytes of one activation slab
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i = lane & 31, h = lane >> 5;
-    unsigned by = blockIdx.y, bz = blockIdx.z;
     {   // XCD-aware tile order: an XCD's contiguous eighth of the (split, N tile) space shares its splits' activation slabs in that XCD's L2
-        const unsigned gy = gridDim.y, total = gy * gridDim.z;
+        const unsigned total = gy * gz;
         if (total % 8 == 0) {
             const unsigned lin = by + gy * bz, tile = (lin % 8) * (total / 8) + lin / 8;
             by = tile % gy, bz = tile / gy;
@@ -360,6 +360,27 @@ __global__ void __launch_bounds__(256) k_fc1_planes_rows(const uint4 *__restrict
             Cz[(i64)m * N + n] = __builtin_fmaf(lo[rt][r], 1.0f / 2048.0f, acc[rt][r]);
         }
 }
+template <int RT>
+__global__ void __launch_bounds__(256) k_fc1_planes_rows(const uint4 *__restrict__ A, const uint4 *__restrict__ W, float *__restrict__ C, int N, int K8, int slabs_per_split) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    fc1_planes_rows_body<RT>(A, W, C, N, K8, slabs_per_split, smem, blockIdx.y, blockIdx.z, gridDim.y, gridDim.z);
+}
+
+// Two handles' one-row-tile launches as one (srlx_qnet_forward_pair_u8): z < za runs the <RTA> body on handle a's planes and partial buffer over a grid of (gy, za),
+// the rest the <RTB> body on handle b's over (gy, gridDim.z - za) -- each workgroup the tile, K split and XCD order of its own launch.
+struct RowsArgs {
+    const uint4 *A, *W;
+    float *C;
+    int sps;  // K-slabs per split
+};
+template <int RTA, int RTB>
+__global__ void __launch_bounds__(256) k_fc1_planes_rows_pair(RowsArgs a, RowsArgs b, int N, int K8, unsigned za) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (blockIdx.z < za)
+        fc1_planes_rows_body<RTA>(a.A, a.W, a.C, N, K8, a.sps, smem, blockIdx.y, blockIdx.z, gridDim.y, za);
+    else
+        fc1_planes_rows_body<RTB>(b.A, b.W, b.C, N, K8, b.sps, smem, blockIdx.y, blockIdx.z - za, gridDim.y, gridDim.z - za);
+}
 
 template <int RT>
 int launch_rows(srlx_qnet *h, int used, int kps, hipStream_t st) {
@@ -376,7 +397,45 @@ int launch_rows(srlx_qnet *h, int used, int kps, hipStream_t st) {
     return SRLX_OK;
 }
 
+template <int RTA, int RTB>
+int launch_rows_pair(srlx_qnet *ha, int used_a, int kps_a, srlx_qnet *hb, int used_b, int kps_b, hipStream_t st) {
+    static bool attr = false;
+    constexpr int lds = kRSlots * (RTA > RTB ? RTA : RTB) * 32 * kHRow;
+    if (!attr) {
+        SRLX_HIP(hipFuncSetAttribute((const void *)k_fc1_planes_rows_pair<RTA, RTB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        attr = true;
+    }
+    const int N1 = 2 * ha->hidden;
+    const RowsArgs a{(const uint4 *)ha->a3_planes, (const uint4 *)ha->wf_planes, ha->partial, kps_a}, b{(const uint4 *)hb->a3_planes, (const uint4 *)hb->wf_planes, hb->partial, kps_b};
+    hipLaunchKernelGGL((k_fc1_planes_rows_pair<RTA, RTB>), dim3(1, (unsigned)(N1 / kTN), (unsigned)(used_a + used_b)), dim3(256), lds, st, a, b, N1, ha->flat / 8, (unsigned)used_a);
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+template <int RTA>
+int launch_rows_pair_b(int rtb, srlx_qnet *ha, int used_a, int kps_a, srlx_qnet *hb, int used_b, int kps_b, hipStream_t st) {
+    switch (rtb) {
+        case 1: return launch_rows_pair<RTA, 1>(ha, used_a, kps_a, hb, used_b, kps_b, st);
+        case 2: return launch_rows_pair<RTA, 2>(ha, used_a, kps_a, hb, used_b, kps_b, st);
+        case 3: return launch_rows_pair<RTA, 3>(ha, used_a, kps_a, hb, used_b, kps_b, st);
+        default: return launch_rows_pair<RTA, 4>(ha, used_a, kps_a, hb, used_b, kps_b, st);
+    }
+}
+
 }  // namespace
+
+// srlx_fc1_planes_gemm of two handles (each <= 128 rows, same layer shape, `wf_planes` already what each pass reads) as one launch
+int srlx_fc1_planes_gemm_pair(srlx_qnet *ha, int64_t rows_a, int kps_a, srlx_qnet *hb, int64_t rows_b, int kps_b, hipStream_t st) {
+    SRLX_REQUIRE(rows_a >= 1 && rows_a <= kTM && rows_b >= 1 && rows_b <= kTM && ha->hidden == hb->hidden && ha->flat == hb->flat, "fc1_planes_gemm_pair: outside the envelope");
+    const int nsl = ha->flat / 32, used_a = (nsl + kps_a - 1) / kps_a, used_b = (nsl + kps_b - 1) / kps_b;
+    ha->fc1_span = hb->fc1_span = nullptr;
+    const int rtb = (int)((rows_b + 31) / 32);
+    switch ((int)((rows_a + 31) / 32)) {
+        case 1: return launch_rows_pair_b<1>(rtb, ha, used_a, kps_a, hb, used_b, kps_b, st);
+        case 2: return launch_rows_pair_b<2>(rtb, ha, used_a, kps_a, hb, used_b, kps_b, st);
+        case 3: return launch_rows_pair_b<3>(rtb, ha, used_a, kps_a, hb, used_b, kps_b, st);
+        default: return launch_rows_pair_b<4>(rtb, ha, used_a, kps_a, hb, used_b, kps_b, st);
+    }
+}
 
 // operand planes of this handle: allocated by srlx_qnet_enable_fc1_planes
 int srlx_fc1_planes_alloc(srlx_qnet *h) {

@@ -550,14 +550,14 @@ __device__ __forceinline__ void fused_policy(const srlx_qnet::Policy &pol, i64 m
 constexpr int kMaxActions = 32;
 // AMAX = 8 / 16 / 32 >= A (round 5: with the loops over kMaxActions = 32 and a run-time A, every one of the accumulate / shuffle / store loops carried 32 uniform
 // branches for 6 live actions, and thread 0 summed the waves' partial rows with 56 dependent LDS reads: 16.5 us for the learner's 128 rows, of which the loads were 7)
+// (the body takes its row as an argument: k_head runs it on its own grid, k_head_pair on a block range of a merged launch)
 template <int AMAX>
-__global__ void __launch_bounds__(512) k_head(const float *__restrict__ partial, int splits, i64 M, int hidden, const float *__restrict__ b1,
-                                              const float *__restrict__ v2w, const float *__restrict__ v2b, const float *__restrict__ a2w,
-                                              const float *__restrict__ a2b, int A, int dueling, float *__restrict__ q, float *__restrict__ h1, i64 ostride,
-                                              i64 *__restrict__ draw, srlx_qnet::Policy pol, srlx_uvfa_dev uv) {
+__device__ __forceinline__ void head_body(const float *__restrict__ partial, int splits, i64 M, int hidden, const float *__restrict__ b1, const float *__restrict__ v2w,
+                                          const float *__restrict__ v2b, const float *__restrict__ a2w, const float *__restrict__ a2b, int A, int dueling,
+                                          float *__restrict__ q, float *__restrict__ h1, i64 ostride, i64 *__restrict__ draw, const srlx_qnet::Policy &pol,
+                                          const srlx_uvfa_dev &uv, const i64 m) {
     __shared__ float red[8][kMaxActions + 1];  // one row per wave (256 or 512 threads)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const i64 m = blockIdx.x;
     // UVFA inputs of this row (agent57_light/model_torch.py:52-62): the rewards scale their columns of the first dense layer, each one-hot selects one
     float x_ext = 0.f, x_int = 0.f;
     const float *col_act = nullptr, *col_actor = nullptr, *col_ext = nullptr, *col_int = nullptr;
@@ -570,7 +570,7 @@ __global__ void __launch_bounds__(512) k_head(const float *__restrict__ partial,
     }
     const i64 mo = m * ostride;  // row of q / h1 this sample's results go to (the partial sums are dense over the launch's rows)
     const int N1 = 2 * hidden;
-    if (draw && blockIdx.x == 0 && t == 0) draw[0] += 1;  // NoisyLinear: the draw this pass used is spent (every reader of draw[0] ran in an earlier launch)
+    if (draw && m == 0 && t == 0) draw[0] += 1;  // NoisyLinear: the draw this pass used is spent (every reader of draw[0] ran in an earlier launch)
     float v = 0.f, adv[AMAX];
 #pragma unroll
     for (int j = 0; j < AMAX; j++) adv[j] = 0.f;
@@ -680,6 +680,29 @@ __global__ void __launch_bounds__(512) k_head(const float *__restrict__ partial,
             }
         fused_policy<AMAX>(pol, m, A, out);
     }
+}
+template <int AMAX>
+__global__ void __launch_bounds__(512) k_head(const float *__restrict__ partial, int splits, i64 M, int hidden, const float *__restrict__ b1,
+                                              const float *__restrict__ v2w, const float *__restrict__ v2b, const float *__restrict__ a2w,
+                                              const float *__restrict__ a2b, int A, int dueling, float *__restrict__ q, float *__restrict__ h1, i64 ostride,
+                                              i64 *__restrict__ draw, srlx_qnet::Policy pol, srlx_uvfa_dev uv) {
+    head_body<AMAX>(partial, splits, M, hidden, b1, v2w, v2b, a2w, a2b, A, dueling, q, h1, ostride, draw, pol, uv, (i64)blockIdx.x);
+}
+
+// Two handles' heads as one launch (srlx_qnet_forward_pair_u8): block < rows_a is row `block` of handle a, the rest rows of handle b -- plain dueling heads without
+// UVFA columns, NoisyLinear draws or a fused policy.
+struct HeadArgs {
+    const float *partial, *b1, *v2w, *v2b, *a2w, *a2b;
+    float *q, *h1;
+    i64 M;
+    int splits, A, dueling;
+};
+template <int AMAX>
+__global__ void __launch_bounds__(512) k_head_pair(HeadArgs a, HeadArgs b, int hidden, int rows_a) {
+    i64 m = blockIdx.x;
+    HeadArgs n = a;  // (block-uniform selection: scalar registers)
+    if (m >= rows_a) m -= rows_a, n = b;
+    head_body<AMAX>(n.partial, n.splits, n.M, hidden, n.b1, n.v2w, n.v2b, n.a2w, n.a2b, n.A, n.dueling, n.q, n.h1, (i64)1, nullptr, srlx_qnet::Policy{}, srlx_uvfa_dev{}, m);
 }
 
 // ---- the plain head (dueling_type kHeadPlain): DQN's out_layer over all N1 = 2 hidden units (srl/algorithms/dqn/model_torch.py:17-29) ----
@@ -953,9 +976,19 @@ int run_dense(srlx_qnet *h, i64 B, float *d_q, hipStream_t st) {
 
 // The dense layers over `rows` activation rows act3[i * stride] (i < rows): FC1 split along K so that ~512 workgroups exist whatever
 // the batch, then the head (split reduction + bias + ReLU, second layers, dueling combine) writing q / h1 rows i * stride.
+// K splits of the first dense layer over B rows: slabs per split and the splits that own a K range
+static void fc1_split_plan(const srlx_qnet *h, int64_t B, int *splits_out, int *kps_out, int *used_out);
+static int srlx_qnet_dense_rows_planned(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hipStream_t st, int splits, int kps, int used);
+
 int srlx_qnet_dense_rows(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hipStream_t st) {
-    const int N1 = 2 * h->hidden;
     h->partial_used = true;
+    int splits, kps, used;
+    fc1_split_plan(h, B, &splits, &kps, &used);
+    return srlx_qnet_dense_rows_planned(h, B, stride, d_q, st, splits, kps, used);
+}
+
+static void fc1_split_plan(const srlx_qnet *h, int64_t B, int *splits_out, int *kps_out, int *used_out) {
+    const int N1 = 2 * h->hidden;
     const i64 tiles = ((B + BM - 1) / BM) * ((N1 + 63) / 64);
     int splits = (int)((512 + tiles - 1) / tiles);  // ~512 workgroups (the learner's 96 / 128 rows at 1024: no faster; at 384 / 256 / 192: +2 / +7 / +9 % per period of a learner rank)
     const int ksteps = h->flat / BK;
@@ -968,7 +1001,12 @@ int srlx_qnet_dense_rows(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hi
     }
     if (splits < 1) splits = 1;
     const int kps = ((ksteps + splits - 1) / splits);
-    const int used = (ksteps + kps - 1) / kps;  // splits that actually own a K range
+    *splits_out = splits, *kps_out = kps;
+    *used_out = (ksteps + kps - 1) / kps;  // splits that actually own a K range
+}
+
+static int srlx_qnet_dense_rows_planned(srlx_qnet *h, int64_t B, int64_t stride, float *d_q, hipStream_t st, int splits, int kps, int used) {
+    const int N1 = 2 * h->hidden;
     const bool fc1_f32 = srlx::switches().fc1_f32;
     // chip-filling launches of a handle with valid weight planes (the actors' pass): conversion-free GEMM on pre-split operands, bit-identical to k_gemm_s16
     const bool planes = !fc1_f32 && stride == 1 && h->planes_valid && !h->eff[0] && srlx_fc1_planes_applicable(h, B);
@@ -1109,6 +1147,34 @@ int srlx_qnet_range_flags(srlx_qnet_t *h, int *out) {
     SRLX_REQUIRE(h && out, "qnet_range_flags: NULL argument");
     srlx::DeviceGuard guard(h->device);
     SRLX_HIP(hipMemcpy(out, h->range_flag, sizeof(int), hipMemcpyDeviceToHost));
+    return SRLX_OK;
+}
+
+// What a forward pass leaves in a handle, for tests that compare two ways of running it (tests/test_forward_pair_gpu.py): `what` 0..8 = device buffer act1, act2,
+// act3, h1, the activation planes, the split-K partial sums, the packed filters, the transposed filters of conv3 / conv2 -> *d_ptr and its size in *n (float32
+// elements; the planes: float16 elements); 100 = the host-side state as bits of *n: 1 wt_from_forward, 2 pack_valid, 4 a3_planes_fresh, 8 planes_valid,
+// 16 want_planes_out, 32 partial_used.  A buffer the handle does not own comes back NULL with *n = 0.
+int srlx_qnet_inspect(srlx_qnet_t *h, int what, void **d_ptr, int64_t *n) {
+    SRLX_REQUIRE(h && d_ptr && n, "qnet_inspect: NULL argument");
+    const int64_t mb = h->max_batch, N1 = 2 * h->hidden;
+    *d_ptr = nullptr, *n = 0;
+    switch (what) {
+        case 0: *d_ptr = h->act1, *n = mb * h->OH1 * h->OW1 * h->F1; break;
+        case 1: *d_ptr = h->act2, *n = mb * h->OH2 * h->OW2 * 2 * h->F1; break;
+        case 2: *d_ptr = h->act3, *n = mb * h->flat; break;
+        case 3: *d_ptr = h->h1, *n = mb * N1; break;
+        case 4: *d_ptr = h->a3_planes, *n = (mb + 127) / 128 * 128 * (int64_t)h->flat * 2; break;
+        case 5: *d_ptr = h->partial, *n = (int64_t)h->partial_floats; break;
+        case 6: *d_ptr = h->wpack, *n = (int64_t)(srlx_qnet_pack_bytes() / sizeof(float)); break;
+        case 7: *d_ptr = h->w_t, *n = (int64_t)2 * h->F1 * 9 * 2 * h->F1; break;
+        case 8: *d_ptr = h->w_t2, *n = (int64_t)2 * h->F1 * 16 * h->F1; break;
+        case 100:
+            *n = (h->wt_from_forward ? 1 : 0) | (h->pack_valid ? 2 : 0) | (h->a3_planes_fresh ? 4 : 0) | (h->planes_valid ? 8 : 0) | (h->want_planes_out ? 16 : 0) |
+                 (h->partial_used ? 32 : 0);
+            return SRLX_OK;
+        default: SRLX_REQUIRE(false, "qnet_inspect: unknown item %d", what);
+    }
+    if (!*d_ptr) *n = 0;
     return SRLX_OK;
 }
 
@@ -1468,6 +1534,59 @@ int srlx_qnet_forward_u8(srlx_qnet_t *h, int64_t batch, const uint8_t *d_frame_b
     SRLX_REQUIRE(batch > 0 && batch <= h->max_batch, "qnet_forward_u8: batch %lld exceeds max_batch %lld", (long long)batch, (long long)h->max_batch);
     srlx::DeviceGuard guard(h->device);
     return forward_u8_impl(h, batch, d_frame_base, d_frame_off, d_q, (hipStream_t)stream);
+}
+
+// is this handle's next `rows`-row pass one that srlx_qnet_forward_pair_u8 reproduces: the fused convolution kernel on the learner-pass path (float32 act3 + operand
+// planes), the one-row-tile planes GEMM and the plain dueling head for up to 8 actions, nothing measured or fused into it
+static bool pair_applicable(const srlx_qnet *h, int64_t rows) {
+    const srlx::Switches &sw = srlx::switches();
+    if (sw.no_fused_conv || sw.no_conv_planes || sw.conv1_f32 || sw.conv23_f32 || sw.fc1_f32) return false;
+    if (!(h->H == 84 && h->W == 84 && h->Wn == 4 && h->F1 == 32) || !h->w1 || h->eff[0] || h->sig[0]) return false;
+    if (rows < 1 || rows > 128 || rows > h->max_batch || !h->planes_valid || !h->planes_small || h->planes_small_h || !srlx_fc1_planes_applicable(h, rows)) return false;
+    if (h->head_mode != 0 || h->dueling == kHeadPlain || h->A > 8 || h->uvfa.X > 0 || h->uvfa.wx || h->pol.eps || h->pol.actions) return false;
+    if (h->probe0 || h->probe1 || h->probe_fc0 || h->probe_fc1 || h->fused_dbg || h->fc1_span) return false;
+    int splits, kps, used;
+    fc1_split_plan(h, rows, &splits, &kps, &used);
+    return (size_t)used * 128 * (2 * (size_t)h->hidden) <= h->partial_floats;
+}
+
+int srlx_qnet_forward_pair_u8(srlx_qnet_t *h_a, int64_t rows_a, const int64_t *d_off_a, float *d_q_a, srlx_qnet_t *h_b, int64_t rows_b, const int64_t *d_off_b, float *d_q_b,
+                              const uint8_t *d_frame_base, int *applied, void *stream) {
+    SRLX_REQUIRE(h_a && h_b && d_off_a && d_off_b && d_q_a && d_q_b && d_frame_base && applied, "qnet_forward_pair_u8: NULL argument");
+    *applied = 0;
+    if (h_a == h_b || h_a->device != h_b->device || h_a->hidden != h_b->hidden || h_a->flat != h_b->flat || !pair_applicable(h_a, rows_a) || !pair_applicable(h_b, rows_b))
+        return SRLX_OK;  // not applicable: nothing was launched, no handle was touched -- the caller runs the two passes on their own
+    srlx::DeviceGuard guard(h_a->device);
+    hipStream_t st = (hipStream_t)stream;
+    SRLX_TRY(srlx_qnet_fused_convs_pair(h_a, rows_a, d_off_a, h_b, rows_b, d_off_b, d_frame_base, st));
+    srlx_qnet *hs[2] = {h_a, h_b};
+    const int64_t rows[2] = {rows_a, rows_b};
+    float *qs[2] = {d_q_a, d_q_b};
+    int kps[2], used[2];
+    void *own[2];
+    for (int k = 0; k < 2; k++) {
+        int splits;
+        hs[k]->partial_used = true;
+        fc1_split_plan(hs[k], rows[k], &splits, &kps[k], &used[k]);
+        hs[k]->a3_planes_fresh = false;
+        own[k] = hs[k]->wf_planes;
+        if (hs[k]->wf_planes_ext) hs[k]->wf_planes = const_cast<void *>(hs[k]->wf_planes_ext);
+    }
+    const int rc = srlx_fc1_planes_gemm_pair(h_a, rows_a, kps[0], h_b, rows_b, kps[1], st);
+    for (int k = 0; k < 2; k++) hs[k]->wf_planes = own[k];
+    SRLX_TRY(rc);
+    if (h_a->stamp_buf) SRLX_TRY(srlx_debug_stamp(h_a->stamp_buf, 11, st));
+    HeadArgs ha[2];
+    for (int k = 0; k < 2; k++) {
+        const srlx_qnet *h = hs[k];
+        ha[k] = HeadArgs{h->partial, h->bf, h->v2w, h->v2b, h->a2w, h->a2b, qs[k], h->h1, (i64)128, used[k], h->A, h->dueling};
+    }
+    hipLaunchKernelGGL(k_head_pair<8>, dim3((unsigned)(rows_a + rows_b)), dim3(h_a->hidden > 256 ? 512 : 256), 0, st, ha[0], ha[1], h_a->hidden, (int)rows_a);
+    for (int k = 0; k < 2; k++) hs[k]->pol = srlx_qnet::Policy{};
+    if (h_a->stamp_buf) SRLX_TRY(srlx_debug_stamp(h_a->stamp_buf, 12, st));
+    SRLX_HIP(hipGetLastError());
+    *applied = 1;
+    return SRLX_OK;
 }
 
 int srlx_qnet_forward_u8_policy(srlx_qnet_t *h, int64_t batch, const uint8_t *d_frame_base, const int64_t *d_frame_off, float *d_q, const float *d_eps, uint64_t seed,

@@ -895,6 +895,26 @@ __global__ void __launch_bounds__(64 * kWaves) k_convnet_fused_multi(const u8 *_
                                                  n_samples, b, false, nets.flag[net]);
 }
 
+// Two networks' learner passes over their OWN frame stacks as ONE launch (srlx_qnet_forward_pair_u8: the update's online pass over s_0..s_n and its target pass over
+// s_1..s_n): workgroup < rows_a runs the learner-pass body (float32 act3 AND operand planes, act1 / act2 kept for a training handle) on net a's arguments, the rest on
+// net b's.  128 + 96 workgroups are still one round of the chip.
+struct PairNet {
+    const i64 *frame_off;
+    const float *wpk, *b1, *b2, *b3;
+    float *act3, *act1, *act2;
+    unsigned char *planes;
+    int *flag;
+    long long rows;
+};
+template <bool H16>
+__global__ void __launch_bounds__(64 * kWaves) k_convnet_fused_pair(const u8 *__restrict__ base, PairNet a, PairNet b) {
+    const bool second = (long long)blockIdx.x >= a.rows;
+    PairNet n = a;  // (block-uniform selection: scalar registers)
+    if (second) n = b;
+    convnet_fused_body<false, true, true, 2, H16>(base, n.frame_off, n.wpk, n.b1, n.b2, n.b3, n.act3, n.act1, n.act2, nullptr, n.planes, (n.rows + 127) / 128 * 128, n.rows,
+                                                  (i64)blockIdx.x - (second ? a.rows : 0), false, n.flag);
+}
+
 }  // namespace
 
 size_t srlx_qnet_pack_bytes() { return (size_t)kPackFloats * sizeof(float); }
@@ -903,7 +923,10 @@ size_t srlx_qnet_pack_bytes() { return (size_t)kPackFloats * sizeof(float); }
 // into an actor set together with the small vectors (layout *L)
 int srlx_qnet_pack_publish(srlx_qnet *src, srlx_qnet::ActorSet *dst_set, const srlx_small_layout *L, hipStream_t st, int64_t *bump, bool adam_small) {
     float *&own = src->aset_cur >= 0 ? src->wpack_own : src->wpack;
-    if (!own) SRLX_HIP(hipMalloc((void **)&own, (size_t)kPackFloats * sizeof(float)));
+    if (!own) {
+        SRLX_HIP(hipMalloc((void **)&own, (size_t)kPackFloats * sizeof(float)));
+        SRLX_HIP(hipMemsetAsync(own, 0, (size_t)kPackFloats * sizeof(float), st));  // (the layout's padding is never written: defined content, whatever the allocator hands out)
+    }
     const bool keep = src->max_train > 0;
     const float *const *b = src->aset_cur >= 0 ? src->bound : nullptr;  // a handle reading a set still packs its BOUND weights
     const float *w1 = b ? b[0] : src->w1, *w2 = b ? b[2] : src->w2, *w3 = b ? b[4] : src->w3;
@@ -1034,6 +1057,44 @@ int srlx_qnet_fused_convs_multi(srlx_qnet *const *hs, int n, int64_t batch, cons
     if (hs[0]->probe1) SRLX_HIP(hipEventRecord(hs[0]->probe1, st));
     hs[0]->probe0 = hs[0]->probe1 = nullptr;
     for (int k = 0; k < n; k++) hs[k]->a3_planes_fresh = true, hs[k]->want_planes_out = true;
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+// The convolution launch of srlx_qnet_forward_pair_u8 (the caller has checked the envelope: srlx_qnet.hip); each handle is left as after srlx_qnet_fused_convs on
+// the learner-pass path (float32 act3, fresh operand planes, act1 / act2 and transposed filters of a training handle).
+int srlx_qnet_fused_convs_pair(srlx_qnet *ha, int64_t rows_a, const int64_t *off_a, srlx_qnet *hb, int64_t rows_b, const int64_t *off_b, const uint8_t *d_frame_base,
+                               hipStream_t st) {
+    static const hipError_t attr = [] {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_convnet_fused_pair<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+        return e != hipSuccess ? e : hipFuncSetAttribute((const void *)k_convnet_fused_pair<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    }();
+    SRLX_HIP(attr);
+    PairNet n[2];
+    srlx_qnet *hs[2] = {ha, hb};
+    const int64_t rows[2] = {rows_a, rows_b};
+    const int64_t *offs[2] = {off_a, off_b};
+    for (int k = 0; k < 2; k++) {
+        srlx_qnet *h = hs[k];
+        h->want_planes_out = true;
+        if (!h->pack_valid) {
+            SRLX_TRY(srlx_qnet_pack_publish(h, nullptr, nullptr, st));
+            h->pack_valid = h->pack_sticky;
+        }
+        const bool keep = h->max_train > 0;
+        h->wt_from_forward = keep;
+        n[k] = PairNet{offs[k], h->wpack, h->b1, h->b2, h->b3, h->act3, keep ? h->act1 : nullptr, keep ? h->act2 : nullptr, (unsigned char *)h->a3_planes, h->range_flag,
+                       (long long)rows[k]};
+    }
+    const srlx::Switches &sw = srlx::switches();
+    const bool h16 = sw.conv_h16 && !sw.conv1_f32;
+    const dim3 grid((unsigned)(rows_a + rows_b));
+    if (h16)
+        hipLaunchKernelGGL(k_convnet_fused_pair<true>, grid, dim3(64 * kWaves), kLdsH16, st, d_frame_base, n[0], n[1]);
+    else
+        hipLaunchKernelGGL(k_convnet_fused_pair<false>, grid, dim3(64 * kWaves), kLdsBytes, st, d_frame_base, n[0], n[1]);
+    for (int k = 0; k < 2; k++) hs[k]->a3_planes_fresh = true, hs[k]->probe0 = hs[k]->probe1 = nullptr;
+    if (ha->stamp_buf) SRLX_TRY(srlx_debug_stamp(ha->stamp_buf, 10, st));
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

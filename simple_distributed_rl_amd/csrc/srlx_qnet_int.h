@@ -191,6 +191,10 @@ size_t srlx_qnet_pack_bytes();
 int srlx_fc1_planes_split_act(srlx_qnet *h, int64_t rows, hipStream_t st);
 bool srlx_fc1_planes_applicable(const srlx_qnet *h, int64_t rows);
 int srlx_fc1_planes_gemm(srlx_qnet *h, int64_t rows, int splits, int kps, hipStream_t st);
+// srlx_qnet_forward_pair_u8's launches: both handles' convolutions (srlx_qnet_fused.hip) and both handles' one-row-tile first dense layers (srlx_fc1_planes.hip) as one launch each
+int srlx_qnet_fused_convs_pair(srlx_qnet *ha, int64_t rows_a, const int64_t *off_a, srlx_qnet *hb, int64_t rows_b, const int64_t *off_b, const uint8_t *d_frame_base,
+                               hipStream_t st);
+int srlx_fc1_planes_gemm_pair(srlx_qnet *ha, int64_t rows_a, int kps_a, srlx_qnet *hb, int64_t rows_b, int kps_b, hipStream_t st);
 
 // implicit-GEMM data gradient on the matrix cores (defined next to k_gemm in srlx_qnet.hip)
 int srlx_qnet_dgrad_gemm(const float *dY, int B, int QH, int QW, int OH, int OW, int CO, int KH, int KW, int S, const float *wT, int CI, float *dXq,

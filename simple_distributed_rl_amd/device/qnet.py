@@ -627,6 +627,19 @@ class QNetInference:
         return q
 
 
+def forward_pair_u8(a: "QNetInference", off_a: torch.Tensor, b: "QNetInference", off_b: torch.Tensor, frame_base_ptr: int, out_a: torch.Tensor = None,
+                    out_b: torch.Tensor = None):
+    """`a.forward_u8(base, off_a)` and `b.forward_u8(base, off_b)` as three launches on the current stream (srlx_qnet_forward_pair_u8): (q_a, q_b), both handles left
+    as their own passes leave them -- or None, nothing launched, where the pair is outside that entry point's envelope (the caller runs the two passes itself)."""
+    Ba, Bb = off_a.numel() // a.window, off_b.numel() // b.window
+    qa = a.q[:Ba] if out_a is None else out_a
+    qb = b.q[:Bb] if out_b is None else out_b
+    applied = ctypes.c_int(0)
+    N.check(a.lib.srlx_qnet_forward_pair_u8(a.h, Ba, N.tptr(off_a), N.tptr(qa), b.h, Bb, N.tptr(off_b), N.tptr(qb), N.c_p(frame_base_ptr), ctypes.byref(applied),
+                                            N.torch_stream_ptr()))
+    return (qa, qb) if applied.value else None
+
+
 class ImageTrunk:
     """The image block of a torch network (DQNImageBlock, dqn_image_block.py:29-54: 8x8/4, 4x4/2, 3x3/1 convolutions with replicate padding
     and ReLU) evaluated by libsrlx straight from the uint8 frame ring -- for networks whose dense part is NOT the dueling head of

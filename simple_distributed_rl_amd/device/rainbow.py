@@ -22,7 +22,7 @@ import torch
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.device import lockstep
 from simple_distributed_rl_amd.device.replay import DeviceReplay
-from simple_distributed_rl_amd.device.qnet import DeviceAdam, EngineQNet, QNetInference, check_ranges
+from simple_distributed_rl_amd.device.qnet import DeviceAdam, EngineQNet, QNetInference, check_ranges, forward_pair_u8
 
 
 @dataclass
@@ -45,6 +45,10 @@ class EngineSchedule:
     fused_td: bool = True  # TD target / Huber / priorities in the backward pass's head kernel (False: a launch of their own)
     autograd_yardstick: bool = False  # the gradient step through torch autograd on float32 pixels: a TEST yardstick, never a fallback
     fused_draw: bool = True  # PER draw + item gather as one launch
+    forward_pair: Optional[bool] = None  # single-GPU fast lock-step with learner_planes: the update's online and target passes as ONE chain of three launches (convolutions,
+    # first dense layers, heads of both networks in one launch each: srlx_qnet_forward_pair_u8) -- three graph nodes and the only mid-chain cross-stream join fewer, the
+    # target stream keeps only the lagged tree add, forked BEHIND the pair's launches (recorded before them it takes the chain's hardware queue: 0.481 against 0.439 ms per
+    # lock-step, profiles/update_fused_ab.json).  Bit-identical.  None: on where it applies; True: raise where it does not; False: off
     learner_planes: Optional[bool] = None  # single-GPU fast lock-step: the update's two forward passes run their first dense layer on float16 operand planes that exist
     # anyway (srlx_fc1_planes.hip: k_fc1_planes_rows) -- the online pass on the published set that holds the current weight, the target pass on planes split at every
     # target sync.  Bit-identical to the staging-split GEMM.  None: on where it applies; True: raise where it does not; False: off (the A/B switch, the tests' yardstick)
@@ -218,6 +222,7 @@ class RainbowEngine:
             self.env = env(self.replay) if callable(env) else env
 
         self.actor_stream = None
+        self._forward_pair, self._pair_applied = False, 0  # EngineSchedule.forward_pair; updates ISSUED (eagerly or into a capture) with the pair forward
         want = actor_stream or sch.actor_stream
         if self.fast and want and want != "default":
             self.actor_stream = lockstep.ActorStream(self.lib, self.dev, want)  # (`close()` hands the thread back)
@@ -334,6 +339,10 @@ class RainbowEngine:
             N.check(self.lib.srlx_qnet_set_main_first(self.inf_online.h, 1))
             if sch.dgrad_split is None or int(sch.dgrad_split) == 2:  # conv3's data-gradient GEMM as twice the workgroups, each half as long (-2 % per period / per lock-step)
                 N.check(self.lib.srlx_qnet_set_dgrad_split(self.inf_online.h, 2))
+            can_pair = role == "both" and learner_replay is None and self._learner_planes and cfg.n_actions <= 8
+            if sch.forward_pair and not can_pair:
+                raise ValueError("EngineSchedule(forward_pair=True): needs the single-GPU fast lock-step with learner_planes and at most 8 actions")
+            self._forward_pair = bool(can_pair and sch.forward_pair is not False)
             if self._update_side:
                 N.check(self.lib.srlx_per_set_update_counter(self.lreplay.h_per, None))
             if fused_adam and not self.noisy and sch.fused_adam_rest:
@@ -660,25 +669,45 @@ class RainbowEngine:
             early = self.learner_replay is not None and self.role == "learner"
             if early:
                 fork_ingest(cur)
-            self._ev_t0.record(cur)
-            self.s_target.wait_event(self._ev_t0)
             on_target = (not early) and ingest is not None  # (... and on the target pass's own stream, behind that pass: -0.5 % against a stream of its own behind the online pass)
-            with torch.cuda.stream(self.s_target):  # fork: target network (rainbow.py:221) alongside the online network
-                q_tg_next = self.inf_target.forward_u8(r.obs_base, r.frame_off_next.view(B * n, cfg.window_length))
-                self._ev_t1.record(self.s_target)
-                if on_target:
+            q_pair = None
+
+            def fork_add():  # the lagged tree add alone on the target stream (draw -> add -> write-back: the write-back waits for _ev_ingested)
+                self._ev_t0.record(cur)
+                self.s_target.wait_event(self._ev_t0)
+                with torch.cuda.stream(self.s_target):
                     ingest()
                     self._ev_ingested.record(self.s_target)
-            q_all = self.inf_online.forward_u8(r.obs_base, r.frame_off_all.view(B * (n + 1), cfg.window_length))
-            if not early and not on_target:
-                fork_ingest(cur)
+
+            if self._forward_pair:
+                # both passes as one chain of three launches on this stream (None: outside the entry point's envelope, e.g. no published set holds the current weight)
+                q_pair = forward_pair_u8(self.inf_online, r.frame_off_all.view(B * (n + 1), cfg.window_length), self.inf_target,
+                                         r.frame_off_next.view(B * n, cfg.window_length), r.obs_base)
+                if q_pair is not None and on_target:
+                    fork_add()
+            if q_pair is not None:
+                q_all, q_tg_next = q_pair
+                self._pair_applied += 1
+            else:
+                self._ev_t0.record(cur)
+                self.s_target.wait_event(self._ev_t0)
+                with torch.cuda.stream(self.s_target):  # fork: target network (rainbow.py:221) alongside the online network
+                    q_tg_next = self.inf_target.forward_u8(r.obs_base, r.frame_off_next.view(B * n, cfg.window_length))
+                    self._ev_t1.record(self.s_target)
+                    if on_target:
+                        ingest()
+                        self._ev_ingested.record(self.s_target)
+                q_all = self.inf_online.forward_u8(r.obs_base, r.frame_off_all.view(B * (n + 1), cfg.window_length))
+                if not early and not on_target:
+                    fork_ingest(cur)
             if self.noisy:
                 # the reference evaluates q_online(s_1..s_n) (rainbow.py:220) and q_online(s_0) (model_torch.py:103) in two forward
                 # calls, i.e. under two noise draws: re-evaluate the dense layers of the s_0 rows under a fresh one
                 self.inf_online.redraw_rows(B, n + 1, out=q_all)
             q_all = q_all.view(B, n + 1, A)
             mark(2)
-            cur.wait_event(self._ev_t1)  # join before the TD kernel
+            if q_pair is None:
+                cur.wait_event(self._ev_t1)  # join before the TD kernel
             # rainbow.py:220 + model_torch.py:103: the TD arithmetic reads s_0 and s_1..s_n rows straight out of the one forward;
             # model_torch.py:107-109 without autograd: every p.grad is (over)written by the backward kernels
             if self.fast and self._update_side:

@@ -70,6 +70,8 @@ if BW:
           "[branch] priority write-back end", "[branch] conv3 weight gradient end", "[branch] conv2 weight gradient end", "[branch] fc1 weight gradient + Adam end",
           "ACTORS policy pass + environments end", "ACTORS ring commit end", "ACTORS join passed", "ACTORS add end",
           "online pass: convolutions end", "online pass: first dense layer end", "online pass: head end"]
+    if getattr(eng, "_forward_pair", False):  # EngineSchedule.forward_pair: stamps 10 / 11 / 12 sit behind the launches that carry BOTH networks' passes
+        nm[13:16] = ["online + target pass: convolutions end", "online + target pass: first dense layers end", "online + target pass: heads end"]
     for j, x in enumerate(nm):
         v = sorted(r[j] for r in bw_rows)
         print(f"  in the free-running loop: {x:44s} median {v[len(v) // 2]:7.1f} us  ({v[0]:7.1f} .. {v[-1]:7.1f})")

@@ -68,6 +68,8 @@ if eng.fast:  # the round-4 lock-step: network pass + selection | environments |
         names = ["update start", "draw + gather end", "online pass end", None, "gradients end (branches joined)", "Adam end", "publish end", None, None, None, "ACTORS: stream start", "ACTORS: policy pass + environments end", "ACTORS: ring commit end", "ACTORS: join passed"] + [None] * 2 + [
             "  head backward (TD) end", "  fc1 data gradient end", "  conv3 data gradient + fold end", "  conv2 data gradient + fold end", "  conv1 weight gradient end",
             "  [branch] priority write-back end", "  [branch] conv3 weight gradient end", "  [branch] conv2 weight gradient end", "  [branch] fc1 weight gradient + Adam end"]
+        if getattr(eng, "_forward_pair", False):  # EngineSchedule.forward_pair: one chain carries the online AND the target pass
+            names[2] = "online + target pass end"
         rec = [[] for _ in names]
         t_end = []
         for k in range(120):
