@@ -1277,6 +1277,30 @@ int srlx_seq_lane_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H, 
                          float *d_states, int64_t *d_actions, float *d_r_ext, float *d_r_int, float *d_dones, uint8_t *d_invalid, int64_t *d_actor, float *d_h_ext,
                          float *d_c_ext, float *d_h_int, float *d_c_int, void *stream);
 
+/* ---- R2D2 sequence target (srlx_r2d2.hip) -----------------------------------------------------------------------------------------------------------------
+ * R2D2's learner arithmetic after the forwards, srl/algorithms/r2d2/r2d2.py:152-209 and the per-sequence mean of :204, in one entry point:
+ *   q / q_target f32 [B][S+1][A] (online / target network over the S+1 in-sequence states), actions i32 [B][S] (0 <= a < A), mu f32 [B][S] (the acting
+ *   probabilities), rewards f32 [B][S], dones u8 [B][S] (1 = the step terminated), invalid u8 [B][S+1][A] or NULL (entry t masks the policy at step t,
+ *   :194-199; entry t + 1 masks the next-state selection, :177), weights f32 [B];
+ *   out: target f32 [B][S]; loss f32 [1] = Huber(delta 1) of target * w against q[a] * w, mean over B S; grad_q f32 [B][S+1][A] = d loss / d q, every entry
+ *   written, the last step's rows zero (:149-150); td_mean f32 [B] = mean over t of gain_t - q_t[a_t], signed (the memory takes the absolute value).
+ * Per (row, step): the selecting row is the online q[t+1] with enable_double_dqn, else q_target[t+1], invalid actions at -inf, the FIRST maximum wins
+ * (np.argmax); the value is q_target[t+1][argmax], unmasked; gain = reward on a terminal step, else reward + discount * value, with inverse_rescaling on the
+ * value before the discount and rescaling on the gain (terminal steps too) when enable_rescale.  Walking t = S-1 .. 0: target_t = gain_t + retrace * next_td;
+ * only with enable_retrace, next_td = gain_t - q_t[a_t] and retrace *= discount * (retrace_h * min(1, pi_t[a_t] / mu_t)), where pi_t is the greedy
+ * distribution over the valid actions of q_t (1 / number of maxima on a maximum, 0 elsewhere); retrace starts at 1 and is never reset inside a window;
+ * without enable_retrace next_td stays 0.
+ * The chain of every (row, step) -- gain, both rescalings, ratio, recursion, Huber term -- runs in double, as the reference's Python floats do, and is rounded
+ * to float32 on output (a row's loss term crosses to the summing launch as one float32).  Gains, argmax and pi are computed in parallel over (b, t); one
+ * thread per row walks the recursion over S values in LDS.  Two launches, no scratch, no atomics: loss and TD means are summed in a fixed order and two calls
+ * on the same inputs give the same bits.
+ * Envelope, validated before any device call (a violation returns SRLX_ERR_INVALID and srlx_last_error() names r2d2_seq_td): B 1..SRLX_SEQ_MAX_B,
+ * S 1..SRLX_SEQ_MAX_L - 1, A 1..SRLX_SEQ_MAX_A, no NULL pointer except invalid, discount and retrace_h finite and >= 0. */
+int srlx_r2d2_seq_td(int64_t batch, int seq_len, int n_actions, const float *d_q, const float *d_q_target, const int32_t *d_actions, const float *d_mu,
+                     const float *d_rewards, const uint8_t *d_dones, const uint8_t *d_invalid, const float *d_weights, double discount, double retrace_h,
+                     int enable_retrace, int enable_double_dqn, int enable_rescale, float *d_target, float *d_loss, float *d_grad_q, float *d_td_mean,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,23 @@ class TdOps:
         self._keep4 = keep + [scratch]
         return target, loss, grad, td
 
+    def r2d2_seq_td(self, q, q_target, actions, mu, rewards, dones, invalid, weights, discount, retrace_h, retrace, double_dqn, rescale):
+        """srlx_r2d2_seq_td (r2d2.py:152-209) over q [B][S + 1][A]: returns (target [B][S], loss [1], grad_q, td_mean [B] = mean_t(gain - q[a]), signed).
+        actions i32, dones u8 and invalid u8 [B][S + 1][A] or None."""
+        d = self.dev
+        B, S1, A = q.shape
+        S = S1 - 1
+        target = torch.empty((B, S), dtype=torch.float32, device=d)
+        loss = torch.empty(1, dtype=torch.float32, device=d)
+        grad = torch.empty((B, S1, A), dtype=torch.float32, device=d)
+        td = torch.empty(B, dtype=torch.float32, device=d)
+        keep = [t.detach().contiguous() if t is not None else None for t in (q, q_target, actions, mu, rewards, dones, invalid, weights)]
+        assert keep[2].dtype == torch.int32 and keep[5].dtype == torch.uint8 and (keep[6] is None or keep[6].dtype == torch.uint8)
+        N.check(self.lib.srlx_r2d2_seq_td(B, S, A, *[N.tptr(t) for t in keep], float(discount), float(retrace_h), int(retrace), int(double_dqn), int(rescale),
+                                          N.tptr(target), N.tptr(loss), N.tptr(grad), N.tptr(td), N.torch_stream_ptr()))
+        self._keep5 = keep
+        return target, loss, grad, td
+
 
 class C51Ops:
     """C51's update arithmetic on logits torch produced (csrc/srlx_c51_math.h through srlx_c51_loss), as `TdOps.huber` serves DQN's."""
