@@ -1033,7 +1033,8 @@ int srlx_agent57_gather_inputs(int64_t batch, int64_t n_envs, const int64_t *d_l
  *       extra_floats = 5: [action | reward | terminated | done | (intrinsic reward, arm, previous action, previous extrinsic reward, previous intrinsic reward) per lane].
  *   srlx_agent57_unpack_fields : the learner rank's inverse for the five fields: environment g = lane g % envs_per_record of record g / envs_per_record; they land
  *       in row (*d_position mod ring_len) of the learner's [ring slot][environment] arrays -- the slot the ring commit of the same slab writes; the position is read
- *       on the device (srlx_store_views), so the launch replays inside a captured update. */
+ *       on the device (srlx_store_views), so the launch replays inside a captured update.  Records are record_stride bytes apart: record_stride >= 30 *
+ *       envs_per_record, envs_per_record % 4 == 0 and record_stride % 4 == 0 (the float fields of every record are read as aligned floats). */
 int srlx_agent57_pack_record(int64_t n_envs, const int32_t *d_actions, const float *d_rewards, const uint8_t *d_terminated, const uint8_t *d_done, const float *d_x_r_int,
                              const int32_t *d_x_actor, const int32_t *d_x_prev_action, const float *d_x_prev_r_ext, const float *d_x_prev_r_int, uint8_t *d_record, void *stream);
 int srlx_agent57_unpack_fields(int64_t n_records, int64_t envs_per_record, const uint8_t *d_records, int64_t record_stride, const int64_t *d_position, int64_t ring_len,

@@ -513,8 +513,10 @@ int srlx_agent57_pack_record(int64_t n_envs, const int32_t *d_actions, const flo
 
 int srlx_agent57_unpack_fields(int64_t n_records, int64_t envs_per_record, const uint8_t *d_records, int64_t record_stride, const int64_t *d_position, int64_t ring_len,
                                float *d_x_r_int, int32_t *d_x_actor, int32_t *d_x_prev_action, float *d_x_prev_r_ext, float *d_x_prev_r_int, void *stream) {
-    SRLX_REQUIRE(n_records > 0 && envs_per_record > 0 && envs_per_record % 4 == 0 && d_records && record_stride >= (10 + 4 * kA57Fields) * envs_per_record && d_position &&
-                     ring_len > 0 && d_x_r_int && d_x_actor && d_x_prev_action && d_x_prev_r_ext && d_x_prev_r_int, "agent57_unpack_fields: bad argument");
+    SRLX_REQUIRE(n_records > 0 && envs_per_record > 0 && envs_per_record % 4 == 0 && d_records && record_stride >= (10 + 4 * kA57Fields) * envs_per_record &&
+                     record_stride % 4 == 0 && d_position && ring_len > 0 && d_x_r_int && d_x_actor && d_x_prev_action && d_x_prev_r_ext && d_x_prev_r_int,
+                 "agent57_unpack_fields: bad argument (envs_per_record and record_stride in multiples of 4: the float fields are read as aligned floats; "
+                 "record_stride >= 30 * envs_per_record)");
     const i64 total = n_records * envs_per_record;
     hipLaunchKernelGGL(k_a57_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, (i64)envs_per_record, d_records, (i64)record_stride, d_position,
                        (i64)ring_len, d_x_r_int, d_x_actor, d_x_prev_action, d_x_prev_r_ext, d_x_prev_r_int);

@@ -19,7 +19,7 @@ from simple_distributed_rl_amd.algorithms import agent57_light  # noqa: E402
 def test_ucb_bank_equals_the_host_controller_per_environment():
     """srlx_agent57_ucb_step vs UcbMetaController (pinned to the reference's trace in tests/test_agent57_cpu.py): E controllers, each
     fed its own episode rewards; the host controller gets the SAME uniforms through a patched `random` (epsilon draw, random arm)."""
-    from simple_distributed_rl_amd.algorithms.agent57_light import UcbMetaController
+    from agent57_kernels_reference import HostUcbBank
     from simple_distributed_rl_amd.device.agent57_light import UcbBank
 
     E, Na, window, eps, beta = 5, 4, 9, 0.2, 0.7
@@ -27,46 +27,16 @@ def test_ucb_bank_equals_the_host_controller_per_environment():
     bank = UcbBank(E, Na, window, eps, beta, dev, seed=1)
     rng = np.random.default_rng(0)
 
-    class Feed:  # the draws the kernel would make: random() < eps -> u0 ; randint -> floor(u1 * N)
-        def __init__(self):
-            self.u = None
-
-        def random(self):
-            return float(self.u[0])
-
-        def randint(self, a, b):
-            return min(int(self.u[1] * (b - a + 1)) + a, b)
-
-    import simple_distributed_rl_amd.algorithms.agent57_light as mod
-
-    feeds = [Feed() for _ in range(E)]
-    hosts = [UcbMetaController(Na, window, eps, beta, tie_break=None) for _ in range(E)]
+    hosts = HostUcbBank(E, Na, window, eps, beta)  # the Feed / tie_break arrangement: tests/agent57_kernels_reference.py
     got_rows, want_rows = [], []
-    saved = mod.random
-    try:
-        last = np.zeros(E, np.float32)
-        for it in range(60):
-            done = (rng.random(E) < 0.7).astype(np.uint8) if it > 0 else np.ones(E, np.uint8)
-            u = rng.random((E, 3))
-            arms = bank.step(torch.as_tensor(done, device=dev), torch.as_tensor(last, device=dev), torch.as_tensor(u, device=dev)).cpu().numpy().copy()
-            for e in range(E):
-                if not done[e]:
-                    continue
-                feeds[e].u = u[e]
-                mod.random = feeds[e]
-
-                def tie(vals, _u=u[e]):
-                    best = max(vals)
-                    idx = [i for i, v in enumerate(vals) if v == best]
-                    return idx[min(int(_u[2] * len(idx)), len(idx) - 1)]
-
-                hosts[e].tie_break = tie
-                hosts[e].next_actor(float(last[e]))
-            got_rows.append(arms)
-            want_rows.append(np.array([h.actor_index for h in hosts]))
-            last = rng.integers(-3, 4, E).astype(np.float32)  # small integers: ties between arms do occur
-    finally:
-        mod.random = saved
+    last = np.zeros(E, np.float32)
+    for it in range(60):
+        done = (rng.random(E) < 0.7).astype(np.uint8) if it > 0 else np.ones(E, np.uint8)
+        u = rng.random((E, 3))
+        arms = bank.step(torch.as_tensor(done, device=dev), torch.as_tensor(last, device=dev), torch.as_tensor(u, device=dev)).cpu().numpy().copy()
+        got_rows.append(arms)
+        want_rows.append(hosts.step(done, last, u))
+        last = rng.integers(-3, 4, E).astype(np.float32)  # small integers: ties between arms do occur
     np.testing.assert_array_equal(np.array(got_rows), np.array(want_rows))
     assert int(bank.n_recent.max()) == window - 1  # the window slid
 

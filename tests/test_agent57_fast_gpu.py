@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from agent57_kernels_reference import _emb_tail_torch
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -130,15 +132,6 @@ def test_hidden_layer_handle_with_layernorm_against_float64():
     r128 = copy.deepcopy(net128).double().cpu()
     want3 = torch.nn.functional.layer_norm(r128(stack), (128,), r128.tail[0], r128.tail[1], 1e-5)
     _close(torch, out3, want3.detach(), what="layernorm")
-
-
-def _emb_tail_torch(torch, emb, actions, params, A):
-    w1, b1, lw, lb, w2, b2 = params
-    x = torch.cat([emb[0::2], emb[1::2]], dim=1)
-    h = torch.relu(x @ w1.t() + b1)
-    y = torch.nn.functional.layer_norm(h, (h.shape[1],), lw, lb, 1e-5)
-    p = torch.softmax(y @ w2.t() + b2, dim=1)
-    return torch.nn.functional.mse_loss(p, torch.eye(A, dtype=p.dtype)[actions.long()])
 
 
 def _run_emb_tail(N, lib, torch, emb, actions, params, lr, steps_taken, adam=True):
