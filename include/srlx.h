@@ -1302,6 +1302,52 @@ int srlx_r2d2_seq_td(int64_t batch, int seq_len, int n_actions, const float *d_q
                      int enable_retrace, int enable_double_dqn, int enable_rescale, float *d_target, float *d_loss, float *d_grad_q, float *d_td_mean,
                      void *stream);
 
+/* ---- R2D2 lane sequence ring (srlx_seqstore.hip) ------------------------------------------------------------------------------------------------------------
+ * The actor side and the sequence replay of E lock-stepped R2D2 lanes (device/sequence_store.py: R2D2LaneStore; device/r2d2.py).  Three stateless entry points on
+ * arrays the CALLER owns; no atomics, no LDS, plain vector stores, launched on the stream they are given.
+ *
+ * srlx_r2d2_policy: per row e, funcs.calc_epsilon_greedy_probs followed by funcs.random_choice_by_probs (srl/rl/functions.py:183-214, r2d2.py:283-291), in
+ * double as the reference's Python floats.  q f32 [E][A], eps f32 [E], u f64 [E] in [0, 1), invalid u8 [E][A] or NULL (a byte != 0 marks an invalid action);
+ * out: actions i32 [E], mu f32 [E].  Over the valid actions: q_max and n_max compare the float32 values; p_a = eps / n_valid, plus (1 - eps) / n_max on a
+ * maximum; total = sum of p_a in action order; r = u * total; the action is the first valid a with r <= acc (acc the running sum in action order);
+ * mu = (float)p_a.  Two departures from the reference: invalid actions (weight 0) are skipped by the walk (the reference returns action 0 at u = 0 whether or
+ * not it is valid), and a row with no valid action yields action 0 and mu 1 (the reference divides by zero).  One work-item per row.
+ * Envelope: n_envs 1..SRLX_SEQ_MAX_LANES, n_actions 1..SRLX_SEQ_MAX_A, no NULL pointer but invalid.
+ *
+ * The ring, position t of all lanes in row t % T:
+ *   ring_frames  f32 [T][E][frame_stride]: the observation o_p of (position, lane); frame_stride >= frame_elems, a multiple of 4 floats for 16-byte rows
+ *   ring_scalars i32 [T][E][8]: action i32, mu f32, reward f32, done i32 (0 / 1), age i32, three zero dwords: the transition that led INTO o_p (done = the
+ *                step terminated); age = steps since the lane's episode began, 0 on the episode's first observation
+ *   ring_invalid u8  [T][E][A]: the invalid-action mask OF o_p
+ *   ring_hidden  f32 [T][E][2][H]: h, c as they were BEFORE the network consumed o_p
+ * srlx_r2d2_lane_push writes position t of all E lanes in one launch: frames f32 [E][frame_elems], action i32 [E], mu / reward f32 [E], done u8 [E], invalid u8
+ * [E][A] (NULL: none), h / c f32 [E][H], first u8 [E].  A lane with first[e] != 0 (and every lane at t = 0) delivers an episode's first observation: the entry
+ * keeps the frame AND the invalid mask and otherwise reads like the padding before an episode -- a keyed pad action, mu = (float)(1.0 / A), reward 0, done 0,
+ * zero recurrent state, age 0.  Every other lane gets age = age[t - 1] + 1, read from the ring.
+ * srlx_r2d2_lane_gather turns B descriptors (i64 [B][3]: lane e, absolute position t of the window's last real entry, flush offset k in 0..S-1) into the tensors
+ * of r2d2.SequenceBatch (L = burnin + S + 1): states f32 [B][L][frame_elems], actions i32 [B][S], probs / rewards f32 [B][S], dones u8 [B][S], invalid u8
+ * [B][S+1][A], h / c f32 [B][H].  Entry l of window (e, t, k) is lane position p = t - (L - 1) + l + k:
+ *   p > t               (after the end)            zero frame; pad action, mu (float)(1.0 / A), reward 0, done 1; no invalid action
+ *   t - p > age[t][e]   (before the episode start) zero frame; pad action, mu (float)(1.0 / A), reward 0, done 0; no invalid action; at l = 0 zero recurrent state
+ *   otherwise           the ring's entry of position p (an episode's first position carries its pad transition, real frame and real mask from the push)
+ * with pad action = rng_u64(seed, e, p) % A (the key of the Agent57 ring).  The S transition fields are entries L-S..L-1, the S + 1 masks entries L-S-1..L-1, and
+ * (h, c) are entry 0's.  A descriptor outside e in [0, E), t >= 0, 0 <= k < S reads nothing and yields zeros.  A position is reduced mod T only once it is
+ * known to be >= 0.  That position p is still in the ring is the caller's ledger's business; a stale one reads other data, never other memory.
+ * Rows move as 16-byte accesses when frame_elems and frame_stride are multiples of 4 and both frame pointers are 16-byte aligned, as dwords otherwise (per
+ * launch); several loads are in flight before the first store.  Envelope, validated before any device call (SRLX_ERR_INVALID, srlx_last_error() names the entry
+ * point): B, L, S, A, H, frame_elems, frame_stride as srlx_seq_gather; E 1..SRLX_SEQ_MAX_LANES; T >= L (push: >= 2) with T * E <= 2^31-1; t >= 0; no NULL
+ * pointer but push's invalid. */
+int srlx_r2d2_policy(int64_t n_envs, int64_t n_actions, const float *d_q, const float *d_eps, const double *d_u, const uint8_t *d_invalid, int32_t *d_actions,
+                     float *d_mu, void *stream);
+int srlx_r2d2_lane_push(int64_t E, int64_t A, int64_t H, int64_t frame_elems, int64_t frame_stride, int64_t T, int64_t t, uint64_t seed, const float *d_frames,
+                        const int32_t *d_action, const float *d_mu, const float *d_reward, const uint8_t *d_done, const uint8_t *d_invalid, const float *d_h,
+                        const float *d_c, const uint8_t *d_first, float *d_ring_frames, int32_t *d_ring_scalars, uint8_t *d_ring_invalid, float *d_ring_hidden,
+                        void *stream);
+int srlx_r2d2_lane_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H, int64_t E, int64_t T, int64_t frame_elems, int64_t frame_stride, uint64_t seed,
+                          const int64_t *d_desc, const float *d_ring_frames, const int32_t *d_ring_scalars, const uint8_t *d_ring_invalid,
+                          const float *d_ring_hidden, float *d_states, int32_t *d_actions, float *d_probs, float *d_rewards, uint8_t *d_dones, uint8_t *d_invalid,
+                          float *d_h, float *d_c, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

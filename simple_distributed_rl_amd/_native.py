@@ -263,6 +263,9 @@ SIGNATURES = {
     "srlx_seq_lane_push": (c_int, [c_i64] * 7 + [c_u64] + [c_p] * 17),
     "srlx_seq_lane_gather": (c_int, [c_i64] * 9 + [c_u64] + [c_p] * 17),
     "srlx_r2d2_seq_td": (c_int, [c_i64, c_int, c_int] + [c_p] * 8 + [c_f64, c_f64, c_int, c_int, c_int] + [c_p] * 5),
+    "srlx_r2d2_policy": (c_int, [c_i64, c_i64] + [c_p] * 7),
+    "srlx_r2d2_lane_push": (c_int, [c_i64] * 7 + [c_u64] + [c_p] * 14),
+    "srlx_r2d2_lane_gather": (c_int, [c_i64] * 9 + [c_u64] + [c_p] * 14),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

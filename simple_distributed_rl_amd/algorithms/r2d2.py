@@ -12,7 +12,8 @@ Network: in_block per step -> LSTM -> dueling head per step (r2d2.py:27-57).  "K
 Trainer: the batch goes to the GPU once, burn-in of both networks and the target pass without grad, one online pass with grad, then ONE libsrlx entry point
 for everything after the forwards (`srlx_r2d2_seq_td`: masked double-DQN gains, value rescaling, retrace with the stored acting probability, the backward
 target recursion, the Huber loss, its gradient seeds and the per-sequence mean TD error); torch back-propagates the seeds and takes the Adam step.
-Worker: the reference's host logic, one environment.  There is no device engine for R2D2 (device/vector_runner.py:engine_kind is None for it)."""
+Worker: the reference's host logic, one environment.  The E-lane device engine is device/r2d2.py, taken by `Runner.train()` only under
+set_vector_envs(n); device/vector_runner.py:engine_kind stays None for R2D2."""
 import random
 from dataclasses import dataclass, field
 from typing import Any, List, Optional

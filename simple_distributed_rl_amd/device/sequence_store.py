@@ -10,7 +10,8 @@ outside the contract (the later windows that share the object keep the snapshot)
 objects and has the same exposure, in the other direction (there every stored window would change).
 
 The E-lane engine (device/agent57.py) has a store of its own below: `LaneLedger` / `LaneSequenceStore` keep every per-step field once in time-major
-rings `[T][E]`, and a window is a view of them (`srlx_seq_lane_push`, `srlx_seq_lane_gather`)."""
+rings `[T][E]`, and a window is a view of them (`srlx_seq_lane_push`, `srlx_seq_lane_gather`).  `R2D2LaneStore` (device/r2d2.py) is the same
+ring with R2D2's fields over the same ledger (`srlx_r2d2_lane_push`, `srlx_r2d2_lane_gather`)."""
 from typing import Any, List, Optional
 
 import numpy as np
@@ -364,24 +365,44 @@ class LaneLedger:
     position t of the window's last real entry, flush offset k).
 
     Order: serials follow the lock-steps, lane-major within a lock-step; within a lane the step's window (k = 0) comes first, then, when the step ended the
-    episode, its L - 1 flush windows (k = 1..L-1) -- the order `agent57.Worker.on_step` adds them in.  A lane that is `first` in a lock-step (it only delivers
+    episode, its flush windows (k = 1..L-1 by default) -- the order `agent57.Worker.on_step` adds them in.  A lane that is `first` in a lock-step (it only delivers
     a new episode's first frame) emits nothing.
 
     Invariant: no live window (one of the last `seq_capacity` serials) references a ring position that has been overwritten.  Window (e, t, k) references the
     positions max(t - (L - 1) + k, t - age[t][e]) .. t; position t sits in row t % T and is overwritten by push t + T.  `push` refuses (LedgerError, before
     anything is changed) a lock-step that would overwrite a position one of the live windows references.
 
-    Ring length: a lane emits at least W - 1 windows in any W consecutive lock-steps (an episode of n steps takes n + 1 lock-steps and emits n + L - 1 >= n + 1
-    windows; only a trailing unfinished episode of j lock-steps emits j - 1), so E lanes emit at least E (W - 1).  If the oldest live window was emitted at
-    lock-step t0 and the ring is now at lock-step t, the windows of lock-steps t0 + 1 .. t are all live and fewer than seq_capacity: E (t - t0 - 1) <
-    seq_capacity, so t - t0 <= ceil(seq_capacity / E).  That window references positions >= t0 - (L - 1), and push t + 1 overwrites position t + 1 - T:
-    T >= ceil(seq_capacity / E) + L + 1 is enough, and the default ceil(seq_capacity / E) + 2 L leaves L - 1 rows of slack."""
+    Flush windows: `flush` is the number of windows a lane emits after the step that ended its episode, k = 1..flush.  The default is L - 1 (Agent57's worker
+    shifts the whole window out); R2D2 passes sequence_length - 1 (`r2d2.Worker.on_step` flushes len(recent_rewards) - 1 times), which is 0 at S = 1.
 
-    def __init__(self, n_lanes: int, seq_capacity: int, window: int, ring_len: Optional[int] = None):
+    Ring length, for a flush count F.  Let w be the oldest live window, emitted at lock-step t0 by lane e0 with flush offset k0, and let the ring be at
+    lock-step t = t0 + D.  w references positions >= t0 - (L - 1 - k0), and push t + 1 overwrites position t + 1 - T, which must be older:
+    T >= D + L - k0 + 1.  Every window emitted after w up to lock-step t is live next to it, so there are at most seq_capacity - 1 = C - 1 of them; how large
+    D - k0 can get is a question of how FEW windows a stream can emit after w.  An episode of n >= 1 steps takes n + 1 lock-steps (the one that delivers its
+    first frame, then its steps) and emits n + F windows; serials are lane-major within a lock-step, so the other lanes' windows of t0 come after w only for
+    the lanes behind e0: the fewest follow when e0 is the last lane.
+      F >= 1: an episode emits at least as many windows as it takes lock-steps, so a lane emits at least D - 1 windows in lock-steps t0 + 1 .. t, and D - 1
+              only if it is `first` at t0 + 1, that is, if its step at t0 ended an episode.  For lane e0 itself that costs the F - k0 >= 1 flush windows behind
+              w, more than the one window it saves, and a later k0 lowers D - k0; so k0 = 0, lane e0 plays on (D windows), the other E - 1 lanes end an
+              episode at t0 (D - 1 each): (E - 1)(D - 1) + D <= C - 1, D <= floor((C - 2) / E) + 1.
+      F = 0:  a lane is never `first` in two consecutive lock-steps (an episode has at least one step), so it emits at least floor(D / 2) windows in lock-steps
+              t0 + 1 .. t, reached by episodes of one step behind an episode that ended at t0, which costs lane e0 nothing here:
+              E floor(D / 2) <= C - 1, floor(D / 2) <= floor((C - 1) / E) = c - 1 with c = ceil(C / E), D <= 2 c - 1.
+    So
+      F >= 1: T >= floor((C - 2) / E) + L + 2         F = 0: T >= 2 c + L
+    is enough and is reached (`min_ring_len`): by a last lane that plays one long episode while the others end an episode of at least L - 1 steps together,
+    and for F = 0 by lanes that end such an episode together and then play episodes of one step.  floor((C - 2) / E) + 1 <= c, so c + L + 1 rows are enough
+    for every F >= 1 (one more than needed when E divides C - 1); the default adds L - 1 rows to that: c + 2 L, and 2 c + 2 L - 1 at F = 0."""
+
+    def __init__(self, n_lanes: int, seq_capacity: int, window: int, ring_len: Optional[int] = None, flush: Optional[int] = None):
         self.E, self.seq_capacity, self.L = int(n_lanes), int(seq_capacity), int(window)
-        if self.E < 1 or self.L < 2 or self.seq_capacity < self.E * self.L:
-            raise ValueError(f"LaneLedger: lanes {n_lanes} >= 1, window {window} >= 2 and seq_capacity {seq_capacity} >= lanes * window (one lock-step's windows) required")
-        self.ring_len = self.default_ring_len(self.E, self.seq_capacity, self.L) if ring_len is None else int(ring_len)
+        self.flush = self.L - 1 if flush is None else int(flush)
+        if not 0 <= self.flush <= self.L - 1:
+            raise ValueError(f"LaneLedger: flush count {flush} outside 0..window - 1 = {self.L - 1}")
+        if self.E < 1 or self.L < 2 or self.seq_capacity < self.E * (1 + self.flush):
+            raise ValueError(f"LaneLedger: lanes {n_lanes} >= 1, window {window} >= 2 and seq_capacity {seq_capacity} >= lanes * {'window' if flush is None else '(1 + flush)'} "
+                             "(one lock-step's windows) required")
+        self.ring_len = self.default_ring_len(self.E, self.seq_capacity, self.L, self.flush) if ring_len is None else int(ring_len)
         if self.ring_len < self.L:
             raise ValueError(f"LaneLedger: ring_len {self.ring_len} below the window {self.L}")
         self.t = 0  # lock-steps pushed so far = the next position
@@ -393,16 +414,24 @@ class LaneLedger:
         self._e, self._t, self._k, self._lo = (np.zeros(C, np.int64) for _ in range(4))  # per serial % seq_capacity; _lo: the oldest position the window references
 
     @staticmethod
-    def default_ring_len(n_lanes: int, seq_capacity: int, window: int) -> int:
-        return -(-int(seq_capacity) // int(n_lanes)) + 2 * int(window)
+    def min_ring_len(n_lanes: int, seq_capacity: int, window: int, flush: Optional[int] = None) -> int:
+        """The shortest ring that never refuses an in-order stream (the class docstring's derivation); `flush` None: window - 1."""
+        E, C, L = int(n_lanes), int(seq_capacity), int(window)
+        span = (C - 2) // E + 1 if flush is None or int(flush) >= 1 else 2 * -(-C // E) - 1
+        return span + L + 1
+
+    @staticmethod
+    def default_ring_len(n_lanes: int, seq_capacity: int, window: int, flush: Optional[int] = None) -> int:
+        c = -(-int(seq_capacity) // int(n_lanes))
+        return (c if flush is None or int(flush) >= 1 else 2 * c - 1) + 2 * int(window)
 
     def is_live(self, serial: int) -> bool:
         return self.serial - self.seq_capacity <= serial < self.serial
 
     def window_counts(self, first, done) -> np.ndarray:
-        """Windows each lane emits in a lock-step: 1 per stepping lane, + L - 1 when its step ended the episode, 0 for `first` lanes."""
+        """Windows each lane emits in a lock-step: 1 per stepping lane, + `flush` (L - 1 by default) when its step ended the episode, 0 for `first` lanes."""
         first, done = np.asarray(first, bool), np.asarray(done, bool)
-        return np.where(first, 0, 1 + done * (self.L - 1)).astype(np.int64)
+        return np.where(first, 0, 1 + done * self.flush).astype(np.int64)
 
     def push(self, first) -> int:
         """Claims the next ring position for a lock-step whose `first` lanes (bool [E]) only deliver a new episode's first frame; returns the position."""
@@ -424,7 +453,7 @@ class LaneLedger:
                 s = oldest + int(np.argmax(lo <= gone))
                 raise LedgerError(f"LaneLedger: lock-step {t} would overwrite position {gone}, which live window {s} (lane {self._e[s % C]}, position "
                                   f"{self._t[s % C]}, flush {self._k[s % C]}) still references (ring of {self.ring_len} rows, {C} live windows of {self.L} entries, "
-                                  f"{self.E} lanes; {self.default_ring_len(self.E, C, self.L)} rows never refuse)")
+                                  f"{self.E} lanes; {self.default_ring_len(self.E, C, self.L, self.flush)} rows never refuse)")
         self.age = np.where(first, 0, self.age + 1)
         self._first = first
         self.t = t + 1
@@ -562,3 +591,112 @@ class LaneSequenceStore:
     def backup(self) -> dict:
         raise RuntimeError("lane store: the lane ring has no backup format yet (its windows are views of rings the running lanes still write); back up a "
                            "'host' memory or the plugin's device store instead")
+
+
+class R2D2LaneStore:
+    """R2D2's lane ring in HBM (srlx.h, "R2D2 lane sequence ring"): frames [T][E][stride] float32, scalars [T][E][8] int32 (action, mu, reward,
+    done, age), invalid masks [T][E][A] uint8 of each position's OWN observation, recurrent vectors [T][E][2][H] float32, and a `LaneLedger` with
+    sequence_length - 1 flush windows.  `push` is one `srlx_r2d2_lane_push` launch and `gather` one `srlx_r2d2_lane_gather` launch on torch's current stream,
+    so pushes and gathers issued on one stream are ordered; neither synchronises.  `gather` returns an `r2d2.SequenceBatch`."""
+
+    def __init__(self, device, n_lanes: int, seq_capacity: int, window: int, sequence_length: int, n_actions: int, units: int, frame_shape, seed: int = 0,
+                 ring_len: Optional[int] = None):
+        import torch
+
+        from simple_distributed_rl_amd import _native as N
+        from simple_distributed_rl_amd.algorithms._device_ops import require_gpu
+
+        self.device = require_gpu(str(device))
+        self._N, self._lib = N, N.lib()
+        self.frame_shape = tuple(int(d) for d in frame_shape)
+        self.frame_elems = int(np.prod(self.frame_shape, dtype=np.int64))
+        self.stride = _round4(self.frame_elems)
+        self.L, self.S, self.A, self.H = int(window), int(sequence_length), int(n_actions), int(units)
+        if self._lib.srlx_seq_record_dwords(self.L, self.S, self.A, self.H) < 0:  # (host arithmetic: the SRLX_SEQ_MAX_* envelope the R2D2 gather shares)
+            raise ValueError(f"r2d2 lane store: window {self.L}, sequence {self.S}, actions {self.A}, units {self.H} are outside srlx_r2d2_lane_gather's envelope (srlx.h)")
+        if not 1 <= self.frame_elems <= 1 << 20:
+            raise ValueError(f"r2d2 lane store: a frame of {self.frame_elems} elements is outside srlx_r2d2_lane_gather's envelope (1..2^20)")
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.ledger = LaneLedger(n_lanes, seq_capacity, self.L, ring_len, flush=self.S - 1)
+        T, E, d = self.ledger.ring_len, self.ledger.E, self.device
+        if E > 65536 or T * E > 2**31 - 1:
+            raise ValueError(f"r2d2 lane store: {T} rows of {E} lanes are outside srlx_r2d2_lane_gather's envelope (E <= 65536, T * E <= 2^31-1)")
+        self.frames = torch.empty((T, E, self.stride), dtype=torch.float32, device=d)
+        self.scalars = torch.zeros((T, E, 8), dtype=torch.int32, device=d)
+        self.invalid = torch.zeros((T, E, self.A), dtype=torch.uint8, device=d)
+        self.hidden = torch.zeros((T, E, 2, self.H), dtype=torch.float32, device=d)
+        self.any_invalid = False  # whether any push has carried an invalid-action mask
+
+    @staticmethod
+    def ring_bytes(n_lanes: int, seq_capacity: int, window: int, sequence_length: int, n_actions: int, units: int, frame_elems: int,
+                   ring_len: Optional[int] = None) -> int:
+        """HBM bytes of the four rings (host arithmetic)."""
+        T = LaneLedger.default_ring_len(n_lanes, seq_capacity, window, int(sequence_length) - 1) if ring_len is None else int(ring_len)
+        return T * int(n_lanes) * (4 * _round4(frame_elems) + 32 + int(n_actions) + 8 * int(units))
+
+    def push(self, frames, action, mu, reward, done, h, c, first, first_dev=None, invalid=None) -> int:
+        """One lock-step of all lanes: device tensors frames float32 [E, ...], action int32 [E], mu / reward float32 [E], done uint8 [E] (the step terminated),
+        h / c float32 [E][H] as they were before the network consumed `frames`, `first` a host bool [E] (`first_dev`: the same mask as device uint8, uploaded
+        here when not given), `invalid` uint8 [E][A] (the masks of `frames`) or None.  Returns the position; `emit(done)` then names the windows."""
+        import torch
+
+        N, led = self._N, self.ledger
+        E, A, H = led.E, self.A, self.H
+        first = np.asarray(first, bool).reshape(-1)
+        want = {"frames": (torch.float32, E * self.frame_elems), "action": (torch.int32, E), "mu": (torch.float32, E), "reward": (torch.float32, E),
+                "done": (torch.uint8, E), "h": (torch.float32, E * H), "c": (torch.float32, E * H)}
+        got = dict(frames=frames, action=action, mu=mu, reward=reward, done=done, h=h, c=c)
+        for k, (dt, n) in want.items():
+            v = got[k]
+            if v.dtype != dt or v.numel() != n or not v.is_contiguous() or v.device != self.device:
+                raise ValueError(f"r2d2 lane store: push argument {k} must be a contiguous {dt} tensor of {n} elements on {self.device}")
+        if invalid is not None and (invalid.dtype != torch.uint8 or invalid.numel() != E * A or not invalid.is_contiguous() or invalid.device != self.device):
+            raise ValueError(f"r2d2 lane store: push argument invalid must be a contiguous uint8 tensor of {E * A} elements on {self.device}")
+        t = led.push(first)  # (refuses before anything is written)
+        if first_dev is None:
+            first_dev = torch.from_numpy(first.astype(np.uint8)).to(self.device)
+        self._keep_push = (got, first_dev, invalid)  # alive until the stream has run the launch
+        self.any_invalid = self.any_invalid or invalid is not None
+        N.check(self._lib.srlx_r2d2_lane_push(E, A, H, self.frame_elems, self.stride, led.ring_len, t, self.seed, N.tptr(frames), N.tptr(action), N.tptr(mu),
+                                              N.tptr(reward), N.tptr(done), N.tptr(invalid), N.tptr(h), N.tptr(c), N.tptr(first_dev), N.tptr(self.frames),
+                                              N.tptr(self.scalars), N.tptr(self.invalid), N.tptr(self.hidden), N.torch_stream_ptr()))
+        return t
+
+    def emit(self, done) -> np.ndarray:
+        return self.ledger.emit(done)
+
+    def gather_serials(self, serials):
+        return self.gather(self.ledger.descriptors(serials))
+
+    def gather(self, descriptors):
+        """descriptors: int64 [B][3] (lane, position, flush offset), host or device -> r2d2.SequenceBatch (`invalid_actions` None while no push has carried a
+        mask, as `SequenceBatch.from_items` returns None when no item has an invalid action)."""
+        import torch
+
+        from simple_distributed_rl_amd.algorithms.r2d2 import SequenceBatch as R2D2Batch
+
+        d = self.device
+        desc = torch.as_tensor(np.ascontiguousarray(descriptors, dtype=np.int64) if not torch.is_tensor(descriptors) else descriptors).to(d).contiguous()
+        if desc.dim() != 2 or desc.shape[1] != 3 or desc.shape[0] < 1 or desc.dtype != torch.int64:
+            raise ValueError("r2d2 lane store: descriptors are int64 [B][3] with B >= 1")
+        B, L, S, A, H = int(desc.shape[0]), self.L, self.S, self.A, self.H
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=d)  # noqa: E731
+        out = dict(states=f32(B, L, *self.frame_shape), actions=torch.empty((B, S), dtype=torch.int32, device=d), probs=f32(B, S), rewards=f32(B, S),
+                   dones=torch.empty((B, S), dtype=torch.uint8, device=d), invalid=torch.empty((B, S + 1, A), dtype=torch.uint8, device=d), h=f32(1, B, H), c=f32(1, B, H))
+        self.gather_into(desc, out)
+        self._keep = desc  # alive until the stream has run the launch
+        return R2D2Batch(states=out["states"], actions=out["actions"], probs=out["probs"], rewards=out["rewards"], dones=out["dones"],
+                         invalid_actions=out["invalid"] if self.any_invalid else None, hidden_states=(out["h"], out["c"]))
+
+    GATHER_OUTPUTS = ("states", "actions", "probs", "rewards", "dones", "invalid", "h", "c")
+
+    def gather_into(self, desc, out: dict) -> None:
+        """The launch alone: `desc` int64 [B][3] on the device, `out` the eight output tensors by `GATHER_OUTPUTS`' names."""
+        N, led = self._N, self.ledger
+        N.check(self._lib.srlx_r2d2_lane_gather(int(desc.shape[0]), self.L, self.S, self.A, self.H, led.E, led.ring_len, self.frame_elems, self.stride, self.seed,
+                                                N.tptr(desc), N.tptr(self.frames), N.tptr(self.scalars), N.tptr(self.invalid), N.tptr(self.hidden),
+                                                *[N.tptr(out[k]) for k in self.GATHER_OUTPUTS], N.torch_stream_ptr()))
+
+    def backup(self) -> dict:
+        raise RuntimeError("r2d2 lane store: the lane ring has no backup format yet (its windows are views of rings the running lanes still write); back up a "
+                           "plugin-path memory instead")

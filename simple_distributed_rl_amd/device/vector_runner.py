@@ -132,7 +132,7 @@ class HostVecEnv:
             self._host_raw = torch.zeros((n_envs,) + self._raw_shape, dtype=torch.uint8).pin_memory()
             self.F = int(processor._out_hw[0] * processor._out_hw[1])
         else:
-            self.F = int(np.prod(sp.shape))
+            self.F = int(np.prod(sp.shape)) if hasattr(sp, "shape") else int(sp.size)  # (an ArrayDiscreteSpace, Grid's, has a size and no shape)
         self._scale = 255.0 if float(np.max(sp.high)) <= 1.0 else 1.0  # "0to1" frames (image_processor.py:140-142) back to bytes
         obs_dtype = torch.float32 if self.float_obs else torch.uint8
         self._host_obs = torch.zeros((n_envs, self.F), dtype=obs_dtype).pin_memory()
@@ -707,6 +707,51 @@ def why_not_agent57_engine(env, rl_config, n_envs=None) -> str:
     return "; ".join(why)
 
 
+R2D2_MP_REASON = "R2D2 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
+
+
+def why_not_r2d2_engine(env, rl_config, n_envs=None) -> str:
+    """Empty string when `R2D2Engine` (device/r2d2.py) can run this r2d2.Config on this environment; otherwise EVERY reason it cannot, joined
+    with "; " (as `why_not_agent57_engine`).  The envelope figures are srlx_r2d2_lane_gather's (srlx.h: SRLX_SEQ_MAX_*) and SrlxLstm's.  `n_envs`: the lane
+    count of set_vector_envs(n), when the caller has one: the reasons that depend on it are then part of the answer.  `engine_kind` stays None for R2D2: the
+    Runner asks this question on its own, ahead of `why_not_vector`, and only under an explicit lane count."""
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+
+    c, why = rl_config, []
+    if c.get_name() != "R2D2":
+        return f"'{c.get_name()}' is not an r2d2.Config"
+    if not str(c.used_device_torch).startswith("cuda"):
+        why.append("the run is not on a GPU device")
+    if not isinstance(env.action_space, DiscreteSpace):
+        why.append("the engine serves discrete action spaces")
+    if env.player_num != 1:
+        why.append("multi-player environment")
+    mem = _why_not_memory(c)
+    if mem:
+        why.append(mem)
+    if c.window_length != 1:
+        why.append("the engine's network reads one observation per step (window_length 1)")
+    if getattr(c, "_obs_processors", None):
+        why.append("observation processors are served by the plugin path: the lanes hand the network the environment's float32 observation")
+    L = c.burnin + c.sequence_length + 1
+    if not 2 <= L <= 513:
+        why.append(f"the window burnin + sequence_length + 1 = {L} is outside the lane gather's 2..513")
+    n = getattr(env.action_space, "n", 0)
+    if isinstance(env.action_space, DiscreteSpace) and not 1 <= n <= 64:
+        why.append(f"{n} actions are outside the lane gather's 1..64")
+    if not 1 <= c.lstm_units <= 1024:
+        why.append(f"{c.lstm_units} recurrent units are outside the lane gather's 1..1024")
+    if c.batch_size > 1024:
+        why.append(f"a batch of {c.batch_size} is outside the lane gather's 1..1024")
+    if isinstance(n_envs, int) and n_envs > 0:
+        if n_envs > 256:
+            why.append(f"{n_envs} lanes: the acting pass's LSTM kernels serve at most 256 rows (srlx.h), and the engine does not fall back to nn.LSTM")
+        S = c.sequence_length
+        if n_envs * S > c.memory.capacity:
+            why.append(f"{n_envs} lanes of sequence length {S} emit up to {n_envs * S} windows in one lock-step, more than memory.capacity {c.memory.capacity} keeps")
+    return "; ".join(why)
+
+
 def frame_space(env, rl_config):
     """The observation space the algorithm sees per step: the environment's, remapped by the config's observation processors."""
     procs = getattr(rl_config, "_obs_processors", None)
@@ -1072,3 +1117,37 @@ class VectorAgent57LstmActor(VectorAgent57Actor):
     def ensure_graphs(self):
         """(the lock-step reads `done` back and the trainer is torch's eager autograd: nothing is captured)"""
         return 0
+
+
+class VectorR2D2Actor(VectorAgent57LstmActor):
+    """`Runner.train()` with R2D2 on a GPU under set_vector_envs(n): n lanes of `R2D2Engine` (device/r2d2.py), which steps host environments with float32
+    observations and their invalid-action masks and trains the Runner's Parameter in place with the plugin's own trainer."""
+
+    def _make_batch_env(self, ring, context):
+        from simple_distributed_rl_amd.device.r2d2 import MaskedHostVecEnv
+
+        env = MaskedHostVecEnv(self.env_run.config, self.lanes, ring.dev, context.seed, float_obs=True)
+        env.setup(context)
+        return env
+
+    def _make_engine(self, context, device: int, seed: int):
+        from simple_distributed_rl_amd.device.r2d2 import R2D2Engine
+
+        return R2D2Engine(self.rl_config, self.lanes, device, seed=seed, env=lambda ring: self._make_batch_env(ring, context), parameter=self.parameter,
+                          context=context)
+
+    def _set_mode(self, context):
+        assert context.training, "R2D2Engine only trains: evaluate / rollout stay on the plugin path"
+
+
+class VectorR2D2Learner(VectorLearner):
+    """`VectorLearner` that stops at the run's `max_train_count`: a lock-step of n lanes owes n updates, and the plugin path's run ends on the update that
+    reaches the budget, not on the lock-step that crosses it."""
+
+    def open(self, context, state):
+        self._budget = int(context.max_train_count) if context.max_train_count > 0 else None
+
+    def update(self, count: int, state) -> int:
+        if self._budget is not None and state is not None:
+            count = min(count, self._budget - state.train_count)
+        return super().update(count, state) if count > 0 else 0

@@ -120,6 +120,16 @@ class Runner:
             return None
         from simple_distributed_rl_amd.device import vector_runner as vr
 
+        # R2D2's engine (device/r2d2.py) is asked for on its own, ahead of `why_not_vector`, and only under an explicit lane count: `engine_kind` is None for
+        # R2D2, so "AUTO" and every other caller keep the plugin path and its reason
+        if self.rl_config.get_name() == "R2D2" and isinstance(self._vector_envs, int) and not isinstance(self._vector_envs, bool) and self._vector_envs > 0:
+            self.vector_reason = vr.why_not_r2d2_engine(env, self.rl_config, n_envs=self._vector_envs)
+            if self.vector_reason:
+                return None
+            actor = self._vector_actor
+            if actor is None or actor.lanes != self._vector_envs:
+                actor = self._vector_actor = vr.VectorR2D2Actor(env, self.rl_config, self.make_parameter(), self._vector_envs)
+            return actor, (vr.VectorR2D2Learner(actor) if with_learner else None)
         self.vector_reason = vr.why_not_vector(c, env, self.rl_config) or vr.auto_lanes_reason(env, self.rl_config, self._vector_envs)
         if not self.vector_reason and vr.engine_kind(self.rl_config) == "agent57":  # the reasons that depend on the lane count
             self.vector_reason = vr.why_not_agent57_engine(env, self.rl_config, n_envs=int(self._vector_envs))
@@ -228,6 +238,8 @@ class Runner:
                     self.vector_reason = vr.AGENT57_MP_REASON
                 if kind == "c51":  # (device/mp_runner.py serves the Rainbow family)
                     self.vector_reason = vr.C51_MP_REASON
+                if self.rl_config.get_name() == "R2D2" and isinstance(self._vector_envs, int) and self._vector_envs > 0:  # its engine is one process on one GPU
+                    self.vector_reason = vr.R2D2_MP_REASON
                 if not self.vector_reason:  # one process per GPU over RCCL (device/mp_runner.py); this process is the learner rank
                     from simple_distributed_rl_amd.device.mp_runner import train_mp_on_engine
 
