@@ -1348,6 +1348,45 @@ int srlx_r2d2_lane_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H,
                           const float *d_ring_hidden, float *d_states, int32_t *d_actions, float *d_probs, float *d_rewards, uint8_t *d_dones, uint8_t *d_invalid,
                           float *d_h, float *d_c, void *stream);
 
+/* ---- Discrete soft actor-critic on flat observations (srlx_sacd.hip; srl/algorithms/sac/sac_tf_discrete.py:158-243) -----------------------------
+ * Five MLPs in float32, torch layouts ([out][in] weights): the policy  state [D] -> n_policy x (Linear + ReLU) -> Linear(A)  and, four times (q1 online, q1
+ * target, q2 online, q2 target), the Q-network  concat(state [D], one-hot action [A]) -> n_q x (Linear + ReLU) -> Linear(1).
+ * Envelope, validated before any device call (SRLX_ERR_INVALID; srlx_last_error() names the entry point): D 1..256, A 2..16, each block 1..3 layers of 32..512
+ * units in multiples of 32, max_batch 1..256.  Every tensor is float32; every sum accumulates in float64 and is rounded to float32 once.
+ *   srlx_sacd_scratch_floats : floats of device scratch a handle of this shape owns; -1 outside the envelope.  Host arithmetic.
+ *   srlx_sacd_bind           : the parameter tensors by address, each network as (weight, bias) per layer in state-dict order, the networks in the order policy,
+ *                              q1 online, q1 target, q2 online, q2 target: 2 (n_policy + 1) + 4 * 2 (n_q + 1) pointers; and log_alpha (one float).
+ *   srlx_sacd_bind_grads     : the caller's gradient tensors of policy, q1 online, q2 online (same order and shapes) and of log_alpha.  Every update writes
+ *                              them before its Adam step reads them.
+ *   srlx_sacd_bind_adam      : exp_avg / exp_avg_sq of policy, q1 online, q2 online and, as the last entry, log_alpha; the optimiser steps already taken
+ *                              (host int64 [4]: policy, q1, q2, alpha; the handle counts on from there, srlx_sacd_steps reads them); torch's Adam
+ *                              (srlx_adam_math.h).  Binding again restarts an optimiser from the counts given.
+ *   srlx_sacd_update         : the whole update of one batch in five launches (states / next states f32 [B][D], actions i32 [B], rewards f32 [B], dones u8 [B]):
+ *                                0. alpha = expf(log_alpha), one value for the whole call
+ *                                1. y = r + (1 - done) discount sum_a p'[a] (min(q1_target, q2_target)(s', e_a) - alpha logp'[a]),  logp' = z' - logsumexp(z')
+ *                                2. q1, q2: loss = mean_b (y - q(s, e_a_b))^2, one Adam step each at lr_q
+ *                                3. qv[a] = min(q1, q2)(s, e_a) after step 2; p = softmax(policy(s)), L = log(clip(p, 1e-7, 1)), entropy = -sum_a p L,
+ *                                   policy_loss = mean_b sum_a p (alpha L - qv); gradient through p and L, none where the clip is active; Adam at lr_policy
+ *                                4. auto_scale: alpha_loss = -mean_b(alpha (target_entropy - entropy_b)) = d alpha_loss / d log_alpha; Adam at lr_alpha
+ *                                5. hard_sync: target = online; otherwise target = (float)(1 - tau) * target + (float)tau * online, two products and one add
+ *                              Outputs: y, q1, q2, entropy f32 [B]; scalars f32 [5] = q1_loss, q2_loss, policy_loss, alpha_loss (0 without auto_scale), alpha.
+ *                              No atomics, every sum in a fixed order: equal inputs give equal bits.
+ *   srlx_sacd_forward        : n rows of states -> logits f32 [n][A] (NULL: not wanted) and min(q1, q2)(s, e_a) f32 [n][A] (NULL: not wanted) of the online
+ *                              (target = 0) or the target (1) Q-networks.  Needs srlx_sacd_bind only. */
+typedef struct srlx_sacd srlx_sacd_t;
+int64_t srlx_sacd_scratch_floats(int obs_dim, int n_actions, int n_policy, const int *policy_widths, int n_q, const int *q_widths, int64_t max_batch);
+int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy, const int *policy_widths, int n_q, const int *q_widths, int64_t max_batch,
+                     int device);
+int srlx_sacd_destroy(srlx_sacd_t *h);
+int srlx_sacd_bind(srlx_sacd_t *h, float *const *d_params, float *d_log_alpha);
+int srlx_sacd_bind_grads(srlx_sacd_t *h, float *const *d_grads, float *d_grad_log_alpha);
+int srlx_sacd_bind_adam(srlx_sacd_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, const int64_t *steps_taken, double beta1, double beta2, double eps);
+int srlx_sacd_steps(const srlx_sacd_t *h, int64_t *steps_taken);
+int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
+                     const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
+                     double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream);
+int srlx_sacd_forward(srlx_sacd_t *h, int64_t n, const float *d_states, int target, float *d_logits, float *d_qmin, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

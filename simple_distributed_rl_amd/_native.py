@@ -266,6 +266,15 @@ SIGNATURES = {
     "srlx_r2d2_policy": (c_int, [c_i64, c_i64] + [c_p] * 7),
     "srlx_r2d2_lane_push": (c_int, [c_i64] * 7 + [c_u64] + [c_p] * 14),
     "srlx_r2d2_lane_gather": (c_int, [c_i64] * 9 + [c_u64] + [c_p] * 14),
+    "srlx_sacd_scratch_floats": (c_i64, [c_int, c_int, c_int, c_p, c_int, c_p, c_i64]),
+    "srlx_sacd_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_p, c_int, c_p, c_i64, c_int]),
+    "srlx_sacd_destroy": (c_int, [c_p]),
+    "srlx_sacd_bind": (c_int, [c_p, c_p, c_p]),
+    "srlx_sacd_bind_grads": (c_int, [c_p, c_p, c_p]),
+    "srlx_sacd_bind_adam": (c_int, [c_p, c_p, c_p, c_p, c_f64, c_f64, c_f64]),
+    "srlx_sacd_steps": (c_int, [c_p, c_p]),
+    "srlx_sacd_update": (c_int, [c_p, c_i64] + [c_p] * 5 + [c_f64] * 5 + [c_int, c_int, c_f64] + [c_p] * 6),
+    "srlx_sacd_forward": (c_int, [c_p, c_i64, c_p, c_int, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

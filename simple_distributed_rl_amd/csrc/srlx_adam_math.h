@@ -39,4 +39,14 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = p - (c.step_size * m) / denom;
 }
 
+// The same step with the roundings of torch.optim.Adam's default implementation for GPU tensors (_multi_tensor_adam: _foreach_lerp_, _foreach_mul_ +
+// _foreach_addcmul_, _foreach_sqrt / _foreach_div_ / _foreach_add_, _foreach_addcdiv_), whose kernels contract three of the multiply-adds: measured bit-equal
+// to it on the MI355X over 200 000 elements and three steps.  adam_one above is left as it is: kernels that use it are pinned bit for bit.
+__device__ __forceinline__ void adam_one_foreach(float &p, float g, float &m, float &v, const AdamCoef &c) {
+    m = fmaf(c.w1, g - m, m);
+    v = fmaf(c.w2, g * g, c.b2 * v);
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = fmaf(-c.step_size, m / denom, p);
+}
+
 }  // namespace srlx

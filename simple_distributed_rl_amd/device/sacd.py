@@ -1,0 +1,152 @@
+"""Discrete SAC's update on libsrlx (csrc/srlx_sacd.hip): `SacdUpdate` binds an `algorithms.sac.Parameter`'s own tensors by address -- the
+five networks and `log_alpha` stay what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write and
+the Adam state (moments here, step counts in the handle).  One `update` is the whole of sac_tf_discrete.py:158-243 for one batch, in five launches."""
+import ctypes
+
+import torch
+
+from simple_distributed_rl_amd import _native as N
+
+MAX_BATCH = 256
+TRAINED = ("policy", "q1_online", "q2_online")
+NETWORKS = ("policy", "q1_online", "q1_target", "q2_online", "q2_target")
+
+
+def _linear_widths(block):
+    """Widths of a block made of (Linear with bias, ReLU) pairs; None for anything else."""
+    layers = [m for m in block.hidden_layers if not isinstance(m, torch.nn.Flatten)]
+    if len(layers) % 2:
+        return None
+    widths = []
+    for lin, act in zip(layers[0::2], layers[1::2]):
+        if type(lin) is not torch.nn.Linear or lin.bias is None or type(act) is not torch.nn.ReLU:
+            return None
+        widths.append(lin.out_features)
+    return tuple(widths)
+
+
+def _int_array(values):
+    return (ctypes.c_int * max(1, len(values)))(*values)
+
+
+def shape_of(parameter):
+    """(D, A, policy widths, q widths) of a sac.Parameter, or a sentence saying why its networks are not ones the kernels run."""
+    pol, q = parameter.policy, parameter.q1_online
+    for name, net in (("policy", pol), ("q", q)):
+        w = _linear_widths(net.in_block)
+        if w is None or len(w):
+            return f"the {name} network's input_block has layers of its own (the kernels start at the observation)"
+    pw, qw = _linear_widths(pol.hidden_block), _linear_widths(q.q_block)
+    if pw is None or qw is None:
+        return "a block is not a chain of Linear (with bias) + ReLU layers"
+    D = pol.in_block.out_size
+    A = pol.out_layer.out_features
+    return D, A, pw, qw
+
+
+class SacdUpdate:
+    def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
+        reason = self.why_not(parameter, max_batch)
+        if reason:
+            raise ValueError(f"SacdUpdate: {reason}")
+        self.parameter = parameter
+        self.D, self.A, self.policy_widths, self.q_widths = shape_of(parameter)
+        self.max_batch = max_batch
+        self.device = parameter.log_alpha.device
+        self.betas, self.eps = betas, eps
+        self._lib = N.lib()
+        self._h = N.c_p()
+        N.check(self._lib.srlx_sacd_create(ctypes.byref(self._h), self.D, self.A, len(self.policy_widths), _int_array(self.policy_widths), len(self.q_widths),
+                                           _int_array(self.q_widths), max_batch, self.device.index or 0))
+        self.params = {name: list(getattr(parameter, name).parameters()) for name in NETWORKS}
+        self.grads = {name: [torch.zeros_like(p) for p in self.params[name]] for name in TRAINED}
+        self.grad_log_alpha = torch.zeros_like(parameter.log_alpha)
+        self.exp_avg = {name: [torch.zeros_like(p) for p in self.params[name]] for name in TRAINED}
+        self.exp_avg_sq = {name: [torch.zeros_like(p) for p in self.params[name]] for name in TRAINED}
+        self.alpha_exp_avg, self.alpha_exp_avg_sq = torch.zeros_like(parameter.log_alpha), torch.zeros_like(parameter.log_alpha)
+        flat = [p for name in NETWORKS for p in self.params[name]]
+        N.check(self._lib.srlx_sacd_bind(self._h, self._ptrs(flat), N.tptr(parameter.log_alpha)))
+        N.check(self._lib.srlx_sacd_bind_grads(self._h, self._ptrs([g for name in TRAINED for g in self.grads[name]]), N.tptr(self.grad_log_alpha)))
+        self._bind_adam([0, 0, 0, 0])
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.srlx_sacd_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def _ptrs(tensors):
+        return (N.c_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+    def _bind_adam(self, steps):
+        m = [t for name in TRAINED for t in self.exp_avg[name]] + [self.alpha_exp_avg]
+        v = [t for name in TRAINED for t in self.exp_avg_sq[name]] + [self.alpha_exp_avg_sq]
+        N.check(self._lib.srlx_sacd_bind_adam(self._h, self._ptrs(m), self._ptrs(v), (N.c_i64 * 4)(*steps), self.betas[0], self.betas[1], self.eps))
+
+    # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def why_not(parameter, batch: int = 1) -> str:
+        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
+        tensors = [parameter.log_alpha] + [p for name in NETWORKS for p in getattr(parameter, name).parameters()]
+        if not all(t.is_cuda for t in tensors):
+            return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)
+        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            return "a parameter is not a dense float32 tensor"
+        shape = shape_of(parameter)
+        if isinstance(shape, str):
+            return shape
+        return SacdUpdate.envelope_reason(*shape, batch)
+
+    @staticmethod
+    def envelope_reason(D, A, pw, qw, batch: int = 1) -> str:
+        """The envelope of srlx_sacd_create as a sentence ('' inside it).  Host arithmetic: no device needed."""
+        if batch > MAX_BATCH:
+            return f"batch size {batch} above max_batch {MAX_BATCH}"
+        if N.lib().srlx_sacd_scratch_floats(D, A, len(pw), _int_array(pw), len(qw), _int_array(qw), max(1, batch)) < 0:
+            return f"outside the envelope (D 1..256, A 2..16, 1..3 layers of 32..512 units in multiples of 32): D {D}, A {A}, policy {tuple(pw)}, q {tuple(qw)}"
+        return ""
+
+    @classmethod
+    def serves(cls, parameter, batch: int = 1) -> bool:
+        return cls.why_not(parameter, batch) == ""
+
+    # ---- the calls --------------------------------------------------------------------------------------------------------------------------------------
+    def steps(self):
+        """Optimiser steps taken: [policy, q1, q2, alpha]."""
+        out = (N.c_i64 * 4)()
+        N.check(self._lib.srlx_sacd_steps(self._h, out))
+        return list(out)
+
+    def reset_alpha_optimizer(self):
+        """A fresh Adam for log_alpha (sac_tf_discrete.py:170-173: rebuilt after a restore); the networks' optimisers go on."""
+        self.alpha_exp_avg.zero_()
+        self.alpha_exp_avg_sq.zero_()
+        self._bind_adam(self.steps()[:3] + [0])
+
+    def update(self, state, action, next_state, reward, done, lr_policy, lr_q, lr_alpha, hard_sync: bool, discount: float, tau: float, auto_scale: bool,
+               target_entropy: float) -> dict:
+        """state / next_state f32 [B][D], action i32 [B], reward f32 [B], done u8 [B], all on the device.  Returns y, q1, q2, entropy [B] and `scalars` [5]
+        (q1_loss, q2_loss, policy_loss, alpha_loss, alpha), device tensors; nothing synchronises."""
+        B = state.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f"SacdUpdate: batch size {B} above max_batch {self.max_batch}")
+        keep = [state.contiguous(), action.contiguous(), next_state.contiguous(), reward.contiguous(), done.contiguous()]
+        assert keep[0].dtype == torch.float32 and keep[1].dtype == torch.int32 and keep[3].dtype == torch.float32 and keep[4].dtype == torch.uint8
+        out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in ("y", "q1", "q2", "entropy")}
+        out["scalars"] = torch.empty(5, dtype=torch.float32, device=self.device)
+        N.check(self._lib.srlx_sacd_update(self._h, B, N.tptr(keep[0]), N.tptr(keep[1]), N.tptr(keep[2]), N.tptr(keep[3]), N.tptr(keep[4]), float(lr_policy), float(lr_q),
+                                           float(lr_alpha), float(discount), float(tau), int(bool(hard_sync)), int(bool(auto_scale)), float(target_entropy),
+                                           N.tptr(out["y"]), N.tptr(out["q1"]), N.tptr(out["q2"]), N.tptr(out["entropy"]), N.tptr(out["scalars"]),
+                                           N.torch_stream_ptr()))
+        self._keep = keep
+        return out
+
+    def forward(self, state, target: bool = False, want_logits: bool = True, want_q: bool = True):
+        """logits [n][A] and min(q1, q2) over every action [n][A] (None when not wanted) of the online or the target Q-networks."""
+        x = state.contiguous()
+        n = x.shape[0]
+        logits = torch.empty((n, self.A), dtype=torch.float32, device=self.device) if want_logits else None
+        qmin = torch.empty((n, self.A), dtype=torch.float32, device=self.device) if want_q else None
+        N.check(self._lib.srlx_sacd_forward(self._h, n, N.tptr(x), int(bool(target)), N.tptr(logits), N.tptr(qmin), N.torch_stream_ptr()))
+        self._keep_fwd = x
+        return logits, qmin
