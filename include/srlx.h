@@ -309,6 +309,9 @@ int srlx_image_preprocess(int64_t n_images, int src_h, int src_w, int src_channe
  *   actions int32 [B][n], rewards/terminated float32 [B][n], invalid_next uint8 [B][n][A] or NULL
  *   weights float32 [B] (IS weights)
  * outputs: target f32 [B], loss f32 [1], grad_q0 f32 [B][A], priorities f32 [B]
+ * n_step <= 32.  The n discounted terms of the target are added in numpy's order (:285 np.sum: one after another below 8 terms,
+ * 8 partial sums and then the tail from 8 up): without rescale the target is the reference's float32 result bit for bit.
+ * Without double DQN a step whose actions are ALL invalid reads -inf from the masked target net, as the reference does (:248-251).
  * ------------------------------------------------------------------------------------ */
 int srlx_nstep_td_huber_priority(int64_t batch, int n_step, int n_actions, const float *d_q_on_next,
                                  const float *d_q_tg_next, const float *d_q_on_0, const int32_t *d_actions,
@@ -338,7 +341,7 @@ int srlx_dqn_target(int64_t batch, int n_actions, const float *d_q_on_next, cons
                     float *d_target, void *stream);
 
 /* torch.optim.Adam(params, lr) .step() (srl/algorithms/rainbow/model_torch.py:71,109; dqn/model_torch.py:75,119) for up
- * to 16 float32 parameter tensors in one launch.  The four pointer arrays and numels are HOST arrays of n_tensors
+ * to 24 float32 parameter tensors in one launch.  The four pointer arrays and numels are HOST arrays of n_tensors
  * entries (device pointers, 16-byte aligned; exp_avg / exp_avg_sq are the optimizer state, zero before the first step);
  * *d_step = optimizer steps already taken (device scalar, so the call is HIP-graph replayable; the caller increments it). */
 int srlx_adam_step(int n_tensors, float *const *d_params, const float *const *d_grads, float *const *d_exp_avg,

@@ -16,6 +16,7 @@
 // the per-workgroup candidates, evaluates the pseudo-count formula in numpy's float32 evaluation order
 // (np.mean / np.sum of a short vector: 8 partial sums, then the tail) and appends the new embedding.
 #include "srlx_common.h"
+#include "srlx_np_sum.h"
 
 namespace {
 
@@ -28,29 +29,7 @@ constexpr int kMaxSplit = 16;
 
 __device__ __forceinline__ float f_sqrt(float x) { return (float)__dsqrt_rn((double)x); }  // correctly rounded fp32 sqrt
 
-// numpy's float32 pairwise summation (numpy/_core/src/umath/loops_utils.h.src) over f(0..n): plain loop below 8
-// elements, 8 partial sums up to 128, recursive halving above.
-template <typename F>
-__device__ float np_pairwise_sum(const F &f, i64 lo, i64 n) {
-    if (n < 8) {
-        float acc = 0.f;  // numpy starts from -0.0; identical for the non-negative inputs used here
-        for (i64 i = 0; i < n; i++) acc = acc + f(lo + i);
-        return acc;
-    }
-    if (n <= 128) {
-        float r[8];
-        for (int j = 0; j < 8; j++) r[j] = f(lo + j);
-        i64 i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] = r[j] + f(lo + i + j);
-        float acc = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) acc = acc + f(lo + i);
-        return acc;
-    }
-    i64 n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum(f, lo, n2) + np_pairwise_sum(f, lo + n2, n - n2);
-}
+using srlx::np_pairwise_sum;  // numpy's float32 pairwise summation: plain loop below 8 elements, 8 partial sums up to 128
 
 struct NguDev {
     i64 E, cap;

@@ -747,10 +747,12 @@ __global__ void __launch_bounds__(256) k_actor_td(StoreDev s, i64 first_slot, i6
         td[k] = gain - qsel;
     }
     (void)double_dqn;  // one set of rows: the greedy action and its value come from the same network
+    // The terms are added one after another at every n.  td_rows follows numpy's pairwise order from 8 terms up (srlx_np_sum.h), so from n = 8 the two can differ
+    // in the last bit: this estimate is an initial priority, not the learner's target, and is not held bit-equal to it.
     double c = 1.0;
     float target = 0.f;
     for (int k = 0; k < n; k++) {
-        if (k > 0) c *= retrace_h * ((act[k] == nact[k]) ? 1.0 : 0.0);  // td_rows: pi = (act[m] == nact[m])
+        if (k > 0) c *= retrace_h * ((act[k] == nact[k]) ? 1.0 : 0.0);  // td_rows: pi = (act[m] == nact)
         const float dm = (float)pow(discount, (double)k);
         target = target + (float)((double)(td[k] * dm) * c);
     }

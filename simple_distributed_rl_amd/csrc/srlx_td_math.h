@@ -3,11 +3,12 @@
 // its prologue (srlx_qnet_backward_td_u8, srlx_qnet_bwd.hip).  Replaces the numpy between the network calls:
 //   srl/algorithms/rainbow/rainbow.py:226-287         (calc_target_q after the two forwards)
 //   srl/algorithms/rainbow/model_torch.py:103-105,113 (selected Q, HuberLoss(target*w, q*w), |target-q|)
-// float32 arithmetic follows numpy's evaluation order of the cited lines.
+// float32 arithmetic follows numpy's evaluation order of the cited lines, the pairwise order of np.sum from 8 terms up included (srlx_np_sum.h).
 #pragma once
 #include <math.h>
 
 #include "srlx_common.h"
+#include "srlx_np_sum.h"
 
 namespace srlx {
 using i64 = int64_t;
@@ -78,32 +79,30 @@ __device__ __forceinline__ double td_rows(const TdArgs &a, int t, int T, float *
         const float *qtg = a.q_tg_next + b * n * A;
         const int32_t *act = a.actions + b * n;
         const u8 *inv = a.invalid_next ? a.invalid_next + b * n * A : nullptr;
-        int nact[kTdMaxStep];
-        float td[kTdMaxStep];
-        for (int m = 0; m < n; m++) {
+        // term m of the discounted sum; called for m = 0, 1, ... in turn (the retrace coefficient is a running product)
+        double c = 1.0;  // :268-284 retrace coefficients, float64 in the reference
+        auto term = [&](int m) {
             // rainbow.py:245-253: greedy next action from the online net (double DQN) or the target net
             const float *sel = a.double_dqn ? qon + m * A : qtg + m * A;
-            nact[m] = argmax_masked(sel, inv ? inv + m * A : nullptr, A);
-            float maxq = qtg[m * A + nact[m]];
+            const int nact = argmax_masked(sel, inv ? inv + m * A : nullptr, A);
+            // :248-251 without double DQN the mask is written into the target net's own rows: a step whose actions are all invalid reads -inf back
+            float maxq = (!a.double_dqn && inv && inv[m * A + nact]) ? -INFINITY : qtg[m * A + nact];
             if (a.rescale) maxq = inverse_rescaling(maxq);  // :255-256
             float gain = a.rewards[b * n + m] + ((1.0f - a.terminated[b * n + m]) * disc_f) * maxq;  // :258
             if (a.rescale) gain = rescaling(gain);  // :260-261
             // :231-233 action value of the online net for steps 1..n-1, 0 for the first step
             const float qsel = (m == 0) ? 0.f : qon[(m - 1) * A + act[m]];
-            td[m] = gain - qsel;  // :263
-        }
-        // :268-286 retrace coefficients (float64 in the reference) and the discounted sum in float32
-        double c = 1.0;
-        float target = 0.f;
-        for (int m = 0; m < n; m++) {
+            const float td = gain - qsel;  // :263
             if (m > 0) {
-                const bool pi = (act[m] == nact[m]);  // argmax(n_action)[m-1] == n_act_idx[:,1:][m-1]
+                const bool pi = (act[m] == nact);  // argmax(n_action)[m-1] == n_act_idx[:,1:][m-1]
                 c *= a.retrace_h * (pi ? 1.0 : 0.0);
             }
             const float dm = a.dm[m];  // float32(discount ** m) (:182), from the host
-            const float term = (float)((double)(td[m] * dm) * c);
-            target = target + term;
-        }
+            return (float)((double)(td * dm) * c);
+        };
+        // :285 np.sum(..., axis=1, dtype=float32) is numpy's pairwise summation: one term after another below 8 terms, 8 partial sums and then the tail from 8
+        // terms up (n <= 32: one leaf, inlined -- no call, no per-step arrays, one copy of the term)
+        const float target = np_sum_leaf_rolled(term, n);
         if (write_global) a.target[b] = target;
 
         // model_torch.py:103-105,113

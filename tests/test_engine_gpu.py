@@ -113,7 +113,7 @@ def test_engine_overlap_and_graphs():
 def test_device_adam_matches_torch_adam():
     """`srlx_adam_step` (one launch over all parameter tensors, step count from a device scalar) against
     torch.optim.Adam on the same gradients: parameters and both moment estimates after every one of 6 steps.
-    Shapes cover whole 2048-element chunks, ragged tails, a tensor smaller than one chunk and a channels_last weight."""
+    Shapes cover whole 4096-element chunks, ragged tails, a tensor smaller than one chunk and a channels_last weight."""
     from simple_distributed_rl_amd.device.qnet import DeviceAdam
 
     dev = torch.device("cuda:0")
