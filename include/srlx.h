@@ -1390,6 +1390,28 @@ int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const
                      double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream);
 int srlx_sacd_forward(srlx_sacd_t *h, int64_t n, const float *d_states, int target, float *d_logits, float *d_qmin, void *stream);
 
+/* ---- Discrete soft actor-critic: the device engine's two launches outside the update (srlx_sacd.hip) --------------------------------------------
+ *   srlx_sacd_act        : the Worker's policy() (algorithms/sac.py:334-338) for n_rows lanes in ONE launch.  Row r is the D floats at d_obs_base +
+ *                          d_row_offsets[r] (offsets in floats, as srlx_mlpq_forward takes them: the store's frame table at window 1; NULL: + r * D).
+ *                          U[r * A + a] is the value srlx_rng_uniform(seed, *d_counter, n_rows * A, .) would write at that index; *d_counter is read, not
+ *                          advanced.  While *d_counter < random_until: action = min(A - 1, (int)floor(U[r * A] * A)).  Otherwise, in float64:
+ *                          u = 1e-6 + (1 - 1e-6) U, score_a = (double)z_a - log(-log(u)), action = the FIRST maximum.  The logits z are the policy's, bit for
+ *                          bit what srlx_sacd_forward(target = 0) writes for the same rows.  d_logits f32 [n_rows][A] and d_scores f64 [n_rows][A] are
+ *                          optional (NULL) and, when asked for, written in both phases; with neither, the random phase does not run the network.  Needs
+ *                          srlx_sacd_bind only and no scratch sized by max_batch.  No atomics: equal inputs give equal bits.  Envelope, validated before
+ *                          any device call (SRLX_ERR_INVALID; srlx_last_error() names sacd_act): a bound handle, n_rows 1..65536, random_until >= 0,
+ *                          non-NULL d_obs_base, d_counter and d_actions.
+ *   srlx_sacd_ring_batch : the items of a draw as srlx_sacd_update's tensors, stateless, ONE launch.  Inputs as srlx_per_sample_gather_train /
+ *                          srlx_store_gather_train write them at window 1, n-step 1: offsets i64 [B][2] (s, s'; in floats), actions i32 [B], rewards and
+ *                          terminated f32 [B].  Outputs: states and next states f32 [B][D], one-hot actions f32 [B][A] (exact 0 / 1), done u8 [B]
+ *                          (terminated != 0).  d_rewards is already the update's [B] tensor: required, not copied.  Rows move as 16-byte accesses when D is a
+ *                          multiple of 4 and the base pointers and the item's offsets are 16-byte aligned.  Envelope: B 1..256, D 1..256, A 2..16, no NULL
+ *                          pointer (srlx_last_error() names sacd_ring_batch). */
+int srlx_sacd_act(srlx_sacd_t *h, int64_t n_rows, const float *d_obs_base, const int64_t *d_row_offsets, uint64_t seed, const int64_t *d_counter,
+                  int64_t random_until, int32_t *d_actions, float *d_logits, double *d_scores, void *stream);
+int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions, const float *d_rewards,
+                         const float *d_terminated, float *d_states, float *d_next_states, float *d_onehot, uint8_t *d_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

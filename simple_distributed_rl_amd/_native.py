@@ -275,6 +275,8 @@ SIGNATURES = {
     "srlx_sacd_steps": (c_int, [c_p, c_p]),
     "srlx_sacd_update": (c_int, [c_p, c_i64] + [c_p] * 5 + [c_f64] * 5 + [c_int, c_int, c_f64] + [c_p] * 6),
     "srlx_sacd_forward": (c_int, [c_p, c_i64, c_p, c_int, c_p, c_p, c_p]),
+    "srlx_sacd_act": (c_int, [c_p, c_i64, c_p, c_p, c_u64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "srlx_sacd_ring_batch": (c_int, [c_i64, c_int, c_int] + [c_p] * 10),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

@@ -16,6 +16,8 @@ Trainer.train() (:158-243) is DESIGN.md 7m's contract, on one of two backends th
   "torch"  plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
+`device/sacd_engine.py: SacdEngine` runs E lock-stepped lanes on one GPU around this Parameter and Trainer (`train_on_batch`); `Runner.train()` does
+not route there yet.
 
 What is kept from the reference although it reads oddly:
   * target_entropy = -A (:151-156, "-1 * n"), the continuous-control heuristic.  A discrete policy's entropy lies in [0, log A], so target_entropy - entropy is
@@ -241,15 +243,19 @@ class Trainer(RLTrainer):
         done = torch.as_tensor(np.asarray(done, dtype=np.uint8), device=d)
         self.train_on_batch(state, action, n_state, reward, done)
 
-    def train_on_batch(self, state, onehot_action, n_state, reward, done) -> dict:
-        """One update (:170-243) from device tensors: state / n_state f32 [B][...], one-hot actions f32 [B][A], reward f32 [B], done u8 [B]."""
+    def train_on_batch(self, state, onehot_action, n_state, reward, done, actions=None) -> dict:
+        """One update (:170-243) from device tensors: state / n_state f32 [B][...], one-hot actions f32 [B][A], reward f32 [B], done u8 [B].  `actions`: the
+        same actions as int32 [B], when the caller has them (the device engine's ring does): the libsrlx backend then skips its argmax over the one-hot rows."""
         if self._backend is None:
             self._choose_backend(state.shape[0])
         cfg = self.config
         hard_sync = self.train_count % cfg.hard_target_update_interval == 0
         if self._backend == "srlx" and state.shape[0] > self._srlx.max_batch:
             raise ValueError(f"a batch of {state.shape[0]} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
-        out = (self._update_srlx if self._backend == "srlx" else self._update_torch)(state, onehot_action, n_state, reward, done, hard_sync)
+        if self._backend == "srlx":
+            out = self._update_srlx(state, onehot_action, n_state, reward, done, hard_sync, actions)
+        else:
+            out = self._update_torch(state, onehot_action, n_state, reward, done, hard_sync)
         self.update_path = self._backend
         self.train_count += 1
         scalars = out["scalars"].tolist()  # (the one synchronisation of the call)
@@ -258,7 +264,7 @@ class Trainer(RLTrainer):
             self.info["alpha_loss"], self.info["alpha"] = scalars[3], scalars[4]
         return out
 
-    def _update_srlx(self, state, onehot_action, n_state, reward, done, hard_sync: bool) -> dict:
+    def _update_srlx(self, state, onehot_action, n_state, reward, done, hard_sync: bool, actions=None) -> dict:
         cfg, u = self.config, self._srlx
         if not self.parameter.load_log_alpha:  # :170-173
             u.reset_alpha_optimizer()
@@ -268,7 +274,9 @@ class Trainer(RLTrainer):
         lr_q = cfg.lr_q * cfg.lr_q_scheduler.factor(steps[1], cfg.lr_q)
         lr_alpha = cfg.lr_alpha * cfg.lr_alpha_scheduler.factor(steps[3], cfg.lr_alpha)
         B = state.shape[0]
-        return u.update(state.reshape(B, -1), onehot_action.argmax(dim=1).to(torch.int32), n_state.reshape(B, -1), reward, done, lr_policy, lr_q, lr_alpha,
+        if actions is None:
+            actions = onehot_action.argmax(dim=1).to(torch.int32)
+        return u.update(state.reshape(B, -1), actions, n_state.reshape(B, -1), reward, done, lr_policy, lr_q, lr_alpha,
                         hard_sync, cfg.discount, cfg.soft_target_update_tau, cfg.entropy_alpha_auto_scale, self.target_entropy)
 
     def _update_torch(self, state, onehot_action, n_state, reward, done, hard_sync: bool) -> dict:

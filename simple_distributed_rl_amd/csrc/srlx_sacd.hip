@@ -12,6 +12,9 @@
 //                   Launched for q1 + q2, then for the policy; the policy's launch also reduces the four losses and takes the temperature's Adam step
 //   k_sacd_policy   both ONLINE Q-networks (as the Q step left them) over every action of s, policy(s), policy_row, the backward chain
 //   k_sacd_forward  logits and min(q1, q2) over every action of n rows, online or target
+// and, for the device engine, outside the update:
+//   k_sacd_act         the policy's logits of ring rows and the Worker's action (uniform while start_steps last, Gumbel-max after), one launch per lock-step
+//   k_sacd_ring_batch  the drawn items' rows out of the ring as the update's dense tensors
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_adam_math.h"
 #include "srlx_common.h"
@@ -55,6 +58,7 @@ struct srlx_sacd {
     int D, A, Lp, Lq, device;
     int Wp[3], Wq[3];
     int wmax;  // the widest row in LDS: max(D + A, every width)
+    int wmax_policy;  // the same over the policy alone: max(D, its widths) -- k_sacd_act's rows
     i64 max_batch;
     float *p[kNets][8];
     float *log_alpha;
@@ -78,6 +82,11 @@ int n_tensors_policy(const srlx_sacd *h) { return 2 * (h->Lp + 1); }
 int n_tensors_q(const srlx_sacd *h) { return 2 * (h->Lq + 1); }
 int lds_stride(const srlx_sacd *h) { return h->wmax + 1; }
 size_t lds_bytes(const srlx_sacd *h) { return sizeof(float) * ((size_t)2 * kRows * lds_stride(h) + kWTile); }
+int act_lds_stride(const srlx_sacd *h) { return h->wmax_policy + 1; }
+size_t act_lds_bytes(const srlx_sacd *h) { return sizeof(float) * ((size_t)2 * kRows * act_lds_stride(h) + kWTile); }
+// the most any handle asks of k_sacd_act (rows of 512 floats): the kernel's cap is set to this at every create, so that creating a narrower handle never
+// lowers it under what an earlier, wider handle launches with
+constexpr size_t kActLdsCap = sizeof(float) * ((size_t)2 * kRows * (512 + 1) + kWTile);
 
 // y[r][u] = act(sum_k W[u][k] x[r][k] + b[u]) for rows r < rows (<= kRows), both in LDS; the thread mapping of srlx_mlpq.hip's dense().  Tensors are float32;
 // every sum ACCUMULATES in float64 (a product of two float32 values is exact there) and is rounded to float32 once, here, in the backward chain and in the
@@ -319,6 +328,91 @@ __global__ void __launch_bounds__(kThreads) k_sacd_forward(const NetD *__restric
     }
 }
 
+// The Worker's policy() for the lanes of a lock-step (algorithms/sac.py:334-338): the policy's logits of `rpw` <= 16 rows per workgroup (rows from a
+// ring through an offset table), then one thread per (row, action) for the keyed uniform, the rescaled uniform and the Gumbel score in float64, then one
+// thread per row for the first maximum -- or, while *counter < random_until, the uniform random action.  A row's logits are the same fma chains whatever rows
+// share its workgroup, so `rpw` changes the launch shape and never a bit.  The scores stand in the weight tile once the network is done with it.
+struct ActArgs {
+    i64 n;
+    const float *obs;
+    const i64 *off;  // NULL: row r at obs + r * D
+    srlx::u64 seed;
+    const i64 *counter;
+    i64 random_until;
+    int32_t *actions;
+    float *logits;   // NULL: not wanted
+    double *scores;  // NULL: not wanted
+};
+
+__global__ void __launch_bounds__(kThreads) k_sacd_act(const NetD *__restrict__ nets, ActArgs a, int rpw, int D, int A, int S) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
+    double *sc = (double *)wl;  // [rpw][A] (2 * kRows * S floats in front of it: a multiple of 16 bytes)
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * rpw;
+    const int nb = (int)(a.n - i0 < rpw ? a.n - i0 : rpw);
+    const srlx::u64 c = (srlx::u64)a.counter[0];
+    const bool random = a.counter[0] < a.random_until;
+    if (!random || a.logits || a.scores) {  // (the same answer in every thread of the launch)
+        for (int p = t; p < nb * D; p += kThreads) {
+            const int r = p / D, k = p % D;
+            b0[r * S + k] = (a.off ? a.obs + a.off[i0 + r] : a.obs + (i0 + r) * D)[k];
+        }
+        __syncthreads();
+        const float *z = forward_rows(nets[0], nb, b0, b1, S, wl, nullptr, 0, 0, 0);
+        if (t < nb * A) {
+            const int r = t / A, j = t % A;
+            const i64 e = (i0 + r) * A + j;
+            const float zv = z[r * S + j];
+            const double s = srlxs::gumbel_score(zv, srlxs::gumbel_uniform(srlx::u53(srlx::rng_u64(a.seed, c, (srlx::u64)e))));
+            sc[t] = s;
+            if (a.logits) a.logits[e] = zv;
+            if (a.scores) a.scores[e] = s;
+        }
+        __syncthreads();
+    }
+    if (t < nb) {
+        const i64 r = i0 + t;
+        a.actions[r] = random ? srlxs::random_action(srlx::u53(srlx::rng_u64(a.seed, c, (srlx::u64)(r * A))), A) : srlxs::first_argmax(sc + t * A, A);
+    }
+}
+
+// The items a uniform draw named, as srlx_sacd_update's tensors: one workgroup per item copies s and s' out of the ring (16 bytes per access where the
+// rows allow), one-hot encodes the action and turns `terminated` into the update's done byte.
+struct RingBatchArgs {
+    const float *obs;
+    const i64 *off;  // [B][2]: s, s'
+    const int32_t *actions;
+    const float *terminated;
+    float *states, *next_states, *onehot;
+    u8 *done;
+    int D, A, vec;
+};
+
+__global__ void __launch_bounds__(128) k_sacd_ring_batch(RingBatchArgs a) {
+    const i64 b = blockIdx.x;
+    const int t = threadIdx.x, D = a.D;
+    const i64 o0 = a.off[2 * b], o1 = a.off[2 * b + 1];
+    const float *s0 = a.obs + o0, *s1 = a.obs + o1;
+    float *d0 = a.states + b * D, *d1 = a.next_states + b * D;
+    if (a.vec && ((o0 | o1) & 3) == 0) {
+        const int q = D / 4;
+        for (int i = t; i < 2 * q; i += 128) {
+            const bool nx = i >= q;
+            const int k = nx ? i - q : i;
+            ((float4 *)(nx ? d1 : d0))[k] = ((const float4 *)(nx ? s1 : s0))[k];
+        }
+    } else {
+        for (int i = t; i < 2 * D; i += 128) {
+            const bool nx = i >= D;
+            const int k = nx ? i - D : i;
+            (nx ? d1 : d0)[k] = (nx ? s1 : s0)[k];
+        }
+    }
+    if (t < a.A) a.onehot[b * a.A + t] = t == a.actions[b] ? 1.f : 0.f;
+    if (t == 0) a.done[b] = a.terminated[b] != 0.f ? 1 : 0;
+}
+
 struct GradArgs {
     const Seg *segs;
     int nseg;
@@ -532,6 +626,7 @@ int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy
     for (int l = 0; l < n_policy; l++) h->Wp[l] = policy_widths[l];
     for (int l = 0; l < n_q; l++) h->Wq[l] = q_widths[l];
     h->wmax = wmax_of(obs_dim, n_actions, n_policy, policy_widths, n_q, q_widths);
+    h->wmax_policy = wmax_of(obs_dim, 0, n_policy, policy_widths, 0, nullptr);
     const size_t plane = (size_t)max_batch * h->wmax;
     hipError_t e = hipMalloc((void **)&h->d_nets, sizeof(NetD) * kNets);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_segs, sizeof(Seg) * 2 * kMaxSegs);
@@ -551,6 +646,7 @@ int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_q_rows, lds);
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_policy, lds);
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_forward, lds);
+    if (st == SRLX_OK) st = set_lds((const void *)k_sacd_act, kActLdsCap);
     if (st != SRLX_OK) {
         srlx_sacd_destroy(h);
         return st;
@@ -636,6 +732,51 @@ int srlx_sacd_forward(srlx_sacd_t *h, int64_t n, const float *d_states, int targ
     const int ipw = kRows / h->A;
     hipLaunchKernelGGL(k_sacd_forward, dim3((unsigned)((n + ipw - 1) / ipw)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const NetD *)h->d_nets, target, (i64)n,
                        d_states, d_logits, d_qmin, h->D, h->A, lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+// rows per workgroup of k_sacd_act: 16 once that still leaves a workgroup for each of the MI355X's 256 compute units, fewer below (a workgroup's time grows with
+// its rows, and every workgroup of a launch that fits the machine runs at once)
+int act_rows_per_workgroup(i64 n) {
+    int rpw = 1;
+    while (rpw < kRows && (n + rpw - 1) / rpw > 256) rpw *= 2;
+    return rpw;
+}
+
+int srlx_sacd_act(srlx_sacd_t *h, int64_t n_rows, const float *d_obs_base, const int64_t *d_row_offsets, uint64_t seed, const int64_t *d_counter,
+                  int64_t random_until, int32_t *d_actions, float *d_logits, double *d_scores, void *stream) {
+    SRLX_REQUIRE(h, "sacd_act: NULL handle");
+    SRLX_REQUIRE(h->bound, "sacd_act: unbound handle (srlx_sacd_bind)");
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= 65536, "sacd_act: %lld rows (1..65536)", (long long)n_rows);
+    SRLX_REQUIRE(random_until >= 0, "sacd_act: random_until %lld is negative", (long long)random_until);
+    SRLX_REQUIRE(d_obs_base && d_counter && d_actions, "sacd_act: NULL observations, counter or actions");
+    srlx::DeviceGuard g(h->device);
+    if (!h->nets_ok) {
+        NetD nets[kNets];
+        for (int k = 0; k < kNets; k++) nets[k] = net_of(h, k);
+        SRLX_HIP(hipMemcpy(h->d_nets, nets, sizeof(nets), hipMemcpyHostToDevice));
+        h->nets_ok = true;
+    }
+    const int rpw = act_rows_per_workgroup(n_rows);
+    ActArgs a{(i64)n_rows, d_obs_base, (const i64 *)d_row_offsets, (srlx::u64)seed, (const i64 *)d_counter, (i64)random_until, d_actions, d_logits, d_scores};
+    hipLaunchKernelGGL(k_sacd_act, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const NetD *)h->d_nets, a, rpw,
+                       h->D, h->A, act_lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions, const float *d_rewards,
+                         const float *d_terminated, float *d_states, float *d_next_states, float *d_onehot, uint8_t *d_done, void *stream) {
+    SRLX_REQUIRE(B >= 1 && B <= 256, "sacd_ring_batch: batch %lld (1..256)", (long long)B);
+    SRLX_REQUIRE(D >= 1 && D <= 256, "sacd_ring_batch: observation length %d (1..256)", D);
+    SRLX_REQUIRE(A >= 2 && A <= 16, "sacd_ring_batch: %d actions (2..16)", A);
+    // (d_rewards is the gather's [B][1] column, already the update's [B] tensor: required like the rest, handed on by the caller, not copied)
+    SRLX_REQUIRE(d_obs_base && d_offsets && d_actions && d_rewards && d_terminated && d_states && d_next_states && d_onehot && d_done,
+                 "sacd_ring_batch: NULL argument");
+    const bool vec = D % 4 == 0 && (((uintptr_t)d_obs_base | (uintptr_t)d_states | (uintptr_t)d_next_states) & 15) == 0;
+    RingBatchArgs a{d_obs_base, (const i64 *)d_offsets, d_actions, d_terminated, d_states, d_next_states, d_onehot, d_done, D, A, vec ? 1 : 0};
+    hipLaunchKernelGGL(k_sacd_ring_batch, dim3((unsigned)B), dim3(128), 0, (hipStream_t)stream, a);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

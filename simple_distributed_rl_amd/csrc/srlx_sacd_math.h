@@ -1,5 +1,6 @@
 // srlx_sacd_math.h -- the closed forms of the discrete soft actor-critic update (srl/algorithms/sac/sac_tf_discrete.py:158-243), written once
-// for the kernels of srlx_sacd.hip.  All float32, every sum over the A <= 16 actions in action order.  The library is built with -ffp-contract=off: a fused
+// for the kernels of srlx_sacd.hip.  The update's forms are all float32, every sum over the A <= 16 actions in action order; the acting pass's forms at the end
+//  are float64.  The library is built with -ffp-contract=off: a fused
 // multiply-add is written fmaf where one is meant, everything else rounds after every operation.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,5 +63,27 @@ __device__ __forceinline__ void policy_row(const float *z, const float *qv, int 
 
 // helper.model_soft_sync per element: (1 - tau) is rounded to float32 from double by the caller; two products and one add
 __device__ __forceinline__ float soft_sync(float target, float online, float one_minus_tau, float tau) { return one_minus_tau * target + tau * online; }
+
+// ---- the Worker's action (srlx_sacd_act).  All float64, as numpy computes algorithms/sac.py:gumbel_max_sample; U is a keyed uniform in [0, 1).
+// Host-compilable: nothing here needs a device.
+
+// rng.uniform(1e-6, 1.0): low + (high - low) * U, the product and the sum rounded separately
+__host__ __device__ __forceinline__ double gumbel_uniform(double U) { return 1e-6 + (1.0 - 1e-6) * U; }
+
+// logits - log(-log(u)) for one action: the logit is exact in float64
+__host__ __device__ __forceinline__ double gumbel_score(float z, double u) { return (double)z - log(-log(u)); }
+
+// np.argmax: the FIRST maximum
+__host__ __device__ __forceinline__ int first_argmax(const double *score, int A) {
+    int best = 0;
+    for (int a = 1; a < A; a++) best = score[a] > score[best] ? a : best;
+    return best;
+}
+
+// the Worker's sample_action() while start_steps last: uniform over the A actions from one uniform
+__host__ __device__ __forceinline__ int random_action(double U, int A) {
+    const int a = (int)floor(U * (double)A);
+    return a < A - 1 ? a : A - 1;
+}
 
 }  // namespace srlxs

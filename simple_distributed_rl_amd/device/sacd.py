@@ -150,3 +150,20 @@ class SacdUpdate:
         N.check(self._lib.srlx_sacd_forward(self._h, n, N.tptr(x), int(bool(target)), N.tptr(logits), N.tptr(qmin), N.torch_stream_ptr()))
         self._keep_fwd = x
         return logits, qmin
+
+    def act(self, n_rows: int, obs_base, row_offsets, seed: int, counter, random_until: int, actions, logits=None, scores=None):
+        """srlx_sacd_act: the Worker's action of `n_rows` rows in one launch.  `obs_base`: a float32 device tensor or the address of a ring
+        (DeviceReplay.obs_base); `row_offsets`: i64 [n_rows] offsets in floats (None: dense rows); `counter`: i64 [1] device tensor, read and not advanced;
+        `actions` i32 [n_rows]; optional `logits` f32 [n_rows][A] and `scores` f64 [n_rows][A].  Nothing synchronises; returns `actions`."""
+        base = N.tptr(obs_base) if isinstance(obs_base, torch.Tensor) else (None if obs_base is None else N.c_p(obs_base))
+        N.check(self._lib.srlx_sacd_act(self._h, int(n_rows), base, N.tptr(row_offsets), N.c_u64(int(seed) & 0xFFFFFFFFFFFFFFFF), N.tptr(counter), int(random_until),
+                                        N.tptr(actions), N.tptr(logits), N.tptr(scores), N.torch_stream_ptr()))
+        return actions
+
+
+def ring_batch(B: int, D: int, A: int, obs_base, offsets, actions, rewards, terminated, states, next_states, onehot, done):
+    """srlx_sacd_ring_batch: what a DeviceReplay draw wrote (`frame_off_all` i64 [B][2], `batch.actions` i32, `batch.rewards` and
+    `batch.terminated` f32, all [B] or [B][1]) as the arguments of `sac.Trainer.train_on_batch`: states / next states f32 [B][D], one-hot f32 [B][A], done u8 [B]."""
+    base = N.tptr(obs_base) if isinstance(obs_base, torch.Tensor) else (None if obs_base is None else N.c_p(obs_base))
+    N.check(N.lib().srlx_sacd_ring_batch(int(B), int(D), int(A), base, N.tptr(offsets), N.tptr(actions), N.tptr(rewards), N.tptr(terminated), N.tptr(states),
+                                         N.tptr(next_states), N.tptr(onehot), N.tptr(done), N.torch_stream_ptr()))

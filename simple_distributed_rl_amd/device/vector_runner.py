@@ -664,6 +664,59 @@ def c51_config_from(rl_config, env, n_envs: int, seed: int):
     )
 
 
+def why_not_sacd_engine(env, rl_config, n_envs=None) -> str:
+    """Empty string when `SacdEngine` (device/sacd_engine.py) can run this sac.Config on this environment; otherwise EVERY reason it cannot, joined
+    with "; " (as `why_not_c51_engine`).  The envelope figures are `SacdUpdate.envelope_reason`'s (srlx_sacd_create's, srlx.h): each dimension is asked about on
+    its own beside the smallest shape the kernels take, and the sentence ends in that answer.  `n_envs`: the lane count, when the caller has one.
+    `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep SAC_Discrete on the plugin path; the engine is built around `runner.make_parameter()`."""
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+    from simple_distributed_rl_amd.device.sacd import SacdUpdate
+    from simple_distributed_rl_amd.device.sacd_engine import MAX_LANES
+    from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig
+
+    c, why = rl_config, []
+    if c.get_name() != "SAC_Discrete":
+        return f"'{c.get_name()}' is not a SAC_Discrete config"
+    small = dict(D=1, A=2, pw=(32,), qw=(32,), batch=1)  # the smallest shape of the envelope: what stands beside the one dimension that is asked about
+
+    def outside(**one) -> str:
+        head, sep, _ = SacdUpdate.envelope_reason(**dict(small, **one)).partition("): ")  # (the tail restates the whole shape, the stand-in values included)
+        return head + ")" if sep else head
+
+    if env.player_num != 1:
+        why.append("multi-player environment")
+    if not isinstance(env.action_space, DiscreteSpace):
+        why.append("the engine serves discrete action spaces")
+    elif outside(A=int(env.action_space.n)):
+        why.append(f"{int(env.action_space.n)} actions: " + outside(A=int(env.action_space.n)))
+    D = flat_dim(frame_space(env, c))
+    if D is None:
+        why.append("the policy and Q-networks read flat BoxSpace((D,)) observations, anything else stays on the plugin path")
+    elif outside(D=D):
+        why.append(f"{D} observation elements: " + outside(D=D))
+    if getattr(c, "_obs_processors", None):
+        why.append("observation processors are served by the plugin path")
+    if c.window_length != 1:
+        why.append("the networks read one observation (window_length 1)")
+    iv = c.input_block.value
+    if iv.name != "MLP" or tuple(iv.kwargs.get("layer_sizes", ())) != ():
+        why.append("an input_block with layers of its own: the kernels start at the observation")
+    for name, block in (("policy_block", c.policy_block), ("q_block", c.q_block)):
+        sizes = _ppo_block_sizes(block)
+        if sizes is None:
+            why.append(f"{name} is not an MLP of ReLU layers (Linear layers with biases)")
+        elif outside(**{"pw" if name == "policy_block" else "qw": sizes}):
+            why.append(f"{name} {sizes}: " + outside(**{"pw" if name == "policy_block" else "qw": sizes}))
+    if outside(batch=int(c.batch_size)):
+        why.append(outside(batch=int(c.batch_size)))
+    if not isinstance(c.memory, ReplayBufferConfig):
+        name = getattr(c.memory, "name", type(c.memory).__name__)
+        why.append(f"SAC draws uniformly from the ReplayBuffer memory, memory '{name}' stays on the plugin path")
+    if n_envs is not None and not (isinstance(n_envs, int) and 1 <= n_envs <= MAX_LANES):
+        why.append(f"{n_envs!r} lanes are outside the engine's 1..{MAX_LANES}")
+    return "; ".join(why)
+
+
 AGENT57_MP_REASON = "Agent57 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
 
 
