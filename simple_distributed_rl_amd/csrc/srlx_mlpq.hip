@@ -3,6 +3,9 @@
 //
 // Every dense layer is Linear (+ ReLU except out_layer), weights in torch's [out][in] layout, plain float32 on the VALU: at D <= 256 inputs, <= 3 layers of
 // <= 512 units and <= 32 actions a pass is a few thousand dependent multiply-adds per row, so launch count and the layer chain bound it, not throughput.
+// The layer descriptor, dense(), the plain-layer forward loop and the hidden-layer backward chain are srlx_mlp_rows.h's, instantiated with float32 sums
+// (srlx_sacd.hip runs the same code with float64 sums); the dueling head, narrow_rows() and the sparse seeds of the chain's top layer are this file's,
+// and so is one kept copy of the forward loop, for k_mlpq_learn_rows and the n-step learner kernels (forward_rows<true>: why, there).
 //   k_mlpq_actor      16 rows per workgroup: rows -> LDS, layer by layer through two LDS buffers (each layer's weight staged in LDS by coalesced loads, in
 //                     tiles of whole rows), Q rows out, epsilon-greedy on each row (= k_head's rule).
 //   k_mlpq_learn_rows 8 sampled items per workgroup: online pass over s_0 and s_1, target pass over s_1, the 1-step (double) DQN target / Huber / priority of
@@ -32,6 +35,7 @@
 #include "srlx_adam_math.h"
 #include "srlx_c51_math.h"
 #include "srlx_common.h"
+#include "srlx_mlp_rows.h"
 #include "srlx_noise_math.h"
 #include "srlx_ppo_math.h"
 #include "srlx_td_math.h"
@@ -72,26 +76,19 @@ using i64 = int64_t;
 using u64 = unsigned long long;
 using u8 = unsigned char;
 
-constexpr int kThreads = 256;
-constexpr int kRows = 16;      // rows of one acting workgroup, and of the learner's online pass (s_0 and s_1 of kItems items)
+using srlxm::kRows;  // rows of one acting workgroup, and of the learner's online pass (s_0 and s_1 of kItems items)
+using srlxm::kThreads;
+using srlxm::kWTile;
 constexpr int kItems = kRows / 2;
 constexpr int kMaxParams = 12;  // two trunk layers and the dueling head's four
 constexpr int kMaxNstep = 7;    // kRows / (n + 1) >= 2 items per workgroup
 
-struct Net {  // (scalar fields and selects, no arrays: a kernel-argument array indexed by a run-time layer number is copied to scratch memory)
-    int D, L, A;
-    int W0, W1, W2;
-    const float *w0, *w1, *w2, *w3, *b0, *b1, *b2, *b3;
+struct Net : srlxm::Layers {  // In = D; Out = A, or A * atoms on a categorical handle; L = the layers in front of the head
     const float *wout;  // out_layer's weight (= the weight of layer L)
     // the dueling head (head != 0; srl/rl/torch_/blocks/dueling_network.py:8-59) behind the L trunk layers: v_layers.0 [H][in], v_layers.2 [1][H],
     // adv_layers.0 [H][in], adv_layers.2 [A][H]; head 1 = "average", 2 = ""
     int H, head;
     const float *vw0, *vb0, *vw1, *vb1, *aw0, *ab0, *aw1, *ab1;
-    __device__ int width(int l) const { return l == 0 ? W0 : (l == 1 ? W1 : W2); }
-    __device__ int in_of(int l) const { return l == 0 ? D : width(l - 1); }
-    __device__ int out_of(int l) const { return l < L ? width(l) : A; }
-    __device__ const float *weight(int l) const { return l == 0 ? w0 : (l == 1 ? w1 : (l == 2 ? w2 : w3)); }
-    __device__ const float *bias(int l) const { return l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3)); }
 };
 
 bool dueling(const srlx_mlpq *h) { return h->head == 1 || h->head == 2; }
@@ -103,7 +100,7 @@ const float *read_ptr(const srlx_mlpq *h, int i, int set) { return h->sig[i] ? h
 
 Net net_of(const srlx_mlpq *h, int set = 0) {
     Net n;
-    n.D = h->D, n.L = h->L, n.A = out_cols(h);  // (a categorical handle's network is a plain one whose out_layer has A * atoms rows)
+    n.In = h->D, n.L = h->L, n.Out = out_cols(h);  // (a categorical handle's network is a plain one whose out_layer has A * atoms rows)
     n.W0 = h->W[0], n.W1 = h->L > 1 ? h->W[1] : 0, n.W2 = h->L > 2 ? h->W[2] : 0;
     const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
     const int plain_layers = dueling(h) ? h->L : h->L + 1;
@@ -122,49 +119,6 @@ int n_params(const srlx_mlpq *h) { return dueling(h) ? 2 * h->L + 8 : 2 * (h->L 
 
 int lds_stride(const srlx_mlpq *h) { return h->wmax + 1; }  // (odd: rows of different row groups fall on different banks)
 
-// y[r][u] = act(sum_k W[u][k] x[r][k] + b[u]) for rows r < rows (<= kRows), both in LDS with row strides sx / sy.  The weight goes through LDS: a tile of whole
-// [out][in] rows (as many units as kWTile floats hold, row stride In + 1) is loaded by the whole workgroup with coalesced reads, then thread -> (unit, row group):
-// a tile narrower than the workgroup runs kThreads / units row groups side by side; each thread keeps its rows' sums in registers.  Every thread of the
-// workgroup must call this (it holds barriers).
-constexpr int kWTile = 8192;  // floats of the weight tile in LDS (32 KB)
-__device__ __forceinline__ void dense(const float *__restrict__ Wt, const float *__restrict__ bias, int In, int Out, int rows, const float *x, int sx, float *y, int sy,
-                                      bool relu, float *wl) {
-    const int t = threadIdx.x;
-    const int ws = In + 1;
-    const int tu_max = kWTile / ws < Out ? kWTile / ws : Out;
-    for (int u0 = 0; u0 < Out; u0 += tu_max) {
-        const int tu = Out - u0 < tu_max ? Out - u0 : tu_max;
-        __syncthreads();  // (the previous tile's readers are done)
-        const float *src = Wt + (i64)u0 * In;
-        for (int i = t; i < tu * In; i += kThreads) wl[(i / In) * ws + i % In] = src[i];
-        __syncthreads();
-        const int uc = tu < kThreads ? tu : kThreads;
-        const int G = kThreads / uc;
-        const int g = t / uc, ul = t % uc;
-        if (g >= G) continue;
-        const int nr = g < rows ? (rows - g + G - 1) / G : 0;
-        for (int u = ul; u < tu; u += uc) {
-            float acc[kRows];
-#pragma unroll
-            for (int j = 0; j < kRows; j++) acc[j] = 0.f;
-            const float *wr = wl + u * ws;
-            for (int k = 0; k < In; k++) {
-                const float w = wr[k];
-#pragma unroll
-                for (int j = 0; j < kRows; j++)
-                    if (j < nr) acc[j] = __builtin_fmaf(w, x[(g + j * G) * sx + k], acc[j]);
-            }
-            const float bu = bias[u0 + u];
-#pragma unroll
-            for (int j = 0; j < kRows; j++)
-                if (j < nr) {
-                    const float z = acc[j] + bu;
-                    y[(g + j * G) * sy + u0 + u] = relu ? (z > 0.f ? z : 0.f) : z;
-                }
-        }
-    }
-}
-
 // The head's second layers (v_layers.2: 1 output, adv_layers.2: A <= 32 outputs, H inputs each): y[r][u] = sum_k W[u][k] x[r][k] + b[u] with 16 lanes per
 // row (kThreads = 16 * kRows) -- every lane a strided partial sum, then a butterfly over the 16.  dense() would leave all but `rows` threads idle on a chain
 // of H dependent multiply-adds per output.  The weight is read from memory as it is ([out][in] rows, 16 consecutive floats per row group).  No barrier inside.
@@ -180,33 +134,43 @@ __device__ __forceinline__ void narrow_rows(const float *__restrict__ Wt, const 
     }
 }
 
-// the whole network over the rows in buf[0] (inputs, D columns); returns the buffer that holds the Q rows.  `keep` (global, per layer l < L: [rows_kept][W_l],
-// NULL: not kept) receives rows 0..kept-1 of every hidden layer's output.
+// the whole network over the rows in buf0 (inputs, D columns); returns the buffer that holds the Q rows, behind a barrier: srlx_mlp_rows.h's plain-layer loop
+// (a plain net: all L + 1 layers; a dueling one: the L trunk layers), then the dueling head.  `keep`: the kept planes of the hidden layers, NULL: not kept.
+// OWN: the plain-layer loop written out here, a kept copy for the learner kernels that run two networks (k_mlpq_learn_rows, learn_nstep_body).  They sit at the
+// SGPR limit, and behind the shared loop the compiler placed their scalar spills differently (k_mlpq_learn_nstep<3>: 150 reloads against 113), which cost
+// the Rainbow and DQN updates 0.4 to 0.7 %; with the loop in this function their instructions are, up to register numbers, within three of
+// what they were before the header.  Same layers, same dense(), same bits.
+template <bool OWN = false>
 __device__ __forceinline__ float *forward_rows(const Net &n, int rows, float *buf0, float *buf1, int S, float *wl, float *keep, i64 keep_plane, i64 keep_row0,
                                                int kept) {
     float *cur = buf0, *nxt = buf1;
-    const int plain_layers = n.head ? n.L : n.L + 1;
-    for (int l = 0; l < plain_layers; l++) {
-        const int In = n.in_of(l), Out = n.out_of(l);
-        dense(n.weight(l), n.bias(l), In, Out, rows, cur, S, nxt, S, l < n.L, wl);
-        __syncthreads();
-        if (keep && l < n.L)
-            for (int p = threadIdx.x; p < kept * Out; p += kThreads) keep[l * keep_plane + (keep_row0 + p / Out) * Out + p % Out] = nxt[(p / Out) * S + p % Out];
-        float *tmp = cur;
-        cur = nxt, nxt = tmp;
+    if constexpr (OWN) {
+        const int plain_layers = n.head ? n.L : n.L + 1;
+        for (int l = 0; l < plain_layers; l++) {
+            const int In = n.in_of(l), Out = n.out_of(l);
+            srlxm::dense<float>(n.weight(l), n.bias(l), In, Out, rows, cur, S, nxt, S, l < n.L, wl);
+            __syncthreads();
+            if (keep && l < n.L)
+                for (int p = threadIdx.x; p < kept * Out; p += kThreads) keep[l * keep_plane + (keep_row0 + p / Out) * Out + p % Out] = nxt[(p / Out) * S + p % Out];
+            float *tmp = cur;
+            cur = nxt, nxt = tmp;
+        }
+    } else {
+        cur = srlxm::forward_rows<float>(n, n.head ? n.L : n.L + 1, rows, buf0, buf1, S, wl, keep, keep_plane, keep_row0, kept);
+        nxt = cur == buf0 ? buf1 : buf0;
     }
     if (!n.head) return cur;
     // the dueling head on the trunk's output rows in `cur` (the observation rows when there is no trunk).  Both branches' hidden rows go through `nxt`, one after
     // the other: the value branch's row is reduced to its scalar before the advantage branch overwrites it, so the row stride stays max width + 1.  Kept planes:
     // L = the value branch's hidden rows, L + 1 = the advantage branch's.
     __shared__ float vrow[kRows], mrow[kRows];
-    const int t = threadIdx.x, In = n.in_of(n.L), H = n.H, A = n.A;
-    dense(n.vw0, n.vb0, In, H, rows, cur, S, nxt, S, true, wl);
+    const int t = threadIdx.x, In = n.in_of(n.L), H = n.H, A = n.Out;
+    srlxm::dense<float>(n.vw0, n.vb0, In, H, rows, cur, S, nxt, S, true, wl);
     __syncthreads();
     if (keep)
         for (int p = t; p < kept * H; p += kThreads) keep[n.L * keep_plane + (keep_row0 + p / H) * H + p % H] = nxt[(p / H) * S + p % H];
     narrow_rows(n.vw1, n.vb1, H, 1, rows, nxt, S, vrow, 1);
-    dense(n.aw0, n.ab0, In, H, rows, cur, S, nxt, S, true, wl);  // (its first barrier is behind every read of the value rows above)
+    srlxm::dense<float>(n.aw0, n.ab0, In, H, rows, cur, S, nxt, S, true, wl);  // (its first barrier is behind every read of the value rows above)
     __syncthreads();
     if (keep)
         for (int p = t; p < kept * H; p += kThreads) keep[(n.L + 1) * keep_plane + (keep_row0 + p / H) * H + p % H] = nxt[(p / H) * S + p % H];
@@ -271,9 +235,9 @@ __device__ __forceinline__ void actor_body(const Net &n, i64 rows_total, const f
     const i64 r0 = (i64)blockIdx.x * kRows;
     const int rows = (int)(rows_total - r0 < kRows ? rows_total - r0 : kRows);
     if (draw && blockIdx.x == 0 && t == 0) draw[0] += 1;  // NoisyLinear: this pass's draw is spent (every reader of draw[0] ran in the launch before)
-    for (int p = t; p < rows * n.D; p += kThreads) {
-        const int r = p / n.D, k = p % n.D;
-        b0[r * S + k] = row_ptr(obs, off, r0 + r, n.D)[k];
+    for (int p = t; p < rows * n.In; p += kThreads) {
+        const int r = p / n.In, k = p % n.In;
+        b0[r * S + k] = row_ptr(obs, off, r0 + r, n.In)[k];
     }
     __syncthreads();
     const float *qs = forward_rows(n, rows, b0, b1, S, wl, nullptr, 0, 0, 0);
@@ -290,8 +254,8 @@ __device__ __forceinline__ void actor_body(const Net &n, i64 rows_total, const f
         if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, A, qe + t * srlxc::kMaxActions);
     } else {
         if (q)
-            for (int p = t; p < rows * n.A; p += kThreads) q[(r0 + p / n.A) * n.A + p % n.A] = qs[(p / n.A) * S + p % n.A];
-        if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.A, qs + t * S);
+            for (int p = t; p < rows * n.Out; p += kThreads) q[(r0 + p / n.Out) * n.Out + p % n.Out] = qs[(p / n.Out) * S + p % n.Out];
+        if (pol.actions && t < rows) pol.actions[r0 + t] = select_action(pol, r0 + t, n.Out, qs + t * S);
     }
 }
 
@@ -368,7 +332,7 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restr
     const int t = threadIdx.x;
     const i64 i0 = (i64)blockIdx.x * kItems;
     const int nb = (int)(a.B - i0 < kItems ? a.B - i0 : kItems);
-    const int D = on.D, A = on.A, L = on.L;
+    const int D = on.In, A = on.Out, L = on.L;
     // rows 0..kItems-1: s_0 of the items, kItems..: s_1 (missing items: zero rows, never stored)
     for (int p = t; p < kRows * D; p += kThreads) {
         const int r = p / D, k = p % D, it = r % kItems, which = r / kItems;
@@ -377,7 +341,7 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restr
         if (which == 0 && it < nb) a.x0[(i0 + it) * D + k] = x;
     }
     __syncthreads();
-    const float *qs = forward_rows(on, kRows, b0, b1, S, wl, a.h, a.hstride, i0, nb);  // (the kept planes are [B][W_l] dense)
+    const float *qs = forward_rows<true>(on, kRows, b0, b1, S, wl, a.h, a.hstride, i0, nb);  // (the kept planes are [B][W_l] dense)
     for (int p = t; p < nb * A; p += kThreads) {
         const int r = p / A, c = p % A;
         a.q0[(i0 + r) * A + c] = qs[r * S + c];
@@ -390,7 +354,7 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restr
         b0[r * S + k] = r < nb ? a.obs[a.off[(i0 + r) * 2 + 1] + k] : 0.f;
     }
     __syncthreads();
-    const float *qt = forward_rows(tg, kItems, b0, b1, S, wl, nullptr, 0, 0, 0);
+    const float *qt = forward_rows<true>(tg, kItems, b0, b1, S, wl, nullptr, 0, 0, 0);
     for (int p = t; p < nb * A; p += kThreads) const_cast<float *>(a.td.q_tg_next)[(i0 + p / A) * A + p % A] = qt[(p / A) * S + p % A];
     __threadfence_block();
     __syncthreads();
@@ -402,32 +366,8 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_rows(const Net *__restr
         gsel[t] = a.td.grad_q0[b * A + act0[t]];
     }
     __syncthreads();
-    // backward chain, row by row: d h_{L-1} from the Q seed (one non-zero column per row), then through every hidden layer's weight; ReLU masks from the kept outputs
-    float *dcur = d0, *dnext = d1;
-    for (int l = L - 1; l >= 0; l--) {
-        const int Wl = on.width(l);
-        const float *hl = a.h + (i64)l * a.hstride;
-        float *dhl = a.dh + (i64)l * a.hstride;
-        for (int p = t; p < nb * Wl; p += kThreads) {
-            const int r = p / Wl, k = p % Wl;
-            float g;
-            if (l == L - 1) {
-                g = gsel[r] * on.wout[act0[r] * Wl + k];
-            } else {
-                const int Wn = on.width(l + 1);
-                const float *wn = on.weight(l + 1);
-                g = 0.f;
-#pragma unroll 8
-                for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
-            }
-            g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
-            dcur[r * S + k] = g;
-            dhl[(i0 + r) * Wl + k] = g;
-        }
-        __syncthreads();
-        float *tmp = dcur;
-        dcur = dnext, dnext = tmp;
-    }
+    // the backward chain, row by row: d h_{L-1} from the Q seed (one non-zero column of out_layer's weight per row), then through every hidden layer's weight
+    srlxm::backward_rows<float>(on, L - 1, nb, i0, d0, d1, S, a.h, a.dh, a.hstride, [&](int r, int k, int Wl) { return gsel[r] * on.wout[act0[r] * Wl + k]; });
 }
 
 
@@ -505,7 +445,7 @@ __device__ __forceinline__ void learn_nstep_body(const Net &on, const Net &on_ne
     const int t = threadIdx.x;
     const i64 i0 = (i64)blockIdx.x * P;
     const int nb = (int)(a.B - i0 < P ? a.B - i0 : P);
-    const int D = on.D, A = on.A, L = on.L;
+    const int D = on.In, A = on.Out, L = on.L;
     for (int p = t; p < R * D; p += kThreads) {  // (missing items: zero rows, never stored)
         const int r = p / D, k = p % D, it = r % P, st = r / P;
         const float x = it < nb ? a.obs[a.off[(i0 + it) * (NS + 1) + st] + k] : 0.f;
@@ -515,13 +455,13 @@ __device__ __forceinline__ void learn_nstep_body(const Net &on, const Net &on_ne
     __syncthreads();
     if constexpr (NZ) {
         // (forward_rows writes rows < `rows` of either buffer only: the s_1..s_n inputs in rows P.. of b0 outlive the s_0 pass)
-        const float *qs = forward_rows(on, P, b0, b1, S, wl, a.h, a.hstride, i0, nb);
+        const float *qs = forward_rows<true>(on, P, b0, b1, S, wl, a.h, a.hstride, i0, nb);
         for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
         __syncthreads();
-        const float *qn = forward_rows(on_next, NS * P, b0 + P * S, b1 + P * S, S, wl, nullptr, 0, 0, 0);
+        const float *qn = forward_rows<true>(on_next, NS * P, b0 + P * S, b1 + P * S, S, wl, nullptr, 0, 0, 0);
         for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qn[(p / A) * S + p % A];
     } else {
-        const float *qs = forward_rows(on, R, b0, b1, S, wl, a.h, a.hstride, i0, nb);
+        const float *qs = forward_rows<true>(on, R, b0, b1, S, wl, a.h, a.hstride, i0, nb);
         for (int p = t; p < nb * A; p += kThreads) a.q0[(i0 + p / A) * A + p % A] = qs[(p / A) * S + p % A];
         for (int p = t; p < NS * P * A; p += kThreads) qon_s[p] = qs[(P + p / A) * S + p % A];
     }
@@ -531,7 +471,7 @@ __device__ __forceinline__ void learn_nstep_body(const Net &on, const Net &on_ne
         b0[r * S + k] = it < nb ? a.obs[a.off[(i0 + it) * (NS + 1) + st] + k] : 0.f;
     }
     __syncthreads();
-    const float *qt = forward_rows(tg, NS * P, b0, b1, S, wl, nullptr, 0, 0, 0);
+    const float *qt = forward_rows<true>(tg, NS * P, b0, b1, S, wl, nullptr, 0, 0, 0);
     for (int p = t; p < NS * P * A; p += kThreads) qtg_s[p] = qt[(p / A) * S + p % A];
     __threadfence_block();  // (q0 rows are read back from memory below)
     __syncthreads();
@@ -546,32 +486,8 @@ __device__ __forceinline__ void learn_nstep_body(const Net &on, const Net &on_ne
     }
     __syncthreads();
     if (!on.head) {
-        // backward chain, row by row: d h_{L-1} from the Q seed (one non-zero column per row), then through every hidden layer's weight (k_mlpq_learn_rows)
-        float *dcur = d0, *dnext = d1;
-        for (int l = L - 1; l >= 0; l--) {
-            const int Wl = on.width(l);
-            const float *hl = a.h + (i64)l * a.hstride;
-            float *dhl = a.dh + (i64)l * a.hstride;
-            for (int p = t; p < nb * Wl; p += kThreads) {
-                const int r = p / Wl, k = p % Wl;
-                float g;
-                if (l == L - 1) {
-                    g = gsel[r] * on.wout[act0[r] * Wl + k];
-                } else {
-                    const int Wn = on.width(l + 1);
-                    const float *wn = on.weight(l + 1);
-                    g = 0.f;
-#pragma unroll 8
-                    for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
-                }
-                g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
-                dcur[r * S + k] = g;
-                dhl[(i0 + r) * Wl + k] = g;
-            }
-            __syncthreads();
-            float *tmp = dcur;
-            dcur = dnext, dnext = tmp;
-        }
+        // the backward chain as in k_mlpq_learn_rows: the Q seed has one non-zero column per row
+        srlxm::backward_rows<float>(on, on.L - 1, nb, i0, d0, d1, S, a.h, a.dh, a.hstride, [&](int r, int k, int Wl) { return gsel[r] * on.wout[act0[r] * Wl + k]; });
         return;
     }
     // the dueling head: d adv_k = g ((k == a_0) - 1/A) ("": g (k == a_0)), d v = g; through adv_layers.2 / v_layers.2 into the two hidden rows (d0: value branch,
@@ -690,7 +606,7 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_c51(const Net *__restri
     const int t = threadIdx.x;
     const i64 i0 = (i64)blockIdx.x * kItems;
     const int nb = (int)(a.it.B - i0 < kItems ? a.it.B - i0 : kItems);
-    const int D = on.D, L = on.L, N = a.it.N;
+    const int D = on.In, N = a.it.N;
     for (int p = t; p < kRows * D; p += kThreads) {  // (missing items: zero rows, never stored)
         const int r = p / D, k = p % D, it = r % kItems, which = r / kItems;
         const float x = it < nb ? a.obs[a.off[(i0 + it) * 2 + which] + k] : 0.f;
@@ -701,32 +617,13 @@ __global__ void __launch_bounds__(kThreads) k_mlpq_learn_c51(const Net *__restri
     const float *lg = forward_rows(on, kRows, b0, b1, S, wl, a.h, a.hstride, i0, nb);  // (returns behind a barrier: every read of the weight tile is done)
     srlxc::items_step<kItems>(a.it, i0, nb, lg, lg + kItems * S, S, pn, seed, ms, act0, row_loss);
     if (t < nb) a.loss_rows[i0 + t] = row_loss[t];
-    float *dcur = d0, *dnext = d1;
-    for (int l = L - 1; l >= 0; l--) {
-        const int Wl = on.width(l);
-        const float *hl = a.h + (i64)l * a.hstride;
-        float *dhl = a.dh + (i64)l * a.hstride;
-        for (int p = t; p < nb * Wl; p += kThreads) {
-            const int r = p / Wl, k = p % Wl;
-            float g = 0.f;
-            if (l == L - 1) {
-                const float *wa = on.wout + (i64)act0[r] * N * Wl + k, *sr = seed + r * srlxc::kMaxAtoms;
+    srlxm::backward_rows<float>(on, on.L - 1, nb, i0, d0, d1, S, a.h, a.dh, a.hstride, [&](int r, int k, int Wl) {
+        const float *wa = on.wout + (i64)act0[r] * N * Wl + k, *sr = seed + r * srlxc::kMaxAtoms;
+        float g = 0.f;
 #pragma unroll 8
-                for (int j = 0; j < N; j++) g = __builtin_fmaf(sr[j], wa[(i64)j * Wl], g);
-            } else {
-                const int Wn = on.width(l + 1);
-                const float *wn = on.weight(l + 1);
-#pragma unroll 8
-                for (int u = 0; u < Wn; u++) g = __builtin_fmaf(dnext[r * S + u], wn[(i64)u * Wl + k], g);
-            }
-            g = hl[(i0 + r) * Wl + k] > 0.f ? g : 0.f;
-            dcur[r * S + k] = g;
-            dhl[(i0 + r) * Wl + k] = g;
-        }
-        __syncthreads();
-        float *tmp = dcur;
-        dcur = dnext, dnext = tmp;
-    }
+        for (int j = 0; j < N; j++) g = __builtin_fmaf(sr[j], wa[(i64)j * Wl], g);
+        return g;
+    });
 }
 
 // srlx_c51_loss: the same item arithmetic on logits torch produced, one workgroup walking the batch kItems items at a time; thread 0 reduces the row terms in

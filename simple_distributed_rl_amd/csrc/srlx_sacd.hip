@@ -3,8 +3,8 @@
 // (concat(state, one-hot action) -> q_block -> Linear(1)).  The arithmetic contract is DESIGN.md 7m; its closed forms are srlx_sacd_math.h.
 //
 // The work is srlx_mlpq.hip's, not a GEMM's (<= 256 x 16 rows through layers of <= 512 units), and so is the shape: 256 threads over <= 16 rows, each layer's
-// weight staged through LDS in tiles of whole rows (dense(): srlx_mlpq.hip's thread mapping, float64 accumulators), hidden rows and their gradients kept in per-layer
-// planes, one thread per parameter for the weight gradient (a sum over the batch in item order) with torch's Adam in the same thread.  A <= 16, so the A
+// weight staged through LDS in tiles of whole rows (srlx_mlp_rows.h, which both files share: here with float64 accumulators), hidden rows and their gradients
+// kept in per-layer planes, one thread per parameter for the weight gradient (a sum over the batch in item order) with torch's Adam in the same thread.  A <= 16, so the A
 // one-hot rows of one item are rows of one workgroup: 16 / A items per workgroup wherever every action is evaluated.
 //   k_sacd_target   policy(s') and both TARGET Q-networks over every action of s', then y (soft_target)
 //   k_sacd_q_rows   blockIdx.y = q1 | q2: forward over (s, e_a), the squared error against y, the backward chain d loss / d h_l
@@ -18,6 +18,7 @@
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_adam_math.h"
 #include "srlx_common.h"
+#include "srlx_mlp_rows.h"
 #include "srlx_sacd_math.h"
 #include <cmath>
 
@@ -26,22 +27,14 @@ namespace {
 using i64 = int64_t;
 using u8 = unsigned char;
 
-constexpr int kThreads = 256;
-constexpr int kRows = 16;
-constexpr int kWTile = 8192;  // floats of the weight tile in LDS (32 KB)
+using srlxm::kRows;
+using srlxm::kThreads;
+using srlxm::kWTile;
 constexpr int kNets = 5;      // policy, q1_online, q1_target, q2_online, q2_target
 constexpr int kMaxSegs = 16;  // q1 + q2: 2 networks x 4 layers x (weight, bias)
 
-struct NetD {  // one network as the kernels read it, in device memory (scalar fields and selects: an array indexed by a run-time layer number goes to scratch)
-    int In, L, Out;  // inputs of layer 0 (the policy: D; a Q-network: D + A), hidden layers, outputs of layer L (A; 1)
-    int W0, W1, W2;
-    const float *w0, *w1, *w2, *w3, *b0, *b1, *b2, *b3;
-    __device__ int width(int l) const { return l == 0 ? W0 : (l == 1 ? W1 : W2); }
-    __device__ int in_of(int l) const { return l == 0 ? In : width(l - 1); }
-    __device__ int out_of(int l) const { return l < L ? width(l) : Out; }
-    __device__ const float *weight(int l) const { return l == 0 ? w0 : (l == 1 ? w1 : (l == 2 ? w2 : w3)); }
-    __device__ const float *bias(int l) const { return l == 0 ? b0 : (l == 1 ? b1 : (l == 2 ? b2 : b3)); }
-};
+// one network in device memory: the policy has In = D and Out = A, a Q-network In = D + A and Out = 1
+using NetD = srlxm::Layers;
 
 struct Seg {  // one parameter tensor of a trained network
     i64 end;       // running element count
@@ -88,64 +81,10 @@ size_t act_lds_bytes(const srlx_sacd *h) { return sizeof(float) * ((size_t)2 * k
 // lowers it under what an earlier, wider handle launches with
 constexpr size_t kActLdsCap = sizeof(float) * ((size_t)2 * kRows * (512 + 1) + kWTile);
 
-// y[r][u] = act(sum_k W[u][k] x[r][k] + b[u]) for rows r < rows (<= kRows), both in LDS; the thread mapping of srlx_mlpq.hip's dense().  Tensors are float32;
-// every sum ACCUMULATES in float64 (a product of two float32 values is exact there) and is rounded to float32 once, here, in the backward chain and in the
-// batch sum of k_sacd_grad.  Why: Adam's first steps are lr g / (|g| + eps), so a gradient entry that cancels to about eps (1e-8 beside terms of 1e-3) turns its
-// relative error into a parameter error of up to lr; with float32 chains of 272 and 512 terms in front of it such an entry was 30 % off.
-__device__ __forceinline__ void dense(const float *__restrict__ Wt, const float *__restrict__ bias, int In, int Out, int rows, const float *x, int sx, float *y, int sy,
-                                      bool relu, float *wl) {
-    const int t = threadIdx.x;
-    const int ws = In + 1;
-    const int tu_max = kWTile / ws < Out ? kWTile / ws : Out;
-    for (int u0 = 0; u0 < Out; u0 += tu_max) {
-        const int tu = Out - u0 < tu_max ? Out - u0 : tu_max;
-        __syncthreads();  // (the previous tile's readers are done)
-        const float *src = Wt + (i64)u0 * In;
-        for (int i = t; i < tu * In; i += kThreads) wl[(i / In) * ws + i % In] = src[i];
-        __syncthreads();
-        const int uc = tu < kThreads ? tu : kThreads;
-        const int G = kThreads / uc;
-        const int g = t / uc, ul = t % uc;
-        if (g >= G) continue;
-        const int nr = g < rows ? (rows - g + G - 1) / G : 0;
-        for (int u = ul; u < tu; u += uc) {
-            double acc[kRows];
-#pragma unroll
-            for (int j = 0; j < kRows; j++) acc[j] = 0.0;
-            const float *wr = wl + u * ws;
-#pragma unroll 4  // (four steps' LDS reads in flight; each row's chain of fused multiply-adds keeps its order)
-            for (int k = 0; k < In; k++) {
-                const double w = (double)wr[k];
-#pragma unroll
-                for (int j = 0; j < kRows; j++)
-                    if (j < nr) acc[j] = fma(w, (double)x[(g + j * G) * sx + k], acc[j]);
-            }
-            const double bu = (double)bias[u0 + u];
-#pragma unroll
-            for (int j = 0; j < kRows; j++)
-                if (j < nr) {
-                    const float z = (float)(acc[j] + bu);
-                    y[(g + j * G) * sy + u0 + u] = relu ? (z > 0.f ? z : 0.f) : z;
-                }
-        }
-    }
-}
-
-// the whole network over the rows in buf0; returns the buffer that holds the output rows.  `keep` (global; plane l: [max_batch][W_l] dense) receives rows
-// 0..kept-1 of every hidden layer's output as rows keep_row0.. of the plane.  Ends behind a barrier.
+// the whole network over the rows in buf0; returns the buffer that holds the output rows, behind a barrier (srlx_mlp_rows.h: the kept planes)
 __device__ __forceinline__ float *forward_rows(const NetD &n, int rows, float *buf0, float *buf1, int S, float *wl, float *keep, i64 keep_plane, i64 keep_row0,
                                                int kept) {
-    float *cur = buf0, *nxt = buf1;
-    for (int l = 0; l <= n.L; l++) {
-        const int In = n.in_of(l), Out = n.out_of(l);
-        dense(n.weight(l), n.bias(l), In, Out, rows, cur, S, nxt, S, l < n.L, wl);
-        __syncthreads();
-        if (keep && l < n.L)
-            for (int p = threadIdx.x; p < kept * Out; p += kThreads) keep[l * keep_plane + (keep_row0 + p / Out) * Out + p % Out] = nxt[(p / Out) * S + p % Out];
-        float *tmp = cur;
-        cur = nxt, nxt = tmp;
-    }
-    return cur;
+    return srlxm::forward_rows<double>(n, n.L + 1, rows, buf0, buf1, S, wl, keep, keep_plane, keep_row0, kept);
 }
 
 // rows r * A + a of buf = concat(state of item i0 + r, e_a), for r < nb
@@ -187,29 +126,6 @@ __device__ __forceinline__ void policy_logits(const NetD &pol, const float *__re
     const float *z = forward_rows(pol, nb, b0, b1, S, wl, keep, keep_plane, i0, nb);
     if (t < nb * A) lg[t] = z[(t / A) * S + t % A];
     __syncthreads();
-}
-
-// d loss / d h_l of every hidden layer for rows i0..i0+nb-1, row by row: `dnext` holds the rows' d loss / d (out layer output) (stride S); ReLU masks from the
-// kept planes.  Writes the planes of dh.
-__device__ __forceinline__ void backward_rows(const NetD &n, int nb, i64 i0, float *dcur, float *dnext, int S, const float *h, float *dh, i64 plane) {
-    for (int l = n.L - 1; l >= 0; l--) {
-        const int Wl = n.width(l), Wn = n.out_of(l + 1);
-        const float *wn = n.weight(l + 1);
-        const float *hl = h + (i64)l * plane;
-        float *dhl = dh + (i64)l * plane;
-        for (int p = threadIdx.x; p < nb * Wl; p += kThreads) {
-            const int r = p / Wl, k = p % Wl;
-            double acc = 0.0;
-#pragma unroll 8
-            for (int u = 0; u < Wn; u++) acc = fma((double)dnext[r * S + u], (double)wn[(i64)u * Wl + k], acc);
-            const float g = hl[(i0 + r) * Wl + k] > 0.f ? (float)acc : 0.f;
-            dcur[r * S + k] = g;
-            dhl[(i0 + r) * Wl + k] = g;
-        }
-        __syncthreads();
-        float *tmp = dcur;
-        dcur = dnext, dnext = tmp;
-    }
 }
 
 struct Batch {
@@ -274,7 +190,7 @@ __global__ void __launch_bounds__(kThreads) k_sacd_q_rows(const NetD *__restrict
     __syncthreads();
     if (t < nb) q[t * S] = dq;
     __syncthreads();
-    backward_rows(n, nb, i0, other, q, S, w.h + net_planes, w.dh + net_planes, w.plane);
+    srlxm::backward_rows<double>(n, n.L - 1, nb, i0, other, q, S, w.h + net_planes, w.dh + net_planes, w.plane);  // (q: the rows' d loss / d q in column 0)
 }
 
 struct PStep {
@@ -306,7 +222,7 @@ __global__ void __launch_bounds__(kThreads) k_sacd_policy(const NetD *__restrict
         w.dlast[(i0 + t / A) * kRows + t % A] = dz[t];
     }
     __syncthreads();
-    backward_rows(nets[0], nb, i0, b1, b0, S, w.h, w.dh, w.plane);
+    srlxm::backward_rows<double>(nets[0], nets[0].L - 1, nb, i0, b1, b0, S, w.h, w.dh, w.plane);  // (b0: the rows' d loss / d logits)
 }
 
 __global__ void __launch_bounds__(kThreads) k_sacd_forward(const NetD *__restrict__ nets, int target, i64 n, const float *__restrict__ states, float *__restrict__ logits,
