@@ -1412,6 +1412,61 @@ int srlx_sacd_act(srlx_sacd_t *h, int64_t n_rows, const float *d_obs_base, const
 int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const int64_t *d_offsets, const int32_t *d_actions, const float *d_rewards,
                          const float *d_terminated, float *d_states, float *d_next_states, float *d_onehot, uint8_t *d_done, void *stream);
 
+/* ---- V-PPO on flat observations (srlx_vppo.hip; srl/algorithms/ppo_v/torch_model.py:111-178) ----------------------------------------------------
+ * One actor-critic MLP in float32, torch layouts ([out][in] weights): a trunk  state [D] -> n_trunk x (Linear + ReLU)  (input value block + hidden block), a value
+ * branch  n_value x (Linear + ReLU) -> Linear(1)  and a policy branch  n_policy x (Linear + ReLU) -> the head: head = 0 categorical, Linear(n_out) logits;
+ * head = 1 Normal, Linear(n_out) locs and Linear(n_out) log-scales.  K = 1 (categorical) or n_out (Normal) log-probabilities per row, N = B K.
+ * Envelope, validated before any device call (SRLX_ERR_INVALID; srlx_last_error() names the entry point): D 1..256, trunk 1..3 layers, value and policy block
+ * 0..2 layers each, every layer 32..512 units in multiples of 32, categorical n_out 2..16, Normal n_out 1..8, max_batch 1..256.  Every tensor is float32; every
+ * sum over a layer's inputs or over the batch accumulates in float64 and is rounded to float32 once; a row's own arithmetic is float32 (srlx_vppo_math.h).
+ *   srlx_vppo_scratch_floats : floats of device scratch a handle of this shape owns; -1 outside the envelope.  Host arithmetic.
+ *   srlx_vppo_bind           : the parameter tensors by address in state-dict order: (weight, bias) of every trunk layer, every value-block layer, the value
+ *                              out layer, every policy-block layer, the head (logits; or locs, then log-scales): 2 (n_trunk + n_value + 1 + n_policy + 1 or 2).
+ *   srlx_vppo_bind_grads     : the caller's gradient tensors (same order and shapes), twice: d_grads receives the gradients after the norm clip (what Adam
+ *                              reads, torch's p.grad after clip_grad_norm_), d_raw_grads the gradients before it.  Every update writes both.
+ *   srlx_vppo_bind_adam      : exp_avg / exp_avg_sq (same order) and the optimiser steps already taken (the handle counts on from there, srlx_vppo_steps
+ *                              reads the count; -1 on a NULL handle); torch's Adam (srlx_adam_math.h).  Binding again restarts the optimiser from that count.
+ *   srlx_vppo_update         : the whole step of one batch in three launches.  Inputs: states / next states f32 [B][D]; actions i32 [B] (categorical) or f32
+ *                              [B][K] (Normal, the value before tanh); old log-probabilities f32 [B][K]; rewards, not-terminated, total rewards f32 [B].
+ *                                1. v = value(s), n_v = value(s'); q = r + (not_terminated discount) n_v; adv = q - v (a constant)
+ *                                2. categorical: p = softmax(logits), lp = log(clamp(p_a, 1e-7, 1)); gradient d lp / d logit_k = (k == a) - p_k where
+ *                                   p_a >= 1e-7, none below.  Normal: ls = clamp(raw log-scale, log_scale_lo, log_scale_hi) (gradient on the closed interval),
+ *                                   u = (a_j - loc_j) / exp(ls_j), lp_j = -0.5 log(2 pi) - ls_j - 0.5 u^2, and with `squashed` every lp_j loses
+ *                                   sum_i log(clamp(1 - tanh(a_i)^2, 1e-10, 1)) (float64; constant in the parameters)
+ *                                3. ratio_j = exp(lp_j - old_j) (a constant in the value losses)
+ *                                4. loss_value = mean_N huber_1(ratio_j q - v), loss_v_align = mean_N (ratio_j total_reward - v)^2; v is the target argument
+ *                                   and takes the gradient: -(d) or -sign(d), and -2 (ratio_j total_reward - v)
+ *                                5. loss_policy = -mean_N min(ratio_j adv, clamp(ratio_j, (float)(1 - clip), (float)(1 + clip)) adv); d / d ratio_j = adv on
+ *                                   the closed interval and where ratio_j adv is the smaller product, 0 elsewhere
+ *                                6. entropy_weight > 0: loss_e = mean_B sum_j exp(lp_j) lp_j, gradient (exp(lp_j) lp_j + exp(lp_j)) / B; otherwise loss_e = 0
+ *                                7. loss = loss_value + loss_align_coeff loss_v_align + loss_policy + entropy_weight loss_e; every parameter gradient is a
+ *                                   sum over the batch in row order (d_raw_grads)
+ *                                8. norm = sqrt(sum of all squared gradient entries) (float64 sum, float32 result); coef = min(1, max_grad_norm /
+ *                                   (norm + 1e-6)) in float32; d_grads = d_raw_grads * coef, always
+ *                                9. one Adam step at lr on d_grads
+ *                              Outputs: v, n_v f32 [B]; new_logpi f32 [B][K]; scalars f32 [5] = loss_value, loss_v_align, loss_policy, loss_e, norm.
+ *                              No atomics, every sum in a fixed order: equal inputs give equal bits.
+ *   srlx_vppo_forward        : n rows of states -> v f32 [n] (NULL: not wanted) and the head's outputs (NULL: not wanted): d_head0 f32 [n][n_out] logits
+ *                              or locs, d_head1 f32 [n][n_out] the log-scales clamped to [log_scale_lo, log_scale_hi] (Normal only, and then required with
+ *                              d_head0).  The same chains as the update's: v bit for bit what srlx_vppo_update writes for the same rows.  Needs
+ *                              srlx_vppo_bind only. */
+typedef struct srlx_vppo srlx_vppo_t;
+int64_t srlx_vppo_scratch_floats(int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
+                                 const int *policy_widths, int64_t max_batch);
+int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
+                     const int *policy_widths, int64_t max_batch, int device);
+int srlx_vppo_destroy(srlx_vppo_t *h);
+int srlx_vppo_bind(srlx_vppo_t *h, float *const *d_params);
+int srlx_vppo_bind_grads(srlx_vppo_t *h, float *const *d_grads, float *const *d_raw_grads);
+int srlx_vppo_bind_adam(srlx_vppo_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2, double eps);
+int64_t srlx_vppo_steps(const srlx_vppo_t *h);
+int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
+                     const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
+                     double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
+                     float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream);
+int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

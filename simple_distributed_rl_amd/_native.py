@@ -277,6 +277,15 @@ SIGNATURES = {
     "srlx_sacd_forward": (c_int, [c_p, c_i64, c_p, c_int, c_p, c_p, c_p]),
     "srlx_sacd_act": (c_int, [c_p, c_i64, c_p, c_p, c_u64, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "srlx_sacd_ring_batch": (c_int, [c_i64, c_int, c_int] + [c_p] * 10),
+    "srlx_vppo_scratch_floats": (c_i64, [c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_i64]),
+    "srlx_vppo_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_i64, c_int]),
+    "srlx_vppo_destroy": (c_int, [c_p]),
+    "srlx_vppo_bind": (c_int, [c_p, c_p]),
+    "srlx_vppo_bind_grads": (c_int, [c_p, c_p, c_p]),
+    "srlx_vppo_bind_adam": (c_int, [c_p, c_p, c_p, c_i64, c_f64, c_f64, c_f64]),
+    "srlx_vppo_steps": (c_i64, [c_p]),
+    "srlx_vppo_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 6 + [c_int, c_f64, c_f64] + [c_p] * 5),
+    "srlx_vppo_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

@@ -1,0 +1,583 @@
+// srlx_vppo.hip -- the whole update of V-PPO (srl/algorithms/ppo_v/torch_model.py:111-178) on flat observations in three launches, and a forward-only pass.
+// One actor-critic MLP: a trunk (input value block + hidden block, 1..3 ReLU layers), a value branch (0..2 ReLU layers + Linear(1)) and a policy branch
+// (0..2 ReLU layers + the head: Linear(A) logits, or Linear(k) locs and Linear(k) log-scales).  The arithmetic contract is DESIGN.md 7o and include/srlx.h; its
+// per-row closed forms are srlx_vppo_math.h.
+//
+// The work is srlx_sacd.hip's, not a GEMM's (<= 256 rows through <= 8 layers of <= 512 units), and so is the shape: 256 threads over <= 16 rows, each layer's
+// weight staged through LDS in tiles of whole rows (srlx_mlp_rows.h with float64 accumulators), hidden rows and their gradients kept in per-layer planes.
+//   k_vppo_rows     16 rows per workgroup: v(s'), then trunk, value branch and policy branch of s with the hidden rows kept, the row's losses and seeds
+//                   (the means are known factors 1 / (B K): no cross-row reduction), then the backward chains of both branches and of the trunk, whose
+//                   top layer sums what the two branches send down
+//   k_vppo_grad     one thread per parameter: the gradient before the clip, a sum over the batch in row order; every workgroup leaves the sum of its squares;
+//                   the last four threads of the launch reduce the four losses
+//   k_vppo_step     every workgroup sums the same partial squares in the same order (the norm), then one thread per parameter: the clipped gradient and Adam
+//   k_vppo_forward  v and the head's outputs of n rows
+// LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
+// widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
+// No atomics and a fixed order in every sum: equal inputs give equal bits.
+#include "srlx_adam_math.h"
+#include "srlx_common.h"
+#include "srlx_mlp_rows.h"
+#include "srlx_vppo_math.h"
+#include <cmath>
+
+namespace {
+
+using i64 = int64_t;
+
+using srlxm::kRows;
+using srlxm::kThreads;
+using srlxm::kWTile;
+using srlxm::Layers;
+using srlxv::kHeadCols;
+using srlxv::kNormalLs;
+constexpr int kMaxTensors = 20;  // 2 x (3 trunk + 2 value + value_out + 2 policy + 2 heads)
+constexpr int kPlanes = 7;       // trunk 0..2, value 3..4, policy 5..6
+constexpr size_t kLdsCap = sizeof(float) * ((size_t)3 * kRows * (512 + 1) + kWTile);
+
+struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
+    Layers trunk, value, policy;
+    const float *w_ls, *b_ls;
+};
+
+struct Seg {  // one parameter tensor
+    i64 end;          // running element count
+    int stride, in;   // row stride of dout; in = 0: a bias
+    const float *dout, *xin;  // [B][stride] d loss / d (layer output), [B][in] the layer's input rows (NULL: the caller's states)
+    float *p, *g, *graw, *m, *v;
+};
+
+}  // namespace
+
+struct srlx_vppo {
+    int D, head, A, Lt, Lv, Lp, device;  // head 0: categorical with A actions; 1: Normal with A = k elements
+    int Wt[3], Wv[2], Wp[2];
+    int wmax, nt;
+    i64 max_batch, elements, grad_blocks;
+    float *p[kMaxTensors], *g[kMaxTensors], *graw[kMaxTensors], *m[kMaxTensors], *v[kMaxTensors];
+    double beta1, beta2, eps;
+    i64 steps;
+    bool bound, grads_bound, adam_bound, table_ok, net_ok;
+    Net *d_net;  // (in device memory: a by-value kernel argument of this size was copied to scratch)
+    Seg *d_segs;
+    float *h, *dh;    // planes [kPlanes][max_batch][wmax]
+    float *dlast_v;   // [max_batch]: d loss / d v
+    float *dlast_p;   // [max_batch][kHeadCols]: d loss / d (head outputs)
+    float *rows;      // [4][max_batch]: the rows' loss sums
+    double *partials; // [grad_blocks]: sums of squared gradients
+};
+
+namespace {
+
+int n_tensors(const srlx_vppo *h) { return 2 * (h->Lt + h->Lv + 1 + h->Lp + (h->head ? 2 : 1)); }
+int lds_stride(const srlx_vppo *h) { return h->wmax + 1; }
+size_t lds_bytes(const srlx_vppo *h) { return sizeof(float) * ((size_t)3 * kRows * lds_stride(h) + kWTile); }
+
+struct Keep {  // planes of the hidden rows (NULL: not kept)
+    float *ht, *hv, *hp;
+    i64 plane;
+};
+
+// v (and, with `policy`, the head's outputs) of rows i0..i0+nb-1 of `states`: vs[r]; zs[r][kHeadCols] = logits, or locs at 0.. and RAW log-scales at kNormalLs...
+// The same chains whatever rows share the workgroup and whether the policy is asked for: k_vppo_forward and k_vppo_rows give the same bits.  Begins and ends
+// behind a barrier.
+__device__ __forceinline__ void forward_heads(const Net &n, const float *__restrict__ states, i64 i0, int nb, int D, float *b0, float *b1, float *b2, int S, float *wl,
+                                              Keep kp, bool policy, float *vs, float *zs) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    for (int p = t; p < nb * D; p += kThreads) b0[(p / D) * S + p % D] = states[(i0 + p / D) * D + p % D];
+    __syncthreads();
+    float *T = srlxm::forward_rows<double>(n.trunk, n.trunk.L, nb, b0, b1, S, wl, kp.ht, kp.plane, i0, kp.ht ? nb : 0);
+    const int Wtop = n.trunk.width(n.trunk.L - 1);
+    if (policy)
+        for (int p = t; p < nb * Wtop; p += kThreads) b2[(p / Wtop) * S + p % Wtop] = T[(p / Wtop) * S + p % Wtop];
+    const float *vo = srlxm::forward_rows<double>(n.value, n.value.L + 1, nb, T, T == b0 ? b1 : b0, S, wl, kp.hv, kp.plane, i0, kp.hv ? nb : 0);
+    if (t < nb) vs[t] = vo[t * S];
+    __syncthreads();
+    if (!policy) return;
+    for (int p = t; p < nb * Wtop; p += kThreads) b0[(p / Wtop) * S + p % Wtop] = b2[(p / Wtop) * S + p % Wtop];
+    __syncthreads();
+    const float *z = srlxm::forward_rows<double>(n.policy, n.policy.L + 1, nb, b0, b1, S, wl, kp.hp, kp.plane, i0, kp.hp ? nb : 0);
+    const float *hin = z == b0 ? b1 : b0;  // the head's input rows
+    const int HO = n.policy.Out;
+    if (t < nb * HO) zs[(t / HO) * kHeadCols + t % HO] = z[(t / HO) * S + t % HO];
+    if (n.w_ls) {
+        srlxm::dense<double>(n.w_ls, n.b_ls, n.policy.in_of(n.policy.L), HO, nb, hin, S, b2, S, false, wl);
+        __syncthreads();
+        if (t < nb * HO) zs[(t / HO) * kHeadCols + kNormalLs + t % HO] = b2[(t / HO) * S + t % HO];
+    }
+    __syncthreads();
+}
+
+// d loss / d h of a layer that up to three Linear layers read: sum over their output rows' seeds through their weights, one float64 chain
+struct Src {
+    const float *d;  // [rows][stride]
+    int stride, n;   // n = 0: none
+    const float *w;  // [n][W of the layer below]
+};
+struct SumSeed {
+    Src a, b, c;
+    __device__ float operator()(int r, int k, int Wl) const {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int u = 0; u < a.n; u++) acc = srlxm::fma_acc((double)a.d[r * a.stride + u], (double)a.w[(i64)u * Wl + k], acc);
+        for (int u = 0; u < b.n; u++) acc = srlxm::fma_acc((double)b.d[r * b.stride + u], (double)b.w[(i64)u * Wl + k], acc);
+        for (int u = 0; u < c.n; u++) acc = srlxm::fma_acc((double)c.d[r * c.stride + u], (double)c.w[(i64)u * Wl + k], acc);
+        return (float)acc;
+    }
+};
+
+struct Batch {
+    i64 B;
+    const float *s, *s2, *old_lp, *reward, *not_term, *total_reward;
+    const int32_t *action_i;  // categorical
+    const float *action_f;    // Normal
+    float *v, *n_v, *new_lp;
+};
+
+struct Work {
+    float *h, *dh, *dlast_v, *dlast_p, *rows;
+    i64 plane, max_batch;
+};
+
+__global__ void __launch_bounds__(kThreads) k_vppo_rows(const Net *__restrict__ net, Batch a, Work w, srlxv::Cfg c, int D, int K, int S) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *b2 = sm + 2 * kRows * S, *wl = sm + 3 * kRows * S;
+    __shared__ float vs[kRows], nvs[kRows], zs[kRows * kHeadCols], dzs[kRows * kHeadCols];
+    const Net &n = *net;
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * kRows;
+    const int nb = (int)(a.B - i0 < kRows ? a.B - i0 : kRows);
+    const i64 plane = w.plane;
+    float *ht = w.h, *hv = w.h + 3 * plane, *hp = w.h + 5 * plane;
+    float *dht = w.dh, *dhv = w.dh + 3 * plane, *dhp = w.dh + 5 * plane;
+    forward_heads(n, a.s2, i0, nb, D, b0, b1, b2, S, wl, Keep{nullptr, nullptr, nullptr, 0}, false, nvs, nullptr);
+    forward_heads(n, a.s, i0, nb, D, b0, b1, b2, S, wl, Keep{ht, hv, hp, plane}, true, vs, zs);
+    const bool normal = n.w_ls != nullptr;
+    for (int p = t; p < nb * kHeadCols; p += kThreads) dzs[p] = 0.f;
+    __syncthreads();
+    if (t < nb) {
+        const i64 b = i0 + t;
+        const float v = vs[t], nv = nvs[t];
+        const float q = a.reward[b] + (a.not_term[b] * c.discount) * nv;
+        srlxv::RowSums s{0.f, 0.f, 0.f, 0.f, 0.f};
+        if (normal) {
+            srlxv::normal_row(c, zs + t * kHeadCols, K, a.action_f + b * K, a.old_lp + b * K, q, a.total_reward[b], v, s, dzs + t * kHeadCols, a.new_lp + b * K);
+        } else {
+            const int A = n.policy.Out, act = a.action_i[b];
+            a.new_lp[b] = srlxv::categorical_row(c, zs + t * kHeadCols, A, act < 0 ? 0 : (act >= A ? A - 1 : act), a.old_lp[b], q, a.total_reward[b], v, s, dzs + t * kHeadCols);
+        }
+        a.v[b] = v, a.n_v[b] = nv;
+        w.rows[b] = s.huber, w.rows[w.max_batch + b] = s.align, w.rows[2 * w.max_batch + b] = s.policy, w.rows[3 * w.max_batch + b] = s.ent;
+        w.dlast_v[b] = s.dv;
+        b0[t * S] = s.dv;  // the value branch's rows of d loss / d (out layer output), column 0
+    }
+    __syncthreads();
+    for (int p = t; p < nb * kHeadCols; p += kThreads) w.dlast_p[i0 * kHeadCols + p] = dzs[p];
+    // ---- value branch: the bottom rows (what the trunk's top layer reads) end in buffer vb
+    const int Lv = n.value.L, Lp = n.policy.L;
+    int vb = 0;
+    if (Lv >= 1) {
+        srlxm::backward_rows<double>(n.value, Lv - 1, nb, i0, b1, b0, S, hv, dhv, plane);
+        vb = (Lv & 1) ? 1 : 0;
+    }
+    float *VB = vb == 0 ? b0 : b1;
+    float *P = vb == 0 ? b1 : b0, *Q = b2;  // the two other buffers
+    const int HO = n.policy.Out;
+    const Src none{nullptr, 0, 0, nullptr};
+    const Src head{dzs, kHeadCols, HO, n.policy.weight(Lp)};
+    const Src head_ls = normal ? Src{dzs + kNormalLs, kHeadCols, HO, n.w_ls} : none;
+    const Src val{VB, S, Lv >= 1 ? n.value.W0 : 1, n.value.w0};  // (Lv = 0: column 0, through the out layer itself)
+    if (Lp >= 1) {
+        srlxm::backward_rows<double>(n.policy, Lp - 1, nb, i0, P, Q, S, hp, dhp, plane, SumSeed{head, head_ls, none});
+        float *PB = (Lp & 1) ? P : Q, *F = (Lp & 1) ? Q : P;
+        srlxm::backward_rows<double>(n.trunk, n.trunk.L - 1, nb, i0, F, VB, S, ht, dht, plane, SumSeed{val, Src{PB, S, n.policy.W0, n.policy.w0}, none});
+    } else {
+        srlxm::backward_rows<double>(n.trunk, n.trunk.L - 1, nb, i0, P, Q, S, ht, dht, plane, SumSeed{val, head, head_ls});
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_vppo_forward(const Net *__restrict__ net, i64 rows, const float *__restrict__ states, float *__restrict__ v, float *__restrict__ head0,
+                                                           float *__restrict__ head1, float ls_lo, float ls_hi, int D, int S) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *b2 = sm + 2 * kRows * S, *wl = sm + 3 * kRows * S;
+    __shared__ float vs[kRows], zs[kRows * kHeadCols];
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * kRows;
+    const int nb = (int)(rows - i0 < kRows ? rows - i0 : kRows);
+    const Net &n = *net;
+    forward_heads(n, states, i0, nb, D, b0, b1, b2, S, wl, Keep{nullptr, nullptr, nullptr, 0}, head0 != nullptr, vs, zs);
+    if (v && t < nb) v[i0 + t] = vs[t];
+    const int HO = n.policy.Out;
+    if (head0 && t < nb * HO) {
+        const int r = t / HO, j = t % HO;
+        head0[(i0 + r) * HO + j] = zs[r * kHeadCols + j];
+        if (head1) head1[(i0 + r) * HO + j] = srlxv::clampf(zs[r * kHeadCols + kNormalLs + j], ls_lo, ls_hi);
+    }
+}
+
+struct GradArgs {
+    const Seg *segs;
+    int nseg;
+    i64 B;
+    const float *xin0;  // the caller's states: the input rows of the first layer
+    const float *rows;
+    i64 max_batch;
+    double inv_n, inv_b;
+    int entropy;
+    double *partials;
+    float *out;  // loss_value, loss_v_align, loss_policy, loss_e, norm
+};
+
+__global__ void __launch_bounds__(kThreads) k_vppo_grad(GradArgs a) {
+    __shared__ double sq[kThreads];
+    const int t = threadIdx.x;
+    const i64 i = (i64)blockIdx.x * kThreads + t;
+    const i64 last = (i64)gridDim.x * kThreads;
+    double mine = 0.0;
+    if (i >= last - 4) {
+        // (the last block's last four threads: the launch rounds the element count + 4 up, so they exist and own no element)
+        const int k = (int)(i - (last - 4));
+        double s = 0.0;
+        for (i64 b = 0; b < a.B; b++) s += (double)a.rows[k * a.max_batch + b];
+        a.out[k] = k == 0 || k == 1 ? (float)(s * a.inv_n) : (k == 2 ? (float)(-s * a.inv_n) : (a.entropy ? (float)(s * a.inv_b) : 0.f));
+    } else if (i < a.segs[a.nseg - 1].end) {
+        int s = 0;
+        while (i >= a.segs[s].end) s++;
+        const Seg sg = a.segs[s];
+        const i64 e = i - (s ? a.segs[s - 1].end : 0);
+        const int St = sg.stride, In = sg.in;
+        double acc = 0.0;
+        if (In) {
+            const int u = (int)(e / In), k = (int)(e % In);
+            const float *dout = sg.dout + u, *xin = (sg.xin ? sg.xin : a.xin0) + k;
+#pragma unroll 8
+            for (int b = 0; b < (int)a.B; b++) acc = fma((double)dout[(i64)b * St], (double)xin[(i64)b * In], acc);
+        } else {
+            const float *dout = sg.dout + e;
+#pragma unroll 8
+            for (int b = 0; b < (int)a.B; b++) acc += (double)dout[(i64)b * St];
+        }
+        const float g = (float)acc;
+        sg.graw[e] = g;
+        mine = (double)g * (double)g;
+    }
+    sq[t] = mine;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if (t < w) sq[t] += sq[t + w];
+        __syncthreads();
+    }
+    if (t == 0) a.partials[blockIdx.x] = sq[0];
+}
+
+struct StepArgs {
+    const Seg *segs;
+    int nseg;
+    const double *partials;
+    i64 n_partials;
+    float max_norm;
+    double lr, beta1, beta2, eps;
+    i64 steps_taken;
+    float *out;
+};
+
+__global__ void __launch_bounds__(kThreads) k_vppo_step(StepArgs a) {
+    __shared__ double sq[kThreads];
+    const int t = threadIdx.x;
+    double mine = 0.0;
+    for (i64 k = t; k < a.n_partials; k += kThreads) mine += a.partials[k];
+    sq[t] = mine;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if (t < w) sq[t] += sq[t + w];
+        __syncthreads();
+    }
+    // clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)) in float32, and the gradients are always multiplied by it
+    const float norm = (float)sqrt(sq[0]);
+    const float coef = fminf(1.f, a.max_norm / (norm + 1e-6f));
+    const i64 i = (i64)blockIdx.x * kThreads + t;
+    if (i == 0) a.out[4] = norm;
+    if (i >= a.segs[a.nseg - 1].end) return;
+    int s = 0;
+    while (i >= a.segs[s].end) s++;
+    const Seg sg = a.segs[s];
+    const i64 e = i - (s ? a.segs[s - 1].end : 0);
+    const float g = sg.graw[e] * coef;
+    sg.g[e] = g;
+    const srlx::AdamCoef c = srlx::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.steps_taken);
+    float p = sg.p[e], m = sg.m[e], v = sg.v[e];
+    srlx::adam_one_foreach(p, g, m, v, c);
+    sg.p[e] = p, sg.m[e] = m, sg.v[e] = v;
+}
+
+bool widths_ok(int n, int lo, int hi, const int *w) {
+    if (n < lo || n > hi || (n && !w)) return false;
+    for (int l = 0; l < n; l++)
+        if (w[l] < 32 || w[l] > 512 || w[l] % 32) return false;
+    return true;
+}
+
+int check_shape(const char *who, int D, int head, int A, int nt, const int *tw, int nv, const int *vw, int np, const int *pw, i64 max_batch) {
+    SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
+    SRLX_REQUIRE(head == 0 || head == 1, "%s: head kind %d (0 categorical, 1 Normal)", who, head);
+    SRLX_REQUIRE(head == 1 || (A >= 2 && A <= 16), "%s: %d actions (2..16)", who, A);
+    SRLX_REQUIRE(head == 0 || (A >= 1 && A <= 8), "%s: %d action elements (1..8)", who, A);
+    SRLX_REQUIRE(widths_ok(nt, 1, 3, tw), "%s: the trunk is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(widths_ok(nv, 0, 2, vw), "%s: the value block is 0..2 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(widths_ok(np, 0, 2, pw), "%s: the policy block is 0..2 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(max_batch >= 1 && max_batch <= 256, "%s: max_batch %lld (1..256)", who, (long long)max_batch);
+    return SRLX_OK;
+}
+
+int wmax_of(int D, int nt, const int *tw, int nv, const int *vw, int np, const int *pw) {
+    int w = D > kHeadCols ? D : kHeadCols;
+    for (int l = 0; l < nt; l++) w = tw[l] > w ? tw[l] : w;
+    for (int l = 0; l < nv; l++) w = vw[l] > w ? vw[l] : w;
+    for (int l = 0; l < np; l++) w = pw[l] > w ? pw[l] : w;
+    return w;
+}
+
+// (out, in) of every Linear in state-dict order
+int linear_shapes(const srlx_vppo *h, int (*shape)[2]) {
+    int n = 0, in = h->D;
+    for (int l = 0; l < h->Lt; l++) shape[n][0] = h->Wt[l], shape[n][1] = in, in = h->Wt[l], n++;
+    const int top = in;
+    for (int l = 0; l < h->Lv; l++) shape[n][0] = h->Wv[l], shape[n][1] = in, in = h->Wv[l], n++;
+    shape[n][0] = 1, shape[n][1] = in, n++;
+    in = top;
+    for (int l = 0; l < h->Lp; l++) shape[n][0] = h->Wp[l], shape[n][1] = in, in = h->Wp[l], n++;
+    shape[n][0] = h->A, shape[n][1] = in, n++;
+    if (h->head) shape[n][0] = h->A, shape[n][1] = in, n++;
+    return n;
+}
+
+i64 elements_of(const srlx_vppo *h) {
+    int shape[kMaxTensors / 2][2];
+    const int n = linear_shapes(h, shape);
+    i64 e = 0;
+    for (int l = 0; l < n; l++) e += (i64)shape[l][0] * shape[l][1] + shape[l][0];
+    return e;
+}
+
+Layers chain(int In, int L, const int *W, int Out, float *const *p) {
+    Layers n;
+    n.In = In, n.L = L, n.Out = Out;
+    n.W0 = L > 0 ? W[0] : 0, n.W1 = L > 1 ? W[1] : 0, n.W2 = L > 2 ? W[2] : 0;
+    const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l <= L && l < 4; l++)
+        if (p[2 * l]) w[l] = p[2 * l], b[l] = p[2 * l + 1];
+    n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
+    return n;
+}
+
+Net net_of(const srlx_vppo *h) {
+    Net n;
+    float *tr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 2 * h->Lt; i++) tr[i] = h->p[i];  // (the trunk has no layer of its own behind its hidden ones: slot Lt stays NULL)
+    n.trunk = chain(h->D, h->Lt, h->Wt, 0, tr);
+    const int top = h->Wt[h->Lt - 1];
+    n.value = chain(top, h->Lv, h->Wv, 1, h->p + 2 * h->Lt);
+    float *const *pp = h->p + 2 * (h->Lt + h->Lv + 1);
+    n.policy = chain(top, h->Lp, h->Wp, h->A, pp);
+    n.w_ls = h->head ? pp[2 * (h->Lp + 1)] : nullptr;
+    n.b_ls = h->head ? pp[2 * (h->Lp + 1) + 1] : nullptr;
+    return n;
+}
+
+int upload_net(srlx_vppo *h) {
+    const Net n = net_of(h);
+    SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(n), hipMemcpyHostToDevice));
+    h->net_ok = true;
+    return SRLX_OK;
+}
+
+int upload_table(srlx_vppo *h) {
+    Seg segs[kMaxTensors];
+    memset(segs, 0, sizeof(segs));
+    int shape[kMaxTensors / 2][2];
+    const int nl = linear_shapes(h, shape);
+    const i64 plane = h->max_batch * h->wmax;
+    const float *ht = h->h, *hv = h->h + 3 * plane, *hp = h->h + 5 * plane;
+    const float *dht = h->dh, *dhv = h->dh + 3 * plane, *dhp = h->dh + 5 * plane;
+    const float *top = ht + (i64)(h->Lt - 1) * plane;
+    i64 end = 0;
+    int s = 0;
+    for (int l = 0; l < nl; l++) {
+        const float *dout, *xin;
+        int stride = shape[l][0];
+        int k = l;
+        if (k < h->Lt) {
+            dout = dht + (i64)k * plane, xin = k ? ht + (i64)(k - 1) * plane : nullptr;
+        } else if ((k -= h->Lt) < h->Lv) {
+            dout = dhv + (i64)k * plane, xin = k ? hv + (i64)(k - 1) * plane : top;
+        } else if ((k -= h->Lv) == 0) {
+            dout = h->dlast_v, xin = h->Lv ? hv + (i64)(h->Lv - 1) * plane : top;
+        } else if ((k -= 1) < h->Lp) {
+            dout = dhp + (i64)k * plane, xin = k ? hp + (i64)(k - 1) * plane : top;
+        } else {
+            k -= h->Lp;  // 0: logits or locs, 1: log-scales
+            dout = h->dlast_p + (k ? kNormalLs : 0), stride = kHeadCols, xin = h->Lp ? hp + (i64)(h->Lp - 1) * plane : top;
+        }
+        for (int j = 0; j < 2; j++, s++) {
+            Seg &g = segs[s];
+            end += j == 0 ? (i64)shape[l][0] * shape[l][1] : shape[l][0];
+            g.end = end, g.stride = stride, g.in = j == 0 ? shape[l][1] : 0;
+            g.dout = dout, g.xin = xin;
+            g.p = h->p[s], g.g = h->g[s], g.graw = h->graw[s], g.m = h->m[s], g.v = h->v[s];
+        }
+    }
+    SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
+    h->table_ok = true;
+    return SRLX_OK;
+}
+
+void fill(srlx_vppo *h, int D, int head, int A, int nt, const int *tw, int nv, const int *vw, int np, const int *pw, i64 max_batch, int device) {
+    h->D = D, h->head = head, h->A = A, h->Lt = nt, h->Lv = nv, h->Lp = np, h->device = device, h->max_batch = max_batch;
+    for (int l = 0; l < nt; l++) h->Wt[l] = tw[l];
+    for (int l = 0; l < nv; l++) h->Wv[l] = vw[l];
+    for (int l = 0; l < np; l++) h->Wp[l] = pw[l];
+    h->wmax = wmax_of(D, nt, tw, nv, vw, np, pw);
+    h->nt = n_tensors(h);
+    h->elements = elements_of(h);
+    h->grad_blocks = (h->elements + 4 + kThreads - 1) / kThreads;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t srlx_vppo_scratch_floats(int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
+                                 const int *policy_widths, int64_t max_batch) {
+    if (check_shape("vppo_scratch_floats", obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch) != SRLX_OK)
+        return -1;
+    srlx_vppo h{};
+    fill(&h, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch, 0);
+    return 2 * kPlanes * max_batch * h.wmax + max_batch + max_batch * kHeadCols + 4 * max_batch + 2 * h.grad_blocks;
+}
+
+int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
+                     const int *policy_widths, int64_t max_batch, int device) {
+    SRLX_REQUIRE(out, "vppo_create: NULL handle pointer");
+    *out = nullptr;
+    SRLX_TRY(check_shape("vppo_create", obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch));
+    srlx::DeviceGuard g(device);
+    SRLX_REQUIRE(g.ok, "vppo_create: device %d unavailable", device);
+    srlx_vppo *h = new srlx_vppo();
+    fill(h, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch, device);
+    const size_t plane = (size_t)max_batch * h->wmax;
+    hipError_t e = hipMalloc((void **)&h->d_segs, sizeof(Seg) * kMaxTensors);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_net, sizeof(Net));
+    if (e == hipSuccess) e = hipMalloc((void **)&h->h, sizeof(float) * kPlanes * plane);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dh, sizeof(float) * kPlanes * plane);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dlast_v, sizeof(float) * max_batch);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->dlast_p, sizeof(float) * max_batch * kHeadCols);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rows, sizeof(float) * 4 * max_batch);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->partials, sizeof(double) * h->grad_blocks);
+    if (e == hipSuccess) e = hipMemset(h->dlast_p, 0, sizeof(float) * max_batch * kHeadCols);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
+    if (e != hipSuccess) {
+        srlx_vppo_destroy(h);
+        srlx::set_error("vppo_create: device set-up failed: %s", hipGetErrorString(e));
+        return SRLX_ERR_NOMEM;
+    }
+    *out = h;
+    return SRLX_OK;
+}
+
+int srlx_vppo_destroy(srlx_vppo_t *h) {
+    if (!h) return SRLX_OK;
+    srlx::DeviceGuard g(h->device);
+    for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->h, (void *)h->dh, (void *)h->dlast_v, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials})
+        if (p) (void)hipFree(p);
+    delete h;
+    return SRLX_OK;
+}
+
+int srlx_vppo_bind(srlx_vppo_t *h, float *const *d_params) {
+    SRLX_REQUIRE(h && d_params, "vppo_bind: NULL argument");
+    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_params[i], "vppo_bind: parameter %d is NULL", i);
+    for (int i = 0; i < h->nt; i++) h->p[i] = d_params[i];
+    h->bound = true, h->table_ok = h->net_ok = false;
+    return SRLX_OK;
+}
+
+int srlx_vppo_bind_grads(srlx_vppo_t *h, float *const *d_grads, float *const *d_raw_grads) {
+    SRLX_REQUIRE(h && d_grads && d_raw_grads, "vppo_bind_grads: NULL argument");
+    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_grads[i] && d_raw_grads[i], "vppo_bind_grads: gradient tensor %d is NULL", i);
+    for (int i = 0; i < h->nt; i++) h->g[i] = d_grads[i], h->graw[i] = d_raw_grads[i];
+    h->grads_bound = true, h->table_ok = false;
+    return SRLX_OK;
+}
+
+int srlx_vppo_bind_adam(srlx_vppo_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2, double eps) {
+    SRLX_REQUIRE(h && d_exp_avg && d_exp_avg_sq, "vppo_bind_adam: NULL argument");
+    SRLX_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0, "vppo_bind_adam: betas in [0, 1) and eps > 0");
+    SRLX_REQUIRE(steps_taken >= 0, "vppo_bind_adam: the step count is non-negative");
+    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_exp_avg[i] && d_exp_avg_sq[i], "vppo_bind_adam: state %d is NULL", i);
+    for (int i = 0; i < h->nt; i++) h->m[i] = d_exp_avg[i], h->v[i] = d_exp_avg_sq[i];
+    h->steps = steps_taken, h->beta1 = beta1, h->beta2 = beta2, h->eps = eps;
+    h->adam_bound = true, h->table_ok = false;
+    return SRLX_OK;
+}
+
+int64_t srlx_vppo_steps(const srlx_vppo_t *h) {
+    if (!h) {
+        srlx::set_error("vppo_steps: NULL handle");
+        return -1;
+    }
+    return h->steps;
+}
+
+int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
+                      void *stream) {
+    SRLX_REQUIRE(h && d_states, "vppo_forward: NULL handle or states");
+    SRLX_REQUIRE(h->bound, "vppo_forward: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(n >= 1 && n <= (int64_t)1 << 24, "vppo_forward: %lld rows (1..2^24)", (long long)n);
+    SRLX_REQUIRE(d_v || d_head0, "vppo_forward: nothing to write");
+    SRLX_REQUIRE(!d_head1 || (d_head0 && h->head == 1), "vppo_forward: log-scales go with locs, on a Normal head");
+    SRLX_REQUIRE(!(h->head == 1 && d_head0 && !d_head1), "vppo_forward: a Normal head writes locs and log-scales");
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_forward: the log-scale clamp's ends are ordered");
+    srlx::DeviceGuard g(h->device);
+    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    hipLaunchKernelGGL(k_vppo_forward, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states, d_v,
+                       d_head0, d_head1, (float)log_scale_lo, (float)log_scale_hi, h->D, lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
+                     const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
+                     double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
+                     float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream) {
+    SRLX_REQUIRE(h, "vppo_update: NULL handle");
+    SRLX_REQUIRE(h->bound && h->grads_bound && h->adam_bound, "vppo_update: bind the parameters, the gradient tensors and the Adam state first");
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "vppo_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_states && d_next_states && d_actions && d_old_logpi && d_rewards && d_not_terminated && d_total_rewards && d_v && d_n_v && d_new_logpi && d_scalars,
+                 "vppo_update: NULL argument");
+    SRLX_REQUIRE(lr >= 0 && clip_range >= 0 && max_grad_norm > 0, "vppo_update: lr and clip_range are non-negative, max_grad_norm positive");
+    SRLX_REQUIRE(squashed == 0 || squashed == 1, "vppo_update: squashed is 0 or 1");
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_update: the log-scale clamp's ends are ordered");
+    srlx::DeviceGuard g(h->device);
+    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    if (!h->table_ok) SRLX_TRY(upload_table(h));
+    hipStream_t st = (hipStream_t)stream;
+    const int K = h->head ? h->A : 1;
+    const double N = (double)batch * K;
+    srlxv::Cfg c{(float)discount, (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)entropy_weight, (float)loss_align_coeff, (float)(1.0 / N),
+                 (float)(1.0 / (double)batch), (float)log_scale_lo, (float)log_scale_hi, squashed};
+    Batch b{(i64)batch, d_states, d_next_states, d_old_logpi, d_rewards, d_not_terminated, d_total_rewards, h->head ? nullptr : (const int32_t *)d_actions,
+            h->head ? (const float *)d_actions : nullptr, d_v, d_n_v, d_new_logpi};
+    Work w{h->h, h->dh, h->dlast_v, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
+    hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
+    GradArgs ga{h->d_segs, h->nt, (i64)batch, d_states, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, h->partials, d_scalars};
+    hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
+    StepArgs sa{h->d_segs, h->nt, h->partials, h->grad_blocks, (float)max_grad_norm, lr, h->beta1, h->beta2, h->eps, h->steps, d_scalars};
+    hipLaunchKernelGGL(k_vppo_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
+    SRLX_HIP(hipGetLastError());
+    h->steps++;
+    return SRLX_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,107 @@
+// srlx_vppo_math.h -- the per-row arithmetic of V-PPO's update (srl/algorithms/ppo_v/torch_model.py:136-171), shared by the kernels of srlx_vppo.hip.  The
+// categorical log-softmax and the Normal constants are srlx_ppo_math.h's (cat_lse, cat_logp, kHalfLog2Pi, clampf): the same arithmetic, one definition.
+// Everything here is one row's float32 arithmetic; sums over the batch and over a layer's inputs live in the kernels (float64, rounded once).  DESIGN.md 7o.
+//
+// One row b with K log-probabilities (K = 1: categorical, K = k: Normal), N = B K, v = v(s_b), q = r + not_terminated discount v(s'_b), adv = q - v:
+//   ratio_j = expf(lp_j - old_j)
+//   Huber (delta 1) of d = ratio_j q - v: 0.5 d^2 where |d| < 1, |d| - 0.5 elsewhere; v is the TARGET, d huber / d v = -d or -sign(d)
+//   align: (ratio_j tr - v)^2, d / d v = -2 (ratio_j tr - v)
+//   surrogate: min(ratio_j adv, clamp(ratio_j, lo, hi) adv); torch.minimum halves the gradient between its arguments at a tie and clamp passes it on the
+//           closed interval, so inside [lo, hi] (always a tie) d / d ratio = adv; outside, adv where the unclipped product is the smaller one and 0 elsewhere
+//   entropy (entropy_weight > 0 only): -expf(lp_j) lp_j per element; loss_e = mean_b sum_j expf(lp_j) lp_j
+#pragma once
+#include "srlx_ppo_math.h"
+
+namespace srlxv {
+
+using srlxp::clampf;
+
+constexpr int kHeadCols = 16;        // columns of a head row in LDS and in the seed table: A logits, or k locs at 0.. and k log-scales at kNormalLs..
+constexpr int kNormalLs = 8;
+constexpr float kProbFloor = 1e-7f;  // categorical_dist_block.py:53-54 (written 10e-8)
+constexpr double kSquashFloor = 1e-10;  // normal_dist_block.py:20-29
+
+struct Cfg {
+    float discount, clip_lo, clip_hi, entropy_w, align_c;
+    float inv_n, inv_b;  // 1 / (B K), 1 / B
+    float ls_lo, ls_hi;  // the log-scale clamp (-inf / +inf: none)
+    int squashed;
+};
+
+struct RowSums {
+    float huber, align, policy, ent;  // sums over the row's K elements: Huber terms, squared alignment errors, surrogate terms, expf(lp) lp
+    float dv;                         // d loss / d v of the row
+};
+
+// one element of the value losses; adds its part of d loss / d v (the means' 1 / N and the alignment coefficient included)
+__device__ __forceinline__ void value_terms(const Cfg &c, float ratio, float q, float tr, float v, RowSums &s) {
+    const float d = ratio * q - v, ad = fabsf(d);
+    s.huber += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+    const float dh = ad < 1.f ? -d : (d > 0.f ? -1.f : 1.f);
+    const float e = ratio * tr - v;
+    s.align += e * e;
+    s.dv += c.inv_n * (dh + c.align_c * (-2.f * e));
+}
+
+// one element of the policy losses given its log-probability; returns d loss / d lp
+__device__ __forceinline__ float policy_terms(const Cfg &c, float lp, float ratio, float adv, RowSums &s) {
+    const float rc = clampf(ratio, c.clip_lo, c.clip_hi);
+    const float lu = ratio * adv, lc = rc * adv;
+    s.policy += fminf(lu, lc);
+    const bool inside = ratio >= c.clip_lo && ratio <= c.clip_hi;
+    const float g_ratio = (inside || lu < lc) ? adv : 0.f;
+    float g = -c.inv_n * g_ratio * ratio;
+    if (c.entropy_w > 0.f) {
+        const float elp = expf(lp);
+        s.ent += elp * lp;
+        g += c.entropy_w * c.inv_b * (elp * lp + elp);
+    }
+    return g;
+}
+
+// Categorical row: z [A] logits (LDS) -> lp of action a, the row's sums, d loss / d z_k into dz [A].  lp = log(clamp(p_a, 1e-7, 1)) with p = softmax(z): inside
+// the clamp that is the log-softmax itself, below it log(1e-7) with no gradient.
+__device__ __forceinline__ float categorical_row(const Cfg &c, const float *z, int A, int a, float old_lp, float q, float tr, float v, RowSums &s, float *dz) {
+    float m, lse;
+    srlxp::cat_lse(z, A, m, lse);
+    const float xa = srlxp::cat_logp(z[a], m, lse);
+    const bool pass = expf(xa) >= kProbFloor;
+    const float lp = pass ? xa : logf(kProbFloor);
+    const float ratio = expf(lp - old_lp);
+    value_terms(c, ratio, q, tr, v, s);
+    const float g_lp = policy_terms(c, lp, ratio, q - v, s);
+    for (int k = 0; k < A; k++) dz[k] = pass ? g_lp * ((k == a ? 1.f : 0.f) - expf(srlxp::cat_logp(z[k], m, lse))) : 0.f;
+    return lp;
+}
+
+// the squashing correction of one row, sum_i log(clamp(1 - tanh(a_i)^2, 1e-10, 1)), in float64 (1 - tanh^2 cancels in float32); constant in the parameters
+__device__ __forceinline__ float squash_correction(const float *act, int k) {
+    double s = 0.0;
+    for (int i = 0; i < k; i++) {
+        const double th = tanh((double)act[i]);
+        const double x = 1.0 - th * th;
+        s += log(x < kSquashFloor ? kSquashFloor : (x > 1.0 ? 1.0 : x));
+    }
+    return (float)s;
+}
+
+// Normal row: z = k locs at 0.. and k raw log-scales at kNormalLs.. (LDS) -> lp [k] (global), the row's sums, the seeds into dz in the same layout
+__device__ __forceinline__ void normal_row(const Cfg &c, const float *z, int k, const float *act, const float *old_lp, float q, float tr, float v, RowSums &s,
+                                           float *dz, float *lp_out) {
+    const float corr = c.squashed ? squash_correction(act, k) : 0.f;
+    for (int j = 0; j < k; j++) {
+        const float loc = z[j], lsr = z[kNormalLs + j];
+        const float ls = clampf(lsr, c.ls_lo, c.ls_hi);
+        const float sd = expf(ls);
+        const float u = (act[j] - loc) / sd;
+        const float lp = (-srlxp::kHalfLog2Pi - ls - 0.5f * (u * u)) - corr;
+        lp_out[j] = lp;
+        const float ratio = expf(lp - old_lp[j]);
+        value_terms(c, ratio, q, tr, v, s);
+        const float g_lp = policy_terms(c, lp, ratio, q - v, s);
+        dz[j] = g_lp * (u / sd);
+        dz[kNormalLs + j] = (lsr >= c.ls_lo && lsr <= c.ls_hi) ? g_lp * (u * u - 1.f) : 0.f;
+    }
+}
+
+}  // namespace srlxv

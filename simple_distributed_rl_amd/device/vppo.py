@@ -1,0 +1,178 @@
+"""V-PPO's update on libsrlx (csrc/srlx_vppo.hip): `VppoUpdate` binds an `algorithms.ppo_v.Parameter`'s own tensors by address -- the network
+stays what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after the norm clip)
+and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches."""
+import ctypes
+import math
+
+import torch
+
+from simple_distributed_rl_amd import _native as N
+
+MAX_BATCH = 256
+# block options the kernels' layers cover; anything else set on a block keeps the update on torch
+_MLP_FREE_KWARGS = {"layer_sizes", "activation", "kernel_initializer", "bias_initializer"}
+
+
+def _linear_widths(block):
+    """Widths of a block made of (Linear with bias, ReLU) pairs; None for anything else."""
+    if not hasattr(block, "hidden_layers"):
+        return None
+    layers = [m for m in block.hidden_layers if not isinstance(m, torch.nn.Flatten)]
+    if len(layers) % 2:
+        return None
+    widths = []
+    for lin, act in zip(layers[0::2], layers[1::2]):
+        if type(lin) is not torch.nn.Linear or lin.bias is None or type(act) is not torch.nn.ReLU:
+            return None
+        widths.append(lin.out_features)
+    return tuple(widths)
+
+
+def _int_array(values):
+    return (ctypes.c_int * max(1, len(values)))(*values)
+
+
+def shape_of(parameter):
+    """(D, head, n_out, trunk widths, value widths, policy widths) of a ppo_v.Parameter, or a sentence saying why its network is not one the kernels run."""
+    net = parameter.net
+    if not hasattr(net.in_block, "hidden_layers"):
+        return "the input_block is an image block (the kernels start at a flat observation)"
+    widths = []
+    for name in ("in_block", "hidden_block", "value_block", "policy_block"):
+        w = _linear_widths(getattr(net, name))
+        if w is None:
+            return f"the {name} is not a chain of Linear (with bias) + ReLU layers"
+        widths.append(w)
+    first = [m for m in list(net.in_block.hidden_layers) + list(net.hidden_block.hidden_layers) if isinstance(m, torch.nn.Linear)]
+    if not first:
+        return "the trunk (input_block + hidden_block) has no layer"
+    D = first[0].in_features
+    dist = net.policy_dist_block
+    if hasattr(dist, "loc_layers"):
+        if len(dist.h_layers) or len(dist.loc_layers) != 1 or len(dist.log_scale_layers) != 1:
+            return "the Normal head has hidden layers of its own"
+        head, n_out = 1, dist.loc_layers[0].out_features
+    else:
+        if len(dist.h_layers) != 1:
+            return "the categorical head has hidden layers of its own"
+        head, n_out = 0, dist.h_layers[0].out_features
+    return D, head, n_out, widths[0] + widths[1], widths[2], widths[3]
+
+
+def log_scale_range(parameter):
+    """The Normal head's clamp as the kernels take it: (lo, hi), infinite when there is none."""
+    dist = parameter.net.policy_dist_block
+    if getattr(dist, "enable_stable_gradients", False):
+        return float(dist.stable_gradients_scale_range[0]), float(dist.stable_gradients_scale_range[1])
+    return -math.inf, math.inf
+
+
+class VppoUpdate:
+    def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
+        reason = self.why_not(parameter, max_batch)
+        if reason:
+            raise ValueError(f"VppoUpdate: {reason}")
+        self.parameter = parameter
+        self.D, self.head, self.n_out, self.trunk_widths, self.value_widths, self.policy_widths = shape_of(parameter)
+        self.K = self.n_out if self.head else 1
+        self.max_batch = max_batch
+        self.params = list(parameter.net.parameters())
+        self.device = self.params[0].device
+        self.betas, self.eps = betas, eps
+        self.ls_lo, self.ls_hi = log_scale_range(parameter)
+        self._lib = N.lib()
+        self._h = N.c_p()
+        N.check(self._lib.srlx_vppo_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(self.trunk_widths), _int_array(self.trunk_widths),
+                                           len(self.value_widths), _int_array(self.value_widths), len(self.policy_widths), _int_array(self.policy_widths),
+                                           max_batch, self.device.index or 0))
+        self.grads = [torch.zeros_like(p) for p in self.params]      # after the norm clip: what Adam reads
+        self.raw_grads = [torch.zeros_like(p) for p in self.params]  # before it
+        self.exp_avg = [torch.zeros_like(p) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        N.check(self._lib.srlx_vppo_bind(self._h, self._ptrs(self.params)))
+        N.check(self._lib.srlx_vppo_bind_grads(self._h, self._ptrs(self.grads), self._ptrs(self.raw_grads)))
+        N.check(self._lib.srlx_vppo_bind_adam(self._h, self._ptrs(self.exp_avg), self._ptrs(self.exp_avg_sq), 0, betas[0], betas[1], eps))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.srlx_vppo_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def _ptrs(tensors):
+        return (N.c_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+    # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def why_not(parameter, batch: int = 1, config=None) -> str:
+        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
+        tensors = list(parameter.net.parameters())
+        if not all(t.is_cuda for t in tensors):
+            return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)
+        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            return "a parameter is not a dense float32 tensor"
+        if config is not None:
+            for name in ("hidden_block", "value_block", "policy_block"):
+                extra = set(getattr(config, name).kwargs) - _MLP_FREE_KWARGS
+                if extra:
+                    return f"the {name} sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)"
+            extra = set(config.input_block.value.kwargs) - _MLP_FREE_KWARGS
+            if extra:
+                return f"the input_block sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)"
+            sch = config.lr_scheduler
+            if sch.schedule_type not in ("", "step", "exp", "cosine", "piecewise"):
+                return f"the lr schedule {sch.schedule_type!r} is not one the host evaluates per step"
+        shape = shape_of(parameter)
+        if isinstance(shape, str):
+            return shape
+        return VppoUpdate.envelope_reason(*shape, batch)
+
+    @staticmethod
+    def envelope_reason(D, head, n_out, tw, vw, pw, batch: int = 1) -> str:
+        """The envelope of srlx_vppo_create as a sentence ('' inside it).  Host arithmetic: no device needed."""
+        if batch > MAX_BATCH:
+            return f"batch size {batch} above max_batch {MAX_BATCH}"
+        if N.lib().srlx_vppo_scratch_floats(D, head, n_out, len(tw), _int_array(tw), len(vw), _int_array(vw), len(pw), _int_array(pw), max(1, batch)) < 0:
+            return ("outside the envelope (D 1..256, trunk 1..3 layers, value and policy block 0..2 layers of 32..512 units in multiples of 32, 2..16 actions or "
+                    f"1..8 action elements): D {D}, {'Normal' if head else 'categorical'} {n_out}, trunk {tuple(tw)}, value {tuple(vw)}, policy {tuple(pw)}")
+        return ""
+
+    @classmethod
+    def serves(cls, parameter, batch: int = 1, config=None) -> bool:
+        return cls.why_not(parameter, batch, config) == ""
+
+    # ---- the calls --------------------------------------------------------------------------------------------------------------------------------------
+    def steps(self) -> int:
+        """Optimiser steps taken."""
+        return int(self._lib.srlx_vppo_steps(self._h))
+
+    def update(self, state, next_state, action, old_logpi, reward, not_terminated, total_reward, lr, discount, clip_range, entropy_weight, loss_align_coeff,
+               max_grad_norm, squashed: bool) -> dict:
+        """state / next_state f32 [B][D]; action i32 [B] (categorical) or f32 [B][K] (Normal); old_logpi f32 [B][K]; reward, not_terminated, total_reward f32 [B];
+        all on the device.  Returns v, n_v [B], new_logpi [B][K] and `scalars` [5] (loss_value, loss_v_align, loss_policy, loss_e, the gradient norm before the
+        clip), device tensors; nothing synchronises."""
+        B = state.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f"VppoUpdate: batch size {B} above max_batch {self.max_batch}")
+        keep = [t.contiguous() for t in (state, next_state, action, old_logpi, reward, not_terminated, total_reward)]
+        assert keep[2].dtype == (torch.float32 if self.head else torch.int32) and all(t.dtype == torch.float32 for t in keep[:2] + keep[3:])
+        assert keep[0].numel() == B * self.D and keep[1].numel() == B * self.D and keep[2].numel() == B * self.K and keep[3].numel() == B * self.K
+        assert all(t.numel() == B for t in keep[4:])
+        out = {"v": torch.empty(B, dtype=torch.float32, device=self.device), "n_v": torch.empty(B, dtype=torch.float32, device=self.device),
+               "new_logpi": torch.empty((B, self.K), dtype=torch.float32, device=self.device), "scalars": torch.empty(5, dtype=torch.float32, device=self.device)}
+        N.check(self._lib.srlx_vppo_update(self._h, B, *[N.tptr(t) for t in keep], float(lr), float(discount), float(clip_range), float(entropy_weight),
+                                           float(loss_align_coeff), float(max_grad_norm), int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(out["v"]),
+                                           N.tptr(out["n_v"]), N.tptr(out["new_logpi"]), N.tptr(out["scalars"]), N.torch_stream_ptr()))
+        self._keep = keep
+        return out
+
+    def forward(self, state, want_v: bool = True, want_head: bool = True):
+        """v [n] and the head's outputs of n rows: logits [n][A], or (locs, clamped log-scales) [n][k] each; None for what is not wanted."""
+        x = state.contiguous()
+        n = x.shape[0]
+        v = torch.empty(n, dtype=torch.float32, device=self.device) if want_v else None
+        h0 = torch.empty((n, self.n_out), dtype=torch.float32, device=self.device) if want_head else None
+        h1 = torch.empty((n, self.n_out), dtype=torch.float32, device=self.device) if want_head and self.head else None
+        N.check(self._lib.srlx_vppo_forward(self._h, n, N.tptr(x), self.ls_lo, self.ls_hi, N.tptr(v), N.tptr(h0), N.tptr(h1), N.torch_stream_ptr()))
+        self._keep_fwd = x
+        return v, (h0 if not self.head else (h0, h1))

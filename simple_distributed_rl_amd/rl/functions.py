@@ -110,3 +110,16 @@ def calc_epsilon_greedy_probs(q, invalid_actions, epsilon, action_num):
             p += (1 - epsilon) / n_max
         probs.append(p)
     return probs
+
+
+def compute_normal_logprob(x, loc, scale):
+    """log N(x; loc, scale) per element (srl/rl/functions.py:232-238)."""
+    return -0.5 * np.log(2 * np.pi) - np.log(scale) - 0.5 * (((x - loc) / scale) ** 2)
+
+
+def compute_normal_logprob_sgp(x, loc, scale, epsilon: float = 1e-10):
+    """Squashed Gaussian policy (srl/rl/functions.py:241-250): x is the value BEFORE tanh; the correction is the sum over the action's elements and is
+    subtracted from every element's log-probability (keepdims)."""
+    logmu = compute_normal_logprob(x, loc, scale)
+    x = np.clip(1.0 - np.tanh(x) ** 2, epsilon, 1.0)
+    return logmu - np.sum(np.log(x), axis=-1, keepdims=True)
