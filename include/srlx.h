@@ -1467,6 +1467,58 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
 int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
                       void *stream);
 
+/* ---- V-PPO: the device engine's launches outside the update (srlx_vppo.hip, srlx_vppo_lanes.hip) -------------------------------------------------
+ *   srlx_vppo_act : the Worker's policy() (algorithms/ppo_v.py, discrete branch, training) for n_rows lanes in ONE launch, on a categorical handle; needs
+ *                   srlx_vppo_bind only.  Rows are dense f32 [n_rows][D].  The pass is trunk and policy branch (the Worker throws v away); a row's logits are
+ *                   bit for bit what srlx_vppo_forward writes into d_head0 for the same rows, whatever rows share a workgroup.
+ *                   U0 = u53(rng_u64(seed, *d_counter, 2 r)), U1 = u53(rng_u64(seed, *d_counter, 2 r + 1)) (what srlx_rng_uniform writes at those indices);
+ *                   *d_counter is read, not advanced.
+ *                     U0 < epsilon : a = min(A - 1, (int)floor(U1 A)), logp = (float)log(1.0 / A)
+ *                     otherwise    : float64 w_k = exp((double)z_k - max z), c_k the running sum in action order, a = the first k with U1 c_{A-1} < c_k
+ *                                    (A - 1 if rounding leaves none); logp = the update's own float32 form, log(clamp(softmax(z)_a, 1e-7, 1)) -- with unchanged
+ *                                    parameters srlx_vppo_update's new_logpi equals it to the bit.  Not floored at log(1e-6): the store's push does that.
+ *                   Outputs: d_actions i32 [n], d_logp f32 [n]; optional (NULL): d_logits f32 [n][A], d_cdf f64 [n][A] (the c_k).  No atomics.
+ *                   Envelope, validated before any device call (SRLX_ERR_INVALID; srlx_last_error() names vppo_act): a bound categorical handle, n_rows
+ *                   1..65536, epsilon in [0, 1], non-NULL d_obs, d_counter, d_actions, d_logp.
+ * The episode store: a tracking ring [R][E] (R = max_episode_steps + 2; row p = the observation each lane acted on at lock-step p with that step's action,
+ * log-probability, reward, not-terminated, done; s' of row p is row p + 1; per lane the running episode length and the needs_reset byte) and an item ring of
+ * `capacity` items (s, s', action, old log-probability, reward, not-terminated, total reward) in which the item with sequence number q lives in slot
+ * q % capacity, as ReplayBuffer.add leaves it.  Envelope of create: lanes 1..4096, D 1..256, max_episode_steps 1..4094, capacity 1..2^24, discount in [0, 1].
+ *   srlx_vppo_lanes_reset  : empties both structures and takes the lanes' first observations f32 [E][D] as row 0.
+ *   srlx_vppo_lanes_push   : one lock-step, TWO launches (the close places a lane's items behind those of the closing lanes before it, so it reads every
+ *                            lane's length and done flag: a launch boundary orders that behind all lanes' stores).  Inputs: actions i32 [E], log-probabilities
+ *                            f32 [E] (floored at (float)log(1e-6) here), rewards f32 [E], terminated and done u8 [E], next observations f32 [E][D] (into row
+ *                            p + 1).  A lane whose needs_reset byte is set stores nothing: the lock-step only delivers its new first observation.  needs_reset
+ *                            becomes done; *d_policy_counter (NULL: none) gains 1.  Every lane whose step was done closes its episode of n steps: walking them
+ *                            backwards, total = reward + discount * total in float64, one chain in the Worker's order, rounded to float32 at the store; the n
+ *                            items are appended in that reversed order, the closing lanes in lane order.  Of the S items a lock-step adds only the last
+ *                            `capacity` are written (what a sequential ring would hold).  A lane that stores more than max_episode_steps steps without
+ *                            closing sets the sticky error word (srlx_vppo_lanes_count) and drops them; the rest of that episode is dropped too (the lane's
+ *                            length reads -1 until its next first observation), so no item with a return cut short reaches the ring.  No atomics.
+ *   srlx_vppo_lanes_sample : `batch` (1..256, <= capacity) distinct slots uniformly from [0, N), N = min(capacity, added), by Floyd's algorithm: for
+ *                            i = 0..batch-1, j = N - batch + i, t = min(j, (int64)floor(U_i (j + 1))), U_i = u53(rng_u64(seed, draw, i)) with `draw` the
+ *                            number of samples since the reset; take t, or j if t is already chosen.  Then the items as srlx_vppo_update's dense tensors:
+ *                            states and next states f32 [B][D], actions i32 [B], old log-probabilities, rewards, not-terminated, total rewards f32 [B], and the
+ *                            slots i64 [B].  Two launches; rows move as 16-byte accesses where D % 4 == 0.  N < batch sets the error word to 2.
+ *   srlx_vppo_lanes_count  : synchronises `stream` and reads the item count (items ever added) and the error word.
+ *   srlx_vppo_lanes_views  : device pointers for tests and the engine: 0 obs ring, 1 action, 2 logp, 3 reward, 4 not-terminated, 5 done, 6 lengths, 7
+ *                            needs_reset, 8 item s, 9 item s', 10 item action, 11 item logp, 12 item reward, 13 item not-terminated, 14 item total, 15 the
+ *                            two count words; and the current row.
+ *   srlx_vppo_lanes_read   : synchronises `stream` and copies one whole view (numbered as above) to host memory; `bytes` must be the view's size. */
+int srlx_vppo_act(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t seed, const int64_t *d_counter, double epsilon, int32_t *d_actions, float *d_logp,
+                  float *d_logits, double *d_cdf, void *stream);
+typedef struct srlx_vppo_lanes srlx_vppo_lanes_t;
+int srlx_vppo_lanes_create(srlx_vppo_lanes_t **out, int64_t n_lanes, int obs_dim, int64_t max_episode_steps, int64_t capacity, double discount, int device);
+int srlx_vppo_lanes_destroy(srlx_vppo_lanes_t *h);
+int srlx_vppo_lanes_reset(srlx_vppo_lanes_t *h, const float *d_first_obs, void *stream);
+int srlx_vppo_lanes_push(srlx_vppo_lanes_t *h, const int32_t *d_actions, const float *d_logp, const float *d_rewards, const uint8_t *d_terminated, const uint8_t *d_done,
+                         const float *d_next_obs, int64_t *d_policy_counter, void *stream);
+int srlx_vppo_lanes_sample(srlx_vppo_lanes_t *h, int64_t batch, uint64_t seed, float *d_states, float *d_next_states, int32_t *d_actions, float *d_old_logpi,
+                           float *d_rewards, float *d_not_terminated, float *d_total_rewards, int64_t *d_slots, void *stream);
+int srlx_vppo_lanes_count(srlx_vppo_lanes_t *h, int64_t *added, int32_t *error, void *stream);
+int srlx_vppo_lanes_views(srlx_vppo_lanes_t *h, void **views, int64_t *current_row);
+int srlx_vppo_lanes_read(srlx_vppo_lanes_t *h, int view, int64_t bytes, void *host_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

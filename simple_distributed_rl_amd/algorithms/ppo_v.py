@@ -15,7 +15,8 @@ Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of two backends th
   "torch"  the reference's step in plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
-There is no device engine: `engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path.
+`engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path; `device/vppo_engine.py: VppoEngine` trains a Parameter of this
+module in place on E lock-stepped lanes, for the categorical head on flat observations.
 
 What is kept from the reference although it reads oddly:
   * The broadcasting (:144-163).  With an action of k > 1 elements new_logpi and ratio are [B][k] while v, q and adv are [B][1]: the Huber, the MSE and the
@@ -298,15 +299,16 @@ class Trainer(RLTrainer):
         self.train_on_batch(torch.as_tensor(np.asarray(state, dtype=f), device=d), torch.as_tensor(np.asarray(n_state, dtype=f), device=d), col(action),
                             col(old_logpi), col(reward), col(not_terminated), col(total_reward))
 
-    def train_on_batch(self, state, n_state, action, old_logpi, reward, not_terminated, total_reward) -> dict:
+    def train_on_batch(self, state, n_state, action, old_logpi, reward, not_terminated, total_reward, actions=None) -> dict:
         """One update (:132-178) from device tensors: state / n_state f32 [B][...]; action f32 [B][A] one-hot or [B][k]; old_logpi f32 [B][1 or k]; reward,
-        not_terminated and total_reward f32 [B][1]."""
+        not_terminated and total_reward f32 [B][1].  `actions`: the discrete actions as int32 [B], for a caller that has them (the device engine): the "srlx"
+        backend then reads them instead of the one-hot's argmax, and `action` may be None there."""
         if self._backend is None:
             self._choose_backend(state.shape[0])
         if self._backend == "srlx" and state.shape[0] > self._srlx.max_batch:
             raise ValueError(f"a batch of {state.shape[0]} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
         if self._backend == "srlx":
-            out = self._update_srlx(state, n_state, action, old_logpi, reward, not_terminated, total_reward)
+            out = self._update_srlx(state, n_state, action, old_logpi, reward, not_terminated, total_reward, actions)
         else:
             out = self._update_torch(state, n_state, action, old_logpi, reward, not_terminated, total_reward)
         self.update_path = self._backend
@@ -317,11 +319,14 @@ class Trainer(RLTrainer):
             self.info["loss_e"] = scalars[3]
         return out
 
-    def _update_srlx(self, state, n_state, action, old_logpi, reward, not_terminated, total_reward) -> dict:
+    def _update_srlx(self, state, n_state, action, old_logpi, reward, not_terminated, total_reward, actions=None) -> dict:
         cfg, u = self.config, self._srlx
         B = state.shape[0]
         lr = cfg.lr * cfg.lr_scheduler.factor(u.steps(), cfg.lr)
-        act = action.argmax(dim=1).to(torch.int32) if self.discrete else action
+        if self.discrete:
+            act = actions if actions is not None else action.argmax(dim=1).to(torch.int32)
+        else:
+            act = action
         return u.update(state.reshape(B, -1), n_state.reshape(B, -1), act, old_logpi, reward.reshape(B), not_terminated.reshape(B), total_reward.reshape(B), lr,
                         cfg.discount, cfg.clip_range, cfg.entropy_weight, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy)
 

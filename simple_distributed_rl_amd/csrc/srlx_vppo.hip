@@ -12,6 +12,8 @@
 //                   the last four threads of the launch reduce the four losses
 //   k_vppo_step     every workgroup sums the same partial squares in the same order (the norm), then one thread per parameter: the clipped gradient and Adam
 //   k_vppo_forward  v and the head's outputs of n rows
+//   k_vppo_act      the Worker's policy() for the lanes of a device engine: trunk and policy branch of up to 16 rows per workgroup, keyed uniforms, the action and
+//                   its log-probability (two row buffers, 98 432 bytes of LDS at most)
 // LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
 // widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
@@ -34,6 +36,9 @@ using srlxv::kNormalLs;
 constexpr int kMaxTensors = 20;  // 2 x (3 trunk + 2 value + value_out + 2 policy + 2 heads)
 constexpr int kPlanes = 7;       // trunk 0..2, value 3..4, policy 5..6
 constexpr size_t kLdsCap = sizeof(float) * ((size_t)3 * kRows * (512 + 1) + kWTile);
+// the most any handle asks of k_vppo_act (two row buffers of 512 floats + 1): the kernel's cap is set to this at every create, so that creating a narrower
+// handle never lowers it under a wider one that is still alive
+constexpr size_t kActLdsCap = sizeof(float) * ((size_t)2 * kRows * (512 + 1) + kWTile);
 
 struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
     Layers trunk, value, policy;
@@ -53,6 +58,7 @@ struct srlx_vppo {
     int D, head, A, Lt, Lv, Lp, device;  // head 0: categorical with A actions; 1: Normal with A = k elements
     int Wt[3], Wv[2], Wp[2];
     int wmax, nt;
+    int wmax_act;  // max(D, trunk widths, policy widths): k_vppo_act's rows
     i64 max_batch, elements, grad_blocks;
     float *p[kMaxTensors], *g[kMaxTensors], *graw[kMaxTensors], *m[kMaxTensors], *v[kMaxTensors];
     double beta1, beta2, eps;
@@ -72,6 +78,8 @@ namespace {
 int n_tensors(const srlx_vppo *h) { return 2 * (h->Lt + h->Lv + 1 + h->Lp + (h->head ? 2 : 1)); }
 int lds_stride(const srlx_vppo *h) { return h->wmax + 1; }
 size_t lds_bytes(const srlx_vppo *h) { return sizeof(float) * ((size_t)3 * kRows * lds_stride(h) + kWTile); }
+int act_lds_stride(const srlx_vppo *h) { return h->wmax_act + 1; }
+size_t act_lds_bytes(const srlx_vppo *h) { return sizeof(float) * ((size_t)2 * kRows * act_lds_stride(h) + kWTile); }
 
 struct Keep {  // planes of the hidden rows (NULL: not kept)
     float *ht, *hv, *hp;
@@ -213,6 +221,70 @@ __global__ void __launch_bounds__(kThreads) k_vppo_forward(const Net *__restrict
         const int r = t / HO, j = t % HO;
         head0[(i0 + r) * HO + j] = zs[r * kHeadCols + j];
         if (head1) head1[(i0 + r) * HO + j] = srlxv::clampf(zs[r * kHeadCols + kNormalLs + j], ls_lo, ls_hi);
+    }
+}
+
+// The Worker's policy() for the lanes of a lock-step (algorithms/ppo_v.py: Worker.policy, discrete branch, training): trunk and policy branch of
+// `rpw` <= 16 dense rows per workgroup -- the value branch is skipped, the Worker throws v away -- then one thread per (row, action) for the softmax weight in
+// float64, then one thread per row for the running sums, the two keyed uniforms, the action and its log-probability.  A row's logits are forward_heads' fma
+// chains whatever rows share its workgroup, so `rpw` changes the launch shape and never a bit.  The weights stand in the weight tile once the network is done
+// with it.  Two row buffers: nothing has to outlive a branch here.
+struct ActArgs {
+    i64 n;
+    const float *obs;  // [n][D] dense
+    srlx::u64 seed;
+    const i64 *counter;  // read, not advanced
+    double epsilon;
+    float uniform_logp;  // act_uniform_logp(A), formed on the host
+    int32_t *actions;
+    float *logp;
+    float *logits;  // NULL: not wanted
+    double *cdf;    // NULL: not wanted
+};
+
+__global__ void __launch_bounds__(kThreads) k_vppo_act(const Net *__restrict__ net, ActArgs a, int rpw, int D, int A, int S) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
+    double *cd = (double *)wl;  // [rpw][A] (2 * kRows * S floats in front of it: a multiple of 16 bytes)
+    const Net &n = *net;
+    const int t = threadIdx.x;
+    const i64 i0 = (i64)blockIdx.x * rpw;
+    const int nb = (int)(a.n - i0 < rpw ? a.n - i0 : rpw);
+    for (int p = t; p < nb * D; p += kThreads) b0[(p / D) * S + p % D] = a.obs[(i0 + p / D) * D + p % D];
+    __syncthreads();
+    float *T = srlxm::forward_rows<double>(n.trunk, n.trunk.L, nb, b0, b1, S, wl, nullptr, 0, 0, 0);
+    const float *z = srlxm::forward_rows<double>(n.policy, n.policy.L + 1, nb, T, T == b0 ? b1 : b0, S, wl, nullptr, 0, 0, 0);
+    if (t < nb * A) {
+        const int r = t / A, j = t % A;
+        const float *zr = z + r * S;
+        float m = zr[0];
+        for (int k = 1; k < A; k++) m = fmaxf(m, zr[k]);
+        cd[t] = srlxv::act_weight(zr[j], m);
+        if (a.logits) a.logits[(i0 + r) * A + j] = zr[j];
+    }
+    __syncthreads();
+    if (t < nb) {
+        const i64 r = i0 + t;
+        double *c = cd + t * A;
+        for (int k = 1; k < A; k++) c[k] = c[k - 1] + c[k];
+        if (a.cdf)
+            for (int k = 0; k < A; k++) a.cdf[r * A + k] = c[k];
+        const srlx::u64 ctr = (srlx::u64)a.counter[0];
+        const double u0 = srlx::u53(srlx::rng_u64(a.seed, ctr, (srlx::u64)(2 * r)));
+        const double u1 = srlx::u53(srlx::rng_u64(a.seed, ctr, (srlx::u64)(2 * r + 1)));
+        int act;
+        float lp;
+        if (srlxv::act_is_random(u0, a.epsilon)) {
+            act = srlxv::act_uniform_action(u1, A);
+            lp = a.uniform_logp;
+        } else {
+            act = srlxv::act_inverse_cdf(c, A, u1);
+            float m, lse;
+            bool pass;
+            lp = srlxv::categorical_logp(z + t * S, A, act, m, lse, pass);
+        }
+        a.actions[r] = act;
+        a.logp[r] = lp;
     }
 }
 
@@ -438,6 +510,9 @@ void fill(srlx_vppo *h, int D, int head, int A, int nt, const int *tw, int nv, c
     for (int l = 0; l < nv; l++) h->Wv[l] = vw[l];
     for (int l = 0; l < np; l++) h->Wp[l] = pw[l];
     h->wmax = wmax_of(D, nt, tw, nv, vw, np, pw);
+    h->wmax_act = D;
+    for (int l = 0; l < nt; l++) h->wmax_act = tw[l] > h->wmax_act ? tw[l] : h->wmax_act;
+    for (int l = 0; l < np; l++) h->wmax_act = pw[l] > h->wmax_act ? pw[l] : h->wmax_act;
     h->nt = n_tensors(h);
     h->elements = elements_of(h);
     h->grad_blocks = (h->elements + 4 + kThreads - 1) / kThreads;
@@ -477,6 +552,7 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
     if (e == hipSuccess) e = hipMemset(h->dlast_p, 0, sizeof(float) * max_batch * kHeadCols);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
     if (e != hipSuccess) {
         srlx_vppo_destroy(h);
         srlx::set_error("vppo_create: device set-up failed: %s", hipGetErrorString(e));
@@ -543,6 +619,32 @@ int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double l
     if (!h->net_ok) SRLX_TRY(upload_net(h));
     hipLaunchKernelGGL(k_vppo_forward, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states, d_v,
                        d_head0, d_head1, (float)log_scale_lo, (float)log_scale_hi, h->D, lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+// rows per workgroup of k_vppo_act: the smallest of 1, 2, 4, 8, 16 that keeps the launch within one workgroup for each of the MI355X's 256 compute units (a
+// workgroup's time grows with its rows, and every workgroup of a launch that fits the machine runs at once: DESIGN.md 7n)
+static int act_rows_per_workgroup(i64 n) {
+    int rpw = 1;
+    while (rpw < kRows && (n + rpw - 1) / rpw > 256) rpw *= 2;
+    return rpw;
+}
+
+int srlx_vppo_act(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t seed, const int64_t *d_counter, double epsilon, int32_t *d_actions, float *d_logp,
+                  float *d_logits, double *d_cdf, void *stream) {
+    SRLX_REQUIRE(h, "vppo_act: NULL handle");
+    SRLX_REQUIRE(h->bound, "vppo_act: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(h->head == 0, "vppo_act: the acting kernel serves the categorical head");
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= 65536, "vppo_act: %lld rows (1..65536)", (long long)n_rows);
+    SRLX_REQUIRE(epsilon >= 0.0 && epsilon <= 1.0, "vppo_act: epsilon %g (0..1)", epsilon);
+    SRLX_REQUIRE(d_obs && d_counter && d_actions && d_logp, "vppo_act: NULL observations, counter, actions or log-probabilities");
+    srlx::DeviceGuard g(h->device);
+    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    const int rpw = act_rows_per_workgroup(n_rows);
+    ActArgs a{(i64)n_rows, d_obs, (srlx::u64)seed, (const i64 *)d_counter, epsilon, srlxv::act_uniform_logp(h->A), d_actions, d_logp, d_logits, d_cdf};
+    hipLaunchKernelGGL(k_vppo_act, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, a, rpw, h->D, h->A,
+                       act_lds_stride(h));
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

@@ -10,6 +10,8 @@
 //           closed interval, so inside [lo, hi] (always a tie) d / d ratio = adv; outside, adv where the unclipped product is the smaller one and 0 elsewhere
 //   entropy (entropy_weight > 0 only): -expf(lp_j) lp_j per element; loss_e = mean_b sum_j expf(lp_j) lp_j
 #pragma once
+#include <cmath>
+
 #include "srlx_ppo_math.h"
 
 namespace srlxv {
@@ -59,14 +61,20 @@ __device__ __forceinline__ float policy_terms(const Cfg &c, float lp, float rati
     return g;
 }
 
-// Categorical row: z [A] logits (LDS) -> lp of action a, the row's sums, d loss / d z_k into dz [A].  lp = log(clamp(p_a, 1e-7, 1)) with p = softmax(z): inside
-// the clamp that is the log-softmax itself, below it log(1e-7) with no gradient.
-__device__ __forceinline__ float categorical_row(const Cfg &c, const float *z, int A, int a, float old_lp, float q, float tr, float v, RowSums &s, float *dz) {
-    float m, lse;
+// lp = log(clamp(p_a, 1e-7, 1)) with p = softmax(z), float32: inside the clamp (`pass`) the log-softmax itself, below it log(1e-7).  The update's new_logpi and the
+// acting kernel's log-probability are both this function: with unchanged parameters they agree to the bit.
+__device__ __forceinline__ float categorical_logp(const float *z, int A, int a, float &m, float &lse, bool &pass) {
     srlxp::cat_lse(z, A, m, lse);
     const float xa = srlxp::cat_logp(z[a], m, lse);
-    const bool pass = expf(xa) >= kProbFloor;
-    const float lp = pass ? xa : logf(kProbFloor);
+    pass = expf(xa) >= kProbFloor;
+    return pass ? xa : logf(kProbFloor);
+}
+
+// Categorical row: z [A] logits (LDS) -> lp of action a, the row's sums, d loss / d z_k into dz [A].  Below the clamp lp has no gradient.
+__device__ __forceinline__ float categorical_row(const Cfg &c, const float *z, int A, int a, float old_lp, float q, float tr, float v, RowSums &s, float *dz) {
+    float m, lse;
+    bool pass;
+    const float lp = categorical_logp(z, A, a, m, lse, pass);
     const float ratio = expf(lp - old_lp);
     value_terms(c, ratio, q, tr, v, s);
     const float g_lp = policy_terms(c, lp, ratio, q - v, s);
@@ -102,6 +110,24 @@ __device__ __forceinline__ void normal_row(const Cfg &c, const float *z, int k, 
         dz[j] = g_lp * (u / sd);
         dz[kNormalLs + j] = (lsr >= c.ls_lo && lsr <= c.ls_hi) ? g_lp * (u * u - 1.f) : 0.f;
     }
+}
+
+// ---- the Worker's action on the categorical head (srlx_vppo_act; algorithms/ppo_v.py: Worker.policy, discrete branch).  U0, U1 are keyed uniforms
+// in [0, 1); everything is float64 and host arithmetic as well, so the mirror of the tests restates it line by line.
+__host__ __device__ __forceinline__ bool act_is_random(double u0, double epsilon) { return u0 < epsilon; }  // random.random() < epsilon
+__host__ __device__ __forceinline__ int act_uniform_action(double u1, int A) {                             // sample_action()
+    const int a = (int)floor(u1 * (double)A);
+    return a < A - 1 ? a : A - 1;
+}
+__host__ __device__ __forceinline__ float act_uniform_logp(int A) { return (float)log(1.0 / (double)A); }
+// the softmax weight of one logit beside the row's maximum, and the inverse CDF over the running sums c_0 <= .. <= c_{A-1} of those weights in action order:
+// the first k with U1 c_{A-1} < c_k (A - 1 if rounding leaves none).  Categorical.sample in distribution.
+__host__ __device__ __forceinline__ double act_weight(float z, float zmax) { return exp((double)z - (double)zmax); }
+__host__ __device__ __forceinline__ int act_inverse_cdf(const double *c, int A, double u1) {
+    const double thr = u1 * c[A - 1];
+    for (int k = 0; k < A; k++)
+        if (thr < c[k]) return k;
+    return A - 1;
 }
 
 }  // namespace srlxv

@@ -717,6 +717,76 @@ def why_not_sacd_engine(env, rl_config, n_envs=None) -> str:
     return "; ".join(why)
 
 
+def why_not_vppo_engine(env, rl_config, n_envs=None) -> str:
+    """Empty string when `VppoEngine` (device/vppo_engine.py) can run this ppo_v.Config on this environment; otherwise EVERY reason it cannot, joined
+    with "; " (as `why_not_sacd_engine`).  The envelope figures are `VppoUpdate.envelope_reason`'s (srlx_vppo_create's, srlx.h): each dimension is asked about on
+    its own beside the smallest shape the kernels take.  `env.max_episode_steps` sizes the tracking ring.  `n_envs`: the lane count, when the caller has one.
+    `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep V-PPO on the plugin path; the engine is built around `runner.make_parameter()`."""
+    from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
+    from simple_distributed_rl_amd.device.vppo import VppoUpdate
+    from simple_distributed_rl_amd.device.vppo_engine import MAX_LANES
+    from simple_distributed_rl_amd.device.vppo_lanes import MAX_EPISODE_STEPS
+    from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig
+
+    c, why = rl_config, []
+    if c.get_name() != "V-PPO":
+        return f"'{c.get_name()}' is not a V-PPO config"
+    small = dict(D=1, head=0, n_out=2, tw=(32,), vw=(), pw=(), batch=1)  # the smallest shape of the envelope: what stands beside the one dimension asked about
+
+    def outside(**one) -> str:
+        head, sep, _ = VppoUpdate.envelope_reason(**dict(small, **one)).partition("): ")  # (the tail restates the whole shape, the stand-in values included)
+        return head + ")" if sep else head
+
+    if env.player_num != 1:
+        why.append("multi-player environment")
+    if not isinstance(env.action_space, DiscreteSpace):
+        why.append("a continuous action space: the Normal head's acting kernel is not built, it stays on the plugin path")
+    elif outside(n_out=int(env.action_space.n)):
+        why.append(f"{int(env.action_space.n)} actions: " + outside(n_out=int(env.action_space.n)))
+    D = flat_dim(frame_space(env, c))
+    if D is None:
+        why.append("the actor-critic reads flat BoxSpace((D,)) observations, anything else stays on the plugin path")
+    elif outside(D=D):
+        why.append(f"{D} observation elements: " + outside(D=D))
+    if getattr(c, "_obs_processors", None):
+        why.append("observation processors are served by the plugin path")
+    if getattr(c, "window_length", 1) != 1:
+        why.append("the network reads one observation (window_length 1)")
+    iv = c.input_block.value
+    trunk = []
+    refused = VppoUpdate.config_reasons(c)  # block options and lr schedules `VppoUpdate.why_not` refuses
+    for name, block in (("input_block", iv), ("hidden_block", c.hidden_block), ("value_block", c.value_block), ("policy_block", c.policy_block)):
+        sizes = _ppo_block_sizes(block)
+        if sizes is None:
+            if not any(f"the {name} sets" in r for r in refused):
+                why.append(f"{name} is not an MLP of ReLU layers (Linear layers with biases)")
+            if name in ("input_block", "hidden_block"):
+                trunk = None
+        elif name in ("input_block", "hidden_block"):
+            if trunk is not None:
+                trunk += list(sizes)
+        elif outside(**{"vw" if name == "value_block" else "pw": sizes}):
+            why.append(f"{name} {sizes}: " + outside(**{"vw" if name == "value_block" else "pw": sizes}))
+    if trunk is not None and outside(tw=tuple(trunk)):
+        why.append(f"input_block + hidden_block {tuple(trunk)}: " + outside(tw=tuple(trunk)))
+    why += refused
+    if outside(batch=int(c.batch_size)):
+        why.append(outside(batch=int(c.batch_size)))
+    if not isinstance(c.memory, ReplayBufferConfig):
+        name = getattr(c.memory, "name", type(c.memory).__name__)
+        why.append(f"V-PPO draws uniformly from the ReplayBuffer memory, memory '{name}' stays on the plugin path")
+    steps = getattr(env, "max_episode_steps", None)
+    if not isinstance(steps, (int, np.integer)) or steps < 1:
+        why.append("no known max_episode_steps: the tracking ring holds a whole episode per lane")
+    elif steps > MAX_EPISODE_STEPS - 1:  # (the engine sizes the ring for one step more: an EnvRun truncates when its step count exceeds the limit)
+        why.append(f"max_episode_steps {int(steps)} above the tracking ring's {MAX_EPISODE_STEPS - 1}")
+    elif isinstance(c.memory, ReplayBufferConfig) and steps > int(c.memory.capacity):
+        why.append(f"max_episode_steps {int(steps)} above the memory's capacity {int(c.memory.capacity)}: one episode would not fit the item ring")
+    if n_envs is not None and not (isinstance(n_envs, int) and 1 <= n_envs <= MAX_LANES):
+        why.append(f"{n_envs!r} lanes are outside the engine's 1..{MAX_LANES}")
+    return "; ".join(why)
+
+
 AGENT57_MP_REASON = "Agent57 runs on the device engine in train() under set_vector_envs(n); train_mp() keeps it on the plugin path"
 
 

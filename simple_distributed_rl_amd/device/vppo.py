@@ -112,20 +112,29 @@ class VppoUpdate:
         if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
             return "a parameter is not a dense float32 tensor"
         if config is not None:
-            for name in ("hidden_block", "value_block", "policy_block"):
-                extra = set(getattr(config, name).kwargs) - _MLP_FREE_KWARGS
-                if extra:
-                    return f"the {name} sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)"
-            extra = set(config.input_block.value.kwargs) - _MLP_FREE_KWARGS
-            if extra:
-                return f"the input_block sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)"
-            sch = config.lr_scheduler
-            if sch.schedule_type not in ("", "step", "exp", "cosine", "piecewise"):
-                return f"the lr schedule {sch.schedule_type!r} is not one the host evaluates per step"
+            reasons = VppoUpdate.config_reasons(config)
+            if reasons:
+                return reasons[0]
         shape = shape_of(parameter)
         if isinstance(shape, str):
             return shape
         return VppoUpdate.envelope_reason(*shape, batch)
+
+    @staticmethod
+    def config_reasons(config) -> list:
+        """What `why_not` refuses on the config alone, every sentence (no Parameter, no device)."""
+        why = []
+        for name in ("hidden_block", "value_block", "policy_block"):
+            extra = set(getattr(config, name).kwargs) - _MLP_FREE_KWARGS
+            if extra:
+                why.append(f"the {name} sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)")
+        extra = set(config.input_block.value.kwargs) - _MLP_FREE_KWARGS
+        if extra:
+            why.append(f"the input_block sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)")
+        sch = config.lr_scheduler
+        if sch.schedule_type not in ("", "step", "exp", "cosine", "piecewise"):
+            why.append(f"the lr schedule {sch.schedule_type!r} is not one the host evaluates per step")
+        return why
 
     @staticmethod
     def envelope_reason(D, head, n_out, tw, vw, pw, batch: int = 1) -> str:
@@ -176,3 +185,11 @@ class VppoUpdate:
         N.check(self._lib.srlx_vppo_forward(self._h, n, N.tptr(x), self.ls_lo, self.ls_hi, N.tptr(v), N.tptr(h0), N.tptr(h1), N.torch_stream_ptr()))
         self._keep_fwd = x
         return v, (h0 if not self.head else (h0, h1))
+
+    def act(self, n_rows: int, obs, seed: int, counter, epsilon: float, actions, logp, logits=None, cdf=None) -> None:
+        """srlx_vppo_act: the Worker's policy() for `n_rows` dense rows [n_rows][D] (a tensor or a device address) in one launch, on the
+        categorical head.  `counter` is a device int64 the call reads; `actions` int32 [n_rows] and `logp` float32 [n_rows] receive the result, `logits`
+        float32 [n_rows][A] and `cdf` float64 [n_rows][A] when given.  Nothing synchronises."""
+        rows = obs if isinstance(obs, ctypes.c_void_p) else N.tptr(obs)
+        N.check(self._lib.srlx_vppo_act(self._h, n_rows, rows, ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), N.tptr(counter), float(epsilon), N.tptr(actions),
+                                        N.tptr(logp), N.tptr(logits), N.tptr(cdf), N.torch_stream_ptr()))
