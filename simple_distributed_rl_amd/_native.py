@@ -411,6 +411,34 @@ def tptr(t):
     return None if t is None else c_p(t.data_ptr())
 
 
+def _int_array(values):
+    """A width list as the create calls take it (never a zero-length array)."""
+    return (c_int * max(1, len(values)))(*values)
+
+
+def _ptrs(tensors):
+    """The tensors' addresses as the bind calls take them."""
+    return (c_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _linear_widths(block):
+    """Widths of a network block made of (Linear with bias, ReLU) pairs, as the create calls take them; None for anything else.  (The one helper here that
+    walks torch modules and not ctypes values: `block.hidden_layers` of the plugins' MLP blocks.)"""
+    import torch
+
+    if not hasattr(block, "hidden_layers"):
+        return None
+    layers = [m for m in block.hidden_layers if not isinstance(m, torch.nn.Flatten)]
+    if len(layers) % 2:
+        return None
+    widths = []
+    for lin, act in zip(layers[0::2], layers[1::2]):
+        if type(lin) is not torch.nn.Linear or lin.bias is None or type(act) is not torch.nn.ReLU:
+            return None
+        widths.append(lin.out_features)
+    return tuple(widths)
+
+
 def torch_stream_ptr():
     """hipStream_t of torch's current stream (so srlx kernels order with torch ops)."""
     import torch

@@ -23,6 +23,50 @@ def invalid_mask(invalid_lists, shape, device) -> torch.Tensor:
     return torch.from_numpy(m).to(device) if fill_invalid_mask(m.reshape(-1, shape[-1]), invalid_lists) else None
 
 
+class SrlxUpdateBackend:
+    """The backend choice of a trainer whose update runs on libsrlx or in torch (sac.Trainer, ppo_v.Trainer).  `update_backend` asks for "srlx" or "torch"; the
+    first `train_on_batch` (or `require_srlx_update`) fixes the answer until the next `setup`: "srlx" when the device layer's update serves the Parameter at that
+    batch size, otherwise "torch", with the reason in `why_not_srlx_update`.  `update_path` names the backend the last update ran on.  The trainer supplies
+    `_srlx_update_class()`, the device layer's update (`why_not(parameter, batch, config)` and a constructor over the Parameter), and `_make_torch_update()`, its
+    torch optimisers and schedulers."""
+
+    def _reset_backend(self) -> None:
+        """(from `on_setup`)"""
+        self.update_path = ""
+        self.why_not_srlx_update = ""
+        self._backend = None
+
+    def _choose_backend(self, batch: int) -> None:
+        if self.update_backend not in ("srlx", "torch"):
+            raise ValueError(f"update_backend {self.update_backend!r}: 'srlx' or 'torch'")
+        self._backend = "torch"
+        if self.update_backend == "srlx":
+            update = self._srlx_update_class()
+            self.why_not_srlx_update = update.why_not(self.parameter, batch, self.config)
+            if not self.why_not_srlx_update:
+                self._backend = "srlx"
+                self._srlx = update(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
+        if self._backend == "torch":
+            self._make_torch_update()
+
+    def _backend_for(self, batch: int) -> str:
+        """The backend a batch of this size runs on: chosen at the first call, and a libsrlx update is sized then."""
+        if self._backend is None:
+            self._choose_backend(batch)
+        if self._backend == "srlx" and batch > self._srlx.max_batch:
+            raise ValueError(f"a batch of {batch} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
+        return self._backend
+
+    def require_srlx_update(self, batch: int, caller: str):
+        """For a device engine, whose acting pass runs on the update's own handle: asks for "srlx", fixes the backend now and not at the first update, and returns
+        the bound update.  An update that would run in torch is an error there, not a slower engine: ValueError in `caller`'s name with the reason."""
+        self.update_backend = "srlx"
+        self._choose_backend(batch)
+        if self._backend != "srlx":
+            raise ValueError(f"{caller}: the update does not run on libsrlx: {self.why_not_srlx_update}")
+        return self._srlx
+
+
 class TdOps:
     def __init__(self, device: torch.device):
         self.dev = device

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from simple_distributed_rl_amd.algorithms._device_ops import SrlxUpdateBackend
 from simple_distributed_rl_amd.base.exception import UndefinedError
 from simple_distributed_rl_amd.base.rl.algorithms.base_ppo import RLConfig, RLWorker
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
@@ -256,7 +257,7 @@ class Parameter(RLParameter):
         print(self.net)
 
 
-class Trainer(RLTrainer):
+class Trainer(SrlxUpdateBackend, RLTrainer):
     # "srlx" | "torch".  The default follows the project's 1.10 rule: 0.36 ms per train() on "srlx" against 2.02 ms on "torch" at ppo_v.Config() on
     # CartPole (profiles/vppo_probe.json).  At the envelope's largest corner "torch" is the faster one (46.9 against 2.6 ms): set it there.
     update_backend = "srlx"
@@ -268,26 +269,18 @@ class Trainer(RLTrainer):
             self.parameter.to_device(self.device)
         self.np_dtype = cfg.get_dtype("np")
         self.discrete = isinstance(cfg.action_space, DiscreteSpace)
-        self.update_path = ""
-        self.why_not_srlx_update = ""
-        self._backend = None
+        self._reset_backend()
 
     # ---- the backends -----------------------------------------------------------------------------------------------------------------------------------
-    def _choose_backend(self, batch: int) -> None:
+    def _srlx_update_class(self):
         from simple_distributed_rl_amd.device.vppo import VppoUpdate
 
-        if self.update_backend not in ("srlx", "torch"):
-            raise ValueError(f"update_backend {self.update_backend!r}: 'srlx' or 'torch'")
-        self._backend = "torch"
-        if self.update_backend == "srlx":
-            self.why_not_srlx_update = VppoUpdate.why_not(self.parameter, batch, self.config)
-            if not self.why_not_srlx_update:
-                self._backend = "srlx"
-                self._srlx = VppoUpdate(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
-        if self._backend == "torch":
-            self.opt = torch.optim.Adam(self.parameter.net.parameters(), lr=self.config.lr)  # :95-96
-            self._scheduler = self.config.lr_scheduler.apply_torch_scheduler(self.opt)
-            self.huber_loss, self.mse_loss = nn.HuberLoss(), nn.MSELoss()
+        return VppoUpdate
+
+    def _make_torch_update(self) -> None:
+        self.opt = torch.optim.Adam(self.parameter.net.parameters(), lr=self.config.lr)  # :95-96
+        self._scheduler = self.config.lr_scheduler.apply_torch_scheduler(self.opt)
+        self.huber_loss, self.mse_loss = nn.HuberLoss(), nn.MSELoss()
 
     def train(self) -> None:
         batches = self.memory.sample()
@@ -303,15 +296,12 @@ class Trainer(RLTrainer):
         """One update (:132-178) from device tensors: state / n_state f32 [B][...]; action f32 [B][A] one-hot or [B][k]; old_logpi f32 [B][1 or k]; reward,
         not_terminated and total_reward f32 [B][1].  `actions`: the discrete actions as int32 [B], for a caller that has them (the device engine): the "srlx"
         backend then reads them instead of the one-hot's argmax, and `action` may be None there."""
-        if self._backend is None:
-            self._choose_backend(state.shape[0])
-        if self._backend == "srlx" and state.shape[0] > self._srlx.max_batch:
-            raise ValueError(f"a batch of {state.shape[0]} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
-        if self._backend == "srlx":
+        backend = self._backend_for(state.shape[0])
+        if backend == "srlx":
             out = self._update_srlx(state, n_state, action, old_logpi, reward, not_terminated, total_reward, actions)
         else:
             out = self._update_torch(state, n_state, action, old_logpi, reward, not_terminated, total_reward)
-        self.update_path = self._backend
+        self.update_path = backend
         self.train_count += 1
         scalars = out["scalars"].tolist()  # (the one synchronisation of the call)
         self.info["loss_value"], self.info["loss_v_align"], self.info["loss_policy"] = scalars[0], scalars[1], scalars[2]

@@ -37,6 +37,7 @@ from typing import Any
 import numpy as np
 import torch
 
+from simple_distributed_rl_amd.algorithms._device_ops import SrlxUpdateBackend
 from simple_distributed_rl_amd.base.exception import NotSupportedError
 from simple_distributed_rl_amd.base.rl.algorithms.base_ppo import RLConfig, RLWorker
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
@@ -192,7 +193,7 @@ class Parameter(RLParameter):
             return self.policy(torch.as_tensor(np.asarray(state, dtype=self.np_dtype), device=self.device)).cpu().numpy()
 
 
-class Trainer(RLTrainer):
+class Trainer(SrlxUpdateBackend, RLTrainer):
     # "srlx" | "torch".  The default follows the project's 1.10 rule: 1.65 ms per train() on "srlx" against 3.58 ms on "torch" at sac.Config() on
     # CartPole (profiles/sacd_probe.json)
     update_backend = "srlx"
@@ -204,31 +205,23 @@ class Trainer(RLTrainer):
             self.parameter.to_device(self.device)
         self.np_dtype = cfg.get_dtype("np")
         self.target_entropy = -1 * cfg.action_space.n  # :151-156
-        self.update_path = ""
-        self.why_not_srlx_update = ""
-        self._backend = None
+        self._reset_backend()
         self.parameter.load_log_alpha = False
 
     # ---- the backends -----------------------------------------------------------------------------------------------------------------------------------
-    def _choose_backend(self, batch: int) -> None:
+    def _srlx_update_class(self):
         from simple_distributed_rl_amd.device.sacd import SacdUpdate
 
-        if self.update_backend not in ("srlx", "torch"):
-            raise ValueError(f"update_backend {self.update_backend!r}: 'srlx' or 'torch'")
-        self._backend = "torch"
-        if self.update_backend == "srlx":
-            self.why_not_srlx_update = SacdUpdate.why_not(self.parameter, batch)
-            if not self.why_not_srlx_update:
-                self._backend = "srlx"
-                self._srlx = SacdUpdate(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
-        if self._backend == "torch":
-            p, cfg = self.parameter, self.config
-            self.q1_optimizer = torch.optim.Adam(p.q1_online.parameters(), lr=cfg.lr_q)
-            self.q2_optimizer = torch.optim.Adam(p.q2_online.parameters(), lr=cfg.lr_q)
-            self.policy_optimizer = torch.optim.Adam(p.policy.parameters(), lr=cfg.lr_policy)
-            self._schedulers = [cfg.lr_q_scheduler.apply_torch_scheduler(self.q1_optimizer), cfg.lr_q_scheduler.apply_torch_scheduler(self.q2_optimizer),
-                                cfg.lr_policy_scheduler.apply_torch_scheduler(self.policy_optimizer)]
-            self.alpha_optimizer = None
+        return SacdUpdate
+
+    def _make_torch_update(self) -> None:
+        p, cfg = self.parameter, self.config
+        self.q1_optimizer = torch.optim.Adam(p.q1_online.parameters(), lr=cfg.lr_q)
+        self.q2_optimizer = torch.optim.Adam(p.q2_online.parameters(), lr=cfg.lr_q)
+        self.policy_optimizer = torch.optim.Adam(p.policy.parameters(), lr=cfg.lr_policy)
+        self._schedulers = [cfg.lr_q_scheduler.apply_torch_scheduler(self.q1_optimizer), cfg.lr_q_scheduler.apply_torch_scheduler(self.q2_optimizer),
+                            cfg.lr_policy_scheduler.apply_torch_scheduler(self.policy_optimizer)]
+        self.alpha_optimizer = None
 
     def train(self) -> None:
         batches = self.memory.sample()
@@ -246,17 +239,14 @@ class Trainer(RLTrainer):
     def train_on_batch(self, state, onehot_action, n_state, reward, done, actions=None) -> dict:
         """One update (:170-243) from device tensors: state / n_state f32 [B][...], one-hot actions f32 [B][A], reward f32 [B], done u8 [B].  `actions`: the
         same actions as int32 [B], when the caller has them (the device engine's ring does): the libsrlx backend then skips its argmax over the one-hot rows."""
-        if self._backend is None:
-            self._choose_backend(state.shape[0])
+        backend = self._backend_for(state.shape[0])
         cfg = self.config
         hard_sync = self.train_count % cfg.hard_target_update_interval == 0
-        if self._backend == "srlx" and state.shape[0] > self._srlx.max_batch:
-            raise ValueError(f"a batch of {state.shape[0]} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
-        if self._backend == "srlx":
+        if backend == "srlx":
             out = self._update_srlx(state, onehot_action, n_state, reward, done, hard_sync, actions)
         else:
             out = self._update_torch(state, onehot_action, n_state, reward, done, hard_sync)
-        self.update_path = self._backend
+        self.update_path = backend
         self.train_count += 1
         scalars = out["scalars"].tolist()  # (the one synchronisation of the call)
         self.info["q1_loss"], self.info["q2_loss"], self.info["policy_loss"] = scalars[0], scalars[1], scalars[2]

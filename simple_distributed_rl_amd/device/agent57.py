@@ -11,7 +11,6 @@ L = burnin + sequence_length + 1 steps shifted through Python lists and stored w
     the sequence replay and the update                               agent57.Memory (sequence_store "device") over the ring + agent57.Trainer, unchanged
 
 The engine trains the Parameter it is given in place (torch networks), so nothing has to be exported.  The lanes carry no invalid-action lists."""
-import time
 from typing import Optional
 
 import numpy as np
@@ -20,63 +19,24 @@ import torch
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.algorithms._device_ops import NguOps
 from simple_distributed_rl_amd.device.agent57_light import UcbBank
+from simple_distributed_rl_amd.device.lane_engine import SequenceLaneEngine
 from simple_distributed_rl_amd.device.sequence_store import LaneSequenceStore
 from simple_distributed_rl_amd.rl import functions as funcs
 
 
-class _ObsRingStub:
-    """What a batch-environment factory asks of the engine's replay: float32 observations on this device."""
-
-    obs_uint8 = False
-
-    def __init__(self, dev):
-        self.dev = dev
-
-
-class _MemoryView:
-    """What the loop and the learner driver ask of `engine.replay`: the priority memory's length and warm-up."""
-
-    def __init__(self, memory):
-        self._memory = memory
-
-    def length(self) -> int:
-        return self._memory.length()
-
-    def is_warmup_needed(self) -> bool:
-        return self._memory.is_warmup_needed()
-
-
-class Agent57Engine:
+class Agent57Engine(SequenceLaneEngine):
     """E environments + the plugin trainer on one GPU, training only (evaluation plays the trained Parameter on the plugin path).  `rl_config`: a set-up algorithms.agent57.Config (window_length 1); `parameter`: its Parameter, created
     here when not given; `env`: a batch environment of `HostVecEnv`'s contract with float32 observations, or a callable that makes one from an object with
     `.dev` and `.obs_uint8 == False`."""
 
-    overlap = False
-
     def __init__(self, rl_config, n_envs: int, device: int = 0, seed: int = 0, env=None, parameter=None, ring_len: Optional[int] = None, context=None):
         from simple_distributed_rl_amd.algorithms import agent57 as plugin
 
-        c = self.cfg = rl_config
-        assert c.is_setup(), "rl_config.setup(env) first: the networks are built from the negotiated spaces"
-        assert env is not None, "Agent57Engine: a batch environment (HostVecEnv's contract, float32 observations) is required"
-        self.dev = torch.device(f"cuda:{device}")
+        self._open_sequence(rl_config, n_envs, device, seed, parameter, env)
+        c, E, d, p = self.cfg, self.E, self.dev, self.parameter
         self.lib = N.lib()
-        self.E, self.seed = int(n_envs), int(seed)
-        E, d = self.E, self.dev
-        self.obs_shape = tuple(int(x) for x in c.observation_space.shape)
-        self.A, self.H = int(c.action_space.n), int(c.lstm_units)
-        self.L, self.S = c.burnin + c.sequence_length + 1, c.sequence_length
-        c._set_device(str(d))
-        if parameter is None:
-            parameter = c.make_parameter()
-        parameter.to_device(d)
-        self.parameter = p = parameter
-        self.memory = plugin.Memory(c, sequence_store="device")
-        self.store = LaneSequenceStore(d, E, c.memory.capacity, self.L, self.S, self.A, self.H, self.obs_shape, seed=self.seed ^ 0x57A, ring_len=ring_len)
-        self.memory.attach_lane_store(self.store)
-        self.replay = _MemoryView(self.memory)
-        self.trainer = c.make_trainer(p, self.memory)
-        self.setup_trainer(context)
+        self._attach_ring(plugin.Memory(c, sequence_store="device"),
+                           LaneSequenceStore(d, E, c.memory.capacity, self.L, self.S, self.A, self.H, self.obs_shape, seed=self.seed ^ 0x57A, ring_len=ring_len), context)
         Na = c.actor_num
         self.beta_list = torch.tensor(np.array(funcs.create_beta_list(Na), np.float32), device=d)
         self.eps_list = torch.tensor(np.array(funcs.create_epsilon_list(Na), np.float32), device=d)
@@ -91,43 +51,17 @@ class Agent57Engine:
         z = lambda dt: torch.zeros(E, dtype=dt, device=d)  # noqa: E731
         self.episode_reward, self.prev_r_ext, self.prev_r_int = z(torch.float32), z(torch.float32), z(torch.float32)
         self.prev_action = z(torch.int64)
-        self.actions = z(torch.int32)
         self.hidden_ext = tuple(torch.zeros((1, E, self.H), dtype=torch.float32, device=d) for _ in range(2))
         self.hidden_int = tuple(torch.zeros((1, E, self.H), dtype=torch.float32, device=d) for _ in range(2))
         self.u_policy = torch.zeros(2 * E, dtype=torch.float64, device=d)
-        self.policy_counter = torch.zeros(1, dtype=torch.int64, device=d)
         self.gen = torch.Generator(device=d)
         self.gen.manual_seed(self.seed + 17)
-        self.total_env_steps = 0
-        self.lock_steps = 0
-        self.ledger = None  # an EpisodeLedger, when a driver wants episode results
-        self.phase_times = None  # a dict: the engine then synchronises around its phases and adds up their host seconds (tools/agent57_engine_probe.py)
-        self.env = env(_ObsRingStub(d)) if callable(env) else env
-        self.obs = self.env.reset().view(E, -1).to(torch.float32)
-        # position 0: every lane delivers its episode's first frame
-        self.reset_lane = torch.ones(E, dtype=torch.uint8, device=d)
-        self._first_host = np.ones(E, bool)
+        self._reset_lanes(env)
         self._begin_episodes(None)
         zf = z(torch.float32)
-        self.store.push(self.obs.contiguous(), self.actions, zf, zf, zf, self.ucb.arm.to(torch.int32), *self._hidden_rows(), first=self._first_host,
-                        first_dev=self.reset_lane)
-        self.store.emit(np.zeros(E, bool))
-        self.reset_lane = torch.zeros(E, dtype=torch.uint8, device=d)
-        self._first_host = np.zeros(E, bool)
+        self._push_first_frames(self.obs.contiguous(), self.actions, zf, zf, zf, self.ucb.arm.to(torch.int32))
 
     # ---- helpers --------------------------------------------------------------------------------
-    @property
-    def train_count(self) -> int:
-        return self.trainer.train_count
-
-    def setup_trainer(self, context=None):
-        """`RLTrainer.setup` with the run's context, as the plugin learner does when a run opens (fresh optimisers; the memory and the networks stay)."""
-        if context is None:
-            from simple_distributed_rl_amd.base.context import RunContext
-
-            context = RunContext()
-        self.trainer.setup(context)
-
     def _hidden_rows(self):
         return tuple(t[0].contiguous() for t in self.hidden_ext + self.hidden_int)
 
@@ -152,14 +86,6 @@ class Agent57Engine:
     def arm(self) -> torch.Tensor:
         return self.ucb.arm.long()
 
-    def _tick(self, name: str, t0: float) -> float:
-        if self.phase_times is None:
-            return 0.0
-        torch.cuda.synchronize(self.dev)
-        now = time.perf_counter()
-        self.phase_times[name] = self.phase_times.get(name, 0.0) + (now - t0)
-        return now
-
     # ---- actor ----------------------------------------------------------------------------------
     def policy_q(self):
         """One forward of both online Q-networks over [E][1] inputs from the lanes' recurrent state (:516-534); the state moves on.  Returns q_ext, q_int, q."""
@@ -177,7 +103,7 @@ class Agent57Engine:
     def actor_step(self):
         """One lock-step of all lanes: arms and action values, actions, environments, intrinsic reward, ring push, priority adds."""
         c, E, st = self.cfg, self.E, N.torch_stream_ptr()
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
+        t0 = self._clock()
         arm = self.arm()
         _, _, q = self.policy_q()
         eps = self.eps_list[arm].contiguous()
@@ -200,12 +126,10 @@ class Agent57Engine:
                 lifelong = self.ngu.lifelong(p.lifelong_target(s), p.lifelong_train(s), c.lifelong_max)
             r_int = torch.where(live, episodic * lifelong, r_int)  # :559-563
         # a lane that begins an episode consumes its first frame from the zero state (on_reset :432-433)
-        self.hidden_ext = tuple(torch.where(first.view(1, E, 1), torch.zeros_like(t), t) for t in self.hidden_ext)
-        self.hidden_int = tuple(torch.where(first.view(1, E, 1), torch.zeros_like(t), t) for t in self.hidden_int)
+        self.hidden_ext, self.hidden_int = self._zero_first(self.hidden_ext, first), self._zero_first(self.hidden_int, first)
         t0 = self._tick("actor", t0)
         undone = 1.0 - terminated.to(torch.float32)
-        self.store.push(next_obs.contiguous(), self.actions, rewards.contiguous(), r_int, undone, arm.to(torch.int32), *self._hidden_rows(), first=self._first_host,
-                        first_dev=self.reset_lane)
+        self._push(next_obs.contiguous(), self.actions, rewards.contiguous(), r_int, undone, arm.to(torch.int32))
         t0 = self._tick("push", t0)
         # the worker's bookkeeping (:546-566): lanes in a reset lock-step took no action
         self.obs = next_obs
@@ -214,37 +138,10 @@ class Agent57Engine:
         self.prev_r_int = torch.where(live, r_int, self.prev_r_int)
         self.episode_reward = self.episode_reward + torch.where(live, rewards, torch.zeros_like(rewards))
         self._begin_episodes(done)  # lanes whose episode just ended: book it with their UCB controller, draw the next arm
-        self.reset_lane = done.clone()
-        done_host = done.cpu().numpy().astype(bool)  # the host needs the window count
-        serials = self.store.emit(done_host)
-        self._first_host = done_host
-        for s in serials:  # (every emitted window: the memory's oldest item must stay among the ledger's live serials)
-            self.memory.add_serial(int(s), None)
-        self.last_serials = serials
-        self.total_env_steps += E
-        self.lock_steps += 1
-        self._tick("adds", t0)
-
-    # ---- learner --------------------------------------------------------------------------------
-    def learner_step(self) -> bool:
-        """One `agent57.Trainer.train()`: it samples serials from the priority memory, and the memory gathers them from the lane ring."""
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
-        before = self.trainer.train_count
-        self.trainer.train()
-        self._tick("train", t0)
-        return self.trainer.train_count > before
-
-    def step(self, learner_updates: int = 1):
-        self.actor_step()
-        for _ in range(learner_updates):
-            self.learner_step()
-
-    def join_learner(self):
-        """(updates run on the caller's stream: nothing to join)"""
+        self._emit_windows(done, t0)
 
     def info(self) -> dict:
-        d = dict(train_count=self.train_count, memory=self.memory.length())
-        d.update(self.trainer.info)
+        d = super().info()
         if "ext_loss" in d:
             d["loss"] = d["ext_loss"]
         return d

@@ -10,7 +10,6 @@ states shifted through Python lists and stored whole on every step.  Here every 
 
 The engine trains the Parameter it is given in place (torch networks), so nothing has to be exported.  Invalid-action masks come from the batch environment's
 optional `invalid_mask()`; an environment without it runs unmasked."""
-import time
 from typing import Optional, Sequence
 
 import numpy as np
@@ -18,7 +17,7 @@ import torch
 
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.algorithms import r2d2 as plugin
-from simple_distributed_rl_amd.device.agent57 import _MemoryView, _ObsRingStub
+from simple_distributed_rl_amd.device.lane_engine import SequenceLaneEngine
 from simple_distributed_rl_amd.device.sequence_store import R2D2LaneStore
 from simple_distributed_rl_amd.device.vector_runner import HostVecEnv
 
@@ -88,89 +87,35 @@ class MaskedHostVecEnv(HostVecEnv):
         return self._mask
 
 
-class R2D2Engine:
+class R2D2Engine(SequenceLaneEngine):
     """E environments + the plugin trainer on one GPU, training only (evaluation plays the trained Parameter on the plugin path).  `rl_config`: a set-up
     algorithms.r2d2.Config (window_length 1); `parameter`: its Parameter, created here when not given; `env`: a batch environment of `HostVecEnv`'s contract
     with float32 observations and, optionally, `invalid_mask()`, or a callable that makes one from an object with `.dev` and `.obs_uint8 == False`;
     `lane_epsilon`: E floats that override `rl_config.epsilon` per lane."""
 
-    overlap = False
-
     def __init__(self, rl_config, n_envs: int, device: int = 0, seed: int = 0, env=None, parameter=None, ring_len: Optional[int] = None, context=None,
                  lane_epsilon: Optional[Sequence[float]] = None):
-        c = self.cfg = rl_config
-        assert c.is_setup(), "rl_config.setup(env) first: the network is built from the negotiated spaces"
-        assert env is not None, "R2D2Engine: a batch environment (HostVecEnv's contract, float32 observations) is required"
-        self.dev = torch.device(f"cuda:{device}")
+        self._open_sequence(rl_config, n_envs, device, seed, parameter, env)
+        c, E, d = self.cfg, self.E, self.dev
         self.lib = N.lib()
-        self.E, self.seed = int(n_envs), int(seed)
-        E, d = self.E, self.dev
-        self.obs_shape = tuple(int(x) for x in c.observation_space.shape)
-        self.A, self.H = int(c.action_space.n), int(c.lstm_units)
-        self.L, self.S = c.burnin + c.sequence_length + 1, c.sequence_length
-        c._set_device(str(d))
-        if parameter is None:
-            parameter = c.make_parameter()
-        parameter.to_device(d)
-        self.parameter = parameter
-        self.memory = LaneMemory(c)
-        self.store = R2D2LaneStore(d, E, c.memory.capacity, self.L, self.S, self.A, self.H, self.obs_shape, seed=self.seed ^ 0x2D2, ring_len=ring_len)
-        self.memory.attach_lane_store(self.store)
-        self.replay = _MemoryView(self.memory)
-        self.trainer = c.make_trainer(parameter, self.memory)
-        self.setup_trainer(context)
+        self._attach_ring(LaneMemory(c), R2D2LaneStore(d, E, c.memory.capacity, self.L, self.S, self.A, self.H, self.obs_shape, seed=self.seed ^ 0x2D2, ring_len=ring_len),
+                           context)
         if lane_epsilon is None:
             lane_epsilon = [c.epsilon] * E
         if len(lane_epsilon) != E:
             raise ValueError(f"R2D2Engine: lane_epsilon has {len(lane_epsilon)} entries, the engine has {E} lanes")
         self.eps = torch.tensor(np.asarray(lane_epsilon, np.float32), device=d)
-        self.actions = torch.zeros(E, dtype=torch.int32, device=d)
         self.mu = torch.zeros(E, dtype=torch.float32, device=d)
         self.hidden = tuple(torch.zeros((1, E, self.H), dtype=torch.float32, device=d) for _ in range(2))
         self.u_policy = torch.zeros(E, dtype=torch.float64, device=d)
-        self.policy_counter = torch.zeros(1, dtype=torch.int64, device=d)
-        self.total_env_steps = 0
-        self.lock_steps = 0
-        self.ledger = None  # an EpisodeLedger, when a driver wants episode results
-        self.phase_times = None  # a dict: the engine then synchronises around its phases and adds up their host seconds (tools/r2d2_engine_probe.py)
-        self.record = None  # a list: every lock-step then appends what the policy saw and drew, as host arrays (tests/test_r2d2_engine_gpu.py)
-        self.env = env(_ObsRingStub(d)) if callable(env) else env
+        self._reset_lanes(env)
         self.masked = hasattr(self.env, "invalid_mask")
-        self.obs = self.env.reset().view(E, -1).to(torch.float32)
         self.mask = self.env.invalid_mask() if self.masked else None  # of `obs`
-        # position 0: every lane delivers its episode's first frame
-        self.reset_lane = torch.ones(E, dtype=torch.uint8, device=d)
-        self._first_host = np.ones(E, bool)
         zf = torch.zeros(E, dtype=torch.float32, device=d)
-        self.store.push(self.obs.contiguous(), self.actions, zf, zf, torch.zeros(E, dtype=torch.uint8, device=d), *self._hidden_rows(), first=self._first_host,
-                        first_dev=self.reset_lane, invalid=self.mask)
-        self.store.emit(np.zeros(E, bool))
-        self.reset_lane = torch.zeros(E, dtype=torch.uint8, device=d)
-        self._first_host = np.zeros(E, bool)
-
-    # ---- helpers --------------------------------------------------------------------------------
-    @property
-    def train_count(self) -> int:
-        return self.trainer.train_count
-
-    def setup_trainer(self, context=None):
-        """`RLTrainer.setup` with the run's context, as the plugin learner does when a run opens (a fresh optimiser; the memory and the network stay)."""
-        if context is None:
-            from simple_distributed_rl_amd.base.context import RunContext
-
-            context = RunContext()
-        self.trainer.setup(context)
+        self._push_first_frames(self.obs.contiguous(), self.actions, zf, zf, torch.zeros(E, dtype=torch.uint8, device=d), invalid=self.mask)
 
     def _hidden_rows(self):
         return tuple(t[0].contiguous() for t in self.hidden)
-
-    def _tick(self, name: str, t0: float) -> float:
-        if self.phase_times is None:
-            return 0.0
-        torch.cuda.synchronize(self.dev)
-        now = time.perf_counter()
-        self.phase_times[name] = self.phase_times.get(name, 0.0) + (now - t0)
-        return now
 
     # ---- actor ----------------------------------------------------------------------------------
     def policy_q(self) -> torch.Tensor:
@@ -184,7 +129,7 @@ class R2D2Engine:
     def actor_step(self):
         """One lock-step of all lanes: action values, the roulette draw, environments, ring push, priority adds."""
         E, st = self.E, N.torch_stream_ptr()
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
+        t0 = self._clock()
         q = self.policy_q()
         N.check(self.lib.srlx_rng_uniform(self.seed ^ 0xAC7, N.tptr(self.policy_counter), E, N.tptr(self.u_policy), st))
         N.check(self.lib.srlx_r2d2_policy(E, self.A, N.tptr(q), N.tptr(self.eps), N.tptr(self.u_policy), N.tptr(self.mask), N.tptr(self.actions), N.tptr(self.mu), st))
@@ -199,45 +144,13 @@ class R2D2Engine:
             self.ledger.account(rewards, done, N.tptr(self.reset_lane))
         first = self.reset_lane.bool()  # lanes whose lock-step only delivered a new episode's first frame: they took no action
         # a lane that begins an episode consumes its first frame from the zero state (on_reset :273)
-        self.hidden = tuple(torch.where(first.view(1, E, 1), torch.zeros_like(t), t) for t in self.hidden)
+        self.hidden = self._zero_first(self.hidden, first)
         if self.record is not None:
             h, c = self._hidden_rows()
             self.record[-1].update(next_obs=next_obs.cpu().numpy(), reward=rewards.cpu().numpy(), terminated=terminated.cpu().numpy(), done=done.cpu().numpy(),
                                    next_mask=None if mask is None else mask.cpu().numpy(), hidden=torch.stack([h, c], dim=1).cpu().numpy())
         t0 = self._tick("actor", t0)
-        self.store.push(next_obs.contiguous(), self.actions, self.mu, rewards.contiguous(), terminated.contiguous(), *self._hidden_rows(), first=self._first_host,
-                        first_dev=self.reset_lane, invalid=mask)
+        self._push(next_obs.contiguous(), self.actions, self.mu, rewards.contiguous(), terminated.contiguous(), invalid=mask)
         t0 = self._tick("push", t0)
         self.obs, self.mask = next_obs, mask
-        self.reset_lane = done.clone()
-        done_host = done.cpu().numpy().astype(bool)  # the host needs the window count
-        serials = self.store.emit(done_host)
-        self._first_host = done_host
-        for s in serials:  # (every emitted window: the memory's oldest item must stay among the ledger's live serials)
-            self.memory.add_serial(int(s), None)
-        self.last_serials = serials
-        self.total_env_steps += E
-        self.lock_steps += 1
-        self._tick("adds", t0)
-
-    # ---- learner --------------------------------------------------------------------------------
-    def learner_step(self) -> bool:
-        """One `r2d2.Trainer.train()`: it samples serials from the priority memory, and the memory gathers them from the lane ring."""
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
-        before = self.trainer.train_count
-        self.trainer.train()
-        self._tick("train", t0)
-        return self.trainer.train_count > before
-
-    def step(self, learner_updates: int = 1):
-        self.actor_step()
-        for _ in range(learner_updates):
-            self.learner_step()
-
-    def join_learner(self):
-        """(updates run on the caller's stream: nothing to join)"""
-
-    def info(self) -> dict:
-        d = dict(train_count=self.train_count, memory=self.memory.length())
-        d.update(self.trainer.info)
-        return d
+        self._emit_windows(done, t0)

@@ -6,27 +6,11 @@ import ctypes
 import torch
 
 from simple_distributed_rl_amd import _native as N
+from simple_distributed_rl_amd._native import _int_array, _linear_widths, _ptrs
 
 MAX_BATCH = 256
 TRAINED = ("policy", "q1_online", "q2_online")
 NETWORKS = ("policy", "q1_online", "q1_target", "q2_online", "q2_target")
-
-
-def _linear_widths(block):
-    """Widths of a block made of (Linear with bias, ReLU) pairs; None for anything else."""
-    layers = [m for m in block.hidden_layers if not isinstance(m, torch.nn.Flatten)]
-    if len(layers) % 2:
-        return None
-    widths = []
-    for lin, act in zip(layers[0::2], layers[1::2]):
-        if type(lin) is not torch.nn.Linear or lin.bias is None or type(act) is not torch.nn.ReLU:
-            return None
-        widths.append(lin.out_features)
-    return tuple(widths)
-
-
-def _int_array(values):
-    return (ctypes.c_int * max(1, len(values)))(*values)
 
 
 def shape_of(parameter):
@@ -65,8 +49,8 @@ class SacdUpdate:
         self.exp_avg_sq = {name: [torch.zeros_like(p) for p in self.params[name]] for name in TRAINED}
         self.alpha_exp_avg, self.alpha_exp_avg_sq = torch.zeros_like(parameter.log_alpha), torch.zeros_like(parameter.log_alpha)
         flat = [p for name in NETWORKS for p in self.params[name]]
-        N.check(self._lib.srlx_sacd_bind(self._h, self._ptrs(flat), N.tptr(parameter.log_alpha)))
-        N.check(self._lib.srlx_sacd_bind_grads(self._h, self._ptrs([g for name in TRAINED for g in self.grads[name]]), N.tptr(self.grad_log_alpha)))
+        N.check(self._lib.srlx_sacd_bind(self._h, _ptrs(flat), N.tptr(parameter.log_alpha)))
+        N.check(self._lib.srlx_sacd_bind_grads(self._h, _ptrs([g for name in TRAINED for g in self.grads[name]]), N.tptr(self.grad_log_alpha)))
         self._bind_adam([0, 0, 0, 0])
 
     def __del__(self):
@@ -74,19 +58,16 @@ class SacdUpdate:
             self._lib.srlx_sacd_destroy(self._h)
             self._h = None
 
-    @staticmethod
-    def _ptrs(tensors):
-        return (N.c_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
     def _bind_adam(self, steps):
         m = [t for name in TRAINED for t in self.exp_avg[name]] + [self.alpha_exp_avg]
         v = [t for name in TRAINED for t in self.exp_avg_sq[name]] + [self.alpha_exp_avg_sq]
-        N.check(self._lib.srlx_sacd_bind_adam(self._h, self._ptrs(m), self._ptrs(v), (N.c_i64 * 4)(*steps), self.betas[0], self.betas[1], self.eps))
+        N.check(self._lib.srlx_sacd_bind_adam(self._h, _ptrs(m), _ptrs(v), (N.c_i64 * 4)(*steps), self.betas[0], self.betas[1], self.eps))
 
     # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def why_not(parameter, batch: int = 1) -> str:
-        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
+    def why_not(parameter, batch: int = 1, config=None) -> str:
+        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not.  (`config`: as `VppoUpdate.why_not` takes it; nothing
+        a sac.Config sets keeps the update off libsrlx.)"""
         tensors = [parameter.log_alpha] + [p for name in NETWORKS for p in getattr(parameter, name).parameters()]
         if not all(t.is_cuda for t in tensors):
             return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)

@@ -29,6 +29,7 @@ import torch
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd.base.define import SpaceTypes
 from simple_distributed_rl_amd.base.run.sequence import ActorDriver, LearnerDriver
+from simple_distributed_rl_amd.device.lane_engine import MAX_LANES
 
 
 # ---------------------------------------------------------------------------------------------
@@ -671,7 +672,6 @@ def why_not_sacd_engine(env, rl_config, n_envs=None) -> str:
     `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep SAC_Discrete on the plugin path; the engine is built around `runner.make_parameter()`."""
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
     from simple_distributed_rl_amd.device.sacd import SacdUpdate
-    from simple_distributed_rl_amd.device.sacd_engine import MAX_LANES
     from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig
 
     c, why = rl_config, []
@@ -724,7 +724,6 @@ def why_not_vppo_engine(env, rl_config, n_envs=None) -> str:
     `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep V-PPO on the plugin path; the engine is built around `runner.make_parameter()`."""
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
     from simple_distributed_rl_amd.device.vppo import VppoUpdate
-    from simple_distributed_rl_amd.device.vppo_engine import MAX_LANES
     from simple_distributed_rl_amd.device.vppo_lanes import MAX_EPISODE_STEPS
     from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig
 

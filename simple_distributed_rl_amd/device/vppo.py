@@ -7,29 +7,11 @@ import math
 import torch
 
 from simple_distributed_rl_amd import _native as N
+from simple_distributed_rl_amd._native import _int_array, _linear_widths, _ptrs
 
 MAX_BATCH = 256
 # block options the kernels' layers cover; anything else set on a block keeps the update on torch
 _MLP_FREE_KWARGS = {"layer_sizes", "activation", "kernel_initializer", "bias_initializer"}
-
-
-def _linear_widths(block):
-    """Widths of a block made of (Linear with bias, ReLU) pairs; None for anything else."""
-    if not hasattr(block, "hidden_layers"):
-        return None
-    layers = [m for m in block.hidden_layers if not isinstance(m, torch.nn.Flatten)]
-    if len(layers) % 2:
-        return None
-    widths = []
-    for lin, act in zip(layers[0::2], layers[1::2]):
-        if type(lin) is not torch.nn.Linear or lin.bias is None or type(act) is not torch.nn.ReLU:
-            return None
-        widths.append(lin.out_features)
-    return tuple(widths)
-
-
-def _int_array(values):
-    return (ctypes.c_int * max(1, len(values)))(*values)
 
 
 def shape_of(parameter):
@@ -89,18 +71,14 @@ class VppoUpdate:
         self.raw_grads = [torch.zeros_like(p) for p in self.params]  # before it
         self.exp_avg = [torch.zeros_like(p) for p in self.params]
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        N.check(self._lib.srlx_vppo_bind(self._h, self._ptrs(self.params)))
-        N.check(self._lib.srlx_vppo_bind_grads(self._h, self._ptrs(self.grads), self._ptrs(self.raw_grads)))
-        N.check(self._lib.srlx_vppo_bind_adam(self._h, self._ptrs(self.exp_avg), self._ptrs(self.exp_avg_sq), 0, betas[0], betas[1], eps))
+        N.check(self._lib.srlx_vppo_bind(self._h, _ptrs(self.params)))
+        N.check(self._lib.srlx_vppo_bind_grads(self._h, _ptrs(self.grads), _ptrs(self.raw_grads)))
+        N.check(self._lib.srlx_vppo_bind_adam(self._h, _ptrs(self.exp_avg), _ptrs(self.exp_avg_sq), 0, betas[0], betas[1], eps))
 
     def __del__(self):
         if getattr(self, "_h", None):
             self._lib.srlx_vppo_destroy(self._h)
             self._h = None
-
-    @staticmethod
-    def _ptrs(tensors):
-        return (N.c_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
     # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
     @staticmethod

@@ -12,133 +12,43 @@ list and a reversed Python walk at episode end, per `train()` a `zip` and seven 
     the update                                          `ppo_v.Trainer.train_on_batch` on its "srlx" backend with the int32 actions: three launches
 
 The engine trains the Parameter it is given in place, so nothing has to be exported: `runner.evaluate()` plays it on the plugin path.  Training only."""
-import time
-
-import numpy as np
 import torch
 
+from simple_distributed_rl_amd.device.lane_engine import FlatLaneEngine
 from simple_distributed_rl_amd.device.vector_runner import why_not_vppo_engine
 from simple_distributed_rl_amd.device.vppo_lanes import VppoLanes
 
-MAX_LANES = 4096
 
-
-class _ConfigSpaces:
-    """What `why_not_vppo_engine` asks of an environment, from a set-up config (the engine is handed a batch environment, not an EnvRun)."""
-
-    player_num = 1
-
-    def __init__(self, rl_config, max_episode_steps):
-        self.action_space, self.observation_space = rl_config.action_space, rl_config.observation_space
-        self.max_episode_steps = max_episode_steps
-
-
-class VppoEngine:
+class VppoEngine(FlatLaneEngine):
     """E environments + the plugin trainer on one GPU.  `rl_config`: a set-up algorithms.ppo_v.Config; `parameter`: its Parameter, created here when not given and
     moved to the device; `env`: None for the device CartPole (max_episode_steps 500), otherwise a batch environment of `HostVecEnv`'s contract with float32
     observations or a callable that makes one from the store; `max_episode_steps`: the longest episode the environments play (the tracking ring's depth)."""
 
-    overlap = False
-
     def __init__(self, rl_config, n_envs: int, device: int = 0, seed: int = 0, env=None, parameter=None, context=None, max_episode_steps=None):
-        c = self.cfg = rl_config
-        assert c.is_setup(), "rl_config.setup(env) first: the network is built from the negotiated spaces"
         if env is None and max_episode_steps is None:
             max_episode_steps = 500
-        why = why_not_vppo_engine(_ConfigSpaces(c, max_episode_steps), c, n_envs=n_envs)
-        if why:
-            raise ValueError(f"VppoEngine cannot run this configuration: {why}")
-        self.dev = torch.device(f"cuda:{device}")
-        self.E, self.seed = int(n_envs), int(seed)
-        E, d = self.E, self.dev
-        self.D, self.A, self.B = int(c.observation_space.shape[0]), int(c.action_space.n), int(c.batch_size)
-        c._set_device(str(d))
-        if parameter is None:
-            parameter = c.make_parameter()
-        parameter.to_device(d)
-        self.parameter = parameter
-        self.trainer = c.make_trainer(parameter, None)  # (train_on_batch is handed its batch: the plugin memory is not needed)
-        self.trainer.update_backend = "srlx"
-        self.setup_trainer(context)
-        mem = c.memory
+        self._open_flat(rl_config, n_envs, device, seed, parameter, context, why_not_vppo_engine, max_episode_steps)
+        c, E, mem = self.cfg, self.E, self.cfg.memory
         # (+ 1: an EnvRun ends an episode when its step count EXCEEDS max_episode_steps (base/env/env_run.py), so a host-stepped lane can store one step more)
         self.replay = VppoLanes(E, self.D, int(max_episode_steps) + 1, int(mem.capacity), self.B, int(mem.warmup_size), float(c.discount), self.seed, device)
-        if env is None:
-            from simple_distributed_rl_amd.device.mlpq import CartPoleVecEnv
-
-            assert self.D == 4 and self.A == 2, "VppoEngine: the device CartPole has 4 observation elements and 2 actions; pass a batch environment"
-            self.env = CartPoleVecEnv(self.replay, max_steps=int(max_episode_steps))
-        else:
-            self.env = env(self.replay) if callable(env) else env
-        # the backend is chosen now, not at the first update: the acting pass runs on the trainer's own handle (it needs the bound parameters only), and an
-        # engine whose update would run in torch is an error, not a slower engine
-        self.trainer._choose_backend(self.B)
-        if self.trainer._backend != "srlx":
-            raise ValueError(f"VppoEngine: the update does not run on libsrlx: {self.trainer.why_not_srlx_update}")
-        self.actor = self.trainer._srlx
+        self._start_envs(env, max_steps=int(max_episode_steps))
         self.epsilon = float(c.epsilon)
-        self.actions = torch.zeros(E, dtype=torch.int32, device=d)
-        self.logp = torch.zeros(E, dtype=torch.float32, device=d)
-        self.policy_counter = torch.zeros(1, dtype=torch.int64, device=d)
-        self.total_env_steps = 0
-        self.lock_steps = 0
-        self.ledger = None  # an EpisodeLedger, when a driver wants episode results
-        self.phase_times = None  # a dict: the engine then synchronises around its phases and adds up their host seconds (tools/vppo_engine_probe.py)
-        # a list: every lock-step then appends what the policy drew and what the store was handed, as host arrays (the tests).  `first`: the lanes whose lock-step
-        # only delivers a new episode's first observation (their previous step ended an episode: the needs_reset protocol); they store nothing
-        self.record = None
-        self._first_host = None  # (kept while recording; set `record` before the first lock-step)
-        self.first_obs = self.env.reset()
-        self.replay.reset_all(self.first_obs)
-
-    # ---- helpers --------------------------------------------------------------------------------
-    @property
-    def train_count(self) -> int:
-        return self.trainer.train_count
-
-    def setup_trainer(self, context=None):
-        """`RLTrainer.setup` with the run's context, as the plugin learner does when a run opens."""
-        if context is None:
-            from simple_distributed_rl_amd.base.context import RunContext
-
-            context = RunContext()
-        self.trainer.setup(context)
-
-    def _tick(self, name: str, t0: float) -> float:
-        if self.phase_times is None:
-            return 0.0
-        torch.cuda.synchronize(self.dev)
-        now = time.perf_counter()
-        self.phase_times[name] = self.phase_times.get(name, 0.0) + (now - t0)
-        return now
+        self.logp = torch.zeros(E, dtype=torch.float32, device=self.dev)
 
     # ---- actor ----------------------------------------------------------------------------------
     def actor_step(self):
         """One lock-step of all lanes, 4 launches on the device CartPole: srlx_vppo_act on the tracking ring's current row, the environments' step, the push's two
         (which also advance the policy counter)."""
         r, E = self.replay, self.E
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
-        rec = None
-        if self.record is not None:
-            rec = dict(logits=torch.zeros((E, self.A), dtype=torch.float32, device=self.dev), cdf=torch.zeros((E, self.A), dtype=torch.float64, device=self.dev))
+        t0 = self._clock()
+        rec = None if self.record is None else self._record_buffers("cdf")
         self.actor.act(E, r.current_row_ptr(), self.seed ^ 0xAC7, self.policy_counter, self.epsilon, self.actions, self.logp,
                        logits=None if rec is None else rec["logits"], cdf=None if rec is None else rec["cdf"])
         if rec is not None:
-            if self._first_host is None:
-                self._first_host = np.zeros(E, bool)
-            rec = {k: v.cpu().numpy() for k, v in rec.items()}
-            rec.update(counter=int(self.policy_counter.item()), actions=self.actions.cpu().numpy(), logp=self.logp.cpu().numpy(), first=self._first_host)
-        next_obs, rewards, terminated, done = self.env.step(self.actions)
-        if rec is not None:
-            rec.update(next_obs=next_obs.view(E, -1).cpu().numpy(), reward=rewards.cpu().numpy(), terminated=terminated.cpu().numpy(), done=done.cpu().numpy())
-            self._first_host = rec["done"].astype(bool)
-            self.record.append(rec)
-        if self.ledger is not None:  # before the push: the store's needs_reset view still marks the lanes that only received a first observation
-            self.ledger.account(rewards, done, r.needs_reset_ptr)
+            rec = self._record_policy(rec, logp=self.logp)
+        next_obs, rewards, terminated, done = self._env_step(rec)
         r.push(self.actions, self.logp, rewards, terminated, done, next_obs.view(E, -1), bump=self.policy_counter)
-        self.total_env_steps += E
-        self.lock_steps += 1
-        self._tick("actor", t0)
+        self._end_lock_step("actor", t0)
 
     # ---- learner --------------------------------------------------------------------------------
     def draw_batch(self):
@@ -149,22 +59,12 @@ class VppoEngine:
         """One update of the plugin's trainer on a batch drawn from the item ring; False while the store is warming up."""
         if self.replay.is_warmup_needed():
             return False
-        t0 = time.perf_counter() if self.phase_times is not None else 0.0
+        t0 = self._clock()
         state, n_state, actions, old_logpi, reward, not_terminated, total_reward, _ = self.draw_batch()
         self.trainer.train_on_batch(state, n_state, None, old_logpi, reward, not_terminated, total_reward, actions=actions)
         self._tick("learner", t0)
         return True
 
-    def step(self, learner_updates: int = 1):
-        self.actor_step()
-        for _ in range(learner_updates):
-            self.learner_step()
-
-    def join_learner(self):
-        """(updates run on the caller's stream: nothing to join)"""
-
     def info(self) -> dict:
         self.replay.check()
-        d = dict(self.trainer.info)
-        d.update(train_count=self.train_count, memory=self.replay.length(), env_steps=self.total_env_steps)
-        return d
+        return super().info()
