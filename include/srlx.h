@@ -1519,6 +1519,47 @@ int srlx_vppo_lanes_count(srlx_vppo_lanes_t *h, int64_t *added, int32_t *error, 
 int srlx_vppo_lanes_views(srlx_vppo_lanes_t *h, void **views, int64_t *current_row);
 int srlx_vppo_lanes_read(srlx_vppo_lanes_t *h, int view, int64_t bytes, void *host_dst, void *stream);
 
+/* ---- V-PPO: the device engine on the Normal head (srlx_vppo.hip, srlx_vppo_lanes.hip) --------------------------------------------------------------
+ *   srlx_vppo_act_normal : the Worker's policy() (algorithms/ppo_v.py, NpArraySpace branch, training) for n_rows lanes in ONE launch, on a Normal handle of K
+ *                   action elements; needs srlx_vppo_bind only.  Rows are dense f32 [n_rows][D].  The pass is trunk and policy branch; a row's loc and clamped
+ *                   log-scale are bit for bit what srlx_vppo_forward writes into d_head0 / d_head1, whatever rows share a workgroup.
+ *                   Row r reads 2 K + 1 keyed uniforms u53(rng_u64(seed, *d_counter, i)): U0 at i = (2 K + 1) r; for element j, Ua at i + 1 + 2 j and Ub at
+ *                   i + 2 + 2 j.  *d_counter is read, not advanced.  z_j = sqrt(-2 log(1 - Ua)) cos(2 pi Ub) in float64.
+ *                     U0 < epsilon : loc_j = 0, sd_j = (float)noise_scale, ls_j = (float)log(noise_scale), for every element of the row
+ *                     otherwise    : loc_j the head's loc, ls_j its log-scale clamped to [log_scale_lo, log_scale_hi], sd_j = expf(ls_j)
+ *                   a_j = (float)((double)loc_j + (double)sd_j z_j), the value BEFORE tanh.  logp_j is the update's own float32 form from the stored a_j:
+ *                   u = (a_j - loc_j) / sd_j, (-0.5 log(2 pi) - ls_j - 0.5 u u) - corr, corr the row's float64 sum of log(clamp(1 - tanh(a_i)^2, 1e-10, 1))
+ *                   when `squashed`, else 0 -- on the policy branch, with unchanged parameters, srlx_vppo_update's new_logpi equals it to the bit on every
+ *                   element.  Not floored at log(1e-6): the store's push does that.  The environment's action, float64 rounded to float32 and then clipped to
+ *                   [low_j, high_j]: low_j + (x + 1) / 2 (high_j - low_j) with x = tanh(a_j) when squashed, x = a_j when plain.
+ *                   Outputs: d_actions, d_logp, d_env_actions f32 [n][K]; optional (NULL): d_loc and d_log_scale f32 [n][K] (the head's, together), d_z f64
+ *                   [n][K].  d_low / d_high: f32 [K] device arrays.  No atomics.
+ *                   Envelope, validated before any device call (SRLX_ERR_INVALID; srlx_last_error() names vppo_act_normal): a bound Normal handle, n_rows
+ *                   1..65536, epsilon in [0, 1], noise_scale positive and finite, squashed 0 or 1, ordered clamp ends, non-NULL required pointers.
+ *   srlx_vppo_lanes_create_normal / _push_normal / _sample_normal : the episode store above with K = action_dim (1..8) float32 action elements and K
+ *                   log-probabilities per step: the tracking ring's action and log-probability views are [R][E][K], the item ring's [capacity][K]; push
+ *                   takes actions and log-probabilities f32 [E][K] and floors EACH log-probability at (float)log(1e-6); sample writes actions and old
+ *                   log-probabilities f32 [B][K].  Everything else -- the ring, needs_reset, the two launches, the float64 return chain, the count, S >
+ *                   capacity, the sticky error, Floyd's draw, count / views / read -- is the categorical store's, one set of kernels.  Each kind of handle
+ *                   refuses the other kind's push and sample (SRLX_ERR_INVALID).
+ *   srlx_pendulum_lane_step : Pendulum-v1 (envs/pendulum.py) for E lanes under srlx_cartpole_step's contract: float64 state [E][2] (th, thdot), steps and
+ *                   episodes i32 [E], torques f32 [E]; outputs obs f32 [E][3] (cos th, sin th, thdot), reward, terminated (always 0), done (steps >=
+ *                   max_steps).  The step is envs/pendulum.py:step in float64, line for line (the reward from the state before the step).  A lane whose
+ *                   needs_reset byte is set only receives its next episode's first observation: th = -pi + 2 pi U_0, thdot = -1 + 2 U_1, U_k =
+ *                   u53(rng_u64(seed ^ 0x50454E44554C554D, lane << 32 | episode, k)); its reward, terminated and done read 0.  NULL torques (or NULL
+ *                   needs_reset) reset every lane; the scalar outputs may then be NULL. */
+int srlx_vppo_act_normal(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t seed, const int64_t *d_counter, double epsilon, double noise_scale, int squashed,
+                         double log_scale_lo, double log_scale_hi, const float *d_low, const float *d_high, float *d_actions, float *d_logp, float *d_env_actions,
+                         float *d_loc, float *d_log_scale, double *d_z, void *stream);
+int srlx_vppo_lanes_create_normal(srlx_vppo_lanes_t **out, int64_t n_lanes, int obs_dim, int64_t max_episode_steps, int64_t capacity, double discount, int action_dim,
+                                  int device);
+int srlx_vppo_lanes_push_normal(srlx_vppo_lanes_t *h, const float *d_actions, const float *d_logp, const float *d_rewards, const uint8_t *d_terminated,
+                                const uint8_t *d_done, const float *d_next_obs, int64_t *d_policy_counter, void *stream);
+int srlx_vppo_lanes_sample_normal(srlx_vppo_lanes_t *h, int64_t batch, uint64_t seed, float *d_states, float *d_next_states, float *d_actions, float *d_old_logpi,
+                                  float *d_rewards, float *d_not_terminated, float *d_total_rewards, int64_t *d_slots, void *stream);
+int srlx_pendulum_lane_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const float *d_torques,
+                            int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,11 @@ SIGNATURES = {
     "srlx_vppo_lanes_count": (c_int, [c_p, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32), c_p]),
     "srlx_vppo_lanes_views": (c_int, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_i64)]),
     "srlx_vppo_lanes_read": (c_int, [c_p, c_int, c_i64, c_p, c_p]),
+    "srlx_vppo_act_normal": (c_int, [c_p, c_i64, c_p, c_u64, c_p, c_f64, c_f64, c_int, c_f64, c_f64] + [c_p] * 9),
+    "srlx_vppo_lanes_create_normal": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_i64, c_f64, c_int, c_int]),
+    "srlx_vppo_lanes_push_normal": (c_int, [c_p] * 9),
+    "srlx_vppo_lanes_sample_normal": (c_int, [c_p, c_i64, c_u64] + [c_p] * 9),
+    "srlx_pendulum_lane_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

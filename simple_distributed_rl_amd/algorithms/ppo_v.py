@@ -16,7 +16,7 @@ Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of two backends th
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
 `engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path; `device/vppo_engine.py: VppoEngine` trains a Parameter of this
-module in place on E lock-stepped lanes, for the categorical head on flat observations.
+module in place on E lock-stepped lanes for the categorical head on flat observations, `VppoNormalEngine` (7q) for the Normal head.
 
 What is kept from the reference although it reads oddly:
   * The broadcasting (:144-163).  With an action of k > 1 elements new_logpi and ratio are [B][k] while v, q and adv are [B][1]: the Huber, the MSE and the

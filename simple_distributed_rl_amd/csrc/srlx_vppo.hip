@@ -14,6 +14,8 @@
 //   k_vppo_forward  v and the head's outputs of n rows
 //   k_vppo_act      the Worker's policy() for the lanes of a device engine: trunk and policy branch of up to 16 rows per workgroup, keyed uniforms, the action and
 //                   its log-probability (two row buffers, 98 432 bytes of LDS at most)
+//   k_vppo_act_normal  the same on the Normal head: Box-Muller on keyed uniforms, the action before tanh, every element's log-probability, the environment's
+//                   action (the same two row buffers)
 // LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
 // widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
@@ -288,6 +290,78 @@ __global__ void __launch_bounds__(kThreads) k_vppo_act(const Net *__restrict__ n
     }
 }
 
+// The Worker's policy() on the Normal head (algorithms/ppo_v.py: Worker.policy, NpArraySpace branch, training), k_vppo_act's launch shape and
+// network pass: trunk and policy branch of `rpw` <= 16 dense rows per workgroup, the locs kept in `zs`, then the log-scale Linear on the head's input rows into
+// the buffer the locs leave free -- forward_heads' fma chains, so a row's loc and clamped log-scale are srlx_vppo_forward's bits whatever rows share its
+// workgroup.  Then one thread per (row, element): the keyed uniforms, Box-Muller in float64, the epsilon branch, the float32 action before tanh; behind a barrier
+// the row's squashing correction from the row's stored actions, the log-probability through normal_logp (the update's own lines) and the environment's action.
+struct ActNormalDraw {  // what the epilogue reads
+    srlx::u64 seed;
+    const i64 *counter;  // read, not advanced
+    double epsilon;
+    float noise_sd, noise_ls;  // policy_noise_normal_scale and (float)log of it, formed on the host
+    float ls_lo, ls_hi;
+    int squashed;
+    const float *low, *high;  // [K]
+    float *actions, *logp, *env_actions;  // [n][K]
+    float *loc, *log_scale;  // [n][K]; NULL: not wanted
+    double *z;               // [n][K]; NULL: not wanted
+};
+struct ActNormalArgs {
+    i64 n;
+    const float *obs;  // [n][D] dense
+    ActNormalDraw draw;
+};
+
+__global__ void __launch_bounds__(kThreads) k_vppo_act_normal(const Net *__restrict__ net, ActNormalArgs args, int rpw, int D, int K, int S) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *b0 = sm, *b1 = sm + kRows * S, *wl = sm + 2 * kRows * S;
+    __shared__ float zs[kRows * kHeadCols], acts[kRows * kNormalLs];
+    // the epilogue's arguments wait in LDS: held in scalar registers through the network pass they spilled (the first barrier below publishes them)
+    __shared__ ActNormalDraw draw;
+    const Net &n = *net;
+    const int t = threadIdx.x;
+    if (t == 0) draw = args.draw;
+    const i64 i0 = (i64)blockIdx.x * rpw;
+    const int nb = (int)(args.n - i0 < rpw ? args.n - i0 : rpw);
+    for (int p = t; p < nb * D; p += kThreads) b0[(p / D) * S + p % D] = args.obs[(i0 + p / D) * D + p % D];
+    __syncthreads();
+    float *T = srlxm::forward_rows<double>(n.trunk, n.trunk.L, nb, b0, b1, S, wl, nullptr, 0, 0, 0);
+    float *z = srlxm::forward_rows<double>(n.policy, n.policy.L + 1, nb, T, T == b0 ? b1 : b0, S, wl, nullptr, 0, 0, 0);
+    const float *hin = z == b0 ? b1 : b0;  // the head's input rows
+    const bool mine = t < nb * K;
+    const int r = t / K, j = t % K;
+    if (mine) zs[r * kHeadCols + j] = z[r * S + j];
+    __syncthreads();
+    srlxm::dense<double>(n.w_ls, n.b_ls, n.policy.in_of(n.policy.L), K, nb, hin, S, z, S, false, wl);
+    __syncthreads();
+    const ActNormalDraw &a = draw;
+    const i64 row = i0 + r;
+    float loc = 0.f, ls = 0.f, sd = 0.f, act = 0.f;
+    if (mine) {
+        const float h_loc = zs[r * kHeadCols + j], h_ls = srlxv::clampf(z[r * S + j], a.ls_lo, a.ls_hi);
+        const srlx::u64 ctr = (srlx::u64)a.counter[0], base = (srlx::u64)(2 * K + 1) * (srlx::u64)row;
+        const double u0 = srlx::u53(srlx::rng_u64(a.seed, ctr, base));
+        const double ua = srlx::u53(srlx::rng_u64(a.seed, ctr, base + 1 + 2 * j));
+        const double ub = srlx::u53(srlx::rng_u64(a.seed, ctr, base + 2 + 2 * j));
+        const double zn = srlxv::act_box_muller(ua, ub);
+        const bool random = srlxv::act_is_random(u0, a.epsilon);
+        loc = random ? 0.f : h_loc, ls = random ? a.noise_ls : h_ls, sd = random ? a.noise_sd : expf(h_ls);
+        act = srlxv::act_normal_action(loc, sd, zn);
+        acts[r * kNormalLs + j] = act;
+        a.actions[row * K + j] = act;
+        if (a.loc) a.loc[row * K + j] = h_loc, a.log_scale[row * K + j] = h_ls;
+        if (a.z) a.z[row * K + j] = zn;
+    }
+    __syncthreads();
+    if (mine) {
+        const float corr = a.squashed ? srlxv::squash_correction(acts + r * kNormalLs, K) : 0.f;
+        float u;
+        a.logp[row * K + j] = srlxv::normal_logp(act, loc, ls, sd, corr, u);
+        a.env_actions[row * K + j] = srlxv::act_env_action(act, a.low[j], a.high[j], a.squashed);
+    }
+}
+
 struct GradArgs {
     const Seg *segs;
     int nseg;
@@ -553,6 +627,7 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act_normal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
     if (e != hipSuccess) {
         srlx_vppo_destroy(h);
         srlx::set_error("vppo_create: device set-up failed: %s", hipGetErrorString(e));
@@ -645,6 +720,31 @@ int srlx_vppo_act(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t s
     ActArgs a{(i64)n_rows, d_obs, (srlx::u64)seed, (const i64 *)d_counter, epsilon, srlxv::act_uniform_logp(h->A), d_actions, d_logp, d_logits, d_cdf};
     hipLaunchKernelGGL(k_vppo_act, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, a, rpw, h->D, h->A,
                        act_lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_vppo_act_normal(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t seed, const int64_t *d_counter, double epsilon, double noise_scale, int squashed,
+                         double log_scale_lo, double log_scale_hi, const float *d_low, const float *d_high, float *d_actions, float *d_logp, float *d_env_actions,
+                         float *d_loc, float *d_log_scale, double *d_z, void *stream) {
+    SRLX_REQUIRE(h, "vppo_act_normal: NULL handle");
+    SRLX_REQUIRE(h->bound, "vppo_act_normal: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(h->head == 1, "vppo_act_normal: the acting kernel serves the Normal head (srlx_vppo_act serves the categorical one)");
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= 65536, "vppo_act_normal: %lld rows (1..65536)", (long long)n_rows);
+    SRLX_REQUIRE(epsilon >= 0.0 && epsilon <= 1.0, "vppo_act_normal: epsilon %g (0..1)", epsilon);
+    SRLX_REQUIRE(noise_scale > 0.0 && std::isfinite(noise_scale), "vppo_act_normal: noise scale %g (positive and finite)", noise_scale);
+    SRLX_REQUIRE(squashed == 0 || squashed == 1, "vppo_act_normal: squashed is 0 or 1");
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_act_normal: the log-scale clamp's ends are ordered");
+    SRLX_REQUIRE(d_obs && d_counter && d_low && d_high && d_actions && d_logp && d_env_actions,
+                 "vppo_act_normal: NULL observations, counter, bounds, actions, log-probabilities or environment actions");
+    SRLX_REQUIRE((d_loc != nullptr) == (d_log_scale != nullptr), "vppo_act_normal: locs and log-scales are written together or not at all");
+    srlx::DeviceGuard g(h->device);
+    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    const int rpw = act_rows_per_workgroup(n_rows);
+    ActNormalArgs a{(i64)n_rows, d_obs, ActNormalDraw{(srlx::u64)seed, (const i64 *)d_counter, epsilon, (float)noise_scale, (float)log(noise_scale), (float)log_scale_lo,
+                                                      (float)log_scale_hi, squashed, d_low, d_high, d_actions, d_logp, d_env_actions, d_loc, d_log_scale, d_z}};
+    hipLaunchKernelGGL(k_vppo_act_normal, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, a, rpw,
+                       h->D, h->A, act_lds_stride(h));
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

@@ -93,6 +93,14 @@ __device__ __forceinline__ float squash_correction(const float *act, int k) {
     return (float)s;
 }
 
+// One element's Normal log-probability, float32: u = (a - loc) / sd comes back, lp = (-0.5 log 2 pi - ls - 0.5 u^2) - corr, with corr the row's squashing
+// correction (0 when plain).  The update's new_logpi and the Normal acting kernel's log-probability are both this function: with unchanged parameters they agree
+// to the bit on every element.
+__device__ __forceinline__ float normal_logp(float a, float loc, float ls, float sd, float corr, float &u) {
+    u = (a - loc) / sd;
+    return (-srlxp::kHalfLog2Pi - ls - 0.5f * (u * u)) - corr;
+}
+
 // Normal row: z = k locs at 0.. and k raw log-scales at kNormalLs.. (LDS) -> lp [k] (global), the row's sums, the seeds into dz in the same layout
 __device__ __forceinline__ void normal_row(const Cfg &c, const float *z, int k, const float *act, const float *old_lp, float q, float tr, float v, RowSums &s,
                                            float *dz, float *lp_out) {
@@ -101,8 +109,8 @@ __device__ __forceinline__ void normal_row(const Cfg &c, const float *z, int k, 
         const float loc = z[j], lsr = z[kNormalLs + j];
         const float ls = clampf(lsr, c.ls_lo, c.ls_hi);
         const float sd = expf(ls);
-        const float u = (act[j] - loc) / sd;
-        const float lp = (-srlxp::kHalfLog2Pi - ls - 0.5f * (u * u)) - corr;
+        float u;
+        const float lp = normal_logp(act[j], loc, ls, sd, corr, u);
         lp_out[j] = lp;
         const float ratio = expf(lp - old_lp[j]);
         value_terms(c, ratio, q, tr, v, s);
@@ -128,6 +136,20 @@ __host__ __device__ __forceinline__ int act_inverse_cdf(const double *c, int A, 
     for (int k = 0; k < A; k++)
         if (thr < c[k]) return k;
     return A - 1;
+}
+
+// ---- the Worker's action on the Normal head (srlx_vppo_act_normal; algorithms/ppo_v.py: Worker.policy, NpArraySpace branch, training).  Row r of a
+// k-element head reads 2 k + 1 keyed uniforms: U0 at (2 k + 1) r, element j's pair at + 1 + 2 j and + 2 + 2 j.  Everything is float64 and host arithmetic as well.
+__host__ __device__ __forceinline__ double act_box_muller(double ua, double ub) {  // one standard normal: 1 - Ua is in (0, 1], the log is finite
+    return sqrt(-2.0 * log(1.0 - ua)) * cos(6.283185307179586 * ub);
+}
+// np.random.normal(loc, scale): the value BEFORE tanh, rounded to the float32 the item holds
+__host__ __device__ __forceinline__ float act_normal_action(float loc, float sd, double z) { return (float)((double)loc + (double)sd * z); }
+// NpArraySpace.rescale_from of tanh(a) (squashed) or of a (plain) from [-1, 1] onto [low, high] in float64, rounded to float32, then sanitize's clip
+__host__ __device__ __forceinline__ float act_env_action(float a, float low, float high, int squashed) {
+    const double x = squashed ? tanh((double)a) : (double)a;
+    const float e = (float)((double)low + (x + 1.0) / 2.0 * ((double)high - (double)low));
+    return e < low ? low : (e > high ? high : e);
 }
 
 }  // namespace srlxv

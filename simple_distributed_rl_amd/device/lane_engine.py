@@ -189,13 +189,16 @@ class SequenceLaneEngine(LaneEngine):
 
 
 class FlatLaneEngine(LaneEngine):
-    """The flat pair: observations [D], A discrete actions, batches of B drawn from a device store (`self.replay`, which the engine makes between `_open_flat` and
-    `_start_envs`) and handed to the trainer's `train_on_batch`, whose libsrlx update handle also runs the acting kernel (`self.actor`)."""
+    """The flat pair: observations [D], A discrete actions (or a continuous action of K elements: `self.K` > 0 and `self.A` = K), batches of B drawn from a device
+    store (`self.replay`, which the engine makes between `_open_flat` and `_start_envs`) and handed to the trainer's `train_on_batch`, whose libsrlx update
+    handle also runs the acting kernel (`self.actor`)."""
 
     def _open_flat(self, rl_config, n_envs, device, seed, parameter, context, why_not, max_episode_steps=None):
         self._open(rl_config, n_envs, device, seed, parameter, lambda: why_not(_ConfigSpaces(rl_config, max_episode_steps), rl_config, n_envs=n_envs))
         c = self.cfg
-        self.D, self.A, self.B = int(c.observation_space.shape[0]), int(c.action_space.n), int(c.batch_size)
+        space = c.action_space
+        self.K = 0 if hasattr(space, "n") else int(space.size)  # 0: A discrete actions; K > 0: a continuous action of K elements (the head's outputs: A = K)
+        self.D, self.A, self.B = int(c.observation_space.shape[0]), int(space.n) if not self.K else self.K, int(c.batch_size)
         self._open_trainer(None, context)  # (train_on_batch is handed its batch: the plugin memory is not needed)
 
     def _start_envs(self, env, **cartpole_kw):
@@ -228,9 +231,10 @@ class FlatLaneEngine(LaneEngine):
         rec.update(counter=int(self.policy_counter.item()), actions=self.actions.cpu().numpy(), **{k: v.cpu().numpy() for k, v in drawn.items()}, first=self._first_host)
         return rec
 
-    def _env_step(self, rec):
-        """The environments' step on `self.actions`; the record gets what they returned, the ledger its episodes."""
-        next_obs, rewards, terminated, done = self.env.step(self.actions)
+    def _env_step(self, rec, env_actions=None):
+        """The environments' step on `self.actions` (or on `env_actions`, where what the environments take is not what the store keeps); the record gets what they
+        returned, the ledger its episodes."""
+        next_obs, rewards, terminated, done = self.env.step(self.actions if env_actions is None else env_actions)
         if rec is not None:
             rec.update(next_obs=next_obs.view(self.E, -1).cpu().numpy(), reward=rewards.cpu().numpy(), terminated=terminated.cpu().numpy(), done=done.cpu().numpy())
             self._first_host = rec["done"].astype(bool)

@@ -300,6 +300,41 @@ class CartPoleVecEnv:
         return self.next_obs, self.rewards, self.terminated, self.done
 
 
+class PendulumLaneVecEnv:
+    """E device-resident Pendulum-v1 environments for a lane engine (envs/pendulum.py, libsrlx srlx_pendulum_lane_step): float64 state (th, thdot), float32
+    observations (cos th, sin th, thdot), one float32 torque per lane.  `CartPoleVecEnv`'s contract, the store's needs_reset protocol included.  (The fused PPO
+    engine's `device/ppo.py: PendulumVecEnv` resets itself inside its step and keeps float32 state: another environment.)"""
+
+    capturable = True
+
+    def __init__(self, replay, max_steps: int = 200, seed: Optional[int] = None):
+        assert not replay.obs_uint8 and replay.F == 3
+        self.replay, self.E, self.max_steps = replay, replay.E, int(max_steps)
+        self.seed = replay.seed if seed is None else int(seed)
+        d = replay.dev
+        self.lib = N.lib()
+        self.state = torch.zeros((self.E, 2), dtype=torch.float64, device=d)
+        self.steps = torch.zeros(self.E, dtype=torch.int32, device=d)
+        self.episodes = torch.zeros(self.E, dtype=torch.int32, device=d)
+        self.next_obs = torch.zeros((self.E, 3), dtype=torch.float32, device=d)
+        self.rewards = torch.zeros(self.E, dtype=torch.float32, device=d)
+        self.terminated = torch.zeros(self.E, dtype=torch.uint8, device=d)
+        self.done = torch.zeros(self.E, dtype=torch.uint8, device=d)
+
+    def reset(self) -> torch.Tensor:
+        N.check(self.lib.srlx_pendulum_lane_step(self.E, N.tptr(self.state), N.tptr(self.steps), N.tptr(self.episodes), None, None, self.max_steps,
+                                                 ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), N.tptr(self.next_obs), None, None, None, N.torch_stream_ptr()))
+        return self.next_obs.clone()
+
+    def step(self, torques: torch.Tensor):
+        """`torques`: float32, E elements ([E] or [E][1])."""
+        assert torques.dtype == torch.float32 and torques.numel() == self.E and torques.is_contiguous()
+        N.check(self.lib.srlx_pendulum_lane_step(self.E, N.tptr(self.state), N.tptr(self.steps), N.tptr(self.episodes), self.replay.needs_reset_ptr, N.tptr(torques),
+                                                 self.max_steps, ctypes.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF), N.tptr(self.next_obs), N.tptr(self.rewards),
+                                                 N.tptr(self.terminated), N.tptr(self.done), N.torch_stream_ptr()))
+        return self.next_obs, self.rewards, self.terminated, self.done
+
+
 @dataclass
 class VectorQConfig:
     # --- dqn.Config fields (srl/algorithms/dqn/dqn.py:50-101)

@@ -187,6 +187,10 @@ class HostVecEnv:
         torch.cuda.current_stream(self.dev).synchronize()
         return first
 
+    def _lane_action(self, acts: np.ndarray, i: int):
+        """Lane i's action as its environment takes it (a subclass with float actions hands over the row)."""
+        return int(acts[i])
+
     def step(self, actions: torch.Tensor):
         from simple_distributed_rl_amd.base.define import DoneTypes
 
@@ -198,7 +202,7 @@ class HostVecEnv:
                 scal[i] = 0.0
                 self._needs_reset[i] = False
                 continue
-            env.step(int(acts[i]))
+            env.step(self._lane_action(acts, i))
             self._take(i)
             scal[i, 0] = env.reward
             scal[i, 1] = 1.0 if env.done_type == DoneTypes.TERMINATED else 0.0
@@ -210,6 +214,14 @@ class HostVecEnv:
         self.terminated.copy_(dev_scal[:, 1].to(torch.uint8))
         self.done.copy_(dev_scal[:, 2].to(torch.uint8))
         return self.next_obs, self.rewards, self.terminated, self.done
+
+
+class FloatActionHostVecEnv(HostVecEnv):
+    """`HostVecEnv` for environments with a continuous action: `step` takes float32 actions [E][K] and hands lane i its row (the V-PPO engine's Normal head,
+    DESIGN.md 7q)."""
+
+    def _lane_action(self, acts: np.ndarray, i: int):
+        return np.asarray(acts[i], np.float32).reshape(-1)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -717,11 +729,30 @@ def why_not_sacd_engine(env, rl_config, n_envs=None) -> str:
     return "; ".join(why)
 
 
-def why_not_vppo_engine(env, rl_config, n_envs=None) -> str:
+def normal_action_bounds(space):
+    """(low, high) as float32 [K] arrays of a continuous action space the Normal head's acting kernel serves -- an NpArraySpace, or a flat continuous
+    BoxSpace((K,)), with finite bounds -- or a sentence saying why it is not one.  K itself is judged by the update's envelope."""
+    from simple_distributed_rl_amd.base.spaces.box import BoxSpace
+    from simple_distributed_rl_amd.base.spaces.np_array import NpArraySpace
+
+    flat = isinstance(space, NpArraySpace) or (type(space) is BoxSpace and len(tuple(space.shape)) == 1 and space.stype == SpaceTypes.CONTINUOUS)
+    if not flat:
+        return "a continuous action space that is not a flat vector of floats (an NpArraySpace or a BoxSpace((K,))): it stays on the plugin path"
+    low, high = np.asarray(space.low, np.float32).reshape(-1), np.asarray(space.high, np.float32).reshape(-1)
+    if not (np.isfinite(low).all() and np.isfinite(high).all()):
+        return "a continuous action space with an infinite bound: the acting kernel rescales its draw onto [low, high]"
+    if not (low <= high).all():
+        return "a continuous action space whose low is above its high"
+    return low, high
+
+
+def why_not_vppo_engine(env, rl_config, n_envs=None, admit_normal=False) -> str:
     """Empty string when `VppoEngine` (device/vppo_engine.py) can run this ppo_v.Config on this environment; otherwise EVERY reason it cannot, joined
     with "; " (as `why_not_sacd_engine`).  The envelope figures are `VppoUpdate.envelope_reason`'s (srlx_vppo_create's, srlx.h): each dimension is asked about on
     its own beside the smallest shape the kernels take.  `env.max_episode_steps` sizes the tracking ring.  `n_envs`: the lane count, when the caller has one.
-    `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep V-PPO on the plugin path; the engine is built around `runner.make_parameter()`."""
+    `Runner.train()` does not ask: `engine_kind` and `why_not_vector` keep V-PPO on the plugin path; the engine is built around `runner.make_parameter()`.
+    `admit_normal`: the caller runs the Normal head too (`VppoNormalEngine`): a flat continuous action space of 1..8 elements with finite bounds is
+    then admitted; the default keeps the categorical engine's answers."""
     from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
     from simple_distributed_rl_amd.device.vppo import VppoUpdate
     from simple_distributed_rl_amd.device.vppo_lanes import MAX_EPISODE_STEPS
@@ -739,7 +770,15 @@ def why_not_vppo_engine(env, rl_config, n_envs=None) -> str:
     if env.player_num != 1:
         why.append("multi-player environment")
     if not isinstance(env.action_space, DiscreteSpace):
-        why.append("a continuous action space: the Normal head's acting kernel is not built, it stays on the plugin path")
+        if not admit_normal:
+            why.append("a continuous action space: the Normal head's acting kernel is not built, it stays on the plugin path")
+        else:
+            bounds = normal_action_bounds(env.action_space)
+            K = None if isinstance(bounds, str) else len(bounds[0])
+            if K is None:
+                why.append(bounds)
+            elif outside(head=1, n_out=K):
+                why.append(f"{K} action elements: " + outside(head=1, n_out=K))
     elif outside(n_out=int(env.action_space.n)):
         why.append(f"{int(env.action_space.n)} actions: " + outside(n_out=int(env.action_space.n)))
     D = flat_dim(frame_space(env, c))

@@ -171,3 +171,14 @@ class VppoUpdate:
         rows = obs if isinstance(obs, ctypes.c_void_p) else N.tptr(obs)
         N.check(self._lib.srlx_vppo_act(self._h, n_rows, rows, ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), N.tptr(counter), float(epsilon), N.tptr(actions),
                                         N.tptr(logp), N.tptr(logits), N.tptr(cdf), N.torch_stream_ptr()))
+
+    def act_normal(self, n_rows: int, obs, seed: int, counter, epsilon: float, noise_scale: float, squashed: bool, low, high, actions, logp, env_actions, loc=None,
+                   log_scale=None, z=None) -> None:
+        """srlx_vppo_act_normal: the Worker's policy() for `n_rows` dense rows [n_rows][D] (a tensor or a device address) in one launch, on the
+        Normal head.  `counter` is a device int64 the call reads; `low` / `high` float32 [K] are the action space's bounds on the device; `actions` (before tanh),
+        `logp` and `env_actions` float32 [n_rows][K] receive the result, `loc` / `log_scale` float32 and `z` float64 [n_rows][K] when given.  The log-scale clamp
+        is the Parameter's own.  Nothing synchronises."""
+        rows = obs if isinstance(obs, ctypes.c_void_p) else N.tptr(obs)
+        N.check(self._lib.srlx_vppo_act_normal(self._h, n_rows, rows, ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), N.tptr(counter), float(epsilon), float(noise_scale),
+                                               int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(low), N.tptr(high), N.tptr(actions), N.tptr(logp),
+                                               N.tptr(env_actions), N.tptr(loc), N.tptr(log_scale), N.tptr(z), N.torch_stream_ptr()))
