@@ -282,8 +282,10 @@ int srlx_synth_env_step_at(srlx_store_t *h, int64_t position, int64_t episode_le
  *   d_skip      uint8 [E] or NULL: lanes that did not take an environment step in this lock-step (the store's
  *               needs_reset view: they only received the first frame of their next episode)
  *   d_ep_return float32 [E], d_ep_len int32 [E]: running return / length of every environment (caller zeroes them once)
- *   d_ring      float32 [ring_cap][2]: (return, length) of finished episodes, appended in environment order
- *   d_totals    32 bytes: int64 episodes finished, int64 environment steps, float64 sum of returns, int64 sum of lengths */
+ *   d_ring      float32 [ring_cap][2]: (return, length) of finished episodes, appended in environment order: episode number k
+ *               (counted from the ledger's start) sits in slot k % ring_cap.  When one call ends more than ring_cap episodes,
+ *               only its newest ring_cap are written -- the same ring as if all had been, one after the other
+ *   d_totals   32 bytes: int64 episodes finished, int64 environment steps, float64 sum of returns, int64 sum of lengths */
 int srlx_episode_account(int64_t n_envs, const float *d_rewards, const uint8_t *d_done, const uint8_t *d_skip, float *d_ep_return,
                          int32_t *d_ep_len, float *d_ring, int64_t ring_cap, void *d_totals, void *stream);
 
@@ -360,9 +362,12 @@ int srlx_gae_scan(int64_t n_envs, int64_t horizon, const float *d_rewards, const
  * Rank-based prioritised replay: srl/rl/memories/priority_memories/rankbased_memory.py:13-77.
  * Which ranks are drawn depends only on N, alpha and numpy's generator and stays on the host (bit-identical
  * np.random.choice); the data-dependent half -- np.argsort(-priorities[:N]) on EVERY sample (:47) -- is a descending
- * radix sort of (priority, index) pairs in HBM + a gather of the drawn ranks.  Ties: the device sort is stable
- * (lower index first), numpy's introsort is not: results agree whenever the priorities are distinct.
- *   srlx_rank_set        : add (:33-40, d_idx NULL: slots (start + i) % capacity) / update (:60-62) of float32 priorities
+ * radix sort of (priority, index) pairs in HBM + a gather of the drawn ranks.  The order is that of
+ * np.argsort(-priorities[:N], kind="stable"): NaN -- what an add without a priority stores (:33-40) -- ranks last as in
+ * numpy, whatever its sign or payload; -0.0 equals +0.0; ties, NaNs among themselves included, are in index order (lower
+ * index first).  numpy's default introsort leaves ties unspecified: results agree with it wherever the priorities are distinct.
+ *   srlx_rank_set        : add (:33-40, d_idx NULL: slots (start + i) % capacity, n <= capacity) / update (:60-62, distinct
+ *                          indices inside the capacity) of float32 priorities
  *   srlx_rank_select     : out[i] = index of the ranks[i]-th largest of priorities[0..n_live)
  *   srlx_rank_priorities : device pointer of the float32 [capacity] priority array (backup / restore, :64-77)
  * ------------------------------------------------------------------------------------------------ */

@@ -28,6 +28,20 @@ __global__ void __launch_bounds__(1024) k_episode_account(i64 E, const float *__
     __shared__ i64 wlen[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const i64 ep0 = tot->episodes;
+    // More lanes than ring slots: one launch can end more episodes than the ring holds, and two of them would then write one slot in no defined
+    // order.  Count the launch's episodes first; only its newest `cap` write below (the older ones would have been overwritten anyway).
+    i64 first_kept = 0;
+    if (E > cap) {
+        __shared__ int wfin[16];
+        int c = 0;
+        for (i64 e = t; e < E; e += 1024) c += (!(skip && skip[e]) && done[e] != 0) ? 1 : 0;
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+        if (lane == 0) wfin[wave] = c;
+        __syncthreads();
+        i64 n_fin = 0;
+        for (int w = 0; w < 16; w++) n_fin += wfin[w];
+        first_kept = n_fin - cap;
+    }
     i64 appended = 0, stepped = 0;
     double ret_acc = 0.0;
     i64 len_acc = 0;
@@ -62,8 +76,9 @@ __global__ void __launch_bounds__(1024) k_episode_account(i64 E, const float *__
             if (w < wave) woff += wcount[w];
             total += wcount[w];
         }
-        if (fin) {
-            const i64 slot = (ep0 + appended + woff + before) % cap;
+        const i64 pos = appended + woff + before;  // this episode's position among the launch's
+        if (fin && pos >= first_kept) {
+            const i64 slot = (ep0 + pos) % cap;
             ring[2 * slot] = R;
             ring[2 * slot + 1] = (float)L;
         }

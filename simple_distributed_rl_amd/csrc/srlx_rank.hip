@@ -20,8 +20,13 @@ namespace {
 using u32 = unsigned int;
 constexpr int kTile = 4096, kWaves = 4, kChunk = kTile / kWaves;  // keys per workgroup / waves per workgroup / keys per wave
 
-__device__ __forceinline__ u32 desc_image(float f) {  // larger float -> smaller integer
-    const u32 u = __float_as_uint(f);
+// larger float -> smaller integer, with numpy's two equalities: -0.0 is +0.0 (folded before the image, so zeros of both signs tie and keep index
+// order) and every NaN, of either sign and any payload, gets the ONE image behind -inf's 0xff800000 (np.argsort(-p) puts NaN last; equal images
+// keep index order).  Done on the bits, so neither a flushed denormal nor a compiler's view of `f + 0.0f` can move a key.
+__device__ __forceinline__ u32 desc_image(float f) {
+    u32 u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if ((u & 0x7fffffffu) == 0u) u = 0u;
     const u32 asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ~asc;
 }
@@ -176,6 +181,7 @@ int srlx_rank_destroy(srlx_rank_t *h) {
 /* priorities[idx[i]] = val[i] (update, :60-62) or, idx == NULL, priorities[(start + i) % capacity] = val[i] (add, :33-40) */
 int srlx_rank_set(srlx_rank_t *h, int64_t n, const int64_t *d_idx, const float *d_val, int64_t start, void *stream) {
     SRLX_REQUIRE(h && d_val && n > 0 && start >= 0, "rank_set: bad argument");
+    SRLX_REQUIRE(d_idx || n <= h->capacity, "rank_set: an add of more items than the capacity would write slots twice");
     srlx::DeviceGuard guard(h->device);
     hipLaunchKernelGGL(k_scatter_prio, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->prio, n, d_idx, d_val, start, h->capacity);
     SRLX_HIP(hipGetLastError());

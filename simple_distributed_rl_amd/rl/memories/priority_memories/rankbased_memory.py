@@ -5,7 +5,9 @@ The reference argsorts all N priorities on every sample().  Here the priorities 
 is decided on the host exactly like the reference does it (`np.random.choice` over the rank probabilities: same
 generator, same consumption, same ranks), and `srlx_rank_select` turns ranks into buffer indices with one descending
 radix sort in HBM.  Host-side edits (add / update) are mirrored in a float32 array and uploaded lazily before the next
-sample.  Ties between equal priorities are ordered by index on the device (numpy's introsort leaves them unspecified)."""
+sample.  The device order is np.argsort(-priorities[:N], kind="stable"): NaN, as stored by an add without a priority,
+ranks last as in numpy; ties (equal priorities, -0.0 and +0.0, the NaNs among themselves) are in index order, where numpy's
+default introsort leaves them unspecified."""
 import ctypes
 import logging
 from typing import Any, List, Optional
