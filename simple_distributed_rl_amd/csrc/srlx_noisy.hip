@@ -11,9 +11,12 @@
 // B-operand loader instead would regenerate every normal once per 128-row tile (8 times at 1024 rows) on the VALU slots that
 // the f32 MFMAs need.
 //
-// Parity with the reference is statistical (its noise comes from torch's Philox stream): tests/test_noisy_gpu.py checks
-// mean / variance of the effective weights and of Q over many draws against torch's NoisyLinear, exact equality at sigma = 0,
-// and the gradients against torch autograd of the same effective weights.
+// Checked by three files.  tests/test_qnet_noisy_envelope_gpu.py: over the envelope this form admits (every head, 1..32 actions, 32 / 64 filters, hidden up to
+// 960, both first-dense-layer data gradients, the grid below at its cap, one-element tensors) the kernels' own eps -- read through a twin handle with mu = 0,
+// sigma = 1 -- equals the float64 host mirror of srlx_noise_math.h, the effective tensors are mu + sigma * eps of it to the bit, and Q, the twelve mu / plain
+// gradients and the six sigma gradients equal float64 arithmetic on those tensors.  tests/test_qnet_noisy_cpu.py: that suite's footing (mirror, tables,
+// yardstick) without a GPU.  tests/test_noisy_gpu.py: parity with the reference, which is statistical (its noise comes from torch's Philox stream) -- moments of
+// the draws and of Q over many draws against torch's NoisyLinear, exact equality at sigma = 0 -- and the engine on rainbow.Config.set_atari_config().
 #include "srlx_noise_math.h"
 #include "srlx_qnet_int.h"
 

@@ -991,6 +991,8 @@ static int backward_impl(srlx_qnet_t *h, int64_t batch, int64_t sample_stride, c
     SRLX_REQUIRE(batch > 0 && batch <= h->max_train && sample_stride >= 1 && batch * sample_stride <= h->max_batch, "qnet_backward_u8: batch %lld x stride %lld out of range",
                  (long long)batch, (long long)sample_stride);
     for (int i = 0; i < 12; i++) SRLX_REQUIRE(g[i], "qnet_backward_u8: gradient buffer %d is NULL", i);
+    // (refused HERE, ahead of every launch: srlx_qnet_noisy_sigma_grads runs last and would leave the twelve other gradients written behind its refusal)
+    SRLX_REQUIRE(!h->sig[0] || h->g_sig[0], "qnet_backward_u8: the network is noisy but no sigma gradient tensors are bound (srlx_qnet_bind_noisy_grads)");
     if (h->rest_on) {  // srlx_qnet_fuse_adam_rest: this pass applies the convolution tensors' optimiser steps itself and leaves the small vectors' to the packing launch
         SRLX_REQUIRE(!h->rest_armed, "qnet_backward_u8: the previous pass's optimiser step was never completed (srlx_qnet_publish must follow every backward pass "
                                      "of a handle with srlx_qnet_fuse_adam_rest)");

@@ -5,7 +5,11 @@ Parity with the reference's noise is statistical by nature (its normals come fro
 where exactness exists -- sigma = 0 reproduces the plain network bit for bit; given the effective weights of a draw (read back
 from the library) the forward equals torch on those weights, and the gradients of mu AND sigma equal torch autograd of
 `mu + sigma * eps` with the same eps -- and the noise itself is checked as a distribution (moments, independence between draws,
-Q statistics against the reference module tree under the same mu / sigma)."""
+Q statistics against the reference module tree under the same mu / sigma).
+
+This file runs ONE geometry (84 x 84 x 4, 32 filters, hidden 512) against float32 torch, with eps recovered as (eff - mu) / sigma.  The envelope this form of the
+network admits -- the other heads, shapes and kernel paths -- against a float64 yardstick on the exact eps of every draw is tests/test_qnet_noisy_envelope_gpu.py
+(footing: tests/test_qnet_noisy_cpu.py, tests/qnet_noisy_reference.py)."""
 import os
 import sys
 
@@ -174,7 +178,7 @@ def test_training_pass_gradients_of_mu_and_sigma_match_autograd(B, stride):
     assert len(qn._params()) == 18
     for name, p, w in zip(names, qn._params(), want):
         scale = float(w.abs().max()) + 1e-12
-        np.testing.assert_allclose(p.grad.cpu().numpy(), w.cpu().numpy(), rtol=2e-4, atol=3e-5 * scale, err_msg=name)
+        np.testing.assert_allclose(p.grad.cpu().numpy(), w.cpu().numpy(), rtol=1e-4, atol=2e-5 * scale, err_msg=name)
 
 
 def test_q_statistics_match_the_reference_module():
