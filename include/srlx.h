@@ -1565,6 +1565,61 @@ int srlx_vppo_lanes_sample_normal(srlx_vppo_lanes_t *h, int64_t batch, uint64_t 
 int srlx_pendulum_lane_step(int64_t n_envs, double *d_state, int32_t *d_steps, int32_t *d_episodes, const uint8_t *d_needs_reset, const float *d_torques,
                             int64_t max_steps, uint64_t seed, float *d_obs, float *d_reward, uint8_t *d_terminated, uint8_t *d_done, void *stream);
 
+/* ---- NoT_SAC on flat observations (srlx_notsac.hip; srl/algorithms/sac_not/torch_model.py:131-191) -------------------------------------------------
+ * A handle is one shape: observations of obs_dim (1..256) floats; head 0 = Gumbel with n_out (2..16) actions, head 1 = Normal with n_out (1..8) action elements;
+ * a policy block and a q block of 1..3 ReLU layers of 32..512 units in multiples of 32 each; act_emb_units (32..512 in multiples of 32) with obs_dim +
+ * act_emb_units <= 512 (the concatenated row is the widest row in LDS); max_batch 1..256.  Everything else is refused at create.  Tensors stay float32; every
+ * sum over a layer's inputs or over the batch accumulates in float64 and is rounded to float32 once; exp, tanh, SiLU, softmax and the Gumbel transform are
+ * evaluated in float64 (srlx_notsac_math.h).  No atomics: equal inputs give equal bits, and a row's outputs do not depend on the rows that share its workgroup
+ * (by default an update runs one row per workgroup; see srlx_notsac_set_rows_per_workgroup).
+ *   srlx_notsac_scratch_floats : floats of device scratch a handle of this shape owns; -1 outside the envelope.  Host arithmetic.
+ *   srlx_notsac_bind           : the parameter tensors by address, n_tensors of them: the policy's in parameters() order ((weight, bias) of every policy-block
+ *                                layer, then of the head's Linear: logits, or locs and then log-scales), then the Q-network's ((weight, bias) of act_block's
+ *                                Linear [E][n_out], of every q-block layer -- the first reads obs_dim + E inputs -- and of q_out).  A count that is not the
+ *                                shape's is refused and leaves the handle as it was.
+ *   srlx_notsac_bind_grads     : the caller's gradient tensors (same order and shapes), twice: d_grads receives the gradients after their network's norm clip
+ *                                (what Adam reads), d_raw_grads those before it.
+ *   srlx_notsac_bind_adam      : exp_avg / exp_avg_sq (same order) and the optimiser steps already taken by BOTH optimisers (the handle counts on from there,
+ *                                srlx_notsac_steps reads the count).
+ *   srlx_notsac_update         : the whole step of one batch in six launches, nothing synchronises.  Inputs: states / next states f32 [B][D]; actions i32 [B]
+ *                                (Gumbel: the index of the stored one-hot's maximum) or f32 [B][K] (Normal: as stored, after tanh when squashed); rewards,
+ *                                not_terminated, total_rewards f32 [B]; noise f32 [2][B][n_out]: standard normals (Normal) or uniforms in [0, 1) (Gumbel), plane
+ *                                0 for the target's next action, plane 1 for the policy step.
+ *                                  a' = tanh(loc(s') + exp(clamp(ls(s'))) e0) (no tanh unless squashed), or the one-hot of the first maximum of logits(s') +
+ *                                  gumbel(u0), gumbel(u) = -log(-log(u + 1e-6) + 1e-6);  target = r + not_terminated * discount * Q(s', a');
+ *                                  loss_q = mean Huber(target - Q(s, a)), loss_q_align = mean (total_reward - Q(s, a))^2, both with their gradient on Q(s, a);
+ *                                  the Q-network's gradient of loss_q + loss_align_coeff * loss_q_align, its norm, clip_grad_norm_(max_grad_norm), Adam(lr);
+ *                                  a = the same sample from the policy on s with plane 1, or softmax(logits(s) + gumbel(u1));
+ *                                  loss_policy = -mean Q(s, a) through the Q-network ALREADY STEPPED; the policy's gradient (the log-scale's is zero outside
+ *                                  the clamp's closed interval), its norm, the clip, Adam(lr).
+ *                                Outputs: q, target_q f32 [B]; next_action, pi_action f32 [B][n_out]; scalars f32 [5] = loss_q, loss_q_align, loss_policy, the
+ *                                Q-network's and the policy's gradient norm before their clips.
+ *   srlx_notsac_set_rows_per_workgroup : the launch shape of the row kernels and of srlx_notsac_forward: 1, 2, 4, 8 or 16 rows per workgroup, or 0 for the
+ *                                default: the smallest of those that keeps the launch within 256 workgroups, which is 1 for every update (B <= 256) and more
+ *                                only for a forward call of more than 256 rows.  It changes the launch shape and never a bit (tests/test_notsac_gpu.py holds
+ *                                updates at 16 rows per workgroup to the bits of the default); there for measurements and tests.
+ *   srlx_notsac_forward        : n rows of states -> the head's outputs (NULL: not wanted): d_head0 f32 [n][n_out] logits or locs, d_head1 the CLAMPED
+ *                                log-scales (Normal only); and, for d_actions f32 [n][n_out] (one-hot or soft rows on the Gumbel head), d_q f32 [n] = Q(s, a)
+ *                                (both NULL: not wanted).  The same chains as the update's.  Needs srlx_notsac_bind only. */
+typedef struct srlx_notsac srlx_notsac_t;
+int64_t srlx_notsac_scratch_floats(int obs_dim, int head, int n_out, int n_policy, const int *policy_widths, int n_q, const int *q_widths, int act_emb_units,
+                                   int64_t max_batch);
+int srlx_notsac_create(srlx_notsac_t **out, int obs_dim, int head, int n_out, int n_policy, const int *policy_widths, int n_q, const int *q_widths, int act_emb_units,
+                       int64_t max_batch, int device);
+int srlx_notsac_destroy(srlx_notsac_t *h);
+int srlx_notsac_bind(srlx_notsac_t *h, int n_tensors, float *const *d_params);
+int srlx_notsac_bind_grads(srlx_notsac_t *h, int n_tensors, float *const *d_grads, float *const *d_raw_grads);
+int srlx_notsac_bind_adam(srlx_notsac_t *h, int n_tensors, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2,
+                          double eps);
+int srlx_notsac_set_rows_per_workgroup(srlx_notsac_t *h, int rows);
+int64_t srlx_notsac_steps(const srlx_notsac_t *h);
+int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_rewards,
+                       const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff,
+                       double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
+                       float *d_pi_action, float *d_scalars, void *stream);
+int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
+                        const float *d_actions, float *d_q, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -300,6 +300,16 @@ SIGNATURES = {
     "srlx_vppo_lanes_push_normal": (c_int, [c_p] * 9),
     "srlx_vppo_lanes_sample_normal": (c_int, [c_p, c_i64, c_u64] + [c_p] * 9),
     "srlx_pendulum_lane_step": (c_int, [c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_notsac_scratch_floats": (c_i64, [c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_i64]),
+    "srlx_notsac_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_i64, c_int]),
+    "srlx_notsac_destroy": (c_int, [c_p]),
+    "srlx_notsac_bind": (c_int, [c_p, c_int, c_p]),
+    "srlx_notsac_bind_grads": (c_int, [c_p, c_int, c_p, c_p]),
+    "srlx_notsac_bind_adam": (c_int, [c_p, c_int, c_p, c_p, c_i64, c_f64, c_f64, c_f64]),
+    "srlx_notsac_set_rows_per_workgroup": (c_int, [c_p, c_int]),
+    "srlx_notsac_steps": (c_i64, [c_p]),
+    "srlx_notsac_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
+    "srlx_notsac_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4
