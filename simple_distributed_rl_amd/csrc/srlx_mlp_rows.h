@@ -1,10 +1,12 @@
-// srlx_mlp_rows.h -- the row-blocked MLP passes shared by the flat-observation kernels: DQN / Rainbow / C51's Q-network (srlx_mlpq.hip, float32 sums) and discrete
-// SAC's five networks (srlx_sacd.hip, float64 sums).  The work is not a GEMM's (<= 16 rows through <= 4 layers of <= 512 units), so launch count and the layer
+// srlx_mlp_rows.h -- the row-blocked MLP passes shared by the flat-observation kernels: DQN / Rainbow / C51's Q-network (srlx_mlpq.hip, float32 sums), discrete
+// SAC's five networks (srlx_sacd.hip), V-PPO's actor-critic (srlx_vppo.hip) and NoT_SAC's policy and Q-network (srlx_notsac.hip; float64 sums).  The work is not a GEMM's (<= 16 rows through <= 4 layers of <= 512 units), so launch count and the layer
 // chain bound it: one workgroup of kThreads threads takes up to kRows rows through the whole network, and back.
 //   Layers         one network as the kernels read it
 //   dense<Acc>     one Linear (+ ReLU) layer over the rows
 //   forward_rows   the first `layers` layers, with the hidden rows kept for the backward pass
 //   backward_rows  d loss / d h_l down the hidden layers, row by row; the top layer through the next weight, or from a seed the caller gives
+//   SumSeed        that seed for a layer which up to three Linear layers read
+//   head_rows      a policy head's output rows in kHeadCols columns: logits, or locs and log-scales
 // Acc = float: one float32 fused multiply-add per term.  Acc = double: the same chain in float64, rounded to float32 once per sum.  Either way every sum runs
 // in k order with no atomics, so equal inputs give equal bits.
 //
@@ -23,6 +25,9 @@ using i64 = int64_t;
 constexpr int kThreads = 256;
 constexpr int kRows = 16;     // rows of one workgroup
 constexpr int kWTile = 8192;  // floats of the weight tile in LDS (32 KB)
+constexpr int kHeadCols = 16;  // a head row in LDS and in the seed tables: A <= 16 logits, or k <= 8 locs at 0.. and k log-scales at kNormalLs..
+constexpr int kNormalLs = 8;
+static_assert(kRows * kHeadCols == kThreads, "one thread per column of a workgroup's head rows (k_notsac_pi_rows zeroes them so)");
 
 // Linear + ReLU layers 0..L-1, then Linear layer L; weights in torch's [out][in] layout.  Scalar fields and selects, no arrays: a kernel-argument array indexed by
 // a run-time layer number is copied to scratch memory.
@@ -150,6 +155,38 @@ __device__ __forceinline__ void backward_rows(const Layers &n, int top, int nb, 
         float *tmp = dcur;
         dcur = dnext, dnext = tmp;
     }
+}
+
+// d loss / d h of a layer that up to three Linear layers read: sum over their output rows' seeds through their weights, one float64 chain
+struct Src {
+    const float *d;  // [rows][stride]
+    int stride, n;   // n = 0: none
+    const float *w;  // [n][W of the layer below]
+};
+struct SumSeed {
+    Src a, b, c;
+    __device__ float operator()(int r, int k, int Wl) const {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int u = 0; u < a.n; u++) acc = fma_acc((double)a.d[r * a.stride + u], (double)a.w[(i64)u * Wl + k], acc);
+        for (int u = 0; u < b.n; u++) acc = fma_acc((double)b.d[r * b.stride + u], (double)b.w[(i64)u * Wl + k], acc);
+        for (int u = 0; u < c.n; u++) acc = fma_acc((double)c.d[r * c.stride + u], (double)c.w[(i64)u * Wl + k], acc);
+        return (float)acc;
+    }
+};
+
+// The head rows of a policy chain `pol` whose out layer's rows are `z` and whose head reads the rows `hin` (both LDS, stride S): zs[r][kHeadCols] = logits, or
+// locs at 0.. and, through the Normal head's second Linear (w_ls NULL: none) and the free buffer b2, RAW log-scales at kNormalLs...  Ends behind a barrier.
+__device__ __forceinline__ void head_rows(const Layers &pol, const float *w_ls, const float *b_ls, int nb, const float *z, const float *hin, float *b2, int S, float *wl,
+                                          float *zs) {
+    const int t = threadIdx.x, HO = pol.Out;
+    if (t < nb * HO) zs[(t / HO) * kHeadCols + t % HO] = z[(t / HO) * S + t % HO];
+    if (w_ls) {
+        dense<double>(w_ls, b_ls, pol.in_of(pol.L), HO, nb, hin, S, b2, S, false, wl);
+        __syncthreads();
+        if (t < nb * HO) zs[(t / HO) * kHeadCols + kNormalLs + t % HO] = b2[(t / HO) * S + t % HO];
+    }
+    __syncthreads();
 }
 
 }  // namespace srlxm

@@ -21,10 +21,8 @@
 // LDS: three row buffers of 16 x (widest row + 1) floats (the act_block's pre-activations have to outlive q_block's chains) and the 32 KB weight tile:
 // 131 264 bytes at a widest row of 512 -- the concatenated row of D + E floats is held to that.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
-#include "srlx_adam_math.h"
-#include "srlx_common.h"
-#include "srlx_mlp_rows.h"
 #include "srlx_notsac_math.h"
+#include "srlx_param_tail.h"
 #include <cmath>
 
 namespace {
@@ -33,26 +31,20 @@ using i64 = int64_t;
 
 using srlxm::kRows;
 using srlxm::kThreads;
-using srlxm::kWTile;
 using srlxm::Layers;
+using srlxm::Src;
+using srlxm::SumSeed;
 using srlxn::kHeadCols;
 using srlxn::kNormalLs;
+using srlxt::Seg;
 constexpr int kNetTensors = 10;  // policy: 2 x (3 layers + 2 heads); Q: 2 x (act_block + 3 layers + q_out)
-constexpr int kMaxTensors = 2 * kNetTensors;
+static_assert(2 * kNetTensors <= srlxt::kMaxTensors, "the policy's tensors, then the Q-network's, in one ParamSet");
 constexpr int kMaxWidth = 512;   // of a hidden layer and of the concatenated row
-constexpr size_t kLdsCap = sizeof(float) * ((size_t)3 * kRows * (kMaxWidth + 1) + kWTile);
 
 struct Net {  // (in device memory: the kernels read it through a pointer)
     Layers pi, q;
     const float *w_ls, *b_ls;  // the Normal head's second Linear (NULL: the Gumbel head)
     const float *wa, *ba;      // act_block's Linear [E][A]
-};
-
-struct Seg {  // one parameter tensor
-    i64 end;          // running element count within its network
-    int stride, in;   // row stride of dout; in = 0: a bias
-    const float *dout, *xin;  // [B][stride] d loss / d (layer output), [B][in] the layer's input rows (NULL: the caller's states)
-    float *p, *g, *graw, *m, *v;
 };
 
 }  // namespace
@@ -63,10 +55,7 @@ struct srlx_notsac {
     int wmax, ntp, ntq;
     int rpw;  // rows per workgroup of the row kernels; 0: rows_per_workgroup's own choice
     i64 max_batch, elements_p, elements_q, blocks_p, blocks_q;
-    float *p[kMaxTensors], *g[kMaxTensors], *graw[kMaxTensors], *m[kMaxTensors], *v[kMaxTensors];  // the policy's tensors, then the Q-network's
-    double beta1, beta2, eps;
-    i64 steps;
-    bool bound, grads_bound, adam_bound, table_ok, net_ok;
+    srlxt::ParamSet ps;  // the policy's tensors, then the Q-network's
     Net *d_net;
     Seg *d_segs;        // [2][kNetTensors]: policy, Q
     float *hp, *dhp;    // planes [3][max_batch][wmax]: the policy's hidden rows and their gradients
@@ -83,7 +72,7 @@ struct srlx_notsac {
 namespace {
 
 int lds_stride(const srlx_notsac *h) { return h->wmax + 1; }
-size_t lds_bytes(const srlx_notsac *h) { return sizeof(float) * ((size_t)3 * kRows * lds_stride(h) + kWTile); }
+size_t lds_bytes(const srlx_notsac *h) { return srlxt::row_lds_bytes(3, h->wmax); }
 
 struct Bufs {
     float *b0, *b1, *b2, *wl;
@@ -98,15 +87,7 @@ __device__ __forceinline__ void pi_forward(const Net &n, const float *__restrict
     for (int p = t; p < nb * D; p += kThreads) B.b0[(p / D) * S + p % D] = states[(i0 + p / D) * D + p % D];
     __syncthreads();
     const float *z = srlxm::forward_rows<double>(n.pi, n.pi.L + 1, nb, B.b0, B.b1, S, B.wl, keep, plane, i0, keep ? nb : 0);
-    const float *hin = z == B.b0 ? B.b1 : B.b0;  // the head's input rows
-    const int HO = n.pi.Out;
-    if (t < nb * HO) zs[(t / HO) * kHeadCols + t % HO] = z[(t / HO) * S + t % HO];
-    if (n.w_ls) {
-        srlxm::dense<double>(n.w_ls, n.b_ls, n.pi.in_of(n.pi.L), HO, nb, hin, S, B.b2, S, false, B.wl);
-        __syncthreads();
-        if (t < nb * HO) zs[(t / HO) * kHeadCols + kNormalLs + t % HO] = B.b2[(t / HO) * S + t % HO];
-    }
-    __syncthreads();
+    srlxm::head_rows(n.pi, n.w_ls, n.b_ls, nb, z, z == B.b0 ? B.b1 : B.b0, B.b2, S, B.wl, zs);
 }
 
 struct QKeep {  // what the Q-network's forward leaves in global memory (NULL: not kept)
@@ -161,20 +142,6 @@ __device__ __forceinline__ float *q_backward(const Net &n, int nb, i64 i0, int D
     __syncthreads();
     return out;
 }
-
-// d loss / d h of the policy's top hidden layer, which the head's one or two Linear layers read: one float64 chain over both
-struct HeadSeed {
-    const float *d;  // [rows][kHeadCols]
-    int n;
-    const float *w, *w_ls;  // [n][W of the layer below]; w_ls NULL: the Gumbel head
-    __device__ float operator()(int r, int k, int Wl) const {
-        double acc = 0.0;
-        for (int u = 0; u < n; u++) acc = srlxm::fma_acc((double)d[r * kHeadCols + u], (double)w[(i64)u * Wl + k], acc);
-        if (w_ls)
-            for (int u = 0; u < n; u++) acc = srlxm::fma_acc((double)d[r * kHeadCols + kNormalLs + u], (double)w_ls[(i64)u * Wl + k], acc);
-        return (float)acc;
-    }
-};
 
 struct Batch {
     i64 B;
@@ -275,7 +242,7 @@ __global__ void __launch_bounds__(kThreads) k_notsac_pi_rows(const Net *__restri
     const bool normal = n.w_ls != nullptr;
     pi_forward(n, args.a.s, i0, nb, D, B, args.w.hp, args.w.plane, zs);
     const float *noise = a.noise + a.B * A;  // plane 1
-    dzs[t] = 0.f;  // (kRows * kHeadCols = kThreads)
+    dzs[t] = 0.f;  // (kRows * kHeadCols = kThreads: srlx_mlp_rows.h asserts it)
     if (normal) {
         if (t < nb * A) {
             const int r = t / A, j = t % A;
@@ -319,7 +286,12 @@ __global__ void __launch_bounds__(kThreads) k_notsac_pi_rows(const Net *__restri
     __syncthreads();
     if (t < nb * kHeadCols) w.dlast_p[i0 * kHeadCols + t] = dzs[t];
     const int Lp = n.pi.L;
-    srlxm::backward_rows<double>(n.pi, Lp - 1, nb, i0, B.b0, B.b1, S, w.hp, w.dhp, w.plane, HeadSeed{dzs, n.pi.Out, n.pi.weight(Lp), n.w_ls});
+    // the policy's top hidden layer is read by the head's one or two Linear layers: one float64 chain over both
+    const int HO = n.pi.Out;
+    const Src none{nullptr, 0, 0, nullptr};
+    const Src head{dzs, kHeadCols, HO, n.pi.weight(Lp)};
+    const Src head_ls = normal ? Src{dzs + kNormalLs, kHeadCols, HO, n.w_ls} : none;
+    srlxm::backward_rows<double>(n.pi, Lp - 1, nb, i0, B.b0, B.b1, S, w.hp, w.dhp, w.plane, SumSeed{head, head_ls, none});
 }
 
 __global__ void __launch_bounds__(kThreads) k_notsac_forward(const Net *__restrict__ net, i64 rows, const float *__restrict__ states, const float *__restrict__ actions,
@@ -347,115 +319,40 @@ __global__ void __launch_bounds__(kThreads) k_notsac_forward(const Net *__restri
     }
 }
 
+// The loss sums of k_notsac_grad's last n threads, one scale for all: out[k] = scale * sum of rows[k]
+struct LossSums {
+    int n;  // <= 2
+    i64 B;
+    const float *rows;  // [n][max_batch]
+    i64 max_batch;
+    double scale;
+    float *out;  // [n]
+    __device__ void operator()(int k) const {
+        double s = 0.0;
+        for (i64 b = 0; b < B; b++) s += (double)rows[k * max_batch + b];
+        out[k] = (float)(s * scale);
+    }
+};
+
 struct GradArgs {
     const Seg *segs;
     int nseg;
-    i64 B;
     const float *xin0;  // the caller's states: the input rows of the policy's first layer
-    const float *rows;  // [n_loss][max_batch]
-    i64 max_batch;
-    int n_loss;         // <= 2
-    double scale;       // of every loss sum
     double *partials;
-    float *out;         // [n_loss]
+    LossSums sums;
 };
 
-__global__ void __launch_bounds__(kThreads) k_notsac_grad(GradArgs a) {
-    __shared__ double sq[kThreads];
-    const int t = threadIdx.x;
-    const i64 i = (i64)blockIdx.x * kThreads + t;
-    const i64 last = (i64)gridDim.x * kThreads;
-    double mine = 0.0;
-    if (i >= last - a.n_loss) {
-        // (the last block's last threads: the launch rounds the element count + 2 up, so they exist and own no element)
-        const int k = (int)(i - (last - a.n_loss));
-        double s = 0.0;
-        for (i64 b = 0; b < a.B; b++) s += (double)a.rows[k * a.max_batch + b];
-        a.out[k] = (float)(s * a.scale);
-    } else if (i < a.segs[a.nseg - 1].end) {
-        int s = 0;
-        while (i >= a.segs[s].end) s++;
-        const Seg sg = a.segs[s];
-        const i64 e = i - (s ? a.segs[s - 1].end : 0);
-        const int St = sg.stride, In = sg.in;
-        double acc = 0.0;
-        if (In) {
-            const int u = (int)(e / In), k = (int)(e % In);
-            const float *dout = sg.dout + u, *xin = (sg.xin ? sg.xin : a.xin0) + k;
-#pragma unroll 8
-            for (int b = 0; b < (int)a.B; b++) acc = fma((double)dout[(i64)b * St], (double)xin[(i64)b * In], acc);
-        } else {
-            const float *dout = sg.dout + e;
-#pragma unroll 8
-            for (int b = 0; b < (int)a.B; b++) acc += (double)dout[(i64)b * St];
-        }
-        const float g = (float)acc;
-        sg.graw[e] = g;
-        mine = (double)g * (double)g;
-    }
-    sq[t] = mine;
-    __syncthreads();
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if (t < w) sq[t] += sq[t + w];
-        __syncthreads();
-    }
-    if (t == 0) a.partials[blockIdx.x] = sq[0];
-}
+__global__ void __launch_bounds__(kThreads) k_notsac_grad(GradArgs a) { srlxt::grad_body(a.segs, a.nseg, a.sums.B, a.xin0, a.partials, a.sums); }
 
-struct StepArgs {
-    const Seg *segs;
-    int nseg;
-    const double *partials;
-    i64 n_partials;
-    float max_norm;
-    double lr, beta1, beta2, eps;
-    i64 steps_taken;
-    float *norm_out;
-};
-
-__global__ void __launch_bounds__(kThreads) k_notsac_step(StepArgs a) {
-    __shared__ double sq[kThreads];
-    const int t = threadIdx.x;
-    double mine = 0.0;
-    for (i64 k = t; k < a.n_partials; k += kThreads) mine += a.partials[k];
-    sq[t] = mine;
-    __syncthreads();
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if (t < w) sq[t] += sq[t + w];
-        __syncthreads();
-    }
-    // clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)) in float32, and the gradients are always multiplied by it
-    const float norm = (float)sqrt(sq[0]);
-    const float coef = fminf(1.f, a.max_norm / (norm + 1e-6f));
-    const i64 i = (i64)blockIdx.x * kThreads + t;
-    if (i == 0) a.norm_out[0] = norm;
-    if (i >= a.segs[a.nseg - 1].end) return;
-    int s = 0;
-    while (i >= a.segs[s].end) s++;
-    const Seg sg = a.segs[s];
-    const i64 e = i - (s ? a.segs[s - 1].end : 0);
-    const float g = sg.graw[e] * coef;
-    sg.g[e] = g;
-    const srlx::AdamCoef c = srlx::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.steps_taken);
-    float p = sg.p[e], m = sg.m[e], v = sg.v[e];
-    srlx::adam_one_foreach(p, g, m, v, c);
-    sg.p[e] = p, sg.m[e] = m, sg.v[e] = v;
-}
-
-bool widths_ok(int n, const int *w) {
-    if (n < 1 || n > 3 || !w) return false;
-    for (int l = 0; l < n; l++)
-        if (w[l] < 32 || w[l] > kMaxWidth || w[l] % 32) return false;
-    return true;
-}
+__global__ void __launch_bounds__(kThreads) k_notsac_step(srlxt::StepArgs a) { srlxt::step_body(a); }
 
 int check_shape(const char *who, int D, int head, int A, int np, const int *pw, int nq, const int *qw, int E, i64 max_batch) {
     SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
     SRLX_REQUIRE(head == 0 || head == 1, "%s: head kind %d (0 Gumbel, 1 Normal)", who, head);
     SRLX_REQUIRE(head == 1 || (A >= 2 && A <= 16), "%s: %d actions (2..16)", who, A);
     SRLX_REQUIRE(head == 0 || (A >= 1 && A <= 8), "%s: %d action elements (1..8)", who, A);
-    SRLX_REQUIRE(widths_ok(np, pw), "%s: the policy block is 1..3 layers of 32..512 units in multiples of 32", who);
-    SRLX_REQUIRE(widths_ok(nq, qw), "%s: the q block is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(np, 1, 3, pw), "%s: the policy block is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(nq, 1, 3, qw), "%s: the q block is 1..3 layers of 32..512 units in multiples of 32", who);
     SRLX_REQUIRE(E >= 32 && E <= kMaxWidth && E % 32 == 0, "%s: %d action-embedding units (32..512 in multiples of 32)", who, E);
     SRLX_REQUIRE(D + E <= kMaxWidth, "%s: the concatenated row of %d + %d floats is wider than %d (the row buffers in LDS)", who, D, E, kMaxWidth);
     SRLX_REQUIRE(max_batch >= 1 && max_batch <= 256, "%s: max_batch %lld (1..256)", who, (long long)max_batch);
@@ -485,26 +382,17 @@ i64 elements_of(int n, const int (*shape)[2]) {
     return e;
 }
 
-Layers chain(int In, int L, const int *W, int Out, float *const *p) {
-    Layers n;
-    n.In = In, n.L = L, n.Out = Out;
-    n.W0 = W[0], n.W1 = L > 1 ? W[1] : 0, n.W2 = L > 2 ? W[2] : 0;
-    const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int l = 0; l <= L; l++) w[l] = p[2 * l], b[l] = p[2 * l + 1];
-    n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
-    return n;
-}
-
 int upload_net(srlx_notsac *h) {
     Net n;
-    n.pi = chain(h->D, h->Lp, h->Wp, h->A, h->p);
-    n.w_ls = h->head ? h->p[2 * (h->Lp + 1)] : nullptr;
-    n.b_ls = h->head ? h->p[2 * (h->Lp + 1) + 1] : nullptr;
-    float *const *q = h->p + h->ntp;
+    float *const *p = h->ps.p;
+    n.pi = srlxt::chain(h->D, h->Lp, h->Wp, h->A, p);
+    n.w_ls = h->head ? p[2 * (h->Lp + 1)] : nullptr;
+    n.b_ls = h->head ? p[2 * (h->Lp + 1) + 1] : nullptr;
+    float *const *q = p + h->ntp;
     n.wa = q[0], n.ba = q[1];
-    n.q = chain(h->D + h->E, h->Lq, h->Wq, 1, q + 2);
+    n.q = srlxt::chain(h->D + h->E, h->Lq, h->Wq, 1, q + 2);
     SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(n), hipMemcpyHostToDevice));
-    h->net_ok = true;
+    h->ps.net_ok = true;
     return SRLX_OK;
 }
 
@@ -516,7 +404,6 @@ int upload_table(srlx_notsac *h) {
     // ---- the policy
     int nl = policy_shapes(h, shape);
     i64 end = 0;
-    int s = 0;
     for (int l = 0; l < nl; l++) {
         const float *dout, *xin;
         int stride = shape[l][0];
@@ -525,13 +412,7 @@ int upload_table(srlx_notsac *h) {
         } else {  // 0: logits or locs, 1: log-scales
             dout = h->dlast_p + (l - h->Lp ? kNormalLs : 0), stride = kHeadCols, xin = h->hp + (i64)(h->Lp - 1) * plane;
         }
-        for (int j = 0; j < 2; j++, s++) {
-            Seg &g = segs[s];
-            end += j == 0 ? (i64)shape[l][0] * shape[l][1] : shape[l][0];
-            g.end = end, g.stride = stride, g.in = j == 0 ? shape[l][1] : 0;
-            g.dout = dout, g.xin = xin;
-            g.p = h->p[s], g.g = h->g[s], g.graw = h->graw[s], g.m = h->m[s], g.v = h->v[s];
-        }
+        srlxt::push_linear(segs + 2 * l, end, shape[l][0], shape[l][1], stride, dout, xin, h->ps, 2 * l);
     }
     // ---- the Q-network
     nl = q_shapes(h, shape);
@@ -546,17 +427,10 @@ int upload_table(srlx_notsac *h) {
         } else {
             dout = h->dlast_q, xin = h->hq + (i64)(h->Lq - 1) * plane;
         }
-        for (int j = 0; j < 2; j++) {
-            const int ti = h->ntp + 2 * l + j;
-            Seg &g = segs[kNetTensors + 2 * l + j];
-            end += j == 0 ? (i64)shape[l][0] * shape[l][1] : shape[l][0];
-            g.end = end, g.stride = shape[l][0], g.in = j == 0 ? shape[l][1] : 0;
-            g.dout = dout, g.xin = xin;
-            g.p = h->p[ti], g.g = h->g[ti], g.graw = h->graw[ti], g.m = h->m[ti], g.v = h->v[ti];
-        }
+        srlxt::push_linear(segs + kNetTensors + 2 * l, end, shape[l][0], shape[l][1], shape[l][0], dout, xin, h->ps, h->ntp + 2 * l);
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
-    h->table_ok = true;
+    h->ps.table_ok = true;
     return SRLX_OK;
 }
 
@@ -575,15 +449,8 @@ void fill(srlx_notsac *h, int D, int head, int A, int np, const int *pw, int nq,
     h->blocks_q = (h->elements_q + 2 + kThreads - 1) / kThreads;
 }
 
-// rows per workgroup of the row kernels: the smallest of 1, 2, 4, 8, 16 that keeps the launch within one workgroup for each of the MI355X's 256 compute units (a
-// workgroup's time grows with its rows, and every workgroup of a launch that fits the machine runs at once: DESIGN.md 7n).  A row's chains are the same whatever
-// rows share its workgroup, so this changes the launch shape and never a bit.
-int rows_per_workgroup(const srlx_notsac *h, i64 n) {
-    if (h->rpw) return h->rpw;
-    int rpw = 1;
-    while (rpw < kRows && (n + rpw - 1) / rpw > 256) rpw *= 2;
-    return rpw;
-}
+// rows per workgroup of the row kernels: what srlx_notsac_set_rows_per_workgroup asked for, or the shared rule
+int rows_per_workgroup(const srlx_notsac *h, i64 n) { return h->rpw ? h->rpw : srlxt::rows_per_workgroup(n); }
 
 i64 scratch_floats(const srlx_notsac *h) {
     const i64 mb = h->max_batch, blocks = h->blocks_p > h->blocks_q ? h->blocks_p : h->blocks_q;
@@ -628,10 +495,9 @@ int srlx_notsac_create(srlx_notsac_t **out, int obs_dim, int head, int n_out, in
     if (e == hipSuccess) e = hipMalloc((void **)&h->rows, sizeof(float) * 3 * mb);
     if (e == hipSuccess) e = hipMalloc((void **)&h->partials, sizeof(double) * blocks);
     if (e == hipSuccess) e = hipMemset(h->dlast_p, 0, sizeof(float) * mb * kHeadCols);
-    // (the cap is the most any handle asks for: creating a narrow handle never lowers it under a wide one that is still alive)
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_q_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_pi_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_q_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_pi_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
     if (e != hipSuccess) {
         srlx_notsac_destroy(h);
         srlx::set_error("notsac_create: device set-up failed: %s", hipGetErrorString(e));
@@ -654,32 +520,20 @@ int srlx_notsac_destroy(srlx_notsac_t *h) {
 int srlx_notsac_bind(srlx_notsac_t *h, int n_tensors, float *const *d_params) {
     SRLX_REQUIRE(h && d_params, "notsac_bind: NULL argument");
     SRLX_REQUIRE(n_tensors == h->ntp + h->ntq, "notsac_bind: %d tensors (this shape has %d policy tensors, then %d Q tensors)", n_tensors, h->ntp, h->ntq);
-    for (int i = 0; i < n_tensors; i++) SRLX_REQUIRE(d_params[i], "notsac_bind: parameter %d is NULL", i);
-    for (int i = 0; i < n_tensors; i++) h->p[i] = d_params[i];
-    h->bound = true, h->table_ok = h->net_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_params("notsac_bind", n_tensors, d_params);
 }
 
 int srlx_notsac_bind_grads(srlx_notsac_t *h, int n_tensors, float *const *d_grads, float *const *d_raw_grads) {
     SRLX_REQUIRE(h && d_grads && d_raw_grads, "notsac_bind_grads: NULL argument");
     SRLX_REQUIRE(n_tensors == h->ntp + h->ntq, "notsac_bind_grads: %d tensors (this shape has %d + %d)", n_tensors, h->ntp, h->ntq);
-    for (int i = 0; i < n_tensors; i++) SRLX_REQUIRE(d_grads[i] && d_raw_grads[i], "notsac_bind_grads: gradient tensor %d is NULL", i);
-    for (int i = 0; i < n_tensors; i++) h->g[i] = d_grads[i], h->graw[i] = d_raw_grads[i];
-    h->grads_bound = true, h->table_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_grads("notsac_bind_grads", n_tensors, d_grads, d_raw_grads);
 }
 
 int srlx_notsac_bind_adam(srlx_notsac_t *h, int n_tensors, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2,
                           double eps) {
     SRLX_REQUIRE(h && d_exp_avg && d_exp_avg_sq, "notsac_bind_adam: NULL argument");
     SRLX_REQUIRE(n_tensors == h->ntp + h->ntq, "notsac_bind_adam: %d tensors (this shape has %d + %d)", n_tensors, h->ntp, h->ntq);
-    SRLX_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0, "notsac_bind_adam: betas in [0, 1) and eps > 0");
-    SRLX_REQUIRE(steps_taken >= 0, "notsac_bind_adam: the step count is non-negative");
-    for (int i = 0; i < n_tensors; i++) SRLX_REQUIRE(d_exp_avg[i] && d_exp_avg_sq[i], "notsac_bind_adam: state %d is NULL", i);
-    for (int i = 0; i < n_tensors; i++) h->m[i] = d_exp_avg[i], h->v[i] = d_exp_avg_sq[i];
-    h->steps = steps_taken, h->beta1 = beta1, h->beta2 = beta2, h->eps = eps;
-    h->adam_bound = true, h->table_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_adam("notsac_bind_adam", n_tensors, d_exp_avg, d_exp_avg_sq, steps_taken, beta1, beta2, eps);
 }
 
 int srlx_notsac_set_rows_per_workgroup(srlx_notsac_t *h, int rows) {
@@ -694,13 +548,13 @@ int64_t srlx_notsac_steps(const srlx_notsac_t *h) {
         srlx::set_error("notsac_steps: NULL handle");
         return -1;
     }
-    return h->steps;
+    return h->ps.steps;
 }
 
 int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
                         const float *d_actions, float *d_q, void *stream) {
     SRLX_REQUIRE(h && d_states, "notsac_forward: NULL handle or states");
-    SRLX_REQUIRE(h->bound, "notsac_forward: unbound handle (srlx_notsac_bind)");
+    SRLX_REQUIRE(h->ps.bound, "notsac_forward: unbound handle (srlx_notsac_bind)");
     SRLX_REQUIRE(n >= 1 && n <= (int64_t)1 << 24, "notsac_forward: %lld rows (1..2^24)", (long long)n);
     SRLX_REQUIRE(d_head0 || d_q, "notsac_forward: nothing to write");
     SRLX_REQUIRE(!d_head1 || (d_head0 && h->head == 1), "notsac_forward: log-scales go with locs, on a Normal head");
@@ -708,7 +562,7 @@ int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, doub
     SRLX_REQUIRE((d_q != nullptr) == (d_actions != nullptr), "notsac_forward: q goes with actions");
     SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "notsac_forward: the log-scale clamp's ends are ordered");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
     const int rpw = rows_per_workgroup(h, n);
     hipLaunchKernelGGL(k_notsac_forward, dim3((unsigned)((n + rpw - 1) / rpw)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states,
                        d_actions, d_head0, d_head1, d_q, (float)log_scale_lo, (float)log_scale_hi, rpw, h->D, h->A, h->E, lds_stride(h));
@@ -721,7 +575,7 @@ int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, c
                        double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
                        float *d_pi_action, float *d_scalars, void *stream) {
     SRLX_REQUIRE(h, "notsac_update: NULL handle");
-    SRLX_REQUIRE(h->bound && h->grads_bound && h->adam_bound, "notsac_update: bind the parameters, the gradient tensors and the Adam state first");
+    SRLX_REQUIRE(h->ps.ready(), "notsac_update: bind the parameters, the gradient tensors and the Adam state first");
     SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "notsac_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
     SRLX_REQUIRE(d_states && d_next_states && d_actions && d_rewards && d_not_terminated && d_total_rewards && d_noise && d_q && d_target_q && d_next_action &&
                      d_pi_action && d_scalars,
@@ -730,8 +584,8 @@ int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, c
     SRLX_REQUIRE(squashed == 0 || squashed == 1, "notsac_update: squashed is 0 or 1");
     SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "notsac_update: the log-scale clamp's ends are ordered");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
-    if (!h->table_ok) SRLX_TRY(upload_table(h));
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
     hipStream_t st = (hipStream_t)stream;
     const double inv_b = 1.0 / (double)batch;
     const Cfg c{(float)discount, (float)loss_align_coeff, (float)log_scale_lo, (float)log_scale_hi, inv_b, squashed};
@@ -744,18 +598,18 @@ int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, c
     const Seg *segs_p = h->d_segs, *segs_q = h->d_segs + kNetTensors;
     // ---- the Q step
     hipLaunchKernelGGL(k_notsac_q_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
-    const GradArgs gq{segs_q, h->ntq, (i64)batch, d_states, h->rows, h->max_batch, 2, inv_b, h->partials, d_scalars};
+    const GradArgs gq{segs_q, h->ntq, d_states, h->partials, LossSums{2, (i64)batch, h->rows, h->max_batch, inv_b, d_scalars}};
     hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_q), dim3(kThreads), 0, st, gq);
-    const StepArgs sq{segs_q, h->ntq, h->partials, h->blocks_q, (float)max_grad_norm, lr, h->beta1, h->beta2, h->eps, h->steps, d_scalars + 3};
+    const srlxt::StepArgs sq = h->ps.step_args(segs_q, h->ntq, h->partials, h->blocks_q, max_grad_norm, lr, d_scalars + 3);
     hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_q + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sq);
     // ---- the policy step, through the Q-network as it stands now
     hipLaunchKernelGGL(k_notsac_pi_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
-    const GradArgs gp{segs_p, h->ntp, (i64)batch, d_states, h->rows + 2 * h->max_batch, h->max_batch, 1, -inv_b, h->partials, d_scalars + 2};
+    const GradArgs gp{segs_p, h->ntp, d_states, h->partials, LossSums{1, (i64)batch, h->rows + 2 * h->max_batch, h->max_batch, -inv_b, d_scalars + 2}};
     hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_p), dim3(kThreads), 0, st, gp);
-    const StepArgs sp{segs_p, h->ntp, h->partials, h->blocks_p, (float)max_grad_norm, lr, h->beta1, h->beta2, h->eps, h->steps, d_scalars + 4};
+    const srlxt::StepArgs sp = h->ps.step_args(segs_p, h->ntp, h->partials, h->blocks_p, max_grad_norm, lr, d_scalars + 4);
     hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_p + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sp);
     SRLX_HIP(hipGetLastError());
-    h->steps++;
+    h->ps.steps++;
     return SRLX_OK;
 }
 

@@ -6,13 +6,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include "srlx_mlp_rows.h"
+#include "srlx_ppo_math.h"
+
 namespace srlxn {
 
-constexpr int kHeadCols = 16;  // a row's head outputs, actions and their gradients: 16 logits, or 8 locs at 0.. and 8 log-scales at kNormalLs..
-constexpr int kNormalLs = 8;
+using srlxm::kHeadCols;  // a row's head outputs, actions and their gradients: 16 logits, or 8 locs at 0.. and 8 log-scales at kNormalLs..
+using srlxm::kNormalLs;
+using srlxp::clampf;
 constexpr double kGumbelEps = 1e-6;
-
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 // SiLU and its derivative at the pre-activation z
 __device__ __forceinline__ float silu(float z) {

@@ -16,9 +16,7 @@
 //   k_sacd_act         the policy's logits of ring rows and the Worker's action (uniform while start_steps last, Gumbel-max after), one launch per lock-step
 //   k_sacd_ring_batch  the drawn items' rows out of the ring as the update's dense tensors
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
-#include "srlx_adam_math.h"
-#include "srlx_common.h"
-#include "srlx_mlp_rows.h"
+#include "srlx_param_tail.h"
 #include "srlx_sacd_math.h"
 #include <cmath>
 
@@ -29,7 +27,6 @@ using u8 = unsigned char;
 
 using srlxm::kRows;
 using srlxm::kThreads;
-using srlxm::kWTile;
 constexpr int kNets = 5;      // policy, q1_online, q1_target, q2_online, q2_target
 constexpr int kMaxSegs = 16;  // q1 + q2: 2 networks x 4 layers x (weight, bias)
 
@@ -74,12 +71,9 @@ namespace {
 int n_tensors_policy(const srlx_sacd *h) { return 2 * (h->Lp + 1); }
 int n_tensors_q(const srlx_sacd *h) { return 2 * (h->Lq + 1); }
 int lds_stride(const srlx_sacd *h) { return h->wmax + 1; }
-size_t lds_bytes(const srlx_sacd *h) { return sizeof(float) * ((size_t)2 * kRows * lds_stride(h) + kWTile); }
+size_t lds_bytes(const srlx_sacd *h) { return srlxt::row_lds_bytes(2, h->wmax); }
 int act_lds_stride(const srlx_sacd *h) { return h->wmax_policy + 1; }
-size_t act_lds_bytes(const srlx_sacd *h) { return sizeof(float) * ((size_t)2 * kRows * act_lds_stride(h) + kWTile); }
-// the most any handle asks of k_sacd_act (rows of 512 floats): the kernel's cap is set to this at every create, so that creating a narrower handle never
-// lowers it under what an earlier, wider handle launches with
-constexpr size_t kActLdsCap = sizeof(float) * ((size_t)2 * kRows * (512 + 1) + kWTile);
+size_t act_lds_bytes(const srlx_sacd *h) { return srlxt::row_lds_bytes(2, h->wmax_policy); }
 
 // the whole network over the rows in buf0; returns the buffer that holds the output rows, behind a barrier (srlx_mlp_rows.h: the kept planes)
 __device__ __forceinline__ float *forward_rows(const NetD &n, int rows, float *buf0, float *buf1, int S, float *wl, float *keep, i64 keep_plane, i64 keep_row0,
@@ -422,18 +416,11 @@ int set_lds(const void *fn, size_t bytes) {
     return SRLX_OK;
 }
 
-bool widths_ok(int n, const int *w) {
-    if (n < 1 || n > 3 || !w) return false;
-    for (int l = 0; l < n; l++)
-        if (w[l] < 32 || w[l] > 512 || w[l] % 32) return false;
-    return true;
-}
-
 int check_shape(const char *who, int D, int A, int n_policy, const int *pw, int n_q, const int *qw, i64 max_batch) {
     SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
     SRLX_REQUIRE(A >= 2 && A <= 16, "%s: %d actions (2..16)", who, A);
-    SRLX_REQUIRE(widths_ok(n_policy, pw), "%s: the policy block is 1..3 layers of 32..512 units in multiples of 32", who);
-    SRLX_REQUIRE(widths_ok(n_q, qw), "%s: the q block is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(n_policy, 1, 3, pw), "%s: the policy block is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(n_q, 1, 3, qw), "%s: the q block is 1..3 layers of 32..512 units in multiples of 32", who);
     SRLX_REQUIRE(max_batch >= 1 && max_batch <= 256, "%s: max_batch %lld (1..256)", who, (long long)max_batch);
     return SRLX_OK;
 }
@@ -452,16 +439,7 @@ void layer_shape(int In, int L, const int *W, int Out, int l, int *out, int *in)
 }
 
 NetD net_of(const srlx_sacd *h, int k) {
-    const bool pol = k == 0;
-    const int L = pol ? h->Lp : h->Lq;
-    const int *W = pol ? h->Wp : h->Wq;
-    NetD n;
-    n.In = pol ? h->D : h->D + h->A, n.L = L, n.Out = pol ? h->A : 1;
-    n.W0 = W[0], n.W1 = L > 1 ? W[1] : 0, n.W2 = L > 2 ? W[2] : 0;
-    const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int l = 0; l <= L; l++) w[l] = h->p[k][2 * l], b[l] = h->p[k][2 * l + 1];
-    n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
-    return n;
+    return k == 0 ? srlxt::chain(h->D, h->Lp, h->Wp, h->A, h->p[0]) : srlxt::chain(h->D + h->A, h->Lq, h->Wq, 1, h->p[k]);
 }
 
 // the segment tables of the two gradient launches, from everything that is bound
@@ -562,7 +540,7 @@ int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_q_rows, lds);
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_policy, lds);
     if (st == SRLX_OK) st = set_lds((const void *)k_sacd_forward, lds);
-    if (st == SRLX_OK) st = set_lds((const void *)k_sacd_act, kActLdsCap);
+    if (st == SRLX_OK) st = set_lds((const void *)k_sacd_act, srlxt::kLdsCap2);
     if (st != SRLX_OK) {
         srlx_sacd_destroy(h);
         return st;
@@ -652,14 +630,6 @@ int srlx_sacd_forward(srlx_sacd_t *h, int64_t n, const float *d_states, int targ
     return SRLX_OK;
 }
 
-// rows per workgroup of k_sacd_act: 16 once that still leaves a workgroup for each of the MI355X's 256 compute units, fewer below (a workgroup's time grows with
-// its rows, and every workgroup of a launch that fits the machine runs at once)
-int act_rows_per_workgroup(i64 n) {
-    int rpw = 1;
-    while (rpw < kRows && (n + rpw - 1) / rpw > 256) rpw *= 2;
-    return rpw;
-}
-
 int srlx_sacd_act(srlx_sacd_t *h, int64_t n_rows, const float *d_obs_base, const int64_t *d_row_offsets, uint64_t seed, const int64_t *d_counter,
                   int64_t random_until, int32_t *d_actions, float *d_logits, double *d_scores, void *stream) {
     SRLX_REQUIRE(h, "sacd_act: NULL handle");
@@ -674,7 +644,7 @@ int srlx_sacd_act(srlx_sacd_t *h, int64_t n_rows, const float *d_obs_base, const
         SRLX_HIP(hipMemcpy(h->d_nets, nets, sizeof(nets), hipMemcpyHostToDevice));
         h->nets_ok = true;
     }
-    const int rpw = act_rows_per_workgroup(n_rows);
+    const int rpw = srlxt::rows_per_workgroup(n_rows);
     ActArgs a{(i64)n_rows, d_obs_base, (const i64 *)d_row_offsets, (srlx::u64)seed, (const i64 *)d_counter, (i64)random_until, d_actions, d_logits, d_scores};
     hipLaunchKernelGGL(k_sacd_act, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const NetD *)h->d_nets, a, rpw,
                        h->D, h->A, act_lds_stride(h));

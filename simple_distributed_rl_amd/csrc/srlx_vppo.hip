@@ -19,9 +19,7 @@
 // LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
 // widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
-#include "srlx_adam_math.h"
-#include "srlx_common.h"
-#include "srlx_mlp_rows.h"
+#include "srlx_param_tail.h"
 #include "srlx_vppo_math.h"
 #include <cmath>
 
@@ -31,27 +29,18 @@ using i64 = int64_t;
 
 using srlxm::kRows;
 using srlxm::kThreads;
-using srlxm::kWTile;
 using srlxm::Layers;
+using srlxm::Src;
+using srlxm::SumSeed;
+using srlxt::kMaxTensors;  // 2 x (3 trunk + 2 value + value_out + 2 policy + 2 heads)
+using srlxt::Seg;
 using srlxv::kHeadCols;
 using srlxv::kNormalLs;
-constexpr int kMaxTensors = 20;  // 2 x (3 trunk + 2 value + value_out + 2 policy + 2 heads)
-constexpr int kPlanes = 7;       // trunk 0..2, value 3..4, policy 5..6
-constexpr size_t kLdsCap = sizeof(float) * ((size_t)3 * kRows * (512 + 1) + kWTile);
-// the most any handle asks of k_vppo_act (two row buffers of 512 floats + 1): the kernel's cap is set to this at every create, so that creating a narrower
-// handle never lowers it under a wider one that is still alive
-constexpr size_t kActLdsCap = sizeof(float) * ((size_t)2 * kRows * (512 + 1) + kWTile);
+constexpr int kPlanes = 7;  // trunk 0..2, value 3..4, policy 5..6
 
 struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
     Layers trunk, value, policy;
     const float *w_ls, *b_ls;
-};
-
-struct Seg {  // one parameter tensor
-    i64 end;          // running element count
-    int stride, in;   // row stride of dout; in = 0: a bias
-    const float *dout, *xin;  // [B][stride] d loss / d (layer output), [B][in] the layer's input rows (NULL: the caller's states)
-    float *p, *g, *graw, *m, *v;
 };
 
 }  // namespace
@@ -62,10 +51,7 @@ struct srlx_vppo {
     int wmax, nt;
     int wmax_act;  // max(D, trunk widths, policy widths): k_vppo_act's rows
     i64 max_batch, elements, grad_blocks;
-    float *p[kMaxTensors], *g[kMaxTensors], *graw[kMaxTensors], *m[kMaxTensors], *v[kMaxTensors];
-    double beta1, beta2, eps;
-    i64 steps;
-    bool bound, grads_bound, adam_bound, table_ok, net_ok;
+    srlxt::ParamSet ps;
     Net *d_net;  // (in device memory: a by-value kernel argument of this size was copied to scratch)
     Seg *d_segs;
     float *h, *dh;    // planes [kPlanes][max_batch][wmax]
@@ -79,9 +65,9 @@ namespace {
 
 int n_tensors(const srlx_vppo *h) { return 2 * (h->Lt + h->Lv + 1 + h->Lp + (h->head ? 2 : 1)); }
 int lds_stride(const srlx_vppo *h) { return h->wmax + 1; }
-size_t lds_bytes(const srlx_vppo *h) { return sizeof(float) * ((size_t)3 * kRows * lds_stride(h) + kWTile); }
+size_t lds_bytes(const srlx_vppo *h) { return srlxt::row_lds_bytes(3, h->wmax); }
 int act_lds_stride(const srlx_vppo *h) { return h->wmax_act + 1; }
-size_t act_lds_bytes(const srlx_vppo *h) { return sizeof(float) * ((size_t)2 * kRows * act_lds_stride(h) + kWTile); }
+size_t act_lds_bytes(const srlx_vppo *h) { return srlxt::row_lds_bytes(2, h->wmax_act); }
 
 struct Keep {  // planes of the hidden rows (NULL: not kept)
     float *ht, *hv, *hp;
@@ -108,34 +94,8 @@ __device__ __forceinline__ void forward_heads(const Net &n, const float *__restr
     for (int p = t; p < nb * Wtop; p += kThreads) b0[(p / Wtop) * S + p % Wtop] = b2[(p / Wtop) * S + p % Wtop];
     __syncthreads();
     const float *z = srlxm::forward_rows<double>(n.policy, n.policy.L + 1, nb, b0, b1, S, wl, kp.hp, kp.plane, i0, kp.hp ? nb : 0);
-    const float *hin = z == b0 ? b1 : b0;  // the head's input rows
-    const int HO = n.policy.Out;
-    if (t < nb * HO) zs[(t / HO) * kHeadCols + t % HO] = z[(t / HO) * S + t % HO];
-    if (n.w_ls) {
-        srlxm::dense<double>(n.w_ls, n.b_ls, n.policy.in_of(n.policy.L), HO, nb, hin, S, b2, S, false, wl);
-        __syncthreads();
-        if (t < nb * HO) zs[(t / HO) * kHeadCols + kNormalLs + t % HO] = b2[(t / HO) * S + t % HO];
-    }
-    __syncthreads();
+    srlxm::head_rows(n.policy, n.w_ls, n.b_ls, nb, z, z == b0 ? b1 : b0, b2, S, wl, zs);
 }
-
-// d loss / d h of a layer that up to three Linear layers read: sum over their output rows' seeds through their weights, one float64 chain
-struct Src {
-    const float *d;  // [rows][stride]
-    int stride, n;   // n = 0: none
-    const float *w;  // [n][W of the layer below]
-};
-struct SumSeed {
-    Src a, b, c;
-    __device__ float operator()(int r, int k, int Wl) const {
-        double acc = 0.0;
-#pragma unroll 4
-        for (int u = 0; u < a.n; u++) acc = srlxm::fma_acc((double)a.d[r * a.stride + u], (double)a.w[(i64)u * Wl + k], acc);
-        for (int u = 0; u < b.n; u++) acc = srlxm::fma_acc((double)b.d[r * b.stride + u], (double)b.w[(i64)u * Wl + k], acc);
-        for (int u = 0; u < c.n; u++) acc = srlxm::fma_acc((double)c.d[r * c.stride + u], (double)c.w[(i64)u * Wl + k], acc);
-        return (float)acc;
-    }
-};
 
 struct Batch {
     i64 B;
@@ -362,116 +322,42 @@ __global__ void __launch_bounds__(kThreads) k_vppo_act_normal(const Net *__restr
     }
 }
 
-struct GradArgs {
-    const Seg *segs;
-    int nseg;
+// The four loss sums of k_vppo_grad's last four threads: loss_value, loss_v_align, loss_policy, loss_e into out[0..3]
+struct LossSums {
+    static constexpr int n = 4;
     i64 B;
-    const float *xin0;  // the caller's states: the input rows of the first layer
-    const float *rows;
+    const float *rows;  // [4][max_batch]
     i64 max_batch;
     double inv_n, inv_b;
     int entropy;
-    double *partials;
-    float *out;  // loss_value, loss_v_align, loss_policy, loss_e, norm
+    float *out;
+    __device__ void operator()(int k) const {
+        double s = 0.0;
+        for (i64 b = 0; b < B; b++) s += (double)rows[k * max_batch + b];
+        out[k] = k == 0 || k == 1 ? (float)(s * inv_n) : (k == 2 ? (float)(-s * inv_n) : (entropy ? (float)(s * inv_b) : 0.f));
+    }
 };
 
-__global__ void __launch_bounds__(kThreads) k_vppo_grad(GradArgs a) {
-    __shared__ double sq[kThreads];
-    const int t = threadIdx.x;
-    const i64 i = (i64)blockIdx.x * kThreads + t;
-    const i64 last = (i64)gridDim.x * kThreads;
-    double mine = 0.0;
-    if (i >= last - 4) {
-        // (the last block's last four threads: the launch rounds the element count + 4 up, so they exist and own no element)
-        const int k = (int)(i - (last - 4));
-        double s = 0.0;
-        for (i64 b = 0; b < a.B; b++) s += (double)a.rows[k * a.max_batch + b];
-        a.out[k] = k == 0 || k == 1 ? (float)(s * a.inv_n) : (k == 2 ? (float)(-s * a.inv_n) : (a.entropy ? (float)(s * a.inv_b) : 0.f));
-    } else if (i < a.segs[a.nseg - 1].end) {
-        int s = 0;
-        while (i >= a.segs[s].end) s++;
-        const Seg sg = a.segs[s];
-        const i64 e = i - (s ? a.segs[s - 1].end : 0);
-        const int St = sg.stride, In = sg.in;
-        double acc = 0.0;
-        if (In) {
-            const int u = (int)(e / In), k = (int)(e % In);
-            const float *dout = sg.dout + u, *xin = (sg.xin ? sg.xin : a.xin0) + k;
-#pragma unroll 8
-            for (int b = 0; b < (int)a.B; b++) acc = fma((double)dout[(i64)b * St], (double)xin[(i64)b * In], acc);
-        } else {
-            const float *dout = sg.dout + e;
-#pragma unroll 8
-            for (int b = 0; b < (int)a.B; b++) acc += (double)dout[(i64)b * St];
-        }
-        const float g = (float)acc;
-        sg.graw[e] = g;
-        mine = (double)g * (double)g;
-    }
-    sq[t] = mine;
-    __syncthreads();
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if (t < w) sq[t] += sq[t + w];
-        __syncthreads();
-    }
-    if (t == 0) a.partials[blockIdx.x] = sq[0];
-}
-
-struct StepArgs {
+struct GradArgs {
     const Seg *segs;
     int nseg;
-    const double *partials;
-    i64 n_partials;
-    float max_norm;
-    double lr, beta1, beta2, eps;
-    i64 steps_taken;
-    float *out;
+    const float *xin0;  // the caller's states: the input rows of the first layer
+    double *partials;
+    LossSums sums;
 };
 
-__global__ void __launch_bounds__(kThreads) k_vppo_step(StepArgs a) {
-    __shared__ double sq[kThreads];
-    const int t = threadIdx.x;
-    double mine = 0.0;
-    for (i64 k = t; k < a.n_partials; k += kThreads) mine += a.partials[k];
-    sq[t] = mine;
-    __syncthreads();
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if (t < w) sq[t] += sq[t + w];
-        __syncthreads();
-    }
-    // clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)) in float32, and the gradients are always multiplied by it
-    const float norm = (float)sqrt(sq[0]);
-    const float coef = fminf(1.f, a.max_norm / (norm + 1e-6f));
-    const i64 i = (i64)blockIdx.x * kThreads + t;
-    if (i == 0) a.out[4] = norm;
-    if (i >= a.segs[a.nseg - 1].end) return;
-    int s = 0;
-    while (i >= a.segs[s].end) s++;
-    const Seg sg = a.segs[s];
-    const i64 e = i - (s ? a.segs[s - 1].end : 0);
-    const float g = sg.graw[e] * coef;
-    sg.g[e] = g;
-    const srlx::AdamCoef c = srlx::adam_coef(a.lr, a.beta1, a.beta2, a.eps, a.steps_taken);
-    float p = sg.p[e], m = sg.m[e], v = sg.v[e];
-    srlx::adam_one_foreach(p, g, m, v, c);
-    sg.p[e] = p, sg.m[e] = m, sg.v[e] = v;
-}
+__global__ void __launch_bounds__(kThreads) k_vppo_grad(GradArgs a) { srlxt::grad_body(a.segs, a.nseg, a.sums.B, a.xin0, a.partials, a.sums); }
 
-bool widths_ok(int n, int lo, int hi, const int *w) {
-    if (n < lo || n > hi || (n && !w)) return false;
-    for (int l = 0; l < n; l++)
-        if (w[l] < 32 || w[l] > 512 || w[l] % 32) return false;
-    return true;
-}
+__global__ void __launch_bounds__(kThreads) k_vppo_step(srlxt::StepArgs a) { srlxt::step_body(a); }
 
 int check_shape(const char *who, int D, int head, int A, int nt, const int *tw, int nv, const int *vw, int np, const int *pw, i64 max_batch) {
     SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
     SRLX_REQUIRE(head == 0 || head == 1, "%s: head kind %d (0 categorical, 1 Normal)", who, head);
     SRLX_REQUIRE(head == 1 || (A >= 2 && A <= 16), "%s: %d actions (2..16)", who, A);
     SRLX_REQUIRE(head == 0 || (A >= 1 && A <= 8), "%s: %d action elements (1..8)", who, A);
-    SRLX_REQUIRE(widths_ok(nt, 1, 3, tw), "%s: the trunk is 1..3 layers of 32..512 units in multiples of 32", who);
-    SRLX_REQUIRE(widths_ok(nv, 0, 2, vw), "%s: the value block is 0..2 layers of 32..512 units in multiples of 32", who);
-    SRLX_REQUIRE(widths_ok(np, 0, 2, pw), "%s: the policy block is 0..2 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(nt, 1, 3, tw), "%s: the trunk is 1..3 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(nv, 0, 2, vw), "%s: the value block is 0..2 layers of 32..512 units in multiples of 32", who);
+    SRLX_REQUIRE(srlxt::widths_ok(np, 0, 2, pw), "%s: the policy block is 0..2 layers of 32..512 units in multiples of 32", who);
     SRLX_REQUIRE(max_batch >= 1 && max_batch <= 256, "%s: max_batch %lld (1..256)", who, (long long)max_batch);
     return SRLX_OK;
 }
@@ -506,26 +392,15 @@ i64 elements_of(const srlx_vppo *h) {
     return e;
 }
 
-Layers chain(int In, int L, const int *W, int Out, float *const *p) {
-    Layers n;
-    n.In = In, n.L = L, n.Out = Out;
-    n.W0 = L > 0 ? W[0] : 0, n.W1 = L > 1 ? W[1] : 0, n.W2 = L > 2 ? W[2] : 0;
-    const float *w[4] = {nullptr, nullptr, nullptr, nullptr}, *b[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int l = 0; l <= L && l < 4; l++)
-        if (p[2 * l]) w[l] = p[2 * l], b[l] = p[2 * l + 1];
-    n.w0 = w[0], n.w1 = w[1], n.w2 = w[2], n.w3 = w[3], n.b0 = b[0], n.b1 = b[1], n.b2 = b[2], n.b3 = b[3];
-    return n;
-}
-
 Net net_of(const srlx_vppo *h) {
     Net n;
     float *tr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 2 * h->Lt; i++) tr[i] = h->p[i];  // (the trunk has no layer of its own behind its hidden ones: slot Lt stays NULL)
-    n.trunk = chain(h->D, h->Lt, h->Wt, 0, tr);
+    for (int i = 0; i < 2 * h->Lt; i++) tr[i] = h->ps.p[i];  // (the trunk has no layer of its own behind its hidden ones: slot Lt stays NULL)
+    n.trunk = srlxt::chain(h->D, h->Lt, h->Wt, 0, tr);
     const int top = h->Wt[h->Lt - 1];
-    n.value = chain(top, h->Lv, h->Wv, 1, h->p + 2 * h->Lt);
-    float *const *pp = h->p + 2 * (h->Lt + h->Lv + 1);
-    n.policy = chain(top, h->Lp, h->Wp, h->A, pp);
+    n.value = srlxt::chain(top, h->Lv, h->Wv, 1, h->ps.p + 2 * h->Lt);
+    float *const *pp = h->ps.p + 2 * (h->Lt + h->Lv + 1);
+    n.policy = srlxt::chain(top, h->Lp, h->Wp, h->A, pp);
     n.w_ls = h->head ? pp[2 * (h->Lp + 1)] : nullptr;
     n.b_ls = h->head ? pp[2 * (h->Lp + 1) + 1] : nullptr;
     return n;
@@ -534,7 +409,7 @@ Net net_of(const srlx_vppo *h) {
 int upload_net(srlx_vppo *h) {
     const Net n = net_of(h);
     SRLX_HIP(hipMemcpy(h->d_net, &n, sizeof(n), hipMemcpyHostToDevice));
-    h->net_ok = true;
+    h->ps.net_ok = true;
     return SRLX_OK;
 }
 
@@ -548,7 +423,6 @@ int upload_table(srlx_vppo *h) {
     const float *dht = h->dh, *dhv = h->dh + 3 * plane, *dhp = h->dh + 5 * plane;
     const float *top = ht + (i64)(h->Lt - 1) * plane;
     i64 end = 0;
-    int s = 0;
     for (int l = 0; l < nl; l++) {
         const float *dout, *xin;
         int stride = shape[l][0];
@@ -565,16 +439,10 @@ int upload_table(srlx_vppo *h) {
             k -= h->Lp;  // 0: logits or locs, 1: log-scales
             dout = h->dlast_p + (k ? kNormalLs : 0), stride = kHeadCols, xin = h->Lp ? hp + (i64)(h->Lp - 1) * plane : top;
         }
-        for (int j = 0; j < 2; j++, s++) {
-            Seg &g = segs[s];
-            end += j == 0 ? (i64)shape[l][0] * shape[l][1] : shape[l][0];
-            g.end = end, g.stride = stride, g.in = j == 0 ? shape[l][1] : 0;
-            g.dout = dout, g.xin = xin;
-            g.p = h->p[s], g.g = h->g[s], g.graw = h->graw[s], g.m = h->m[s], g.v = h->v[s];
-        }
+        srlxt::push_linear(segs + 2 * l, end, shape[l][0], shape[l][1], stride, dout, xin, h->ps, 2 * l);
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
-    h->table_ok = true;
+    h->ps.table_ok = true;
     return SRLX_OK;
 }
 
@@ -624,10 +492,10 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
     if (e == hipSuccess) e = hipMalloc((void **)&h->rows, sizeof(float) * 4 * max_batch);
     if (e == hipSuccess) e = hipMalloc((void **)&h->partials, sizeof(double) * h->grad_blocks);
     if (e == hipSuccess) e = hipMemset(h->dlast_p, 0, sizeof(float) * max_batch * kHeadCols);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act_normal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap2);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act_normal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap2);
     if (e != hipSuccess) {
         srlx_vppo_destroy(h);
         srlx::set_error("vppo_create: device set-up failed: %s", hipGetErrorString(e));
@@ -648,29 +516,17 @@ int srlx_vppo_destroy(srlx_vppo_t *h) {
 
 int srlx_vppo_bind(srlx_vppo_t *h, float *const *d_params) {
     SRLX_REQUIRE(h && d_params, "vppo_bind: NULL argument");
-    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_params[i], "vppo_bind: parameter %d is NULL", i);
-    for (int i = 0; i < h->nt; i++) h->p[i] = d_params[i];
-    h->bound = true, h->table_ok = h->net_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_params("vppo_bind", h->nt, d_params);
 }
 
 int srlx_vppo_bind_grads(srlx_vppo_t *h, float *const *d_grads, float *const *d_raw_grads) {
     SRLX_REQUIRE(h && d_grads && d_raw_grads, "vppo_bind_grads: NULL argument");
-    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_grads[i] && d_raw_grads[i], "vppo_bind_grads: gradient tensor %d is NULL", i);
-    for (int i = 0; i < h->nt; i++) h->g[i] = d_grads[i], h->graw[i] = d_raw_grads[i];
-    h->grads_bound = true, h->table_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_grads("vppo_bind_grads", h->nt, d_grads, d_raw_grads);
 }
 
 int srlx_vppo_bind_adam(srlx_vppo_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2, double eps) {
     SRLX_REQUIRE(h && d_exp_avg && d_exp_avg_sq, "vppo_bind_adam: NULL argument");
-    SRLX_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps > 0, "vppo_bind_adam: betas in [0, 1) and eps > 0");
-    SRLX_REQUIRE(steps_taken >= 0, "vppo_bind_adam: the step count is non-negative");
-    for (int i = 0; i < h->nt; i++) SRLX_REQUIRE(d_exp_avg[i] && d_exp_avg_sq[i], "vppo_bind_adam: state %d is NULL", i);
-    for (int i = 0; i < h->nt; i++) h->m[i] = d_exp_avg[i], h->v[i] = d_exp_avg_sq[i];
-    h->steps = steps_taken, h->beta1 = beta1, h->beta2 = beta2, h->eps = eps;
-    h->adam_bound = true, h->table_ok = false;
-    return SRLX_OK;
+    return h->ps.bind_adam("vppo_bind_adam", h->nt, d_exp_avg, d_exp_avg_sq, steps_taken, beta1, beta2, eps);
 }
 
 int64_t srlx_vppo_steps(const srlx_vppo_t *h) {
@@ -678,45 +534,37 @@ int64_t srlx_vppo_steps(const srlx_vppo_t *h) {
         srlx::set_error("vppo_steps: NULL handle");
         return -1;
     }
-    return h->steps;
+    return h->ps.steps;
 }
 
 int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
                       void *stream) {
     SRLX_REQUIRE(h && d_states, "vppo_forward: NULL handle or states");
-    SRLX_REQUIRE(h->bound, "vppo_forward: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(h->ps.bound, "vppo_forward: unbound handle (srlx_vppo_bind)");
     SRLX_REQUIRE(n >= 1 && n <= (int64_t)1 << 24, "vppo_forward: %lld rows (1..2^24)", (long long)n);
     SRLX_REQUIRE(d_v || d_head0, "vppo_forward: nothing to write");
     SRLX_REQUIRE(!d_head1 || (d_head0 && h->head == 1), "vppo_forward: log-scales go with locs, on a Normal head");
     SRLX_REQUIRE(!(h->head == 1 && d_head0 && !d_head1), "vppo_forward: a Normal head writes locs and log-scales");
     SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_forward: the log-scale clamp's ends are ordered");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
     hipLaunchKernelGGL(k_vppo_forward, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states, d_v,
                        d_head0, d_head1, (float)log_scale_lo, (float)log_scale_hi, h->D, lds_stride(h));
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
 
-// rows per workgroup of k_vppo_act: the smallest of 1, 2, 4, 8, 16 that keeps the launch within one workgroup for each of the MI355X's 256 compute units (a
-// workgroup's time grows with its rows, and every workgroup of a launch that fits the machine runs at once: DESIGN.md 7n)
-static int act_rows_per_workgroup(i64 n) {
-    int rpw = 1;
-    while (rpw < kRows && (n + rpw - 1) / rpw > 256) rpw *= 2;
-    return rpw;
-}
-
 int srlx_vppo_act(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uint64_t seed, const int64_t *d_counter, double epsilon, int32_t *d_actions, float *d_logp,
                   float *d_logits, double *d_cdf, void *stream) {
     SRLX_REQUIRE(h, "vppo_act: NULL handle");
-    SRLX_REQUIRE(h->bound, "vppo_act: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(h->ps.bound, "vppo_act: unbound handle (srlx_vppo_bind)");
     SRLX_REQUIRE(h->head == 0, "vppo_act: the acting kernel serves the categorical head");
     SRLX_REQUIRE(n_rows >= 1 && n_rows <= 65536, "vppo_act: %lld rows (1..65536)", (long long)n_rows);
     SRLX_REQUIRE(epsilon >= 0.0 && epsilon <= 1.0, "vppo_act: epsilon %g (0..1)", epsilon);
     SRLX_REQUIRE(d_obs && d_counter && d_actions && d_logp, "vppo_act: NULL observations, counter, actions or log-probabilities");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
-    const int rpw = act_rows_per_workgroup(n_rows);
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    const int rpw = srlxt::rows_per_workgroup(n_rows);
     ActArgs a{(i64)n_rows, d_obs, (srlx::u64)seed, (const i64 *)d_counter, epsilon, srlxv::act_uniform_logp(h->A), d_actions, d_logp, d_logits, d_cdf};
     hipLaunchKernelGGL(k_vppo_act, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, a, rpw, h->D, h->A,
                        act_lds_stride(h));
@@ -728,7 +576,7 @@ int srlx_vppo_act_normal(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uin
                          double log_scale_lo, double log_scale_hi, const float *d_low, const float *d_high, float *d_actions, float *d_logp, float *d_env_actions,
                          float *d_loc, float *d_log_scale, double *d_z, void *stream) {
     SRLX_REQUIRE(h, "vppo_act_normal: NULL handle");
-    SRLX_REQUIRE(h->bound, "vppo_act_normal: unbound handle (srlx_vppo_bind)");
+    SRLX_REQUIRE(h->ps.bound, "vppo_act_normal: unbound handle (srlx_vppo_bind)");
     SRLX_REQUIRE(h->head == 1, "vppo_act_normal: the acting kernel serves the Normal head (srlx_vppo_act serves the categorical one)");
     SRLX_REQUIRE(n_rows >= 1 && n_rows <= 65536, "vppo_act_normal: %lld rows (1..65536)", (long long)n_rows);
     SRLX_REQUIRE(epsilon >= 0.0 && epsilon <= 1.0, "vppo_act_normal: epsilon %g (0..1)", epsilon);
@@ -739,8 +587,8 @@ int srlx_vppo_act_normal(srlx_vppo_t *h, int64_t n_rows, const float *d_obs, uin
                  "vppo_act_normal: NULL observations, counter, bounds, actions, log-probabilities or environment actions");
     SRLX_REQUIRE((d_loc != nullptr) == (d_log_scale != nullptr), "vppo_act_normal: locs and log-scales are written together or not at all");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
-    const int rpw = act_rows_per_workgroup(n_rows);
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    const int rpw = srlxt::rows_per_workgroup(n_rows);
     ActNormalArgs a{(i64)n_rows, d_obs, ActNormalDraw{(srlx::u64)seed, (const i64 *)d_counter, epsilon, (float)noise_scale, (float)log(noise_scale), (float)log_scale_lo,
                                                       (float)log_scale_hi, squashed, d_low, d_high, d_actions, d_logp, d_env_actions, d_loc, d_log_scale, d_z}};
     hipLaunchKernelGGL(k_vppo_act_normal, dim3((unsigned)((n_rows + rpw - 1) / rpw)), dim3(kThreads), act_lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, a, rpw,
@@ -754,7 +602,7 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
                      double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
                      float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream) {
     SRLX_REQUIRE(h, "vppo_update: NULL handle");
-    SRLX_REQUIRE(h->bound && h->grads_bound && h->adam_bound, "vppo_update: bind the parameters, the gradient tensors and the Adam state first");
+    SRLX_REQUIRE(h->ps.ready(), "vppo_update: bind the parameters, the gradient tensors and the Adam state first");
     SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "vppo_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
     SRLX_REQUIRE(d_states && d_next_states && d_actions && d_old_logpi && d_rewards && d_not_terminated && d_total_rewards && d_v && d_n_v && d_new_logpi && d_scalars,
                  "vppo_update: NULL argument");
@@ -762,8 +610,8 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
     SRLX_REQUIRE(squashed == 0 || squashed == 1, "vppo_update: squashed is 0 or 1");
     SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_update: the log-scale clamp's ends are ordered");
     srlx::DeviceGuard g(h->device);
-    if (!h->net_ok) SRLX_TRY(upload_net(h));
-    if (!h->table_ok) SRLX_TRY(upload_table(h));
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
     hipStream_t st = (hipStream_t)stream;
     const int K = h->head ? h->A : 1;
     const double N = (double)batch * K;
@@ -773,12 +621,12 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
             h->head ? (const float *)d_actions : nullptr, d_v, d_n_v, d_new_logpi};
     Work w{h->h, h->dh, h->dlast_v, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
     hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
-    GradArgs ga{h->d_segs, h->nt, (i64)batch, d_states, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, h->partials, d_scalars};
+    GradArgs ga{h->d_segs, h->nt, d_states, h->partials, LossSums{(i64)batch, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, d_scalars}};
     hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
-    StepArgs sa{h->d_segs, h->nt, h->partials, h->grad_blocks, (float)max_grad_norm, lr, h->beta1, h->beta2, h->eps, h->steps, d_scalars};
+    const srlxt::StepArgs sa = h->ps.step_args(h->d_segs, h->nt, h->partials, h->grad_blocks, max_grad_norm, lr, d_scalars + 4);
     hipLaunchKernelGGL(k_vppo_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
     SRLX_HIP(hipGetLastError());
-    h->steps++;
+    h->ps.steps++;
     return SRLX_OK;
 }
 

@@ -12,14 +12,15 @@
 #pragma once
 #include <cmath>
 
+#include "srlx_mlp_rows.h"
 #include "srlx_ppo_math.h"
 
 namespace srlxv {
 
 using srlxp::clampf;
 
-constexpr int kHeadCols = 16;        // columns of a head row in LDS and in the seed table: A logits, or k locs at 0.. and k log-scales at kNormalLs..
-constexpr int kNormalLs = 8;
+using srlxm::kHeadCols;  // columns of a head row in LDS and in the seed table: A logits, or k locs at 0.. and k log-scales at kNormalLs..
+using srlxm::kNormalLs;
 constexpr float kProbFloor = 1e-7f;  // categorical_dist_block.py:53-54 (written 10e-8)
 constexpr double kSquashFloor = 1e-10;  // normal_dist_block.py:20-29
 

@@ -3,16 +3,13 @@ networks stay what the plugin, checkpoints and `load_state_dict` see -- and owns
 network's norm clip) and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:150-189 for one batch and one
 noise tensor, in six launches."""
 import ctypes
-import math
 
 import torch
 
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd._native import _int_array, _linear_widths, _ptrs
-
-MAX_BATCH = 256
-# block options the kernels' layers cover; anything else set on a block keeps the update on torch
-_MLP_FREE_KWARGS = {"layer_sizes", "activation", "kernel_initializer", "bias_initializer"}
+from simple_distributed_rl_amd.device import _row_update as R
+from simple_distributed_rl_amd.device._row_update import MAX_BATCH
 
 
 def shape_of(parameter):
@@ -32,98 +29,53 @@ def shape_of(parameter):
         return "the policy_block or the q_block has no layer"
     act = qnet.act_block[0]
     D = [m for m in policy.policy_block.hidden_layers if isinstance(m, torch.nn.Linear)][0].in_features
-    dist = policy.policy_dist_block
-    if hasattr(dist, "loc_layers"):
-        if len(dist.h_layers) or len(dist.loc_layers) != 1 or len(dist.log_scale_layers) != 1:
-            return "the Normal head has hidden layers of its own"
-        head, n_out = 1, dist.loc_layers[0].out_features
-    else:
-        if len(dist.h_layers) != 1:
-            return "the Gumbel head has hidden layers of its own"
-        head, n_out = 0, dist.h_layers[0].out_features
-    return D, head, n_out, pw, qw, act.out_features
+    head = R.head_of(policy.policy_dist_block, "Gumbel")
+    if isinstance(head, str):
+        return head
+    return D, head[0], head[1], pw, qw, act.out_features
 
 
 def log_scale_range(parameter):
     """The Normal head's clamp as the kernels take it: (lo, hi), infinite when there is none."""
-    dist = parameter.policy.policy_dist_block
-    if getattr(dist, "enable_stable_gradients", False):
-        return float(dist.stable_gradients_scale_range[0]), float(dist.stable_gradients_scale_range[1])
-    return -math.inf, math.inf
+    return R.log_scale_range(parameter.policy.policy_dist_block)
 
 
-class NotSacUpdate:
+class NotSacUpdate(R.RowUpdate):
+    ABI = "notsac"
+    shape_of = staticmethod(shape_of)
+
+    @staticmethod
+    def tensors_of(parameter) -> list:
+        """The policy's tensors, then the Q-network's: the order of srlx_notsac_bind."""
+        return list(parameter.policy.parameters()) + list(parameter.qnet.parameters())
+
     def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
-        reason = self.why_not(parameter, max_batch)
-        if reason:
-            raise ValueError(f"NotSacUpdate: {reason}")
-        self.parameter = parameter
-        self.D, self.head, self.n_out, self.policy_widths, self.q_widths, self.act_emb = shape_of(parameter)
-        self.max_batch = max_batch
-        self.policy_params, self.q_params = list(parameter.policy.parameters()), list(parameter.qnet.parameters())
-        self.params = self.policy_params + self.q_params  # the order of srlx_notsac_bind
-        self.device = self.params[0].device
-        self.betas, self.eps = betas, eps
+        self.D, self.head, self.n_out, self.policy_widths, self.q_widths, self.act_emb = self._open(parameter, max_batch, betas, eps)
+        n_policy = len(list(parameter.policy.parameters()))
+        self.policy_params, self.q_params = self.params[:n_policy], self.params[n_policy:]
         self.ls_lo, self.ls_hi = log_scale_range(parameter)
-        self._lib = N.lib()
-        self._h = N.c_p()
         N.check(self._lib.srlx_notsac_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(self.policy_widths), _int_array(self.policy_widths),
                                              len(self.q_widths), _int_array(self.q_widths), self.act_emb, max_batch, self.device.index or 0))
-        self.grads = [torch.zeros_like(p) for p in self.params]      # after the norm clips: what Adam reads
-        self.raw_grads = [torch.zeros_like(p) for p in self.params]  # before them
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        self._alloc()
         n = len(self.params)
         N.check(self._lib.srlx_notsac_bind(self._h, n, _ptrs(self.params)))
         N.check(self._lib.srlx_notsac_bind_grads(self._h, n, _ptrs(self.grads), _ptrs(self.raw_grads)))
         N.check(self._lib.srlx_notsac_bind_adam(self._h, n, _ptrs(self.exp_avg), _ptrs(self.exp_avg_sq), 0, betas[0], betas[1], eps))
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.srlx_notsac_destroy(self._h)
-            self._h = None
-
     def split(self, tensors):
         """(the policy's, the Q-network's) of a list in bind order."""
         return tensors[:len(self.policy_params)], tensors[len(self.policy_params):]
 
-    # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def why_not(parameter, batch: int = 1, config=None) -> str:
-        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
-        tensors = list(parameter.policy.parameters()) + list(parameter.qnet.parameters())
-        if not all(t.is_cuda for t in tensors):
-            return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)
-        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
-            return "a parameter is not a dense float32 tensor"
-        if config is not None:
-            reasons = NotSacUpdate.config_reasons(config)
-            if reasons:
-                return reasons[0]
-        shape = shape_of(parameter)
-        if isinstance(shape, str):
-            return shape
-        return NotSacUpdate.envelope_reason(*shape, batch)
-
+    # ---- what it serves (`why_not` and `serves`: RowUpdate) ------------------------------------------------------------------------------------------------
     @staticmethod
     def config_reasons(config) -> list:
         """What `why_not` refuses on the config alone, every sentence (no Parameter, no device)."""
-        why = []
-        for name in ("policy_block", "q_block"):
-            extra = set(getattr(config, name).kwargs) - _MLP_FREE_KWARGS
-            if extra:
-                why.append(f"the {name} sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)")
-        extra = set(config.input_block.value.kwargs) - _MLP_FREE_KWARGS
-        if extra:
-            why.append(f"the input_block sets {sorted(extra)} (the kernels start at the observation)")
+        why = R.block_kwarg_reasons(config, ("policy_block", "q_block"), "the kernels start at the observation")
         if tuple(config.input_block.value.kwargs.get("layer_sizes", ())) != ():
             why.append("the input_block has layers of its own (the Q-network concatenates behind it: the kernels concatenate behind the observation)")
         if not config.target_policy_temperature > 0:
             why.append(f"target_policy_temperature {config.target_policy_temperature} is not positive (the kernel's argmax assumes a temperature that keeps the order)")
-        sch = config.lr_scheduler
-        if sch.schedule_type not in ("", "step", "exp", "cosine", "piecewise"):
-            why.append(f"the lr schedule {sch.schedule_type!r} is not one the host evaluates per step")
-        return why
+        return why + R.lr_schedule_reason(config)
 
     @staticmethod
     def envelope_reason(D, head, n_out, pw, qw, act_emb, batch: int = 1) -> str:
@@ -136,15 +88,7 @@ class NotSacUpdate:
                     f"q {tuple(qw)}, act_emb_units {act_emb}")
         return ""
 
-    @classmethod
-    def serves(cls, parameter, batch: int = 1, config=None) -> bool:
-        return cls.why_not(parameter, batch, config) == ""
-
-    # ---- the calls --------------------------------------------------------------------------------------------------------------------------------------
-    def steps(self) -> int:
-        """Optimiser steps taken (by each of the two optimisers)."""
-        return int(self._lib.srlx_notsac_steps(self._h))
-
+    # ---- the calls (`steps`: RowUpdate) --------------------------------------------------------------------------------------------------------------------
     def set_rows_per_workgroup(self, rows: int = 0) -> None:
         """The row kernels' launch shape: 1, 2, 4, 8 or 16 rows per workgroup, 0 for the default (one row per workgroup for every update).  Never changes a bit."""
         N.check(self._lib.srlx_notsac_set_rows_per_workgroup(self._h, int(rows)))

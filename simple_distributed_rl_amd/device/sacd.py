@@ -7,8 +7,8 @@ import torch
 
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd._native import _int_array, _linear_widths, _ptrs
+from simple_distributed_rl_amd.device._row_update import MAX_BATCH, LibUpdate, tensor_reason
 
-MAX_BATCH = 256
 TRAINED = ("policy", "q1_online", "q2_online")
 NETWORKS = ("policy", "q1_online", "q1_target", "q2_online", "q2_target")
 
@@ -28,7 +28,9 @@ def shape_of(parameter):
     return D, A, pw, qw
 
 
-class SacdUpdate:
+class SacdUpdate(LibUpdate):
+    ABI = "sacd"
+
     def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
         reason = self.why_not(parameter, max_batch)
         if reason:
@@ -53,11 +55,6 @@ class SacdUpdate:
         N.check(self._lib.srlx_sacd_bind_grads(self._h, _ptrs([g for name in TRAINED for g in self.grads[name]]), N.tptr(self.grad_log_alpha)))
         self._bind_adam([0, 0, 0, 0])
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.srlx_sacd_destroy(self._h)
-            self._h = None
-
     def _bind_adam(self, steps):
         m = [t for name in TRAINED for t in self.exp_avg[name]] + [self.alpha_exp_avg]
         v = [t for name in TRAINED for t in self.exp_avg_sq[name]] + [self.alpha_exp_avg_sq]
@@ -69,10 +66,9 @@ class SacdUpdate:
         """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not.  (`config`: as `VppoUpdate.why_not` takes it; nothing
         a sac.Config sets keeps the update off libsrlx.)"""
         tensors = [parameter.log_alpha] + [p for name in NETWORKS for p in getattr(parameter, name).parameters()]
-        if not all(t.is_cuda for t in tensors):
-            return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)
-        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
-            return "a parameter is not a dense float32 tensor"
+        reason = tensor_reason(tensors)
+        if reason:
+            return reason
         shape = shape_of(parameter)
         if isinstance(shape, str):
             return shape
@@ -86,10 +82,6 @@ class SacdUpdate:
         if N.lib().srlx_sacd_scratch_floats(D, A, len(pw), _int_array(pw), len(qw), _int_array(qw), max(1, batch)) < 0:
             return f"outside the envelope (D 1..256, A 2..16, 1..3 layers of 32..512 units in multiples of 32): D {D}, A {A}, policy {tuple(pw)}, q {tuple(qw)}"
         return ""
-
-    @classmethod
-    def serves(cls, parameter, batch: int = 1) -> bool:
-        return cls.why_not(parameter, batch) == ""
 
     # ---- the calls --------------------------------------------------------------------------------------------------------------------------------------
     def steps(self):

@@ -2,16 +2,13 @@
 stays what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after the norm clip)
 and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches."""
 import ctypes
-import math
 
 import torch
 
 from simple_distributed_rl_amd import _native as N
 from simple_distributed_rl_amd._native import _int_array, _linear_widths, _ptrs
-
-MAX_BATCH = 256
-# block options the kernels' layers cover; anything else set on a block keeps the update on torch
-_MLP_FREE_KWARGS = {"layer_sizes", "activation", "kernel_initializer", "bias_initializer"}
+from simple_distributed_rl_amd.device import _row_update as R
+from simple_distributed_rl_amd.device._row_update import MAX_BATCH
 
 
 def shape_of(parameter):
@@ -29,90 +26,43 @@ def shape_of(parameter):
     if not first:
         return "the trunk (input_block + hidden_block) has no layer"
     D = first[0].in_features
-    dist = net.policy_dist_block
-    if hasattr(dist, "loc_layers"):
-        if len(dist.h_layers) or len(dist.loc_layers) != 1 or len(dist.log_scale_layers) != 1:
-            return "the Normal head has hidden layers of its own"
-        head, n_out = 1, dist.loc_layers[0].out_features
-    else:
-        if len(dist.h_layers) != 1:
-            return "the categorical head has hidden layers of its own"
-        head, n_out = 0, dist.h_layers[0].out_features
-    return D, head, n_out, widths[0] + widths[1], widths[2], widths[3]
+    head = R.head_of(net.policy_dist_block, "categorical")
+    if isinstance(head, str):
+        return head
+    return D, head[0], head[1], widths[0] + widths[1], widths[2], widths[3]
 
 
 def log_scale_range(parameter):
     """The Normal head's clamp as the kernels take it: (lo, hi), infinite when there is none."""
-    dist = parameter.net.policy_dist_block
-    if getattr(dist, "enable_stable_gradients", False):
-        return float(dist.stable_gradients_scale_range[0]), float(dist.stable_gradients_scale_range[1])
-    return -math.inf, math.inf
+    return R.log_scale_range(parameter.net.policy_dist_block)
 
 
-class VppoUpdate:
+class VppoUpdate(R.RowUpdate):
+    ABI = "vppo"
+    shape_of = staticmethod(shape_of)
+
+    @staticmethod
+    def tensors_of(parameter) -> list:
+        return list(parameter.net.parameters())
+
     def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
-        reason = self.why_not(parameter, max_batch)
-        if reason:
-            raise ValueError(f"VppoUpdate: {reason}")
-        self.parameter = parameter
-        self.D, self.head, self.n_out, self.trunk_widths, self.value_widths, self.policy_widths = shape_of(parameter)
+        self.D, self.head, self.n_out, self.trunk_widths, self.value_widths, self.policy_widths = self._open(parameter, max_batch, betas, eps)
         self.K = self.n_out if self.head else 1
-        self.max_batch = max_batch
-        self.params = list(parameter.net.parameters())
-        self.device = self.params[0].device
-        self.betas, self.eps = betas, eps
         self.ls_lo, self.ls_hi = log_scale_range(parameter)
-        self._lib = N.lib()
-        self._h = N.c_p()
         N.check(self._lib.srlx_vppo_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(self.trunk_widths), _int_array(self.trunk_widths),
                                            len(self.value_widths), _int_array(self.value_widths), len(self.policy_widths), _int_array(self.policy_widths),
                                            max_batch, self.device.index or 0))
-        self.grads = [torch.zeros_like(p) for p in self.params]      # after the norm clip: what Adam reads
-        self.raw_grads = [torch.zeros_like(p) for p in self.params]  # before it
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        self._alloc()
         N.check(self._lib.srlx_vppo_bind(self._h, _ptrs(self.params)))
         N.check(self._lib.srlx_vppo_bind_grads(self._h, _ptrs(self.grads), _ptrs(self.raw_grads)))
         N.check(self._lib.srlx_vppo_bind_adam(self._h, _ptrs(self.exp_avg), _ptrs(self.exp_avg_sq), 0, betas[0], betas[1], eps))
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.srlx_vppo_destroy(self._h)
-            self._h = None
-
-    # ---- what it serves ---------------------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def why_not(parameter, batch: int = 1, config=None) -> str:
-        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
-        tensors = list(parameter.net.parameters())
-        if not all(t.is_cuda for t in tensors):
-            return "the parameters are CPU tensors"  # (answered before libsrlx is loaded)
-        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
-            return "a parameter is not a dense float32 tensor"
-        if config is not None:
-            reasons = VppoUpdate.config_reasons(config)
-            if reasons:
-                return reasons[0]
-        shape = shape_of(parameter)
-        if isinstance(shape, str):
-            return shape
-        return VppoUpdate.envelope_reason(*shape, batch)
-
+    # ---- what it serves (`why_not` and `serves`: RowUpdate) ------------------------------------------------------------------------------------------------
     @staticmethod
     def config_reasons(config) -> list:
         """What `why_not` refuses on the config alone, every sentence (no Parameter, no device)."""
-        why = []
-        for name in ("hidden_block", "value_block", "policy_block"):
-            extra = set(getattr(config, name).kwargs) - _MLP_FREE_KWARGS
-            if extra:
-                why.append(f"the {name} sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)")
-        extra = set(config.input_block.value.kwargs) - _MLP_FREE_KWARGS
-        if extra:
-            why.append(f"the input_block sets {sorted(extra)} (the kernels' layers are Linear with bias + ReLU)")
-        sch = config.lr_scheduler
-        if sch.schedule_type not in ("", "step", "exp", "cosine", "piecewise"):
-            why.append(f"the lr schedule {sch.schedule_type!r} is not one the host evaluates per step")
-        return why
+        blocks = R.block_kwarg_reasons(config, ("hidden_block", "value_block", "policy_block"), "the kernels' layers are Linear with bias + ReLU")
+        return blocks + R.lr_schedule_reason(config)
 
     @staticmethod
     def envelope_reason(D, head, n_out, tw, vw, pw, batch: int = 1) -> str:
@@ -124,15 +74,7 @@ class VppoUpdate:
                     f"1..8 action elements): D {D}, {'Normal' if head else 'categorical'} {n_out}, trunk {tuple(tw)}, value {tuple(vw)}, policy {tuple(pw)}")
         return ""
 
-    @classmethod
-    def serves(cls, parameter, batch: int = 1, config=None) -> bool:
-        return cls.why_not(parameter, batch, config) == ""
-
-    # ---- the calls --------------------------------------------------------------------------------------------------------------------------------------
-    def steps(self) -> int:
-        """Optimiser steps taken."""
-        return int(self._lib.srlx_vppo_steps(self._h))
-
+    # ---- the calls (`steps`: RowUpdate) --------------------------------------------------------------------------------------------------------------------
     def update(self, state, next_state, action, old_logpi, reward, not_terminated, total_reward, lr, discount, clip_range, entropy_weight, loss_align_coeff,
                max_grad_norm, squashed: bool) -> dict:
         """state / next_state f32 [B][D]; action i32 [B] (categorical) or f32 [B][K] (Normal); old_logpi f32 [B][K]; reward, not_terminated, total_reward f32 [B];

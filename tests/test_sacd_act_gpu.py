@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 # (D, A, policy widths): every D of {1, 4, 255, 256}, every A of {2, 3, 16}, every block of {(32,), (64, 64, 64), (512, 32)}
 CASES = [(1, 2, (32,)), (4, 3, (64, 64, 64)), (255, 16, (512, 32)), (256, 2, (512, 32)), (4, 16, (32,)), (256, 3, (64, 64, 64))]
 ROWS = (1, 15, 16, 17, 33)
-# beside the issue's rows: the launch cuts a workgroup's rows to 1, 2, 4, 8, 16 by the row count (srlx_sacd.hip: act_rows_per_workgroup); 300, 1000, 1030 and
+# beside the issue's rows: the launch cuts a workgroup's rows to 1, 2, 4, 8, 16 by the row count (srlx_param_tail.h: rows_per_workgroup); 300, 1000, 1030 and
 # 2049 rows reach 2, 4, 8 and 16 rows per workgroup, three of them with a partly filled last workgroup
 MANY_ROWS = (300, 1000, 1030, 2049)
 SEED, RANDOM_UNTIL = 0x5AC0FFEE, 5

@@ -1,12 +1,15 @@
-"""The bits of everything the row-blocked MLP passes (csrc/srlx_mlp_rows.h) produce, for comparing two BUILDS of libsrlx on one box:
+"""The bits of everything the row-blocked MLP passes (csrc/srlx_mlp_rows.h) and the update tail behind them (csrc/srlx_param_tail.h) produce, for comparing two
+BUILDS of libsrlx on one box:
 
-    SRLX_LIB=/path/to/another/libsrlx.so python tools/mlp_rows_bits.py --out a.json
-    python tools/mlp_rows_bits.py --out b.json          # the in-tree build; the two files must be equal
+    SRLX_LIB=/path/to/another/libsrlx.so python tools/mlp_rows_bits.py --out a.json     # one process per build: the library is chosen at import
+    python tools/mlp_rows_bits.py --out b.json                                          # the in-tree build
+    python tools/mlp_rows_bits.py --compare a.json b.json --out profiles/NAME.json      # both outputs, one digest per case, and the keys that differ; exit status 1 if any does
 
-Every case drives libsrlx's entry points (through the zero-copy handles of device/mlpq.py and device/sacd.py) on seeded inputs and records the SHA-256 of every
-output array and, after an update, of every parameter, gradient and Adam tensor.  The library is built with -ffp-contract=off and every product-sum is an explicit
-fma in a fixed order, so a change that only moves code must leave every digest as it was.  The shapes are the smallest at which the shared code takes each of
-its paths (one tile / many tiles with a partial last one; 1, 8 and 128 row groups; idle threads; chains of 0, 1 and 2 steps; a full and a one-item workgroup)."""
+Every case drives libsrlx's entry points (through the zero-copy handles of device/mlpq.py, sacd.py, vppo.py and notsac.py) on seeded inputs and records the
+SHA-256 of every output array and, after an update, of every parameter, gradient and Adam tensor (V-PPO and NoT_SAC: one digest over each list of tensors, in
+bind order).  The library is built with -ffp-contract=off and every product-sum is an explicit fma in a fixed order, so a change that only moves code must leave
+every digest as it was.  The shapes are the smallest at which the shared code takes each of its paths (one tile / many tiles with a partial last one; 1, 8 and
+128 row groups; idle threads; chains of 0, 1 and 2 steps; a full and a one-item workgroup; B 16 / 17, both heads, a clip that bites and one that does not)."""
 import argparse
 import hashlib
 import json
@@ -24,6 +27,13 @@ DISCOUNT, RETRACE_H, LR = 0.99, 0.9, 1e-3
 
 def digest(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def digest_all(tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
 
 
 def record(out, case, **tensors):
@@ -148,10 +158,103 @@ def sacd(out, i):
                **{"exp_avg_" + n: u.exp_avg[n] for n in TRAINED}, **{"exp_avg_sq_" + n: u.exp_avg_sq[n] for n in TRAINED})
 
 
+def record_update(out, case, res, u):
+    """What an update returned, and one digest over each of the handle's tensor lists."""
+    record(out, case, **res)
+    for kind in ("raw_grads", "grads", "params", "exp_avg", "exp_avg_sq"):
+        out[f"{case}/{kind}"] = digest_all(getattr(u, kind))
+
+
+def vppo(out, name):
+    """A case of tests/vppo_cases.py: two srlx_vppo_update, srlx_vppo_forward of the last batch, then srlx_vppo_act or srlx_vppo_act_normal of 17 rows."""
+    import vppo_cases as C
+    from simple_distributed_rl_amd.device.vppo import VppoUpdate
+
+    B, D, head = C.CASES[name][:3]
+    case = "vppo/" + name
+    p = C.make_parameter(name, "cuda")
+    cfg = p.config
+    u = VppoUpdate(p, max_batch=B)
+    f = lambda x: x.float().cuda()  # noqa: E731
+    for k, b in enumerate(C.make_batches(name)):
+        res = u.update(f(b["state"]), f(b["n_state"]), f(b["action"]) if head else b["action"].int().cuda(), f(b["old_logpi"]), f(b["reward"]),
+                       f(b["not_terminated"]), f(b["total_reward"]), cfg.lr, cfg.discount, cfg.clip_range, cfg.entropy_weight, cfg.loss_align_coeff,
+                       cfg.max_grad_norm, cfg.squashed_gaussian_policy)
+        torch.cuda.synchronize()
+        record_update(out, f"{case}/update{k}", res, u)
+    v, heads = u.forward(f(b["state"]))
+    torch.cuda.synchronize()
+    record(out, case + "/forward", v=v, head=heads)
+    n, K = 17, u.n_out
+    x = torch.randn(n, D, generator=torch.Generator().manual_seed(17)).cuda()
+    counter = torch.full((1,), 5, dtype=torch.int64, device="cuda")
+    z32 = lambda *shape: torch.zeros(shape, device="cuda")  # noqa: E731
+    if head:
+        low, high = torch.full((K,), -2.0, device="cuda"), torch.full((K,), 2.0, device="cuda")
+        got = dict(actions=z32(n, K), logp=z32(n, K), env_actions=z32(n, K), loc=z32(n, K), log_scale=z32(n, K), z=torch.zeros(n, K, dtype=torch.float64, device="cuda"))
+        u.act_normal(n, x, 0x5EED, counter, 0.25, 0.5, cfg.squashed_gaussian_policy, low, high, **got)
+    else:
+        got = dict(actions=torch.zeros(n, dtype=torch.int32, device="cuda"), logp=z32(n), logits=z32(n, K), cdf=torch.zeros(n, K, dtype=torch.float64, device="cuda"))
+        u.act(n, x, 0x5EED, counter, 0.25, **got)
+    torch.cuda.synchronize()
+    record(out, case + "/act", **got)
+
+
+def notsac(out, name):
+    """A case of tests/notsac_cases.py: two srlx_notsac_update on a fresh Parameter at the default launch shape and at 16 rows per workgroup, then
+    srlx_notsac_forward of the last batch with and without actions."""
+    import notsac_cases as C
+    from simple_distributed_rl_amd.device.notsac import NotSacUpdate
+
+    B, _, head = C.CASES[name][:3]
+    case = "notsac/" + name
+    f = lambda x: x.float().cuda()  # noqa: E731
+    for rpw in (0, 16):
+        p = C.make_parameter(name, "cuda")
+        cfg = p.config
+        u = NotSacUpdate(p, max_batch=B)
+        u.set_rows_per_workgroup(rpw)
+        for k, b in enumerate(C.make_batches(name)):
+            res = u.update(f(b["state"]), f(b["n_state"]), f(b["action"]) if head else b["action"].argmax(1).int().cuda(), f(b["reward"]), f(b["not_terminated"]),
+                           f(b["total_reward"]), b["noise"].cuda(), cfg.lr, cfg.discount, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy)
+            torch.cuda.synchronize()
+            record_update(out, f"{case}/rpw{rpw}/update{k}", res, u)
+    actions = f(b["action"])  # the Normal head's stored action, or the stored one-hot
+    for tag, a in (("with_actions", actions), ("heads_only", None)):
+        heads, q = u.forward(f(b["state"]), a)
+        torch.cuda.synchronize()
+        record(out, f"{case}/forward/{tag}", head=heads, **({} if q is None else {"q": q}))
+
+
+def by_case(digests):
+    """One SHA-256 per case (the first two parts of a key) over its keys and digests in key order: a whole output in a few dozen lines."""
+    cases = {}
+    for k in sorted(digests):
+        cases.setdefault("/".join(k.split("/")[:2]), hashlib.sha256()).update(f"{k}={digests[k]}\n".encode())
+    return {c: h.hexdigest() for c, h in cases.items()}
+
+
+def compare(a_path, b_path, out_path):
+    """Compares two outputs key by key and records both, folded to one digest per case, with the keys that differ; returns how many differ."""
+    with open(a_path) as fa, open(b_path) as fb:
+        a, b = json.load(fa), json.load(fb)
+    differing = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+    result = dict(what="tools/mlp_rows_bits.py on two builds of libsrlx on one box: SHA-256 of every recorded array compared key by key; a_cases / b_cases hold one "
+                       "SHA-256 per case over that build's keys and digests",
+                  a=os.path.basename(a_path), b=os.path.basename(b_path), digests=len(set(a) | set(b)), differing=differing, a_cases=by_case(a), b_cases=by_case(b))
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+    print(f"{result['digests']} digests, {len(differing)} differ; wrote {out_path}")
+    return len(differing)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
+    ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
     args = ap.parse_args()
+    if args.compare:
+        sys.exit(1 if compare(args.compare[0], args.compare[1], args.out) else 0)
     assert torch.cuda.is_available(), "the tool needs a GPU"
     out = {}
     plain = [dict(obs_dim=1, in_sizes=(), hidden_sizes=(32,), n_actions=2), dict(obs_dim=256, in_sizes=(), hidden_sizes=(512, 32, 512), n_actions=32)]
@@ -169,6 +272,13 @@ def main():
     mlpq_categorical(out, "mlpq/c51_256", 4, (64,), 2, 256, 9, 71)
     for i in (0, 3, 4):
         sacd(out, i)
+    import notsac_cases
+    import vppo_cases
+
+    for name in vppo_cases.NAMES:
+        vppo(out, name)
+    for name in notsac_cases.NAMES:
+        notsac(out, name)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
