@@ -1451,6 +1451,15 @@ int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const
  *                                9. one Adam step at lr on d_grads
  *                              Outputs: v, n_v f32 [B]; new_logpi f32 [B][K]; scalars f32 [5] = loss_value, loss_v_align, loss_policy, loss_e, norm.
  *                              No atomics, every sum in a fixed order: equal inputs give equal bits.
+ *   srlx_vppo_update_gemm    : srlx_vppo_update's contract -- arguments, preconditions, steps 1 to 9, outputs; srlx_last_error() names vppo_update_gemm -- on
+ *                              gfx950's float64 matrix cores (srlx_mlp_gemm.h): every Linear over the whole batch as one tiled GEMM, layers of
+ *                              equal depth in one launch (forward: trunk on s and s', both branches side by side, the heads; one pointwise launch for steps
+ *                              1 to 6 of every row; the data gradients back down), then srlx_vppo_update's own gradient and Adam launches.  Products of
+ *                              float32 values are exact in float64, every sum accumulates in float64 and is rounded to float32 once, as in srlx_vppo_update;
+ *                              the matrix core's order inside a group of 4 terms is its own, so a value may differ from srlx_vppo_update's in its last bit.
+ *                              The same handle, planes, gradient tensors, Adam state and step count: one handle may alternate the two calls.  The first
+ *                              call of a handle allocates 2 max_batch (widest row) + 18 max_batch floats and the job table (srlx_vppo_scratch_floats does
+ *                              not count them).  No host synchronisation, no atomics: equal inputs give equal bits.
  *   srlx_vppo_forward        : n rows of states -> v f32 [n] (NULL: not wanted) and the head's outputs (NULL: not wanted): d_head0 f32 [n][n_out] logits
  *                              or locs, d_head1 f32 [n][n_out] the log-scales clamped to [log_scale_lo, log_scale_hi] (Normal only, and then required with
  *                              d_head0).  The same chains as the update's: v bit for bit what srlx_vppo_update writes for the same rows.  Needs
@@ -1469,6 +1478,10 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
                      const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
                      double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
                      float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream);
+int srlx_vppo_update_gemm(srlx_vppo_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
+                          const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
+                          double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
+                          float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream);
 int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
                       void *stream);
 

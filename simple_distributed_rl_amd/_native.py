@@ -285,6 +285,7 @@ SIGNATURES = {
     "srlx_vppo_bind_adam": (c_int, [c_p, c_p, c_p, c_i64, c_f64, c_f64, c_f64]),
     "srlx_vppo_steps": (c_i64, [c_p]),
     "srlx_vppo_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 6 + [c_int, c_f64, c_f64] + [c_p] * 5),
+    "srlx_vppo_update_gemm": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 6 + [c_int, c_f64, c_f64] + [c_p] * 5),
     "srlx_vppo_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p]),
     "srlx_vppo_act": (c_int, [c_p, c_i64, c_p, c_u64, c_p, c_f64, c_p, c_p, c_p, c_p, c_p]),
     "srlx_vppo_lanes_create": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_i64, c_f64, c_int]),

@@ -28,7 +28,10 @@ class SrlxUpdateBackend:
     first `train_on_batch` (or `require_srlx_update`) fixes the answer until the next `setup`: "srlx" when the device layer's update serves the Parameter at that
     batch size, otherwise "torch", with the reason in `why_not_srlx_update`.  `update_path` names the backend the last update ran on.  The trainer supplies
     `_srlx_update_class()`, the device layer's update (`why_not(parameter, batch, config)` and a constructor over the Parameter), and `_make_torch_update()`, its
-    torch optimisers and schedulers."""
+    torch optimisers and schedulers.  A trainer whose device update has a second path names it in `SRLX_BACKENDS` (ppo_v.Trainer: "srlx_gemm"); such a name is
+    served, refused and reported as "srlx" is, on the same update object."""
+
+    SRLX_BACKENDS = ("srlx",)  # the names that ask for the libsrlx update
 
     def _reset_backend(self) -> None:
         """(from `on_setup`)"""
@@ -37,14 +40,15 @@ class SrlxUpdateBackend:
         self._backend = None
 
     def _choose_backend(self, batch: int) -> None:
-        if self.update_backend not in ("srlx", "torch"):
-            raise ValueError(f"update_backend {self.update_backend!r}: 'srlx' or 'torch'")
+        if self.update_backend not in self.SRLX_BACKENDS + ("torch",):
+            extra = "".join(f", {b!r}" for b in self.SRLX_BACKENDS[1:])
+            raise ValueError(f"update_backend {self.update_backend!r}: 'srlx' or 'torch'{extra}")
         self._backend = "torch"
-        if self.update_backend == "srlx":
+        if self.update_backend in self.SRLX_BACKENDS:
             update = self._srlx_update_class()
             self.why_not_srlx_update = update.why_not(self.parameter, batch, self.config)
             if not self.why_not_srlx_update:
-                self._backend = "srlx"
+                self._backend = self.update_backend
                 self._srlx = update(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
         if self._backend == "torch":
             self._make_torch_update()
@@ -53,7 +57,7 @@ class SrlxUpdateBackend:
         """The backend a batch of this size runs on: chosen at the first call, and a libsrlx update is sized then."""
         if self._backend is None:
             self._choose_backend(batch)
-        if self._backend == "srlx" and batch > self._srlx.max_batch:
+        if self._backend != "torch" and batch > self._srlx.max_batch:
             raise ValueError(f"a batch of {batch} on a libsrlx update sized for {self._srlx.max_batch} (the backend is fixed at the first train())")
         return self._backend
 

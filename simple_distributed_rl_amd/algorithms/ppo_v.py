@@ -10,9 +10,10 @@ module tree and the state-dict keys are the reference's (`hidden_block.hidden_la
 srl/rl/torch_/distributions/categorical_dist_block.py:74-97, normal_dist_block.py:66-145), so a state dict moves between the two by key.  The blocks'
 layers start as the reference's do (he_normal / zeros in the MLP blocks, torch's default nn.Linear in the out layer and the heads).
 
-Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of two backends that implement it alike:
-  "srlx"   one libsrlx call, three launches (device/vppo.py, csrc/srlx_vppo.hip), for GPU parameters inside the kernels' envelope;
-  "torch"  the reference's step in plain torch float32 with torch.optim.Adam, for everything else.
+Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of three backends that implement it alike:
+  "srlx"       one libsrlx call, three launches (device/vppo.py, csrc/srlx_vppo.hip), for GPU parameters inside the kernels' envelope;
+  "srlx_gemm"  the same call layer by layer on the float64 matrix cores (DESIGN.md 7t): opt-in, for wide layers and full batches; served and refused as "srlx";
+  "torch"      the reference's step in plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
 `engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path; `device/vppo_engine.py: VppoEngine` trains a Parameter of this
@@ -258,9 +259,11 @@ class Parameter(RLParameter):
 
 
 class Trainer(SrlxUpdateBackend, RLTrainer):
-    # "srlx" | "torch".  The default follows the project's 1.10 rule: 0.36 ms per train() on "srlx" against 2.02 ms on "torch" at ppo_v.Config() on
-    # CartPole (profiles/vppo_probe.json).  At the envelope's largest corner "torch" is the faster one (46.9 against 2.6 ms): set it there.
+    # "srlx" | "srlx_gemm" | "torch".  The default follows the project's 1.10 rule: 0.36 ms per train() on "srlx" against 2.02 ms on "torch" at
+    # ppo_v.Config() on CartPole (profiles/vppo_probe.json).  At the envelope's largest corner "srlx" takes 46.2 ms against 2.6 ms on "torch" and 0.62 ms on
+    # "srlx_gemm" (profiles/vppo_gemm_probe.json): set "srlx_gemm" for wide layers and full batches.
     update_backend = "srlx"
+    SRLX_BACKENDS = ("srlx", "srlx_gemm")
 
     def on_setup(self) -> None:
         cfg = self.config
@@ -297,7 +300,7 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         not_terminated and total_reward f32 [B][1].  `actions`: the discrete actions as int32 [B], for a caller that has them (the device engine): the "srlx"
         backend then reads them instead of the one-hot's argmax, and `action` may be None there."""
         backend = self._backend_for(state.shape[0])
-        if backend == "srlx":
+        if backend != "torch":
             out = self._update_srlx(state, n_state, action, old_logpi, reward, not_terminated, total_reward, actions)
         else:
             out = self._update_torch(state, n_state, action, old_logpi, reward, not_terminated, total_reward)
@@ -318,7 +321,8 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         else:
             act = action
         return u.update(state.reshape(B, -1), n_state.reshape(B, -1), act, old_logpi, reward.reshape(B), not_terminated.reshape(B), total_reward.reshape(B), lr,
-                        cfg.discount, cfg.clip_range, cfg.entropy_weight, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy)
+                        cfg.discount, cfg.clip_range, cfg.entropy_weight, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy,
+                        gemm=self._backend == "srlx_gemm")
 
     def _update_torch(self, state, n_state, action, old_logpi, reward, not_terminated, total_reward) -> dict:
         cfg, net = self.config, self.parameter.net

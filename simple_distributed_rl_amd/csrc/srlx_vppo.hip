@@ -19,6 +19,7 @@
 // LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
 // widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
+#include "srlx_mlp_gemm.h"
 #include "srlx_param_tail.h"
 #include "srlx_vppo_math.h"
 #include <cmath>
@@ -37,6 +38,8 @@ using srlxt::Seg;
 using srlxv::kHeadCols;
 using srlxv::kNormalLs;
 constexpr int kPlanes = 7;  // trunk 0..2, value 3..4, policy 5..6
+constexpr int kGemmLaunches = 11;  // forward 3 trunk + 3 branch depths, backward 2 branch depths + 3 trunk
+constexpr int kGemmJobs = 32;      // forward 3 x 2 + 3 x 4, backward 2 x 2 + 3
 
 struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
     Layers trunk, value, policy;
@@ -59,6 +62,12 @@ struct srlx_vppo {
     float *dlast_p;   // [max_batch][kHeadCols]: d loss / d (head outputs)
     float *rows;      // [4][max_batch]: the rows' loss sums
     double *partials; // [grad_blocks]: sums of squared gradients
+    // srlx_vppo_update_gemm's own, allocated at its first call
+    float *gemm_scratch;    // s' activations [2][max_batch][wmax], then v and n_v [2][max_batch], then the head rows z [max_batch][kHeadCols]
+    srlxg::Job *d_jobs;     // [kGemmJobs]: the plan's jobs, launch after launch
+    srlxg::Launch plan[kGemmLaunches];
+    int n_fwd, n_launches;  // forward launches, then the data-gradient ones
+    bool gemm_ok;           // the job table holds the bound tensors (upload_table makes it stale)
 };
 
 namespace {
@@ -165,6 +174,33 @@ __global__ void __launch_bounds__(kThreads) k_vppo_rows(const Net *__restrict__ 
     } else {
         srlxm::backward_rows<double>(n.trunk, n.trunk.L - 1, nb, i0, P, Q, S, ht, dht, plane, SumSeed{val, head, head_ls});
     }
+}
+
+// The gemm path's pointwise launch (srlx_vppo_update_gemm): what k_vppo_rows does between its forward and its backward chains, one thread per row.
+// `vn` [2][max_batch] holds v and n_v, `z` [max_batch][kHeadCols] the head rows the forward launches left; the row's closed forms are the same lines on the same
+// values.  A thread's head row and its gradient stand in LDS (indexed at run time: registers would go to scratch); no thread reads another's, so no barrier.
+constexpr int kLossThreads = 64;
+SRLXG_KERNEL void __launch_bounds__(kLossThreads) k_vppo_loss_rows(Batch a, Work w, const float *__restrict__ vn, const float *__restrict__ z, srlxv::Cfg c, int K, int A,
+                                                                 int normal) {
+    __shared__ float zs[kLossThreads * kHeadCols], dzs[kLossThreads * kHeadCols];
+    const int t = threadIdx.x;
+    const i64 b = (i64)blockIdx.x * kLossThreads + t;
+    if (b >= a.B) return;
+    float *zr = zs + t * kHeadCols, *dz = dzs + t * kHeadCols;
+    for (int j = 0; j < kHeadCols; j++) zr[j] = z[b * kHeadCols + j], dz[j] = 0.f;
+    const float v = vn[b], nv = vn[w.max_batch + b];
+    const float q = a.reward[b] + (a.not_term[b] * c.discount) * nv;
+    srlxv::RowSums s{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (normal) {
+        srlxv::normal_row(c, zr, K, a.action_f + b * K, a.old_lp + b * K, q, a.total_reward[b], v, s, dz, a.new_lp + b * K);
+    } else {
+        const int act = a.action_i[b];
+        a.new_lp[b] = srlxv::categorical_row(c, zr, A, act < 0 ? 0 : (act >= A ? A - 1 : act), a.old_lp[b], q, a.total_reward[b], v, s, dz);
+    }
+    a.v[b] = v, a.n_v[b] = nv;
+    w.rows[b] = s.huber, w.rows[w.max_batch + b] = s.align, w.rows[2 * w.max_batch + b] = s.policy, w.rows[3 * w.max_batch + b] = s.ent;
+    w.dlast_v[b] = s.dv;
+    for (int j = 0; j < kHeadCols; j++) w.dlast_p[b * kHeadCols + j] = dz[j];
 }
 
 __global__ void __launch_bounds__(kThreads) k_vppo_forward(const Net *__restrict__ net, i64 rows, const float *__restrict__ states, float *__restrict__ v, float *__restrict__ head0,
@@ -443,6 +479,7 @@ int upload_table(srlx_vppo *h) {
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     h->ps.table_ok = true;
+    h->gemm_ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
     return SRLX_OK;
 }
 
@@ -460,6 +497,159 @@ void fill(srlx_vppo *h, int D, int head, int A, int nt, const int *tw, int nv, c
     h->grad_blocks = (h->elements + 4 + kThreads - 1) / kThreads;
 }
 
+// The gemm path's launch plan: every Linear over the whole batch as one job, jobs of equal depth in one launch.  Forward: the trunk, layer by
+// layer, on s (kept) and s' (two scratch buffers in turn); then value and policy branch side by side, s' down the value branch only, the heads last.  Backward:
+// both branches side by side, then the trunk, whose top layer sums its sources in SumSeed's order: the value branch, the policy branch or the head, the log-scale
+// head.  The planes, and the layout upload_table hands to the tail, are the row path's.  Allocates the path's scratch at its first call.
+int upload_gemm(srlx_vppo *h) {
+    using srlxg::Job;
+    using srlxg::Src;
+    const i64 plane = h->max_batch * h->wmax;
+    if (!h->gemm_scratch) {
+        const size_t bytes = sizeof(float) * (size_t)(2 * plane + 2 * h->max_batch + h->max_batch * kHeadCols);
+        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, bytes));
+        SRLX_HIP(hipMemset(h->gemm_scratch, 0, bytes));
+        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
+    }
+    Job jobs[kGemmJobs];
+    memset(jobs, 0, sizeof(jobs));
+    int nj = 0, nl = 0;
+    float *const *P = h->ps.p;
+    const int Lt = h->Lt, Lv = h->Lv, Lp = h->Lp, A = h->A;
+    const int value_out = Lt + Lv, pol = Lt + Lv + 1, head = pol + Lp;  // Linear numbers in state-dict order
+    float *ht = h->h, *hv = h->h + 3 * plane, *hp = h->h + 5 * plane;
+    float *dht = h->dh, *dhv = h->dh + 3 * plane, *dhp = h->dh + 5 * plane;
+    float *sp[2] = {h->gemm_scratch, h->gemm_scratch + plane};
+    float *vb = h->gemm_scratch + 2 * plane, *nvb = vb + h->max_batch, *z = nvb + h->max_batch;
+    auto begin = [&](int bwd) { h->plan[nl] = srlxg::Launch{nj, 0, 0, bwd}; };
+    auto add = [&](int N) -> Job & {
+        h->plan[nl].njobs++;
+        h->plan[nl].nmax = N > h->plan[nl].nmax ? N : h->plan[nl].nmax;
+        return jobs[nj++];
+    };
+    auto fwd = [&](const float *x, int sel, int K, int lin, int N, float *y, int ldy, int relu) {
+        Job &j = add(N);
+        j.s[0] = Src{x, K, sel, P[2 * lin], K};
+        j.nsrc = 1, j.N = N, j.aux = P[2 * lin + 1], j.y = y, j.ldy = ldy, j.relu = relu;
+    };
+    int in = h->D;
+    for (int l = 0; l < Lt; in = h->Wt[l], l++, nl++) {
+        begin(0);
+        fwd(l ? ht + (l - 1) * plane : nullptr, l ? srlxg::kFromJob : srlxg::kArg0, in, l, h->Wt[l], ht + l * plane, h->Wt[l], 1);
+        fwd(l ? sp[(l - 1) & 1] : nullptr, l ? srlxg::kFromJob : srlxg::kArg1, in, l, h->Wt[l], sp[l & 1], h->Wt[l], 1);
+    }
+    const float *top = ht + (Lt - 1) * plane, *top2 = sp[(Lt - 1) & 1];
+    const int Wtop = in, depth = Lv > Lp ? Lv : Lp;
+    for (int d = 0; d <= depth; d++, nl++) {
+        begin(0);
+        if (d <= Lv) {
+            const float *x = d ? hv + (d - 1) * plane : top, *x2 = d ? sp[(Lt - 1 + d) & 1] : top2;
+            const int K = d ? h->Wv[d - 1] : Wtop;
+            if (d < Lv) {
+                fwd(x, 0, K, Lt + d, h->Wv[d], hv + d * plane, h->Wv[d], 1);
+                fwd(x2, 0, K, Lt + d, h->Wv[d], sp[(Lt + d) & 1], h->Wv[d], 1);
+            } else {
+                fwd(x, 0, K, value_out, 1, vb, 1, 0);
+                fwd(x2, 0, K, value_out, 1, nvb, 1, 0);
+            }
+        }
+        if (d <= Lp) {
+            const float *x = d ? hp + (d - 1) * plane : top;
+            const int K = d ? h->Wp[d - 1] : Wtop;
+            if (d < Lp) {
+                fwd(x, 0, K, pol + d, h->Wp[d], hp + d * plane, h->Wp[d], 1);
+            } else {
+                fwd(x, 0, K, head, A, z, kHeadCols, 0);
+                if (h->head) fwd(x, 0, K, head + 1, A, z + kNormalLs, kHeadCols, 0);
+            }
+        }
+    }
+    h->n_fwd = nl;
+    auto bwd = [&](float *y, const float *kept, int N) -> Job & {
+        Job &j = add(N);
+        j.nsrc = 0, j.N = N, j.aux = kept, j.y = y, j.ldy = N;
+        return j;
+    };
+    auto src = [&](Job &j, const float *a, int lda, int n, int lin) { j.s[j.nsrc++] = Src{a, lda, srlxg::kFromJob, P[2 * lin], n}; };
+    auto head_srcs = [&](Job &j) {
+        src(j, h->dlast_p, kHeadCols, A, head);
+        if (h->head) src(j, h->dlast_p + kNormalLs, kHeadCols, A, head + 1);
+    };
+    for (int d = 0; d < depth; d++, nl++) {
+        begin(1);
+        if (int l = Lv - 1 - d; l >= 0) {
+            Job &j = bwd(dhv + l * plane, hv + l * plane, h->Wv[l]);
+            if (d == 0) src(j, h->dlast_v, 1, 1, value_out);
+            else src(j, dhv + (l + 1) * plane, h->Wv[l + 1], h->Wv[l + 1], Lt + l + 1);
+        }
+        if (int l = Lp - 1 - d; l >= 0) {
+            Job &j = bwd(dhp + l * plane, hp + l * plane, h->Wp[l]);
+            if (d == 0) head_srcs(j);
+            else src(j, dhp + (l + 1) * plane, h->Wp[l + 1], h->Wp[l + 1], pol + l + 1);
+        }
+    }
+    for (int l = Lt - 1; l >= 0; l--, nl++) {
+        begin(1);
+        Job &j = bwd(dht + l * plane, ht + l * plane, h->Wt[l]);
+        if (l < Lt - 1) {
+            src(j, dht + (l + 1) * plane, h->Wt[l + 1], h->Wt[l + 1], l + 1);
+            continue;
+        }
+        if (Lv) src(j, dhv, h->Wv[0], h->Wv[0], Lt);
+        else src(j, h->dlast_v, 1, 1, value_out);
+        if (Lp) src(j, dhp, h->Wp[0], h->Wp[0], pol);
+        else head_srcs(j);
+    }
+    h->n_launches = nl;
+    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
+    h->gemm_ok = true;
+    return SRLX_OK;
+}
+
+
+// srlx_vppo_update (gemm = false: k_vppo_rows) and srlx_vppo_update_gemm (the layer-wise launches of upload_gemm's plan around k_vppo_loss_rows): one contract, one
+// set of planes, one gradient, clip and Adam tail.  `who` names the entry point in every message.
+int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
+           const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range, double entropy_weight,
+           double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v, float *d_n_v, float *d_new_logpi,
+           float *d_scalars, void *stream) {
+    SRLX_REQUIRE(h, "%s: NULL handle", who);
+    SRLX_REQUIRE(h->ps.ready(), "%s: bind the parameters, the gradient tensors and the Adam state first", who);
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "%s: batch %lld (handle sized for %lld)", who, (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_states && d_next_states && d_actions && d_old_logpi && d_rewards && d_not_terminated && d_total_rewards && d_v && d_n_v && d_new_logpi && d_scalars,
+                 "%s: NULL argument", who);
+    SRLX_REQUIRE(lr >= 0 && clip_range >= 0 && max_grad_norm > 0, "%s: lr and clip_range are non-negative, max_grad_norm positive", who);
+    SRLX_REQUIRE(squashed == 0 || squashed == 1, "%s: squashed is 0 or 1", who);
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "%s: the log-scale clamp's ends are ordered", who);
+    srlx::DeviceGuard g(h->device);
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
+    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
+    hipStream_t st = (hipStream_t)stream;
+    const int K = h->head ? h->A : 1;
+    const double N = (double)batch * K;
+    srlxv::Cfg c{(float)discount, (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)entropy_weight, (float)loss_align_coeff, (float)(1.0 / N),
+                 (float)(1.0 / (double)batch), (float)log_scale_lo, (float)log_scale_hi, squashed};
+    Batch b{(i64)batch, d_states, d_next_states, d_old_logpi, d_rewards, d_not_terminated, d_total_rewards, h->head ? nullptr : (const int32_t *)d_actions,
+            h->head ? (const float *)d_actions : nullptr, d_v, d_n_v, d_new_logpi};
+    Work w{h->h, h->dh, h->dlast_v, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
+    if (gemm) {
+        const float *vn = h->gemm_scratch + 2 * w.plane;
+        for (int l = 0; l < h->n_fwd; l++) srlxg::launch(h->plan[l], h->d_jobs, (int)batch, d_states, d_next_states, st);
+        hipLaunchKernelGGL(k_vppo_loss_rows, dim3((unsigned)((batch + kLossThreads - 1) / kLossThreads)), dim3(kLossThreads), 0, st, b, w, vn, vn + 2 * h->max_batch, c, K,
+                           h->A, h->head);
+        for (int l = h->n_fwd; l < h->n_launches; l++) srlxg::launch(h->plan[l], h->d_jobs, (int)batch, nullptr, nullptr, st);
+    } else {
+        hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
+    }
+    GradArgs ga{h->d_segs, h->nt, d_states, h->partials, LossSums{(i64)batch, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, d_scalars}};
+    hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
+    const srlxt::StepArgs sa = h->ps.step_args(h->d_segs, h->nt, h->partials, h->grad_blocks, max_grad_norm, lr, d_scalars + 4);
+    hipLaunchKernelGGL(k_vppo_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
+    SRLX_HIP(hipGetLastError());
+    h->ps.steps++;
+    return SRLX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -508,7 +698,8 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
 int srlx_vppo_destroy(srlx_vppo_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
-    for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->h, (void *)h->dh, (void *)h->dlast_v, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials})
+    for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->h, (void *)h->dh, (void *)h->dlast_v, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials,
+                    (void *)h->gemm_scratch, (void *)h->d_jobs})
         if (p) (void)hipFree(p);
     delete h;
     return SRLX_OK;
@@ -601,33 +792,16 @@ int srlx_vppo_update(srlx_vppo_t *h, int64_t batch, const float *d_states, const
                      const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
                      double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
                      float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream) {
-    SRLX_REQUIRE(h, "vppo_update: NULL handle");
-    SRLX_REQUIRE(h->ps.ready(), "vppo_update: bind the parameters, the gradient tensors and the Adam state first");
-    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "vppo_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
-    SRLX_REQUIRE(d_states && d_next_states && d_actions && d_old_logpi && d_rewards && d_not_terminated && d_total_rewards && d_v && d_n_v && d_new_logpi && d_scalars,
-                 "vppo_update: NULL argument");
-    SRLX_REQUIRE(lr >= 0 && clip_range >= 0 && max_grad_norm > 0, "vppo_update: lr and clip_range are non-negative, max_grad_norm positive");
-    SRLX_REQUIRE(squashed == 0 || squashed == 1, "vppo_update: squashed is 0 or 1");
-    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_update: the log-scale clamp's ends are ordered");
-    srlx::DeviceGuard g(h->device);
-    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
-    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
-    hipStream_t st = (hipStream_t)stream;
-    const int K = h->head ? h->A : 1;
-    const double N = (double)batch * K;
-    srlxv::Cfg c{(float)discount, (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)entropy_weight, (float)loss_align_coeff, (float)(1.0 / N),
-                 (float)(1.0 / (double)batch), (float)log_scale_lo, (float)log_scale_hi, squashed};
-    Batch b{(i64)batch, d_states, d_next_states, d_old_logpi, d_rewards, d_not_terminated, d_total_rewards, h->head ? nullptr : (const int32_t *)d_actions,
-            h->head ? (const float *)d_actions : nullptr, d_v, d_n_v, d_new_logpi};
-    Work w{h->h, h->dh, h->dlast_v, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
-    hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
-    GradArgs ga{h->d_segs, h->nt, d_states, h->partials, LossSums{(i64)batch, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, d_scalars}};
-    hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
-    const srlxt::StepArgs sa = h->ps.step_args(h->d_segs, h->nt, h->partials, h->grad_blocks, max_grad_norm, lr, d_scalars + 4);
-    hipLaunchKernelGGL(k_vppo_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
-    SRLX_HIP(hipGetLastError());
-    h->ps.steps++;
-    return SRLX_OK;
+    return update("vppo_update", false, h, batch, d_states, d_next_states, d_actions, d_old_logpi, d_rewards, d_not_terminated, d_total_rewards, lr, discount, clip_range,
+                  entropy_weight, loss_align_coeff, max_grad_norm, squashed, log_scale_lo, log_scale_hi, d_v, d_n_v, d_new_logpi, d_scalars, stream);
+}
+
+int srlx_vppo_update_gemm(srlx_vppo_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
+                          const float *d_rewards, const float *d_not_terminated, const float *d_total_rewards, double lr, double discount, double clip_range,
+                          double entropy_weight, double loss_align_coeff, double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_v,
+                          float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream) {
+    return update("vppo_update_gemm", true, h, batch, d_states, d_next_states, d_actions, d_old_logpi, d_rewards, d_not_terminated, d_total_rewards, lr, discount,
+                  clip_range, entropy_weight, loss_align_coeff, max_grad_norm, squashed, log_scale_lo, log_scale_hi, d_v, d_n_v, d_new_logpi, d_scalars, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """V-PPO's update on libsrlx (csrc/srlx_vppo.hip): `VppoUpdate` binds an `algorithms.ppo_v.Parameter`'s own tensors by address -- the network
 stays what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after the norm clip)
-and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches."""
+and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches;
+`update(..., gemm=True)` is the same step layer by layer on the float64 matrix cores (srlx_vppo_update_gemm), the path for wide layers and full
+batches."""
 import ctypes
 
 import torch
@@ -76,10 +78,11 @@ class VppoUpdate(R.RowUpdate):
 
     # ---- the calls (`steps`: RowUpdate) --------------------------------------------------------------------------------------------------------------------
     def update(self, state, next_state, action, old_logpi, reward, not_terminated, total_reward, lr, discount, clip_range, entropy_weight, loss_align_coeff,
-               max_grad_norm, squashed: bool) -> dict:
+               max_grad_norm, squashed: bool, gemm: bool = False) -> dict:
         """state / next_state f32 [B][D]; action i32 [B] (categorical) or f32 [B][K] (Normal); old_logpi f32 [B][K]; reward, not_terminated, total_reward f32 [B];
         all on the device.  Returns v, n_v [B], new_logpi [B][K] and `scalars` [5] (loss_value, loss_v_align, loss_policy, loss_e, the gradient norm before the
-        clip), device tensors; nothing synchronises."""
+        clip), device tensors; nothing synchronises.  `gemm`: the layer-wise path on the float64 matrix cores; the two paths share the handle's planes, gradient
+        tensors and Adam state, so one VppoUpdate may alternate them between updates."""
         B = state.shape[0]
         if B > self.max_batch:
             raise ValueError(f"VppoUpdate: batch size {B} above max_batch {self.max_batch}")
@@ -89,9 +92,10 @@ class VppoUpdate(R.RowUpdate):
         assert all(t.numel() == B for t in keep[4:])
         out = {"v": torch.empty(B, dtype=torch.float32, device=self.device), "n_v": torch.empty(B, dtype=torch.float32, device=self.device),
                "new_logpi": torch.empty((B, self.K), dtype=torch.float32, device=self.device), "scalars": torch.empty(5, dtype=torch.float32, device=self.device)}
-        N.check(self._lib.srlx_vppo_update(self._h, B, *[N.tptr(t) for t in keep], float(lr), float(discount), float(clip_range), float(entropy_weight),
-                                           float(loss_align_coeff), float(max_grad_norm), int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(out["v"]),
-                                           N.tptr(out["n_v"]), N.tptr(out["new_logpi"]), N.tptr(out["scalars"]), N.torch_stream_ptr()))
+        call = self._lib.srlx_vppo_update_gemm if gemm else self._lib.srlx_vppo_update
+        N.check(call(self._h, B, *[N.tptr(t) for t in keep], float(lr), float(discount), float(clip_range), float(entropy_weight), float(loss_align_coeff),
+                     float(max_grad_norm), int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(out["v"]), N.tptr(out["n_v"]), N.tptr(out["new_logpi"]),
+                     N.tptr(out["scalars"]), N.torch_stream_ptr()))
         self._keep = keep
         return out
 

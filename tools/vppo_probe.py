@@ -1,17 +1,20 @@
-"""Probe: V-PPO's Trainer.train() on libsrlx's fused update ("srlx") next to the plain torch backend ("torch"), the measurement that decides
-ppo_v.Trainer.update_backend's default.
+"""Probe: V-PPO's Trainer.train() on libsrlx's fused update ("srlx"), on its layer-wise update on the float64 matrix cores ("srlx_gemm") and on the
+plain torch backend ("torch"): the measurement that decides ppo_v.Trainer.update_backend's default and says on which side of the row path a shape
+falls.
 
-    python tools/vppo_probe.py --out profiles/vppo_probe.json
-    rocprofv3 --kernel-trace --stats -d DIR -o vppo --output-format csv -- python tools/vppo_probe.py --trace-loop     # a run of its own, no counters
+    python tools/vppo_probe.py --out profiles/vppo_gemm_probe.json
+    rocprofv3 --kernel-trace --stats -d DIR -o vppo --output-format csv -- python tools/vppo_probe.py --trace-loop [--shape corner]   # a run of its own, no counters
 
-Both arms run in ONE process.  Per shape: one untimed train() of each arm (allocation, the handle, torch's lazy initialisation), then three interleaved rounds
-(srlx, torch, srlx, torch, ...) of CALLS whole train() calls each -- host batch assembly from a memory that hands out one fixed batch, the update, and the
+All arms run in ONE process.  Per shape: one untimed train() of each arm (allocation, the handle, torch's lazy initialisation), then three interleaved rounds
+(srlx, srlx_gemm, torch, srlx, ...) of CALLS whole train() calls each -- host batch assembly from a memory that hands out one fixed batch, the update, and the
 `info` read that synchronises -- every round ending in a device synchronise.  The figure is milliseconds per train().
   default  ppo_v.Config() on CartPole: B 64, D 4, A 2, hidden 64-64, value 64, policy ()
+  b64-w256   B 64, D 4, A 2, every block 256 wide at the default's depths
+  b256-w128  B 256, D 4, A 2, every block 128 wide at the default's depths
   corner   the largest corner of the envelope: B 256, D 256, A 16, hidden 512-512-512, value 512-512, policy 512-512
 The default rule: "srlx" iff default.srlx_ms_mean <= 1.10 * default.torch_ms_mean of the same run.
---trace-loop runs, at the default shape, one train() of each arm and then TRACE_CALLS of "srlx" followed by TRACE_CALLS of "torch": a kernel trace of it gives
-the launches per train() of each arm (the libsrlx kernels are named k_vppo_*; everything else is torch's)."""
+--trace-loop runs, at --shape, one train() of each arm and then TRACE_CALLS of each arm in turn: a kernel trace of it gives the launches and the kernel time
+per train() of each arm (the libsrlx kernels are named k_vppo_* and k_mlp_gemm_*; everything else is torch's)."""
 import argparse
 import json
 import os
@@ -23,7 +26,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 CALLS, TRACE_CALLS = 200, 100
 # B, D, A, hidden, value, policy
-SHAPES = dict(default=(64, 4, 2, (64, 64), (64,), ()), corner=(256, 256, 16, (512, 512, 512), (512, 512), (512, 512)))
+SHAPES = {"default": (64, 4, 2, (64, 64), (64,), ()), "b64-w256": (64, 4, 2, (256, 256), (256,), ()), "b256-w128": (256, 4, 2, (128, 128), (128,), ()),
+          "corner": (256, 256, 16, (512, 512, 512), (512, 512), (512, 512))}
+ARMS = ("srlx", "srlx_gemm", "torch")
 
 
 class _FixedMemory:
@@ -69,7 +74,7 @@ def _loop(tr, calls):
 
 
 def measure(shape):
-    arms = {a: _trainer(shape, a) for a in ("srlx", "torch")}
+    arms = {a: _trainer(shape, a) for a in ARMS}
     for a, tr in arms.items():
         tr.train()
         assert tr.update_path == a, (a, tr.update_path, tr.why_not_srlx_update)
@@ -83,6 +88,10 @@ def measure(shape):
     res.update({a + "_ms": r for a, r in runs.items()})
     res.update({a + "_ms_mean": sum(r) / len(r) for a, r in runs.items()})
     res["srlx_over_torch"] = res["srlx_ms_mean"] / res["torch_ms_mean"]
+    res["gemm_over_srlx_by_round"] = [g / r for g, r in zip(runs["srlx_gemm"], runs["srlx"])]
+    res["gemm_over_torch_by_round"] = [g / t for g, t in zip(runs["srlx_gemm"], runs["torch"])]
+    res["gemm_side_of_row_path"] = "faster" if all(x < 1 for x in res["gemm_over_srlx_by_round"]) else (
+        "slower" if all(x > 1 for x in res["gemm_over_srlx_by_round"]) else "within the rounds' spread")
     res["updates_per_s"] = {a: 1e3 / res[a + "_ms_mean"] for a in arms}
     return res
 
@@ -91,16 +100,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vppo_probe.json"))
     ap.add_argument("--trace-loop", action="store_true")
+    ap.add_argument("--shape", default="default", choices=list(SHAPES), help="the shape of --trace-loop")
     args = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
     if args.trace_loop:
-        for a in ("srlx", "torch"):
-            tr = _trainer("default", a)
+        for a in ARMS:
+            tr = _trainer(args.shape, a)
             tr.train()
             _loop(tr, TRACE_CALLS)
-        print(f"trace loop: 1 + {TRACE_CALLS} train() calls per arm at the default shape")
+        print(f"trace loop: 1 + {TRACE_CALLS} train() calls per arm at the {args.shape} shape")
         return
     t0 = time.time()
     from simple_distributed_rl_amd import _native as N
@@ -108,7 +118,7 @@ def main():
     out = dict(device=N.device_info(0), torch=torch.__version__)
     for shape in SHAPES:
         out[shape] = measure(shape)
-        print(shape, {k: out[shape][k] for k in ("srlx_ms_mean", "torch_ms_mean", "srlx_over_torch")}, flush=True)
+        print(shape, {k: out[shape][k] for k in ("srlx_ms", "srlx_gemm_ms", "torch_ms", "gemm_side_of_row_path")}, flush=True)
     out["default_rule"] = dict(rule="update_backend = 'srlx' iff default.srlx_ms_mean <= 1.10 * default.torch_ms_mean",
                                srlx=bool(out["default"]["srlx_ms_mean"] <= 1.10 * out["default"]["torch_ms_mean"]))
     out["wall_s"] = time.time() - t0
