@@ -1607,6 +1607,20 @@ int srlx_pendulum_lane_step(int64_t n_envs, double *d_state, int32_t *d_steps, i
  *                                  the clamp's closed interval), its norm, the clip, Adam(lr).
  *                                Outputs: q, target_q f32 [B]; next_action, pi_action f32 [B][n_out]; scalars f32 [5] = loss_q, loss_q_align, loss_policy, the
  *                                Q-network's and the policy's gradient norm before their clips.
+ *   srlx_notsac_update_gemm    : srlx_notsac_update's contract -- arguments, preconditions, arithmetic, outputs; srlx_last_error() names notsac_update_gemm -- on
+ *                                gfx950's float64 matrix cores (srlx_mlp_gemm.h): every Linear of both networks over the whole batch as one tiled
+ *                                GEMM, layers of equal depth in one launch.  Target half: the policy on s' layer by layer, its head, one pointwise launch for a'
+ *                                and the stored actions, one for act_block (an A-term chain per column, not a GEMM) on both row sets, q_block and q_out on
+ *                                (s, a) and (s', a') side by side, one pointwise launch for the target and the loss rows, the data gradients down q_block and
+ *                                through the embedding columns of its first weight and the SiLU derivative; then srlx_notsac_update's own gradient and Adam
+ *                                launches.  Policy half: the policy on s, its head, the action, act_block, the STEPPED q_block and q_out, the data gradients
+ *                                only (down to d loss / d action through act_block's weight), the head's Jacobian, the policy's chain; the same two launches.
+ *                                Products of float32 values are exact in float64, every sum accumulates in float64 and is rounded to float32 once, as in
+ *                                srlx_notsac_update; the matrix core's order inside a group of 4 terms is its own, so a value may differ from
+ *                                srlx_notsac_update's in its last bit.  The same handle, planes, gradient tensors, Adam state and step count: one handle may
+ *                                alternate the two calls.  The first call of a handle allocates 2 max_batch (widest row) + max_batch (D + act_emb_units) + 34
+ *                                max_batch floats and the job table (srlx_notsac_scratch_floats does not count them).  No host synchronisation, no atomics:
+ *                                equal inputs give equal bits.
  *   srlx_notsac_set_rows_per_workgroup : the launch shape of the row kernels and of srlx_notsac_forward: 1, 2, 4, 8 or 16 rows per workgroup, or 0 for the
  *                                default: the smallest of those that keeps the launch within 256 workgroups, which is 1 for every update (B <= 256) and more
  *                                only for a forward call of more than 256 rows.  It changes the launch shape and never a bit (tests/test_notsac_gpu.py holds
@@ -1630,6 +1644,10 @@ int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, c
                        const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff,
                        double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
                        float *d_pi_action, float *d_scalars, void *stream);
+int srlx_notsac_update_gemm(srlx_notsac_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_rewards,
+                            const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff,
+                            double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
+                            float *d_pi_action, float *d_scalars, void *stream);
 int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
                         const float *d_actions, float *d_q, void *stream);
 

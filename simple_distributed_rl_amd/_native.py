@@ -310,6 +310,7 @@ SIGNATURES = {
     "srlx_notsac_set_rows_per_workgroup": (c_int, [c_p, c_int]),
     "srlx_notsac_steps": (c_i64, [c_p]),
     "srlx_notsac_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
+    "srlx_notsac_update_gemm": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
     "srlx_notsac_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
 }
 OBS_U8, OBS_F32 = 0, 1

@@ -13,9 +13,10 @@ Networks.  PolicyNetwork (:27-56): in_block -> policy_block -> policy_dist_block
 Normal head, `act_block.0.*`, `q_block.hidden_layers.*`, `q_out_layer.*`), so a state dict moves between the two by key.  The Normal head is ppo_v's block: the
 reference builds the same one.
 
-Trainer.train() (:131-191) is DESIGN.md 7r's contract, on one of two backends that implement it alike:
-  "srlx"   one libsrlx call, six launches (device/notsac.py, csrc/srlx_notsac.hip), for GPU parameters inside the kernels' envelope;
-  "torch"  the reference's step in plain torch float32 with two torch.optim.Adam, for everything else.
+Trainer.train() (:131-191) is DESIGN.md 7r's contract, on one of three backends that implement it alike:
+  "srlx"       one libsrlx call, six launches (device/notsac.py, csrc/srlx_notsac.hip), for GPU parameters inside the kernels' envelope;
+  "srlx_gemm"  the same call layer by layer on the float64 matrix cores (DESIGN.md 7u): opt-in, for wide layers and full batches; served and refused as "srlx";
+  "torch"      the reference's step in plain torch float32 with two torch.optim.Adam, for everything else.
 `update_backend`, `update_path` and `why_not_srlx_update` work as in ppo_v.Trainer.  `engine_kind(sac_not.Config())` is None: there is no device engine.
 
 The noise is an input.  `train_on_batch(..., noise)` takes a float32 tensor [2][B][K] of standard normals (Normal head) or [2][B][A] of uniforms in [0, 1)
@@ -212,9 +213,11 @@ class Parameter(RLParameter):
 
 
 class Trainer(SrlxUpdateBackend, RLTrainer):
-    # "srlx" | "torch".  The default follows the project's 1.10 rule: 1.45 ms per train() on "srlx" against 3.41 ms on "torch" at sac_not.Config()
-    # on Pendulum (profiles/notsac_probe.json).  At the envelope's largest corner "torch" is the faster one (54.8 against 3 to 6 ms): set it there.
+    # "srlx" | "srlx_gemm" | "torch".  The default follows the project's 1.10 rule: 1.45 ms per train() on "srlx" against 3.41 ms on "torch" at
+    # sac_not.Config() on Pendulum (profiles/notsac_probe.json).  At the envelope's largest corner "srlx" takes 53.9 ms against 3.0 to 3.6 ms on "torch" and 0.92 to
+    # 0.95 ms on "srlx_gemm" (profiles/notsac_gemm_probe.json): set "srlx_gemm" for wide layers and full batches.
     update_backend = "srlx"
+    SRLX_BACKENDS = ("srlx", "srlx_gemm")
 
     def on_setup(self) -> None:
         cfg = self.config
@@ -265,7 +268,7 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         backend = self._backend_for(B)
         if noise is None:
             noise = self.draw_noise(B)
-        if backend == "srlx":
+        if backend != "torch":
             out = self._update_srlx(state, n_state, action, reward, not_terminated, total_reward, noise)
         else:
             out = self._update_torch(state, n_state, action, reward, not_terminated, total_reward, noise)
@@ -281,7 +284,7 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         lr = cfg.lr * cfg.lr_scheduler.factor(u.steps(), cfg.lr)
         act = action.argmax(dim=1).to(torch.int32) if self.discrete else action
         return u.update(state.reshape(B, -1), n_state.reshape(B, -1), act, reward.reshape(B), not_terminated.reshape(B), total_reward.reshape(B), noise, lr,
-                        cfg.discount, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy)
+                        cfg.discount, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy, gemm=self._backend == "srlx_gemm")
 
     def _update_torch(self, state, n_state, action, reward, not_terminated, total_reward, noise) -> dict:
         cfg, policy, qnet = self.config, self.parameter.policy, self.parameter.qnet

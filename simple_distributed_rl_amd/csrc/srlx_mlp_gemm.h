@@ -1,7 +1,8 @@
 // srlx_mlp_gemm.h -- the layer passes of an MLP update over the WHOLE batch, one tiled GEMM per Linear on gfx950's float64 matrix cores
 // (v_mfma_f64_16x16x4_f64).  The row-blocked passes of srlx_mlp_rows.h walk at most 16 rows through every layer in one workgroup; at wide layers and full batches
 // that is a GEMM-sized problem walked as chains, and this header is the other way to run it: V-PPO is the first consumer
-// (srlx_vppo.hip: srlx_vppo_update_gemm); NoT_SAC and SAC-Discrete can build their job tables on the same two kernels.
+// (srlx_vppo.hip: srlx_vppo_update_gemm), NoT_SAC the second (srlx_notsac.hip: srlx_notsac_update_gemm, DESIGN.md 7u: k_mlp_gemm_fwd and a backward
+// kernel of its own on tile_sums); SAC-Discrete can build its job tables on the same routines.
 //   Job, Src          one GEMM of a launch: up to three (rows, weight) sources summed into one output tile, in the order a, b, c (SumSeed's order)
 //   k_mlp_gemm_fwd    Y[M][N] = act(X[M][K] W[N][K]^T + b): the weight in torch's [out][in] layout, both operands contiguous along k
 //   k_mlp_gemm_bwd    dH[M][N] = H[M][N] > 0 ? sum_s dOut_s[M][n_s] W_s[n_s][N] : 0: the weight read untransposed, coalesced along the output column
@@ -172,7 +173,8 @@ __device__ __forceinline__ f64x4 tile_sums(const Job &job, int M, int m0, int n0
 }
 
 // grid (column tiles of the launch's widest job, row tiles, jobs); a job narrower than the grid leaves its spare workgroups idle
-SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_fwd(const Job *__restrict__ jobs, int M, const float *__restrict__ x0, const float *__restrict__ x1) {
+// (static: every translation unit that includes this header -- srlx_vppo.hip, srlx_notsac.hip -- holds the two kernels for its own launches)
+static SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_fwd(const Job *__restrict__ jobs, int M, const float *__restrict__ x0, const float *__restrict__ x1) {
     __shared__ __attribute__((aligned(16))) float As[2 * kTile * kLdK], Bs[2 * kTile * kLdK];
     const Job &job = jobs[blockIdx.z];
     const int n0 = blockIdx.x * kTile, m0 = blockIdx.y * kTile;
@@ -191,7 +193,7 @@ SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_fwd(const Job *__restri
     }
 }
 
-SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_bwd(const Job *__restrict__ jobs, int M, const float *__restrict__ x0, const float *__restrict__ x1) {
+static SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_bwd(const Job *__restrict__ jobs, int M, const float *__restrict__ x0, const float *__restrict__ x1) {
     __shared__ __attribute__((aligned(16))) float As[2 * kTile * kLdK], Bs[2 * kChunk * kLdN];
     const Job &job = jobs[blockIdx.z];
     const int n0 = blockIdx.x * kTile, m0 = blockIdx.y * kTile;

@@ -21,6 +21,17 @@
 // LDS: three row buffers of 16 x (widest row + 1) floats (the act_block's pre-activations have to outlive q_block's chains) and the 32 KB weight tile:
 // 131 264 bytes at a widest row of 512 -- the concatenated row of D + E floats is held to that.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
+//
+// srlx_notsac_update_gemm is the same update layer by layer: every Linear of both networks over the whole batch as one job of srlx_mlp_gemm.h's
+// tile on the float64 matrix cores, jobs of equal depth in one launch, and between those launches
+//   k_notsac_gemm_action     one thread per row (Gumbel) or per row and element (Normal): the action from the head rows and one noise plane, act_block's input rows
+//   k_notsac_gemm_embed      one thread per (row set, row, column of the concatenated row): the state copied, act_block's Linear (A <= 16 terms) and SiLU
+//   k_notsac_gemm_q_loss     one thread per row: the target, the Huber and MSE terms, the seed d loss / d q
+//   k_notsac_gemm_bwd        srlx_mlp_gemm.h's backward tile with NoT_SAC's three epilogues: the ReLU mask, the SiLU derivative behind a column range of
+//                            q_block's first weight, none (d loss / d action)
+//   k_notsac_gemm_head_grad  one thread per row or per row and element: the head's Jacobian
+// with k_notsac_grad and k_notsac_step as the tail of each half.
+#include "srlx_mlp_gemm.h"
 #include "srlx_notsac_math.h"
 #include "srlx_param_tail.h"
 #include <cmath>
@@ -40,6 +51,16 @@ using srlxt::Seg;
 constexpr int kNetTensors = 10;  // policy: 2 x (3 layers + 2 heads); Q: 2 x (act_block + 3 layers + q_out)
 static_assert(2 * kNetTensors <= srlxt::kMaxTensors, "the policy's tensors, then the Q-network's, in one ParamSet");
 constexpr int kMaxWidth = 512;   // of a hidden layer and of the concatenated row
+
+// The gemm path's plan: a list of steps, each a launch of jobs from the device table or one of the pointwise kernels between them.
+enum StepKind { kFwd, kBwd, kNextAction, kEmbedBoth, kQLoss, kTailQ, kPiAction, kEmbedOne, kHeadGrad, kTailP };
+struct Step {
+    int kind;
+    srlxg::Launch l;  // kFwd, kBwd
+};
+constexpr int kGemmSteps = 40;  // target half: 3 + 1 policy, 2 pointwise, 3 + 1 Q, 1 pointwise, 3 + 1 backward, the tail; policy half: 20
+constexpr int kGemmJobs = 40;   // target half: 3 + 2, 2 x (3 + 1), 3 + 1; policy half: 3 + 2, 3 + 1, 3 + 1 + 1, 3
+enum Epilogue { kEpiRelu = 0, kEpiSilu = 1, kEpiNone = 2 };  // of a k_notsac_gemm_bwd job, in Job::relu
 
 struct Net {  // (in device memory: the kernels read it through a pointer)
     Layers pi, q;
@@ -67,6 +88,13 @@ struct srlx_notsac {
     float *dlast_p;     // [max_batch][kHeadCols]: d loss / d (head outputs)
     float *rows;        // [3][max_batch]: the rows' Huber terms, MSE terms and q(s, pi(s))
     double *partials;   // [max(blocks_p, blocks_q)]: sums of squared gradients
+    // srlx_notsac_update_gemm's own, allocated at its first call
+    float *gemm_scratch;  // two planes [max_batch][wmax] (the layers nothing keeps, in turn), the s' rows of xcat, the head rows and d loss / d action
+                          // [max_batch][kHeadCols] each, q(s', a') and q(s, a) [2][max_batch]
+    srlxg::Job *d_jobs;   // [kGemmJobs]: the plan's jobs, launch after launch
+    Step plan[kGemmSteps];
+    int n_steps;
+    bool gemm_ok;         // the job table holds the bound tensors (upload_table makes it stale)
 };
 
 namespace {
@@ -346,6 +374,138 @@ __global__ void __launch_bounds__(kThreads) k_notsac_grad(GradArgs a) { srlxt::g
 
 __global__ void __launch_bounds__(kThreads) k_notsac_step(srlxt::StepArgs a) { srlxt::step_body(a); }
 
+// ---- the gemm path's own kernels (srlx_notsac_update_gemm).  The closed forms are the lines the row kernels run, on the same float32 values.
+
+// The backward tile of srlx_mlp_gemm.h with the epilogue the job names in Job::relu:
+//   kEpiRelu  dH = H > 0 ? sum : 0, H = aux [M][N] (k_mlp_gemm_bwd's)
+//   kEpiSilu  the columns c0..N-1 of the weight only (q_block's first [H][D + E] matrix from its embedding column on: the tile starts at column c0 of the whole
+//             matrix, so the row stride stays N and nothing below c0 is computed): d z = (float)(sum * silu_grad(z)), z = aux [M][N - c0], as q_backward
+//   kEpiNone  the rounded sum (d loss / d action through act_block's weight)
+// grid (column tiles of the launch's widest output, row tiles, jobs).
+SRLXG_KERNEL void __launch_bounds__(srlxg::kThreads) k_notsac_gemm_bwd(const srlxg::Job *__restrict__ jobs, int M, int c0) {
+    using namespace srlxg;
+    __shared__ __attribute__((aligned(16))) float As[2 * kTile * kLdK], Bs[2 * kChunk * kLdN];
+    const Job &job = jobs[blockIdx.z];
+    const int epi = job.relu, first = epi == kEpiSilu ? c0 : 0, width = job.N - first;
+    const int n0 = blockIdx.x * kTile, m0 = blockIdx.y * kTile;
+    if (n0 >= width) return;
+    const f64x4 acc = tile_sums<true>(job, M, m0, first + n0, nullptr, nullptr, As, Bs);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = n0 + (wave & 1) * 16 + (lane & 15);
+    if (col >= width) return;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int row = m0 + (wave >> 1) * 16 + 4 * r + (lane >> 4);
+        if (row >= M) continue;
+        float g = (float)acc[r];
+        if (epi == kEpiRelu) g = job.aux[(i64)row * width + col] > 0.f ? g : 0.f;
+        else if (epi == kEpiSilu) g = (float)(acc[r] * srlxn::silu_grad(job.aux[(i64)row * width + col]));
+        job.y[(i64)row * job.ldy + col] = g;
+    }
+}
+
+constexpr int kRowThreads = 64;  // of the one-thread-per-row kernels
+
+// One row set of k_notsac_gemm_embed: states [B][D] and actions [B][A] in, the concatenated rows [B][D + E] and (NULL: not kept) act_block's pre-activations out
+struct EmbedSet {
+    const float *s, *act;
+    float *xcat, *zact;
+};
+
+// q_block's input rows: one thread per (row set, row, column).  Columns below D copy the state; column D + j is SiLU of act_block's Linear, an A-term float64
+// chain in dense<double>'s order, rounded once.  blockIdx.y: the row set (the target half runs (s, a) and (s', a') in one launch).
+SRLXG_KERNEL void __launch_bounds__(kThreads) k_notsac_gemm_embed(EmbedSet s0, EmbedSet s1, i64 B, const float *__restrict__ wa, const float *__restrict__ ba, int D, int A,
+                                                                  int E) {
+    const int W = D + E;
+    const i64 p = (i64)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= B * W) return;
+    const bool second = blockIdx.y != 0;
+    const float *s = second ? s1.s : s0.s, *act = second ? s1.act : s0.act;
+    float *xcat = second ? s1.xcat : s0.xcat, *zact = second ? s1.zact : s0.zact;
+    const i64 r = p / W;
+    const int k = (int)(p % W);
+    if (k < D) {
+        xcat[p] = s[r * D + k];
+        return;
+    }
+    const int j = k - D;
+    double acc = 0.0;
+    for (int i = 0; i < A; i++) acc = srlxm::fma_acc((double)wa[j * A + i], (double)act[r * A + i], acc);
+    const float z = (float)(acc + (double)ba[j]);
+    if (zact) zact[r * E + j] = z;
+    xcat[p] = srlxn::silu(z);
+}
+
+// The action of every row from its head row `z` [B][kHeadCols] and one noise plane, and act_block's input rows `ain`.
+//   half 0 (the target): a' = normal_action / the one-hot of gumbel_argmax into `out` (next_action); `ain` takes the STORED actions
+//   half 1 (the policy): a = normal_action / gumbel_softmax into `out` (pi_action) and `ain`; dlast_q takes the seed -1 / B of q(s, pi(s))
+// One thread per row and element (Normal) or per row (Gumbel).
+struct ActionArgs {
+    i64 B;
+    const float *z, *noise;
+    float *out, *ain, *dlast_q;
+    const int32_t *action_i;
+    const float *action_f;
+    float ls_lo, ls_hi, seed;
+    int squashed, A, normal, half;
+};
+SRLXG_KERNEL void __launch_bounds__(kRowThreads) k_notsac_gemm_action(ActionArgs a) {
+    const i64 p = (i64)blockIdx.x * kRowThreads + threadIdx.x;
+    const int A = a.A;
+    if (a.normal) {
+        if (p >= a.B * A) return;
+        const i64 r = p / A;
+        const int j = (int)(p % A);
+        const float x = srlxn::normal_action(a.z[r * kHeadCols + j], a.z[r * kHeadCols + kNormalLs + j], a.ls_lo, a.ls_hi, a.noise[p], a.squashed);
+        a.out[p] = x;
+        a.ain[p] = a.half ? x : a.action_f[p];
+        if (a.half && j == 0) a.dlast_q[r] = a.seed;
+        return;
+    }
+    if (p >= a.B) return;
+    if (a.half) {
+        srlxn::gumbel_softmax(a.z + p * kHeadCols, a.noise + p * A, A, a.out + p * A);
+        for (int k = 0; k < A; k++) a.ain[p * A + k] = a.out[p * A + k];
+        a.dlast_q[p] = a.seed;
+    } else {
+        const int best = srlxn::gumbel_argmax(a.z + p * kHeadCols, a.noise + p * A, A);
+        const int act = a.action_i[p];
+        const int ac = act < 0 ? 0 : (act >= A ? A - 1 : act);
+        for (int k = 0; k < A; k++) a.out[p * A + k] = k == best ? 1.f : 0.f, a.ain[p * A + k] = k == ac ? 1.f : 0.f;
+    }
+}
+
+// The Q step's rows: `qv` [2][max_batch] holds q(s', a') and q(s, a)
+SRLXG_KERNEL void __launch_bounds__(kRowThreads) k_notsac_gemm_q_loss(Batch a, const float *__restrict__ qv, float *__restrict__ rows, float *__restrict__ dlast_q,
+                                                                     i64 max_batch, Cfg c) {
+    const i64 b = (i64)blockIdx.x * kRowThreads + threadIdx.x;
+    if (b >= a.B) return;
+    const float qn = qv[b], q = qv[max_batch + b];
+    const srlxn::QRow r = srlxn::q_row(q, qn, a.reward[b], a.not_term[b], a.total_reward[b], c.discount, c.coeff, c.inv_b);
+    a.q[b] = q, a.target[b] = r.target;
+    rows[b] = r.huber, rows[max_batch + b] = r.align;
+    dlast_q[b] = r.dq;
+}
+
+// d loss / d (head outputs) from d loss / d action `ga` [B][kHeadCols], the actions `act` [B][A] they belong to, the head rows and noise plane 1.  The columns of
+// dlast_p no head writes stay the zeros srlx_notsac_create left.
+SRLXG_KERNEL void __launch_bounds__(kRowThreads) k_notsac_gemm_head_grad(i64 B, const float *__restrict__ ga, const float *__restrict__ act, const float *__restrict__ z,
+                                                                        const float *__restrict__ noise, float *__restrict__ dlast_p, float ls_lo, float ls_hi,
+                                                                        int squashed, int A, int normal) {
+    const i64 p = (i64)blockIdx.x * kRowThreads + threadIdx.x;
+    if (normal) {
+        if (p >= B * A) return;
+        const i64 r = p / A;
+        const int j = (int)(p % A);
+        float dloc, dls;
+        srlxn::normal_action_grad(ga[r * kHeadCols + j], act[p], z[r * kHeadCols + kNormalLs + j], ls_lo, ls_hi, noise[p], squashed, dloc, dls);
+        dlast_p[r * kHeadCols + j] = dloc, dlast_p[r * kHeadCols + kNormalLs + j] = dls;
+        return;
+    }
+    if (p >= B) return;
+    srlxn::softmax_grad(act + p * A, ga + p * kHeadCols, A, dlast_p + p * kHeadCols);
+}
+
 int check_shape(const char *who, int D, int head, int A, int np, const int *pw, int nq, const int *qw, int E, i64 max_batch) {
     SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
     SRLX_REQUIRE(head == 0 || head == 1, "%s: head kind %d (0 Gumbel, 1 Normal)", who, head);
@@ -431,6 +591,121 @@ int upload_table(srlx_notsac *h) {
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     h->ps.table_ok = true;
+    h->gemm_ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
+    return SRLX_OK;
+}
+
+// The gemm path's plan: every Linear with a reduction length worth a tile is one job, jobs of equal depth share a launch, the pointwise kernels
+// stand between them.  The planes, and the layout upload_table hands to the tail, are the row path's; what the row path keeps in LDS only (the s' rows, the
+// head rows, d loss / d action) goes through the path's own scratch, allocated at its first call.
+int upload_gemm(srlx_notsac *h) {
+    using srlxg::Job;
+    const i64 mb = h->max_batch, plane = mb * h->wmax;
+    const int D = h->D, A = h->A, E = h->E, Lp = h->Lp, Lq = h->Lq, W = D + E;
+    if (!h->gemm_scratch) {
+        const size_t bytes = sizeof(float) * (size_t)(2 * plane + mb * W + 2 * mb * kHeadCols + 2 * mb);
+        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, bytes));
+        SRLX_HIP(hipMemset(h->gemm_scratch, 0, bytes));
+        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
+    }
+    float *sp[2] = {h->gemm_scratch, h->gemm_scratch + plane};
+    float *xcat2 = h->gemm_scratch + 2 * plane, *z = xcat2 + mb * W, *ga = z + mb * kHeadCols, *qv = ga + mb * kHeadCols;
+    Job jobs[kGemmJobs];
+    memset(jobs, 0, sizeof(jobs));
+    int nj = 0, ns = 0;
+    float *const *P = h->ps.p, *const *Q = h->ps.p + h->ntp;  // Q: act_block, q_block's layers, q_out
+    auto point = [&](int kind) { h->plan[ns++] = Step{kind, srlxg::Launch{0, 0, 0, 0}}; };
+    auto begin = [&](int bwd) { h->plan[ns] = Step{bwd ? kBwd : kFwd, srlxg::Launch{nj, 0, 0, bwd}}; };
+    auto add = [&](int width) -> Job & {  // (width: the columns the job writes)
+        srlxg::Launch &l = h->plan[ns].l;
+        l.njobs++, l.nmax = width > l.nmax ? width : l.nmax;
+        return jobs[nj++];
+    };
+    auto fwd = [&](const float *x, int sel, int K, float *const *lin, int N, float *y, int ldy, int relu) {
+        Job &j = add(N);
+        j.s[0] = srlxg::Src{x, K, sel, lin[0], K};
+        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = ldy, j.relu = relu;
+    };
+    auto bwd = [&](float *y, int ldy, const float *aux, int N, int width, int epi) -> Job & {
+        Job &j = add(width);
+        j.nsrc = 0, j.N = N, j.aux = aux, j.y = y, j.ldy = ldy, j.relu = epi;
+        return j;
+    };
+    auto src = [&](Job &j, const float *a, int lda, int n, const float *w) { j.s[j.nsrc++] = srlxg::Src{a, lda, srlxg::kFromJob, w, n}; };
+    // the policy's hidden layers and head on the rows of launch argument `sel`: kept in hp's planes, or through the two scratch planes in turn
+    auto plan_policy = [&](int sel, bool keep) {
+        const float *x = nullptr;
+        int in = D;
+        for (int l = 0; l < Lp; in = h->Wp[l], l++, ns++) {
+            float *y = keep ? h->hp + l * plane : sp[l & 1];
+            begin(0);
+            fwd(x, l ? srlxg::kFromJob : sel, in, P + 2 * l, h->Wp[l], y, h->Wp[l], 1);
+            x = y;
+        }
+        begin(0);
+        fwd(x, 0, in, P + 2 * Lp, A, z, kHeadCols, 0);
+        if (h->head) fwd(x, 0, in, P + 2 * (Lp + 1), A, z + kNormalLs, kHeadCols, 0);
+        ns++;
+    };
+    // q_block and q_out on the kept rows (xcat -> hq's planes -> q_kept) and, `both`, on the s' rows (xcat2 -> the scratch planes -> qv[0])
+    auto plan_q = [&](bool both, float *q_kept) {
+        const float *x = h->xcat, *x2 = xcat2;
+        int in = W;
+        for (int l = 0; l < Lq; in = h->Wq[l], l++, ns++) {
+            begin(0);
+            fwd(x, 0, in, Q + 2 + 2 * l, h->Wq[l], h->hq + l * plane, h->Wq[l], 1);
+            if (both) fwd(x2, 0, in, Q + 2 + 2 * l, h->Wq[l], sp[l & 1], h->Wq[l], 1);
+            x = h->hq + l * plane, x2 = sp[l & 1];
+        }
+        begin(0);
+        fwd(x, 0, in, Q + 2 + 2 * Lq, 1, q_kept, 1, 0);
+        if (both) fwd(x2, 0, in, Q + 2 + 2 * Lq, 1, qv, 1, 0);
+        ns++;
+    };
+    // from dlast_q down q_block (the masks of hq's planes, into dhq's), then through the embedding columns of its first weight and the SiLU derivative into dact
+    auto plan_q_back = [&]() {
+        for (int l = Lq - 1; l >= 0; l--, ns++) {
+            begin(1);
+            Job &j = bwd(h->dhq + l * plane, h->Wq[l], h->hq + l * plane, h->Wq[l], h->Wq[l], kEpiRelu);
+            if (l == Lq - 1) src(j, h->dlast_q, 1, 1, Q[2 + 2 * Lq]);
+            else src(j, h->dhq + (l + 1) * plane, h->Wq[l + 1], h->Wq[l + 1], Q[2 + 2 * (l + 1)]);
+        }
+        begin(1);
+        src(bwd(h->dact, E, h->zact, W, E, kEpiSilu), h->dhq, h->Wq[0], h->Wq[0], Q[2]);
+        ns++;
+    };
+    // ---- the target half and the Q step
+    plan_policy(srlxg::kArg1, false);
+    point(kNextAction);
+    point(kEmbedBoth);
+    plan_q(true, qv + mb);
+    point(kQLoss);
+    plan_q_back();
+    point(kTailQ);
+    // ---- the policy half, through the Q-network as it stands now: its planes, xcat, zact and dact are free again
+    plan_policy(srlxg::kArg0, true);
+    point(kPiAction);
+    point(kEmbedOne);
+    plan_q(false, h->rows + 2 * mb);
+    plan_q_back();
+    begin(1);
+    src(bwd(ga, kHeadCols, nullptr, A, A, kEpiNone), h->dact, E, E, Q[0]);
+    ns++;
+    point(kHeadGrad);
+    for (int l = Lp - 1; l >= 0; l--, ns++) {
+        begin(1);
+        Job &j = bwd(h->dhp + l * plane, h->Wp[l], h->hp + l * plane, h->Wp[l], h->Wp[l], kEpiRelu);
+        if (l < Lp - 1) {
+            src(j, h->dhp + (l + 1) * plane, h->Wp[l + 1], h->Wp[l + 1], P[2 * (l + 1)]);
+            continue;
+        }
+        src(j, h->dlast_p, kHeadCols, A, P[2 * Lp]);  // SumSeed's order: the head, then the log-scale head
+        if (h->head) src(j, h->dlast_p + kNormalLs, kHeadCols, A, P[2 * (Lp + 1)]);
+    }
+    point(kTailP);
+    h->n_steps = ns;  // (at most 16 + 20 steps and 17 + 17 jobs, at three layers everywhere and a Normal head)
+    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
+    h->gemm_ok = true;
     return SRLX_OK;
 }
 
@@ -455,6 +730,109 @@ int rows_per_workgroup(const srlx_notsac *h, i64 n) { return h->rpw ? h->rpw : s
 i64 scratch_floats(const srlx_notsac *h) {
     const i64 mb = h->max_batch, blocks = h->blocks_p > h->blocks_q ? h->blocks_p : h->blocks_q;
     return 12 * mb * h->wmax + mb * (h->D + h->E) + 2 * mb * h->E + mb * h->A + mb + mb * kHeadCols + 3 * mb + 2 * blocks;
+}
+
+// srlx_notsac_update (gemm = false: the two row kernels) and srlx_notsac_update_gemm (upload_gemm's plan): one contract, one set of planes, one gradient, clip
+// and Adam tail behind each half.  `who` names the entry point in every message.
+int update(const char *who, bool gemm, srlx_notsac *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_rewards,
+           const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff, double max_grad_norm,
+           int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action, float *d_pi_action, float *d_scalars,
+           void *stream) {
+    SRLX_REQUIRE(h, "%s: NULL handle", who);
+    SRLX_REQUIRE(h->ps.ready(), "%s: bind the parameters, the gradient tensors and the Adam state first", who);
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "%s: batch %lld (handle sized for %lld)", who, (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_states && d_next_states && d_actions && d_rewards && d_not_terminated && d_total_rewards && d_noise && d_q && d_target_q && d_next_action &&
+                     d_pi_action && d_scalars,
+                 "%s: NULL argument", who);
+    SRLX_REQUIRE(lr >= 0 && max_grad_norm > 0, "%s: lr is non-negative, max_grad_norm positive", who);
+    SRLX_REQUIRE(squashed == 0 || squashed == 1, "%s: squashed is 0 or 1", who);
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "%s: the log-scale clamp's ends are ordered", who);
+    srlx::DeviceGuard g(h->device);
+    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
+    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
+    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
+    hipStream_t st = (hipStream_t)stream;
+    const double inv_b = 1.0 / (double)batch;
+    const Cfg c{(float)discount, (float)loss_align_coeff, (float)log_scale_lo, (float)log_scale_hi, inv_b, squashed};
+    const Batch b{(i64)batch, d_states, d_next_states, d_rewards, d_not_terminated, d_total_rewards, h->head ? nullptr : (const int32_t *)d_actions,
+                  h->head ? (const float *)d_actions : nullptr, d_noise, d_q, d_target_q, d_next_action, d_pi_action};
+    const Seg *segs_p = h->d_segs, *segs_q = h->d_segs + kNetTensors;
+    // the tail of each half: the network's gradient before the clip with its loss sums, then the norm, the clip and Adam
+    auto tail_q = [&]() {
+        const GradArgs gq{segs_q, h->ntq, d_states, h->partials, LossSums{2, (i64)batch, h->rows, h->max_batch, inv_b, d_scalars}};
+        hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_q), dim3(kThreads), 0, st, gq);
+        const srlxt::StepArgs sq = h->ps.step_args(segs_q, h->ntq, h->partials, h->blocks_q, max_grad_norm, lr, d_scalars + 3);
+        hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_q + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sq);
+    };
+    auto tail_p = [&]() {
+        const GradArgs gp{segs_p, h->ntp, d_states, h->partials, LossSums{1, (i64)batch, h->rows + 2 * h->max_batch, h->max_batch, -inv_b, d_scalars + 2}};
+        hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_p), dim3(kThreads), 0, st, gp);
+        const srlxt::StepArgs sp = h->ps.step_args(segs_p, h->ntp, h->partials, h->blocks_p, max_grad_norm, lr, d_scalars + 4);
+        hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_p + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sp);
+    };
+    if (!gemm) {
+        const Work w{h->hp, h->dhp, h->hq, h->dhq, h->xcat, h->zact, h->dact, h->ain, h->dlast_q, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
+        const RowArgs ra{b, w, c};
+        const int rpw = rows_per_workgroup(h, batch);
+        const dim3 row_grid((unsigned)((batch + rpw - 1) / rpw));
+        // ---- the Q step
+        hipLaunchKernelGGL(k_notsac_q_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
+        tail_q();
+        // ---- the policy step, through the Q-network as it stands now
+        hipLaunchKernelGGL(k_notsac_pi_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
+        tail_p();
+    } else {
+        const i64 mb = h->max_batch, plane = mb * h->wmax;
+        const int D = h->D, A = h->A, E = h->E, W = D + E, M = (int)batch;
+        float *xcat2 = h->gemm_scratch + 2 * plane, *z = xcat2 + mb * W, *ga = z + mb * kHeadCols, *qv = ga + mb * kHeadCols;  // (upload_gemm's layout)
+        const float *wa = h->ps.p[h->ntp], *ba = h->ps.p[h->ntp + 1];
+        const i64 heads = h->head ? batch * A : batch;  // threads of the kernels that run one per row and element (Normal) or per row (Gumbel)
+        const dim3 head_grid((unsigned)((heads + kRowThreads - 1) / kRowThreads)), row_grid((unsigned)((batch + kRowThreads - 1) / kRowThreads));
+        const unsigned embed_blocks = (unsigned)((batch * W + kThreads - 1) / kThreads);
+        const EmbedSet kept{d_states, h->ain, h->xcat, h->zact}, next{d_next_states, d_next_action, xcat2, nullptr};
+        for (int i = 0; i < h->n_steps; i++) {
+            const Step &s = h->plan[i];
+            switch (s.kind) {
+            case kFwd:
+                srlxg::launch(s.l, h->d_jobs, M, d_states, d_next_states, st);
+                break;
+            case kBwd:
+                hipLaunchKernelGGL(k_notsac_gemm_bwd, dim3((unsigned)((s.l.nmax + srlxg::kTile - 1) / srlxg::kTile), (unsigned)((M + srlxg::kTile - 1) / srlxg::kTile),
+                                                           (unsigned)s.l.njobs),
+                                   dim3(srlxg::kThreads), 0, st, (const srlxg::Job *)h->d_jobs + s.l.first, M, D);
+                break;
+            case kNextAction:
+                hipLaunchKernelGGL(k_notsac_gemm_action, head_grid, dim3(kRowThreads), 0, st,
+                                   ActionArgs{(i64)batch, z, d_noise, d_next_action, h->ain, h->dlast_q, b.action_i, b.action_f, c.ls_lo, c.ls_hi, 0.f, squashed, A, h->head, 0});
+                break;
+            case kPiAction:
+                hipLaunchKernelGGL(k_notsac_gemm_action, head_grid, dim3(kRowThreads), 0, st,
+                                   ActionArgs{(i64)batch, z, d_noise + batch * A, d_pi_action, h->ain, h->dlast_q, nullptr, nullptr, c.ls_lo, c.ls_hi, (float)(-inv_b),
+                                              squashed, A, h->head, 1});
+                break;
+            case kEmbedBoth:
+            case kEmbedOne:
+                hipLaunchKernelGGL(k_notsac_gemm_embed, dim3(embed_blocks, s.kind == kEmbedBoth ? 2u : 1u), dim3(kThreads), 0, st, kept, next, (i64)batch, wa, ba, D, A, E);
+                break;
+            case kQLoss:
+                hipLaunchKernelGGL(k_notsac_gemm_q_loss, row_grid, dim3(kRowThreads), 0, st, b, (const float *)qv, h->rows, h->dlast_q, mb, c);
+                break;
+            case kHeadGrad:
+                hipLaunchKernelGGL(k_notsac_gemm_head_grad, head_grid, dim3(kRowThreads), 0, st, (i64)batch, (const float *)ga, (const float *)d_pi_action, (const float *)z,
+                                   d_noise + batch * A, h->dlast_p, c.ls_lo, c.ls_hi, squashed, A, h->head);
+                break;
+            case kTailQ:
+                tail_q();
+                break;
+            case kTailP:
+                tail_p();
+                break;
+            }
+        }
+    }
+    SRLX_HIP(hipGetLastError());
+    h->ps.steps++;
+    return SRLX_OK;
 }
 
 }  // namespace
@@ -511,7 +889,7 @@ int srlx_notsac_destroy(srlx_notsac_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
     for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->hp, (void *)h->dhp, (void *)h->hq, (void *)h->dhq, (void *)h->xcat, (void *)h->zact, (void *)h->dact,
-                    (void *)h->ain, (void *)h->dlast_q, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials})
+                    (void *)h->ain, (void *)h->dlast_q, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials, (void *)h->gemm_scratch, (void *)h->d_jobs})
         if (p) (void)hipFree(p);
     delete h;
     return SRLX_OK;
@@ -574,43 +952,16 @@ int srlx_notsac_update(srlx_notsac_t *h, int64_t batch, const float *d_states, c
                        const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff,
                        double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
                        float *d_pi_action, float *d_scalars, void *stream) {
-    SRLX_REQUIRE(h, "notsac_update: NULL handle");
-    SRLX_REQUIRE(h->ps.ready(), "notsac_update: bind the parameters, the gradient tensors and the Adam state first");
-    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "notsac_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
-    SRLX_REQUIRE(d_states && d_next_states && d_actions && d_rewards && d_not_terminated && d_total_rewards && d_noise && d_q && d_target_q && d_next_action &&
-                     d_pi_action && d_scalars,
-                 "notsac_update: NULL argument");
-    SRLX_REQUIRE(lr >= 0 && max_grad_norm > 0, "notsac_update: lr is non-negative, max_grad_norm positive");
-    SRLX_REQUIRE(squashed == 0 || squashed == 1, "notsac_update: squashed is 0 or 1");
-    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "notsac_update: the log-scale clamp's ends are ordered");
-    srlx::DeviceGuard g(h->device);
-    if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
-    if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
-    hipStream_t st = (hipStream_t)stream;
-    const double inv_b = 1.0 / (double)batch;
-    const Cfg c{(float)discount, (float)loss_align_coeff, (float)log_scale_lo, (float)log_scale_hi, inv_b, squashed};
-    const Batch b{(i64)batch, d_states, d_next_states, d_rewards, d_not_terminated, d_total_rewards, h->head ? nullptr : (const int32_t *)d_actions,
-                  h->head ? (const float *)d_actions : nullptr, d_noise, d_q, d_target_q, d_next_action, d_pi_action};
-    const Work w{h->hp, h->dhp, h->hq, h->dhq, h->xcat, h->zact, h->dact, h->ain, h->dlast_q, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
-    const RowArgs ra{b, w, c};
-    const int rpw = rows_per_workgroup(h, batch);
-    const dim3 row_grid((unsigned)((batch + rpw - 1) / rpw));
-    const Seg *segs_p = h->d_segs, *segs_q = h->d_segs + kNetTensors;
-    // ---- the Q step
-    hipLaunchKernelGGL(k_notsac_q_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
-    const GradArgs gq{segs_q, h->ntq, d_states, h->partials, LossSums{2, (i64)batch, h->rows, h->max_batch, inv_b, d_scalars}};
-    hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_q), dim3(kThreads), 0, st, gq);
-    const srlxt::StepArgs sq = h->ps.step_args(segs_q, h->ntq, h->partials, h->blocks_q, max_grad_norm, lr, d_scalars + 3);
-    hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_q + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sq);
-    // ---- the policy step, through the Q-network as it stands now
-    hipLaunchKernelGGL(k_notsac_pi_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
-    const GradArgs gp{segs_p, h->ntp, d_states, h->partials, LossSums{1, (i64)batch, h->rows + 2 * h->max_batch, h->max_batch, -inv_b, d_scalars + 2}};
-    hipLaunchKernelGGL(k_notsac_grad, dim3((unsigned)h->blocks_p), dim3(kThreads), 0, st, gp);
-    const srlxt::StepArgs sp = h->ps.step_args(segs_p, h->ntp, h->partials, h->blocks_p, max_grad_norm, lr, d_scalars + 4);
-    hipLaunchKernelGGL(k_notsac_step, dim3((unsigned)((h->elements_p + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sp);
-    SRLX_HIP(hipGetLastError());
-    h->ps.steps++;
-    return SRLX_OK;
+    return update("notsac_update", false, h, batch, d_states, d_next_states, d_actions, d_rewards, d_not_terminated, d_total_rewards, d_noise, lr, discount,
+                  loss_align_coeff, max_grad_norm, squashed, log_scale_lo, log_scale_hi, d_q, d_target_q, d_next_action, d_pi_action, d_scalars, stream);
+}
+
+int srlx_notsac_update_gemm(srlx_notsac_t *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_rewards,
+                            const float *d_not_terminated, const float *d_total_rewards, const float *d_noise, double lr, double discount, double loss_align_coeff,
+                            double max_grad_norm, int squashed, double log_scale_lo, double log_scale_hi, float *d_q, float *d_target_q, float *d_next_action,
+                            float *d_pi_action, float *d_scalars, void *stream) {
+    return update("notsac_update_gemm", true, h, batch, d_states, d_next_states, d_actions, d_rewards, d_not_terminated, d_total_rewards, d_noise, lr, discount,
+                  loss_align_coeff, max_grad_norm, squashed, log_scale_lo, log_scale_hi, d_q, d_target_q, d_next_action, d_pi_action, d_scalars, stream);
 }
 
 }  // extern "C"

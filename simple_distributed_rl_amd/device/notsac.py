@@ -1,7 +1,8 @@
 """NoT_SAC's update on libsrlx (csrc/srlx_notsac.hip): `NotSacUpdate` binds an `algorithms.sac_not.Parameter`'s own tensors by address -- the two
 networks stay what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after each
 network's norm clip) and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:150-189 for one batch and one
-noise tensor, in six launches."""
+noise tensor, in six launches; `update(..., gemm=True)` is the same step layer by layer on the float64 matrix cores (srlx_notsac_update_gemm), the
+path for wide layers and full batches."""
 import ctypes
 
 import torch
@@ -93,10 +94,13 @@ class NotSacUpdate(R.RowUpdate):
         """The row kernels' launch shape: 1, 2, 4, 8 or 16 rows per workgroup, 0 for the default (one row per workgroup for every update).  Never changes a bit."""
         N.check(self._lib.srlx_notsac_set_rows_per_workgroup(self._h, int(rows)))
 
-    def update(self, state, next_state, action, reward, not_terminated, total_reward, noise, lr, discount, loss_align_coeff, max_grad_norm, squashed: bool) -> dict:
+    def update(self, state, next_state, action, reward, not_terminated, total_reward, noise, lr, discount, loss_align_coeff, max_grad_norm, squashed: bool,
+               gemm: bool = False) -> dict:
         """state / next_state f32 [B][D]; action i32 [B] (Gumbel: the index of the stored one-hot's maximum) or f32 [B][K] (Normal); reward, not_terminated,
         total_reward f32 [B]; noise f32 [2][B][n_out]; all on the device.  Returns q, target_q [B], next_action, pi_action [B][n_out] and `scalars` [5] (loss_q,
-        loss_q_align, loss_policy, the Q-network's and the policy's gradient norm before their clips), device tensors; nothing synchronises."""
+        loss_q_align, loss_policy, the Q-network's and the policy's gradient norm before their clips), device tensors; nothing synchronises.  `gemm`: the layer-wise
+        path on the float64 matrix cores; the two paths share the handle's planes, gradient tensors and Adam state, so one NotSacUpdate may alternate them
+        between updates."""
         B = state.shape[0]
         if B > self.max_batch:
             raise ValueError(f"NotSacUpdate: batch size {B} above max_batch {self.max_batch}")
@@ -107,9 +111,10 @@ class NotSacUpdate(R.RowUpdate):
         f = dict(dtype=torch.float32, device=self.device)
         out = {"q": torch.empty(B, **f), "target_q": torch.empty(B, **f), "next_action": torch.empty((B, self.n_out), **f),
                "pi_action": torch.empty((B, self.n_out), **f), "scalars": torch.empty(5, **f)}
-        N.check(self._lib.srlx_notsac_update(self._h, B, *[N.tptr(t) for t in keep], float(lr), float(discount), float(loss_align_coeff), float(max_grad_norm),
-                                             int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(out["q"]), N.tptr(out["target_q"]), N.tptr(out["next_action"]),
-                                             N.tptr(out["pi_action"]), N.tptr(out["scalars"]), N.torch_stream_ptr()))
+        call = self._lib.srlx_notsac_update_gemm if gemm else self._lib.srlx_notsac_update
+        N.check(call(self._h, B, *[N.tptr(t) for t in keep], float(lr), float(discount), float(loss_align_coeff), float(max_grad_norm), int(bool(squashed)), self.ls_lo,
+                     self.ls_hi, N.tptr(out["q"]), N.tptr(out["target_q"]), N.tptr(out["next_action"]), N.tptr(out["pi_action"]), N.tptr(out["scalars"]),
+                     N.torch_stream_ptr()))
         self._keep = keep
         return out
 

@@ -1,19 +1,22 @@
-"""Probe: NoT_SAC's Trainer.train() on libsrlx's fused update ("srlx") next to the plain torch backend ("torch"), the measurement that decides
-sac_not.Trainer.update_backend's default.
+"""Probe: NoT_SAC's Trainer.train() on libsrlx's fused update ("srlx"), on its layer-wise update on the float64 matrix cores ("srlx_gemm") and on the
+plain torch backend ("torch"): the measurement that decides sac_not.Trainer.update_backend's default and says on which side of the row path a shape
+falls.
 
-    python tools/notsac_probe.py --out profiles/notsac_probe.json
-    rocprofv3 --kernel-trace --stats -d DIR -o notsac --output-format csv -- python tools/notsac_probe.py --trace-loop     # a run of its own, no counters
+    python tools/notsac_probe.py --out profiles/notsac_gemm_probe.json
+    rocprofv3 --kernel-trace --stats -d DIR -o notsac --output-format csv -- python tools/notsac_probe.py --trace-loop [--shape large]   # a run of its own, no counters
 
-Both arms run in ONE process.  Per shape: one untimed train() of each arm (allocation, the handle, torch's lazy initialisation), then three interleaved rounds
-(srlx, torch, srlx, torch, ...) of CALLS whole train() calls each -- host batch assembly from a memory that hands out one fixed batch, the noise draw, the
+All arms run in ONE process.  Per shape: one untimed train() of each arm (allocation, the handle, torch's lazy initialisation), then three interleaved rounds
+(srlx, srlx_gemm, torch, srlx, ...) of CALLS whole train() calls each -- host batch assembly from a memory that hands out one fixed batch, the noise draw, the
 update, and the `info` read that synchronises -- every round ending in a device synchronise.  The figure is milliseconds per train().
   pendulum  sac_not.Config() on Pendulum-v1: B 64, D 3, Normal K 1, policy 512, q 512, act_emb 64
   cartpole  sac_not.Config() on CartPole-v1: B 64, D 4, Gumbel A 2, policy 512, q 512, act_emb 64
+  b64-w256  B 64, D 3, Normal K 1, policy 256, q 256, act_emb 64
+  b256-w128 B 256, D 3, Normal K 1, policy 128, q 128, act_emb 64
   large     B 256, D 256, Normal K 8, policy 512-512-512, q 512-512-512, act_emb 256: the envelope's largest corner
 pendulum_rows16 and large_rows16 repeat two of them with the row kernels at 16 rows per workgroup (srlx_notsac_set_rows_per_workgroup) in place of the default.
 The default rule: "srlx" iff pendulum.srlx_ms_mean <= 1.10 * pendulum.torch_ms_mean of the same run.
---trace-loop runs, at the pendulum shape, one train() of each arm and then TRACE_CALLS of "srlx" followed by TRACE_CALLS of "torch": a kernel trace of it
-gives the launches per train() of each arm (the libsrlx kernels are named k_notsac_*; everything else is torch's)."""
+--trace-loop runs, at --shape, one train() of each arm and then TRACE_CALLS of each arm in turn: a kernel trace of it gives the launches and the kernel time
+per train() of each arm (the libsrlx kernels are named k_notsac_* and k_mlp_gemm_*; everything else is torch's)."""
 import argparse
 import json
 import os
@@ -25,8 +28,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 CALLS, TRACE_CALLS = 200, 100
 # B, D, head, n_out, policy, q, act_emb
-SHAPES = dict(pendulum=(64, 3, 1, 1, (512,), (512,), 64), cartpole=(64, 4, 0, 2, (512,), (512,), 64),
-              large=(256, 256, 1, 8, (512, 512, 512), (512, 512, 512), 256))
+SHAPES = {"pendulum": (64, 3, 1, 1, (512,), (512,), 64), "cartpole": (64, 4, 0, 2, (512,), (512,), 64), "b64-w256": (64, 3, 1, 1, (256,), (256,), 64),
+          "b256-w128": (256, 3, 1, 1, (128,), (128,), 64), "large": (256, 256, 1, 8, (512, 512, 512), (512, 512, 512), 256)}
+ARMS = ("srlx", "srlx_gemm", "torch")
 
 
 class _FixedMemory:
@@ -75,7 +79,7 @@ def _loop(tr, calls):
 
 
 def measure(shape, rpw=0):
-    arms = {a: _trainer(shape, a, rpw) for a in ("srlx", "torch")}
+    arms = {a: _trainer(shape, a, rpw) for a in ARMS}
     for a, tr in arms.items():
         tr.train()
         assert tr.update_path == a, (a, tr.update_path, tr.why_not_srlx_update)
@@ -89,6 +93,10 @@ def measure(shape, rpw=0):
     res.update({a + "_ms": r for a, r in runs.items()})
     res.update({a + "_ms_mean": sum(r) / len(r) for a, r in runs.items()})
     res["srlx_over_torch"] = res["srlx_ms_mean"] / res["torch_ms_mean"]
+    res["gemm_over_srlx_by_round"] = [g / r for g, r in zip(runs["srlx_gemm"], runs["srlx"])]
+    res["gemm_over_torch_by_round"] = [g / t for g, t in zip(runs["srlx_gemm"], runs["torch"])]
+    res["gemm_side_of_row_path"] = "faster" if all(x < 1 for x in res["gemm_over_srlx_by_round"]) else (
+        "slower" if all(x > 1 for x in res["gemm_over_srlx_by_round"]) else "within the rounds' spread")
     res["updates_per_s"] = {a: 1e3 / res[a + "_ms_mean"] for a in arms}
     return res
 
@@ -97,16 +105,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "notsac_probe.json"))
     ap.add_argument("--trace-loop", action="store_true")
+    ap.add_argument("--shape", default="pendulum", choices=list(SHAPES), help="the shape of --trace-loop")
     args = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
     if args.trace_loop:
-        for a in ("srlx", "torch"):
-            tr = _trainer("pendulum", a)
+        for a in ARMS:
+            tr = _trainer(args.shape, a)
             tr.train()
             _loop(tr, TRACE_CALLS)
-        print(f"trace loop: 1 + {TRACE_CALLS} train() calls per arm at the pendulum shape")
+        print(f"trace loop: 1 + {TRACE_CALLS} train() calls per arm at the {args.shape} shape")
         return
     t0 = time.time()
     from simple_distributed_rl_amd import _native as N
@@ -114,7 +123,7 @@ def main():
     out = dict(device=N.device_info(0), torch=torch.__version__)
     for shape in SHAPES:
         out[shape] = measure(shape)
-        print(shape, {k: out[shape][k] for k in ("srlx_ms_mean", "torch_ms_mean", "srlx_over_torch")}, flush=True)
+        print(shape, {k: out[shape][k] for k in ("srlx_ms", "srlx_gemm_ms", "torch_ms", "gemm_side_of_row_path")}, flush=True)
     for shape in ("pendulum", "large"):  # the same arms with the row kernels at 16 rows per workgroup (B / 16 workgroups): what the default launch shape buys
         key = shape + "_rows16"
         out[key] = measure(shape, 16)
