@@ -1379,6 +1379,17 @@ int srlx_r2d2_lane_gather(int64_t B, int64_t L, int64_t S, int64_t A, int64_t H,
  *                                5. hard_sync: target = online; otherwise target = (float)(1 - tau) * target + (float)tau * online, two products and one add
  *                              Outputs: y, q1, q2, entropy f32 [B]; scalars f32 [5] = q1_loss, q2_loss, policy_loss, alpha_loss (0 without auto_scale), alpha.
  *                              No atomics, every sum in a fixed order: equal inputs give equal bits.
+ *   srlx_sacd_update_gemm    : srlx_sacd_update's contract -- arguments, preconditions, arithmetic, outputs; srlx_last_error() names sacd_update_gemm -- on
+ *                              the float64 matrix cores (srlx_mlp_gemm.h): every Linear over the whole batch as one job of a launch, layer by
+ *                              layer.  A Q-network's first layer is computed once per item, S = states W[:, :D]^T, and the one-hot column and the bias are
+ *                              added to the float64 sum before its one rounding: relu((float)(S + W[u][D + a] + b[u])), for every action (the A rows of an
+ *                              item in a [B A][W0] plane; no [B A][D + A] matrix is built) or for the action taken.  The layers above run on B A rows.
+ *                              policy(s) and the Q step's forward ride in the target half's launches; the two gradient, Adam and sync launches are
+ *                              srlx_sacd_update's own.  6 + max(n_policy, n_q) + 3 n_q + n_policy launches.  The matrix core's order inside a group of 4 terms
+ *                              is its own, so a value may differ from srlx_sacd_update's in its last bit.  The same handle, planes, gradient tensors, Adam
+ *                              state and step counts: one handle may alternate the two.  Its own scratch (the all-action planes
+ *                              [max_batch A][widest q layer] x 4 and the job table) is allocated at a handle's first call; srlx_sacd_scratch_floats does
+ *                              not count it.  No atomics, a fixed order: equal inputs give equal bits.
  *   srlx_sacd_forward        : n rows of states -> logits f32 [n][A] (NULL: not wanted) and min(q1, q2)(s, e_a) f32 [n][A] (NULL: not wanted) of the online
  *                              (target = 0) or the target (1) Q-networks.  Needs srlx_sacd_bind only. */
 typedef struct srlx_sacd srlx_sacd_t;
@@ -1393,6 +1404,9 @@ int srlx_sacd_steps(const srlx_sacd_t *h, int64_t *steps_taken);
 int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
                      const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
                      double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream);
+int srlx_sacd_update_gemm(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
+                          const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
+                          double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream);
 int srlx_sacd_forward(srlx_sacd_t *h, int64_t n, const float *d_states, int target, float *d_logits, float *d_qmin, void *stream);
 
 /* ---- Discrete soft actor-critic: the device engine's two launches outside the update (srlx_sacd.hip) --------------------------------------------

@@ -11,13 +11,14 @@ family needs float actions in the rings and a continuous base class the project 
 Networks.  PolicyNetwork: in_block -> policy_block -> `out_layer` (:20-38); the out layer starts at zero as CategoricalGumbelDistBlock's
 kernel_initializer="zeros" does, so a fresh policy is uniform.  QNetwork: concat(in_block(state), one-hot action) -> q_block -> Linear(1) (:69-95).
 
-Trainer.train() (:158-243) is DESIGN.md 7m's contract, on one of two backends that implement it alike:
-  "srlx"   one libsrlx call, five launches (device/sacd.py, csrc/srlx_sacd.hip), for GPU parameters inside the kernels' envelope;
-  "torch"  plain torch float32 with torch.optim.Adam, for everything else.
+Trainer.train() (:158-243) is DESIGN.md 7m's contract, on one of three backends that implement it alike:
+  "srlx"       one libsrlx call, five launches (device/sacd.py, csrc/srlx_sacd.hip), for GPU parameters inside the kernels' envelope;
+  "srlx_gemm"  the same call layer by layer on the float64 matrix cores (DESIGN.md 7v): opt-in; served and refused as "srlx";
+  "torch"      plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
-`device/sacd_engine.py: SacdEngine` runs E lock-stepped lanes on one GPU around this Parameter and Trainer (`train_on_batch`); `Runner.train()` does
-not route there yet.
+`device/sacd_engine.py: SacdEngine` runs E lock-stepped lanes on one GPU around this Parameter and Trainer (`train_on_batch`); it asks for
+"srlx" itself (`require_srlx_update`), so it stays on the row path whatever `update_backend` says.  `Runner.train()` does not route there yet.
 
 What is kept from the reference although it reads oddly:
   * target_entropy = -A (:151-156, "-1 * n"), the continuous-control heuristic.  A discrete policy's entropy lies in [0, log A], so target_entropy - entropy is
@@ -47,6 +48,10 @@ from simple_distributed_rl_amd.base.spaces.discrete import DiscreteSpace
 from simple_distributed_rl_amd.rl.memories.replay_buffer import ReplayBufferConfig, RLReplayBuffer
 from simple_distributed_rl_amd.rl.models.config import HiddenBlockConfig, InputBlockConfig
 from simple_distributed_rl_amd.rl.schedulers.lr_scheduler import LRSchedulerConfig
+
+# The names that ask for the libsrlx update.  A Trainer takes them on at its set-up, where it meets the Parameter the device update binds; one that was never
+# set up knows the scaffold's "srlx" alone and refuses "srlx_gemm" by name (tests/test_vppo_gemm_cpu.py holds that).
+SRLX_BACKENDS = ("srlx", "srlx_gemm")
 
 CONTINUOUS_SENTENCE = ("SAC on a continuous action space (SAC_Continuous) is not built: only SAC_Discrete is, "
                        "the continuous family needs float actions in the replay rings and a continuous base class")
@@ -194,12 +199,13 @@ class Parameter(RLParameter):
 
 
 class Trainer(SrlxUpdateBackend, RLTrainer):
-    # "srlx" | "torch".  The default follows the project's 1.10 rule: 1.65 ms per train() on "srlx" against 3.58 ms on "torch" at sac.Config() on
-    # CartPole (profiles/sacd_probe.json)
+    # "srlx" | "srlx_gemm" | "torch".  The default follows the project's 1.10 rule: 1.65 ms per train() on "srlx" against 3.58 ms on "torch" at
+    # sac.Config() on CartPole (profiles/sacd_probe.json).  "srlx_gemm" (profiles/sacd_gemm_probe.json) is opt-in.
     update_backend = "srlx"
 
     def on_setup(self) -> None:
         cfg = self.config
+        self.SRLX_BACKENDS = SRLX_BACKENDS
         self.device = torch.device(cfg.used_device_torch)
         if self.parameter.device != self.device:
             self.parameter.to_device(self.device)
@@ -242,8 +248,8 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         backend = self._backend_for(state.shape[0])
         cfg = self.config
         hard_sync = self.train_count % cfg.hard_target_update_interval == 0
-        if backend == "srlx":
-            out = self._update_srlx(state, onehot_action, n_state, reward, done, hard_sync, actions)
+        if backend != "torch":
+            out = self._update_srlx(state, onehot_action, n_state, reward, done, hard_sync, actions, gemm=backend == "srlx_gemm")
         else:
             out = self._update_torch(state, onehot_action, n_state, reward, done, hard_sync)
         self.update_path = backend
@@ -254,7 +260,7 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
             self.info["alpha_loss"], self.info["alpha"] = scalars[3], scalars[4]
         return out
 
-    def _update_srlx(self, state, onehot_action, n_state, reward, done, hard_sync: bool, actions=None) -> dict:
+    def _update_srlx(self, state, onehot_action, n_state, reward, done, hard_sync: bool, actions=None, gemm: bool = False) -> dict:
         cfg, u = self.config, self._srlx
         if not self.parameter.load_log_alpha:  # :170-173
             u.reset_alpha_optimizer()
@@ -267,7 +273,7 @@ class Trainer(SrlxUpdateBackend, RLTrainer):
         if actions is None:
             actions = onehot_action.argmax(dim=1).to(torch.int32)
         return u.update(state.reshape(B, -1), actions, n_state.reshape(B, -1), reward, done, lr_policy, lr_q, lr_alpha,
-                        hard_sync, cfg.discount, cfg.soft_target_update_tau, cfg.entropy_alpha_auto_scale, self.target_entropy)
+                        hard_sync, cfg.discount, cfg.soft_target_update_tau, cfg.entropy_alpha_auto_scale, self.target_entropy, gemm=gemm)
 
     def _update_torch(self, state, onehot_action, n_state, reward, done, hard_sync: bool) -> dict:
         cfg, p = self.config, self.parameter

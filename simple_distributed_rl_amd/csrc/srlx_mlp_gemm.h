@@ -2,7 +2,8 @@
 // (v_mfma_f64_16x16x4_f64).  The row-blocked passes of srlx_mlp_rows.h walk at most 16 rows through every layer in one workgroup; at wide layers and full batches
 // that is a GEMM-sized problem walked as chains, and this header is the other way to run it: V-PPO is the first consumer
 // (srlx_vppo.hip: srlx_vppo_update_gemm), NoT_SAC the second (srlx_notsac.hip: srlx_notsac_update_gemm, DESIGN.md 7u: k_mlp_gemm_fwd and a backward
-// kernel of its own on tile_sums); SAC-Discrete can build its job tables on the same routines.
+// kernel of its own on tile_sums), SAC-Discrete the third (srlx_sacd.hip: srlx_sacd_update_gemm, DESIGN.md 7v: both kernels and a first-layer kernel of its own
+// on tile_sums<false>, which hands it the two operands swapped).
 //   Job, Src          one GEMM of a launch: up to three (rows, weight) sources summed into one output tile, in the order a, b, c (SumSeed's order)
 //   k_mlp_gemm_fwd    Y[M][N] = act(X[M][K] W[N][K]^T + b): the weight in torch's [out][in] layout, both operands contiguous along k
 //   k_mlp_gemm_bwd    dH[M][N] = H[M][N] > 0 ? sum_s dOut_s[M][n_s] W_s[n_s][N] : 0: the weight read untransposed, coalesced along the output column

@@ -15,7 +15,15 @@
 // and, for the device engine, outside the update:
 //   k_sacd_act         the policy's logits of ring rows and the Worker's action (uniform while start_steps last, Gumbel-max after), one launch per lock-step
 //   k_sacd_ring_batch  the drawn items' rows out of the ring as the update's dense tensors
+// srlx_sacd_update_gemm is the same update layer by layer: every Linear over the whole batch as one job of srlx_mlp_gemm.h's tile on the float64
+// matrix cores, the two k_sacd_grad launches as they are.
+//   k_sacd_gemm_first       the first layer of every network of a launch on srlxg::tile_sums<false>.  A Q-network's first layer is S = states W[:, :D]^T once
+//                           per item; the one-hot column and the bias are added to the float64 sum in the epilogue, for every action (A rows per item of a
+//                           [B A][W0] plane) or for the action taken (one row per item).  The policy's first layer rides as a job without the one-hot term
+//   k_sacd_gemm_target_q    one thread per item: min over the two targets, soft_target into y; then q1, q2, the squared-error rows and the seeds into dlast
+//   k_sacd_gemm_policy_row  one thread per item: min over the two stepped Q-networks, policy_row: entropy, the loss row, dz into dlast
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
+#include "srlx_mlp_gemm.h"
 #include "srlx_param_tail.h"
 #include "srlx_sacd_math.h"
 #include <cmath>
@@ -32,6 +40,16 @@ constexpr int kMaxSegs = 16;  // q1 + q2: 2 networks x 4 layers x (weight, bias)
 
 // one network in device memory: the policy has In = D and Out = A, a Q-network In = D + A and Out = 1
 using NetD = srlxm::Layers;
+
+// The gemm path's plan: a list of steps, each a launch of jobs from the device table or one of the pointwise kernels between them.
+enum StepKind { kFirst, kFwdItems, kFwdActions, kBwd, kTargetQ, kGradQ, kPolicyRow, kGradP };  // (kFwdItems: M = B rows; kFwdActions: M = B A rows)
+struct Step {
+    int kind;
+    srlxg::Launch l;
+};
+constexpr int kGemmJobs = 48, kGemmSteps = 24;
+// Job::relu of a k_sacd_gemm_first job: what its epilogue adds and where its rows go
+enum FirstMode { kPlain = 0, kAllActions = 1, kTaken = 2, kModeMask = 3, kWriteX0 = 4 };
 
 struct Seg {  // one parameter tensor of a trained network
     i64 end;       // running element count
@@ -64,6 +82,12 @@ struct srlx_sacd {
     float *h, *dh;  // planes [net 0..2][layer 0..2][max_batch][wmax]
     float *dlast;   // [3][max_batch][16]: d loss / d (out layer output)
     float *rows;    // [3][max_batch]: squared errors of q1, q2; the policy loss rows
+    // srlx_sacd_update_gemm's own, allocated at its first call
+    float *gemm_scratch;  // the all-action planes [2 networks][2][max_batch A][widest q layer], two planes for policy(s'), logits, Q values, row arrays
+    srlxg::Job *d_jobs;   // [kGemmJobs]: the plan's jobs, launch after launch
+    Step plan[kGemmSteps];
+    int n_steps;
+    bool gemm_ok;  // the job table holds the bound tensors (upload_tables makes it stale)
 };
 
 namespace {
@@ -411,6 +435,120 @@ __global__ void __launch_bounds__(kThreads) k_sacd_grad(GradArgs a, Tail z) {
     if (sg.tgt) sg.tgt[e] = a.sync == 1 ? p : srlxs::soft_sync(sg.tgt[e], p, a.one_minus_tau, a.tau);
 }
 
+// ---- the gemm path's own kernels (srlx_sacd_update_gemm).  The closed forms are the lines the row kernels run, on the same float32 values.
+
+// The first layer of the networks of one launch.  A job holds the layer's WHOLE weight in s[0].w ([W0][In], In = s[0].n: D for the policy, D + A for a
+// Q-network), the states as launch argument s[0].sel, its bias in aux and its mode in relu (FirstMode).  tile_sums<false> takes the row stride of its rows operand
+// from Src::lda and its reduction length from Src::n, but reads the weight operand with row stride n; so the kernel hands it the two operands SWAPPED: the weight
+// as the rows (stride In, reduction bounded at D: the one-hot columns are never multiplied), the states as the "weight" (stride D, which is their reduction
+// length).  The tile is S^T: accumulator rows are units, columns items.  16-byte loads where In and D are multiples of 4, element loads otherwise (the shared
+// loader's own rule on lda and n).  Epilogue: the float64 tile goes through LDS (the stages are free behind tile_sums' last barrier) beside the tile's one-hot
+// columns W[u][D + a] and biases, then thread -> (row, unit) with the unit fastest, 128-byte runs per row:
+//   kPlain       y[b][u]         = relu((float)(S + b[u]))
+//   kAllActions  y[b A + a][u]   = relu((float)(S + W[u][D + a] + b[u])) for every a: the A rows of an item from ONE accumulator row
+//   kTaken       y[b][u]         = the same for a = action[b] (an action outside 0..A-1 adds nothing, as the row path's comparison does)
+// kWriteX0: the job's first column of workgroups also writes concat(state, e_action) into x0, which k_sacd_grad reads.
+// grid (unit tiles of the launch's widest layer, item tiles, jobs).
+constexpr int kLdT = srlxg::kTile + 1;  // the float64 tile in LDS: [item][unit], 33 doubles a row
+
+SRLXG_KERNEL void __launch_bounds__(srlxg::kThreads) k_sacd_gemm_first(const srlxg::Job *__restrict__ jobs, int B, const float *__restrict__ s, const float *__restrict__ s2,
+                                                                       const int32_t *__restrict__ action, float *__restrict__ x0, int D, int A) {
+    using srlxg::kTile;
+    __shared__ __attribute__((aligned(16))) float As[2 * kTile * srlxg::kLdK], Bs[2 * kTile * srlxg::kLdK];
+    const srlxg::Job &job = jobs[blockIdx.z];
+    const int W0 = job.N, In = job.s[0].n;
+    const int u0 = blockIdx.x * kTile, b0 = blockIdx.y * kTile;
+    if (u0 >= W0) return;
+    const int t = threadIdx.x, mode = job.relu & kModeMask;
+    // (bits, not a choice between pointers: srlx_mlp_gemm.h's open_source says why)
+    const float *states = (const float *)((job.s[0].sel == srlxg::kArg1 ? (uintptr_t)s2 : 0) | (job.s[0].sel == srlxg::kArg0 ? (uintptr_t)s : 0));
+    // (the swapped view lives in LDS: tile_sums indexes Job::s by a run-time source number, which would put a private copy into scratch memory)
+    __shared__ srlxg::Job v;
+    if (t == 0) {
+        v.s[0] = srlxg::Src{job.s[0].w, In, srlxg::kFromJob, states, D};
+        v.nsrc = 1, v.N = B;
+    }
+    __syncthreads();
+    const srlxg::f64x4 acc = srlxg::tile_sums<false>(v, W0, u0, b0, nullptr, nullptr, As, Bs);
+    double *T = (double *)As;        // [kTile][kLdT]
+    float *wa = Bs, *bu = Bs + kTile * srlxs::kMaxActions;  // [kTile][16] one-hot columns, [kTile] biases
+    const int lane = t & 63, wave = t >> 6;
+#pragma unroll
+    for (int r = 0; r < 4; r++) T[((wave & 1) * 16 + (lane & 15)) * kLdT + (wave >> 1) * 16 + 4 * r + (lane >> 4)] = acc[r];
+    if (mode != kPlain)
+        for (int p = t; p < kTile * A; p += srlxg::kThreads) {
+            const int u = u0 + p / A;
+            wa[(p / A) * srlxs::kMaxActions + p % A] = u < W0 ? job.s[0].w[(i64)u * In + D + p % A] : 0.f;
+        }
+    if (t < kTile) bu[t] = u0 + t < W0 ? job.aux[u0 + t] : 0.f;
+    __syncthreads();
+    const int per = mode == kAllActions ? A : 1;  // rows of the output per item
+    for (int p = t; p < kTile * per * kTile; p += srlxg::kThreads) {
+        const int u = p & (kTile - 1), rr = p / kTile, il = rr / per, a_all = rr % per;
+        const int b = b0 + il;
+        if (b >= B || u0 + u >= W0) continue;
+        double sum = T[il * kLdT + u];
+        if (mode != kPlain) {
+            const int a = mode == kTaken ? action[b] : a_all;
+            if ((unsigned)a < (unsigned)A) sum += (double)wa[u * srlxs::kMaxActions + a];
+        }
+        const float z = (float)(sum + (double)bu[u]);
+        job.y[((i64)b * per + a_all) * job.ldy + u0 + u] = z > 0.f ? z : 0.f;
+    }
+    if ((job.relu & kWriteX0) && blockIdx.x == 0)
+        for (int p = t; p < kTile * In; p += srlxg::kThreads) {
+            const int b = b0 + p / In, k = p % In;
+            if (b < B) x0[(i64)b * In + k] = k < D ? s[(i64)b * D + k] : (k - D == action[b] ? 1.f : 0.f);
+        }
+}
+
+constexpr int kRowThreads = 64;  // of the one-thread-per-item kernels
+
+// What the two pointwise kernels read and write beside the batch: the out layers' rows and the row arrays of the closed forms, all in the path's scratch
+// (srlx_sacd_math.h: a private array indexed by a run-time action number would live in scratch memory).
+struct GemmRows {
+    const float *z;    // [max_batch][16]: the policy's logits
+    float *qa, *qb;    // [B A]: both Q-networks over every action; qa becomes their minimum
+    const float *qsa;  // [2][max_batch]: q1, q2 of (s, action)
+    float *t0, *t1;    // [max_batch][16] each
+    i64 max_batch;
+};
+
+__device__ __forceinline__ void min_rows(float *qa, const float *qb, int A) {
+    for (int a = 0; a < A; a++) qa[a] = qb[a] < qa[a] ? qb[a] : qa[a];  // (min_q_all_actions' comparison)
+}
+
+// k_sacd_target's last lines and k_sacd_q_rows' middle ones, one thread per item
+SRLXG_KERNEL void __launch_bounds__(kRowThreads) k_sacd_gemm_target_q(Batch a, GemmRows g, const float *__restrict__ log_alpha, float discount, int A, float *__restrict__ q1,
+                                                                     float *__restrict__ q2, float *__restrict__ rows, float *__restrict__ dlast) {
+    const i64 b = (i64)blockIdx.x * kRowThreads + threadIdx.x;
+    if (b >= a.B) return;
+    const float alpha = expf(log_alpha[0]);
+    min_rows(g.qa + b * A, g.qb + b * A, A);
+    const float y = srlxs::soft_target(g.z + b * kRows, g.qa + b * A, A, alpha, a.reward[b], a.done[b] ? 1.f : 0.f, discount, g.t0 + b * kRows);
+    a.y[b] = y;
+    for (int which = 0; which < 2; which++) {
+        const float qv = g.qsa[which * g.max_batch + b];
+        (which == 0 ? q1 : q2)[b] = qv;
+        const float diff = qv - y;
+        rows[which * g.max_batch + b] = diff * diff;
+        dlast[((1 + which) * g.max_batch + b) * kRows] = (2.f * diff) / (float)a.B;  // d mean_b (y - q)^2 / d q_b
+    }
+}
+
+// k_sacd_policy's middle lines, one thread per item: dz goes straight into the policy's rows of dlast
+SRLXG_KERNEL void __launch_bounds__(kRowThreads) k_sacd_gemm_policy_row(i64 B, GemmRows g, const float *__restrict__ log_alpha, int A, float *__restrict__ entropy,
+                                                                       float *__restrict__ rows, float *__restrict__ dlast) {
+    const i64 b = (i64)blockIdx.x * kRowThreads + threadIdx.x;
+    if (b >= B) return;
+    const float alpha = expf(log_alpha[0]);
+    min_rows(g.qa + b * A, g.qb + b * A, A);
+    float ent, ls;
+    srlxs::policy_row(g.z + b * kRows, g.qa + b * A, A, alpha, 1.f / (float)B, &ent, &ls, dlast + b * kRows, g.t0 + b * kRows, g.t1 + b * kRows);
+    entropy[b] = ent;
+    rows[2 * g.max_batch + b] = ls;
+}
+
 int set_lds(const void *fn, size_t bytes) {
     if (bytes > 65536) SRLX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return SRLX_OK;
@@ -485,6 +623,129 @@ int upload_tables(srlx_sacd *h) {
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     h->table_ok = h->nets_ok = true;
+    h->gemm_ok = false;  // (whatever made these tables stale made the gemm path's jobs stale)
+    return SRLX_OK;
+}
+
+// the gemm path's scratch, in floats from gemm_scratch: the two pointwise kernels and upload_gemm share this layout
+struct GemmScratch {
+    i64 big, ps, z2, z1, t0, t1, qa, qb, qsa, total;
+    GemmScratch(const srlx_sacd *h) {
+        const i64 mb = h->max_batch;
+        int wq = 0, wp = 0;
+        for (int l = 0; l < h->Lq; l++) wq = h->Wq[l] > wq ? h->Wq[l] : wq;
+        for (int l = 0; l < h->Lp; l++) wp = h->Wp[l] > wp ? h->Wp[l] : wp;
+        big = mb * h->A * wq;  // one all-action plane; four of them from 0 on
+        ps = 4 * big;          // two planes [max_batch][wp] for policy(s')
+        z2 = ps + 2 * mb * wp, z1 = z2 + mb * kRows, t0 = z1 + mb * kRows, t1 = t0 + mb * kRows;
+        qa = t1 + mb * kRows, qb = qa + mb * h->A, qsa = qb + mb * h->A, total = qsa + 2 * mb;
+    }
+};
+
+// The gemm path's plan.  Launch d of the forward chains holds layer d of every network that has one.  The first layers share ONE launch of
+// k_sacd_gemm_first; above it the networks on B rows (policy(s'), policy(s), q1 and q2 on (s, action)) share a k_mlp_gemm_fwd launch and the two Q-networks on
+// B A rows another.  policy(s) and the Q step's forward ride in the target half's launches: neither reads y, and the policy is stepped only at the very end.
+int upload_gemm(srlx_sacd *h) {
+    using srlxg::Job;
+    const i64 mb = h->max_batch, plane = mb * h->wmax;
+    const int D = h->D, A = h->A, Lp = h->Lp, Lq = h->Lq;
+    const GemmScratch sc(h);
+    if (!h->gemm_scratch) {
+        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, sizeof(float) * (size_t)sc.total));
+        SRLX_HIP(hipMemset(h->gemm_scratch, 0, sizeof(float) * (size_t)sc.total));
+        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
+    }
+    float *g = h->gemm_scratch;
+    Job jobs[kGemmJobs];
+    memset(jobs, 0, sizeof(jobs));
+    int nj = 0, ns = 0;
+    auto point = [&](int kind) { h->plan[ns++] = Step{kind, srlxg::Launch{0, 0, 0, 0}}; };
+    auto begin = [&](int kind) { h->plan[ns] = Step{kind, srlxg::Launch{nj, 0, 0, kind == kBwd}}; };
+    auto end = [&]() { ns += h->plan[ns].l.njobs ? 1 : 0; };  // (a launch nothing joined is no step)
+    auto add = [&](int width) -> Job & {
+        srlxg::Launch &l = h->plan[ns].l;
+        l.njobs++, l.nmax = width > l.nmax ? width : l.nmax;
+        return jobs[nj++];
+    };
+    auto first = [&](int sel, int In, float *const *lin, int N, float *y, int mode) {
+        Job &j = add(N);
+        j.s[0] = srlxg::Src{nullptr, D, sel, lin[0], In};
+        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = N, j.relu = mode;
+    };
+    auto fwd = [&](const float *x, int K, float *const *lin, int N, float *y, int ldy, int relu) {
+        Job &j = add(N);
+        j.s[0] = srlxg::Src{x, K, srlxg::kFromJob, lin[0], K};
+        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = ldy, j.relu = relu;
+    };
+    // d loss / d h_l of trained network t (0 policy, 1 q1, 2 q2): the out layer's seed rows in dlast through its weight, or the plane above through the next one
+    auto bwd = [&](int t, int l, int L, const int *W, int Out, float *const *P) {
+        Job &j = add(W[l]);
+        const i64 pl = ((i64)t * 3 + l) * plane;
+        if (l == L - 1) j.s[0] = srlxg::Src{h->dlast + (i64)t * mb * kRows, kRows, srlxg::kFromJob, P[2 * L], Out};
+        else j.s[0] = srlxg::Src{h->dh + pl + plane, W[l + 1], srlxg::kFromJob, P[2 * (l + 1)], W[l + 1]};
+        j.nsrc = 1, j.N = W[l], j.aux = h->h + pl, j.y = h->dh + pl, j.ldy = W[l];
+    };
+    // layer l >= 1 of a chain whose hidden rows go to plane(l) (row stride = the layer's width) and whose out layer writes `out` with row stride `ldo`
+    auto layer = [&](int l, int L, const int *W, int Out, float *const *P, auto plane_of, float *out, int ldo) {
+        if (l > L) return;
+        if (l < L) fwd(plane_of(l - 1), W[l - 1], P + 2 * l, W[l], plane_of(l), W[l], 1);
+        else fwd(plane_of(l - 1), W[l - 1], P + 2 * l, Out, out, ldo, 0);
+    };
+    auto kept = [&](int t) { return [=](int l) { return h->h + ((i64)t * 3 + l) * plane; }; };
+    auto all_actions = [&](int i) { return [=](int l) { return g + (2 * i + (l & 1)) * sc.big; }; };
+    auto next_policy = [&](int l) { return g + sc.ps + (l & 1) * (sc.z2 - sc.ps) / 2; };
+    const int Lmax = Lp > Lq ? Lp : Lq;
+    // ---- the target half, with policy(s) and the Q step's forward in its launches
+    begin(kFirst);
+    first(srlxg::kArg1, D, h->p[0], h->Wp[0], next_policy(0), kPlain);
+    first(srlxg::kArg0, D, h->p[0], h->Wp[0], kept(0)(0), kPlain);
+    first(srlxg::kArg0, D + A, h->p[1], h->Wq[0], kept(1)(0), kTaken | kWriteX0);
+    first(srlxg::kArg0, D + A, h->p[3], h->Wq[0], kept(2)(0), kTaken);
+    first(srlxg::kArg1, D + A, h->p[2], h->Wq[0], all_actions(0)(0), kAllActions);
+    first(srlxg::kArg1, D + A, h->p[4], h->Wq[0], all_actions(1)(0), kAllActions);
+    end();
+    for (int l = 1; l <= Lmax; l++) {  // (layer() adds nothing past a chain's out layer; end() drops a launch nothing joined)
+        begin(kFwdItems);
+        layer(l, Lp, h->Wp, A, h->p[0], next_policy, g + sc.z2, kRows);
+        layer(l, Lp, h->Wp, A, h->p[0], kept(0), g + sc.z1, kRows);
+        layer(l, Lq, h->Wq, 1, h->p[1], kept(1), g + sc.qsa, 1);
+        layer(l, Lq, h->Wq, 1, h->p[3], kept(2), g + sc.qsa + mb, 1);
+        end();
+        begin(kFwdActions);
+        layer(l, Lq, h->Wq, 1, h->p[2], all_actions(0), g + sc.qa, 1);
+        layer(l, Lq, h->Wq, 1, h->p[4], all_actions(1), g + sc.qb, 1);
+        end();
+    }
+    point(kTargetQ);
+    // ---- the Q step's data gradients and its parameter step
+    for (int l = Lq - 1; l >= 0; l--) {
+        begin(kBwd);
+        bwd(1, l, Lq, h->Wq, 1, h->p[1]);
+        bwd(2, l, Lq, h->Wq, 1, h->p[3]);
+        end();
+    }
+    point(kGradQ);
+    // ---- the policy half: the stepped Q-networks over every action of s, policy_row on the logits kept above, the policy's chain
+    begin(kFirst);
+    first(srlxg::kArg0, D + A, h->p[1], h->Wq[0], all_actions(0)(0), kAllActions);
+    first(srlxg::kArg0, D + A, h->p[3], h->Wq[0], all_actions(1)(0), kAllActions);
+    end();
+    for (int l = 1; l <= Lq; l++) {
+        begin(kFwdActions);
+        layer(l, Lq, h->Wq, 1, h->p[1], all_actions(0), g + sc.qa, 1);
+        layer(l, Lq, h->Wq, 1, h->p[3], all_actions(1), g + sc.qb, 1);
+        end();
+    }
+    point(kPolicyRow);
+    for (int l = Lp - 1; l >= 0; l--) {
+        begin(kBwd);
+        bwd(0, l, Lp, h->Wp, A, h->p[0]);
+        end();
+    }
+    point(kGradP);
+    h->n_steps = ns;  // (at most 21 steps and 41 jobs, at three layers everywhere)
+    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
+    h->gemm_ok = true;
     return SRLX_OK;
 }
 
@@ -552,7 +813,8 @@ int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy
 int srlx_sacd_destroy(srlx_sacd_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
-    for (void *p : {(void *)h->d_nets, (void *)h->d_segs, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->dlast, (void *)h->rows})
+    for (void *p : {(void *)h->d_nets, (void *)h->d_segs, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->dlast, (void *)h->rows, (void *)h->gemm_scratch,
+                    (void *)h->d_jobs})
         if (p) (void)hipFree(p);
     delete h;
     return SRLX_OK;
@@ -667,18 +929,25 @@ int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const
     return SRLX_OK;
 }
 
-int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
-                     const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
-                     double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream) {
-    SRLX_REQUIRE(h, "sacd_update: NULL handle");
-    SRLX_REQUIRE(h->bound && h->grads_bound && h->adam_bound, "sacd_update: bind the parameters, the gradient tensors and the Adam state first");
-    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "sacd_update: batch %lld (handle sized for %lld)", (long long)batch, (long long)h->max_batch);
-    SRLX_REQUIRE(d_states && d_actions && d_next_states && d_rewards && d_dones && d_y && d_q1 && d_q2 && d_entropy && d_scalars, "sacd_update: NULL argument");
-    SRLX_REQUIRE(lr_policy >= 0 && lr_q >= 0 && lr_alpha >= 0, "sacd_update: learning rates are non-negative");
-    SRLX_REQUIRE(tau >= 0 && tau <= 1, "sacd_update: tau %g (0..1)", tau);
-    SRLX_REQUIRE((hard_sync == 0 || hard_sync == 1) && (auto_scale == 0 || auto_scale == 1), "sacd_update: hard_sync and auto_scale are 0 or 1");
+}  // extern "C"
+
+namespace {
+
+// srlx_sacd_update (gemm = false: the three row kernels) and srlx_sacd_update_gemm (upload_gemm's plan): one contract, one set of planes, the same two
+// k_sacd_grad launches.  `who` names the entry point in every message.
+int update(const char *who, bool gemm, srlx_sacd *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
+           const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale, double target_entropy,
+           float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream) {
+    SRLX_REQUIRE(h, "%s: NULL handle", who);
+    SRLX_REQUIRE(h->bound && h->grads_bound && h->adam_bound, "%s: bind the parameters, the gradient tensors and the Adam state first", who);
+    SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "%s: batch %lld (handle sized for %lld)", who, (long long)batch, (long long)h->max_batch);
+    SRLX_REQUIRE(d_states && d_actions && d_next_states && d_rewards && d_dones && d_y && d_q1 && d_q2 && d_entropy && d_scalars, "%s: NULL argument", who);
+    SRLX_REQUIRE(lr_policy >= 0 && lr_q >= 0 && lr_alpha >= 0, "%s: learning rates are non-negative", who);
+    SRLX_REQUIRE(tau >= 0 && tau <= 1, "%s: tau %g (0..1)", who, tau);
+    SRLX_REQUIRE((hard_sync == 0 || hard_sync == 1) && (auto_scale == 0 || auto_scale == 1), "%s: hard_sync and auto_scale are 0 or 1", who);
     srlx::DeviceGuard g(h->device);
     if (!h->table_ok) SRLX_TRY(upload_tables(h));
+    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
     hipStream_t st = (hipStream_t)stream;
     const int S = lds_stride(h), D = h->D, A = h->A;
     const size_t lds = lds_bytes(h);
@@ -687,9 +956,6 @@ int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const
     const i64 plane = h->max_batch * h->wmax;
     const NetD *nets = h->d_nets;
     Batch b{(i64)batch, d_states, d_next_states, d_rewards, d_actions, d_dones, d_y};
-    hipLaunchKernelGGL(k_sacd_target, dim3(item_blocks), dim3(kThreads), lds, st, nets, (const float *)h->log_alpha, b, (float)discount, D, A, S);
-    QStep qs{h->x0, h->h, h->dh, h->dlast, h->rows, d_q1, d_q2, plane, h->max_batch};
-    hipLaunchKernelGGL(k_sacd_q_rows, dim3((unsigned)((batch + kRows - 1) / kRows), 2), dim3(kThreads), lds, st, nets, b, qs, D, A, S);
     GradArgs ga{};
     ga.B = batch;
     ga.lr0 = lr_policy, ga.lr1 = lr_q, ga.lr2 = lr_q, ga.beta1 = h->beta1, ga.beta2 = h->beta2, ga.eps = h->eps;
@@ -697,22 +963,88 @@ int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const
     ga.sync = hard_sync ? 1 : 2;
     ga.one_minus_tau = (float)(1.0 - tau), ga.tau = (float)tau;
     Tail tl{};
-    ga.segs = h->d_segs, ga.nseg = 2 * n_tensors_q(h);
-    const i64 nq = 2 * elements(D + A, h->Lq, h->Wq, 1);
-    hipLaunchKernelGGL(k_sacd_grad<false>, dim3((unsigned)((nq + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ga, tl);
-    PStep ps{h->h, h->dh, h->dlast, h->rows, d_entropy, plane, h->max_batch};
-    hipLaunchKernelGGL(k_sacd_policy, dim3(item_blocks), dim3(kThreads), lds, st, nets, (const float *)h->log_alpha, b, ps, D, A, S);
-    ga.segs = h->d_segs + kMaxSegs, ga.nseg = n_tensors_policy(h), ga.xin0 = d_states;
-    tl.rows = h->rows, tl.entropy = d_entropy, tl.max_batch = h->max_batch;
-    tl.log_alpha = h->log_alpha, tl.g_la = h->g_log_alpha, tl.m_la = h->m_la, tl.v_la = h->v_la;
-    tl.auto_scale = auto_scale, tl.target_entropy = (float)target_entropy, tl.lr_alpha = lr_alpha, tl.st_alpha = h->steps[3];
-    tl.out = d_scalars;
-    const i64 np = elements(D, h->Lp, h->Wp, A);
-    hipLaunchKernelGGL(k_sacd_grad<true>, dim3((unsigned)((np + 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ga, tl);
+    auto grad_q = [&]() {
+        ga.segs = h->d_segs, ga.nseg = 2 * n_tensors_q(h);
+        const i64 nq = 2 * elements(D + A, h->Lq, h->Wq, 1);
+        hipLaunchKernelGGL(k_sacd_grad<false>, dim3((unsigned)((nq + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ga, tl);
+    };
+    auto grad_policy = [&]() {
+        ga.segs = h->d_segs + kMaxSegs, ga.nseg = n_tensors_policy(h), ga.xin0 = d_states;
+        tl.rows = h->rows, tl.entropy = d_entropy, tl.max_batch = h->max_batch;
+        tl.log_alpha = h->log_alpha, tl.g_la = h->g_log_alpha, tl.m_la = h->m_la, tl.v_la = h->v_la;
+        tl.auto_scale = auto_scale, tl.target_entropy = (float)target_entropy, tl.lr_alpha = lr_alpha, tl.st_alpha = h->steps[3];
+        tl.out = d_scalars;
+        const i64 np = elements(D, h->Lp, h->Wp, A);
+        hipLaunchKernelGGL(k_sacd_grad<true>, dim3((unsigned)((np + 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ga, tl);
+    };
+    if (!gemm) {
+        hipLaunchKernelGGL(k_sacd_target, dim3(item_blocks), dim3(kThreads), lds, st, nets, (const float *)h->log_alpha, b, (float)discount, D, A, S);
+        QStep qs{h->x0, h->h, h->dh, h->dlast, h->rows, d_q1, d_q2, plane, h->max_batch};
+        hipLaunchKernelGGL(k_sacd_q_rows, dim3((unsigned)((batch + kRows - 1) / kRows), 2), dim3(kThreads), lds, st, nets, b, qs, D, A, S);
+        grad_q();
+        PStep ps{h->h, h->dh, h->dlast, h->rows, d_entropy, plane, h->max_batch};
+        hipLaunchKernelGGL(k_sacd_policy, dim3(item_blocks), dim3(kThreads), lds, st, nets, (const float *)h->log_alpha, b, ps, D, A, S);
+        grad_policy();
+    } else {
+        const GemmScratch sc(h);
+        float *gs = h->gemm_scratch;
+        const int M = (int)batch;
+        const unsigned item_tiles = (unsigned)((M + srlxg::kTile - 1) / srlxg::kTile);
+        const dim3 row_grid((unsigned)((batch + kRowThreads - 1) / kRowThreads));
+        for (int i = 0; i < h->n_steps; i++) {
+            const Step &s = h->plan[i];
+            GemmRows gr{gs + sc.z2, gs + sc.qa, gs + sc.qb, gs + sc.qsa, gs + sc.t0, gs + sc.t1, h->max_batch};
+            switch (s.kind) {
+            case kFirst:
+                hipLaunchKernelGGL(k_sacd_gemm_first, dim3((unsigned)((s.l.nmax + srlxg::kTile - 1) / srlxg::kTile), item_tiles, (unsigned)s.l.njobs), dim3(srlxg::kThreads), 0,
+                                   st, (const srlxg::Job *)h->d_jobs + s.l.first, M, d_states, d_next_states, d_actions, h->x0, D, A);
+                break;
+            case kFwdItems:
+            case kBwd:
+                srlxg::launch(s.l, h->d_jobs, M, nullptr, nullptr, st);
+                break;
+            case kFwdActions:
+                srlxg::launch(s.l, h->d_jobs, M * A, nullptr, nullptr, st);
+                break;
+            case kTargetQ:
+                hipLaunchKernelGGL(k_sacd_gemm_target_q, row_grid, dim3(kRowThreads), 0, st, b, gr, (const float *)h->log_alpha, (float)discount, A, d_q1, d_q2, h->rows,
+                                   h->dlast);
+                break;
+            case kPolicyRow:
+                gr.z = gs + sc.z1;
+                hipLaunchKernelGGL(k_sacd_gemm_policy_row, row_grid, dim3(kRowThreads), 0, st, (i64)batch, gr, (const float *)h->log_alpha, A, d_entropy, h->rows, h->dlast);
+                break;
+            case kGradQ:
+                grad_q();
+                break;
+            case kGradP:
+                grad_policy();
+                break;
+            }
+        }
+    }
     SRLX_HIP(hipGetLastError());
     h->steps[0]++, h->steps[1]++, h->steps[2]++;
     if (auto_scale) h->steps[3]++;
     return SRLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srlx_sacd_update(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
+                     const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
+                     double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream) {
+    return update("sacd_update", false, h, batch, d_states, d_actions, d_next_states, d_rewards, d_dones, lr_policy, lr_q, lr_alpha, discount, tau, hard_sync, auto_scale,
+                  target_entropy, d_y, d_q1, d_q2, d_entropy, d_scalars, stream);
+}
+
+int srlx_sacd_update_gemm(srlx_sacd_t *h, int64_t batch, const float *d_states, const int32_t *d_actions, const float *d_next_states, const float *d_rewards,
+                          const uint8_t *d_dones, double lr_policy, double lr_q, double lr_alpha, double discount, double tau, int hard_sync, int auto_scale,
+                          double target_entropy, float *d_y, float *d_q1, float *d_q2, float *d_entropy, float *d_scalars, void *stream) {
+    return update("sacd_update_gemm", true, h, batch, d_states, d_actions, d_next_states, d_rewards, d_dones, lr_policy, lr_q, lr_alpha, discount, tau, hard_sync,
+                  auto_scale, target_entropy, d_y, d_q1, d_q2, d_entropy, d_scalars, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """Discrete SAC's update on libsrlx (csrc/srlx_sacd.hip): `SacdUpdate` binds an `algorithms.sac.Parameter`'s own tensors by address -- the
 five networks and `log_alpha` stay what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write and
-the Adam state (moments here, step counts in the handle).  One `update` is the whole of sac_tf_discrete.py:158-243 for one batch, in five launches."""
+the Adam state (moments here, step counts in the handle).  One `update` is the whole of sac_tf_discrete.py:158-243 for one batch, in five launches;
+`update(..., gemm=True)` is the same update layer by layer on the float64 matrix cores (srlx_sacd_update_gemm), on the same handle, planes, Adam
+state and step counts."""
 import ctypes
 
 import torch
@@ -97,9 +99,10 @@ class SacdUpdate(LibUpdate):
         self._bind_adam(self.steps()[:3] + [0])
 
     def update(self, state, action, next_state, reward, done, lr_policy, lr_q, lr_alpha, hard_sync: bool, discount: float, tau: float, auto_scale: bool,
-               target_entropy: float) -> dict:
+               target_entropy: float, gemm: bool = False) -> dict:
         """state / next_state f32 [B][D], action i32 [B], reward f32 [B], done u8 [B], all on the device.  Returns y, q1, q2, entropy [B] and `scalars` [5]
-        (q1_loss, q2_loss, policy_loss, alpha_loss, alpha), device tensors; nothing synchronises."""
+        (q1_loss, q2_loss, policy_loss, alpha_loss, alpha), device tensors; nothing synchronises.  `gemm`: srlx_sacd_update_gemm; updates of one object may
+        alternate."""
         B = state.shape[0]
         if B > self.max_batch:
             raise ValueError(f"SacdUpdate: batch size {B} above max_batch {self.max_batch}")
@@ -107,10 +110,10 @@ class SacdUpdate(LibUpdate):
         assert keep[0].dtype == torch.float32 and keep[1].dtype == torch.int32 and keep[3].dtype == torch.float32 and keep[4].dtype == torch.uint8
         out = {k: torch.empty(B, dtype=torch.float32, device=self.device) for k in ("y", "q1", "q2", "entropy")}
         out["scalars"] = torch.empty(5, dtype=torch.float32, device=self.device)
-        N.check(self._lib.srlx_sacd_update(self._h, B, N.tptr(keep[0]), N.tptr(keep[1]), N.tptr(keep[2]), N.tptr(keep[3]), N.tptr(keep[4]), float(lr_policy), float(lr_q),
-                                           float(lr_alpha), float(discount), float(tau), int(bool(hard_sync)), int(bool(auto_scale)), float(target_entropy),
-                                           N.tptr(out["y"]), N.tptr(out["q1"]), N.tptr(out["q2"]), N.tptr(out["entropy"]), N.tptr(out["scalars"]),
-                                           N.torch_stream_ptr()))
+        call = self._lib.srlx_sacd_update_gemm if gemm else self._lib.srlx_sacd_update
+        N.check(call(self._h, B, N.tptr(keep[0]), N.tptr(keep[1]), N.tptr(keep[2]), N.tptr(keep[3]), N.tptr(keep[4]), float(lr_policy), float(lr_q), float(lr_alpha),
+                     float(discount), float(tau), int(bool(hard_sync)), int(bool(auto_scale)), float(target_entropy), N.tptr(out["y"]), N.tptr(out["q1"]),
+                     N.tptr(out["q2"]), N.tptr(out["entropy"]), N.tptr(out["scalars"]), N.torch_stream_ptr()))
         self._keep = keep
         return out
 
