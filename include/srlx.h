@@ -1474,7 +1474,13 @@ int srlx_sacd_ring_batch(int64_t B, int D, int A, const float *d_obs_base, const
  *                              The same handle, planes, gradient tensors, Adam state and step count: one handle may alternate the two calls.  The first
  *                              call of a handle allocates 2 max_batch (widest row) + 18 max_batch floats and the job table (srlx_vppo_scratch_floats does
  *                              not count them).  No host synchronisation, no atomics: equal inputs give equal bits.
- *   srlx_vppo_forward        : n rows of states -> v f32 [n] (NULL: not wanted) and the head's outputs (NULL: not wanted): d_head0 f32 [n][n_out] logits
+ *   srlx_vppo_create_gemm    : srlx_vppo_create's arguments and envelope with max_batch 1..4096 (srlx_last_error() names vppo_create_gemm).  The
+ *                              handle serves srlx_vppo_update_gemm at every batch it admits and refuses srlx_vppo_update (SRLX_ERR_INVALID); bind, steps, forward
+ *                              and the acting calls serve it as any handle.  Its gradient launch is k_mlp_gemm_wgrad (srlx_mlp_gemm.h): every Linear's weight
+ *                              and bias gradient as 32 x 32 tiles of dOut^T X on the float64 matrix cores, the batch the reduction index in row order, and the
+ *                              four loss sums as float64 block reductions in the same launch; steps 7 to 9 stand.  Planes and scratch are sized by max_batch
+ *                              as srlx_vppo_create's: 14 max_batch (widest row) floats of planes.  A handle of srlx_vppo_create launches what it always did.
+ *   srlx_vppo_forward       : n rows of states -> v f32 [n] (NULL: not wanted) and the head's outputs (NULL: not wanted): d_head0 f32 [n][n_out] logits
  *                              or locs, d_head1 f32 [n][n_out] the log-scales clamped to [log_scale_lo, log_scale_hi] (Normal only, and then required with
  *                              d_head0).  The same chains as the update's: v bit for bit what srlx_vppo_update writes for the same rows.  Needs
  *                              srlx_vppo_bind only. */
@@ -1483,6 +1489,8 @@ int64_t srlx_vppo_scratch_floats(int obs_dim, int head, int n_out, int n_trunk, 
                                  const int *policy_widths, int64_t max_batch);
 int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
                      const int *policy_widths, int64_t max_batch, int device);
+int srlx_vppo_create_gemm(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths,
+                          int n_policy, const int *policy_widths, int64_t max_batch, int device);
 int srlx_vppo_destroy(srlx_vppo_t *h);
 int srlx_vppo_bind(srlx_vppo_t *h, float *const *d_params);
 int srlx_vppo_bind_grads(srlx_vppo_t *h, float *const *d_grads, float *const *d_raw_grads);

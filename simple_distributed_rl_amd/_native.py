@@ -280,6 +280,7 @@ SIGNATURES = {
     "srlx_sacd_ring_batch": (c_int, [c_i64, c_int, c_int] + [c_p] * 10),
     "srlx_vppo_scratch_floats": (c_i64, [c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_i64]),
     "srlx_vppo_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_i64, c_int]),
+    "srlx_vppo_create_gemm": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_i64, c_int]),
     "srlx_vppo_destroy": (c_int, [c_p]),
     "srlx_vppo_bind": (c_int, [c_p, c_p]),
     "srlx_vppo_bind_grads": (c_int, [c_p, c_p, c_p]),

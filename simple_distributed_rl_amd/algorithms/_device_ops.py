@@ -29,7 +29,8 @@ class SrlxUpdateBackend:
     batch size, otherwise "torch", with the reason in `why_not_srlx_update`.  `update_path` names the backend the last update ran on.  The trainer supplies
     `_srlx_update_class()`, the device layer's update (`why_not(parameter, batch, config)` and a constructor over the Parameter), and `_make_torch_update()`, its
     torch optimisers and schedulers.  A trainer whose device update has a second path names it in `SRLX_BACKENDS` (ppo_v.Trainer: "srlx_gemm"); such a name is
-    served, refused and reported as "srlx" is, on the same update object."""
+    served, refused and reported as "srlx" is, on the same update object.  Where the update class declares `GEMM_MAX_BATCH` (VppoUpdate), "srlx_gemm" at
+    a first batch above 256 builds a gemm-only update sized for it; "srlx" there, and every other class on either name, answers as before."""
 
     SRLX_BACKENDS = ("srlx",)  # the names that ask for the libsrlx update
 
@@ -46,10 +47,15 @@ class SrlxUpdateBackend:
         self._backend = "torch"
         if self.update_backend in self.SRLX_BACKENDS:
             update = self._srlx_update_class()
-            self.why_not_srlx_update = update.why_not(self.parameter, batch, self.config)
+            # past 256 rows only a gemm-only handle serves, on the gemm name alone, and only an update class that declares GEMM_MAX_BATCH has one (VppoUpdate)
+            wide = getattr(update, "GEMM_MAX_BATCH", 0) if self.update_backend == "srlx_gemm" and batch > 256 else 0
+            self.why_not_srlx_update = update.why_not(self.parameter, batch, self.config, gemm=True) if wide else update.why_not(self.parameter, batch, self.config)
             if not self.why_not_srlx_update:
                 self._backend = self.update_backend
-                self._srlx = update(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
+                if wide:
+                    self._srlx = update(self.parameter, max_batch=max(batch, min(wide, self.config.batch_size)), gemm_only=True)
+                else:
+                    self._srlx = update(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
         if self._backend == "torch":
             self._make_torch_update()
 

@@ -12,7 +12,8 @@ layers start as the reference's do (he_normal / zeros in the MLP blocks, torch's
 
 Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of three backends that implement it alike:
   "srlx"       one libsrlx call, three launches (device/vppo.py, csrc/srlx_vppo.hip), for GPU parameters inside the kernels' envelope;
-  "srlx_gemm"  the same call layer by layer on the float64 matrix cores (DESIGN.md 7t): opt-in, for wide layers and full batches; served and refused as "srlx";
+  "srlx_gemm"  the same call layer by layer on the float64 matrix cores: opt-in, for wide layers and full batches; served and refused as "srlx"
+               up to a batch of 256, and from 257 to 4096 on a gemm-only handle whose weight gradient runs on the matrix cores too (DESIGN.md 7w);
   "torch"      the reference's step in plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.

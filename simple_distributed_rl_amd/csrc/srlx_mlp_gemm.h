@@ -7,6 +7,8 @@
 //   Job, Src          one GEMM of a launch: up to three (rows, weight) sources summed into one output tile, in the order a, b, c (SumSeed's order)
 //   k_mlp_gemm_fwd    Y[M][N] = act(X[M][K] W[N][K]^T + b): the weight in torch's [out][in] layout, both operands contiguous along k
 //   k_mlp_gemm_bwd    dH[M][N] = H[M][N] > 0 ? sum_s dOut_s[M][n_s] W_s[n_s][N] : 0: the weight read untransposed, coalesced along the output column
+//   k_mlp_gemm_wgrad  dW[N][K] = dOut[M][N]^T X[M][K] and db[N] = sum_m dOut[m][N] of every Linear of a srlxt::Seg table in one launch, the batch the reduction
+//                     index: the gradient launch of a handle of srlx_vppo_create_gemm (its own comment stands in front of it below)
 // Numeric contract (dense<double>'s, on the matrix cores): tensors are float32 in memory; a lane widens its operand to float64 when it reads its fragment, a product
 // of two float32 values is exact there, the sum accumulates in float64 and is rounded to float32 ONCE, in the epilogue.  Inside a group of 4 terms the matrix core's
 // order is its own, so a sum may differ from dense<double>'s in the last bit of that one rounding.
@@ -28,6 +30,8 @@
 #include <stdint.h>
 
 #include <hip/hip_runtime.h>
+
+#include "srlx_param_tail.h"
 
 namespace srlxg {
 using i64 = int64_t;
@@ -209,6 +213,120 @@ static SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_bwd(const Job *_
         if (row >= M) continue;
         job.y[(i64)row * job.ldy + col] = job.aux[(i64)row * job.N + col] > 0.f ? (float)acc[r] : 0.f;
     }
+}
+
+// ---- the weight gradient ------------------------------------------------------------------------------------------------------------------------
+// Every weight / bias pair of a srlxt::Seg table in ONE launch: graw_w[u][k] = sum_b dout[b][u] xin[b][k], graw_b[u] = sum_b dout[b][u], the batch row the
+// reduction index.  A workgroup owns a 32 (out) x 32 (in) tile of one Linear; the bias is column `in` of that Linear's X, a 1.0f the loader writes for rows < B, so
+// a Linear has ceil((in + 1) / 32) tile columns.  Transposed A: BOTH operands are read as fetch_k_cols reads the backward pass's weight -- for each of the chunk's
+// 64 batch rows, 32 consecutive columns -- and staged [k][column] at stride kLdN, so the A fragment of lane l (row l % 16, k = l / 16) and the B fragment
+// (k = l / 16, column l % 16) are both As[(kk + l / 16) kLdN + quadrant + l % 16]: bank 48 (l / 16) + l % 16 mod 64, 64 different banks.  49 152 bytes of stage and
+// 2 048 of block_sum.  The same numeric contract; every workgroup leaves the float64 sum of the squares of the float32 values it stored in partials[blockIdx.x].
+struct WgradLin {  // one Linear of the table: segs[2 l] (weight) and segs[2 l + 1] (bias)
+    int tile_end;  // running tile count: blockIdx.x is searched here as grad_body searches segs[].end
+    int out, in, ktiles;  // ktiles = ceil((in + 1) / 32): tile t of the Linear is (t / ktiles, t % ktiles)
+};
+
+// tiles of one Linear
+inline int wgrad_tiles(int out, int in) { return ((out + kTile - 1) / kTile) * ((in + 1 + kTile - 1) / kTile); }
+
+// One chunk of a [k][ld]-strided operand: reduction rows k0.. (below `n`), columns c0.. (below `cols`); 64 x 8 quads, two per thread.  `one` >= 0: column `one`
+// of every row below `n` reads 1.0f (the bias column; it lies at or behind `cols`).
+__device__ __forceinline__ void fetch_k_cols_ld(const float *p, i64 ld, int cols, int n, int k0, int c0, bool vec, int one, float4 (&q)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int slot = threadIdx.x + i * kThreads, k = k0 + (slot >> 3), c = c0 + ((slot & 7) << 2);
+        q[i] = load_quad(p + (i64)k * ld + c, k < n ? cols - c : 0, vec);
+        const int j = one - c;
+        if (k < n && one >= 0) {
+            if (j == 0) q[i].x = 1.f;
+            if (j == 1) q[i].y = 1.f;
+            if (j == 2) q[i].z = 1.f;
+            if (j == 3) q[i].w = 1.f;
+        }
+    }
+}
+
+// The tile's accumulators: sum_b dout[b][u0 + .] x[b][k0 + .] over b < B, chunk by chunk.  Every thread of the workgroup must call this (it holds barriers);
+// returns this lane's 4 sums: register r is out row u0 + 16 (wave / 2) + 4 r + l / 16, in column k0 + 16 (wave % 2) + l % 16.
+__device__ __forceinline__ f64x4 tile_sums_wgrad(const float *dout, int stride, int out, const float *x, int in, int B, int u0, int k0, float *As, float *Bs) {
+    constexpr int kStage = kChunk * kLdN;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fk = lane >> 4;
+    const int au = (wave >> 1) * 16 + fr, bn = (wave & 1) * 16 + fr;
+    const bool avec = aligned16(dout) && stride % 4 == 0 && out % 4 == 0, xvec = aligned16(x) && in % 4 == 0;
+    const int chunks = (B + kChunk - 1) / kChunk;
+    float4 qa[2], qb[2];
+    auto fetch = [&](int c) {
+        fetch_k_cols_ld(dout, stride, out, B, c * kChunk, u0, avec, -1, qa);
+        fetch_k_cols_ld(x, in, in, B, c * kChunk, k0, xvec, in, qb);
+    };
+    auto stage = [&](int half) {
+        stage_k_cols(As + half * kStage, qa);
+        stage_k_cols(Bs + half * kStage, qb);
+    };
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (int c = 0; c < chunks; c++) {
+        const bool more = c + 1 < chunks;
+        if (more) fetch(c + 1);  // (in flight under this chunk's MFMAs)
+        const float *A = As + (c & 1) * kStage + fk * kLdN + au;
+        const float *Bp = Bs + (c & 1) * kStage + fk * kLdN + bn;
+#pragma unroll
+        for (int kk = 0; kk < kChunk; kk += 4) {
+            const double av = (double)A[kk * kLdN], bv = (double)Bp[kk * kLdN];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        }
+        if (more) stage((c + 1) & 1);  // (the half whose readers passed the barrier that ended chunk c - 1)
+        __syncthreads();
+    }
+    return acc;
+}
+
+struct WgradArgs {
+    const srlxt::Seg *segs;
+    const WgradLin *lins;  // [nlin]
+    int nlin, B;
+    const float *xin0;     // the caller's states: the input rows of a Linear whose xin is NULL
+    double *partials;      // [lins[nlin - 1].tile_end]
+};
+
+// grid lins[nlin - 1].tile_end + 1: one workgroup per tile, and a last one that owns no tile and runs the caller's loss sums: tail(sq) with every thread of the
+// workgroup, `sq` block_sum's buffer.  (A template: a translation unit holds the kernel for the tails it launches.)
+template <typename Tail>
+SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_wgrad(WgradArgs a, Tail tail) {
+    static_assert(kThreads == srlxt::kThreads, "block_sum reduces the tail's workgroup size");
+    __shared__ __attribute__((aligned(16))) float As[2 * kChunk * kLdN], Bs[2 * kChunk * kLdN];
+    __shared__ double sq[kThreads];
+    const int tile = (int)blockIdx.x;
+    if (tile >= a.lins[a.nlin - 1].tile_end) {
+        tail(sq);
+        return;
+    }
+    int l = 0;
+    while (tile >= a.lins[l].tile_end) l++;
+    const WgradLin ln = a.lins[l];
+    const srlxt::Seg sw = a.segs[2 * l];
+    float *graw_b = a.segs[2 * l + 1].graw;
+    const int t = tile - (l ? a.lins[l - 1].tile_end : 0);
+    const int u0 = (t / ln.ktiles) * kTile, k0 = (t % ln.ktiles) * kTile;
+    const f64x4 acc = tile_sums_wgrad(sw.dout, sw.stride, ln.out, sw.xin ? sw.xin : a.xin0, ln.in, a.B, u0, k0, As, Bs);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = k0 + (wave & 1) * 16 + (lane & 15);
+    double mine = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int u = u0 + (wave >> 1) * 16 + 4 * r + (lane >> 4);
+        if (u >= ln.out || k > ln.in) continue;
+        const float g = (float)acc[r];
+        if (k < ln.in) sw.graw[(i64)u * ln.in + k] = g;
+        else graw_b[u] = g;
+        mine += (double)g * (double)g;
+    }
+    srlxt::block_sum(sq, mine);
+    if (threadIdx.x == 0) a.partials[tile] = sq[0];
 }
 
 // One launch of a plan: `njobs` jobs from `first` on in the device table, the widest of them `nmax` columns.

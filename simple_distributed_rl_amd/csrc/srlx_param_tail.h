@@ -2,7 +2,8 @@
 // (srlx_vppo.hip) and NoT_SAC (srlx_notsac.hip).  An algorithm's file keeps its row kernels, its loss sums and which rows feed which tensor; the rest is here.
 //   Seg, push_linear   the segment table: one entry per parameter tensor, a weight + bias pair per Linear
 //   grad_body          one thread per parameter: the gradient before the clip, a sum over the batch in row order; every workgroup leaves the sum of its squares;
-//                      the last threads of the launch own no element and run the caller's loss sums instead
+//                      the last threads of the launch own no element and run the caller's loss sums instead.  (srlx_mlp_gemm.h's k_mlp_gemm_wgrad is the same
+//                      launch as 32 x 32 tiles on the float64 matrix cores, over the same Seg table and into the same partials: DESIGN.md 7w)
 //   step_body          every workgroup sums the same partial squares in the same order (the norm), then one thread per parameter: the clipped gradient and Adam
 //   ParamSet           the host's side of the table: the bound tensors, Adam's constants, the step count and what is stale
 //   chain, widths_ok, rows_per_workgroup, row_lds_bytes   the shape rules of a handle (srlx_sacd.hip reads these too; its gradient kernel, which has no norm

@@ -40,6 +40,7 @@ using srlxv::kNormalLs;
 constexpr int kPlanes = 7;  // trunk 0..2, value 3..4, policy 5..6
 constexpr int kGemmLaunches = 11;  // forward 3 trunk + 3 branch depths, backward 2 branch depths + 3 trunk
 constexpr int kGemmJobs = 32;      // forward 3 x 2 + 3 x 4, backward 2 x 2 + 3
+constexpr i64 kRowMaxBatch = 256, kGemmMaxBatch = 4096;  // srlx_vppo_create's and srlx_vppo_create_gemm's largest max_batch
 
 struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
     Layers trunk, value, policy;
@@ -68,6 +69,10 @@ struct srlx_vppo {
     srlxg::Launch plan[kGemmLaunches];
     int n_fwd, n_launches;  // forward launches, then the data-gradient ones
     bool gemm_ok;           // the job table holds the bound tensors (upload_table makes it stale)
+    // a handle of srlx_vppo_create_gemm: max_batch up to kGemmMaxBatch, the gemm path only, the gradient launch k_mlp_gemm_wgrad
+    bool gemm_only;
+    srlxg::WgradLin *d_lins;  // [kMaxTensors / 2]: the tile prefix of every Linear, uploaded with the segment table
+    int nlin, wgrad_tiles;
 };
 
 namespace {
@@ -386,7 +391,25 @@ __global__ void __launch_bounds__(kThreads) k_vppo_grad(GradArgs a) { srlxt::gra
 
 __global__ void __launch_bounds__(kThreads) k_vppo_step(srlxt::StepArgs a) { srlxt::step_body(a); }
 
-int check_shape(const char *who, int D, int head, int A, int nt, const int *tw, int nv, const int *vw, int np, const int *pw, i64 max_batch) {
+// The same four sums as the last workgroup of k_mlp_gemm_wgrad's launch: every thread takes the rows t, t + 256, ... of a sum in row order, then block_sum's
+// tree -- a fixed order in float64, rounded once.
+struct LossBlockSums {
+    LossSums s;
+    __device__ __forceinline__ void operator()(double *sq) const {  // (a call here cost the kernel 64 bytes of scratch per lane)
+        for (int k = 0; k < LossSums::n; k++) {
+            double mine = 0.0;
+            for (i64 b = threadIdx.x; b < s.B; b += kThreads) mine += (double)s.rows[k * s.max_batch + b];
+            srlxt::block_sum(sq, mine);
+            const double sum = sq[0];
+            __syncthreads();  // (every thread has read sq[0] before the next sum's first write)
+            if (threadIdx.x == 0)
+                s.out[k] = k == 0 || k == 1 ? (float)(sum * s.inv_n) : (k == 2 ? (float)(-sum * s.inv_n) : (s.entropy ? (float)(sum * s.inv_b) : 0.f));
+        }
+    }
+};
+
+int check_shape(const char *who, int D, int head, int A, int nt, const int *tw, int nv, const int *vw, int np, const int *pw, i64 max_batch,
+                i64 cap = kRowMaxBatch) {
     SRLX_REQUIRE(D >= 1 && D <= 256, "%s: observation length %d (1..256)", who, D);
     SRLX_REQUIRE(head == 0 || head == 1, "%s: head kind %d (0 categorical, 1 Normal)", who, head);
     SRLX_REQUIRE(head == 1 || (A >= 2 && A <= 16), "%s: %d actions (2..16)", who, A);
@@ -394,7 +417,7 @@ int check_shape(const char *who, int D, int head, int A, int nt, const int *tw, 
     SRLX_REQUIRE(srlxt::widths_ok(nt, 1, 3, tw), "%s: the trunk is 1..3 layers of 32..512 units in multiples of 32", who);
     SRLX_REQUIRE(srlxt::widths_ok(nv, 0, 2, vw), "%s: the value block is 0..2 layers of 32..512 units in multiples of 32", who);
     SRLX_REQUIRE(srlxt::widths_ok(np, 0, 2, pw), "%s: the policy block is 0..2 layers of 32..512 units in multiples of 32", who);
-    SRLX_REQUIRE(max_batch >= 1 && max_batch <= 256, "%s: max_batch %lld (1..256)", who, (long long)max_batch);
+    SRLX_REQUIRE(max_batch >= 1 && max_batch <= cap, "%s: max_batch %lld (1..%lld)", who, (long long)max_batch, (long long)cap);
     return SRLX_OK;
 }
 
@@ -478,6 +501,16 @@ int upload_table(srlx_vppo *h) {
         srlxt::push_linear(segs + 2 * l, end, shape[l][0], shape[l][1], stride, dout, xin, h->ps, 2 * l);
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
+    if (h->gemm_only) {  // (the prefix depends on the shape alone; it travels with the table so that one flag covers both)
+        srlxg::WgradLin lins[kMaxTensors / 2];
+        memset(lins, 0, sizeof(lins));
+        int tiles = 0;
+        for (int l = 0; l < nl; l++) {
+            tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
+            lins[l] = srlxg::WgradLin{tiles, shape[l][0], shape[l][1], (shape[l][1] + 1 + srlxg::kTile - 1) / srlxg::kTile};
+        }
+        SRLX_HIP(hipMemcpy(h->d_lins, lins, sizeof(lins), hipMemcpyHostToDevice));
+    }
     h->ps.table_ok = true;
     h->gemm_ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
     return SRLX_OK;
@@ -495,6 +528,10 @@ void fill(srlx_vppo *h, int D, int head, int A, int nt, const int *tw, int nv, c
     h->nt = n_tensors(h);
     h->elements = elements_of(h);
     h->grad_blocks = (h->elements + 4 + kThreads - 1) / kThreads;
+    int shape[kMaxTensors / 2][2];
+    h->nlin = linear_shapes(h, shape);
+    h->wgrad_tiles = 0;
+    for (int l = 0; l < h->nlin; l++) h->wgrad_tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
 }
 
 // The gemm path's launch plan: every Linear over the whole batch as one job, jobs of equal depth in one launch.  Forward: the trunk, layer by
@@ -615,6 +652,8 @@ int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float 
            float *d_scalars, void *stream) {
     SRLX_REQUIRE(h, "%s: NULL handle", who);
     SRLX_REQUIRE(h->ps.ready(), "%s: bind the parameters, the gradient tensors and the Adam state first", who);
+    SRLX_REQUIRE(gemm || !h->gemm_only, "%s: a handle of srlx_vppo_create_gemm runs srlx_vppo_update_gemm only (the row path stops at max_batch %lld)", who,
+                 (long long)kRowMaxBatch);
     SRLX_REQUIRE(batch >= 1 && batch <= h->max_batch, "%s: batch %lld (handle sized for %lld)", who, (long long)batch, (long long)h->max_batch);
     SRLX_REQUIRE(d_states && d_next_states && d_actions && d_old_logpi && d_rewards && d_not_terminated && d_total_rewards && d_v && d_n_v && d_new_logpi && d_scalars,
                  "%s: NULL argument", who);
@@ -642,9 +681,15 @@ int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float 
     } else {
         hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
     }
-    GradArgs ga{h->d_segs, h->nt, d_states, h->partials, LossSums{(i64)batch, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, d_scalars}};
-    hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
-    const srlxt::StepArgs sa = h->ps.step_args(h->d_segs, h->nt, h->partials, h->grad_blocks, max_grad_norm, lr, d_scalars + 4);
+    const LossSums sums{(i64)batch, h->rows, h->max_batch, 1.0 / N, 1.0 / (double)batch, entropy_weight > 0 ? 1 : 0, d_scalars};
+    if (h->gemm_only) {
+        const srlxg::WgradArgs wa{h->d_segs, h->d_lins, h->nlin, (int)batch, d_states, h->partials};
+        hipLaunchKernelGGL(srlxg::k_mlp_gemm_wgrad<LossBlockSums>, dim3((unsigned)h->wgrad_tiles + 1), dim3(kThreads), 0, st, wa, LossBlockSums{sums});
+    } else {
+        GradArgs ga{h->d_segs, h->nt, d_states, h->partials, sums};
+        hipLaunchKernelGGL(k_vppo_grad, dim3((unsigned)h->grad_blocks), dim3(kThreads), 0, st, ga);
+    }
+    const srlxt::StepArgs sa = h->ps.step_args(h->d_segs, h->nt, h->partials, h->gemm_only ? h->wgrad_tiles : h->grad_blocks, max_grad_norm, lr, d_scalars + 4);
     hipLaunchKernelGGL(k_vppo_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
     SRLX_HIP(hipGetLastError());
     h->ps.steps++;
@@ -663,15 +708,19 @@ int64_t srlx_vppo_scratch_floats(int obs_dim, int head, int n_out, int n_trunk, 
     return 2 * kPlanes * max_batch * h.wmax + max_batch + max_batch * kHeadCols + 4 * max_batch + 2 * h.grad_blocks;
 }
 
-int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
-                     const int *policy_widths, int64_t max_batch, int device) {
-    SRLX_REQUIRE(out, "vppo_create: NULL handle pointer");
+// srlx_vppo_create (gemm_only = false) and srlx_vppo_create_gemm: one set of planes, sized by max_batch; `who` names the entry point in every message.
+static int create(const char *who, bool gemm_only, srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value,
+                  const int *value_widths, int n_policy, const int *policy_widths, int64_t max_batch, int device) {
+    SRLX_REQUIRE(out, "%s: NULL handle pointer", who);
     *out = nullptr;
-    SRLX_TRY(check_shape("vppo_create", obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch));
+    SRLX_TRY(check_shape(who, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch,
+                         gemm_only ? kGemmMaxBatch : kRowMaxBatch));
     srlx::DeviceGuard g(device);
-    SRLX_REQUIRE(g.ok, "vppo_create: device %d unavailable", device);
+    SRLX_REQUIRE(g.ok, "%s: device %d unavailable", who, device);
     srlx_vppo *h = new srlx_vppo();
     fill(h, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch, device);
+    h->gemm_only = gemm_only;
+    const i64 n_partials = gemm_only ? h->wgrad_tiles : h->grad_blocks;
     const size_t plane = (size_t)max_batch * h->wmax;
     hipError_t e = hipMalloc((void **)&h->d_segs, sizeof(Seg) * kMaxTensors);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_net, sizeof(Net));
@@ -680,7 +729,8 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
     if (e == hipSuccess) e = hipMalloc((void **)&h->dlast_v, sizeof(float) * max_batch);
     if (e == hipSuccess) e = hipMalloc((void **)&h->dlast_p, sizeof(float) * max_batch * kHeadCols);
     if (e == hipSuccess) e = hipMalloc((void **)&h->rows, sizeof(float) * 4 * max_batch);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->partials, sizeof(double) * h->grad_blocks);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->partials, sizeof(double) * n_partials);
+    if (e == hipSuccess && gemm_only) e = hipMalloc((void **)&h->d_lins, sizeof(srlxg::WgradLin) * (kMaxTensors / 2));
     if (e == hipSuccess) e = hipMemset(h->dlast_p, 0, sizeof(float) * max_batch * kHeadCols);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
@@ -688,18 +738,28 @@ int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act_normal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap2);
     if (e != hipSuccess) {
         srlx_vppo_destroy(h);
-        srlx::set_error("vppo_create: device set-up failed: %s", hipGetErrorString(e));
+        srlx::set_error("%s: device set-up failed: %s", who, hipGetErrorString(e));
         return SRLX_ERR_NOMEM;
     }
     *out = h;
     return SRLX_OK;
 }
 
+int srlx_vppo_create(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths, int n_policy,
+                     const int *policy_widths, int64_t max_batch, int device) {
+    return create("vppo_create", false, out, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch, device);
+}
+
+int srlx_vppo_create_gemm(srlx_vppo_t **out, int obs_dim, int head, int n_out, int n_trunk, const int *trunk_widths, int n_value, const int *value_widths,
+                          int n_policy, const int *policy_widths, int64_t max_batch, int device) {
+    return create("vppo_create_gemm", true, out, obs_dim, head, n_out, n_trunk, trunk_widths, n_value, value_widths, n_policy, policy_widths, max_batch, device);
+}
+
 int srlx_vppo_destroy(srlx_vppo_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
     for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->h, (void *)h->dh, (void *)h->dlast_v, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials,
-                    (void *)h->gemm_scratch, (void *)h->d_jobs})
+                    (void *)h->gemm_scratch, (void *)h->d_jobs, (void *)h->d_lins})
         if (p) (void)hipFree(p);
     delete h;
     return SRLX_OK;

@@ -78,9 +78,9 @@ class RowUpdate(LibUpdate):
     """A subclass gives ABI, `tensors_of(parameter)` (bind order), `shape_of(parameter)` (a tuple or a sentence), `config_reasons(config)` and
     `envelope_reason(*shape, batch)`."""
 
-    def _open(self, parameter, max_batch, betas, eps):
-        """Everything of a constructor that comes before srlx_<ABI>_create; returns the shape."""
-        reason = self.why_not(parameter, max_batch)
+    def _open(self, parameter, max_batch, betas, eps, gemm: bool = False):
+        """Everything of a constructor that comes before srlx_<ABI>_create; returns the shape.  `gemm`: see `why_not`."""
+        reason = self.why_not(parameter, max_batch, gemm=gemm)
         if reason:
             raise ValueError(f"{type(self).__name__}: {reason}")
         self.parameter = parameter
@@ -100,8 +100,9 @@ class RowUpdate(LibUpdate):
         self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
 
     @classmethod
-    def why_not(cls, parameter, batch: int = 1, config=None) -> str:
-        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not."""
+    def why_not(cls, parameter, batch: int = 1, config=None, gemm: bool = False) -> str:
+        """'' when libsrlx runs this Parameter's update at this batch size, otherwise the reason it does not.  `gemm`: asked of a gemm-only handle, by a class
+        that declares GEMM_MAX_BATCH and whose `envelope_reason` takes the flag (VppoUpdate); no other class is asked so."""
         reason = tensor_reason(cls.tensors_of(parameter))
         if reason:
             return reason
@@ -112,7 +113,7 @@ class RowUpdate(LibUpdate):
         shape = cls.shape_of(parameter)
         if isinstance(shape, str):
             return shape
-        return cls.envelope_reason(*shape, batch)
+        return cls.envelope_reason(*shape, batch, gemm=True) if gemm else cls.envelope_reason(*shape, batch)
 
     def steps(self) -> int:
         """Optimiser steps taken (by every optimiser of the handle)."""

@@ -2,7 +2,8 @@
 stays what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after the norm clip)
 and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches;
 `update(..., gemm=True)` is the same step layer by layer on the float64 matrix cores (srlx_vppo_update_gemm), the path for wide layers and full
-batches."""
+batches.  `VppoUpdate(parameter, max_batch, gemm_only=True)` is a handle of srlx_vppo_create_gemm: batches up to GEMM_MAX_BATCH = 4096 on the gemm
+path alone, its weight and bias gradients one tiled launch on the matrix cores (k_mlp_gemm_wgrad)."""
 import ctypes
 
 import torch
@@ -41,19 +42,21 @@ def log_scale_range(parameter):
 
 class VppoUpdate(R.RowUpdate):
     ABI = "vppo"
+    GEMM_MAX_BATCH = 4096  # srlx_vppo_create_gemm's largest max_batch; declaring it is what lets a trainer ask with gemm=True (SrlxUpdateBackend)
     shape_of = staticmethod(shape_of)
 
     @staticmethod
     def tensors_of(parameter) -> list:
         return list(parameter.net.parameters())
 
-    def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8):
-        self.D, self.head, self.n_out, self.trunk_widths, self.value_widths, self.policy_widths = self._open(parameter, max_batch, betas, eps)
+    def __init__(self, parameter, max_batch: int = MAX_BATCH, betas=(0.9, 0.999), eps: float = 1e-8, gemm_only: bool = False):
+        self.gemm_only = bool(gemm_only)
+        self.D, self.head, self.n_out, self.trunk_widths, self.value_widths, self.policy_widths = self._open(parameter, max_batch, betas, eps, gemm=self.gemm_only)
         self.K = self.n_out if self.head else 1
         self.ls_lo, self.ls_hi = log_scale_range(parameter)
-        N.check(self._lib.srlx_vppo_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(self.trunk_widths), _int_array(self.trunk_widths),
-                                           len(self.value_widths), _int_array(self.value_widths), len(self.policy_widths), _int_array(self.policy_widths),
-                                           max_batch, self.device.index or 0))
+        create = self._lib.srlx_vppo_create_gemm if self.gemm_only else self._lib.srlx_vppo_create
+        N.check(create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(self.trunk_widths), _int_array(self.trunk_widths), len(self.value_widths),
+                       _int_array(self.value_widths), len(self.policy_widths), _int_array(self.policy_widths), max_batch, self.device.index or 0))
         self._alloc()
         N.check(self._lib.srlx_vppo_bind(self._h, _ptrs(self.params)))
         N.check(self._lib.srlx_vppo_bind_grads(self._h, _ptrs(self.grads), _ptrs(self.raw_grads)))
@@ -67,11 +70,15 @@ class VppoUpdate(R.RowUpdate):
         return blocks + R.lr_schedule_reason(config)
 
     @staticmethod
-    def envelope_reason(D, head, n_out, tw, vw, pw, batch: int = 1) -> str:
-        """The envelope of srlx_vppo_create as a sentence ('' inside it).  Host arithmetic: no device needed."""
-        if batch > MAX_BATCH:
-            return f"batch size {batch} above max_batch {MAX_BATCH}"
-        if N.lib().srlx_vppo_scratch_floats(D, head, n_out, len(tw), _int_array(tw), len(vw), _int_array(vw), len(pw), _int_array(pw), max(1, batch)) < 0:
+    def envelope_reason(D, head, n_out, tw, vw, pw, batch: int = 1, gemm: bool = False) -> str:
+        """The envelope of srlx_vppo_create (`gemm`: of srlx_vppo_create_gemm, whose max_batch reaches GEMM_MAX_BATCH) as a sentence ('' inside it).  Host
+        arithmetic: no device needed."""
+        cap = VppoUpdate.GEMM_MAX_BATCH if gemm else MAX_BATCH
+        if batch > cap:
+            return f"batch size {batch} above max_batch {cap}"
+        # (the shape's envelope is one and the same; srlx_vppo_scratch_floats keeps srlx_vppo_create's bound on the batch, so it is asked at a batch both admit)
+        if N.lib().srlx_vppo_scratch_floats(D, head, n_out, len(tw), _int_array(tw), len(vw), _int_array(vw), len(pw), _int_array(pw),
+                                            max(1, min(batch, MAX_BATCH))) < 0:
             return ("outside the envelope (D 1..256, trunk 1..3 layers, value and policy block 0..2 layers of 32..512 units in multiples of 32, 2..16 actions or "
                     f"1..8 action elements): D {D}, {'Normal' if head else 'categorical'} {n_out}, trunk {tuple(tw)}, value {tuple(vw)}, policy {tuple(pw)}")
         return ""
@@ -86,6 +93,8 @@ class VppoUpdate(R.RowUpdate):
         B = state.shape[0]
         if B > self.max_batch:
             raise ValueError(f"VppoUpdate: batch size {B} above max_batch {self.max_batch}")
+        if self.gemm_only and not gemm:
+            raise ValueError("VppoUpdate: a handle of srlx_vppo_create_gemm runs srlx_vppo_update_gemm only (the row path stops at max_batch 256)")
         keep = [t.contiguous() for t in (state, next_state, action, old_logpi, reward, not_terminated, total_reward)]
         assert keep[2].dtype == (torch.float32 if self.head else torch.int32) and all(t.dtype == torch.float32 for t in keep[:2] + keep[3:])
         assert keep[0].numel() == B * self.D and keep[1].numel() == B * self.D and keep[2].numel() == B * self.K and keep[3].numel() == B * self.K
