@@ -1673,6 +1673,32 @@ int srlx_notsac_update_gemm(srlx_notsac_t *h, int64_t batch, const float *d_stat
 int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
                         const float *d_actions, float *d_q, void *stream);
 
+/* ---- NoTarget_DQN on flat observations (srlx_dqnnot.hip; srl/algorithms/dqn_not/trainer.py:33-87) -----------------------------------------------
+ * One dueling Q-network -- hidden_block Linear(D, U) + ReLU; v_block Linear(U, U) + ReLU + Linear(U, 1); adv_block Linear(U, U) + ReLU + Linear(U, A);
+ * q = v + adv - mean(adv) -- whose target comes from the same network on the next states.  D 1..256, U 32..512 in multiples of 32, A 2..32, max_batch 1..4096;
+ * srlx_dqnnot_create validates before it touches a device.  Tensors are float32; products and sums are float64, rounded once per stored value (the layer
+ * launches are srlx_mlp_gemm.h's on the float64 matrix cores).  No atomics and a fixed order in every sum: equal inputs give equal bits.
+ *   srlx_dqnnot_bind_params : the ten parameter tensors by address, in state-dict order: hidden_block.0, v_block.0, v_block.2, adv_block.0, adv_block.2,
+ *                             weight then bias each.
+ *   srlx_dqnnot_bind_grads  : the caller's gradient tensors (same order and shapes), twice, as the sibling handles take them: after and before a norm clip.  The
+ *                             reference does not clip, so both receive the same values and the caller may pass the same tensors for both.
+ *   srlx_dqnnot_bind_adam   : exp_avg / exp_avg_sq (same order) and the optimiser steps already taken (the handle counts on from there; srlx_dqnnot_steps).
+ *   srlx_dqnnot_update      : the whole step of one batch in six launches, nothing synchronises.  d_states f32 [2 batch][D]: rows batch.. are the next states;
+ *                             d_actions i32 [batch] in 0..A-1; d_rewards, d_not_terminated, d_total_rewards f32 [batch]; d_weights f32 [batch] or NULL (every
+ *                             weight 1).  target = r + nd * discount * (max_a q(s') + v(s')) / 2; d = target - q[a];
+ *                             loss = mean(w huber_1(d)) + align_coeff mean(w (total_reward - q[a])^2), its gradient through rows 0..batch-1 only; then one Adam
+ *                             step at `lr` with the bound betas and eps.  Writes d_q, d_target f32 [batch] and d_losses f32 [2]: the two means. */
+typedef struct srlx_dqnnot srlx_dqnnot_t;
+int srlx_dqnnot_create(srlx_dqnnot_t **out, int obs_dim, int units, int n_actions, int64_t max_batch, int device);
+int srlx_dqnnot_destroy(srlx_dqnnot_t *h);
+int srlx_dqnnot_bind_params(srlx_dqnnot_t *h, float *const *d_params);
+int srlx_dqnnot_bind_grads(srlx_dqnnot_t *h, float *const *d_grads, float *const *d_raw_grads);
+int srlx_dqnnot_bind_adam(srlx_dqnnot_t *h, float *const *d_exp_avg, float *const *d_exp_avg_sq, int64_t steps_taken, double beta1, double beta2, double eps);
+int64_t srlx_dqnnot_steps(const srlx_dqnnot_t *h);
+int srlx_dqnnot_update(srlx_dqnnot_t *h, const float *d_states, const int32_t *d_actions, const float *d_rewards, const float *d_not_terminated,
+                       const float *d_total_rewards, const float *d_weights, int64_t batch, double discount, double align_coeff, double lr, float *d_q,
+                       float *d_target, float *d_losses, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -314,6 +314,13 @@ SIGNATURES = {
     "srlx_notsac_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
     "srlx_notsac_update_gemm": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
     "srlx_notsac_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_dqnnot_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_i64, c_int]),
+    "srlx_dqnnot_destroy": (c_int, [c_p]),
+    "srlx_dqnnot_bind_params": (c_int, [c_p, c_p]),
+    "srlx_dqnnot_bind_grads": (c_int, [c_p, c_p, c_p]),
+    "srlx_dqnnot_bind_adam": (c_int, [c_p, c_p, c_p, c_i64, c_f64, c_f64, c_f64]),
+    "srlx_dqnnot_steps": (c_i64, [c_p]),
+    "srlx_dqnnot_update": (c_int, [c_p] * 7 + [c_i64, c_f64, c_f64, c_f64] + [c_p] * 4),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

@@ -55,7 +55,8 @@ class SrlxUpdateBackend:
                 if wide:
                     self._srlx = update(self.parameter, max_batch=max(batch, min(wide, self.config.batch_size)), gemm_only=True)
                 else:
-                    self._srlx = update(self.parameter, max_batch=max(batch, min(256, self.config.batch_size)))
+                    # (an ordinary update's bound is its class's MAX_BATCH -- DqnNotUpdate: 4096 -- and 256 where the class declares none)
+                    self._srlx = update(self.parameter, max_batch=max(batch, min(getattr(update, "MAX_BATCH", 256), self.config.batch_size)))
         if self._backend == "torch":
             self._make_torch_update()
 
