@@ -9,7 +9,8 @@
 //   k_mlp_gemm_bwd    M = B, one job with two sources: dh = h > 0 ? dhv Wv1 + dha Wa1 : 0
 //   k_mlp_gemm_wgrad  the five Linears' weight and bias gradients as 32 x 32 tiles; its last workgroup reduces the two loss means
 //   k_dqnnot_step     srlxt::step_body with max_norm = +inf (the reference does not clip: coef is exactly 1) and Adam
-// The layer launches are srlx_mlp_gemm.h's on v_mfma_f64_16x16x4_f64, the table and the tail srlx_param_tail.h's; the head kernel is this file's.
+// The layer launches are srlx_mlp_gemm.h's on v_mfma_f64_16x16x4_f64, their four jobs and the weight gradient's tile table srlx_gemm_plan.h's,
+// the segment table and the tail srlx_param_tail.h's; the head kernel is this file's.
 //
 // k_dqnnot_head.  A workgroup of 4 waves stages the (1 + A) x U head weights (v_block.2's row, then adv_block.2's A rows) ONCE in LDS as float32, at most
 // 33 x 512 x 4 = 67 584 bytes of dynamic LDS, and its four waves take one item each.  A lane keeps the strips u = lane + 64 j of hv[b], ha[b], hv[B + b] and
@@ -209,8 +210,6 @@ void linear_shapes(const srlx_dqnnot *h, int (*shape)[2]) {
 
 // The segment table, the weight gradient's tile prefix and the four layer jobs, from the bound tensors.
 int upload_table(srlx_dqnnot *h) {
-    using srlxg::Job;
-    using srlxg::Src;
     int shape[kLinears][2];
     linear_shapes(h, shape);
     const int U = h->U, Z = 1 + h->A;
@@ -222,29 +221,22 @@ int upload_table(srlx_dqnnot *h) {
     memset(segs, 0, sizeof(segs));
     memset(lins, 0, sizeof(lins));
     i64 end = 0;
-    int tiles = 0;
-    for (int l = 0; l < kLinears; l++) {
-        srlxt::push_linear(segs + 2 * l, end, shape[l][0], shape[l][1], stride[l], dout[l], xin[l], h->ps, 2 * l);
-        tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
-        lins[l] = srlxg::WgradLin{tiles, shape[l][0], shape[l][1], (shape[l][1] + 1 + srlxg::kTile - 1) / srlxg::kTile};
-    }
+    for (int l = 0; l < kLinears; l++) srlxt::push_linear(segs + 2 * l, end, shape[l][0], shape[l][1], stride[l], dout[l], xin[l], h->ps, 2 * l);
+    srlxg::wgrad_table(shape, kLinears, lins);
     float *const *P = h->ps.p;
-    Job jobs[kJobs];
-    memset(jobs, 0, sizeof(jobs));
-    auto fwd = [&](Job &j, const float *x, int sel, int K, int lin, float *y) {
-        j.s[0] = Src{x, K, sel, P[2 * lin], K};
-        j.nsrc = 1, j.N = U, j.aux = P[2 * lin + 1], j.y = y, j.ldy = U, j.relu = 1;
-    };
-    fwd(jobs[0], nullptr, srlxg::kArg0, h->D, 0, h->h);
-    fwd(jobs[1], h->h, srlxg::kFromJob, U, 1, h->hv);
-    fwd(jobs[2], h->h, srlxg::kFromJob, U, 3, h->ha);
-    Job &bw = jobs[3];  // the value branch first, then the advantage branch: SumSeed's order
-    bw.s[0] = Src{h->dhv, U, srlxg::kFromJob, P[2], U};
-    bw.s[1] = Src{h->dha, U, srlxg::kFromJob, P[6], U};
-    bw.nsrc = 2, bw.N = U, bw.aux = h->h, bw.y = h->dh, bw.ldy = U;
+    srlxg::Plan<kJobs, 1> plan;  // (for the job table alone: srlx_dqnnot_update writes its four launches out, so the one step is begun and never read)
+    plan.clear();
+    plan.begin(srlxg::kFwd);
+    plan.fwd(nullptr, srlxg::kArg0, h->D, P[0], P[1], h->D, U, h->h, U, 1);
+    plan.fwd(h->h, srlxg::kFromJob, U, P[2], P[3], U, U, h->hv, U, 1);
+    plan.fwd(h->h, srlxg::kFromJob, U, P[6], P[7], U, U, h->ha, U, 1);
+    srlxg::Job &bw = plan.bwd(h->dh, U, h->h, U, U, 0);
+    plan.src(bw, h->dhv, U, U, P[2]);  // the value branch first, then the advantage branch: SumSeed's order
+    plan.src(bw, h->dha, U, U, P[6]);
+    SRLX_REQUIRE(!plan.overflow && plan.nj == kJobs, "dqnnot_update: the layer jobs do not fill their table of %d", kJobs);
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     SRLX_HIP(hipMemcpy(h->d_lins, lins, sizeof(lins), hipMemcpyHostToDevice));
-    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(jobs), hipMemcpyHostToDevice));
+    SRLX_HIP(hipMemcpy(h->d_jobs, plan.jobs, sizeof(plan.jobs), hipMemcpyHostToDevice));
     h->ps.table_ok = h->ps.net_ok = true;
     return SRLX_OK;
 }
@@ -273,10 +265,8 @@ int srlx_dqnnot_create(srlx_dqnnot_t **out, int obs_dim, int units, int n_action
     h->D = obs_dim, h->U = units, h->A = n_actions, h->device = device, h->max_batch = max_batch;
     int shape[kLinears][2];
     linear_shapes(h, shape);
-    for (int l = 0; l < kLinears; l++) {
-        h->elements += (i64)shape[l][0] * shape[l][1] + shape[l][0];
-        h->wgrad_tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
-    }
+    for (int l = 0; l < kLinears; l++) h->elements += (i64)shape[l][0] * shape[l][1] + shape[l][0];
+    h->wgrad_tiles = srlxg::wgrad_table(shape, kLinears, nullptr);
     const size_t plane = sizeof(float) * (size_t)max_batch * units;
     hipError_t e = hipMalloc((void **)&h->d_segs, sizeof(Seg) * kTensors);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_lins, sizeof(srlxg::WgradLin) * kLinears);

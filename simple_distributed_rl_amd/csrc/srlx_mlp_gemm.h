@@ -3,8 +3,10 @@
 // that is a GEMM-sized problem walked as chains, and this header is the other way to run it: V-PPO is the first consumer
 // (srlx_vppo.hip: srlx_vppo_update_gemm), NoT_SAC the second (srlx_notsac.hip: srlx_notsac_update_gemm, DESIGN.md 7u: k_mlp_gemm_fwd and a backward
 // kernel of its own on tile_sums), SAC-Discrete the third (srlx_sacd.hip: srlx_sacd_update_gemm, DESIGN.md 7v: both kernels and a first-layer kernel of its own
-// on tile_sums<false>, which hands it the two operands swapped).
-//   Job, Src          one GEMM of a launch: up to three (rows, weight) sources summed into one output tile, in the order a, b, c (SumSeed's order)
+// on tile_sums<false>, which hands it the two operands swapped), NoTarget_DQN the fourth (srlx_dqnnot.hip).  What the host needs to drive the kernels
+// is one piece of code for all of them: srlx_gemm_plan.h holds Job, Src, Launch, the plan builder and the weight gradient's table, and GemmPath
+// at the end of this header the path's device state.
+//   Job, Src          (srlx_gemm_plan.h) one GEMM of a launch: up to three (rows, weight) sources summed into one output tile, in the order a, b, c
 //   k_mlp_gemm_fwd    Y[M][N] = act(X[M][K] W[N][K]^T + b): the weight in torch's [out][in] layout, both operands contiguous along k
 //   k_mlp_gemm_bwd    dH[M][N] = H[M][N] > 0 ? sum_s dOut_s[M][n_s] W_s[n_s][N] : 0: the weight read untransposed, coalesced along the output column
 //   k_mlp_gemm_wgrad  dW[N][K] = dOut[M][N]^T X[M][K] and db[N] = sum_m dOut[m][N] of every Linear of a srlxt::Seg table in one launch, the batch the reduction
@@ -31,34 +33,16 @@
 
 #include <hip/hip_runtime.h>
 
+#include "srlx_gemm_plan.h"
 #include "srlx_param_tail.h"
 
 namespace srlxg {
 using i64 = int64_t;
 
 constexpr int kThreads = 256;
-constexpr int kTile = 32;    // rows and columns of a workgroup's output tile
 constexpr int kChunk = 64;   // reduction indices per LDS stage
 constexpr int kLdK = kChunk + 4;  // [row][k] stage: 68 floats (16-byte multiples: rows stay aligned for the float4 stores)
 constexpr int kLdN = kTile + 16;  // [k][column] stage: 48 floats
-constexpr int kMaxSrc = 3;
-
-enum Sel { kFromJob = 0, kArg0 = 1, kArg1 = 2 };  // where a source's rows come from: the job's own pointer, or one of the launch's two per-call pointers
-
-struct Src {
-    const float *a;  // rows [M][lda]
-    int lda, sel;
-    const float *w;  // forward [N][n] (row stride n); backward [n][N] (row stride N)
-    int n;           // reduction length
-};
-
-struct Job {
-    Src s[kMaxSrc];
-    int nsrc, N;        // sources in use; output columns
-    const float *aux;   // forward: bias [N]; backward: the kept activations [M][N] whose sign is the ReLU mask
-    float *y;           // [M][ldy]
-    int ldy, relu;      // (relu: forward only)
-};
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -222,13 +206,7 @@ static SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_bwd(const Job *_
 // 64 batch rows, 32 consecutive columns -- and staged [k][column] at stride kLdN, so the A fragment of lane l (row l % 16, k = l / 16) and the B fragment
 // (k = l / 16, column l % 16) are both As[(kk + l / 16) kLdN + quadrant + l % 16]: bank 48 (l / 16) + l % 16 mod 64, 64 different banks.  49 152 bytes of stage and
 // 2 048 of block_sum.  The same numeric contract; every workgroup leaves the float64 sum of the squares of the float32 values it stored in partials[blockIdx.x].
-struct WgradLin {  // one Linear of the table: segs[2 l] (weight) and segs[2 l + 1] (bias)
-    int tile_end;  // running tile count: blockIdx.x is searched here as grad_body searches segs[].end
-    int out, in, ktiles;  // ktiles = ceil((in + 1) / 32): tile t of the Linear is (t / ktiles, t % ktiles)
-};
-
-// tiles of one Linear
-inline int wgrad_tiles(int out, int in) { return ((out + kTile - 1) / kTile) * ((in + 1 + kTile - 1) / kTile); }
+// (WgradLin, the table's rows, and wgrad_table, which fills them: srlx_gemm_plan.h.)
 
 // One chunk of a [k][ld]-strided operand: reduction rows k0.. (below `n`), columns c0.. (below `cols`); 64 x 8 quads, two per thread.  `one` >= 0: column `one`
 // of every row below `n` reads 1.0f (the bias column; it lies at or behind `cols`).
@@ -329,15 +307,40 @@ SRLXG_KERNEL void __launch_bounds__(kThreads) k_mlp_gemm_wgrad(WgradArgs a, Tail
     if (threadIdx.x == 0) a.partials[tile] = sq[0];
 }
 
-// One launch of a plan: `njobs` jobs from `first` on in the device table, the widest of them `nmax` columns.
-struct Launch {
-    int first, njobs, nmax, bwd;
-};
-
 inline void launch(const Launch &l, const Job *d_jobs, int M, const float *x0, const float *x1, hipStream_t st) {
-    const dim3 grid((unsigned)((l.nmax + kTile - 1) / kTile), (unsigned)((M + kTile - 1) / kTile), (unsigned)l.njobs);
+    const Grid g = grid_of(l, M);
+    const dim3 grid((unsigned)g.x, (unsigned)g.y, (unsigned)g.z);
     if (l.bwd) hipLaunchKernelGGL(k_mlp_gemm_bwd, grid, dim3(kThreads), 0, st, d_jobs + l.first, M, x0, x1);
     else hipLaunchKernelGGL(k_mlp_gemm_fwd, grid, dim3(kThreads), 0, st, d_jobs + l.first, M, x0, x1);
 }
+
+// The path's device state in a handle: the scratch the layer launches write beside the handle's planes, the device copy of the plan's jobs, and
+// whether that copy holds the bound tensors (whatever makes the handle's segment table stale sets `ok` false).  `who` names the entry point in every message.
+template <int MaxJobs, int MaxSteps>
+struct GemmPath {
+    float *scratch;  // zeroed when allocated, at the path's first call
+    Job *d_jobs;     // [MaxJobs]: the plan's jobs, launch after launch
+    Plan<MaxJobs, MaxSteps> plan;
+    bool ok;
+
+    int ensure(size_t scratch_floats) {
+        if (scratch) return SRLX_OK;
+        SRLX_HIP(hipMalloc((void **)&scratch, sizeof(float) * scratch_floats));
+        SRLX_HIP(hipMemset(scratch, 0, sizeof(float) * scratch_floats));
+        SRLX_HIP(hipMalloc((void **)&d_jobs, sizeof(Job) * MaxJobs));
+        return SRLX_OK;
+    }
+    int upload(const char *who) {
+        SRLX_REQUIRE(!plan.overflow, "%s: the gemm plan asked for more than %d jobs, %d steps or %d sources of a job", who, MaxJobs, MaxSteps, kMaxSrc);
+        SRLX_HIP(hipMemcpy(d_jobs, plan.jobs, sizeof(Job) * plan.nj, hipMemcpyHostToDevice));
+        ok = true;
+        return SRLX_OK;
+    }
+    void release() {
+        if (scratch) (void)hipFree(scratch);
+        if (d_jobs) (void)hipFree(d_jobs);
+        scratch = nullptr, d_jobs = nullptr, ok = false;
+    }
+};
 
 }  // namespace srlxg

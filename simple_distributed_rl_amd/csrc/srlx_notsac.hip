@@ -30,7 +30,8 @@
 //   k_notsac_gemm_bwd        srlx_mlp_gemm.h's backward tile with NoT_SAC's three epilogues: the ReLU mask, the SiLU derivative behind a column range of
 //                            q_block's first weight, none (d loss / d action)
 //   k_notsac_gemm_head_grad  one thread per row or per row and element: the head's Jacobian
-// with k_notsac_grad and k_notsac_step as the tail of each half.
+// with k_notsac_grad and k_notsac_step as the tail of each half.  upload_gemm builds these steps on srlxg::Plan, the handle keeps them in a srlxg::GemmPath
+//  and update walks them; GemmScratch is the one statement of the path's scratch layout.
 #include "srlx_mlp_gemm.h"
 #include "srlx_notsac_math.h"
 #include "srlx_param_tail.h"
@@ -52,12 +53,9 @@ constexpr int kNetTensors = 10;  // policy: 2 x (3 layers + 2 heads); Q: 2 x (ac
 static_assert(2 * kNetTensors <= srlxt::kMaxTensors, "the policy's tensors, then the Q-network's, in one ParamSet");
 constexpr int kMaxWidth = 512;   // of a hidden layer and of the concatenated row
 
-// The gemm path's plan: a list of steps, each a launch of jobs from the device table or one of the pointwise kernels between them.
-enum StepKind { kFwd, kBwd, kNextAction, kEmbedBoth, kQLoss, kTailQ, kPiAction, kEmbedOne, kHeadGrad, kTailP };
-struct Step {
-    int kind;
-    srlxg::Launch l;  // kFwd, kBwd
-};
+// The gemm path's plan (srlxg::Plan): a list of steps, each a launch of jobs from the device table (srlxg::kFwd; srlxg::kBwd, here through
+// k_notsac_gemm_bwd) or one of the pointwise kernels between them.
+enum StepKind { kNextAction = srlxg::kBwd + 1, kEmbedBoth, kQLoss, kTailQ, kPiAction, kEmbedOne, kHeadGrad, kTailP };
 constexpr int kGemmSteps = 40;  // target half: 3 + 1 policy, 2 pointwise, 3 + 1 Q, 1 pointwise, 3 + 1 backward, the tail; policy half: 20
 constexpr int kGemmJobs = 40;   // target half: 3 + 2, 2 x (3 + 1), 3 + 1; policy half: 3 + 2, 3 + 1, 3 + 1 + 1, 3
 enum Epilogue { kEpiRelu = 0, kEpiSilu = 1, kEpiNone = 2 };  // of a k_notsac_gemm_bwd job, in Job::relu
@@ -88,13 +86,8 @@ struct srlx_notsac {
     float *dlast_p;     // [max_batch][kHeadCols]: d loss / d (head outputs)
     float *rows;        // [3][max_batch]: the rows' Huber terms, MSE terms and q(s, pi(s))
     double *partials;   // [max(blocks_p, blocks_q)]: sums of squared gradients
-    // srlx_notsac_update_gemm's own, allocated at its first call
-    float *gemm_scratch;  // two planes [max_batch][wmax] (the layers nothing keeps, in turn), the s' rows of xcat, the head rows and d loss / d action
-                          // [max_batch][kHeadCols] each, q(s', a') and q(s, a) [2][max_batch]
-    srlxg::Job *d_jobs;   // [kGemmJobs]: the plan's jobs, launch after launch
-    Step plan[kGemmSteps];
-    int n_steps;
-    bool gemm_ok;         // the job table holds the bound tensors (upload_table makes it stale)
+    // srlx_notsac_update_gemm's own, allocated at its first call; scratch: GemmScratch
+    srlxg::GemmPath<kGemmJobs, kGemmSteps> path;
 };
 
 namespace {
@@ -591,122 +584,117 @@ int upload_table(srlx_notsac *h) {
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     h->ps.table_ok = true;
-    h->gemm_ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
+    h->path.ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
     return SRLX_OK;
 }
+
+// the gemm path's scratch: upload_gemm and update share this layout
+struct GemmScratch {
+    float *sp[2];  // two planes [max_batch][wmax]: the layers nothing keeps, in turn
+    float *xcat2;  // [max_batch][D + E]: the s' rows of xcat
+    float *z, *ga; // [max_batch][kHeadCols] each: the head rows and d loss / d action
+    float *qv;     // [2][max_batch]: q(s', a') and q(s, a)
+    static size_t floats(const srlx_notsac *h) {
+        const size_t mb = (size_t)h->max_batch;
+        return 2 * mb * h->wmax + mb * (h->D + h->E) + 2 * mb * kHeadCols + 2 * mb;
+    }
+    GemmScratch(const srlx_notsac *h) {
+        const i64 mb = h->max_batch, plane = mb * h->wmax;
+        float *g = h->path.scratch;
+        sp[0] = g, sp[1] = g + plane, xcat2 = g + 2 * plane, z = xcat2 + mb * (h->D + h->E), ga = z + mb * kHeadCols, qv = ga + mb * kHeadCols;
+    }
+};
 
 // The gemm path's plan: every Linear with a reduction length worth a tile is one job, jobs of equal depth share a launch, the pointwise kernels
 // stand between them.  The planes, and the layout upload_table hands to the tail, are the row path's; what the row path keeps in LDS only (the s' rows, the
 // head rows, d loss / d action) goes through the path's own scratch, allocated at its first call.
-int upload_gemm(srlx_notsac *h) {
+int upload_gemm(const char *who, srlx_notsac *h) {
     using srlxg::Job;
     const i64 mb = h->max_batch, plane = mb * h->wmax;
     const int D = h->D, A = h->A, E = h->E, Lp = h->Lp, Lq = h->Lq, W = D + E;
-    if (!h->gemm_scratch) {
-        const size_t bytes = sizeof(float) * (size_t)(2 * plane + mb * W + 2 * mb * kHeadCols + 2 * mb);
-        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, bytes));
-        SRLX_HIP(hipMemset(h->gemm_scratch, 0, bytes));
-        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
-    }
-    float *sp[2] = {h->gemm_scratch, h->gemm_scratch + plane};
-    float *xcat2 = h->gemm_scratch + 2 * plane, *z = xcat2 + mb * W, *ga = z + mb * kHeadCols, *qv = ga + mb * kHeadCols;
-    Job jobs[kGemmJobs];
-    memset(jobs, 0, sizeof(jobs));
-    int nj = 0, ns = 0;
+    SRLX_TRY(h->path.ensure(GemmScratch::floats(h)));
+    const GemmScratch sc(h);
+    float *const *sp = sc.sp, *xcat2 = sc.xcat2, *z = sc.z, *ga = sc.ga, *qv = sc.qv;
+    auto &p = h->path.plan;
+    p.clear();
     float *const *P = h->ps.p, *const *Q = h->ps.p + h->ntp;  // Q: act_block, q_block's layers, q_out
-    auto point = [&](int kind) { h->plan[ns++] = Step{kind, srlxg::Launch{0, 0, 0, 0}}; };
-    auto begin = [&](int bwd) { h->plan[ns] = Step{bwd ? kBwd : kFwd, srlxg::Launch{nj, 0, 0, bwd}}; };
-    auto add = [&](int width) -> Job & {  // (width: the columns the job writes)
-        srlxg::Launch &l = h->plan[ns].l;
-        l.njobs++, l.nmax = width > l.nmax ? width : l.nmax;
-        return jobs[nj++];
-    };
-    auto fwd = [&](const float *x, int sel, int K, float *const *lin, int N, float *y, int ldy, int relu) {
-        Job &j = add(N);
-        j.s[0] = srlxg::Src{x, K, sel, lin[0], K};
-        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = ldy, j.relu = relu;
-    };
-    auto bwd = [&](float *y, int ldy, const float *aux, int N, int width, int epi) -> Job & {
-        Job &j = add(width);
-        j.nsrc = 0, j.N = N, j.aux = aux, j.y = y, j.ldy = ldy, j.relu = epi;
-        return j;
-    };
-    auto src = [&](Job &j, const float *a, int lda, int n, const float *w) { j.s[j.nsrc++] = srlxg::Src{a, lda, srlxg::kFromJob, w, n}; };
+    auto fwd = [&](const float *x, int sel, int K, float *const *lin, int N, float *y, int ldy, int relu) { p.fwd(x, sel, K, lin[0], lin[1], K, N, y, ldy, relu); };
     // the policy's hidden layers and head on the rows of launch argument `sel`: kept in hp's planes, or through the two scratch planes in turn
     auto plan_policy = [&](int sel, bool keep) {
         const float *x = nullptr;
         int in = D;
-        for (int l = 0; l < Lp; in = h->Wp[l], l++, ns++) {
+        for (int l = 0; l < Lp; in = h->Wp[l], l++) {
             float *y = keep ? h->hp + l * plane : sp[l & 1];
-            begin(0);
+            p.begin(srlxg::kFwd);
             fwd(x, l ? srlxg::kFromJob : sel, in, P + 2 * l, h->Wp[l], y, h->Wp[l], 1);
+            p.end();
             x = y;
         }
-        begin(0);
+        p.begin(srlxg::kFwd);
         fwd(x, 0, in, P + 2 * Lp, A, z, kHeadCols, 0);
         if (h->head) fwd(x, 0, in, P + 2 * (Lp + 1), A, z + kNormalLs, kHeadCols, 0);
-        ns++;
+        p.end();
     };
     // q_block and q_out on the kept rows (xcat -> hq's planes -> q_kept) and, `both`, on the s' rows (xcat2 -> the scratch planes -> qv[0])
     auto plan_q = [&](bool both, float *q_kept) {
         const float *x = h->xcat, *x2 = xcat2;
         int in = W;
-        for (int l = 0; l < Lq; in = h->Wq[l], l++, ns++) {
-            begin(0);
+        for (int l = 0; l < Lq; in = h->Wq[l], l++) {
+            p.begin(srlxg::kFwd);
             fwd(x, 0, in, Q + 2 + 2 * l, h->Wq[l], h->hq + l * plane, h->Wq[l], 1);
             if (both) fwd(x2, 0, in, Q + 2 + 2 * l, h->Wq[l], sp[l & 1], h->Wq[l], 1);
+            p.end();
             x = h->hq + l * plane, x2 = sp[l & 1];
         }
-        begin(0);
+        p.begin(srlxg::kFwd);
         fwd(x, 0, in, Q + 2 + 2 * Lq, 1, q_kept, 1, 0);
         if (both) fwd(x2, 0, in, Q + 2 + 2 * Lq, 1, qv, 1, 0);
-        ns++;
+        p.end();
     };
     // from dlast_q down q_block (the masks of hq's planes, into dhq's), then through the embedding columns of its first weight and the SiLU derivative into dact
     auto plan_q_back = [&]() {
-        for (int l = Lq - 1; l >= 0; l--, ns++) {
-            begin(1);
-            Job &j = bwd(h->dhq + l * plane, h->Wq[l], h->hq + l * plane, h->Wq[l], h->Wq[l], kEpiRelu);
-            if (l == Lq - 1) src(j, h->dlast_q, 1, 1, Q[2 + 2 * Lq]);
-            else src(j, h->dhq + (l + 1) * plane, h->Wq[l + 1], h->Wq[l + 1], Q[2 + 2 * (l + 1)]);
+        for (int l = Lq - 1; l >= 0; l--) {
+            p.begin(srlxg::kBwd);
+            Job &j = p.bwd(h->dhq + l * plane, h->Wq[l], h->hq + l * plane, h->Wq[l], h->Wq[l], kEpiRelu);
+            if (l == Lq - 1) p.src(j, h->dlast_q, 1, 1, Q[2 + 2 * Lq]);
+            else p.src(j, h->dhq + (l + 1) * plane, h->Wq[l + 1], h->Wq[l + 1], Q[2 + 2 * (l + 1)]);
+            p.end();
         }
-        begin(1);
-        src(bwd(h->dact, E, h->zact, W, E, kEpiSilu), h->dhq, h->Wq[0], h->Wq[0], Q[2]);
-        ns++;
+        p.begin(srlxg::kBwd);
+        p.src(p.bwd(h->dact, E, h->zact, W, E, kEpiSilu), h->dhq, h->Wq[0], h->Wq[0], Q[2]);
+        p.end();
     };
     // ---- the target half and the Q step
     plan_policy(srlxg::kArg1, false);
-    point(kNextAction);
-    point(kEmbedBoth);
+    p.point(kNextAction);
+    p.point(kEmbedBoth);
     plan_q(true, qv + mb);
-    point(kQLoss);
+    p.point(kQLoss);
     plan_q_back();
-    point(kTailQ);
+    p.point(kTailQ);
     // ---- the policy half, through the Q-network as it stands now: its planes, xcat, zact and dact are free again
     plan_policy(srlxg::kArg0, true);
-    point(kPiAction);
-    point(kEmbedOne);
+    p.point(kPiAction);
+    p.point(kEmbedOne);
     plan_q(false, h->rows + 2 * mb);
     plan_q_back();
-    begin(1);
-    src(bwd(ga, kHeadCols, nullptr, A, A, kEpiNone), h->dact, E, E, Q[0]);
-    ns++;
-    point(kHeadGrad);
-    for (int l = Lp - 1; l >= 0; l--, ns++) {
-        begin(1);
-        Job &j = bwd(h->dhp + l * plane, h->Wp[l], h->hp + l * plane, h->Wp[l], h->Wp[l], kEpiRelu);
+    p.begin(srlxg::kBwd);
+    p.src(p.bwd(ga, kHeadCols, nullptr, A, A, kEpiNone), h->dact, E, E, Q[0]);
+    p.end();
+    p.point(kHeadGrad);
+    for (int l = Lp - 1; l >= 0; l--) {
+        p.begin(srlxg::kBwd);
+        Job &j = p.bwd(h->dhp + l * plane, h->Wp[l], h->hp + l * plane, h->Wp[l], h->Wp[l], kEpiRelu);
         if (l < Lp - 1) {
-            src(j, h->dhp + (l + 1) * plane, h->Wp[l + 1], h->Wp[l + 1], P[2 * (l + 1)]);
-            continue;
+            p.src(j, h->dhp + (l + 1) * plane, h->Wp[l + 1], h->Wp[l + 1], P[2 * (l + 1)]);
+        } else {
+            p.src(j, h->dlast_p, kHeadCols, A, P[2 * Lp]);  // SumSeed's order: the head, then the log-scale head
+            if (h->head) p.src(j, h->dlast_p + kNormalLs, kHeadCols, A, P[2 * (Lp + 1)]);
         }
-        src(j, h->dlast_p, kHeadCols, A, P[2 * Lp]);  // SumSeed's order: the head, then the log-scale head
-        if (h->head) src(j, h->dlast_p + kNormalLs, kHeadCols, A, P[2 * (Lp + 1)]);
+        p.end();
     }
-    point(kTailP);
-    h->n_steps = ns;  // (at most 16 + 20 steps and 17 + 17 jobs, at three layers everywhere and a Normal head)
-    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
-    h->gemm_ok = true;
-    return SRLX_OK;
+    p.point(kTailP);
+    return h->path.upload(who);  // (at most 16 + 20 steps and 17 + 17 jobs, at three layers everywhere and a Normal head)
 }
 
 void fill(srlx_notsac *h, int D, int head, int A, int np, const int *pw, int nq, const int *qw, int E, i64 max_batch, int device) {
@@ -750,7 +738,7 @@ int update(const char *who, bool gemm, srlx_notsac *h, int64_t batch, const floa
     srlx::DeviceGuard g(h->device);
     if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
     if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
-    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
+    if (gemm && !h->path.ok) SRLX_TRY(upload_gemm(who, h));
     hipStream_t st = (hipStream_t)stream;
     const double inv_b = 1.0 / (double)batch;
     const Cfg c{(float)discount, (float)loss_align_coeff, (float)log_scale_lo, (float)log_scale_hi, inv_b, squashed};
@@ -782,24 +770,25 @@ int update(const char *who, bool gemm, srlx_notsac *h, int64_t batch, const floa
         hipLaunchKernelGGL(k_notsac_pi_rows, row_grid, dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, ra, rpw, h->D, h->A, h->E, lds_stride(h));
         tail_p();
     } else {
-        const i64 mb = h->max_batch, plane = mb * h->wmax;
+        const i64 mb = h->max_batch;
         const int D = h->D, A = h->A, E = h->E, W = D + E, M = (int)batch;
-        float *xcat2 = h->gemm_scratch + 2 * plane, *z = xcat2 + mb * W, *ga = z + mb * kHeadCols, *qv = ga + mb * kHeadCols;  // (upload_gemm's layout)
+        const GemmScratch sc(h);
+        float *xcat2 = sc.xcat2, *z = sc.z, *ga = sc.ga, *qv = sc.qv;
         const float *wa = h->ps.p[h->ntp], *ba = h->ps.p[h->ntp + 1];
         const i64 heads = h->head ? batch * A : batch;  // threads of the kernels that run one per row and element (Normal) or per row (Gumbel)
         const dim3 head_grid((unsigned)((heads + kRowThreads - 1) / kRowThreads)), row_grid((unsigned)((batch + kRowThreads - 1) / kRowThreads));
         const unsigned embed_blocks = (unsigned)((batch * W + kThreads - 1) / kThreads);
         const EmbedSet kept{d_states, h->ain, h->xcat, h->zact}, next{d_next_states, d_next_action, xcat2, nullptr};
-        for (int i = 0; i < h->n_steps; i++) {
-            const Step &s = h->plan[i];
+        for (int i = 0; i < h->path.plan.ns; i++) {
+            const srlxg::Step &s = h->path.plan.steps[i];
+            const srlxg::Grid gr = srlxg::grid_of(s.l, M);
             switch (s.kind) {
-            case kFwd:
-                srlxg::launch(s.l, h->d_jobs, M, d_states, d_next_states, st);
+            case srlxg::kFwd:
+                srlxg::launch(s.l, h->path.d_jobs, M, d_states, d_next_states, st);
                 break;
-            case kBwd:
-                hipLaunchKernelGGL(k_notsac_gemm_bwd, dim3((unsigned)((s.l.nmax + srlxg::kTile - 1) / srlxg::kTile), (unsigned)((M + srlxg::kTile - 1) / srlxg::kTile),
-                                                           (unsigned)s.l.njobs),
-                                   dim3(srlxg::kThreads), 0, st, (const srlxg::Job *)h->d_jobs + s.l.first, M, D);
+            case srlxg::kBwd:
+                hipLaunchKernelGGL(k_notsac_gemm_bwd, dim3((unsigned)gr.x, (unsigned)gr.y, (unsigned)gr.z), dim3(srlxg::kThreads), 0, st,
+                                   (const srlxg::Job *)h->path.d_jobs + s.l.first, M, D);
                 break;
             case kNextAction:
                 hipLaunchKernelGGL(k_notsac_gemm_action, head_grid, dim3(kRowThreads), 0, st,
@@ -889,8 +878,9 @@ int srlx_notsac_destroy(srlx_notsac_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
     for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->hp, (void *)h->dhp, (void *)h->hq, (void *)h->dhq, (void *)h->xcat, (void *)h->zact, (void *)h->dact,
-                    (void *)h->ain, (void *)h->dlast_q, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials, (void *)h->gemm_scratch, (void *)h->d_jobs})
+                    (void *)h->ain, (void *)h->dlast_q, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials})
         if (p) (void)hipFree(p);
+    h->path.release();
     delete h;
     return SRLX_OK;
 }

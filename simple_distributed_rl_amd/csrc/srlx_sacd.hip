@@ -22,6 +22,7 @@
 //                           [B A][W0] plane) or for the action taken (one row per item).  The policy's first layer rides as a job without the one-hot term
 //   k_sacd_gemm_target_q    one thread per item: min over the two targets, soft_target into y; then q1, q2, the squared-error rows and the seeds into dlast
 //   k_sacd_gemm_policy_row  one thread per item: min over the two stepped Q-networks, policy_row: entropy, the loss row, dz into dlast
+// upload_gemm builds the steps on srlxg::Plan, the handle keeps them in a srlxg::GemmPath and update walks them.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_mlp_gemm.h"
 #include "srlx_param_tail.h"
@@ -41,13 +42,10 @@ constexpr int kMaxSegs = 16;  // q1 + q2: 2 networks x 4 layers x (weight, bias)
 // one network in device memory: the policy has In = D and Out = A, a Q-network In = D + A and Out = 1
 using NetD = srlxm::Layers;
 
-// The gemm path's plan: a list of steps, each a launch of jobs from the device table or one of the pointwise kernels between them.
-enum StepKind { kFirst, kFwdItems, kFwdActions, kBwd, kTargetQ, kGradQ, kPolicyRow, kGradP };  // (kFwdItems: M = B rows; kFwdActions: M = B A rows)
-struct Step {
-    int kind;
-    srlxg::Launch l;
-};
-constexpr int kGemmJobs = 48, kGemmSteps = 24;
+// The gemm path's plan (srlxg::Plan): a list of steps, each a launch of jobs from the device table or one of the pointwise kernels between them.
+// srlxg::kFwd and srlxg::kBwd run on M = B rows; kFwdActions is k_mlp_gemm_fwd on M = B A rows, kFirst k_sacd_gemm_first.
+enum StepKind { kFirst = srlxg::kBwd + 1, kFwdActions, kTargetQ, kGradQ, kPolicyRow, kGradP };
+constexpr int kGemmJobs = 48, kGemmSteps = 24;  // (upload_gemm: at most 41 jobs and 21 steps)
 // Job::relu of a k_sacd_gemm_first job: what its epilogue adds and where its rows go
 enum FirstMode { kPlain = 0, kAllActions = 1, kTaken = 2, kModeMask = 3, kWriteX0 = 4 };
 
@@ -82,12 +80,9 @@ struct srlx_sacd {
     float *h, *dh;  // planes [net 0..2][layer 0..2][max_batch][wmax]
     float *dlast;   // [3][max_batch][16]: d loss / d (out layer output)
     float *rows;    // [3][max_batch]: squared errors of q1, q2; the policy loss rows
-    // srlx_sacd_update_gemm's own, allocated at its first call
-    float *gemm_scratch;  // the all-action planes [2 networks][2][max_batch A][widest q layer], two planes for policy(s'), logits, Q values, row arrays
-    srlxg::Job *d_jobs;   // [kGemmJobs]: the plan's jobs, launch after launch
-    Step plan[kGemmSteps];
-    int n_steps;
-    bool gemm_ok;  // the job table holds the bound tensors (upload_tables makes it stale)
+    // srlx_sacd_update_gemm's own, allocated at its first call; scratch (GemmScratch): the all-action planes [2 networks][2][max_batch A]
+    // [widest q layer], two planes for policy(s'), logits, Q values, row arrays
+    srlxg::GemmPath<kGemmJobs, kGemmSteps> path;
 };
 
 namespace {
@@ -623,7 +618,7 @@ int upload_tables(srlx_sacd *h) {
     }
     SRLX_HIP(hipMemcpy(h->d_segs, segs, sizeof(segs), hipMemcpyHostToDevice));
     h->table_ok = h->nets_ok = true;
-    h->gemm_ok = false;  // (whatever made these tables stale made the gemm path's jobs stale)
+    h->path.ok = false;  // (whatever made these tables stale made the gemm path's jobs stale)
     return SRLX_OK;
 }
 
@@ -645,45 +640,23 @@ struct GemmScratch {
 // The gemm path's plan.  Launch d of the forward chains holds layer d of every network that has one.  The first layers share ONE launch of
 // k_sacd_gemm_first; above it the networks on B rows (policy(s'), policy(s), q1 and q2 on (s, action)) share a k_mlp_gemm_fwd launch and the two Q-networks on
 // B A rows another.  policy(s) and the Q step's forward ride in the target half's launches: neither reads y, and the policy is stepped only at the very end.
-int upload_gemm(srlx_sacd *h) {
-    using srlxg::Job;
+int upload_gemm(const char *who, srlx_sacd *h) {
     const i64 mb = h->max_batch, plane = mb * h->wmax;
     const int D = h->D, A = h->A, Lp = h->Lp, Lq = h->Lq;
     const GemmScratch sc(h);
-    if (!h->gemm_scratch) {
-        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, sizeof(float) * (size_t)sc.total));
-        SRLX_HIP(hipMemset(h->gemm_scratch, 0, sizeof(float) * (size_t)sc.total));
-        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
-    }
-    float *g = h->gemm_scratch;
-    Job jobs[kGemmJobs];
-    memset(jobs, 0, sizeof(jobs));
-    int nj = 0, ns = 0;
-    auto point = [&](int kind) { h->plan[ns++] = Step{kind, srlxg::Launch{0, 0, 0, 0}}; };
-    auto begin = [&](int kind) { h->plan[ns] = Step{kind, srlxg::Launch{nj, 0, 0, kind == kBwd}}; };
-    auto end = [&]() { ns += h->plan[ns].l.njobs ? 1 : 0; };  // (a launch nothing joined is no step)
-    auto add = [&](int width) -> Job & {
-        srlxg::Launch &l = h->plan[ns].l;
-        l.njobs++, l.nmax = width > l.nmax ? width : l.nmax;
-        return jobs[nj++];
-    };
-    auto first = [&](int sel, int In, float *const *lin, int N, float *y, int mode) {
-        Job &j = add(N);
-        j.s[0] = srlxg::Src{nullptr, D, sel, lin[0], In};
-        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = N, j.relu = mode;
-    };
-    auto fwd = [&](const float *x, int K, float *const *lin, int N, float *y, int ldy, int relu) {
-        Job &j = add(N);
-        j.s[0] = srlxg::Src{x, K, srlxg::kFromJob, lin[0], K};
-        j.nsrc = 1, j.N = N, j.aux = lin[1], j.y = y, j.ldy = ldy, j.relu = relu;
-    };
+    SRLX_TRY(h->path.ensure((size_t)sc.total));
+    float *g = h->path.scratch;
+    auto &p = h->path.plan;
+    p.clear();
+    // a first layer: the WHOLE weight [N][In] with the states (row stride D, launch argument `sel`) as its rows; `mode`: FirstMode
+    auto first = [&](int sel, int In, float *const *lin, int N, float *y, int mode) { p.fwd(nullptr, sel, D, lin[0], lin[1], In, N, y, N, mode); };
+    auto fwd = [&](const float *x, int K, float *const *lin, int N, float *y, int ldy, int relu) { p.fwd(x, srlxg::kFromJob, K, lin[0], lin[1], K, N, y, ldy, relu); };
     // d loss / d h_l of trained network t (0 policy, 1 q1, 2 q2): the out layer's seed rows in dlast through its weight, or the plane above through the next one
     auto bwd = [&](int t, int l, int L, const int *W, int Out, float *const *P) {
-        Job &j = add(W[l]);
         const i64 pl = ((i64)t * 3 + l) * plane;
-        if (l == L - 1) j.s[0] = srlxg::Src{h->dlast + (i64)t * mb * kRows, kRows, srlxg::kFromJob, P[2 * L], Out};
-        else j.s[0] = srlxg::Src{h->dh + pl + plane, W[l + 1], srlxg::kFromJob, P[2 * (l + 1)], W[l + 1]};
-        j.nsrc = 1, j.N = W[l], j.aux = h->h + pl, j.y = h->dh + pl, j.ldy = W[l];
+        srlxg::Job &j = p.bwd(h->dh + pl, W[l], h->h + pl, W[l], W[l], 0);
+        if (l == L - 1) p.src(j, h->dlast + (i64)t * mb * kRows, kRows, Out, P[2 * L]);
+        else p.src(j, h->dh + pl + plane, W[l + 1], W[l + 1], P[2 * (l + 1)]);
     };
     // layer l >= 1 of a chain whose hidden rows go to plane(l) (row stride = the layer's width) and whose out layer writes `out` with row stride `ldo`
     auto layer = [&](int l, int L, const int *W, int Out, float *const *P, auto plane_of, float *out, int ldo) {
@@ -696,57 +669,54 @@ int upload_gemm(srlx_sacd *h) {
     auto next_policy = [&](int l) { return g + sc.ps + (l & 1) * (sc.z2 - sc.ps) / 2; };
     const int Lmax = Lp > Lq ? Lp : Lq;
     // ---- the target half, with policy(s) and the Q step's forward in its launches
-    begin(kFirst);
+    p.begin(kFirst);
     first(srlxg::kArg1, D, h->p[0], h->Wp[0], next_policy(0), kPlain);
     first(srlxg::kArg0, D, h->p[0], h->Wp[0], kept(0)(0), kPlain);
     first(srlxg::kArg0, D + A, h->p[1], h->Wq[0], kept(1)(0), kTaken | kWriteX0);
     first(srlxg::kArg0, D + A, h->p[3], h->Wq[0], kept(2)(0), kTaken);
     first(srlxg::kArg1, D + A, h->p[2], h->Wq[0], all_actions(0)(0), kAllActions);
     first(srlxg::kArg1, D + A, h->p[4], h->Wq[0], all_actions(1)(0), kAllActions);
-    end();
-    for (int l = 1; l <= Lmax; l++) {  // (layer() adds nothing past a chain's out layer; end() drops a launch nothing joined)
-        begin(kFwdItems);
+    p.end();
+    for (int l = 1; l <= Lmax; l++) {  // (layer() adds nothing past a chain's out layer; p.end() drops a launch nothing joined)
+        p.begin(srlxg::kFwd);
         layer(l, Lp, h->Wp, A, h->p[0], next_policy, g + sc.z2, kRows);
         layer(l, Lp, h->Wp, A, h->p[0], kept(0), g + sc.z1, kRows);
         layer(l, Lq, h->Wq, 1, h->p[1], kept(1), g + sc.qsa, 1);
         layer(l, Lq, h->Wq, 1, h->p[3], kept(2), g + sc.qsa + mb, 1);
-        end();
-        begin(kFwdActions);
+        p.end();
+        p.begin(kFwdActions);
         layer(l, Lq, h->Wq, 1, h->p[2], all_actions(0), g + sc.qa, 1);
         layer(l, Lq, h->Wq, 1, h->p[4], all_actions(1), g + sc.qb, 1);
-        end();
+        p.end();
     }
-    point(kTargetQ);
+    p.point(kTargetQ);
     // ---- the Q step's data gradients and its parameter step
     for (int l = Lq - 1; l >= 0; l--) {
-        begin(kBwd);
+        p.begin(srlxg::kBwd);
         bwd(1, l, Lq, h->Wq, 1, h->p[1]);
         bwd(2, l, Lq, h->Wq, 1, h->p[3]);
-        end();
+        p.end();
     }
-    point(kGradQ);
+    p.point(kGradQ);
     // ---- the policy half: the stepped Q-networks over every action of s, policy_row on the logits kept above, the policy's chain
-    begin(kFirst);
+    p.begin(kFirst);
     first(srlxg::kArg0, D + A, h->p[1], h->Wq[0], all_actions(0)(0), kAllActions);
     first(srlxg::kArg0, D + A, h->p[3], h->Wq[0], all_actions(1)(0), kAllActions);
-    end();
+    p.end();
     for (int l = 1; l <= Lq; l++) {
-        begin(kFwdActions);
+        p.begin(kFwdActions);
         layer(l, Lq, h->Wq, 1, h->p[1], all_actions(0), g + sc.qa, 1);
         layer(l, Lq, h->Wq, 1, h->p[3], all_actions(1), g + sc.qb, 1);
-        end();
+        p.end();
     }
-    point(kPolicyRow);
+    p.point(kPolicyRow);
     for (int l = Lp - 1; l >= 0; l--) {
-        begin(kBwd);
+        p.begin(srlxg::kBwd);
         bwd(0, l, Lp, h->Wp, A, h->p[0]);
-        end();
+        p.end();
     }
-    point(kGradP);
-    h->n_steps = ns;  // (at most 21 steps and 41 jobs, at three layers everywhere)
-    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
-    h->gemm_ok = true;
-    return SRLX_OK;
+    p.point(kGradP);
+    return h->path.upload(who);  // (at most 21 steps and 41 jobs, at three layers everywhere)
 }
 
 i64 elements(int In, int L, const int *W, int Out) {
@@ -813,9 +783,9 @@ int srlx_sacd_create(srlx_sacd_t **out, int obs_dim, int n_actions, int n_policy
 int srlx_sacd_destroy(srlx_sacd_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
-    for (void *p : {(void *)h->d_nets, (void *)h->d_segs, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->dlast, (void *)h->rows, (void *)h->gemm_scratch,
-                    (void *)h->d_jobs})
+    for (void *p : {(void *)h->d_nets, (void *)h->d_segs, (void *)h->x0, (void *)h->h, (void *)h->dh, (void *)h->dlast, (void *)h->rows})
         if (p) (void)hipFree(p);
+    h->path.release();
     delete h;
     return SRLX_OK;
 }
@@ -947,7 +917,7 @@ int update(const char *who, bool gemm, srlx_sacd *h, int64_t batch, const float 
     SRLX_REQUIRE((hard_sync == 0 || hard_sync == 1) && (auto_scale == 0 || auto_scale == 1), "%s: hard_sync and auto_scale are 0 or 1", who);
     srlx::DeviceGuard g(h->device);
     if (!h->table_ok) SRLX_TRY(upload_tables(h));
-    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
+    if (gemm && !h->path.ok) SRLX_TRY(upload_gemm(who, h));
     hipStream_t st = (hipStream_t)stream;
     const int S = lds_stride(h), D = h->D, A = h->A;
     const size_t lds = lds_bytes(h);
@@ -987,24 +957,25 @@ int update(const char *who, bool gemm, srlx_sacd *h, int64_t batch, const float 
         grad_policy();
     } else {
         const GemmScratch sc(h);
-        float *gs = h->gemm_scratch;
+        float *gs = h->path.scratch;
+        const srlxg::Job *d_jobs = h->path.d_jobs;
         const int M = (int)batch;
-        const unsigned item_tiles = (unsigned)((M + srlxg::kTile - 1) / srlxg::kTile);
         const dim3 row_grid((unsigned)((batch + kRowThreads - 1) / kRowThreads));
-        for (int i = 0; i < h->n_steps; i++) {
-            const Step &s = h->plan[i];
+        for (int i = 0; i < h->path.plan.ns; i++) {
+            const srlxg::Step &s = h->path.plan.steps[i];
+            const srlxg::Grid fg = srlxg::grid_of(s.l, M);  // (kFirst: unit tiles, item tiles, jobs)
             GemmRows gr{gs + sc.z2, gs + sc.qa, gs + sc.qb, gs + sc.qsa, gs + sc.t0, gs + sc.t1, h->max_batch};
             switch (s.kind) {
             case kFirst:
-                hipLaunchKernelGGL(k_sacd_gemm_first, dim3((unsigned)((s.l.nmax + srlxg::kTile - 1) / srlxg::kTile), item_tiles, (unsigned)s.l.njobs), dim3(srlxg::kThreads), 0,
-                                   st, (const srlxg::Job *)h->d_jobs + s.l.first, M, d_states, d_next_states, d_actions, h->x0, D, A);
+                hipLaunchKernelGGL(k_sacd_gemm_first, dim3((unsigned)fg.x, (unsigned)fg.y, (unsigned)fg.z), dim3(srlxg::kThreads), 0, st, d_jobs + s.l.first, M, d_states,
+                                   d_next_states, d_actions, h->x0, D, A);
                 break;
-            case kFwdItems:
-            case kBwd:
-                srlxg::launch(s.l, h->d_jobs, M, nullptr, nullptr, st);
+            case srlxg::kFwd:
+            case srlxg::kBwd:
+                srlxg::launch(s.l, d_jobs, M, nullptr, nullptr, st);
                 break;
             case kFwdActions:
-                srlxg::launch(s.l, h->d_jobs, M * A, nullptr, nullptr, st);
+                srlxg::launch(s.l, d_jobs, M * A, nullptr, nullptr, st);
                 break;
             case kTargetQ:
                 hipLaunchKernelGGL(k_sacd_gemm_target_q, row_grid, dim3(kRowThreads), 0, st, b, gr, (const float *)h->log_alpha, (float)discount, A, d_q1, d_q2, h->rows,

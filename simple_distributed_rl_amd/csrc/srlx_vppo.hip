@@ -18,6 +18,8 @@
 //                   action (the same two row buffers)
 // LDS: three row buffers of 16 x (widest row + 1) floats (the trunk's output has to outlive the value branch) and the 32 KB weight tile: 131 264 bytes at
 // widths of 512, one workgroup per compute unit, which is all these launches (<= 16 workgroups) ask for.
+// srlx_vppo_update_gemm is the same update layer by layer on srlx_mlp_gemm.h's tiles: upload_gemm builds its steps on srlxg::Plan (forward
+// launches, k_vppo_loss_rows as one pointwise step, backward launches), the handle keeps them in a srlxg::GemmPath and update walks them.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_mlp_gemm.h"
 #include "srlx_param_tail.h"
@@ -38,8 +40,9 @@ using srlxt::Seg;
 using srlxv::kHeadCols;
 using srlxv::kNormalLs;
 constexpr int kPlanes = 7;  // trunk 0..2, value 3..4, policy 5..6
-constexpr int kGemmLaunches = 11;  // forward 3 trunk + 3 branch depths, backward 2 branch depths + 3 trunk
-constexpr int kGemmJobs = 32;      // forward 3 x 2 + 3 x 4, backward 2 x 2 + 3
+constexpr int kGemmSteps = 12;  // forward 3 trunk + 3 branch depths, the loss kernel, backward 2 branch depths + 3 trunk
+constexpr int kGemmJobs = 32;   // forward 3 x 2 + 3 x 4, backward 2 x 2 + 3
+enum StepKind { kLoss = srlxg::kBwd + 1 };  // k_vppo_loss_rows, between the forward and the backward launches
 constexpr i64 kRowMaxBatch = 256, kGemmMaxBatch = 4096;  // srlx_vppo_create's and srlx_vppo_create_gemm's largest max_batch
 
 struct Net {  // the three chains as the kernels read them; the Normal head's second Linear beside the policy chain (NULL: categorical)
@@ -63,12 +66,8 @@ struct srlx_vppo {
     float *dlast_p;   // [max_batch][kHeadCols]: d loss / d (head outputs)
     float *rows;      // [4][max_batch]: the rows' loss sums
     double *partials; // [grad_blocks]: sums of squared gradients
-    // srlx_vppo_update_gemm's own, allocated at its first call
-    float *gemm_scratch;    // s' activations [2][max_batch][wmax], then v and n_v [2][max_batch], then the head rows z [max_batch][kHeadCols]
-    srlxg::Job *d_jobs;     // [kGemmJobs]: the plan's jobs, launch after launch
-    srlxg::Launch plan[kGemmLaunches];
-    int n_fwd, n_launches;  // forward launches, then the data-gradient ones
-    bool gemm_ok;           // the job table holds the bound tensors (upload_table makes it stale)
+    // srlx_vppo_update_gemm's own, allocated at its first call; scratch: GemmScratch
+    srlxg::GemmPath<kGemmJobs, kGemmSteps> path;
     // a handle of srlx_vppo_create_gemm: max_batch up to kGemmMaxBatch, the gemm path only, the gradient launch k_mlp_gemm_wgrad
     bool gemm_only;
     srlxg::WgradLin *d_lins;  // [kMaxTensors / 2]: the tile prefix of every Linear, uploaded with the segment table
@@ -504,15 +503,11 @@ int upload_table(srlx_vppo *h) {
     if (h->gemm_only) {  // (the prefix depends on the shape alone; it travels with the table so that one flag covers both)
         srlxg::WgradLin lins[kMaxTensors / 2];
         memset(lins, 0, sizeof(lins));
-        int tiles = 0;
-        for (int l = 0; l < nl; l++) {
-            tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
-            lins[l] = srlxg::WgradLin{tiles, shape[l][0], shape[l][1], (shape[l][1] + 1 + srlxg::kTile - 1) / srlxg::kTile};
-        }
+        srlxg::wgrad_table(shape, nl, lins);
         SRLX_HIP(hipMemcpy(h->d_lins, lins, sizeof(lins), hipMemcpyHostToDevice));
     }
     h->ps.table_ok = true;
-    h->gemm_ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
+    h->path.ok = false;  // (whatever made this table stale made the gemm path's jobs stale)
     return SRLX_OK;
 }
 
@@ -530,55 +525,52 @@ void fill(srlx_vppo *h, int D, int head, int A, int nt, const int *tw, int nv, c
     h->grad_blocks = (h->elements + 4 + kThreads - 1) / kThreads;
     int shape[kMaxTensors / 2][2];
     h->nlin = linear_shapes(h, shape);
-    h->wgrad_tiles = 0;
-    for (int l = 0; l < h->nlin; l++) h->wgrad_tiles += srlxg::wgrad_tiles(shape[l][0], shape[l][1]);
+    h->wgrad_tiles = srlxg::wgrad_table(shape, h->nlin, nullptr);
 }
 
-// The gemm path's launch plan: every Linear over the whole batch as one job, jobs of equal depth in one launch.  Forward: the trunk, layer by
-// layer, on s (kept) and s' (two scratch buffers in turn); then value and policy branch side by side, s' down the value branch only, the heads last.  Backward:
-// both branches side by side, then the trunk, whose top layer sums its sources in SumSeed's order: the value branch, the policy branch or the head, the log-scale
-// head.  The planes, and the layout upload_table hands to the tail, are the row path's.  Allocates the path's scratch at its first call.
-int upload_gemm(srlx_vppo *h) {
-    using srlxg::Job;
-    using srlxg::Src;
-    const i64 plane = h->max_batch * h->wmax;
-    if (!h->gemm_scratch) {
-        const size_t bytes = sizeof(float) * (size_t)(2 * plane + 2 * h->max_batch + h->max_batch * kHeadCols);
-        SRLX_HIP(hipMalloc((void **)&h->gemm_scratch, bytes));
-        SRLX_HIP(hipMemset(h->gemm_scratch, 0, bytes));
-        SRLX_HIP(hipMalloc((void **)&h->d_jobs, sizeof(Job) * kGemmJobs));
+// the gemm path's scratch: upload_gemm and update share this layout
+struct GemmScratch {
+    float *sp[2];     // s' activations, two planes [max_batch][wmax] in turn
+    float *vb, *nvb;  // [max_batch] each: v and n_v
+    float *z;         // [max_batch][kHeadCols]: the head rows
+    static size_t floats(const srlx_vppo *h) { return (size_t)h->max_batch * (2 * h->wmax + 2 + kHeadCols); }
+    GemmScratch(const srlx_vppo *h) {
+        const i64 mb = h->max_batch;
+        sp[0] = h->path.scratch, sp[1] = sp[0] + mb * h->wmax, vb = sp[1] + mb * h->wmax, nvb = vb + mb, z = nvb + mb;
     }
-    Job jobs[kGemmJobs];
-    memset(jobs, 0, sizeof(jobs));
-    int nj = 0, nl = 0;
+};
+
+// The gemm path's plan (built on srlxg::Plan: 7y): every Linear over the whole batch as one job, jobs of equal depth in one launch.  Forward: the
+// trunk, layer by layer, on s (kept) and s' (two scratch buffers in turn); then value and policy branch side by side, s' down the value branch only, the heads
+// last.  Then k_vppo_loss_rows.  Backward: both branches side by side, then the trunk, whose top layer sums its sources in SumSeed's order: the value branch, the
+// policy branch or the head, the log-scale head.  The planes, and the layout upload_table hands to the tail, are the row path's.  Allocates the path's scratch at
+// its first call.
+int upload_gemm(const char *who, srlx_vppo *h) {
+    using srlxg::Job;
+    const i64 plane = h->max_batch * h->wmax;
+    SRLX_TRY(h->path.ensure(GemmScratch::floats(h)));
+    const GemmScratch sc(h);
+    auto &p = h->path.plan;
+    p.clear();
     float *const *P = h->ps.p;
     const int Lt = h->Lt, Lv = h->Lv, Lp = h->Lp, A = h->A;
     const int value_out = Lt + Lv, pol = Lt + Lv + 1, head = pol + Lp;  // Linear numbers in state-dict order
     float *ht = h->h, *hv = h->h + 3 * plane, *hp = h->h + 5 * plane;
     float *dht = h->dh, *dhv = h->dh + 3 * plane, *dhp = h->dh + 5 * plane;
-    float *sp[2] = {h->gemm_scratch, h->gemm_scratch + plane};
-    float *vb = h->gemm_scratch + 2 * plane, *nvb = vb + h->max_batch, *z = nvb + h->max_batch;
-    auto begin = [&](int bwd) { h->plan[nl] = srlxg::Launch{nj, 0, 0, bwd}; };
-    auto add = [&](int N) -> Job & {
-        h->plan[nl].njobs++;
-        h->plan[nl].nmax = N > h->plan[nl].nmax ? N : h->plan[nl].nmax;
-        return jobs[nj++];
-    };
-    auto fwd = [&](const float *x, int sel, int K, int lin, int N, float *y, int ldy, int relu) {
-        Job &j = add(N);
-        j.s[0] = Src{x, K, sel, P[2 * lin], K};
-        j.nsrc = 1, j.N = N, j.aux = P[2 * lin + 1], j.y = y, j.ldy = ldy, j.relu = relu;
-    };
+    float *const *sp = sc.sp, *vb = sc.vb, *nvb = sc.nvb, *z = sc.z;
+    // (Linear number `lin`: its weight and bias)
+    auto fwd = [&](const float *x, int sel, int K, int lin, int N, float *y, int ldy, int relu) { p.fwd(x, sel, K, P[2 * lin], P[2 * lin + 1], K, N, y, ldy, relu); };
     int in = h->D;
-    for (int l = 0; l < Lt; in = h->Wt[l], l++, nl++) {
-        begin(0);
+    for (int l = 0; l < Lt; in = h->Wt[l], l++) {
+        p.begin(srlxg::kFwd);
         fwd(l ? ht + (l - 1) * plane : nullptr, l ? srlxg::kFromJob : srlxg::kArg0, in, l, h->Wt[l], ht + l * plane, h->Wt[l], 1);
         fwd(l ? sp[(l - 1) & 1] : nullptr, l ? srlxg::kFromJob : srlxg::kArg1, in, l, h->Wt[l], sp[l & 1], h->Wt[l], 1);
+        p.end();
     }
     const float *top = ht + (Lt - 1) * plane, *top2 = sp[(Lt - 1) & 1];
     const int Wtop = in, depth = Lv > Lp ? Lv : Lp;
-    for (int d = 0; d <= depth; d++, nl++) {
-        begin(0);
+    for (int d = 0; d <= depth; d++) {
+        p.begin(srlxg::kFwd);
         if (d <= Lv) {
             const float *x = d ? hv + (d - 1) * plane : top, *x2 = d ? sp[(Lt - 1 + d) & 1] : top2;
             const int K = d ? h->Wv[d - 1] : Wtop;
@@ -600,20 +592,17 @@ int upload_gemm(srlx_vppo *h) {
                 if (h->head) fwd(x, 0, K, head + 1, A, z + kNormalLs, kHeadCols, 0);
             }
         }
+        p.end();
     }
-    h->n_fwd = nl;
-    auto bwd = [&](float *y, const float *kept, int N) -> Job & {
-        Job &j = add(N);
-        j.nsrc = 0, j.N = N, j.aux = kept, j.y = y, j.ldy = N;
-        return j;
-    };
-    auto src = [&](Job &j, const float *a, int lda, int n, int lin) { j.s[j.nsrc++] = Src{a, lda, srlxg::kFromJob, P[2 * lin], n}; };
+    p.point(kLoss);
+    auto bwd = [&](float *y, const float *kept, int N) -> Job & { return p.bwd(y, N, kept, N, N, 0); };
+    auto src = [&](Job &j, const float *a, int lda, int n, int lin) { p.src(j, a, lda, n, P[2 * lin]); };
     auto head_srcs = [&](Job &j) {
         src(j, h->dlast_p, kHeadCols, A, head);
         if (h->head) src(j, h->dlast_p + kNormalLs, kHeadCols, A, head + 1);
     };
-    for (int d = 0; d < depth; d++, nl++) {
-        begin(1);
+    for (int d = 0; d < depth; d++) {
+        p.begin(srlxg::kBwd);
         if (int l = Lv - 1 - d; l >= 0) {
             Job &j = bwd(dhv + l * plane, hv + l * plane, h->Wv[l]);
             if (d == 0) src(j, h->dlast_v, 1, 1, value_out);
@@ -624,25 +613,23 @@ int upload_gemm(srlx_vppo *h) {
             if (d == 0) head_srcs(j);
             else src(j, dhp + (l + 1) * plane, h->Wp[l + 1], h->Wp[l + 1], pol + l + 1);
         }
+        p.end();
     }
-    for (int l = Lt - 1; l >= 0; l--, nl++) {
-        begin(1);
+    for (int l = Lt - 1; l >= 0; l--) {
+        p.begin(srlxg::kBwd);
         Job &j = bwd(dht + l * plane, ht + l * plane, h->Wt[l]);
         if (l < Lt - 1) {
             src(j, dht + (l + 1) * plane, h->Wt[l + 1], h->Wt[l + 1], l + 1);
-            continue;
+        } else {
+            if (Lv) src(j, dhv, h->Wv[0], h->Wv[0], Lt);
+            else src(j, h->dlast_v, 1, 1, value_out);
+            if (Lp) src(j, dhp, h->Wp[0], h->Wp[0], pol);
+            else head_srcs(j);
         }
-        if (Lv) src(j, dhv, h->Wv[0], h->Wv[0], Lt);
-        else src(j, h->dlast_v, 1, 1, value_out);
-        if (Lp) src(j, dhp, h->Wp[0], h->Wp[0], pol);
-        else head_srcs(j);
+        p.end();
     }
-    h->n_launches = nl;
-    SRLX_HIP(hipMemcpy(h->d_jobs, jobs, sizeof(Job) * nj, hipMemcpyHostToDevice));
-    h->gemm_ok = true;
-    return SRLX_OK;
+    return h->path.upload(who);
 }
-
 
 // srlx_vppo_update (gemm = false: k_vppo_rows) and srlx_vppo_update_gemm (the layer-wise launches of upload_gemm's plan around k_vppo_loss_rows): one contract, one
 // set of planes, one gradient, clip and Adam tail.  `who` names the entry point in every message.
@@ -663,7 +650,7 @@ int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float 
     srlx::DeviceGuard g(h->device);
     if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
     if (!h->ps.table_ok) SRLX_TRY(upload_table(h));
-    if (gemm && !h->gemm_ok) SRLX_TRY(upload_gemm(h));
+    if (gemm && !h->path.ok) SRLX_TRY(upload_gemm(who, h));
     hipStream_t st = (hipStream_t)stream;
     const int K = h->head ? h->A : 1;
     const double N = (double)batch * K;
@@ -673,11 +660,22 @@ int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float 
             h->head ? (const float *)d_actions : nullptr, d_v, d_n_v, d_new_logpi};
     Work w{h->h, h->dh, h->dlast_v, h->dlast_p, h->rows, h->max_batch * h->wmax, h->max_batch};
     if (gemm) {
-        const float *vn = h->gemm_scratch + 2 * w.plane;
-        for (int l = 0; l < h->n_fwd; l++) srlxg::launch(h->plan[l], h->d_jobs, (int)batch, d_states, d_next_states, st);
-        hipLaunchKernelGGL(k_vppo_loss_rows, dim3((unsigned)((batch + kLossThreads - 1) / kLossThreads)), dim3(kLossThreads), 0, st, b, w, vn, vn + 2 * h->max_batch, c, K,
-                           h->A, h->head);
-        for (int l = h->n_fwd; l < h->n_launches; l++) srlxg::launch(h->plan[l], h->d_jobs, (int)batch, nullptr, nullptr, st);
+        const GemmScratch sc(h);
+        for (int i = 0; i < h->path.plan.ns; i++) {
+            const srlxg::Step &s = h->path.plan.steps[i];
+            switch (s.kind) {
+            case srlxg::kFwd:
+                srlxg::launch(s.l, h->path.d_jobs, (int)batch, d_states, d_next_states, st);
+                break;
+            case srlxg::kBwd:
+                srlxg::launch(s.l, h->path.d_jobs, (int)batch, nullptr, nullptr, st);
+                break;
+            case kLoss:
+                hipLaunchKernelGGL(k_vppo_loss_rows, dim3((unsigned)((batch + kLossThreads - 1) / kLossThreads)), dim3(kLossThreads), 0, st, b, w,
+                                   (const float *)sc.vb, (const float *)sc.z, c, K, h->A, h->head);
+                break;
+            }
+        }
     } else {
         hipLaunchKernelGGL(k_vppo_rows, dim3((unsigned)((batch + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), st, (const Net *)h->d_net, b, w, c, h->D, K, lds_stride(h));
     }
@@ -759,8 +757,9 @@ int srlx_vppo_destroy(srlx_vppo_t *h) {
     if (!h) return SRLX_OK;
     srlx::DeviceGuard g(h->device);
     for (void *p : {(void *)h->d_net, (void *)h->d_segs, (void *)h->h, (void *)h->dh, (void *)h->dlast_v, (void *)h->dlast_p, (void *)h->rows, (void *)h->partials,
-                    (void *)h->gemm_scratch, (void *)h->d_jobs, (void *)h->d_lins})
+                    (void *)h->d_lins})
         if (p) (void)hipFree(p);
+    h->path.release();
     delete h;
     return SRLX_OK;
 }

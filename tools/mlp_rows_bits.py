@@ -4,12 +4,18 @@ BUILDS of libsrlx on one box:
     SRLX_LIB=/path/to/another/libsrlx.so python tools/mlp_rows_bits.py --out a.json     # one process per build: the library is chosen at import
     python tools/mlp_rows_bits.py --out b.json                                          # the in-tree build
     python tools/mlp_rows_bits.py --compare a.json b.json --out profiles/NAME.json      # both outputs, one digest per case, and the keys that differ; exit status 1 if any does
+    python tools/mlp_rows_bits.py --gemm --out a.json                                   # the same, with the cases of the float64-MFMA layer path added (below)
 
 Every case drives libsrlx's entry points (through the zero-copy handles of device/mlpq.py, sacd.py, vppo.py and notsac.py) on seeded inputs and records the
 SHA-256 of every output array and, after an update, of every parameter, gradient and Adam tensor (V-PPO and NoT_SAC: one digest over each list of tensors, in
 bind order).  The library is built with -ffp-contract=off and every product-sum is an explicit fma in a fixed order, so a change that only moves code must leave
 every digest as it was.  The shapes are the smallest at which the shared code takes each of its paths (one tile / many tiles with a partial last one; 1, 8 and
-128 row groups; idle threads; chains of 0, 1 and 2 steps; a full and a one-item workgroup; B 16 / 17, both heads, a clip that bites and one that does not)."""
+128 row groups; idle threads; chains of 0, 1 and 2 steps; a full and a one-item workgroup; B 16 / 17, both heads, a clip that bites and one that does not).
+
+`--gemm` adds the updates that run layer by layer on csrc/srlx_mlp_gemm.h from a plan of csrc/srlx_gemm_plan.h, keys under "gemm-...": two
+updates at gemm=True of every case of tests/vppo_cases.py and tests/notsac_cases.py and of the shapes of tests/sacd_cases.py, every case of
+tests/vppo_wide_cases.py on a gemm_only=True handle, and every case of tests/dqnnot_reference.py.  The job tables decide which tile reads what, so a change to
+the host code that builds them must leave these digests as they were."""
 import argparse
 import hashlib
 import json
@@ -226,6 +232,94 @@ def notsac(out, name):
         record(out, f"{case}/forward/{tag}", head=heads, **({} if q is None else {"q": q}))
 
 
+def gemm_vppo(out, name, wide):
+    """Two updates at gemm=True of a case of tests/vppo_cases.py, or (`wide`) of tests/vppo_wide_cases.py on a gemm-only handle."""
+    import vppo_cases
+    import vppo_wide_cases
+    from simple_distributed_rl_amd.device.vppo import VppoUpdate
+
+    C = vppo_wide_cases if wide else vppo_cases
+    B, _, head = C.CASES[name][:3]
+    p = C.make_parameter(name, "cuda")
+    cfg = p.config
+    u = VppoUpdate(p, max_batch=B, gemm_only=True) if wide else VppoUpdate(p, max_batch=B)
+    f = lambda x: x.float().cuda()  # noqa: E731
+    for k, b in enumerate(C.make_batches(name)):
+        res = u.update(f(b["state"]), f(b["n_state"]), f(b["action"]) if head else b["action"].int().cuda(), f(b["old_logpi"]), f(b["reward"]),
+                       f(b["not_terminated"]), f(b["total_reward"]), cfg.lr, cfg.discount, cfg.clip_range, cfg.entropy_weight, cfg.loss_align_coeff,
+                       cfg.max_grad_norm, cfg.squashed_gaussian_policy, gemm=True)
+        torch.cuda.synchronize()
+        record_update(out, f"gemm-vppo{'-wide' if wide else ''}/{name}/update{k}", res, u)
+
+
+def gemm_notsac(out, name):
+    """Two updates at gemm=True of a case of tests/notsac_cases.py."""
+    import notsac_cases as C
+    from simple_distributed_rl_amd.device.notsac import NotSacUpdate
+
+    B, _, head = C.CASES[name][:3]
+    p = C.make_parameter(name, "cuda")
+    cfg = p.config
+    u = NotSacUpdate(p, max_batch=B)
+    f = lambda x: x.float().cuda()  # noqa: E731
+    for k, b in enumerate(C.make_batches(name)):
+        res = u.update(f(b["state"]), f(b["n_state"]), f(b["action"]) if head else b["action"].argmax(1).int().cuda(), f(b["reward"]), f(b["not_terminated"]),
+                       f(b["total_reward"]), b["noise"].cuda(), cfg.lr, cfg.discount, cfg.loss_align_coeff, cfg.max_grad_norm, cfg.squashed_gaussian_policy,
+                       gemm=True)
+        torch.cuda.synchronize()
+        record_update(out, f"gemm-notsac/{name}/update{k}", res, u)
+
+
+def gemm_sacd(out, i):
+    """Row i of tests/sacd_cases.py:SHAPES: srlx_sacd_update_gemm with a hard sync, then with a soft one."""
+    import sacd_cases as C
+    from simple_distributed_rl_amd.device.sacd import NETWORKS, TRAINED, SacdUpdate
+
+    B, D, A, pw, qw = C.SHAPES[i]
+    cfg = C.make_config(D, A, pw, qw, device="cuda", lr_policy=C.LR, lr_q=C.LR, lr_alpha=C.LR, discount=C.DISCOUNT, soft_target_update_tau=C.TAU)
+    p = C.make_parameter(cfg, 1000 + i)
+    u = SacdUpdate(p, max_batch=B)
+    b = C.make_batch(B, D, A, 3000 + i)
+    for k, hard in enumerate((True, False)):
+        res = u.update(b["state"].float().cuda(), b["action"].int().cuda(), b["n_state"].float().cuda(), b["reward"].float().cuda(),
+                       b["done"].to(torch.uint8).cuda(), C.LR, C.LR, C.LR, hard, C.DISCOUNT, C.TAU, True, -A, gemm=True)
+        torch.cuda.synchronize()
+        record(out, f"gemm-sacd/{C.shape_id(i)}/update{k}", log_alpha=p.log_alpha, grad_log_alpha=u.grad_log_alpha, alpha_exp_avg=u.alpha_exp_avg,
+               alpha_exp_avg_sq=u.alpha_exp_avg_sq, **res, **{"params_" + n: u.params[n] for n in NETWORKS}, **{"grads_" + n: u.grads[n] for n in TRAINED},
+               **{"exp_avg_" + n: u.exp_avg[n] for n in TRAINED}, **{"exp_avg_sq_" + n: u.exp_avg_sq[n] for n in TRAINED})
+
+
+def gemm_dqnnot(out, name):
+    """The two updates of a case of tests/dqnnot_reference.py."""
+    import dqnnot_reference as R
+    from simple_distributed_rl_amd.device.dqnnot import DqnNotUpdate
+
+    u = DqnNotUpdate(R.make_parameter(name, "cuda"), max_batch=R.CASES[name][0])
+    for k, (b, _) in enumerate(R.reference(name)):
+        res = u.update(*R.device_batch(b, "cuda"), R.DISCOUNT, R.ALIGN, R.LR)
+        torch.cuda.synchronize()
+        record_update(out, f"gemm-dqnnot/{name}/update{k}", res, u)
+
+
+def gemm_cases(out):
+    import dqnnot_reference
+    import notsac_cases
+    import sacd_cases
+    import vppo_cases
+    import vppo_wide_cases
+
+    for name in vppo_cases.NAMES:
+        gemm_vppo(out, name, False)
+    for name in vppo_wide_cases.NAMES:
+        gemm_vppo(out, name, True)
+    for name in notsac_cases.NAMES:
+        gemm_notsac(out, name)
+    for i in range(len(sacd_cases.SHAPES)):
+        gemm_sacd(out, i)
+    for name in dqnnot_reference.NAMES:
+        gemm_dqnnot(out, name)
+
+
 def by_case(digests):
     """One SHA-256 per case (the first two parts of a key) over its keys and digests in key order: a whole output in a few dozen lines."""
     cases = {}
@@ -252,6 +346,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    ap.add_argument("--gemm", action="store_true", help="also record the updates of the float64-MFMA layer path")
     args = ap.parse_args()
     if args.compare:
         sys.exit(1 if compare(args.compare[0], args.compare[1], args.out) else 0)
@@ -279,6 +374,8 @@ def main():
         vppo(out, name)
     for name in notsac_cases.NAMES:
         notsac(out, name)
+    if args.gemm:
+        gemm_cases(out)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
