@@ -1698,6 +1698,19 @@ int64_t srlx_dqnnot_steps(const srlx_dqnnot_t *h);
 int srlx_dqnnot_update(srlx_dqnnot_t *h, const float *d_states, const int32_t *d_actions, const float *d_rewards, const float *d_not_terminated,
                        const float *d_total_rewards, const float *d_weights, int64_t batch, double discount, double align_coeff, double lr, float *d_q,
                        float *d_target, float *d_losses, void *stream);
+/* srlx_dqnnot_act: the network's whole forward for n_rows flat observations in ONE launch (k_dqnnot_act): what Parameter.pred_q and
+ * Worker.policy compute (dqn_not/parameter.py:65-71, worker.py:24-27 without the epsilon branch).  It needs srlx_dqnnot_bind_params only: no gradient tensors,
+ * no Adam state, and it reads the bound tensors where they are, so it sees every update of them.  d_states f32 [n_rows][D].  Writes d_q f32 [n_rows][A] and
+ * d_v f32 [n_rows][1] (either may be NULL: not wanted) and d_actions i32 [n_rows] (required).
+ * Arithmetic: a workgroup walks 16 rows through every layer on v_mfma_f64_16x16x4_f64, the activations in LDS.  Operands are float32, widened to float64;
+ * products are exact, sums float64, rounded to float32 ONCE per Linear where the bias is added and ReLU applied.  The head keeps v, adv, mean(adv) and
+ * q = v + adv - mean(adv) in float64 and rounds q and v once (the update's stated departure).  Fixed order in every sum, no atomics: equal inputs give equal
+ * bits, and a row's result depends neither on n_rows nor on the row's place in the call.
+ * The action is the FIRST maximum of the row's ROUNDED float32 q -- numpy.argmax of the d_q row, a NaN counting as the maximum as it does there.
+ * Envelope: the handle's D, U, A; n_rows 1..65536 whatever the handle's max_batch (nothing of the launch is sized by it).  Refusals come before any device
+ * call, as SRLX_ERR_INVALID with a message that names dqnnot_act, in this order: n_rows outside 1..65536, a NULL handle, unbound parameters, NULL d_states or
+ * d_actions.  Nothing synchronises. */
+int srlx_dqnnot_act(srlx_dqnnot_t *h, int64_t n_rows, const float *d_states, float *d_q, float *d_v, int32_t *d_actions, void *stream);
 
 #ifdef __cplusplus
 }

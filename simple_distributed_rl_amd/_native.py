@@ -321,6 +321,7 @@ SIGNATURES = {
     "srlx_dqnnot_bind_adam": (c_int, [c_p, c_p, c_p, c_i64, c_f64, c_f64, c_f64]),
     "srlx_dqnnot_steps": (c_i64, [c_p]),
     "srlx_dqnnot_update": (c_int, [c_p] * 7 + [c_i64, c_f64, c_f64, c_f64] + [c_p] * 4),
+    "srlx_dqnnot_act": (c_int, [c_p, c_i64] + [c_p] * 5),
 }
 OBS_U8, OBS_F32 = 0, 1
 PRIO_NONE_MASKED = 4

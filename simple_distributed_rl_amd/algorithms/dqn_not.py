@@ -11,8 +11,9 @@ importance weights (1 for a memory without priorities); Adam at torch's defaults
   "srlx"   one libsrlx call, six launches on the float64 matrix cores (device/dqnnot.py, csrc/srlx_dqnnot.hip), for GPU parameters inside the
            kernels' envelope (flat observations of 1..256 floats, base_units 32..512 in multiples of 32, 2..32 actions, batches up to 4096);
   "torch"  the reference's step in plain torch float32 with torch.optim.Adam, for CPU parameters and everything else.
-`update_backend`, `update_path` and `why_not_srlx_update` work as in ppo_v.Trainer.  `engine_kind(dqn_not.Config())` is None: there is no device engine and no
-acting kernel; the Worker acts through `Parameter.pred_q` on the host.
+`update_backend`, `update_path` and `why_not_srlx_update` work as in ppo_v.Trainer.  `engine_kind(dqn_not.Config())` is None: there is no device engine; the
+Worker acts through `Parameter.pred_q`, whose forward is one srlx_dqnnot_act launch for GPU parameters inside the same envelope (`Parameter.act_backend`,
+DESIGN.md 7z) and the module's torch forward otherwise; the epsilon branch and the argmax stay on the host.
 
 Kept from the reference although it reads oddly:
   * The target is the FIRST argument of HuberLoss and MSELoss (trainer.py:66,70); q is their second and takes the gradient.
@@ -90,13 +91,22 @@ class QNetwork(nn.Module):
 
 
 class Parameter(RLParameter):
-    """parameter.py:49-71."""
+    """parameter.py:49-71.  `pred_q` runs on one of two backends, as the Trainer's update does: `act_backend` asks for "srlx" (one srlx_dqnnot_act launch,
+    device/dqnnot.py: DqnNotAct) or "torch" (the module's forward); `act_path` names what the last call ran, and `why_not_srlx_act` holds the
+    reason when "srlx" was asked for and torch ran: CPU parameters, an image or layered input block, a shape outside the kernels' envelope, more than 65536
+    rows.  The handle is made at the first GPU call and binds the tensors by address, so it sees `call_restore` and a Trainer's updates; `to_device` drops it."""
+
+    # "srlx" | "torch".  The default follows the project's 1.10 rule (DESIGN.md 7z): 0.133 to 0.134 ms per pred_q of one row on "srlx" against 0.236 to 0.237 ms
+    # on "torch" at dqn_not.Config() on CartPole, a ratio of 0.57 in every round (profiles/dqnnot_act_probe.json).
+    act_backend = "srlx"
 
     def setup(self):
         self.np_dtype = self.config.get_dtype("np")
         self.device = torch.device(self.config.used_device_torch)
         self.q_online = QNetwork(self.config).to(self.device)
         self.q_online.train()
+        self.act_path = self.why_not_srlx_act = ""
+        self._act, self._act_why = None, None  # the acting handle, and why there is none (None: not asked yet for these tensors)
 
     def call_restore(self, data: Any, from_serialized: bool = False, **kwargs) -> None:
         self.q_online.load_state_dict(data)  # (in place: the libsrlx backend holds these tensors by address)
@@ -109,14 +119,37 @@ class Parameter(RLParameter):
         """Moves every tensor; the tensors are new ones afterwards (call before a Trainer binds them)."""
         self.device = torch.device(device)
         self.q_online.to(self.device)
+        self._act, self._act_why = None, None  # (the handle held the old tensors' addresses)
 
     def summary(self, **kwargs):
         print(self.q_online)
 
+    def _srlx_act(self, n: int):
+        """The acting handle when libsrlx serves a call of n rows; otherwise None, with the reason in `why_not_srlx_act` ('' where "torch" was asked for)."""
+        if self.act_backend not in ("srlx", "torch"):
+            raise ValueError(f"act_backend {self.act_backend!r}: 'srlx' or 'torch'")
+        self.why_not_srlx_act = ""
+        if self.act_backend == "torch":
+            return None
+        from simple_distributed_rl_amd.device.dqnnot import DqnNotAct
+
+        if self._act_why is None:
+            self._act_why = DqnNotAct.why_not(self)
+            if not self._act_why:
+                self._act = DqnNotAct(self)
+        self.why_not_srlx_act = self._act_why or DqnNotAct.rows_reason(n)
+        return None if self.why_not_srlx_act else self._act
+
     def pred_q(self, state: np.ndarray):
         """(q [n][A], v [n][1]) as numpy arrays (parameter.py:65-71)."""
-        with torch.no_grad():
-            q, v = self.q_online(torch.as_tensor(np.asarray(state, dtype=self.np_dtype), device=self.device))
+        x = torch.as_tensor(np.asarray(state, dtype=self.np_dtype), device=self.device)
+        act = self._srlx_act(x.shape[0])
+        if act is not None:
+            q, v, _ = act.act(x.reshape(x.shape[0], -1).float())
+        else:
+            with torch.no_grad():
+                q, v = self.q_online(x)
+        self.act_path = "srlx" if act is not None else "torch"
         return q.cpu().numpy(), v.cpu().numpy()
 
 

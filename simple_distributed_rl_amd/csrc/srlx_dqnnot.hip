@@ -174,6 +174,193 @@ __global__ void __launch_bounds__(kThreads) k_dqnnot_head(HeadArgs a) {
     }
 }
 
+// ---- acting: the whole forward of 16 rows in one workgroup ------------------------------------------------------------------------------------------
+// k_dqnnot_act.  Grid ceil(n / 16); a workgroup of kActWaves waves owns 16 rows -- the M of one v_mfma_f64_16x16x4_f64 tile -- and walks hidden_block.0, then
+// v_block.0 and adv_block.0 as ONE pass of 2 U output columns, then the head.  x, h, hv and ha live in dynamic LDS as float32 planes [16][K + 4] (K padded to
+// kActStep) and never touch HBM; rows >= n are zero on load and never stored, and no thread leaves before the last barrier.
+// Weights go from L2 straight into the B fragment.  A wave owns the column tiles w, w + kActWaves, ... of a pass and runs two of them at a time on one read
+// of A.  Per step of kActStep = 32 reduction indices, lane l (column l % 16, lane group g = l / 16) loads the quads k0 + 4 g.. and k0 + 16 + 4 g.. of its
+// column's weight row -- the four lane groups of a column cover 128 contiguous bytes -- one step ahead of the matrix cores; element by element where the
+// pointer or K do not allow 16-byte loads (load_quad's rule).  MFMA j of a quad therefore reduces k = k0 + 4 g + j in lane group g, and A has to agree: a plane stores reduction index k of a row at act_slot(k), the 4 x 4 transpose inside each group of 16, so the lane's A read of that MFMA is
+// plane[row][k0 + 4 j + g] -- row l % 16, consecutive floats across the lane groups -- and with a row stride of 4 * odd floats the 64 reads of one MFMA fall on
+// banks 4 (l % 16) stride + l / 16: 64 different ones, srlx_mlp_gemm.h's argument.  The epilogue adds the bias in float64, rounds ONCE, applies ReLU and
+// writes the next plane at act_slot(column).  One barrier per layer.
+// The head: wave 0 runs v_block.2 (one live column) over hv, waves 1.. the ceil(A / 16) tiles of adv_block.2 over ha, through the same tile loop; sums and
+// biases stay float64 in LDS.  Then thread r finishes row r in float64 -- the mean in action order, q = v + adv - mean -- rounds q and v once and takes the
+// first maximum of the ROUNDED q.  Fixed order everywhere, no atomics; a row's arithmetic does not know its place or n.
+constexpr int kActWaves = 16, kActThreads = 64 * kActWaves;
+constexpr int kActRows = 16;   // rows of a workgroup
+constexpr int kActStep = 32;   // reduction indices per step
+constexpr i64 kActMaxRows = 65536;
+
+constexpr int act_ld(int K) { return (K + kActStep - 1) / kActStep * kActStep + 4; }  // a plane's row stride in floats: 4 * odd
+constexpr size_t act_lds_bytes(int D, int U, int A) { return sizeof(float) * kActRows * (act_ld(D) + 3 * act_ld(U)) + sizeof(double) * kActRows * (1 + A); }
+constexpr size_t kActLdsCap = act_lds_bytes(256, kMaxUnits, kMaxActions);  // 119 936 bytes
+
+struct ActArgs {
+    i64 n;
+    int D, U, A;
+    const float *x;  // [n][D]
+    const float *w0, *b0, *wv1, *bv1, *wv2, *bv2, *wa1, *ba1, *wa2, *ba2;
+    float *q, *v;     // [n][A], [n][1]; NULL: not wanted
+    int32_t *action;  // [n]
+};
+
+// where a plane keeps reduction index k of a row
+__device__ __forceinline__ int act_slot(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
+
+__device__ __forceinline__ float quad_at(const float4 &q, int j) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; }
+
+// kT column tiles over the K reduction indices of one plane: acc[i] += sum_k plane[row][k] w[i][k].  `a`: the plane at this lane's row and lane group;
+// w[i]: this lane's weight row of tile i.  live[i] false: the lane's column does not exist; w[i] is then the weight's first row, the lane computes a column
+// nobody stores (a column's B operand reaches that column's sums only), and only the masked last step asks.
+// The K / 32 full steps load WITHOUT a condition: a branch around a load makes the compiler wait for every load in flight where the branch ends, which put
+// each quad's latency in front of the MFMAs (measured: 128 us per call at U 512 against 80 us without).  Two steps per trip on two sets of registers; a
+// step's quads are requested before the MFMAs of the step in front of it, and the request behind the last full step repeats that step's.  What is left of K
+// (the first layer's D, where it is no multiple of 32) is one more step on load_quad, masked at K.
+template <int kT, bool kVec>
+__device__ __forceinline__ void act_tiles(const float *a, int K, const float *const (&w)[kT], const bool (&live)[kT], srlxg::f64x4 (&acc)[kT]) {
+    const int g4 = ((threadIdx.x & 63) >> 4) << 2;
+    float4 q0[kT][2], q1[kT][2];
+    auto fetch = [&](float4(&q)[kT][2], int k0) {
+#pragma unroll
+        for (int i = 0; i < kT; i++)
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                const float *p = w[i] + k0 + 16 * s + g4;
+                if constexpr (kVec) q[i][s] = *reinterpret_cast<const float4 *>(p);
+                else q[i][s] = make_float4(p[0], p[1], p[2], p[3]);
+            }
+    };
+    auto step = [&](const float4(&q)[kT][2], int k0) {
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const double av = (double)a[k0 + 16 * s + 4 * j];
+#pragma unroll
+                for (int i = 0; i < kT; i++) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, (double)quad_at(q[i][s], j), acc[i], 0, 0, 0);
+            }
+    };
+    const int full = K / kActStep;
+    if (full > 0) {
+        const int last = (full - 1) * kActStep;
+        int k0 = 0;
+        fetch(q0, 0);
+        for (; k0 < last; k0 += 2 * kActStep) {  // (nothing conditional inside: the compiler moves a load whose values one branch reads into that branch)
+            fetch(q1, k0 + kActStep);
+            step(q0, k0);
+            fetch(q0, min(k0 + 2 * kActStep, last));
+            step(q1, k0 + kActStep);
+        }
+        if (k0 == last) step(q0, last);  // an odd number of steps: q0 holds the last one's quads
+    }
+    if (K % kActStep) {
+        const int k0 = full * kActStep;
+#pragma unroll
+        for (int i = 0; i < kT; i++)
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                const int k = k0 + 16 * s + g4;
+                q0[i][s] = srlxg::load_quad(w[i] + k, live[i] ? K - k : 0, kVec);
+            }
+        step(q0, k0);
+    }
+}
+
+// One pass of Linear + ReLU from the plane `in` (K reduction indices, row stride ldin): column tiles 0..UT-1 are (w0, b0) into out0, tiles UT.. (w1, b1) into
+// out1, U output columns each.  Every wave takes its tiles two at a time; no barrier inside.
+__device__ __forceinline__ void act_layer(const float *in, int ldin, int K, int U, int NT, const float *w0, const float *b0, float *out0, const float *w1,
+                                          const float *b1, float *out1, int ldout) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
+    const int UT = U / 16;
+    const bool vec = K % 4 == 0 && srlxg::aligned16(w0) && srlxg::aligned16(w1);
+    const float *a = in + fr * ldin + g;
+    for (int t = wave; t < NT; t += 2 * kActWaves) {
+        const float *w[2], *b[2];
+        float *o[2];
+        int col[2];
+        bool live[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int ti = t + i * kActWaves;
+            const bool second = ti >= UT;
+            col[i] = (ti - (second ? UT : 0)) * 16 + fr;
+            const float *base = second ? w1 : w0;
+            live[i] = ti < NT;
+            w[i] = base + (live[i] ? (i64)col[i] * K : 0);
+            b[i] = second ? b1 : b0, o[i] = second ? out1 : out0;
+        }
+        srlxg::f64x4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+        if (vec) act_tiles<2, true>(a, K, w, live, acc);
+        else act_tiles<2, false>(a, K, w, live, acc);
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            if (!live[i]) continue;
+            const double bias = (double)b[i][col[i]];
+            float *dst = o[i] + act_slot(col[i]);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {  // (D layout: register r is row 4 r + l / 16)
+                const float z = (float)(acc[i][r] + bias);
+                dst[(4 * r + g) * ldout] = z > 0.f ? z : 0.f;
+            }
+        }
+    }
+}
+
+SRLXG_KERNEL void __launch_bounds__(kActThreads) k_dqnnot_act(ActArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float act_lds[];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, fr = lane & 15, g = lane >> 4;
+    const int D = a.D, U = a.U, A = a.A, Z = 1 + A;
+    const int Dp = act_ld(D) - 4, ldx = act_ld(D), ldu = act_ld(U);
+    float *xs = act_lds, *hs = xs + kActRows * ldx, *hvs = hs + kActRows * ldu, *has = hvs + kActRows * ldu;
+    double *zs = reinterpret_cast<double *>(has + kActRows * ldu);  // [16][1 + A]: v, then adv, bias added (the float planes are a multiple of 256 bytes)
+    const i64 row0 = (i64)blockIdx.x * kActRows;
+
+    for (int i = t; i < kActRows * Dp; i += kActThreads) {  // rows >= n and the padding behind D: zero
+        const int r = i / Dp, k = i - r * Dp;
+        xs[r * ldx + act_slot(k)] = row0 + r < a.n && k < D ? a.x[(row0 + r) * D + k] : 0.f;
+    }
+    __syncthreads();
+    act_layer(xs, ldx, D, U, U / 16, a.w0, a.b0, hs, a.w0, a.b0, hs, ldu);
+    __syncthreads();
+    act_layer(hs, ldu, U, U, 2 * (U / 16), a.wv1, a.bv1, hvs, a.wa1, a.ba1, has, ldu);
+    __syncthreads();
+    if (wave < 1 + (A + 15) / 16) {  // (wave-uniform; no barrier inside)
+        const bool isv = wave == 0;
+        const int col = isv ? fr : (wave - 1) * 16 + fr;
+        const float *hw = isv ? a.wv2 : a.wa2;
+        const bool live[1] = {col < (isv ? 1 : A)};
+        const float *w[1] = {hw + (live[0] ? (i64)col * U : 0)};
+        srlxg::f64x4 acc[1] = {{0.0, 0.0, 0.0, 0.0}};
+        const float *ha = (isv ? hvs : has) + fr * ldu + g;
+        if (srlxg::aligned16(a.wv2) && srlxg::aligned16(a.wa2)) act_tiles<1, true>(ha, U, w, live, acc);  // (U is a multiple of 4)
+        else act_tiles<1, false>(ha, U, w, live, acc);
+        if (live[0]) {
+            const double bias = isv ? (double)a.bv2[0] : (double)a.ba2[col];
+#pragma unroll
+            for (int r = 0; r < 4; r++) zs[(4 * r + g) * Z + (isv ? 0 : 1 + col)] = acc[0][r] + bias;
+        }
+    }
+    __syncthreads();  // (the workgroup's last barrier)
+    if (t < kActRows && row0 + t < a.n) {
+        const double *z = zs + t * Z;
+        const i64 row = row0 + t;
+        double sum = 0.0;
+        for (int j = 1; j <= A; j++) sum += z[j];
+        const double v = z[0], mean = sum / (double)A;
+        float best = 0.f;
+        int arg = 0;
+        for (int j = 0; j < A; j++) {
+            const float q = (float)(v + z[1 + j] - mean);
+            if (a.q) a.q[row * A + j] = q;
+            if (j == 0 || (best == best && (q > best || q != q))) best = q, arg = j;  // numpy.argmax: the first maximum, a NaN counting as one
+        }
+        if (a.v) a.v[row] = (float)v;
+        a.action[row] = arg;
+    }
+}
+
 // The two loss means in the last workgroup of k_mlp_gemm_wgrad's launch: every thread takes the items t, t + 256, ... of a term in item order, then block_sum's
 // tree -- a fixed order in float64, rounded once.
 struct LossMeans {
@@ -282,6 +469,7 @@ int srlx_dqnnot_create(srlx_dqnnot_t **out, int obs_dim, int units, int n_action
     // (every instantiation's limit at its cap, at every create: a narrow handle never lowers it under a wide one that is still alive)
     for (HeadKernel k : kHeadKernels)
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadLdsCap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_dqnnot_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsCap);
     if (e != hipSuccess) {
         srlx_dqnnot_destroy(h);
         srlx::set_error("dqnnot_create: device set-up failed: %s", hipGetErrorString(e));
@@ -349,6 +537,19 @@ int srlx_dqnnot_update(srlx_dqnnot_t *h, const float *d_states, const int32_t *d
     hipLaunchKernelGGL(k_dqnnot_step, dim3((unsigned)((h->elements + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, sa);
     SRLX_HIP(hipGetLastError());
     h->ps.steps++;
+    return SRLX_OK;
+}
+
+int srlx_dqnnot_act(srlx_dqnnot_t *h, int64_t n_rows, const float *d_states, float *d_q, float *d_v, int32_t *d_actions, void *stream) {
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= kActMaxRows, "dqnnot_act: n_rows %lld (1..%lld)", (long long)n_rows, (long long)kActMaxRows);
+    SRLX_REQUIRE(h, "dqnnot_act: NULL handle");
+    SRLX_REQUIRE(h->ps.bound, "dqnnot_act: bind the parameters first (srlx_dqnnot_bind_params)");
+    SRLX_REQUIRE(d_states && d_actions, "dqnnot_act: NULL d_states or d_actions (d_q and d_v alone are optional)");
+    srlx::DeviceGuard g(h->device);
+    float *const *P = h->ps.p;
+    const ActArgs aa{n_rows, h->D, h->U, h->A, d_states, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], P[8], P[9], d_q, d_v, d_actions};
+    hipLaunchKernelGGL(k_dqnnot_act, dim3((unsigned)((n_rows + kActRows - 1) / kActRows)), dim3(kActThreads), act_lds_bytes(h->D, h->U, h->A), (hipStream_t)stream, aa);
+    SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }
 

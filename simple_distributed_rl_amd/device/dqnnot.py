@@ -1,6 +1,7 @@
 """NoTarget_DQN's update on libsrlx (csrc/srlx_dqnnot.hip): `DqnNotUpdate` binds an `algorithms.dqn_not.Parameter`'s own tensors by address -- the
 network stays what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write and the Adam state (moments
-here, the step count in the handle).  One `update` is the whole of trainer.py:54-80 for one batch, in six launches on the float64 matrix cores."""
+here, the step count in the handle).  One `update` is the whole of trainer.py:54-80 for one batch, in six launches on the float64 matrix cores.  `DqnNotAct`
+is the acting side: a handle that binds the same tensors and nothing else, and runs the network's forward in one launch."""
 import ctypes
 
 import torch
@@ -10,6 +11,7 @@ from simple_distributed_rl_amd._native import _linear_widths, _ptrs
 from simple_distributed_rl_amd.device import _row_update as R
 
 MAX_BATCH = 4096  # srlx_dqnnot_create's largest max_batch
+MAX_ACT_ROWS = 65536  # srlx_dqnnot_act's largest n_rows
 
 
 def shape_of(parameter):
@@ -22,16 +24,17 @@ def shape_of(parameter):
     return net.hidden_block[0].in_features, net.hidden_block[0].out_features, net.adv_block[2].out_features
 
 
+def tensors_of(parameter) -> list:
+    """hidden_block.0, v_block.0, v_block.2, adv_block.0, adv_block.2, weight then bias each: the order of srlx_dqnnot_bind_params."""
+    net = parameter.q_online
+    return [t for lin in (net.hidden_block[0], net.v_block[0], net.v_block[2], net.adv_block[0], net.adv_block[2]) for t in (lin.weight, lin.bias)]
+
+
 class DqnNotUpdate(R.RowUpdate):
     ABI = "dqnnot"
     MAX_BATCH = MAX_BATCH  # declaring it is what lets SrlxUpdateBackend size an ordinary update past 256
     shape_of = staticmethod(shape_of)
-
-    @staticmethod
-    def tensors_of(parameter) -> list:
-        """hidden_block.0, v_block.0, v_block.2, adv_block.0, adv_block.2, weight then bias each: the order of srlx_dqnnot_bind_params."""
-        net = parameter.q_online
-        return [t for lin in (net.hidden_block[0], net.v_block[0], net.v_block[2], net.adv_block[0], net.adv_block[2]) for t in (lin.weight, lin.bias)]
+    tensors_of = staticmethod(tensors_of)
 
     def __init__(self, parameter, max_batch: int = 256, betas=(0.9, 0.999), eps: float = 1e-8):
         self.D, self.U, self.A = self._open(parameter, max_batch, betas, eps)
@@ -80,3 +83,51 @@ class DqnNotUpdate(R.RowUpdate):
                                              N.tptr(out["target_q"]), N.tptr(out["losses"]), N.torch_stream_ptr()))
         self._keep = keep
         return out
+
+
+class DqnNotAct(R.LibUpdate):
+    """The network's forward on libsrlx for acting (srlx_dqnnot_act): a handle of its own with max_batch 1 -- nothing of the acting launch is
+    sized by it -- that binds the Parameter's own tensors by address and nothing else: no gradient tensors, no Adam state.  It reads the weights where they
+    are, so it sees `load_state_dict` and every update of a DqnNotUpdate on the same tensors."""
+    ABI = "dqnnot"
+    MAX_ROWS = MAX_ACT_ROWS
+
+    @staticmethod
+    def rows_reason(n: int) -> str:
+        return f"{n} rows above {MAX_ACT_ROWS} in one call" if n > MAX_ACT_ROWS else ""
+
+    @classmethod
+    def why_not(cls, parameter, n: int = 1, config=None) -> str:
+        """'' when libsrlx runs this Parameter's forward for n rows, otherwise the reason it does not: DqnNotUpdate's sentences, then the rows'."""
+        reason = R.tensor_reason(tensors_of(parameter))
+        if reason:
+            return reason
+        shape = shape_of(parameter)
+        if isinstance(shape, str):
+            return shape
+        return DqnNotUpdate.envelope_reason(*shape) or cls.rows_reason(n)
+
+    def __init__(self, parameter):
+        reason = self.why_not(parameter)
+        if reason:
+            raise ValueError(f"DqnNotAct: {reason}")
+        self.params = tensors_of(parameter)
+        self.device = self.params[0].device
+        self.D, self.U, self.A = shape_of(parameter)
+        self._lib = N.lib()
+        self._h = N.c_p()
+        N.check(self._lib.srlx_dqnnot_create(ctypes.byref(self._h), self.D, self.U, self.A, 1, self.device.index or 0))
+        N.check(self._lib.srlx_dqnnot_bind_params(self._h, _ptrs(self.params)))
+
+    def act(self, states):
+        """states f32 [n][D] on the device, n 1..65536.  Returns q f32 [n][A], v f32 [n][1] and the greedy actions i32 [n] -- the first maximum of the returned
+        q row -- as device tensors; nothing synchronises."""
+        states = states.contiguous()
+        n = states.shape[0]
+        assert states.dtype == torch.float32 and states.device == self.device and states.numel() == n * self.D
+        q = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+        v = torch.empty(n, 1, dtype=torch.float32, device=self.device)
+        actions = torch.empty(n, dtype=torch.int32, device=self.device)
+        N.check(self._lib.srlx_dqnnot_act(self._h, n, N.tptr(states), N.tptr(q), N.tptr(v), N.tptr(actions), N.torch_stream_ptr()))
+        self._keep = states
+        return q, v, actions

@@ -12,7 +12,15 @@ that synchronises -- every round ending in a device synchronise.  The figure is 
   b1024    B 1024, D 4, A 2, U 512
 The default rule: "srlx" iff EVERY round's srlx time at the default shape is at most 1.10 times the same round's torch time.
 --trace-loop runs, at --shape, one train() of each arm and then TRACE_CALLS of each arm in turn: a kernel trace of it gives the launches and the kernel time per
-train() of each arm (the libsrlx kernels are named k_dqnnot_* and k_mlp_gemm_*; everything else is torch's)."""
+train() of each arm (the libsrlx kernels are named k_dqnnot_* and k_mlp_gemm_*; everything else is torch's).
+
+The acting arm, the measurement that decides dqn_not.Parameter.act_backend's default:
+
+    python tools/dqnnot_probe.py --act --out profiles/dqnnot_act_probe.json
+    rocprofv3 --kernel-trace --stats -d DIR -o dqnnot_act --output-format csv -- python tools/dqnnot_probe.py --act --trace-loop   # a run of its own
+
+Whole `Parameter.pred_q` calls on dqn_not.Config()'s network on CartPole-v1 (D 4, A 2, U 512) at n = 1 (what Worker.policy asks) and n = 1024, "srlx" against
+"torch" on equal weights: one untimed call of each arm, then three interleaved rounds of ACT_CALLS calls each.  The rule is the same, at n = 1."""
 import argparse
 import json
 import os
@@ -23,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 CALLS, TRACE_CALLS = 200, 100
+ACT_CALLS, ACT_ROWS = 2000, (1, 1024)
 SHAPES = {"default": (32, 4, 2, 512), "b256": (256, 64, 16, 512), "b1024": (1024, 4, 2, 512)}  # B, D, A, U
 ARMS = ("srlx", "torch")
 
@@ -86,15 +95,82 @@ def measure(shape):
     return res
 
 
+def _actor(backend):
+    """A GPU dqn_not.Parameter of dqn_not.Config() on CartPole-v1 (D 4, A 2, U 512) on one acting backend; both arms hold equal weights."""
+    import torch
+
+    import dqnnot_reference as R
+    from simple_distributed_rl_amd.algorithms import dqn_not
+
+    torch.manual_seed(1)
+    p = dqn_not.Parameter(R.make_config(4, 512, 2, device="cuda"))
+    p.act_backend = backend
+    return p
+
+
+def _act_loop(p, states, calls):
+    import torch
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        p.pred_q(states)  # (ends in two device-to-host copies: every call is synchronous)
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / calls
+
+
+def measure_act(n):
+    import numpy as np
+
+    states = np.random.default_rng(3).standard_normal((n, 4)).astype(np.float32)
+    arms = {a: _actor(a) for a in ARMS}
+    for a, p in arms.items():
+        p.pred_q(states)
+        assert p.act_path == a, (a, p.act_path, p.why_not_srlx_act)
+    runs = {a: [] for a in arms}
+    for _ in range(3):
+        for a, p in arms.items():
+            runs[a].append(_act_loop(p, states, ACT_CALLS))
+    res = dict(what=f"one whole Parameter.pred_q(states) (host-to-device copy of the states, the forward, q and v back as numpy), ms, mean of {ACT_CALLS} calls per round",
+               shape=dict(rows=n, obs_dim=4, actions=2, base_units=512))
+    res.update({a + "_ms": r for a, r in runs.items()})
+    res["srlx_over_torch_by_round"] = [s / t for s, t in zip(runs["srlx"], runs["torch"])]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dqnnot_probe.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/dqnnot_probe.json, with --act profiles/dqnnot_act_probe.json")
+    ap.add_argument("--act", action="store_true", help="the acting arm (DESIGN.md 7z): whole pred_q calls at n = 1 and n = 1024, which decide Parameter.act_backend")
     ap.add_argument("--trace-loop", action="store_true")
     ap.add_argument("--shape", default="default", choices=list(SHAPES), help="the shape of --trace-loop")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "dqnnot_act_probe.json" if args.act else "dqnnot_probe.json")
     import torch
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
+    if args.act and args.trace_loop:  # (a kernel trace of it gives k_dqnnot_act's time at both row counts: the grid is 1, then 64)
+        import numpy as np
+
+        p = _actor("srlx")
+        for n in ACT_ROWS:
+            _act_loop(p, np.zeros((n, 4), np.float32), 1 + TRACE_CALLS)
+        print(f"trace loop: 1 + {TRACE_CALLS} pred_q calls on 'srlx' at each of n = {ACT_ROWS}")
+        return
+    if args.act:
+        from simple_distributed_rl_amd import _native as N
+
+        out = dict(device=N.device_info(0), torch=torch.__version__)
+        for n in ACT_ROWS:
+            out[f"n{n}"] = measure_act(n)
+            print(n, {k: out[f"n{n}"][k] for k in ("srlx_ms", "torch_ms", "srlx_over_torch_by_round")}, flush=True)
+        out["default_rule"] = dict(rule="act_backend = 'srlx' iff every round's srlx_ms <= 1.10 * torch_ms at n = 1",
+                                   srlx=bool(all(r <= 1.10 for r in out["n1"]["srlx_over_torch_by_round"])))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+        print("wrote", args.out)
+        return
     if args.trace_loop:
         for a in ARMS:
             tr = _trainer(args.shape, a)
