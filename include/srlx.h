@@ -1506,6 +1506,21 @@ int srlx_vppo_update_gemm(srlx_vppo_t *h, int64_t batch, const float *d_states, 
                           float *d_n_v, float *d_new_logpi, float *d_scalars, void *stream);
 int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
                       void *stream);
+/* srlx_vppo_walk: the network's whole forward for n_rows flat observations in ONE launch (k_mlp_walk, srlx_mlp_walk.h): what the plugin's
+ * Worker asks of `Parameter.net` on every environment step.  It needs srlx_vppo_bind only and reads the bound tensors where they are, so it sees every update
+ * of them.  d_states f32 [n_rows][D].  Writes d_v f32 [n_rows], d_head0 f32 [n_rows][n_out] (logits or locs) and, on a Normal head, d_head1 f32
+ * [n_rows][n_out]: the log-scales clamped to [log_scale_lo, log_scale_hi] as srlx_vppo_forward clamps them (rounded to float32, then clamped).  d_head1 is
+ * required on a Normal head and NULL on a categorical one.  Nothing is sampled.
+ * Arithmetic: a workgroup of 16 waves walks 16 rows through every layer on v_mfma_f64_16x16x4_f64, the activations in LDS planes: the trunk layer by layer,
+ * value_block.0 and policy_block.0 as one pass over the trunk's output where both exist, the remaining branch layers, then value_out_layer and the head.
+ * Operands are float32, widened to float64; products are exact, sums float64 in a fixed order, rounded to float32 ONCE per Linear where the bias is added
+ * (and ReLU applied).  No atomics: equal inputs give equal bits, and a row's result depends neither on n_rows nor on the row's place in the call.  The matrix
+ * core's order inside a group of 4 terms is its own, so a value may differ from srlx_vppo_forward's in its last bit.
+ * Envelope: the handle's shape; n_rows 1..65536 whatever the handle's max_batch.  Refusals come before any device call, as SRLX_ERR_INVALID with a message
+ * that names vppo_walk, in this order: n_rows outside 1..65536, a NULL handle, unbound parameters, NULL d_states, d_v or d_head0, d_head1 against the head,
+ * unordered clamp ends.  Nothing synchronises. */
+int srlx_vppo_walk(srlx_vppo_t *h, int64_t n_rows, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
+                   void *stream);
 
 /* ---- V-PPO: the device engine's launches outside the update (srlx_vppo.hip, srlx_vppo_lanes.hip) -------------------------------------------------
  *   srlx_vppo_act : the Worker's policy() (algorithms/ppo_v.py, discrete branch, training) for n_rows lanes in ONE launch, on a categorical handle; needs
@@ -1672,6 +1687,13 @@ int srlx_notsac_update_gemm(srlx_notsac_t *h, int64_t batch, const float *d_stat
                             float *d_pi_action, float *d_scalars, void *stream);
 int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
                         const float *d_actions, float *d_q, void *stream);
+/* srlx_notsac_walk: the policy's whole forward for n_rows flat observations in ONE launch (k_mlp_walk, srlx_mlp_walk.h): what the plugin's
+ * Worker asks of `Parameter.policy` on every environment step.  srlx_vppo_walk's contract without a value: d_head0 f32 [n_rows][n_out] logits or locs,
+ * d_head1 the CLAMPED log-scales (required on a Normal head, NULL on a Gumbel one).  It needs srlx_notsac_bind only; the Q-network is not read.  n_rows
+ * 1..65536 whatever the handle's max_batch; refusals before any device call, as SRLX_ERR_INVALID with a message that names notsac_walk, in srlx_vppo_walk's
+ * order.  Nothing synchronises. */
+int srlx_notsac_walk(srlx_notsac_t *h, int64_t n_rows, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
+                     void *stream);
 
 /* ---- NoTarget_DQN on flat observations (srlx_dqnnot.hip; srl/algorithms/dqn_not/trainer.py:33-87) -----------------------------------------------
  * One dueling Q-network -- hidden_block Linear(D, U) + ReLU; v_block Linear(U, U) + ReLU + Linear(U, 1); adv_block Linear(U, U) + ReLU + Linear(U, A);

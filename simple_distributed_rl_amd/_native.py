@@ -289,6 +289,7 @@ SIGNATURES = {
     "srlx_vppo_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 6 + [c_int, c_f64, c_f64] + [c_p] * 5),
     "srlx_vppo_update_gemm": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 6 + [c_int, c_f64, c_f64] + [c_p] * 5),
     "srlx_vppo_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p]),
+    "srlx_vppo_walk": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p]),
     "srlx_vppo_act": (c_int, [c_p, c_i64, c_p, c_u64, c_p, c_f64, c_p, c_p, c_p, c_p, c_p]),
     "srlx_vppo_lanes_create": (c_int, [ctypes.POINTER(c_p), c_i64, c_int, c_i64, c_i64, c_f64, c_int]),
     "srlx_vppo_lanes_destroy": (c_int, [c_p]),
@@ -314,6 +315,7 @@ SIGNATURES = {
     "srlx_notsac_update": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
     "srlx_notsac_update_gemm": (c_int, [c_p, c_i64] + [c_p] * 7 + [c_f64] * 4 + [c_int, c_f64, c_f64] + [c_p] * 6),
     "srlx_notsac_forward": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p, c_p, c_p]),
+    "srlx_notsac_walk": (c_int, [c_p, c_i64, c_p, c_f64, c_f64, c_p, c_p, c_p]),
     "srlx_dqnnot_create": (c_int, [ctypes.POINTER(c_p), c_int, c_int, c_int, c_i64, c_int]),
     "srlx_dqnnot_destroy": (c_int, [c_p]),
     "srlx_dqnnot_bind_params": (c_int, [c_p, c_p]),

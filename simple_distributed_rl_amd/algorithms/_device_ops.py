@@ -78,6 +78,36 @@ class SrlxUpdateBackend:
         return self._srlx
 
 
+class SrlxActBackend:
+    """The acting backend of a Parameter whose policy forward runs on libsrlx or in torch (ppo_v.Parameter, sac_not.Parameter), with dqn_not.Parameter's
+    meaning: `act_backend` asks for "srlx" (one k_mlp_walk launch) or "torch" (the module's forward); `act_path` names what the last call ran,
+    and `why_not_srlx_act` holds the reason when "srlx" was asked for and torch ran.  The handle is made at the first GPU call and binds the tensors by
+    address, so it sees `call_restore` and a Trainer's updates; `to_device` drops it (`_reset_act`).  The Parameter supplies `_srlx_act_class()`."""
+
+    # "srlx" | "torch".  "torch" until the measurement of DESIGN.md 7za has decided by the project's 1.10 rule.
+    act_backend = "torch"
+
+    def _reset_act(self) -> None:
+        """(from `setup` and `to_device`: a handle held the old tensors' addresses)"""
+        self.act_path = self.why_not_srlx_act = ""
+        self._act, self._act_why = None, None  # the acting handle, and why there is none (None: not asked yet for these tensors)
+
+    def _srlx_act(self, n: int):
+        """The acting handle when libsrlx serves a call of n rows; otherwise None, with the reason in `why_not_srlx_act` ('' where "torch" was asked for)."""
+        if self.act_backend not in ("srlx", "torch"):
+            raise ValueError(f"act_backend {self.act_backend!r}: 'srlx' or 'torch'")
+        self.why_not_srlx_act = ""
+        if self.act_backend == "torch":
+            return None
+        cls = self._srlx_act_class()
+        if self._act_why is None:
+            self._act_why = cls.why_not(self)
+            if not self._act_why:
+                self._act = cls(self)
+        self.why_not_srlx_act = self._act_why or cls.rows_reason(n)
+        return None if self.why_not_srlx_act else self._act
+
+
 class TdOps:
     def __init__(self, device: torch.device):
         self.dev = device

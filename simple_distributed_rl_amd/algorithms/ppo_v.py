@@ -17,7 +17,8 @@ Trainer.train() (:111-178) is DESIGN.md 7o's contract, on one of three backends 
   "torch"      the reference's step in plain torch float32 with torch.optim.Adam, for everything else.
 `update_backend` is an attribute of the class (the default) or of a Trainer; the backend is fixed for a Trainer's life at its first train(), and each backend
 owns its Adam state.  `update_path` names the path of the last call, `why_not_srlx_update` the reason a request for "srlx" was served by torch.
-`engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path; `device/vppo_engine.py: VppoEngine` trains a Parameter of this
+The Worker acts through `Parameter.dist`, whose forward is one srlx_vppo_walk launch where `Parameter.act_backend` is "srlx" (the default is
+"torch").  `engine_kind(ppo_v.Config())` is None and `Runner.train()` runs the plugin path; `device/vppo_engine.py: VppoEngine` trains a Parameter of this
 module in place on E lock-stepped lanes for the categorical head on flat observations, `VppoNormalEngine` (7q) for the Normal head.
 
 What is kept from the reference although it reads oddly:
@@ -42,7 +43,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from simple_distributed_rl_amd.algorithms._device_ops import SrlxUpdateBackend
+from simple_distributed_rl_amd.algorithms._device_ops import SrlxActBackend, SrlxUpdateBackend
 from simple_distributed_rl_amd.base.exception import UndefinedError
 from simple_distributed_rl_amd.base.rl.algorithms.base_ppo import RLConfig, RLWorker
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
@@ -232,13 +233,33 @@ class ActorCriticNetwork(nn.Module):
         return self.value_out_layer(self.value_block(x)), self.policy_dist_block(self.policy_block(x))
 
 
-class Parameter(RLParameter):
-    """:75-87."""
+class Parameter(SrlxActBackend, RLParameter):
+    """:75-87.  `dist` is what the Worker acts through, on one of two backends (SrlxActBackend: `act_backend`, `act_path`, `why_not_srlx_act`): "srlx" is one
+    srlx_vppo_walk launch (device/vppo.py: VppoAct) for GPU parameters inside the update's envelope, "torch" the module's forward."""
 
     def setup(self):
         self.np_dtype = self.config.get_dtype("np")
         self.device = torch.device(self.config.used_device_torch)
         self.net = ActorCriticNetwork(self.config).to(self.device)
+        self._reset_act()
+
+    def _srlx_act_class(self):
+        from simple_distributed_rl_amd.device.vppo import VppoAct
+
+        return VppoAct
+
+    def dist(self, state: np.ndarray):
+        """The policy's distribution over the rows of `state` [n][...]: on "srlx" built from the kernel's outputs, on "torch" by the module."""
+        x = torch.as_tensor(state, device=self.device)
+        act = self._srlx_act(x.shape[0])
+        if act is not None:
+            _, h0, h1 = act.act(x.reshape(x.shape[0], -1).float())
+            p_dist = CategoricalDist(h0) if h1 is None else NormalDist(h0, h1)
+        else:
+            with torch.no_grad():
+                p_dist = self.net(x)[1]
+        self.act_path = "srlx" if act is not None else "torch"
+        return p_dist
 
     def call_restore(self, data: Any, from_serialized: bool = False, **kwargs) -> None:
         # (in place: the libsrlx backend holds these tensors by address)
@@ -254,6 +275,7 @@ class Parameter(RLParameter):
         """Moves every tensor; the tensors are new ones afterwards (call before a Trainer binds them)."""
         self.device = torch.device(device)
         self.net.to(self.device)
+        self._reset_act()
 
     def summary(self, **kwargs):
         print(self.net)
@@ -367,9 +389,7 @@ class Worker(RLWorker):
         self.np_dtype = self.config.get_dtype("np")
 
     def _dist(self, worker):
-        p = self.parameter
-        with torch.no_grad():
-            return p.net(torch.as_tensor(worker.state[np.newaxis, ...].astype(self.np_dtype), device=p.device))[1]
+        return self.parameter.dist(worker.state[np.newaxis, ...].astype(self.np_dtype))
 
     def policy(self, worker):
         cfg = self.config

@@ -18,6 +18,8 @@ Trainer.train() (:131-191) is DESIGN.md 7r's contract, on one of three backends 
   "srlx_gemm"  the same call layer by layer on the float64 matrix cores (DESIGN.md 7u): opt-in, for wide layers and full batches; served and refused as "srlx";
   "torch"      the reference's step in plain torch float32 with two torch.optim.Adam, for everything else.
 `update_backend`, `update_path` and `why_not_srlx_update` work as in ppo_v.Trainer.  `engine_kind(sac_not.Config())` is None: there is no device engine.
+The Worker acts through `Parameter.dist`, whose forward is one srlx_notsac_walk launch where `Parameter.act_backend` is "srlx" (the default is
+"torch").
 
 The noise is an input.  `train_on_batch(..., noise)` takes a float32 tensor [2][B][K] of standard normals (Normal head) or [2][B][A] of uniforms in [0, 1)
 (Gumbel head): plane 0 serves the target's next action, plane 1 the policy step.  With None the trainer draws the planes with torch on the parameter's
@@ -44,8 +46,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from simple_distributed_rl_amd.algorithms._device_ops import SrlxUpdateBackend
-from simple_distributed_rl_amd.algorithms.ppo_v import NormalDistBlock
+from simple_distributed_rl_amd.algorithms._device_ops import SrlxActBackend, SrlxUpdateBackend
+from simple_distributed_rl_amd.algorithms.ppo_v import NormalDist, NormalDistBlock
 from simple_distributed_rl_amd.base.exception import UndefinedError
 from simple_distributed_rl_amd.base.rl.algorithms.base_ppo import RLConfig, RLWorker
 from simple_distributed_rl_amd.base.rl.parameter import RLParameter
@@ -180,14 +182,34 @@ class QNetwork(nn.Module):
         return self.q_out_layer(self.q_block(x))
 
 
-class Parameter(RLParameter):
-    """:87-105."""
+class Parameter(SrlxActBackend, RLParameter):
+    """:87-105.  `dist` is what the Worker acts through, on one of two backends (SrlxActBackend: `act_backend`, `act_path`, `why_not_srlx_act`): "srlx" is one
+    srlx_notsac_walk launch (device/notsac.py: NotSacAct) for GPU parameters inside the update's envelope, "torch" the module's forward."""
 
     def setup(self):
         self.np_dtype = self.config.get_dtype("np")
         self.device = torch.device(self.config.used_device_torch)
         self.policy = PolicyNetwork(self.config).to(self.device)
         self.qnet = QNetwork(self.config).to(self.device)
+        self._reset_act()
+
+    def _srlx_act_class(self):
+        from simple_distributed_rl_amd.device.notsac import NotSacAct
+
+        return NotSacAct
+
+    def dist(self, state: np.ndarray):
+        """The policy's distribution over the rows of `state` [n][...]: on "srlx" built from the kernel's outputs, on "torch" by the module."""
+        x = torch.as_tensor(state, device=self.device)
+        act = self._srlx_act(x.shape[0])
+        if act is not None:
+            h0, h1 = act.act(x.reshape(x.shape[0], -1).float())
+            p_dist = CategoricalGumbelDist(h0) if h1 is None else NormalDist(h0, h1)
+        else:
+            with torch.no_grad():
+                p_dist = self.policy(x)
+        self.act_path = "srlx" if act is not None else "torch"
+        return p_dist
 
     def call_restore(self, data: Any, from_serialized: bool = False, **kwargs) -> None:
         # (in place: the libsrlx backend holds these tensors by address)
@@ -206,6 +228,7 @@ class Parameter(RLParameter):
         self.device = torch.device(device)
         self.policy.to(self.device)
         self.qnet.to(self.device)
+        self._reset_act()
 
     def summary(self, **kwargs):
         print(self.policy)
@@ -333,9 +356,7 @@ class Worker(RLWorker):
         self.np_dtype = self.config.get_dtype("np")
 
     def _dist(self, worker):
-        p = self.parameter
-        with torch.no_grad():
-            return p.policy(torch.as_tensor(worker.state[np.newaxis, ...].astype(self.np_dtype), device=p.device))
+        return self.parameter.dist(worker.state[np.newaxis, ...].astype(self.np_dtype))
 
     def policy(self, worker):
         cfg = self.config

@@ -20,6 +20,7 @@
 // butterfly each and everything after them is lane-uniform float64.  The gradient row is rounded to float32 BEFORE the data gradients read it (the weight
 // gradient launch reads the same floats), lane r's element broadcast by a uniform read.  No atomics, a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_mlp_gemm.h"
+#include "srlx_mlp_walk.h"
 #include "srlx_param_tail.h"
 #include <cmath>
 
@@ -188,12 +189,16 @@ __global__ void __launch_bounds__(kThreads) k_dqnnot_head(HeadArgs a) {
 // The head: wave 0 runs v_block.2 (one live column) over hv, waves 1.. the ceil(A / 16) tiles of adv_block.2 over ha, through the same tile loop; sums and
 // biases stay float64 in LDS.  Then thread r finishes row r in float64 -- the mean in action order, q = v + adv - mean -- rounds q and v once and takes the
 // first maximum of the ROUNDED q.  Fixed order everywhere, no atomics; a row's arithmetic does not know its place or n.
-constexpr int kActWaves = 16, kActThreads = 64 * kActWaves;
-constexpr int kActRows = 16;   // rows of a workgroup
-constexpr int kActStep = 32;   // reduction indices per step
-constexpr i64 kActMaxRows = 65536;
+// The plane layout, the tile loop and the pass (act_slot, quad_at, act_tiles, act_layer) are srlx_mlp_walk.h's since DESIGN.md 7za: this kernel's own, lifted
+// there unchanged for k_mlp_walk to share.
+using srlxw::act_layer;
+using srlxw::act_slot;
+using srlxw::act_tiles;
+constexpr int kActThreads = srlxw::kThreads;  // kActWaves = 16 waves
+constexpr int kActRows = srlxw::kRows;        // rows of a workgroup
+constexpr i64 kActMaxRows = srlxw::kMaxRows;
 
-constexpr int act_ld(int K) { return (K + kActStep - 1) / kActStep * kActStep + 4; }  // a plane's row stride in floats: 4 * odd
+constexpr int act_ld(int K) { return srlxw::ld(K); }  // a plane's row stride in floats: 4 * odd
 constexpr size_t act_lds_bytes(int D, int U, int A) { return sizeof(float) * kActRows * (act_ld(D) + 3 * act_ld(U)) + sizeof(double) * kActRows * (1 + A); }
 constexpr size_t kActLdsCap = act_lds_bytes(256, kMaxUnits, kMaxActions);  // 119 936 bytes
 
@@ -205,108 +210,6 @@ struct ActArgs {
     float *q, *v;     // [n][A], [n][1]; NULL: not wanted
     int32_t *action;  // [n]
 };
-
-// where a plane keeps reduction index k of a row
-__device__ __forceinline__ int act_slot(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-
-__device__ __forceinline__ float quad_at(const float4 &q, int j) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; }
-
-// kT column tiles over the K reduction indices of one plane: acc[i] += sum_k plane[row][k] w[i][k].  `a`: the plane at this lane's row and lane group;
-// w[i]: this lane's weight row of tile i.  live[i] false: the lane's column does not exist; w[i] is then the weight's first row, the lane computes a column
-// nobody stores (a column's B operand reaches that column's sums only), and only the masked last step asks.
-// The K / 32 full steps load WITHOUT a condition: a branch around a load makes the compiler wait for every load in flight where the branch ends, which put
-// each quad's latency in front of the MFMAs (measured: 128 us per call at U 512 against 80 us without).  Two steps per trip on two sets of registers; a
-// step's quads are requested before the MFMAs of the step in front of it, and the request behind the last full step repeats that step's.  What is left of K
-// (the first layer's D, where it is no multiple of 32) is one more step on load_quad, masked at K.
-template <int kT, bool kVec>
-__device__ __forceinline__ void act_tiles(const float *a, int K, const float *const (&w)[kT], const bool (&live)[kT], srlxg::f64x4 (&acc)[kT]) {
-    const int g4 = ((threadIdx.x & 63) >> 4) << 2;
-    float4 q0[kT][2], q1[kT][2];
-    auto fetch = [&](float4(&q)[kT][2], int k0) {
-#pragma unroll
-        for (int i = 0; i < kT; i++)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const float *p = w[i] + k0 + 16 * s + g4;
-                if constexpr (kVec) q[i][s] = *reinterpret_cast<const float4 *>(p);
-                else q[i][s] = make_float4(p[0], p[1], p[2], p[3]);
-            }
-    };
-    auto step = [&](const float4(&q)[kT][2], int k0) {
-#pragma unroll
-        for (int s = 0; s < 2; s++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const double av = (double)a[k0 + 16 * s + 4 * j];
-#pragma unroll
-                for (int i = 0; i < kT; i++) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, (double)quad_at(q[i][s], j), acc[i], 0, 0, 0);
-            }
-    };
-    const int full = K / kActStep;
-    if (full > 0) {
-        const int last = (full - 1) * kActStep;
-        int k0 = 0;
-        fetch(q0, 0);
-        for (; k0 < last; k0 += 2 * kActStep) {  // (nothing conditional inside: the compiler moves a load whose values one branch reads into that branch)
-            fetch(q1, k0 + kActStep);
-            step(q0, k0);
-            fetch(q0, min(k0 + 2 * kActStep, last));
-            step(q1, k0 + kActStep);
-        }
-        if (k0 == last) step(q0, last);  // an odd number of steps: q0 holds the last one's quads
-    }
-    if (K % kActStep) {
-        const int k0 = full * kActStep;
-#pragma unroll
-        for (int i = 0; i < kT; i++)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const int k = k0 + 16 * s + g4;
-                q0[i][s] = srlxg::load_quad(w[i] + k, live[i] ? K - k : 0, kVec);
-            }
-        step(q0, k0);
-    }
-}
-
-// One pass of Linear + ReLU from the plane `in` (K reduction indices, row stride ldin): column tiles 0..UT-1 are (w0, b0) into out0, tiles UT.. (w1, b1) into
-// out1, U output columns each.  Every wave takes its tiles two at a time; no barrier inside.
-__device__ __forceinline__ void act_layer(const float *in, int ldin, int K, int U, int NT, const float *w0, const float *b0, float *out0, const float *w1,
-                                          const float *b1, float *out1, int ldout) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
-    const int UT = U / 16;
-    const bool vec = K % 4 == 0 && srlxg::aligned16(w0) && srlxg::aligned16(w1);
-    const float *a = in + fr * ldin + g;
-    for (int t = wave; t < NT; t += 2 * kActWaves) {
-        const float *w[2], *b[2];
-        float *o[2];
-        int col[2];
-        bool live[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int ti = t + i * kActWaves;
-            const bool second = ti >= UT;
-            col[i] = (ti - (second ? UT : 0)) * 16 + fr;
-            const float *base = second ? w1 : w0;
-            live[i] = ti < NT;
-            w[i] = base + (live[i] ? (i64)col[i] * K : 0);
-            b[i] = second ? b1 : b0, o[i] = second ? out1 : out0;
-        }
-        srlxg::f64x4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-        if (vec) act_tiles<2, true>(a, K, w, live, acc);
-        else act_tiles<2, false>(a, K, w, live, acc);
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            if (!live[i]) continue;
-            const double bias = (double)b[i][col[i]];
-            float *dst = o[i] + act_slot(col[i]);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {  // (D layout: register r is row 4 r + l / 16)
-                const float z = (float)(acc[i][r] + bias);
-                dst[(4 * r + g) * ldout] = z > 0.f ? z : 0.f;
-            }
-        }
-    }
-}
 
 SRLXG_KERNEL void __launch_bounds__(kActThreads) k_dqnnot_act(ActArgs a) {
     extern __shared__ __attribute__((aligned(16))) float act_lds[];

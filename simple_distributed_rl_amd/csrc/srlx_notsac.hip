@@ -17,6 +17,8 @@
 //                     down q_out and q_block, through the embedding columns, the SiLU derivative and the act_block's weight transposed (d loss / d action),
 //                     through the head's Jacobian and down the policy's chain
 //   k_notsac_forward  the head's outputs of n rows and, for given actions, q(s, a)
+//   k_mlp_walk        (srlx_mlp_walk.h) the head's outputs for the plugin's acting: 16 rows per workgroup through the policy on the float64
+//                     matrix cores, the activations in LDS
 // One update: q_rows, grad (Q), step (Q), pi_rows, grad (policy), step (policy); the stream orders them and nothing synchronises the host.
 // LDS: three row buffers of 16 x (widest row + 1) floats (the act_block's pre-activations have to outlive q_block's chains) and the 32 KB weight tile:
 // 131 264 bytes at a widest row of 512 -- the concatenated row of D + E floats is held to that.
@@ -33,6 +35,7 @@
 // with k_notsac_grad and k_notsac_step as the tail of each half.  upload_gemm builds these steps on srlxg::Plan, the handle keeps them in a srlxg::GemmPath
 //  and update walks them; GemmScratch is the one statement of the path's scratch layout.
 #include "srlx_mlp_gemm.h"
+#include "srlx_mlp_walk.h"
 #include "srlx_notsac_math.h"
 #include "srlx_param_tail.h"
 #include <cmath>
@@ -865,6 +868,7 @@ int srlx_notsac_create(srlx_notsac_t **out, int obs_dim, int head, int n_out, in
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_q_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_pi_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_notsac_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
+    if (e == hipSuccess) e = srlxw::raise_lds_limit();
     if (e != hipSuccess) {
         srlx_notsac_destroy(h);
         srlx::set_error("notsac_create: device set-up failed: %s", hipGetErrorString(e));
@@ -934,6 +938,28 @@ int srlx_notsac_forward(srlx_notsac_t *h, int64_t n, const float *d_states, doub
     const int rpw = rows_per_workgroup(h, n);
     hipLaunchKernelGGL(k_notsac_forward, dim3((unsigned)((n + rpw - 1) / rpw)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states,
                        d_actions, d_head0, d_head1, d_q, (float)log_scale_lo, (float)log_scale_hi, rpw, h->D, h->A, h->E, lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_notsac_walk(srlx_notsac_t *h, int64_t n_rows, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_head0, float *d_head1,
+                     void *stream) {
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= srlxw::kMaxRows, "notsac_walk: n_rows %lld (1..%lld)", (long long)n_rows, (long long)srlxw::kMaxRows);
+    SRLX_REQUIRE(h, "notsac_walk: NULL handle");
+    SRLX_REQUIRE(h->ps.bound, "notsac_walk: bind the parameters first (srlx_notsac_bind)");
+    SRLX_REQUIRE(d_states && d_head0, "notsac_walk: NULL d_states or d_head0");
+    SRLX_REQUIRE((d_head1 != nullptr) == (h->head == 1), "notsac_walk: d_head1 takes the log-scales of a Normal head and is NULL on a Gumbel one");
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "notsac_walk: the log-scale clamp's ends are ordered");
+    // the policy alone, layer by layer; its head in the kernel's last round
+    float *const *P = h->ps.p;
+    srlxw::WalkPlan w;
+    int v = 0, K = h->D;
+    for (int l = 0; l < h->Lp; K = h->Wp[l], l++) v = w.pass(v, K, P[2 * l], P[2 * l + 1], h->Wp[l]);
+    float *const *hd = P + 2 * h->Lp;
+    w.dist_head(v, K, h->A, hd[0], hd[1], h->head ? hd[2] : nullptr, h->head ? hd[3] : nullptr);
+    SRLX_REQUIRE(w.finish(h->D), "notsac_walk: the network's planes do not fit the kernel's LDS");
+    srlx::DeviceGuard g(h->device);
+    srlxw::launch(w, n_rows, d_states, (float)log_scale_lo, (float)log_scale_hi, nullptr, d_head0, d_head1, (hipStream_t)stream);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

@@ -12,6 +12,8 @@
 //                   the last four threads of the launch reduce the four losses
 //   k_vppo_step     every workgroup sums the same partial squares in the same order (the norm), then one thread per parameter: the clipped gradient and Adam
 //   k_vppo_forward  v and the head's outputs of n rows
+//   k_mlp_walk      (srlx_mlp_walk.h) the same outputs for the plugin's acting: 16 rows per workgroup through the whole network on the float64
+//                   matrix cores, the activations in LDS; walk_plan below writes its pass table
 //   k_vppo_act      the Worker's policy() for the lanes of a device engine: trunk and policy branch of up to 16 rows per workgroup, keyed uniforms, the action and
 //                   its log-probability (two row buffers, 98 432 bytes of LDS at most)
 //   k_vppo_act_normal  the same on the Normal head: Box-Muller on keyed uniforms, the action before tanh, every element's log-probability, the environment's
@@ -22,6 +24,7 @@
 // launches, k_vppo_loss_rows as one pointwise step, backward launches), the handle keeps them in a srlxg::GemmPath and update walks them.
 // No atomics and a fixed order in every sum: equal inputs give equal bits.
 #include "srlx_mlp_gemm.h"
+#include "srlx_mlp_walk.h"
 #include "srlx_param_tail.h"
 #include "srlx_vppo_math.h"
 #include <cmath>
@@ -631,6 +634,28 @@ int upload_gemm(const char *who, srlx_vppo *h) {
     return h->path.upload(who);
 }
 
+// k_mlp_walk's pass table for this handle: the trunk layer by layer; value_block.0 || policy_block.0 as ONE pass on one read of the trunk's
+// output where both exist; what is left of either branch as one-matrix passes (their inputs are different planes); value_out_layer and the distribution head
+// in the kernel's last round.  False: the plan does not fit (no shape of check_shape's envelope).
+bool walk_plan(const srlx_vppo *h, srlxw::WalkPlan &w) {
+    float *const *P = h->ps.p;
+    const int Lt = h->Lt, Lv = h->Lv, Lp = h->Lp;
+    auto lin = [&](int l) { return P + 2 * l; };  // Linear number l in state-dict order: weight, bias
+    int top = 0, K = h->D;
+    for (int l = 0; l < Lt; K = h->Wt[l], l++) top = w.pass(top, K, lin(l)[0], lin(l)[1], h->Wt[l]);
+    const int value_out = Lt + Lv, pol = Lt + Lv + 1, head = pol + Lp;
+    int vv = top, vp = top, Kv = K, Kp = K, dv = 0, dp = 0;
+    if (Lv && Lp) {
+        vv = w.pass(top, K, lin(Lt)[0], lin(Lt)[1], h->Wv[0], lin(pol)[0], lin(pol)[1], h->Wp[0]);
+        vp = vv + 1, Kv = h->Wv[0], Kp = h->Wp[0], dv = dp = 1;
+    }
+    for (; dv < Lv; Kv = h->Wv[dv], dv++) vv = w.pass(vv, Kv, lin(Lt + dv)[0], lin(Lt + dv)[1], h->Wv[dv]);
+    for (; dp < Lp; Kp = h->Wp[dp], dp++) vp = w.pass(vp, Kp, lin(pol + dp)[0], lin(pol + dp)[1], h->Wp[dp]);
+    w.value_head(vv, Kv, lin(value_out)[0], lin(value_out)[1]);
+    w.dist_head(vp, Kp, h->A, lin(head)[0], lin(head)[1], h->head ? lin(head + 1)[0] : nullptr, h->head ? lin(head + 1)[1] : nullptr);
+    return w.finish(h->D);
+}
+
 // srlx_vppo_update (gemm = false: k_vppo_rows) and srlx_vppo_update_gemm (the layer-wise launches of upload_gemm's plan around k_vppo_loss_rows): one contract, one
 // set of planes, one gradient, clip and Adam tail.  `who` names the entry point in every message.
 int update(const char *who, bool gemm, srlx_vppo *h, int64_t batch, const float *d_states, const float *d_next_states, const void *d_actions, const float *d_old_logpi,
@@ -734,6 +759,7 @@ static int create(const char *who, bool gemm_only, srlx_vppo_t **out, int obs_di
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap3);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap2);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vppo_act_normal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)srlxt::kLdsCap2);
+    if (e == hipSuccess) e = srlxw::raise_lds_limit();
     if (e != hipSuccess) {
         srlx_vppo_destroy(h);
         srlx::set_error("%s: device set-up failed: %s", who, hipGetErrorString(e));
@@ -800,6 +826,22 @@ int srlx_vppo_forward(srlx_vppo_t *h, int64_t n, const float *d_states, double l
     if (!h->ps.net_ok) SRLX_TRY(upload_net(h));
     hipLaunchKernelGGL(k_vppo_forward, dim3((unsigned)((n + kRows - 1) / kRows)), dim3(kThreads), lds_bytes(h), (hipStream_t)stream, (const Net *)h->d_net, (i64)n, d_states, d_v,
                        d_head0, d_head1, (float)log_scale_lo, (float)log_scale_hi, h->D, lds_stride(h));
+    SRLX_HIP(hipGetLastError());
+    return SRLX_OK;
+}
+
+int srlx_vppo_walk(srlx_vppo_t *h, int64_t n_rows, const float *d_states, double log_scale_lo, double log_scale_hi, float *d_v, float *d_head0, float *d_head1,
+                   void *stream) {
+    SRLX_REQUIRE(n_rows >= 1 && n_rows <= srlxw::kMaxRows, "vppo_walk: n_rows %lld (1..%lld)", (long long)n_rows, (long long)srlxw::kMaxRows);
+    SRLX_REQUIRE(h, "vppo_walk: NULL handle");
+    SRLX_REQUIRE(h->ps.bound, "vppo_walk: bind the parameters first (srlx_vppo_bind)");
+    SRLX_REQUIRE(d_states && d_v && d_head0, "vppo_walk: NULL d_states, d_v or d_head0");
+    SRLX_REQUIRE((d_head1 != nullptr) == (h->head == 1), "vppo_walk: d_head1 takes the log-scales of a Normal head and is NULL on a categorical one");
+    SRLX_REQUIRE(log_scale_lo <= log_scale_hi, "vppo_walk: the log-scale clamp's ends are ordered");
+    srlxw::WalkPlan w;
+    SRLX_REQUIRE(walk_plan(h, w), "vppo_walk: the network's planes do not fit the kernel's LDS");
+    srlx::DeviceGuard g(h->device);
+    srlxw::launch(w, n_rows, d_states, (float)log_scale_lo, (float)log_scale_hi, d_v, d_head0, d_head1, (hipStream_t)stream);
     SRLX_HIP(hipGetLastError());
     return SRLX_OK;
 }

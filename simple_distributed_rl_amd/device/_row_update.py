@@ -74,6 +74,89 @@ class LibUpdate:
         return cls.why_not(parameter, batch, config) == ""
 
 
+# ---- acting on k_mlp_walk (csrc/srlx_mlp_walk.h) ------------------------------------------------------------------------------------------------
+WALK_MAX_ROWS = 65536  # srlx_*_walk's largest n_rows
+WALK_MAX_PLANES = 3
+WALK_LDS_LIMIT = 163840  # gfx950's LDS per workgroup
+
+
+def walk_ld(K: int) -> int:
+    """A plane's row stride in floats."""
+    return (K + 31) // 32 * 32 + 4
+
+
+def walk_plan(D: int, passes, heads):
+    """srlx_mlp_walk.h's WalkPlan::finish as host arithmetic: `passes` is the walk as [(input value, (widths of its 1 or 2 outputs))] with value 0 the observation
+    and every output the next value, `heads` the values the heads read.  A value keeps its plane up to its last reader; an output takes the lowest plane free
+    while its pass runs.  Returns (planes, bytes of dynamic LDS), or None where the kernel refuses: more than WALK_MAX_PLANES planes, or more LDS than gfx950's."""
+    last, outs, nval = {}, [], 1
+    for p, (vin, widths) in enumerate(passes):
+        last[vin] = p
+        outs.append(list(range(nval, nval + len(widths))))
+        nval += len(widths)
+    for v in heads:
+        last[v] = len(passes)
+    holder, planes = [None] * WALK_MAX_PLANES, 0
+    for p in range(len(passes)):
+        holder = [v if v is not None and last.get(v, -1) >= p else None for v in holder]
+        for v in outs[p]:
+            if None not in holder:
+                return None
+            k = holder.index(None)
+            holder[k], planes = v, max(planes, k + 1)
+    size = 4 * 16 * (walk_ld(D) + planes * walk_ld(max(u for _, widths in passes for u in widths)))
+    return (planes, size) if size <= WALK_LDS_LIMIT else None
+
+
+class WalkAct(LibUpdate):
+    """A network's forward on libsrlx for acting (srlx_<ABI>_walk: k_mlp_walk): a handle of its own with max_batch 1 -- nothing of the launch is
+    sized by it -- that binds the Parameter's own tensors by address and nothing else: no gradient tensors, no Adam state.  It reads the weights where they are,
+    so it sees `load_state_dict` and every update on the same tensors.  A subclass gives ABI, UPDATE (the update class whose `tensors_of`, `shape_of` and
+    `envelope_reason` say what is served), `passes_of(*shape)` (the walk, for `walk_plan`) and `_create`."""
+    MAX_ROWS = WALK_MAX_ROWS
+    UPDATE = None
+
+    @staticmethod
+    def rows_reason(n: int) -> str:
+        return f"{n} rows above {WALK_MAX_ROWS} in one call" if n > WALK_MAX_ROWS else ""
+
+    @classmethod
+    def why_not(cls, parameter, n: int = 1, config=None) -> str:
+        """'' when libsrlx runs this Parameter's forward for n rows, otherwise the reason it does not: the update class's sentences, the plane plan's, the rows'."""
+        reason = tensor_reason(cls.UPDATE.tensors_of(parameter))
+        if reason:
+            return reason
+        shape = cls.UPDATE.shape_of(parameter)
+        if isinstance(shape, str):
+            return shape
+        reason = cls.UPDATE.envelope_reason(*shape)
+        if not reason and walk_plan(shape[0], *cls.passes_of(*shape)) is None:
+            reason = "the network's planes do not fit the walk kernel's LDS"
+        return reason or cls.rows_reason(n)
+
+    def __init__(self, parameter):
+        reason = self.why_not(parameter)
+        if reason:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        self.params = self.UPDATE.tensors_of(parameter)
+        self.device = self.params[0].device
+        self.shape = self.UPDATE.shape_of(parameter)
+        self.D, self.head, self.n_out = self.shape[:3]
+        self.planes, self.lds_bytes = walk_plan(self.D, *self.passes_of(*self.shape))
+        self._lib = N.lib()
+        self._h = N.c_p()
+        self._create(parameter)
+
+    def _outputs(self, states, want_v: bool):
+        """(states, n, v, head0, head1): the contiguous input and the tensors a call writes."""
+        states = states.contiguous()
+        n = states.shape[0]
+        assert states.dtype == torch.float32 and states.device == self.device and states.numel() == n * self.D
+        f = dict(dtype=torch.float32, device=self.device)
+        v = torch.empty(n, **f) if want_v else None
+        return states, n, v, torch.empty((n, self.n_out), **f), torch.empty((n, self.n_out), **f) if self.head else None
+
+
 class RowUpdate(LibUpdate):
     """A subclass gives ABI, `tensors_of(parameter)` (bind order), `shape_of(parameter)` (a tuple or a sentence), `config_reasons(config)` and
     `envelope_reason(*shape, batch)`."""

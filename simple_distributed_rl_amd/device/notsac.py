@@ -2,7 +2,8 @@
 networks stay what the plugin, checkpoints and `load_state_dict` see -- and owns the handle, the gradient tensors the kernels write (before and after each
 network's norm clip) and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:150-189 for one batch and one
 noise tensor, in six launches; `update(..., gemm=True)` is the same step layer by layer on the float64 matrix cores (srlx_notsac_update_gemm), the
-path for wide layers and full batches."""
+path for wide layers and full batches.  `NotSacAct` is the acting side: a handle that binds the same tensors and nothing else, and runs the
+policy's forward in one launch."""
 import ctypes
 
 import torch
@@ -131,3 +132,30 @@ class NotSacUpdate(R.RowUpdate):
         N.check(self._lib.srlx_notsac_forward(self._h, n, N.tptr(x), self.ls_lo, self.ls_hi, N.tptr(h0), N.tptr(h1), N.tptr(a), N.tptr(q), N.torch_stream_ptr()))
         self._keep_fwd = (x, a)
         return (h0 if not self.head else (h0, h1)) if want_head else None, q
+
+
+class NotSacAct(R.WalkAct):
+    """srlx_notsac_walk for an `algorithms.sac_not.Parameter` (R.WalkAct).  The handle is a whole srlx_notsac handle, so the Q-network's tensors
+    are bound beside the policy's; the walk reads the policy's alone."""
+    ABI = "notsac"
+    UPDATE = NotSacUpdate
+
+    @staticmethod
+    def passes_of(D, head, n_out, pw, qw, act_emb):
+        """The walk for R.walk_plan: the policy block layer by layer; the value its head reads."""
+        return [(l, (w,)) for l, w in enumerate(pw)], (len(pw),)
+
+    def _create(self, parameter):
+        pw, qw, act_emb = self.shape[3:]
+        self.ls_lo, self.ls_hi = log_scale_range(parameter)
+        N.check(self._lib.srlx_notsac_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(pw), _int_array(pw), len(qw), _int_array(qw), act_emb, 1,
+                                             self.device.index or 0))
+        N.check(self._lib.srlx_notsac_bind(self._h, len(self.params), _ptrs(self.params)))
+
+    def act(self, states):
+        """states f32 [n][D] on the device, n 1..65536.  Returns head0 f32 [n][n_out] (logits or locs) and head1 (the clamped log-scales; None on the Gumbel
+        head) as device tensors; nothing synchronises."""
+        states, n, _, h0, h1 = self._outputs(states, False)
+        N.check(self._lib.srlx_notsac_walk(self._h, n, N.tptr(states), self.ls_lo, self.ls_hi, N.tptr(h0), N.tptr(h1), N.torch_stream_ptr()))
+        self._keep = states
+        return h0, h1

@@ -3,7 +3,8 @@ stays what the plugin, checkpoints and `load_state_dict` see -- and owns the han
 and the Adam state (moments here, the step count in the handle).  One `update` is the whole of torch_model.py:132-176 for one batch, in three launches;
 `update(..., gemm=True)` is the same step layer by layer on the float64 matrix cores (srlx_vppo_update_gemm), the path for wide layers and full
 batches.  `VppoUpdate(parameter, max_batch, gemm_only=True)` is a handle of srlx_vppo_create_gemm: batches up to GEMM_MAX_BATCH = 4096 on the gemm
-path alone, its weight and bias gradients one tiled launch on the matrix cores (k_mlp_gemm_wgrad)."""
+path alone, its weight and bias gradients one tiled launch on the matrix cores (k_mlp_gemm_wgrad).  `VppoAct` is the acting side: a handle that
+binds the same tensors and nothing else, and runs the network's forward in one launch."""
 import ctypes
 
 import torch
@@ -137,3 +138,42 @@ class VppoUpdate(R.RowUpdate):
         N.check(self._lib.srlx_vppo_act_normal(self._h, n_rows, rows, ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), N.tptr(counter), float(epsilon), float(noise_scale),
                                                int(bool(squashed)), self.ls_lo, self.ls_hi, N.tptr(low), N.tptr(high), N.tptr(actions), N.tptr(logp),
                                                N.tptr(env_actions), N.tptr(loc), N.tptr(log_scale), N.tptr(z), N.torch_stream_ptr()))
+
+
+class VppoAct(R.WalkAct):
+    """srlx_vppo_walk for an `algorithms.ppo_v.Parameter` (R.WalkAct)."""
+    ABI = "vppo"
+    UPDATE = VppoUpdate
+
+    @staticmethod
+    def passes_of(D, head, n_out, tw, vw, pw):
+        """The walk of srlx_vppo.hip's walk_plan, for R.walk_plan: the trunk, value_block.0 || policy_block.0 as one pass where both exist, the rest of either
+        branch; the values value_out_layer and the head read."""
+        passes = [(l, (w,)) for l, w in enumerate(tw)]
+        top = vv = vp = len(tw)
+        nval, dv, dp = top + 1, 0, 0
+        if vw and pw:
+            passes.append((top, (vw[0], pw[0])))
+            vv, vp, nval, dv, dp = nval, nval + 1, nval + 2, 1, 1
+        for w in vw[dv:]:
+            passes.append((vv, (w,)))
+            vv, nval = nval, nval + 1
+        for w in pw[dp:]:
+            passes.append((vp, (w,)))
+            vp, nval = nval, nval + 1
+        return passes, (vv, vp)
+
+    def _create(self, parameter):
+        tw, vw, pw = self.shape[3:]
+        self.ls_lo, self.ls_hi = log_scale_range(parameter)
+        N.check(self._lib.srlx_vppo_create(ctypes.byref(self._h), self.D, self.head, self.n_out, len(tw), _int_array(tw), len(vw), _int_array(vw), len(pw),
+                                           _int_array(pw), 1, self.device.index or 0))
+        N.check(self._lib.srlx_vppo_bind(self._h, _ptrs(self.params)))
+
+    def act(self, states):
+        """states f32 [n][D] on the device, n 1..65536.  Returns v f32 [n], head0 f32 [n][n_out] (logits or locs) and head1 (the clamped log-scales; None on
+        the categorical head) as device tensors; nothing synchronises."""
+        states, n, v, h0, h1 = self._outputs(states, True)
+        N.check(self._lib.srlx_vppo_walk(self._h, n, N.tptr(states), self.ls_lo, self.ls_hi, N.tptr(v), N.tptr(h0), N.tptr(h1), N.torch_stream_ptr()))
+        self._keep = states
+        return v, h0, h1

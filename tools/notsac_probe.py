@@ -16,7 +16,14 @@ update, and the `info` read that synchronises -- every round ending in a device 
 pendulum_rows16 and large_rows16 repeat two of them with the row kernels at 16 rows per workgroup (srlx_notsac_set_rows_per_workgroup) in place of the default.
 The default rule: "srlx" iff pendulum.srlx_ms_mean <= 1.10 * pendulum.torch_ms_mean of the same run.
 --trace-loop runs, at --shape, one train() of each arm and then TRACE_CALLS of each arm in turn: a kernel trace of it gives the launches and the kernel time
-per train() of each arm (the libsrlx kernels are named k_notsac_* and k_mlp_gemm_*; everything else is torch's)."""
+per train() of each arm (the libsrlx kernels are named k_notsac_* and k_mlp_gemm_*; everything else is torch's).
+
+The acting arm (tools/act_probe.py), the measurement that decides sac_not.Parameter.act_backend's default:
+
+    python tools/notsac_probe.py --act --out profiles/notsac_act_probe.json
+    rocprofv3 --kernel-trace --stats -d DIR -o notsac_act --output-format csv -- python tools/notsac_probe.py --act --trace-loop   # a run of its own
+
+Whole Worker._dist calls for one state at sac_not.Config()'s policy on Pendulum-v1 (pendulum) and at the envelope's corner (large: three 512-wide layers)."""
 import argparse
 import json
 import os
@@ -103,13 +110,23 @@ def measure(shape, rpw=0):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "notsac_probe.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/notsac_probe.json, with --act profiles/notsac_act_probe.json")
+    ap.add_argument("--act", action="store_true", help="the acting arm (DESIGN.md 7za): whole Worker._dist calls for one state, which decide Parameter.act_backend")
     ap.add_argument("--trace-loop", action="store_true")
     ap.add_argument("--shape", default="pendulum", choices=list(SHAPES), help="the shape of --trace-loop")
     args = ap.parse_args()
     import torch
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
+    if args.act:
+        import act_probe
+        import notsac_cases as C
+        from simple_distributed_rl_amd.algorithms import sac_not
+
+        shapes = {name: ((lambda s=SHAPES[name]: C.make_config(*s[1:], device="cuda")), dict(zip(("obs_dim", "head", "n_out", "policy", "q", "act_emb"), SHAPES[name][1:])))
+                  for name in ("pendulum", "large")}
+        return act_probe.run(args, sac_not, shapes, "pendulum", os.path.join(ROOT, "profiles", "notsac_act_probe.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "notsac_probe.json")
     if args.trace_loop:
         for a in ARMS:
             tr = _trainer(args.shape, a)

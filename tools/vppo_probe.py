@@ -18,7 +18,14 @@ The default rule: "srlx" iff default.srlx_ms_mean <= 1.10 * default.torch_ms_mea
 per train() of each arm (the libsrlx kernels are named k_vppo_* and k_mlp_gemm_*; everything else is torch's).
 --wide measures "srlx_gemm" against "torch" the same way (WIDE_CALLS calls per round) at B 512, 1024 and 4096 on ppo_v.Config()'s blocks and on 512-wide blocks,
 where "srlx_gemm" is a gemm-only handle whose gradient launch is k_mlp_gemm_wgrad; and, at the corner (B 256), an ordinary handle on the gemm path
-("srlx_gemm", gradient launch k_vppo_grad) against a gemm-only one ("srlx_gemm_only").  --trace-loop --shape corner-wgrad traces those two arms."""
+("srlx_gemm", gradient launch k_vppo_grad) against a gemm-only one ("srlx_gemm_only").  --trace-loop --shape corner-wgrad traces those two arms.
+
+The acting arm (tools/act_probe.py), the measurement that decides ppo_v.Parameter.act_backend's default:
+
+    python tools/vppo_probe.py --act --out profiles/vppo_act_probe.json
+    rocprofv3 --kernel-trace --stats -d DIR -o vppo_act --output-format csv -- python tools/vppo_probe.py --act --trace-loop   # a run of its own
+
+Whole Worker._dist calls for one state at ppo_v.Config()'s network on CartPole-v1 (default) and at the envelope's corner (512-wide blocks at full depth)."""
 import argparse
 import json
 import os
@@ -115,7 +122,8 @@ def measure(shape, arm_names=ARMS, calls=CALLS):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vppo_probe.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/vppo_probe.json, with --act profiles/vppo_act_probe.json")
+    ap.add_argument("--act", action="store_true", help="the acting arm (DESIGN.md 7za): whole Worker._dist calls for one state, which decide Parameter.act_backend")
     ap.add_argument("--trace-loop", action="store_true")
     ap.add_argument("--wide", action="store_true", help="the shapes of WIDE_ARMS instead of the four of the docstring")
     ap.add_argument("--shape", default="default", choices=list(SHAPES), help="the shape of --trace-loop")
@@ -123,6 +131,15 @@ def main():
     import torch
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
+    if args.act:
+        import act_probe
+        import vppo_cases as C
+        from simple_distributed_rl_amd.algorithms import ppo_v
+
+        shapes = {name: ((lambda s=SHAPES[name]: C.make_config(s[1], 0, s[2], *s[3:], device="cuda")), dict(zip(("obs_dim", "actions", "hidden", "value", "policy"), SHAPES[name][1:])))
+                  for name in ("default", "corner")}
+        return act_probe.run(args, ppo_v, shapes, "default", os.path.join(ROOT, "profiles", "vppo_act_probe.json"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "vppo_probe.json")
     if args.trace_loop:
         for a in WIDE_ARMS.get(args.shape, ARMS):
             tr = _trainer(args.shape, a)
